@@ -27,10 +27,21 @@ per-GPU launcher) puts every rank on device D with its own context slot; the gat
 shard, read out of the gathered buffer, against the oracle (`parity.ranks_checked`): the device generator is
 deterministic in (seed + rank, row), so rank 0 regenerates any rank's rows.
 
-Rank 0 prints the headline JSON line LAST (extras, when asked for, as {"extra": ...} lines before it); it holds the driver's contract plus `roofline` (HIP-event kernel time vs algorithmic
-bytes, and the VALU-issue view that actually binds this kernel -- DESIGN.md 4.3), `cpu_baseline` (the oracle
-timed on the host: the only place it is timed), `parity` (a sample strided over the whole batch, checked
-against the oracle) and, at N = 1, `secondary` (segmenter line), `exact_only_reads_per_s` and `end_to_end`.
+Rank 0 prints the headline JSON line LAST.  A plain run only sets up, warms up, times the --steps steps, writes
+--dump-outputs and prints that line: the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step),
+the config, the screening guard of the last step and each rank's own step time.  Everything else is measured or
+checked only under --full, after the timed region (extras as {"extra": ...} lines before the headline): on the line,
+`roofline` (HIP-event kernel time vs algorithmic bytes, and the VALU-issue view that actually binds this kernel --
+DESIGN.md 4.3), `cpu_baseline` (the oracle timed on the host: the only place it is timed), `parity` (a sample strided
+over the whole batch, checked against the oracle; at N > 1 a sample of every rank's shard out of the gathered buffer),
+at N > 1 the other scaling curve and `end_to_end`, and at N = 1 `secondary` (segmenter line), the other BASELINE.json
+configs, `exact_only_reads_per_s`, `end_to_end` and the bench_extras.py programmes.
+
+--dump-outputs DIR: what the last timed step computed, as a caller of the path receives it, written as DIR/<name>.npy
+in float64 (the records of every read; at N > 1 the gathered ones): MotifSeq dist / start / end / n / flags,
+segmenter nsegs / segs (boundaries past a read's count set to -1).  Beyond DUMP_BYTES in all, a fixed seeded sample
+of reads is written instead, its row numbers in DIR/rows.npy.  The device generator is seeded, so the same arguments
+give the same inputs on every run.
 """
 import argparse
 import ctypes as C
@@ -85,7 +96,15 @@ def parse(argv=None):
                     help="N = 1: skip the extra lines for the other BASELINE.json configs (c2_10k, c3, c5)")
     ap.add_argument("--force-comm", action="store_true",
                     help="N = 1: still create the RCCL communicator and gather every step (exercises the N > 1 path)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: roofline, CPU "
+                         "baseline, oracle parity, the other scaling curve, the extras (implied by --only-other-paths "
+                         "and --sweep-reads)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    a = ap.parse_args(argv)
+    a.full = a.full or a.only_other_paths or a.sweep_reads
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -231,6 +250,52 @@ def timed(w, comm, steps, warmup):
     if comm is not None:
         elapsed = float(comm.allgather_host(np.array([elapsed], dtype=np.float64)).max())
     return elapsed, prof
+
+
+# ----------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ----------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64_000_000        # at most this much in all (64 MB)
+DUMP_SEED = 20261016           # the fixed sample of reads when the whole output does not fit
+
+
+def step_outputs(w, shard_sizes):
+    """Rank 0, after the timed steps: what the last step computed, per read, as a caller of the path receives it --
+    the records of every rank out of the gathered buffer when there is an exchange, else this rank's."""
+    from squigglekit_amd._lib import HIT_DTYPE, check, ptr
+    if w.comm is not None:
+        blocks = w.gathered()
+        rec = np.concatenate([blocks[r][:int(n) * w.rec_bytes] for r, n in enumerate(shard_sizes)])
+    else:
+        rec = np.empty(w.R * w.rec_bytes, dtype=np.uint8)
+        if w.R:
+            check(w.L.sk_dev_download(ptr(rec), w.d_out, rec.nbytes))
+    if w.kind == "motifseq":
+        hits = rec.view(HIT_DTYPE)
+        return {name: hits[name] for name in HIT_DTYPE.names}
+    nsegs = rec.view(np.int32)
+    segs = np.empty((w.R, MAX_SEGS, 2), dtype=np.int32)
+    if w.R:
+        check(w.L.sk_dev_download(ptr(segs), w.d_segs, segs.nbytes))
+    # only the first nsegs boundaries of a read are results; what lies past them is not defined
+    segs[np.arange(MAX_SEGS)[None, :] >= np.minimum(nsegs[:w.R], MAX_SEGS)[:, None]] = -1
+    return {"nsegs": nsegs, "segs": segs}
+
+
+def write_outputs(dirpath, outs, limit=DUMP_BYTES):
+    """Each array of `outs` (first axis = reads) as dirpath/<name>.npy in float64.  When they would take more than
+    `limit` bytes, the same fixed seeded sample of reads of every array, and its row numbers as rows.npy."""
+    os.makedirs(dirpath, exist_ok=True)
+    rows = min(len(v) for v in outs.values())
+    per_row = sum(8 * int(np.prod(v.shape[1:], dtype=np.int64)) for v in outs.values())
+    if rows * per_row > limit:
+        keep = (limit - 4096) // (per_row + 8)                      # (+ rows.npy; 4 KB for the .npy headers)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+        outs = {k: v[idx] for k, v in outs.items()}
+        outs["rows"] = idx
+    for name, v in outs.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    return sorted(outs)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -771,9 +836,12 @@ def rank_body(a, comm, rank, world, shape):
     elapsed, prof, per_rank_ms = run(a.scaling, a.steps, a.warmup)
     shard_sizes = sharding.shard_sizes(a.reads, world) if a.scaling == "strong" else [a.reads] * world
     ranks_seen = use_comm.ranks_seen() if use_comm is not None else 1
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, step_outputs(w, shard_sizes))
 
+    # everything below the headline's timed steps is --full's
     other = None
-    if world > 1 and a.workload == "motifseq":
+    if a.full and world > 1 and a.workload == "motifseq":
         # the other curve on the data already resident (weak: C4 on every GPU; strong: C4 as BASELINE.json words it)
         oscale = "weak" if a.scaling == "strong" else "strong"
         el_o, _, pr_o = run(oscale, a.steps, 1)
@@ -784,7 +852,7 @@ def rank_body(a, comm, rank, world, shape):
     if a.scaling == "strong":
         w.R, w.pad = strong_R, strong_pad
     e2e_multi, h2d = None, None
-    if world > 1 and a.workload == "motifseq" and not a.no_extras:
+    if a.full and world > 1 and a.workload == "motifseq" and not a.no_extras:
         e2e_multi = e2e_all_ranks(a, w, use_comm)               # (every rank takes part)
         h2d = [float(v) for v in use_comm.allgather_host(np.array([e2e_multi[2]], dtype=np.float64))]
     if rank != 0:
@@ -794,27 +862,31 @@ def rank_body(a, comm, rank, world, shape):
     total_reads = a.reads * world if a.scaling == "weak" else a.reads
     ms_per_step = elapsed / a.steps * 1e3
     value = total_reads * a.steps / elapsed
-    want_cpu = world == 1 and a.cpu_seconds > 0          # the CPU baseline is timed at N = 1 only
-    parity, cpu, mean_n = parity_and_cpu(a, w, want_cpu)
-    if use_comm is not None:
-        # what did the gather gather?  a sample of every rank's shard out of the gathered buffer, against the oracle
-        gv = verify_gather(a, w, shard_sizes)
-        parity.update(gv)
-        for key in ("dist_bit_identical", "start_end_exact", "segments_bit_exact"):
-            if key in parity:
-                parity[key] = bool(parity[key] and gv["every_rank_ok"])
-    parity["oracle_pinned"] = ORACLE_PINNED[a.workload]
-    parity["oracle_pinned_note"] = ("filter / medmad / zscale are pinned by reference-made goldens; the DTW core (D1-D3) restates "
-                                    "mlpy 3.5.0, absent here: *_bit_identical means identical to oracle/sk_oracle.c "
-                                    "(tools/pin_mlpy.py pins it where mlpy imports)") if a.workload == "motifseq" else \
-        "pinned by outputs of the reference itself (tools/gen_golden.py, tests/golden/)"
+    parity, cpu, mean_n, roofline = None, None, None, None
+    if a.full:
+        want_cpu = world == 1 and a.cpu_seconds > 0      # the CPU baseline is timed at N = 1 only
+        parity, cpu, mean_n = parity_and_cpu(a, w, want_cpu)
+        if use_comm is not None:
+            # what did the gather gather?  a sample of every rank's shard out of the gathered buffer, against the oracle
+            gv = verify_gather(a, w, shard_sizes)
+            parity.update(gv)
+            for key in ("dist_bit_identical", "start_end_exact", "segments_bit_exact"):
+                if key in parity:
+                    parity[key] = bool(parity[key] and gv["every_rank_ok"])
+        parity["oracle_pinned"] = ORACLE_PINNED[a.workload]
+        parity["oracle_pinned_note"] = ("filter / medmad / zscale are pinned by reference-made goldens; the DTW core (D1-D3) restates "
+                                        "mlpy 3.5.0, absent here: *_bit_identical means identical to oracle/sk_oracle.c "
+                                        "(tools/pin_mlpy.py pins it where mlpy imports)") if a.workload == "motifseq" else \
+            "pinned by outputs of the reference itself (tools/gen_golden.py, tests/golden/)"
     if a.workload == "motifseq":
-        roofline = headline_roofline_labels(motifseq_roofline(a, w, prof, a.steps, mean_n))
+        if a.full:
+            roofline = headline_roofline_labels(motifseq_roofline(a, w, prof, a.steps, mean_n))
         name = "reads/sec MotifSeq DTW (4k-sample read x 200-sample motif)"
         wl = workload_name("motifseq", a.reads, a.samples, a.motif, a.scaling, a.scale)
     else:
-        roofline = segmenter_roofline(w, *seg_kernel_prof(w, prof, a.steps), step_ms=ms_per_step) if use_comm is None \
-            else segmenter_roofline(w, prof, a.steps)
+        if a.full:
+            roofline = segmenter_roofline(w, *seg_kernel_prof(w, prof, a.steps), step_ms=ms_per_step) \
+                if use_comm is None else segmenter_roofline(w, prof, a.steps)
         name = "reads/sec segmenter (4k-sample read)"
         wl = workload_name("segmenter", a.reads, a.samples, None, a.scaling)
     line = {"metric": name, "value": value, "unit": "reads/s", "n_gpus": world, "steps": a.steps,
@@ -835,8 +907,9 @@ def rank_body(a, comm, rank, world, shape):
                        "gather_backend": use_comm.backend if use_comm is not None else None,
                        "ranks_seen": ranks_seen,
                        "oversubscribed": ("every rank on device %d (dry run of the N > 1 path)" % a.ranks_on_device)
-                       if a.ranks_on_device is not None else None},
-            "roofline": roofline, "cpu_baseline": cpu, "parity": parity}
+                       if a.ranks_on_device is not None else None}}
+    if a.full:
+        line.update(roofline=roofline, cpu_baseline=cpu, parity=parity)
     line["ranks_seen"] = ranks_seen
     line["gather_backend"] = use_comm.backend if use_comm is not None else None
     # a silent fallback must not produce a clean-looking scaling line: fewer ranks than asked for, or the gather done by
@@ -869,9 +942,9 @@ def rank_body(a, comm, rank, world, shape):
     # headline is printed last and stays a few KB, so that a tail of stdout always holds it whole (round 4's record lost
     # its `secondary` and `parity` blocks to a line of 14 KB).  --full-json PATH writes headline + extras as one object.
     extras = {}
-    if world == 1 and a.only_other_paths:
+    if world == 1 and a.full and a.only_other_paths:
         extras["other_paths"] = bench_extras.other_paths_block(a, L, w)
-    elif world == 1 and not a.no_extras:
+    elif world == 1 and a.full and not a.no_extras:
         if a.workload == "motifseq" and not a.no_baseline_configs and a.reads == 1_000_000 and a.samples == 4000:
             extras.update(baseline_configs_block(a, L))               # c2_10k, c3, c5: lines of their own
         extras.update(extras_single_gpu(a, L, w))
@@ -880,7 +953,7 @@ def rank_body(a, comm, rank, world, shape):
             extras["other_paths"] = bench_extras.other_paths_block(a, L, w)
             extras["cli"] = bench_extras.cli_block(a, L, w)
             extras["sensitivity"] = bench_extras.sensitivity_block(a, L, w)
-    elif world == 1 and a.sweep_reads:
+    elif world == 1 and a.full and a.sweep_reads:
         extras["sweep"] = bench_extras.sweep_block(a, L, w)
     sec = extras.get("secondary")
     if sec:
@@ -900,7 +973,8 @@ def rank_body(a, comm, rank, world, shape):
     if sw.get("predicted_strong_scaling"):
         line["predicted_strong_scaling"] = dict(sw["predicted_strong_scaling"],
                                                 fixed_ms_per_call=sw["motifseq"]["fit"]["fixed_ms_per_call"])
-    line["extras"] = sorted(extras)
+    if a.full:
+        line["extras"] = sorted(extras)
     w.free()
     return line, extras
 

@@ -66,7 +66,7 @@ def test_bench_gather_path_bare_python(gpu, scaling, backend):
     """`python bench.py` run plainly (no launcher), with the per-step gather forced on at one rank: over RCCL, and by
     host concatenation (what a node without a usable librccl gets; SK_COMM=host)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-comm", "--reads", "20000", "--steps", "2",
-           "--warmup", "1", "--cpu-seconds", "2", "--no-extras", "--scaling", scaling]
+           "--warmup", "1", "--cpu-seconds", "2", "--no-extras", "--full", "--scaling", scaling]
     env = dict(os.environ, SK_COMM=backend)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -106,7 +106,7 @@ def test_bench_world_gt1_oversubscribed_threads(gpu, world, scaling, reads):
     weak run's strong re-slice, the every-rank end-to-end leg -- and rank 0 checks a sample of EVERY rank's shard
     out of the gathered buffer against the oracle."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--ranks-on-device", "0", "--reads",
-           str(reads), "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--scaling", scaling]
+           str(reads), "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--full", "--scaling", scaling]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -130,7 +130,7 @@ def test_bench_world2_oversubscribed_process_per_rank(gpu):
     pytest.importorskip("torch")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29633", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--reads", "20000",
-           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"]
+           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--full"]
     env = dict(os.environ, SK_OVERSUBSCRIBE="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -210,7 +210,7 @@ def test_bench_under_torch_distributed_run_one_rank(gpu):
     pytest.importorskip("torch")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--reads", "20000",
-           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--no-extras", "--force-comm"]
+           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--no-extras", "--force-comm", "--full"]
     env = dict(os.environ, SK_FORCE_PROCESS_SHAPE="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]

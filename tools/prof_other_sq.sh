@@ -6,7 +6,7 @@ set -u
 TAG=${1:-r06}
 R=$(pwd); OUT=$R/gpurun_out/prof_$TAG; mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp SK_TUNING=1
-CMD="python $R/bench.py --only-other-paths --steps 1 --warmup 0 --cpu-seconds 0"
+CMD="python $R/bench.py --full --only-other-paths --steps 1 --warmup 0 --cpu-seconds 0"
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
 SQ2="SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM GRBM_GUI_ACTIVE"
 i=1
