@@ -144,8 +144,8 @@ int sk_segment_batch_i16_pa(const int16_t *sig, int64_t stride, const int32_t *l
  * instead of 8 -- and certified against numpy's rounding; reads that cannot be certified are redone from their float64
  * values in numpy's order.  sk_pa_calib turns the records' {digitisation, offset, range} into the {offset, raw_unit}
  * pairs of the device-resident form (range cut to two decimals first, segmenter.py:385); sk_last_pa_retries: reads of
- * the last such call that took the redo (-1: the call expanded every row to float64 -- rows whose stride is not a
- * multiple of 8). */
+ * the last such call, all its sub-batches, that took the redo (-1: the call expanded every row to float64 -- rows whose
+ * stride is not a multiple of 8 -- or a MotifSeq / segmenter call of another route came after it). */
 int sk_pa_calib(const double *calib, int32_t nreads, double *cal2);
 int sk_segment_dev_i16_pa(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
                           const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs);
@@ -406,7 +406,8 @@ int sk_last_dtw_audit_mismatches(void);
 int sk_last_dtw_window_steps(uint64_t *out /* [2] */);
 /* Reads of the most recent float64 call (sk_segment_*_f64, sk_motifseq_*_f64 with medmad) whose comparisons /
  * selection the streaming statistics kernel could not certify and that were redone in numpy's order (diagnostic);
- * -1 when the call did not use the streaming kernel (reads longer than 4 096 samples, zscale). */
+ * -1 when the call did not use the streaming kernel (reads longer than 4 096 samples, zscale), or when a MotifSeq /
+ * segmenter call of another route came after it. */
 int sk_last_f64_retries(void);
 /* Shader clock (GHz) the screening pass of the most recent DTW call ran at: its first wavefront counts shader cycles
  * (s_memtime) against the constant 100 MHz reference (s_memrealtime) over its whole sweep.  0 when the call did not

@@ -260,8 +260,9 @@ def segment_batch_pa(sig, lens, calib, params=None, max_segs=64, devices=None):
 
 
 def last_pa_retries():
-    """Reads of the most recent segment_batch_pa call on this thread's device (its last sub-batch) that took the
-    numpy-order redo; -1 when the call expanded its rows to float64 instead of staying in the raw domain."""
+    """Reads of the most recent segment_batch_pa call on this thread's device (all its sub-batches) that took the
+    numpy-order redo; -1 when the call expanded its rows to float64 instead of staying in the raw domain, or when a
+    MotifSeq / segmenter call of another route came after it."""
     return int(_lib.load().sk_last_pa_retries())
 
 

@@ -125,12 +125,97 @@ SubBatches sub_batches(int32_t nreads, int64_t stride)
     return sb;
 }
 
-int second_stream(sk_ctx *c)
+// The sub-batch loop: copies the host rows of each sub-batch of B to d_rows (and, when len is given, their lengths to
+// c->len), then runs step(r0, nr, d_sig, d_len) -- the sub-batch's kernels on the main stream.
+template <class Step>
+int ingest_rows(sk_ctx *c, const SubBatches &B, int16_t *d_rows, const int16_t *sig, int64_t stride, const int32_t *len,
+                int32_t nreads, Step step)
 {
-    if (!c->stream2) {
-        SK_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        for (int i = 0; i < 9; i++) SK_HIP(hipEventCreateWithFlags(&c->ev_chunk[i], hipEventDisableTiming));
+    int rc;
+    if (B.n > 1 && (rc = sk_second_stream(c))) return rc;
+    const hipStream_t cs = B.n > 1 ? c->stream2 : c->stream;
+    for (int32_t bi = 0; bi < B.n; bi++) {
+        const int32_t r0 = bi * B.per;
+        const int32_t nr = (nreads - r0 < B.per) ? nreads - r0 : B.per;
+        if (nr <= 0) break;
+        int16_t *d_sig = d_rows + (size_t)r0 * (size_t)stride;
+        int32_t *d_len = (int32_t *)c->len.p + r0;
+        SK_HIP(hipMemcpyAsync(d_sig, sig + (size_t)r0 * (size_t)stride, (size_t)nr * (size_t)stride * sizeof(int16_t),
+                              hipMemcpyHostToDevice, cs));
+        if (len) SK_HIP(hipMemcpyAsync(d_len, len + r0, (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, cs));
+        if (B.n > 1) {                                      // the kernels of this sub-batch wait for its copy only
+            SK_HIP(hipEventRecord(c->ev_chunk[bi & 7], cs));
+            SK_HIP(hipStreamWaitEvent(c->stream, c->ev_chunk[bi & 7], 0));
+        }
+        if ((rc = step(r0, nr, d_sig, d_len))) return rc;
     }
+    return SK_OK;
+}
+
+// The redo record (sk_ctx::redo) of a MotifSeq / segmenter call.  redo_forget drops the last call's (the int16
+// MotifSeq calls write none); redo_begin does so and makes room for `lists` lists of `nreads` reads in all (one list
+// per sub-batch); redo_list hands the next list, of nr reads, to the statistics route that fills it; redo_count sums
+// the counters of the call if `route` wrote them, else -1.
+void redo_forget(sk_ctx *c)
+{
+    c->redo_route = SK_REDO_NONE;
+    c->redo_off.clear();
+    c->redo_used = 0;
+}
+
+int redo_begin(sk_ctx *c, int32_t nreads, int32_t lists)
+{
+    redo_forget(c);
+    return sk_reserve(c, &c->redo, ((size_t)nreads + 16 * (size_t)lists) * sizeof(int32_t));
+}
+
+int redo_list(sk_ctx *c, int route, int32_t nr, int32_t **list)
+{
+    const size_t end = c->redo_used + (size_t)nr + 16;
+    if (end * sizeof(int32_t) > c->redo.cap) return sk_fail(SK_ERR_INVALID, "internal: redo list past its reservation");
+    *list = (int32_t *)c->redo.p + c->redo_used;
+    c->redo_used = end;
+    c->redo_route = route;
+    return SK_OK;
+}
+
+int redo_count(sk_ctx *c, int route)
+{
+    if (c->redo_route != route) return -1;
+    SK_HIP(hipStreamSynchronize(c->stream));
+    int total = 0;
+    for (size_t o : c->redo_off) {
+        int32_t v = 0;
+        SK_HIP(hipMemcpy(&v, (const int32_t *)c->redo.p + o, sizeof v, hipMemcpyDeviceToHost));
+        total += v;
+    }
+    return total;
+}
+
+// The checks every segmenter entry point makes after those of its input: parameters, max_segs, and -- when there are
+// reads -- its outputs (null_out: one of them is NULL; `what` names them).  SK_NOTHING: no reads, nothing to do.
+enum { SK_NOTHING = 1 };
+int check_seg(const sk_seg_params *p, int32_t max_segs, int32_t nreads, bool null_out, const char *what)
+{
+    int rc = check_seg_params(p);
+    if (rc) return rc;
+    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
+    if (nreads == 0) return SK_NOTHING;
+    if (null_out) return sk_fail(SK_ERR_INVALID, "NULL %s", what);
+    return SK_OK;
+}
+
+// The tail of the segmenter batch entry points: segments (c->out) and counts (c->out2) back to the caller, then the
+// check that no read has more than max_segs.
+int read_segs(sk_ctx *c, int32_t nreads, int32_t max_segs, int32_t *segs, int32_t *nsegs)
+{
+    SK_HIP(hipMemcpyAsync(segs, c->out.p, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t), hipMemcpyDeviceToHost,
+                          c->stream));
+    SK_HIP(hipMemcpyAsync(nsegs, c->out2.p, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    for (int32_t r = 0; r < nreads; r++)
+        if (nsegs[r] > max_segs)
+            return sk_fail(SK_ERR_OVERFLOW, "read %d has %d segments, max_segs is %d", r, nsegs[r], max_segs);
     return SK_OK;
 }
 
@@ -145,9 +230,8 @@ extern "C" {
 // ------------------------------------------------------------------ pinned host memory for callers
 void *sk_host_alloc(size_t bytes)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return nullptr;
-    sk_ctx_guard c_lock(c);
+    sk_entry entry;
+    if (!entry.c) return nullptr;
     void *p = nullptr;
     hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -184,9 +268,8 @@ int sk_motifseq_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_l
                         const double *motif, int32_t nmotif, int32_t scale_mode,
                         int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
+    redo_forget(c);
     return motifseq_dev(c, d_sig, stride, d_len, nreads, motif, nmotif, scale_mode, scale_low, scale_hi, d_out, 0);
 }
 
@@ -244,9 +327,7 @@ int sk_motifseq_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len
                           const double *motif, int32_t nmotif, int32_t scale_mode,
                           int32_t scale_low, int32_t scale_hi, sk_hit *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
     if (rc) return rc;
     if ((rc = check_len_host(len, nreads, stride))) return rc;
@@ -256,26 +337,13 @@ int sk_motifseq_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len
     if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
     if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->out, (size_t)nreads * sizeof(sk_hit)))) return rc;
-    const SubBatches B = sub_batches(nreads, stride);
-    if (B.n > 1 && (rc = second_stream(c))) return rc;
-    for (int32_t bi = 0; bi < B.n; bi++) {
-        const int32_t r0 = bi * B.per;
-        const int32_t nr = (nreads - r0 < B.per) ? nreads - r0 : B.per;
-        if (nr <= 0) break;
-        int16_t *d_sig = (int16_t *)c->sig.p + (size_t)r0 * (size_t)stride;
-        int32_t *d_len = (int32_t *)c->len.p + r0;
-        hipStream_t cs = (B.n > 1) ? c->stream2 : c->stream;
-        SK_HIP(hipMemcpyAsync(d_sig, sig + (size_t)r0 * (size_t)stride, (size_t)nr * (size_t)stride * sizeof(int16_t),
-                              hipMemcpyHostToDevice, cs));
-        SK_HIP(hipMemcpyAsync(d_len, len + r0, (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, cs));
-        if (B.n > 1) {                                      // the kernels of this sub-batch wait for its copy only
-            SK_HIP(hipEventRecord(c->ev_chunk[bi & 7], cs));
-            SK_HIP(hipStreamWaitEvent(c->stream, c->ev_chunk[bi & 7], 0));
-        }
-        rc = motifseq_dev(c, d_sig, stride, d_len, nr, motif, nmotif, scale_mode, scale_low, scale_hi,
-                          (sk_hit *)c->out.p + r0, bi > 0);
-        if (rc) return rc;
-    }
+    redo_forget(c);
+    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return motifseq_dev(c, d_sig, stride, d_len, nr, motif, nmotif, scale_mode, scale_low, scale_hi,
+                                             (sk_hit *)c->out.p + r0, r0 > 0);
+                     });
+    if (rc) return rc;
     SK_HIP(hipMemcpyAsync(out, c->out.p, (size_t)nreads * sizeof(sk_hit), hipMemcpyDeviceToHost, c->stream));
     if ((rc = finish_dtw_host(c))) return rc;
     return SK_OK;
@@ -330,15 +398,14 @@ int sk_motifseq_multi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_
                               const double *motifs, const int32_t *motif_off, int32_t nmotifs,
                               int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(d_sig, stride, d_len, nreads);
     if (rc) return rc;
     if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
     if (nreads == 0) return SK_OK;
     if (!d_out) return sk_fail(SK_ERR_INVALID, "NULL out");
     clamp_limits(&scale_low, &scale_hi);
+    redo_forget(c);
     if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
     rc = motifseq_multi_dev(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs,
@@ -354,9 +421,7 @@ int sk_motifseq_multi_batch_i16(const int16_t *sig, int64_t stride, const int32_
                                 const double *motifs, const int32_t *motif_off, int32_t nmotifs,
                                 int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
     if (rc) return rc;
     if ((rc = check_len_host(len, nreads, stride))) return rc;
@@ -371,31 +436,16 @@ int sk_motifseq_multi_batch_i16(const int16_t *sig, int64_t stride, const int32_
     if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
     if ((rc = sk_reserve(c, &c->out, ob))) return rc;
-    // sub-batches as in sk_motifseq_batch_i16: the H2D copy of one runs on the second stream under the kernels of the
-    // previous one; filter + statistics once per sub-batch (as the prologue of the first motif's screening pass when
-    // that applies), then one DTW launch set per motif
-    const SubBatches B = sub_batches(nreads, stride);
-    if (B.n > 1 && (rc = second_stream(c))) return rc;
-    for (int32_t bi = 0; bi < B.n; bi++) {
-        const int32_t r0 = bi * B.per;
-        const int32_t nr = (nreads - r0 < B.per) ? nreads - r0 : B.per;
-        if (nr <= 0) break;
-        int16_t *d_sig = (int16_t *)c->sig.p + (size_t)r0 * (size_t)stride;
-        int16_t *d_comp = (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride;
-        int32_t *d_len = (int32_t *)c->len.p + r0;
-        sk_prep *d_prep = (sk_prep *)c->prep.p + r0;
-        hipStream_t cs = (B.n > 1) ? c->stream2 : c->stream;
-        SK_HIP(hipMemcpyAsync(d_sig, sig + (size_t)r0 * (size_t)stride, (size_t)nr * (size_t)stride * sizeof(int16_t),
-                              hipMemcpyHostToDevice, cs));
-        SK_HIP(hipMemcpyAsync(d_len, len + r0, (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, cs));
-        if (B.n > 1) {                                      // the kernels of this sub-batch wait for its copy only
-            SK_HIP(hipEventRecord(c->ev_chunk[bi & 7], cs));
-            SK_HIP(hipStreamWaitEvent(c->stream, c->ev_chunk[bi & 7], 0));
-        }
-        rc = motifseq_multi_dev(c, d_sig, stride, d_len, nr, d_comp, d_prep, motifs, motif_off, nmotifs, scale_mode,
-                                scale_low, scale_hi, (sk_hit *)c->out.p + r0, nreads, bi > 0);
-        if (rc) return rc;
-    }
+    // sub-batches as in sk_motifseq_batch_i16: filter + statistics once per sub-batch (as the prologue of the first
+    // motif's screening pass when that applies), then one DTW launch set per motif
+    redo_forget(c);
+    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return motifseq_multi_dev(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
+                                                   (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode,
+                                                   scale_low, scale_hi, (sk_hit *)c->out.p + r0, nreads, r0 > 0);
+                     });
+    if (rc) return rc;
     c->ev_valid = true;
     SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
     if ((rc = finish_dtw_host(c))) return rc;
@@ -447,13 +497,12 @@ static int motifseq_multi_dev_f64(sk_ctx *c, const double *d_sig, const int64_t 
     if ((rc = sk_reserve(c, &c->comp, (size_t)(total > 0 ? total : 1) * sizeof(double)))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    c->f64_stream = 0;
     if (scale_mode == SK_SCALE_MEDMAD && sk_f64_fast_applies(maxlen, 1.0)) {
-        c->f64_stream = 1;
         // streaming statistics (sk_f64stat.hip), then the general kernel over the (almost always empty) list of reads
         // whose median / MAD bin it could not resolve
-        if ((rc = sk_reserve(c, &c->retry, ((size_t)nreads + 16) * sizeof(int32_t)))) return rc;
-        int32_t *retry = (int32_t *)c->retry.p;
+        int32_t *retry;
+        if ((rc = redo_list(c, SK_REDO_F64, nreads, &retry))) return rc;
+        c->redo_off.push_back((size_t)(retry - (int32_t *)c->redo.p));
         rc = sk_launch_f64_stats(c, d_sig, d_off, nullptr, nreads, maxlen, (double)scale_low, (double)scale_hi, SK_PREP_MEDMAD,
                                  0.0, (sk_prep *)c->prep.p, nullptr, 0, nullptr, retry, (double *)c->comp.p);
         if (rc) return rc;
@@ -494,9 +543,7 @@ int sk_motifseq_batch_f64(const double *sig, const int64_t *off, int32_t nreads,
                           const double *motif, int32_t nmotif, int32_t scale_mode,
                           int32_t scale_low, int32_t scale_hi, sk_hit *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
     if (!motif || nmotif <= 0) return sk_fail(SK_ERR_INVALID, "empty motif");
     if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
@@ -507,6 +554,7 @@ int sk_motifseq_batch_f64(const double *sig, const int64_t *off, int32_t nreads,
     int rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen);
     if (rc) return rc;
     if ((rc = sk_reserve(c, &c->out, (size_t)nreads * sizeof(sk_hit)))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
     rc = motifseq_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, motif, nmotif,
                           scale_mode, scale_low, scale_hi, (sk_hit *)c->out.p);
     if (rc) return rc;
@@ -536,9 +584,7 @@ static int motifseq_multi_batch_ragged(const void *sig, bool centi, const int64_
                                        const double *motifs, const int32_t *motif_off, int32_t nmotifs,
                                        int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
     int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
     if (rc) return rc;
@@ -548,6 +594,7 @@ static int motifseq_multi_batch_ragged(const void *sig, bool centi, const int64_
     if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
     const size_t ob = (size_t)nreads * (size_t)nmotifs * sizeof(sk_hit);
     if ((rc = sk_reserve(c, &c->out, ob))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
     rc = motifseq_multi_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, motifs,
                                 motif_off, nmotifs, scale_mode, scale_low, scale_hi, (sk_hit *)c->out.p, nreads);
     if (rc) return rc;
@@ -560,15 +607,15 @@ int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nread
                         const double *motif, int32_t nmotif, int32_t scale_mode,
                         int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (nreads < 0 || total < 0 || max_len < 0 || max_len > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "bad sizes");
     if (!motif || nmotif <= 0) return sk_fail(SK_ERR_INVALID, "empty motif");
     if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
         return sk_fail(SK_ERR_INVALID, "unknown scale mode %d", scale_mode);
     if (nreads == 0) return SK_OK;
     if (!d_sig || !d_off || !d_out) return sk_fail(SK_ERR_INVALID, "NULL sig/off/out");
+    const int rc = redo_begin(c, nreads, 1);
+    if (rc) return rc;
     return motifseq_dev_f64(c, d_sig, d_off, nreads, total, max_len, motif, nmotif, scale_mode, scale_low, scale_hi,
                             d_out);
 }
@@ -577,9 +624,7 @@ int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nread
 int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const int64_t *off,
                              int32_t nreads, sk_hit *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (nreads < 0 || nx <= 0 || !x) return sk_fail(SK_ERR_INVALID, "bad query");
     if (nreads == 0) return SK_OK;
     if (!y || !off || !out) return sk_fail(SK_ERR_INVALID, "NULL y/off/out");
@@ -616,9 +661,7 @@ int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const
 int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
                        double *dist, int32_t *start, int32_t *end, double *cost_last_row)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!x || !y || nx <= 0 || ny <= 0) return sk_fail(SK_ERR_INVALID, "empty x or y");
     int rc;
     if ((rc = sk_reserve(c, &c->sig, (size_t)ny * sizeof(double)))) return rc;
@@ -649,9 +692,7 @@ int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
 int sk_normalise_i16(const int16_t *sig, int32_t len, int32_t scale_mode,
                      int32_t scale_low, int32_t scale_hi, double *out, int32_t *n_out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (len < 0 || (len && (!sig || !out))) return sk_fail(SK_ERR_INVALID, "bad arguments");
     if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
         return sk_fail(SK_ERR_INVALID, "unknown scale mode %d", scale_mode);
@@ -686,9 +727,7 @@ int sk_normalise_i16(const int16_t *sig, int32_t len, int32_t scale_mode,
 int sk_normalise_f64(const double *sig, int32_t len, int32_t scale_mode,
                      int32_t scale_low, int32_t scale_hi, double *out, int32_t *n_out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (len < 0 || (len && (!sig || !out))) return sk_fail(SK_ERR_INVALID, "bad arguments");
     if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
         return sk_fail(SK_ERR_INVALID, "unknown scale mode %d", scale_mode);
@@ -717,18 +756,13 @@ int sk_normalise_f64(const double *sig, int32_t len, int32_t scale_mode,
 }
 
 // ------------------------------------------------------------------ segmenter
-int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                       const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
+} // extern "C"
+
+// device-resident core of the int16 segmenter path (d_segs zeroed here)
+static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                           const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
-    int rc = check_i16(d_sig, stride, d_len, nreads);
-    if (rc) return rc;
-    if ((rc = check_seg_params(p))) return rc;
-    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
-    if (nreads == 0) return SK_OK;
-    if (!d_segs || !d_nsegs) return sk_fail(SK_ERR_INVALID, "NULL segs/nsegs");
+    int rc;
     int32_t lo = p->lim_low, hi = p->lim_hi;
     clamp_limits(&lo, &hi);
     const int64_t words = (stride + 63) / 64;
@@ -740,9 +774,10 @@ int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_le
         // integer thresholds; the numpy-order kernel redoes the (almost always empty) list of uncertified reads
         const size_t mb = (size_t)nreads * (size_t)sk_segment_fast_row16(stride) * 16;
         if ((rc = sk_reserve(c, &c->mask, mb))) return rc;
-        if ((rc = sk_reserve(c, &c->retry, ((size_t)nreads + 16) * sizeof(int32_t)))) return rc;
+        int32_t *redo;
+        if ((rc = redo_list(c, SK_REDO_I16, nreads, &redo))) return rc;
         rc = sk_launch_segment_fast(c, d_sig, stride, d_len, nreads, p, lo, hi, (sk_prep *)c->prep.p, c->mask.p,
-                                    (int32_t *)c->retry.p, d_segs, d_nsegs, max_segs);
+                                    redo, d_segs, d_nsegs, max_segs);
         if (rc) return rc;
         c->ev_valid = true;
         return SK_OK;
@@ -761,54 +796,6 @@ int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_le
     return SK_OK;
 }
 
-int sk_segment_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                         const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
-{
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
-    int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
-    if ((rc = check_len_host(len, nreads, stride))) return rc;
-    if ((rc = check_seg_params(p))) return rc;
-    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
-    if (nreads == 0) return SK_OK;
-    if (!segs || !nsegs) return sk_fail(SK_ERR_INVALID, "NULL segs/nsegs");
-    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
-    const size_t gb = (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t);
-    if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
-    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, gb))) return rc;
-    if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
-    const SubBatches B = sub_batches(nreads, stride);
-    if (B.n > 1 && (rc = second_stream(c))) return rc;
-    for (int32_t bi = 0; bi < B.n; bi++) {
-        const int32_t r0 = bi * B.per;
-        const int32_t nr = (nreads - r0 < B.per) ? nreads - r0 : B.per;
-        if (nr <= 0) break;
-        int16_t *d_sig = (int16_t *)c->sig.p + (size_t)r0 * (size_t)stride;
-        int32_t *d_len = (int32_t *)c->len.p + r0;
-        hipStream_t cs = (B.n > 1) ? c->stream2 : c->stream;
-        SK_HIP(hipMemcpyAsync(d_sig, sig + (size_t)r0 * (size_t)stride, (size_t)nr * (size_t)stride * sizeof(int16_t),
-                              hipMemcpyHostToDevice, cs));
-        SK_HIP(hipMemcpyAsync(d_len, len + r0, (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, cs));
-        if (B.n > 1) {
-            SK_HIP(hipEventRecord(c->ev_chunk[bi & 7], cs));
-            SK_HIP(hipStreamWaitEvent(c->stream, c->ev_chunk[bi & 7], 0));
-        }
-        rc = sk_segment_dev_i16(d_sig, stride, d_len, nr, p, (int32_t *)c->out.p + (size_t)r0 * 2 * (size_t)max_segs,
-                                (int32_t *)c->out2.p + r0, max_segs);
-        if (rc) return rc;
-    }
-    SK_HIP(hipMemcpyAsync(segs, c->out.p, gb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(nsegs, c->out2.p, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    for (int32_t r = 0; r < nreads; r++)
-        if (nsegs[r] > max_segs)
-            return sk_fail(SK_ERR_OVERFLOW, "read %d has %d segments, max_segs is %d", r, nsegs[r], max_segs);
-    return SK_OK;
-}
-
 // device-resident core of the float64 segmenter path (d_off zero based; d_segs zeroed here)
 static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
                            int64_t maxlen, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
@@ -817,9 +804,7 @@ static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off,
     int rc;
     const int64_t words = (maxlen + 63) / 64 > 0 ? (maxlen + 63) / 64 : 1;
     const size_t gb = (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t);
-    c->f64_stream = 0;
     if (sk_f64_fast_applies(maxlen, p->std_scale)) {
-        c->f64_stream = 1;
         // streaming statistics with certified comparisons (sk_f64stat.hip), the numpy-order kernel over the (almost
         // always empty) list of uncertified reads, then the run-hopping walk of the int16 path over the same masks
         const int row16 = sk_f64_row16(maxlen > 0 ? maxlen : 1);
@@ -828,9 +813,10 @@ static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off,
         if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
         if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
         if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-        if ((rc = sk_reserve(c, &c->retry, ((size_t)nreads + 16) * sizeof(int32_t)))) return rc;
         if ((rc = sk_reserve(c, &c->comp, (size_t)grid * (size_t)(srow > 0 ? srow : 8) * sizeof(double)))) return rc;
-        int32_t *retry = (int32_t *)c->retry.p;
+        int32_t *retry;
+        if ((rc = redo_list(c, SK_REDO_F64, nreads, &retry))) return rc;
+        c->redo_off.push_back((size_t)(retry - (int32_t *)c->redo.p));
         SK_HIP(hipMemsetAsync(d_segs, 0, gb, c->stream));
         SK_HIP(hipEventRecord(c->ev[0], c->stream));
         rc = sk_launch_f64_stats(c, d_sig, d_off, d_rlen, nreads, maxlen, (double)p->lim_low, (double)p->lim_hi, SK_PREP_SEGMENT,
@@ -863,30 +849,50 @@ static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off,
     return SK_OK;
 }
 
-static int segment_batch_ragged(const void *sig, bool centi, const int64_t *off, const int32_t *len, int32_t nreads,
-                                const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs);
-int sk_segment_batch_f64_len(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,
-                             const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
+// Device-resident core.  Since round 6 the values stay int16: the pA conversion is a monotone map of the sample, so
+// limits, median, std and the two thresholds are found in the raw domain (k_seg_stats<.., PA>, sk_segstat.hip: 2 bytes a
+// sample instead of 8; reads it cannot certify are redone from their float64 values in numpy's order).  Rows the
+// streaming kernel does not take (stride not a multiple of 8, unaligned): the float64 image of every row, then the
+// float64 segmenter path -- what every call did before round 6.
+static int segment_dev_i16_pa(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const double *d_cal2, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
 {
-    return segment_batch_ragged(sig, false, off, len, nreads, p, segs, nsegs, max_segs);
+    int rc;
+    if (sk_segment_pa_applies(d_sig, stride, p->std_scale)) {
+        const size_t mb = (size_t)nreads * (size_t)sk_segment_fast_row16(stride) * 16;
+        if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+        if ((rc = sk_reserve(c, &c->mask, mb))) return rc;
+        if ((rc = sk_reserve(c, &c->comp, (size_t)c->num_cu * (size_t)stride * sizeof(double)))) return rc;
+        int32_t *redo;
+        if ((rc = redo_list(c, SK_REDO_PA, nreads, &redo))) return rc;
+        SK_HIP(hipMemsetAsync(d_segs, 0, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t), c->stream));
+        rc = sk_launch_segment_fast(c, d_sig, stride, d_len, nreads, p, p->lim_low, p->lim_hi, (sk_prep *)c->prep.p, c->mask.p,
+                                    redo, d_segs, d_nsegs, max_segs, d_cal2, (double *)c->comp.p);
+        if (rc) return rc;
+        c->ev_valid = true;
+        return SK_OK;
+    }
+    // every read in a slot of `stride` doubles; the cut to len[r] is the float64 path's per-read length
+    const int64_t total = (int64_t)nreads * stride;
+    c->pa_off_host.resize((size_t)nreads + 1);
+    for (int32_t r = 0; r <= nreads; r++) c->pa_off_host[r] = (int64_t)r * stride;
+    if ((rc = sk_reserve(c, &c->sig, (size_t)(total > 0 ? total : 1) * sizeof(double)))) return rc;
+    if ((rc = sk_reserve(c, &c->off, c->pa_off_host.size() * sizeof(int64_t)))) return rc;
+    SK_HIP(hipMemcpyAsync(c->off.p, c->pa_off_host.data(), c->pa_off_host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));                 // (the vector may be resized by the next call)
+    rc = sk_launch_rows_to_pa(c, d_sig, stride, nreads, (const int64_t *)c->off.p, d_cal2, (double *)c->sig.p);
+    if (rc) return rc;
+    return segment_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, stride, p,
+                           d_segs, d_nsegs, max_segs, d_len);
 }
-int sk_segment_batch_centi_len(const int32_t *centi, const int64_t *off, const int32_t *len, int32_t nreads,
-                               const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
-{
-    return segment_batch_ragged(centi, true, off, len, nreads, p, segs, nsegs, max_segs);
-}
+
 static int segment_batch_ragged(const void *sig, bool centi, const int64_t *off, const int32_t *len, int32_t nreads,
                                 const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
-    int rc = check_seg_params(p);
-    if (rc) return rc;
-    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
-    if (nreads == 0) return SK_OK;
-    if (!segs || !nsegs) return sk_fail(SK_ERR_INVALID, "NULL segs/nsegs");
+    int rc = check_seg(p, max_segs, nreads, !segs || !nsegs, "segs/nsegs");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
     int64_t total, maxlen;
     if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
     const int32_t *d_rlen = nullptr;
@@ -904,25 +910,65 @@ static int segment_batch_ragged(const void *sig, bool centi, const int64_t *off,
         maxlen = 0;
         for (int32_t r = 0; r < nreads; r++) if (len[r] > maxlen) maxlen = len[r];
     }
-    const size_t gb = (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t);
-    if ((rc = sk_reserve(c, &c->out, gb))) return rc;
+    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
     rc = segment_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, p,
                          (int32_t *)c->out.p, (int32_t *)c->out2.p, max_segs, d_rlen);
     if (rc) return rc;
-    SK_HIP(hipMemcpyAsync(segs, c->out.p, gb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(nsegs, c->out2.p, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    for (int32_t r = 0; r < nreads; r++)
-        if (nsegs[r] > max_segs)
-            return sk_fail(SK_ERR_OVERFLOW, "read %d has %d segments, max_segs is %d", r, nsegs[r], max_segs);
-    return SK_OK;
+    return read_segs(c, nreads, max_segs, segs, nsegs);
 }
 
+extern "C" {
+
+int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                       const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
+{
+    SK_ENTER(c);
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (!rc) rc = check_seg(p, max_segs, nreads, !d_segs || !d_nsegs, "segs/nsegs");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    return segment_dev_i16(c, d_sig, stride, d_len, nreads, p, d_segs, d_nsegs, max_segs);
+}
+
+int sk_segment_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (!rc) rc = check_len_host(len, nreads, stride);
+    if (!rc) rc = check_seg(p, max_segs, nreads, !segs || !nsegs, "segs/nsegs");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
+    const SubBatches B = sub_batches(nreads, stride);
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = redo_begin(c, nreads, B.n))) return rc;
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return segment_dev_i16(c, d_sig, stride, d_len, nr, p, (int32_t *)c->out.p + (size_t)r0 * 2 * (size_t)max_segs,
+                                                (int32_t *)c->out2.p + r0, max_segs);
+                     });
+    if (rc) return rc;
+    return read_segs(c, nreads, max_segs, segs, nsegs);
+}
+
+int sk_segment_batch_f64_len(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,
+                             const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
+{
+    return segment_batch_ragged(sig, false, off, len, nreads, p, segs, nsegs, max_segs);
+}
+int sk_segment_batch_centi_len(const int32_t *centi, const int64_t *off, const int32_t *len, int32_t nreads,
+                               const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
+{
+    return segment_batch_ragged(centi, true, off, len, nreads, p, segs, nsegs, max_segs);
+}
 int sk_segment_batch_f64(const double *sig, const int64_t *off, int32_t nreads, const sk_seg_params *p,
                          int32_t *segs, int32_t *nsegs, int32_t max_segs)
 {
-    return sk_segment_batch_f64_len(sig, off, nullptr, nreads, p, segs, nsegs, max_segs);
+    return segment_batch_ragged(sig, false, off, nullptr, nreads, p, segs, nsegs, max_segs);
 }
 
 // Raw reads through the pA route: what segmenter.py does with fast5 / slow5 input unless --raw_signal is given
@@ -942,150 +988,72 @@ int sk_pa_calib(const double *calib, int32_t nreads, double *cal2)
     return SK_OK;
 }
 
-// Device-resident core.  Since round 6 the values stay int16: the pA conversion is a monotone map of the sample, so
-// limits, median, std and the two thresholds are found in the raw domain (k_seg_stats<.., PA>, sk_segstat.hip: 2 bytes a
-// sample instead of 8; reads it cannot certify are redone from their float64 values in numpy's order).  Rows the
-// streaming kernel does not take (stride not a multiple of 8, unaligned): the float64 image of every row, then the
-// float64 segmenter path -- what every call did before round 6.
-static int segment_dev_i16_pa(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                              const double *d_cal2, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
-{
-    int rc;
-    c->pa_raw = 0;
-    if (sk_segment_pa_applies(d_sig, stride, p->std_scale)) {
-        c->pa_raw = 1;
-        const size_t mb = (size_t)nreads * (size_t)sk_segment_fast_row16(stride) * 16;
-        if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-        if ((rc = sk_reserve(c, &c->mask, mb))) return rc;
-        if ((rc = sk_reserve(c, &c->retry, ((size_t)nreads + 16) * sizeof(int32_t)))) return rc;
-        if ((rc = sk_reserve(c, &c->comp, (size_t)c->num_cu * (size_t)stride * sizeof(double)))) return rc;
-        SK_HIP(hipMemsetAsync(d_segs, 0, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t), c->stream));
-        rc = sk_launch_segment_fast(c, d_sig, stride, d_len, nreads, p, p->lim_low, p->lim_hi, (sk_prep *)c->prep.p, c->mask.p,
-                                    (int32_t *)c->retry.p, d_segs, d_nsegs, max_segs, d_cal2, (double *)c->comp.p);
-        if (rc) return rc;
-        c->ev_valid = true;
-        return SK_OK;
-    }
-    // every read in a slot of `stride` doubles; the cut to len[r] is the float64 path's per-read length
-    const int64_t total = (int64_t)nreads * stride;
-    c->pa_off_host.resize((size_t)nreads + 1);
-    for (int32_t r = 0; r <= nreads; r++) c->pa_off_host[r] = (int64_t)r * stride;
-    if ((rc = sk_reserve(c, &c->sig, (size_t)(total > 0 ? total : 1) * sizeof(double)))) return rc;
-    if ((rc = sk_reserve(c, &c->off, c->pa_off_host.size() * sizeof(int64_t)))) return rc;
-    SK_HIP(hipMemcpyAsync(c->off.p, c->pa_off_host.data(), c->pa_off_host.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));                 // (the vector may be resized by the next call)
-    rc = sk_launch_rows_to_pa(c, d_sig, stride, nreads, (const int64_t *)c->off.p, d_cal2, (double *)c->sig.p);
-    if (rc) return rc;
-    return segment_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, stride, p,
-                           d_segs, d_nsegs, max_segs, d_len);
-}
-
-// Reads of the most recent sk_segment_*_i16_pa call (its last sub-batch) that the raw-domain kernel could not certify and
-// that were redone from their float64 values; -1 when that call expanded every read to float64 instead.
+// Reads of the most recent sk_segment_*_i16_pa call (all its sub-batches) that the raw-domain kernel could not certify
+// and that were redone from their float64 values; -1 when that call expanded every read to float64 instead, or when a
+// MotifSeq / segmenter call of another route came after it.
 int sk_last_pa_retries(void)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
-    if (!c->pa_raw) return -1;
-    SK_HIP(hipStreamSynchronize(c->stream));
-    int total = 0;
-    for (const int32_t *ptr : c->pa_retry_ptrs) {
-        int32_t v = 0;
-        SK_HIP(hipMemcpy(&v, ptr, sizeof v, hipMemcpyDeviceToHost));
-        total += v;
-    }
-    return total;
+    SK_ENTER(c);
+    return redo_count(c, SK_REDO_PA);
 }
 
 int sk_segment_dev_i16_pa(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
                           const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(d_sig, stride, d_len, nreads);
-    if (rc) return rc;
-    if ((rc = check_seg_params(p))) return rc;
-    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
-    if (nreads == 0) return SK_OK;
-    if (!d_cal2 || !d_segs || !d_nsegs) return sk_fail(SK_ERR_INVALID, "NULL cal2/segs/nsegs");
+    if (!rc) rc = check_seg(p, max_segs, nreads, !d_cal2 || !d_segs || !d_nsegs, "cal2/segs/nsegs");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
     return segment_dev_i16_pa(c, d_sig, stride, d_len, nreads, d_cal2, p, d_segs, d_nsegs, max_segs);
 }
 
 int sk_segment_batch_i16_pa(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *calib,
                             const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
-    if ((rc = check_len_host(len, nreads, stride))) return rc;
-    if ((rc = check_seg_params(p))) return rc;
-    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
-    if (nreads == 0) return SK_OK;
-    if (!calib || !segs || !nsegs) return sk_fail(SK_ERR_INVALID, "NULL calib/segs/nsegs");
+    if (!rc) rc = check_len_host(len, nreads, stride);
+    if (!rc) rc = check_seg(p, max_segs, nreads, !calib || !segs || !nsegs, "calib/segs/nsegs");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
     std::vector<double> cal((size_t)nreads * 2);
     if ((rc = sk_pa_calib(calib, nreads, cal.data()))) return rc;
-    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
-    const size_t gb = (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t);
-    if ((rc = sk_reserve(c, &c->misc, sb))) return rc;
+    if ((rc = sk_reserve(c, &c->misc, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
     if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->pacal, cal.size() * sizeof(double)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, gb))) return rc;
+    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
     SK_HIP(hipMemcpyAsync(c->pacal.p, cal.data(), cal.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     SK_HIP(hipMemcpyAsync(c->len.p, len, (size_t)nreads * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    // rows in sub-batches, the copy of one beside the kernels of the one before (as sk_segment_batch_i16)
-    const SubBatches B = sub_batches(nreads, stride);
-    if (B.n > 1 && (rc = second_stream(c))) return rc;
     SK_HIP(hipStreamSynchronize(c->stream));                 // cal goes out of scope; len / cal are there for every sub-batch
-    // (the float64 fallback keeps its lengths in c->len as well: it gets a copy of its own)
+    // rows in sub-batches as sk_segment_batch_i16 (the rows in c->misc: the float64 fallback puts its image in c->sig);
+    // the float64 fallback takes them in one piece and keeps its lengths in c->len as well: it gets a copy of its own
     const bool raw_domain = sk_segment_pa_applies(c->misc.p, stride, p->std_scale);
     if (!raw_domain) {
         if ((rc = sk_reserve(c, &c->rlen, (size_t)nreads * sizeof(int32_t)))) return rc;
         SK_HIP(hipMemcpyAsync(c->rlen.p, len, (size_t)nreads * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
-    for (int32_t bi = 0; bi < (raw_domain ? B.n : 1); bi++) {
-        const int32_t per = raw_domain ? B.per : nreads;
-        const int32_t r0 = bi * per;
-        const int32_t nr = (nreads - r0 < per) ? nreads - r0 : per;
-        if (nr <= 0) break;
-        int16_t *d_sig = (int16_t *)c->misc.p + (size_t)r0 * (size_t)stride;
-        hipStream_t cs = (raw_domain && B.n > 1) ? c->stream2 : c->stream;
-        SK_HIP(hipMemcpyAsync(d_sig, sig + (size_t)r0 * (size_t)stride, (size_t)nr * (size_t)stride * sizeof(int16_t),
-                              hipMemcpyHostToDevice, cs));
-        if (cs != c->stream) {
-            SK_HIP(hipEventRecord(c->ev_chunk[bi & 7], cs));
-            SK_HIP(hipStreamWaitEvent(c->stream, c->ev_chunk[bi & 7], 0));
-        }
-        rc = segment_dev_i16_pa(c, d_sig, stride, (const int32_t *)(raw_domain ? c->len.p : c->rlen.p) + r0, nr,
-                                (const double *)c->pacal.p + 2 * (size_t)r0, p,
-                                (int32_t *)c->out.p + (size_t)r0 * 2 * (size_t)max_segs, (int32_t *)c->out2.p + r0, max_segs);
-        if (rc) return rc;
-    }
-    SK_HIP(hipMemcpyAsync(segs, c->out.p, gb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(nsegs, c->out2.p, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    for (int32_t r = 0; r < nreads; r++)
-        if (nsegs[r] > max_segs)
-            return sk_fail(SK_ERR_OVERFLOW, "read %d has %d segments, max_segs is %d", r, nsegs[r], max_segs);
-    return SK_OK;
+    const SubBatches B = raw_domain ? sub_batches(nreads, stride) : SubBatches{nreads, 1};
+    if ((rc = redo_begin(c, nreads, B.n))) return rc;
+    rc = ingest_rows(c, B, (int16_t *)c->misc.p, sig, stride, nullptr, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return segment_dev_i16_pa(c, d_sig, stride, raw_domain ? d_len : (const int32_t *)c->rlen.p + r0,
+                                                   nr, (const double *)c->pacal.p + 2 * (size_t)r0, p,
+                                                   (int32_t *)c->out.p + (size_t)r0 * 2 * (size_t)max_segs,
+                                                   (int32_t *)c->out2.p + r0, max_segs);
+                     });
+    if (rc) return rc;
+    return read_segs(c, nreads, max_segs, segs, nsegs);
 }
 
 int sk_segment_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t max_len,
                        const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (nreads < 0 || total < 0 || max_len < 0 || max_len > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "bad sizes");
-    int rc = check_seg_params(p);
-    if (rc) return rc;
-    if (max_segs <= 0) return sk_fail(SK_ERR_INVALID, "max_segs must be positive");
-    if (nreads == 0) return SK_OK;
-    if (!d_sig || !d_off || !d_segs || !d_nsegs) return sk_fail(SK_ERR_INVALID, "NULL sig/off/segs/nsegs");
+    int rc = check_seg(p, max_segs, nreads, !d_sig || !d_off || !d_segs || !d_nsegs, "sig/off/segs/nsegs");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
     return segment_dev_f64(c, d_sig, d_off, nreads, total, max_len, p, d_segs, d_nsegs, max_segs);
 }
 
@@ -1186,9 +1154,7 @@ static int check_drna(const sk_drna_params *p, int32_t max_segs)
 int sk_drna_roll_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                          const sk_roll_params *p, int32_t *d_xy, int32_t *d_found)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(d_sig, stride, d_len, nreads);
     if (rc) return rc;
     if ((rc = check_roll(p))) return rc;
@@ -1200,9 +1166,7 @@ int sk_drna_roll_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_
 int sk_drna_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                             const sk_drna_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(d_sig, stride, d_len, nreads);
     if (rc) return rc;
     if ((rc = check_drna(p, max_segs))) return rc;
@@ -1214,9 +1178,7 @@ int sk_drna_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t 
 int sk_drna_roll_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
                            const sk_roll_params *p, int32_t *xy, int32_t *found)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
     if (rc) return rc;
     if ((rc = check_len_host(len, nreads, stride))) return rc;
@@ -1241,9 +1203,7 @@ int sk_drna_roll_batch_i16(const int16_t *sig, int64_t stride, const int32_t *le
 int sk_drna_segment_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
                               const sk_drna_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
     if (rc) return rc;
     if ((rc = check_len_host(len, nreads, stride))) return rc;
@@ -1260,22 +1220,14 @@ int sk_drna_segment_batch_i16(const int16_t *sig, int64_t stride, const int32_t 
     SK_HIP(hipMemcpyAsync(c->len.p, len, (size_t)nreads * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     if ((rc = drna_segment_dev(c, (const int16_t *)c->sig.p, stride, (const int32_t *)c->len.p, nreads, p,
                                (int32_t *)c->out.p, (int32_t *)c->out2.p, max_segs))) return rc;
-    SK_HIP(hipMemcpyAsync(segs, c->out.p, gb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(nsegs, c->out2.p, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    for (int32_t r = 0; r < nreads; r++)
-        if (nsegs[r] > max_segs)
-            return sk_fail(SK_ERR_OVERFLOW, "read %d has %d segments, max_segs is %d", r, nsegs[r], max_segs);
-    return SK_OK;
+    return read_segs(c, nreads, max_segs, segs, nsegs);
 }
 
 // ------------------------------------------------------------------ bench input
 int sk_synth_squiggles_dev(int16_t *d_sig, int64_t stride, int32_t nreads, int32_t nsamples,
                            uint64_t seed, const double *motif, int32_t nmotif)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!d_sig || stride < nsamples || nreads < 0 || nsamples < 0)
         return sk_fail(SK_ERR_INVALID, "bad arguments");
     const int16_t *d_m = nullptr;
@@ -1300,9 +1252,7 @@ int sk_synth_squiggles_dev(int16_t *d_sig, int64_t stride, int32_t nreads, int32
 int sk_synth_variant_dev(int16_t *d_sig, int64_t stride, int32_t nreads, int32_t nsamples, uint64_t seed,
                          const double *motif, int32_t nmotif, const sk_synth_opts *o)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!d_sig || !o || stride < nsamples || nreads < 0 || nsamples < 0 || o->row0 < 0)
         return sk_fail(SK_ERR_INVALID, "bad arguments");
     int rc;
@@ -1338,9 +1288,7 @@ int sk_synth_variant_dev(int16_t *d_sig, int64_t stride, int32_t nreads, int32_t
 int sk_synth_pa_dev(const int16_t *d_raw, int64_t stride, int32_t nreads, int32_t nsamples,
                     double offset, double range, double digitisation, double *d_out, int64_t *d_off)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!d_raw || !d_out || !d_off || stride < nsamples || nreads < 0 || nsamples < 0 || !(digitisation > 0))
         return sk_fail(SK_ERR_INVALID, "bad arguments");
     int rc = sk_launch_raw_to_pa(c, d_raw, stride, nreads, nsamples, offset, range / digitisation, d_out, d_off);
@@ -1350,17 +1298,12 @@ int sk_synth_pa_dev(const int16_t *d_raw, int64_t stride, int32_t nreads, int32_
 }
 
 // Reads of the most recent float64 call (segmenter or MotifSeq medmad) that the streaming statistics kernel handed
-// to the numpy-order kernel (diagnostic); -1 when that call did not take the streaming kernel.
+// to the numpy-order kernel (diagnostic); -1 when that call did not take the streaming kernel, or when a MotifSeq /
+// segmenter call of another route came after it.
 int sk_last_f64_retries(void)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
-    if (!c->f64_stream || !c->retry.p) return -1;
-    int32_t n = 0;
-    SK_HIP(hipStreamSynchronize(c->stream));
-    SK_HIP(hipMemcpy(&n, c->retry.p, sizeof n, hipMemcpyDeviceToHost));
-    return n;
+    SK_ENTER(c);
+    return redo_count(c, SK_REDO_F64);
 }
 
 // mlpy.dtw_subsequence(x, y) in the reference's own C arithmetic, NaN / inf included (k_dtw_cref above): what
@@ -1368,9 +1311,7 @@ int sk_last_f64_retries(void)
 int sk_dtw_subsequence_cref(const double *x, int32_t nx, const double *y, int32_t ny,
                             double *dist, int32_t *start, int32_t *end)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!x || !y || nx <= 0 || ny <= 0) return sk_fail(SK_ERR_INVALID, "empty x or y");
     const size_t cells = (size_t)nx * (size_t)ny;
     if (cells > ((size_t)1 << 28)) return sk_fail(SK_ERR_UNSUPPORTED, "%d x %d cost matrix is over 2 GB", nx, ny);

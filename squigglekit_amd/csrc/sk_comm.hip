@@ -14,6 +14,7 @@
 #include "sk_common.h"
 #include <rccl/rccl.h>      // types only: every entry point is resolved with dlsym
 #include <dlfcn.h>
+#include <memory>
 #include <mutex>
 #include <string.h>
 
@@ -92,9 +93,7 @@ int sk_comm_unique_id(void *id128)
 
 int sk_comm_init_rank(const void *id128, int nranks, int rank)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!id128 || nranks <= 0 || rank < 0 || rank >= nranks) return sk_fail(SK_ERR_INVALID, "bad id / rank / nranks");
     if (c->comm) return sk_fail(SK_ERR_INVALID, "device %d already has a communicator", c->device);
     Rccl *R = rccl();
@@ -113,26 +112,33 @@ int sk_comm_init_all(const int *devices, int ndev)
     Rccl *R = rccl();
     if (!R) return no_rccl();
     const int before = sk_bound_device();
+    bool listed[SK_MAX_DEVICES] = {};
     for (int i = 0; i < ndev; i++) {                      // every device needs its context (stream)
         const int rc = sk_init(devices[i]);
         if (rc) return rc;
-        if (sk_ctx_of(devices[i])->comm)
-            return sk_fail(SK_ERR_INVALID, "device %d already has a communicator", devices[i]);
-        for (int j = 0; j < i; j++)
-            if (devices[j] == devices[i]) return sk_fail(SK_ERR_INVALID, "device %d listed twice", devices[i]);
+        if (listed[devices[i]]) return sk_fail(SK_ERR_INVALID, "device %d listed twice", devices[i]);
+        listed[devices[i]] = true;
     }
-    ncclComm_t comms[SK_MAX_DEVICES];
-    SK_NCCL(R, R->CommInitAll(comms, ndev, devices));
-    for (int i = 0; i < ndev; i++) sk_ctx_of(devices[i])->comm = comms[i];
+    {
+        // every context locked, in slot order, from the check of its communicator until it is set
+        std::unique_ptr<sk_entry> held[SK_MAX_DEVICES];
+        for (int d = 0; d < SK_MAX_DEVICES; d++) {
+            if (!listed[d]) continue;
+            held[d].reset(new sk_entry(d));
+            if (!held[d]->c) return SK_ERR_NO_DEVICE;
+            if (held[d]->c->comm) return sk_fail(SK_ERR_INVALID, "device %d already has a communicator", d);
+        }
+        ncclComm_t comms[SK_MAX_DEVICES];
+        SK_NCCL(R, R->CommInitAll(comms, ndev, devices));
+        for (int i = 0; i < ndev; i++) held[devices[i]]->c->comm = comms[i];
+    }
     if (before >= 0) return sk_init_slot(before, sk_ctx_of(before)->device);   // the calling thread keeps its binding
     return SK_OK;
 }
 
 int sk_comm_info(int *nranks, int *rank)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!c->comm) return sk_fail(SK_ERR_INVALID, "no communicator on device %d", c->device);
     Rccl *R = rccl();
     if (!R) return no_rccl();
@@ -148,9 +154,7 @@ int sk_comm_info(int *nranks, int *rank)
 // bound device's stream behind the kernels that produced d_send; sk_sync() waits for it.
 int sk_comm_allgather_dev(const void *d_send, void *d_recv, size_t bytes)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!c->comm) return sk_fail(SK_ERR_INVALID, "no communicator on device %d", c->device);
     if (bytes && (!d_send || !d_recv)) return sk_fail(SK_ERR_INVALID, "NULL buffer");
     Rccl *R = rccl();
@@ -162,18 +166,18 @@ int sk_comm_allgather_dev(const void *d_send, void *d_recv, size_t bytes)
 // small host-side exchange (timings, counts, a barrier): staged through device scratch, synchronous
 int sk_comm_allgather_host(const void *send, void *recv, size_t bytes)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!c->comm) return sk_fail(SK_ERR_INVALID, "no communicator on device %d", c->device);
     if (!send || !recv || bytes == 0) return sk_fail(SK_ERR_INVALID, "bad buffer");
+    Rccl *R = rccl();
+    if (!R) return no_rccl();
     int n = 0;
-    int rc = sk_comm_info(&n, nullptr);
+    SK_NCCL(R, R->CommCount((ncclComm_t)c->comm, &n));
+    int rc = sk_reserve(c, &c->commbuf, bytes * (size_t)(n + 1));
     if (rc) return rc;
-    if ((rc = sk_reserve(c, &c->commbuf, bytes * (size_t)(n + 1)))) return rc;
     char *d_send = (char *)c->commbuf.p, *d_recv = d_send + bytes;
     SK_HIP(hipMemcpyAsync(d_send, send, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = sk_comm_allgather_dev(d_send, d_recv, bytes))) return rc;
+    SK_NCCL(R, R->AllGather(d_send, d_recv, bytes, ncclUint8, (ncclComm_t)c->comm, c->stream));
     SK_HIP(hipMemcpyAsync(recv, d_recv, bytes * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
@@ -181,9 +185,7 @@ int sk_comm_allgather_host(const void *send, void *recv, size_t bytes)
 
 int sk_comm_destroy(void)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!c->comm) return SK_OK;
     Rccl *R = rccl();
     if (!R) return no_rccl();

@@ -30,6 +30,9 @@ struct sk_prep {
 
 enum sk_prep_mode { SK_PREP_MEDMAD = 0, SK_PREP_ZSCALE = 1, SK_PREP_SEGMENT = 2, SK_PREP_DRNA = 3 };
 
+// which statistics route wrote sk_ctx::redo (sk_last_f64_retries / sk_last_pa_retries)
+enum sk_redo_route { SK_REDO_NONE = 0, SK_REDO_I16 = 1, SK_REDO_F64 = 2, SK_REDO_PA = 3 };
+
 // Growable device scratch buffer.
 struct sk_buf {
     void  *p = nullptr;
@@ -82,7 +85,7 @@ struct sk_ctx {
     sk_buf motifw;    // the motif (doubles) in the screening scheme's own per-lane layout
     std::vector<double> motifw_host;
     int    motifq_L = 0;   // lanes per read of the layouts in motifq / motifw
-    sk_buf retry;     // DTW retry list: [0] = count, [1] = pad, [2 ..] = reads (segmenter: [0] = count, [1 ..] = reads)
+    sk_buf retry;     // DTW retry list: [0] = count, [1] = pad, [2 ..] = reads
     sk_buf dtwcnt;    // [0] = reads retried by the exact pass, summed over the launches of one API call (device); [1] second tier; +16 clock; +32 guard counters
     sk_buf audit;     // the audit's read list ([0] = count, [2 ..] = reads) and its exact records
     sk_buf sib;       // window passes: [0..3] count, then {read, jlo, jhi, -} per second cluster of candidate columns
@@ -91,10 +94,15 @@ struct sk_ctx {
     bool   retry_dev = false;   // the last DTW call left its retry count on the device (read lazily)
     std::vector<unsigned> motifq_host;
     bool   motifq_valid = false;
-    int    f64_stream = 0;   // the last float64 call took the streaming statistics kernel (its retry count: retry[0])
-    int    pa_raw = 0;       // the last pA call of raw rows stayed in the raw domain (k_seg_stats<.., PA>)
-    std::vector<const int32_t *> pa_retry_ptrs;   // ... the device counters of its numpy-order redo lists (one per chunk)
-    std::vector<int64_t> pa_off_host;             // slot offsets of the float64 fallback of that route
+    // numpy-order redo lists of the segmenter's statistics routes (int16, float64, pA): a buffer of their own, so that
+    // no DTW launch moves or overwrites them.  Per list [0] = count, [1 ..] = reads; the lists of one API call (one
+    // per sub-batch) lie side by side.  redo_route: the route that wrote them in the last MotifSeq / segmenter call,
+    // redo_off: where in `redo` the counters of that call are (ints), redo_used: ints handed out so far in that call.
+    sk_buf redo;
+    int    redo_route = SK_REDO_NONE;
+    std::vector<size_t> redo_off;
+    size_t redo_used = 0;
+    std::vector<int64_t> pa_off_host;             // slot offsets of the float64 fallback of the pA route
     int    last_retry = 0;   // reads that needed the exact single-pass retry in the last DTW call
     std::vector<hipEvent_t> evpool;   // per-launch events of the two-pass DTW (3 per chunk)
     int    prof_chunks = 0;  // chunks of the last two-pass DTW call (0: single pass)
@@ -114,24 +122,29 @@ struct sk_ctx {
 const char *sk_tune(const char *name);
 
 // ---- runtime (sk_runtime.hip) ----
-// Every entry point that touches a context holds that context's lock from sk_cur() to its return (SURVEY 8(b):
-// "per-device context guarded by a mutex"): two host threads bound to the same slot take turns call by call -- the
-// scratch buffers sk_reserve may free, the streams' event slots and the "last call" counters belong to one call at a
-// time.  Recursive: entry points call each other.  Contexts of different slots never wait for each other.
-void sk_ctx_lock(sk_ctx *c);
-void sk_ctx_unlock(sk_ctx *c);
-struct sk_ctx_guard {
-    sk_ctx *c;
-    explicit sk_ctx_guard(sk_ctx *ctx) : c(ctx) { if (c) sk_ctx_lock(c); }
-    ~sk_ctx_guard() { if (c) sk_ctx_unlock(c); }
-    sk_ctx_guard(const sk_ctx_guard &) = delete;
-    sk_ctx_guard &operator=(const sk_ctx_guard &) = delete;
+// Every public entry point that touches a context opens with an sk_entry and holds it to its return (SURVEY 8(b):
+// "per-device context guarded by a mutex"): it takes the slot's lock first, then checks that the context is ready
+// (SK_ERR_NO_DEVICE otherwise: never set up, or shut down while this thread waited for the lock), then makes its
+// device current.  Two host threads bound to the same slot take turns call by call -- the scratch buffers sk_reserve
+// may free, the streams' event slots and the "last call" counters belong to one call at a time.  Contexts of different
+// slots never wait for each other; g_mu (sk_init_slot, sk_shutdown) is always taken before a context lock.
+struct sk_entry {
+    sk_ctx *c = nullptr;                     // nullptr: no ready context (the error is set)
+    sk_entry();                              // the slot the calling thread is bound to
+    explicit sk_entry(int slot);
+    ~sk_entry();
+    sk_entry(const sk_entry &) = delete;
+    sk_entry &operator=(const sk_entry &) = delete;
 };
-sk_ctx *sk_cur(void);                       // bound context or nullptr (error set)
+#define SK_ENTER(c)                                                                     \
+    sk_entry c##_entry_;                                                                \
+    sk_ctx *const c = c##_entry_.c;                                                     \
+    if (!c) return SK_ERR_NO_DEVICE
 sk_ctx *sk_ctx_of(int device);              // context slot of a device (ready or not)
 int  sk_bound_device(void);                 // device the calling thread is bound to, or -1
 int  sk_fail(int code, const char *fmt, ...);
 int  sk_reserve(sk_ctx *c, sk_buf *b, size_t bytes);
+int  sk_second_stream(sk_ctx *c);           // creates stream2 and its ordering events ev_chunk on first use
 // Reads per chunk of a checkpointing DTW call: scratch budget (64 GB, or SK_DTW_SCRATCH_MB) / per_read, at
 // least 1024 reads (64 when the budget was set by hand, so that tests can force many small chunks).
 int64_t sk_dtw_chunk_reads(size_t per_read, int64_t nreads);

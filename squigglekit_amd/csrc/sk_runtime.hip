@@ -15,10 +15,7 @@ static thread_local char  g_err[512] = "";
 static thread_local int   g_cur = -1;
 static sk_ctx             g_ctx[SK_MAX_DEVICES];
 static std::mutex         g_mu;
-static std::recursive_mutex g_ctx_mu[SK_MAX_DEVICES];      // one per context slot (sk_ctx_guard)
-
-void sk_ctx_lock(sk_ctx *c)   { g_ctx_mu[c - g_ctx].lock(); }
-void sk_ctx_unlock(sk_ctx *c) { g_ctx_mu[c - g_ctx].unlock(); }
+static std::recursive_mutex g_ctx_mu[SK_MAX_DEVICES];      // one per context slot (sk_entry)
 
 int sk_fail(int code, const char *fmt, ...)
 {
@@ -29,18 +26,25 @@ int sk_fail(int code, const char *fmt, ...)
     return code;
 }
 
-sk_ctx *sk_cur(void)
+sk_entry::sk_entry() : sk_entry(g_cur) {}
+
+sk_entry::sk_entry(int slot)
 {
-    if (g_cur < 0 || !g_ctx[g_cur].ready) {
-        sk_fail(SK_ERR_NO_DEVICE, "no device bound: call sk_init(device) first (no CPU fallback exists)");
-        return nullptr;
+    if (slot >= 0 && slot < SK_MAX_DEVICES) {
+        g_ctx_mu[slot].lock();                             // the lock first: sk_shutdown may be tearing this context down
+        sk_ctx *ctx = &g_ctx[slot];
+        if (ctx->ready) {
+            if (hipSetDevice(ctx->device) == hipSuccess) { c = ctx; return; }
+            sk_fail(SK_ERR_NO_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+            g_ctx_mu[slot].unlock();
+            return;
+        }
+        g_ctx_mu[slot].unlock();
     }
-    if (hipSetDevice(g_ctx[g_cur].device) != hipSuccess) {
-        sk_fail(SK_ERR_NO_DEVICE, "hipSetDevice(%d) failed", g_ctx[g_cur].device);
-        return nullptr;
-    }
-    return &g_ctx[g_cur];
+    sk_fail(SK_ERR_NO_DEVICE, "no device bound: call sk_init(device) first (no CPU fallback exists)");
 }
+
+sk_entry::~sk_entry() { if (c) g_ctx_mu[c - g_ctx].unlock(); }
 
 sk_ctx *sk_ctx_of(int device) { return (device >= 0 && device < SK_MAX_DEVICES) ? &g_ctx[device] : nullptr; }
 int sk_bound_device(void) { return g_cur; }
@@ -57,6 +61,15 @@ int sk_reserve(sk_ctx *c, sk_buf *b, size_t bytes)
         return sk_fail(SK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
     }
     b->cap = want;
+    return SK_OK;
+}
+
+int sk_second_stream(sk_ctx *c)
+{
+    if (!c->stream2) {
+        SK_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+        for (int i = 0; i < 9; i++) SK_HIP(hipEventCreateWithFlags(&c->ev_chunk[i], hipEventDisableTiming));
+    }
     return SK_OK;
 }
 
@@ -176,7 +189,7 @@ int sk_init_slot(int slot, int device)
         return sk_fail(SK_ERR_INVALID, "context slot %d out of range (0..%d)", slot, SK_MAX_DEVICES - 1);
     std::lock_guard<std::mutex> lk(g_mu);
     sk_ctx *c = &g_ctx[slot];
-    sk_ctx_guard c_lock(c);
+    std::lock_guard<std::recursive_mutex> c_lock(g_ctx_mu[slot]);
     if (c->ready && c->device != device)
         return sk_fail(SK_ERR_INVALID, "context slot %d already serves device %d", slot, c->device);
     SK_HIP(hipSetDevice(device));
@@ -203,13 +216,13 @@ int sk_shutdown(void)
     std::lock_guard<std::mutex> lk(g_mu);
     for (int d = 0; d < SK_MAX_DEVICES; d++) {
         sk_ctx *c = &g_ctx[d];
-        sk_ctx_guard c_lock(c);                            // (a call in flight on another thread finishes first)
+        std::lock_guard<std::recursive_mutex> c_lock(g_ctx_mu[d]);   // (a call in flight on another thread finishes first)
         if (!c->ready) continue;
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         sk_buf *bufs[] = {&c->sig, &c->len, &c->off, &c->comp, &c->prep, &c->mask,
                           &c->motif, &c->out, &c->out2, &c->misc, &c->ckpt, &c->retry, &c->motifq, &c->lastq, &c->qflag,
-                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->sib, &c->sibout, &c->sibstate};
+                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate};
         for (sk_buf *b : bufs) free_buf(b);
         for (int i = 0; i < 4; i++) (void)hipEventDestroy(c->ev[i]);
         for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
@@ -240,18 +253,14 @@ int sk_shutdown(void)
 
 int sk_sync(void)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
 }
 
 int sk_device_name(char *buf, int cap)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!buf || cap <= 0) return sk_fail(SK_ERR_INVALID, "bad buffer");
     hipDeviceProp_t prop;
     SK_HIP(hipGetDeviceProperties(&prop, c->device));
@@ -262,9 +271,7 @@ int sk_device_name(char *buf, int cap)
 // "0000:c1:00.0" of the bound device: what /sys/bus/pci/devices/<id>/local_cpulist and numa_node are keyed on
 int sk_device_pci_bus_id(char *buf, int cap)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!buf || cap < 16) return sk_fail(SK_ERR_INVALID, "bad buffer");
     SK_HIP(hipDeviceGetPCIBusId(buf, cap, c->device));
     return SK_OK;
@@ -272,9 +279,8 @@ int sk_device_pci_bus_id(char *buf, int cap)
 
 void *sk_dev_alloc(size_t bytes)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return nullptr;
-    sk_ctx_guard c_lock(c);
+    sk_entry entry;
+    if (!entry.c) return nullptr;
     void *p = nullptr;
     hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
     if (e != hipSuccess) {
@@ -286,18 +292,14 @@ void *sk_dev_alloc(size_t bytes)
 
 int sk_dev_free(void *dptr)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (dptr) SK_HIP(hipFree(dptr));
     return SK_OK;
 }
 
 int sk_dev_upload(void *dst_dev, const void *src_host, size_t bytes)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (bytes && (!dst_dev || !src_host)) return sk_fail(SK_ERR_INVALID, "NULL pointer");
     SK_HIP(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
@@ -306,9 +308,7 @@ int sk_dev_upload(void *dst_dev, const void *src_host, size_t bytes)
 
 int sk_dev_download(void *dst_host, const void *src_dev, size_t bytes)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (bytes && (!dst_host || !src_dev)) return sk_fail(SK_ERR_INVALID, "NULL pointer");
     SK_HIP(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
@@ -317,9 +317,7 @@ int sk_dev_download(void *dst_host, const void *src_dev, size_t bytes)
 
 int sk_last_kernel_ms(float *prep_ms, float *main_ms)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!c->ev_valid) return sk_fail(SK_ERR_INVALID, "no timed call yet");
     SK_HIP(hipEventSynchronize(c->ev[3]));
     float a = 0.f, b = 0.f;
@@ -333,9 +331,7 @@ int sk_last_kernel_ms(float *prep_ms, float *main_ms)
 int sk_last_dtw_profile(float *dist_ms, int *dist_launches, float *start_ms, int *start_launches,
                         int *reads_per_launch)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     float a = 0.f, b = 0.f;
     int mx = 0;
     for (int i = 0; i < c->prof_chunks; i++) {
@@ -357,9 +353,7 @@ int sk_last_dtw_profile(float *dist_ms, int *dist_launches, float *start_ms, int
 
 int sk_last_dtw_retries(void)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (c->retry_dev && c->dtwcnt.p) {              // the count stayed on the device: fetch it now
         int32_t n = 0;
         if (hipMemcpyAsync(&n, c->dtwcnt.p, sizeof n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -372,9 +366,7 @@ int sk_last_dtw_retries(void)
 
 int sk_last_dtw_clock(double *ghz)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!ghz) return sk_fail(SK_ERR_INVALID, "NULL pointer");
     *ghz = 0.0;
     if (!(c->retry_dev && c->dtwcnt.p)) return SK_OK;
@@ -392,9 +384,7 @@ int sk_last_dtw_clock(double *ghz)
 // for a call that did not take the screening scheme.
 int sk_last_dtw_guard(int32_t *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!out) return sk_fail(SK_ERR_INVALID, "NULL pointer");
     memset(out, 0, 8 * sizeof(int32_t));
     if (!(c->retry_dev && c->dtwcnt.p)) return SK_OK;
@@ -422,9 +412,7 @@ int sk_last_dtw_audit_mismatches(void)
 // reads asked for, summed over the read groups (a wavefront's groups step together: out[0] * groups per wave >= out[1])
 int sk_last_dtw_window_steps(uint64_t *out)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!out) return sk_fail(SK_ERR_INVALID, "NULL pointer");
     out[0] = out[1] = 0;
     if (!(c->retry_dev && c->dtwcnt.p && c->dtwcnt.cap >= 128)) return SK_OK;
@@ -436,9 +424,7 @@ int sk_last_dtw_window_steps(uint64_t *out)
 
 int sk_last_dtw_tier2(void)
 {
-    sk_ctx *c = sk_cur();
-    if (!c) return SK_ERR_NO_DEVICE;
-    sk_ctx_guard c_lock(c);
+    SK_ENTER(c);
     if (!(c->retry_dev && c->dtwcnt.p)) return 0;
     int32_t n = 0;
     if (hipMemcpyAsync(&n, (const int32_t *)c->dtwcnt.p + 1, sizeof n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||

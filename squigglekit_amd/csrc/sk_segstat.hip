@@ -1726,7 +1726,8 @@ bool sk_segment_fast_applies(const void *d_sig, int64_t stride, int32_t lo, int3
 // Streaming statistics, the numpy-order redo of the (almost always empty) list of uncertified reads, then the walk.
 // Large batches go in SK_SEG_CHUNKS chunks (4), the walk of chunk i on a second stream beside the statistics of
 // chunk i + 1 (see below; folding the walk into the statistics kernel itself was built and measured too: DESIGN 4.0).
-// d_retry: nreads + 16 ints (per chunk: [0] = count, [1 ..] = list; zeroed here).  Records ev[0..3] like the
+// d_retry: nreads + 16 ints of c->redo (per chunk: [0] = count, [1 ..] = list; zeroed here; the chunks' counters are
+// added to c->redo_off).  Records ev[0..3] like the
 // other segment paths: ev[0]..ev[1] statistics of all chunks, ev[2]..ev[3] what is left of the walks after that.
 int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                            const sk_seg_params *p, int32_t lo, int32_t hi, sk_prep *d_prep, void *d_mask2,
@@ -1756,10 +1757,7 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     int nchunks = nreads >= 262144 && !walk_jumps_apply(wp, fast, by_runs, a.row16) ? 4 : 1;
     if (const char *e = sk_tune("SK_SEG_CHUNKS")) { int v = atoi(e); if (v >= 1 && v <= 8) nchunks = v; }
     if (nreads < 65536) nchunks = 1;
-    if (nchunks > 1 && !c->stream2) {
-        SK_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        for (int i = 0; i < 9; i++) SK_HIP(hipEventCreateWithFlags(&c->ev_chunk[i], hipEventDisableTiming));
-    }
+    if (nchunks > 1) { int rc = sk_second_stream(c); if (rc) return rc; }
     int per_cu = nchunks > 1 ? 4 : 8, rounds = 8;
     if (const char *e = sk_tune("SK_PREP_ROUNDS")) { int v = atoi(e); if (v > 0) rounds = v; }
     if (const char *e = sk_tune("SK_PREP_PERCU")) { int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; }
@@ -1771,7 +1769,6 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
         a.hints = (unsigned *)c->seghints.p;
     }
     unsigned *const hints0 = a.hints;
-    if (d_cal) c->pa_retry_ptrs.clear();
     SK_HIP(hipMemsetAsync(d_retry, 0, ((size_t)nreads + 16) * sizeof(int32_t), c->stream));
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
     if (nchunks > 1) {                                             // the second stream starts behind the memsets
@@ -1801,8 +1798,8 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
         SK_HIP(hipGetLastError());
         // reads whose ceil(top) / floor(bot) could not be certified: numpy-order statistics, masks rewritten in place
         // (reads too long for the redo's LDS copy: one scratch row per workgroup of its persistent grid, <= one per CU)
+        c->redo_off.push_back((size_t)(retry - (int32_t *)c->redo.p));
         if (d_cal) {
-            c->pa_retry_ptrs.push_back(retry);
             // (pA: the listed reads from their float64 values, one scratch row of doubles per workgroup)
             const int g2 = nr < c->num_cu ? nr : c->num_cu;
             int rc = sk_launch_prep_pa_listed(c, a.sig, stride, a.len, a.cal, retry + 1, retry, g2, (double)lo, (double)hi,

@@ -244,6 +244,22 @@ def test_f64_streaming_medmad_vs_oracle(gpu, ora, example_model):
             assert (got["dist"][r], got["start"][r], got["end"][r], got["n"][r]) == w, r
 
 
+def test_f64_redo_count_is_not_the_dtw_retry_count(gpu, example_model, monkeypatch):
+    """float64 medmad MotifSeq through the streaming statistics kernel and the screening scheme (>= 256 reads of at most
+    4 096 samples): the statistics redo count does not move when the DTW path retries many reads (SK_DTW_SPAN=30)"""
+    from squigglekit_amd import api
+    L = gpu.load()
+    reads = _pa_reads(400, 3000, 31)
+    plain = api.motifseq_reads_f64(reads, example_model, scale="medmad", scale_low=0, scale_hi=900)
+    r_plain = L.sk_last_f64_retries()
+    monkeypatch.setenv("SK_DTW_SPAN", "30")
+    narrow = api.motifseq_reads_f64(reads, example_model, scale="medmad", scale_low=0, scale_hi=900)
+    r_narrow = L.sk_last_f64_retries()
+    assert L.sk_last_dtw_retries() > 20, "SK_DTW_SPAN=30 did not make the DTW path retry"
+    assert narrow.tobytes() == plain.tobytes()
+    assert 0 <= r_plain == r_narrow, (r_plain, r_narrow)
+
+
 def _long_reads(rng):
     """Reads beyond 4 096 samples (the window-by-window float64 kernel): pA-like, ungridded (hundreds of distinct values
     in the median's bin: resolved in LDS), three distinct values (more than 512 equal-bin members), an outlier-stretched

@@ -183,3 +183,28 @@ def test_centi_unit_batches_equal_the_float64_ones(gpu, ora):
         ha = api.motifseq_multi_ragged_f64(flat, off, [motif, motif[10:90]], scale=scale)
         hb = api.motifseq_multi_ragged_f64(vals, off, [motif, motif[10:90]], scale=scale)
         assert [h.tobytes() for h in ha] == [h.tobytes() for h in hb]
+
+
+def test_redo_count_sums_over_sub_batches_and_is_not_left_stale(gpu, monkeypatch):
+    """every read through the numpy-order redo (SK_SEG_DELTA_SCALE) in one call of three sub-batches (SK_INGEST_MB):
+    the count covers all of them, as in the single-shot call; a later MotifSeq call on a larger batch (which regrows the
+    DTW retry list) leaves -1, not the pA call's count"""
+    from squigglekit_amd import api, synth
+    R, M = 9000, 1000
+    raw = squiggles(R, M, 4242)
+    lens = np.full(R, M, dtype=np.int32)
+    lens[::7] = 600
+    calib = np.tile(np.array(MINION), (R, 1))
+    monkeypatch.setenv("SK_SEG_DELTA_SCALE", "1e13")
+    one = api.segment_batch_pa(raw, lens, calib)
+    r_one = api.last_pa_retries()
+    monkeypatch.setenv("SK_INGEST_MB", "1")          # 4 096 reads a sub-batch at least -> 3 sub-batches of 3 000
+    got = api.segment_batch_pa(raw, lens, calib)
+    r_all = api.last_pa_retries()
+    assert np.array_equal(got[0], one[0]) and np.array_equal(got[1], one[1])
+    assert r_all == r_one and r_all > 4096, (r_all, r_one)
+    monkeypatch.delenv("SK_INGEST_MB")
+    monkeypatch.delenv("SK_SEG_DELTA_SCALE")
+    motif = synth.synthetic_motif(100, seed=3)
+    api.motifseq_batch(synth.squiggle_batch(2 * R, M, 99, motif=motif), np.full(2 * R, M, dtype=np.int32), motif)
+    assert api.last_pa_retries() == -1

@@ -1,7 +1,7 @@
 """GPU: two host threads bound to the SAME context slot (SURVEY 8(b) "Threading": per-device context guarded by a mutex).
 
-Every compute / upload / download entry point of csrc/sk_api.hip holds its context's lock (sk_ctx_guard, csrc/sk_common.h)
-from sk_cur() to its return, so calls of different threads on one slot take turns: the scratch buffers one call's
+Every compute / upload / download entry point of csrc/sk_api.hip holds its context's lock (sk_entry, csrc/sk_common.h)
+from its first line to its return, so calls of different threads on one slot take turns: the scratch buffers one call's
 sk_reserve may free, the event slots and the "last call" counters belong to one call at a time.  Before round 6 only
 sk_init_slot / sk_shutdown took a lock and two threads on one slot corrupted each other's records (round 4's advisor
 finding; it had been fixed by ordering in motifseq_cli.py, not in the library).
