@@ -765,7 +765,6 @@ static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     int rc;
     int32_t lo = p->lim_low, hi = p->lim_hi;
     clamp_limits(&lo, &hi);
-    const int64_t words = (stride + 63) / 64;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
     // slots past nsegs[r] read as zero, whatever the buffer held before
     SK_HIP(hipMemsetAsync(d_segs, 0, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t), c->stream));
@@ -782,15 +781,17 @@ static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
         c->ev_valid = true;
         return SK_OK;
     }
+    // the numpy-order kernel for every read: it writes the streaming path's {in band, kept} entries, the same walk follows
+    const int row16 = (int)((stride + 63) / 64);
     if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)words * sizeof(uint64_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
     rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nreads, lo, hi, SK_PREP_SEGMENT, p->std_scale,
-                            (int16_t *)c->comp.p, (sk_prep *)c->prep.p, (uint64_t *)c->mask.p, nreads);
+                            (int16_t *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0, 0, 0x7fffffff, nullptr, nullptr,
+                            c->mask.p, row16);
     if (rc) return rc;
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
-    rc = sk_launch_segment_walk(c, (const uint64_t *)c->mask.p, nreads, nullptr, (const sk_prep *)c->prep.p,
-                                nreads, p, d_segs, d_nsegs, max_segs);
+    rc = sk_launch_seg_walk_masks(c, c->mask.p, row16, d_len, nreads, p, d_segs, d_nsegs, max_segs);
     if (rc) return rc;
     c->ev_valid = true;
     return SK_OK;
@@ -802,48 +803,43 @@ static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off,
                            const int32_t *d_rlen = nullptr)
 {
     int rc;
-    const int64_t words = (maxlen + 63) / 64 > 0 ? (maxlen + 63) / 64 : 1;
     const size_t gb = (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t);
-    if (sk_f64_fast_applies(maxlen, p->std_scale)) {
-        // streaming statistics with certified comparisons (sk_f64stat.hip), the numpy-order kernel over the (almost
-        // always empty) list of uncertified reads, then the run-hopping walk of the int16 path over the same masks
-        const int row16 = sk_f64_row16(maxlen > 0 ? maxlen : 1);
-        const int grid = nreads < 2 * c->num_cu ? nreads : 2 * c->num_cu;
-        const int64_t srow = (maxlen + 7) & ~(int64_t)7;
-        if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-        if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
-        if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-        if ((rc = sk_reserve(c, &c->comp, (size_t)grid * (size_t)(srow > 0 ? srow : 8) * sizeof(double)))) return rc;
-        int32_t *retry;
+    // streaming statistics with certified comparisons (sk_f64stat.hip) and the numpy-order kernel over the (almost
+    // always empty) list of uncertified reads -- or, outside the streaming kernel's range, the numpy-order kernel for
+    // every read.  Either writes {in band, kept} entries and raw lengths; the run-hopping walk of the int16 path follows.
+    const bool fast = sk_f64_fast_applies(maxlen, p->std_scale);
+    const int row16 = sk_f64_row16(maxlen > 0 ? maxlen : 1);
+    const int grid = nreads < 2 * c->num_cu ? nreads : 2 * c->num_cu;
+    const int64_t srow = (maxlen + 7) & ~(int64_t)7;
+    // compacted samples: one scratch row per workgroup of the listed redo, or every read's
+    const size_t cb = fast ? (size_t)grid * (size_t)(srow > 0 ? srow : 8) * sizeof(double)
+                           : (size_t)(total > 0 ? total : 1) * sizeof(double);
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->comp, cb))) return rc;
+    int32_t *retry = nullptr;
+    if (fast) {
         if ((rc = redo_list(c, SK_REDO_F64, nreads, &retry))) return rc;
         c->redo_off.push_back((size_t)(retry - (int32_t *)c->redo.p));
-        SK_HIP(hipMemsetAsync(d_segs, 0, gb, c->stream));
-        SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    }
+    SK_HIP(hipMemsetAsync(d_segs, 0, gb, c->stream));
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    if (fast) {
         rc = sk_launch_f64_stats(c, d_sig, d_off, d_rlen, nreads, maxlen, (double)p->lim_low, (double)p->lim_hi, SK_PREP_SEGMENT,
                                  p->std_scale, (sk_prep *)c->prep.p, c->mask.p, row16, (int32_t *)c->len.p, retry, nullptr);
         if (rc) return rc;
         rc = sk_launch_prep_f64_listed(c, d_sig, d_off, retry + 1, retry, grid, (double)p->lim_low, (double)p->lim_hi,
                                        SK_PREP_SEGMENT, p->std_scale, (double *)c->comp.p, srow, (sk_prep *)c->prep.p,
                                        c->mask.p, row16, d_rlen);
-        if (rc) return rc;
-        SK_HIP(hipEventRecord(c->ev[1], c->stream));
-        rc = sk_launch_seg_walk_masks(c, c->mask.p, row16, (const int32_t *)c->len.p, nreads, p, d_segs, d_nsegs, max_segs);
-        if (rc) return rc;
-        c->ev_valid = true;
-        return SK_OK;
+    } else {
+        rc = sk_launch_prep_f64(c, d_sig, d_off, nreads, (double)p->lim_low, (double)p->lim_hi, SK_PREP_SEGMENT,
+                                p->std_scale, (double *)c->comp.p, (sk_prep *)c->prep.p, c->mask.p, row16,
+                                (int32_t *)c->len.p, d_rlen);
     }
-    if ((rc = sk_reserve(c, &c->comp, (size_t)(total > 0 ? total : 1) * sizeof(double)))) return rc;
-    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)words * sizeof(uint64_t)))) return rc;
-    SK_HIP(hipMemsetAsync(d_segs, 0, gb, c->stream));
-    SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    rc = sk_launch_prep_f64(c, d_sig, d_off, nreads, (double)p->lim_low,
-                            (double)p->lim_hi, SK_PREP_SEGMENT, p->std_scale, (double *)c->comp.p,
-                            (sk_prep *)c->prep.p, (uint64_t *)c->mask.p, nreads, d_rlen);
     if (rc) return rc;
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
-    rc = sk_launch_segment_walk(c, (const uint64_t *)c->mask.p, nreads, nullptr, (const sk_prep *)c->prep.p,
-                                nreads, p, d_segs, d_nsegs, max_segs);
+    rc = sk_launch_seg_walk_masks(c, c->mask.p, row16, (const int32_t *)c->len.p, nreads, p, d_segs, d_nsegs, max_segs);
     if (rc) return rc;
     c->ev_valid = true;
     return SK_OK;

@@ -159,23 +159,27 @@ void    sk_dtw_scratch_shrink(int reset);   // halve the calling thread's scratc
 
 // ---- prep (sk_prep.hip) ----
 // i16: rows of `stride` samples; comp gets the filtered samples of read r at
-// comp + r*stride.  mask (segmenter only) gets ceil(stride/64) words per read.
+// comp + r*stride.  mask (dRNA mode) gets ceil(stride/64) transposed words per read, word wi of read r at
+// [wi * mask_stride + r].  SEGMENT mode writes d_mask2 instead: {in band, kept} entries in raw coordinates, row16 per
+// read, entries [0, ceil(len/64)) in full (the layout sk_launch_seg_walk_masks reads).
 int sk_launch_prep_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len,
                        int32_t nreads, int32_t lo, int32_t hi, int mode, double std_scale,
                        int16_t *d_comp, sk_prep *d_prep, uint64_t *d_mask, int64_t mask_stride,
                        int32_t t0 = 0, int32_t t1 = 0x7fffffff,    // statistics window (filtered index)
                        // SEGMENT mode over a device-side list of reads (d_list[0 .. *d_count)): statistics in numpy's
-                       // order, masks written as {in band, kept} entries in raw coordinates (sk_segstat.hip)
+                       // order for those reads only (the streaming segmenter's uncertified reads, sk_segstat.hip)
                        const int32_t *d_list = nullptr, const int32_t *d_count = nullptr,
                        void *d_mask2 = nullptr, int row16 = 0);
 // wavefront-per-read medmad variant (sk_prepw.hip): same results; returns 1 (nothing launched) when
 // the configuration is outside its range and the caller has to use the workgroup-per-read kernel
 int sk_launch_prepw_medmad(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len,
                            int32_t nreads, int32_t lo, int32_t hi, int16_t *d_comp, sk_prep *d_prep);
-// f64 ragged: read r is sig[off[r]..off[r+1]); comp uses the same offsets.
+// f64 ragged: read r is sig[off[r]..off[r+1]); comp uses the same offsets.  SEGMENT mode writes {in band, kept}
+// entries in raw coordinates (row16 per read, as sk_launch_prep_i16) and each read's raw length to d_len_out.
 int sk_launch_prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads,
                        double lo, double hi, int mode, double std_scale,
-                       double *d_comp, sk_prep *d_prep, uint64_t *d_mask, int64_t mask_rows,
+                       double *d_comp, sk_prep *d_prep, void *d_mask2 = nullptr, int row16 = 0,
+                       int32_t *d_len_out = nullptr,
                        const int32_t *d_rlen = nullptr);   // optional: read r is its first d_rlen[r] samples
 
 // ---- DTW (sk_sdtw.hip) ----
@@ -220,7 +224,7 @@ int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a);
 int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, int span2,
                           int32_t *d_retry_cnt, int32_t *d_retry, int32_t *d_early_cnt, int32_t *d_early);
 
-// ---- dRNA --signal branch (rolling mean): statistics + masks (sk_prep.hip), scan (sk_segment.hip) ----
+// ---- dRNA --signal branch (rolling mean): statistics + masks (sk_prep.hip), scan (sk_drna_walk.hip) ----
 struct sk_roll_params;
 // comp / prep as left by sk_launch_prep_i16; psum: nreads * (stride + 1) int64 scratch; masks: two
 // transposed bit masks (t < bot, t > bot), `words` words per read each, word wi of read r at [wi * nreads + r]
@@ -250,15 +254,11 @@ int  sk_launch_prep_pa_listed(sk_ctx *c, const int16_t *d_sig, int64_t stride, c
                               const int32_t *d_list, const int32_t *d_count, int grid, double lo, double hi, double std_scale,
                               double *d_scratch, int64_t scratch_stride, sk_prep *d_prep, void *d_mask2, int row16);
 
-// ---- segment walk (sk_segment.hip) ----
+// ---- dRNA slow5-branch walk (sk_drna_walk.hip) ----
 struct sk_drna_params;
 int sk_launch_drna_walk(sk_ctx *c, const uint64_t *d_mask, int64_t mask_rows, const sk_prep *d_prep,
                         int32_t nreads, const sk_drna_params *p, int32_t *d_segs, int32_t *d_nsegs,
                         int32_t max_segs);
-int sk_launch_segment_walk(sk_ctx *c, const uint64_t *d_mask, int64_t mask_stride,
-                           const int64_t *d_mask_off, const sk_prep *d_prep, int32_t nreads,
-                           const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs,
-                           int32_t max_segs);
 
 // ---- synth (sk_synth.hip) ----
 int sk_launch_synth(sk_ctx *c, int16_t *d_sig, int64_t stride, int32_t nreads, int32_t nsamples,

@@ -320,8 +320,9 @@ __device__ __forceinline__ void put8(P *dst, const unsigned (&q)[4], int al)
 // WINDOWED: statistics over filtered samples [t0, t1) only (dRNA_segmenter.py:109-110)
 // MEDMAD: the medmad variant (its own instantiation: it shares no statistics code with the
 // mean/std variants, and one kernel carrying both runs out of registers)
-// LISTED: the reads are list[0 .. *count) (the streaming segmenter's uncertified reads, sk_segstat.hip); the
-// mask goes out as {in band, kept} bytes in RAW sample coordinates into that path's per-read entries.
+// LISTED: the reads are list[0 .. *count) (the streaming segmenter's uncertified reads, sk_segstat.hip).
+// SEGMENT mode writes the mask as {in band, kept} bytes in RAW sample coordinates, row16 16-byte entries per read
+// (the layout the segmenter's walk reads); DRNA mode as transposed words over the filtered samples (maskT).
 struct ListedArgs {
     const int32_t *list;
     const int32_t *count;
@@ -377,6 +378,29 @@ void k_prep_i16(const int16_t *__restrict__ sig, int64_t stride, const int32_t *
     };
     auto sample = [](const unsigned (&q)[4], int k) -> int {
         return (k & 1) ? (int)q[k >> 1] >> 16 : (int)(short)(q[k >> 1] & 0xffffu);
+    };
+    // SEGMENT mode's mask, one byte of each per 8 samples: every entry [0, ceil(M / 64)) in full, the groups past M
+    // too (nothing kept there) -- the buffer is reused across calls and the walk reads whole entries
+    auto put_mask2 = [&](int r, const int16_t *row, int M, int first, unsigned width) {
+        unsigned char *mb = la.mask2 + (int64_t)r * la.row16 * 16;
+        const int Me = (M + 63) & ~63;
+        for (int base = 0; base < Me; base += TPB * 8) {
+            const int i0 = base + tid * 8;
+            if (i0 < Me) {
+                unsigned q[4];
+                load8(row, M, i0, q);
+                unsigned in8 = 0, kp8 = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const int x = sample(q, k);
+                    const bool kept = i0 + k < M && x > lo && x < hi;
+                    kp8 |= (kept ? 1u : 0u) << k;
+                    in8 |= ((kept && (unsigned)(x - first) < width) ? 1u : 0u) << k;
+                }
+                mb[(i0 >> 6) * 16 + ((i0 & 63) >> 3)] = (unsigned char)in8;
+                mb[(i0 >> 6) * 16 + 8 + ((i0 & 63) >> 3)] = (unsigned char)kp8;
+            }
+        }
     };
 
     if (tid == 0) sc->tree_m = -1;                         // no pairwise tree cached yet
@@ -472,6 +496,7 @@ void k_prep_i16(const int16_t *__restrict__ sig, int64_t stride, const int32_t *
         const double qnan = __builtin_nan("");
         pr.center = qnan; pr.scale = qnan; pr.top = qnan; pr.bot = qnan;
         if (tid == 0) prep[r] = pr;
+        if (mode == SK_PREP_SEGMENT) put_mask2(r, row, M, 0, 0u);
         lds_barrier();
         continue;
     }
@@ -484,7 +509,8 @@ void k_prep_i16(const int16_t *__restrict__ sig, int64_t stride, const int32_t *
         const double qnan = __builtin_nan("");
         pr.center = qnan; pr.scale = qnan; pr.top = qnan; pr.bot = qnan;
         if (tid == 0) prep[r] = pr;
-        if (maskT != nullptr)
+        if (mode == SK_PREP_SEGMENT) put_mask2(r, row, M, 0, 0u);
+        else if (maskT != nullptr)
             for (int wi = tid; wi * 64 < n; wi += TPB) maskT[(int64_t)wi * mask_rows + r] = 0ull;
         lds_barrier();
         continue;
@@ -590,25 +616,8 @@ void k_prep_i16(const int16_t *__restrict__ sig, int64_t stride, const int32_t *
     // ---- in-band mask: one compare per sample, the lane mask of the compare is the word -------
     const int first = sc->sel[2];
     const unsigned width = (unsigned)sc->sel[3];
-    if constexpr (LISTED) {                                // raw coordinates: one byte of each mask per 8 samples
-        unsigned char *mb = la.mask2 + (int64_t)r * la.row16 * 16;
-        for (int base = 0; base < M; base += TPB * 8) {
-            const int i0 = base + tid * 8;
-            if (i0 < M) {
-                unsigned q[4];
-                load8(row, M, i0, q);
-                unsigned in8 = 0, kp8 = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int x = sample(q, k);
-                    const bool kept = i0 + k < M && x > lo && x < hi;
-                    kp8 |= (kept ? 1u : 0u) << k;
-                    in8 |= ((kept && (unsigned)(x - first) < width) ? 1u : 0u) << k;
-                }
-                mb[(i0 >> 6) * 16 + ((i0 & 63) >> 3)] = (unsigned char)in8;
-                mb[(i0 >> 6) * 16 + 8 + ((i0 & 63) >> 3)] = (unsigned char)kp8;
-            }
-        }
+    if (mode == SK_PREP_SEGMENT) {
+        put_mask2(r, row, M, first, width);
         lds_barrier();                                     // LDS is reused by the next read
         continue;
     }
@@ -932,15 +941,17 @@ __device__ double median_select(int n, Scratch *sc, unsigned *hist256, unsigned 
 }
 
 // LISTED: the reads are list[0 .. *count) -- the streaming float64 kernel's uncertified reads (sk_f64stat.hip).
-// Segmenter mode then compacts into one scratch row per workgroup and writes the masks as {in band, kept} bytes
-// in RAW sample coordinates into that path's per-read entries; medmad mode writes comp / prep as usual.
+// Segmenter mode then compacts into one scratch row per workgroup; medmad mode writes comp / prep as usual.
+// Segmenter mode, listed or not, writes the masks as {in band, kept} bytes in RAW sample coordinates, row16 16-byte
+// entries per read (the layout the segmenter's walk reads).
 struct ListedF64 {
     const int32_t *list;
     const int32_t *count;
     unsigned char *mask2;
     int            row16;
-    int64_t        scratch_stride;      // doubles per scratch row (segmenter mode)
+    int64_t        scratch_stride;      // doubles per scratch row (listed segmenter mode)
     const int32_t *len;                 // optional: read r is its first len[r] samples
+    int32_t       *len_out;             // optional: gets read r's raw length (what the walk takes)
 };
 
 struct PrepF64Shared {
@@ -967,28 +978,52 @@ struct RowPA {
     }
 };
 
-template <bool LISTED, typename Row>
+template <typename Row>
 __device__ void prep_f64_core(PrepF64Shared *sh, int r, const Row row, int M, double *__restrict__ crow,
                               double lo, double hi, int mode, double std_scale, sk_prep *__restrict__ prep,
-                              uint64_t *__restrict__ maskT, int64_t mask_rows, const ListedF64 &la);
+                              const ListedF64 &la);
 
 template <bool LISTED>
 __device__ void prep_f64_read(PrepF64Shared *sh, int r, const double *__restrict__ sig, const int64_t *__restrict__ off,
                               double lo, double hi, int mode, double std_scale,
-                              double *__restrict__ comp, sk_prep *__restrict__ prep,
-                              uint64_t *__restrict__ maskT, int64_t mask_rows, const ListedF64 &la)
+                              double *__restrict__ comp, sk_prep *__restrict__ prep, const ListedF64 &la)
 {
     const int64_t o0 = off[r];
     int M = (int)(off[r + 1] - o0);
     if (la.len) M = min(M, max(la.len[r], 0));
+    if (la.len_out && threadIdx.x == 0) la.len_out[r] = M;
     double *crow = (LISTED && mode == SK_PREP_SEGMENT) ? comp + (int64_t)blockIdx.x * la.scratch_stride : comp + o0;
-    prep_f64_core<LISTED>(sh, r, RowF64{sig + o0}, M, crow, lo, hi, mode, std_scale, prep, maskT, mask_rows, la);
+    prep_f64_core(sh, r, RowF64{sig + o0}, M, crow, lo, hi, mode, std_scale, prep, la);
 }
 
-template <bool LISTED, typename Row>
+// SEGMENT mode's mask, one byte of each per 8 samples: every entry [0, ceil(M / 64)) in full, the groups past M too
+// (nothing kept there) -- the buffer is reused across calls and the walk reads whole entries
+template <typename Row>
+__device__ void put_mask2_f64(const ListedF64 &la, int r, const Row row, int M, double lo, double hi, double top, double bot)
+{
+    unsigned char *mb = la.mask2 + (int64_t)r * la.row16 * 16;
+    const int Me = (M + 63) & ~63;
+    for (int base = 0; base < Me; base += TPB * 8) {
+        const int i0 = base + (int)threadIdx.x * 8;
+        if (i0 < Me) {
+            unsigned in8 = 0, kp8 = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const double a = (i0 + k < M) ? row[i0 + k] : 0.0;
+                const bool kept = i0 + k < M && a > lo && a < hi;
+                kp8 |= (kept ? 1u : 0u) << k;
+                in8 |= ((kept && a < top && a > bot) ? 1u : 0u) << k;
+            }
+            mb[(i0 >> 6) * 16 + ((i0 & 63) >> 3)] = (unsigned char)in8;
+            mb[(i0 >> 6) * 16 + 8 + ((i0 & 63) >> 3)] = (unsigned char)kp8;
+        }
+    }
+}
+
+template <typename Row>
 __device__ void prep_f64_core(PrepF64Shared *sh, int r, const Row row, int M, double *__restrict__ crow,
                               double lo, double hi, int mode, double std_scale, sk_prep *__restrict__ prep,
-                              uint64_t *__restrict__ maskT, int64_t mask_rows, const ListedF64 &la)
+                              const ListedF64 &la)
 {
     Scratch *sc = &sh->sc;
     unsigned *hist256 = sh->hist256;
@@ -1044,6 +1079,7 @@ __device__ void prep_f64_core(PrepF64Shared *sh, int r, const Row row, int M, do
         const double qnan = __builtin_nan("");
         pr.center = qnan; pr.scale = qnan; pr.top = qnan; pr.bot = qnan;
         if (tid == 0) prep[r] = pr;
+        if (mode == SK_PREP_SEGMENT) put_mask2_f64(la, r, row, M, lo, hi, qnan, qnan);
         return;
     }
     block_minmax_u64(kmin, kmax, mm);
@@ -1102,53 +1138,24 @@ __device__ void prep_f64_core(PrepF64Shared *sh, int r, const Row row, int M, do
     const double bot = median - spread;
     pr.center = median; pr.scale = sd; pr.top = top; pr.bot = bot;
     if (tid == 0) prep[r] = pr;
-    if constexpr (LISTED) {                                // raw coordinates: one byte of each mask per 8 samples
-        unsigned char *mb = la.mask2 + (int64_t)r * la.row16 * 16;
-        for (int base = 0; base < M; base += TPB * 8) {
-            const int i0 = base + tid * 8;
-            if (i0 < M) {
-                unsigned in8 = 0, kp8 = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const double a = (i0 + k < M) ? row[i0 + k] : 0.0;
-                    const bool kept = i0 + k < M && a > lo && a < hi;
-                    kp8 |= (kept ? 1u : 0u) << k;
-                    in8 |= ((kept && a < top && a > bot) ? 1u : 0u) << k;
-                }
-                mb[(i0 >> 6) * 16 + ((i0 & 63) >> 3)] = (unsigned char)in8;
-                mb[(i0 >> 6) * 16 + 8 + ((i0 & 63) >> 3)] = (unsigned char)kp8;
-            }
-        }
-        return;
-    }
-    for (int base = 0; base < n; base += TPB) {
-        const int i = base + tid;
-        bool in = false;
-        if (i < n) {
-            const double a = crow[i];
-            in = (a < top) && (a > bot);
-        }
-        const unsigned long long bits = __ballot(in);
-        if (lane == 0) maskT[(int64_t)(i >> 6) * mask_rows + r] = bits;
-    }
+    put_mask2_f64(la, r, row, M, lo, hi, top, bot);
 }
 
 template <bool LISTED>
 __global__ __launch_bounds__(TPB)
 void k_prep_f64(const double *__restrict__ sig, const int64_t *__restrict__ off, int nreads,
                 double lo, double hi, int mode, double std_scale,
-                double *__restrict__ comp, sk_prep *__restrict__ prep,
-                uint64_t *__restrict__ maskT, int64_t mask_rows, ListedF64 la)
+                double *__restrict__ comp, sk_prep *__restrict__ prep, ListedF64 la)
 {
     __shared__ PrepF64Shared sh;
     if constexpr (LISTED) {
         const int cnt = *la.count;
         for (int k = blockIdx.x; k < cnt; k += gridDim.x) {
             __syncthreads();                               // the previous read is done with the shared scratch
-            prep_f64_read<true>(&sh, la.list[k], sig, off, lo, hi, mode, std_scale, comp, prep, maskT, mask_rows, la);
+            prep_f64_read<true>(&sh, la.list[k], sig, off, lo, hi, mode, std_scale, comp, prep, la);
         }
     } else {
-        prep_f64_read<false>(&sh, blockIdx.x, sig, off, lo, hi, mode, std_scale, comp, prep, maskT, mask_rows, la);
+        prep_f64_read<false>(&sh, blockIdx.x, sig, off, lo, hi, mode, std_scale, comp, prep, la);
     }
 }
 
@@ -1166,9 +1173,8 @@ void k_prep_pa_listed(const int16_t *__restrict__ sig, int64_t stride, const int
         __syncthreads();                                   // the previous read is done with the shared scratch
         const int r = la.list[k];
         const int M = (int)min((int64_t)max(len[r], 0), stride);
-        prep_f64_core<true>(&sh, r, RowPA{sig + (int64_t)r * stride, cal[2 * r], cal[2 * r + 1]}, M,
-                            scratch + (int64_t)blockIdx.x * la.scratch_stride, lo, hi, SK_PREP_SEGMENT, std_scale, prep,
-                            (uint64_t *)nullptr, (int64_t)0, la);
+        prep_f64_core(&sh, r, RowPA{sig + (int64_t)r * stride, cal[2 * r], cal[2 * r + 1]}, M,
+                      scratch + (int64_t)blockIdx.x * la.scratch_stride, lo, hi, SK_PREP_SEGMENT, std_scale, prep, la);
     }
 }
 
@@ -1908,6 +1914,8 @@ int sk_launch_prep_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const in
     const bool windowed = t0 > 0 || t1 < 0x7fffffff;
     if (listed && (windowed || mode != SK_PREP_SEGMENT || (!ldscomp && d_comp == nullptr)))
         return sk_fail(SK_ERR_INVALID, "internal: listed prep is the segmenter variant (scratch rows for long reads)");
+    if (mode == SK_PREP_SEGMENT && d_mask2 == nullptr)
+        return sk_fail(SK_ERR_INVALID, "internal: segmenter prep without masks");
     auto fn = listed ? (ldscomp ? k_prep_i16<true, false, false, true> : k_prep_i16<false, false, false, true>)
               : (mode == SK_PREP_MEDMAD) ? k_prep_i16<false, false, true>
               : ldscomp ? (windowed ? k_prep_i16<true, true, false> : k_prep_i16<true, false, false>)
@@ -1934,13 +1942,17 @@ int sk_launch_prep_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const in
 
 int sk_launch_prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads,
                        double lo, double hi, int mode, double std_scale,
-                       double *d_comp, sk_prep *d_prep, uint64_t *d_mask, int64_t mask_rows, const int32_t *d_rlen)
+                       double *d_comp, sk_prep *d_prep, void *d_mask2, int row16, int32_t *d_len_out,
+                       const int32_t *d_rlen)
 {
     if (nreads <= 0) return SK_OK;
+    if (mode == SK_PREP_SEGMENT && (d_mask2 == nullptr || d_len_out == nullptr))
+        return sk_fail(SK_ERR_INVALID, "internal: segmenter prep without masks / lengths");
     ListedF64 la;
-    la.list = nullptr; la.count = nullptr; la.mask2 = nullptr; la.row16 = 0; la.scratch_stride = 0; la.len = d_rlen;
+    la.list = nullptr; la.count = nullptr; la.mask2 = (unsigned char *)d_mask2; la.row16 = row16; la.scratch_stride = 0;
+    la.len = d_rlen; la.len_out = d_len_out;
     hipLaunchKernelGGL(k_prep_f64<false>, dim3(nreads), dim3(TPB), 0, c->stream, d_sig, d_off, nreads, lo, hi, mode,
-                       std_scale, d_comp, d_prep, d_mask, mask_rows, la);
+                       std_scale, d_comp, d_prep, la);
     SK_HIP(hipGetLastError());
     return SK_OK;
 }
@@ -1954,7 +1966,7 @@ int sk_launch_prep_pa_listed(sk_ctx *c, const int16_t *d_sig, int64_t stride, co
     if (grid <= 0) return SK_OK;
     ListedF64 la;
     la.list = d_list; la.count = d_count; la.mask2 = (unsigned char *)d_mask2; la.row16 = row16;
-    la.scratch_stride = scratch_stride; la.len = nullptr;
+    la.scratch_stride = scratch_stride; la.len = nullptr; la.len_out = nullptr;
     hipLaunchKernelGGL(k_prep_pa_listed, dim3(grid), dim3(TPB), 0, c->stream, d_sig, stride, d_len, d_cal, lo, hi, std_scale,
                        d_scratch, d_prep, la);
     SK_HIP(hipGetLastError());
@@ -1972,9 +1984,9 @@ int sk_launch_prep_f64_listed(sk_ctx *c, const double *d_sig, const int64_t *d_o
     if (grid <= 0) return SK_OK;
     ListedF64 la;
     la.list = d_list; la.count = d_count; la.mask2 = (unsigned char *)d_mask2; la.row16 = row16;
-    la.scratch_stride = scratch_stride; la.len = d_rlen;
+    la.scratch_stride = scratch_stride; la.len = d_rlen; la.len_out = nullptr;
     hipLaunchKernelGGL(k_prep_f64<true>, dim3(grid), dim3(TPB), 0, c->stream, d_sig, d_off, 0, lo, hi, mode,
-                       std_scale, d_comp_or_scratch, d_prep, (uint64_t *)nullptr, (int64_t)0, la);
+                       std_scale, d_comp_or_scratch, d_prep, la);
     SK_HIP(hipGetLastError());
     return SK_OK;
 }

@@ -106,7 +106,6 @@ static const sk_tunable SK_TUNABLES[] = {
     {"SK_SEG_WG_ALL",         "1",           "segmenter: the workgroup-per-read statistics kernel for every row of 4 097 .. 65 536 samples (default: where it is faster)"},
     {"SK_SEG_OCC",            "7 8",         "segmenter statistics kernel: waves per SIMD the registers are sized for"},
     {"SK_SEG_CHUNKS",         "2 8",         "segmenter: chunks of a large batch (walk of one beside the statistics of the next)"},
-    {"SK_WALK_STEP",          "1",           "segmenter walk: per-sample straight-line step instead of run hopping"},
     {"SK_WALK_GENERAL",       "1",           "segmenter walk: general step (corrector test live)"},
     {"SK_WALK_SYNC",          "1",           "segmenter walk: run hopping with the 64 lanes of a wavefront on the same word (k_seg_walk3)"},
     {"SK_WALK_OWNPASS",       "1",           "segmenter walk: finds the quiet stretches and anchors in a pass of its own instead of taking the statistics kernel's hints"},

@@ -4,7 +4,7 @@
 //   scale_outliers      :311-318     strict lo < x < hi
 //   np.median, np.std   :410, :412   -> top / bot (:413-414)
 //   a < top and a > bot :431         one bit per sample
-// and hands the walk kernel (k_seg_walk2 below, the state machine of :420-464) two bit masks per read in RAW
+// and hands the walk kernels (k_seg_walk2/3/4/L below, the state machine of :420-464) two bit masks per read in RAW
 // sample coordinates: "in band" and "kept by the filter".  The walk deletes the dropped samples' bits on the
 // fly, so nothing in here needs an order-preserving compaction.
 //
@@ -18,7 +18,7 @@
 //     |top_numpy - top_here| <= delta := 8 eps (|spread| (n + 16) + |median| + |spread|)   (8x headroom).
 //   * if no integer lies within delta of top (resp. bot), ceil(top) (floor(bot)) is numpy's.  CERTIFIED.
 //     Otherwise (probability ~1e-10 per read) the read goes to a retry list and is redone by the
-//     numpy-order kernel (k_prep_i16 + k_segment_walk over the listed reads only).
+//     numpy-order kernel (k_prep_i16 over the listed reads only, which rewrites their masks in place).
 // One wavefront owns one read from its first load to its last store: the whole read (<= 4096 samples) sits in
 // 32 VGPRs as packed int16 pairs, all loads are issued up front, no workgroup barrier anywhere, 32 reads in
 // flight per CU.  LDS: one value histogram per wave (median by rank select from registers, as k_prepw_medmad).
@@ -881,44 +881,6 @@ __device__ __forceinline__ void report_segment(WalkState &st, int start, int end
     st.last_end = end;
 }
 
-__device__ __forceinline__ unsigned mad24(unsigned a, unsigned b, unsigned c)
-{
-    unsigned r;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ unsigned mul24(unsigned a, unsigned b)
-{
-    unsigned r;
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// 32 samples, all valid, corrector test dead (error < corrector): the straight-line step of sk_segment.hip
-__device__ __forceinline__ void walk_fast32(WalkState &st, unsigned bits, int i0, const WalkParams &p,
-                                            int thr_first, int32_t *my, int max_segs)
-{
-    unsigned prev = (unsigned)st.prev, err = (unsigned)st.err, perr = (unsigned)st.prev_err, c = (unsigned)st.c;
-    unsigned thr = (st.nseg == 0) ? (unsigned)thr_first : (unsigned)p.window;
-#pragma unroll 16
-    for (int b = 0; b < 32; b++) {
-        const unsigned inb = (bits >> b) & 1u;                                     // :431 in band
-        const unsigned ltm = (unsigned)(((int)err - p.error) >> 31);               // all ones: err < error
-        const unsigned tol = prev & ~inb & ltm;                                    // :442 tolerated
-        const unsigned closing = prev & ~inb & ~ltm;                               // :448 / :458
-        const unsigned act = inb | tol;
-        if (mul24(closing, c) >= thr) {                                            // thr >= 1
-            report_segment(st, i0 + b - (int)c, i0 + b - (int)perr, p, my, max_segs);   // :449
-            thr = (unsigned)p.window;
-        }
-        c = mad24(c, act, act);
-        err = mad24(err, act, tol);
-        perr = mad24(perr, tol, tol);
-        prev = act;
-    }
-    st.prev = (int)prev; st.err = (int)err; st.prev_err = (int)perr; st.c = (int)c;
-}
-
 // general step: any parameters, samples at index >= n ignored; keeps `start` and `w`
 __device__ __forceinline__ void walk_general32(WalkState &st, unsigned bits, int i0, int n, const WalkParams &p,
                                                int32_t *my, int max_segs)
@@ -947,11 +909,12 @@ __device__ __forceinline__ void walk_general32(WalkState &st, unsigned bits, int
     st.prev = prev; st.err = err; st.prev_err = prev_err; st.c = c; st.w = w; st.start = start;
 }
 
-// FAST: error < corrector (the corrector test can never fire, see sk_segment.hip) and positive thresholds.
+// Any parameters.  With error < corrector (the defaults included) the corrector test of segmenter.py:439/446 can
+// never fire -- c <= (in-band samples of this segment) + err and w = corrector + (all in-band samples so far), so
+// c >= w needs err >= corrector -- and the run-hopping walks below take those calls (positive thresholds too).
 // Each lane streams its read's entries; the kept bits of an entry are squeezed together (the filter drops a
 // handful of samples per read, so the squeeze loop runs a few times per READ) and appended to a bit queue;
 // whenever the queue holds 64 bits they go through the state machine.
-template <bool FAST>
 __global__ __launch_bounds__(64)
 void k_seg_walk2(const uint4 *__restrict__ mask2, int row16, const int32_t *__restrict__ len, int64_t stride,
                  int nreads, WalkParams p, int32_t *__restrict__ segs, int32_t *__restrict__ nsegs, int max_segs)
@@ -964,9 +927,8 @@ void k_seg_walk2(const uint4 *__restrict__ mask2, int row16, const int32_t *__re
 
     WalkState st;
     st.prev = 0; st.err = 0; st.prev_err = 0; st.c = 0;
-    st.w = FAST ? 0x7fffffff : p.corrector;       // segmenter.py:424 -- never reset inside a read
+    st.w = p.corrector;                           // segmenter.py:424 -- never reset inside a read
     st.start = 0; st.nseg = 0; st.last_end = 0;
-    const int thr_first = min(p.window, p.first_len);
 
     const int nent = (M + 63) >> 6;               // my entries
     int nmax = nent;
@@ -1000,19 +962,13 @@ void k_seg_walk2(const uint4 *__restrict__ mask2, int row16, const int32_t *__re
             fill += cnt;
         }
         if (fill >= 64) {
-            if (FAST) {
-                walk_fast32(st, (unsigned)qlo, done, p, thr_first, my, max_segs);
-                walk_fast32(st, (unsigned)(qlo >> 32), done + 32, p, thr_first, my, max_segs);
-            } else {
-                walk_general32(st, (unsigned)qlo, done, 0x7fffffff, p, my, max_segs);
-                walk_general32(st, (unsigned)(qlo >> 32), done + 32, 0x7fffffff, p, my, max_segs);
-            }
+            walk_general32(st, (unsigned)qlo, done, 0x7fffffff, p, my, max_segs);
+            walk_general32(st, (unsigned)(qlo >> 32), done + 32, 0x7fffffff, p, my, max_segs);
             done += 64; fill -= 64;
             qlo = qhi; qhi = 0ull;
         }
     }
     // the last fill (< 64) bits
-    if (FAST) st.start = done - st.c;             // hand over to the general step (which tracks `start`)
     if (fill > 0) {
         const int n = done + fill;
         walk_general32(st, (unsigned)qlo, done, n, p, my, max_segs);
@@ -1022,7 +978,7 @@ void k_seg_walk2(const uint4 *__restrict__ mask2, int row16, const int32_t *__re
 }
 
 // ------------------------------------------------------------------------------------------------------
-// the same walk by RUNS instead of by samples (error < corrector, positive thresholds: what k_seg_walk2<true> covers)
+// the same walk by RUNS instead of by samples (error < corrector, positive thresholds)
 // ------------------------------------------------------------------------------------------------------
 // With the corrector test dead, get_segs' per-sample state has a closed form.  A candidate segment ("run") opens at
 // an in-band sample s; every in-band sample and the first E = max(error, 0) out-of-band ones extend it (:431-447);
@@ -1581,14 +1537,14 @@ void k_seg_walkL(const uint4 *__restrict__ mask2, int row16, const int32_t *__re
 }
 
 // k_seg_walk4's preconditions (else: k_seg_walk3 / k_seg_walk2)
-bool walk_jumps_apply(const WalkParams &wp, bool fast, bool by_runs, int row16)
+bool walk_jumps_apply(const WalkParams &wp, bool fast, int row16)
 {
-    return fast && by_runs && wp.error < 32 && wp.window >= 127 && (int64_t)row16 * 64 <= 65536 &&
+    return fast && wp.error < 32 && wp.window >= 127 && (int64_t)row16 * 64 <= 65536 &&
            sk_tune("SK_WALK_SYNC") == nullptr;
 }
 
 void launch_walk(hipStream_t ws, const uint4 *mask2, int row16, const int32_t *len, int64_t stride, int nr,
-                 const WalkParams &wp, bool fast, bool by_runs, int32_t *d_segs, int32_t *d_nsegs, int max_segs,
+                 const WalkParams &wp, bool fast, int32_t *d_segs, int32_t *d_nsegs, int max_segs,
                  const unsigned *d_hints = nullptr)
 {
     const int wgrid = (nr + 63) / 64;
@@ -1599,7 +1555,7 @@ void launch_walk(hipStream_t ws, const uint4 *mask2, int row16, const int32_t *l
     // with the batch, the lane-per-read one by one lane's latency chain and barely does)
     int long_max = row16 > 64 ? 131072 : 16384;
     if (const char *e = sk_tune("SK_WALK_WAVE_MAXREADS")) long_max = atoi(e);
-    if (fast && by_runs && wp.error < 32 && nr <= long_max && nr > 0 &&
+    if (fast && wp.error < 32 && nr <= long_max && nr > 0 &&
         sk_tune("SK_WALK_NOWAVE") == nullptr && sk_tune("SK_WALK_SYNC") == nullptr) {
         // rows of up to 1 024 entries are staged in LDS; longer rows (only some of whose reads may fit) read global memory
         const bool staged = row16 <= 1024;
@@ -1611,22 +1567,19 @@ void launch_walk(hipStream_t ws, const uint4 *mask2, int row16, const int32_t *l
                            lds_entries);
         return;
     }
-    if (walk_jumps_apply(wp, fast, by_runs, row16)) {
+    if (walk_jumps_apply(wp, fast, row16)) {
         const int use_jumps = sk_tune("SK_WALK_NOJUMP") == nullptr;
         const unsigned *h = use_jumps ? d_hints : nullptr;
         auto fn = wp.error == 5 ? (h ? k_seg_walk4<6, true> : k_seg_walk4<6, false>)
                                 : (h ? k_seg_walk4<0, true> : k_seg_walk4<0, false>);
         hipLaunchKernelGGL(fn, dim3(wgrid), dim3(64), 0, ws, mask2, row16, len, stride, nr, wp, d_segs, d_nsegs, max_segs,
                            use_jumps, h);
-    } else if (fast && by_runs)
+    } else if (fast)
         hipLaunchKernelGGL(k_seg_walk3, dim3(wgrid), dim3(64), 0, ws, mask2, row16, len, stride, nr, wp, d_segs, d_nsegs,
                            max_segs);
-    else if (fast)
-        hipLaunchKernelGGL(k_seg_walk2<true>, dim3(wgrid), dim3(64), 0, ws, mask2, row16, len, stride, nr, wp, d_segs,
-                           d_nsegs, max_segs);
     else
-        hipLaunchKernelGGL(k_seg_walk2<false>, dim3(wgrid), dim3(64), 0, ws, mask2, row16, len, stride, nr, wp, d_segs,
-                           d_nsegs, max_segs);
+        hipLaunchKernelGGL(k_seg_walk2, dim3(wgrid), dim3(64), 0, ws, mask2, row16, len, stride, nr, wp, d_segs, d_nsegs,
+                           max_segs);
 }
 
 WalkParams walk_params(const sk_seg_params *p, bool *fast)
@@ -1712,7 +1665,7 @@ bool sk_segment_pa_applies(const void *d_sig, int64_t stride, double std_scale)
     return true;
 }
 
-// Is (stride, limits, std_scale) inside the streaming path's range?  (else: k_prep_i16 + k_segment_walk)
+// Is (stride, limits, std_scale) inside the streaming path's range?  (else: k_prep_i16 for every read, the same walk)
 bool sk_segment_fast_applies(const void *d_sig, int64_t stride, int32_t lo, int32_t hi, double std_scale)
 {
     if (sk_tune("SK_SEG_OLD")) return false;                 // A/B switch: the numpy-order kernels for everything
@@ -1746,7 +1699,6 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     bool fast;
     const WalkParams wp = walk_params(p, &fast);
 
-    const bool by_runs = sk_tune("SK_WALK_STEP") == nullptr;       // A/B switch: the per-sample straight-line walk
     // Large batches go in four chunks, the walk of one on a second stream beside the statistics of the next -- which
     // only pays when the persistent statistics grid leaves the walk's waves room on the SIMDs: at its full six
     // workgroups per CU (78 VGPRs x 24 waves) nothing else fits and the overlap gained nothing (round 2: 3.35 / 3.33 /
@@ -1754,7 +1706,7 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     // co-limited by HBM) and the step drops from 2.89 to 2.70 ms per 1 M reads (round 3, same box).
     // (round 4) k_seg_walk4 takes a fifth of the statistics kernel's time and gains nothing beside it (1 / 2 / 3 / 4 / 6
     // chunks: 2.53 / 2.56 / 2.57 / 2.58 / 2.60 ms per 1 M reads): one chunk; the older walks keep the four.
-    int nchunks = nreads >= 262144 && !walk_jumps_apply(wp, fast, by_runs, a.row16) ? 4 : 1;
+    int nchunks = nreads >= 262144 && !walk_jumps_apply(wp, fast, a.row16) ? 4 : 1;
     if (const char *e = sk_tune("SK_SEG_CHUNKS")) { int v = atoi(e); if (v >= 1 && v <= 8) nchunks = v; }
     if (nreads < 65536) nchunks = 1;
     if (nchunks > 1) { int rc = sk_second_stream(c); if (rc) return rc; }
@@ -1764,7 +1716,7 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
 
     // the walk's hints come out of the statistics kernel (reads of up to 4 096 samples, the jumping walk)
     a.hints = nullptr; a.e1 = (p->error > 0 ? p->error : 0) + 1;
-    if (walk_jumps_apply(wp, fast, by_runs, a.row16) && stride <= 4096 && sk_tune("SK_WALK_OWNPASS") == nullptr) {
+    if (walk_jumps_apply(wp, fast, a.row16) && stride <= 4096 && sk_tune("SK_WALK_OWNPASS") == nullptr) {
         if (int rch = sk_reserve(c, &c->seghints, (size_t)nreads * SEG_HINTS * sizeof(unsigned))) return rch;
         a.hints = (unsigned *)c->seghints.p;
     }
@@ -1826,7 +1778,7 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
             SK_HIP(hipEventRecord(c->ev[1], c->stream));
             SK_HIP(hipEventRecord(c->ev[2], c->stream));
         }
-        launch_walk(ws, (const uint4 *)a.mask2, a.row16, a.len, stride, nr, wp, fast, by_runs,
+        launch_walk(ws, (const uint4 *)a.mask2, a.row16, a.len, stride, nr, wp, fast,
                     d_segs + (int64_t)r0 * 2 * max_segs, d_nsegs + r0, max_segs, a.hints);
         SK_HIP(hipGetLastError());
     }
@@ -1840,8 +1792,8 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     return SK_OK;
 }
 
-// The walk alone, over {in band, kept} entries somebody else wrote (the float64 statistics kernel, sk_f64stat.hip):
-// read r has d_len[r] samples (clamped to 64 row16), its entries at d_mask2 + r * row16.  Records ev[2] .. ev[3].
+// The walk alone, over {in band, kept} entries somebody else wrote (the float64 statistics kernel, sk_f64stat.hip, or
+// the numpy-order kernels of sk_prep.hip): read r has d_len[r] samples (clamped to 64 row16), its entries at d_mask2 + r * row16.  Records ev[2] .. ev[3].
 int sk_launch_seg_walk_masks(sk_ctx *c, const void *d_mask2, int row16, const int32_t *d_len, int32_t nreads,
                              const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
 {
@@ -1849,8 +1801,8 @@ int sk_launch_seg_walk_masks(sk_ctx *c, const void *d_mask2, int row16, const in
     bool fast;
     const WalkParams wp = walk_params(p, &fast);
     SK_HIP(hipEventRecord(c->ev[2], c->stream));
-    launch_walk(c->stream, (const uint4 *)d_mask2, row16, d_len, (int64_t)row16 * 64, nreads, wp, fast,
-                sk_tune("SK_WALK_STEP") == nullptr, d_segs, d_nsegs, max_segs);
+    launch_walk(c->stream, (const uint4 *)d_mask2, row16, d_len, (int64_t)row16 * 64, nreads, wp, fast, d_segs, d_nsegs,
+                max_segs);
     SK_HIP(hipGetLastError());
     SK_HIP(hipEventRecord(c->ev[3], c->stream));
     return SK_OK;

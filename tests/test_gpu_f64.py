@@ -299,6 +299,27 @@ def test_f64_long_reads_segmenter_vs_oracle(gpu, ora, monkeypatch):
             assert not bad, (kw, delta, bad[:8], retried)
 
 
+def test_f64_reads_beyond_the_streaming_kernel_segmenter_vs_oracle(gpu, ora):
+    """A read longer than 2^20 samples sends the whole batch to the numpy-order kernel; its masks go through the same
+    walk as the streaming kernel's.  Defaults, and a live corrector test (error >= corrector)."""
+    from squigglekit_amd import api, synth
+    from squigglekit_amd._lib import SegParams
+    rng = np.random.default_rng(1200001)
+    reads = [synth.squiggle_batch(1, n, 17 + n)[0] + np.round(rng.random(n), 2) for n in (1200001, 1, 63, 65, 4097, 9000)]
+    reads[0][rng.integers(0, reads[0].size, 50)] = 2000.0        # outliers dropped by the filter
+    reads.append(np.full(100, 1000.0))                           # every sample dropped
+    reads.append(np.array([], dtype=np.float64))
+    for kw in (dict(), dict(error=60, corrector=50, window=100)):
+        p = SegParams(**kw)
+        op = ora.SegParams(p.error, p.corrector, p.window, p.seg_dist, p.std_scale, p.stall_len)
+        want = [ora.get_segs(f, op) if f.size else False
+                for f in (ora.scale_outliers(sig, p.lim_low, p.lim_hi) for sig in reads)]
+        got = api.segment_reads_f64(reads, p)
+        bad = [r for r in range(len(reads)) if got[r] != want[r]]
+        assert not bad, (kw, bad)
+        assert any(want), "the reads do produce segments"
+
+
 def test_f64_long_reads_medmad_vs_oracle(gpu, ora, example_model):
     from concurrent.futures import ThreadPoolExecutor
     from squigglekit_amd import api

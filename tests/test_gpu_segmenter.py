@@ -94,8 +94,8 @@ def test_vs_oracle_random_params_and_lengths(gpu, ora):
 
 
 def test_fast_and_general_walk_agree(gpu, ora, monkeypatch):
-    """The straight-line walk (error < corrector) against the general one and the oracle, with
-    ragged lengths so that the hand-over between the two step forms is exercised inside a wave."""
+    """The run-hopping walks (error < corrector) against the general per-sample one (SK_WALK_GENERAL) and the
+    oracle, with ragged lengths inside a wave."""
     from squigglekit_amd import api, synth
     rng = np.random.default_rng(99)
     sig = synth.squiggle_batch(192, 5000, 777)
@@ -181,7 +181,8 @@ STREAM_PARAMS = [dict(), dict(error=10, corrector=0), dict(error=12, corrector=3
                  dict(window=10, seg_dist=0, stall_len=0.0), dict(std_scale=3.0), dict(std_scale=-0.5),
                  dict(error=0), dict(window=1, error=0, seg_dist=1000), dict(lim_low=400, lim_hi=600),
                  dict(lim_low=-10, lim_hi=1500), dict(lim_low=499, lim_hi=502), dict(lim_low=-32769, lim_hi=-30722),
-                 dict(std_scale=1e-9), dict(std_scale=40.0), dict(stall_len=1.5), dict(lim_low=0, lim_hi=2048)]
+                 dict(std_scale=1e-9), dict(std_scale=40.0), dict(stall_len=1.5), dict(lim_low=0, lim_hi=2048),
+                 dict(lim_low=-1000, lim_hi=3000)]     # (limits too wide for the streaming kernel's histogram: numpy-order kernel)
 
 
 def test_streaming_statistics_path_vs_oracle(gpu, ora):
@@ -191,10 +192,30 @@ def test_streaming_statistics_path_vs_oracle(gpu, ora):
     for kw in STREAM_PARAMS:
         total += int(_check_vs_oracle(api, ora, sig, lens, kw, "streaming").sum())
     assert total > 2000                              # the cases do produce segments
-    # narrower rows use the 2- and 4-tile instantiations
-    for width in (8, 1000, 1024, 1032, 2048, 2056):
+    # narrower rows use the 2- and 4-tile instantiations; strides that are not a multiple of 8 the numpy-order kernel
+    for width in (8, 1000, 1001, 1024, 1032, 2048, 2056, 4001):
         _check_vs_oracle(api, ora, np.ascontiguousarray(sig[:, :width]), np.minimum(lens, width), dict(),
                          "width %d" % width)
+
+
+def test_numpy_order_route_leaves_no_stale_mask(gpu, ora):
+    """The numpy-order kernel writes every mask entry of every read in full: reads that are empty, reads whose samples
+    are all dropped and lengths that end inside an entry, right after a streaming call on longer reads has filled the
+    same (reused) mask buffer with other reads' bits."""
+    from squigglekit_amd import api, synth
+    rng = np.random.default_rng(515)
+    sig, lens = _streaming_cases(rng)
+    _check_vs_oracle(api, ora, sig, lens, dict(), "streaming first")
+    W = 1000
+    R = 200
+    small = synth.squiggle_batch(R, W, 616)
+    slen = rng.integers(1, W + 1, size=R).astype(np.int32)
+    slen[:16] = [0, 0, 1, 63, 65, 100, 127, 129, 191, 500, 513, 777, 999, W, W, 0]
+    small[16:24, :] = -2000                          # every sample dropped by lim_low = -1000
+    small[24:28, 70:] = 5000                         # all dropped after the first entry
+    for kw in (dict(lim_low=-1000, lim_hi=3000), dict(lim_low=-1000, lim_hi=3000, error=60, corrector=50)):
+        _check_vs_oracle(api, ora, small, slen, kw, "numpy-order after streaming")
+        _check_vs_oracle(api, ora, sig, lens, dict(), "streaming again")
 
 
 @pytest.mark.parametrize("M", [4096, 9000])
@@ -226,13 +247,12 @@ def test_jumping_walk_on_pattern_reads(gpu, ora, monkeypatch, M):
 def test_streaming_path_retry_list_and_old_kernels_agree(gpu, ora, monkeypatch):
     """SK_SEG_DELTA_SCALE widens the certification margin until (nearly) every read fails it, so the numpy-order
     redo of listed reads is what produces the masks; SK_SEG_OLD runs the numpy-order kernels for everything;
-    SK_WALK_STEP takes the per-sample walk instead of the run-hopping one, SK_WALK_SYNC the run-hopping walk that keeps
-    a wavefront's lanes on one word, SK_WALK_NOJUMP the default walk without its jumps; SK_SEG_CHUNKS overlaps walk and
+    SK_WALK_SYNC the run-hopping walk that keeps a wavefront's lanes on one word, SK_WALK_NOJUMP the default walk without its jumps; SK_SEG_CHUNKS overlaps walk and
     statistics on two streams.  All must give the oracle's segments."""
     from squigglekit_amd import api
     sig, lens = _streaming_cases(np.random.default_rng(7))
     for env, val in (("SK_SEG_DELTA_SCALE", "1e13"), ("SK_SEG_DELTA_SCALE", "3e10"), ("SK_SEG_OLD", "1"),
-                     ("SK_WALK_STEP", "1"), ("SK_WALK_SYNC", "1"), ("SK_WALK_NOJUMP", "1"), ("SK_SEG_CHUNKS", "3")):
+                     ("SK_WALK_SYNC", "1"), ("SK_WALK_NOJUMP", "1"), ("SK_SEG_CHUNKS", "3")):
         monkeypatch.setenv(env, val)
         for kw in STREAM_PARAMS[:9]:
             _check_vs_oracle(api, ora, sig, lens, kw, "%s=%s" % (env, val))

@@ -158,7 +158,7 @@ def test_jumping_walk_model_equals_get_segs(ora, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# k_drna_walk_runs (csrc/sk_segment.hip): the dRNA slow5-branch scan by pieces, trip for trip as the kernel takes them
+# k_drna_walk_runs (csrc/sk_drna_walk.hip): the dRNA slow5-branch scan by pieces, trip for trip as the kernel takes them
 # ---------------------------------------------------------------------------------------------------------------
 def _drna_pieces(mask, error, no_err_thresh, w, window, seg_dist):
     """The kernel's loop on a Python bool mask (True = a < top): 64-sample windows at the lane's own position, a piece cut
