@@ -443,6 +443,31 @@ int sk_synth_variant_dev(int16_t *d_sig, int64_t stride, int32_t nreads, int32_t
 int sk_synth_pa_dev(const int16_t *d_raw, int64_t stride, int32_t nreads, int32_t nsamples,
                     double offset, double range, double digitisation, double *d_out, int64_t *d_off);
 
+/* ---- SquigglePull text (SquigglePull.py) ------------------------------- */
+/* Replaces, per read, SquigglePull's sample loop (SquigglePull.py:178-179, 211-212), its pA conversion
+ * (convert_to_pA_numpy + np.round(.., 2), :185-189, 218-222, 238-240) and print_data (:243-253): the lines
+ *     prefix[r] + tok(s0) + '\t' + ... + tok(s_{n-1}) + '\n'          (an empty read: prefix[r] + '\n')
+ * in read order, made on the device.  prefix[r] = prefix[prefix_off[r] .. prefix_off[r+1]) is everything before the
+ * first sample, trailing tab included (file name, read id, the -i columns), built by the caller.
+ *   SK_PULL_RAW : tok = str(int(sample))
+ *   SK_PULL_PA  : tok = str(np.round((sample + offset) * raw_unit, 2)) byte for byte: the integer
+ *                 k = rint(((sample + offset) * raw_unit) * 100) printed with two decimals, a trailing zero dropped,
+ *                 "-0.0" for a negative zero; raw_unit = float("%.2f" % range) / digitisation.
+ * The host form takes calib[3 r ..] = digitisation, offset, range (what a fast5 / BLOW5 record carries; NULL in raw
+ * mode), rows of `stride` samples with len[r] in [0, stride], and writes the text to `text` (capacity bytes) and
+ * nreads + 1 line offsets to line_off (may be NULL; line_off[nreads] = *total).  *total always gets the text's size:
+ * SK_ERR_OVERFLOW when it exceeds `capacity`, and then nothing is written to `text`.  SK_ERR_UNSUPPORTED: some pA
+ * value is not finite or has |k| >= 1e15 (numpy would print it in another notation).
+ * The _dev form: device pointers but `total` (host); d_cal2 = {offset, raw_unit} per read as sk_pa_calib makes them
+ * (NULL in raw mode), d_line_off: nreads + 1 entries; len[r] is clamped into [0, stride]. */
+typedef enum sk_pull_mode { SK_PULL_RAW = 0, SK_PULL_PA = 1 } sk_pull_mode;
+int sk_pull_text(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *calib, int32_t mode,
+                 const char *prefix, const int64_t *prefix_off, char *text, int64_t capacity, int64_t *total,
+                 int64_t *line_off);
+int sk_pull_text_dev(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
+                     int32_t mode, const char *d_prefix, const int64_t *d_prefix_off, char *d_text, int64_t capacity,
+                     int64_t *total, int64_t *d_line_off);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ class SquiggleKitError(RuntimeError):
 # sk_status (include/squigglekit_hip.h)
 SK_OK, SK_ERR_INVALID, SK_ERR_NO_DEVICE, SK_ERR_HIP, SK_ERR_NOMEM, SK_ERR_UNSUPPORTED, SK_ERR_OVERFLOW = 0, -1, -2, -3, -4, -5, -6
 SK_SCALE = {"medmad": 0, "zscale": 1}
+SK_PULL_RAW, SK_PULL_PA = 0, 1
 SK_FLAG_EMPTY, SK_FLAG_DEGENERATE, SK_FLAG_RECENTRE = 1, 2, 4
 
 
@@ -178,6 +179,8 @@ ABI = {
     "sk_synth_squiggles_dev": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _vp, C.c_int32]),
     "sk_synth_variant_dev": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _vp, C.c_int32, _vp]),
     "sk_synth_pa_dev": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "sk_pull_text": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _i64p, _vp]),
+    "sk_pull_text_dev": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _i64p, _vp]),
 }
 
 

@@ -259,6 +259,54 @@ def segment_batch_pa(sig, lens, calib, params=None, max_segs=64, devices=None):
         return segs[:R], nsegs[:R]
 
 
+def pack_prefixes(prefixes):
+    """A list of bytes -> (blob, int64 offsets [n + 1]) for pull_text; a (blob, offsets) pair passes through."""
+    if isinstance(prefixes, tuple):
+        blob, off = prefixes
+        return blob, np.ascontiguousarray(off, dtype=np.int64)
+    off = np.zeros(len(prefixes) + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in prefixes], out=off[1:])
+    return b"".join(prefixes), off
+
+
+def pull_text(rows, lens, prefixes, calib=None, raw=False, out=None):
+    """SquigglePull's lines for int16 rows, made on the GPU (sk_pull_text; SquigglePull.py:178-189, 211-222, 238-253):
+    read r's line is prefixes[r] + the first lens[r] samples of rows[r], tab-separated, + "\n" -- str(int(x)) with
+    raw=True, else str(np.round((x + offset) * (float("%.2f" % range) / digitisation), 2)) with calib[r] = digitisation,
+    offset, range (float64 [n, 3], as Blow5Block.calib holds them; the range is cut to two decimals on the host).
+    prefixes: a list of bytes (file name, read id, -i columns, trailing tab), or a (blob, offsets) pair.
+    Returns bytes; with `out` (a uint8 array, e.g. pinned) the text goes there and a memoryview of it comes back
+    (a larger array is made when `out` is too small)."""
+    L = _lib.ensure_init()
+    rows = np.ascontiguousarray(rows, dtype=np.int16)
+    R = rows.shape[0] if rows.ndim == 2 else 0
+    stride = max(1, rows.shape[1] if rows.ndim == 2 else 1)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    blob, poff = pack_prefixes(prefixes)
+    if len(lens) != R or len(poff) != R + 1:
+        raise ValueError("rows, lens and prefixes disagree on the number of reads")
+    mode = _lib.SK_PULL_RAW if raw else _lib.SK_PULL_PA
+    cal = None
+    if not raw and R:
+        cal = np.ascontiguousarray(calib, dtype=np.float64).reshape(R, 3)
+    pbuf = np.frombuffer(blob, dtype=np.uint8) if len(blob) else np.zeros(1, dtype=np.uint8)
+    # most tokens take at most 7 characters + separator ("-123.45\t", "-32768\t"): a retry with the exact size otherwise
+    cap = int(poff[-1] - poff[0]) + 8 * int(lens.sum()) + R + 1
+    total = C.c_int64(0)
+    while True:
+        buf = out if out is not None and out.nbytes >= cap else np.empty(cap, dtype=np.uint8)
+        rc = L.sk_pull_text(ptr(rows), stride, ptr(lens), R, None if cal is None else ptr(cal), mode, ptr(pbuf), ptr(poff),
+                            ptr(buf), buf.nbytes, C.byref(total), None)
+        if rc == _lib.SK_ERR_OVERFLOW and total.value > buf.nbytes:
+            cap = total.value
+            continue
+        check(rc)
+        break
+    if out is not None:
+        return memoryview(buf)[:total.value]
+    return buf[:total.value].tobytes()
+
+
 def last_pa_retries():
     """Reads of the most recent segment_batch_pa call on this thread's device (all its sub-batches) that took the
     numpy-order redo; -1 when the call expanded its rows to float64 instead of staying in the raw domain, or when a

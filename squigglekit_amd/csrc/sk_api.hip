@@ -1331,3 +1331,134 @@ int sk_dtw_subsequence_cref(const double *x, int32_t nx, const double *y, int32_
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ SquigglePull text (sk_pull.hip)
+namespace {
+
+struct PullScratch {
+    int32_t *err;
+    int64_t *tile0, *tb, *lines, *bsum;
+    int64_t  tile_cap;
+};
+
+int check_pull(int32_t mode, int64_t capacity, const void *text, const int64_t *total)
+{
+    if (mode != SK_PULL_RAW && mode != SK_PULL_PA) return sk_fail(SK_ERR_INVALID, "mode must be SK_PULL_RAW or SK_PULL_PA");
+    if (!total) return sk_fail(SK_ERR_INVALID, "NULL total");
+    if (capacity < 0) return sk_fail(SK_ERR_INVALID, "capacity < 0");
+    if (capacity > 0 && !text) return sk_fail(SK_ERR_INVALID, "NULL text with a capacity");
+    return SK_OK;
+}
+
+// pass 1 and the scans; *total = the text's size (synchronises), SK_ERR_UNSUPPORTED for a value the formatter cannot
+// print, SK_ERR_OVERFLOW past `capacity`
+int pull_count(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal,
+               const int64_t *d_poff, int64_t capacity, int64_t *total, PullScratch *s)
+{
+    int rc;
+    s->tile_cap = sk_pull_tile_cap(nreads, stride);
+    const int64_t nb = sk_scan_blocks(s->tile_cap > nreads ? s->tile_cap : nreads);
+    const size_t items = (size_t)(nreads + 1) * 2 + (size_t)(s->tile_cap + 1) + (size_t)nb;
+    if ((rc = sk_reserve(c, &c->pull, 16 + items * sizeof(int64_t)))) return rc;
+    s->err = (int32_t *)c->pull.p;
+    s->tile0 = (int64_t *)((char *)c->pull.p + 16);
+    s->tb = s->tile0 + nreads + 1;
+    s->lines = s->tb + s->tile_cap + 1;
+    s->bsum = s->lines + nreads + 1;
+    SK_HIP(hipMemsetAsync(s->err, 0, 16, c->stream));
+    if ((rc = sk_launch_pull_count(c, d_sig, stride, d_len, nreads, d_cal, d_poff, s->tile0, s->tb, s->tile_cap, s->bsum,
+                                   s->lines, s->err)))
+        return rc;
+    int64_t t = 0;
+    int32_t bad = 0;
+    SK_HIP(hipMemcpyAsync(&t, s->lines + nreads, sizeof t, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(&bad, s->err, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    *total = t;
+    if (bad) return sk_fail(SK_ERR_UNSUPPORTED, "a pA value is not finite or has |value| >= 1e13 (calibration out of range)");
+    if (t > capacity)
+        return sk_fail(SK_ERR_OVERFLOW, "the text needs %lld bytes, capacity is %lld", (long long)t, (long long)capacity);
+    return SK_OK;
+}
+
+} // namespace
+
+int sk_pull_text_dev(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
+                     int32_t mode, const char *d_prefix, const int64_t *d_prefix_off, char *d_text, int64_t capacity,
+                     int64_t *total, int64_t *d_line_off)
+{
+    SK_ENTER(c);
+    int rc = check_pull(mode, capacity, d_text, total);
+    if (!rc) rc = check_i16(d_sig, stride, d_len, nreads);
+    if (!rc && nreads && (!d_prefix || !d_prefix_off || !d_line_off)) rc = sk_fail(SK_ERR_INVALID, "NULL prefix / prefix_off / line_off");
+    if (!rc && nreads && mode == SK_PULL_PA && !d_cal2) rc = sk_fail(SK_ERR_INVALID, "NULL cal2 in pA mode");
+    if (rc) return rc;
+    *total = 0;
+    if (nreads == 0) {
+        if (d_line_off) SK_HIP(hipMemsetAsync(d_line_off, 0, sizeof(int64_t), c->stream));
+        return SK_OK;
+    }
+    const double *cal = mode == SK_PULL_PA ? d_cal2 : nullptr;
+    PullScratch s;
+    if ((rc = pull_count(c, d_sig, stride, d_len, nreads, cal, d_prefix_off, capacity, total, &s))) return rc;
+    if ((rc = sk_launch_pull_write(c, d_sig, stride, d_len, nreads, cal, d_prefix, d_prefix_off, s.tile0, s.tb, s.tile_cap,
+                                   s.lines, d_text)))
+        return rc;
+    SK_HIP(hipMemcpyAsync(d_line_off, s.lines, (size_t)(nreads + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
+    return SK_OK;
+}
+
+int sk_pull_text(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *calib, int32_t mode,
+                 const char *prefix, const int64_t *prefix_off, char *text, int64_t capacity, int64_t *total,
+                 int64_t *line_off)
+{
+    SK_ENTER(c);
+    int rc = check_pull(mode, capacity, text, total);
+    if (!rc) rc = check_i16(sig, stride, len, nreads);
+    if (!rc) rc = check_len_host(len, nreads, stride);
+    if (!rc && nreads && !prefix_off) rc = sk_fail(SK_ERR_INVALID, "NULL prefix_off");
+    if (!rc && nreads && mode == SK_PULL_PA && !calib) rc = sk_fail(SK_ERR_INVALID, "NULL calib in pA mode");
+    if (rc) return rc;
+    *total = 0;
+    if (nreads == 0) {
+        if (line_off) line_off[0] = 0;
+        return SK_OK;
+    }
+    if (prefix_off[0] < 0) return sk_fail(SK_ERR_INVALID, "prefix_off[0] < 0");
+    for (int32_t r = 0; r < nreads; r++)
+        if (prefix_off[r + 1] < prefix_off[r]) return sk_fail(SK_ERR_INVALID, "prefix_off decreases at read %d", r);
+    const int64_t pbytes = prefix_off[nreads];
+    if (pbytes > 0 && !prefix) return sk_fail(SK_ERR_INVALID, "NULL prefix");
+    std::vector<double> cal;
+    if (mode == SK_PULL_PA) {
+        cal.resize((size_t)nreads * 2);
+        if ((rc = sk_pa_calib(calib, nreads, cal.data()))) return rc;
+    }
+    const size_t row_bytes = (size_t)nreads * (size_t)stride * sizeof(int16_t);
+    const size_t poff_bytes = (size_t)(nreads + 1) * sizeof(int64_t);
+    if ((rc = sk_reserve(c, &c->sig, row_bytes))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, poff_bytes + (size_t)pbytes))) return rc;
+    if (!cal.empty() && (rc = sk_reserve(c, &c->pacal, cal.size() * sizeof(double)))) return rc;
+    int64_t *d_poff = (int64_t *)c->out.p;
+    char *d_prefix = (char *)c->out.p + poff_bytes;
+    SK_HIP(hipMemcpyAsync(c->sig.p, sig, row_bytes, hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipMemcpyAsync(c->len.p, len, (size_t)nreads * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipMemcpyAsync(d_poff, prefix_off, poff_bytes, hipMemcpyHostToDevice, c->stream));
+    if (pbytes > 0) SK_HIP(hipMemcpyAsync(d_prefix, prefix, (size_t)pbytes, hipMemcpyHostToDevice, c->stream));
+    if (!cal.empty())
+        SK_HIP(hipMemcpyAsync(c->pacal.p, cal.data(), cal.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const double *d_cal = cal.empty() ? nullptr : (const double *)c->pacal.p;
+    const int16_t *d_sig = (const int16_t *)c->sig.p;
+    const int32_t *d_len = (const int32_t *)c->len.p;
+    PullScratch s;
+    if ((rc = pull_count(c, d_sig, stride, d_len, nreads, d_cal, d_poff, capacity, total, &s))) return rc;   // (synchronises:
+    if ((rc = sk_reserve(c, &c->pulltext, (size_t)*total))) return rc;                                           //  cal is safe)
+    if ((rc = sk_launch_pull_write(c, d_sig, stride, d_len, nreads, d_cal, d_prefix, d_poff, s.tile0, s.tb, s.tile_cap, s.lines,
+                                   (char *)c->pulltext.p)))
+        return rc;
+    SK_HIP(hipMemcpyAsync(text, c->pulltext.p, (size_t)*total, hipMemcpyDeviceToHost, c->stream));
+    if (line_off) SK_HIP(hipMemcpyAsync(line_off, s.lines, (size_t)(nreads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}

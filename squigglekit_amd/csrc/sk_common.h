@@ -69,6 +69,8 @@ struct sk_ctx {
     sk_buf misc;
     sk_buf seghints;  // per read: the stretches of quiet mask entries and their anchors, k_seg_stats -> k_seg_walk4
     sk_buf pacal;     // per read {offset, range / digitisation}: the pA conversion of raw rows (sk_segment_batch_i16_pa)
+    sk_buf pull;      // SquigglePull text: tile / line scans (int64) and the error word (sk_pull.hip)
+    sk_buf pulltext;  // SquigglePull text: the prefixes and the text of the host entry point
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -285,3 +287,17 @@ int  sk_launch_prep_f64_listed(sk_ctx *c, const double *d_sig, const int64_t *d_
                                int row16, const int32_t *d_rlen = nullptr);
 int  sk_launch_seg_walk_masks(sk_ctx *c, const void *d_mask2, int row16, const int32_t *d_len, int32_t nreads,
                               const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs);
+
+// ---- SquigglePull text (sk_pull.hip) ----
+// exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries
+int64_t sk_scan_blocks(int64_t n);
+int     sk_launch_scan_i64(sk_ctx *c, const int64_t *v, int64_t n, int64_t *bsum, int64_t *out);
+int64_t sk_pull_tile_cap(int32_t nreads, int64_t stride);   // tiles the rows can hold at most
+// d_cal: {offset, raw unit} per read, nullptr in raw mode.  Count: tile0 (nreads + 1), tb (tile_cap + 1) and
+// line_off (nreads + 1) get their exclusive scans, *d_err |= 1 for a value the formatter cannot print.
+int sk_launch_pull_count(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                         const double *d_cal, const int64_t *d_poff, int64_t *d_tile0, int64_t *d_tb, int64_t tile_cap,
+                         int64_t *d_bsum, int64_t *d_line_off, int32_t *d_err);
+int sk_launch_pull_write(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                         const double *d_cal, const char *d_prefix, const int64_t *d_poff, const int64_t *d_tile0,
+                         const int64_t *d_tb, int64_t tile_cap, const int64_t *d_line_off, char *d_out);
