@@ -158,6 +158,50 @@ int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_le
 int sk_segment_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t max_len,
                        const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs);
 
+/* ---- segmenter parameter sweep ----------------------------------------- */
+/* Every set of a grid over the same reads in one call: for set k and read r, what sk_segment_batch_i16 (or the float64
+ * route) reports with set k's sk_seg_params, cut to the first two segments, and per set the counts segmenter.py's
+ * acceptance tests give (segmenter.py:473-494; -k/-j stall_start, -g/-b gap_dist).  The statistics and masks are built
+ * once per distinct (lim_low, lim_hi, std_scale); the walks of all sets that share them read them once.
+ * The sets are checked as sk_segment_batch_i16 checks its params (corrector >= 0); SK_ERR_INVALID names the set. */
+typedef struct sk_seg_sweep_set {          /* 48 bytes */
+    sk_seg_params seg;                     /* the segmenter's flags                  */
+    int32_t stall_start;                   /* -j, default 300                        */
+    int32_t gap_dist;                      /* -b, default 3000                       */
+} sk_seg_sweep_set;
+
+typedef struct sk_seg_sweep_rec {          /* 24 bytes, one per (set, read) */
+    int32_t nsegs;                         /* segment count after merges, as sk_segment_batch_i16 reports it */
+    int32_t s0_start, s0_end;              /* first segment, filtered coordinates; -1 when nsegs == 0        */
+    int32_t s1_start, s1_end;              /* second segment; -1 when nsegs < 2                              */
+    int32_t reserved;                      /* 0 */
+} sk_seg_sweep_rec;
+
+/* Exact integer counts over the reads, per set.  gap_ok counts a read with exactly ONE segment as passing: the
+ * reference's test_segs reads segs[1] inside a bare `except` (segmenter.py:485-492), so such a read is printed. */
+typedef struct sk_seg_sweep_sum {          /* 64 bytes */
+    int64_t reads;                         /* reads given                                                          */
+    int64_t with_segs;                     /* nsegs >= 1: lines segmenter.py prints without -u                     */
+    int64_t segs;                          /* sum of nsegs                                                         */
+    int64_t stall_ok;                      /* nsegs >= 1 && s0_start <= stall_start: lines with -k -u              */
+    int64_t gap_ok;                        /* nsegs >= 1 && (nsegs == 1 || s1_start <= s0_end + gap_dist): -g -u   */
+    int64_t stall_gap_ok;                  /* both: lines with -k -g -u                                            */
+    int64_t seg0_end_sum;                  /* sum of s0_end over the reads with nsegs >= 1 (filtered coordinates)  */
+    int64_t reserved;                      /* 0 */
+} sk_seg_sweep_sum;
+
+/* int16 rows as sk_segment_batch_i16 takes them (len[r] in [0, stride]).  sums[nsets]; recs[nsets][nreads] or NULL. */
+int sk_segment_sweep_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const sk_seg_sweep_set *sets, int32_t nsets, sk_seg_sweep_sum *sums, sk_seg_sweep_rec *recs);
+/* the same with every pointer on the device except `sets` (host); sums / recs are device buffers (recs may be NULL). */
+int sk_segment_sweep_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const sk_seg_sweep_set *sets, int32_t nsets, sk_seg_sweep_sum *d_sums,
+                             sk_seg_sweep_rec *d_recs);
+/* float64 reads as sk_segment_batch_f64_len takes them: read r is the first len[r] samples of sig[off[r] .. off[r+1])
+ * (len may be NULL: whole reads). */
+int sk_segment_sweep_f64(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,
+                         const sk_seg_sweep_set *sets, int32_t nsets, sk_seg_sweep_sum *sums, sk_seg_sweep_rec *recs);
+
 /* ---- dRNA adapter segmenter (dRNA_segmenter.py, slow5 branch :85-176) ---- */
 /* The script hard-codes these (dRNA_segmenter.py:80-104); they are parameters here. */
 typedef struct sk_drna_params {

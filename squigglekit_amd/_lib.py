@@ -45,6 +45,30 @@ class SegParams(C.Structure):
                    args.stall_len, getattr(args, "lim_low", 0), getattr(args, "lim_hi", 900))
 
 
+class SweepSet(C.Structure):
+    """sk_seg_sweep_set: one parameter set of a sweep -- the segmenter's flags plus the -j / -b test thresholds."""
+    _fields_ = [("seg", SegParams), ("stall_start", C.c_int32), ("gap_dist", C.c_int32)]
+
+    def __init__(self, seg=None, stall_start=300, gap_dist=3000):
+        super().__init__(seg if seg is not None else SegParams(), stall_start, gap_dist)
+
+
+class SweepRec(C.Structure):
+    """sk_seg_sweep_rec: one (set, read) of a sweep."""
+    _fields_ = [("nsegs", C.c_int32), ("s0_start", C.c_int32), ("s0_end", C.c_int32),
+                ("s1_start", C.c_int32), ("s1_end", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SweepSum(C.Structure):
+    """sk_seg_sweep_sum: one set's counts over the reads."""
+    _fields_ = [("reads", C.c_int64), ("with_segs", C.c_int64), ("segs", C.c_int64), ("stall_ok", C.c_int64),
+                ("gap_ok", C.c_int64), ("stall_gap_ok", C.c_int64), ("seg0_end_sum", C.c_int64), ("reserved", C.c_int64)]
+
+
+SWEEP_REC_DTYPE = np.dtype([(n, "<i4") for n, _ in SweepRec._fields_])
+SWEEP_SUM_DTYPE = np.dtype([(n, "<i8") for n, _ in SweepSum._fields_])
+
+
 class DrnaParams(C.Structure):
     """sk_drna_params; defaults are the constants hard-coded at dRNA_segmenter.py:80-104."""
     _fields_ = [("error", C.c_int32), ("no_err_thresh", C.c_int32), ("w", C.c_int32),
@@ -180,6 +204,9 @@ ABI = {
     "sk_synth_variant_dev": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, _vp, C.c_int32, _vp]),
     "sk_synth_pa_dev": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "sk_pull_text": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _i64p, _vp]),
+    "sk_segment_sweep_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    "sk_segment_sweep_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    "sk_segment_sweep_f64": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
     "sk_pull_text_dev": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _i64p, _vp]),
 }
 

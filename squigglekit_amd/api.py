@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import HIT_DTYPE, SegParams, SquiggleKitError, check, ptr
+from ._lib import (HIT_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+                   check, ptr)
 
 
 # ----------------------------------------------------------------------------
@@ -166,6 +167,144 @@ def segment_batch(sig, lens=None, params=None, max_segs=64, devices=None):
             continue
         check(rc)
         return segs, nsegs
+
+
+# ----------------------------------------------------------------------------
+# segmenter parameter sweep
+# ----------------------------------------------------------------------------
+SWEEP_KEYS = ("error", "corrector", "window", "seg_dist", "std_scale", "stall_len", "lim_low", "lim_hi",
+              "stall_start", "gap_dist")
+SWEEP_DEFAULTS = dict(error=5, corrector=50, window=150, seg_dist=50, std_scale=0.75, stall_len=0.25, lim_low=0,
+                      lim_hi=900, stall_start=300, gap_dist=3000)        # segmenter.py's argparse defaults
+_SWEEP_FLOAT = ("std_scale", "stall_len")
+
+
+def sweep_set(**kw):
+    """One sweep set (sk_seg_sweep_set) from keyword values of SWEEP_KEYS; the others take segmenter.py's defaults."""
+    bad = set(kw) - set(SWEEP_KEYS)
+    if bad:
+        raise TypeError("unknown sweep parameter(s): %s" % ", ".join(sorted(bad)))
+    v = dict(SWEEP_DEFAULTS, **kw)
+    seg = SegParams(int(v["error"]), int(v["corrector"]), int(v["window"]), int(v["seg_dist"]), float(v["std_scale"]),
+                    float(v["stall_len"]), int(v["lim_low"]), int(v["lim_hi"]))
+    return SweepSet(seg, int(v["stall_start"]), int(v["gap_dist"]))
+
+
+def sweep_values(s):
+    """The ten parameters of a sweep set, in SWEEP_KEYS order."""
+    g = s.seg
+    return (g.error, g.corrector, g.window, g.seg_dist, g.std_scale, g.stall_len, g.lim_low, g.lim_hi, s.stall_start,
+            s.gap_dist)
+
+
+def sweep_grid(**kw):
+    """The Cartesian product of the given values as a list of sweep sets.  Each argument (any of SWEEP_KEYS) is a scalar
+    or a sequence; the others take segmenter.py's defaults.  Order: error, corrector, window, seg_dist, std_scale,
+    stall_len, lim_low, lim_hi, stall_start, gap_dist -- the last one varying fastest."""
+    import itertools
+    bad = set(kw) - set(SWEEP_KEYS)
+    if bad:
+        raise TypeError("unknown sweep parameter(s): %s" % ", ".join(sorted(bad)))
+    axes = []
+    for k in SWEEP_KEYS:
+        v = kw.get(k, SWEEP_DEFAULTS[k])
+        axes.append(list(v) if isinstance(v, (list, tuple, range, np.ndarray)) else [v])
+    return [sweep_set(**dict(zip(SWEEP_KEYS, combo))) for combo in itertools.product(*axes)]
+
+
+def _check_sweep_sets(sets):
+    for k, s in enumerate(sets):
+        if s.seg.corrector < 0:
+            raise ValueError("sweep set %d: corrector must be >= 0 (the reference divides by zero otherwise)" % k)
+
+
+def _sweep_route(entry, R, args_of, sets, records, devices):
+    """One sweep entry point over R reads, block-sharded over `devices`: (sums, recs) with the shards' counts added and
+    their records in input order."""
+    import threading
+    ns = len(sets)
+    arr = (SweepSet * max(ns, 1))(*sets)
+    sums = np.zeros(ns, dtype=SWEEP_SUM_DTYPE)
+    recs = np.zeros((ns, R), dtype=SWEEP_REC_DTYPE) if records else None
+    lock = threading.Lock()
+
+    def call(lo, hi):
+        part = np.zeros(max(ns, 1), dtype=SWEEP_SUM_DTYPE)
+        rp = np.zeros((ns, hi - lo), dtype=SWEEP_REC_DTYPE) if records else None
+        rc = entry(*args_of(lo, hi), arr, ns, ptr(part), None if rp is None or rp.size == 0 else ptr(rp))
+        if rc == 0:
+            with lock:
+                sums.view(np.int64).reshape(ns, 8)[:] += part[:ns].view(np.int64).reshape(ns, 8)
+                if rp is not None:
+                    recs[:, lo:hi] = rp
+        return rc
+    if ns:
+        _over_devices(devices, R, call)
+    return sums, recs
+
+
+def _add_sweep(a, b):
+    out = a.copy()
+    out.view(np.int64).reshape(len(a), 8)[:] += b.view(np.int64).reshape(len(b), 8)
+    return out
+
+
+def segment_sweep(reads, sets, lens=None, records=False, devices=None):
+    """segmenter.py's scale_outliers + get_segs + test_segs for every set of a grid over the same reads, in one pass per
+    distinct (lim_low, lim_hi, std_scale) (sk_segment_sweep_i16 / _f64).
+
+    reads: an int16 [R, stride] batch (with `lens`), or a list of reads routed like segment_any -- integer-valued reads
+    that fit int16 go to the int16 entry, the others to the float64 one; sets whose limits are too wide for the int16
+    kernels take the float64 route too, as in segment_batch.  sets: sweep sets (sweep_grid / sweep_set).
+    Returns (sums, recs): sums a SWEEP_SUM_DTYPE array [nsets], recs a SWEEP_REC_DTYPE array [nsets, R] (records=True)
+    or None.  For set k and read r the record holds what segment_batch reports with set k's params: the segment count
+    and the first two segments (-1 where there is none).  devices: the reads are block-sharded over those GPUs."""
+    sets = list(sets)
+    _check_sweep_sets(sets)
+    L = _lib.load()
+    ns = len(sets)
+    if isinstance(reads, np.ndarray) and reads.ndim == 2:
+        sig = np.ascontiguousarray(reads, dtype=np.int16)
+        R, stride = sig.shape
+        ln = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+        ints, arrs, flts = list(range(R)), None, []
+    else:
+        if lens is not None:
+            raise ValueError("lens goes with an int16 [R, stride] batch")
+        R = len(reads)
+        ints, arrs, flts = _split_int16(reads)
+        sig = ln = None
+        if ints:
+            sig, ln = pack_i16(arrs)
+    wide = [k for k, s in enumerate(sets) if _too_wide_for_i16(s.seg.lim_low, s.seg.lim_hi)]
+    narrow = [k for k in range(ns) if k not in set(wide)]
+    sums = np.zeros(ns, dtype=SWEEP_SUM_DTYPE)
+    recs = np.zeros((ns, R), dtype=SWEEP_REC_DTYPE) if records else None
+
+    def put(idx_sets, idx_reads, part):
+        ps, pr = part
+        sums[idx_sets] = _add_sweep(sums[idx_sets], ps)
+        if records:
+            recs[np.ix_(idx_sets, idx_reads)] = pr
+
+    def f64_route(rows, idx_reads, idx_sets):
+        flat, off = pack_f64(rows)
+        sub = [sets[k] for k in idx_sets]
+        put(idx_sets, idx_reads, _sweep_route(L.sk_segment_sweep_f64, len(rows),
+                                              lambda lo, hi: (ptr(flat), ptr(off[lo:hi + 1]), None, hi - lo),
+                                              sub, records, devices))
+    if ints:
+        stride = sig.shape[1]
+        if narrow:
+            sub = [sets[k] for k in narrow]
+            put(narrow, ints, _sweep_route(L.sk_segment_sweep_i16, len(ints),
+                                           lambda lo, hi: (ptr(sig[lo:hi]), stride, ptr(ln[lo:hi]), hi - lo),
+                                           sub, records, devices))
+        if wide:
+            f64_route([sig[i, :ln[i]].astype(np.float64) for i in range(len(ints))], ints, wide)
+    if flts:
+        f64_route([np.asarray(reads[i], dtype=np.float64) for i in flts], flts, list(range(ns)))
+    return sums, recs
 
 
 def segment_reads(reads, params=None):

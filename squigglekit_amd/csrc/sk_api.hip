@@ -797,18 +797,19 @@ static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     return SK_OK;
 }
 
-// device-resident core of the float64 segmenter path (d_off zero based; d_segs zeroed here)
-static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
-                           int64_t maxlen, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
-                           const int32_t *d_rlen = nullptr)
+// The statistics and masks of the float64 segmenter path (d_off zero based): {in band, kept} entries in c->mask (*row16
+// per read) and each read's raw length in c->len.  Records ev[0] .. ev[1].  d_zero (bytes): zeroed first, on the stream.
+static int segment_masks_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
+                             int64_t maxlen, int32_t lim_low, int32_t lim_hi, double std_scale, const int32_t *d_rlen,
+                             int *row16_out, void *d_zero = nullptr, size_t zero_bytes = 0)
 {
     int rc;
-    const size_t gb = (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t);
     // streaming statistics with certified comparisons (sk_f64stat.hip) and the numpy-order kernel over the (almost
     // always empty) list of uncertified reads -- or, outside the streaming kernel's range, the numpy-order kernel for
     // every read.  Either writes {in band, kept} entries and raw lengths; the run-hopping walk of the int16 path follows.
-    const bool fast = sk_f64_fast_applies(maxlen, p->std_scale);
+    const bool fast = sk_f64_fast_applies(maxlen, std_scale);
     const int row16 = sk_f64_row16(maxlen > 0 ? maxlen : 1);
+    *row16_out = row16;
     const int grid = nreads < 2 * c->num_cu ? nreads : 2 * c->num_cu;
     const int64_t srow = (maxlen + 7) & ~(int64_t)7;
     // compacted samples: one scratch row per workgroup of the listed redo, or every read's
@@ -823,22 +824,34 @@ static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off,
         if ((rc = redo_list(c, SK_REDO_F64, nreads, &retry))) return rc;
         c->redo_off.push_back((size_t)(retry - (int32_t *)c->redo.p));
     }
-    SK_HIP(hipMemsetAsync(d_segs, 0, gb, c->stream));
+    if (d_zero) SK_HIP(hipMemsetAsync(d_zero, 0, zero_bytes, c->stream));
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
     if (fast) {
-        rc = sk_launch_f64_stats(c, d_sig, d_off, d_rlen, nreads, maxlen, (double)p->lim_low, (double)p->lim_hi, SK_PREP_SEGMENT,
-                                 p->std_scale, (sk_prep *)c->prep.p, c->mask.p, row16, (int32_t *)c->len.p, retry, nullptr);
+        rc = sk_launch_f64_stats(c, d_sig, d_off, d_rlen, nreads, maxlen, (double)lim_low, (double)lim_hi, SK_PREP_SEGMENT,
+                                 std_scale, (sk_prep *)c->prep.p, c->mask.p, row16, (int32_t *)c->len.p, retry, nullptr);
         if (rc) return rc;
-        rc = sk_launch_prep_f64_listed(c, d_sig, d_off, retry + 1, retry, grid, (double)p->lim_low, (double)p->lim_hi,
-                                       SK_PREP_SEGMENT, p->std_scale, (double *)c->comp.p, srow, (sk_prep *)c->prep.p,
+        rc = sk_launch_prep_f64_listed(c, d_sig, d_off, retry + 1, retry, grid, (double)lim_low, (double)lim_hi,
+                                       SK_PREP_SEGMENT, std_scale, (double *)c->comp.p, srow, (sk_prep *)c->prep.p,
                                        c->mask.p, row16, d_rlen);
     } else {
-        rc = sk_launch_prep_f64(c, d_sig, d_off, nreads, (double)p->lim_low, (double)p->lim_hi, SK_PREP_SEGMENT,
-                                p->std_scale, (double *)c->comp.p, (sk_prep *)c->prep.p, c->mask.p, row16,
+        rc = sk_launch_prep_f64(c, d_sig, d_off, nreads, (double)lim_low, (double)lim_hi, SK_PREP_SEGMENT,
+                                std_scale, (double *)c->comp.p, (sk_prep *)c->prep.p, c->mask.p, row16,
                                 (int32_t *)c->len.p, d_rlen);
     }
     if (rc) return rc;
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    return SK_OK;
+}
+
+// device-resident core of the float64 segmenter path (d_off zero based; d_segs zeroed here)
+static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
+                           int64_t maxlen, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
+                           const int32_t *d_rlen = nullptr)
+{
+    int row16;
+    int rc = segment_masks_f64(c, d_sig, d_off, nreads, total, maxlen, p->lim_low, p->lim_hi, p->std_scale, d_rlen, &row16,
+                               d_segs, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t));
+    if (rc) return rc;
     rc = sk_launch_seg_walk_masks(c, c->mask.p, row16, (const int32_t *)c->len.p, nreads, p, d_segs, d_nsegs, max_segs);
     if (rc) return rc;
     c->ev_valid = true;
@@ -1056,6 +1069,221 @@ int sk_segment_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nreads
 // ------------------------------------------------------------------ dRNA adapter segmenter
 // ------------------------------------------------------------------ dRNA --signal branch (rolling mean)
 // device-resident cores of the two dRNA branches (d_sig / d_len / outputs are device pointers)
+// ------------------------------------------------------------------ segmenter parameter sweep
+} // extern "C"
+
+// The sets as sk_segment_batch_i16 checks its params (check_seg_params), the failure naming the set.
+static int check_sweep(const sk_seg_sweep_set *sets, int32_t nsets, bool null_sums)
+{
+    if (nsets < 0) return sk_fail(SK_ERR_INVALID, "nsets < 0");
+    if (nsets && (!sets || null_sums)) return sk_fail(SK_ERR_INVALID, "NULL sets/sums");
+    for (int32_t k = 0; k < nsets; k++)
+        if (sets[k].seg.corrector < 0)
+            return sk_fail(SK_ERR_INVALID, "set %d: corrector must be >= 0 (the reference divides by zero otherwise)", k);
+    return SK_OK;
+}
+
+// The plan's lanes to the device (c->sweep), followed by room for nsets summaries (*d_sums_scratch) when asked
+static int sweep_stage(sk_ctx *c, const sk_seg_sweep_set *sets, int32_t nsets, std::vector<sk_sweep_group> &groups,
+                       sk_sweep_lane **d_lanes, sk_seg_sweep_sum **d_sums_scratch)
+{
+    std::vector<sk_sweep_lane> lanes;
+    sk_sweep_plan(sets, nsets, groups, lanes);
+    const size_t lb = ((lanes.size() * sizeof(sk_sweep_lane)) + 255) & ~(size_t)255;
+    int rc = sk_reserve(c, &c->sweep, lb + (size_t)nsets * sizeof(sk_seg_sweep_sum));
+    if (rc) return rc;
+    *d_lanes = (sk_sweep_lane *)c->sweep.p;
+    SK_HIP(hipMemcpyAsync(c->sweep.p, lanes.data(), lanes.size() * sizeof(sk_sweep_lane), hipMemcpyHostToDevice, c->stream));
+    if (d_sums_scratch) {
+        *d_sums_scratch = (sk_seg_sweep_sum *)((char *)c->sweep.p + lb);
+        SK_HIP(hipMemsetAsync(*d_sums_scratch, 0, (size_t)nsets * sizeof(sk_seg_sweep_sum), c->stream));
+    }
+    SK_HIP(hipStreamSynchronize(c->stream));                 // (lanes goes out of scope)
+    return SK_OK;
+}
+
+// The two walks of one group over the masks in c->mask (the run-hopping sets, then the others)
+static int sweep_walk_group(sk_ctx *c, const sk_sweep_group &g, const sk_sweep_lane *d_lanes, int row16, const int32_t *d_len,
+                            int64_t mmax, int32_t nreads, sk_seg_sweep_sum *d_sums, sk_seg_sweep_rec *d_recs, int64_t rec_stride)
+{
+    int rc = sk_launch_seg_sweep_walk(c, c->mask.p, row16, d_len, mmax, nreads, d_lanes + g.first, g.nfast, true, d_sums,
+                                      d_recs, rec_stride);
+    if (rc) return rc;
+    return sk_launch_seg_sweep_walk(c, c->mask.p, row16, d_len, mmax, nreads, d_lanes + g.first + g.nfast, g.ngen, false,
+                                    d_sums, d_recs, rec_stride);
+}
+
+// Device-resident core of the int16 sweep: per group the statistics and masks of segment_dev_i16 without its walk (the
+// streaming kernel and the numpy-order redo of its uncertified reads, or the numpy-order kernel for every read), then
+// the group's walks.  Records of read r at d_recs[set * rec_stride + r] (d_recs: already offset to this block's reads).
+static int sweep_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                         const sk_seg_sweep_set *sets, const std::vector<sk_sweep_group> &groups, const sk_sweep_lane *d_lanes,
+                         sk_seg_sweep_sum *d_sums, sk_seg_sweep_rec *d_recs, int64_t rec_stride)
+{
+    int rc;
+    if (nreads <= 0) return SK_OK;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    for (const sk_sweep_group &g : groups) {
+        const sk_seg_params &p = sets[g.rep].seg;
+        int32_t lo = p.lim_low, hi = p.lim_hi;
+        clamp_limits(&lo, &hi);
+        int row16;
+        if (sk_segment_fast_applies(d_sig, stride, lo, hi, p.std_scale)) {
+            row16 = sk_segment_fast_row16(stride);
+            if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
+            if ((rc = redo_begin(c, nreads, 1))) return rc;
+            int32_t *redo;
+            if ((rc = redo_list(c, SK_REDO_I16, nreads, &redo))) return rc;
+            rc = sk_launch_segment_masks(c, d_sig, stride, d_len, nreads, p.std_scale, lo, hi, (sk_prep *)c->prep.p,
+                                         c->mask.p, redo);
+        } else {
+            row16 = (int)((stride + 63) / 64);
+            if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+            if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
+            rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nreads, lo, hi, SK_PREP_SEGMENT, p.std_scale,
+                                    (int16_t *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0, 0, 0x7fffffff, nullptr, nullptr,
+                                    c->mask.p, row16);
+        }
+        if (rc) return rc;
+        if ((rc = sweep_walk_group(c, g, d_lanes, row16, d_len, stride, nreads, d_sums, d_recs, rec_stride))) return rc;
+    }
+    return SK_OK;
+}
+
+// Reads per block of a device-resident sweep: one group's masks (and the numpy-order route's compacted rows) stay
+// within 1 GiB, or SK_SWEEP_BLOCK reads when set (tests)
+static int32_t sweep_block_reads(int64_t stride, int32_t nreads)
+{
+    const int64_t per = (int64_t)((stride + 63) / 64) * 16 + stride * (int64_t)sizeof(int16_t) + (int64_t)sizeof(sk_prep);
+    int64_t b = ((int64_t)1 << 30) / per;
+    if (b < 4096) b = 4096;
+    return b >= nreads ? nreads : (int32_t)b;
+}
+
+extern "C" {
+
+// segmenter.py's whole pipeline (:207-211 scale_outliers + get_segs, :473-494 test_segs) once per set of a grid:
+// sk_seg_sweep_sum / sk_seg_sweep_rec in the header.  The masks are built once per (lim_low, lim_hi, std_scale) group.
+int sk_segment_sweep_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const sk_seg_sweep_set *sets, int32_t nsets, sk_seg_sweep_sum *d_sums, sk_seg_sweep_rec *d_recs)
+{
+    SK_ENTER(c);
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (!rc) rc = check_sweep(sets, nsets, !d_sums);
+    if (rc) return rc;
+    if (nsets == 0) return SK_OK;
+    c->ev_valid = false;
+    std::vector<sk_sweep_group> groups;
+    sk_sweep_lane *d_lanes;
+    if ((rc = sweep_stage(c, sets, nsets, groups, &d_lanes, nullptr))) return rc;
+    SK_HIP(hipMemsetAsync(d_sums, 0, (size_t)nsets * sizeof(sk_seg_sweep_sum), c->stream));
+    const int32_t blk = sweep_block_reads(stride, nreads);
+    for (int32_t r0 = 0; r0 < nreads; r0 += blk) {
+        const int32_t nr = nreads - r0 < blk ? nreads - r0 : blk;
+        rc = sweep_dev_i16(c, d_sig + (int64_t)r0 * stride, stride, d_len + r0, nr, sets, groups, d_lanes, d_sums,
+                           d_recs ? d_recs + r0 : nullptr, nreads);
+        if (rc) return rc;
+    }
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_segment_sweep_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const sk_seg_sweep_set *sets, int32_t nsets, sk_seg_sweep_sum *sums, sk_seg_sweep_rec *recs)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (!rc) rc = check_len_host(len, nreads, stride);
+    if (!rc) rc = check_sweep(sets, nsets, !sums);
+    if (rc) return rc;
+    if (nsets == 0) return SK_OK;
+    c->ev_valid = false;
+    std::vector<sk_sweep_group> groups;
+    sk_sweep_lane *d_lanes;
+    sk_seg_sweep_sum *d_sums;
+    if ((rc = sweep_stage(c, sets, nsets, groups, &d_lanes, &d_sums))) return rc;
+    sk_seg_sweep_rec *d_recs = nullptr;
+    const size_t rb = (size_t)nsets * (size_t)nreads * sizeof(sk_seg_sweep_rec);
+    if (recs && nreads) {
+        if ((rc = sk_reserve(c, &c->sweeprec, rb))) return rc;
+        d_recs = (sk_seg_sweep_rec *)c->sweeprec.p;
+    }
+    if (nreads) {
+        // sub-batches of the host rows as sk_segment_batch_i16's, each small enough for sweep_block_reads' budget
+        SubBatches B = sub_batches(nreads, stride);
+        const int32_t blk = sweep_block_reads(stride, nreads);
+        if (B.per > blk) {
+            B.n = (nreads + blk - 1) / blk;
+            B.per = (int32_t)(((int64_t)nreads + B.n - 1) / B.n);
+        }
+        if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+        if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+        rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                         [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                             return sweep_dev_i16(c, d_sig, stride, d_len, nr, sets, groups, d_lanes, d_sums,
+                                                  d_recs ? d_recs + r0 : nullptr, nreads);
+                         });
+        if (rc) return rc;
+    }
+    SK_HIP(hipMemcpyAsync(sums, d_sums, (size_t)nsets * sizeof(sk_seg_sweep_sum), hipMemcpyDeviceToHost, c->stream));
+    if (d_recs) SK_HIP(hipMemcpyAsync(recs, d_recs, rb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// The float64 route (pA TSVs, converted fast5 / BLOW5 reads): as sk_segment_batch_f64_len, every group through the
+// statistics of segment_dev_f64 without its walk.
+int sk_segment_sweep_f64(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,
+                         const sk_seg_sweep_set *sets, int32_t nsets, sk_seg_sweep_sum *sums, sk_seg_sweep_rec *recs)
+{
+    SK_ENTER(c);
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_sweep(sets, nsets, !sums);
+    if (rc) return rc;
+    if (nsets == 0) return SK_OK;
+    c->ev_valid = false;
+    std::vector<sk_sweep_group> groups;
+    sk_sweep_lane *d_lanes;
+    sk_seg_sweep_sum *d_sums;
+    if ((rc = sweep_stage(c, sets, nsets, groups, &d_lanes, &d_sums))) return rc;
+    sk_seg_sweep_rec *d_recs = nullptr;
+    const size_t rb = (size_t)nsets * (size_t)nreads * sizeof(sk_seg_sweep_rec);
+    if (nreads) {
+        int64_t total, maxlen;
+        if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen))) return rc;
+        const int32_t *d_rlen = nullptr;
+        if (len) {                                  // read r is its first len[r] samples (segment_batch_ragged)
+            for (int32_t r = 0; r < nreads; r++)
+                if (len[r] < 0 || (int64_t)len[r] > off[r + 1] - off[r])
+                    return sk_fail(SK_ERR_INVALID, "len[%d] = %d is outside [0, %lld]", r, len[r], (long long)(off[r + 1] - off[r]));
+            if ((rc = sk_reserve(c, &c->rlen, (size_t)nreads * sizeof(int32_t)))) return rc;
+            SK_HIP(hipMemcpyAsync(c->rlen.p, len, (size_t)nreads * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            d_rlen = (const int32_t *)c->rlen.p;
+            maxlen = 0;
+            for (int32_t r = 0; r < nreads; r++) if (len[r] > maxlen) maxlen = len[r];
+        }
+        if (recs) {
+            if ((rc = sk_reserve(c, &c->sweeprec, rb))) return rc;
+            d_recs = (sk_seg_sweep_rec *)c->sweeprec.p;
+        }
+        for (const sk_sweep_group &g : groups) {
+            const sk_seg_params &p = sets[g.rep].seg;
+            if ((rc = redo_begin(c, nreads, 1))) return rc;
+            int row16;
+            rc = segment_masks_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, p.lim_low,
+                                   p.lim_hi, p.std_scale, d_rlen, &row16);
+            if (rc) return rc;
+            rc = sweep_walk_group(c, g, d_lanes, row16, (const int32_t *)c->len.p, (int64_t)row16 * 64, nreads, d_sums, d_recs,
+                                  nreads);
+            if (rc) return rc;
+        }
+    }
+    SK_HIP(hipMemcpyAsync(sums, d_sums, (size_t)nsets * sizeof(sk_seg_sweep_sum), hipMemcpyDeviceToHost, c->stream));
+    if (d_recs) SK_HIP(hipMemcpyAsync(recs, d_recs, rb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
 static int drna_roll_dev(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                          const sk_roll_params *p, int32_t *d_xy, int32_t *d_found)
 {

@@ -71,6 +71,8 @@ struct sk_ctx {
     sk_buf pacal;     // per read {offset, range / digitisation}: the pA conversion of raw rows (sk_segment_batch_i16_pa)
     sk_buf pull;      // SquigglePull text: tile / line scans (int64) and the error word (sk_pull.hip)
     sk_buf pulltext;  // SquigglePull text: the prefixes and the text of the host entry point
+    sk_buf sweep;     // parameter sweep: the sets in walk form, then the summaries (sk_sweep.hip)
+    sk_buf sweeprec;  // parameter sweep: the per-(set, read) records of the host entry points
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -255,6 +257,30 @@ bool sk_segment_pa_applies(const void *d_sig, int64_t stride, double std_scale);
 int  sk_launch_prep_pa_listed(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, const double *d_cal,
                               const int32_t *d_list, const int32_t *d_count, int grid, double lo, double hi, double std_scale,
                               double *d_scratch, int64_t scratch_stride, sk_prep *d_prep, void *d_mask2, int row16);
+
+// the statistics and the redo of sk_launch_segment_fast without its walk (int16 route; d_retry: nreads + 16 ints)
+int  sk_launch_segment_masks(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             double std_scale, int32_t lo, int32_t hi, sk_prep *d_prep, void *d_mask2, int32_t *d_retry);
+
+// ---- segmenter parameter sweep (sk_sweep.hip) ----
+// One set of a sweep as the walk holds it (a lane's parameters); `index`: its place in the caller's list.
+struct sk_sweep_lane {
+    int32_t error, corrector, window, seg_dist, first_len, stall_start, gap_dist, index;
+};
+// The sets that share one mask pass -- equal (lim_low, lim_hi, std_scale) bit patterns -- as runs of `lanes`: nfast sets
+// that take the run-hopping walk from `first`, then ngen that take the per-sample one.  `rep`: one of its sets.
+struct sk_sweep_group {
+    int32_t rep, first, nfast, ngen;
+};
+// Groups the sets (in the order of their first member) and lays out their lanes; the lanes go to the device as they are.
+void sk_sweep_plan(const sk_seg_sweep_set *sets, int32_t nsets, std::vector<sk_sweep_group> &groups,
+                   std::vector<sk_sweep_lane> &lanes);
+// The walk of `nlanes` sets of one kind (fast: the run-hopping form) over the entries of nreads reads (row16 per read, read r
+// clamped to min(d_len[r], mmax) samples); adds into d_sums[lane.index]; d_recs != nullptr: record of (set, read r) at
+// d_recs[lane.index * rec_stride + r].
+int  sk_launch_seg_sweep_walk(sk_ctx *c, const void *d_mask2, int row16, const int32_t *d_len, int64_t mmax, int32_t nreads,
+                              const sk_sweep_lane *d_lanes, int32_t nlanes, bool fast, sk_seg_sweep_sum *d_sums,
+                              sk_seg_sweep_rec *d_recs, int64_t rec_stride);
 
 // ---- dRNA slow5-branch walk (sk_drna_walk.hip) ----
 struct sk_drna_params;

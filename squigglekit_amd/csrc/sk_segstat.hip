@@ -1645,6 +1645,62 @@ segstat_fn pick_stats(int64_t stride, int nbins, bool pa)
     return k_seg_stats<8, 8, 8, false>;
 }
 
+// The statistics kernel for (stride, limits, route) and its arguments, less the per-chunk pointers
+SegStatArgs stats_setup(int64_t stride, int32_t lo, int32_t hi, double std_scale, const double *d_cal, segstat_fn *fn,
+                        segstat_fn *fn_wg)
+{
+    *fn = pick_stats(stride, hi - lo - 1, d_cal != nullptr);
+    *fn_wg = pick_stats_wg(stride, hi - lo - 1, d_cal != nullptr);
+    if (*fn_wg) *fn = *fn_wg;
+    SegStatArgs a;
+    a.stride = stride; a.lo = lo; a.hi = hi; a.cal = d_cal;
+    a.std_scale = std_scale; a.delta_scale = 1.0;
+    if (const char *e = sk_tune("SK_SEG_DELTA_SCALE")) { const double v = atof(e); if (v > 0) a.delta_scale = v; }
+    a.row16 = sk_segment_fast_row16(stride);
+    a.hints = nullptr; a.e1 = 1;
+    return a;
+}
+
+// One chunk's statistics kernel (a: the chunk's rows, lengths, outputs and retry list) and the numpy-order redo of the
+// reads it lists.  The single-set launcher below and the masks-only one (the parameter sweep, sk_sweep.hip) both run it.
+int stats_and_redo(sk_ctx *c, segstat_fn fn, bool wg, const SegStatArgs &a, int per_cu, int rounds, int32_t lo, int32_t hi,
+                   double *d_scratch)
+{
+    // persistent grid: a whole number of "rounds" of what the chip actually holds (6 workgroups per CU at 78
+    // VGPRs, not the 8 the thread limit allows) -- with 8 assumed the last round ran a third full
+    int resident = per_cu;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void *)fn, 64 * WPB, 0) != hipSuccess || resident < 1)
+        resident = per_cu;
+    if (resident > per_cu) resident = per_cu;
+    const long long g = (long long)c->num_cu * resident * rounds;
+    const long long need = wg ? (long long)a.nreads : ((long long)a.nreads + WPB - 1) / WPB;   // (a workgroup per read / per WPB reads)
+    const int grid = (int)(g > need ? need : g);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * WPB), 0, c->stream, a);
+    SK_HIP(hipGetLastError());
+    // reads whose ceil(top) / floor(bot) could not be certified: numpy-order statistics, masks rewritten in place
+    // (reads too long for the redo's LDS copy: one scratch row per workgroup of its persistent grid, <= one per CU)
+    c->redo_off.push_back((size_t)(a.retry - (int32_t *)c->redo.p));
+    if (a.cal) {
+        // (pA: the listed reads from their float64 values, one scratch row of doubles per workgroup)
+        const int g2 = a.nreads < c->num_cu ? a.nreads : c->num_cu;
+        int rc = sk_launch_prep_pa_listed(c, a.sig, a.stride, a.len, a.cal, a.retry + 1, a.retry, g2, (double)lo, (double)hi,
+                                          a.std_scale, d_scratch, a.stride, a.prep, a.mask2, a.row16);
+        if (rc) return rc;
+    }
+    int16_t *scratch_rows = nullptr;
+    if (!a.cal && a.stride * (int64_t)sizeof(int16_t) > 24 * 1024) {
+        int rc0 = sk_reserve(c, &c->comp, (size_t)c->num_cu * (size_t)a.stride * sizeof(int16_t));
+        if (rc0) return rc0;
+        scratch_rows = (int16_t *)c->comp.p;
+    }
+    if (!a.cal) {
+        int rc = sk_launch_prep_i16(c, a.sig, a.stride, a.len, a.nreads, lo, hi, SK_PREP_SEGMENT, a.std_scale, scratch_rows, a.prep,
+                                    nullptr, 0, 0, 0x7fffffff, a.retry + 1, a.retry, a.mask2, a.row16);
+        if (rc) return rc;
+    }
+    return SK_OK;
+}
+
 } // namespace
 
 // 16-byte entries per read in the {in band, kept} mask: 8 per 512-sample tile the statistics kernel holds
@@ -1687,14 +1743,8 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
                            int32_t *d_retry, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
                            const double *d_cal, double *d_scratch)
 {
-    segstat_fn fn = pick_stats(stride, hi - lo - 1, d_cal != nullptr);
-    const segstat_fn fn_wg = pick_stats_wg(stride, hi - lo - 1, d_cal != nullptr);
-    if (fn_wg) fn = fn_wg;
-    SegStatArgs a;
-    a.stride = stride; a.lo = lo; a.hi = hi; a.cal = d_cal;
-    a.std_scale = p->std_scale; a.delta_scale = 1.0;
-    if (const char *e = sk_tune("SK_SEG_DELTA_SCALE")) { const double v = atof(e); if (v > 0) a.delta_scale = v; }
-    a.row16 = sk_segment_fast_row16(stride);
+    segstat_fn fn, fn_wg;
+    SegStatArgs a = stats_setup(stride, lo, hi, p->std_scale, d_cal, &fn, &fn_wg);
 
     bool fast;
     const WalkParams wp = walk_params(p, &fast);
@@ -1737,38 +1787,7 @@ int sk_launch_segment_fast(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
         a.prep = d_prep + r0; a.mask2 = (uint4 *)d_mask2 + (int64_t)r0 * a.row16; a.retry = retry;
         a.hints = hints0 ? hints0 + (int64_t)r0 * SEG_HINTS : nullptr;
         a.cal = d_cal ? d_cal + 2 * (int64_t)r0 : nullptr;
-        // persistent grid: a whole number of "rounds" of what the chip actually holds (6 workgroups per CU at 78
-        // VGPRs, not the 8 the thread limit allows) -- with 8 assumed the last round ran a third full
-        int resident = per_cu;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void *)fn, 64 * WPB, 0) != hipSuccess || resident < 1)
-            resident = per_cu;
-        if (resident > per_cu) resident = per_cu;
-        const long long g = (long long)c->num_cu * resident * rounds;
-        const long long need = fn_wg ? (long long)nr : ((long long)nr + WPB - 1) / WPB;   // (a workgroup per read / per WPB reads)
-        const int grid = (int)(g > need ? need : g);
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * WPB), 0, c->stream, a);
-        SK_HIP(hipGetLastError());
-        // reads whose ceil(top) / floor(bot) could not be certified: numpy-order statistics, masks rewritten in place
-        // (reads too long for the redo's LDS copy: one scratch row per workgroup of its persistent grid, <= one per CU)
-        c->redo_off.push_back((size_t)(retry - (int32_t *)c->redo.p));
-        if (d_cal) {
-            // (pA: the listed reads from their float64 values, one scratch row of doubles per workgroup)
-            const int g2 = nr < c->num_cu ? nr : c->num_cu;
-            int rc = sk_launch_prep_pa_listed(c, a.sig, stride, a.len, a.cal, retry + 1, retry, g2, (double)lo, (double)hi,
-                                              p->std_scale, d_scratch, stride, a.prep, a.mask2, a.row16);
-            if (rc) return rc;
-        }
-        int16_t *scratch_rows = nullptr;
-        if (!d_cal && stride * (int64_t)sizeof(int16_t) > 24 * 1024) {
-            int rc0 = sk_reserve(c, &c->comp, (size_t)c->num_cu * (size_t)stride * sizeof(int16_t));
-            if (rc0) return rc0;
-            scratch_rows = (int16_t *)c->comp.p;
-        }
-        if (!d_cal) {
-            int rc = sk_launch_prep_i16(c, a.sig, stride, a.len, nr, lo, hi, SK_PREP_SEGMENT, p->std_scale, scratch_rows, a.prep,
-                                        nullptr, 0, 0, 0x7fffffff, retry + 1, retry, a.mask2, a.row16);
-            if (rc) return rc;
-        }
+        if (int rc = stats_and_redo(c, fn, fn_wg != nullptr, a, per_cu, rounds, lo, hi, d_scratch)) return rc;
         hipStream_t ws = c->stream;
         if (nchunks > 1) {
             SK_HIP(hipEventRecord(c->ev_chunk[ci], c->stream));
@@ -1806,4 +1825,22 @@ int sk_launch_seg_walk_masks(sk_ctx *c, const void *d_mask2, int row16, const in
     SK_HIP(hipGetLastError());
     SK_HIP(hipEventRecord(c->ev[3], c->stream));
     return SK_OK;
+}
+
+// The statistics and the numpy-order redo of sk_launch_segment_fast without the walk (int16 route, no walk hints, one
+// chunk): the {in band, kept} entries of every read at d_mask2 (sk_segment_fast_row16(stride) per read) for a walk that
+// somebody else runs -- the parameter sweep's, once per (lim_low, lim_hi, std_scale) group.  d_retry: nreads + 16 ints
+// (zeroed here).  Same kernels, same order, same certificate as the single-set call.
+int sk_launch_segment_masks(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                            double std_scale, int32_t lo, int32_t hi, sk_prep *d_prep, void *d_mask2, int32_t *d_retry)
+{
+    if (nreads <= 0) return SK_OK;
+    segstat_fn fn, fn_wg;
+    SegStatArgs a = stats_setup(stride, lo, hi, std_scale, nullptr, &fn, &fn_wg);
+    int per_cu = 8, rounds = 8;
+    if (const char *e = sk_tune("SK_PREP_ROUNDS")) { int v = atoi(e); if (v > 0) rounds = v; }
+    if (const char *e = sk_tune("SK_PREP_PERCU")) { int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; }
+    SK_HIP(hipMemsetAsync(d_retry, 0, ((size_t)nreads + 16) * sizeof(int32_t), c->stream));
+    a.sig = d_sig; a.len = d_len; a.nreads = nreads; a.prep = d_prep; a.mask2 = (uint4 *)d_mask2; a.retry = d_retry;
+    return stats_and_redo(c, fn, fn_wg != nullptr, a, per_cu, rounds, lo, hi, nullptr);
 }
