@@ -287,6 +287,36 @@ int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nread
                         const double *motif, int32_t nmotif, int32_t scale_mode,
                         int32_t scale_low, int32_t scale_hi, sk_hit *d_out);
 
+/* Hit lists: up to max_hits non-overlapping matches per read and motif, not only the first argmin of
+ * cost[-1, :] that MotifSeq.py:437-439 keeps (view_region plots that whole row, :506-513).  For read r
+ * (filtered and normalised as above) and motif x of N points, d_j = cost[-1, j] and s_j = the column where
+ * subsequence_path's back-trace from (N-1, j) reaches row 0 (diagonal, then j-1, then i-1).  Greedy:
+ * max_hits times, among the columns j with d_j <= max_dist whose [s_j, j] is disjoint from every interval
+ * taken so far, take the smallest d_j (ties: the smallest j); stop when there is none.  Hit 1 is the record
+ * of sk_motifseq_multi_batch_i16 bit for bit; dist never decreases with rank.
+ * out is [nmotifs][nreads][max_hits] (dist, start, end, n, flags), count [nmotifs][nreads]; unused slots
+ * hold dist NaN, start = end = -1 and the read's n and flags.  Reads flagged SK_FLAG_EMPTY or
+ * SK_FLAG_DEGENERATE have count 0.  max_hits outside 1..64 or a NaN max_dist (+inf: no limit): SK_ERR_INVALID. */
+int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                         int32_t *count);
+/* the same on ragged float64 reads (pA input): read r = sig[off[r] .. off[r+1]) */
+int sk_motifseq_hits_f64(const double *sig, const int64_t *off, int32_t nreads,
+                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                         int32_t *count);
+/* sk_motifseq_hits_f64 for int32 centi-units (value / 100 made on the device, as sk_motifseq_multi_batch_centi) */
+int sk_motifseq_hits_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count);
+/* device-resident form (d_sig, d_len, d_out, d_count device; motifs / motif_off host) */
+int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                             int32_t *d_count);
+
 /* The mlpy boundary itself: dtw_subsequence(x, y) on already-normalised
  * float64 signals (MotifSeq.py:437).  Batch form: read r is y[off[r]..off[r+1]). */
 int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const int64_t *off,

@@ -770,6 +770,103 @@ def motifseq_multi(reads, motifs, scale="medmad", scale_low=0, scale_hi=1200, _p
     return outs
 
 
+# ----------------------------------------------------------------------------
+# MotifSeq hit lists: up to K non-overlapping matches per read and motif
+# ----------------------------------------------------------------------------
+def _hits_args(motifs, max_hits, max_dist):
+    max_hits, max_dist = int(max_hits), float(max_dist)
+    if not 1 <= max_hits <= 64:
+        raise ValueError("max_hits must be in 1..64, got %d" % max_hits)
+    if max_dist != max_dist:
+        raise ValueError("max_dist is NaN")
+    ms = [np.ascontiguousarray(m, dtype=np.float64) for m in motifs]
+    flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros(0)
+    moff = np.concatenate([[0], np.cumsum([m.size for m in ms])]).astype(np.int32)
+    return ms, flat, moff, max_hits, max_dist
+
+
+def motifseq_hits_batch(sig, lens, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0,
+                        scale_hi=1200, devices=None):
+    """Hit lists of every motif against every row of an int16 [R, stride] batch (one filter / statistics pass):
+    a list, per motif, of (hits[R, max_hits] HIT_DTYPE, count[R]).  The block form of motifseq_hits."""
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    R = sig.shape[0]
+    if _too_wide_for_i16(scale_low, scale_hi):
+        # limits wider than the int16 kernels' histogram: the float64 kernels (the same filter, the same statistics)
+        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
+        return motifseq_hits_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
+    L = _lib.load()
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
+    count = np.zeros((len(ms), R), dtype=np.int32)
+
+    def call(lo, hi):
+        part = np.zeros((len(ms), hi - lo, K), dtype=HIT_DTYPE)
+        cnt = np.zeros((len(ms), hi - lo), dtype=np.int32)
+        rc = L.sk_motifseq_hits_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff),
+                                    len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part),
+                                    ptr(cnt))
+        if rc == 0:
+            hits[:, lo:hi] = part
+            count[:, lo:hi] = cnt
+        return rc
+    if R and ms:
+        _over_devices(devices, R, call)
+    return [(hits[k], count[k]) for k in range(len(ms))]
+
+
+def motifseq_hits_ragged_f64(values, off, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0,
+                             scale_hi=1200, devices=None):
+    """Hit lists of every motif against a ragged float64 batch (read r = values[off[r]:off[r+1]]; int32 values are
+    centi-units, value / 100): per motif (hits[R, max_hits], count[R]).  The pA TSV / BLOW5-pA route."""
+    L = _lib.load()
+    centi = isinstance(values, np.ndarray) and values.dtype == np.int32      # converted on the device (value / 100)
+    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
+    entry = L.sk_motifseq_hits_centi if centi else L.sk_motifseq_hits_f64
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = off.size - 1
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
+    count = np.zeros((len(ms), R), dtype=np.int32)
+
+    def call(lo, hi):
+        part = np.zeros((len(ms), hi - lo, K), dtype=HIT_DTYPE)
+        cnt = np.zeros((len(ms), hi - lo), dtype=np.int32)
+        rc = entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms),
+                                    _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt))
+        if rc == 0:
+            hits[:, lo:hi] = part
+            count[:, lo:hi] = cnt
+        return rc
+    if R and ms:
+        _over_devices(devices, R, call)
+    return [(hits[k], count[k]) for k in range(len(ms))]
+
+
+def motifseq_hits(reads, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
+                  devices=None):
+    """Up to max_hits non-overlapping matches of every motif in every read: a list, per motif, of
+    (hits[nreads, max_hits] HIT_DTYPE, count[nreads]).  Rank 1 is motifseq_multi's record; the ranks after it take
+    the next smallest distance whose [start, end] overlaps no earlier hit, up to max_dist.  Unused slots: dist NaN,
+    start = end = -1.  Integer-valued reads go through the int16 kernels, the rest through the float64 ones."""
+    _hits_args(motifs, max_hits, max_dist)                    # (argument errors before any GPU work)
+    ints, arrs, flts = _split_int16(reads)
+    R, K = len(reads), int(max_hits)
+    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32)) for _ in motifs]
+    if ints and len(motifs):
+        buf, lens = pack_i16(arrs)
+        for (h, c), (hi, ci) in zip(res, motifseq_hits_batch(buf, lens, motifs, K, max_dist, scale, scale_low,
+                                                             scale_hi, devices)):
+            h[ints], c[ints] = hi, ci
+    if flts and len(motifs):
+        flat, off = pack_f64([reads[i] for i in flts])
+        for (h, c), (hf, cf) in zip(res, motifseq_hits_ragged_f64(flat, off, motifs, K, max_dist, scale, scale_low,
+                                                                  scale_hi, devices)):
+            h[flts], c[flts] = hf, cf
+    return res
+
+
 def normalise(sig, scale="medmad", scale_low=0, scale_hi=1200):
     """Filtered + normalised signal of one read, as MotifSeq hands it to
     dtw_subsequence (MotifSeq.py:274-289)."""

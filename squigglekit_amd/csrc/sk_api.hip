@@ -486,12 +486,35 @@ static int stage_ragged_f64(sk_ctx *c, const void *sig_any, const int64_t *off, 
     return SK_OK;
 }
 
+static int prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t maxlen,
+                    int32_t scale_mode, int32_t scale_low, int32_t scale_hi);
+
 // device-resident core of the float64 MotifSeq path: d_sig / d_off (zero based, nreads + 1) are device pointers.
 // Filter + statistics once, then one DTW launch set per motif (nmotifs >= 1; motif k = motifs + motif_off[k], its records
 // go to d_out + k * out_stride).
 static int motifseq_multi_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
                                   int64_t maxlen, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
                                   int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *d_out, int64_t out_stride)
+{
+    int rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, scale_mode, scale_low, scale_hi);
+    if (rc) return rc;
+    for (int32_t k = 0; k < nmotifs; k++) {
+        sk_sdtw_args a;
+        a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.stride = 0; a.off = d_off;
+        a.samples_raw = d_sig;                          // (reads the filter left whole are not copied: SK_IFLAG_INPLACE)
+        a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.motif = motifs + motif_off[k];
+        a.nmotif = motif_off[k + 1] - motif_off[k];
+        a.out = d_out + (size_t)k * (size_t)out_stride; a.last_row = nullptr; a.max_len = maxlen; a.force_single = 0;
+        a.accumulate = k > 0 ? 1 : 0;
+        if ((rc = sk_launch_sdtw(c, &a))) return rc;
+    }
+    c->ev_valid = true;
+    return SK_OK;
+}
+
+// filter + statistics of a staged ragged float64 batch: normalisation terms to c->prep, filtered samples to c->comp
+static int prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t maxlen,
+                    int32_t scale_mode, int32_t scale_low, int32_t scale_hi)
 {
     int rc;
     if ((rc = sk_reserve(c, &c->comp, (size_t)(total > 0 ? total : 1) * sizeof(double)))) return rc;
@@ -516,17 +539,6 @@ static int motifseq_multi_dev_f64(sk_ctx *c, const double *d_sig, const int64_t 
     }
     if (rc) return rc;
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
-    for (int32_t k = 0; k < nmotifs; k++) {
-        sk_sdtw_args a;
-        a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.stride = 0; a.off = d_off;
-        a.samples_raw = d_sig;                          // (reads the filter left whole are not copied: SK_IFLAG_INPLACE)
-        a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.motif = motifs + motif_off[k];
-        a.nmotif = motif_off[k + 1] - motif_off[k];
-        a.out = d_out + (size_t)k * (size_t)out_stride; a.last_row = nullptr; a.max_len = maxlen; a.force_single = 0;
-        a.accumulate = k > 0 ? 1 : 0;
-        if ((rc = sk_launch_sdtw(c, &a))) return rc;
-    }
-    c->ev_valid = true;
     return SK_OK;
 }
 
@@ -618,6 +630,189 @@ int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nread
     if (rc) return rc;
     return motifseq_dev_f64(c, d_sig, d_off, nreads, total, max_len, motif, nmotif, scale_mode, scale_low, scale_hi,
                             d_out);
+}
+
+// ------------------------------------------------------------------ MotifSeq hit lists (sk_hits.hip)
+// Up to K disjoint matches per read and motif instead of the first argmin only (MotifSeq.py:437-439 keeps that one;
+// view_region, :506-513, plots the whole last row they come from).  Reads are prepared once (filter + statistics, the
+// kernels of the default path); per motif, chunks of reads go through the exact pass that stores the last rows
+// (MODE_ROWS; the chained pass beyond 1 024 points) and k_hits_select.  The row buffer (12 B per column) is capped at
+// 2 GiB (SK_HITS_ROW_BYTES) and reused chunk after chunk, motif after motif.
+static int check_hits(int32_t max_hits, double max_dist, const void *out, const void *count)
+{
+    if (max_hits < 1 || max_hits > 64) return sk_fail(SK_ERR_INVALID, "max_hits %d outside 1..64", max_hits);
+    if (max_dist != max_dist) return sk_fail(SK_ERR_INVALID, "max_dist is NaN");
+    if (!out || !count) return sk_fail(SK_ERR_INVALID, "NULL out/count");
+    return SK_OK;
+}
+
+// base: feed, samples (+ samples_raw), stride / off, prep, max_len and nreads of prepared reads.  Motif k's records of
+// read r go to d_out[(k * out_reads + r) * K ..], its count to d_count[k * out_reads + r].
+static int hits_core(sk_ctx *c, const sk_sdtw_args &base, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                     int32_t K, double max_dist, sk_hit *d_out, int32_t *d_count, int64_t out_reads)
+{
+    const int64_t row_stride = base.max_len > 0 ? base.max_len : 1;
+    const size_t per_read = sizeof(sk_hit) + (size_t)row_stride * (sizeof(double) + sizeof(int32_t));
+    size_t budget = (size_t)2 << 30;
+    if (const char *e = sk_tune("SK_HITS_ROW_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    int64_t chunk = (int64_t)(budget / per_read);
+    if (chunk < 1) chunk = 1;
+    if (chunk > base.nreads) chunk = base.nreads;
+    int rc = sk_reserve(c, &c->hitrows, (size_t)chunk * per_read);
+    if (rc) return rc;
+    sk_hit *rec = (sk_hit *)c->hitrows.p;
+    double *rowD = (double *)(rec + chunk);
+    int32_t *rowS = (int32_t *)(rowD + (size_t)chunk * row_stride);
+    for (int32_t k = 0; k < nmotifs; k++) {
+        for (int64_t r0 = 0; r0 < base.nreads; r0 += chunk) {
+            sk_sdtw_args a = base;
+            a.nreads = (int32_t)(base.nreads - r0 < chunk ? base.nreads - r0 : chunk);
+            a.prep = base.prep + r0;
+            if (base.feed == SK_FEED_I16) a.samples = (const int16_t *)base.samples + r0 * base.stride;
+            else a.off = base.off + r0;
+            a.motif = motifs + motif_off[k]; a.nmotif = motif_off[k + 1] - motif_off[k];
+            a.out = rec; a.last_row = nullptr; a.force_single = 1; a.accumulate = 0; a.fuse = nullptr;
+            if ((rc = sk_launch_sdtw_rows(c, &a, rowD, rowS))) return rc;
+            const int64_t o = (int64_t)k * out_reads + r0;
+            if ((rc = sk_launch_hits_select(c, rowD, rowS, row_stride, rec, a.nreads, K, max_dist, d_out + o * K,
+                                            d_count + o))) return rc;
+        }
+    }
+    c->retry_dev = false;                               // (no screening counters: finish_dtw_host reads none)
+    return SK_OK;
+}
+
+// int16 rows, device resident: filter + statistics (the kernels of the default path), then hits_core
+static int hits_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                        int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                        int32_t scale_mode, int32_t scale_low, int32_t scale_hi, int32_t K, double max_dist,
+                        sk_hit *d_out, int32_t *d_count, int64_t out_reads)
+{
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    int rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nreads, scale_low, scale_hi,
+                                scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp, d_prep,
+                                nullptr, 0);
+    if (rc) return rc;
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    sk_sdtw_args a;
+    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nreads;
+    a.max_len = stride;
+    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, K, max_dist, d_out, d_count, out_reads))) return rc;
+    c->ev_valid = true;
+    return SK_OK;
+}
+
+// device-resident form: d_out is [nmotifs][nreads][max_hits], d_count [nmotifs][nreads]
+int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                             int32_t *d_count)
+{
+    SK_ENTER(c);
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (rc) return rc;
+    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
+    if ((rc = check_hits(max_hits, max_dist, nreads ? d_out : (void *)1, nreads ? d_count : (void *)1))) return rc;
+    if (nreads == 0) return SK_OK;
+    clamp_limits(&scale_low, &scale_hi);
+    redo_forget(c);
+    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    return hits_dev_i16(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
+                        nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads);
+}
+
+// host buffers: out is [nmotifs][nreads][max_hits], count [nmotifs][nreads]; sub-batches as sk_motifseq_multi_batch_i16
+int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                         int32_t *count)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
+    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
+    if (nreads == 0) return SK_OK;
+    clamp_limits(&scale_low, &scale_hi);
+    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
+    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
+    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
+    if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
+    redo_forget(c);
+    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return hits_dev_i16(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
+                                             (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
+                                             scale_hi, max_hits, max_dist, (sk_hit *)c->out.p + (size_t)r0 * max_hits,
+                                             (int32_t *)c->out2.p + r0, nreads);
+                     });
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// ragged float64 reads (pA TSV / BLOW5 in pA): read r = sig[off[r] .. off[r+1]); out / count as sk_motifseq_hits_i16.
+// centi: int32 centi-units, made float64 on the device (stage_ragged_f64)
+static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
+                       const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                       int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                       int32_t *count);
+int sk_motifseq_hits_f64(const double *sig, const int64_t *off, int32_t nreads,
+                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                         int32_t *count)
+{
+    return hits_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                       max_dist, out, count);
+}
+int sk_motifseq_hits_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count)
+{
+    return hits_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                       max_dist, out, count);
+}
+static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
+                       const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                       int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                       int32_t *count)
+{
+    SK_ENTER(c);
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
+    if (rc) return rc;
+    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
+    if (nreads == 0) return SK_OK;
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
+    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
+    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
+    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    const double *d_sig = (const double *)c->sig.p;
+    const int64_t *d_off = (const int64_t *)c->off.p;
+    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, scale_mode, scale_low, scale_hi))) return rc;
+    sk_sdtw_args a;
+    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
+    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
+    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, max_hits, max_dist, (sk_hit *)c->out.p, (int32_t *)c->out2.p,
+                        nreads))) return rc;
+    c->ev_valid = true;
+    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
 }
 
 // ------------------------------------------------------------------ mlpy boundary (pre-normalised f64)

@@ -73,6 +73,7 @@ struct sk_ctx {
     sk_buf pulltext;  // SquigglePull text: the prefixes and the text of the host entry point
     sk_buf sweep;     // parameter sweep: the sets in walk form, then the summaries (sk_sweep.hip)
     sk_buf sweeprec;  // parameter sweep: the per-(set, read) records of the host entry points
+    sk_buf hitrows;   // hit lists: the last rows of a chunk of reads (cost f64, start i32) and their records
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -224,6 +225,11 @@ struct sk_sdtw_args {
                                           // the writable c->comp / c->prep buffers
 };
 int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a);
+// the exact single pass that also stores every read's last row (cost, back-trace start) at r * max_len (sk_sdtw.hip)
+int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t *rowS);
+// hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]
+int sk_launch_hits_select(sk_ctx *c, const double *rowD, const int32_t *rowS, int64_t row_stride, const sk_hit *rec,
+                          int32_t nreads, int32_t K, double max_dist, sk_hit *out, int32_t *count);
 // fixed-point screening + certified window over all reads (sk_sdtwq.hip); leaves the retry list on the device
 int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, int span2,
                           int32_t *d_retry_cnt, int32_t *d_retry, int32_t *d_early_cnt, int32_t *d_early);

@@ -26,7 +26,7 @@
 //   * the normalisation (x - center) / scale of MotifSeq.py:192-200 / :186-191 is fused into
 //     the sample feed: every L steps each lane normalises one sample of the next block.
 //
-// Three modes of the one kernel template:
+// Modes of the one kernel template:
 //   FULL   one pass carrying D and S (12 of its 28 VALU cycles per cell are the S tracking).
 //   DIST   pass A of the two-pass scheme: D only (16 cycles per cell) -> dist and end; every
 //          CK steps each lane dumps its systolic state (R D's, y, bottom, diag) to HBM.
@@ -35,6 +35,9 @@
 //          restart front carry S = -1; if the optimal path crosses the front the read's start
 //          stays -1 and the read is appended to a retry list (FULL pass on those reads only).
 //          The restart reproduces the state bit for bit, so the result is exact either way.
+//   CHAIN  FULL on one 1 024-row chunk of a longer motif (launch_chained).
+//   ROWS   FULL that also stores the last row, (D[N-1][j], S[N-1][j]) per column: the input of the hit lists
+//          (sk_hits.hip).  12 B per column against 8 VALU instructions per cell.
 #include "sk_sdtw_dev.h"
 #include <math.h>
 #include <stdlib.h>
@@ -262,7 +265,7 @@ void k_sdtw(const sdtw_kargs a)
                         if (l == L - 1 && slot == 0 && j >= 0 && j < n) a.last_row[j] = D[R - 1];
                     }
                 }
-                if constexpr (MODE == MODE_CHAIN) {
+                if constexpr (MODE == MODE_CHAIN || MODE == MODE_ROWS) {
                     if (a.rowD != nullptr && live && l == L - 1 && j >= 0 && j < n) {
                         a.rowD[(int64_t)(r - a.read0) * a.row_stride + j] = D[R - 1];
                         a.rowS[(int64_t)(r - a.read0) * a.row_stride + j] = S[R - 1];
@@ -351,9 +354,11 @@ sdtw_fn pick(int L, int R, int mode)
     if (L == 16) {
         if (mode == MODE_FULL) return pick_r<16, FEED, MODE_FULL>(R);
         if (mode == MODE_DIST) return pick_r<16, FEED, MODE_DIST>(R);
+        if (mode == MODE_ROWS) return pick_r<16, FEED, MODE_ROWS>(R);
         return pick_r<16, FEED, MODE_START>(R);
     }
     if (mode == MODE_FULL) return pick_r<64, FEED, MODE_FULL>(R);
+    if (mode == MODE_ROWS) return pick_r<64, FEED, MODE_ROWS>(R);
     if (mode == MODE_DIST) return pick_r<64, FEED, MODE_DIST>(R);
     if (mode == MODE_CHAIN) return pick_r<64, FEED, MODE_CHAIN>(R);
     return pick_r<64, FEED, MODE_START>(R);
@@ -385,7 +390,8 @@ int launch(sk_ctx *c, sdtw_fn fn, const sdtw_kargs &k, int L, hipStream_t stream
 // with the exact single pass; the last row of a chunk (cost and start column, per read column) goes
 // through memory and enters the next chunk where the virtual row -1 enters the first.  Reads are
 // processed in batches so that the two row buffers stay within a fixed budget.
-static int launch_chained(sk_ctx *c, const sk_sdtw_args *a)
+// finD / finS (or nullptr): the last chunk also stores the motif's last row there, [read][max_len] (MODE_ROWS' output)
+static int launch_chained(sk_ctx *c, const sk_sdtw_args *a, double *finD = nullptr, int32_t *finS = nullptr)
 {
     const int N = a->nmotif;
     const int CH = 64 * 16;
@@ -451,8 +457,8 @@ static int launch_chained(sk_ctx *c, const sk_sdtw_args *a)
             k.P = Pc[i];
             k.prevD = (i > 0) ? bufD[(i - 1) & 1] : nullptr;
             k.prevS = (i > 0) ? bufS[(i - 1) & 1] : nullptr;
-            k.rowD = (i + 1 < nchunks) ? bufD[i & 1] : nullptr;
-            k.rowS = (i + 1 < nchunks) ? bufS[i & 1] : nullptr;
+            k.rowD = (i + 1 < nchunks) ? bufD[i & 1] : (finD ? finD + r0 * row_stride : nullptr);
+            k.rowS = (i + 1 < nchunks) ? bufS[i & 1] : (finS ? finS + r0 * row_stride : nullptr);
             k.last_row = (i + 1 == nchunks && r0 == 0) ? a->last_row : nullptr;
             if ((rc = launch(c, fn, k, 64))) return rc;
         }
@@ -482,6 +488,73 @@ static bool screens(const sk_sdtw_args *a, int span, int ck)
     return true;
 }
 
+// The laid-out motif stays resident between calls; re-upload only when it changes.
+static int upload_layout(sk_ctx *c, const double *motif, int N, int L, int R)
+{
+    const int P = L * R - N;
+    const bool same = c->motif.p && c->motif_L == L && c->motif_src.size() == (size_t)N &&
+                      memcmp(c->motif_src.data(), motif, (size_t)N * sizeof(double)) == 0;
+    if (!same) {
+        // the previous launch may still be reading the old layout
+        SK_HIP(hipStreamSynchronize(c->stream));
+        c->motif_host.assign((size_t)L * R, 0.0);
+        int row = 0;
+        for (int l = 0; l < L; l++) {
+            int cnt = (l < P) ? R - 1 : R;
+            for (int k = 0; k < cnt; k++) c->motif_host[(size_t)l * R + k] = motif[row++];
+        }
+        if (row != N) return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
+        int rc = sk_reserve(c, &c->motif, c->motif_host.size() * sizeof(double));
+        if (rc) return rc;
+        SK_HIP(hipMemcpyAsync(c->motif.p, c->motif_host.data(), c->motif_host.size() * sizeof(double),
+                              hipMemcpyHostToDevice, c->stream));
+        c->motif_src.assign(motif, motif + N);
+        c->motif_L = L;
+        c->motif64_valid = false;
+        c->motifq_valid = false;
+    }
+    return SK_OK;
+}
+
+// (L, R) of the exact single pass for a motif of N <= 1 024 points over `nreads` reads (the choice sk_launch_sdtw makes)
+static void exact_shape(int N, int32_t nreads, int *L, int *R)
+{
+    if (N <= 16 * 16) { *L = 16; *R = (N + 15) / 16; }
+    else              { *L = 64; *R = (N + 63) / 64; }
+    // A couple of thousand reads cannot fill the chip four to a wavefront: what counts then is the
+    // latency of one sweep, which is shorter with the read spread over 64 lanes (fewer rows per lane).
+    // Measured at 163 points x 4 000 samples: 64 reads 1.12 -> 0.54 ms, 1 024 reads 0.52 -> 0.29 ms,
+    // break-even near 4 096 reads.
+    int small_max = 2048;
+    if (const char *e = sk_tune("SK_DTW_SMALL_MAX")) { int v = atoi(e); if (v >= 0) small_max = v; }
+    if (*L == 16 && N >= 32 && nreads <= small_max && !sk_tune("SK_DTW_NO_SMALL")) { *L = 64; *R = (N + 63) / 64; }
+}
+
+// The exact single pass over a->nreads reads that also stores every read's last row: D[N-1][j] to rowD and the
+// back-trace start S[N-1][j] to rowS, read r at r * a->max_len (r relative to a's pointers).  The hit lists of
+// sk_hits.hip select from them.  a->out receives the usual records (n and flags included).  No screening scheme:
+// its certificate proves the argmin of the row only, not the row.
+int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t *rowS)
+{
+    const int N = a->nmotif;
+    if (N <= 0) return sk_fail(SK_ERR_INVALID, "empty motif");
+    if (a->nreads <= 0) return SK_OK;
+    if (a->fuse) return sk_fail(SK_ERR_INVALID, "internal: fused prologue without a screening pass");
+    if (N > 64 * 16) return launch_chained(c, a, rowD, rowS);
+    int L, R;
+    exact_shape(N, a->nreads, &L, &R);
+    int rc = upload_layout(c, a->motif, N, L, R);
+    if (rc) return rc;
+    sdtw_kargs k;
+    memset(&k, 0, sizeof k);
+    k.samples = a->samples; k.samples_raw = a->samples_raw; k.stride = a->stride; k.off = a->off; k.prep = a->prep;
+    k.nreads = a->nreads; k.read0 = 0; k.xlay = (const double *)c->motif.p; k.P = L * R - N;
+    k.out = a->out; k.rowD = rowD; k.rowS = rowS; k.row_stride = a->max_len > 0 ? a->max_len : 1;
+    sdtw_fn fn = pick_any(a->feed, L, R, MODE_ROWS);
+    if (!fn) return sk_fail(SK_ERR_UNSUPPORTED, "no kernel for L=%d R=%d", L, R);
+    return launch(c, fn, k, L);
+}
+
 int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a_in)
 {
     const sk_sdtw_args *a = a_in;
@@ -505,41 +578,12 @@ int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a_in)
             a = &a_unfused;
         }
     }
+    if (N > 64 * 16) return launch_chained(c, a);   // more rows than a wavefront keeps in registers
     int L, R;
-    if (N <= 16 * 16)      { L = 16; R = (N + 15) / 16; }
-    else if (N <= 64 * 16) { L = 64; R = (N + 63) / 64; }
-    else return launch_chained(c, a);               // more rows than a wavefront keeps in registers
-    // A couple of thousand reads cannot fill the chip four to a wavefront: what counts then is the
-    // latency of one sweep, which is shorter with the read spread over 64 lanes (fewer rows per lane).
-    // Measured at 163 points x 4 000 samples: 64 reads 1.12 -> 0.54 ms, 1 024 reads 0.52 -> 0.29 ms,
-    // break-even near 4 096 reads.
-    int small_max = 2048;
-    if (const char *e = sk_tune("SK_DTW_SMALL_MAX")) { int v = atoi(e); if (v >= 0) small_max = v; }
-    if (L == 16 && N >= 32 && a->nreads <= small_max && !sk_tune("SK_DTW_NO_SMALL")) { L = 64; R = (N + 63) / 64; }
+    exact_shape(N, a->nreads, &L, &R);
     const int P = L * R - N;                 // short lanes (own R-1 rows), always < L
 
-    // The laid-out motif stays resident between calls; re-upload only when it changes.
-    const bool same = c->motif.p && c->motif_L == L && c->motif_src.size() == (size_t)N &&
-                      memcmp(c->motif_src.data(), a->motif, (size_t)N * sizeof(double)) == 0;
-    if (!same) {
-        // the previous launch may still be reading the old layout
-        SK_HIP(hipStreamSynchronize(c->stream));
-        c->motif_host.assign((size_t)L * R, 0.0);
-        int row = 0;
-        for (int l = 0; l < L; l++) {
-            int cnt = (l < P) ? R - 1 : R;
-            for (int k = 0; k < cnt; k++) c->motif_host[(size_t)l * R + k] = a->motif[row++];
-        }
-        if (row != N) return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
-        int rc = sk_reserve(c, &c->motif, c->motif_host.size() * sizeof(double));
-        if (rc) return rc;
-        SK_HIP(hipMemcpyAsync(c->motif.p, c->motif_host.data(), c->motif_host.size() * sizeof(double),
-                              hipMemcpyHostToDevice, c->stream));
-        c->motif_src.assign(a->motif, a->motif + N);
-        c->motif_L = L;
-        c->motif64_valid = false;
-        c->motifq_valid = false;
-    }
+    if (int rc = upload_layout(c, a->motif, N, L, R)) return rc;
 
     sdtw_kargs k;
     memset(&k, 0, sizeof k);

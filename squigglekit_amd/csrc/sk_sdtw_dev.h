@@ -12,7 +12,8 @@ constexpr int DPP_ROW_SHL1  = 0x101;   // lane i <- lane i+1 inside a row of 16;
 constexpr int DPP_WAVE_SHL1 = 0x130;   // lane i <- lane i+1 across the wave; lane 63 keeps `old`
 constexpr int DPP_WAVE_ROL1 = 0x134;   // lane i <- lane i+1 across the wave (rotate)
 
-enum { MODE_FULL = 0, MODE_DIST = 1, MODE_START = 2, MODE_CHAIN = 3 };   // CHAIN: FULL on one row chunk of a long motif
+enum { MODE_FULL = 0, MODE_DIST = 1, MODE_START = 2, MODE_CHAIN = 3,   // CHAIN: FULL on one row chunk of a long motif
+       MODE_ROWS = 4 };                                                   // ROWS: FULL that also stores the last row (hit lists)
 
 // Fixed-point screening (sk_sdtwq.hip): one unit = 2^-22 of a normalised signal unit.
 constexpr int      QS     = 22;
@@ -116,7 +117,7 @@ struct sdtw_kargs {
     const int32_t *wl_count;
     int32_t       *soft;        // where a read goes whose path crossed THIS look-back (nullptr: the exact retry list)
     int32_t       *soft_cnt;
-    // row-chunked motifs (MODE_CHAIN): the last row of the chunk above / of this chunk, per column
+    // row-chunked motifs (MODE_CHAIN): the last row of the chunk above / of this chunk, per column; MODE_ROWS: the last row
     const double  *prevD;       // [slot][row_stride] or nullptr (first chunk: virtual row -1)
     const int32_t *prevS;
     double        *rowD;        // [slot][row_stride] or nullptr (last chunk)

@@ -5,7 +5,7 @@ scale_outliers + medmad/zscale + dtw_subsequence run on the GPU (batched, C ABI)
 the scoring of MotifSeq.py:441-445 stays in Python so the printed floats are the
 reference's digit for digit.  fast5 input (-f / -p) goes through h5py when it is importable and
 through the built-in reader (hdf5min.py) otherwise, with the reference's stderr messages.
-Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16.
+Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p.
 Whole chunks of plain integer reads (TSV chunks, BLOW5 / packed blocks) go to the GPU as one batch and their rows are
 formatted natively (csrc/sk_io.cpp writes floats as Python does); anything unusual takes the per-read route.
 """
@@ -79,7 +79,21 @@ def build_parser():
     p.add_argument("--stats", action="store_true", help="[extension] the same as one line on stderr at the end")
     p.add_argument("--strict-compat", action="store_true",
                    help="[extension] keep the reference's -m defect (empty model order: header only)")
+    p.add_argument("--hits", type=int, default=None, metavar="K",
+                   help="[extension] up to K non-overlapping matches per read and motif (1..64), best first")
+    p.add_argument("--min_hit_p", type=float, default=None, metavar="P",
+                   help="[extension] with --hits: leave out the lines whose hit_Probability is below P")
     return p
+
+
+def check_hit_flags(parser, args):
+    """--hits / --min_hit_p: what they take, and what they do not combine with."""
+    if args.hits is not None and not 1 <= args.hits <= 64:
+        parser.error("--hits must be between 1 and 64")
+    if args.min_hit_p is not None and args.hits is None:
+        parser.error("--min_hit_p needs --hits")
+    if args.hits is not None and args.after_stall:
+        parser.error("--hits does not combine with --after_stall")
 
 
 def norm_cdf(z):
@@ -147,24 +161,35 @@ class _Batcher:
                 self.sigs[i] = s
         if sigs:
             _STATS[0].batch(len(sigs))
-        hits = (api.motifseq_multi(sigs, [np.asarray(self.models[name], dtype=np.float64) for name in self.order],
-                                   a.scale, a.scale_low, a.scale_hi) if sigs else [[] for _ in self.order])
+        motifs = [np.asarray(self.models[name], dtype=np.float64) for name in self.order]
+        if a.hits is not None:
+            hits = api.motifseq_hits(sigs, motifs, a.hits, float("inf"), a.scale, a.scale_low, a.scale_hi)
+        else:
+            hits = (api.motifseq_multi(sigs, motifs, a.scale, a.scale_low, a.scale_hi) if sigs
+                    else [[] for _ in self.order])
         slot = {i: k for k, i in enumerate(live)}
         for i, (fast5, read_id) in enumerate(self.meta):
             if self.sigs[i] is None:
                 sys.stderr.write(read_id)
                 continue
             r = slot[i]
-            self.emit(fast5, read_id, [hits[c][r] for c in range(len(self.order))], self.sigs[i],
-                      None if cuts is None else int(cuts[r]))
+            self.emit(fast5, read_id, self.of_read(hits, r), self.sigs[i], None if cuts is None else int(cuts[r]))
         self.meta, self.sigs = [], []
 
+    def of_read(self, hits, r):
+        """Read r's entry per motif: its record, or with --hits (its records [K], their count)."""
+        if self.args.hits is not None:
+            return [(h[r], cnt[r]) for h, cnt in hits]
+        return [hits[c][r] for c in range(len(self.order))]
+
     def emit(self, fast5, read_id, hits, sig, cut):
-        """The rows of one read, one per motif (MotifSeq.py:436-449)."""
+        """The rows of one read, one per motif (MotifSeq.py:436-449); with --hits one per match, best first."""
         a = self.args
         norm = None
         for c, name in enumerate(self.order):
-            h = hits[c]
+            h, found = hits[c], None
+            if isinstance(h, tuple):                                # --hits: slot 0 carries the read's flags
+                h, found = h[0][0], [(float(x["dist"]), int(x["start"]), int(x["end"])) for x in h[0][:h[1]]]
             if h["flags"] & 1:
                 sys.stderr.write("MotifSeq: no sample of {} survived the outlier limits; skipped\n".format(read_id))
                 break
@@ -186,21 +211,25 @@ class _Batcher:
                     sys.stderr.write("MotifSeq: {} has MAD 0 and is too long for the literal evaluation of the reference's "
                                      "nan row ({} samples x {} points); skipped\n".format(read_id, len(norm), len(self.models[name])))
                     break
-            else:
-                dist, start, end = float(h["dist"]), int(h["start"]), int(h["end"])
-            mod_mean = (a.slope * self.lens[c]) + a.intercept
-            mod_stdev = mod_mean * a.std_const
-            z = (dist - mod_mean) / mod_stdev
-            p_value = norm_cdf(z)
-            hit_p = (1 - p_value) * 100
-            row = [fast5, read_id, name, start, end, end - start, dist, mod_mean, mod_stdev, z, p_value, hit_p]
-            if a.sig_extract:
-                if norm is None:
-                    norm = api.normalise(sig, a.scale, a.scale_low, a.scale_hi)
-                row.append("\t".join(str(v) for v in norm[start:end]))
-            if cut is not None:
-                row.append(cut)
-            print("\t".join("{}".format(v) for v in row))
+                found = [(dist, start, end)]
+            elif found is None:
+                found = [(float(h["dist"]), int(h["start"]), int(h["end"]))]
+            for dist, start, end in found:
+                mod_mean = (a.slope * self.lens[c]) + a.intercept
+                mod_stdev = mod_mean * a.std_const
+                z = (dist - mod_mean) / mod_stdev
+                p_value = norm_cdf(z)
+                hit_p = (1 - p_value) * 100
+                if a.min_hit_p is not None and hit_p < a.min_hit_p:
+                    continue
+                row = [fast5, read_id, name, start, end, end - start, dist, mod_mean, mod_stdev, z, p_value, hit_p]
+                if a.sig_extract:
+                    if norm is None:
+                        norm = api.normalise(sig, a.scale, a.scale_low, a.scale_hi)
+                    row.append("\t".join(str(v) for v in norm[start:end]))
+                if cut is not None:
+                    row.append(cut)
+                print("\t".join("{}".format(v) for v in row))
 
     def table(self, n, fast5_col, id_col, hits):
         """The rows of n reads x every motif through the native formatter (file order, read-major).  Returns False --
@@ -239,6 +268,48 @@ class _Batcher:
         fastio.write_stdout(text)
         return True
 
+    def table_hits(self, n, fast5_col, id_col, hits):
+        """table() for --hits: per read, per motif, its `count` matches in rank order (lines below --min_hit_p left
+        out), through the same formatter and the same scoring arithmetic."""
+        a = self.args
+        K = len(self.order)
+        if a.sig_extract or any(bool((h[:, 0]["flags"] & 3).any()) for h, _ in hits):
+            return False
+        names = [nm.encode() for nm in self.order]
+        nblob = b"".join(names)
+        noff = np.concatenate([[0], np.cumsum([len(x) for x in names])]).astype(np.int64)
+        nspan = np.stack([noff[:-1], noff[1:]], axis=1)
+        mm = np.array([(a.slope * self.lens[c]) + a.intercept for c in range(K)], dtype=np.float64)
+        ms = mm * a.std_const
+        recs = np.stack([h for h, _ in hits], axis=1)                        # [n, K motifs, slots]
+        cnt = np.stack([c for _, c in hits], axis=1).ravel().astype(np.int64)   # per (read, motif), read-major
+        pair = np.repeat(np.arange(n * K), cnt)
+        rank = np.arange(pair.size) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        ri, ci = pair // K, pair % K
+        sel = recs[ri, ci, rank]
+        dist, start, end = sel["dist"], sel["start"], sel["end"]
+        with np.errstate(all="ignore"):
+            z = (dist - mm[ci]) / ms[ci]                                     # MotifSeq.py:441-445, as table()
+            pv = norm_cdf(z)
+            hp = (1 - pv) * 100
+        if a.min_hit_p is not None:
+            keep = ~(hp < a.min_hit_p)
+            ri, ci, dist, start, end, z, pv, hp = (v[keep] for v in (ri, ci, dist, start, end, z, pv, hp))
+
+        def per_row(col):                                                    # one entry per read -> one per line
+            kind = col[0]
+            if kind == "span":
+                return ("span", col[1], np.asarray(col[2])[ri])
+            if kind == "i32":
+                return ("i32", np.asarray(col[1])[ri])
+            return col
+        cols = [per_row(fast5_col), per_row(id_col), ("span", nblob, nspan[ci]), ("i32", start), ("i32", end),
+                ("i32", end - start), ("f64", dist), ("f64", mm[ci]), ("f64", ms[ci]), ("f64", z), ("f64", pv),
+                ("f64", hp)]
+        if ri.size:
+            fastio.write_stdout(fastio.fmt_rows(int(ri.size), cols))
+        return True
+
     def rows(self, rows, nsamp, fast5_col, id_col, name_of, id_of):
         """A block of plain int16 reads (BLOW5 / packed input): one GPU batch, native table; the per-read route only
         when a read is flagged.  One block deep pipeline: the GPU call of this block runs on a worker thread while the
@@ -261,6 +332,9 @@ class _Batcher:
         def call():
             _mark("GPU call starts")
             try:
+                if a.hits is not None:
+                    return api.motifseq_hits_batch(rows, nsamp, motifs, a.hits, float("inf"), a.scale, a.scale_low,
+                                                   a.scale_hi)
                 return api.motifseq_multi_batch(rows, nsamp, motifs, a.scale, a.scale_low, a.scale_hi)
             finally:
                 _mark("GPU call ends")
@@ -281,7 +355,11 @@ class _Batcher:
             from concurrent.futures import ThreadPoolExecutor
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d float64 reads to the GPU worker" % fb.n)
-        job = self._worker.submit(api.motifseq_multi_ragged_f64, fb.batch_values(), fb.off, motifs, a.scale, a.scale_low, a.scale_hi)
+        if a.hits is not None:
+            job = self._worker.submit(api.motifseq_hits_ragged_f64, fb.batch_values(), fb.off, motifs, a.hits,
+                                      float("inf"), a.scale, a.scale_low, a.scale_hi)
+        else:
+            job = self._worker.submit(api.motifseq_multi_ragged_f64, fb.batch_values(), fb.off, motifs, a.scale, a.scale_low, a.scale_hi)
         prev, self._pending = self._pending, (job, fb.n, ("span", fb.buf, fb.spans("name")), ("span", fb.buf, fb.spans("id")),
                                               lambda i, b=fb: b.text("name", i), lambda i, b=fb: b.text("id", i),
                                               lambda i, b=fb: b.values[b.off[i]:b.off[i + 1]])
@@ -298,7 +376,7 @@ class _Batcher:
         hits = job.result()
         _STATS[0].batch(n)
         _mark("block of %d reads back from the GPU" % n)
-        if self.table(n, fast5_col, id_col, hits):
+        if (self.table_hits if self.args.hits is not None else self.table)(n, fast5_col, id_col, hits):
             _mark("table written")
             return
         if self._pending is not None and (self.args.sig_extract or self.args.strict_compat):
@@ -307,7 +385,7 @@ class _Batcher:
             # of scratch buffers, no lock: the next block's call has to be over first (its result stays in the future)
             self._pending[0].exception()
         for i in range(n):
-            self.emit(name_of(i), id_of(i), [hits[c][i] for c in range(len(self.order))],
+            self.emit(name_of(i), id_of(i), self.of_read(hits, i),
                       sig_of(i) if (self.args.sig_extract or self.args.strict_compat) else None, None)
 
     def block(self, blk):
@@ -328,7 +406,24 @@ class _Batcher:
             return
         self.drain()                                                        # (what follows prints directly)
         res, hits = {}, None
-        if idx.size:
+        if idx.size and a.hits is not None:
+            rows = blk.rows[idx] if idx.size != blk.n else blk.rows
+            hits = api.motifseq_hits_batch(rows, blk.nsamp[idx], [np.asarray(self.models[n], dtype=np.float64)
+                                                                   for n in self.order],
+                                           a.hits, float("inf"), a.scale, a.scale_low, a.scale_hi)
+            res = {int(i): k for k, i in enumerate(idx)}
+            cols = []
+            for c in range(len(self.order)):                                # the scoring of every slot, as below
+                h, cnt = hits[c]
+                mod_mean = (a.slope * self.lens[c]) + a.intercept
+                mod_stdev = mod_mean * a.std_const
+                with np.errstate(all="ignore"):
+                    z = (h["dist"] - mod_mean) / mod_stdev
+                    pv = norm_cdf(z)
+                    hp = (1 - pv) * 100
+                cols.append((h[:, 0]["flags"].tolist(), h["start"].tolist(), h["end"].tolist(), h["dist"].tolist(),
+                             mod_mean, mod_stdev, z.tolist(), pv.tolist(), hp.tolist(), cnt.tolist()))
+        elif idx.size:
             rows = blk.rows[idx] if idx.size != blk.n else blk.rows
             hits = api.motifseq_multi_batch(rows, blk.nsamp[idx], [np.asarray(self.models[n], dtype=np.float64)
                                                                     for n in self.order],
@@ -352,9 +447,19 @@ class _Batcher:
             if k is not None:
                 if a.sig_extract or any(cols[c][0][k] & 3 for c in range(len(self.order))):
                     sig = blk.rows[i, :blk.nsamp[i]] if (a.sig_extract or a.strict_compat) else None   # the general route: -x, flagged reads
-                    self.emit(blk.name(i), blk.read_id(i), [hits[c][k] for c in range(len(self.order))], sig, None)
+                    self.emit(blk.name(i), blk.read_id(i), self.of_read(hits, k), sig, None)
                     continue
                 fast5, read_id = blk.name(i), blk.read_id(i)
+                if a.hits is not None:
+                    for c, name in enumerate(self.order):
+                        _, st, en, dist, mm, ms, z, pv, hp, cnt = cols[c]
+                        for q in range(cnt[k]):
+                            if a.min_hit_p is not None and hp[k][q] < a.min_hit_p:
+                                continue
+                            print("\t".join((fast5, read_id, name, str(st[k][q]), str(en[k][q]), str(en[k][q] - st[k][q]),
+                                             repr(dist[k][q]), str(mm), str(ms), repr(z[k][q]), repr(pv[k][q]),
+                                             repr(hp[k][q]))))
+                    continue
                 for c, name in enumerate(self.order):
                     _, st, en, dist, mm, ms, z, pv, hp = cols[c]
                     print("\t".join((fast5, read_id, name, str(st[k]), str(en[k]), str(en[k] - st[k]), repr(dist[k]),
@@ -390,6 +495,7 @@ def main(argv=None):
     parser = build_parser()
     argv = sys.argv[1:] if argv is None else argv
     args = parser.parse_args(argv)
+    check_hit_flags(parser, args)
     if len(argv) == 0:                               # MotifSeq.py:129-131
         parser.print_help(sys.stderr)
         sys.exit(1)
