@@ -317,6 +317,39 @@ int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t
                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
                              int32_t *d_count);
 
+/* Alignment paths: the hit list, and per hit which samples belong to which point of the motif.  mlpy's
+ * dtw_subsequence returns the whole warping path (MotifSeq.py:437); the path of a hit (dist, start, end) is
+ * subsequence_path's back-trace in the full N x n matrix from (N-1, end): while i > 0 -- at j == 0 up, else
+ * with mc = min3(up, diag, left): diagonal if diag == mc, else left if left == mc, else up -- reversed.  In it
+ * motif point i covers one contiguous column range [a_i, b_i], with a_0 = b_0 = start, b_{N-1} = end and
+ * a_{i+1} = b_i or b_i + 1; the path is (i, j) for j = a_i .. b_i, i ascending.
+ * spans holds (a_i, b_i) per hit, in filtered coordinates like start / end: motif k's block begins at
+ * 2 * max_hits * nreads * motif_off[k] int32, inside it [read][hit][N_k][2].  A hit without a path -- an unused
+ * slot, a read flagged SK_FLAG_EMPTY or SK_FLAG_DEGENERATE, a failed self-check -- has all spans -1.
+ * out / count: exactly what the sk_motifseq_hits_* twin returns; the other arguments are its own. */
+int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                          int32_t *count, int32_t *spans);
+int sk_motifseq_paths_f64(const double *sig, const int64_t *off, int32_t nreads,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                          int32_t *count, int32_t *spans);
+int sk_motifseq_paths_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                            const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                            int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                            int32_t *count, int32_t *spans);
+/* device-resident form (d_sig, d_len, d_out, d_count, d_spans device; motifs / motif_off host) */
+int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                              int32_t *d_count, int32_t *d_spans);
+/* Every path is checked on the device: the kernel recomputes the DTW on the window y[start .. end] alone, whose
+ * corner must carry the bits of the hit's dist and whose back-trace must end on (0, start).  A hit that fails
+ * gets spans -1 and is counted here, for the calling thread's last paths call (-1: none yet).  A healthy build
+ * reports 0. */
+int sk_last_path_mismatches(void);
+
 /* The mlpy boundary itself: dtw_subsequence(x, y) on already-normalised
  * float64 signals (MotifSeq.py:437).  Batch form: read r is y[off[r]..off[r+1]). */
 int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const int64_t *off,
@@ -325,6 +358,9 @@ int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const
  * ny doubles) receives cost[-1, :] (what view_region plots, MotifSeq.py:507). */
 int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
                        double *dist, int32_t *start, int32_t *end, double *cost_last_row);
+/* Single pair with the path of its match: spans [nx][2] as above (mlpy's third return value). */
+int sk_dtw_subsequence_path(const double *x, int32_t nx, const double *y, int32_t ny,
+                            double *dist, int32_t *start, int32_t *end, int32_t *spans);
 
 /* The same call in mlpy's own C arithmetic for inputs that hold inf / nan -- `min3` as "a; if (b < m) m = b; if (c < m)
  * m = c", fabs, np.argmin's first-NaN rule, the back-trace of subsequence_path, all evaluated literally by one GPU lane

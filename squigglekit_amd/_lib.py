@@ -168,6 +168,16 @@ ABI = {
                                          C.c_int32, C.c_double, _vp, _vp]),
     "sk_motifseq_hits_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_motifseq_paths_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_paths_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_paths_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_paths_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_last_path_mismatches": (C.c_int, []),
+    "sk_dtw_subsequence_path": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _dp, _i32p, _i32p, _vp]),
     "sk_motifseq_dev_f64": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _vp]),
     "sk_dtw_subsequence_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp]),

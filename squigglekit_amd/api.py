@@ -867,6 +867,141 @@ def motifseq_hits(reads, motifs, max_hits=8, max_dist=float("inf"), scale="medma
     return res
 
 
+# ----------------------------------------------------------------------------
+# MotifSeq alignment paths: per hit, the samples each motif point covers
+# ----------------------------------------------------------------------------
+_path_lock = __import__("threading").Lock()
+_path_mismatches = [-1]
+
+
+def _paths_over(devices, R, ms, moff, K, entry_call):
+    """Runs entry_call(lo, hi, hits_part, count_part, spans_part) over the devices; returns per motif
+    (hits[R, K], count[R], spans[R, K, N, 2]).  The self-check counters of the shards add up (last_path_mismatches)."""
+    L = _lib.load()
+    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
+    count = np.zeros((len(ms), R), dtype=np.int32)
+    spans = [np.full((R, K, m.size, 2), -1, dtype=np.int32) for m in ms]
+    total = int(moff[-1])
+    with _path_lock:
+        _path_mismatches[0] = 0
+
+    def call(lo, hi):
+        n = hi - lo
+        part = np.zeros((len(ms), n, K), dtype=HIT_DTYPE)
+        cnt = np.zeros((len(ms), n), dtype=np.int32)
+        sp = np.zeros(2 * K * n * total, dtype=np.int32)
+        rc = entry_call(lo, hi, part, cnt, sp)
+        if rc == 0:
+            hits[:, lo:hi] = part
+            count[:, lo:hi] = cnt
+            for k, m in enumerate(ms):                      # motif k's block: [read][hit][N_k][2] at 2 K n moff[k]
+                b = 2 * K * n * int(moff[k])
+                spans[k][lo:hi] = sp[b:b + 2 * K * n * m.size].reshape(n, K, m.size, 2)
+            bad = L.sk_last_path_mismatches()
+            with _path_lock:
+                _path_mismatches[0] += max(bad, 0)
+        return rc
+    if R and ms:
+        _over_devices(devices, R, call)
+    return [(hits[k], count[k], spans[k]) for k in range(len(ms))]
+
+
+def motifseq_paths_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
+                         scale_hi=1200, devices=None):
+    """motifseq_hits_batch plus, per hit, the spans of its warping path: a list, per motif, of
+    (hits[R, max_hits], count[R], spans[R, max_hits, N, 2]).  spans[r, h, i] = (a_i, b_i): the filtered samples motif
+    point i covers in hit h of read r (expand_path turns them into mlpy's (px, py)); -1 where there is no path."""
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    R = sig.shape[0]
+    if _too_wide_for_i16(scale_low, scale_hi):
+        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
+        return motifseq_paths_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
+    L = _lib.load()
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, part, cnt, sp):
+        return L.sk_motifseq_paths_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff),
+                                       len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part),
+                                       ptr(cnt), ptr(sp))
+    return _paths_over(devices, R, ms, moff, K, call)
+
+
+def motifseq_paths_ragged_f64(values, off, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
+                              scale_hi=1200, devices=None):
+    """motifseq_hits_ragged_f64 plus the spans (see motifseq_paths_batch); int32 values are centi-units."""
+    L = _lib.load()
+    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
+    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
+    entry = L.sk_motifseq_paths_centi if centi else L.sk_motifseq_paths_f64
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = off.size - 1
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, part, cnt, sp):
+        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
+                     int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt), ptr(sp))
+    return _paths_over(devices, R, ms, moff, K, call)
+
+
+def motifseq_paths(reads, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
+                   devices=None):
+    """motifseq_hits plus the alignment path of every hit: a list, per motif, of
+    (hits[nreads, max_hits], count[nreads], spans[nreads, max_hits, N, 2])."""
+    ms = _hits_args(motifs, max_hits, max_dist)[0]
+    ints, arrs, flts = _split_int16(reads)
+    R, K = len(reads), int(max_hits)
+    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32), np.full((R, K, m.size, 2), -1, dtype=np.int32))
+           for m in ms]
+    bad = 0
+    if ints and ms:
+        buf, lens = pack_i16(arrs)
+        for (h, c, s), (hi, ci, si) in zip(res, motifseq_paths_batch(buf, lens, ms, K, max_dist, scale, scale_low,
+                                                                     scale_hi, devices)):
+            h[ints], c[ints], s[ints] = hi, ci, si
+        bad += _path_mismatches[0]
+    if flts and ms:
+        flat, off = pack_f64([reads[i] for i in flts])
+        for (h, c, s), (hf, cf, sf) in zip(res, motifseq_paths_ragged_f64(flat, off, ms, K, max_dist, scale, scale_low,
+                                                                          scale_hi, devices)):
+            h[flts], c[flts], s[flts] = hf, cf, sf
+        bad += _path_mismatches[0]
+    with _path_lock:
+        _path_mismatches[0] = bad
+    return res
+
+
+def spans_of_path(px, py, n_points):
+    """(a_i, b_i) per motif point of a warping path (px, py): the inverse of expand_path."""
+    px, py = np.asarray(px), np.asarray(py)
+    spans = np.full((int(n_points), 2), -1, dtype=np.int32)
+    if px.size:
+        first = np.flatnonzero(np.r_[True, px[1:] != px[:-1]])
+        last = np.r_[first[1:] - 1, px.size - 1]
+        spans[px[first], 0] = py[first]
+        spans[px[first], 1] = py[last]
+    return spans
+
+
+def expand_path(spans):
+    """mlpy's path (px, py) from the spans [N, 2] of one hit: (i, j) for j = a_i .. b_i, i ascending.
+    A hit without a path (spans -1) gives two empty arrays."""
+    spans = np.asarray(spans).reshape(-1, 2)
+    if spans.size == 0 or spans[0, 0] < 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    cnt = (spans[:, 1] - spans[:, 0] + 1).astype(np.int64)
+    px = np.repeat(np.arange(spans.shape[0], dtype=np.int64), cnt)
+    first = np.cumsum(cnt) - cnt
+    py = np.arange(cnt.sum(), dtype=np.int64) - np.repeat(first, cnt) + np.repeat(spans[:, 0].astype(np.int64), cnt)
+    return px, py
+
+
+def last_path_mismatches():
+    """Hits of the last paths call of this module whose path failed the kernel's self-check (they carry spans -1);
+    a healthy build reports 0.  -1: no paths call yet."""
+    return _path_mismatches[0]
+
+
 def normalise(sig, scale="medmad", scale_low=0, scale_hi=1200):
     """Filtered + normalised signal of one read, as MotifSeq hands it to
     dtw_subsequence (MotifSeq.py:274-289)."""
@@ -904,10 +1039,11 @@ class LastRowCost:
         raise IndexError("only the last row of the DTW cost matrix is kept on this path")
 
 
-def dtw_subsequence(x, y, last_row=False):
+def dtw_subsequence(x, y, last_row=False, full_path=False):
     """Drop-in for mlpy.dtw_subsequence(x, y) as MotifSeq.py:437-439 consumes it:
     returns (dist, cost, path) with path[1][0] == start and path[1][-1] == end.
-    `cost` supports cost[-1, :] when last_row=True, else it is None."""
+    `cost` supports cost[-1, :] when last_row=True, else it is None.  full_path=True: `path` is mlpy's whole warping
+    path (px, py), rebuilt from the spans the path kernel returns; the default keeps its two ends only."""
     L = _lib.ensure_init()
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.ascontiguousarray(y, dtype=np.float64)
@@ -916,6 +1052,13 @@ def dtw_subsequence(x, y, last_row=False):
     check(L.sk_dtw_subsequence(ptr(x), x.size, ptr(y), y.size, C.byref(dist), C.byref(s),
                                C.byref(e), ptr(row) if last_row else None))
     path = (np.array([0, x.size - 1]), np.array([s.value, e.value]))
+    if full_path:
+        spans = np.empty((x.size, 2), dtype=np.int32)
+        d2, s2, e2 = C.c_double(), C.c_int32(), C.c_int32()
+        check(L.sk_dtw_subsequence_path(ptr(x), x.size, ptr(y), y.size, C.byref(d2), C.byref(s2), C.byref(e2), ptr(spans)))
+        with _path_lock:
+            _path_mismatches[0] = max(L.sk_last_path_mismatches(), 0)
+        path = expand_path(spans)
     return dist.value, (LastRowCost(row, x.size) if last_row else None), path
 
 

@@ -815,6 +815,194 @@ static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t 
     return SK_OK;
 }
 
+// ------------------------------------------------------------------ MotifSeq alignment paths (sk_path.hip)
+// The hit list, then per hit the spans of its warping path: which columns [a_i, b_i] each motif point i covers
+// (mlpy's subsequence_path, MotifSeq.py:437, as a fixed-size record).  Layout of `spans`: motif k's block begins at
+// 2 * max_hits * nreads * motif_off[k] int32, inside it [read][hit][N_k][2].  hits / count are the hit-list call's.
+static int paths_begin(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs, const void *spans)
+{
+    if (!spans) return sk_fail(SK_ERR_INVALID, "NULL spans");
+    int rc = sk_path_begin(c);
+    if (rc) return rc;
+    const size_t mb = (size_t)motif_off[nmotifs] * sizeof(double);
+    if ((rc = sk_reserve(c, &c->pathmotif, mb))) return rc;
+    SK_HIP(hipMemcpyAsync(c->pathmotif.p, motifs + motif_off[0], mb, hipMemcpyHostToDevice, c->stream));
+    return SK_OK;
+}
+
+// base: as hits_core's; d_out: the records hits_core left ([k * out_reads + r][K], r relative to this (sub-)batch);
+// read0: the (sub-)batch's first read within the out_reads reads of d_spans
+static int paths_core(sk_ctx *c, const sk_sdtw_args &base, const int32_t *motif_off, int32_t nmotifs, int32_t K,
+                      const sk_hit *d_out, int64_t out_reads, int32_t *d_spans, int64_t read0)
+{
+    for (int32_t k = 0; k < nmotifs; k++) {
+        const int64_t m0 = motif_off[k] - motif_off[0], N = motif_off[k + 1] - motif_off[k];
+        sk_path_args p;
+        p.feed = base.feed; p.samples = base.samples; p.samples_raw = base.samples_raw; p.stride = base.stride;
+        p.off = base.off; p.prep = base.prep; p.nreads = base.nreads; p.max_len = base.max_len;
+        p.d_motif = (const double *)c->pathmotif.p + m0; p.nmotif = (int32_t)N;
+        p.hits = d_out + (int64_t)k * out_reads * K; p.K = K;
+        p.spans = d_spans + 2 * (int64_t)K * out_reads * m0 + read0 * K * N * 2;
+        const int rc = sk_launch_paths(c, &p);
+        if (rc) return rc;
+    }
+    return SK_OK;
+}
+
+static size_t spans_bytes(int32_t nreads, int32_t max_hits, const int32_t *motif_off, int32_t nmotifs)
+{
+    return (size_t)2 * (size_t)max_hits * (size_t)nreads * (size_t)(motif_off[nmotifs] - motif_off[0]) * sizeof(int32_t);
+}
+
+static int paths_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                         int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                         int32_t scale_mode, int32_t scale_low, int32_t scale_hi, int32_t K, double max_dist,
+                         sk_hit *d_out, int32_t *d_count, int64_t out_reads, int32_t *d_spans, int64_t read0)
+{
+    int rc = hits_dev_i16(c, d_sig, stride, d_len, nreads, d_comp, d_prep, motifs, motif_off, nmotifs, scale_mode, scale_low,
+                          scale_hi, K, max_dist, d_out, d_count, out_reads);
+    if (rc) return rc;
+    sk_sdtw_args a;
+    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nreads;
+    a.max_len = stride;
+    return paths_core(c, a, motif_off, nmotifs, K, d_out, out_reads, d_spans, read0);
+}
+
+// device-resident form: d_out / d_count as sk_motifseq_hits_dev_i16, d_spans in the layout above
+int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                              int32_t *d_count, int32_t *d_spans)
+{
+    SK_ENTER(c);
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (rc) return rc;
+    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
+    if ((rc = check_hits(max_hits, max_dist, nreads ? d_out : (void *)1, nreads ? d_count : (void *)1))) return rc;
+    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? d_spans : (void *)1))) return rc;
+    if (nreads == 0) return SK_OK;
+    clamp_limits(&scale_low, &scale_hi);
+    redo_forget(c);
+    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    return paths_dev_i16(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
+                         nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads, d_spans, 0);
+}
+
+// host buffers; sub-batches as sk_motifseq_hits_i16
+int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                          int32_t *count, int32_t *spans)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
+    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
+    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? spans : (void *)1))) return rc;
+    if (nreads == 0) return SK_OK;
+    clamp_limits(&scale_low, &scale_hi);
+    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
+    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
+    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
+    const size_t pb = spans_bytes(nreads, max_hits, motif_off, nmotifs);
+    if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
+    if ((rc = sk_reserve(c, &c->pathspans, pb))) return rc;
+    redo_forget(c);
+    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return paths_dev_i16(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
+                                              (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
+                                              scale_hi, max_hits, max_dist, (sk_hit *)c->out.p + (size_t)r0 * max_hits,
+                                              (int32_t *)c->out2.p + r0, nreads, (int32_t *)c->pathspans.p, r0);
+                     });
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// ragged float64 / centi reads, as sk_motifseq_hits_f64 / _centi
+static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
+                        const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                        int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                        int32_t *count, int32_t *spans);
+int sk_motifseq_paths_f64(const double *sig, const int64_t *off, int32_t nreads,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                          int32_t *count, int32_t *spans)
+{
+    return paths_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                        max_dist, out, count, spans);
+}
+int sk_motifseq_paths_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                            const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                            int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                            int32_t *count, int32_t *spans)
+{
+    return paths_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                        max_dist, out, count, spans);
+}
+static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
+                        const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                        int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                        int32_t *count, int32_t *spans)
+{
+    SK_ENTER(c);
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
+    if (rc) return rc;
+    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
+    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? spans : (void *)1))) return rc;
+    if (nreads == 0) return SK_OK;
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
+    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
+    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
+    const size_t pb = spans_bytes(nreads, max_hits, motif_off, nmotifs);
+    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
+    if ((rc = sk_reserve(c, &c->pathspans, pb))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    const double *d_sig = (const double *)c->sig.p;
+    const int64_t *d_off = (const int64_t *)c->off.p;
+    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, scale_mode, scale_low, scale_hi))) return rc;
+    sk_sdtw_args a;
+    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
+    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
+    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, max_hits, max_dist, (sk_hit *)c->out.p, (int32_t *)c->out2.p,
+                        nreads))) return rc;
+    if ((rc = paths_core(c, a, motif_off, nmotifs, max_hits, (const sk_hit *)c->out.p, nreads, (int32_t *)c->pathspans.p,
+                         0))) return rc;
+    c->ev_valid = true;
+    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// hits of the last paths call whose path failed the self-check (window corner == dist bit for bit, a_0 == start,
+// b_{N-1} == end) and got spans -1; a healthy build reports 0.  -1: no paths call yet on this context.
+int sk_last_path_mismatches(void)
+{
+    SK_ENTER(c);
+    if (!c->path_valid || !c->pathcnt.p) return -1;
+    SK_HIP(hipStreamSynchronize(c->stream));
+    int32_t v = 0;
+    SK_HIP(hipMemcpy(&v, c->pathcnt.p, sizeof v, hipMemcpyDeviceToHost));
+    return v;
+}
+
 // ------------------------------------------------------------------ mlpy boundary (pre-normalised f64)
 int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const int64_t *off,
                              int32_t nreads, sk_hit *out)
@@ -877,6 +1065,40 @@ int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
     SK_HIP(hipMemcpyAsync(&h, c->out.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     if (cost_last_row)
         SK_HIP(hipMemcpyAsync(cost_last_row, c->misc.p, (size_t)ny * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    if (dist) *dist = h.dist;
+    if (start) *start = h.start;
+    if (end) *end = h.end;
+    return SK_OK;
+}
+
+// One already-normalised pair with the path of its match: dist / start / end as sk_dtw_subsequence, spans [nx][2]
+// (mlpy's path: (i, j) for j = spans[i][0] .. spans[i][1], i ascending).  All -1: no path (NaN distance).
+int sk_dtw_subsequence_path(const double *x, int32_t nx, const double *y, int32_t ny,
+                            double *dist, int32_t *start, int32_t *end, int32_t *spans)
+{
+    SK_ENTER(c);
+    if (!x || !y || nx <= 0 || ny <= 0) return sk_fail(SK_ERR_INVALID, "empty x or y");
+    const int32_t moff[2] = {0, nx};
+    int rc = paths_begin(c, x, moff, 1, spans);
+    if (rc) return rc;
+    if ((rc = sk_reserve(c, &c->sig, (size_t)ny * sizeof(double)))) return rc;
+    if ((rc = sk_reserve(c, &c->off, 2 * sizeof(int64_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, sizeof(sk_hit)))) return rc;
+    if ((rc = sk_reserve(c, &c->pathspans, (size_t)nx * 2 * sizeof(int32_t)))) return rc;
+    const int64_t rel[2] = {0, ny};
+    SK_HIP(hipMemcpyAsync(c->sig.p, y, (size_t)ny * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipMemcpyAsync(c->off.p, rel, sizeof rel, hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    sk_sdtw_args a;
+    a.feed = SK_FEED_F64_RAW; a.samples = c->sig.p; a.stride = 0; a.off = (const int64_t *)c->off.p;
+    a.prep = nullptr; a.nreads = 1; a.motif = x; a.nmotif = nx; a.out = (sk_hit *)c->out.p;
+    a.last_row = nullptr; a.max_len = ny; a.force_single = 1;
+    if ((rc = sk_launch_sdtw(c, &a))) return rc;
+    if ((rc = paths_core(c, a, moff, 1, 1, (const sk_hit *)c->out.p, 1, (int32_t *)c->pathspans.p, 0))) return rc;
+    sk_hit h;
+    SK_HIP(hipMemcpyAsync(&h, c->out.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, (size_t)nx * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     if (dist) *dist = h.dist;
     if (start) *start = h.start;

@@ -74,6 +74,12 @@ struct sk_ctx {
     sk_buf sweep;     // parameter sweep: the sets in walk form, then the summaries (sk_sweep.hip)
     sk_buf sweeprec;  // parameter sweep: the per-(set, read) records of the host entry points
     sk_buf hitrows;   // hit lists: the last rows of a chunk of reads (cost f64, start i32) and their records
+    sk_buf pathcnt;   // alignment paths: [0] = hits of the call that failed the self-check (sk_last_path_mismatches)
+    bool   path_valid = false;   // ... the last MotifSeq call was a paths call (the counter is that call's)
+    sk_buf pathlist;  // alignment paths: [0] = count, [2 ..] = hits of a launch left to the scratch tier
+    sk_buf pathscratch;   // alignment paths: the scratch tier's slabs (direction words + stripe boundary row per wavefront)
+    sk_buf pathmotif; // alignment paths: the motifs of the call, flat (device)
+    sk_buf pathspans; // alignment paths: the spans of the host entry points
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -230,6 +236,26 @@ int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t 
 // hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]
 int sk_launch_hits_select(sk_ctx *c, const double *rowD, const int32_t *rowS, int64_t row_stride, const sk_hit *rec,
                           int32_t nreads, int32_t K, double max_dist, sk_hit *out, int32_t *count);
+// alignment paths (sk_path.hip): spans [nreads][K][nmotif][2] of the hits [nreads][K] of prepared reads (samples / prep /
+// stride / off / max_len as sk_sdtw_args); d_motif: the motif on the DEVICE.  sk_path_begin: once per API call, before
+// the first launch (zeroes the call's mismatch counter).
+struct sk_path_args {
+    int            feed;
+    const void    *samples;
+    const void    *samples_raw = nullptr;
+    int64_t        stride = 0;
+    const int64_t *off = nullptr;
+    const sk_prep *prep = nullptr;
+    int32_t        nreads = 0;
+    int64_t        max_len = 0;
+    const double  *d_motif = nullptr;
+    int32_t        nmotif = 0;
+    const sk_hit  *hits = nullptr;
+    int32_t        K = 1;
+    int32_t       *spans = nullptr;
+};
+int sk_path_begin(sk_ctx *c);
+int sk_launch_paths(sk_ctx *c, const sk_path_args *p);
 // fixed-point screening + certified window over all reads (sk_sdtwq.hip); leaves the retry list on the device
 int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, int span2,
                           int32_t *d_retry_cnt, int32_t *d_retry, int32_t *d_early_cnt, int32_t *d_early);

@@ -5,7 +5,7 @@ scale_outliers + medmad/zscale + dtw_subsequence run on the GPU (batched, C ABI)
 the scoring of MotifSeq.py:441-445 stays in Python so the printed floats are the
 reference's digit for digit.  fast5 input (-f / -p) goes through h5py when it is importable and
 through the built-in reader (hdf5min.py) otherwise, with the reference's stderr messages.
-Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p.
+Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p, --paths.
 Whole chunks of plain integer reads (TSV chunks, BLOW5 / packed blocks) go to the GPU as one batch and their rows are
 formatted natively (csrc/sk_io.cpp writes floats as Python does); anything unusual takes the per-read route.
 """
@@ -83,11 +83,19 @@ def build_parser():
                    help="[extension] up to K non-overlapping matches per read and motif (1..64), best first")
     p.add_argument("--min_hit_p", type=float, default=None, metavar="P",
                    help="[extension] with --hits: leave out the lines whose hit_Probability is below P")
+    p.add_argument("--paths", default=None, metavar="FILE",
+                   help="[extension] write to FILE, per printed hit and motif base, the samples the alignment path gives "
+                        "that base (start, end, length, mean normalised signal); stdout is unchanged")
     return p
 
 
+PATHS_HEADER = ["fast5", "readID", "model", "hit", "pos", "base", "model_current", "start", "end", "length", "mean_signal"]
+
+
 def check_hit_flags(parser, args):
-    """--hits / --min_hit_p: what they take, and what they do not combine with."""
+    """--hits / --min_hit_p / --paths: what they take, and what they do not combine with."""
+    if args.paths is not None and args.after_stall:
+        parser.error("--paths does not combine with --after_stall")
     if args.hits is not None and not 1 <= args.hits <= 64:
         parser.error("--hits must be between 1 and 64")
     if args.min_hit_p is not None and args.hits is None:
@@ -134,6 +142,35 @@ class _Batcher:
         self.args, self.models, self.order, self.lens = args, models, order, lens
         self.meta, self.sigs = [], []
         self._pending, self._worker = None, None
+        self.bases, self.paths_fh = {}, None          # --paths: base table per model (scrappie text), the open FILE
+
+    def search(self, fn_hits, fn_multi, fn_paths, *args):
+        """The GPU call of one batch: (what of_read / table take, spans per motif or None).  --paths takes the paths
+        call -- hit lists plus spans; without --hits its rank-1 records stand in for the default path's (the same
+        records bit for bit)."""
+        a = self.args
+        tail = (a.scale, a.scale_low, a.scale_hi)
+        if a.paths is not None:
+            res = fn_paths(*args, a.hits or 1, float("inf"), *tail)
+            hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
+            return hits, [sp for _, _, sp in res]
+        if a.hits is not None:
+            return fn_hits(*args, a.hits, float("inf"), *tail), None
+        return fn_multi(*args, *tail), None
+
+    def path_lines(self, fast5, read_id, name, rank, spans, norm):
+        """One line per base of the model (per motif point when it has no base table) for one printed hit."""
+        motif = self.models[name]
+        table = self.bases.get(name) or [(i, ".", float(motif[i]), i, 1) for i in range(len(motif))]
+        out = []
+        for pos, base, current, first, cnt in table:
+            if cnt == 0 or spans[0, 0] < 0:
+                lo, hi, length, mean = -1, -1, 0, float("nan")
+            else:
+                lo, hi = int(spans[first, 0]), int(spans[first + cnt - 1, 1])
+                length, mean = hi - lo + 1, np.mean(norm[lo:hi + 1])
+            out.append("\t".join("{}".format(v) for v in (fast5, read_id, name, rank, pos, base, current, lo, hi, length, mean)))
+        self.paths_fh.write("\n".join(out) + "\n")
 
     def add(self, fast5, read_id, sig):
         self.meta.append((fast5, read_id))
@@ -162,18 +199,18 @@ class _Batcher:
         if sigs:
             _STATS[0].batch(len(sigs))
         motifs = [np.asarray(self.models[name], dtype=np.float64) for name in self.order]
-        if a.hits is not None:
-            hits = api.motifseq_hits(sigs, motifs, a.hits, float("inf"), a.scale, a.scale_low, a.scale_hi)
+        if sigs or a.hits is not None:
+            hits, spans = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths, sigs, motifs)
         else:
-            hits = (api.motifseq_multi(sigs, motifs, a.scale, a.scale_low, a.scale_hi) if sigs
-                    else [[] for _ in self.order])
+            hits, spans = [[] for _ in self.order], None
         slot = {i: k for k, i in enumerate(live)}
         for i, (fast5, read_id) in enumerate(self.meta):
             if self.sigs[i] is None:
                 sys.stderr.write(read_id)
                 continue
             r = slot[i]
-            self.emit(fast5, read_id, self.of_read(hits, r), self.sigs[i], None if cuts is None else int(cuts[r]))
+            self.emit(fast5, read_id, self.of_read(hits, r), self.sigs[i], None if cuts is None else int(cuts[r]),
+                      None if spans is None else [sp[r] for sp in spans])
         self.meta, self.sigs = [], []
 
     def of_read(self, hits, r):
@@ -182,8 +219,9 @@ class _Batcher:
             return [(h[r], cnt[r]) for h, cnt in hits]
         return [hits[c][r] for c in range(len(self.order))]
 
-    def emit(self, fast5, read_id, hits, sig, cut):
-        """The rows of one read, one per motif (MotifSeq.py:436-449); with --hits one per match, best first."""
+    def emit(self, fast5, read_id, hits, sig, cut, spans=None):
+        """The rows of one read, one per motif (MotifSeq.py:436-449); with --hits one per match, best first.
+        spans (--paths): per motif the read's [K, N, 2]; every printed hit also writes its lines to the paths file."""
         a = self.args
         norm = None
         for c, name in enumerate(self.order):
@@ -214,7 +252,7 @@ class _Batcher:
                 found = [(dist, start, end)]
             elif found is None:
                 found = [(float(h["dist"]), int(h["start"]), int(h["end"]))]
-            for dist, start, end in found:
+            for rank, (dist, start, end) in enumerate(found):
                 mod_mean = (a.slope * self.lens[c]) + a.intercept
                 mod_stdev = mod_mean * a.std_const
                 z = (dist - mod_mean) / mod_stdev
@@ -230,13 +268,17 @@ class _Batcher:
                 if cut is not None:
                     row.append(cut)
                 print("\t".join("{}".format(v) for v in row))
+                if spans is not None and not h["flags"] & 2:
+                    if norm is None:
+                        norm = api.normalise(sig, a.scale, a.scale_low, a.scale_hi)
+                    self.path_lines(fast5, read_id, name, rank + 1, spans[c][rank], norm)
 
     def table(self, n, fast5_col, id_col, hits):
         """The rows of n reads x every motif through the native formatter (file order, read-major).  Returns False --
         nothing written -- when some read needs the general route (-x, a flagged read)."""
         a = self.args
         K = len(self.order)
-        if a.sig_extract or any(bool((h["flags"] & 3).any()) for h in hits):
+        if a.sig_extract or a.paths is not None or any(bool((h["flags"] & 3).any()) for h in hits):
             return False
         names = [nm.encode() for nm in self.order]
         nblob = b"".join(names)
@@ -273,7 +315,7 @@ class _Batcher:
         out), through the same formatter and the same scoring arithmetic."""
         a = self.args
         K = len(self.order)
-        if a.sig_extract or any(bool((h[:, 0]["flags"] & 3).any()) for h, _ in hits):
+        if a.sig_extract or a.paths is not None or any(bool((h[:, 0]["flags"] & 3).any()) for h, _ in hits):
             return False
         names = [nm.encode() for nm in self.order]
         nblob = b"".join(names)
@@ -332,10 +374,8 @@ class _Batcher:
         def call():
             _mark("GPU call starts")
             try:
-                if a.hits is not None:
-                    return api.motifseq_hits_batch(rows, nsamp, motifs, a.hits, float("inf"), a.scale, a.scale_low,
-                                                   a.scale_hi)
-                return api.motifseq_multi_batch(rows, nsamp, motifs, a.scale, a.scale_low, a.scale_hi)
+                return self.search(api.motifseq_hits_batch, api.motifseq_multi_batch, api.motifseq_paths_batch, rows, nsamp,
+                                   motifs)
             finally:
                 _mark("GPU call ends")
         job = self._worker.submit(call)
@@ -343,7 +383,7 @@ class _Batcher:
                                               lambda i, r=rows, ns=nsamp: r[i, :ns[i]])
         if prev is not None:
             self._finish(prev)
-        if a.sig_extract:                                   # (-x normalises on the GPU from this thread: no overlap)
+        if a.sig_extract or a.paths is not None:            # (they normalise on the GPU from this thread: no overlap)
             self.drain()
 
     def rows_f64(self, fb):
@@ -355,11 +395,8 @@ class _Batcher:
             from concurrent.futures import ThreadPoolExecutor
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d float64 reads to the GPU worker" % fb.n)
-        if a.hits is not None:
-            job = self._worker.submit(api.motifseq_hits_ragged_f64, fb.batch_values(), fb.off, motifs, a.hits,
-                                      float("inf"), a.scale, a.scale_low, a.scale_hi)
-        else:
-            job = self._worker.submit(api.motifseq_multi_ragged_f64, fb.batch_values(), fb.off, motifs, a.scale, a.scale_low, a.scale_hi)
+        job = self._worker.submit(self.search, api.motifseq_hits_ragged_f64, api.motifseq_multi_ragged_f64,
+                                  api.motifseq_paths_ragged_f64, fb.batch_values(), fb.off, motifs)
         prev, self._pending = self._pending, (job, fb.n, ("span", fb.buf, fb.spans("name")), ("span", fb.buf, fb.spans("id")),
                                               lambda i, b=fb: b.text("name", i), lambda i, b=fb: b.text("id", i),
                                               lambda i, b=fb: b.values[b.off[i]:b.off[i + 1]])
@@ -373,7 +410,7 @@ class _Batcher:
 
     def _finish(self, p):
         job, n, fast5_col, id_col, name_of, id_of, sig_of = p
-        hits = job.result()
+        hits, spans = job.result()
         _STATS[0].batch(n)
         _mark("block of %d reads back from the GPU" % n)
         if (self.table_hits if self.args.hits is not None else self.table)(n, fast5_col, id_col, hits):
@@ -384,16 +421,17 @@ class _Batcher:
             # --strict-compat) while the worker runs the next block on the same device context -- one stream, one set
             # of scratch buffers, no lock: the next block's call has to be over first (its result stays in the future)
             self._pending[0].exception()
+        need_sig = self.args.sig_extract or self.args.strict_compat or spans is not None
         for i in range(n):
-            self.emit(name_of(i), id_of(i), self.of_read(hits, i),
-                      sig_of(i) if (self.args.sig_extract or self.args.strict_compat) else None, None)
+            self.emit(name_of(i), id_of(i), self.of_read(hits, i), sig_of(i) if need_sig else None, None,
+                      None if spans is None else [sp[i] for sp in spans])
 
     def block(self, blk):
         """A parsed TSV chunk (tsvio.TsvBlock): its integer lines go to the GPU as ONE int16 batch straight from the
         tokenizer's rows (every motif against them); any other line takes the per-read route, in its place."""
         a = self.args
         fast = (blk.flags & 27) == 3                                        # ALLINT | ANY, not SLOW / SHORT
-        if a.after_stall:
+        if a.after_stall or a.paths is not None:
             fast[:] = False                                                 # (needs the raw reads on the host)
         idx = np.flatnonzero(fast)
         if idx.size == blk.n and blk.n and not a.sig_extract:
@@ -466,7 +504,7 @@ class _Batcher:
                                      str(mm), str(ms), repr(z[k]), repr(pv[k]), repr(hp[k]))))
                 continue
             fl = int(blk.flags[i])
-            if a.after_stall:
+            if a.after_stall or a.paths is not None:
                 # nothing of this chunk was printed directly, so the batcher alone keeps the file order: reads queue
                 # up to --batch per GPU call (segment + search) instead of one call per read
                 if (fl & 27) == 1:
@@ -530,6 +568,10 @@ def main(argv=None):
     if args.gpus > 1:
         api.set_devices(range(args.gpus))
     out = _Batcher(args, models, order, lens)
+    if args.paths is not None:
+        out.bases = tsvio.model_bases_auto(args.model) if args.model else {}
+        out.paths_fh = open(args.paths, "w")
+        out.paths_fh.write("\t".join(PATHS_HEADER) + "\n")
     if args.signal:
         # native tokenizer (csrc/sk_tsv.cpp): integer lines arrive as int16 rows, one GPU batch per chunk of the
         # file; decimal (pA) chunks go through the float64 tokenizer, odd lines through the reference's own parse
@@ -543,7 +585,7 @@ def main(argv=None):
                 fb = blk.float_block(8)
                 if fb is None:
                     continue
-            if fb.clean() and not (args.sig_extract or args.after_stall):
+            if fb.clean() and not (args.sig_extract or args.after_stall or args.paths is not None):
                 out.rows_f64(fb)                         # the whole chunk as one batch, no Python per read
                 continue
             out.flush()
@@ -612,6 +654,8 @@ def main(argv=None):
             out.add(fast5, read_id, np.array(sig, dtype=int))
     out.drain()
     out.flush()
+    if out.paths_fh is not None:
+        out.paths_fh.close()
     _mark("end of main()")
     _STATS[0].finish(args, [args.signal, getattr(args, "blow5", None), getattr(args, "i16", None)] + list(getattr(args, "ind", None) or []))
 

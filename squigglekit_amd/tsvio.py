@@ -392,6 +392,29 @@ def read_scrappie_model(path):
     return models, order, lens
 
 
+def read_scrappie_model_bases(path):
+    """read_scrappie_model plus the base table behind the expansion: (models, order, L, bases) with bases[name] a list
+    of (pos, base, current, first point, point count) per row of the model -- the points first .. first + count - 1 of
+    models[name] are that base's (count = round(dwell) may be 0: a base no point stands for)."""
+    models, order, lens = read_scrappie_model(path)
+    bases, name = {}, None
+    with open_text(path) as fh:
+        for line in fh:
+            line = line.strip("\n")
+            if not line or line[:3] == "pos":
+                continue
+            if line[0] == "#":
+                name = line[1:]
+                bases[name] = []
+                at = 0
+            else:
+                f = line.split()
+                cnt = int(round(float(f[4])))
+                bases[name].append((int(f[0]), f[1], float(f[2]), at, cnt))
+                at += cnt
+    return models, order, lens, bases
+
+
 def read_bait_model(path):
     """Custom TSV model: name <tab> kmer_length <tab> (ignored) <tab> v0 <tab> v1 ...
     (layout documented at MotifSeq.py:408-428; the reference forgets to fill
@@ -416,6 +439,14 @@ def read_model_auto(path):
     if first.startswith("#"):
         return read_scrappie_model(path)
     return read_bait_model(path)
+
+
+def model_bases_auto(path):
+    """The base tables of a '#'-headed scrappie text ({name: rows of read_scrappie_model_bases}); {} for the bait TSV,
+    which has none."""
+    with open_text(path) as fh:
+        first = fh.readline()
+    return read_scrappie_model_bases(path)[3] if first.startswith("#") else {}
 
 
 def fasta_to_models(path, scrappie_model):
