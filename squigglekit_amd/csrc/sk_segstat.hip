@@ -909,9 +909,10 @@ __device__ __forceinline__ void walk_general32(WalkState &st, unsigned bits, int
     st.prev = prev; st.err = err; st.prev_err = prev_err; st.c = c; st.w = w; st.start = start;
 }
 
-// Any parameters.  With error < corrector (the defaults included) the corrector test of segmenter.py:439/446 can
-// never fire -- c <= (in-band samples of this segment) + err and w = corrector + (all in-band samples so far), so
-// c >= w needs err >= corrector -- and the run-hopping walks below take those calls (positive thresholds too).
+// Any parameters.  With error < corrector and corrector >= 1 (the defaults included) the corrector test of
+// segmenter.py:439/446 can never fire -- c <= (in-band samples of this segment) + err and w = corrector + (all in-band
+// samples so far), so c >= w needs err >= corrector, and err stays within 0 .. max(error, 0) -- and the run-hopping
+// walks below take those calls (positive thresholds too).
 // Each lane streams its read's entries; the kept bits of an entry are squeezed together (the filter drops a
 // handful of samples per read, so the squeeze loop runs a few times per READ) and appended to a bit queue;
 // whenever the queue holds 64 bits they go through the state machine.
@@ -1591,7 +1592,10 @@ WalkParams walk_params(const sk_seg_params *p, bool *fast)
     else if (fl > 2147483000.) wp.first_len = 0x7fffffff;
     else if (fl < -2147483000.) wp.first_len = -0x7fffffff;
     else                       wp.first_len = (int)ceil(fl);
-    *fast = wp.error < wp.corrector && wp.window >= 1 && wp.first_len >= 1 && sk_tune("SK_WALK_GENERAL") == nullptr;
+    // corrector >= 1: the bound below needs it.  With corrector 0 and error < 0 the first run of a read has c == w, the
+    // corrector test fires at every sample past `window`, err falls below `error` and out-of-band samples are tolerated.
+    *fast = wp.error < wp.corrector && wp.corrector >= 1 && wp.window >= 1 && wp.first_len >= 1 &&
+            sk_tune("SK_WALK_GENERAL") == nullptr;
     return wp;
 }
 

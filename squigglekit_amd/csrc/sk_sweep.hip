@@ -10,7 +10,7 @@
 //   * the lanes of one read load the same 16-byte entries (one address per read: a 128-byte line serves 8 entries for
 //     all of them) and squeeze the dropped samples out of the same bits;
 //   * each lane runs the state machine with its own parameters, held in registers, over the same 32-bit words: the
-//     run-hopping form of k_seg_walk3 (run_word32) for sets with error < corrector, window >= 1 and first_len >= 1, the
+//     run-hopping form of k_seg_walk3 (run_word32) for sets with error < corrector, corrector, window, first_len >= 1, the
 //     per-sample form of k_seg_walk2 (walk_general32) for the others.  The host launches the two kinds apart, so that a
 //     wavefront holds only one.
 // Only the first two segments are kept (in registers), with the exact count after merges.  The summary counters go
@@ -296,7 +296,9 @@ void sk_sweep_plan(const sk_seg_sweep_set *sets, int32_t nsets, std::vector<sk_s
                 else if (fl < -2147483000.) L.first_len = -0x7fffffff;
                 else                       L.first_len = (int)ceil(fl);
                 L.stall_start = sets[k].stall_start; L.gap_dist = sets[k].gap_dist; L.index = k;
-                const bool fast = L.error < L.corrector && L.window >= 1 && L.first_len >= 1 &&
+                // (corrector >= 1: with corrector 0 and a negative error the first run has c == w, the corrector test
+                // fires and err falls below `error` -- tolerance the run-hopping form does not have)
+                const bool fast = L.error < L.corrector && L.corrector >= 1 && L.window >= 1 && L.first_len >= 1 &&
                                   sk_tune("SK_WALK_GENERAL") == nullptr;
                 if (fast != (pass == 0)) continue;
                 lanes.push_back(L);

@@ -95,6 +95,35 @@ def test_sweep_equals_segment_batch_per_set(gpu, ora):
     assert _lib.SWEEP_SUM_DTYPE.itemsize == 64
 
 
+def test_negative_error_with_corrector_zero_takes_the_general_walk(gpu, ora):
+    """Found by tests/test_gpu_random.py (sweep seeds 16 and 60): error = -1 < corrector = 0 passed the run-hopping
+    walks' test, but there the first run of a read has c == w, the corrector test of segmenter.py:439 fires at every
+    sample past `window`, err falls below `error` and out-of-band samples are tolerated from then on -- the reference
+    reports other segments (often none, the run reaching the end of the read) than a walk without the corrector.
+    Both planners (sk_sweep_plan, walk_params) now ask for corrector >= 1; the sweep and segment_batch against the oracle."""
+    from squigglekit_amd import api, synth
+    sig = synth.squiggle_batch(64, 4000, 16)
+    lens = np.full(64, 4000, dtype=np.int32)
+    lens[::7] = 1000
+    sets = api.sweep_grid(error=[-1, -3], corrector=0, window=[20, 127], stall_len=[0.05, 1.2], lim_low=300, lim_hi=800,
+                          std_scale=[1.5, 3.0])
+    sums, recs = api.segment_sweep(sig, sets, lens, records=True)
+    differs = 0
+    for k, s in enumerate(sets):
+        g = s.seg
+        op = ora.SegParams(g.error, g.corrector, g.window, g.seg_dist, g.std_scale, g.stall_len)
+        plain = ora.SegParams(g.error, 50, g.window, g.seg_dist, g.std_scale, g.stall_len)      # the corrector test dead
+        segs, nsegs = api.segment_batch(sig, lens, g)
+        for r in range(sig.shape[0]):
+            f = ora.scale_outliers(sig[r, :lens[r]].astype(float), g.lim_low, g.lim_hi)
+            want = ora.get_segs(f, op, max_segs=f.size) or []
+            assert tuple(int(x) for x in recs[k, r].tolist()) == _expected_rec(want, len(want)), (k, r)
+            assert segs[r, :nsegs[r]].tolist() == want, (k, r)
+            differs += want != (ora.get_segs(f, plain, max_segs=f.size) or [])
+    assert differs > 0                                       # the inputs are ones where the corrector test matters
+    assert np.array_equal(sums, _sums_from_recs(sets, recs))
+
+
 def test_sweep_small_group_packs_reads(gpu):
     """8 sets in one group (several reads per wavefront) and 3 sets (lanes left idle) give the per-set results."""
     from squigglekit_amd import api, synth

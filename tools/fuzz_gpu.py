@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle sweep over shapes the unit tests do not pin: random read counts, ragged
-lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters.
+lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; and, per round, one drawn case each
+of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py).
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -14,6 +15,8 @@ import numpy as np
 os.environ["SK_TUNING"] = "1"      # this tool flips tuning switches
 
 sys.path.insert(0, ".")
+sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
+import randcases                                      # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -257,6 +260,27 @@ def main():
                     print("DRNA ROLL mismatch n=%d %s step=%s switch=%s" % (len(x), rkw, os.environ.get("SK_DRNA_STEP"), rkey))
             os.environ.pop("SK_DRNA_STEP", None)
             for key in ("SK_ROLL_TWO_KERNELS", "SK_ROLL_ONE_LOOK", "SK_ROLL_DELTA_SCALE"):
+                os.environ.pop(key, None)
+        # ---- the sweep, the hit lists, the paths and pull: tests/randcases.py's draws with this tool's running generator,
+        # against the same references as tests/test_gpu_random.py (the oracle per (set, read), reference_hits,
+        # reference_paths, numpy_pull_text).  A mismatch line carries the round, so `fuzz_gpu.py <seconds> <seed>` up to
+        # that round rebuilds the case, and the drawn parameters and switches.
+        for fam in ("sweep", "hits", "paths", "pull"):
+            case = randcases.DRAW[fam](rng)
+            for key in randcases.SWITCHES:
+                if key in case["env"]:
+                    os.environ[key] = case["env"][key]
+                else:
+                    os.environ.pop(key, None)
+            exp = randcases.EXPECT[fam](ora, case)
+            got = randcases.CALL[fam](api, case, exp)
+            msg = randcases.DIFF[fam](case, got, exp)
+            if msg is None and fam == "paths" and api.last_path_mismatches() != 0:
+                msg = "%d hits failed the path kernel's self-check" % api.last_path_mismatches()
+            if msg is not None:
+                bad += 1
+                print("%s mismatch round %d %s: %s" % (fam.upper(), rounds, randcases.describe(case), msg))
+            for key in randcases.SWITCHES:
                 os.environ.pop(key, None)
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
