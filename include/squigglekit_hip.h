@@ -350,6 +350,57 @@ int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_
  * reports 0. */
 int sk_last_path_mismatches(void);
 
+/* Motif panel inside a search region: which of K known signals (barcodes, adapters, primers) sits at a known place of
+ * the read.  Region: read r's raw samples are cut as the Python slice raw[begin:end] BEFORE scale_outliers -- negative
+ * values count from the end of the read, end = INT32_MAX means "to the end", everything resolved as
+ * slice(begin, end).indices(len[r]) resolves it (an empty result is allowed: SK_FLAG_EMPTY); win (NULL, or [nreads][2])
+ * gives every read its own (begin, end) instead, e.g. segmenter-derived cuts.  What follows is the reference run on the
+ * sliced read: the filter (MotifSeq.py:317-324), medmad or zscale over the slice (:186-200), dtw_subsequence (:437);
+ * start / end / n index the slice's filtered samples, from[r] is the resolved raw begin (what --after_stall prints as
+ * search_from).  Records: motif k's (dist, start, end, n, flags) of read r is bit for bit what
+ * sk_motifseq_multi_batch_i16 returns for the sliced rows.  Ranking: score[k] = (dist_k - mean[k]) / sd[k], one
+ * correctly rounded FP64 subtraction and one division -- the Z-score of MotifSeq.py:441-443, mean = slope * L_k +
+ * intercept and sd = mean * std_const made by the caller; best = the smallest score (ties: the smallest k), second =
+ * the best of the rest; a NaN score is never ranked.  A read flagged SK_FLAG_EMPTY or SK_FLAG_DEGENERATE has
+ * best = second = -1 and NaN scores; with one motif second = -1 and score_second is NaN. */
+typedef struct sk_panel_rec {   /* 48 bytes, one per read */
+    int32_t best, second;       /* motif indices, -1: none                                              */
+    double  score_best, score_second;
+    sk_hit  hit;                /* the best motif's record (dist NaN, start = end = -1, the read's n and flags when best == -1) */
+} sk_panel_rec;
+/* out [nreads]; from [nreads] or NULL; all [nmotifs][nreads] (every motif's record) or NULL.  Region alone is this call
+ * with one motif and `all`.  SK_ERR_INVALID: nmotifs outside 1..256, an empty motif, sd[k] == 0, a non-finite mean or
+ * sd, a win row whose resolved begin lies behind its end (unless both were cut to the read, as a slice cuts them), NULL
+ * where a pointer is required.  Large calls are moved in sub-batches like the other host entry points. */
+int sk_motifseq_panel_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          int32_t begin, int32_t end, const int32_t *win,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                          const double *mean, const double *sd,
+                          int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
+                          sk_panel_rec *out, int32_t *from, sk_hit *all);
+/* device-resident form: d_sig, d_len, d_win, d_out, d_from, d_all device; motifs / motif_off / mean / sd host.  len[r]
+ * is clamped into [0, stride]; a d_win row whose resolved begin lies behind its end is an empty window (the library
+ * cannot look).  Nothing is synchronised. */
+int sk_motifseq_panel_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              int32_t begin, int32_t end, const int32_t *d_win,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                              const double *mean, const double *sd,
+                              int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
+                              sk_panel_rec *d_out, int32_t *d_from, sk_hit *d_all);
+/* ragged float64 reads (pA input): read r = sig[off[r] .. off[r+1]) */
+int sk_motifseq_panel_f64(const double *sig, const int64_t *off, int32_t nreads,
+                          int32_t begin, int32_t end, const int32_t *win,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                          const double *mean, const double *sd,
+                          int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
+                          sk_panel_rec *out, int32_t *from, sk_hit *all);
+/* The gather alone (k_region_rows): the window rows of the region, for callers that hand them to another entry point
+ * (hit lists, paths).  rows [nreads][wstride] (zero padded), wlen [nreads], from [nreads] or NULL; wstride: a multiple
+ * of 8 that holds the longest resolved slice (SK_ERR_INVALID otherwise).  win as above. */
+int sk_region_rows_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                       int32_t begin, int32_t end, const int32_t *win, int64_t wstride,
+                       int16_t *rows, int32_t *wlen, int32_t *from);
+
 /* The mlpy boundary itself: dtw_subsequence(x, y) on already-normalised
  * float64 signals (MotifSeq.py:437).  Batch form: read r is y[off[r]..off[r+1]). */
 int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const int64_t *off,

@@ -113,6 +113,17 @@ class Hit(C.Structure):
 HIT_DTYPE = np.dtype([("dist", "<f8"), ("start", "<i4"), ("end", "<i4"),
                       ("n", "<i4"), ("flags", "<i4")])
 
+
+
+class PanelRec(C.Structure):
+    """sk_panel_rec: one read of a motif panel -- the two best motifs by score and the best one's record."""
+    _fields_ = [("best", C.c_int32), ("second", C.c_int32), ("score_best", C.c_double), ("score_second", C.c_double),
+                ("hit", Hit)]
+
+
+PANEL_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("score_best", "<f8"), ("score_second", "<f8"),
+                        ("hit", HIT_DTYPE)])
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -177,6 +188,13 @@ ABI = {
     "sk_motifseq_paths_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
     "sk_last_path_mismatches": (C.c_int, []),
+    "sk_motifseq_panel_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
+                                        _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sk_motifseq_panel_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
+                                            _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sk_motifseq_panel_f64": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
+                                        _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sk_region_rows_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp]),
     "sk_dtw_subsequence_path": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _dp, _i32p, _i32p, _vp]),
     "sk_motifseq_dev_f64": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _vp]),

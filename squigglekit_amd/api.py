@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (HIT_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (HIT_DTYPE, PANEL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -1086,3 +1086,161 @@ def dtw_subsequence_batch(x, ys):
     out = np.zeros(len(ys), dtype=HIT_DTYPE)
     check(L.sk_dtw_subsequence_batch(ptr(x), x.size, ptr(flat), ptr(off), len(ys), ptr(out)))
     return out
+
+
+# ----------------------------------------------------------------------------
+# MotifSeq panel: many motifs ranked per read, inside a search region
+# ----------------------------------------------------------------------------
+INT32_MAX = 2 ** 31 - 1
+
+
+def resolve_region(lens, begin, end):
+    """Per read the (start, stop) that slice(begin, end).indices(len) gives (pure numpy; end None: to the end of the
+    read): negative values count from the end, everything is cut to the read, stop < start is an empty slice."""
+    n = np.asarray(lens, dtype=np.int64)
+
+    def side(v):
+        if v is None:
+            return n.copy()
+        v = int(v)
+        return np.clip(n + v, 0, None) if v < 0 else np.minimum(n, v)
+    lo = np.zeros_like(n) if begin is None else side(begin)
+    return np.stack([lo, side(end)], axis=-1)
+
+
+def _region_pair(region):
+    begin, end = (0, None) if region is None else region
+    begin = 0 if begin is None else int(begin)
+    end = INT32_MAX if end is None else int(end)
+    if not (-2 ** 31 <= begin <= INT32_MAX and -2 ** 31 <= end <= INT32_MAX):
+        raise ValueError("region bounds must fit int32")
+    return begin, end
+
+
+def _panel_args(motifs, means, sds, win, R):
+    ms = [np.ascontiguousarray(m, dtype=np.float64) for m in motifs]
+    if not 1 <= len(ms) <= 256:
+        raise ValueError("a panel takes 1..256 motifs, got %d" % len(ms))
+    flat = np.ascontiguousarray(np.concatenate(ms))
+    moff = np.concatenate([[0], np.cumsum([m.size for m in ms])]).astype(np.int32)
+    means = np.ascontiguousarray(means, dtype=np.float64).reshape(-1)
+    sds = np.ascontiguousarray(sds, dtype=np.float64).reshape(-1)
+    if means.size != len(ms) or sds.size != len(ms):
+        raise ValueError("means / sds need one entry per motif")
+    if win is not None:
+        win = np.ascontiguousarray(win, dtype=np.int32)
+        if win.shape != (R, 2):
+            raise ValueError("win must be [reads, 2]")
+    return ms, flat, moff, means, sds, win
+
+
+def _panel_result(out, frm, allrec, records):
+    return (out, frm, [allrec[k] for k in range(allrec.shape[0])]) if records else (out, frm)
+
+
+def motifseq_panel_batch(sig, lens, motifs, means, sds, region=(0, None), win=None, scale="medmad", scale_low=0,
+                         scale_hi=1200, records=False, devices=None):
+    """The panel over an int16 [R, stride] batch: per read the slice raw[begin:end] (region; or the read's own win row)
+    is cut before scale_outliers, every motif is searched in it, and score[k] = (dist_k - means[k]) / sds[k] is
+    ranked on the GPU.  Returns (panel[R] PANEL_DTYPE, from[R]) -- from: the raw index the slice starts at -- and with
+    records=True also the list, per motif, of HIT_DTYPE records (what motifseq_multi_batch gives for the sliced rows)."""
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    begin, end = _region_pair(region)
+    ms, flat, moff, means, sds, win = _panel_args(motifs, means, sds, win, R)
+    if _too_wide_for_i16(scale_low, scale_hi):
+        vals, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
+        return motifseq_panel_ragged_f64(vals, off, motifs, means, sds, region, win, scale, scale_low, scale_hi, records,
+                                         devices)
+    L = _lib.load()
+    out = np.zeros(R, dtype=PANEL_DTYPE)
+    frm = np.zeros(R, dtype=np.int32)
+    allrec = np.zeros((len(ms), R), dtype=HIT_DTYPE)
+
+    def call(lo, hi):
+        part = np.zeros((len(ms), hi - lo), dtype=HIT_DTYPE)
+        rc = L.sk_motifseq_panel_i16(ptr(sig[lo:hi]), stride, ptr(lens[lo:hi]), hi - lo, begin, end,
+                                     None if win is None else ptr(win[lo:hi]), ptr(flat), ptr(moff), len(ms), ptr(means),
+                                     ptr(sds), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), ptr(out[lo:hi]),
+                                     ptr(frm[lo:hi]), ptr(part) if records else None)
+        if rc == 0:
+            allrec[:, lo:hi] = part
+        return rc
+    if R:
+        _over_devices(devices, R, call)
+    return _panel_result(out, frm, allrec, records)
+
+
+def motifseq_panel_ragged_f64(values, off, motifs, means, sds, region=(0, None), win=None, scale="medmad", scale_low=0,
+                              scale_hi=1200, records=False, devices=None):
+    """motifseq_panel_batch for a ragged float64 batch (read r = values[off[r]:off[r+1]]): the pA route."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = off.size - 1
+    begin, end = _region_pair(region)
+    ms, flat, moff, means, sds, win = _panel_args(motifs, means, sds, win, R)
+    L = _lib.load()
+    out = np.zeros(R, dtype=PANEL_DTYPE)
+    frm = np.zeros(R, dtype=np.int32)
+    allrec = np.zeros((len(ms), R), dtype=HIT_DTYPE)
+
+    def call(lo, hi):
+        part = np.zeros((len(ms), hi - lo), dtype=HIT_DTYPE)
+        rc = L.sk_motifseq_panel_f64(ptr(values), ptr(off[lo:hi + 1]), hi - lo, begin, end,
+                                     None if win is None else ptr(win[lo:hi]), ptr(flat), ptr(moff), len(ms), ptr(means),
+                                     ptr(sds), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), ptr(out[lo:hi]),
+                                     ptr(frm[lo:hi]), ptr(part) if records else None)
+        if rc == 0:
+            allrec[:, lo:hi] = part
+        return rc
+    if R:
+        _over_devices(devices, R, call)
+    return _panel_result(out, frm, allrec, records)
+
+
+def motifseq_panel(reads, motifs, means, sds, region=(0, None), win=None, scale="medmad", scale_low=0, scale_hi=1200,
+                   records=False, devices=None):
+    """The panel over a list of reads: integer-valued reads go through the int16 kernels, the rest through the float64
+    ones (the same records either way); input order is kept.  See motifseq_panel_batch."""
+    R = len(reads)
+    ms, _, _, means, sds, win = _panel_args(motifs, means, sds, win, R)
+    out = np.zeros(R, dtype=PANEL_DTYPE)
+    frm = np.zeros(R, dtype=np.int32)
+    allrec = np.zeros((len(ms), R), dtype=HIT_DTYPE)
+    ints, arrs, flts = _split_int16(reads)
+    for idx, run in ((ints, lambda w: motifseq_panel_batch(*pack_i16(arrs), ms, means, sds, region, w, scale, scale_low,
+                                                           scale_hi, True, devices)),
+                     (flts, lambda w: motifseq_panel_ragged_f64(*pack_f64([reads[i] for i in flts]), ms, means, sds, region,
+                                                                w, scale, scale_low, scale_hi, True, devices))):
+        if idx:
+            o, f, a = run(None if win is None else win[idx])
+            out[idx], frm[idx] = o, f
+            for k in range(len(ms)):
+                allrec[k][idx] = a[k]
+    return _panel_result(out, frm, allrec, records)
+
+
+def region_rows(sig, lens, region=(0, None), win=None):
+    """The window rows alone (k_region_rows): (rows int16 [R, wstride] zero padded, wlen[R], from[R]) of an int16
+    [R, stride] batch -- what the hit-list and path calls take when they search a region."""
+    L = _lib.ensure_init()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    begin, end = _region_pair(region)
+    if win is not None:
+        win = np.ascontiguousarray(win, dtype=np.int32)
+        se = np.stack([np.array(slice(int(a), int(b)).indices(int(n))[:2]) for (a, b), n in zip(win, lens)]) if R else \
+            np.zeros((0, 2), dtype=np.int64)
+    else:
+        se = resolve_region(lens, begin, None if end == INT32_MAX else end)
+    longest = int(np.clip(se[:, 1] - se[:, 0], 0, None).max()) if R else 0
+    wstride = max(8, (longest + 7) // 8 * 8)
+    rows = np.zeros((R, wstride), dtype=np.int16)
+    wlen = np.zeros(R, dtype=np.int32)
+    frm = np.zeros(R, dtype=np.int32)
+    if R:
+        check(L.sk_region_rows_i16(ptr(sig), stride, ptr(lens), R, begin, end, None if win is None else ptr(win), wstride,
+                                   ptr(rows), ptr(wlen), ptr(frm)))
+    return rows, wlen, frm

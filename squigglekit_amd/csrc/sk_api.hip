@@ -2107,3 +2107,268 @@ int sk_pull_text(const int16_t *sig, int64_t stride, const int32_t *len, int32_t
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
 }
+
+// ------------------------------------------------------------------ MotifSeq panel inside a search region (sk_panel.hip)
+// Per read: the slice raw[begin:end] (or the read's own win row) is cut BEFORE scale_outliers (MotifSeq.py:274,317-324),
+// filter + medmad / zscale (:186-200) run once over the slice, every motif's dtw_subsequence (:436-439) runs over the
+// window in one grid per shape group, and the Z-scores of :441-443 are formed and ranked on the device.
+namespace {
+
+int check_panel(const double *motifs, const int32_t *motif_off, int32_t nmotifs, const double *mean, const double *sd,
+                int32_t scale_mode)
+{
+    if (nmotifs < 1 || nmotifs > 256) return sk_fail(SK_ERR_INVALID, "nmotifs %d outside 1..256", nmotifs);
+    int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
+    if (rc) return rc;
+    if (!mean || !sd) return sk_fail(SK_ERR_INVALID, "NULL mean/sd");
+    for (int32_t k = 0; k < nmotifs; k++) {
+        if (!isfinite(mean[k]) || !isfinite(sd[k])) return sk_fail(SK_ERR_INVALID, "mean / sd of motif %d is not finite", k);
+        if (sd[k] == 0.0) return sk_fail(SK_ERR_INVALID, "sd of motif %d is 0", k);
+    }
+    return SK_OK;
+}
+
+// Read r's window on the host: resolved begin and length.  A win row whose resolved begin lies behind its end is an
+// error unless both ends were cut to the read (what a slice does with a row that lies outside the read altogether).
+int panel_window(int32_t r, int32_t len, int32_t begin, int32_t end, const int32_t *win, int32_t *lo, int32_t *m)
+{
+    int32_t hi;
+    int cl;
+    sk_slice_indices(len, win ? win[2 * r] : begin, win ? win[2 * r + 1] : end, lo, &hi, &cl);
+    if (win && *lo > hi && cl != 3)
+        return sk_fail(SK_ERR_INVALID, "win[%d] = (%d, %d): begin lies behind end in a read of %d samples", r, win[2 * r],
+                       win[2 * r + 1], len);
+    *m = hi > *lo ? hi - *lo : 0;
+    return SK_OK;
+}
+
+int64_t round8(int64_t v) { return v < 8 ? 8 : (v + 7) / 8 * 8; }
+
+// One (sub-)batch of int16 rows, everything device resident: gather, filter + statistics over the windows, DTW of every
+// motif, ranking.  Window rows / lengths / statistics of read r live at slot r of the buffers given.
+int panel_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr, int32_t begin,
+                  int32_t end, const int32_t *d_win, int16_t *d_rows, int64_t wstride, int32_t *d_wlen, int32_t *d_from,
+                  int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                  int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *d_all, int64_t out_stride,
+                  sk_panel_rec *d_out, int later_batch)
+{
+    int rc;
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = sk_launch_region_rows_i16(c, d_sig, stride, d_len, nr, begin, end, d_win, d_rows, wstride, d_wlen, d_from)))
+        return rc;
+    rc = sk_launch_prep_i16(c, d_rows, wstride, d_wlen, nr, scale_low, scale_hi,
+                            scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp, d_prep, nullptr, 0);
+    if (rc) return rc;
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    sk_sdtw_args a;
+    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = wstride; a.off = nullptr; a.prep = d_prep; a.nreads = nr;
+    a.motif = nullptr; a.nmotif = 0; a.out = nullptr; a.last_row = nullptr; a.max_len = wstride; a.force_single = 1;
+    a.accumulate = later_batch;
+    if ((rc = sk_launch_panel_dtw(c, &a, motifs, motif_off, d_all, out_stride))) return rc;
+    if ((rc = sk_launch_panel_rank(c, d_all, out_stride, nr, nmotifs, d_out))) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_motifseq_panel_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              int32_t begin, int32_t end, const int32_t *d_win,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                              const double *mean, const double *sd,
+                              int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
+                              sk_panel_rec *d_out, int32_t *d_from, sk_hit *d_all)
+{
+    SK_ENTER(c);
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (rc) return rc;
+    if ((rc = check_panel(motifs, motif_off, nmotifs, mean, sd, scale_mode))) return rc;
+    if (nreads == 0) return SK_OK;
+    if (!d_out) return sk_fail(SK_ERR_INVALID, "NULL out");
+    clamp_limits(&scale_low, &scale_hi);
+    redo_forget(c);
+    // the longest slice any read can resolve to, from the per-call pair alone (the lengths live on the device)
+    int64_t bound = stride;
+    if (!d_win) {
+        const int64_t b = begin, e = end;
+        if (b >= 0 && e >= 0 && end != INT32_MAX) bound = e > b ? e - b : 0;
+        else if (b < 0 && end == INT32_MAX) bound = -b;
+        else if (b < 0 && e < 0) bound = e > b ? e - b : 0;
+        if (bound > stride) bound = stride;
+    }
+    const int64_t wstride = round8(bound);
+    if ((rc = sk_reserve(c, &c->panelwin, (size_t)nreads * (size_t)wstride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->panelaux, (size_t)nreads * 2 * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)wstride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    if (!d_all) {
+        if ((rc = sk_reserve(c, &c->panelrec, (size_t)nreads * (size_t)nmotifs * sizeof(sk_hit)))) return rc;
+        d_all = (sk_hit *)c->panelrec.p;
+    }
+    if ((rc = sk_panel_plan(c, motifs, motif_off, nmotifs, mean, sd, (int64_t)nreads * nmotifs))) return rc;
+    int32_t *d_wlen = (int32_t *)c->panelaux.p;
+    return panel_dev_i16(c, d_sig, stride, d_len, nreads, begin, end, d_win, (int16_t *)c->panelwin.p, wstride, d_wlen,
+                         d_from ? d_from : d_wlen + nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
+                         nmotifs, scale_mode, scale_low, scale_hi, d_all, nreads, d_out, 0);
+}
+
+int sk_motifseq_panel_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          int32_t begin, int32_t end, const int32_t *win,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                          const double *mean, const double *sd,
+                          int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
+                          sk_panel_rec *out, int32_t *from, sk_hit *all)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    if ((rc = check_panel(motifs, motif_off, nmotifs, mean, sd, scale_mode))) return rc;
+    if (nreads == 0) return SK_OK;
+    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
+    clamp_limits(&scale_low, &scale_hi);
+    int64_t longest = 0;
+    for (int32_t r = 0; r < nreads; r++) {
+        int32_t lo, m;
+        if ((rc = panel_window(r, len[r], begin, end, win, &lo, &m))) return rc;
+        if (m > longest) longest = m;
+    }
+    const int64_t wstride = round8(longest);
+    const size_t wb = (size_t)nreads * (size_t)wstride * sizeof(int16_t);
+    const size_t ab = (size_t)nreads * (size_t)nmotifs * sizeof(sk_hit);
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->panelwin, wb))) return rc;
+    if ((rc = sk_reserve(c, &c->panelaux, (size_t)nreads * 4 * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->comp, wb))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    if ((rc = sk_reserve(c, &c->panelrec, ab + (size_t)nreads * sizeof(sk_panel_rec)))) return rc;
+    redo_forget(c);
+    const SubBatches B = sub_batches(nreads, stride);
+    if ((rc = sk_panel_plan(c, motifs, motif_off, nmotifs, mean, sd, (int64_t)B.per * nmotifs))) return rc;
+    int32_t *d_wlen = (int32_t *)c->panelaux.p, *d_from = d_wlen + nreads, *d_win = nullptr;
+    if (win) {
+        d_win = d_from + nreads;
+        SK_HIP(hipMemcpyAsync(d_win, win, (size_t)nreads * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    sk_hit *d_all = (sk_hit *)c->panelrec.p;
+    sk_panel_rec *d_out = (sk_panel_rec *)(d_all + (size_t)nreads * (size_t)nmotifs);
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return panel_dev_i16(c, d_sig, stride, d_len, nr, begin, end, d_win ? d_win + 2 * (size_t)r0 : nullptr,
+                                              (int16_t *)c->panelwin.p + (size_t)r0 * (size_t)wstride, wstride, d_wlen + r0,
+                                              d_from + r0, (int16_t *)c->comp.p + (size_t)r0 * (size_t)wstride,
+                                              (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
+                                              scale_hi, d_all + r0, nreads, d_out + r0, r0 > 0);
+                     });
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, (size_t)nreads * sizeof(sk_panel_rec), hipMemcpyDeviceToHost, c->stream));
+    if (from) SK_HIP(hipMemcpyAsync(from, d_from, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (all) SK_HIP(hipMemcpyAsync(all, d_all, ab, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_motifseq_panel_f64(const double *sig, const int64_t *off, int32_t nreads,
+                          int32_t begin, int32_t end, const int32_t *win,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                          const double *mean, const double *sd,
+                          int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
+                          sk_panel_rec *out, int32_t *from, sk_hit *all)
+{
+    SK_ENTER(c);
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_panel(motifs, motif_off, nmotifs, mean, sd, scale_mode);
+    if (rc) return rc;
+    if (nreads == 0) return SK_OK;
+    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen))) return rc;     // (checks sig / off and the lengths)
+    // the windows, resolved on the host: source offset of each and the ragged offsets of the gathered batch
+    std::vector<int64_t> aux(2 * (size_t)nreads + 1);
+    int64_t *src = aux.data(), *woff = src + nreads;
+    std::vector<int32_t> lo_host((size_t)nreads);
+    int64_t wtotal = 0, wmax = 0;
+    for (int32_t r = 0; r < nreads; r++) {
+        int32_t lo, m;
+        if ((rc = panel_window(r, (int32_t)(off[r + 1] - off[r]), begin, end, win, &lo, &m))) return rc;
+        src[r] = off[r] - off[0] + lo;
+        woff[r] = wtotal;
+        wtotal += m;
+        if (m > wmax) wmax = m;
+        lo_host[r] = lo;
+    }
+    woff[nreads] = wtotal;
+    const size_t ab = (size_t)nreads * (size_t)nmotifs * sizeof(sk_hit);
+    if ((rc = sk_reserve(c, &c->panelwin, (size_t)(wtotal > 0 ? wtotal : 1) * sizeof(double)))) return rc;
+    if ((rc = sk_reserve(c, &c->panelaux, aux.size() * sizeof(int64_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->panelrec, ab + (size_t)nreads * sizeof(sk_panel_rec)))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    if ((rc = sk_panel_plan(c, motifs, motif_off, nmotifs, mean, sd, (int64_t)nreads * nmotifs))) return rc;
+    const int64_t *d_src = (const int64_t *)c->panelaux.p, *d_woff = d_src + nreads;
+    double *d_wsig = (double *)c->panelwin.p;
+    SK_HIP(hipMemcpyAsync(c->panelaux.p, aux.data(), aux.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_launch_region_rows_f64(c, (const double *)c->sig.p, d_src, d_woff, nreads, d_wsig))) return rc;
+    if ((rc = prep_f64(c, d_wsig, d_woff, nreads, wtotal, wmax, scale_mode, scale_low, scale_hi))) return rc;
+    sk_sdtw_args a;
+    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_wsig; a.stride = 0; a.off = d_woff;
+    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.motif = nullptr; a.nmotif = 0; a.out = nullptr;
+    a.last_row = nullptr; a.max_len = wmax; a.force_single = 1;
+    sk_hit *d_all = (sk_hit *)c->panelrec.p;
+    sk_panel_rec *d_out = (sk_panel_rec *)(d_all + (size_t)nreads * (size_t)nmotifs);
+    if ((rc = sk_launch_panel_dtw(c, &a, motifs, motif_off, d_all, nreads))) return rc;
+    if ((rc = sk_launch_panel_rank(c, d_all, nreads, nreads, nmotifs, d_out))) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    SK_HIP(hipMemcpyAsync(out, d_out, (size_t)nreads * sizeof(sk_panel_rec), hipMemcpyDeviceToHost, c->stream));
+    if (all) SK_HIP(hipMemcpyAsync(all, d_all, ab, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));                      // (aux goes out of scope)
+    if (from) memcpy(from, lo_host.data(), (size_t)nreads * sizeof(int32_t));
+    return SK_OK;
+}
+
+int sk_region_rows_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                       int32_t begin, int32_t end, const int32_t *win, int64_t wstride,
+                       int16_t *rows, int32_t *wlen, int32_t *from)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    if (wstride < 8 || wstride % 8) return sk_fail(SK_ERR_INVALID, "wstride must be a positive multiple of 8");
+    if (nreads == 0) return SK_OK;
+    if (!rows || !wlen) return sk_fail(SK_ERR_INVALID, "NULL rows/wlen");
+    for (int32_t r = 0; r < nreads; r++) {
+        int32_t lo, m;
+        if ((rc = panel_window(r, len[r], begin, end, win, &lo, &m))) return rc;
+        if (m > wstride) return sk_fail(SK_ERR_INVALID, "read %d: a window of %d samples does not fit wstride %lld", r, m, (long long)wstride);
+    }
+    const size_t wb = (size_t)nreads * (size_t)wstride * sizeof(int16_t);
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->panelwin, wb))) return rc;
+    if ((rc = sk_reserve(c, &c->panelaux, (size_t)nreads * 4 * sizeof(int32_t)))) return rc;
+    int32_t *d_wlen = (int32_t *)c->panelaux.p, *d_from = d_wlen + nreads, *d_win = nullptr;
+    if (win) {
+        d_win = d_from + nreads;
+        SK_HIP(hipMemcpyAsync(d_win, win, (size_t)nreads * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return sk_launch_region_rows_i16(c, d_sig, stride, d_len, nr, begin, end,
+                                                          d_win ? d_win + 2 * (size_t)r0 : nullptr,
+                                                          (int16_t *)c->panelwin.p + (size_t)r0 * (size_t)wstride, wstride,
+                                                          d_wlen + r0, d_from + r0);
+                     });
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(rows, c->panelwin.p, wb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(wlen, d_wlen, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (from) SK_HIP(hipMemcpyAsync(from, d_from, (size_t)nreads * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+} // extern "C"

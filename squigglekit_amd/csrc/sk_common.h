@@ -39,6 +39,18 @@ struct sk_buf {
     size_t cap = 0;
 };
 
+// Motif panel (sk_panel.hip): one motif's place in the per-call device table, and the motifs that share a lane layout.
+struct sk_panel_motif {
+    int32_t xoff;     // first double of its [L][R] layout inside the panel's layout block
+    int32_t P;        // short lanes (own R - 1 rows)
+    int32_t k;        // the caller's motif index: records go to out[k * out_stride + read]
+    int32_t pad;
+};
+struct sk_panel_group {
+    int32_t L, R;     // lanes per read, rows per lane
+    int32_t first, count;   // its run of table entries
+};
+
 struct sk_ctx {
     int         device = -1;
     bool        ready = false;
@@ -80,6 +92,14 @@ struct sk_ctx {
     sk_buf pathscratch;   // alignment paths: the scratch tier's slabs (direction words + stripe boundary row per wavefront)
     sk_buf pathmotif; // alignment paths: the motifs of the call, flat (device)
     sk_buf pathspans; // alignment paths: the spans of the host entry points
+    sk_buf panel;     // motif panel: the motifs of the call laid out per lane, their table, mean / sd (sk_panel.hip)
+    sk_buf panelwin;  // motif panel: the window rows (int16, stride wstride) or the gathered float64 windows
+    sk_buf panelaux;  // motif panel: per read window length, resolved begin, the caller's win rows / float64 offsets
+    sk_buf panelrec;  // motif panel: [K][R] records when the caller takes none, and the host entry points' sk_panel_rec
+    std::vector<double> panel_host;           // laid-out motifs as uploaded (kept alive for the async H2D)
+    std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
+    std::vector<sk_panel_group> panel_groups;
+    std::vector<int32_t> panel_long;          // motifs of more than 1 024 points: the chained launcher, one at a time
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -259,6 +279,40 @@ int sk_launch_paths(sk_ctx *c, const sk_path_args *p);
 // fixed-point screening + certified window over all reads (sk_sdtwq.hip); leaves the retry list on the device
 int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, int span2,
                           int32_t *d_retry_cnt, int32_t *d_retry, int32_t *d_early_cnt, int32_t *d_early);
+
+// ---- motif panel inside a search region (sk_panel.hip) ----
+// slice(begin, end).indices(len) of a Python slice with step 1: *lo = start, *hi = stop (stop < start: empty).
+// clamped (optional): bit 0 / bit 1 = begin / end lay outside the read and was cut to it.
+__host__ __device__ static inline void sk_slice_indices(int32_t len, int32_t begin, int32_t end, int32_t *lo, int32_t *hi, int *clamped = nullptr)
+{
+    int64_t s = begin, e = end;
+    int cl = 0;
+    if (s < 0) { s += len; if (s < 0) { s = 0; cl |= 1; } } else if (s > len) { s = len; cl |= 1; }
+    if (e < 0) { e += len; if (e < 0) { e = 0; cl |= 2; } } else if (e > len) { e = len; cl |= 2; }
+    *lo = (int32_t)s; *hi = (int32_t)e;
+    if (clamped) *clamped = cl;
+}
+// k_region_rows: read r's slice [begin:end] (or d_win[r][0] : d_win[r][1]) of its first min(d_len[r], stride) samples ->
+// d_rows + r * wstride (zero padded to wstride, a multiple of 8; a slice longer than wstride is cut to it), its length
+// -> d_wlen[r], the resolved raw begin -> d_from[r] (may be nullptr).
+int sk_launch_region_rows_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              int32_t begin, int32_t end, const int32_t *d_win, int16_t *d_rows, int64_t wstride,
+                              int32_t *d_wlen, int32_t *d_from);
+// float64 reads: window r = d_sig[d_src[r] .. d_src[r] + (d_woff[r + 1] - d_woff[r])) -> d_out + d_woff[r]
+int sk_launch_region_rows_f64(sk_ctx *c, const double *d_sig, const int64_t *d_src, const int64_t *d_woff, int32_t nreads,
+                              double *d_out);
+// Lays the motifs of a call out per lane, groups them by (L, R) and uploads layouts, table, mean and sd (c->panel);
+// `pairs`: reads x motifs the call will sweep at a time (chooses four reads or one read per wavefront).
+int sk_panel_plan(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs, const double *mean,
+                  const double *sd, int64_t pairs);
+// k_panel_dtw over prepared reads (feed / samples / samples_raw / stride / off / prep / nreads / max_len of `base`) and
+// every motif of the plan: motif k's record of read r -> d_all[k * out_stride + r].  motifs: the caller's (host), for
+// the chained launcher of the long ones.
+int sk_launch_panel_dtw(sk_ctx *c, const sk_sdtw_args *base, const double *motifs, const int32_t *motif_off,
+                        sk_hit *d_all, int64_t out_stride);
+// k_panel_rank: scores and ranking of nreads reads from d_all[k * out_stride + r] -> d_out[r]
+int sk_launch_panel_rank(sk_ctx *c, const sk_hit *d_all, int64_t out_stride, int32_t nreads, int32_t nmotifs,
+                         sk_panel_rec *d_out);
 
 // ---- dRNA --signal branch (rolling mean): statistics + masks (sk_prep.hip), scan (sk_drna_walk.hip) ----
 struct sk_roll_params;

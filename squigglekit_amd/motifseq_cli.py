@@ -5,7 +5,8 @@ scale_outliers + medmad/zscale + dtw_subsequence run on the GPU (batched, C ABI)
 the scoring of MotifSeq.py:441-445 stays in Python so the printed floats are the
 reference's digit for digit.  fast5 input (-f / -p) goes through h5py when it is importable and
 through the built-in reader (hdf5min.py) otherwise, with the reference's stderr messages.
-Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p, --paths.
+Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p, --paths,
+--region, --panel.
 Whole chunks of plain integer reads (TSV chunks, BLOW5 / packed blocks) go to the GPU as one batch and their rows are
 formatted natively (csrc/sk_io.cpp writes floats as Python does); anything unusual takes the per-read route.
 """
@@ -86,9 +87,32 @@ def build_parser():
     p.add_argument("--paths", default=None, metavar="FILE",
                    help="[extension] write to FILE, per printed hit and motif base, the samples the alignment path gives "
                         "that base (start, end, length, mean normalised signal); stdout is unchanged")
+    p.add_argument("--region", default=None, metavar="A:B",
+                   help="[extension] search only the raw samples [A:B] of every read, cut as a Python slice before the outlier "
+                        "filter (either side may be empty or negative: 0:2000, --region=-3000:); coordinates then index "
+                        "that slice and a last column `search_from` gives the raw sample index where it starts")
+    p.add_argument("--panel", action="store_true",
+                   help="[extension] two or more motifs: one row per read naming the motif with the smallest Z-score, the "
+                        "runner-up and their difference (ranked on the GPU)")
     return p
 
 
+def parse_region(parser, text):
+    """'A:B' -> (begin, end); an empty side is None."""
+    parts = text.split(":")
+    try:
+        if len(parts) != 2:
+            raise ValueError(text)
+        begin, end = (None if x.strip() == "" else int(x) for x in parts)
+    except ValueError:
+        parser.error("--region takes A:B with integer or empty sides, got {!r}".format(text))
+    if any(v is not None and not -2 ** 31 <= v < 2 ** 31 - 1 for v in (begin, end)):
+        parser.error("--region bounds must fit int32")
+    return (0 if begin is None else begin, end)
+
+
+PANEL_HEADER = ["fast5", "readID", "best_model", "start", "end", "length", "distance_score", "Z-score", "p-value",
+                "hit_Probability", "second_model", "second_Z", "delta_Z", "search_from"]
 PATHS_HEADER = ["fast5", "readID", "model", "hit", "pos", "base", "model_current", "start", "end", "length", "mean_signal"]
 
 
@@ -102,6 +126,11 @@ def check_hit_flags(parser, args):
         parser.error("--min_hit_p needs --hits")
     if args.hits is not None and args.after_stall:
         parser.error("--hits does not combine with --after_stall")
+    if args.region is not None and args.after_stall:
+        parser.error("--region does not combine with --after_stall")
+    args.region = None if args.region is None else parse_region(parser, args.region)
+    if args.panel and (args.hits is not None or args.paths is not None or args.sig_extract or args.after_stall):
+        parser.error("--panel prints one row per read: it does not combine with --hits, --paths, -x or --after_stall")
 
 
 def norm_cdf(z):
@@ -143,6 +172,8 @@ class _Batcher:
         self.meta, self.sigs = [], []
         self._pending, self._worker = None, None
         self.bases, self.paths_fh = {}, None          # --paths: base table per model (scrappie text), the open FILE
+        # --region / --panel: every read goes through the per-read queue (add / flush), --batch reads per GPU call
+        self.queued = args.region is not None or args.panel
 
     def search(self, fn_hits, fn_multi, fn_paths, *args):
         """The GPU call of one batch: (what of_read / table take, spans per motif or None).  --paths takes the paths
@@ -191,6 +222,12 @@ class _Batcher:
         live = [i for i, s in enumerate(self.sigs) if s is not None]
         sigs = [self.sigs[i] for i in live]
         cuts = None
+        motifs = [np.asarray(self.models[name], dtype=np.float64) for name in self.order]
+        if self.queued and sigs:
+            _STATS[0].batch(len(sigs))
+            self.flush_region(live, sigs, motifs)
+            self.meta, self.sigs = [], []
+            return
         if a.after_stall and sigs:                    # [extension] search only after the segmenter's first segment
             cuts = api.stall_cuts(sigs)
             sigs = [np.asarray(s)[c:] for s, c in zip(sigs, cuts)]
@@ -198,7 +235,6 @@ class _Batcher:
                 self.sigs[i] = s
         if sigs:
             _STATS[0].batch(len(sigs))
-        motifs = [np.asarray(self.models[name], dtype=np.float64) for name in self.order]
         if sigs or a.hits is not None:
             hits, spans = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths, sigs, motifs)
         else:
@@ -212,6 +248,96 @@ class _Batcher:
             self.emit(fast5, read_id, self.of_read(hits, r), self.sigs[i], None if cuts is None else int(cuts[r]),
                       None if spans is None else [sp[r] for sp in spans])
         self.meta, self.sigs = [], []
+
+    def windows(self, sigs, region):
+        """The reads cut to the region: (windows, raw index each starts at).  Integer reads are gathered on the GPU
+        (api.region_rows), the rest sliced here -- the same slice either way."""
+        out, frm = [None] * len(sigs), np.zeros(len(sigs), dtype=np.int64)
+        ints, arrs, flts = api._split_int16(sigs)
+        if ints:
+            rows, wlen, f = api.region_rows(*api.pack_i16(arrs), region)
+            for k, i in enumerate(ints):
+                out[i], frm[i] = rows[k, :wlen[k]], f[k]
+        for i in flts:
+            s = np.asarray(sigs[i])
+            lo, hi = slice(*region).indices(s.size)[:2]
+            out[i], frm[i] = s[lo:hi], lo
+        return out, frm
+
+    def flush_region(self, live, sigs, motifs):
+        """--region / --panel over the queued reads.  --hits / --paths: the window rows go to the existing hit-list and
+        path calls; otherwise the panel call searches every motif inside the region in one GPU call."""
+        a = self.args
+        region = a.region if a.region is not None else (0, None)
+        mm = np.array([(a.slope * self.lens[c]) + a.intercept for c in range(len(self.order))], dtype=np.float64)
+        ms = mm * a.std_const                                               # MotifSeq.py:441-442
+        slot = {i: k for k, i in enumerate(live)}
+        if a.panel:
+            recs, frm = api.motifseq_panel(sigs, motifs, mm, ms, region, None, a.scale, a.scale_low, a.scale_hi)
+            keep = []
+            for i, (fast5, read_id) in enumerate(self.meta):
+                if self.sigs[i] is None:
+                    if keep:
+                        self.panel_table(keep, recs, frm)
+                        keep = []
+                    sys.stderr.write(read_id)
+                    continue
+                r = slot[i]
+                fl = int(recs[r]["hit"]["flags"])
+                if recs[r]["best"] >= 0:
+                    keep.append((fast5, read_id, r))
+                elif fl & 1:
+                    sys.stderr.write("MotifSeq: no sample of {} survived the outlier limits; skipped\n".format(read_id))
+                elif fl & 2:
+                    sys.stderr.write("MotifSeq: the MAD of {} is 0 (medmad divides by it, MotifSeq.py:196-199); "
+                                     "skipped\n".format(read_id))
+                else:
+                    sys.stderr.write("MotifSeq: no motif has a finite score in {}; skipped\n".format(read_id))
+            if keep:
+                self.panel_table(keep, recs, frm)
+            return
+        if a.hits is not None or a.paths is not None:
+            wins, frm = self.windows(sigs, region)
+            hits, spans = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths, wins, motifs)
+        else:
+            _, frm, hits = api.motifseq_panel(sigs, motifs, mm, ms, region, None, a.scale, a.scale_low, a.scale_hi,
+                                              records=True)
+            wins, spans = None, None
+        for i, (fast5, read_id) in enumerate(self.meta):
+            if self.sigs[i] is None:
+                sys.stderr.write(read_id)
+                continue
+            r = slot[i]
+            if wins is not None:
+                sig = wins[r]
+            else:                                                           # (-x / --strict-compat normalise the slice)
+                sig = np.asarray(sigs[r])[slice(*region)] if (a.sig_extract or a.strict_compat) else None
+            self.emit(fast5, read_id, self.of_read(hits, r), sig, int(frm[r]), None if spans is None else [sp[r] for sp in spans])
+
+    def panel_table(self, keep, recs, frm):
+        """The --panel rows of the reads in `keep` [(fast5, readID, slot)] through the native formatter: the GPU's scores,
+        scipy's ndtr restated (fastio.ndtr) and Python's float text (fastio.fmt_rows)."""
+        idx = np.array([r for _, _, r in keep], dtype=np.int64)
+        rec = recs[idx]
+        names = [nm.encode() for nm in self.order] + [b"."]
+        nblob = b"".join(names)
+        noff = np.concatenate([[0], np.cumsum([len(x) for x in names])]).astype(np.int64)
+        nspan = np.stack([noff[:-1], noff[1:]], axis=1)
+
+        def strs(items):
+            enc = [x.encode() if isinstance(x, str) else bytes(x) for x in items]
+            return ("str", b"".join(enc), np.concatenate([[0], np.cumsum([len(x) for x in enc])]).astype(np.int64))
+        z, z2 = rec["score_best"], rec["score_second"]
+        with np.errstate(all="ignore"):
+            pv = norm_cdf(z)
+            hp = (1 - pv) * 100
+            dz = z2 - z
+        h = rec["hit"]
+        cols = [strs([k[0] for k in keep]), strs([k[1] for k in keep]), ("span", nblob, nspan[rec["best"]]),
+                ("i32", h["start"]), ("i32", h["end"]), ("i32", h["end"] - h["start"]), ("f64", h["dist"]), ("f64", z),
+                ("f64", pv), ("f64", hp), ("span", nblob, nspan[rec["second"]]), ("f64", z2), ("f64", dz),
+                ("i32", frm[idx])]
+        fastio.write_stdout(fastio.fmt_rows(len(keep), cols))
 
     def of_read(self, hits, r):
         """Read r's entry per motif: its record, or with --hits (its records [K], their count)."""
@@ -359,7 +485,7 @@ class _Batcher:
         if not len(nsamp):
             return
         a = self.args
-        if a.after_stall:
+        if a.after_stall or self.queued:
             # get_segs first, then the search behind the stall: the per-read queue does that (api.motifseq_after_stall,
             # up to --batch reads per GPU call) and prints the search_from column; `rows` is reused by the reader
             self.drain()
@@ -431,7 +557,7 @@ class _Batcher:
         tokenizer's rows (every motif against them); any other line takes the per-read route, in its place."""
         a = self.args
         fast = (blk.flags & 27) == 3                                        # ALLINT | ANY, not SLOW / SHORT
-        if a.after_stall or a.paths is not None:
+        if a.after_stall or a.paths is not None or self.queued:
             fast[:] = False                                                 # (needs the raw reads on the host)
         idx = np.flatnonzero(fast)
         if idx.size == blk.n and blk.n and not a.sig_extract:
@@ -504,7 +630,7 @@ class _Batcher:
                                      str(mm), str(ms), repr(z[k]), repr(pv[k]), repr(hp[k]))))
                 continue
             fl = int(blk.flags[i])
-            if a.after_stall or a.paths is not None:
+            if a.after_stall or a.paths is not None or self.queued:
                 # nothing of this chunk was printed directly, so the batcher alone keeps the file order: reads queue
                 # up to --batch per GPU call (segment + search) instead of one call per read
                 if (fl & 27) == 1:
@@ -553,8 +679,13 @@ def main(argv=None):
     del _KEEP[:]                                     # (a previous call in this process: its buffers can go now)
     models, order, lens = load_models(args)
     _mark("models loaded")
-    print("\t".join(HEADER + (["normalised_signal"] if args.sig_extract else [])
-                    + (["search_from"] if args.after_stall else [])))                  # MotifSeq.py:160-163
+    if args.panel and len(order) < 2:
+        parser.error("--panel needs two or more motifs, got {}".format(len(order)))
+    if args.panel:
+        print("\t".join(PANEL_HEADER))
+    else:
+        print("\t".join(HEADER + (["normalised_signal"] if args.sig_extract else [])
+                        + (["search_from"] if args.after_stall or args.region is not None else [])))   # MotifSeq.py:160-163
 
     if not (args.f5f or args.f5_path or args.signal or args.blow5 or args.i16):
         sys.stderr.write("Unknown file or path input")
@@ -585,7 +716,7 @@ def main(argv=None):
                 fb = blk.float_block(8)
                 if fb is None:
                     continue
-            if fb.clean() and not (args.sig_extract or args.after_stall or args.paths is not None):
+            if fb.clean() and not (args.sig_extract or args.after_stall or args.paths is not None or out.queued):
                 out.rows_f64(fb)                         # the whole chunk as one batch, no Python per read
                 continue
             out.flush()
