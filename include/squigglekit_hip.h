@@ -350,6 +350,49 @@ int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_
  * reports 0. */
 int sk_last_path_mismatches(void);
 
+/* Read background: the hit list, and per read and motif the statistics of the whole last DTW row the hits were
+ * taken from.  view_region draws a hit against its read's own row of distance scores (MotifSeq.py:507-513:
+ * M = np.mean(cost[-1,]), S = np.std(cost[-1,]), lines at M and M - S); with d = cost[-1, :] of motif k against
+ * read r (its n filtered, normalised samples -- the row the hit list selects from), one record holds, bit for bit
+ * what numpy gives on that row:
+ *   mean   = np.mean(d)                 (np.add.reduce's order: serial over chunks of 8 192, pairwise inside)
+ *   std    = np.std(d)                  (ddof 0, two passes: sqrt(sum((d - mean)^2) / n), the same order)
+ *   median = np.median(d)               (even n: (a + b) / 2 of the two middle values)
+ *   mad    = np.median(np.abs(d - median))          (not multiplied by 1.4826)
+ *   below  = number of columns with d[j] < mean - std   (one float64 subtraction, strict compare; :510)
+ *   n      = columns of the row = the read's filtered length
+ * A read flagged SK_FLAG_EMPTY or SK_FLAG_DEGENERATE has four NaNs, below = -1 and its n.  Scores of a hit
+ * against its read are left to the caller: local_Z = (dist - mean) / std, robust_Z = (dist - median) /
+ * (mad * 1.4826), the constant of MotifSeq.py:192-200. */
+typedef struct sk_bg_rec {          /* 48 bytes */
+    double  mean;
+    double  std;
+    double  median;
+    double  mad;
+    int32_t below;
+    int32_t n;
+    int32_t reserved[2];            /* 0 */
+} sk_bg_rec;
+/* bg is [nmotifs][nreads]; out / count: exactly what the sk_motifseq_hits_* twin returns; the other arguments are
+ * its own.  A NULL bg is SK_ERR_INVALID. */
+int sk_motifseq_background_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                               int32_t *count, sk_bg_rec *bg);
+int sk_motifseq_background_f64(const double *sig, const int64_t *off, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                               int32_t *count, sk_bg_rec *bg);
+int sk_motifseq_background_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                                 const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                                 int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                                 int32_t *count, sk_bg_rec *bg);
+/* device-resident form (d_sig, d_len, d_out, d_count, d_bg device; motifs / motif_off host) */
+int sk_motifseq_background_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                                   const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                                   int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                                   int32_t *d_count, sk_bg_rec *d_bg);
+
 /* Motif panel inside a search region: which of K known signals (barcodes, adapters, primers) sits at a known place of
  * the read.  Region: read r's raw samples are cut as the Python slice raw[begin:end] BEFORE scale_outliers -- negative
  * values count from the end of the read, end = INT32_MAX means "to the end", everything resolved as

@@ -124,6 +124,18 @@ class PanelRec(C.Structure):
 PANEL_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("score_best", "<f8"), ("score_second", "<f8"),
                         ("hit", HIT_DTYPE)])
 
+
+class BgRec(C.Structure):
+    """sk_bg_rec: the statistics of one read's whole last DTW row against one motif (MotifSeq.py:507-513)."""
+    _fields_ = [("mean", C.c_double), ("std", C.c_double), ("median", C.c_double), ("mad", C.c_double),
+                ("below", C.c_int32), ("n", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# the six fields of the 48-byte record (its two reserved words are not exposed)
+BG_DTYPE = np.dtype({"names": ["mean", "std", "median", "mad", "below", "n"],
+                     "formats": ["<f8", "<f8", "<f8", "<f8", "<i4", "<i4"],
+                     "offsets": [0, 8, 16, 24, 32, 36], "itemsize": 48})
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -179,6 +191,14 @@ ABI = {
                                          C.c_int32, C.c_double, _vp, _vp]),
     "sk_motifseq_hits_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_motifseq_background_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_background_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_background_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_background_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
     "sk_motifseq_paths_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
     "sk_motifseq_paths_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

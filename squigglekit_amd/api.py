@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (HIT_DTYPE, PANEL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, HIT_DTYPE, PANEL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -865,6 +865,109 @@ def motifseq_hits(reads, motifs, max_hits=8, max_dist=float("inf"), scale="medma
                                                                   scale_hi, devices)):
             h[flts], c[flts] = hf, cf
     return res
+
+
+# ----------------------------------------------------------------------------
+# MotifSeq read background: the hit list plus the statistics of each read's whole last row
+# ----------------------------------------------------------------------------
+MAD_SCALE = 1.4826                     # medmad's constant (MotifSeq.py:192-200)
+
+
+def _background_over(devices, R, ms, K, entry_call):
+    """Runs entry_call(lo, hi, hits_part, count_part, bg_part) over the devices (the split of motifseq_hits_batch);
+    returns per motif (hits[R, K], count[R], bg[R])."""
+    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
+    count = np.zeros((len(ms), R), dtype=np.int32)
+    bg = np.zeros((len(ms), R), dtype=BG_DTYPE)
+
+    def call(lo, hi):
+        part = np.zeros((len(ms), hi - lo, K), dtype=HIT_DTYPE)
+        cnt = np.zeros((len(ms), hi - lo), dtype=np.int32)
+        b = np.zeros((len(ms), hi - lo), dtype=BG_DTYPE)
+        rc = entry_call(lo, hi, part, cnt, b)
+        if rc == 0:
+            hits[:, lo:hi] = part
+            count[:, lo:hi] = cnt
+            bg[:, lo:hi] = b
+        return rc
+    if R and ms:
+        _over_devices(devices, R, call)
+    return [(hits[k], count[k], bg[k]) for k in range(len(ms))]
+
+
+def motifseq_background_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
+                              scale_hi=1200, devices=None):
+    """motifseq_hits_batch plus each read's own background: a list, per motif, of (hits[R, max_hits], count[R], bg[R]).
+    bg (BG_DTYPE) describes d = cost[-1, :], the whole last DTW row of the motif against the read -- the row view_region
+    draws a hit against (MotifSeq.py:507-513) -- bit for bit as numpy would: mean = np.mean(d), std = np.std(d),
+    median = np.median(d), mad = np.median(np.abs(d - median)), below = the columns with d < mean - std, n = columns.
+    Reads flagged empty or degenerate: NaN, below -1.  local_scores turns a hit's distance into scores against it."""
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    R = sig.shape[0]
+    if _too_wide_for_i16(scale_low, scale_hi):
+        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
+        return motifseq_background_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
+    L = _lib.load()
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, part, cnt, b):
+        return L.sk_motifseq_background_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat),
+                                            ptr(moff), len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K,
+                                            md, ptr(part), ptr(cnt), ptr(b))
+    return _background_over(devices, R, ms, K, call)
+
+
+def motifseq_background_ragged_f64(values, off, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
+                                   scale_hi=1200, devices=None):
+    """motifseq_hits_ragged_f64 plus the background records (see motifseq_background_batch); int32 values are
+    centi-units."""
+    L = _lib.load()
+    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
+    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
+    entry = L.sk_motifseq_background_centi if centi else L.sk_motifseq_background_f64
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = off.size - 1
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, part, cnt, b):
+        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
+                     int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt), ptr(b))
+    return _background_over(devices, R, ms, K, call)
+
+
+def motifseq_background(reads, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
+                        devices=None):
+    """motifseq_hits plus each read's own background: a list, per motif, of
+    (hits[nreads, max_hits], count[nreads], bg[nreads]) -- see motifseq_background_batch.  The same read kinds as
+    motifseq_hits: integer-valued reads through the int16 kernels, the rest through the float64 ones."""
+    ms = _hits_args(motifs, max_hits, max_dist)[0]
+    ints, arrs, flts = _split_int16(reads)
+    R, K = len(reads), int(max_hits)
+    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32), np.zeros(R, dtype=BG_DTYPE)) for _ in ms]
+    if ints and ms:
+        buf, lens = pack_i16(arrs)
+        for (h, c, b), (hi, ci, bi) in zip(res, motifseq_background_batch(buf, lens, ms, K, max_dist, scale, scale_low,
+                                                                          scale_hi, devices)):
+            h[ints], c[ints], b[ints] = hi, ci, bi
+    if flts and ms:
+        flat, off = pack_f64([reads[i] for i in flts])
+        for (h, c, b), (hf, cf, bf) in zip(res, motifseq_background_ragged_f64(flat, off, ms, K, max_dist, scale,
+                                                                               scale_low, scale_hi, devices)):
+            h[flts], c[flts], b[flts] = hf, cf, bf
+    return res
+
+
+def local_scores(dist, bg):
+    """(local_Z, robust_Z) of hit distances against their reads' background records (arrays that broadcast against each
+    other, e.g. hits["dist"] [R, K] and bg[:, None]): local_Z = (dist - mean) / std and robust_Z = (dist - median) /
+    (mad * 1.4826), in numpy float64 on the host like MotifSeq's own scores.  std == 0 or mad == 0 give the IEEE result
+    (inf or NaN)."""
+    dist = np.asarray(dist, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        local_z = (dist - bg["mean"]) / bg["std"]
+        robust_z = (dist - bg["median"]) / (bg["mad"] * MAD_SCALE)
+    return local_z, robust_z
 
 
 # ----------------------------------------------------------------------------

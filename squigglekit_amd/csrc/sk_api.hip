@@ -647,9 +647,11 @@ static int check_hits(int32_t max_hits, double max_dist, const void *out, const 
 }
 
 // base: feed, samples (+ samples_raw), stride / off, prep, max_len and nreads of prepared reads.  Motif k's records of
-// read r go to d_out[(k * out_reads + r) * K ..], its count to d_count[k * out_reads + r].
+// read r go to d_out[(k * out_reads + r) * K ..], its count to d_count[k * out_reads + r].  d_bg (optional): the
+// statistics of that read's whole row (k_row_background, sk_bg.hip) go to d_bg[k * out_reads + r].
 static int hits_core(sk_ctx *c, const sk_sdtw_args &base, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                     int32_t K, double max_dist, sk_hit *d_out, int32_t *d_count, int64_t out_reads)
+                     int32_t K, double max_dist, sk_hit *d_out, int32_t *d_count, int64_t out_reads,
+                     sk_bg_rec *d_bg = nullptr)
 {
     const int64_t row_stride = base.max_len > 0 ? base.max_len : 1;
     const size_t per_read = sizeof(sk_hit) + (size_t)row_stride * (sizeof(double) + sizeof(int32_t));
@@ -674,6 +676,7 @@ static int hits_core(sk_ctx *c, const sk_sdtw_args &base, const double *motifs, 
             a.out = rec; a.last_row = nullptr; a.force_single = 1; a.accumulate = 0; a.fuse = nullptr;
             if ((rc = sk_launch_sdtw_rows(c, &a, rowD, rowS))) return rc;
             const int64_t o = (int64_t)k * out_reads + r0;
+            if (d_bg && (rc = sk_launch_row_background(c, rowD, row_stride, rec, a.nreads, d_bg + o))) return rc;
             if ((rc = sk_launch_hits_select(c, rowD, rowS, row_stride, rec, a.nreads, K, max_dist, d_out + o * K,
                                             d_count + o))) return rc;
         }
@@ -686,7 +689,7 @@ static int hits_core(sk_ctx *c, const sk_sdtw_args &base, const double *motifs, 
 static int hits_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                         int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
                         int32_t scale_mode, int32_t scale_low, int32_t scale_hi, int32_t K, double max_dist,
-                        sk_hit *d_out, int32_t *d_count, int64_t out_reads)
+                        sk_hit *d_out, int32_t *d_count, int64_t out_reads, sk_bg_rec *d_bg = nullptr)
 {
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
     int rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nreads, scale_low, scale_hi,
@@ -697,36 +700,64 @@ static int hits_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const i
     sk_sdtw_args a;
     a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nreads;
     a.max_len = stride;
-    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, K, max_dist, d_out, d_count, out_reads))) return rc;
+    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, K, max_dist, d_out, d_count, out_reads, d_bg))) return rc;
     c->ev_valid = true;
     return SK_OK;
 }
 
-// device-resident form: d_out is [nmotifs][nreads][max_hits], d_count [nmotifs][nreads]
-int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                             int32_t *d_count)
+// Read background (sk_bg.hip): every hit-list entry point has a twin that also returns the statistics of each read's
+// whole last row.  The twins share the bodies below: want_bg says which one is running, and a hit-list call (want_bg
+// false) launches and reserves nothing more than it did.
+static int check_bg(bool want_bg, const void *bg)
+{
+    if (want_bg && !bg) return sk_fail(SK_ERR_INVALID, "NULL bg");
+    return SK_OK;
+}
+
+// device-resident form: d_out is [nmotifs][nreads][max_hits], d_count [nmotifs][nreads], d_bg [nmotifs][nreads]
+static int hits_dev_i16_entry(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                              int32_t *d_count, bool want_bg, sk_bg_rec *d_bg)
 {
     SK_ENTER(c);
     int rc = check_i16(d_sig, stride, d_len, nreads);
     if (rc) return rc;
     if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
     if ((rc = check_hits(max_hits, max_dist, nreads ? d_out : (void *)1, nreads ? d_count : (void *)1))) return rc;
+    if ((rc = check_bg(want_bg, d_bg))) return rc;
     if (nreads == 0) return SK_OK;
     clamp_limits(&scale_low, &scale_hi);
     redo_forget(c);
     if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
     return hits_dev_i16(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
-                        nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads);
+                        nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads,
+                        want_bg ? d_bg : nullptr);
+}
+int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                             int32_t *d_count)
+{
+    return hits_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
+                              max_hits, max_dist, d_out, d_count, false, nullptr);
+}
+int sk_motifseq_background_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                                   const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                                   int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                                   int32_t *d_count, sk_bg_rec *d_bg)
+{
+    return hits_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
+                              max_hits, max_dist, d_out, d_count, true, d_bg);
 }
 
-// host buffers: out is [nmotifs][nreads][max_hits], count [nmotifs][nreads]; sub-batches as sk_motifseq_multi_batch_i16
-int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                         int32_t *count)
+// host buffers: out is [nmotifs][nreads][max_hits], count [nmotifs][nreads], bg [nmotifs][nreads]; sub-batches as
+// sk_motifseq_multi_batch_i16
+static int hits_i16_entry(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                          int32_t *count, bool want_bg, sk_bg_rec *bg)
 {
     SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
@@ -734,11 +765,14 @@ int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len,
     if ((rc = check_len_host(len, nreads, stride))) return rc;
     if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
     if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
+    if ((rc = check_bg(want_bg, bg))) return rc;
     if (nreads == 0) return SK_OK;
     clamp_limits(&scale_low, &scale_hi);
     const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
     const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
     const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
+    const size_t bb = (size_t)nreads * (size_t)nmotifs * sizeof(sk_bg_rec);
+    if (want_bg && (rc = sk_reserve(c, &c->bgrec, bb))) return rc;
     if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
     if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
@@ -751,13 +785,31 @@ int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len,
                          return hits_dev_i16(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
                                              (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
                                              scale_hi, max_hits, max_dist, (sk_hit *)c->out.p + (size_t)r0 * max_hits,
-                                             (int32_t *)c->out2.p + r0, nreads);
+                                             (int32_t *)c->out2.p + r0, nreads,
+                                             want_bg ? (sk_bg_rec *)c->bgrec.p + r0 : nullptr);
                      });
     if (rc) return rc;
     SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
+    if (want_bg) SK_HIP(hipMemcpyAsync(bg, c->bgrec.p, bb, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
+}
+int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                         int32_t *count)
+{
+    return hits_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                          max_dist, out, count, false, nullptr);
+}
+int sk_motifseq_background_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                               int32_t *count, sk_bg_rec *bg)
+{
+    return hits_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                          max_dist, out, count, true, bg);
 }
 
 // ragged float64 reads (pA TSV / BLOW5 in pA): read r = sig[off[r] .. off[r+1]); out / count as sk_motifseq_hits_i16.
@@ -765,7 +817,7 @@ int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len,
 static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
                        const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                        int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                       int32_t *count);
+                       int32_t *count, bool want_bg = false, sk_bg_rec *bg = nullptr);
 int sk_motifseq_hits_f64(const double *sig, const int64_t *off, int32_t nreads,
                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
@@ -782,16 +834,33 @@ int sk_motifseq_hits_centi(const int32_t *centi, const int64_t *off, int32_t nre
     return hits_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
                        max_dist, out, count);
 }
+int sk_motifseq_background_f64(const double *sig, const int64_t *off, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                               int32_t *count, sk_bg_rec *bg)
+{
+    return hits_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                       max_dist, out, count, true, bg);
+}
+int sk_motifseq_background_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                                 const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                                 int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                                 int32_t *count, sk_bg_rec *bg)
+{
+    return hits_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                       max_dist, out, count, true, bg);
+}
 static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
                        const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                        int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                       int32_t *count)
+                       int32_t *count, bool want_bg, sk_bg_rec *bg)
 {
     SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
     int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
     if (rc) return rc;
     if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
+    if ((rc = check_bg(want_bg, bg))) return rc;
     if (nreads == 0) return SK_OK;
     int64_t total, maxlen;
     if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
@@ -799,6 +868,8 @@ static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t 
     const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
     if ((rc = sk_reserve(c, &c->out, ob))) return rc;
     if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
+    const size_t bb = (size_t)nreads * (size_t)nmotifs * sizeof(sk_bg_rec);
+    if (want_bg && (rc = sk_reserve(c, &c->bgrec, bb))) return rc;
     if ((rc = redo_begin(c, nreads, 1))) return rc;
     const double *d_sig = (const double *)c->sig.p;
     const int64_t *d_off = (const int64_t *)c->off.p;
@@ -807,10 +878,11 @@ static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t 
     a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
     a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
     if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, max_hits, max_dist, (sk_hit *)c->out.p, (int32_t *)c->out2.p,
-                        nreads))) return rc;
+                        nreads, want_bg ? (sk_bg_rec *)c->bgrec.p : nullptr))) return rc;
     c->ev_valid = true;
     SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
+    if (want_bg) SK_HIP(hipMemcpyAsync(bg, c->bgrec.p, bb, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
 }

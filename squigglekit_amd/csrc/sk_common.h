@@ -86,6 +86,7 @@ struct sk_ctx {
     sk_buf sweep;     // parameter sweep: the sets in walk form, then the summaries (sk_sweep.hip)
     sk_buf sweeprec;  // parameter sweep: the per-(set, read) records of the host entry points
     sk_buf hitrows;   // hit lists: the last rows of a chunk of reads (cost f64, start i32) and their records
+    sk_buf bgrec;     // read background: the sk_bg_rec [nmotifs][nreads] of the host entry points
     sk_buf pathcnt;   // alignment paths: [0] = hits of the call that failed the self-check (sk_last_path_mismatches)
     bool   path_valid = false;   // ... the last MotifSeq call was a paths call (the counter is that call's)
     sk_buf pathlist;  // alignment paths: [0] = count, [2 ..] = hits of a launch left to the scratch tier
@@ -256,6 +257,10 @@ int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t 
 // hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]
 int sk_launch_hits_select(sk_ctx *c, const double *rowD, const int32_t *rowS, int64_t row_stride, const sk_hit *rec,
                           int32_t nreads, int32_t K, double max_dist, sk_hit *out, int32_t *count);
+// read background (sk_bg.hip): mean, std, median, MAD and the count below mean - std of each read's last row, in numpy's
+// order and bit for bit; rec supplies n and the flags (flagged reads: NaN fields, below -1); out [nreads]
+int sk_launch_row_background(sk_ctx *c, const double *rowD, int64_t row_stride, const sk_hit *rec, int32_t nreads,
+                             sk_bg_rec *out);
 // alignment paths (sk_path.hip): spans [nreads][K][nmotif][2] of the hits [nreads][K] of prepared reads (samples / prep /
 // stride / off / max_len as sk_sdtw_args); d_motif: the motif on the DEVICE.  sk_path_begin: once per API call, before
 // the first launch (zeroes the call's mismatch counter).

@@ -290,7 +290,48 @@ __device__ __forceinline__ zs_env zs_setup(int16_t *lcomp, double *nodes, int lo
     return e;
 }
 
-// sum over i < m of sq(lcomp[i]) in np.add.reduce's order, m <= 8192 (one reduction chunk); sq(v) >= 0
+// One reduction chunk (8 <= m <= 4096 PROBES <= 8192 terms) in np.add.reduce's order: leaf(s, len) gives the sum of the
+// terms [s, s + len) of one leaf (len <= 128, and >= 64 unless the chunk is one leaf; s a multiple of 8) in numpy's leaf
+// order; every sum is >= 0.  Lane l probes the positions 64 l (+ 4096 for the second probe) and sums a leaf if its
+// probe is the first one inside it.  nodes: 128 PROBES doubles of LDS.
+template <int PROBES, typename Leaf>
+__device__ __forceinline__ double wave_pairwise_leaves(int m, double *nodes, int lane, Leaf leaf)
+{
+    // a chunk of up to 4 096 terms has its leaves at depth <= 6 (heap ids < 128), one of up to 8 192 at depth <= 7
+    constexpr int DEPTH = 5 + PROBES;
+#pragma unroll
+    for (int k = 0; k < 2 * PROBES; k++) nodes[lane + 64 * k] = -1.0;   // "no such node" (the sums are >= 0)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < PROBES; q++) {
+        const int p = q * 4096 + lane * 64;
+        int s = 0, len = m, id = 1;
+#pragma unroll 1
+        for (int it = 0; it < 7; it++) {
+            if (len > 128) {
+                int n2 = len / 2;
+                n2 -= n2 % 8;
+                if (p < s + n2) { len = n2; id = 2 * id; }
+                else            { s += n2; len -= n2; id = 2 * id + 1; }
+            }
+        }
+        const bool active = p < m && (p == 0 || s > p - 64);    // the first probe inside its leaf
+        if (active) nodes[id] = leaf(s, len);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int d = DEPTH; d >= 1; d--) {                          // parents at depth d - 1 from their children at depth d
+        const int pid = (1 << (d - 1)) + lane;
+        if (lane < (1 << (d - 1))) {
+            const double a = nodes[2 * pid], b = nodes[2 * pid + 1];
+            if (a >= 0.0 && b >= 0.0) nodes[pid] = a + b;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    return nodes[1];
+}
+
+// sum over i < m of sq(lcomp[i]) in np.add.reduce's order, m <= 4096 (the zscale prologue's longest read); sq(v) >= 0
 template <typename Sq>
 __device__ __forceinline__ double wave_pairwise_sq(int m, const int16_t *lcomp, double *nodes, int lane, Sq sq)
 {
@@ -299,21 +340,7 @@ __device__ __forceinline__ double wave_pairwise_sq(int m, const int16_t *lcomp, 
         for (int i = 0; i < m; i++) res += sq((int)lcomp[i]);
         return res;
     }
-    const int p = lane * 64;
-    int s = 0, len = m, id = 1;
-#pragma unroll 1
-    for (int it = 0; it < 7; it++) {
-        if (len > 128) {
-            int n2 = len / 2;
-            n2 -= n2 % 8;
-            if (p < s + n2) { len = n2; id = 2 * id; }
-            else            { s += n2; len -= n2; id = 2 * id + 1; }
-        }
-    }
-    const bool active = p < m && (lane == 0 || s > p - 64);     // the first probe inside its leaf
-    nodes[lane] = -1.0; nodes[lane + 64] = -1.0;                // "no such node" (the sums are >= 0)
-    __builtin_amdgcn_wave_barrier();
-    if (active) {
+    return wave_pairwise_leaves<1>(m, nodes, lane, [&](int s, int len) {
         const int16_t *q = lcomp + s;                            // (s is a multiple of 8: 16-byte aligned)
         double r[8];
         {
@@ -331,19 +358,33 @@ __device__ __forceinline__ double wave_pairwise_sq(int m, const int16_t *lcomp, 
         }
         double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
         for (int i = full; i < len; i++) res += sq((int)q[i]);
-        nodes[id] = res;
+        return res;
+    });
+}
+
+// the same over float64 terms, m <= 8192 (one reduction chunk): term(i) >= 0 is the i-th term of the chunk (the
+// last-row statistics of sk_bg.hip)
+template <typename Term>
+__device__ __forceinline__ double wave_pairwise_terms(int m, double *nodes, int lane, Term term)
+{
+    if (m < 8) {
+        double res = 0.0;
+        for (int i = 0; i < m; i++) res += term(i);
+        return res;
     }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll 1
-    for (int d = 6; d >= 1; d--) {                              // parents at depth d - 1 from their children at depth d
-        const int pid = (1 << (d - 1)) + lane;
-        if (lane < (1 << (d - 1))) {
-            const double a = nodes[2 * pid], b = nodes[2 * pid + 1];
-            if (a >= 0.0 && b >= 0.0) nodes[pid] = a + b;
+    return wave_pairwise_leaves<2>(m, nodes, lane, [&](int s, int len) {
+        double r[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) r[j] = term(s + j);
+        const int full = len - (len % 8);
+        for (int i = 8; i < full; i += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) r[j] += term(s + i + j);
         }
-        __builtin_amdgcn_wave_barrier();
-    }
-    return nodes[1];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (int i = full; i < len; i++) res += term(s + i);
+        return res;
+    });
 }
 
 // Read r: filter, compacted samples -> comp row (and LDS), mean / std -> prep[r] (lane 0 stores), returned in every lane.

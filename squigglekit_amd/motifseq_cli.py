@@ -6,7 +6,7 @@ the scoring of MotifSeq.py:441-445 stays in Python so the printed floats are the
 reference's digit for digit.  fast5 input (-f / -p) goes through h5py when it is importable and
 through the built-in reader (hdf5min.py) otherwise, with the reference's stderr messages.
 Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p, --paths,
---region, --panel.
+--background, --max_local_Z, --region, --panel.
 Whole chunks of plain integer reads (TSV chunks, BLOW5 / packed blocks) go to the GPU as one batch and their rows are
 formatted natively (csrc/sk_io.cpp writes floats as Python does); anything unusual takes the per-read route.
 """
@@ -87,6 +87,12 @@ def build_parser():
     p.add_argument("--paths", default=None, metavar="FILE",
                    help="[extension] write to FILE, per printed hit and motif base, the samples the alignment path gives "
                         "that base (start, end, length, mean normalised signal); stdout is unchanged")
+    p.add_argument("--background", default=None, metavar="FILE",
+                   help="[extension] write to FILE, per printed line, the read's own background for that motif -- mean, "
+                        "stdev, median and MAD of the whole last DTW row (view_region's M and S, MotifSeq.py:507-513) -- "
+                        "and the hit's local_Z and robust_Z against it; stdout is unchanged")
+    p.add_argument("--max_local_Z", type=float, default=None, metavar="Z",
+                   help="[extension] with --background: leave out the lines whose local_Z is above Z")
     p.add_argument("--region", default=None, metavar="A:B",
                    help="[extension] search only the raw samples [A:B] of every read, cut as a Python slice before the outlier "
                         "filter (either side may be empty or negative: 0:2000, --region=-3000:); coordinates then index "
@@ -113,11 +119,22 @@ def parse_region(parser, text):
 
 PANEL_HEADER = ["fast5", "readID", "best_model", "start", "end", "length", "distance_score", "Z-score", "p-value",
                 "hit_Probability", "second_model", "second_Z", "delta_Z", "search_from"]
+BACKGROUND_HEADER = ["fast5", "readID", "model", "hit", "distance_score", "row_mean", "row_stdev", "local_Z", "row_median",
+                     "row_mad", "robust_Z", "below_1sd", "n"]
 PATHS_HEADER = ["fast5", "readID", "model", "hit", "pos", "base", "model_current", "start", "end", "length", "mean_signal"]
 
 
 def check_hit_flags(parser, args):
-    """--hits / --min_hit_p / --paths: what they take, and what they do not combine with."""
+    """--hits / --min_hit_p / --paths / --background / --max_local_Z: what they take, and what they do not combine
+    with."""
+    if args.max_local_Z is not None and args.background is None:
+        parser.error("--max_local_Z needs --background")
+    if args.max_local_Z is not None and args.max_local_Z != args.max_local_Z:
+        parser.error("--max_local_Z is NaN (with --background)")
+    if args.background is not None and args.after_stall:
+        parser.error("--background does not combine with --after_stall")
+    if args.background is not None and args.panel:
+        parser.error("--background writes one line per printed hit: it does not combine with --panel")
     if args.paths is not None and args.after_stall:
         parser.error("--paths does not combine with --after_stall")
     if args.hits is not None and not 1 <= args.hits <= 64:
@@ -172,22 +189,39 @@ class _Batcher:
         self.meta, self.sigs = [], []
         self._pending, self._worker = None, None
         self.bases, self.paths_fh = {}, None          # --paths: base table per model (scrappie text), the open FILE
+        self.background_fh = None                     # --background: the open FILE
+        # --paths / --background write per printed line: every read takes the per-read route (emit)
+        self.per_line = args.paths is not None or args.background is not None
         # --region / --panel: every read goes through the per-read queue (add / flush), --batch reads per GPU call
         self.queued = args.region is not None or args.panel
 
-    def search(self, fn_hits, fn_multi, fn_paths, *args):
-        """The GPU call of one batch: (what of_read / table take, spans per motif or None).  --paths takes the paths
-        call -- hit lists plus spans; without --hits its rank-1 records stand in for the default path's (the same
-        records bit for bit)."""
+    def search(self, fn_hits, fn_multi, fn_paths, fn_background, *args):
+        """The GPU call of one batch: (what of_read / table take, spans per motif or None, background records per motif
+        or None).  --paths takes the paths call -- hit lists plus spans -- and --background the background call -- hit
+        lists plus each read's row statistics; without --hits their rank-1 records stand in for the default path's (the
+        same records bit for bit)."""
         a = self.args
         tail = (a.scale, a.scale_low, a.scale_hi)
+        hits = spans = bgs = None
+        if a.background is not None:
+            res = fn_background(*args, a.hits or 1, float("inf"), *tail)
+            hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
+            bgs = [b for _, _, b in res]
         if a.paths is not None:
             res = fn_paths(*args, a.hits or 1, float("inf"), *tail)
             hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
-            return hits, [sp for _, _, sp in res]
+            spans = [sp for _, _, sp in res]
+        if hits is not None:
+            return hits, spans, bgs
         if a.hits is not None:
-            return fn_hits(*args, a.hits, float("inf"), *tail), None
-        return fn_multi(*args, *tail), None
+            return fn_hits(*args, a.hits, float("inf"), *tail), None, None
+        return fn_multi(*args, *tail), None, None
+
+    def background_line(self, fast5, read_id, name, rank, dist, bg, local_z, robust_z):
+        """One line of the --background file for one printed hit."""
+        row = (fast5, read_id, name, rank, dist, float(bg["mean"]), float(bg["std"]), local_z, float(bg["median"]),
+               float(bg["mad"]), robust_z, int(bg["below"]), int(bg["n"]))
+        self.background_fh.write("\t".join("{}".format(v) for v in row) + "\n")
 
     def path_lines(self, fast5, read_id, name, rank, spans, norm):
         """One line per base of the model (per motif point when it has no base table) for one printed hit."""
@@ -236,9 +270,10 @@ class _Batcher:
         if sigs:
             _STATS[0].batch(len(sigs))
         if sigs or a.hits is not None:
-            hits, spans = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths, sigs, motifs)
+            hits, spans, bgs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
+                                           api.motifseq_background, sigs, motifs)
         else:
-            hits, spans = [[] for _ in self.order], None
+            hits, spans, bgs = [[] for _ in self.order], None, None
         slot = {i: k for k, i in enumerate(live)}
         for i, (fast5, read_id) in enumerate(self.meta):
             if self.sigs[i] is None:
@@ -246,7 +281,7 @@ class _Batcher:
                 continue
             r = slot[i]
             self.emit(fast5, read_id, self.of_read(hits, r), self.sigs[i], None if cuts is None else int(cuts[r]),
-                      None if spans is None else [sp[r] for sp in spans])
+                      None if spans is None else [sp[r] for sp in spans], None if bgs is None else [b[r] for b in bgs])
         self.meta, self.sigs = [], []
 
     def windows(self, sigs, region):
@@ -296,9 +331,11 @@ class _Batcher:
             if keep:
                 self.panel_table(keep, recs, frm)
             return
-        if a.hits is not None or a.paths is not None:
+        bgs = None
+        if a.hits is not None or self.per_line:
             wins, frm = self.windows(sigs, region)
-            hits, spans = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths, wins, motifs)
+            hits, spans, bgs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
+                                           api.motifseq_background, wins, motifs)
         else:
             _, frm, hits = api.motifseq_panel(sigs, motifs, mm, ms, region, None, a.scale, a.scale_low, a.scale_hi,
                                               records=True)
@@ -312,7 +349,8 @@ class _Batcher:
                 sig = wins[r]
             else:                                                           # (-x / --strict-compat normalise the slice)
                 sig = np.asarray(sigs[r])[slice(*region)] if (a.sig_extract or a.strict_compat) else None
-            self.emit(fast5, read_id, self.of_read(hits, r), sig, int(frm[r]), None if spans is None else [sp[r] for sp in spans])
+            self.emit(fast5, read_id, self.of_read(hits, r), sig, int(frm[r]), None if spans is None else [sp[r] for sp in spans],
+                      None if bgs is None else [b[r] for b in bgs])
 
     def panel_table(self, keep, recs, frm):
         """The --panel rows of the reads in `keep` [(fast5, readID, slot)] through the native formatter: the GPU's scores,
@@ -345,9 +383,11 @@ class _Batcher:
             return [(h[r], cnt[r]) for h, cnt in hits]
         return [hits[c][r] for c in range(len(self.order))]
 
-    def emit(self, fast5, read_id, hits, sig, cut, spans=None):
+    def emit(self, fast5, read_id, hits, sig, cut, spans=None, bgs=None):
         """The rows of one read, one per motif (MotifSeq.py:436-449); with --hits one per match, best first.
-        spans (--paths): per motif the read's [K, N, 2]; every printed hit also writes its lines to the paths file."""
+        spans (--paths): per motif the read's [K, N, 2]; every printed hit also writes its lines to the paths file.
+        bgs (--background): per motif the read's background record; every printed hit also writes its line to the
+        background file, and --max_local_Z leaves out of both the hits that score above it."""
         a = self.args
         norm = None
         for c, name in enumerate(self.order):
@@ -386,6 +426,10 @@ class _Batcher:
                 hit_p = (1 - p_value) * 100
                 if a.min_hit_p is not None and hit_p < a.min_hit_p:
                     continue
+                if bgs is not None:
+                    local_z, robust_z = (float(v) for v in api.local_scores(dist, bgs[c]))
+                    if a.max_local_Z is not None and local_z > a.max_local_Z:
+                        continue
                 row = [fast5, read_id, name, start, end, end - start, dist, mod_mean, mod_stdev, z, p_value, hit_p]
                 if a.sig_extract:
                     if norm is None:
@@ -394,6 +438,8 @@ class _Batcher:
                 if cut is not None:
                     row.append(cut)
                 print("\t".join("{}".format(v) for v in row))
+                if bgs is not None:
+                    self.background_line(fast5, read_id, name, rank + 1, dist, bgs[c], local_z, robust_z)
                 if spans is not None and not h["flags"] & 2:
                     if norm is None:
                         norm = api.normalise(sig, a.scale, a.scale_low, a.scale_hi)
@@ -404,7 +450,7 @@ class _Batcher:
         nothing written -- when some read needs the general route (-x, a flagged read)."""
         a = self.args
         K = len(self.order)
-        if a.sig_extract or a.paths is not None or any(bool((h["flags"] & 3).any()) for h in hits):
+        if a.sig_extract or self.per_line or any(bool((h["flags"] & 3).any()) for h in hits):
             return False
         names = [nm.encode() for nm in self.order]
         nblob = b"".join(names)
@@ -441,7 +487,7 @@ class _Batcher:
         out), through the same formatter and the same scoring arithmetic."""
         a = self.args
         K = len(self.order)
-        if a.sig_extract or a.paths is not None or any(bool((h[:, 0]["flags"] & 3).any()) for h, _ in hits):
+        if a.sig_extract or self.per_line or any(bool((h[:, 0]["flags"] & 3).any()) for h, _ in hits):
             return False
         names = [nm.encode() for nm in self.order]
         nblob = b"".join(names)
@@ -500,8 +546,8 @@ class _Batcher:
         def call():
             _mark("GPU call starts")
             try:
-                return self.search(api.motifseq_hits_batch, api.motifseq_multi_batch, api.motifseq_paths_batch, rows, nsamp,
-                                   motifs)
+                return self.search(api.motifseq_hits_batch, api.motifseq_multi_batch, api.motifseq_paths_batch,
+                                   api.motifseq_background_batch, rows, nsamp, motifs)
             finally:
                 _mark("GPU call ends")
         job = self._worker.submit(call)
@@ -522,7 +568,8 @@ class _Batcher:
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d float64 reads to the GPU worker" % fb.n)
         job = self._worker.submit(self.search, api.motifseq_hits_ragged_f64, api.motifseq_multi_ragged_f64,
-                                  api.motifseq_paths_ragged_f64, fb.batch_values(), fb.off, motifs)
+                                  api.motifseq_paths_ragged_f64, api.motifseq_background_ragged_f64, fb.batch_values(),
+                                  fb.off, motifs)
         prev, self._pending = self._pending, (job, fb.n, ("span", fb.buf, fb.spans("name")), ("span", fb.buf, fb.spans("id")),
                                               lambda i, b=fb: b.text("name", i), lambda i, b=fb: b.text("id", i),
                                               lambda i, b=fb: b.values[b.off[i]:b.off[i + 1]])
@@ -536,7 +583,7 @@ class _Batcher:
 
     def _finish(self, p):
         job, n, fast5_col, id_col, name_of, id_of, sig_of = p
-        hits, spans = job.result()
+        hits, spans, bgs = job.result()
         _STATS[0].batch(n)
         _mark("block of %d reads back from the GPU" % n)
         if (self.table_hits if self.args.hits is not None else self.table)(n, fast5_col, id_col, hits):
@@ -550,14 +597,14 @@ class _Batcher:
         need_sig = self.args.sig_extract or self.args.strict_compat or spans is not None
         for i in range(n):
             self.emit(name_of(i), id_of(i), self.of_read(hits, i), sig_of(i) if need_sig else None, None,
-                      None if spans is None else [sp[i] for sp in spans])
+                      None if spans is None else [sp[i] for sp in spans], None if bgs is None else [b[i] for b in bgs])
 
     def block(self, blk):
         """A parsed TSV chunk (tsvio.TsvBlock): its integer lines go to the GPU as ONE int16 batch straight from the
         tokenizer's rows (every motif against them); any other line takes the per-read route, in its place."""
         a = self.args
         fast = (blk.flags & 27) == 3                                        # ALLINT | ANY, not SLOW / SHORT
-        if a.after_stall or a.paths is not None or self.queued:
+        if a.after_stall or self.per_line or self.queued:
             fast[:] = False                                                 # (needs the raw reads on the host)
         idx = np.flatnonzero(fast)
         if idx.size == blk.n and blk.n and not a.sig_extract:
@@ -630,7 +677,7 @@ class _Batcher:
                                      str(mm), str(ms), repr(z[k]), repr(pv[k]), repr(hp[k]))))
                 continue
             fl = int(blk.flags[i])
-            if a.after_stall or a.paths is not None or self.queued:
+            if a.after_stall or self.per_line or self.queued:
                 # nothing of this chunk was printed directly, so the batcher alone keeps the file order: reads queue
                 # up to --batch per GPU call (segment + search) instead of one call per read
                 if (fl & 27) == 1:
@@ -703,6 +750,9 @@ def main(argv=None):
         out.bases = tsvio.model_bases_auto(args.model) if args.model else {}
         out.paths_fh = open(args.paths, "w")
         out.paths_fh.write("\t".join(PATHS_HEADER) + "\n")
+    if args.background is not None:
+        out.background_fh = open(args.background, "w")
+        out.background_fh.write("\t".join(BACKGROUND_HEADER) + "\n")
     if args.signal:
         # native tokenizer (csrc/sk_tsv.cpp): integer lines arrive as int16 rows, one GPU batch per chunk of the
         # file; decimal (pA) chunks go through the float64 tokenizer, odd lines through the reference's own parse
@@ -716,7 +766,7 @@ def main(argv=None):
                 fb = blk.float_block(8)
                 if fb is None:
                     continue
-            if fb.clean() and not (args.sig_extract or args.after_stall or args.paths is not None or out.queued):
+            if fb.clean() and not (args.sig_extract or args.after_stall or out.per_line or out.queued):
                 out.rows_f64(fb)                         # the whole chunk as one batch, no Python per read
                 continue
             out.flush()
@@ -787,6 +837,8 @@ def main(argv=None):
     out.flush()
     if out.paths_fh is not None:
         out.paths_fh.close()
+    if out.background_fh is not None:
+        out.background_fh.close()
     _mark("end of main()")
     _STATS[0].finish(args, [args.signal, getattr(args, "blow5", None), getattr(args, "i16", None)] + list(getattr(args, "ind", None) or []))
 

@@ -282,6 +282,35 @@ def main():
                 print("%s mismatch round %d %s: %s" % (fam.upper(), rounds, randcases.describe(case), msg))
             for key in randcases.SWITCHES:
                 os.environ.pop(key, None)
+        # ---- the read background: a hit-list draw through the background twin, every record against numpy on the
+        # oracle's last row (tests/test_background_host.py), the hit lists against the hit-list call's
+        case = randcases.DRAW["hits"](rng)
+        for key in randcases.SWITCHES:
+            if key in case["env"]:
+                os.environ[key] = case["env"][key]
+        from test_background_host import reference_background_reads
+        bkw = (case["motifs"], case["K"], float("inf"), case["scale"], case["lo"], case["hi"])
+        got, twin = api.motifseq_background(case["reads"], *bkw), api.motifseq_hits(case["reads"], *bkw)
+        for m, motif in enumerate(case["motifs"]):
+            want = reference_background_reads(ora, case["reads"], motif, case["scale"], case["lo"], case["hi"])
+            msg = None
+            if got[m][0].tobytes() != twin[m][0].tobytes() or not np.array_equal(got[m][1], twin[m][1]):
+                msg = "hit lists differ from the hit-list call's"
+            for r, w in enumerate(want):
+                g = got[m][2][r]
+                if w is None:
+                    ok = g["below"] == -1 and all(np.isnan(g[f]) for f in ("mean", "std", "median", "mad"))
+                else:
+                    ok = (int(g["below"]), int(g["n"])) == w[4:] and all(
+                        np.float64(g[f]).tobytes() == np.float64(v).tobytes()
+                        for f, v in zip(("mean", "std", "median", "mad"), w))
+                if not ok and msg is None:
+                    msg = "motif %d read %d (%d samples): got %s want %s" % (m, r, len(case["reads"][r]), g, w)
+            if msg is not None:
+                bad += 1
+                print("BACKGROUND mismatch round %d %s: %s" % (rounds, randcases.describe(case), msg))
+        for key in randcases.SWITCHES:
+            os.environ.pop(key, None)
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
