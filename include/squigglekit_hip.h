@@ -350,6 +350,75 @@ int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_
  * reports 0. */
 int sk_last_path_mismatches(void);
 
+/* Events: the hit list, and per hit and motif point what the signal did in the samples the path gives that point --
+ * the row an eventalign / resquiggle table has per base.  With y the read's filtered, normalised samples (the values
+ * the DTW compares, as sk_normalise_* returns them), x the motif and w = y[a_i .. b_i] the span of point i:
+ *   sum    = np.sum(w)                 (np.add.reduce's order, as sk_bg_rec documents it: serial below 8 samples,
+ *                                       eight accumulators up to 128, the pairwise split above, buffers of 8 192)
+ *   std    = np.std(w)                 (ddof 0, two passes, the same order; one sample: 0.0)
+ *   cost   = np.sum(np.abs(x[i] - w))  (this point's share of the hit's distance; the same order)
+ *   start  = a_i, dwell = b_i - a_i + 1       (filtered coordinates)
+ * bit for bit what numpy gives.  The mean is not stored: sum / dwell has the bits of np.mean(w).  A column two
+ * consecutive points share (a_{i+1} == b_i) counts for both.  A hit without a path -- an unused slot, a read flagged
+ * SK_FLAG_EMPTY or SK_FLAG_DEGENERATE, a failed self-check -- has sum = std = cost = NaN, start = -1, dwell = 0 in
+ * all its records. */
+typedef struct sk_event {           /* 32 bytes */
+    double  sum;
+    double  std;
+    double  cost;
+    int32_t start;
+    int32_t dwell;
+} sk_event;
+/* events follows the layout of spans: motif k's block begins at max_hits * nreads * motif_off[k] records, inside it
+ * [read][hit][N_k].  out / count: exactly what the sk_motifseq_hits_* twin returns; the other arguments are those of
+ * the sk_motifseq_paths_* twin, and sk_last_path_mismatches() counts for an events call as for a paths call.  A NULL
+ * events is SK_ERR_INVALID. */
+int sk_motifseq_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count, sk_event *events);
+int sk_motifseq_events_f64(const double *sig, const int64_t *off, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count, sk_event *events);
+int sk_motifseq_events_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                             int32_t *count, sk_event *events);
+/* device-resident form (d_sig, d_len, d_out, d_count, d_events device; motifs / motif_off host) */
+int sk_motifseq_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                               int32_t *d_count, sk_event *d_events);
+
+/* Pooled model: the events of nhits hits against one motif of N points (ev is [nhits][N], in any order the caller
+ * likes -- the hits of many reads, of many calls) reduced to one record per motif point.  A hit is selected when
+ * use[h] != 0 (use NULL: every hit) and it has a path (dwell > 0 in its first record; the records of a hit have a
+ * path or none).  With the selected records of point i taken as contiguous float64 arrays in hit order -- sum_col,
+ * std_col, cost_col, dwell_col -- and total_dwell the exact int64 sum of dwell_col, one record holds, bit for bit
+ * what numpy gives:
+ *   level      = np.sum(sum_col) / total_dwell   (sample weighted: one update of DTW barycentre averaging)
+ *   level_sd   = np.std(sum_col / dwell_col)     (spread of the event means over the hits)
+ *   sd_mean    = np.mean(std_col)                (noise inside an event)
+ *   dwell_mean = total_dwell / hits
+ *   dwell_sd   = np.std(dwell_col.astype(np.float64))
+ *   cost_mean  = np.mean(cost_col)
+ *   hits       = selected hits; 0: the six doubles are NaN
+ * nhits above 2 147 418 112 or N < 1: SK_ERR_INVALID. */
+typedef struct sk_pool_rec {        /* 56 bytes */
+    double  level;
+    double  level_sd;
+    double  sd_mean;
+    double  dwell_mean;
+    double  dwell_sd;
+    double  cost_mean;
+    int32_t hits;
+    int32_t pad;                    /* 0 */
+} sk_pool_rec;
+int sk_events_pool(const sk_event *ev, const uint8_t *use, int64_t nhits, int32_t N, sk_pool_rec *out);
+/* device-resident form (d_ev, d_use, d_out device) */
+int sk_events_pool_dev(const sk_event *d_ev, const uint8_t *d_use, int64_t nhits, int32_t N, sk_pool_rec *d_out);
+
 /* Read background: the hit list, and per read and motif the statistics of the whole last DTW row the hits were
  * taken from.  view_region draws a hit against its read's own row of distance scores (MotifSeq.py:507-513:
  * M = np.mean(cost[-1,]), S = np.std(cost[-1,]), lines at M and M - S); with d = cost[-1, :] of motif k against

@@ -136,6 +136,24 @@ BG_DTYPE = np.dtype({"names": ["mean", "std", "median", "mad", "below", "n"],
                      "formats": ["<f8", "<f8", "<f8", "<f8", "<i4", "<i4"],
                      "offsets": [0, 8, 16, 24, 32, 36], "itemsize": 48})
 
+class Event(C.Structure):
+    """sk_event: what the signal did in the samples of one motif point of one hit."""
+    _fields_ = [("sum", C.c_double), ("std", C.c_double), ("cost", C.c_double), ("start", C.c_int32), ("dwell", C.c_int32)]
+
+
+EVENT_DTYPE = np.dtype([("sum", "<f8"), ("std", "<f8"), ("cost", "<f8"), ("start", "<i4"), ("dwell", "<i4")])
+
+
+class PoolRec(C.Structure):
+    """sk_pool_rec: one motif point of the model the pooled hits show."""
+    _fields_ = [("level", C.c_double), ("level_sd", C.c_double), ("sd_mean", C.c_double), ("dwell_mean", C.c_double),
+                ("dwell_sd", C.c_double), ("cost_mean", C.c_double), ("hits", C.c_int32), ("pad", C.c_int32)]
+
+
+# the seven fields of the 56-byte record (its pad word is not exposed)
+POOL_DTYPE = np.dtype({"names": ["level", "level_sd", "sd_mean", "dwell_mean", "dwell_sd", "cost_mean", "hits"],
+                       "formats": ["<f8"] * 6 + ["<i4"], "offsets": [0, 8, 16, 24, 32, 40, 48], "itemsize": 56})
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -207,6 +225,16 @@ ABI = {
                                           C.c_int32, C.c_double, _vp, _vp, _vp]),
     "sk_motifseq_paths_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_events_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_events_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_events_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_events_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_events_pool": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
+    "sk_events_pool_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
     "sk_last_path_mismatches": (C.c_int, []),
     "sk_motifseq_panel_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32,
                                         _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, HIT_DTYPE, PANEL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, EVENT_DTYPE, HIT_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -1103,6 +1103,168 @@ def last_path_mismatches():
     """Hits of the last paths call of this module whose path failed the kernel's self-check (they carry spans -1);
     a healthy build reports 0.  -1: no paths call yet."""
     return _path_mismatches[0]
+
+
+# ----------------------------------------------------------------------------
+# MotifSeq events: per hit and motif point what the signal did; pooled models
+# ----------------------------------------------------------------------------
+def _events_over(devices, R, ms, moff, K, entry_call):
+    """Runs entry_call(lo, hi, hits_part, count_part, events_part) over the devices; returns per motif
+    (hits[R, K], count[R], events[R, K, N]).  The self-check counters of the shards add up (last_path_mismatches)."""
+    L = _lib.load()
+    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
+    count = np.zeros((len(ms), R), dtype=np.int32)
+    events = [no_events((R, K, m.size)) for m in ms]
+    total = int(moff[-1])
+    with _path_lock:
+        _path_mismatches[0] = 0
+
+    def call(lo, hi):
+        n = hi - lo
+        part = np.zeros((len(ms), n, K), dtype=HIT_DTYPE)
+        cnt = np.zeros((len(ms), n), dtype=np.int32)
+        ev = np.zeros(K * n * total, dtype=EVENT_DTYPE)
+        rc = entry_call(lo, hi, part, cnt, ev)
+        if rc == 0:
+            hits[:, lo:hi] = part
+            count[:, lo:hi] = cnt
+            for k, m in enumerate(ms):                      # motif k's block: [read][hit][N_k] at K n moff[k]
+                b = K * n * int(moff[k])
+                events[k][lo:hi] = ev[b:b + K * n * m.size].reshape(n, K, m.size)
+            bad = L.sk_last_path_mismatches()
+            with _path_lock:
+                _path_mismatches[0] += max(bad, 0)
+        return rc
+    if R and ms:
+        _over_devices(devices, R, call)
+    return [(hits[k], count[k], events[k]) for k in range(len(ms))]
+
+
+def no_events(shape):
+    """An EVENT_DTYPE array of hits without a path: sum = std = cost = NaN, start -1, dwell 0."""
+    ev = np.zeros(shape, dtype=EVENT_DTYPE)
+    ev["sum"] = ev["std"] = ev["cost"] = np.nan
+    ev["start"] = -1
+    return ev
+
+
+def motifseq_events_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
+                          scale_hi=1200, devices=None):
+    """motifseq_hits_batch plus, per hit and motif point, what the signal did in the samples the path gives that point:
+    a list, per motif, of (hits[R, max_hits], count[R], events[R, max_hits, N]).  With y the read's filtered, normalised
+    samples and w = y[a_i : b_i + 1] (the span motifseq_paths_batch returns), events[r, h, i] (EVENT_DTYPE) holds
+    sum = np.sum(w), std = np.std(w), cost = np.sum(np.abs(motif[i] - w)), start = a_i and dwell = b_i - a_i + 1, bit
+    for bit as numpy would; sum / dwell is np.mean(w).  No path: NaN, start -1, dwell 0."""
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    R = sig.shape[0]
+    if _too_wide_for_i16(scale_low, scale_hi):
+        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
+        return motifseq_events_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
+    L = _lib.load()
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, part, cnt, ev):
+        return L.sk_motifseq_events_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff),
+                                        len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part),
+                                        ptr(cnt), ptr(ev))
+    return _events_over(devices, R, ms, moff, K, call)
+
+
+def motifseq_events_ragged_f64(values, off, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
+                               scale_hi=1200, devices=None):
+    """motifseq_hits_ragged_f64 plus the events (see motifseq_events_batch); int32 values are centi-units."""
+    L = _lib.load()
+    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
+    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
+    entry = L.sk_motifseq_events_centi if centi else L.sk_motifseq_events_f64
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = off.size - 1
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, part, cnt, ev):
+        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
+                     int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt), ptr(ev))
+    return _events_over(devices, R, ms, moff, K, call)
+
+
+def motifseq_events(reads, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
+                    devices=None):
+    """motifseq_hits plus the events of every hit: a list, per motif, of
+    (hits[nreads, max_hits], count[nreads], events[nreads, max_hits, N]) -- see motifseq_events_batch.  The same read
+    kinds as motifseq_paths; spans_of_events gives the spans a paths call would have returned."""
+    ms = _hits_args(motifs, max_hits, max_dist)[0]
+    ints, arrs, flts = _split_int16(reads)
+    R, K = len(reads), int(max_hits)
+    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32), no_events((R, K, m.size))) for m in ms]
+    bad = 0
+    if ints and ms:
+        buf, lens = pack_i16(arrs)
+        for (h, c, e), (hi, ci, ei) in zip(res, motifseq_events_batch(buf, lens, ms, K, max_dist, scale, scale_low,
+                                                                      scale_hi, devices)):
+            h[ints], c[ints], e[ints] = hi, ci, ei
+        bad += _path_mismatches[0]
+    if flts and ms:
+        flat, off = pack_f64([reads[i] for i in flts])
+        for (h, c, e), (hf, cf, ef) in zip(res, motifseq_events_ragged_f64(flat, off, ms, K, max_dist, scale, scale_low,
+                                                                           scale_hi, devices)):
+            h[flts], c[flts], e[flts] = hf, cf, ef
+        bad += _path_mismatches[0]
+    with _path_lock:
+        _path_mismatches[0] = bad
+    return res
+
+
+def spans_of_events(events):
+    """The spans [..., N, 2] int32 a paths call returns for the hits of `events` [..., N]: (start, start + dwell - 1),
+    -1 where there is no path."""
+    events = np.asarray(events)
+    spans = np.empty(events.shape + (2,), dtype=np.int32)
+    spans[..., 0] = events["start"]
+    spans[..., 1] = events["start"] + events["dwell"] - 1
+    spans[events["dwell"] <= 0] = -1
+    return spans
+
+
+def pool_events(events, use=None):
+    """The model the hits of `events` show: POOL_DTYPE[N], one record per motif point, from events [..., N] (every
+    leading axis is flattened into the hit order) and an optional boolean mask over the hits.  A hit without a path
+    (dwell 0) is never used.  Over the selected records of point i: level = np.sum(sum) / total dwell (sample weighted:
+    one update of DTW barycentre averaging), level_sd = np.std(sum / dwell), sd_mean = np.mean(std), dwell_mean, dwell_sd
+    = np.std(dwell), cost_mean = np.mean(cost), hits -- bit for bit as numpy would; no hit: NaN.  Always one device (the
+    calling thread's), so the reduction order does not depend on how the events call was sharded."""
+    events = np.asarray(events)
+    if events.dtype != EVENT_DTYPE or events.ndim < 1 or events.shape[-1] < 1:
+        raise ValueError("events must be an EVENT_DTYPE array [..., N] with N >= 1")
+    N = events.shape[-1]
+    ev = np.ascontiguousarray(events).reshape(-1, N)
+    H = ev.shape[0]
+    mask = None
+    if use is not None:
+        mask = np.ascontiguousarray(np.asarray(use).reshape(-1) != 0).view(np.uint8)
+        if mask.size != H:
+            raise ValueError("use has %d entries for %d hits" % (mask.size, H))
+    L = _lib.ensure_init()
+    out = np.zeros(N, dtype=POOL_DTYPE)
+    check(L.sk_events_pool(ptr(ev), None if mask is None else ptr(mask), H, N, ptr(out)))
+    return out
+
+
+def refine_motif(reads, motif, rounds=1, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
+                 devices=None):
+    """Corrects a motif from the data: `rounds` times -- motifseq_events of the current motif, pool_events of the hits
+    with dist <= max_dist, then x_i = level_i (a point no hit covers keeps its value).  One round is one step of DTW
+    barycentre averaging.  Returns the list of (motif_t, pool_t) per round: the motif after round t and the pool it was
+    made from."""
+    x = np.ascontiguousarray(motif, dtype=np.float64).copy()
+    max_dist = float(max_dist)
+    out = []
+    for _ in range(int(rounds)):
+        hits, _, events = motifseq_events(reads, [x], max_hits, float("inf"), scale, scale_low, scale_hi, devices)[0]
+        pool = pool_events(events, hits["dist"] <= max_dist)
+        x = np.where(pool["hits"] > 0, pool["level"], x)
+        out.append((x.copy(), pool))
+    return out
 
 
 def normalise(sig, scale="medmad", scale_low=0, scale_hi=1200):

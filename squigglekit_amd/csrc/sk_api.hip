@@ -891,9 +891,10 @@ static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t 
 // The hit list, then per hit the spans of its warping path: which columns [a_i, b_i] each motif point i covers
 // (mlpy's subsequence_path, MotifSeq.py:437, as a fixed-size record).  Layout of `spans`: motif k's block begins at
 // 2 * max_hits * nreads * motif_off[k] int32, inside it [read][hit][N_k][2].  hits / count are the hit-list call's.
-static int paths_begin(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs, const void *spans)
+static int paths_begin(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs, const void *spans,
+                       const char *what = "spans")
 {
-    if (!spans) return sk_fail(SK_ERR_INVALID, "NULL spans");
+    if (!spans) return sk_fail(SK_ERR_INVALID, "NULL %s", what);
     int rc = sk_path_begin(c);
     if (rc) return rc;
     const size_t mb = (size_t)motif_off[nmotifs] * sizeof(double);
@@ -903,9 +904,10 @@ static int paths_begin(sk_ctx *c, const double *motifs, const int32_t *motif_off
 }
 
 // base: as hits_core's; d_out: the records hits_core left ([k * out_reads + r][K], r relative to this (sub-)batch);
-// read0: the (sub-)batch's first read within the out_reads reads of d_spans
+// read0: the (sub-)batch's first read within the out_reads reads of d_spans.  d_events (optional, sk_events.hip): the
+// events of those spans, in the same layout with one record where the spans have two ints.
 static int paths_core(sk_ctx *c, const sk_sdtw_args &base, const int32_t *motif_off, int32_t nmotifs, int32_t K,
-                      const sk_hit *d_out, int64_t out_reads, int32_t *d_spans, int64_t read0)
+                      const sk_hit *d_out, int64_t out_reads, int32_t *d_spans, int64_t read0, sk_event *d_events = nullptr)
 {
     for (int32_t k = 0; k < nmotifs; k++) {
         const int64_t m0 = motif_off[k] - motif_off[0], N = motif_off[k + 1] - motif_off[k];
@@ -915,10 +917,16 @@ static int paths_core(sk_ctx *c, const sk_sdtw_args &base, const int32_t *motif_
         p.d_motif = (const double *)c->pathmotif.p + m0; p.nmotif = (int32_t)N;
         p.hits = d_out + (int64_t)k * out_reads * K; p.K = K;
         p.spans = d_spans + 2 * (int64_t)K * out_reads * m0 + read0 * K * N * 2;
-        const int rc = sk_launch_paths(c, &p);
+        int rc = sk_launch_paths(c, &p);
         if (rc) return rc;
+        if (d_events && (rc = sk_launch_events(c, &p, d_events + (int64_t)K * out_reads * m0 + read0 * K * N))) return rc;
     }
     return SK_OK;
+}
+
+static size_t events_bytes(int32_t nreads, int32_t max_hits, const int32_t *motif_off, int32_t nmotifs)
+{
+    return (size_t)max_hits * (size_t)nreads * (size_t)(motif_off[nmotifs] - motif_off[0]) * sizeof(sk_event);
 }
 
 static size_t spans_bytes(int32_t nreads, int32_t max_hits, const int32_t *motif_off, int32_t nmotifs)
@@ -929,7 +937,8 @@ static size_t spans_bytes(int32_t nreads, int32_t max_hits, const int32_t *motif
 static int paths_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                          int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
                          int32_t scale_mode, int32_t scale_low, int32_t scale_hi, int32_t K, double max_dist,
-                         sk_hit *d_out, int32_t *d_count, int64_t out_reads, int32_t *d_spans, int64_t read0)
+                         sk_hit *d_out, int32_t *d_count, int64_t out_reads, int32_t *d_spans, int64_t read0,
+                         sk_event *d_events = nullptr)
 {
     int rc = hits_dev_i16(c, d_sig, stride, d_len, nreads, d_comp, d_prep, motifs, motif_off, nmotifs, scale_mode, scale_low,
                           scale_hi, K, max_dist, d_out, d_count, out_reads);
@@ -937,35 +946,61 @@ static int paths_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const 
     sk_sdtw_args a;
     a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nreads;
     a.max_len = stride;
-    return paths_core(c, a, motif_off, nmotifs, K, d_out, out_reads, d_spans, read0);
+    return paths_core(c, a, motif_off, nmotifs, K, d_out, out_reads, d_spans, read0, d_events);
 }
 
-// device-resident form: d_out / d_count as sk_motifseq_hits_dev_i16, d_spans in the layout above
-int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                              int32_t *d_count, int32_t *d_spans)
+// Events (sk_events.hip): every paths entry point has a twin that returns one sk_event per motif point where the paths
+// call returns a span.  The twins share the bodies below: want_events says which one is running; an events call keeps
+// its spans in c->pathspans and a paths call launches and reserves nothing more than it did.
+//
+// device-resident form: d_out / d_count as sk_motifseq_hits_dev_i16, d_spans / d_events in the layout above
+static int paths_dev_i16_entry(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                               int32_t *d_count, int32_t *d_spans, bool want_events, sk_event *d_events)
 {
     SK_ENTER(c);
     int rc = check_i16(d_sig, stride, d_len, nreads);
     if (rc) return rc;
     if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
     if ((rc = check_hits(max_hits, max_dist, nreads ? d_out : (void *)1, nreads ? d_count : (void *)1))) return rc;
-    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? d_spans : (void *)1))) return rc;
+    const void *res = want_events ? (const void *)d_events : (const void *)d_spans;
+    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? res : (void *)1, want_events ? "events" : "spans"))) return rc;
     if (nreads == 0) return SK_OK;
     clamp_limits(&scale_low, &scale_hi);
     redo_forget(c);
     if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    if (want_events) {
+        if ((rc = sk_reserve(c, &c->pathspans, spans_bytes(nreads, max_hits, motif_off, nmotifs)))) return rc;
+        d_spans = (int32_t *)c->pathspans.p;
+    }
     return paths_dev_i16(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
-                         nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads, d_spans, 0);
+                         nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads, d_spans, 0,
+                         want_events ? d_events : nullptr);
+}
+int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                              int32_t *d_count, int32_t *d_spans)
+{
+    return paths_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
+                               max_hits, max_dist, d_out, d_count, d_spans, false, nullptr);
+}
+int sk_motifseq_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
+                               int32_t *d_count, sk_event *d_events)
+{
+    return paths_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
+                               max_hits, max_dist, d_out, d_count, nullptr, true, d_events);
 }
 
 // host buffers; sub-batches as sk_motifseq_hits_i16
-int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                          int32_t *count, int32_t *spans)
+static int paths_i16_entry(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count, int32_t *spans, bool want_events, sk_event *events)
 {
     SK_ENTER(c);
     int rc = check_i16(sig, stride, len, nreads);
@@ -973,9 +1008,12 @@ int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len
     if ((rc = check_len_host(len, nreads, stride))) return rc;
     if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
     if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
-    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? spans : (void *)1))) return rc;
+    const void *res = want_events ? (const void *)events : (const void *)spans;
+    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? res : (void *)1, want_events ? "events" : "spans"))) return rc;
     if (nreads == 0) return SK_OK;
     clamp_limits(&scale_low, &scale_hi);
+    const size_t eb = events_bytes(nreads, max_hits, motif_off, nmotifs);
+    if (want_events && (rc = sk_reserve(c, &c->events, eb))) return rc;
     const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
     const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
     const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
@@ -993,21 +1031,39 @@ int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len
                          return paths_dev_i16(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
                                               (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
                                               scale_hi, max_hits, max_dist, (sk_hit *)c->out.p + (size_t)r0 * max_hits,
-                                              (int32_t *)c->out2.p + r0, nreads, (int32_t *)c->pathspans.p, r0);
+                                              (int32_t *)c->out2.p + r0, nreads, (int32_t *)c->pathspans.p, r0,
+                                              want_events ? (sk_event *)c->events.p : nullptr);
                      });
     if (rc) return rc;
     SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
+    if (want_events) SK_HIP(hipMemcpyAsync(events, c->events.p, eb, hipMemcpyDeviceToHost, c->stream));
+    else SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
+}
+int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                          int32_t *count, int32_t *spans)
+{
+    return paths_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                           max_dist, out, count, spans, false, nullptr);
+}
+int sk_motifseq_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count, sk_event *events)
+{
+    return paths_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                           max_dist, out, count, nullptr, true, events);
 }
 
 // ragged float64 / centi reads, as sk_motifseq_hits_f64 / _centi
 static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                        int32_t *count, int32_t *spans);
+                        int32_t *count, int32_t *spans, bool want_events = false, sk_event *events = nullptr);
 int sk_motifseq_paths_f64(const double *sig, const int64_t *off, int32_t nreads,
                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
@@ -1024,18 +1080,37 @@ int sk_motifseq_paths_centi(const int32_t *centi, const int64_t *off, int32_t nr
     return paths_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
                         max_dist, out, count, spans);
 }
+int sk_motifseq_events_f64(const double *sig, const int64_t *off, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count, sk_event *events)
+{
+    return paths_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                        max_dist, out, count, nullptr, true, events);
+}
+int sk_motifseq_events_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                             int32_t *count, sk_event *events)
+{
+    return paths_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
+                        max_dist, out, count, nullptr, true, events);
+}
 static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
                         const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                         int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                        int32_t *count, int32_t *spans)
+                        int32_t *count, int32_t *spans, bool want_events, sk_event *events)
 {
     SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
     int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
     if (rc) return rc;
     if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
-    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? spans : (void *)1))) return rc;
+    const void *res = want_events ? (const void *)events : (const void *)spans;
+    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? res : (void *)1, want_events ? "events" : "spans"))) return rc;
     if (nreads == 0) return SK_OK;
+    const size_t eb = events_bytes(nreads, max_hits, motif_off, nmotifs);
+    if (want_events && (rc = sk_reserve(c, &c->events, eb))) return rc;
     int64_t total, maxlen;
     if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
     const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
@@ -1054,13 +1129,63 @@ static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t
     if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, max_hits, max_dist, (sk_hit *)c->out.p, (int32_t *)c->out2.p,
                         nreads))) return rc;
     if ((rc = paths_core(c, a, motif_off, nmotifs, max_hits, (const sk_hit *)c->out.p, nreads, (int32_t *)c->pathspans.p,
-                         0))) return rc;
+                         0, want_events ? (sk_event *)c->events.p : nullptr))) return rc;
     c->ev_valid = true;
     SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
+    if (want_events) SK_HIP(hipMemcpyAsync(events, c->events.p, eb, hipMemcpyDeviceToHost, c->stream));
+    else SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     return SK_OK;
+}
+
+// ------------------------------------------------------------------ pooled events (sk_events.hip)
+// c->pool: the result [N] (host form), then the count, the mask (host form), the list of selected hits
+static int pool_core(sk_ctx *c, const sk_event *d_ev, const uint8_t *use, bool use_on_host, int64_t nhits, int32_t N,
+                     sk_pool_rec *d_out, sk_pool_rec *host_out)
+{
+    const size_t rb = ((size_t)N * sizeof(sk_pool_rec) + 15) & ~(size_t)15;
+    const size_t ub = ((size_t)(use && use_on_host ? nhits : 0) + 15) & ~(size_t)15;
+    int rc = sk_reserve(c, &c->pool, rb + 16 + ub + (size_t)(nhits > 0 ? nhits : 1) * sizeof(int32_t));
+    if (rc) return rc;
+    char *base = (char *)c->pool.p;
+    int32_t *d_cnt = (int32_t *)(base + rb);
+    uint8_t *d_use = (uint8_t *)(base + rb + 16);
+    int32_t *d_idx = (int32_t *)(base + rb + 16 + ub);
+    if (use && use_on_host) SK_HIP(hipMemcpyAsync(d_use, use, (size_t)nhits, hipMemcpyHostToDevice, c->stream));
+    const uint8_t *mask = !use ? nullptr : (use_on_host ? d_use : use);
+    if (!d_out) d_out = (sk_pool_rec *)base;
+    if ((rc = sk_launch_events_pool(c, d_ev, mask, nhits, N, d_idx, d_cnt, d_out))) return rc;
+    if (host_out) SK_HIP(hipMemcpyAsync(host_out, d_out, (size_t)N * sizeof(sk_pool_rec), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+static int check_pool(const void *ev, int64_t nhits, int32_t N, const void *out)
+{
+    if (nhits < 0 || nhits > 0x7fff0000) return sk_fail(SK_ERR_INVALID, "nhits %lld outside 0..2147418112", (long long)nhits);
+    if (N < 1) return sk_fail(SK_ERR_INVALID, "N < 1");
+    if (!out || (nhits && !ev)) return sk_fail(SK_ERR_INVALID, "NULL ev/out");
+    return SK_OK;
+}
+
+int sk_events_pool(const sk_event *ev, const uint8_t *use, int64_t nhits, int32_t N, sk_pool_rec *out)
+{
+    SK_ENTER(c);
+    int rc = check_pool(ev, nhits, N, out);
+    if (rc) return rc;
+    const size_t eb = (size_t)nhits * (size_t)N * sizeof(sk_event);
+    if ((rc = sk_reserve(c, &c->poolev, eb ? eb : 16))) return rc;
+    if (eb) SK_HIP(hipMemcpyAsync(c->poolev.p, ev, eb, hipMemcpyHostToDevice, c->stream));
+    return pool_core(c, (const sk_event *)c->poolev.p, use, true, nhits, N, nullptr, out);
+}
+
+int sk_events_pool_dev(const sk_event *d_ev, const uint8_t *d_use, int64_t nhits, int32_t N, sk_pool_rec *d_out)
+{
+    SK_ENTER(c);
+    const int rc = check_pool(d_ev, nhits, N, d_out);
+    if (rc) return rc;
+    return pool_core(c, d_ev, d_use, false, nhits, N, d_out, nullptr);
 }
 
 // hits of the last paths call whose path failed the self-check (window corner == dist bit for bit, a_0 == start,

@@ -29,7 +29,6 @@
 
 namespace {
 
-constexpr int BG_NPY_CHUNK = 8192;                       // numpy's reduction buffer
 constexpr int BG_STATIC_LDS = 256 * 8 + 256 * 4;         // the tree's partial sums + the digit histogram
 constexpr int BG_LDS_COLS = (160 * 1024 - BG_STATIC_LDS) / 8;   // 20 096 columns fit beside them
 
@@ -143,12 +142,7 @@ void k_row_background(const double *__restrict__ rowD, int64_t row_stride, const
     }
     auto at = [&](int j) -> double { if constexpr (STAGED) return lrow[j]; else return g[j]; };
     auto np_sum = [&](auto f) {                          // np.add.reduce over f(d[j])
-        double res = 0.0;
-        for (int base = 0; base < n; base += BG_NPY_CHUNK) {
-            const int m = n - base < BG_NPY_CHUNK ? n - base : BG_NPY_CHUNK;
-            res += wave_pairwise_terms(m, nodes, lane, [&](int i) { return f(at(base + i)); });
-        }
-        return res;
+        return wave_np_sum(n, nodes, lane, [&](int j) { return f(at(j)); });
     };
     const double mean = np_sum([](double v) { return v; }) / (double)n;
     const double ssq = np_sum([&](double v) { const double e = v - mean; return e * e; });

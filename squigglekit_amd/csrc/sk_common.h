@@ -93,6 +93,9 @@ struct sk_ctx {
     sk_buf pathscratch;   // alignment paths: the scratch tier's slabs (direction words + stripe boundary row per wavefront)
     sk_buf pathmotif; // alignment paths: the motifs of the call, flat (device)
     sk_buf pathspans; // alignment paths: the spans of the host entry points
+    sk_buf events;    // events: the sk_event records of the host entry points
+    sk_buf poolev;    // events: the records sk_events_pool uploads
+    sk_buf pool;      // events: pooling scratch -- the result [N], the count, the mask, the list of selected hits
     sk_buf panel;     // motif panel: the motifs of the call laid out per lane, their table, mean / sd (sk_panel.hip)
     sk_buf panelwin;  // motif panel: the window rows (int16, stride wstride) or the gathered float64 windows
     sk_buf panelaux;  // motif panel: per read window length, resolved begin, the caller's win rows / float64 offsets
@@ -281,6 +284,12 @@ struct sk_path_args {
 };
 int sk_path_begin(sk_ctx *c);
 int sk_launch_paths(sk_ctx *c, const sk_path_args *p);
+// events (sk_events.hip): one sk_event per motif point of the hits whose spans sk_launch_paths left in p->spans (same
+// arguments); events [nreads][K][nmotif].  A hit with spans -1 gets NaN / -1 / 0 records.
+int sk_launch_events(sk_ctx *c, const sk_path_args *p, sk_event *events);
+// pooling: d_ev [nhits][N] and d_use [nhits] (or nullptr) -> d_out [N]; d_idx (nhits ints) and d_cnt (one int): scratch
+int sk_launch_events_pool(sk_ctx *c, const sk_event *d_ev, const uint8_t *d_use, int64_t nhits, int32_t N,
+                          int32_t *d_idx, int32_t *d_cnt, sk_pool_rec *d_out);
 // fixed-point screening + certified window over all reads (sk_sdtwq.hip); leaves the retry list on the device
 int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, int span2,
                           int32_t *d_retry_cnt, int32_t *d_retry, int32_t *d_early_cnt, int32_t *d_early);

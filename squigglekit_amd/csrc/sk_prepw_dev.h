@@ -294,13 +294,25 @@ __device__ __forceinline__ zs_env zs_setup(int16_t *lcomp, double *nodes, int lo
 // terms [s, s + len) of one leaf (len <= 128, and >= 64 unless the chunk is one leaf; s a multiple of 8) in numpy's leaf
 // order; every sum is >= 0.  Lane l probes the positions 64 l (+ 4096 for the second probe) and sums a leaf if its
 // probe is the first one inside it.  nodes: 128 PROBES doubles of LDS.
-template <int PROBES, typename Leaf>
+// ANY: the sums may have either sign (sk_events.hip: sums of normalised samples) -- "no such node" is then one NaN bit
+// pattern, compared as bits.  A NaN the hardware computes is the canonical 0x7FF8...0, so no sum carries the marker
+// unless an input already does: an input NaN is passed on with its payload, and a caller who hands in that very
+// payload (already-normalised float64 samples, the records of a pool call) gets an undefined sum for that column.
+constexpr long long PAIRWISE_NO_NODE = (long long)0xFFF8736B5F6E6F21ull;
+template <bool ANY>
+__device__ __forceinline__ bool pairwise_has_node(double v)
+{
+    if constexpr (ANY) return __double_as_longlong(v) != PAIRWISE_NO_NODE;
+    else return v >= 0.0;
+}
+template <int PROBES, bool ANY = false, typename Leaf>
 __device__ __forceinline__ double wave_pairwise_leaves(int m, double *nodes, int lane, Leaf leaf)
 {
     // a chunk of up to 4 096 terms has its leaves at depth <= 6 (heap ids < 128), one of up to 8 192 at depth <= 7
     constexpr int DEPTH = 5 + PROBES;
 #pragma unroll
-    for (int k = 0; k < 2 * PROBES; k++) nodes[lane + 64 * k] = -1.0;   // "no such node" (the sums are >= 0)
+    for (int k = 0; k < 2 * PROBES; k++)                                // "no such node" (-1: the sums are >= 0)
+        nodes[lane + 64 * k] = ANY ? __longlong_as_double(PAIRWISE_NO_NODE) : -1.0;
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int q = 0; q < PROBES; q++) {
@@ -324,7 +336,7 @@ __device__ __forceinline__ double wave_pairwise_leaves(int m, double *nodes, int
         const int pid = (1 << (d - 1)) + lane;
         if (lane < (1 << (d - 1))) {
             const double a = nodes[2 * pid], b = nodes[2 * pid + 1];
-            if (a >= 0.0 && b >= 0.0) nodes[pid] = a + b;
+            if (pairwise_has_node<ANY>(a) && pairwise_has_node<ANY>(b)) nodes[pid] = a + b;
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -362,9 +374,9 @@ __device__ __forceinline__ double wave_pairwise_sq(int m, const int16_t *lcomp, 
     });
 }
 
-// the same over float64 terms, m <= 8192 (one reduction chunk): term(i) >= 0 is the i-th term of the chunk (the
-// last-row statistics of sk_bg.hip)
-template <typename Term>
+// the same over float64 terms, m <= 8192 (one reduction chunk): term(i) is the i-th term of the chunk, >= 0 unless ANY
+// (the last-row statistics of sk_bg.hip; the event and pool sums of sk_events.hip)
+template <bool ANY = false, typename Term>
 __device__ __forceinline__ double wave_pairwise_terms(int m, double *nodes, int lane, Term term)
 {
     if (m < 8) {
@@ -372,7 +384,7 @@ __device__ __forceinline__ double wave_pairwise_terms(int m, double *nodes, int 
         for (int i = 0; i < m; i++) res += term(i);
         return res;
     }
-    return wave_pairwise_leaves<2>(m, nodes, lane, [&](int s, int len) {
+    return wave_pairwise_leaves<2, ANY>(m, nodes, lane, [&](int s, int len) {
         double r[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) r[j] = term(s + j);
@@ -385,6 +397,20 @@ __device__ __forceinline__ double wave_pairwise_terms(int m, double *nodes, int 
         for (int i = full; i < len; i++) res += term(s + i);
         return res;
     });
+}
+
+// np.add.reduce over term(0) .. term(n - 1) of a contiguous float64 array: serial over numpy's reduction buffers of
+// 8 192 terms, the pairwise tree inside one.  nodes: 256 doubles of LDS; every lane returns the sum.
+constexpr int NPY_REDUCE_CHUNK = 8192;
+template <bool ANY = false, typename Index, typename Term>
+__device__ __forceinline__ double wave_np_sum(Index n, double *nodes, int lane, Term term)
+{
+    double res = 0.0;
+    for (Index base = 0; base < n; base += NPY_REDUCE_CHUNK) {
+        const int m = n - base < NPY_REDUCE_CHUNK ? (int)(n - base) : NPY_REDUCE_CHUNK;
+        res += wave_pairwise_terms<ANY>(m, nodes, lane, [&](int i) { return term(base + i); });
+    }
+    return res;
 }
 
 // Read r: filter, compacted samples -> comp row (and LDS), mean / std -> prep[r] (lane 0 stores), returned in every lane.

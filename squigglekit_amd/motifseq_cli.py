@@ -6,7 +6,7 @@ the scoring of MotifSeq.py:441-445 stays in Python so the printed floats are the
 reference's digit for digit.  fast5 input (-f / -p) goes through h5py when it is importable and
 through the built-in reader (hdf5min.py) otherwise, with the reference's stderr messages.
 Additive flags: --device, --gpus, --batch, --after_stall, --strict-compat, --blow5, --i16, --hits, --min_hit_p, --paths,
---background, --max_local_Z, --region, --panel.
+--background, --max_local_Z, --region, --panel, --pool.
 Whole chunks of plain integer reads (TSV chunks, BLOW5 / packed blocks) go to the GPU as one batch and their rows are
 formatted natively (csrc/sk_io.cpp writes floats as Python does); anything unusual takes the per-read route.
 """
@@ -93,6 +93,10 @@ def build_parser():
                         "and the hit's local_Z and robust_Z against it; stdout is unchanged")
     p.add_argument("--max_local_Z", type=float, default=None, metavar="Z",
                    help="[extension] with --background: leave out the lines whose local_Z is above Z")
+    p.add_argument("--pool", default=None, metavar="FILE",
+                   help="[extension] write to FILE after the run, per model and motif point, the model the printed hits show "
+                        "when pooled: hits, level (sample weighted), its spread over the hits, the noise inside an event, "
+                        "dwell and cost; stdout is unchanged")
     p.add_argument("--region", default=None, metavar="A:B",
                    help="[extension] search only the raw samples [A:B] of every read, cut as a Python slice before the outlier "
                         "filter (either side may be empty or negative: 0:2000, --region=-3000:); coordinates then index "
@@ -121,6 +125,8 @@ PANEL_HEADER = ["fast5", "readID", "best_model", "start", "end", "length", "dist
                 "hit_Probability", "second_model", "second_Z", "delta_Z", "search_from"]
 BACKGROUND_HEADER = ["fast5", "readID", "model", "hit", "distance_score", "row_mean", "row_stdev", "local_Z", "row_median",
                      "row_mad", "robust_Z", "below_1sd", "n"]
+POOL_HEADER = ["model", "point", "pos", "base", "model_current", "hits", "level", "level_sd", "sd_mean", "dwell_mean",
+               "dwell_sd", "cost_mean"]
 PATHS_HEADER = ["fast5", "readID", "model", "hit", "pos", "base", "model_current", "start", "end", "length", "mean_signal"]
 
 
@@ -137,6 +143,10 @@ def check_hit_flags(parser, args):
         parser.error("--background writes one line per printed hit: it does not combine with --panel")
     if args.paths is not None and args.after_stall:
         parser.error("--paths does not combine with --after_stall")
+    if args.pool is not None and args.after_stall:
+        parser.error("--pool does not combine with --after_stall")
+    if args.pool is not None and args.panel:
+        parser.error("--pool pools the printed hits: it does not combine with --panel")
     if args.hits is not None and not 1 <= args.hits <= 64:
         parser.error("--hits must be between 1 and 64")
     if args.min_hit_p is not None and args.hits is None:
@@ -190,32 +200,60 @@ class _Batcher:
         self._pending, self._worker = None, None
         self.bases, self.paths_fh = {}, None          # --paths: base table per model (scrappie text), the open FILE
         self.background_fh = None                     # --background: the open FILE
-        # --paths / --background write per printed line: every read takes the per-read route (emit)
-        self.per_line = args.paths is not None or args.background is not None
+        self.pooled = {name: [] for name in order}    # --pool: per model the events [N] of every printed hit
+        # --paths / --background / --pool work per printed line: every read takes the per-read route (emit)
+        self.per_line = args.paths is not None or args.background is not None or args.pool is not None
         # --region / --panel: every read goes through the per-read queue (add / flush), --batch reads per GPU call
         self.queued = args.region is not None or args.panel
 
-    def search(self, fn_hits, fn_multi, fn_paths, fn_background, *args):
+    def search(self, fn_hits, fn_multi, fn_paths, fn_background, fn_events, *args):
         """The GPU call of one batch: (what of_read / table take, spans per motif or None, background records per motif
-        or None).  --paths takes the paths call -- hit lists plus spans -- and --background the background call -- hit
-        lists plus each read's row statistics; without --hits their rank-1 records stand in for the default path's (the
-        same records bit for bit)."""
+        or None, events per motif or None).  --paths takes the paths call -- hit lists plus spans -- and --background the
+        background call -- hit lists plus each read's row statistics; without --hits their rank-1 records stand in for
+        the default path's (the same records bit for bit).  --pool takes the events call, whose records also give the
+        spans of --paths."""
         a = self.args
         tail = (a.scale, a.scale_low, a.scale_hi)
-        hits = spans = bgs = None
+        hits = spans = bgs = evs = None
         if a.background is not None:
             res = fn_background(*args, a.hits or 1, float("inf"), *tail)
             hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
             bgs = [b for _, _, b in res]
-        if a.paths is not None:
+        if a.pool is not None:
+            # (with --background this is a second search of the batch: no entry point returns row statistics and events
+            # together yet.  Both calls give the same hit lists bit for bit; the events call's are the ones printed.)
+            res = fn_events(*args, a.hits or 1, float("inf"), *tail)
+            hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
+            evs = [ev for _, _, ev in res]
+            if a.paths is not None:
+                spans = [api.spans_of_events(ev) for ev in evs]
+        elif a.paths is not None:
             res = fn_paths(*args, a.hits or 1, float("inf"), *tail)
             hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
             spans = [sp for _, _, sp in res]
         if hits is not None:
-            return hits, spans, bgs
+            return hits, spans, bgs, evs
         if a.hits is not None:
-            return fn_hits(*args, a.hits, float("inf"), *tail), None, None
-        return fn_multi(*args, *tail), None, None
+            return fn_hits(*args, a.hits, float("inf"), *tail), None, None, None
+        return fn_multi(*args, *tail), None, None, None
+
+    def pool_table(self, path):
+        """--pool: one pool_events call per model over the events of its printed hits, one line per motif point."""
+        with open(path, "w") as fh:
+            fh.write("\t".join(POOL_HEADER) + "\n")
+            for name in self.order:
+                motif = self.models[name]
+                evs = self.pooled[name]
+                pool = api.pool_events(np.stack(evs) if evs else api.no_events((0, len(motif))))
+                where = {}
+                for pos, base, _, first, cnt in self.bases.get(name) or []:
+                    for i in range(first, first + cnt):
+                        where[i] = (pos, base)
+                for i, rec in enumerate(pool):
+                    pos, base = where.get(i, (".", "."))
+                    row = (name, i, pos, base, float(motif[i]), int(rec["hits"]), float(rec["level"]), float(rec["level_sd"]),
+                           float(rec["sd_mean"]), float(rec["dwell_mean"]), float(rec["dwell_sd"]), float(rec["cost_mean"]))
+                    fh.write("\t".join("{}".format(v) for v in row) + "\n")
 
     def background_line(self, fast5, read_id, name, rank, dist, bg, local_z, robust_z):
         """One line of the --background file for one printed hit."""
@@ -270,10 +308,10 @@ class _Batcher:
         if sigs:
             _STATS[0].batch(len(sigs))
         if sigs or a.hits is not None:
-            hits, spans, bgs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
-                                           api.motifseq_background, sigs, motifs)
+            hits, spans, bgs, evs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
+                                                api.motifseq_background, api.motifseq_events, sigs, motifs)
         else:
-            hits, spans, bgs = [[] for _ in self.order], None, None
+            hits, spans, bgs, evs = [[] for _ in self.order], None, None, None
         slot = {i: k for k, i in enumerate(live)}
         for i, (fast5, read_id) in enumerate(self.meta):
             if self.sigs[i] is None:
@@ -281,7 +319,8 @@ class _Batcher:
                 continue
             r = slot[i]
             self.emit(fast5, read_id, self.of_read(hits, r), self.sigs[i], None if cuts is None else int(cuts[r]),
-                      None if spans is None else [sp[r] for sp in spans], None if bgs is None else [b[r] for b in bgs])
+                      None if spans is None else [sp[r] for sp in spans], None if bgs is None else [b[r] for b in bgs],
+                      None if evs is None else [e[r] for e in evs])
         self.meta, self.sigs = [], []
 
     def windows(self, sigs, region):
@@ -331,11 +370,11 @@ class _Batcher:
             if keep:
                 self.panel_table(keep, recs, frm)
             return
-        bgs = None
+        bgs = evs = None
         if a.hits is not None or self.per_line:
             wins, frm = self.windows(sigs, region)
-            hits, spans, bgs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
-                                           api.motifseq_background, wins, motifs)
+            hits, spans, bgs, evs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
+                                                api.motifseq_background, api.motifseq_events, wins, motifs)
         else:
             _, frm, hits = api.motifseq_panel(sigs, motifs, mm, ms, region, None, a.scale, a.scale_low, a.scale_hi,
                                               records=True)
@@ -350,7 +389,7 @@ class _Batcher:
             else:                                                           # (-x / --strict-compat normalise the slice)
                 sig = np.asarray(sigs[r])[slice(*region)] if (a.sig_extract or a.strict_compat) else None
             self.emit(fast5, read_id, self.of_read(hits, r), sig, int(frm[r]), None if spans is None else [sp[r] for sp in spans],
-                      None if bgs is None else [b[r] for b in bgs])
+                      None if bgs is None else [b[r] for b in bgs], None if evs is None else [e[r] for e in evs])
 
     def panel_table(self, keep, recs, frm):
         """The --panel rows of the reads in `keep` [(fast5, readID, slot)] through the native formatter: the GPU's scores,
@@ -383,11 +422,12 @@ class _Batcher:
             return [(h[r], cnt[r]) for h, cnt in hits]
         return [hits[c][r] for c in range(len(self.order))]
 
-    def emit(self, fast5, read_id, hits, sig, cut, spans=None, bgs=None):
+    def emit(self, fast5, read_id, hits, sig, cut, spans=None, bgs=None, evs=None):
         """The rows of one read, one per motif (MotifSeq.py:436-449); with --hits one per match, best first.
         spans (--paths): per motif the read's [K, N, 2]; every printed hit also writes its lines to the paths file.
         bgs (--background): per motif the read's background record; every printed hit also writes its line to the
-        background file, and --max_local_Z leaves out of both the hits that score above it."""
+        background file, and --max_local_Z leaves out of both the hits that score above it.
+        evs (--pool): per motif the read's events [K, N]; those of every printed hit are kept for the pool table."""
         a = self.args
         norm = None
         for c, name in enumerate(self.order):
@@ -444,6 +484,8 @@ class _Batcher:
                     if norm is None:
                         norm = api.normalise(sig, a.scale, a.scale_low, a.scale_hi)
                     self.path_lines(fast5, read_id, name, rank + 1, spans[c][rank], norm)
+                if evs is not None and not h["flags"] & 2:
+                    self.pooled[name].append(evs[c][rank])
 
     def table(self, n, fast5_col, id_col, hits):
         """The rows of n reads x every motif through the native formatter (file order, read-major).  Returns False --
@@ -547,7 +589,7 @@ class _Batcher:
             _mark("GPU call starts")
             try:
                 return self.search(api.motifseq_hits_batch, api.motifseq_multi_batch, api.motifseq_paths_batch,
-                                   api.motifseq_background_batch, rows, nsamp, motifs)
+                                   api.motifseq_background_batch, api.motifseq_events_batch, rows, nsamp, motifs)
             finally:
                 _mark("GPU call ends")
         job = self._worker.submit(call)
@@ -568,8 +610,8 @@ class _Batcher:
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d float64 reads to the GPU worker" % fb.n)
         job = self._worker.submit(self.search, api.motifseq_hits_ragged_f64, api.motifseq_multi_ragged_f64,
-                                  api.motifseq_paths_ragged_f64, api.motifseq_background_ragged_f64, fb.batch_values(),
-                                  fb.off, motifs)
+                                  api.motifseq_paths_ragged_f64, api.motifseq_background_ragged_f64,
+                                  api.motifseq_events_ragged_f64, fb.batch_values(), fb.off, motifs)
         prev, self._pending = self._pending, (job, fb.n, ("span", fb.buf, fb.spans("name")), ("span", fb.buf, fb.spans("id")),
                                               lambda i, b=fb: b.text("name", i), lambda i, b=fb: b.text("id", i),
                                               lambda i, b=fb: b.values[b.off[i]:b.off[i + 1]])
@@ -583,7 +625,7 @@ class _Batcher:
 
     def _finish(self, p):
         job, n, fast5_col, id_col, name_of, id_of, sig_of = p
-        hits, spans, bgs = job.result()
+        hits, spans, bgs, evs = job.result()
         _STATS[0].batch(n)
         _mark("block of %d reads back from the GPU" % n)
         if (self.table_hits if self.args.hits is not None else self.table)(n, fast5_col, id_col, hits):
@@ -597,7 +639,8 @@ class _Batcher:
         need_sig = self.args.sig_extract or self.args.strict_compat or spans is not None
         for i in range(n):
             self.emit(name_of(i), id_of(i), self.of_read(hits, i), sig_of(i) if need_sig else None, None,
-                      None if spans is None else [sp[i] for sp in spans], None if bgs is None else [b[i] for b in bgs])
+                      None if spans is None else [sp[i] for sp in spans], None if bgs is None else [b[i] for b in bgs],
+                      None if evs is None else [e[i] for e in evs])
 
     def block(self, blk):
         """A parsed TSV chunk (tsvio.TsvBlock): its integer lines go to the GPU as ONE int16 batch straight from the
@@ -746,8 +789,11 @@ def main(argv=None):
     if args.gpus > 1:
         api.set_devices(range(args.gpus))
     out = _Batcher(args, models, order, lens)
-    if args.paths is not None:
+    if args.paths is not None or args.pool is not None:
         out.bases = tsvio.model_bases_auto(args.model) if args.model else {}
+    if args.pool is not None:
+        open(args.pool, "w").close()                 # (an unwritable FILE fails before the run, not after it)
+    if args.paths is not None:
         out.paths_fh = open(args.paths, "w")
         out.paths_fh.write("\t".join(PATHS_HEADER) + "\n")
     if args.background is not None:
@@ -839,6 +885,9 @@ def main(argv=None):
         out.paths_fh.close()
     if out.background_fh is not None:
         out.background_fh.close()
+    if args.pool is not None:
+        sys.stdout.flush()
+        out.pool_table(args.pool)
     _mark("end of main()")
     _STATS[0].finish(args, [args.signal, getattr(args, "blow5", None), getattr(args, "i16", None)] + list(getattr(args, "ind", None) or []))
 

@@ -311,6 +311,35 @@ def main():
                 print("BACKGROUND mismatch round %d %s: %s" % (rounds, randcases.describe(case), msg))
         for key in randcases.SWITCHES:
             os.environ.pop(key, None)
+        # ---- events and pooling: a paths draw through the events twin, every record and the pooled model against the
+        # numpy statement of the contract (tests/test_events_host.py), the hit lists against the hit-list call's
+        case = randcases.DRAW["paths"](rng)
+        for key in randcases.SWITCHES:
+            if key in case["env"]:
+                os.environ[key] = case["env"][key]
+        from test_events_host import reference_batch, reference_pool
+        ekw = (case["motifs"], case["K"], float("inf"), case["scale"], case["lo"], case["hi"])
+        got, twin = api.motifseq_events(case["reads"], *ekw), api.motifseq_hits(case["reads"], *ekw)
+        for m, motif in enumerate(case["motifs"]):
+            _, want = reference_batch(ora, case["reads"], motif, case["K"], case["scale"], case["lo"], case["hi"])
+            msg = None
+            if got[m][0].tobytes() != twin[m][0].tobytes() or not np.array_equal(got[m][1], twin[m][1]):
+                msg = "hit lists differ from the hit-list call's"
+            elif api.last_path_mismatches() != 0:
+                msg = "%d hits failed the path kernel's self-check" % api.last_path_mismatches()
+            elif got[m][2].tobytes() != want.tobytes():
+                r, k, i = (int(v[0]) for v in np.nonzero(got[m][2] != want))
+                msg = "motif %d read %d hit %d point %d: got %s want %s" % (m, r, k, i, got[m][2][r, k, i], want[r, k, i])
+            else:
+                use = rng.random(want.shape[0] * want.shape[1]) < 0.7
+                pool, ref = api.pool_events(got[m][2], use), reference_pool(want, use)
+                if any(pool[f].tobytes() != ref[f].tobytes() for f in api.POOL_DTYPE.names):
+                    msg = "motif %d: the pooled model differs from numpy's" % m
+            if msg is not None:
+                bad += 1
+                print("EVENTS mismatch round %d %s: %s" % (rounds, randcases.describe(case), msg))
+        for key in randcases.SWITCHES:
+            os.environ.pop(key, None)
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
