@@ -157,6 +157,11 @@ POOL_DTYPE = np.dtype({"names": ["level", "level_sd", "sd_mean", "dwell_mean", "
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
+# the hit family (hit lists, background, paths, events): its int16 and its ragged forms share an argument list up to
+# out, count; background, paths and events add one output
+_HITS_TAIL = [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, _vp, _vp]
+_HITS_I16 = [_vp, C.c_int64, _vp, C.c_int32] + _HITS_TAIL
+_HITS_RAGGED = [_vp, _vp, C.c_int32] + _HITS_TAIL
 ABI = {
     "sk_version": (C.c_char_p, []),
     "sk_last_error": (C.c_char_p, []),
@@ -201,38 +206,22 @@ ABI = {
                                       C.c_int32, C.c_int32, _vp]),
     "sk_motifseq_multi_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, _vp]),
-    "sk_motifseq_hits_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
-    "sk_motifseq_hits_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_double, _vp, _vp]),
-    "sk_motifseq_hits_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                         C.c_int32, C.c_double, _vp, _vp]),
-    "sk_motifseq_hits_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                           C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
-    "sk_motifseq_background_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_background_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_background_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                               C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_background_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                                 C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_paths_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_paths_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_paths_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                          C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_paths_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                            C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_events_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                         C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_events_f64": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                         C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_events_centi": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                           C.c_int32, C.c_double, _vp, _vp, _vp]),
-    "sk_motifseq_events_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "sk_motifseq_hits_i16": (C.c_int, _HITS_I16),
+    "sk_motifseq_hits_f64": (C.c_int, _HITS_RAGGED),
+    "sk_motifseq_hits_centi": (C.c_int, _HITS_RAGGED),
+    "sk_motifseq_hits_dev_i16": (C.c_int, _HITS_I16),
+    "sk_motifseq_background_i16": (C.c_int, _HITS_I16 + [_vp]),
+    "sk_motifseq_background_f64": (C.c_int, _HITS_RAGGED + [_vp]),
+    "sk_motifseq_background_centi": (C.c_int, _HITS_RAGGED + [_vp]),
+    "sk_motifseq_background_dev_i16": (C.c_int, _HITS_I16 + [_vp]),
+    "sk_motifseq_paths_i16": (C.c_int, _HITS_I16 + [_vp]),
+    "sk_motifseq_paths_f64": (C.c_int, _HITS_RAGGED + [_vp]),
+    "sk_motifseq_paths_centi": (C.c_int, _HITS_RAGGED + [_vp]),
+    "sk_motifseq_paths_dev_i16": (C.c_int, _HITS_I16 + [_vp]),
+    "sk_motifseq_events_i16": (C.c_int, _HITS_I16 + [_vp]),
+    "sk_motifseq_events_f64": (C.c_int, _HITS_RAGGED + [_vp]),
+    "sk_motifseq_events_centi": (C.c_int, _HITS_RAGGED + [_vp]),
+    "sk_motifseq_events_dev_i16": (C.c_int, _HITS_I16 + [_vp]),
     "sk_events_pool": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
     "sk_events_pool_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
     "sk_last_path_mismatches": (C.c_int, []),

@@ -771,7 +771,9 @@ def motifseq_multi(reads, motifs, scale="medmad", scale_low=0, scale_hi=1200, _p
 
 
 # ----------------------------------------------------------------------------
-# MotifSeq hit lists: up to K non-overlapping matches per read and motif
+# MotifSeq hit lists: up to K non-overlapping matches per read and motif -- and the three families that return the
+# hit lists plus one more array (read background, alignment paths, events).  The four share everything below but
+# their names and docstrings.
 # ----------------------------------------------------------------------------
 def _hits_args(motifs, max_hits, max_dist):
     max_hits, max_dist = int(max_hits), float(max_dist)
@@ -785,63 +787,146 @@ def _hits_args(motifs, max_hits, max_dist):
     return ms, flat, moff, max_hits, max_dist
 
 
-def motifseq_hits_batch(sig, lens, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0,
-                        scale_hi=1200, devices=None):
-    """Hit lists of every motif against every row of an int16 [R, stride] batch (one filter / statistics pass):
-    a list, per motif, of (hits[R, max_hits] HIT_DTYPE, count[R]).  The block form of motifseq_hits."""
+class _Family:
+    """What the calls of one family return per motif besides (hits[R, K], count[R]) -- `per`: "" nothing, "read" one
+    record per read (in C [motif][read]), "point" `width` values per motif point (in C the blocks of _unpack_blocks) --
+    with the array's dtype and the fill of a read no call reaches, and whether its calls make paths (the self-check
+    counter of last_path_mismatches)."""
+
+    def __init__(self, name, dtype=None, per="", width=1, fill=None, counts_paths=False):
+        self.name, self.dtype, self.per, self.width = name, dtype, per, width
+        self.fill, self.counts_paths = fill, counts_paths
+
+    def shape(self, R, K, N):
+        """of one motif's array: [R], [R, K, N] or [R, K, N, width]"""
+        return (R,) if self.per == "read" else (R, K, N) + ((self.width,) if self.width > 1 else ())
+
+    def flat(self, nmotifs, n, K, total):
+        """elements of the C buffer of a shard of n reads (total: the motifs' points in all)"""
+        return nmotifs * n if self.per == "read" else self.width * K * n * total
+
+
+_HITS = _Family("hits")
+_BACKGROUND = _Family("background", BG_DTYPE, "read", fill=lambda shape: np.zeros(shape, dtype=BG_DTYPE))
+_PATHS = _Family("paths", np.int32, "point", 2, lambda shape: np.full(shape, -1, dtype=np.int32), True)
+_EVENTS = _Family("events", EVENT_DTYPE, "point", 1, lambda shape: no_events(shape), True)
+_path_lock = __import__("threading").Lock()
+_path_mismatches = [-1]
+
+
+def _unpack_blocks(buf, moff, K, n, width):
+    """The per-motif arrays of the flat spans (width 2) or events (width 1) buffer of a call over n reads
+    (include/squigglekit_hip.h): motif k's block begins at width * K * n * moff[k], inside it [read][hit][N_k][width]
+    ([read][hit][N_k] for width 1)."""
+    out = []
+    for k in range(len(moff) - 1):
+        N, b = int(moff[k + 1] - moff[k]), width * K * n * int(moff[k])
+        out.append(buf[b:b + width * K * n * N].reshape((n, K, N) + ((width,) if width > 1 else ())))
+    return out
+
+
+def _hits_over(fam, devices, R, ms, moff, K, entry_call):
+    """Runs entry_call(lo, hi, hits_part, count_part[, third_part]) over the devices (_over_devices: every shard writes
+    its reads); returns per motif (hits[R, K], count[R]) plus the family's third array.  A family that makes paths
+    resets the self-check counter and adds up its shards' (last_path_mismatches)."""
+    L = _lib.load()
+    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
+    count = np.zeros((len(ms), R), dtype=np.int32)
+    third = [fam.fill(fam.shape(R, K, m.size)) for m in ms] if fam.per else None
+    if fam.counts_paths:
+        with _path_lock:
+            _path_mismatches[0] = 0
+
+    def call(lo, hi):
+        n = hi - lo
+        bufs = [np.zeros((len(ms), n, K), dtype=HIT_DTYPE), np.zeros((len(ms), n), dtype=np.int32)]
+        if fam.per:
+            bufs.append(np.zeros(fam.flat(len(ms), n, K, int(moff[-1])), dtype=fam.dtype))
+        rc = entry_call(lo, hi, *bufs)
+        if rc == 0:
+            hits[:, lo:hi], count[:, lo:hi] = bufs[0], bufs[1]
+            if fam.per:
+                parts = bufs[2].reshape(len(ms), n) if fam.per == "read" else _unpack_blocks(bufs[2], moff, K, n, fam.width)
+                for k in range(len(ms)):
+                    third[k][lo:hi] = parts[k]
+            if fam.counts_paths:
+                bad = L.sk_last_path_mismatches()
+                with _path_lock:
+                    _path_mismatches[0] += max(bad, 0)
+        return rc
+    if R and ms:
+        _over_devices(devices, R, call)
+    return [(hits[k], count[k]) + ((third[k],) if fam.per else ()) for k in range(len(ms))]
+
+
+def _hits_batch(fam, sig, lens, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices):
+    """The packed int16 form of a family: rows of an int16 [R, stride] batch."""
     sig = np.ascontiguousarray(sig, dtype=np.int16)
     lens = np.ascontiguousarray(lens, dtype=np.int32)
     R = sig.shape[0]
     if _too_wide_for_i16(scale_low, scale_hi):
         # limits wider than the int16 kernels' histogram: the float64 kernels (the same filter, the same statistics)
         flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
-        return motifseq_hits_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
-    L = _lib.load()
+        return globals()["motifseq_%s_ragged_f64" % fam.name](flat, off, motifs, max_hits, max_dist, scale, scale_low,
+                                                              scale_hi, devices)
+    entry = getattr(_lib.load(), "sk_motifseq_%s_i16" % fam.name)
     ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
-    count = np.zeros((len(ms), R), dtype=np.int32)
 
-    def call(lo, hi):
-        part = np.zeros((len(ms), hi - lo, K), dtype=HIT_DTYPE)
-        cnt = np.zeros((len(ms), hi - lo), dtype=np.int32)
-        rc = L.sk_motifseq_hits_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff),
-                                    len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part),
-                                    ptr(cnt))
-        if rc == 0:
-            hits[:, lo:hi] = part
-            count[:, lo:hi] = cnt
-        return rc
-    if R and ms:
-        _over_devices(devices, R, call)
-    return [(hits[k], count[k]) for k in range(len(ms))]
+    def call(lo, hi, *bufs):
+        return entry(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff), len(ms),
+                     _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, *map(ptr, bufs))
+    return _hits_over(fam, devices, R, ms, moff, K, call)
+
+
+def _hits_ragged(fam, values, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices):
+    """The ragged form of a family: read r = values[off[r]:off[r+1]], float64 or int32 centi-units."""
+    centi = isinstance(values, np.ndarray) and values.dtype == np.int32      # converted on the device (value / 100)
+    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
+    entry = getattr(_lib.load(), "sk_motifseq_%s_%s" % (fam.name, "centi" if centi else "f64"))
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
+
+    def call(lo, hi, *bufs):
+        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
+                     int(scale_low), int(scale_hi), K, md, *map(ptr, bufs))
+    return _hits_over(fam, devices, off.size - 1, ms, moff, K, call)
+
+
+def _hits_mixed(fam, reads, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices):
+    """The per-read form of a family: integer-valued reads through its packed int16 form, the rest through its ragged
+    form (both looked up by name when called), merged in read order; the self-check counters of the two add up."""
+    ms = _hits_args(motifs, max_hits, max_dist)[0]            # (argument errors before any GPU work)
+    ints, arrs, flts = _split_int16(reads)
+    R, K = len(reads), int(max_hits)
+    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32))
+           + ((fam.fill(fam.shape(R, K, m.size)),) if fam.per else ()) for m in ms]
+    bad = 0
+    for idx, route, pack in ((ints, "_batch", lambda: pack_i16(arrs)),
+                             (flts, "_ragged_f64", lambda: pack_f64([reads[i] for i in flts]))):
+        if idx and ms:
+            got = globals()["motifseq_" + fam.name + route](*pack(), ms, K, max_dist, scale, scale_low, scale_hi, devices)
+            for whole, part in zip(res, got):
+                for a, b in zip(whole, part):
+                    a[idx] = b
+            bad += _path_mismatches[0]
+    if fam.counts_paths:
+        with _path_lock:
+            _path_mismatches[0] = bad
+    return res
+
+
+def motifseq_hits_batch(sig, lens, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0,
+                        scale_hi=1200, devices=None):
+    """Hit lists of every motif against every row of an int16 [R, stride] batch (one filter / statistics pass):
+    a list, per motif, of (hits[R, max_hits] HIT_DTYPE, count[R]).  The block form of motifseq_hits."""
+    return _hits_batch(_HITS, sig, lens, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_hits_ragged_f64(values, off, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0,
                              scale_hi=1200, devices=None):
     """Hit lists of every motif against a ragged float64 batch (read r = values[off[r]:off[r+1]]; int32 values are
     centi-units, value / 100): per motif (hits[R, max_hits], count[R]).  The pA TSV / BLOW5-pA route."""
-    L = _lib.load()
-    centi = isinstance(values, np.ndarray) and values.dtype == np.int32      # converted on the device (value / 100)
-    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
-    entry = L.sk_motifseq_hits_centi if centi else L.sk_motifseq_hits_f64
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    R = off.size - 1
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
-    count = np.zeros((len(ms), R), dtype=np.int32)
-
-    def call(lo, hi):
-        part = np.zeros((len(ms), hi - lo, K), dtype=HIT_DTYPE)
-        cnt = np.zeros((len(ms), hi - lo), dtype=np.int32)
-        rc = entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms),
-                                    _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt))
-        if rc == 0:
-            hits[:, lo:hi] = part
-            count[:, lo:hi] = cnt
-        return rc
-    if R and ms:
-        _over_devices(devices, R, call)
-    return [(hits[k], count[k]) for k in range(len(ms))]
+    return _hits_ragged(_HITS, values, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_hits(reads, motifs, max_hits=8, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
@@ -850,49 +935,13 @@ def motifseq_hits(reads, motifs, max_hits=8, max_dist=float("inf"), scale="medma
     (hits[nreads, max_hits] HIT_DTYPE, count[nreads]).  Rank 1 is motifseq_multi's record; the ranks after it take
     the next smallest distance whose [start, end] overlaps no earlier hit, up to max_dist.  Unused slots: dist NaN,
     start = end = -1.  Integer-valued reads go through the int16 kernels, the rest through the float64 ones."""
-    _hits_args(motifs, max_hits, max_dist)                    # (argument errors before any GPU work)
-    ints, arrs, flts = _split_int16(reads)
-    R, K = len(reads), int(max_hits)
-    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32)) for _ in motifs]
-    if ints and len(motifs):
-        buf, lens = pack_i16(arrs)
-        for (h, c), (hi, ci) in zip(res, motifseq_hits_batch(buf, lens, motifs, K, max_dist, scale, scale_low,
-                                                             scale_hi, devices)):
-            h[ints], c[ints] = hi, ci
-    if flts and len(motifs):
-        flat, off = pack_f64([reads[i] for i in flts])
-        for (h, c), (hf, cf) in zip(res, motifseq_hits_ragged_f64(flat, off, motifs, K, max_dist, scale, scale_low,
-                                                                  scale_hi, devices)):
-            h[flts], c[flts] = hf, cf
-    return res
+    return _hits_mixed(_HITS, reads, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 # ----------------------------------------------------------------------------
 # MotifSeq read background: the hit list plus the statistics of each read's whole last row
 # ----------------------------------------------------------------------------
 MAD_SCALE = 1.4826                     # medmad's constant (MotifSeq.py:192-200)
-
-
-def _background_over(devices, R, ms, K, entry_call):
-    """Runs entry_call(lo, hi, hits_part, count_part, bg_part) over the devices (the split of motifseq_hits_batch);
-    returns per motif (hits[R, K], count[R], bg[R])."""
-    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
-    count = np.zeros((len(ms), R), dtype=np.int32)
-    bg = np.zeros((len(ms), R), dtype=BG_DTYPE)
-
-    def call(lo, hi):
-        part = np.zeros((len(ms), hi - lo, K), dtype=HIT_DTYPE)
-        cnt = np.zeros((len(ms), hi - lo), dtype=np.int32)
-        b = np.zeros((len(ms), hi - lo), dtype=BG_DTYPE)
-        rc = entry_call(lo, hi, part, cnt, b)
-        if rc == 0:
-            hits[:, lo:hi] = part
-            count[:, lo:hi] = cnt
-            bg[:, lo:hi] = b
-        return rc
-    if R and ms:
-        _over_devices(devices, R, call)
-    return [(hits[k], count[k], bg[k]) for k in range(len(ms))]
 
 
 def motifseq_background_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
@@ -902,38 +951,14 @@ def motifseq_background_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf
     draws a hit against (MotifSeq.py:507-513) -- bit for bit as numpy would: mean = np.mean(d), std = np.std(d),
     median = np.median(d), mad = np.median(np.abs(d - median)), below = the columns with d < mean - std, n = columns.
     Reads flagged empty or degenerate: NaN, below -1.  local_scores turns a hit's distance into scores against it."""
-    sig = np.ascontiguousarray(sig, dtype=np.int16)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    R = sig.shape[0]
-    if _too_wide_for_i16(scale_low, scale_hi):
-        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
-        return motifseq_background_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
-    L = _lib.load()
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-
-    def call(lo, hi, part, cnt, b):
-        return L.sk_motifseq_background_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat),
-                                            ptr(moff), len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K,
-                                            md, ptr(part), ptr(cnt), ptr(b))
-    return _background_over(devices, R, ms, K, call)
+    return _hits_batch(_BACKGROUND, sig, lens, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_background_ragged_f64(values, off, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
                                    scale_hi=1200, devices=None):
     """motifseq_hits_ragged_f64 plus the background records (see motifseq_background_batch); int32 values are
     centi-units."""
-    L = _lib.load()
-    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
-    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
-    entry = L.sk_motifseq_background_centi if centi else L.sk_motifseq_background_f64
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    R = off.size - 1
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-
-    def call(lo, hi, part, cnt, b):
-        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
-                     int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt), ptr(b))
-    return _background_over(devices, R, ms, K, call)
+    return _hits_ragged(_BACKGROUND, values, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_background(reads, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
@@ -941,21 +966,7 @@ def motifseq_background(reads, motifs, max_hits=1, max_dist=float("inf"), scale=
     """motifseq_hits plus each read's own background: a list, per motif, of
     (hits[nreads, max_hits], count[nreads], bg[nreads]) -- see motifseq_background_batch.  The same read kinds as
     motifseq_hits: integer-valued reads through the int16 kernels, the rest through the float64 ones."""
-    ms = _hits_args(motifs, max_hits, max_dist)[0]
-    ints, arrs, flts = _split_int16(reads)
-    R, K = len(reads), int(max_hits)
-    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32), np.zeros(R, dtype=BG_DTYPE)) for _ in ms]
-    if ints and ms:
-        buf, lens = pack_i16(arrs)
-        for (h, c, b), (hi, ci, bi) in zip(res, motifseq_background_batch(buf, lens, ms, K, max_dist, scale, scale_low,
-                                                                          scale_hi, devices)):
-            h[ints], c[ints], b[ints] = hi, ci, bi
-    if flts and ms:
-        flat, off = pack_f64([reads[i] for i in flts])
-        for (h, c, b), (hf, cf, bf) in zip(res, motifseq_background_ragged_f64(flat, off, ms, K, max_dist, scale,
-                                                                               scale_low, scale_hi, devices)):
-            h[flts], c[flts], b[flts] = hf, cf, bf
-    return res
+    return _hits_mixed(_BACKGROUND, reads, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def local_scores(dist, bg):
@@ -973,105 +984,25 @@ def local_scores(dist, bg):
 # ----------------------------------------------------------------------------
 # MotifSeq alignment paths: per hit, the samples each motif point covers
 # ----------------------------------------------------------------------------
-_path_lock = __import__("threading").Lock()
-_path_mismatches = [-1]
-
-
-def _paths_over(devices, R, ms, moff, K, entry_call):
-    """Runs entry_call(lo, hi, hits_part, count_part, spans_part) over the devices; returns per motif
-    (hits[R, K], count[R], spans[R, K, N, 2]).  The self-check counters of the shards add up (last_path_mismatches)."""
-    L = _lib.load()
-    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
-    count = np.zeros((len(ms), R), dtype=np.int32)
-    spans = [np.full((R, K, m.size, 2), -1, dtype=np.int32) for m in ms]
-    total = int(moff[-1])
-    with _path_lock:
-        _path_mismatches[0] = 0
-
-    def call(lo, hi):
-        n = hi - lo
-        part = np.zeros((len(ms), n, K), dtype=HIT_DTYPE)
-        cnt = np.zeros((len(ms), n), dtype=np.int32)
-        sp = np.zeros(2 * K * n * total, dtype=np.int32)
-        rc = entry_call(lo, hi, part, cnt, sp)
-        if rc == 0:
-            hits[:, lo:hi] = part
-            count[:, lo:hi] = cnt
-            for k, m in enumerate(ms):                      # motif k's block: [read][hit][N_k][2] at 2 K n moff[k]
-                b = 2 * K * n * int(moff[k])
-                spans[k][lo:hi] = sp[b:b + 2 * K * n * m.size].reshape(n, K, m.size, 2)
-            bad = L.sk_last_path_mismatches()
-            with _path_lock:
-                _path_mismatches[0] += max(bad, 0)
-        return rc
-    if R and ms:
-        _over_devices(devices, R, call)
-    return [(hits[k], count[k], spans[k]) for k in range(len(ms))]
-
-
 def motifseq_paths_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
                          scale_hi=1200, devices=None):
     """motifseq_hits_batch plus, per hit, the spans of its warping path: a list, per motif, of
     (hits[R, max_hits], count[R], spans[R, max_hits, N, 2]).  spans[r, h, i] = (a_i, b_i): the filtered samples motif
     point i covers in hit h of read r (expand_path turns them into mlpy's (px, py)); -1 where there is no path."""
-    sig = np.ascontiguousarray(sig, dtype=np.int16)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    R = sig.shape[0]
-    if _too_wide_for_i16(scale_low, scale_hi):
-        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
-        return motifseq_paths_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
-    L = _lib.load()
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-
-    def call(lo, hi, part, cnt, sp):
-        return L.sk_motifseq_paths_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff),
-                                       len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part),
-                                       ptr(cnt), ptr(sp))
-    return _paths_over(devices, R, ms, moff, K, call)
+    return _hits_batch(_PATHS, sig, lens, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_paths_ragged_f64(values, off, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
                               scale_hi=1200, devices=None):
     """motifseq_hits_ragged_f64 plus the spans (see motifseq_paths_batch); int32 values are centi-units."""
-    L = _lib.load()
-    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
-    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
-    entry = L.sk_motifseq_paths_centi if centi else L.sk_motifseq_paths_f64
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    R = off.size - 1
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-
-    def call(lo, hi, part, cnt, sp):
-        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
-                     int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt), ptr(sp))
-    return _paths_over(devices, R, ms, moff, K, call)
+    return _hits_ragged(_PATHS, values, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_paths(reads, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
                    devices=None):
     """motifseq_hits plus the alignment path of every hit: a list, per motif, of
     (hits[nreads, max_hits], count[nreads], spans[nreads, max_hits, N, 2])."""
-    ms = _hits_args(motifs, max_hits, max_dist)[0]
-    ints, arrs, flts = _split_int16(reads)
-    R, K = len(reads), int(max_hits)
-    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32), np.full((R, K, m.size, 2), -1, dtype=np.int32))
-           for m in ms]
-    bad = 0
-    if ints and ms:
-        buf, lens = pack_i16(arrs)
-        for (h, c, s), (hi, ci, si) in zip(res, motifseq_paths_batch(buf, lens, ms, K, max_dist, scale, scale_low,
-                                                                     scale_hi, devices)):
-            h[ints], c[ints], s[ints] = hi, ci, si
-        bad += _path_mismatches[0]
-    if flts and ms:
-        flat, off = pack_f64([reads[i] for i in flts])
-        for (h, c, s), (hf, cf, sf) in zip(res, motifseq_paths_ragged_f64(flat, off, ms, K, max_dist, scale, scale_low,
-                                                                          scale_hi, devices)):
-            h[flts], c[flts], s[flts] = hf, cf, sf
-        bad += _path_mismatches[0]
-    with _path_lock:
-        _path_mismatches[0] = bad
-    return res
+    return _hits_mixed(_PATHS, reads, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def spans_of_path(px, py, n_points):
@@ -1108,38 +1039,6 @@ def last_path_mismatches():
 # ----------------------------------------------------------------------------
 # MotifSeq events: per hit and motif point what the signal did; pooled models
 # ----------------------------------------------------------------------------
-def _events_over(devices, R, ms, moff, K, entry_call):
-    """Runs entry_call(lo, hi, hits_part, count_part, events_part) over the devices; returns per motif
-    (hits[R, K], count[R], events[R, K, N]).  The self-check counters of the shards add up (last_path_mismatches)."""
-    L = _lib.load()
-    hits = np.zeros((len(ms), R, K), dtype=HIT_DTYPE)
-    count = np.zeros((len(ms), R), dtype=np.int32)
-    events = [no_events((R, K, m.size)) for m in ms]
-    total = int(moff[-1])
-    with _path_lock:
-        _path_mismatches[0] = 0
-
-    def call(lo, hi):
-        n = hi - lo
-        part = np.zeros((len(ms), n, K), dtype=HIT_DTYPE)
-        cnt = np.zeros((len(ms), n), dtype=np.int32)
-        ev = np.zeros(K * n * total, dtype=EVENT_DTYPE)
-        rc = entry_call(lo, hi, part, cnt, ev)
-        if rc == 0:
-            hits[:, lo:hi] = part
-            count[:, lo:hi] = cnt
-            for k, m in enumerate(ms):                      # motif k's block: [read][hit][N_k] at K n moff[k]
-                b = K * n * int(moff[k])
-                events[k][lo:hi] = ev[b:b + K * n * m.size].reshape(n, K, m.size)
-            bad = L.sk_last_path_mismatches()
-            with _path_lock:
-                _path_mismatches[0] += max(bad, 0)
-        return rc
-    if R and ms:
-        _over_devices(devices, R, call)
-    return [(hits[k], count[k], events[k]) for k in range(len(ms))]
-
-
 def no_events(shape):
     """An EVENT_DTYPE array of hits without a path: sum = std = cost = NaN, start -1, dwell 0."""
     ev = np.zeros(shape, dtype=EVENT_DTYPE)
@@ -1155,37 +1054,13 @@ def motifseq_events_batch(sig, lens, motifs, max_hits=1, max_dist=float("inf"), 
     samples and w = y[a_i : b_i + 1] (the span motifseq_paths_batch returns), events[r, h, i] (EVENT_DTYPE) holds
     sum = np.sum(w), std = np.std(w), cost = np.sum(np.abs(motif[i] - w)), start = a_i and dwell = b_i - a_i + 1, bit
     for bit as numpy would; sum / dwell is np.mean(w).  No path: NaN, start -1, dwell 0."""
-    sig = np.ascontiguousarray(sig, dtype=np.int16)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    R = sig.shape[0]
-    if _too_wide_for_i16(scale_low, scale_hi):
-        flat, off = pack_f64([sig[r, :lens[r]] for r in range(R)])
-        return motifseq_events_ragged_f64(flat, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
-    L = _lib.load()
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-
-    def call(lo, hi, part, cnt, ev):
-        return L.sk_motifseq_events_i16(ptr(sig[lo:hi]), sig.shape[1], ptr(lens[lo:hi]), hi - lo, ptr(flat), ptr(moff),
-                                        len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), K, md, ptr(part),
-                                        ptr(cnt), ptr(ev))
-    return _events_over(devices, R, ms, moff, K, call)
+    return _hits_batch(_EVENTS, sig, lens, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_events_ragged_f64(values, off, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0,
                                scale_hi=1200, devices=None):
     """motifseq_hits_ragged_f64 plus the events (see motifseq_events_batch); int32 values are centi-units."""
-    L = _lib.load()
-    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
-    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
-    entry = L.sk_motifseq_events_centi if centi else L.sk_motifseq_events_f64
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    R = off.size - 1
-    ms, flat, moff, K, md = _hits_args(motifs, max_hits, max_dist)
-
-    def call(lo, hi, part, cnt, ev):
-        return entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale],
-                     int(scale_low), int(scale_hi), K, md, ptr(part), ptr(cnt), ptr(ev))
-    return _events_over(devices, R, ms, moff, K, call)
+    return _hits_ragged(_EVENTS, values, off, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def motifseq_events(reads, motifs, max_hits=1, max_dist=float("inf"), scale="medmad", scale_low=0, scale_hi=1200,
@@ -1193,26 +1068,7 @@ def motifseq_events(reads, motifs, max_hits=1, max_dist=float("inf"), scale="med
     """motifseq_hits plus the events of every hit: a list, per motif, of
     (hits[nreads, max_hits], count[nreads], events[nreads, max_hits, N]) -- see motifseq_events_batch.  The same read
     kinds as motifseq_paths; spans_of_events gives the spans a paths call would have returned."""
-    ms = _hits_args(motifs, max_hits, max_dist)[0]
-    ints, arrs, flts = _split_int16(reads)
-    R, K = len(reads), int(max_hits)
-    res = [(np.zeros((R, K), dtype=HIT_DTYPE), np.zeros(R, dtype=np.int32), no_events((R, K, m.size))) for m in ms]
-    bad = 0
-    if ints and ms:
-        buf, lens = pack_i16(arrs)
-        for (h, c, e), (hi, ci, ei) in zip(res, motifseq_events_batch(buf, lens, ms, K, max_dist, scale, scale_low,
-                                                                      scale_hi, devices)):
-            h[ints], c[ints], e[ints] = hi, ci, ei
-        bad += _path_mismatches[0]
-    if flts and ms:
-        flat, off = pack_f64([reads[i] for i in flts])
-        for (h, c, e), (hf, cf, ef) in zip(res, motifseq_events_ragged_f64(flat, off, ms, K, max_dist, scale, scale_low,
-                                                                           scale_hi, devices)):
-            h[flts], c[flts], e[flts] = hf, cf, ef
-        bad += _path_mismatches[0]
-    with _path_lock:
-        _path_mismatches[0] = bad
-    return res
+    return _hits_mixed(_EVENTS, reads, motifs, max_hits, max_dist, scale, scale_low, scale_hi, devices)
 
 
 def spans_of_events(events):

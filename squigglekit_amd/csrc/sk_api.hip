@@ -632,27 +632,127 @@ int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nread
                             d_out);
 }
 
+} // extern "C"
+
+namespace {
+
 // ------------------------------------------------------------------ MotifSeq hit lists (sk_hits.hip)
 // Up to K disjoint matches per read and motif instead of the first argmin only (MotifSeq.py:437-439 keeps that one;
 // view_region, :506-513, plots the whole last row they come from).  Reads are prepared once (filter + statistics, the
 // kernels of the default path); per motif, chunks of reads go through the exact pass that stores the last rows
 // (MODE_ROWS; the chained pass beyond 1 024 points) and k_hits_select.  The row buffer (12 B per column) is capped at
 // 2 GiB (SK_HITS_ROW_BYTES) and reused chunk after chunk, motif after motif.
-static int check_hits(int32_t max_hits, double max_dist, const void *out, const void *count)
+//
+// On top of the hit lists a call may return, in any combination:
+//   read background (sk_bg.hip)   the statistics of each read's whole last row, bg [nmotifs][nreads];
+//   alignment paths (sk_path.hip) per hit the spans of its warping path: which columns [a_i, b_i] each motif point i
+//                                 covers (mlpy's subsequence_path, MotifSeq.py:437, as a fixed-size record).  Motif k's
+//                                 block of `spans` begins at 2 * max_hits * nreads * motif_off[k] int32, inside it
+//                                 [read][hit][N_k][2];
+//   events (sk_events.hip)        one sk_event per motif point where the paths have a span: the same layout with one
+//                                 record where the spans have two ints.  Events are made from spans: a call that
+//                                 returns events and no spans keeps its spans in c->pathspans.
+// A call that asks for none of them launches and reserves nothing for them.
+struct hits_out {
+    sk_hit    *out;                 // [nmotifs][nreads][max_hits]
+    int32_t   *count;               // [nmotifs][nreads]
+    sk_bg_rec *bg;
+    int32_t   *spans;
+    sk_event  *events;
+};
+enum { HITS_BG = 1, HITS_SPANS = 2, HITS_EVENTS = 4 };
+struct hits_req {
+    const double  *motifs;          // motif k = motifs[motif_off[k] .. motif_off[k + 1])
+    const int32_t *motif_off;
+    int32_t        nmotifs;
+    int32_t        scale_mode, scale_low, scale_hi, max_hits;
+    double         max_dist;
+    hits_out       to;              // the caller's buffers: device memory for a *_dev_* entry point, else host memory
+    int            want;            // HITS_*: what the entry point promises besides out / count (the rest of `to` is ignored)
+};
+// the request of an entry point from its parameters -- all sixteen name them alike -- and what it adds to the hit lists
+#define HITS_REQ(want, bg, spans, events)                                                                             \
+    hits_req{motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist,                         \
+             {out, count, bg, spans, events}, want}
+
+// after the checks of the input.  Without reads the outputs may be NULL -- bg excepted (squigglekit_hip.h).
+int hits_check(const hits_req &q, int32_t nreads)
 {
-    if (max_hits < 1 || max_hits > 64) return sk_fail(SK_ERR_INVALID, "max_hits %d outside 1..64", max_hits);
-    if (max_dist != max_dist) return sk_fail(SK_ERR_INVALID, "max_dist is NaN");
-    if (!out || !count) return sk_fail(SK_ERR_INVALID, "NULL out/count");
+    const int rc = check_multi(q.motifs, q.motif_off, q.nmotifs, q.scale_mode);
+    if (rc) return rc;
+    if (q.max_hits < 1 || q.max_hits > 64) return sk_fail(SK_ERR_INVALID, "max_hits %d outside 1..64", q.max_hits);
+    if (q.max_dist != q.max_dist) return sk_fail(SK_ERR_INVALID, "max_dist is NaN");
+    if (nreads && (!q.to.out || !q.to.count)) return sk_fail(SK_ERR_INVALID, "NULL out/count");
+    if ((q.want & HITS_BG) && !q.to.bg) return sk_fail(SK_ERR_INVALID, "NULL bg");
+    if (nreads && (q.want & HITS_SPANS) && !q.to.spans) return sk_fail(SK_ERR_INVALID, "NULL spans");
+    if (nreads && (q.want & HITS_EVENTS) && !q.to.events) return sk_fail(SK_ERR_INVALID, "NULL events");
     return SK_OK;
 }
 
-// base: feed, samples (+ samples_raw), stride / off, prep, max_len and nreads of prepared reads.  Motif k's records of
-// read r go to d_out[(k * out_reads + r) * K ..], its count to d_count[k * out_reads + r].  d_bg (optional): the
-// statistics of that read's whole row (k_row_background, sk_bg.hip) go to d_bg[k * out_reads + r].
-static int hits_core(sk_ctx *c, const sk_sdtw_args &base, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                     int32_t K, double max_dist, sk_hit *d_out, int32_t *d_count, int64_t out_reads,
-                     sk_bg_rec *d_bg = nullptr)
+// what a call that makes paths needs before its first launch: the mismatch counter zeroed (sk_path_begin) and its
+// motifs, flat, on the device
+int paths_begin(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs)
 {
+    int rc = sk_path_begin(c);
+    if (rc) return rc;
+    const size_t mb = (size_t)motif_off[nmotifs] * sizeof(double);
+    if ((rc = sk_reserve(c, &c->pathmotif, mb))) return rc;
+    SK_HIP(hipMemcpyAsync(c->pathmotif.p, motifs + motif_off[0], mb, hipMemcpyHostToDevice, c->stream));
+    return SK_OK;
+}
+
+// how every body opens once its input is checked: hits_check, then paths_begin if it applies (also without reads)
+int hits_begin(sk_ctx *c, const hits_req &q, int32_t nreads)
+{
+    const int rc = hits_check(q, nreads);
+    if (rc || !(q.want & (HITS_SPANS | HITS_EVENTS))) return rc;
+    return paths_begin(c, q.motifs, q.motif_off, q.nmotifs);
+}
+
+struct hits_sizes { size_t out, count, bg, spans, events; };      // bytes of a call's outputs
+hits_sizes hits_bytes(const hits_req &q, int32_t nreads)
+{
+    const size_t lists = (size_t)nreads * (size_t)q.nmotifs;
+    const size_t points = (size_t)q.max_hits * (size_t)nreads * (size_t)(q.motif_off[q.nmotifs] - q.motif_off[0]);
+    return {lists * (size_t)q.max_hits * sizeof(sk_hit), lists * sizeof(int32_t), lists * sizeof(sk_bg_rec),
+            points * 2 * sizeof(int32_t), points * sizeof(sk_event)};
+}
+
+// host entry points: room on the device for what the request names (d: where; nullptr for the rest) ...
+int hits_reserve(sk_ctx *c, const hits_req &q, const hits_sizes &z, hits_out *d)
+{
+    const bool bg = q.want & HITS_BG, events = q.want & HITS_EVENTS, spans = events || (q.want & HITS_SPANS);
+    int rc;
+    if ((rc = sk_reserve(c, &c->out, z.out))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, z.count))) return rc;
+    if (bg && (rc = sk_reserve(c, &c->bgrec, z.bg))) return rc;
+    if (spans && (rc = sk_reserve(c, &c->pathspans, z.spans))) return rc;
+    if (events && (rc = sk_reserve(c, &c->events, z.events))) return rc;
+    *d = {(sk_hit *)c->out.p, (int32_t *)c->out2.p, bg ? (sk_bg_rec *)c->bgrec.p : nullptr,
+          spans ? (int32_t *)c->pathspans.p : nullptr, events ? (sk_event *)c->events.p : nullptr};
+    return SK_OK;
+}
+
+// ... and, after the launches, those outputs back to the caller
+int hits_copy_back(sk_ctx *c, const hits_req &q, const hits_sizes &z, const hits_out &d)
+{
+    SK_HIP(hipMemcpyAsync(q.to.out, d.out, z.out, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(q.to.count, d.count, z.count, hipMemcpyDeviceToHost, c->stream));
+    if (q.want & HITS_BG) SK_HIP(hipMemcpyAsync(q.to.bg, d.bg, z.bg, hipMemcpyDeviceToHost, c->stream));
+    if (q.want & HITS_SPANS) SK_HIP(hipMemcpyAsync(q.to.spans, d.spans, z.spans, hipMemcpyDeviceToHost, c->stream));
+    if (q.want & HITS_EVENTS) SK_HIP(hipMemcpyAsync(q.to.events, d.events, z.events, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// One prepared (sub-)batch.  base: feed, samples (+ samples_raw), stride / off, prep, max_len and nreads of prepared
+// reads.  d: the call's outputs on the device, laid out for the out_reads reads of the whole call (bg / spans / events:
+// nullptr = not made; events need spans); read0: the (sub-)batch's first read among them.  Motif k's records of read r
+// go to d.out[(k * out_reads + read0 + r) * K ..], its count and its row's statistics (k_row_background) to
+// [k * out_reads + read0 + r], its spans and events into motif k's block (above) from read read0 + r on.
+int hits_core(sk_ctx *c, const sk_sdtw_args &base, const hits_req &q, const hits_out &d, int64_t out_reads, int64_t read0)
+{
+    const int32_t K = q.max_hits;
     const int64_t row_stride = base.max_len > 0 ? base.max_len : 1;
     const size_t per_read = sizeof(sk_hit) + (size_t)row_stride * (sizeof(double) + sizeof(int32_t));
     size_t budget = (size_t)2 << 30;
@@ -665,478 +765,250 @@ static int hits_core(sk_ctx *c, const sk_sdtw_args &base, const double *motifs, 
     sk_hit *rec = (sk_hit *)c->hitrows.p;
     double *rowD = (double *)(rec + chunk);
     int32_t *rowS = (int32_t *)(rowD + (size_t)chunk * row_stride);
-    for (int32_t k = 0; k < nmotifs; k++) {
+    for (int32_t k = 0; k < q.nmotifs; k++) {
         for (int64_t r0 = 0; r0 < base.nreads; r0 += chunk) {
             sk_sdtw_args a = base;
             a.nreads = (int32_t)(base.nreads - r0 < chunk ? base.nreads - r0 : chunk);
             a.prep = base.prep + r0;
             if (base.feed == SK_FEED_I16) a.samples = (const int16_t *)base.samples + r0 * base.stride;
             else a.off = base.off + r0;
-            a.motif = motifs + motif_off[k]; a.nmotif = motif_off[k + 1] - motif_off[k];
+            a.motif = q.motifs + q.motif_off[k]; a.nmotif = q.motif_off[k + 1] - q.motif_off[k];
             a.out = rec; a.last_row = nullptr; a.force_single = 1; a.accumulate = 0; a.fuse = nullptr;
             if ((rc = sk_launch_sdtw_rows(c, &a, rowD, rowS))) return rc;
-            const int64_t o = (int64_t)k * out_reads + r0;
-            if (d_bg && (rc = sk_launch_row_background(c, rowD, row_stride, rec, a.nreads, d_bg + o))) return rc;
-            if ((rc = sk_launch_hits_select(c, rowD, rowS, row_stride, rec, a.nreads, K, max_dist, d_out + o * K,
-                                            d_count + o))) return rc;
+            const int64_t o = (int64_t)k * out_reads + read0 + r0;
+            if (d.bg && (rc = sk_launch_row_background(c, rowD, row_stride, rec, a.nreads, d.bg + o))) return rc;
+            if ((rc = sk_launch_hits_select(c, rowD, rowS, row_stride, rec, a.nreads, K, q.max_dist, d.out + o * K,
+                                            d.count + o))) return rc;
         }
     }
     c->retry_dev = false;                               // (no screening counters: finish_dtw_host reads none)
+    c->ev_valid = true;
+    for (int32_t k = 0; d.spans && k < q.nmotifs; k++) {
+        const int64_t m0 = q.motif_off[k] - q.motif_off[0], N = q.motif_off[k + 1] - q.motif_off[k];
+        const int64_t at = (int64_t)K * out_reads * m0 + read0 * K * N;      // in motif points
+        sk_path_args p;
+        p.feed = base.feed; p.samples = base.samples; p.samples_raw = base.samples_raw; p.stride = base.stride;
+        p.off = base.off; p.prep = base.prep; p.nreads = base.nreads; p.max_len = base.max_len;
+        p.d_motif = (const double *)c->pathmotif.p + m0; p.nmotif = (int32_t)N;
+        p.hits = d.out + ((int64_t)k * out_reads + read0) * K; p.K = K;
+        p.spans = d.spans + 2 * at;
+        if ((rc = sk_launch_paths(c, &p))) return rc;
+        if (d.events && (rc = sk_launch_events(c, &p, d.events + at))) return rc;
+    }
     return SK_OK;
 }
 
-// int16 rows, device resident: filter + statistics (the kernels of the default path), then hits_core
-static int hits_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                        int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                        int32_t scale_mode, int32_t scale_low, int32_t scale_hi, int32_t K, double max_dist,
-                        sk_hit *d_out, int32_t *d_count, int64_t out_reads, sk_bg_rec *d_bg = nullptr)
+// Reads [read0, read0 + nr) of a call on int16 rows, on the device: filter + statistics (the kernels of the default path)
+// into their rows of c->comp / c->prep, then the core.
+int hits_rows_i16(sk_ctx *c, const hits_req &q, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr,
+                  const hits_out &d, int64_t out_reads, int64_t read0)
 {
+    int16_t *d_comp = (int16_t *)c->comp.p + (size_t)read0 * (size_t)stride;
+    sk_prep *d_prep = (sk_prep *)c->prep.p + read0;
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    int rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nreads, scale_low, scale_hi,
-                                scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp, d_prep,
-                                nullptr, 0);
+    const int rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nr, q.scale_low, q.scale_hi,
+                                      q.scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp,
+                                      d_prep, nullptr, 0);
     if (rc) return rc;
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
     sk_sdtw_args a;
-    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nreads;
+    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nr;
     a.max_len = stride;
-    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, K, max_dist, d_out, d_count, out_reads, d_bg))) return rc;
-    c->ev_valid = true;
-    return SK_OK;
+    return hits_core(c, a, q, d, out_reads, read0);
 }
 
-// Read background (sk_bg.hip): every hit-list entry point has a twin that also returns the statistics of each read's
-// whole last row.  The twins share the bodies below: want_bg says which one is running, and a hit-list call (want_bg
-// false) launches and reserves nothing more than it did.
-static int check_bg(bool want_bg, const void *bg)
-{
-    if (want_bg && !bg) return sk_fail(SK_ERR_INVALID, "NULL bg");
-    return SK_OK;
-}
-
-// device-resident form: d_out is [nmotifs][nreads][max_hits], d_count [nmotifs][nreads], d_bg [nmotifs][nreads]
-static int hits_dev_i16_entry(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                              int32_t *d_count, bool want_bg, sk_bg_rec *d_bg)
+// The three bodies, one per input kind.  Device-resident int16 rows: the outputs are the caller's device buffers.
+int hits_dev_i16(hits_req q, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads)
 {
     SK_ENTER(c);
-    int rc = check_i16(d_sig, stride, d_len, nreads);
-    if (rc) return rc;
-    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
-    if ((rc = check_hits(max_hits, max_dist, nreads ? d_out : (void *)1, nreads ? d_count : (void *)1))) return rc;
-    if ((rc = check_bg(want_bg, d_bg))) return rc;
+    int rc;
+    if ((rc = check_i16(d_sig, stride, d_len, nreads)) || (rc = hits_begin(c, q, nreads))) return rc;
     if (nreads == 0) return SK_OK;
-    clamp_limits(&scale_low, &scale_hi);
+    clamp_limits(&q.scale_low, &q.scale_hi);
     redo_forget(c);
     if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    return hits_dev_i16(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
-                        nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads,
-                        want_bg ? d_bg : nullptr);
-}
-int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                             int32_t *d_count)
-{
-    return hits_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
-                              max_hits, max_dist, d_out, d_count, false, nullptr);
-}
-int sk_motifseq_background_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                                   const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                                   int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                                   int32_t *d_count, sk_bg_rec *d_bg)
-{
-    return hits_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
-                              max_hits, max_dist, d_out, d_count, true, d_bg);
+    hits_out d = {q.to.out, q.to.count, (q.want & HITS_BG) ? q.to.bg : nullptr, (q.want & HITS_SPANS) ? q.to.spans : nullptr,
+                  (q.want & HITS_EVENTS) ? q.to.events : nullptr};
+    if (d.events && !d.spans) {
+        if ((rc = sk_reserve(c, &c->pathspans, hits_bytes(q, nreads).spans))) return rc;
+        d.spans = (int32_t *)c->pathspans.p;
+    }
+    return hits_rows_i16(c, q, d_sig, stride, d_len, nreads, d, nreads, 0);
 }
 
-// host buffers: out is [nmotifs][nreads][max_hits], count [nmotifs][nreads], bg [nmotifs][nreads]; sub-batches as
-// sk_motifseq_multi_batch_i16
-static int hits_i16_entry(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                          int32_t *count, bool want_bg, sk_bg_rec *bg)
+// int16 rows in host memory; sub-batches as sk_motifseq_multi_batch_i16.  Every sub-batch writes its reads' places in
+// the outputs of the whole call, so these come back in one piece.
+int hits_host_i16(hits_req q, const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads)
 {
     SK_ENTER(c);
-    int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
-    if ((rc = check_len_host(len, nreads, stride))) return rc;
-    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
-    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
-    if ((rc = check_bg(want_bg, bg))) return rc;
+    int rc;
+    if ((rc = check_i16(sig, stride, len, nreads)) || (rc = check_len_host(len, nreads, stride)) ||
+        (rc = hits_begin(c, q, nreads))) return rc;
     if (nreads == 0) return SK_OK;
-    clamp_limits(&scale_low, &scale_hi);
+    clamp_limits(&q.scale_low, &q.scale_hi);
+    const hits_sizes z = hits_bytes(q, nreads);
     const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
-    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
-    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
-    const size_t bb = (size_t)nreads * (size_t)nmotifs * sizeof(sk_bg_rec);
-    if (want_bg && (rc = sk_reserve(c, &c->bgrec, bb))) return rc;
+    hits_out d;
     if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
     if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
     if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
-    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
+    if ((rc = hits_reserve(c, q, z, &d))) return rc;
     redo_forget(c);
     rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
                      [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
-                         return hits_dev_i16(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
-                                             (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
-                                             scale_hi, max_hits, max_dist, (sk_hit *)c->out.p + (size_t)r0 * max_hits,
-                                             (int32_t *)c->out2.p + r0, nreads,
-                                             want_bg ? (sk_bg_rec *)c->bgrec.p + r0 : nullptr);
+                         return hits_rows_i16(c, q, d_sig, stride, d_len, nr, d, nreads, r0);
                      });
     if (rc) return rc;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
-    if (want_bg) SK_HIP(hipMemcpyAsync(bg, c->bgrec.p, bb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    return SK_OK;
+    return hits_copy_back(c, q, z, d);
+}
+
+// ragged float64 reads (pA TSV / BLOW5 in pA): read r = sig[off[r] .. off[r+1]).  centi: int32 centi-units, made
+// float64 on the device (stage_ragged_f64)
+int hits_ragged(hits_req q, const void *sig, bool centi, const int64_t *off, int32_t nreads)
+{
+    SK_ENTER(c);
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = hits_begin(c, q, nreads);
+    if (rc) return rc;
+    if (nreads == 0) return SK_OK;
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
+    const hits_sizes z = hits_bytes(q, nreads);
+    hits_out d;
+    if ((rc = hits_reserve(c, q, z, &d))) return rc;
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    const double *d_sig = (const double *)c->sig.p;
+    const int64_t *d_off = (const int64_t *)c->off.p;
+    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, q.scale_mode, q.scale_low, q.scale_hi))) return rc;
+    sk_sdtw_args a;
+    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
+    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
+    if ((rc = hits_core(c, a, q, d, nreads, 0))) return rc;
+    return hits_copy_back(c, q, z, d);
+}
+
+} // namespace
+
+extern "C" {
+
+// The entry points: hit lists, then their twins with the read background, the alignment paths, the events.  *_dev_i16:
+// every buffer is device memory.
+int sk_motifseq_hits_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                             int32_t *count)
+{
+    return hits_dev_i16(HITS_REQ(0, nullptr, nullptr, nullptr), d_sig, stride, d_len, nreads);
 }
 int sk_motifseq_hits_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                          int32_t *count)
 {
-    return hits_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                          max_dist, out, count, false, nullptr);
+    return hits_host_i16(HITS_REQ(0, nullptr, nullptr, nullptr), sig, stride, len, nreads);
 }
-int sk_motifseq_background_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                               int32_t *count, sk_bg_rec *bg)
-{
-    return hits_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                          max_dist, out, count, true, bg);
-}
-
-// ragged float64 reads (pA TSV / BLOW5 in pA): read r = sig[off[r] .. off[r+1]); out / count as sk_motifseq_hits_i16.
-// centi: int32 centi-units, made float64 on the device (stage_ragged_f64)
-static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
-                       const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                       int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                       int32_t *count, bool want_bg = false, sk_bg_rec *bg = nullptr);
 int sk_motifseq_hits_f64(const double *sig, const int64_t *off, int32_t nreads,
                          const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                          int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                          int32_t *count)
 {
-    return hits_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                       max_dist, out, count);
+    return hits_ragged(HITS_REQ(0, nullptr, nullptr, nullptr), sig, false, off, nreads);
 }
 int sk_motifseq_hits_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
                            const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                            int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                            int32_t *count)
 {
-    return hits_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                       max_dist, out, count);
+    return hits_ragged(HITS_REQ(0, nullptr, nullptr, nullptr), centi, true, off, nreads);
+}
+
+int sk_motifseq_background_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                                   const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                                   int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                                   int32_t *count, sk_bg_rec *bg)
+{
+    return hits_dev_i16(HITS_REQ(HITS_BG, bg, nullptr, nullptr), d_sig, stride, d_len, nreads);
+}
+int sk_motifseq_background_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                               int32_t *count, sk_bg_rec *bg)
+{
+    return hits_host_i16(HITS_REQ(HITS_BG, bg, nullptr, nullptr), sig, stride, len, nreads);
 }
 int sk_motifseq_background_f64(const double *sig, const int64_t *off, int32_t nreads,
                                const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                                int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                                int32_t *count, sk_bg_rec *bg)
 {
-    return hits_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                       max_dist, out, count, true, bg);
+    return hits_ragged(HITS_REQ(HITS_BG, bg, nullptr, nullptr), sig, false, off, nreads);
 }
 int sk_motifseq_background_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
                                  const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                                  int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                                  int32_t *count, sk_bg_rec *bg)
 {
-    return hits_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                       max_dist, out, count, true, bg);
-}
-static int hits_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
-                       const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                       int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                       int32_t *count, bool want_bg, sk_bg_rec *bg)
-{
-    SK_ENTER(c);
-    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
-    int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
-    if (rc) return rc;
-    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
-    if ((rc = check_bg(want_bg, bg))) return rc;
-    if (nreads == 0) return SK_OK;
-    int64_t total, maxlen;
-    if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
-    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
-    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
-    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
-    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
-    const size_t bb = (size_t)nreads * (size_t)nmotifs * sizeof(sk_bg_rec);
-    if (want_bg && (rc = sk_reserve(c, &c->bgrec, bb))) return rc;
-    if ((rc = redo_begin(c, nreads, 1))) return rc;
-    const double *d_sig = (const double *)c->sig.p;
-    const int64_t *d_off = (const int64_t *)c->off.p;
-    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, scale_mode, scale_low, scale_hi))) return rc;
-    sk_sdtw_args a;
-    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
-    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
-    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, max_hits, max_dist, (sk_hit *)c->out.p, (int32_t *)c->out2.p,
-                        nreads, want_bg ? (sk_bg_rec *)c->bgrec.p : nullptr))) return rc;
-    c->ev_valid = true;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
-    if (want_bg) SK_HIP(hipMemcpyAsync(bg, c->bgrec.p, bb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    return SK_OK;
+    return hits_ragged(HITS_REQ(HITS_BG, bg, nullptr, nullptr), centi, true, off, nreads);
 }
 
-// ------------------------------------------------------------------ MotifSeq alignment paths (sk_path.hip)
-// The hit list, then per hit the spans of its warping path: which columns [a_i, b_i] each motif point i covers
-// (mlpy's subsequence_path, MotifSeq.py:437, as a fixed-size record).  Layout of `spans`: motif k's block begins at
-// 2 * max_hits * nreads * motif_off[k] int32, inside it [read][hit][N_k][2].  hits / count are the hit-list call's.
-static int paths_begin(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs, const void *spans,
-                       const char *what = "spans")
-{
-    if (!spans) return sk_fail(SK_ERR_INVALID, "NULL %s", what);
-    int rc = sk_path_begin(c);
-    if (rc) return rc;
-    const size_t mb = (size_t)motif_off[nmotifs] * sizeof(double);
-    if ((rc = sk_reserve(c, &c->pathmotif, mb))) return rc;
-    SK_HIP(hipMemcpyAsync(c->pathmotif.p, motifs + motif_off[0], mb, hipMemcpyHostToDevice, c->stream));
-    return SK_OK;
-}
-
-// base: as hits_core's; d_out: the records hits_core left ([k * out_reads + r][K], r relative to this (sub-)batch);
-// read0: the (sub-)batch's first read within the out_reads reads of d_spans.  d_events (optional, sk_events.hip): the
-// events of those spans, in the same layout with one record where the spans have two ints.
-static int paths_core(sk_ctx *c, const sk_sdtw_args &base, const int32_t *motif_off, int32_t nmotifs, int32_t K,
-                      const sk_hit *d_out, int64_t out_reads, int32_t *d_spans, int64_t read0, sk_event *d_events = nullptr)
-{
-    for (int32_t k = 0; k < nmotifs; k++) {
-        const int64_t m0 = motif_off[k] - motif_off[0], N = motif_off[k + 1] - motif_off[k];
-        sk_path_args p;
-        p.feed = base.feed; p.samples = base.samples; p.samples_raw = base.samples_raw; p.stride = base.stride;
-        p.off = base.off; p.prep = base.prep; p.nreads = base.nreads; p.max_len = base.max_len;
-        p.d_motif = (const double *)c->pathmotif.p + m0; p.nmotif = (int32_t)N;
-        p.hits = d_out + (int64_t)k * out_reads * K; p.K = K;
-        p.spans = d_spans + 2 * (int64_t)K * out_reads * m0 + read0 * K * N * 2;
-        int rc = sk_launch_paths(c, &p);
-        if (rc) return rc;
-        if (d_events && (rc = sk_launch_events(c, &p, d_events + (int64_t)K * out_reads * m0 + read0 * K * N))) return rc;
-    }
-    return SK_OK;
-}
-
-static size_t events_bytes(int32_t nreads, int32_t max_hits, const int32_t *motif_off, int32_t nmotifs)
-{
-    return (size_t)max_hits * (size_t)nreads * (size_t)(motif_off[nmotifs] - motif_off[0]) * sizeof(sk_event);
-}
-
-static size_t spans_bytes(int32_t nreads, int32_t max_hits, const int32_t *motif_off, int32_t nmotifs)
-{
-    return (size_t)2 * (size_t)max_hits * (size_t)nreads * (size_t)(motif_off[nmotifs] - motif_off[0]) * sizeof(int32_t);
-}
-
-static int paths_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                         int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                         int32_t scale_mode, int32_t scale_low, int32_t scale_hi, int32_t K, double max_dist,
-                         sk_hit *d_out, int32_t *d_count, int64_t out_reads, int32_t *d_spans, int64_t read0,
-                         sk_event *d_events = nullptr)
-{
-    int rc = hits_dev_i16(c, d_sig, stride, d_len, nreads, d_comp, d_prep, motifs, motif_off, nmotifs, scale_mode, scale_low,
-                          scale_hi, K, max_dist, d_out, d_count, out_reads);
-    if (rc) return rc;
-    sk_sdtw_args a;
-    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nreads;
-    a.max_len = stride;
-    return paths_core(c, a, motif_off, nmotifs, K, d_out, out_reads, d_spans, read0, d_events);
-}
-
-// Events (sk_events.hip): every paths entry point has a twin that returns one sk_event per motif point where the paths
-// call returns a span.  The twins share the bodies below: want_events says which one is running; an events call keeps
-// its spans in c->pathspans and a paths call launches and reserves nothing more than it did.
-//
-// device-resident form: d_out / d_count as sk_motifseq_hits_dev_i16, d_spans / d_events in the layout above
-static int paths_dev_i16_entry(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                               int32_t *d_count, int32_t *d_spans, bool want_events, sk_event *d_events)
-{
-    SK_ENTER(c);
-    int rc = check_i16(d_sig, stride, d_len, nreads);
-    if (rc) return rc;
-    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
-    if ((rc = check_hits(max_hits, max_dist, nreads ? d_out : (void *)1, nreads ? d_count : (void *)1))) return rc;
-    const void *res = want_events ? (const void *)d_events : (const void *)d_spans;
-    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? res : (void *)1, want_events ? "events" : "spans"))) return rc;
-    if (nreads == 0) return SK_OK;
-    clamp_limits(&scale_low, &scale_hi);
-    redo_forget(c);
-    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    if (want_events) {
-        if ((rc = sk_reserve(c, &c->pathspans, spans_bytes(nreads, max_hits, motif_off, nmotifs)))) return rc;
-        d_spans = (int32_t *)c->pathspans.p;
-    }
-    return paths_dev_i16(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
-                         nmotifs, scale_mode, scale_low, scale_hi, max_hits, max_dist, d_out, d_count, nreads, d_spans, 0,
-                         want_events ? d_events : nullptr);
-}
 int sk_motifseq_paths_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                              int32_t *d_count, int32_t *d_spans)
+                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                              int32_t *count, int32_t *spans)
 {
-    return paths_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
-                               max_hits, max_dist, d_out, d_count, d_spans, false, nullptr);
-}
-int sk_motifseq_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *d_out,
-                               int32_t *d_count, sk_event *d_events)
-{
-    return paths_dev_i16_entry(d_sig, stride, d_len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi,
-                               max_hits, max_dist, d_out, d_count, nullptr, true, d_events);
-}
-
-// host buffers; sub-batches as sk_motifseq_hits_i16
-static int paths_i16_entry(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                           int32_t *count, int32_t *spans, bool want_events, sk_event *events)
-{
-    SK_ENTER(c);
-    int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
-    if ((rc = check_len_host(len, nreads, stride))) return rc;
-    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
-    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
-    const void *res = want_events ? (const void *)events : (const void *)spans;
-    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? res : (void *)1, want_events ? "events" : "spans"))) return rc;
-    if (nreads == 0) return SK_OK;
-    clamp_limits(&scale_low, &scale_hi);
-    const size_t eb = events_bytes(nreads, max_hits, motif_off, nmotifs);
-    if (want_events && (rc = sk_reserve(c, &c->events, eb))) return rc;
-    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
-    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
-    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
-    const size_t pb = spans_bytes(nreads, max_hits, motif_off, nmotifs);
-    if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
-    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
-    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
-    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
-    if ((rc = sk_reserve(c, &c->pathspans, pb))) return rc;
-    redo_forget(c);
-    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
-                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
-                         return paths_dev_i16(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
-                                              (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
-                                              scale_hi, max_hits, max_dist, (sk_hit *)c->out.p + (size_t)r0 * max_hits,
-                                              (int32_t *)c->out2.p + r0, nreads, (int32_t *)c->pathspans.p, r0,
-                                              want_events ? (sk_event *)c->events.p : nullptr);
-                     });
-    if (rc) return rc;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
-    if (want_events) SK_HIP(hipMemcpyAsync(events, c->events.p, eb, hipMemcpyDeviceToHost, c->stream));
-    else SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    return SK_OK;
+    return hits_dev_i16(HITS_REQ(HITS_SPANS, nullptr, spans, nullptr), d_sig, stride, d_len, nreads);
 }
 int sk_motifseq_paths_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                           int32_t *count, int32_t *spans)
 {
-    return paths_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                           max_dist, out, count, spans, false, nullptr);
+    return hits_host_i16(HITS_REQ(HITS_SPANS, nullptr, spans, nullptr), sig, stride, len, nreads);
 }
-int sk_motifseq_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                           int32_t *count, sk_event *events)
-{
-    return paths_i16_entry(sig, stride, len, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                           max_dist, out, count, nullptr, true, events);
-}
-
-// ragged float64 / centi reads, as sk_motifseq_hits_f64 / _centi
-static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
-                        const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                        int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                        int32_t *count, int32_t *spans, bool want_events = false, sk_event *events = nullptr);
 int sk_motifseq_paths_f64(const double *sig, const int64_t *off, int32_t nreads,
                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                           int32_t *count, int32_t *spans)
 {
-    return paths_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                        max_dist, out, count, spans);
+    return hits_ragged(HITS_REQ(HITS_SPANS, nullptr, spans, nullptr), sig, false, off, nreads);
 }
 int sk_motifseq_paths_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
                             const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                             int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                             int32_t *count, int32_t *spans)
 {
-    return paths_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                        max_dist, out, count, spans);
+    return hits_ragged(HITS_REQ(HITS_SPANS, nullptr, spans, nullptr), centi, true, off, nreads);
+}
+
+int sk_motifseq_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                               const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                               int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                               int32_t *count, sk_event *events)
+{
+    return hits_dev_i16(HITS_REQ(HITS_EVENTS, nullptr, nullptr, events), d_sig, stride, d_len, nreads);
+}
+int sk_motifseq_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                           const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
+                           int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
+                           int32_t *count, sk_event *events)
+{
+    return hits_host_i16(HITS_REQ(HITS_EVENTS, nullptr, nullptr, events), sig, stride, len, nreads);
 }
 int sk_motifseq_events_f64(const double *sig, const int64_t *off, int32_t nreads,
                            const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                            int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                            int32_t *count, sk_event *events)
 {
-    return paths_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                        max_dist, out, count, nullptr, true, events);
+    return hits_ragged(HITS_REQ(HITS_EVENTS, nullptr, nullptr, events), sig, false, off, nreads);
 }
 int sk_motifseq_events_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
                              const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
                              int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
                              int32_t *count, sk_event *events)
 {
-    return paths_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, max_hits,
-                        max_dist, out, count, nullptr, true, events);
-}
-static int paths_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
-                        const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode,
-                        int32_t scale_low, int32_t scale_hi, int32_t max_hits, double max_dist, sk_hit *out,
-                        int32_t *count, int32_t *spans, bool want_events, sk_event *events)
-{
-    SK_ENTER(c);
-    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
-    int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
-    if (rc) return rc;
-    if ((rc = check_hits(max_hits, max_dist, nreads ? out : (void *)1, nreads ? count : (void *)1))) return rc;
-    const void *res = want_events ? (const void *)events : (const void *)spans;
-    if ((rc = paths_begin(c, motifs, motif_off, nmotifs, nreads ? res : (void *)1, want_events ? "events" : "spans"))) return rc;
-    if (nreads == 0) return SK_OK;
-    const size_t eb = events_bytes(nreads, max_hits, motif_off, nmotifs);
-    if (want_events && (rc = sk_reserve(c, &c->events, eb))) return rc;
-    int64_t total, maxlen;
-    if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
-    const size_t ob = (size_t)nreads * (size_t)nmotifs * (size_t)max_hits * sizeof(sk_hit);
-    const size_t cb = (size_t)nreads * (size_t)nmotifs * sizeof(int32_t);
-    const size_t pb = spans_bytes(nreads, max_hits, motif_off, nmotifs);
-    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
-    if ((rc = sk_reserve(c, &c->out2, cb))) return rc;
-    if ((rc = sk_reserve(c, &c->pathspans, pb))) return rc;
-    if ((rc = redo_begin(c, nreads, 1))) return rc;
-    const double *d_sig = (const double *)c->sig.p;
-    const int64_t *d_off = (const int64_t *)c->off.p;
-    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, scale_mode, scale_low, scale_hi))) return rc;
-    sk_sdtw_args a;
-    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
-    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
-    if ((rc = hits_core(c, a, motifs, motif_off, nmotifs, max_hits, max_dist, (sk_hit *)c->out.p, (int32_t *)c->out2.p,
-                        nreads))) return rc;
-    if ((rc = paths_core(c, a, motif_off, nmotifs, max_hits, (const sk_hit *)c->out.p, nreads, (int32_t *)c->pathspans.p,
-                         0, want_events ? (sk_event *)c->events.p : nullptr))) return rc;
-    c->ev_valid = true;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(count, c->out2.p, cb, hipMemcpyDeviceToHost, c->stream));
-    if (want_events) SK_HIP(hipMemcpyAsync(events, c->events.p, eb, hipMemcpyDeviceToHost, c->stream));
-    else SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, pb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    return SK_OK;
+    return hits_ragged(HITS_REQ(HITS_EVENTS, nullptr, nullptr, events), centi, true, off, nreads);
 }
 
 // ------------------------------------------------------------------ pooled events (sk_events.hip)
@@ -1277,7 +1149,8 @@ int sk_dtw_subsequence_path(const double *x, int32_t nx, const double *y, int32_
     SK_ENTER(c);
     if (!x || !y || nx <= 0 || ny <= 0) return sk_fail(SK_ERR_INVALID, "empty x or y");
     const int32_t moff[2] = {0, nx};
-    int rc = paths_begin(c, x, moff, 1, spans);
+    if (!spans) return sk_fail(SK_ERR_INVALID, "NULL spans");
+    int rc = paths_begin(c, x, moff, 1);
     if (rc) return rc;
     if ((rc = sk_reserve(c, &c->sig, (size_t)ny * sizeof(double)))) return rc;
     if ((rc = sk_reserve(c, &c->off, 2 * sizeof(int64_t)))) return rc;
@@ -1292,7 +1165,11 @@ int sk_dtw_subsequence_path(const double *x, int32_t nx, const double *y, int32_
     a.prep = nullptr; a.nreads = 1; a.motif = x; a.nmotif = nx; a.out = (sk_hit *)c->out.p;
     a.last_row = nullptr; a.max_len = ny; a.force_single = 1;
     if ((rc = sk_launch_sdtw(c, &a))) return rc;
-    if ((rc = paths_core(c, a, moff, 1, 1, (const sk_hit *)c->out.p, 1, (int32_t *)c->pathspans.p, 0))) return rc;
+    sk_path_args p;
+    p.feed = a.feed; p.samples = a.samples; p.off = a.off; p.nreads = 1; p.max_len = ny;
+    p.d_motif = (const double *)c->pathmotif.p; p.nmotif = nx; p.hits = (const sk_hit *)c->out.p; p.K = 1;
+    p.spans = (int32_t *)c->pathspans.p;
+    if ((rc = sk_launch_paths(c, &p))) return rc;
     sk_hit h;
     SK_HIP(hipMemcpyAsync(&h, c->out.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     SK_HIP(hipMemcpyAsync(spans, c->pathspans.p, (size_t)nx * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

@@ -88,7 +88,8 @@ struct sk_ctx {
     sk_buf hitrows;   // hit lists: the last rows of a chunk of reads (cost f64, start i32) and their records
     sk_buf bgrec;     // read background: the sk_bg_rec [nmotifs][nreads] of the host entry points
     sk_buf pathcnt;   // alignment paths: [0] = hits of the call that failed the self-check (sk_last_path_mismatches)
-    bool   path_valid = false;   // ... the last MotifSeq call was a paths call (the counter is that call's)
+    bool   path_valid = false;   // ... set by the first paths / events call (sk_path_begin) and never cleared: the counter is
+                                 // the last such call's, also after a later call that makes no paths
     sk_buf pathlist;  // alignment paths: [0] = count, [2 ..] = hits of a launch left to the scratch tier
     sk_buf pathscratch;   // alignment paths: the scratch tier's slabs (direction words + stripe boundary row per wavefront)
     sk_buf pathmotif; // alignment paths: the motifs of the call, flat (device)

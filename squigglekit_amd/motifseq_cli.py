@@ -206,36 +206,40 @@ class _Batcher:
         # --region / --panel: every read goes through the per-read queue (add / flush), --batch reads per GPU call
         self.queued = args.region is not None or args.panel
 
-    def search(self, fn_hits, fn_multi, fn_paths, fn_background, fn_events, *args):
-        """The GPU call of one batch: (what of_read / table take, spans per motif or None, background records per motif
-        or None, events per motif or None).  --paths takes the paths call -- hit lists plus spans -- and --background the
-        background call -- hit lists plus each read's row statistics; without --hits their rank-1 records stand in for
-        the default path's (the same records bit for bit).  --pool takes the events call, whose records also give the
-        spans of --paths."""
+    def search(self, route, *args):
+        """The GPU call of one batch through api.motifseq_{multi,hits,paths,background,events}<route> (route: "" per read,
+        "_batch" packed int16 rows, "_ragged_f64" ragged values; looked up when called): (what of_read / table take, spans
+        per motif or None, background records per motif or None, events per motif or None).  --paths takes the paths call
+        -- hit lists plus spans -- and --background the background call -- hit lists plus each read's row statistics;
+        without --hits their rank-1 records stand in for the default path's (the same records bit for bit).  --pool takes
+        the events call, whose records also give the spans of --paths."""
         a = self.args
         tail = (a.scale, a.scale_low, a.scale_hi)
+
+        def fn(family):
+            return getattr(api, "motifseq_" + family + route)
         hits = spans = bgs = evs = None
         if a.background is not None:
-            res = fn_background(*args, a.hits or 1, float("inf"), *tail)
+            res = fn("background")(*args, a.hits or 1, float("inf"), *tail)
             hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
             bgs = [b for _, _, b in res]
         if a.pool is not None:
             # (with --background this is a second search of the batch: no entry point returns row statistics and events
             # together yet.  Both calls give the same hit lists bit for bit; the events call's are the ones printed.)
-            res = fn_events(*args, a.hits or 1, float("inf"), *tail)
+            res = fn("events")(*args, a.hits or 1, float("inf"), *tail)
             hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
             evs = [ev for _, _, ev in res]
             if a.paths is not None:
                 spans = [api.spans_of_events(ev) for ev in evs]
         elif a.paths is not None:
-            res = fn_paths(*args, a.hits or 1, float("inf"), *tail)
+            res = fn("paths")(*args, a.hits or 1, float("inf"), *tail)
             hits = [(h, c) for h, c, _ in res] if a.hits is not None else [h[:, 0] for h, _, _ in res]
             spans = [sp for _, _, sp in res]
         if hits is not None:
             return hits, spans, bgs, evs
         if a.hits is not None:
-            return fn_hits(*args, a.hits, float("inf"), *tail), None, None, None
-        return fn_multi(*args, *tail), None, None, None
+            return fn("hits")(*args, a.hits, float("inf"), *tail), None, None, None
+        return fn("multi")(*args, *tail), None, None, None
 
     def pool_table(self, path):
         """--pool: one pool_events call per model over the events of its printed hits, one line per motif point."""
@@ -308,8 +312,7 @@ class _Batcher:
         if sigs:
             _STATS[0].batch(len(sigs))
         if sigs or a.hits is not None:
-            hits, spans, bgs, evs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
-                                                api.motifseq_background, api.motifseq_events, sigs, motifs)
+            hits, spans, bgs, evs = self.search("", sigs, motifs)
         else:
             hits, spans, bgs, evs = [[] for _ in self.order], None, None, None
         slot = {i: k for k, i in enumerate(live)}
@@ -373,8 +376,7 @@ class _Batcher:
         bgs = evs = None
         if a.hits is not None or self.per_line:
             wins, frm = self.windows(sigs, region)
-            hits, spans, bgs, evs = self.search(api.motifseq_hits, api.motifseq_multi, api.motifseq_paths,
-                                                api.motifseq_background, api.motifseq_events, wins, motifs)
+            hits, spans, bgs, evs = self.search("", wins, motifs)
         else:
             _, frm, hits = api.motifseq_panel(sigs, motifs, mm, ms, region, None, a.scale, a.scale_low, a.scale_hi,
                                               records=True)
@@ -588,8 +590,7 @@ class _Batcher:
         def call():
             _mark("GPU call starts")
             try:
-                return self.search(api.motifseq_hits_batch, api.motifseq_multi_batch, api.motifseq_paths_batch,
-                                   api.motifseq_background_batch, api.motifseq_events_batch, rows, nsamp, motifs)
+                return self.search("_batch", rows, nsamp, motifs)
             finally:
                 _mark("GPU call ends")
         job = self._worker.submit(call)
@@ -609,9 +610,7 @@ class _Batcher:
             from concurrent.futures import ThreadPoolExecutor
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d float64 reads to the GPU worker" % fb.n)
-        job = self._worker.submit(self.search, api.motifseq_hits_ragged_f64, api.motifseq_multi_ragged_f64,
-                                  api.motifseq_paths_ragged_f64, api.motifseq_background_ragged_f64,
-                                  api.motifseq_events_ragged_f64, fb.batch_values(), fb.off, motifs)
+        job = self._worker.submit(self.search, "_ragged_f64", fb.batch_values(), fb.off, motifs)
         prev, self._pending = self._pending, (job, fb.n, ("span", fb.buf, fb.spans("name")), ("span", fb.buf, fb.spans("id")),
                                               lambda i, b=fb: b.text("name", i), lambda i, b=fb: b.text("id", i),
                                               lambda i, b=fb: b.values[b.off[i]:b.off[i + 1]])

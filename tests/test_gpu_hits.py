@@ -111,6 +111,39 @@ def test_long_read_and_many_row_chunks(gpu, ora, monkeypatch):
     same(many[0], reference_hits(ora, [sig[r, :lens[r]] for r in range(9)], m2, 5), "chunks")
 
 
+def test_sub_batched_call_matches_one_sub_batch(gpu, monkeypatch):
+    """The host int16 route of the four families over three sub-batches: the only place where a sub-batch's first read,
+    the whole call's read count and the per-motif block offsets all differ.  Same bytes as one sub-batch."""
+    from squigglekit_amd import api, synth
+    motifs = [synth.synthetic_motif(5, seed=1), synth.synthetic_motif(8, seed=2)]
+    R, M = 9000, 128
+    sig = synth.squiggle_batch(R, M, 424, motif=motifs[1])
+    lens = np.full(R, M, dtype=np.int32)
+    lens[::11] = 70
+    fns = (api.motifseq_hits_batch, api.motifseq_background_batch, api.motifseq_paths_batch, api.motifseq_events_batch)
+
+    def all_four():
+        res = []
+        for fn in fns:
+            res.append(fn(sig, lens, motifs, 2))
+            if fn in fns[2:]:
+                assert api.last_path_mismatches() == 0, fn.__name__
+        return res
+    one = all_four()
+    monkeypatch.setenv("SK_INGEST_MB", "1")                              # 4 096 reads a sub-batch at least: 3 sub-batches
+    got = all_four()
+    for fn, g, o in zip(fns, got, one):
+        assert len(g) == len(o) == 2 and all(len(gk) == len(ok) == (2 if fn is fns[0] else 3) for gk, ok in zip(g, o))
+        assert all(a.tobytes() == b.tobytes() and a.shape == b.shape for gk, ok in zip(g, o) for a, b in zip(gk, ok)), \
+            fn.__name__
+    for k in range(2):
+        assert got[2][k][2].shape == (R, 2, motifs[k].size, 2) and got[3][k][2].shape == (R, 2, motifs[k].size)
+        assert np.array_equal(api.spans_of_events(got[3][k][2]), got[2][k][2]), k
+        for g in got[1:]:
+            assert g[k][0].tobytes() == got[0][k][0].tobytes() and np.array_equal(g[k][1], got[0][k][1]), k
+    assert np.any(got[0][0][1] >= 1) and np.any(got[2][1][2] >= 0)       # (the batch has hits and paths to compare)
+
+
 def test_mad_zero_read_has_no_hits(gpu):
     from squigglekit_amd import _lib, api, synth
     motif = synth.synthetic_motif(40)

@@ -200,6 +200,32 @@ def test_api_rejects_bad_arguments():
         api.motifseq_paths([np.arange(10)], [np.zeros(3)], max_dist=float("nan"))
 
 
+@pytest.mark.parametrize("width", [1, 2])
+@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("n", [1, 5])
+def test_flat_buffer_unpacks_as_the_header_lays_it_out(width, K, n):
+    """include/squigglekit_hip.h: motif k's block of spans begins at 2 * max_hits * nreads * motif_off[k] int32, inside it
+    [read][hit][N_k][2]; events follow that layout with one record where the spans have two ints.  A buffer that holds
+    its own indices: every element of every per-motif array must be the index the header gives it."""
+    from squigglekit_amd import api
+    sizes = (1, 4, 2)
+    moff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    buf = np.arange(width * K * n * int(moff[-1]), dtype=np.int32)
+    got = api._unpack_blocks(buf, moff, K, n, width)
+    assert len(got) == len(sizes)
+    seen = 0
+    for k, N in enumerate(sizes):
+        assert got[k].shape == ((n, K, N, 2) if width == 2 else (n, K, N))
+        for r in range(n):
+            for h in range(K):
+                for i in range(N):
+                    for w in range(width):
+                        want = width * K * n * int(moff[k]) + ((r * K + h) * N + i) * width + w
+                        assert (got[k][r, h, i, w] if width == 2 else got[k][r, h, i]) == want, (k, r, h, i, w)
+                        seen += 1
+    assert seen == buf.size                                              # (every element of the buffer has a place)
+
+
 # ---- the base table of a scrappie model ----------------------------------------------------------------------------------
 def test_base_table_of_the_shipped_model():
     from squigglekit_amd import tsvio
