@@ -346,6 +346,15 @@ def segment_reads_f64(reads, params=None, max_segs=64):
         return [segs[i, :nsegs[i]].tolist() if nsegs[i] else False for i in range(R)]
 
 
+def _flat_motifs(motifs):
+    """A list of motifs as the multi-motif entry points take it: (the float64 arrays, all points in one array, int32
+    offsets [len + 1])."""
+    ms = [np.ascontiguousarray(m, dtype=np.float64) for m in motifs]
+    flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros(0)
+    moff = np.concatenate([[0], np.cumsum([m.size for m in ms])]).astype(np.int32)
+    return ms, flat, moff
+
+
 def _over_devices(devices, R, call):
     """call(lo, hi) -> status on the calling thread's GPU, or -- with several devices -- on one host thread per GPU
     over the block split of the R reads (multigpu.run_sharded; every shard writes its slice of the caller's arrays).
@@ -488,23 +497,27 @@ def motifseq_multi_ragged_f64(values, off, motifs, scale="medmad", scale_low=0, 
     entry = L.sk_motifseq_multi_batch_centi if centi else L.sk_motifseq_multi_batch_f64
     off = np.ascontiguousarray(off, dtype=np.int64)
     R = off.size - 1
-    ms = [np.ascontiguousarray(m, dtype=np.float64) for m in motifs]
-    out = [np.zeros(max(R, 1), dtype=HIT_DTYPE) for _ in ms]
-    flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros(0)
-    moff = np.concatenate([[0], np.cumsum([m.size for m in ms])]).astype(np.int32)
+    # a shard is staged and filtered ONCE, every motif runs against it on the device (sk_motifseq_multi_batch_f64)
+    return _multi_over(devices, R, motifs, scale, scale_low, scale_hi,
+                       lambda lo, hi, *tail: entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, *tail))
+
+
+def _multi_over(devices, R, motifs, scale, scale_low, scale_hi, entry_call):
+    """Runs entry_call(lo, hi, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, out) -- the tail of every
+    multi-motif first-match entry point -- over the devices (_over_devices: every shard writes its reads); returns one
+    HIT_DTYPE array [R] per motif."""
+    ms, flat, moff = _flat_motifs(motifs)
+    out = np.zeros((len(ms), R), dtype=HIT_DTYPE)
 
     def call(lo, hi):
-        # the shard is staged and filtered ONCE, every motif runs against it on the device (sk_motifseq_multi_batch_f64)
         part = np.zeros((len(ms), hi - lo), dtype=HIT_DTYPE)
-        rc = entry(ptr(values), ptr(off[lo:hi + 1]), hi - lo, ptr(flat), ptr(moff), len(ms),
-                   _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), ptr(part))
+        rc = entry_call(lo, hi, ptr(flat), ptr(moff), len(ms), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), ptr(part))
         if rc == 0:
-            for k, hits in enumerate(out):
-                hits[lo:hi] = part[k]
+            out[:, lo:hi] = part
         return rc
     if R and ms:
         _over_devices(devices, R, call)
-    return [h[:R] for h in out]
+    return list(out)
 
 
 def drna_segment_batch(sig, lens, params=None, max_segs=32):
@@ -624,7 +637,7 @@ def motifseq_batch(sig, lens, motif, scale="medmad", scale_low=0, scale_hi=1200,
     every shard's records straight into the result, gather="rccl" all-gathers them GPU to GPU first (RCCL) and
     downloads the complete result from the first device (multigpu.motifseq_sharded)."""
     devices = _devs(devices)
-    L = _lib.load() if devices else _lib.ensure_init()
+    L = _lib.load()
     sig = np.ascontiguousarray(sig, dtype=np.int16)
     R, stride = sig.shape
     lens = (np.full(R, stride, dtype=np.int32) if lens is None
@@ -633,24 +646,14 @@ def motifseq_batch(sig, lens, motif, scale="medmad", scale_low=0, scale_hi=1200,
     if _too_wide_for_i16(scale_low, scale_hi):
         return motifseq_reads_f64([sig[r, :lens[r]].astype(np.float64) for r in range(R)], motif, scale,
                                   scale_low, scale_hi)
-    out = np.zeros(R, dtype=HIT_DTYPE)
-    if devices is not None and len(devices) > 1 and R >= len(devices):
+    if gather == "rccl" and devices is not None and len(devices) > 1 and R >= len(devices):
         from . import multigpu
-        if gather == "rccl":
-            return multigpu.motifseq_sharded(sig, lens, motif, _lib.SK_SCALE[scale], scale_low, scale_hi,
-                                             devices, gather="rccl")[0]
-
-        def shard(lo, hi, comm):
-            if hi > lo:
-                check(L.sk_motifseq_batch_i16(ptr(sig[lo:hi]), stride, ptr(lens[lo:hi]), hi - lo, ptr(motif),
-                                              motif.size, _lib.SK_SCALE[scale], int(scale_low), int(scale_hi),
-                                              ptr(out[lo:hi])))
-        multigpu.run_sharded(devices, R, shard)
-        return out
-    if devices:
-        _lib.init(devices[0])
-    check(L.sk_motifseq_batch_i16(ptr(sig), stride, ptr(lens), R, ptr(motif), motif.size,
-                                  _lib.SK_SCALE[scale], int(scale_low), int(scale_hi), ptr(out)))
+        return multigpu.motifseq_sharded(sig, lens, motif, _lib.SK_SCALE[scale], scale_low, scale_hi,
+                                         devices, gather="rccl")[0]
+    out = np.zeros(R, dtype=HIT_DTYPE)
+    _over_devices(devices, R, lambda lo, hi: L.sk_motifseq_batch_i16(
+        ptr(sig[lo:hi]), stride, ptr(lens[lo:hi]), hi - lo, ptr(motif), motif.size, _lib.SK_SCALE[scale], int(scale_low),
+        int(scale_hi), ptr(out[lo:hi])))
     return out
 
 
@@ -714,6 +717,14 @@ def motifseq_after_stall(reads, motif, scale="medmad", scale_low=0, scale_hi=120
     return motifseq_any([np.asarray(r)[c:] for r, c in zip(reads, cuts)], motif, scale, scale_low, scale_hi), cuts
 
 
+def _multi_rows(buf, lens, motifs, scale, scale_low, scale_hi):
+    """Every motif against the rows of a packed int16 batch (limits the int16 kernels take): one array per motif."""
+    L = _lib.load()
+    return _multi_over(None, buf.shape[0], motifs, scale, scale_low, scale_hi,
+                       lambda lo, hi, *tail: L.sk_motifseq_multi_batch_i16(ptr(buf[lo:hi]), buf.shape[1], ptr(lens[lo:hi]),
+                                                                           hi - lo, *tail))
+
+
 def motifseq_multi_batch(sig, lens, motifs, scale="medmad", scale_low=0, scale_hi=1200):
     """Every motif of `motifs` against every row of an int16 [R, stride] batch (one filter / statistics pass):
     list (one per motif) of HIT_DTYPE arrays in read order.  The block form of motifseq_multi."""
@@ -722,51 +733,24 @@ def motifseq_multi_batch(sig, lens, motifs, scale="medmad", scale_low=0, scale_h
     lens = np.ascontiguousarray(lens, dtype=np.int32)
     if _too_wide_for_i16(scale_low, scale_hi):
         return motifseq_multi([sig[r, :lens[r]] for r in range(R)], motifs, scale, scale_low, scale_hi)
-    return motifseq_multi([], motifs, scale, scale_low, scale_hi, _packed=(sig, lens))
+    return _multi_rows(sig, lens, motifs, scale, scale_low, scale_hi)
 
 
-def motifseq_multi(reads, motifs, scale="medmad", scale_low=0, scale_hi=1200, _packed=None):
+def motifseq_multi(reads, motifs, scale="medmad", scale_low=0, scale_hi=1200):
     """Every motif of `motifs` (list of float vectors) against every read: list (one per motif,
     in order) of HIT_DTYPE arrays in read order -- the double loop of MotifSeq.py:261-298,436.
-    Integer reads share one filter/statistics pass across motifs."""
-    L = _lib.ensure_init()
-    motifs = [np.ascontiguousarray(m, dtype=np.float64) for m in motifs]
-    if _packed is not None:                                   # an int16 batch as it is (motifseq_multi_batch)
-        buf, lens = _packed
-        ints, flts = list(range(buf.shape[0])), []
-        outs = [np.zeros(len(ints), dtype=HIT_DTYPE) for _ in motifs]
-    else:
-        outs = [np.zeros(len(reads), dtype=HIT_DTYPE) for _ in motifs]
-        ints, arrs, flts = _split_int16(reads)
-        if ints and motifs:
-            buf, lens = pack_i16(arrs)
+    The reads share one filter/statistics pass across motifs: the integer-valued ones as int16 rows, the rest as one
+    ragged float64 batch."""
+    motifs = list(motifs)
+    outs = [np.zeros(len(reads), dtype=HIT_DTYPE) for _ in motifs]
+    ints, arrs, flts = _split_int16(reads)
     if ints and motifs:
-        moff = np.zeros(len(motifs) + 1, dtype=np.int32)
-        moff[1:] = np.cumsum([m.size for m in motifs])
-        flat = np.ascontiguousarray(np.concatenate(motifs))
-        res = np.zeros((len(motifs), len(ints)), dtype=HIT_DTYPE)
-        devices = _devs(None)
-        if devices is not None and len(devices) > 1 and len(ints) >= len(devices):
-            from . import multigpu
-
-            def shard(lo, hi, comm):
-                if hi > lo:
-                    part = np.zeros((len(motifs), hi - lo), dtype=HIT_DTYPE)
-                    check(L.sk_motifseq_multi_batch_i16(ptr(buf[lo:hi]), buf.shape[1], ptr(lens[lo:hi]), hi - lo,
-                                                        ptr(flat), ptr(moff), len(motifs), _lib.SK_SCALE[scale],
-                                                        int(scale_low), int(scale_hi), ptr(part)))
-                    res[:, lo:hi] = part
-            multigpu.run_sharded(devices, len(ints), shard)
-        else:
-            check(L.sk_motifseq_multi_batch_i16(ptr(buf), buf.shape[1], ptr(lens), len(ints), ptr(flat), ptr(moff),
-                                                len(motifs), _lib.SK_SCALE[scale], int(scale_low), int(scale_hi),
-                                                ptr(res)))
-        for k in range(len(motifs)):
-            outs[k][ints] = res[k]
-    if flts:
-        sub = [reads[i] for i in flts]
-        for k, m in enumerate(motifs):
-            outs[k][flts] = motifseq_reads_f64(sub, m, scale, scale_low, scale_hi)
+        for k, part in enumerate(_multi_rows(*pack_i16(arrs), motifs, scale, scale_low, scale_hi)):
+            outs[k][ints] = part
+    if flts and motifs:
+        flat, off = pack_f64([reads[i] for i in flts])
+        for k, part in enumerate(motifseq_multi_ragged_f64(flat, off, motifs, scale, scale_low, scale_hi)):
+            outs[k][flts] = part
     return outs
 
 
@@ -781,10 +765,7 @@ def _hits_args(motifs, max_hits, max_dist):
         raise ValueError("max_hits must be in 1..64, got %d" % max_hits)
     if max_dist != max_dist:
         raise ValueError("max_dist is NaN")
-    ms = [np.ascontiguousarray(m, dtype=np.float64) for m in motifs]
-    flat = np.ascontiguousarray(np.concatenate(ms)) if ms else np.zeros(0)
-    moff = np.concatenate([[0], np.cumsum([m.size for m in ms])]).astype(np.int32)
-    return ms, flat, moff, max_hits, max_dist
+    return _flat_motifs(motifs) + (max_hits, max_dist)
 
 
 class _Family:

@@ -219,39 +219,13 @@ int read_segs(sk_ctx *c, int32_t nreads, int32_t max_segs, int32_t *segs, int32_
     return SK_OK;
 }
 
-int motifseq_dev(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                 const double *motif, int32_t nmotif, int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
-                 sk_hit *d_out, int accumulate);
+// ------------------------------------------------------------------ MotifSeq: what every family shares
+int prep_mode(int32_t scale_mode) { return scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE; }
 
-} // namespace
-
-extern "C" {
-
-// ------------------------------------------------------------------ pinned host memory for callers
-void *sk_host_alloc(size_t bytes)
-{
-    sk_entry entry;
-    if (!entry.c) return nullptr;
-    void *p = nullptr;
-    hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        sk_fail(SK_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        return nullptr;
-    }
-    return p;
-}
-
-int sk_host_free(void *p)
-{
-    if (p) SK_HIP(hipHostFree(p));
-    return SK_OK;
-}
-
-// ------------------------------------------------------------------ MotifSeq, device resident
 // Last step of the host-facing DTW entry points: the guard counters of the screening scheme (sk_last_dtw_guard) ride
 // with the final synchronisation, and an alarm -- something that cannot happen in a healthy build -- is said out loud
 // once per call (the records are right either way: the library redid the call with the exact pass).
-static int finish_dtw_host(sk_ctx *c)
+int finish_dtw_host(sk_ctx *c)
 {
     int32_t g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (c->retry_dev && c->dtwcnt.p)
@@ -264,126 +238,7 @@ static int finish_dtw_host(sk_ctx *c)
     return SK_OK;
 }
 
-int sk_motifseq_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                        const double *motif, int32_t nmotif, int32_t scale_mode,
-                        int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
-{
-    SK_ENTER(c);
-    redo_forget(c);
-    return motifseq_dev(c, d_sig, stride, d_len, nreads, motif, nmotif, scale_mode, scale_low, scale_hi, d_out, 0);
-}
-
-} // extern "C"
-
-namespace {
-
-int motifseq_dev(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                 const double *motif, int32_t nmotif, int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
-                 sk_hit *d_out, int accumulate)
-{
-    int rc = check_i16(d_sig, stride, d_len, nreads);
-    if (rc) return rc;
-    if (!motif || nmotif <= 0) return sk_fail(SK_ERR_INVALID, "empty motif");
-    if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
-        return sk_fail(SK_ERR_INVALID, "unknown scale mode %d", scale_mode);
-    if (nreads == 0) return SK_OK;
-    if (!d_out) return sk_fail(SK_ERR_INVALID, "NULL out");
-    clamp_limits(&scale_low, &scale_hi);
-    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-
-    // medmad with the usual limits: filter + statistics ride in the screening pass as its prologue (sk_sdtwq.hip);
-    // sk_launch_sdtw runs them as a kernel of their own when it does not take the screening scheme
-    sk_prep_fuse fz;
-    fz.raw = d_sig; fz.len = d_len; fz.lo = scale_low; fz.hi = scale_hi;
-    fz.mode = scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE;
-    const bool fuse = sk_sdtw_fuse_ok(scale_low, scale_hi, fz.mode, stride);
-    SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    if (!fuse) {
-        rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nreads, scale_low, scale_hi,
-                                scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0,
-                                (int16_t *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0);
-        if (rc) return rc;
-    }
-    SK_HIP(hipEventRecord(c->ev[1], c->stream));
-
-    sk_sdtw_args a;
-    a.feed = SK_FEED_I16; a.samples = c->comp.p; a.stride = stride; a.off = nullptr;
-    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.motif = motif; a.nmotif = nmotif;
-    a.out = d_out; a.last_row = nullptr; a.max_len = stride; a.force_single = 0; a.accumulate = accumulate;
-    a.fuse = fuse ? &fz : nullptr;
-    rc = sk_launch_sdtw(c, &a);
-    if (rc) return rc;
-    c->ev_valid = true;
-    return SK_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-// ------------------------------------------------------------------ MotifSeq, host buffers
-int sk_motifseq_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                          const double *motif, int32_t nmotif, int32_t scale_mode,
-                          int32_t scale_low, int32_t scale_hi, sk_hit *out)
-{
-    SK_ENTER(c);
-    int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
-    if ((rc = check_len_host(len, nreads, stride))) return rc;
-    if (nreads == 0) return SK_OK;
-    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
-    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
-    if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
-    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * sizeof(sk_hit)))) return rc;
-    redo_forget(c);
-    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
-                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
-                         return motifseq_dev(c, d_sig, stride, d_len, nr, motif, nmotif, scale_mode, scale_low, scale_hi,
-                                             (sk_hit *)c->out.p + r0, r0 > 0);
-                     });
-    if (rc) return rc;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, (size_t)nreads * sizeof(sk_hit), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = finish_dtw_host(c))) return rc;
-    return SK_OK;
-}
-
-// One (sub-)batch of the multi-motif path, everything device resident: filter + statistics once (as the prologue of
-// the first motif's screening pass when that applies), then one DTW launch set per motif.  Motif k's records go to
-// d_out + k * out_stride.
-static int motifseq_multi_dev(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr,
-                              int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off,
-                              int32_t nmotifs, int32_t scale_mode, int32_t scale_low, int32_t scale_hi,
-                              sk_hit *d_out, int64_t out_stride, int later_batch)
-{
-    int rc;
-    sk_prep_fuse fz;
-    fz.raw = d_sig; fz.len = d_len; fz.lo = scale_low; fz.hi = scale_hi;
-    fz.mode = scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE;
-    const bool fuse = sk_sdtw_fuse_ok(scale_low, scale_hi, fz.mode, stride);
-    SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    if (!fuse) {
-        rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nr, scale_low, scale_hi,
-                                scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp, d_prep,
-                                nullptr, 0);
-        if (rc) return rc;
-    }
-    SK_HIP(hipEventRecord(c->ev[1], c->stream));
-    for (int32_t k = 0; k < nmotifs; k++) {
-        sk_sdtw_args a;
-        a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr;
-        a.prep = d_prep; a.nreads = nr; a.motif = motifs + motif_off[k];
-        a.nmotif = motif_off[k + 1] - motif_off[k]; a.out = d_out + (size_t)k * (size_t)out_stride;
-        a.last_row = nullptr; a.max_len = stride; a.force_single = 0;
-        a.accumulate = (later_batch || k > 0) ? 1 : 0;
-        a.fuse = (fuse && k == 0) ? &fz : nullptr;      // (the later motifs find the samples / statistics in place)
-        if ((rc = sk_launch_sdtw(c, &a))) return rc;
-    }
-    return SK_OK;
-}
-
-static int check_multi(const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode)
+int check_multi(const double *motifs, const int32_t *motif_off, int32_t nmotifs, int32_t scale_mode)
 {
     if (!motifs || !motif_off || nmotifs <= 0) return sk_fail(SK_ERR_INVALID, "no motifs");
     for (int32_t k = 0; k < nmotifs; k++)
@@ -393,71 +248,12 @@ static int check_multi(const double *motifs, const int32_t *motif_off, int32_t n
     return SK_OK;
 }
 
-// device-resident form: d_out is [nmotifs][nreads]
-int sk_motifseq_multi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                              const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                              int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
-{
-    SK_ENTER(c);
-    int rc = check_i16(d_sig, stride, d_len, nreads);
-    if (rc) return rc;
-    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
-    if (nreads == 0) return SK_OK;
-    if (!d_out) return sk_fail(SK_ERR_INVALID, "NULL out");
-    clamp_limits(&scale_low, &scale_hi);
-    redo_forget(c);
-    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    rc = motifseq_multi_dev(c, d_sig, stride, d_len, nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs,
-                            motif_off, nmotifs, scale_mode, scale_low, scale_hi, d_out, nreads, 0);
-    if (rc) return rc;
-    c->ev_valid = true;
-    return SK_OK;
-}
-
-// Several motifs against the same reads (the `for name in m_order` loop of MotifSeq.py:436):
-// filter + statistics once, one DTW launch set per motif.  out is [nmotifs][nreads].
-int sk_motifseq_multi_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
-                                const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                                int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
-{
-    SK_ENTER(c);
-    int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
-    if ((rc = check_len_host(len, nreads, stride))) return rc;
-    if ((rc = check_multi(motifs, motif_off, nmotifs, scale_mode))) return rc;
-    if (nreads == 0) return SK_OK;
-    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
-    clamp_limits(&scale_low, &scale_hi);
-    const size_t sb = (size_t)nreads * (size_t)stride * sizeof(int16_t);
-    const size_t ob = (size_t)nreads * (size_t)nmotifs * sizeof(sk_hit);
-    if ((rc = sk_reserve(c, &c->sig, sb))) return rc;
-    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->comp, sb))) return rc;
-    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
-    // sub-batches as in sk_motifseq_batch_i16: filter + statistics once per sub-batch (as the prologue of the first
-    // motif's screening pass when that applies), then one DTW launch set per motif
-    redo_forget(c);
-    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
-                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
-                         return motifseq_multi_dev(c, d_sig, stride, d_len, nr, (int16_t *)c->comp.p + (size_t)r0 * (size_t)stride,
-                                                   (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode,
-                                                   scale_low, scale_hi, (sk_hit *)c->out.p + r0, nreads, r0 > 0);
-                     });
-    if (rc) return rc;
-    c->ev_valid = true;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = finish_dtw_host(c))) return rc;
-    return SK_OK;
-}
-
 // Stage a ragged float64 batch: samples -> c->sig, zero-based offsets -> c->off.
 // Returns the total sample count in *total and the longest read in *maxlen.
 // centi: `sig` holds int32 centi-units (sk_tsv_parse_centi) -- half the bytes over PCIe; the float64 image
 // (c / 100.0 = float("ddd.dd"), sk_synth.hip k_centi_to_f64) is made on the device, and what follows is the same.
-static int stage_ragged_f64(sk_ctx *c, const void *sig_any, const int64_t *off, int32_t nreads,
-                            int64_t *total, int64_t *maxlen, bool centi = false)
+int stage_ragged_f64(sk_ctx *c, const void *sig_any, const int64_t *off, int32_t nreads, int64_t *total, int64_t *maxlen,
+                     bool centi = false)
 {
     const double *sig = (const double *)sig_any;
     if (!sig || !off) return sk_fail(SK_ERR_INVALID, "NULL sig/off");
@@ -486,35 +282,40 @@ static int stage_ragged_f64(sk_ctx *c, const void *sig_any, const int64_t *off, 
     return SK_OK;
 }
 
-static int prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t maxlen,
-                    int32_t scale_mode, int32_t scale_low, int32_t scale_hi);
-
-// device-resident core of the float64 MotifSeq path: d_sig / d_off (zero based, nreads + 1) are device pointers.
-// Filter + statistics once, then one DTW launch set per motif (nmotifs >= 1; motif k = motifs + motif_off[k], its records
-// go to d_out + k * out_stride).
-static int motifseq_multi_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
-                                  int64_t maxlen, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                                  int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *d_out, int64_t out_stride)
+// The two prepare helpers, one per input kind: filter + statistics of one (sub-)batch on the device between ev[0] and
+// ev[1], and that batch as the DTW launchers take it -- *a gets feed, samples (+ samples_raw), stride / off, prep,
+// nreads and max_len, with last_row, force_single and fuse cleared; motif, out and accumulate are the caller's.
+//
+// int16 rows.  d_comp / d_prep: where this (sub-)batch's filtered samples / statistics go.  fz: nullptr, or room for
+// the fused prologue where the caller allows it: when it applies (sk_sdtw_fuse_ok: medmad with the usual limits,
+// zscale on short rows) nothing is launched here, a->fuse = fz, and filter + statistics ride in the screening pass of
+// the first sk_launch_sdtw (sk_sdtwq.hip; it runs them as a kernel of their own when it does not take the screening
+// scheme).  ev0_set: the caller has recorded ev[0] already (the panel: its gather lies inside the interval).
+int prep_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr, int32_t scale_mode,
+             int32_t scale_low, int32_t scale_hi, int16_t *d_comp, sk_prep *d_prep, sk_prep_fuse *fz, bool ev0_set,
+             sk_sdtw_args *a)
 {
-    int rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, scale_mode, scale_low, scale_hi);
-    if (rc) return rc;
-    for (int32_t k = 0; k < nmotifs; k++) {
-        sk_sdtw_args a;
-        a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.stride = 0; a.off = d_off;
-        a.samples_raw = d_sig;                          // (reads the filter left whole are not copied: SK_IFLAG_INPLACE)
-        a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.motif = motifs + motif_off[k];
-        a.nmotif = motif_off[k + 1] - motif_off[k];
-        a.out = d_out + (size_t)k * (size_t)out_stride; a.last_row = nullptr; a.max_len = maxlen; a.force_single = 0;
-        a.accumulate = k > 0 ? 1 : 0;
-        if ((rc = sk_launch_sdtw(c, &a))) return rc;
+    const int mode = prep_mode(scale_mode);
+    const bool fuse = fz && sk_sdtw_fuse_ok(scale_low, scale_hi, mode, stride);
+    if (!ev0_set) SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    if (fuse) {
+        fz->raw = d_sig; fz->len = d_len; fz->lo = scale_low; fz->hi = scale_hi; fz->mode = mode;
+    } else {
+        const int rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nr, scale_low, scale_hi, mode, 0.0, d_comp, d_prep,
+                                          nullptr, 0);
+        if (rc) return rc;
     }
-    c->ev_valid = true;
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    a->feed = SK_FEED_I16; a->samples = d_comp; a->samples_raw = nullptr; a->stride = stride; a->off = nullptr;
+    a->prep = d_prep; a->nreads = nr; a->max_len = stride; a->last_row = nullptr; a->force_single = 0;
+    a->fuse = fuse ? fz : nullptr;
     return SK_OK;
 }
 
-// filter + statistics of a staged ragged float64 batch: normalisation terms to c->prep, filtered samples to c->comp
-static int prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t maxlen,
-                    int32_t scale_mode, int32_t scale_low, int32_t scale_hi)
+// A staged ragged float64 batch (d_sig / d_off: zero based, nreads + 1): normalisation terms to c->prep, filtered
+// samples to c->comp (reads the filter left whole are not copied: SK_IFLAG_INPLACE, read from samples_raw).
+int prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t maxlen,
+             int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_sdtw_args *a)
 {
     int rc;
     if ((rc = sk_reserve(c, &c->comp, (size_t)(total > 0 ? total : 1) * sizeof(double)))) return rc;
@@ -533,108 +334,150 @@ static int prep_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_
                                        (double)scale_low, (double)scale_hi, SK_PREP_MEDMAD, 0.0, (double *)c->comp.p, 0,
                                        (sk_prep *)c->prep.p, nullptr, 0);
     } else {
-        rc = sk_launch_prep_f64(c, d_sig, d_off, nreads, (double)scale_low,
-                                (double)scale_hi, scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE,
-                                0.0, (double *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0);
+        rc = sk_launch_prep_f64(c, d_sig, d_off, nreads, (double)scale_low, (double)scale_hi, prep_mode(scale_mode), 0.0,
+                                (double *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0);
     }
     if (rc) return rc;
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    a->feed = SK_FEED_F64_NORM; a->samples = c->comp.p; a->samples_raw = d_sig; a->stride = 0; a->off = d_off;
+    a->prep = (const sk_prep *)c->prep.p; a->nreads = nreads; a->max_len = maxlen; a->last_row = nullptr;
+    a->force_single = 0; a->fuse = nullptr;
     return SK_OK;
 }
 
-static int motifseq_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
-                            int64_t maxlen, const double *motif, int32_t nmotif, int32_t scale_mode,
-                            int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
-{
-    const int32_t moff[2] = {0, nmotif};
-    return motifseq_multi_dev_f64(c, d_sig, d_off, nreads, total, maxlen, motif, moff, 1, scale_mode, scale_low, scale_hi,
-                                  d_out, nreads);
-}
+// ------------------------------------------------------------------ MotifSeq first match
+// scale_outliers + medmad / zscale + dtw_subsequence (MotifSeq.py:186-200, 436-439): one record per read and motif.
+// Several motifs against the same reads (the `for name in m_order` loop of :436) share one filter + statistics pass;
+// a single-motif entry point is the same call with a two-element motif_off on its stack.
+struct fm_req {
+    const double  *motifs;          // motif k = motifs[motif_off[k] .. motif_off[k + 1])
+    const int32_t *motif_off;
+    int32_t        nmotifs;
+    int32_t        scale_mode, scale_low, scale_hi;
+    sk_hit        *out;             // [nmotifs][nreads]: device memory for a *_dev_* entry point, else host memory
+};
+// the request of an entry point from its parameters (all eight name scaling and out alike)
+#define FM_REQ(motifs, motif_off, nmotifs) fm_req{motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, out}
 
-int sk_motifseq_batch_f64(const double *sig, const int64_t *off, int32_t nreads,
-                          const double *motif, int32_t nmotif, int32_t scale_mode,
-                          int32_t scale_low, int32_t scale_hi, sk_hit *out)
+// after the checks of the input.  Without reads out may be NULL.
+int fm_check(const fm_req &q, int32_t nreads)
 {
-    SK_ENTER(c);
-    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
-    if (!motif || nmotif <= 0) return sk_fail(SK_ERR_INVALID, "empty motif");
-    if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
-        return sk_fail(SK_ERR_INVALID, "unknown scale mode %d", scale_mode);
-    if (nreads == 0) return SK_OK;
-    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
-    int64_t total, maxlen;
-    int rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen);
+    const int rc = check_multi(q.motifs, q.motif_off, q.nmotifs, q.scale_mode);
     if (rc) return rc;
-    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * sizeof(sk_hit)))) return rc;
-    if ((rc = redo_begin(c, nreads, 1))) return rc;
-    rc = motifseq_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, motif, nmotif,
-                          scale_mode, scale_low, scale_hi, (sk_hit *)c->out.p);
-    if (rc) return rc;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, (size_t)nreads * sizeof(sk_hit), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = finish_dtw_host(c))) return rc;
+    if (nreads && !q.out) return sk_fail(SK_ERR_INVALID, "NULL out");
     return SK_OK;
 }
 
-// Several motifs against the same ragged float64 batch (the `for name in m_order` loop of MotifSeq.py:436 on pA input):
-// the batch is staged once, filter + statistics run once, one DTW launch set per motif.  out is [nmotifs][nreads].
-static int motifseq_multi_batch_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
-                                       const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                                       int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out);
-int sk_motifseq_multi_batch_f64(const double *sig, const int64_t *off, int32_t nreads,
-                                const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                                int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+// One prepared (sub-)batch (a: from a prepare helper): one DTW launch set per motif, motif k's records to
+// d_out + k * out_stride.  The first launch set of a call starts the retry total, every other one (later_batch: of a
+// later sub-batch) adds to it; a fused prologue runs with the first motif, the later ones find samples and statistics
+// in place.
+int fm_core(sk_ctx *c, sk_sdtw_args a, const fm_req &q, sk_hit *d_out, int64_t out_stride, bool later_batch)
 {
-    return motifseq_multi_batch_ragged(sig, false, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, out);
+    for (int32_t k = 0; k < q.nmotifs; k++) {
+        a.motif = q.motifs + q.motif_off[k]; a.nmotif = q.motif_off[k + 1] - q.motif_off[k];
+        a.out = d_out + (size_t)k * (size_t)out_stride;
+        a.accumulate = (later_batch || k > 0) ? 1 : 0;
+        if (k > 0) a.fuse = nullptr;
+        const int rc = sk_launch_sdtw(c, &a);
+        if (rc) return rc;
+    }
+    c->ev_valid = true;
+    return SK_OK;
 }
-int sk_motifseq_multi_batch_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
-                                  const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                                  int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+
+// The four bodies, one per input.  Device-resident int16 rows: q.out is the caller's device buffer.
+int fm_dev_i16(fm_req q, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads)
 {
-    return motifseq_multi_batch_ragged(centi, true, off, nreads, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, out);
+    SK_ENTER(c);
+    int rc;
+    if ((rc = check_i16(d_sig, stride, d_len, nreads)) || (rc = fm_check(q, nreads))) return rc;
+    if (nreads == 0) return SK_OK;
+    clamp_limits(&q.scale_low, &q.scale_hi);
+    redo_forget(c);
+    if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, (size_t)nreads * sizeof(sk_prep)))) return rc;
+    sk_prep_fuse fz;
+    sk_sdtw_args a;
+    if ((rc = prep_i16(c, d_sig, stride, d_len, nreads, q.scale_mode, q.scale_low, q.scale_hi, (int16_t *)c->comp.p,
+                       (sk_prep *)c->prep.p, &fz, false, &a))) return rc;
+    return fm_core(c, a, q, q.out, nreads, false);
 }
-static int motifseq_multi_batch_ragged(const void *sig, bool centi, const int64_t *off, int32_t nreads,
-                                       const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                                       int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+
+// int16 rows in host memory, in sub-batches (ingest_rows).  whole: c->comp / c->prep hold the filtered samples and
+// statistics of the whole call, each sub-batch at its reads' place, as the hit family lays them out; otherwise every
+// sub-batch reuses the room of one.  sk_motifseq_batch_i16 is the one entry point that asks for the latter, and it
+// has to: its batches go up to 1 M x 4 000 samples, where the whole-call layout would cost 8 GB more.  It also
+// answers an empty batch before it looks at the motif, as it always has.
+int fm_host_i16(fm_req q, const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, bool whole)
+{
+    SK_ENTER(c);
+    int rc;
+    if ((rc = check_i16(sig, stride, len, nreads)) || (rc = check_len_host(len, nreads, stride))) return rc;
+    if (nreads == 0 && !whole) return SK_OK;
+    if ((rc = fm_check(q, nreads))) return rc;
+    if (nreads == 0) return SK_OK;
+    clamp_limits(&q.scale_low, &q.scale_hi);
+    const SubBatches B = sub_batches(nreads, stride);
+    const size_t rows = whole ? nreads : B.per, ob = (size_t)nreads * (size_t)q.nmotifs * sizeof(sk_hit);
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->comp, rows * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->prep, rows * sizeof(sk_prep)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, ob))) return rc;
+    redo_forget(c);
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         const size_t at = whole ? r0 : 0;
+                         sk_prep_fuse fz;
+                         sk_sdtw_args a;
+                         const int rc = prep_i16(c, d_sig, stride, d_len, nr, q.scale_mode, q.scale_low, q.scale_hi,
+                                                 (int16_t *)c->comp.p + at * (size_t)stride, (sk_prep *)c->prep.p + at,
+                                                 &fz, false, &a);
+                         return rc ? rc : fm_core(c, a, q, (sk_hit *)c->out.p + r0, nreads, r0 > 0);
+                     });
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(q.out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
+    return finish_dtw_host(c);
+}
+
+// ragged float64 reads in host memory (pA TSV / BLOW5 in pA): read r = sig[off[r] .. off[r+1]), staged once.  centi:
+// int32 centi-units, made float64 on the device (stage_ragged_f64)
+int fm_ragged(fm_req q, const void *sig, bool centi, const int64_t *off, int32_t nreads)
 {
     SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
-    int rc = check_multi(motifs, motif_off, nmotifs, scale_mode);
+    int rc = fm_check(q, nreads);
     if (rc) return rc;
     if (nreads == 0) return SK_OK;
-    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
     int64_t total, maxlen;
     if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
-    const size_t ob = (size_t)nreads * (size_t)nmotifs * sizeof(sk_hit);
+    const size_t ob = (size_t)nreads * (size_t)q.nmotifs * sizeof(sk_hit);
     if ((rc = sk_reserve(c, &c->out, ob))) return rc;
     if ((rc = redo_begin(c, nreads, 1))) return rc;
-    rc = motifseq_multi_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, motifs,
-                                motif_off, nmotifs, scale_mode, scale_low, scale_hi, (sk_hit *)c->out.p, nreads);
-    if (rc) return rc;
-    SK_HIP(hipMemcpyAsync(out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = finish_dtw_host(c))) return rc;
-    return SK_OK;
+    sk_sdtw_args a;
+    if ((rc = prep_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, q.scale_mode,
+                       q.scale_low, q.scale_hi, &a))) return rc;
+    if ((rc = fm_core(c, a, q, (sk_hit *)c->out.p, nreads, false))) return rc;
+    SK_HIP(hipMemcpyAsync(q.out, c->out.p, ob, hipMemcpyDeviceToHost, c->stream));
+    return finish_dtw_host(c);
 }
 
-int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t max_len,
-                        const double *motif, int32_t nmotif, int32_t scale_mode,
-                        int32_t scale_low, int32_t scale_hi, sk_hit *d_out)
+// the same batch already on the device: d_sig / d_off (zero based, nreads + 1) and q.out are device pointers
+int fm_dev_f64(fm_req q, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t max_len)
 {
     SK_ENTER(c);
     if (nreads < 0 || total < 0 || max_len < 0 || max_len > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "bad sizes");
-    if (!motif || nmotif <= 0) return sk_fail(SK_ERR_INVALID, "empty motif");
-    if (scale_mode != SK_SCALE_MEDMAD && scale_mode != SK_SCALE_ZSCALE)
-        return sk_fail(SK_ERR_INVALID, "unknown scale mode %d", scale_mode);
-    if (nreads == 0) return SK_OK;
-    if (!d_sig || !d_off || !d_out) return sk_fail(SK_ERR_INVALID, "NULL sig/off/out");
-    const int rc = redo_begin(c, nreads, 1);
+    int rc = fm_check(q, nreads);
     if (rc) return rc;
-    return motifseq_dev_f64(c, d_sig, d_off, nreads, total, max_len, motif, nmotif, scale_mode, scale_low, scale_hi,
-                            d_out);
+    if (nreads == 0) return SK_OK;
+    if (!d_sig || !d_off) return sk_fail(SK_ERR_INVALID, "NULL sig/off");
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    sk_sdtw_args a;
+    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, max_len, q.scale_mode, q.scale_low, q.scale_hi, &a))) return rc;
+    return fm_core(c, a, q, q.out, nreads, false);
 }
 
-} // extern "C"
-
-namespace {
 
 // ------------------------------------------------------------------ MotifSeq hit lists (sk_hits.hip)
 // Up to K disjoint matches per read and motif instead of the first argmin only (MotifSeq.py:437-439 keeps that one;
@@ -803,18 +646,11 @@ int hits_core(sk_ctx *c, const sk_sdtw_args &base, const hits_req &q, const hits
 int hits_rows_i16(sk_ctx *c, const hits_req &q, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr,
                   const hits_out &d, int64_t out_reads, int64_t read0)
 {
-    int16_t *d_comp = (int16_t *)c->comp.p + (size_t)read0 * (size_t)stride;
-    sk_prep *d_prep = (sk_prep *)c->prep.p + read0;
-    SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    const int rc = sk_launch_prep_i16(c, d_sig, stride, d_len, nr, q.scale_low, q.scale_hi,
-                                      q.scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp,
-                                      d_prep, nullptr, 0);
-    if (rc) return rc;
-    SK_HIP(hipEventRecord(c->ev[1], c->stream));
     sk_sdtw_args a;
-    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = stride; a.off = nullptr; a.prep = d_prep; a.nreads = nr;
-    a.max_len = stride;
-    return hits_core(c, a, q, d, out_reads, read0);
+    const int rc = prep_i16(c, d_sig, stride, d_len, nr, q.scale_mode, q.scale_low, q.scale_hi,
+                            (int16_t *)c->comp.p + (size_t)read0 * (size_t)stride, (sk_prep *)c->prep.p + read0, nullptr,
+                            false, &a);
+    return rc ? rc : hits_core(c, a, q, d, out_reads, read0);
 }
 
 // The three bodies, one per input kind.  Device-resident int16 rows: the outputs are the caller's device buffers.
@@ -837,7 +673,7 @@ int hits_dev_i16(hits_req q, const int16_t *d_sig, int64_t stride, const int32_t
     return hits_rows_i16(c, q, d_sig, stride, d_len, nreads, d, nreads, 0);
 }
 
-// int16 rows in host memory; sub-batches as sk_motifseq_multi_batch_i16.  Every sub-batch writes its reads' places in
+// int16 rows in host memory; sub-batches and the whole-call layout of c->comp / c->prep as fm_host_i16.  Every sub-batch writes its reads' places in
 // the outputs of the whole call, so these come back in one piece.
 int hits_host_i16(hits_req q, const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads)
 {
@@ -879,12 +715,9 @@ int hits_ragged(hits_req q, const void *sig, bool centi, const int64_t *off, int
     hits_out d;
     if ((rc = hits_reserve(c, q, z, &d))) return rc;
     if ((rc = redo_begin(c, nreads, 1))) return rc;
-    const double *d_sig = (const double *)c->sig.p;
-    const int64_t *d_off = (const int64_t *)c->off.p;
-    if ((rc = prep_f64(c, d_sig, d_off, nreads, total, maxlen, q.scale_mode, q.scale_low, q.scale_hi))) return rc;
     sk_sdtw_args a;
-    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_sig; a.stride = 0; a.off = d_off;
-    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.max_len = maxlen;
+    if ((rc = prep_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, q.scale_mode,
+                       q.scale_low, q.scale_hi, &a))) return rc;
     if ((rc = hits_core(c, a, q, d, nreads, 0))) return rc;
     return hits_copy_back(c, q, z, d);
 }
@@ -892,6 +725,82 @@ int hits_ragged(hits_req q, const void *sig, bool centi, const int64_t *off, int
 } // namespace
 
 extern "C" {
+
+// ------------------------------------------------------------------ pinned host memory for callers
+void *sk_host_alloc(size_t bytes)
+{
+    sk_entry entry;
+    if (!entry.c) return nullptr;
+    void *p = nullptr;
+    hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        sk_fail(SK_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    return p;
+}
+
+int sk_host_free(void *p)
+{
+    if (p) SK_HIP(hipHostFree(p));
+    return SK_OK;
+}
+
+// ------------------------------------------------------------------ MotifSeq first match: the entry points
+// *_dev_*: every buffer is device memory.  Multi-motif forms: out is [nmotifs][nreads].
+int sk_motifseq_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                        const double *motif, int32_t nmotif, int32_t scale_mode,
+                        int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    const int32_t motif_off[2] = {0, nmotif};
+    return fm_dev_i16(FM_REQ(motif, motif_off, 1), d_sig, stride, d_len, nreads);
+}
+int sk_motifseq_multi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                              int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    return fm_dev_i16(FM_REQ(motifs, motif_off, nmotifs), d_sig, stride, d_len, nreads);
+}
+int sk_motifseq_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const double *motif, int32_t nmotif, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    const int32_t motif_off[2] = {0, nmotif};
+    return fm_host_i16(FM_REQ(motif, motif_off, 1), sig, stride, len, nreads, false);
+}
+int sk_motifseq_multi_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                                const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                                int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    return fm_host_i16(FM_REQ(motifs, motif_off, nmotifs), sig, stride, len, nreads, true);
+}
+int sk_motifseq_batch_f64(const double *sig, const int64_t *off, int32_t nreads,
+                          const double *motif, int32_t nmotif, int32_t scale_mode,
+                          int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    const int32_t motif_off[2] = {0, nmotif};
+    return fm_ragged(FM_REQ(motif, motif_off, 1), sig, false, off, nreads);
+}
+int sk_motifseq_multi_batch_f64(const double *sig, const int64_t *off, int32_t nreads,
+                                const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                                int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    return fm_ragged(FM_REQ(motifs, motif_off, nmotifs), sig, false, off, nreads);
+}
+int sk_motifseq_multi_batch_centi(const int32_t *centi, const int64_t *off, int32_t nreads,
+                                  const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                                  int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    return fm_ragged(FM_REQ(motifs, motif_off, nmotifs), centi, true, off, nreads);
+}
+int sk_motifseq_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t max_len,
+                        const double *motif, int32_t nmotif, int32_t scale_mode,
+                        int32_t scale_low, int32_t scale_hi, sk_hit *out)
+{
+    const int32_t motif_off[2] = {0, nmotif};
+    return fm_dev_f64(FM_REQ(motif, motif_off, 1), d_sig, d_off, nreads, total, max_len);
+}
+
 
 // The entry points: hit lists, then their twins with the read background, the alignment paths, the events.  *_dev_i16:
 // every buffer is device memory.
@@ -1200,7 +1109,7 @@ int sk_normalise_i16(const int16_t *sig, int32_t len, int32_t scale_mode,
     SK_HIP(hipMemcpyAsync(c->len.p, &len, sizeof len, hipMemcpyHostToDevice, c->stream));
     SK_HIP(hipStreamSynchronize(c->stream));
     rc = sk_launch_prep_i16(c, (const int16_t *)c->sig.p, stride, (const int32_t *)c->len.p, 1, scale_low,
-                            scale_hi, scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0,
+                            scale_hi, prep_mode(scale_mode), 0.0,
                             (int16_t *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0);
     if (rc) return rc;
     hipLaunchKernelGGL(k_normalise_i16, dim3(64), dim3(256), 0, c->stream, (const int16_t *)c->comp.p,
@@ -1231,7 +1140,7 @@ int sk_normalise_f64(const double *sig, int32_t len, int32_t scale_mode,
     if ((rc = sk_reserve(c, &c->prep, sizeof(sk_prep)))) return rc;
     if ((rc = sk_reserve(c, &c->misc, (size_t)len * sizeof(double)))) return rc;
     rc = sk_launch_prep_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, 1, (double)scale_low,
-                            (double)scale_hi, scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE,
+                            (double)scale_hi, prep_mode(scale_mode),
                             0.0, (double *)c->comp.p, (sk_prep *)c->prep.p, nullptr, 0);
     if (rc) return rc;
     hipLaunchKernelGGL(k_normalise_f64, dim3(64), dim3(256), 0, c->stream, (const double *)c->comp.p,
@@ -2218,28 +2127,40 @@ int panel_window(int32_t r, int32_t len, int32_t begin, int32_t end, const int32
 
 int64_t round8(int64_t v) { return v < 8 ? 8 : (v + 7) / 8 * 8; }
 
-// One (sub-)batch of int16 rows, everything device resident: gather, filter + statistics over the windows, DTW of every
-// motif, ranking.  Window rows / lengths / statistics of read r live at slot r of the buffers given.
-int panel_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr, int32_t begin,
-                  int32_t end, const int32_t *d_win, int16_t *d_rows, int64_t wstride, int32_t *d_wlen, int32_t *d_from,
-                  int16_t *d_comp, sk_prep *d_prep, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
-                  int32_t scale_mode, int32_t scale_low, int32_t scale_hi, sk_hit *d_all, int64_t out_stride,
-                  sk_panel_rec *d_out, int later_batch)
+// What one int16 call asks of each of its (sub-)batches, and where the call keeps its per-read buffers on the device:
+// read r of the call has slot r of each (d_win: nullptr = the begin / end pair; d_all / d_out: [nmotifs][nreads] and
+// [nreads]).  comp / prep are c->comp / c->prep, laid out for the whole call like the rest.
+struct panel_req {
+    int32_t        begin, end;
+    const int32_t *d_win;
+    const double  *motifs;
+    const int32_t *motif_off;
+    int32_t        nmotifs, scale_mode, scale_low, scale_hi;
+    int32_t        nreads;          // of the whole call
+    int64_t        wstride;
+    int16_t       *d_rows;          // window rows, stride wstride
+    int32_t       *d_wlen, *d_from;
+    sk_hit        *d_all;
+    sk_panel_rec  *d_out;
+};
+
+// Reads [r0, r0 + nr) of the call, everything device resident: gather, filter + statistics over the windows (never
+// fused: the panel's DTW has no screening pass), DTW of every motif, ranking.
+int panel_dev_i16(sk_ctx *c, const panel_req &q, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nr,
+                  int32_t r0)
 {
     int rc;
+    int16_t *d_rows = q.d_rows + (size_t)r0 * (size_t)q.wstride;
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
-    if ((rc = sk_launch_region_rows_i16(c, d_sig, stride, d_len, nr, begin, end, d_win, d_rows, wstride, d_wlen, d_from)))
-        return rc;
-    rc = sk_launch_prep_i16(c, d_rows, wstride, d_wlen, nr, scale_low, scale_hi,
-                            scale_mode == SK_SCALE_MEDMAD ? SK_PREP_MEDMAD : SK_PREP_ZSCALE, 0.0, d_comp, d_prep, nullptr, 0);
-    if (rc) return rc;
-    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    if ((rc = sk_launch_region_rows_i16(c, d_sig, stride, d_len, nr, q.begin, q.end, q.d_win ? q.d_win + 2 * (size_t)r0 : nullptr,
+                                        d_rows, q.wstride, q.d_wlen + r0, q.d_from + r0))) return rc;
     sk_sdtw_args a;
-    a.feed = SK_FEED_I16; a.samples = d_comp; a.stride = wstride; a.off = nullptr; a.prep = d_prep; a.nreads = nr;
-    a.motif = nullptr; a.nmotif = 0; a.out = nullptr; a.last_row = nullptr; a.max_len = wstride; a.force_single = 1;
-    a.accumulate = later_batch;
-    if ((rc = sk_launch_panel_dtw(c, &a, motifs, motif_off, d_all, out_stride))) return rc;
-    if ((rc = sk_launch_panel_rank(c, d_all, out_stride, nr, nmotifs, d_out))) return rc;
+    if ((rc = prep_i16(c, d_rows, q.wstride, q.d_wlen + r0, nr, q.scale_mode, q.scale_low, q.scale_hi,
+                       (int16_t *)c->comp.p + (size_t)r0 * (size_t)q.wstride, (sk_prep *)c->prep.p + r0, nullptr, true, &a)))
+        return rc;
+    a.motif = nullptr; a.nmotif = 0; a.out = nullptr; a.force_single = 1; a.accumulate = r0 > 0;
+    if ((rc = sk_launch_panel_dtw(c, &a, q.motifs, q.motif_off, q.d_all + r0, q.nreads))) return rc;
+    if ((rc = sk_launch_panel_rank(c, q.d_all + r0, q.nreads, nr, q.nmotifs, q.d_out + r0))) return rc;
     SK_HIP(hipEventRecord(c->ev[3], c->stream));
     c->ev_valid = true;
     return SK_OK;
@@ -2284,9 +2205,9 @@ int sk_motifseq_panel_dev_i16(const int16_t *d_sig, int64_t stride, const int32_
     }
     if ((rc = sk_panel_plan(c, motifs, motif_off, nmotifs, mean, sd, (int64_t)nreads * nmotifs))) return rc;
     int32_t *d_wlen = (int32_t *)c->panelaux.p;
-    return panel_dev_i16(c, d_sig, stride, d_len, nreads, begin, end, d_win, (int16_t *)c->panelwin.p, wstride, d_wlen,
-                         d_from ? d_from : d_wlen + nreads, (int16_t *)c->comp.p, (sk_prep *)c->prep.p, motifs, motif_off,
-                         nmotifs, scale_mode, scale_low, scale_hi, d_all, nreads, d_out, 0);
+    const panel_req q = {begin, end, d_win, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, nreads, wstride,
+                         (int16_t *)c->panelwin.p, d_wlen, d_from ? d_from : d_wlen + nreads, d_all, d_out};
+    return panel_dev_i16(c, q, d_sig, stride, d_len, nreads, 0);
 }
 
 int sk_motifseq_panel_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
@@ -2330,13 +2251,11 @@ int sk_motifseq_panel_i16(const int16_t *sig, int64_t stride, const int32_t *len
     }
     sk_hit *d_all = (sk_hit *)c->panelrec.p;
     sk_panel_rec *d_out = (sk_panel_rec *)(d_all + (size_t)nreads * (size_t)nmotifs);
+    const panel_req q = {begin, end, d_win, motifs, motif_off, nmotifs, scale_mode, scale_low, scale_hi, nreads, wstride,
+                         (int16_t *)c->panelwin.p, d_wlen, d_from, d_all, d_out};
     rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
                      [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
-                         return panel_dev_i16(c, d_sig, stride, d_len, nr, begin, end, d_win ? d_win + 2 * (size_t)r0 : nullptr,
-                                              (int16_t *)c->panelwin.p + (size_t)r0 * (size_t)wstride, wstride, d_wlen + r0,
-                                              d_from + r0, (int16_t *)c->comp.p + (size_t)r0 * (size_t)wstride,
-                                              (sk_prep *)c->prep.p + r0, motifs, motif_off, nmotifs, scale_mode, scale_low,
-                                              scale_hi, d_all + r0, nreads, d_out + r0, r0 > 0);
+                         return panel_dev_i16(c, q, d_sig, stride, d_len, nr, r0);
                      });
     if (rc) return rc;
     SK_HIP(hipMemcpyAsync(out, d_out, (size_t)nreads * sizeof(sk_panel_rec), hipMemcpyDeviceToHost, c->stream));
@@ -2386,11 +2305,9 @@ int sk_motifseq_panel_f64(const double *sig, const int64_t *off, int32_t nreads,
     double *d_wsig = (double *)c->panelwin.p;
     SK_HIP(hipMemcpyAsync(c->panelaux.p, aux.data(), aux.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if ((rc = sk_launch_region_rows_f64(c, (const double *)c->sig.p, d_src, d_woff, nreads, d_wsig))) return rc;
-    if ((rc = prep_f64(c, d_wsig, d_woff, nreads, wtotal, wmax, scale_mode, scale_low, scale_hi))) return rc;
     sk_sdtw_args a;
-    a.feed = SK_FEED_F64_NORM; a.samples = c->comp.p; a.samples_raw = d_wsig; a.stride = 0; a.off = d_woff;
-    a.prep = (const sk_prep *)c->prep.p; a.nreads = nreads; a.motif = nullptr; a.nmotif = 0; a.out = nullptr;
-    a.last_row = nullptr; a.max_len = wmax; a.force_single = 1;
+    if ((rc = prep_f64(c, d_wsig, d_woff, nreads, wtotal, wmax, scale_mode, scale_low, scale_hi, &a))) return rc;
+    a.motif = nullptr; a.nmotif = 0; a.out = nullptr; a.force_single = 1;
     sk_hit *d_all = (sk_hit *)c->panelrec.p;
     sk_panel_rec *d_out = (sk_panel_rec *)(d_all + (size_t)nreads * (size_t)nmotifs);
     if ((rc = sk_launch_panel_dtw(c, &a, motifs, motif_off, d_all, nreads))) return rc;
