@@ -158,6 +158,57 @@ int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_le
 int sk_segment_dev_f64(const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total, int64_t max_len,
                        const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs);
 
+/* ---- segment levels ----------------------------------------------------- */
+/* What a segment IS, and where it lies in the raw read.  get_segs returns index pairs into the filtered signal and
+ * nothing else (segmenter.py:399-470); a stall, a homopolymer stretch and an adapter differ in level and noise, measured
+ * against the read's own median and stdev (the two numbers get_segs builds its band from, segmenter.py:410-414).  With y
+ * the read after the [:Num] cut and scale_outliers (segmenter.py:207-209, 311-318) -- the array get_segs is given, int64
+ * for integer input, float64 for pA input (segmenter.py:198-201) -- kept[i] the raw index of y[i], and w = y[s:e] for a
+ * span [s, e) of y, one record holds, bit for bit what numpy gives on w in its own dtype:
+ *   mean   = np.mean(w)                 (np.add.reduce's order, as sk_bg_rec documents it)
+ *   std    = np.std(w)                  (ddof 0, two passes, the same order; one sample: 0.0)
+ *   median = np.median(w)               (even length: (a + b) / 2 of the two middle values)
+ *   mad    = np.median(np.abs(w - median))          (not multiplied by 1.4826)
+ *   min, max = float(w.min()), float(w.max())
+ *   raw_start = kept[s], raw_end = kept[e - 1] + 1: raw[raw_start:raw_end], filtered, is exactly w
+ *   n      = e - s
+ * A span with e <= s has six NaNs, raw_start = raw_end = -1 and n = 0; so has every unused slot, and every slot of a
+ * read with no surviving sample. */
+typedef struct sk_seg_level {       /* 64 bytes */
+    double  mean;
+    double  std;
+    double  median;
+    double  mad;
+    double  min;
+    double  max;
+    int32_t raw_start;
+    int32_t raw_end;
+    int32_t n;
+    int32_t pad;                    /* 0 */
+} sk_seg_level;
+/* levels is [nreads][max_segs]: the record of segs[r][k] = [start, end], end taken as exclusive (the slice
+ * segmenter.py's users cut, sig[start:end]).  read_level is [nreads]: the same record over the whole of y, [0, n) --
+ * top = median + std * std_scale and bot = median - std * std_scale of segmenter.py:413-414 follow from it in two
+ * float64 operations.  segs / nsegs and the return value (SK_ERR_OVERFLOW with the true counts in nsegs included):
+ * exactly what the sk_segment_batch_* / sk_segment_dev_* twin returns; the other arguments are its own.  A NULL levels
+ * or read_level is SK_ERR_INVALID. */
+int sk_segment_levels_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                          sk_seg_level *levels, sk_seg_level *read_level);
+/* ragged float64 reads with the caller's [:Num] cut (sk_segment_batch_f64_len; segmenter.py:198-199, 207) */
+int sk_segment_levels_f64_len(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,
+                              const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                              sk_seg_level *levels, sk_seg_level *read_level);
+/* the same for int32 centi-units (sk_segment_batch_centi_len) */
+int sk_segment_levels_centi_len(const int32_t *centi, const int64_t *off, const int32_t *len, int32_t nreads,
+                                const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                                sk_seg_level *levels, sk_seg_level *read_level);
+/* device-resident form of sk_segment_levels_i16 (all pointers device but p; nothing is synchronised;
+ * segmenter.py:209-211 per read) */
+int sk_segment_levels_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
+                              sk_seg_level *d_levels, sk_seg_level *d_read_level);
+
 /* ---- segmenter parameter sweep ----------------------------------------- */
 /* Every set of a grid over the same reads in one call: for set k and read r, what sk_segment_batch_i16 (or the float64
  * route) reports with set k's sk_seg_params, cut to the first two segments, and per set the counts segmenter.py's

@@ -154,6 +154,16 @@ class PoolRec(C.Structure):
 POOL_DTYPE = np.dtype({"names": ["level", "level_sd", "sd_mean", "dwell_mean", "dwell_sd", "cost_mean", "hits"],
                        "formats": ["<f8"] * 6 + ["<i4"], "offsets": [0, 8, 16, 24, 32, 40, 48], "itemsize": 56})
 
+class SegLevel(C.Structure):
+    """sk_seg_level: what the signal did in one segment (or in the whole filtered read), and where it lies in the raw read."""
+    _fields_ = [("mean", C.c_double), ("std", C.c_double), ("median", C.c_double), ("mad", C.c_double),
+                ("min", C.c_double), ("max", C.c_double), ("raw_start", C.c_int32), ("raw_end", C.c_int32),
+                ("n", C.c_int32), ("pad", C.c_int32)]
+
+
+LEVEL_DTYPE = np.dtype([("mean", "<f8"), ("std", "<f8"), ("median", "<f8"), ("mad", "<f8"), ("min", "<f8"), ("max", "<f8"),
+                        ("raw_start", "<i4"), ("raw_end", "<i4"), ("n", "<i4"), ("pad", "<i4")])
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -190,6 +200,10 @@ ABI = {
     "sk_segment_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(SegParams),
                                      _vp, _vp, C.c_int32]),
     "sk_segment_dev_f64": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.POINTER(SegParams), _vp, _vp, C.c_int32]),
+    "sk_segment_levels_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(SegParams), _vp, _vp, C.c_int32, _vp, _vp]),
+    "sk_segment_levels_f64_len": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(SegParams), _vp, _vp, C.c_int32, _vp, _vp]),
+    "sk_segment_levels_centi_len": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(SegParams), _vp, _vp, C.c_int32, _vp, _vp]),
+    "sk_segment_levels_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(SegParams), _vp, _vp, C.c_int32, _vp, _vp]),
     "sk_drna_segment_batch_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32]),
     "sk_drna_roll_batch_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp]),
     "sk_drna_segment_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, EVENT_DTYPE, HIT_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, EVENT_DTYPE, HIT_DTYPE, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -486,6 +486,140 @@ def segment_ragged_f64(values, off, lens=None, params=None, max_segs=64, devices
             max_segs = int(nsegs.max()) + 8
             continue
         return segs[:R], nsegs[:R]
+
+
+# ----------------------------------------------------------------------------
+# segment levels: per-segment and per-read signal statistics, raw coordinates
+# ----------------------------------------------------------------------------
+def no_levels(shape):
+    """LEVEL_DTYPE records of slots that hold no span: six NaNs, raw_start = raw_end = -1, n = 0."""
+    a = np.zeros(shape, dtype=LEVEL_DTYPE)
+    for f in ("mean", "std", "median", "mad", "min", "max"):
+        a[f] = np.nan
+    a["raw_start"] = a["raw_end"] = -1
+    return a
+
+
+def _levels_call(R, max_segs, devices, call):
+    """The shared tail of the levels calls: call(lo, hi, segs, nsegs, levels, read_level, max_segs) -> status over the
+    reads [lo, hi) (sharded over `devices` like segment_batch), max_segs grown until no read overflows."""
+    while True:
+        segs = np.zeros((max(R, 1), max_segs, 2), dtype=np.int32)
+        nsegs = np.zeros(max(R, 1), dtype=np.int32)
+        levels = no_levels((max(R, 1), max_segs))
+        read_level = no_levels(max(R, 1))
+        rc = _over_devices(devices, R, lambda lo, hi, ms=max_segs: call(lo, hi, segs, nsegs, levels, read_level, ms))
+        if rc == _lib.SK_ERR_OVERFLOW:
+            max_segs = int(nsegs.max()) + 8
+            continue
+        return segs[:R], nsegs[:R], levels[:R], read_level[:R]
+
+
+def segment_levels_ragged_f64(values, off, lens=None, params=None, max_segs=64, devices=None):
+    """segment_ragged_f64, and what every segment is: (segs, nsegs, levels, read_level).  levels[r, k] (LEVEL_DTYPE) is the
+    record of segs[r, k] = [s, e] over w = y[s:e], y the read after the cut and scale_outliers: np.mean, np.std, np.median,
+    np.median(np.abs(w - median)), min, max -- numpy's bits -- and raw_start, raw_end, the slice of the RAW read that,
+    filtered, is w.  read_level[r] is the same over all of y.  float64 values, or int32 centi-units."""
+    L = _lib.load()
+    centi = isinstance(values, np.ndarray) and values.dtype == np.int32
+    values = np.ascontiguousarray(values, dtype=np.int32 if centi else np.float64)
+    entry = L.sk_segment_levels_centi_len if centi else L.sk_segment_levels_f64_len
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    params = params or SegParams()
+    ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    return _levels_call(off.size - 1, max_segs, devices, lambda lo, hi, segs, nsegs, lv, rl, ms: entry(
+        ptr(values), ptr(off[lo:hi + 1]), None if ln is None else ptr(ln[lo:hi]), hi - lo, C.byref(params),
+        ptr(segs[lo:hi]), ptr(nsegs[lo:hi]), ms, ptr(lv[lo:hi]), ptr(rl[lo:hi])))
+
+
+def segment_levels_batch(sig, lens=None, params=None, max_segs=64, devices=None):
+    """segment_batch, and what every segment is: (segs, nsegs, levels, read_level) for the rows of an int16 [R, stride]
+    batch (see segment_levels_ragged_f64; w is int64 here, as segmenter.py:200-201 makes it).  Limits too wide for the
+    int16 kernels go through the float64 ones, like segment_batch's."""
+    L = _lib.load()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    if sig.ndim != 2:
+        raise ValueError("sig must be [reads, samples]")
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    params = params or SegParams()
+    if _too_wide_for_i16(params.lim_low, params.lim_hi):
+        off = np.arange(R + 1, dtype=np.int64) * stride
+        return segment_levels_ragged_f64(sig.astype(np.float64).reshape(-1), off, lens, params, max_segs, devices)
+    return _levels_call(R, max_segs, devices, lambda lo, hi, segs, nsegs, lv, rl, ms: L.sk_segment_levels_i16(
+        ptr(sig[lo:hi]), stride, ptr(lens[lo:hi]), hi - lo, C.byref(params), ptr(segs[lo:hi]), ptr(nsegs[lo:hi]), ms,
+        ptr(lv[lo:hi]), ptr(rl[lo:hi])))
+
+
+def pa_values(sig, lens, calib):
+    """The float64 pA reads segmenter.py makes of raw rows (convert_to_pA_numpy + np.round(.., 2), segmenter.py:345-349,
+    515-520; range cut to two decimals first, :385): a list of arrays."""
+    calib = np.asarray(calib, dtype=np.float64).reshape(-1, 3)
+    out = []
+    for r in range(len(lens)):
+        dig, ofs, rng = calib[r]
+        unit = float("{0:.2f}".format(rng)) / dig
+        out.append(np.round((np.asarray(sig[r][:lens[r]], dtype=np.float64) + ofs) * unit, 2))
+    return out
+
+
+def segment_levels_batch_pa(sig, lens, calib, params=None, max_segs=64, devices=None):
+    """segment_batch_pa's reads with their levels: the float64 pA values are formed first (pa_values) and go through the
+    float64 route, so that every record is numpy's on the pA array."""
+    flat, off = pack_f64(pa_values(sig, lens, calib))
+    return segment_levels_ragged_f64(flat, off, None, params, max_segs, devices)
+
+
+def segment_levels(reads, params=None):
+    """Mixed input, as segment_any: integer-valued reads that fit int16 through the int16 route, the rest through the
+    float64 one.  Returns (segs, nsegs, levels, read_level) in input order, max_segs the widest any route needed."""
+    ints, arrs, flts = _split_int16(reads)
+    parts = []
+    if ints:
+        buf, lens = pack_i16(arrs)
+        parts.append((ints, segment_levels_batch(buf, lens, params)))
+    if flts:
+        flat, off = pack_f64([reads[i] for i in flts])
+        parts.append((flts, segment_levels_ragged_f64(flat, off, None, params)))
+    R = len(reads)
+    ms = max([p[1][0].shape[1] for p in parts] or [1])
+    segs = np.zeros((R, ms, 2), dtype=np.int32)
+    nsegs = np.zeros(R, dtype=np.int32)
+    levels = no_levels((R, ms))
+    read_level = no_levels(R)
+    for idx, (sg, ns, lv, rl) in parts:
+        segs[idx, :sg.shape[1]] = sg
+        nsegs[idx] = ns
+        levels[idx, :lv.shape[1]] = lv
+        read_level[idx] = rl
+    return segs, nsegs, levels, read_level
+
+
+def thresholds_of(read_level, params=None):
+    """(top, bot) of get_segs from the whole-read records: median + std * std_scale and median - std * std_scale, two
+    float64 operations each in the order of segmenter.py:413-414."""
+    params = params or SegParams()
+    rl = np.asarray(read_level)
+    d = rl["std"].astype(np.float64) * np.float64(params.std_scale)
+    return rl["median"] + d, rl["median"] - d
+
+
+LEVELS_HEADER = ("fast5", "seg", "start", "end", "raw_start", "raw_end", "length", "mean", "stdev", "median", "mad", "min",
+                 "max", "read_median", "read_stdev", "top", "bot")
+
+
+def levels_lines(name, segs, levels, read_level, params=None):
+    """The rows `segmenter.py --levels FILE` writes for one printed read: one tab-separated line per segment, columns
+    LEVELS_HEADER, floats as Python's "{}" writes them.  segs: the [start, end] pairs printed for the read."""
+    top, bot = thresholds_of(read_level, params)
+    out = []
+    for k, (s, e) in enumerate(segs):
+        v = levels[k]
+        cols = [name, k, int(s), int(e), int(v["raw_start"]), int(v["raw_end"]), int(v["n"])]
+        cols += [float(v[f]) for f in ("mean", "std", "median", "mad", "min", "max")]
+        cols += [float(read_level["median"]), float(read_level["std"]), float(top), float(bot)]
+        out.append("\t".join("{}".format(c) for c in cols) + "\n")
+    return out
 
 
 def motifseq_multi_ragged_f64(values, off, motifs, scale="medmad", scale_low=0, scale_hi=1200, devices=None):

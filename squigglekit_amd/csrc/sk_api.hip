@@ -1160,7 +1160,8 @@ int sk_normalise_f64(const double *sig, int32_t len, int32_t scale_mode,
 
 // device-resident core of the int16 segmenter path (d_segs zeroed here)
 static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
-                           const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs)
+                           const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
+                           int *row16_out = nullptr)
 {
     int rc;
     int32_t lo = p->lim_low, hi = p->lim_hi;
@@ -1172,6 +1173,7 @@ static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
         // streaming statistics (sk_segstat.hip): reads of up to 4 096 samples, exact integer sums, certified
         // integer thresholds; the numpy-order kernel redoes the (almost always empty) list of uncertified reads
         const size_t mb = (size_t)nreads * (size_t)sk_segment_fast_row16(stride) * 16;
+        if (row16_out) *row16_out = sk_segment_fast_row16(stride);
         if ((rc = sk_reserve(c, &c->mask, mb))) return rc;
         int32_t *redo;
         if ((rc = redo_list(c, SK_REDO_I16, nreads, &redo))) return rc;
@@ -1183,6 +1185,7 @@ static int segment_dev_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, cons
     }
     // the numpy-order kernel for every read: it writes the streaming path's {in band, kept} entries, the same walk follows
     const int row16 = (int)((stride + 63) / 64);
+    if (row16_out) *row16_out = row16;
     if ((rc = sk_reserve(c, &c->comp, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
     if ((rc = sk_reserve(c, &c->mask, (size_t)nreads * (size_t)row16 * 16))) return rc;
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
@@ -1246,12 +1249,13 @@ static int segment_masks_f64(sk_ctx *c, const double *d_sig, const int64_t *d_of
 // device-resident core of the float64 segmenter path (d_off zero based; d_segs zeroed here)
 static int segment_dev_f64(sk_ctx *c, const double *d_sig, const int64_t *d_off, int32_t nreads, int64_t total,
                            int64_t maxlen, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
-                           const int32_t *d_rlen = nullptr)
+                           const int32_t *d_rlen = nullptr, int *row16_out = nullptr)
 {
     int row16;
     int rc = segment_masks_f64(c, d_sig, d_off, nreads, total, maxlen, p->lim_low, p->lim_hi, p->std_scale, d_rlen, &row16,
                                d_segs, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t));
     if (rc) return rc;
+    if (row16_out) *row16_out = row16;
     rc = sk_launch_seg_walk_masks(c, c->mask.p, row16, (const int32_t *)c->len.p, nreads, p, d_segs, d_nsegs, max_segs);
     if (rc) return rc;
     c->ev_valid = true;
@@ -1295,12 +1299,103 @@ static int segment_dev_i16_pa(sk_ctx *c, const int16_t *d_sig, int64_t stride, c
                            d_segs, d_nsegs, max_segs, d_len);
 }
 
+// ------------------------------------------------------------------ segment levels
+// What the levels entry points add to their segmenter twin: where the records go.  `on` distinguishes "not asked for"
+// (the plain segmenter entry points: both NULL) from a NULL the caller must not pass.
+struct levels_req {
+    bool          on = false;
+    sk_seg_level *levels = nullptr;       // [nreads][max_segs]: host (the batch entry points) or device (_dev)
+    sk_seg_level *read_level = nullptr;   // [nreads]
+};
+static levels_req levels_of(sk_seg_level *levels, sk_seg_level *read_level)
+{
+    levels_req q;
+    q.on = true; q.levels = levels; q.read_level = read_level;
+    return q;
+}
+
+// The records of nr reads whose segmenter route has just run on the stream (entries in c->mask, row16 per read):
+// d_levels / d_read_level are device pointers.
+static int levels_launch(sk_ctx *c, int feed, const void *d_samples, int64_t stride, const int64_t *d_off, int row16,
+                         const int32_t *d_len, int64_t mmax, int32_t nr, const int32_t *d_segs, const int32_t *d_nsegs,
+                         int32_t max_segs, sk_seg_level *d_levels, sk_seg_level *d_read_level)
+{
+    int rc;
+    if ((rc = sk_reserve(c, &c->seglevwork, sk_seglev_work_bytes(c, nr, max_segs, mmax)))) return rc;
+    return sk_launch_seg_levels(c, feed, d_samples, stride, d_off, c->mask.p, row16, d_len, mmax, nr, d_segs, d_nsegs,
+                                max_segs, c->seglevwork.p, d_levels, d_read_level);
+}
+
+// host entry points: room for the records of the whole call in c->seglev, and their way back (before read_segs: an
+// overflowing call returns its truncated records like its truncated segs)
+static int levels_reserve(sk_ctx *c, const levels_req &q, int32_t nreads, int32_t max_segs)
+{
+    if (!q.on) return SK_OK;
+    return sk_reserve(c, &c->seglev, (size_t)nreads * ((size_t)max_segs + 1) * sizeof(sk_seg_level));
+}
+static sk_seg_level *levels_dev(sk_ctx *c, int32_t r0, int32_t max_segs) { return (sk_seg_level *)c->seglev.p + (size_t)r0 * (size_t)max_segs; }
+static sk_seg_level *read_level_dev(sk_ctx *c, int32_t nreads, int32_t r0, int32_t max_segs)
+{
+    return (sk_seg_level *)c->seglev.p + (size_t)nreads * (size_t)max_segs + r0;
+}
+static int levels_copy_back(sk_ctx *c, const levels_req &q, int32_t nreads, int32_t max_segs)
+{
+    if (!q.on) return SK_OK;
+    SK_HIP(hipMemcpyAsync(q.levels, levels_dev(c, 0, max_segs), (size_t)nreads * (size_t)max_segs * sizeof(sk_seg_level),
+                          hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(q.read_level, read_level_dev(c, nreads, 0, max_segs), (size_t)nreads * sizeof(sk_seg_level),
+                          hipMemcpyDeviceToHost, c->stream));
+    return SK_OK;
+}
+
+// int16 rows on the device: the segmenter route, then (when asked for) the records
+static int levels_rows_i16(sk_ctx *c, const levels_req &q, const int16_t *d_sig, int64_t stride, const int32_t *d_len,
+                           int32_t nr, const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
+                           sk_seg_level *d_levels, sk_seg_level *d_read_level)
+{
+    int row16 = 0;
+    int rc = segment_dev_i16(c, d_sig, stride, d_len, nr, p, d_segs, d_nsegs, max_segs, &row16);
+    if (rc || !q.on) return rc;
+    return levels_launch(c, SK_FEED_I16, d_sig, stride, nullptr, row16, d_len, stride, nr, d_segs, d_nsegs, max_segs,
+                         d_levels, d_read_level);
+}
+
+static int segment_host_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const sk_seg_params *p,
+                            int32_t *segs, int32_t *nsegs, int32_t max_segs, const levels_req &q)
+{
+    SK_ENTER(c);
+    int rc = check_i16(sig, stride, len, nreads);
+    if (!rc) rc = check_len_host(len, nreads, stride);
+    if (!rc) rc = check_seg(p, max_segs, nreads, !segs || !nsegs, "segs/nsegs");
+    if (!rc && q.on && (!q.levels || !q.read_level)) rc = sk_fail(SK_ERR_INVALID, "NULL levels/read_level");
+    if (rc) return rc == SK_NOTHING ? SK_OK : rc;
+    const SubBatches B = sub_batches(nreads, stride);
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = levels_reserve(c, q, nreads, max_segs))) return rc;
+    if ((rc = redo_begin(c, nreads, B.n))) return rc;
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return levels_rows_i16(c, q, d_sig, stride, d_len, nr, p,
+                                                (int32_t *)c->out.p + (size_t)r0 * 2 * (size_t)max_segs, (int32_t *)c->out2.p + r0,
+                                                max_segs, q.on ? levels_dev(c, r0, max_segs) : nullptr,
+                                                q.on ? read_level_dev(c, nreads, r0, max_segs) : nullptr);
+                     });
+    if (rc) return rc;
+    if ((rc = levels_copy_back(c, q, nreads, max_segs))) return rc;
+    return read_segs(c, nreads, max_segs, segs, nsegs);
+}
+
 static int segment_batch_ragged(const void *sig, bool centi, const int64_t *off, const int32_t *len, int32_t nreads,
-                                const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
+                                const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                                const levels_req &q = levels_req())
 {
     SK_ENTER(c);
     if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
     int rc = check_seg(p, max_segs, nreads, !segs || !nsegs, "segs/nsegs");
+    if (!rc && q.on && (!q.levels || !q.read_level)) rc = sk_fail(SK_ERR_INVALID, "NULL levels/read_level");
     if (rc) return rc == SK_NOTHING ? SK_OK : rc;
     int64_t total, maxlen;
     if ((rc = stage_ragged_f64(c, sig, off, nreads, &total, &maxlen, centi))) return rc;
@@ -1321,10 +1416,19 @@ static int segment_batch_ragged(const void *sig, bool centi, const int64_t *off,
     }
     if ((rc = sk_reserve(c, &c->out, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t)))) return rc;
     if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = levels_reserve(c, q, nreads, max_segs))) return rc;
     if ((rc = redo_begin(c, nreads, 1))) return rc;
+    int row16 = 0;
     rc = segment_dev_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, total, maxlen, p,
-                         (int32_t *)c->out.p, (int32_t *)c->out2.p, max_segs, d_rlen);
+                         (int32_t *)c->out.p, (int32_t *)c->out2.p, max_segs, d_rlen, &row16);
     if (rc) return rc;
+    if (q.on) {                                      // (c->len: each read's raw length after the cut, as the walk read it)
+        rc = levels_launch(c, SK_FEED_F64_NORM, c->sig.p, 0, (const int64_t *)c->off.p, row16, (const int32_t *)c->len.p,
+                           maxlen, nreads, (const int32_t *)c->out.p, (const int32_t *)c->out2.p, max_segs,
+                           levels_dev(c, 0, max_segs), read_level_dev(c, nreads, 0, max_segs));
+        if (rc) return rc;
+        if ((rc = levels_copy_back(c, q, nreads, max_segs))) return rc;
+    }
     return read_segs(c, nreads, max_segs, segs, nsegs);
 }
 
@@ -1344,24 +1448,39 @@ int sk_segment_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_le
 int sk_segment_batch_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
                          const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs)
 {
+    return segment_host_i16(sig, stride, len, nreads, p, segs, nsegs, max_segs, levels_req());
+}
+
+int sk_segment_levels_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                          const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                          sk_seg_level *levels, sk_seg_level *read_level)
+{
+    return segment_host_i16(sig, stride, len, nreads, p, segs, nsegs, max_segs, levels_of(levels, read_level));
+}
+int sk_segment_levels_f64_len(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,
+                              const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                              sk_seg_level *levels, sk_seg_level *read_level)
+{
+    return segment_batch_ragged(sig, false, off, len, nreads, p, segs, nsegs, max_segs, levels_of(levels, read_level));
+}
+int sk_segment_levels_centi_len(const int32_t *centi, const int64_t *off, const int32_t *len, int32_t nreads,
+                                const sk_seg_params *p, int32_t *segs, int32_t *nsegs, int32_t max_segs,
+                                sk_seg_level *levels, sk_seg_level *read_level)
+{
+    return segment_batch_ragged(centi, true, off, len, nreads, p, segs, nsegs, max_segs, levels_of(levels, read_level));
+}
+int sk_segment_levels_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                              const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs,
+                              sk_seg_level *d_levels, sk_seg_level *d_read_level)
+{
     SK_ENTER(c);
-    int rc = check_i16(sig, stride, len, nreads);
-    if (!rc) rc = check_len_host(len, nreads, stride);
-    if (!rc) rc = check_seg(p, max_segs, nreads, !segs || !nsegs, "segs/nsegs");
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (!rc) rc = check_seg(p, max_segs, nreads, !d_segs || !d_nsegs, "segs/nsegs");
+    if (!rc && (!d_levels || !d_read_level)) rc = sk_fail(SK_ERR_INVALID, "NULL levels/read_level");
     if (rc) return rc == SK_NOTHING ? SK_OK : rc;
-    const SubBatches B = sub_batches(nreads, stride);
-    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->out, (size_t)nreads * 2 * (size_t)max_segs * sizeof(int32_t)))) return rc;
-    if ((rc = sk_reserve(c, &c->out2, (size_t)nreads * sizeof(int32_t)))) return rc;
-    if ((rc = redo_begin(c, nreads, B.n))) return rc;
-    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
-                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
-                         return segment_dev_i16(c, d_sig, stride, d_len, nr, p, (int32_t *)c->out.p + (size_t)r0 * 2 * (size_t)max_segs,
-                                                (int32_t *)c->out2.p + r0, max_segs);
-                     });
-    if (rc) return rc;
-    return read_segs(c, nreads, max_segs, segs, nsegs);
+    if ((rc = redo_begin(c, nreads, 1))) return rc;
+    return levels_rows_i16(c, levels_of(d_levels, d_read_level), d_sig, stride, d_len, nreads, p, d_segs, d_nsegs, max_segs,
+                           d_levels, d_read_level);
 }
 
 int sk_segment_batch_f64_len(const double *sig, const int64_t *off, const int32_t *len, int32_t nreads,

@@ -101,6 +101,8 @@ struct sk_ctx {
     sk_buf panelwin;  // motif panel: the window rows (int16, stride wstride) or the gathered float64 windows
     sk_buf panelaux;  // motif panel: per read window length, resolved begin, the caller's win rows / float64 offsets
     sk_buf panelrec;  // motif panel: [K][R] records when the caller takes none, and the host entry points' sk_panel_rec
+    sk_buf seglev;    // segment levels: the sk_seg_level records of the host entry points ([nreads][max_segs], then [nreads])
+    sk_buf seglevwork;    // segment levels: [0] = items, [4 ..] = the (read, slot) work list, then the long items' scratch rows
     std::vector<double> panel_host;           // laid-out motifs as uploaded (kept alive for the async H2D)
     std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
     std::vector<sk_panel_group> panel_groups;
@@ -414,6 +416,17 @@ int  sk_launch_prep_f64_listed(sk_ctx *c, const double *d_sig, const int64_t *d_
                                int row16, const int32_t *d_rlen = nullptr);
 int  sk_launch_seg_walk_masks(sk_ctx *c, const void *d_mask2, int row16, const int32_t *d_len, int32_t nreads,
                               const sk_seg_params *p, int32_t *d_segs, int32_t *d_nsegs, int32_t max_segs);
+
+// ---- segment levels (sk_seglev.hip) ----
+// Per-segment and per-read signal statistics over the {in band, kept} entries a segmenter route left at d_mask2 (row16 per
+// read; read r has min(d_len[r], mmax) raw samples) and the segments its walk reported (d_segs [nreads][max_segs][2],
+// d_nsegs [nreads]).  feed: SK_FEED_I16 (samples = int16 rows of `stride`) or SK_FEED_F64_NORM (samples = float64, read
+// r at d_off[r]).  levels [nreads][max_segs], read_level [nreads].  d_work: sk_seglev_work_bytes(..) bytes of scratch.
+size_t sk_seglev_work_bytes(sk_ctx *c, int32_t nreads, int32_t max_segs, int64_t mmax);
+int sk_launch_seg_levels(sk_ctx *c, int feed, const void *samples, int64_t stride, const int64_t *d_off,
+                         const void *d_mask2, int row16, const int32_t *d_len, int64_t mmax, int32_t nreads,
+                         const int32_t *d_segs, const int32_t *d_nsegs, int32_t max_segs, void *d_work,
+                         sk_seg_level *levels, sk_seg_level *read_level);
 
 // ---- SquigglePull text (sk_pull.hip) ----
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries

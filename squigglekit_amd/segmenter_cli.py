@@ -3,7 +3,7 @@
 Same flags, same stdout (`name<TAB>s0,e0,s1,e1,...`), same stderr strings, same exit
 codes; the per-read work (scale_outliers + get_segs) runs on the GPU in batches
 through the C ABI.  Reads are buffered `--batch` at a time and printed in input
-order.  Additive flags: --device, --batch, --blow5.  There is no CPU path.
+order.  Additive flags: --device, --batch, --blow5, --levels.  There is no CPU path.
 """
 import argparse
 import os
@@ -64,10 +64,29 @@ def build_parser():
                    help="[extension] write reads / reads per second / input GB per second / GPU calls of this run to PATH "
                         "as JSON (also $SK_STATS_JSON); stdout and stderr stay the reference's")
     p.add_argument("--stats", action="store_true", help="[extension] the same as one line on stderr at the end")
+    p.add_argument("--levels", default=None, metavar="FILE",
+                   help="[extension] write one line per printed segment to FILE: raw coordinates, mean, stdev, median, MAD, "
+                        "min, max of its samples, the read's median and stdev and the band; stdout and stderr stay the "
+                        "reference's")
     return p
 
 
 _STATS = [_Stats("segmenter")]      # this run's throughput counters (--stats-json / --stats)
+
+
+class LevelsWriter:
+    """--levels FILE: a header, then one line per segment of every printed read (api.levels_lines)."""
+
+    def __init__(self, path, params):
+        self.fh = open(path, "w")
+        self.params = params
+        self.fh.write("\t".join(api.LEVELS_HEADER) + "\n")
+
+    def read(self, name, segs, levels, read_level):
+        self.fh.writelines(api.levels_lines(name, segs, levels, read_level, self.params))
+
+    def close(self):
+        self.fh.close()
 
 
 class _Batcher:
@@ -78,6 +97,11 @@ class _Batcher:
         self.params = SegParams.from_args(args)
         self.names, self.sigs = [], []
         self._pending, self._worker = None, None
+        self.levels = LevelsWriter(args.levels, self.params) if getattr(args, "levels", None) else None
+        # with --levels every GPU call is its levels twin: the same segs / nsegs, and the records
+        self.seg_batch = api.segment_levels_batch if self.levels else api.segment_batch
+        self.seg_batch_pa = api.segment_levels_batch_pa if self.levels else api.segment_batch_pa
+        self.seg_ragged = api.segment_levels_ragged_f64 if self.levels else api.segment_ragged_f64
 
     def add(self, name, sig, miss_name=None):
         self.names.append((name, miss_name if miss_name is not None else name))
@@ -90,8 +114,9 @@ class _Batcher:
         self.names.append((None, message))
         self.sigs.append(None)
 
-    def emit(self, name, miss, segs):
-        """What the reference does with one read's get_segs result (segmenter.py:211-227)."""
+    def emit(self, name, miss, segs, lev=None):
+        """What the reference does with one read's get_segs result (segmenter.py:211-227).  lev: the read's
+        (levels, read_level) for --levels, written when the read is printed."""
         if not segs:
             sys.stderr.write("no segments found: {}".format(miss))            # segmenter.py:213
             return
@@ -102,6 +127,8 @@ class _Batcher:
                     sys.stderr.write("no segs for testing: {}".format(miss))   # :219 (TSV branch only)
                 return
         print("\t".join([name, ",".join(str(v) for pair in segs for v in pair)]))
+        if lev is not None:
+            self.levels.read(name, segs, lev[0], lev[1])
 
     def flush(self):
         self.drain()                                  # (a pipelined block's table comes first)
@@ -110,12 +137,18 @@ class _Batcher:
         live = [s for s in self.sigs if s is not None]
         if live:
             _STATS[0].batch(len(live))
-        results = iter(api.segment_any(live, self.params) if live else [])
+        levs = iter([])
+        if self.levels and live:
+            segs, nsegs, lv, rl = api.segment_levels(live, self.params)
+            results = iter([segs[i, :nsegs[i]].tolist() if nsegs[i] else False for i in range(len(live))])
+            levs = iter(zip(lv, rl))
+        else:
+            results = iter(api.segment_any(live, self.params) if live else [])
         for (name, miss), sig in zip(self.names, self.sigs):
             if sig is None:
                 sys.stderr.write(miss)
                 continue
-            self.emit(name, miss, next(results))
+            self.emit(name, miss, next(results), next(levs, None))
         self.names, self.sigs = [], []
 
     def rows(self, rows, nsamp, name_col, name_of):
@@ -130,7 +163,7 @@ class _Batcher:
             from concurrent.futures import ThreadPoolExecutor
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d reads to the GPU worker" % len(nsamp))
-        job = self._worker.submit(api.segment_batch, rows, lens, self.params)
+        job = self._worker.submit(self.seg_batch, rows, lens, self.params)
         prev, self._pending = self._pending, (job, len(nsamp), name_col, name_of)
         if prev is not None:
             self._finish(prev)
@@ -146,7 +179,7 @@ class _Batcher:
         if self._worker is None:
             from concurrent.futures import ThreadPoolExecutor
             self._worker = ThreadPoolExecutor(1)
-        job = self._worker.submit(api.segment_batch_pa, rows, lens, calib, self.params)
+        job = self._worker.submit(self.seg_batch_pa, rows, lens, calib, self.params)
         prev, self._pending = self._pending, (job, len(nsamp), name_col, name_of)
         if prev is not None:
             self._finish(prev)
@@ -162,7 +195,7 @@ class _Batcher:
             from concurrent.futures import ThreadPoolExecutor
             self._worker = ThreadPoolExecutor(1)
         _mark("block of %d float64 reads to the GPU worker" % fb.n)
-        job = self._worker.submit(api.segment_ragged_f64, fb.batch_values(), fb.off, lens, self.params)
+        job = self._worker.submit(self.seg_ragged, fb.batch_values(), fb.off, lens, self.params)
         prev, self._pending = self._pending, (job, fb.n, ("span", fb.buf, fb.spans("name")), lambda i, b=fb: b.text("name", i))
         if prev is not None:
             self._finish(prev)
@@ -174,14 +207,17 @@ class _Batcher:
 
     def _finish(self, p):
         job, n, name_col, name_of = p
-        segs, nsegs = job.result()
+        segs, nsegs, *lev = job.result()
         _STATS[0].batch(n)
         _mark("block of %d reads back from the GPU" % n)
         if self.args.test:
             for i in range(n):
                 nm = name_of(i)
-                self.emit(nm, nm, segs[i, :nsegs[i]].tolist() if nsegs[i] else False)
+                self.emit(nm, nm, segs[i, :nsegs[i]].tolist() if nsegs[i] else False, (lev[0][i], lev[1][i]) if lev else None)
             return
+        if lev:
+            for i in np.flatnonzero(nsegs):
+                self.levels.read(name_of(int(i)), segs[i, :nsegs[i]].tolist(), lev[0][i], lev[1][i])
         for i in np.flatnonzero(nsegs == 0):
             sys.stderr.write("no segments found: {}".format(name_of(int(i))))          # segmenter.py:213
         off = np.zeros(n + 1, dtype=np.int64)
@@ -209,14 +245,14 @@ class _Batcher:
             ns = blk.nsamp[idx]
             lens = (np.maximum(ns + Num, 0) if Num < 0 else np.minimum(ns, Num)).astype(np.int32)   # sig[:Num]
             rows = blk.rows[idx] if idx.size != blk.n else blk.rows
-            segs, nsegs = api.segment_batch(rows, lens, self.params)
+            segs, nsegs, *lev = self.seg_batch(rows, lens, self.params)
             _STATS[0].batch(idx.size)
             res = {int(i): k for k, i in enumerate(idx)}
         for i in range(blk.n):
             k = res.get(i)
             if k is not None:
                 name = blk.name(i)
-                self.emit(name, name, segs[k, :nsegs[k]].tolist() if nsegs[k] else False)
+                self.emit(name, name, segs[k, :nsegs[k]].tolist() if nsegs[k] else False, (lev[0][k], lev[1][k]) if lev else None)
                 continue
             fl = int(blk.flags[i])
             if (fl & 27) == 1:                                              # integers, all zero: segmenter.py:203-205
@@ -365,6 +401,8 @@ def main(argv=None):
                     out.add(read, np.array(sig[:args.Num], dtype=float), miss_name=label)
     out.drain()
     out.flush()
+    if out.levels:
+        out.levels.close()
     _mark("end of main()")
     _STATS[0].finish(args, [args.signal, args.blow5, args.i16] + list(args.ind or []))
     sys.stderr.write("Done")                        # segmenter.py:297

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle sweep over shapes the unit tests do not pin: random read counts, ragged
 lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; and, per round, one drawn case each
-of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py).
+of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py);
+the segment levels of every segmenter round against plain numpy.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -20,6 +21,33 @@ import randcases                                      # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
+
+
+def levels_mismatch(levels, read_level, reads, segs, nsegs, lo, hi):
+    """None, or where the records differ from numpy's on the given segments (doubles by bit pattern)"""
+    want_l, want_r = api.no_levels(levels.shape), api.no_levels(len(reads))
+
+    def one(w, kept, s):
+        m = np.median(w)
+        return (np.mean(w), np.std(w), m, np.median(np.abs(w - m)), w.min(), w.max(), kept[s], kept[s + len(w) - 1] + 1, len(w), 0)
+    for r, a in enumerate(reads):
+        kept = np.flatnonzero((a > lo) & (a < hi))
+        y = a[kept]
+        if y.size:
+            want_r[r] = one(y, kept, 0)
+        for k in range(min(int(nsegs[r]), levels.shape[1])):
+            s, e = segs[r, k]
+            if len(y[s:e]):
+                want_l[r, k] = one(y[s:e], kept, s)
+    for got, want, what in ((levels, want_l, "levels"), (read_level, want_r, "read_level")):
+        for f in got.dtype.names:
+            g, w = np.ascontiguousarray(got[f]), np.ascontiguousarray(want[f])
+            if g.dtype.kind == "f":
+                g, w = g.view(np.uint64), w.view(np.uint64)
+            d = np.argwhere(g != w)
+            if d.size:
+                return "%s.%s at %s: got %r want %r" % (what, f, d[0].tolist(), got[f][tuple(d[0])], want[f][tuple(d[0])])
+    return None
 
 
 def main():
@@ -89,6 +117,16 @@ def main():
                 not np.array_equal(segs[r, :nsegs[r]], osegs[r, :nsegs[r]]) for r in range(R)):
             bad += 1
             print("SEGMENTER mismatch R=%d M=%d %s ownpass=%s" % (R, M, kw, os.environ.get("SK_WALK_OWNPASS")))
+        # ---- segment levels: the same call with its records, against plain numpy on the oracle's segments ----
+        s2, n2, lv, rl = api.segment_levels_batch(sig, lens, p, max_segs=segs.shape[1])
+        if not np.array_equal(n2, nsegs) or not np.array_equal(s2, segs):
+            bad += 1
+            print("LEVELS segs differ from segment_batch R=%d M=%d %s" % (R, M, kw))
+        else:
+            why = levels_mismatch(lv, rl, [sig[r, :lens[r]].astype(np.int64) for r in range(R)], osegs, onsegs, p.lim_low, p.lim_hi)
+            if why:
+                bad += 1
+                print("LEVELS mismatch R=%d M=%d %s: %s" % (R, M, kw, why))
         os.environ.pop("SK_WALK_OWNPASS", None)
         # ---- float64 reads (pA-like), per-read oracle composition ----
         # (round 4: reads of up to 4 096 samples take the streaming statistics kernel, sk_f64stat.hip -- histogram median,
