@@ -792,6 +792,47 @@ int sk_pull_text_dev(const int16_t *d_sig, int64_t stride, const int32_t *d_len,
                      int32_t mode, const char *d_prefix, const int64_t *d_prefix_off, char *d_text, int64_t capacity,
                      int64_t *total, int64_t *d_line_off);
 
+/* ---- event detection ---------------------------------------------------- */
+/* A read cut into its own sequence of levels, without a model: a boundary wherever the current steps.  The definition is
+ * the project's own ("Event detection"; tests/detect_ref.py states it in numpy); the reference has no such
+ * step (its segmenter.py lists "push algorithm into C" and "integration with MotifSeq" as open).  Per read x[0..n) of raw
+ * int16 samples -- no outlier filter, no [:Num] cut, raw coordinates throughout -- and per window w in (w_short, w_long),
+ * with s1, s2 the sums and q1, q2 the sums of squares of x[i-w..i) and x[i..i+w), all exact integers:
+ *     t_w[i] = sqrt( (double)((s2-s1)^2 * w) / (double)max(w*(q1+q2) - s1^2 - s2^2, 1) )   for w <= i <= n - w, else 0.0
+ * (one correctly rounded division, one correctly rounded square root: the two-sample t-statistic, invariant under the
+ * affine pA calibration).  Two peak detectors, short first, walk i = 0 .. n-1 with state pos = -1, val = +inf,
+ * valid = false, masked_to = -1 each and cur = t_k[i]:
+ *     skip the detector when i <= masked_to[k];
+ *     pos == -1:  cur < val: val = cur;  else cur - val > peak_height: val = cur, pos = i;
+ *     else:       cur > val: val = cur, pos = i;
+ *                 k short and val > th_short: masked_to[long] = pos + w_short, the long detector back to its first state;
+ *                 val - cur > peak_height and val > th_k: valid = true;
+ *                 valid and i - pos > w_k / 2 (integer division): pos is marked; pos = -1, val = cur, valid = false.
+ * Boundaries: 0, the marked positions (> 0, sorted, merged), n.  Events: the intervals between consecutive boundaries;
+ * n = 0 has none, a read without a mark has [0, n).  A record holds an event's exact integers; mean = sum / length and
+ * stdv = sqrt(max(length * sumsq - sum^2, 0)) / length are the host's to derive.
+ * Valid parameters: 1 <= w_short <= w_long <= 64, finite thresholds, finite peak_height >= 0 (SK_ERR_INVALID otherwise).
+ * Presets: dna = {3, 6, 1.4, 9.0, 0.2}, rna = {7, 14, 2.5, 9.0, 1.0}. */
+typedef struct sk_det_params {      /* 32 bytes */
+    int32_t w_short, w_long;
+    double  th_short, th_long, peak_height;
+} sk_det_params;
+typedef struct sk_det_event {       /* 24 bytes */
+    int32_t start, length;
+    int64_t sum, sumsq;
+} sk_det_event;
+/* Rows of `stride` samples, len[r] clamped into [0, stride].  off gets nreads + 1 entries, always: read r's events are
+ * rec[off[r] .. off[r+1]).  The records are written only when off[nreads] <= cap; otherwise the call returns
+ * SK_ERR_OVERFLOW, off is complete and nothing is written to rec.  rec == NULL with cap == 0 is the counting call (it
+ * returns SK_OK when there are no events at all).  NULL p / off, rec == NULL with cap > 0, cap < 0: SK_ERR_INVALID; the
+ * arguments are checked before the device is looked at. */
+int sk_detect_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const sk_det_params *p, int64_t *off /* [nreads + 1] */, sk_det_event *rec, int64_t cap);
+/* device-resident form (all pointers device but p; nothing is synchronised): the check against cap happens on the
+ * device, so the call returns SK_OK and the caller reads d_off[nreads] -- above cap, d_rec is untouched. */
+int sk_detect_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const sk_det_params *p, int64_t *d_off /* [nreads + 1] */, sk_det_event *d_rec, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,24 @@ class SegLevel(C.Structure):
 LEVEL_DTYPE = np.dtype([("mean", "<f8"), ("std", "<f8"), ("median", "<f8"), ("mad", "<f8"), ("min", "<f8"), ("max", "<f8"),
                         ("raw_start", "<i4"), ("raw_end", "<i4"), ("n", "<i4"), ("pad", "<i4")])
 
+class DetParams(C.Structure):
+    """sk_det_params: windows, thresholds and peak height of event detection (the header's "event detection" section
+    states the definition); the defaults are its dna preset."""
+    _fields_ = [("w_short", C.c_int32), ("w_long", C.c_int32), ("th_short", C.c_double), ("th_long", C.c_double),
+                ("peak_height", C.c_double)]
+
+    def __init__(self, w_short=3, w_long=6, th_short=1.4, th_long=9.0, peak_height=0.2):
+        super().__init__(w_short, w_long, th_short, th_long, peak_height)
+
+
+class DetEvent(C.Structure):
+    """sk_det_event: one event [start, start + length) of a read in raw coordinates, with the exact sum and sum of squares
+    of its samples."""
+    _fields_ = [("start", C.c_int32), ("length", C.c_int32), ("sum", C.c_int64), ("sumsq", C.c_int64)]
+
+
+DET_EVENT_DTYPE = np.dtype([("start", "<i4"), ("length", "<i4"), ("sum", "<i8"), ("sumsq", "<i8")])
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -295,6 +313,11 @@ ABI = {
     "sk_segment_sweep_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
     "sk_segment_sweep_f64": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp]),
     "sk_pull_text_dev": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _i64p, _vp]),
+    # event detection (the definition: "event detection" in include/squigglekit_hip.h and DESIGN.md; tests/detect_ref.py
+    # states it in numpy): sig, stride, len, nreads, params, off [nreads + 1], rec, cap
+    "sk_detect_events_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(DetParams), _vp, _vp, C.c_int64]),
+    # ... its device-resident form (all pointers device but params; the check against cap happens on the device)
+    "sk_detect_events_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(DetParams), _vp, _vp, C.c_int64]),
 }
 
 

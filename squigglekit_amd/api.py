@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, EVENT_DTYPE, HIT_DTYPE, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -1480,3 +1480,94 @@ def region_rows(sig, lens, region=(0, None), win=None):
         check(L.sk_region_rows_i16(ptr(sig), stride, ptr(lens), R, begin, end, None if win is None else ptr(win), wstride,
                                    ptr(rows), ptr(wlen), ptr(frm)))
     return rows, wlen, frm
+
+
+# ----------------------------------------------------------------------------
+# event detection: a read cut into its own sequence of levels (the definition: "event detection" in
+# include/squigglekit_hip.h and DESIGN.md)
+# ----------------------------------------------------------------------------
+DET_PRESETS = {"dna": dict(w_short=3, w_long=6, th_short=1.4, th_long=9.0, peak_height=0.2),
+               "rna": dict(w_short=7, w_long=14, th_short=2.5, th_long=9.0, peak_height=1.0)}
+
+
+def det_params(preset="dna", **overrides):
+    """The sk_det_params of a named preset ("dna" or "rna") with single fields replaced: det_params("rna", th_long=8.0)."""
+    if preset not in DET_PRESETS:
+        raise ValueError("preset %r: need one of %s" % (preset, sorted(DET_PRESETS)))
+    kw = dict(DET_PRESETS[preset])
+    for k, v in overrides.items():
+        if k not in kw:
+            raise TypeError("det_params: no field %r (fields: %s)" % (k, ", ".join(kw)))
+        kw[k] = v
+    return DetParams(int(kw["w_short"]), int(kw["w_long"]), float(kw["th_short"]), float(kw["th_long"]),
+                     float(kw["peak_height"]))
+
+
+def detect_events_batch(sig, lens=None, params=None):
+    """Event detection for every row of an int16 [R, stride] batch of RAW samples (no outlier filter, no cut; raw
+    coordinates).  Returns (off int64 [R + 1], rec DET_EVENT_DTYPE [off[R]]): read r's events are rec[off[r]:off[r + 1]],
+    each with start, length and the exact sum and sum of squares of its samples.  The room for the records is a first
+    guess (one event per eight samples); a batch that needs more is counted by that call and runs again with the count.
+    Single device (the calling thread's): the ragged output is not sharded over `devices`."""
+    L = _lib.ensure_init()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    if sig.ndim != 2:
+        raise ValueError("sig must be [reads, samples]")
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    if lens.shape != (R,):
+        raise ValueError("lens must hold one length per row")
+    params = params or det_params()
+    off = np.zeros(R + 1, dtype=np.int64)
+    if R == 0 or stride == 0:
+        return off, np.zeros(0, dtype=DET_EVENT_DTYPE)
+    cap = int(np.clip(lens, 0, stride).sum()) // 8 + R
+    while True:
+        rec = np.zeros(cap, dtype=DET_EVENT_DTYPE)
+        rc = L.sk_detect_events_i16(ptr(sig), stride, ptr(lens), R, C.byref(params), ptr(off), ptr(rec), cap)
+        if rc == _lib.SK_ERR_OVERFLOW and int(off[R]) > cap:
+            cap = int(off[R])
+            continue
+        check(rc)
+        return off, rec[:int(off[R])]
+
+
+def detect_events(reads, params=None):
+    """detect_events_batch for a list of reads of any lengths.  Every read must hold int16-exact values: the detector runs
+    on the raw samples, and as its statistic does not change under the affine pA calibration, pA users detect on the raw
+    samples too (event_levels maps the levels to pA).  A float read that is not int16-exact raises ValueError."""
+    arrs = []
+    for i, r in enumerate(reads):
+        b = as_int16_exact(r)
+        if b is None:
+            raise ValueError("read %d is not int16-exact: event detection takes raw samples (detect on the raw read; "
+                             "event_levels(off, rec, calib) gives the levels in pA)" % i)
+        arrs.append(np.asarray(b).reshape(-1))
+    buf, lens = pack_i16(arrs)
+    return detect_events_batch(buf, lens, params)
+
+
+def event_levels(off, rec, calib=None):
+    """(values float64, off): the level of every event, sum / length, as the ragged rows motifseq_multi_ragged_f64,
+    motifseq_hits_ragged_f64 and dtw_subsequence_batch (after a split at off) take.  calib [R, 3] = digitisation, offset,
+    range per read: the levels in pA, by pa_values' expression."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    rec = np.asarray(rec)
+    values = rec["sum"].astype(np.float64) / rec["length"].astype(np.float64)
+    if calib is not None:
+        calib = np.asarray(calib, dtype=np.float64).reshape(-1, 3)
+        if len(calib) != off.size - 1:
+            raise ValueError("calib must hold one (digitisation, offset, range) per read")
+        unit = np.array([float("{0:.2f}".format(rng)) / dig for dig, _, rng in calib], dtype=np.float64)
+        per = np.diff(off)
+        values = np.round((values + np.repeat(calib[:, 1], per)) * np.repeat(unit, per), 2)
+    return values, off
+
+
+def event_stdv(rec):
+    """The standard deviation of every event's samples (ddof 0) from its exact integers:
+    sqrt(max(length * sumsq - sum * sum, 0)) / length in float64."""
+    rec = np.asarray(rec)
+    n = rec["length"].astype(np.int64)
+    var = np.maximum(n * rec["sumsq"] - rec["sum"] * rec["sum"], 0)
+    return np.sqrt(var.astype(np.float64)) / n.astype(np.float64)

@@ -2482,3 +2482,88 @@ int sk_region_rows_i16(const int16_t *sig, int64_t stride, const int32_t *len, i
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ event detection (sk_detect.hip)
+// The definition: include/squigglekit_hip.h, "event detection".  Mark and count per sub-batch, one scan over the whole
+// call, then the records.
+namespace {
+
+int check_detect(const void *sig, int64_t stride, const int32_t *len, int32_t nreads, const sk_det_params *p,
+                 const int64_t *off, const sk_det_event *rec, int64_t cap)
+{
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if (!p) return sk_fail(SK_ERR_INVALID, "NULL sk_det_params");
+    if (p->w_short < 1 || p->w_short > p->w_long || p->w_long > 64)
+        return sk_fail(SK_ERR_INVALID, "windows must satisfy 1 <= w_short <= w_long <= 64 (got %d, %d)", p->w_short, p->w_long);
+    if (!isfinite(p->th_short) || !isfinite(p->th_long)) return sk_fail(SK_ERR_INVALID, "the thresholds must be finite");
+    if (!isfinite(p->peak_height) || p->peak_height < 0) return sk_fail(SK_ERR_INVALID, "peak_height must be finite and >= 0");
+    if (!off) return sk_fail(SK_ERR_INVALID, "NULL off");
+    if (cap < 0) return sk_fail(SK_ERR_INVALID, "cap < 0");
+    if (cap > 0 && !rec) return sk_fail(SK_ERR_INVALID, "NULL rec with a cap");
+    if ((int64_t)nreads * sk_detect_words(stride) > ((int64_t)1 << 40))
+        return sk_fail(SK_ERR_UNSUPPORTED, "detect: %d rows of %lld samples in one call", nreads, (long long)stride);
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_detect_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const sk_det_params *p, int64_t *d_off, sk_det_event *d_rec, int64_t cap)
+{
+    int rc = check_detect(d_sig, stride, d_len, nreads, p, d_off, d_rec, cap);
+    if (rc) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) {
+        SK_HIP(hipMemsetAsync(d_off, 0, sizeof(int64_t), c->stream));
+        return SK_OK;
+    }
+    if ((rc = sk_reserve(c, &c->detect, sk_detect_work_bytes(nreads, stride)))) return rc;
+    int64_t *d_bsum = (int64_t *)c->detect.p + (size_t)nreads * (size_t)sk_detect_words(stride);
+    if ((rc = sk_launch_detect_mark(c, d_sig, stride, d_len, nreads, p, c->detect.p, d_off))) return rc;
+    if ((rc = sk_launch_detect_scan(c, nreads, d_bsum, d_off))) return rc;
+    return sk_launch_detect_fill(c, d_sig, stride, d_len, nreads, p, c->detect.p, d_off, d_rec, cap);
+}
+
+int sk_detect_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
+                         const sk_det_params *p, int64_t *off, sk_det_event *rec, int64_t cap)
+{
+    int rc = check_detect(sig, stride, len, nreads, p, off, rec, cap);
+    if (rc) return rc;
+    SK_ENTER(c);
+    off[0] = 0;
+    if (nreads == 0) return SK_OK;
+    const SubBatches B = sub_batches(nreads, stride);
+    const int64_t W = sk_detect_words(stride);
+    const size_t off_bytes = ((size_t)nreads + 2) / 2 * 2 * sizeof(int64_t);         // (the records start 16-byte aligned)
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->detect, sk_detect_work_bytes(nreads, stride)))) return rc;
+    if ((rc = sk_reserve(c, &c->detectout, off_bytes + (size_t)cap * sizeof(sk_det_event)))) return rc;
+    uint64_t *d_words = (uint64_t *)c->detect.p;
+    int64_t *d_bsum = (int64_t *)c->detect.p + (size_t)nreads * (size_t)W;
+    int64_t *d_off = (int64_t *)c->detectout.p;
+    sk_det_event *d_rec = cap > 0 ? (sk_det_event *)((char *)c->detectout.p + off_bytes) : nullptr;
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return sk_launch_detect_mark(c, d_sig, stride, d_len, nr, p, d_words + (size_t)r0 * (size_t)W, d_off + r0);
+                     });
+    if (rc) return rc;
+    if ((rc = sk_launch_detect_scan(c, nreads, d_bsum, d_off))) return rc;
+    SK_HIP(hipMemcpyAsync(off, d_off, ((size_t)nreads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    const int64_t total = off[nreads];
+    if (total > cap)
+        return sk_fail(SK_ERR_OVERFLOW, "the reads hold %lld events, cap is %lld", (long long)total, (long long)cap);
+    if (total == 0) return SK_OK;
+    if ((rc = sk_launch_detect_fill(c, (const int16_t *)c->sig.p, stride, (const int32_t *)c->len.p, nreads, p, d_words, d_off,
+                                    d_rec, cap)))
+        return rc;
+    SK_HIP(hipMemcpyAsync(rec, d_rec, (size_t)total * sizeof(sk_det_event), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+} // extern "C"

@@ -103,6 +103,8 @@ struct sk_ctx {
     sk_buf panelrec;  // motif panel: [K][R] records when the caller takes none, and the host entry points' sk_panel_rec
     sk_buf seglev;    // segment levels: the sk_seg_level records of the host entry points ([nreads][max_segs], then [nreads])
     sk_buf seglevwork;    // segment levels: [0] = items, [4 ..] = the (read, slot) work list, then the long items' scratch rows
+    sk_buf detect;    // event detection: the mark words [nreads][ceil(stride / 64)], then the scan's block sums (sk_detect.hip)
+    sk_buf detectout; // event detection: off [nreads + 1], then the sk_det_event records of the host entry point
     std::vector<double> panel_host;           // laid-out motifs as uploaded (kept alive for the async H2D)
     std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
     std::vector<sk_panel_group> panel_groups;
@@ -427,6 +429,19 @@ int sk_launch_seg_levels(sk_ctx *c, int feed, const void *samples, int64_t strid
                          const void *d_mask2, int row16, const int32_t *d_len, int64_t mmax, int32_t nreads,
                          const int32_t *d_segs, const int32_t *d_nsegs, int32_t max_segs, void *d_work,
                          sk_seg_level *levels, sk_seg_level *read_level);
+
+// ---- event detection (sk_detect.hip) ----
+// Mark: the mark words of read r (one bit per sample, sk_detect_words(stride) words of 8 bytes per read) at d_words and
+// its event count, as int64, at d_cnt[r].  Scan: d_off[0 .. nreads) counts -> d_off[0 .. nreads] offsets (d_bsum:
+// sk_scan_blocks(nreads) entries).  Fill: the records at d_rec[d_off[r] ..], nothing when d_off[nreads] > cap.
+// sk_detect_work_bytes: the words of nreads rows and the block sums behind them.
+int64_t sk_detect_words(int64_t stride);
+size_t  sk_detect_work_bytes(int32_t nreads, int64_t stride);
+int sk_launch_detect_mark(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                          const sk_det_params *p, void *d_words, int64_t *d_cnt);
+int sk_launch_detect_scan(sk_ctx *c, int32_t nreads, int64_t *d_bsum, int64_t *d_off);
+int sk_launch_detect_fill(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                          const sk_det_params *p, const void *d_words, const int64_t *d_off, sk_det_event *d_rec, int64_t cap);
 
 // ---- SquigglePull text (sk_pull.hip) ----
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries

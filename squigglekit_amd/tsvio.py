@@ -392,6 +392,29 @@ def read_scrappie_model(path):
     return models, order, lens
 
 
+def read_scrappie_levels(path):
+    """The per-base currents of a scrappie model without the dwell expansion: (levels, order, dwells) with
+    levels[name] a float64 array of one current per row of the model and dwells[name] the rounded dwell of each row
+    (np.repeat(levels[name], dwells[name]) is read_scrappie_model's vector).  What event-space search runs against:
+    the levels of detected events (api.event_levels) are compared with a model's levels, not with its samples."""
+    levels, order, dwells, name = {}, [], {}, None
+    with open_text(path) as fh:
+        for line in fh:
+            line = line.strip("\n")
+            if not line or line[:3] == "pos":
+                continue
+            if line[0] == "#":
+                name = line[1:]
+                levels[name], dwells[name] = [], []
+                order.append(name)
+            else:
+                f = line.split()
+                levels[name].append(float(f[2]))
+                dwells[name].append(int(round(float(f[4]))))
+    return ({k: np.array(v, dtype=np.float64) for k, v in levels.items()}, order,
+            {k: np.array(v, dtype=np.int64) for k, v in dwells.items()})
+
+
 def read_scrappie_model_bases(path):
     """read_scrappie_model plus the base table behind the expansion: (models, order, L, bases) with bases[name] a list
     of (pos, base, current, first point, point count) per row of the model -- the points first .. first + count - 1 of

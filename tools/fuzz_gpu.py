@@ -2,7 +2,8 @@
 """Randomised GPU-vs-oracle sweep over shapes the unit tests do not pin: random read counts, ragged
 lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; and, per round, one drawn case each
 of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py);
-the segment levels of every segmenter round against plain numpy.
+the segment levels of every segmenter round against plain numpy; event detection (random read counts, lengths, strides and
+parameters) against the numpy statement of its definition (tests/detect_ref.py).
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -378,6 +379,38 @@ def main():
                 print("EVENTS mismatch round %d %s: %s" % (rounds, randcases.describe(case), msg))
         for key in randcases.SWITCHES:
             os.environ.pop(key, None)
+        # ---- event detection: random read counts, lengths and parameters against the numpy statement of the
+        # definition (tests/detect_ref.py); every off and every record field exactly
+        import detect_ref
+        dn = int(rng.choice([1, 3, 63, 64, 65, 200]))
+        dmax = int(rng.choice([8, 70, 130, 300, 1500, 5000]))
+        dlens = rng.integers(0, dmax + 1, dn)
+        dreads = []
+        for n in dlens:
+            kind = rng.random()
+            if kind < 0.6:                                      # levels with noise
+                lv = np.repeat(rng.normal(500, 80, n // 3 + 1), rng.integers(1, 20, n // 3 + 1))[:n]
+                x = lv + rng.normal(0, float(rng.choice([0, 2, 8, 30])), lv.size)
+            elif kind < 0.8:                                    # anything an int16 holds
+                x = rng.integers(-32768, 32768, n).astype(np.float64)
+            else:                                               # flat, or two values
+                x = np.where(rng.random(n) < float(rng.choice([0.0, 0.5])), 32767.0, float(rng.integers(-32768, 32767)))
+            dreads.append(np.clip(np.rint(x), -32768, 32767).astype(np.int16))
+        dlens = np.array([x.size for x in dreads])
+        ws = int(rng.integers(1, 65))
+        dpar = [detect_ref.PRESETS["dna"], detect_ref.PRESETS["rna"],
+                (ws, int(rng.integers(ws, 65)), float(rng.choice([0.0, 1.4, 2.5, 20.0])), float(rng.choice([0.0, 4.0, 9.0])),
+                 float(rng.choice([0.0, 0.2, 1.0, 5.0])))][int(rng.integers(3))]
+        dstride = int(max(dlens.max(), 1)) + int(rng.integers(0, 9))     # any stride: rows need not be 16-byte aligned
+        dbuf = np.full((dn, dstride), -7, dtype=np.int16)
+        for r, x in enumerate(dreads):
+            dbuf[r, :x.size] = x
+        goff, grec = api.detect_events_batch(dbuf, dlens.astype(np.int32), api.det_params(
+            w_short=dpar[0], w_long=dpar[1], th_short=dpar[2], th_long=dpar[3], peak_height=dpar[4]))
+        woff, wrec = detect_ref.detect(dreads, dpar)
+        if not np.array_equal(goff, woff) or grec.tobytes() != wrec.tobytes():
+            bad += 1
+            print("DETECT mismatch round %d: %d reads, max length %d, stride %d, params %s" % (rounds, dn, dmax, dstride, dpar))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
