@@ -833,6 +833,60 @@ int sk_detect_events_i16(const int16_t *sig, int64_t stride, const int32_t *len,
 int sk_detect_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                              const sk_det_params *p, int64_t *d_off /* [nreads + 1] */, sk_det_event *d_rec, int64_t cap);
 
+/* ---- signal HMM: Viterbi per read ---------------------------------------- */
+/* Every sample of a read assigned to one of up to SK_HMM_STATES named stretches (for a direct-RNA read: open pore,
+ * leader, adapter, poly(A), transcript body) by the best path through a small hidden Markov model.  The definition is
+ * the project's own ("Signal HMM"; tests/hmm_ref.py states it in numpy); the reference has no such step.
+ * Everything is float64 add, subtract, multiply and the comparison `>`, one correctly rounded operation each (no
+ * multiply-add, no log, no exp: the logarithms are taken when the model is built, on the host).
+ *
+ * Model (S = nstates, 1 <= S <= 6; rows and columns at and above S are ignored):
+ *     linit[j], ltrans[i][j]   finite or -inf; at least one linit[j] finite
+ *     c[j][m], mu[j][m], h[j][m], m = 0, 1: the two emission components of state j -- c finite or -inf (at least one
+ *                              finite per state), mu finite, h finite and >= 0.  A Gaussian (weight, mean, sigma):
+ *                              c = log(weight) - log(sigma * sqrt(2 pi)), h = 1 / (2 sigma^2); a flat component over
+ *                              `range`: c = log(weight / range), h = 0; an absent component: c = -inf.
+ * Samples: x_t = (double)raw_t, or with a calibration x_t = ((double)raw_t + offset_r) * unit_r -- the {offset, unit}
+ * pair of read r as sk_pa_calib makes it and sk_pull_text_dev takes it, and no rounding to decimals.  limit > 0: only
+ * the first min(len, limit) samples of a read are used (n below); never more than 0x7fffff00 of them.
+ * Emission, with max(a, b) = (b > a ? b : a) throughout:
+ *     a_m  = c[j][m] - ((x - mu[j][m]) * (x - mu[j][m])) * h[j][m]
+ *     e_j(x) = max(a_0, a_1)
+ * Recurrence:
+ *     v_j(0) = linit[j] + e_j(x_0)
+ *     v_j(t) = b_j + e_j(x_t),   b_j = max over i = 0 .. S-1, in rising i, of v_i(t-1) + ltrans[i][j]
+ * -- a later i replaces an earlier one only when it is strictly greater: the lowest i wins ties, also ties at -inf.
+ * No +inf can arise from valid input, so no NaN can (given |x - mu| < 2^511: the square stays finite).
+ * Path summary instead of a back-trace: state j carries enter_j[0..6), enter_j[k] = the first sample at which the best
+ * path into j was in state k, or -1.  t = 0: enter_j[j] = 0, the rest -1.  t >= 1: enter_j = the tuple of the winning
+ * predecessor at t - 1, then enter_j[j] = t if it is still -1.
+ * Result: f = the lowest j with the largest v_j(n - 1); score = v_f(n - 1), final_state = f, n_used = n,
+ * enter = enter_f (-1 for k >= S).  n = 0: score 0.0, final_state -1, every enter -1. */
+#define SK_HMM_STATES 6
+typedef struct sk_hmm_model {       /* 632 bytes */
+    int32_t nstates, reserved;
+    double  linit[SK_HMM_STATES];
+    double  ltrans[SK_HMM_STATES][SK_HMM_STATES];   /* [from][to] */
+    double  c[SK_HMM_STATES][2], mu[SK_HMM_STATES][2], h[SK_HMM_STATES][2];
+} sk_hmm_model;
+typedef struct sk_hmm_rec {         /* 40 bytes */
+    double  score;
+    int32_t final_state, n_used;
+    int32_t enter[SK_HMM_STATES];
+} sk_hmm_rec;
+/* Rows of `stride` int16 samples, len[r] in [0, stride]; cal2: NULL, or nreads {offset, unit} pairs; rec: nreads
+ * records.  A model outside the rules above, NULL model / rec, limit < 0: SK_ERR_INVALID -- the arguments are checked
+ * before the device is looked at. */
+int sk_hmm_viterbi_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,
+                       const sk_hmm_model *model, int32_t limit, sk_hmm_rec *rec);
+/* device-resident form: every pointer is a device pointer but `model` (host); d_len[r] is clamped into [0, stride];
+ * nothing is synchronised. */
+int sk_hmm_viterbi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
+                           const sk_hmm_model *model, int32_t limit, sk_hmm_rec *d_rec);
+/* ragged float64 values (pA, as a SquigglePull TSV holds them): read r = values[off[r] .. off[r+1]), x_t = the value. */
+int sk_hmm_viterbi_f64_len(const double *values, const int64_t *off, int32_t nreads, const sk_hmm_model *model,
+                           int32_t limit, sk_hmm_rec *rec);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,54 @@ class DetEvent(C.Structure):
 
 DET_EVENT_DTYPE = np.dtype([("start", "<i4"), ("length", "<i4"), ("sum", "<i8"), ("sumsq", "<i8")])
 
+
+SK_HMM_STATES = 6
+
+
+class HmmModel(C.Structure):
+    """sk_hmm_model: a signal HMM of up to six states with two emission components each, as plain doubles (the header's
+    "signal HMM" section states the definition; api.hmm_model builds one from probabilities)."""
+    _fields_ = [("nstates", C.c_int32), ("reserved", C.c_int32), ("linit", C.c_double * SK_HMM_STATES),
+                ("ltrans", (C.c_double * SK_HMM_STATES) * SK_HMM_STATES), ("c", (C.c_double * 2) * SK_HMM_STATES),
+                ("mu", (C.c_double * 2) * SK_HMM_STATES), ("h", (C.c_double * 2) * SK_HMM_STATES)]
+
+    @classmethod
+    def from_arrays(cls, nstates, linit, ltrans, c, mu, h):
+        """The model of the given numbers, unchecked (the library checks): linit [S], ltrans [S, S], c / mu / h [S, 2] for
+        S = len(linit); nstates may differ from S only to build a model the library must refuse."""
+        m = cls()
+        m.nstates = int(nstates)
+        linit, ltrans = np.asarray(linit, dtype=np.float64), np.asarray(ltrans, dtype=np.float64)
+        S = linit.size
+        if S > SK_HMM_STATES or ltrans.shape != (S, S):
+            raise ValueError("need linit [S] and ltrans [S, S] with S <= %d" % SK_HMM_STATES)
+        m.linit[:] = [float("-inf")] * SK_HMM_STATES
+        for i in range(SK_HMM_STATES):
+            m.ltrans[i][:] = [float("-inf")] * SK_HMM_STATES
+            m.c[i][:] = [float("-inf")] * 2
+        for name, a in (("c", c), ("mu", mu), ("h", h)):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != (S, 2):
+                raise ValueError("%s must be [S, 2]" % name)
+            for j in range(S):
+                getattr(m, name)[j][:] = [float(a[j, 0]), float(a[j, 1])]
+        for i in range(S):
+            m.linit[i] = float(linit[i])
+            for j in range(S):
+                m.ltrans[i][j] = float(ltrans[i, j])
+        return m
+
+    def arrays(self):
+        """{"nstates", "linit" [6], "ltrans" [6, 6], "c" / "mu" / "h" [6, 2]} as numpy arrays"""
+        return {"nstates": int(self.nstates), "linit": np.array(self.linit[:], dtype=np.float64),
+                "ltrans": np.array([row[:] for row in self.ltrans], dtype=np.float64),
+                "c": np.array([row[:] for row in self.c], dtype=np.float64),
+                "mu": np.array([row[:] for row in self.mu], dtype=np.float64),
+                "h": np.array([row[:] for row in self.h], dtype=np.float64)}
+
+
+HMM_DTYPE = np.dtype([("score", "<f8"), ("final_state", "<i4"), ("n_used", "<i4"), ("enter", "<i4", (SK_HMM_STATES,))])
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -318,6 +366,12 @@ ABI = {
     "sk_detect_events_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(DetParams), _vp, _vp, C.c_int64]),
     # ... its device-resident form (all pointers device but params; the check against cap happens on the device)
     "sk_detect_events_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.POINTER(DetParams), _vp, _vp, C.c_int64]),
+    # signal HMM ("signal HMM" in include/squigglekit_hip.h; tests/hmm_ref.py states it in numpy): sig, stride, len, nreads,
+    # cal2 or NULL, model, limit, rec -- the device-resident form takes the same list
+    "sk_hmm_viterbi_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp]),
+    "sk_hmm_viterbi_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp]),
+    # ... ragged float64 values: values, off, nreads, model, limit, rec
+    "sk_hmm_viterbi_f64_len": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(HmmModel), C.c_int32, _vp]),
 }
 
 

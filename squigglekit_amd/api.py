@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HmmModel, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -1571,3 +1571,173 @@ def event_stdv(rec):
     n = rec["length"].astype(np.int64)
     var = np.maximum(n * rec["sumsq"] - rec["sum"] * rec["sum"], 0)
     return np.sqrt(var.astype(np.float64)) / n.astype(np.float64)
+
+
+# ----------------------------------------------------------------------------
+# signal HMM: every sample of a read assigned to a named stretch by the best path through a small model (the
+# definition: "signal HMM" in include/squigglekit_hip.h and DESIGN.md 4.12)
+# ----------------------------------------------------------------------------
+def _log0(p):
+    """log(p), -inf for p == 0"""
+    p = float(p)
+    if not p >= 0.0:
+        raise ValueError("a probability or weight must be >= 0, got %r" % p)
+    return float(np.log(p)) if p > 0.0 else float("-inf")
+
+
+def hmm_model(init, trans, emissions):
+    """The sk_hmm_model of probabilities: init [S], trans [S][S] (from, to) -- a zero becomes -inf -- and per state one
+    or two emission components, each (weight, mean, sigma) for a Gaussian, c = log(weight) - log(sigma * sqrt(2 pi)),
+    h = 1 / (2 sigma^2), or (weight, None, range) for a flat one, c = log(weight / range), h = 0.  An absent second
+    component has c = -inf.  Nothing is normalised: the numbers are used as given."""
+    S = len(init)
+    if not 1 <= S <= _lib.SK_HMM_STATES or len(trans) != S or any(len(row) != S for row in trans) or len(emissions) != S:
+        raise ValueError("need 1 <= S <= %d states, trans [S][S] and S emission lists" % _lib.SK_HMM_STATES)
+    c = np.full((S, 2), -np.inf)
+    mu = np.zeros((S, 2))
+    h = np.zeros((S, 2))
+    for j, comps in enumerate(emissions):
+        if not 1 <= len(comps) <= 2:
+            raise ValueError("state %d: one or two emission components" % j)
+        for q, (weight, mean, width) in enumerate(comps):
+            width = float(width)
+            if not (width > 0.0 and np.isfinite(width)):
+                raise ValueError("state %d: sigma / range must be positive and finite" % j)
+            if mean is None:
+                c[j, q] = _log0(float(weight) / width)
+            else:
+                c[j, q] = _log0(weight) - float(np.log(width * np.sqrt(2.0 * np.pi)))
+                mu[j, q] = float(mean)
+                h[j, q] = 1.0 / (2.0 * width * width)
+    return HmmModel.from_arrays(S, [_log0(p) for p in init], [[_log0(p) for p in row] for row in trans], c, mu, h)
+
+
+def _hmm_cal(cal2, R):
+    if cal2 is None:
+        return None
+    cal2 = np.ascontiguousarray(cal2, dtype=np.float64)
+    if cal2.shape != (R, 2):
+        raise ValueError("cal2 must hold one (offset, unit) pair per read")
+    return cal2
+
+
+def hmm_viterbi_batch(sig, lens, model, cal2=None, limit=0):
+    """The Viterbi record (HMM_DTYPE: score, final_state, n_used, enter[6]) of every row of an int16 [R, stride] batch of
+    raw samples.  cal2 [R, 2] = (offset, unit) per read: the model sees (raw + offset) * unit, i.e. pA with unit =
+    range / digitisation; None: it sees the raw values.  limit > 0: only the first min(len, limit) samples of a read.
+    Single device (the calling thread's)."""
+    L = _lib.ensure_init()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    if sig.ndim != 2:
+        raise ValueError("sig must be [reads, samples]")
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    if lens.shape != (R,):
+        raise ValueError("lens must hold one length per row")
+    cal2 = _hmm_cal(cal2, R)
+    rec = np.zeros(R, dtype=HMM_DTYPE)
+    if R == 0 or stride == 0:                            # no samples at all: the record of an empty read
+        rec["final_state"], rec["enter"] = -1, -1
+        return rec
+    check(L.sk_hmm_viterbi_i16(ptr(sig), stride, ptr(lens), R, None if cal2 is None else ptr(cal2), C.byref(model), int(limit),
+                               ptr(rec)))
+    return rec
+
+
+def hmm_viterbi_ragged_f64(values, off, model, limit=0):
+    """hmm_viterbi_batch for ragged float64 reads (pA values as a SquigglePull TSV holds them): read r is
+    values[off[r]:off[r + 1]] and the model sees the values as they are."""
+    L = _lib.ensure_init()
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = off.size - 1
+    rec = np.zeros(max(R, 0), dtype=HMM_DTYPE)
+    if values.size == 0:
+        values = np.zeros(1)
+    check(L.sk_hmm_viterbi_f64_len(ptr(values), ptr(off), R, C.byref(model), int(limit), ptr(rec)))
+    return rec
+
+
+def hmm_viterbi(reads, model, limit=0):
+    """The records of a list of reads of any lengths: integer-valued reads go through the int16 feed, the rest through the
+    float64 one (the same records either way); input order is kept."""
+    rec = np.zeros(len(reads), dtype=HMM_DTYPE)
+    ints, arrs, flts = _split_int16(reads)
+    if ints:
+        rec[ints] = hmm_viterbi_batch(*pack_i16([np.asarray(a).reshape(-1) for a in arrs]), model, None, limit)
+    if flts:
+        rec[flts] = hmm_viterbi_ragged_f64(*pack_f64([reads[i] for i in flts]), model, limit)
+    return rec
+
+
+# the poly(A) layer: a left-to-right model of a direct-RNA read
+POLYA_STATES = ("START", "LEADER", "ADAPTER", "POLYA", "CLIFF", "TRANSCRIPT")
+START, LEADER, ADAPTER, POLYA, CLIFF, TRANSCRIPT = range(6)
+# Per preset: the emission components of the six states, (weight, mean, sigma) or (weight, None, range).
+#   synth_raw  raw units, what synth.drna_reads plants: adapter N(430, 25), poly(A) N(560, 8), a body of event levels
+#              N(530, 80) with plateaus near 535; the flat components take the spikes and the excursions it adds.
+#   rna_pa     pA.  These numbers are this project's own choice, read off published direct-RNA (SQK-RNA002) traces -- open
+#              pore well above 150 pA, leader near 105 pA, adapter near 80 pA, a tight poly(A) plateau near 108 pA, a
+#              body spread around 95 pA -- and not fitted to data: treat them as a starting point and check them against
+#              the reads at hand.
+POLYA_PRESETS = {
+    "synth_raw": {
+        "emissions": [[(1.0, 900.0, 120.0)],
+                      [(1.0, 500.0, 150.0)],
+                      [(0.98, 430.0, 25.0), (0.02, None, 2400.0)],
+                      [(0.98, 560.0, 8.0), (0.02, None, 2400.0)],
+                      [(1.0, 480.0, 40.0)],
+                      [(0.3, 535.0, 15.0), (0.7, 530.0, 90.0)]],
+        "stay": (0.9, 0.9, 0.9995, 0.999, 0.3, 1.0), "cliff": 0.0001},
+    "rna_pa": {
+        "emissions": [[(1.0, 220.0, 40.0)],
+                      [(1.0, 105.0, 12.0)],
+                      [(0.98, 80.0, 6.0), (0.02, None, 300.0)],
+                      [(0.98, 108.0, 2.5), (0.02, None, 300.0)],
+                      [(1.0, 85.0, 8.0)],
+                      [(0.4, 100.0, 8.0), (0.6, 95.0, 18.0)]],
+        "stay": (0.9, 0.99, 0.9995, 0.999, 0.3, 1.0), "cliff": 0.0001},
+}
+
+
+def polya_model(preset="rna_pa"):
+    """The six-state model START, LEADER, ADAPTER, POLYA, CLIFF, TRANSCRIPT of a direct-RNA read.  Transitions: S -> S, L;
+    L -> L, A; A -> A, P; P -> P, C, T; C -> C, P; T -> T; every other one is impossible, and a read starts in START or
+    LEADER.  POLYA is one tight Gaussian plus a flat component, TRANSCRIPT a mixture of two Gaussians.  Presets:
+    "rna_pa" (pA; the values are this project's own choice, see POLYA_PRESETS) and "synth_raw" (raw units, matching
+    synth.drna_reads)."""
+    if preset not in POLYA_PRESETS:
+        raise ValueError("preset %r: need one of %s" % (preset, sorted(POLYA_PRESETS)))
+    p = POLYA_PRESETS[preset]
+    stay, cliff = p["stay"], p["cliff"]
+    T = [[0.0] * 6 for _ in range(6)]
+    T[START][START], T[START][LEADER] = stay[START], 1.0 - stay[START]
+    T[LEADER][LEADER], T[LEADER][ADAPTER] = stay[LEADER], 1.0 - stay[LEADER]
+    T[ADAPTER][ADAPTER], T[ADAPTER][POLYA] = stay[ADAPTER], 1.0 - stay[ADAPTER]
+    T[POLYA][POLYA], T[POLYA][CLIFF], T[POLYA][TRANSCRIPT] = stay[POLYA], cliff, 1.0 - stay[POLYA] - cliff
+    T[CLIFF][CLIFF], T[CLIFF][POLYA] = stay[CLIFF], 1.0 - stay[CLIFF]
+    T[TRANSCRIPT][TRANSCRIPT] = 1.0
+    return hmm_model([0.5, 0.5, 0.0, 0.0, 0.0, 0.0], T, p["emissions"])
+
+
+POLYA_DTYPE = np.dtype([("adapter_start", "<i4"), ("adapter_end", "<i4"), ("polya_start", "<i4"), ("polya_end", "<i4"),
+                        ("polya_samples", "<i4"), ("found", "?")])
+
+
+def polya_segments(records):
+    """Where the adapter and the poly(A) tail lie, from the records of a polya_model (POLYA_DTYPE per read): adapter =
+    [adapter_start, adapter_end], poly(A) = [polya_start, polya_end] in samples, both ends included: adapter_start =
+    enter[ADAPTER], adapter_end = enter[POLYA] - 1, polya_start = enter[POLYA], polya_end = enter[TRANSCRIPT] - 1,
+    polya_samples = polya_end - polya_start + 1 (cliffs inside the tail count).  found: the best path ends in TRANSCRIPT
+    and went through POLYA; every coordinate of a read that is not found is -1 and polya_samples 0."""
+    records = np.asarray(records)
+    en = records["enter"].reshape(-1, 6)
+    out = np.zeros(en.shape[0], dtype=POLYA_DTYPE)
+    found = (records["final_state"].reshape(-1) == TRANSCRIPT) & (en[:, POLYA] >= 0) & (en[:, TRANSCRIPT] >= 0)
+    out["found"] = found
+    out["adapter_start"] = np.where(found, en[:, ADAPTER], -1)
+    out["adapter_end"] = np.where(found, en[:, POLYA] - 1, -1)
+    out["polya_start"] = np.where(found, en[:, POLYA], -1)
+    out["polya_end"] = np.where(found, en[:, TRANSCRIPT] - 1, -1)
+    out["polya_samples"] = np.where(found, en[:, TRANSCRIPT] - en[:, POLYA], 0)
+    return out

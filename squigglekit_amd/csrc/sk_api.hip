@@ -2567,3 +2567,78 @@ int sk_detect_events_i16(const int16_t *sig, int64_t stride, const int32_t *len,
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ signal HMM (sk_hmm.hip)
+// The definition: include/squigglekit_hip.h, "signal HMM".  One kernel per sub-batch; the records of the whole call come
+// back in one copy.
+namespace {
+
+int check_hmm(const sk_hmm_model *model, int32_t limit, int32_t nreads, const sk_hmm_rec *rec)
+{
+    if (const char *what = sk_hmm_model_error(model)) return sk_fail(SK_ERR_INVALID, "sk_hmm_model: %s", what);
+    if (limit < 0) return sk_fail(SK_ERR_INVALID, "limit < 0");
+    if (nreads && !rec) return sk_fail(SK_ERR_INVALID, "NULL rec");
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_hmm_viterbi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
+                           const sk_hmm_model *model, int32_t limit, sk_hmm_rec *d_rec)
+{
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (rc) return rc;
+    if ((rc = check_hmm(model, limit, nreads, d_rec))) return rc;
+    SK_ENTER(c);
+    return sk_launch_hmm_i16(c, d_sig, stride, d_len, nreads, d_cal2, model, limit, d_rec);
+}
+
+int sk_hmm_viterbi_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,
+                       const sk_hmm_model *model, int32_t limit, sk_hmm_rec *rec)
+{
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_hmm(model, limit, nreads, rec))) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) return SK_OK;
+    const size_t rec_bytes = (size_t)nreads * sizeof(sk_hmm_rec);                     // (40 bytes each: the pairs stay 8-byte aligned)
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->hmm, rec_bytes + (size_t)nreads * 2 * sizeof(double)))) return rc;
+    sk_hmm_rec *d_rec = (sk_hmm_rec *)c->hmm.p;
+    double *d_cal = cal2 ? (double *)((char *)c->hmm.p + rec_bytes) : nullptr;
+    if (d_cal) SK_HIP(hipMemcpyAsync(d_cal, cal2, (size_t)nreads * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    rc = ingest_rows(c, sub_batches(nreads, stride), (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return sk_launch_hmm_i16(c, d_sig, stride, d_len, nr, d_cal ? d_cal + 2 * (size_t)r0 : nullptr, model,
+                                                  limit, d_rec + r0);
+                     });
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_hmm_viterbi_f64_len(const double *values, const int64_t *off, int32_t nreads, const sk_hmm_model *model,
+                           int32_t limit, sk_hmm_rec *rec)
+{
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_hmm(model, limit, nreads, rec);
+    if (rc) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) return SK_OK;
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, values, off, nreads, &total, &maxlen))) return rc;  // (checks values / off and the lengths)
+    const size_t rec_bytes = (size_t)nreads * sizeof(sk_hmm_rec);
+    if ((rc = sk_reserve(c, &c->hmm, rec_bytes))) return rc;
+    sk_hmm_rec *d_rec = (sk_hmm_rec *)c->hmm.p;
+    if ((rc = sk_launch_hmm_f64(c, (const double *)c->sig.p, (const int64_t *)c->off.p, nreads, model, limit, d_rec))) return rc;
+    SK_HIP(hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+} // extern "C"

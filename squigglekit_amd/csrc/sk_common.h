@@ -105,6 +105,7 @@ struct sk_ctx {
     sk_buf seglevwork;    // segment levels: [0] = items, [4 ..] = the (read, slot) work list, then the long items' scratch rows
     sk_buf detect;    // event detection: the mark words [nreads][ceil(stride / 64)], then the scan's block sums (sk_detect.hip)
     sk_buf detectout; // event detection: off [nreads + 1], then the sk_det_event records of the host entry point
+    sk_buf hmm;       // signal HMM: the sk_hmm_rec records of the host entry points, then their {offset, unit} pairs (sk_hmm.hip)
     std::vector<double> panel_host;           // laid-out motifs as uploaded (kept alive for the async H2D)
     std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
     std::vector<sk_panel_group> panel_groups;
@@ -442,6 +443,23 @@ int sk_launch_detect_mark(sk_ctx *c, const int16_t *d_sig, int64_t stride, const
 int sk_launch_detect_scan(sk_ctx *c, int32_t nreads, int64_t *d_bsum, int64_t *d_off);
 int sk_launch_detect_fill(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
                           const sk_det_params *p, const void *d_words, const int64_t *d_off, sk_det_event *d_rec, int64_t cap);
+
+// ---- signal HMM (sk_hmm.hip) ----
+// the pA value of a raw sample under a read's {offset, unit} pair (sk_pa_calib): one add, one multiply -- what
+// SquigglePull's text rounds to two decimals and what the HMM's emissions take unrounded
+__host__ __device__ static inline double sk_raw_to_pa(double raw, double offset, double unit)
+{
+    const double x = raw + offset;
+    return x * unit;
+}
+// nullptr when the model keeps the rules of the header's "signal HMM" section, else what it breaks
+const char *sk_hmm_model_error(const sk_hmm_model *m);
+// Viterbi records of nreads reads -> d_rec[0 .. nreads): int16 rows (d_cal: {offset, unit} per read, or nullptr), or
+// ragged float64 values (read r = d_values[d_off[r] .. d_off[r + 1])).  limit > 0: the first min(len, limit) samples.
+int sk_launch_hmm_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                      const double *d_cal, const sk_hmm_model *m, int32_t limit, sk_hmm_rec *d_rec);
+int sk_launch_hmm_f64(sk_ctx *c, const double *d_values, const int64_t *d_off, int32_t nreads, const sk_hmm_model *m,
+                      int32_t limit, sk_hmm_rec *d_rec);
 
 // ---- SquigglePull text (sk_pull.hip) ----
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries

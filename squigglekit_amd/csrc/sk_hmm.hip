@@ -1,0 +1,346 @@
+// sk_hmm.hip -- signal HMM: the best path of every read through a model of up to six states, for gfx950.
+//
+// The definition is the project's own (include/squigglekit_hip.h, "signal HMM"; tests/hmm_ref.py restates
+// it in numpy).  Per read x[0..n) and per state j:
+//     e_j(x)  = max_m ( c[j][m] - ((x - mu[j][m]) * (x - mu[j][m])) * h[j][m] )          m = 0, 1
+//     v_j(0)  = linit[j] + e_j(x_0)
+//     v_j(t)  = max_i ( v_i(t-1) + ltrans[i][j] ) + e_j(x_t)                             the lowest i wins ties
+// with max(a, b) = (b > a ? b : a), one correctly rounded float64 operation at a time (the file is compiled with
+// -ffp-contract=off like the rest) and no log / exp.  Instead of a back-trace every state carries enter[0..6): the first
+// sample at which its best path was in state k (-1: never) -- the winning predecessor's tuple is copied forward, as the
+// DTW kernels carry their start column.
+//
+// k_hmm_viterbi<FEED>   one lane per read, 64 reads per wavefront (one wavefront per workgroup), k_detect_mark's mapping.
+//     The wavefront loads a tile of its 64 rows into LDS and every lane then walks its own row:
+//       int16 rows     tile of 128 samples, 16-byte loads (16 lanes per row; rows that are not 16-byte aligned take 2-byte
+//                      loads), pitch 65 dwords: the 2-byte reads of the lanes -- all at the same position of their own
+//                      rows -- fall into distinct banks;
+//       float64 ragged tile of 32 values, 8-byte loads (32 lanes per row: a ragged row is 8-byte aligned and no more),
+//                      pitch 66 dwords: the 8-byte reads of 32 lanes fall into distinct bank pairs.
+//     The six scores and the six tuples of six sample indices stay in registers: every loop over states is unrolled, the
+//     winning predecessor is chosen by compare-and-select.  The model is a kernel argument, so its constants are wave
+//     uniform and the compiler holds them in scalar registers.  A wavefront has 102 of them and the model alone is 78
+//     doubles, so 245 scalar values are spilled: parked in lanes of vector registers (v_writelane once, v_readlane at
+//     each use inside the sample loop; no scratch, no memory access -- profiles/hmm_kernel_resources.txt).  That costs
+//     vector ALU issue slots in a loop bound by them and is not removed yet.  A transition or a second
+//     component of -inf is skipped by a scalar branch on a bit mask made on the host -- exact: such a candidate is -inf and
+//     never strictly greater than the one in hand (predecessor 0 and component 0 are always taken, so ties at -inf
+//     resolve as the definition says).  States at and above S are skipped the same way.  The sample index is the same
+//     for all lanes, so t == 0 is a scalar branch too.  A lane whose read has ended idles; the wavefront leaves after
+//     the tile that ends its longest read.  Global traffic: the samples once, 40 bytes per read out.
+//
+// The work per sample is about S^2 compare-and-selects of a tuple: the kernel is bound by vector ALU issue, not by
+// memory, which is why one tile (no ring) and two barriers per tile are enough.  A call of a few hundred reads fills a
+// few of the 1 024 SIMDs only: the lane-per-read mapping is for batches.
+#include "sk_common.h"
+
+namespace {
+
+constexpr int HS = SK_HMM_STATES;
+
+template <int FEED> struct hmm_feed;
+template <> struct hmm_feed<SK_FEED_I16> {
+    typedef int16_t T;
+    static constexpr int TILE = 128;              // samples per row and load round
+    static constexpr int PITCH = TILE / 2 + 1;    // dwords per row in LDS (odd: lane l at position j -> bank (l + j / 2) mod 32)
+};
+template <> struct hmm_feed<SK_FEED_F64_NORM> {
+    typedef double T;
+    static constexpr int TILE = 32;
+    static constexpr int PITCH = TILE * 2 + 2;    // lane l at position j -> dwords 66 l + 2 j, + 1: bank pair 2 (l + j) mod 64
+};
+
+// the model as the kernel takes it: flat arrays, and which transitions / second components are not -inf
+struct hmm_kmodel {
+    double   linit[HS];
+    double   ltrans[HS * HS];     // [from * 6 + to]
+    double   c[HS * 2], mu[HS * 2], h[HS * 2];
+    uint64_t tmask;               // bit from * 6 + to: ltrans is not -inf
+    uint32_t cmask;               // bit j: component 1 of state j is not -inf
+    int32_t  S;
+};
+
+struct hmm_kargs {
+    const void    *sig;           // int16 rows of `stride`, or float64 values
+    int64_t        stride;
+    const int32_t *len;           // int16 rows
+    const int64_t *off;           // float64 values: read r = sig[off[r] .. off[r + 1])
+    const double  *cal;           // {offset, unit} per read, or nullptr
+    int32_t        nreads;
+    int32_t        limit;
+    int32_t        vec;           // int16 rows are 16-byte aligned (base and stride)
+    sk_hmm_rec    *rec;
+    hmm_kmodel     m;
+};
+
+template <int FEED>
+__device__ __forceinline__ int32_t hmm_len(const hmm_kargs &a, int64_t r)
+{
+    if (r >= a.nreads) return 0;
+    int64_t n;
+    if (FEED == SK_FEED_I16) {
+        n = a.len[r];
+        if (n > a.stride) n = a.stride;
+    } else {
+        n = a.off[r + 1] - a.off[r];
+    }
+    if (n > 0x7fffff00) n = 0x7fffff00;                         // either feed: nmax + TILE - 1 stays inside int32
+    if (n < 0) n = 0;
+    if (a.limit > 0 && n > a.limit) n = a.limit;
+    return (int32_t)n;
+}
+
+// tile k of the wavefront's 64 rows -> LDS; row `row` holds its samples [k * TILE, min((k + 1) * TILE, nrow[row]))
+template <int FEED>
+__device__ __forceinline__ void hmm_load_tile(const hmm_kargs &a, uint32_t *tile, const int32_t *nrow, int64_t r0, int k, int lane)
+{
+    constexpr int TILE = hmm_feed<FEED>::TILE, PITCH = hmm_feed<FEED>::PITCH;
+    if (FEED == SK_FEED_I16) {
+        const int16_t *sig = (const int16_t *)a.sig;
+        if (a.vec) {
+#pragma unroll 4
+            for (int it = 0; it < 16; it++) {
+                const int row = it * 4 + (lane >> 4);
+                const int32_t pos = k * TILE + (lane & 15) * 8;
+                if (pos < nrow[row]) {                          // (a row of the batch: nrow is 0 past nreads)
+                    const uint4 v = *(const uint4 *)(sig + (r0 + row) * a.stride + pos);
+                    uint32_t *dst = tile + row * PITCH + ((lane & 15) * 4);
+                    dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+                }
+            }
+        } else {
+            // Knowingly slow: 2-byte loads, 128 bytes per load instruction, one row after the other.  Taken only when the
+            // base or the stride breaks the 16-byte alignment; the loop over samples, not this one, bounds the kernel.
+            int16_t *t16 = (int16_t *)tile;
+            for (int row = 0; row < 64; row++) {
+                const int32_t nr = nrow[row];
+                for (int cc = lane; cc < TILE; cc += 64) {
+                    const int32_t pos = k * TILE + cc;
+                    if (pos < nr) t16[row * (2 * PITCH) + cc] = sig[(r0 + row) * a.stride + pos];
+                }
+            }
+        }
+    } else {
+        const double *sig = (const double *)a.sig;
+#pragma unroll 4
+        for (int it = 0; it < 32; it++) {
+            const int row = it * 2 + (lane >> 5);
+            const int32_t pos = k * TILE + (lane & 31);
+            if (pos < nrow[row]) {
+                const double v = sig[a.off[r0 + row] + pos];
+                *(double *)(tile + row * PITCH + (lane & 31) * 2) = v;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ double hmm_emit(const hmm_kmodel &m, int j, double x)
+{
+    const double d0 = x - m.mu[2 * j];
+    double e = m.c[2 * j] - (d0 * d0) * m.h[2 * j];
+    if ((m.cmask >> j) & 1u) {
+        const double d1 = x - m.mu[2 * j + 1];
+        const double e1 = m.c[2 * j + 1] - (d1 * d1) * m.h[2 * j + 1];
+        if (e1 > e) e = e1;
+    }
+    return e;
+}
+
+template <int FEED>
+__global__ __launch_bounds__(64)
+void k_hmm_viterbi(const hmm_kargs a)
+{
+    typedef typename hmm_feed<FEED>::T T;
+    constexpr int TILE = hmm_feed<FEED>::TILE, PITCH = hmm_feed<FEED>::PITCH;
+    __shared__ __attribute__((aligned(16))) uint32_t tile[64 * PITCH];
+    __shared__ int32_t nrow[64];
+    const int lane = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * 64;
+    const int64_t r = r0 + lane;
+    const int32_t n = hmm_len<FEED>(a, r);
+    nrow[lane] = n;
+    int32_t nmax = n;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const int32_t q = __shfl_xor(nmax, o); nmax = q > nmax ? q : nmax; }
+    __syncthreads();
+
+    const int S = a.m.S;
+    const double ninf = -__builtin_inf();
+    double ofs = 0.0, unit = 1.0;                               // (x + 0.0) * 1.0 == x for every int16 x
+    if (FEED == SK_FEED_I16 && a.cal && r < a.nreads) { ofs = a.cal[2 * r]; unit = a.cal[2 * r + 1]; }
+
+    double v[HS];
+    int32_t E[HS][HS];
+#pragma unroll
+    for (int j = 0; j < HS; j++) {
+        v[j] = ninf;
+#pragma unroll
+        for (int q = 0; q < HS; q++) E[j][q] = -1;
+    }
+
+    const T *xrow = (const T *)tile + (size_t)lane * (PITCH * 4 / sizeof(T));
+    const int ntiles = (nmax + TILE - 1) / TILE;
+    for (int k = 0; k < ntiles; k++) {
+        hmm_load_tile<FEED>(a, tile, nrow, r0, k, lane);
+        __syncthreads();
+        const int32_t t0 = k * TILE;
+        const int32_t tend = nmax - t0 < TILE ? nmax - t0 : TILE;   // wave uniform
+        for (int jj = 0; jj < tend; jj++) {
+            const int32_t t = t0 + jj;                          // wave uniform
+            if (t < n) {
+                double x = (double)xrow[jj];
+                if (FEED == SK_FEED_I16) x = sk_raw_to_pa(x, ofs, unit);
+                if (t == 0) {
+#pragma unroll
+                    for (int j = 0; j < HS; j++)
+                        if (j < S) { v[j] = a.m.linit[j] + hmm_emit(a.m, j, x); E[j][j] = 0; }
+                } else {
+                    double nv[HS];
+                    int32_t NE[HS][HS];
+#pragma unroll
+                    for (int j = 0; j < HS; j++) {
+                        nv[j] = ninf;
+#pragma unroll
+                        for (int q = 0; q < HS; q++) NE[j][q] = -1;
+                        if (j < S) {
+                            double b = v[0] + a.m.ltrans[j];    // predecessor 0: always taken
+#pragma unroll
+                            for (int q = 0; q < HS; q++) NE[j][q] = E[0][q];
+#pragma unroll
+                            for (int i = 1; i < HS; i++)
+                                if (i < S && ((a.m.tmask >> (i * HS + j)) & 1ull)) {
+                                    const double cand = v[i] + a.m.ltrans[i * HS + j];
+                                    const bool w = cand > b;
+                                    b = w ? cand : b;
+#pragma unroll
+                                    for (int q = 0; q < HS; q++) NE[j][q] = w ? E[i][q] : NE[j][q];
+                                }
+                            NE[j][j] = NE[j][j] < 0 ? t : NE[j][j];
+                            nv[j] = b + hmm_emit(a.m, j, x);
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < HS; j++) {
+                        v[j] = nv[j];
+#pragma unroll
+                        for (int q = 0; q < HS; q++) E[j][q] = NE[j][q];
+                    }
+                }
+            }
+        }
+        __syncthreads();                                        // the tile is read before the next one lands
+    }
+
+    if (r >= a.nreads) return;
+    sk_hmm_rec out;
+    if (n == 0) {
+        out.score = 0.0; out.final_state = -1; out.n_used = 0;
+#pragma unroll
+        for (int q = 0; q < HS; q++) out.enter[q] = -1;
+    } else {
+        double best = v[0];
+        int32_t f = 0;
+        int32_t en[HS];
+#pragma unroll
+        for (int q = 0; q < HS; q++) en[q] = E[0][q];
+#pragma unroll
+        for (int j = 1; j < HS; j++)
+            if (j < S) {
+                const bool w = v[j] > best;
+                best = w ? v[j] : best;
+                f = w ? j : f;
+#pragma unroll
+                for (int q = 0; q < HS; q++) en[q] = w ? E[j][q] : en[q];
+            }
+        out.score = best; out.final_state = f; out.n_used = n;
+#pragma unroll
+        for (int q = 0; q < HS; q++) out.enter[q] = en[q];
+    }
+    a.rec[r] = out;
+}
+
+} // namespace
+
+static_assert(sizeof(sk_hmm_rec) == 40, "sk_hmm_rec is 40 bytes (include/squigglekit_hip.h)");
+static_assert(sizeof(sk_hmm_model) == 632, "sk_hmm_model is 632 bytes (include/squigglekit_hip.h)");
+
+// The rules of the header's "signal HMM" section; nullptr when the model keeps them, else what it breaks.
+const char *sk_hmm_model_error(const sk_hmm_model *m)
+{
+    if (!m) return "NULL sk_hmm_model";
+    const int S = m->nstates;
+    if (S < 1 || S > HS) return "nstates must lie in [1, 6]";
+    const double inf = __builtin_inf();
+    bool any = false;
+    for (int j = 0; j < S; j++) {
+        const double li = m->linit[j];
+        if (li != li || li == inf) return "linit must be finite or -inf";
+        if (li != -inf) any = true;
+        for (int i = 0; i < S; i++) {
+            const double lt = m->ltrans[i][j];
+            if (lt != lt || lt == inf) return "ltrans must be finite or -inf";
+        }
+        bool comp = false;
+        for (int q = 0; q < 2; q++) {
+            const double c = m->c[j][q], mu = m->mu[j][q], h = m->h[j][q];
+            if (c != c || c == inf) return "c must be finite or -inf";
+            if (c != -inf) comp = true;
+            if (!(mu - mu == 0.0)) return "mu must be finite";
+            if (!(h - h == 0.0) || h < 0.0) return "h must be finite and >= 0";
+        }
+        if (!comp) return "every state needs a component with a finite c";
+    }
+    if (!any) return "at least one linit must be finite";
+    return nullptr;
+}
+
+static hmm_kmodel hmm_flatten(const sk_hmm_model *m)
+{
+    hmm_kmodel k;
+    const double ninf = -__builtin_inf();
+    const int S = m->nstates;
+    k.S = S; k.tmask = 0; k.cmask = 0;
+    for (int i = 0; i < HS; i++) {
+        const bool in = i < S;
+        k.linit[i] = in ? m->linit[i] : ninf;
+        for (int j = 0; j < HS; j++) {
+            const double lt = (in && j < S) ? m->ltrans[i][j] : ninf;
+            k.ltrans[i * HS + j] = lt;
+            if (lt != ninf) k.tmask |= 1ull << (i * HS + j);
+        }
+        for (int q = 0; q < 2; q++) {
+            k.c[2 * i + q] = in ? m->c[i][q] : ninf;
+            k.mu[2 * i + q] = in ? m->mu[i][q] : 0.0;
+            k.h[2 * i + q] = in ? m->h[i][q] : 0.0;
+        }
+        if (k.c[2 * i + 1] != ninf) k.cmask |= 1u << i;
+    }
+    return k;
+}
+
+// the records of nreads int16 rows (d_cal: {offset, unit} per read or nullptr) -> d_rec[0 .. nreads)
+int sk_launch_hmm_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                      const double *d_cal, const sk_hmm_model *m, int32_t limit, sk_hmm_rec *d_rec)
+{
+    if (nreads <= 0) return SK_OK;
+    hmm_kargs a;
+    a.sig = d_sig; a.stride = stride; a.len = d_len; a.off = nullptr; a.cal = d_cal; a.nreads = nreads; a.limit = limit;
+    a.vec = ((uintptr_t)d_sig % 16 == 0 && stride % 8 == 0) ? 1 : 0;
+    a.rec = d_rec; a.m = hmm_flatten(m);
+    hipLaunchKernelGGL(k_hmm_viterbi<SK_FEED_I16>, dim3((unsigned)((nreads + 63) / 64)), dim3(64), 0, c->stream, a);
+    SK_HIP(hipGetLastError());
+    return SK_OK;
+}
+
+// ... of nreads ragged float64 reads, read r = d_values[d_off[r] .. d_off[r + 1])
+int sk_launch_hmm_f64(sk_ctx *c, const double *d_values, const int64_t *d_off, int32_t nreads, const sk_hmm_model *m,
+                      int32_t limit, sk_hmm_rec *d_rec)
+{
+    if (nreads <= 0) return SK_OK;
+    hmm_kargs a;
+    a.sig = d_values; a.stride = 0; a.len = nullptr; a.off = d_off; a.cal = nullptr; a.nreads = nreads; a.limit = limit;
+    a.vec = 0; a.rec = d_rec; a.m = hmm_flatten(m);
+    hipLaunchKernelGGL(k_hmm_viterbi<SK_FEED_F64_NORM>, dim3((unsigned)((nreads + 63) / 64)), dim3(64), 0, c->stream, a);
+    SK_HIP(hipGetLastError());
+    return SK_OK;
+}

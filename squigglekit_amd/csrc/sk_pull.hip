@@ -177,8 +177,7 @@ __device__ __forceinline__ tok make_tok(int16_t d, double ofs, double unit, int 
 {
     tok t;
     if (PA) {
-        double x = (double)d + ofs;
-        x = x * unit;
+        double x = sk_raw_to_pa((double)d, ofs, unit);
         x = x * 100.0;
         const double k = rint(x);
         if (!(fabs(k) < PULL_K_LIMIT)) { *bad = 1; t.u = 0; t.neg = 0; t.len = 3; return t; }

@@ -3,7 +3,8 @@
 lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; and, per round, one drawn case each
 of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py);
 the segment levels of every segmenter round against plain numpy; event detection (random read counts, lengths, strides and
-parameters) against the numpy statement of its definition (tests/detect_ref.py).
+parameters) against the numpy statement of its definition (tests/detect_ref.py); the signal HMM (the same reads, a random
+model, calibration, limit, either feed) against tests/hmm_ref.py.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -411,6 +412,40 @@ def main():
         if not np.array_equal(goff, woff) or grec.tobytes() != wrec.tobytes():
             bad += 1
             print("DETECT mismatch round %d: %d reads, max length %d, stride %d, params %s" % (rounds, dn, dmax, dstride, dpar))
+        # ---- signal HMM: the same rows under a random model (1 .. 6 states, -inf transitions and components, sometimes
+        # integer scores), a random calibration and limit, through the int16 or the float64 feed, against the numpy
+        # statement (tests/hmm_ref.py); every record byte for byte
+        import hmm_ref
+        hS = int(rng.integers(1, 7))
+        integer = rng.random() < 0.3
+        if integer:
+            hl, ht = rng.integers(-3, 1, hS).astype(np.float64), rng.integers(-2, 1, (hS, hS)).astype(np.float64)
+            hc, hmu = rng.integers(-2, 1, (hS, 2)).astype(np.float64), rng.integers(-3, 4, (hS, 2)).astype(np.float64) * 100 + 500
+            hh = rng.integers(0, 2, (hS, 2)).astype(np.float64)
+        else:
+            hl, ht = np.log(rng.uniform(0.01, 1, hS)), np.log(rng.uniform(0.001, 1, (hS, hS)))
+            hc, hmu = np.log(rng.uniform(0.01, 1, (hS, 2)) / rng.uniform(2, 90, (hS, 2))), rng.uniform(-200, 1200, (hS, 2))
+            hh = np.where(rng.random((hS, 2)) < 0.2, 0.0, 1.0 / (2.0 * rng.uniform(2, 90, (hS, 2)) ** 2))
+        hl[rng.random(hS) < 0.3] = -np.inf
+        if not np.isfinite(hl).any():
+            hl[int(rng.integers(hS))] = 0.0
+        ht[rng.random((hS, hS)) < 0.4] = -np.inf
+        hc[rng.random(hS) < 0.5, 1] = -np.inf
+        hmodel = api.HmmModel.from_arrays(hS, hl, ht, hc, hmu, hh)
+        hlimit = int(rng.choice([0, 0, 1, 33, 129, 100000]))
+        if rng.random() < 0.3:                                  # the float64 feed (no calibration)
+            hgot = api.hmm_viterbi_ragged_f64(*api.pack_f64(dreads), hmodel, hlimit)
+            hwant = hmm_ref.viterbi_reads(hmodel, dreads, hlimit)
+            hwhat = "float64 feed"
+        else:
+            hcal = None if rng.random() < 0.5 else np.stack([rng.uniform(-50, 50, dn), rng.uniform(0.1, 0.3, dn)], axis=1)
+            hgot = api.hmm_viterbi_batch(dbuf, dlens.astype(np.int32), hmodel, hcal, hlimit)
+            hwant = hmm_ref.viterbi_batch(hmodel, dbuf, dlens, hcal, hlimit)
+            hwhat = "int16 feed, %s" % ("calibrated" if hcal is not None else "raw")
+        if hgot.tobytes() != hwant.tobytes():
+            bad += 1
+            print("HMM mismatch round %d: %d reads, max length %d, stride %d, %d states%s, limit %d, %s" %
+                  (rounds, dn, dmax, dstride, hS, " (integer scores)" if integer else "", hlimit, hwhat))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
