@@ -887,6 +887,48 @@ int sk_hmm_viterbi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *
 int sk_hmm_viterbi_f64_len(const double *values, const int64_t *off, int32_t nreads, const sk_hmm_model *model,
                            int32_t limit, sk_hmm_rec *rec);
 
+/* ---- signal HMM: state paths --------------------------------------------- */
+/* The best path itself, as run-length segments with exact statistics ("Signal HMM state paths";
+ * tests/hmm_path_ref.py states it in numpy).  Model, samples, emission, recurrence and tie rules are those of the section
+ * above, unchanged, and so is the sk_hmm_rec of every read.
+ * Back pointer: for t >= 1 and j < S, arg_j(t) = the predecessor i that won b_j at t -- the lowest i wins ties, also ties
+ *     at -inf.
+ * Path: s(n - 1) = f, the record's final_state; s(t - 1) = arg_{s(t)}(t).
+ * Segments: the maximal runs of equal s(t), in rising start; a read with n = 0 has none.
+ * Winning component of sample t: m = 1 when a_1 > a_0 for state s(t), else m = 0 -- a_0, a_1 by e_j(x)'s operations in
+ *     e_j(x)'s order, on the calibrated x where a calibration is given.
+ * Record: n1 = the segment's samples whose component 1 won; sum[m] = the sum of the samples component m won, sumsq[m] the
+ *     sum of their squares.  int16 rows: exact integers of the RAW samples, with or without cal2 (the calibration is
+ *     affine: the host converts).  float64 values: doubles, each accumulated one sample at a time in rising t from 0.0 as
+ *     sum += x and sumsq += x * x, every step one correctly rounded operation.
+ * It follows that a read's segments tile [0, n), that neighbours differ in state, that the first start of state k is
+ * enter[k], that the last segment's state is final_state, and that every step between neighbours has a finite ltrans. */
+typedef struct sk_hmm_seg {         /* 48 bytes */
+    int32_t state, start, length, n1;
+    int64_t sum[2], sumsq[2];
+} sk_hmm_seg;
+typedef struct sk_hmm_segf {        /* 48 bytes: the float64 feed's record */
+    int32_t state, start, length, n1;
+    double  sum[2], sumsq[2];
+} sk_hmm_segf;
+/* The arguments of the matching sk_hmm_viterbi_* call, then off, seg and cap with sk_detect_events_*'s contract: off gets
+ * nreads + 1 entries, always -- read r's segments are seg[off[r] .. off[r+1]).  The segments are written only when
+ * off[nreads] <= cap; otherwise the call returns SK_ERR_OVERFLOW, rec and off are complete and nothing is written to seg.
+ * seg == NULL with cap == 0 is the counting call (SK_OK when there is no segment at all).  Besides the checks of
+ * sk_hmm_viterbi_*: NULL off, seg == NULL with cap > 0, cap < 0 are SK_ERR_INVALID, before the device is looked at. */
+int sk_hmm_segments_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,
+                        const sk_hmm_model *model, int32_t limit, sk_hmm_rec *rec, int64_t *off /* [nreads + 1] */,
+                        sk_hmm_seg *seg, int64_t cap);
+/* device-resident form (every pointer a device pointer but `model`; nothing is synchronised): returns SK_OK, the caller
+ * reads d_off[nreads]; above cap the contents of d_seg are unspecified (nothing is written past d_seg[cap - 1]).  A
+ * large batch is worked through in slices of whole 64-read groups, 4 bytes of scratch per sample padded to `stride` (or
+ * `limit`) within a fixed budget. */
+int sk_hmm_segments_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
+                            const sk_hmm_model *model, int32_t limit, sk_hmm_rec *d_rec, int64_t *d_off /* [nreads + 1] */,
+                            sk_hmm_seg *d_seg, int64_t cap);
+int sk_hmm_segments_f64_len(const double *values, const int64_t *in_off, int32_t nreads, const sk_hmm_model *model,
+                            int32_t limit, sk_hmm_rec *rec, int64_t *off /* [nreads + 1] */, sk_hmm_segf *seg, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,11 @@ class HmmModel(C.Structure):
 
 
 HMM_DTYPE = np.dtype([("score", "<f8"), ("final_state", "<i4"), ("n_used", "<i4"), ("enter", "<i4", (SK_HMM_STATES,))])
+# sk_hmm_seg / sk_hmm_segf: a maximal run of one state on the best path (int16 feed: exact integers of the raw samples)
+HMM_SEG_DTYPE = np.dtype([("state", "<i4"), ("start", "<i4"), ("length", "<i4"), ("n1", "<i4"), ("sum", "<i8", (2,)),
+                          ("sumsq", "<i8", (2,))])
+HMM_SEGF_DTYPE = np.dtype([("state", "<i4"), ("start", "<i4"), ("length", "<i4"), ("n1", "<i4"), ("sum", "<f8", (2,)),
+                           ("sumsq", "<f8", (2,))])
 
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
@@ -372,6 +377,12 @@ ABI = {
     "sk_hmm_viterbi_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp]),
     # ... ragged float64 values: values, off, nreads, model, limit, rec
     "sk_hmm_viterbi_f64_len": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(HmmModel), C.c_int32, _vp]),
+    # signal HMM state paths: the arguments of the matching sk_hmm_viterbi_* call, then off [nreads + 1], seg, cap
+    "sk_hmm_segments_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp,
+                                      C.c_int64]),
+    "sk_hmm_segments_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp,
+                                          C.c_int64]),
+    "sk_hmm_segments_f64_len": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp, C.c_int64]),
 }
 
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HmmModel, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HmmModel, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -1700,12 +1700,9 @@ POLYA_PRESETS = {
 }
 
 
-def polya_model(preset="rna_pa"):
-    """The six-state model START, LEADER, ADAPTER, POLYA, CLIFF, TRANSCRIPT of a direct-RNA read.  Transitions: S -> S, L;
-    L -> L, A; A -> A, P; P -> P, C, T; C -> C, P; T -> T; every other one is impossible, and a read starts in START or
-    LEADER.  POLYA is one tight Gaussian plus a flat component, TRANSCRIPT a mixture of two Gaussians.  Presets:
-    "rna_pa" (pA; the values are this project's own choice, see POLYA_PRESETS) and "synth_raw" (raw units, matching
-    synth.drna_reads)."""
+def polya_spec(preset="rna_pa"):
+    """The description (init, trans, emissions) of polya_model(preset), as hmm_model takes it and hmm_refit changes it:
+    polya_model(preset) is hmm_model(*polya_spec(preset))."""
     if preset not in POLYA_PRESETS:
         raise ValueError("preset %r: need one of %s" % (preset, sorted(POLYA_PRESETS)))
     p = POLYA_PRESETS[preset]
@@ -1717,7 +1714,16 @@ def polya_model(preset="rna_pa"):
     T[POLYA][POLYA], T[POLYA][CLIFF], T[POLYA][TRANSCRIPT] = stay[POLYA], cliff, 1.0 - stay[POLYA] - cliff
     T[CLIFF][CLIFF], T[CLIFF][POLYA] = stay[CLIFF], 1.0 - stay[CLIFF]
     T[TRANSCRIPT][TRANSCRIPT] = 1.0
-    return hmm_model([0.5, 0.5, 0.0, 0.0, 0.0, 0.0], T, p["emissions"])
+    return [0.5, 0.5, 0.0, 0.0, 0.0, 0.0], T, [[tuple(comp) for comp in comps] for comps in p["emissions"]]
+
+
+def polya_model(preset="rna_pa"):
+    """The six-state model START, LEADER, ADAPTER, POLYA, CLIFF, TRANSCRIPT of a direct-RNA read.  Transitions: S -> S, L;
+    L -> L, A; A -> A, P; P -> P, C, T; C -> C, P; T -> T; every other one is impossible, and a read starts in START or
+    LEADER.  POLYA is one tight Gaussian plus a flat component, TRANSCRIPT a mixture of two Gaussians.  Presets:
+    "rna_pa" (pA; the values are this project's own choice, see POLYA_PRESETS) and "synth_raw" (raw units, matching
+    synth.drna_reads)."""
+    return hmm_model(*polya_spec(preset))
 
 
 POLYA_DTYPE = np.dtype([("adapter_start", "<i4"), ("adapter_end", "<i4"), ("polya_start", "<i4"), ("polya_end", "<i4"),
@@ -1741,3 +1747,290 @@ def polya_segments(records):
     out["polya_end"] = np.where(found, en[:, TRANSCRIPT] - 1, -1)
     out["polya_samples"] = np.where(found, en[:, TRANSCRIPT] - en[:, POLYA], 0)
     return out
+
+
+# ----------------------------------------------------------------------------
+# signal HMM state paths: the best path as run-length segments with exact statistics, pooled counts, and one-call
+# re-estimation of a model from them (the definition: "signal HMM: state paths" in include/squigglekit_hip.h)
+# ----------------------------------------------------------------------------
+def _segments_call(call, R, dtype, cap):
+    """rec, off, seg of one C call; the room for the segments is a first guess, a batch that needs more is counted by
+    that call and runs again with the count"""
+    rec = np.zeros(R, dtype=HMM_DTYPE)
+    off = np.zeros(R + 1, dtype=np.int64)
+    while True:
+        seg = np.zeros(cap, dtype=dtype)
+        rc = call(rec, off, seg, cap)
+        if rc == _lib.SK_ERR_OVERFLOW and int(off[R]) > cap:
+            cap = int(off[R])
+            continue
+        check(rc)
+        return rec, off, seg[:int(off[R])]
+
+
+def hmm_segments_batch(sig, lens, model, cal2=None, limit=0):
+    """hmm_viterbi_batch with the best path itself: (rec HMM_DTYPE [R], off int64 [R + 1], seg HMM_SEG_DTYPE [off[R]]).
+    Read r's segments -- the maximal runs of one state, in rising start -- are seg[off[r]:off[r + 1]]; each holds state,
+    start, length, n1 (samples whose second emission component won) and per winning component the exact sum and sum of
+    squares of its RAW samples, with or without cal2 (hmm_segment_levels converts).  rec is hmm_viterbi_batch's."""
+    L = _lib.ensure_init()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    if sig.ndim != 2:
+        raise ValueError("sig must be [reads, samples]")
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    if lens.shape != (R,):
+        raise ValueError("lens must hold one length per row")
+    cal2 = _hmm_cal(cal2, R)
+    if R == 0 or stride == 0:
+        rec = np.zeros(R, dtype=HMM_DTYPE)
+        rec["final_state"], rec["enter"] = -1, -1
+        return rec, np.zeros(R + 1, dtype=np.int64), np.zeros(0, dtype=HMM_SEG_DTYPE)
+    cap = 16 * R + int(np.clip(lens, 0, stride).sum()) // 512
+
+    def call(rec, off, seg, cap):
+        return L.sk_hmm_segments_i16(ptr(sig), stride, ptr(lens), R, None if cal2 is None else ptr(cal2), C.byref(model),
+                                     int(limit), ptr(rec), ptr(off), ptr(seg) if cap else None, cap)
+    return _segments_call(call, R, HMM_SEG_DTYPE, cap)
+
+
+def hmm_segments_ragged_f64(values, off, model, limit=0):
+    """hmm_segments_batch for ragged float64 reads, read r = values[off[r]:off[r + 1]]: (rec, seg_off, seg HMM_SEGF_DTYPE)
+    -- the sums are float64, accumulated sample by sample in rising order."""
+    L = _lib.ensure_init()
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = max(off.size - 1, 0)
+    if R == 0:
+        return np.zeros(0, dtype=HMM_DTYPE), np.zeros(1, dtype=np.int64), np.zeros(0, dtype=HMM_SEGF_DTYPE)
+    if values.size == 0:
+        values = np.zeros(1)
+    cap = 16 * R + int(off[R] - off[0]) // 512
+
+    def call(rec, soff, seg, cap):
+        return L.sk_hmm_segments_f64_len(ptr(values), ptr(off), R, C.byref(model), int(limit), ptr(rec), ptr(soff),
+                                         ptr(seg) if cap else None, cap)
+    return _segments_call(call, R, HMM_SEGF_DTYPE, cap)
+
+
+def _segments_parts(reads, model, limit=0):
+    """the reads of a list through both feeds: [(indices into reads, rec, off, seg)], integer-valued reads first"""
+    ints, arrs, flts = _split_int16(reads)
+    parts = []
+    if ints:
+        parts.append((ints,) + hmm_segments_batch(*pack_i16([np.asarray(a).reshape(-1) for a in arrs]), model, None, limit))
+    if flts:
+        parts.append((flts,) + hmm_segments_ragged_f64(*pack_f64([reads[i] for i in flts]), model, limit))
+    return parts
+
+
+def hmm_segments(reads, model, limit=0):
+    """The records and segments of a list of reads of any lengths: (rec HMM_DTYPE [R], segs) with segs[r] the segments of
+    read r -- HMM_SEG_DTYPE for an integer-valued read (int16 feed), HMM_SEGF_DTYPE otherwise.  Input order is kept."""
+    rec = np.zeros(len(reads), dtype=HMM_DTYPE)
+    segs = [None] * len(reads)
+    for idx, prec, off, seg in _segments_parts(reads, model, limit):
+        rec[idx] = prec
+        for k, i in enumerate(idx):
+            segs[i] = seg[int(off[k]):int(off[k + 1])]
+    return rec, segs
+
+
+def hmm_state_path(seg_of_read, n=None):
+    """The state of every sample of one read from its segments (int32 [n]); n, when given, is checked against them."""
+    seg = np.asarray(seg_of_read)
+    path = np.repeat(seg["state"].astype(np.int32), seg["length"])
+    if n is not None and path.size != int(n):
+        raise ValueError("the segments hold %d samples, not %d" % (path.size, int(n)))
+    return path
+
+
+def _seg_moments(seg):
+    """length, sum and sum of squares of every segment (both components together) as long doubles"""
+    seg = np.asarray(seg)
+    return (seg["length"].astype(np.longdouble), seg["sum"].astype(np.longdouble).sum(axis=1),
+            seg["sumsq"].astype(np.longdouble).sum(axis=1))
+
+
+def hmm_segment_levels(seg, cal=None):
+    """(mean, stdv) of every segment's samples (ddof 0) in the model's units, float64.  cal: None, one (offset, unit) pair,
+    or one pair per segment ([len(seg), 2], e.g. np.repeat(cal2, np.diff(off), axis=0)) -- the affine conversion of the raw
+    sums of the int16 feed: mean = (mean_raw + offset) * unit, stdv = stdv_raw * |unit|."""
+    n, s, q = _seg_moments(seg)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = s / n
+        stdv = np.sqrt(np.maximum(q / n - mean * mean, 0))
+    if cal is not None:
+        cal = np.asarray(cal, dtype=np.float64).reshape(-1, 2)
+        if len(cal) not in (1, len(mean)):
+            raise ValueError("cal must hold one (offset, unit) pair, or one per segment")
+        mean = (mean + cal[:, 0]) * cal[:, 1]
+        stdv = stdv * np.abs(cal[:, 1])
+    return mean.astype(np.float64), stdv.astype(np.float64)
+
+
+def hmm_pool(rec, off, seg, S, cal2=None):
+    """What the paths of a batch say about its model, as a dict: "n", "sum", "sumsq" [S, 2] -- per state and emission
+    component the samples it won, their sum and sum of squares in the model's units (int64 and exact for the int16 feed
+    without cal2; float64 under cal2 [R, 2] = (offset, unit) per read: x = (raw + offset) * unit, expanded on the sums) --
+    "trans" [S, S] int64: length - 1 stays per segment plus one step per pair of neighbours, "init" [S] int64: the first
+    state of every read with samples, and "reads": those reads."""
+    off = np.asarray(off, dtype=np.int64)
+    seg = np.asarray(seg)
+    R = off.size - 1
+    if len(np.asarray(rec)) != R:
+        raise ValueError("rec and off must describe the same reads")
+    st = seg["state"].astype(np.int64)
+    ln = seg["length"].astype(np.int64)
+    n1 = seg["n1"].astype(np.int64)
+    per = np.diff(off)
+    exact = seg["sum"].dtype.kind == "i" and cal2 is None
+    sm, sq = seg["sum"], seg["sumsq"]
+    cnt = np.stack([ln - n1, n1], axis=1)
+    if cal2 is not None:
+        cal2 = np.asarray(cal2, dtype=np.float64).reshape(-1, 2)
+        if len(cal2) != R:
+            raise ValueError("cal2 must hold one (offset, unit) pair per read")
+        o, u = np.repeat(cal2[:, 0], per)[:, None], np.repeat(cal2[:, 1], per)[:, None]
+        smf, sqf, cf = sm.astype(np.float64), sq.astype(np.float64), cnt.astype(np.float64)
+        sq = (u * u) * (sqf + 2.0 * o * smf + cf * (o * o))
+        sm = u * (smf + cf * o)
+    dt = np.int64 if exact else np.float64
+    out = {"n": np.zeros((S, 2), dtype=np.int64), "sum": np.zeros((S, 2), dtype=dt), "sumsq": np.zeros((S, 2), dtype=dt),
+           "trans": np.zeros((S, S), dtype=np.int64), "init": np.zeros(S, dtype=np.int64), "reads": int((per > 0).sum())}
+    np.add.at(out["n"], st, cnt)
+    np.add.at(out["sum"], st, sm.astype(dt))
+    np.add.at(out["sumsq"], st, sq.astype(dt))
+    np.add.at(out["trans"], (st, st), ln - 1)
+    if st.size:
+        first = np.zeros(st.size, dtype=bool)
+        first[off[:-1][per > 0]] = True
+        np.add.at(out["init"], st[first], 1)
+        nb = ~first[1:]                                      # pairs of neighbours inside one read
+        np.add.at(out["trans"], (st[:-1][nb], st[1:][nb]), 1)
+    return out
+
+
+def hmm_pool_add(a, b):
+    """the pooled counts of two batches together (a may be None)"""
+    if a is None:
+        return b
+    out = {}
+    for k in a:
+        if k == "reads":
+            out[k] = a[k] + b[k]
+        elif a[k].dtype == b[k].dtype:
+            out[k] = a[k] + b[k]
+        else:
+            out[k] = a[k].astype(np.float64) + b[k].astype(np.float64)
+    return out
+
+
+def hmm_spec_to_json(spec):
+    """The description (init, trans, emissions) of a model as JSON text -- settings only; a flat component's mean is null.
+    hmm_spec_from_json gives the same numbers back."""
+    import json
+    init, trans, emissions = spec
+    return json.dumps({"init": [float(p) for p in init], "trans": [[float(p) for p in row] for row in trans],
+                       "emissions": [[[float(w), None if m is None else float(m), float(s)] for w, m, s in comps]
+                                     for comps in emissions]}, indent=1) + "\n"
+
+
+def hmm_spec_from_json(text):
+    import json
+    d = json.loads(text)
+    try:
+        spec = ([float(p) for p in d["init"]], [[float(p) for p in row] for row in d["trans"]],
+                [[(float(w), None if m is None else float(m), float(s)) for w, m, s in comps] for comps in d["emissions"]])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("not a model description: need init [S], trans [S][S] and emissions [S][1 or 2][3]") from None
+    hmm_model(*spec)                                         # (its checks)
+    return spec
+
+
+HMM_REFIT_FIELDS = ("mean", "sigma", "weight", "trans")
+
+
+def hmm_refit(spec, pooled, states, update=("mean", "sigma"), sigma_floor=1.0, min_count=16, pseudo=1.0):
+    """One round of Viterbi training: a new description from `spec` and the pooled counts of its paths (hmm_pool).  Only
+    the states named in `states` and only the fields named in `update` change:
+      "mean", "sigma"  a Gaussian component that won N >= min_count samples: mean = sum / N,
+                       sigma = sqrt(max(sumsq / N - (sum / N)^2, sigma_floor^2)); a flat component keeps its range.
+      "weight"         a state of two components, N = N_0 + N_1 >= min_count: weight_m = W * (N_m + pseudo * old_m / W) /
+                       (N + pseudo) with W = old_0 + old_1 -- smoothed toward the old weights by `pseudo` samples.
+      "trans"          the state's row, N = its steps >= min_count: over the allowed (non-zero) transitions only,
+                       p_j = (A_j + pseudo * old_j / sum(old)) / (N + pseudo): the row sums to 1, a forbidden transition
+                       stays forbidden and an allowed one stays above zero.
+    The default leaves weights and transitions alone on purpose: with everything free, wide states take samples from their
+    neighbours round after round."""
+    init, trans, emissions = spec
+    bad = [f for f in update if f not in HMM_REFIT_FIELDS]
+    if bad:
+        raise ValueError("update: no field %r (fields: %s)" % (bad[0], ", ".join(HMM_REFIT_FIELDS)))
+    if not (sigma_floor > 0 and pseudo > 0):
+        raise ValueError("sigma_floor and pseudo must be positive")
+    S = len(init)
+    init = [float(p) for p in init]
+    trans = [[float(p) for p in row] for row in trans]
+    emissions = [[tuple(comp) for comp in comps] for comps in emissions]
+    for k in states:
+        k = int(k)
+        if not 0 <= k < S:
+            raise ValueError("state %d: the model has %d states" % (k, S))
+        n = [float(v) for v in pooled["n"][k]]
+        comps = list(emissions[k])
+        for m, (w, mean, width) in enumerate(comps):
+            if mean is None or n[m] < max(min_count, 1):
+                continue
+            mu = float(pooled["sum"][k][m]) / n[m]
+            if "sigma" in update:
+                width = float(np.sqrt(max(float(pooled["sumsq"][k][m]) / n[m] - mu * mu, sigma_floor * sigma_floor)))
+            if "mean" in update:
+                mean = mu
+            comps[m] = (w, mean, width)
+        if "weight" in update and len(comps) == 2 and n[0] + n[1] >= max(min_count, 1):
+            W = comps[0][0] + comps[1][0]
+            comps = [(W * (n[m] + pseudo * comps[m][0] / W) / (n[0] + n[1] + pseudo),) + comps[m][1:] for m in range(2)]
+        emissions[k] = comps
+        if "trans" in update:
+            A = [float(v) for v in pooled["trans"][k]]
+            allowed = [j for j in range(S) if trans[k][j] > 0.0]
+            N, old = sum(A[j] for j in allowed), sum(trans[k][j] for j in allowed)
+            if allowed and N >= max(min_count, 1):
+                for j in allowed:
+                    trans[k][j] = (A[j] + pseudo * trans[k][j] / old) / (N + pseudo)
+    return init, trans, emissions
+
+
+def hmm_fit(batches, spec, states, rounds, update=("mean", "sigma"), sigma_floor=1.0, min_count=16, pseudo=1.0, limit=0,
+            decode=None):
+    """Viterbi training: `rounds` times decode every batch under the current model, pool the paths, refit (hmm_refit).
+    batches: a list of reads (one batch), or a callable that returns an iterable of batches -- each a list of reads or a
+    tuple (sig int16 [R, stride], lens, cal2 or None) -- and is called once per round (a file streamed again).  decode:
+    None for the GPU (hmm_segments_batch / hmm_segments_ragged_f64), or decode(batch, model, limit) -> an iterable of
+    (rec, off, seg, cal2).  Returns (spec, history): history[i] = {"round", "reads", "segments", "max_segments", "pooled",
+    "spec"} of round i -- its counts and the description they led to."""
+    def gpu_decode(batch, model, limit):
+        if isinstance(batch, tuple):
+            sig, lens, cal2 = (tuple(batch) + (None,))[:3]
+            yield hmm_segments_batch(sig, lens, model, cal2, limit) + (cal2,)
+        else:
+            for _idx, rec, off, seg in _segments_parts(batch, model, limit):
+                yield rec, off, seg, None
+    decode = decode or gpu_decode
+    S = len(spec[0])
+    history = []
+    for rnd in range(int(rounds)):
+        model = hmm_model(*spec)
+        pooled, nseg, most = None, 0, 0
+        for batch in (batches() if callable(batches) else [batches]):
+            for rec, off, seg, cal2 in decode(batch, model, limit):
+                pooled = hmm_pool_add(pooled, hmm_pool(rec, off, seg, S, cal2))
+                nseg += int(off[-1])
+                most = max(most, int(np.diff(off).max(initial=0)))
+        if pooled is None:
+            raise ValueError("hmm_fit: no reads")
+        spec = hmm_refit(spec, pooled, states, update, sigma_floor, min_count, pseudo)
+        history.append({"round": rnd, "reads": pooled["reads"], "segments": nseg, "max_segments": most, "pooled": pooled,
+                        "spec": spec})
+    return spec, history

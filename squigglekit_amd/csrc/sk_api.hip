@@ -2642,3 +2642,128 @@ int sk_hmm_viterbi_f64_len(const double *values, const int64_t *off, int32_t nre
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ signal HMM: state paths (sk_hmm.hip)
+// The definition: include/squigglekit_hip.h, "signal HMM: state paths".  Per sub-batch and per slice of whole 64-read
+// groups: the forward pass that keeps the back pointers, the running scan of the segment counts, the backward sweep;
+// then the statistics of the whole call in one launch.
+namespace {
+
+int check_hmm_segments(const sk_hmm_model *model, int32_t limit, int32_t nreads, const sk_hmm_rec *rec, const int64_t *off,
+                       const void *seg, int64_t cap)
+{
+    int rc = check_hmm(model, limit, nreads, rec);
+    if (rc) return rc;
+    if (!off) return sk_fail(SK_ERR_INVALID, "NULL off");
+    if (cap < 0) return sk_fail(SK_ERR_INVALID, "cap < 0");
+    if (cap > 0 && !seg) return sk_fail(SK_ERR_INVALID, "NULL seg with a cap");
+    return SK_OK;
+}
+
+// off [nreads + 1] of a host entry point on the device, the records behind it (16-byte aligned)
+size_t hmm_off_bytes(int32_t nreads) { return ((size_t)nreads + 2) / 2 * 2 * sizeof(int64_t); }
+
+// rec, off and -- unless they overflow cap -- the segments of a host entry point, from the device
+int hmm_segments_finish(sk_ctx *c, int32_t nreads, const sk_hmm_rec *d_rec, const int64_t *d_off, const void *d_seg,
+                        sk_hmm_rec *rec, int64_t *off, void *seg, int64_t cap)
+{
+    SK_HIP(hipMemcpyAsync(rec, d_rec, (size_t)nreads * sizeof(sk_hmm_rec), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(off, d_off, ((size_t)nreads + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    const int64_t total = off[nreads];
+    if (total > cap)
+        return sk_fail(SK_ERR_OVERFLOW, "the reads hold %lld segments, cap is %lld", (long long)total, (long long)cap);
+    if (total == 0) return SK_OK;
+    SK_HIP(hipMemcpyAsync(seg, d_seg, (size_t)total * sizeof(sk_hmm_seg), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_hmm_segments_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads, const double *d_cal2,
+                            const sk_hmm_model *model, int32_t limit, sk_hmm_rec *d_rec, int64_t *d_off, sk_hmm_seg *d_seg,
+                            int64_t cap)
+{
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (rc) return rc;
+    if ((rc = check_hmm_segments(model, limit, nreads, d_rec, d_off, d_seg, cap))) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) {
+        SK_HIP(hipMemsetAsync(d_off, 0, sizeof(int64_t), c->stream));
+        return SK_OK;
+    }
+    const int64_t npad = sk_hmm_npad(stride, limit);
+    if ((rc = sk_reserve(c, &c->hmmpath, sk_hmm_path_work_bytes(nreads, npad)))) return rc;
+    if ((rc = sk_launch_hmm_paths(c, SK_FEED_I16, d_sig, stride, d_len, nullptr, nreads, d_cal2, model, limit, npad,
+                                  c->hmmpath.p, 1, d_rec, d_off, d_seg, cap)))
+        return rc;
+    return sk_launch_hmm_stats(c, SK_FEED_I16, d_sig, stride, nullptr, nreads, d_cal2, model, d_off, d_seg, cap);
+}
+
+int sk_hmm_segments_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,
+                        const sk_hmm_model *model, int32_t limit, sk_hmm_rec *rec, int64_t *off, sk_hmm_seg *seg, int64_t cap)
+{
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_hmm_segments(model, limit, nreads, rec, off, seg, cap))) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    SK_ENTER(c);
+    off[0] = 0;
+    if (nreads == 0) return SK_OK;
+    const SubBatches B = sub_batches(nreads, stride);
+    const int64_t npad = sk_hmm_npad(stride, limit);
+    const size_t rec_bytes = (size_t)nreads * sizeof(sk_hmm_rec), off_bytes = hmm_off_bytes(nreads);
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->hmm, rec_bytes + (size_t)nreads * 2 * sizeof(double)))) return rc;
+    if ((rc = sk_reserve(c, &c->hmmpath, sk_hmm_path_work_bytes(B.per, npad)))) return rc;
+    if ((rc = sk_reserve(c, &c->hmmseg, off_bytes + (size_t)cap * sizeof(sk_hmm_seg)))) return rc;
+    sk_hmm_rec *d_rec = (sk_hmm_rec *)c->hmm.p;
+    double *d_cal = cal2 ? (double *)((char *)c->hmm.p + rec_bytes) : nullptr;
+    int64_t *d_off = (int64_t *)c->hmmseg.p;
+    sk_hmm_seg *d_seg = cap > 0 ? (sk_hmm_seg *)((char *)c->hmmseg.p + off_bytes) : nullptr;
+    if (d_cal) SK_HIP(hipMemcpyAsync(d_cal, cal2, (size_t)nreads * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return sk_launch_hmm_paths(c, SK_FEED_I16, d_sig, stride, d_len, nullptr, nr,
+                                                    d_cal ? d_cal + 2 * (size_t)r0 : nullptr, model, limit, npad, c->hmmpath.p,
+                                                    r0 == 0, d_rec + r0, d_off + r0, d_seg, cap);
+                     });
+    if (rc) return rc;
+    if ((rc = sk_launch_hmm_stats(c, SK_FEED_I16, c->sig.p, stride, nullptr, nreads, d_cal, model, d_off, d_seg, cap))) return rc;
+    return hmm_segments_finish(c, nreads, d_rec, d_off, d_seg, rec, off, seg, cap);
+}
+
+int sk_hmm_segments_f64_len(const double *values, const int64_t *in_off, int32_t nreads, const sk_hmm_model *model,
+                            int32_t limit, sk_hmm_rec *rec, int64_t *off, sk_hmm_segf *seg, int64_t cap)
+{
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_hmm_segments(model, limit, nreads, rec, off, seg, cap);
+    if (rc) return rc;
+    if (!values || !in_off) return sk_fail(SK_ERR_INVALID, "NULL values/off");
+    SK_ENTER(c);
+    off[0] = 0;
+    if (nreads == 0) return SK_OK;
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, values, in_off, nreads, &total, &maxlen))) return rc;   // (checks the lengths)
+    const int64_t npad = sk_hmm_npad(maxlen, limit);
+    const size_t rec_bytes = (size_t)nreads * sizeof(sk_hmm_rec), off_bytes = hmm_off_bytes(nreads);
+    if ((rc = sk_reserve(c, &c->hmm, rec_bytes))) return rc;
+    if ((rc = sk_reserve(c, &c->hmmpath, sk_hmm_path_work_bytes(nreads, npad)))) return rc;
+    if ((rc = sk_reserve(c, &c->hmmseg, off_bytes + (size_t)cap * sizeof(sk_hmm_segf)))) return rc;
+    sk_hmm_rec *d_rec = (sk_hmm_rec *)c->hmm.p;
+    int64_t *d_off = (int64_t *)c->hmmseg.p;
+    sk_hmm_segf *d_seg = cap > 0 ? (sk_hmm_segf *)((char *)c->hmmseg.p + off_bytes) : nullptr;
+    if ((rc = sk_launch_hmm_paths(c, SK_FEED_F64_NORM, c->sig.p, 0, nullptr, (const int64_t *)c->off.p, nreads, nullptr, model,
+                                  limit, npad, c->hmmpath.p, 1, d_rec, d_off, (sk_hmm_seg *)d_seg, cap)))
+        return rc;
+    if ((rc = sk_launch_hmm_stats(c, SK_FEED_F64_NORM, c->sig.p, 0, (const int64_t *)c->off.p, nreads, nullptr, model, d_off,
+                                  d_seg, cap)))
+        return rc;
+    return hmm_segments_finish(c, nreads, d_rec, d_off, d_seg, rec, off, seg, cap);
+}
+
+} // extern "C"

@@ -106,6 +106,8 @@ struct sk_ctx {
     sk_buf detect;    // event detection: the mark words [nreads][ceil(stride / 64)], then the scan's block sums (sk_detect.hip)
     sk_buf detectout; // event detection: off [nreads + 1], then the sk_det_event records of the host entry point
     sk_buf hmm;       // signal HMM: the sk_hmm_rec records of the host entry points, then their {offset, unit} pairs (sk_hmm.hip)
+    sk_buf hmmpath;   // state paths: a slice's back pointers [group][t][lane], its segment counts, the scan's block sums
+    sk_buf hmmseg;    // state paths: off [nreads + 1], then the sk_hmm_seg records of the host entry points
     std::vector<double> panel_host;           // laid-out motifs as uploaded (kept alive for the async H2D)
     std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
     std::vector<sk_panel_group> panel_groups;
@@ -460,6 +462,20 @@ int sk_launch_hmm_i16(sk_ctx *c, const int16_t *d_sig, int64_t stride, const int
                       const double *d_cal, const sk_hmm_model *m, int32_t limit, sk_hmm_rec *d_rec);
 int sk_launch_hmm_f64(sk_ctx *c, const double *d_values, const int64_t *d_off, int32_t nreads, const sk_hmm_model *m,
                       int32_t limit, sk_hmm_rec *d_rec);
+// State paths (the header's "signal HMM: state paths").  npad: the most samples a read of the call can use (maxlen: the
+// stride, or the longest ragged read); the back pointers of a slice of whole 64-read groups, its counts and the scan's
+// block sums take sk_hmm_path_work_bytes(nreads, npad) bytes -- never more than the budget (16 GiB, or
+// SK_HMM_SCRATCH_MB) unless one group alone needs more.  Paths: records, offsets (continuing from d_off[0] unless
+// `first`) and state / start / length of every segment, slice by slice; stats: n1, sum, sumsq of the whole call.  Reads
+// whose segments end past cap get no records.
+int64_t sk_hmm_npad(int64_t maxlen, int32_t limit);
+int64_t sk_hmm_slice_groups(int32_t nreads, int64_t npad);
+size_t  sk_hmm_path_work_bytes(int32_t nreads, int64_t npad);
+int sk_launch_hmm_paths(sk_ctx *c, int feed, const void *d_sig, int64_t stride, const int32_t *d_len, const int64_t *d_roff,
+                        int32_t nreads, const double *d_cal, const sk_hmm_model *m, int32_t limit, int64_t npad, void *d_work,
+                        int first, sk_hmm_rec *d_rec, int64_t *d_off, sk_hmm_seg *d_seg, int64_t cap);
+int sk_launch_hmm_stats(sk_ctx *c, int feed, const void *d_sig, int64_t stride, const int64_t *d_roff, int32_t nreads,
+                        const double *d_cal, const sk_hmm_model *m, const int64_t *d_off, void *d_seg, int64_t cap);
 
 // ---- SquigglePull text (sk_pull.hip) ----
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries

@@ -4,7 +4,7 @@ lengths, strides, motif lengths, outlier limits, both scalings, segmenter parame
 of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py);
 the segment levels of every segmenter round against plain numpy; event detection (random read counts, lengths, strides and
 parameters) against the numpy statement of its definition (tests/detect_ref.py); the signal HMM (the same reads, a random
-model, calibration, limit, either feed) against tests/hmm_ref.py.
+model, calibration, limit, either feed) against tests/hmm_ref.py, and its state paths against tests/hmm_path_ref.py.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -445,6 +445,19 @@ def main():
         if hgot.tobytes() != hwant.tobytes():
             bad += 1
             print("HMM mismatch round %d: %d reads, max length %d, stride %d, %d states%s, limit %d, %s" %
+                  (rounds, dn, dmax, dstride, hS, " (integer scores)" if integer else "", hlimit, hwhat))
+        # ---- signal HMM state paths: the same reads, model, calibration and limit through the matching segments call,
+        # against the numpy statement (tests/hmm_path_ref.py): records, offsets and segments byte for byte
+        import hmm_path_ref
+        if hwhat == "float64 feed":
+            pgot = api.hmm_segments_ragged_f64(*api.pack_f64(dreads), hmodel, hlimit)
+            pwant = hmm_path_ref.segments_reads(hmodel, dreads, hlimit)
+        else:
+            pgot = api.hmm_segments_batch(dbuf, dlens.astype(np.int32), hmodel, hcal, hlimit)
+            pwant = hmm_path_ref.segments_batch(hmodel, dbuf, dlens, hcal, hlimit)
+        if [x.tobytes() for x in pgot] != [x.tobytes() for x in pwant] or pgot[0].tobytes() != hgot.tobytes():
+            bad += 1
+            print("HMM PATH mismatch round %d: %d reads, max length %d, stride %d, %d states%s, limit %d, %s" %
                   (rounds, dn, dmax, dstride, hS, " (integer scores)" if integer else "", hlimit, hwhat))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
