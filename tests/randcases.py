@@ -1,20 +1,21 @@
-"""Seeded random cases for the four newest kernel files (csrc/sk_sweep.hip, sk_hits.hip, sk_path.hip, sk_pull.hip): per
-family  draw_<family>(rng) -> case,  expect_<family>(ora, case) -> what the reference says,  call_<family>(api, case,
-exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or the first difference as text.
+"""Seeded random cases for the kernel files that have no other randomised test in the suite -- csrc/sk_sweep.hip,
+sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, and through the twins
+of the hit family sk_bg.hip and sk_events.hip: per family  draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
+what the reference says,  call_<family>(api, case, exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or
+the first difference as text.
 
 A plain module: not collected, no conftest, pure numpy, no GPU import at module level (`api` is handed in).  The same
 seed gives the same case on any machine: draw_* take a numpy.random.Generator and nothing else.  Used by
 tests/test_random_cases.py (CPU: the committed seeds reach what they claim), tests/test_gpu_random.py (GPU: every seed
-against its reference, plus one interleaved sequence) and tools/fuzz_gpu.py (open-ended).  tests/RANDOM_CASES.md says
-what each family draws and which one-line kernel mutants the committed seeds catch.
+against its reference, plus two interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
+families is DRAW[family] with its running generator).  tests/RANDOM_CASES.md says what each family draws, the
+references, the budgets, the wall times, and which one-line kernel mutants the committed seeds catch.
 
 The references are the statements that already exist: the oracle's scale_outliers + get_segs per (set, read) for the
-sweep, reference_hits (test_hits_host.py), reference_paths (test_paths_host.py), numpy_pull_text (test_squigglepull.py).
-Every comparison is exact: integers as integers, distances and text byte for byte.
-
-Wall times (one run each, 16 oracle threads at most): `pytest tests -m "not gpu"` 70.6 s without tests/test_random_cases.py
-and 69.2 s with it (the module alone: 14 s); `pytest tests -m gpu` on the MI355X 277.7 s with tests/test_gpu_random.py,
-which alone takes 10.4 s -- about 267 s without it (not run separately).
+sweep, reference_hits (test_hits_host.py), reference_paths (test_paths_host.py), numpy_pull_text (test_squigglepull.py),
+reference_panel (test_panel_host.py), detect_ref.py, hmm_ref.py, hmm_path_ref.py, plain numpy on the oracle's segments
+for the levels, reference_background_reads (test_background_host.py), reference_batch / reference_pool
+(test_events_host.py).  Every comparison is exact: integers as integers, doubles and text byte for byte.
 """
 import os
 import sys
@@ -31,16 +32,26 @@ SEEDS = {
     "hits": [1, 20, 87, 95, 131, 214, 298, 324],
     "paths": [1, 12, 29, 50, 123, 135, 187, 272],
     "pull": [0, 3, 21, 40],
+    "panel": [4, 6, 8, 25, 29, 36, 66, 93, 94],
+    "detect": [4, 6, 8, 10, 27, 44],
+    "hmm": [3, 10, 11, 15, 21, 35, 39, 54],
+    "levels": [13, 18, 22, 26, 42, 59],
 }
 
 # every tuning switch a case may set; a runner clears the ones a case does not name
 SWITCHES = ("SK_SEG_DELTA_SCALE", "SK_WALK_GENERAL", "SK_DTW_SMALL_MAX", "SK_HITS_ROW_BYTES", "SK_PATH_LDS_BYTES",
-            "SK_PATH_SCRATCH_BYTES")
+            "SK_PATH_SCRATCH_BYTES", "SK_DTW_NO_SMALL", "SK_PANEL_EXACT", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB")
+
+
+# the family's number in the seed of its generator.  Frozen: the first four are what sorted(SEEDS).index(family) gave when
+# the table held four keys, so those cases stay what they were (tests/test_random_cases.py pins their digests); a new
+# family takes the next free number, whatever its name.
+FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7)
 
 
 def rng_of(family, seed):
-    """The generator of a committed case: the family is part of the seed, so the four lists do not share streams."""
-    return np.random.default_rng([sorted(SEEDS).index(family), int(seed)])
+    """The generator of a committed case: the family is part of the seed, so the lists do not share streams."""
+    return np.random.default_rng([FAMILY_INDEX[family], int(seed)])
 
 
 def case_of(family, seed):
@@ -53,6 +64,11 @@ def _pick(rng, values):
     return values[int(rng.integers(len(values)))]
 
 
+# what a case holds besides its drawn parameters: the arrays (describe leaves them out, case_digest hashes them)
+ARRAY_KEYS = ("reads", "rows", "sets", "motifs", "prefixes", "calib", "lens", "sig", "win", "means", "sds", "model", "cal",
+              "use")
+
+
 def _plain(v):
     if isinstance(v, (np.integer,)):
         return int(v)
@@ -63,10 +79,39 @@ def _plain(v):
 
 def describe(case):
     """Everything needed to reproduce a case, on one line."""
-    keys = [k for k in case if k not in ("reads", "rows", "sets", "motifs", "prefixes", "calib", "lens", "sig")]
+    keys = [k for k in case if k not in ARRAY_KEYS]
     return "%s seed=%s %s env=%s" % (case["family"], case.get("seed"),
                                      " ".join("%s=%s" % (k, _plain(case[k])) for k in keys
                                               if k not in ("family", "seed", "env")), case["env"])
+
+
+def _digest_into(h, v):
+    if isinstance(v, np.ndarray):
+        h.update(("%s%s" % (v.dtype.str, v.shape)).encode())
+        h.update(np.ascontiguousarray(v).tobytes())
+    elif isinstance(v, (bytes, bytearray)):
+        h.update(b"b%d:" % len(v) + bytes(v))
+    elif isinstance(v, dict):
+        for k in sorted(v):
+            h.update(("{%s}" % k).encode())
+            _digest_into(h, v[k])
+    elif isinstance(v, (list, tuple)):
+        h.update(b"[%d]" % len(v))
+        for x in v:
+            _digest_into(h, x)
+    else:
+        h.update(repr(_plain(v)).encode())
+
+
+def case_digest(case):
+    """sha256 over describe(case) and every array the case holds (dtype, shape, bytes): two cases with the same digest
+    are the same input on any machine."""
+    import hashlib
+    h = hashlib.sha256(describe(case).encode())
+    for k in sorted(k for k in case if k in ARRAY_KEYS):
+        h.update(("<%s>" % k).encode())
+        _digest_into(h, case[k])
+    return h.hexdigest()
 
 
 # ======================================================================================================================
@@ -641,6 +686,821 @@ def diff_pull(case, got, exp):
 
 
 # ======================================================================================================================
+# panel
+# ======================================================================================================================
+# sk_panel_plan gives a motif of N points L lanes and R rows per lane: beyond 1 024 points the chained launcher; up to 256
+# points L = 16, R = ceil(N / 16) -- unless the call is "small" (reads * motifs <= SK_DTW_SMALL_MAX = 2 048, and no
+# SK_DTW_NO_SMALL) and N >= 32; everything else L = 64, R = ceil(N / 64).  P = L * R - N lanes hold one row fewer.
+PANEL_N = (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)
+PANEL_K = (1, 2, 3, 12, 64, 256)                 # 256: the ABI's limit
+PANEL_CELLS = 120_000_000                        # cost-matrix cells the oracle fills per case (about 1 s, see RANDOM_CASES.md)
+PANEL_LIMITS = (0, 1200)                         # test_panel_host.oracle_records' limits
+INT32_MAX = 2 ** 31 - 1
+
+
+def panel_shape(N, pairs, env):
+    """(L, R) as sk_panel_plan picks them for a motif of N points in a call of `pairs` (read, motif) pairs; None: the
+    chained launcher."""
+    if N > 64 * 16:
+        return None
+    small_max = 2048
+    if "SK_DTW_SMALL_MAX" in env and int(env["SK_DTW_SMALL_MAX"]) >= 0:
+        small_max = int(env["SK_DTW_SMALL_MAX"])
+    spread = pairs <= small_max and "SK_DTW_NO_SMALL" not in env
+    if N <= 256 and not (spread and N >= 32):
+        return 16, (N + 15) // 16
+    return 64, (N + 63) // 64
+
+
+def _is_int_read(r):
+    r = np.asarray(r)
+    return r.dtype.kind in "iu" or r.size == 0 or bool(np.all(np.isfinite(r)) and np.all(r == np.rint(r)))
+
+
+def panel_calls(case):
+    """Reads per C call: the list form splits into the integer-valued reads and the rest."""
+    if case["route"] != "list":
+        return [case["nreads"]]
+    n = sum(_is_int_read(r) for r in case["reads"])
+    return [v for v in (n, case["nreads"] - n) if v]
+
+
+def panel_groups(case):
+    """[{(L, R) or None: [motif indices]}] per C call of the case."""
+    out = []
+    for R in panel_calls(case):
+        g = {}
+        for k, m in enumerate(case["motifs"]):
+            g.setdefault(panel_shape(len(m), R * len(case["motifs"]), case["env"]), []).append(k)
+        out.append(g)
+    return out
+
+
+def panel_windows(case):
+    """(begin, length) of every read's window, as Python slices it."""
+    out = []
+    for r, raw in enumerate(case["reads"]):
+        a, b = (int(case["win"][r][0]), int(case["win"][r][1])) if case["win"] is not None else case["region"]
+        lo, hi, _ = slice(a, b).indices(len(raw))
+        out.append((lo, max(0, hi - lo)))
+    return out
+
+
+def panel_screened(case):
+    """sk_launch_panel_dtw hands a group to the screening path: 256 reads or more and a longest window of at least
+    4 * (N0 + N0 / 8 + 136) samples, N0 the group's first motif."""
+    if "SK_PANEL_EXACT" in case["env"] or min(panel_calls(case)) < 256:
+        return False
+    longest = max(w for _, w in panel_windows(case))
+    return any(shape is not None and longest >= 4 * (len(case["motifs"][ks[0]]) + len(case["motifs"][ks[0]]) // 8 + 136)
+               for g in panel_groups(case) for shape, ks in g.items())
+
+
+def _panel_len_for(kind, a, c, E, w):
+    """A read length whose window under the region kind has w samples (w <= E)."""
+    return {"head": w, "tail": w, "mid": a + w, "negend": a + c + w}[kind]
+
+
+def _panel_region(kind, a, c, E):
+    return {"head": (0, E), "tail": (-E, None), "mid": (a, a + E), "negend": (a, -c), "empty": (a + E, a + E - c),
+            "beyond": (20000, 20000 + E)}[kind]
+
+
+def draw_panel(rng):
+    from squigglekit_amd import synth
+    env = {}
+    screen = rng.random() < 0.12                  # 256 reads and windows long enough for the screening path
+    batchlay = rng.random() < 0.5
+    if batchlay:                                  # the layout big batches get: every motif of up to 256 points on L = 16
+        env["SK_DTW_SMALL_MAX"] = "0"
+        env["SK_DTW_NO_SMALL"] = "1"
+    K = int(_pick(rng, PANEL_K[:3])) if screen else int(_pick(rng, PANEL_K if batchlay else PANEL_K[:4]))
+    # ---- motif lengths: the listed ones, (L, R, P) triples made on purpose, random ones; for big panels mostly short
+    def one_n(short):
+        u = rng.random()
+        if short:
+            return int(rng.integers(1, 49))
+        if u < 0.4:
+            return int(_pick(rng, PANEL_N))
+        if u < 0.8:
+            L = int(_pick(rng, (16, 64)))
+            return max(1, L * int(rng.integers(1, 17)) - int(_pick(rng, (0, 1, L - 1, int(rng.integers(0, L))))))
+        return int(rng.integers(1, 300))
+    if screen:
+        Ns = [16] + [int(rng.integers(1, 25)) for _ in range(K - 1)]
+    else:
+        Ns = [one_n(k >= 6) for k in range(K)]
+        if K >= 12 and rng.random() < 0.6:       # a ladder: up to 16 different R of one L in one call
+            L = 16 if batchlay and rng.random() < 0.6 else 64
+            for k, r in enumerate(rng.permutation(16)[:min(K, 16)] + 1):
+                Ns[k] = max(1, L * int(r) - int(_pick(rng, (0, 1, L - 1, int(rng.integers(0, L))))))
+        elif K >= 3 and rng.random() < 0.6:      # three groups or more with several members each, and a long motif
+            base = [int(_pick(rng, (5, 16, 20, 40, 48)))]
+            base += [base[0] + 16, base[0] + 40]
+            for k in range(K):
+                if k >= 1 and rng.random() < 0.7:
+                    Ns[k] = base[k % 3] - int(rng.integers(0, 3))
+            Ns[int(rng.integers(1, K))] = int(rng.integers(1025, 1101))
+    motifs = [synth.synthetic_motif(N, seed=int(rng.integers(1000))) for N in Ns]
+    twins = None
+    if K >= 2 and rng.random() < 0.6:            # two identical motifs (same length: same mean and sd): score ties
+        i, j = (int(v) for v in rng.choice(K, 2, replace=False))
+        if screen and j == 0:                     # (the screening case keeps its 16-point first motif)
+            i, j = j, i
+        if Ns[i] <= 1024:
+            motifs[j], Ns[j], twins = motifs[i].copy(), Ns[i], (min(i, j), max(i, j))
+    order = np.arange(K) if screen else rng.permutation(K)       # groups interleaved in motif order
+    motifs, Ns = [motifs[int(i)] for i in order], [Ns[int(i)] for i in order]
+    if twins:
+        inv = np.argsort(order)
+        twins = tuple(sorted(int(inv[t]) for t in twins))
+    N0 = Ns[0]
+    route = "batch" if screen else _pick(rng, ("batch", "batch", "f64", "list"))
+    scale = _pick(rng, ("medmad", "medmad", "zscale"))
+    # ---- a tie between `left` and `diag` that moves `start`: a motif that begins with z points of exactly 0.0, and (below)
+    # a three-level read with a run of more than z samples at its median -- medmad makes them exactly 0.0, so the first z
+    # rows cost nothing along the run, every cell there ties, and the tie order decides where the hit starts
+    plateau = None
+    if not screen and scale == "medmad" and rng.random() < 0.5:
+        free = [k for k in range(K) if not twins or k not in twins]
+        if free:
+            z = int(_pick(rng, (2, 3, 5)))
+            plateau = (int(_pick(rng, free)), z)
+            motifs[plateau[0]] = np.array([0.0] * z + [1.0 / 1.4826] * 2)
+            Ns[plateau[0]] = z + 2
+            N0 = Ns[0]
+    # ---- the region
+    E = int(_pick(rng, (700, 760))) if screen else int(_pick(rng, (120, 300, 700, 2000)))
+    a, c = int(_pick(rng, (5, 100, 333))), int(_pick(rng, (1, 50)))
+    kind = _pick(rng, ("head", "tail")) if screen else _pick(rng, ("head", "tail", "mid", "negend", "win", "win", "rare"))
+    if kind == "rare":
+        kind = _pick(rng, ("empty", "beyond"))
+    # ---- window sizes: the listed ones around the first motif's N and L, then random
+    sumN = sum(Ns)
+    room = max(1, PANEL_CELLS // max(1, sumN) - (121 if plateau else 0))     # window samples the reference can afford
+    L0 = (panel_shape(N0, 10 ** 9 if batchlay else 1, env) or (64, 16))[0]
+    if screen:
+        wins = [int(rng.integers(640, E + 1)) for _ in range(256 + int(rng.integers(0, 9)))]
+        wins[:3] = [0, 9, 40]
+    else:
+        wins = [w for w in (0, 7, 8, 9, N0 - 1, N0, N0 + 1, L0 - 1, L0, L0 + 1, 2 * L0 + 1) if 0 <= w <= E]
+        if rng.random() < 0.4:
+            wins.append(1)                        # (one sample: MAD 0, only its flag is compared)
+        wins = list(dict.fromkeys(wins))
+        cap = max(12, 2048 // K if not batchlay else 400)
+        more = int(_pick(rng, (8, 30, 60)))
+        for _ in range(more):
+            w = int(rng.integers(16, E + E // 2))
+            if len(wins) < cap and sum(wins) + w <= room:
+                wins.append(w)
+        while sum(wins) > room and len(wins) > 1:    # (many long motifs: the listed windows alone are too much)
+            wins.remove(max(wins))
+    if plateau:
+        wins.append(int(rng.integers(100, 121)))
+    nspecial = sum(w == 1 for w in wins)
+    # ---- the reads
+    plant = [m for m in motifs if len(m) <= 300][:3]
+    reads, kinds, rows_kind = [], [], []
+    for w in wins:
+        rk = kind if kind != "win" else _pick(rng, ("head", "tail", "mid", "negend"))
+        if rk in ("empty", "beyond"):
+            n = w + int(rng.integers(0, 200))
+        else:
+            n = _panel_len_for(rk, a, c, E, w) if w <= E else w + a + c
+        k = "squiggle" if w < 16 else _pick(rng, ("squiggle", "squiggle", "ties", "dropped"))
+        if plateau and len(reads) == len(wins) - 1:                        # the read with the run at its median
+            step = int(_pick(rng, (1, 10)))
+            x = (480 + step * rng.integers(0, 3, size=n)).astype(np.int16)
+            b, e = _panel_region(rk, a, c, E)
+            lo, hi, _ = slice(b, e).indices(n)
+            run = [480 + step] * (plateau[1] + int(rng.integers(3, 8))) + [480 + 2 * step] * 2
+            if hi - lo > len(run):                                         # (an empty region: nothing to plant in)
+                at = lo + int(rng.integers(0, hi - lo - len(run)))
+                x[at:at + len(run)] = run
+            reads.append(x)
+            kinds.append("z")
+            rows_kind.append(rk)
+            continue
+        reads.append(_hit_read(rng, n, plant, k))
+        kinds.append(k[0])
+        rows_kind.append(rk)
+    def add(read, tag):
+        reads.append(read)
+        kinds.append(tag)
+        rows_kind.append(kind if kind != "win" else "head")
+    if len(reads) >= 10 * (nspecial + 1) + 1 and rng.random() < 0.6:
+        add(np.full(a + c + int(rng.integers(40, E + 40)), 500, dtype=np.int16), "m")           # MAD 0 in any window
+        nspecial += 1
+    if rng.random() < 0.5:
+        add(np.full(a + c + int(rng.integers(2, 300)), 2000, dtype=np.int16), "e")              # nothing inside the limits
+    while len(reads) <= 10 * nspecial:            # (the reads whose distance is not compared stay under a tenth)
+        w = int(rng.integers(16, 40))
+        add(_hit_read(rng, w + (a + c if kind in ("mid", "negend") else 0), plant, "squiggle"), "s")
+    order = rng.permutation(len(reads))
+    reads, rows_kind = [reads[int(i)] for i in order], [rows_kind[int(i)] for i in order]
+    kinds = "".join(kinds[int(i)] for i in order)
+    R = len(reads)
+    win = None
+    region = _panel_region(kind, a, c, E) if kind != "win" else (0, None)
+    if kind == "win":
+        win = np.zeros((R, 2), dtype=np.int32)
+        for r in range(R):
+            b, e = _panel_region(rows_kind[r], a, c, E)
+            win[r] = (b, INT32_MAX if e is None else e)
+            if rows_kind[r] == "negend" and len(reads[r]) < a + c:       # (begin behind end, one side cut: refused)
+                win[r] = (0, E)
+        win[int(rng.integers(R))] = (10 ** 6, -10 ** 6)                   # both ends cut to the read: an empty window
+    # ---- the routes
+    nfloat = 0
+    if route in ("f64", "list"):
+        dig, ofs, rg = _pick(rng, ((8192.0, 16.0, 1493.94), (2048.0, -3.0, 748.58), (8192.0, 7.25, 1467.61)))
+        for r in range(R):
+            if route == "f64" or (rng.random() < 0.5 and len(reads[r])):
+                x = np.round((reads[r].astype(np.int64) + ofs) * (rg / dig), 2)
+                if kinds[r] == "e":
+                    x[:] = 1500.25
+                if x.size:
+                    x[0] += 0.005                                         # (never integer-valued as a whole)
+                reads[r] = x
+                nfloat += 1
+    longest = max(len(r) for r in reads)
+    case = dict(family="panel", route=route, scale=scale, K=K, Ns=Ns, twins=twins, plateau=plateau, kind=kind, region=region, E=E,
+                screen=screen, motifs=motifs, reads=reads, nreads=R, nfloat=nfloat, nspecial=nspecial, longest=longest,
+                kinds=kinds, win=win, env=env)
+    if route == "batch":
+        stride = (longest + 8 + int(rng.integers(0, 64))) // 8 * 8       # stride > the longest row
+        sig = rng.integers(300, 700, size=(R, stride)).astype(np.int16)  # (padding is not zeros)
+        for i, r in enumerate(reads):
+            sig[i, :len(r)] = r
+        case["sig"], case["lens"], case["stride"] = sig, np.array([len(r) for r in reads], dtype=np.int32), stride
+    return case
+
+
+def expect_panel(ora, case):
+    from test_panel_host import model_terms, reference_panel
+    mean, sd = model_terms(case["motifs"])
+    ref = reference_panel(ora, case["reads"], case["motifs"], case["region"], case["win"], case["scale"])
+    return dict(ref=ref, means=mean, sds=sd)
+
+
+def call_panel(api, case, exp):
+    kw = dict(region=case["region"], win=case["win"], scale=case["scale"], records=True)
+    if case["route"] == "batch":
+        return api.motifseq_panel_batch(case["sig"], case["lens"], case["motifs"], exp["means"], exp["sds"], **kw)
+    if case["route"] == "f64":
+        return api.motifseq_panel_ragged_f64(*api.pack_f64(case["reads"]), case["motifs"], exp["means"], exp["sds"], **kw)
+    return api.motifseq_panel(case["reads"], case["motifs"], exp["means"], exp["sds"], **kw)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def diff_panel(case, got, exp):
+    """What test_gpu_panel.same asserts, as text with the first differing (motif, read)."""
+    panel, frm, allrec = got
+    recs, flags, rfrm, best, second, sb, ss = exp["ref"]
+
+    def first(bad):
+        return int(np.flatnonzero(bad)[0])
+    if not np.array_equal(frm, rfrm):
+        r = first(frm != rfrm)
+        return "read %d (%d samples): window from %d, want %d" % (r, len(case["reads"][r]), frm[r], rfrm[r])
+    cmp = flags != 2
+    for k, g in enumerate(allrec):
+        w = recs[k]
+        bad = (g["n"] != w["n"]) | ((g["flags"] & 3) != flags) | \
+              (cmp & ((_bits(g["dist"]) != _bits(w["dist"])) | (g["start"] != w["start"]) | (g["end"] != w["end"])))
+        if bad.any():
+            r = first(bad)
+            return "motif %d (N=%d, shape %s) read %d (%d samples, window %s): got %s want %s flags %d" % (
+                k, len(case["motifs"][k]), panel_shape(len(case["motifs"][k]), case["nreads"] * case["K"], case["env"]), r,
+                len(case["reads"][r]), panel_windows(case)[r], g[r], w[r], flags[r])
+    bad = (panel["best"] != best) | (panel["second"] != second) | (_bits(panel["score_best"]) != _bits(sb)) | \
+          (_bits(panel["score_second"]) != _bits(ss))
+    if bad.any():
+        r = first(bad)
+        return "read %d: ranked (%d, %d) scores (%r, %r), want (%d, %d) (%r, %r)" % (
+            r, panel["best"][r], panel["second"][r], float(panel["score_best"][r]), float(panel["score_second"][r]),
+            best[r], second[r], float(sb[r]), float(ss[r]))
+    for r in range(len(frm)):
+        h = panel["hit"][r]
+        if best[r] >= 0:
+            if h.tobytes() != allrec[best[r]][r].tobytes():
+                return "read %d: the panel's hit is not the best motif's record" % r
+        elif not (np.isnan(h["dist"]) and h["start"] == -1 and h["end"] == -1 and h["n"] == recs[0]["n"][r]
+                  and h["flags"] & 3 == flags[r]):
+            return "read %d: unranked, but its hit is %s" % (r, h)
+    return None
+
+
+# ======================================================================================================================
+# event detection
+# ======================================================================================================================
+# sk_detect.hip: k_detect_mark takes 64 reads a workgroup and gathers marks in 64-sample words; k_detect_fill walks a
+# read in rounds of 4 096 samples, a lane per word; rows are loaded with 16-byte loads where the stride allows it.
+DET_WORD = 64
+DET_ROUND = 4096
+DET_COUNTS = (1, 63, 64, 65, 130)
+DET_LENS = (0, 1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 4095, 4096, 4097)
+DET_LONG = 8192
+DET_SAMPLES = 600_000                            # samples per case (the numpy reference: about 2 us each)
+DET_PRESETS = {"dna": (3, 6, 1.4, 9.0, 0.2), "rna": (7, 14, 2.5, 9.0, 1.0)}
+
+
+def _det_read(rng, n):
+    """tools/fuzz_gpu.py's reads: levels with noise, anything an int16 holds, flat or two values."""
+    kind = rng.random()
+    if kind < 0.6:
+        lv = np.repeat(rng.normal(500, 80, n // 3 + 1), rng.integers(1, 20, n // 3 + 1))[:n]
+        x = lv + rng.normal(0, float(rng.choice([0, 2, 8, 30])), lv.size)
+    elif kind < 0.8:
+        x = rng.integers(-32768, 32768, n).astype(np.float64)
+    else:
+        x = np.where(rng.random(n) < float(rng.choice([0.0, 0.5])), 32767.0, float(rng.integers(-32768, 32767)))
+    return np.clip(np.rint(x), -32768, 32767).astype(np.int16), "lrf"[0 if kind < 0.6 else 1 if kind < 0.8 else 2]
+
+
+def _ragged_lens(rng, R, seams, dmax, budget):
+    lens = [int(_pick(rng, seams)) if rng.random() < 0.5 else int(rng.integers(0, dmax + 1)) for _ in range(R)]
+    total = 0
+    for i, n in enumerate(lens):                 # (the reference's CPU time)
+        if total + n > budget:
+            lens[i] = n = int(rng.integers(0, 70))
+        total += n
+    return lens
+
+
+def _i16_rows(rng, reads, aligned, pad=-7):
+    """(rows [R, stride], lens int32, stride): stride a multiple of 8 or not, padding not zeros."""
+    longest = max([len(r) for r in reads] + [1])
+    stride = (longest + 7 + 8 * int(rng.integers(0, 2))) // 8 * 8 if aligned else (longest + int(rng.integers(0, 9))) | 1
+    buf = np.full((len(reads), stride), pad, dtype=np.int16)
+    for r, x in enumerate(reads):
+        buf[r, :len(x)] = x
+    return buf, np.array([len(x) for x in reads], dtype=np.int32), stride
+
+
+def draw_detect(rng):
+    R = int(_pick(rng, DET_COUNTS))
+    u = rng.random()
+    if u < 0.25:
+        params, pk = DET_PRESETS["dna"], "dna"
+    elif u < 0.4:
+        params, pk = DET_PRESETS["rna"], "rna"
+    else:
+        v = rng.random()
+        ws = 1 if v < 0.2 else int(rng.integers(1, 65))
+        wl = 64 if v < 0.35 else ws if v < 0.5 else int(rng.integers(ws, 65))
+        params = (ws, wl, float(_pick(rng, (0.0, 1.4, 2.5, 20.0))), float(_pick(rng, (0.0, 4.0, 9.0))),
+                  float(_pick(rng, (0.0, 0.2, 1.0, 5.0))))
+        pk = "drawn"
+    ws, wl = params[0], params[1]
+    seams = DET_LENS + (2 * ws - 1, 2 * ws, 2 * ws + 1, 2 * wl - 1, 2 * wl, 2 * wl + 1)
+    dmax = int(_pick(rng, (8, 70, 130, 300, 1500, 5000)))
+    lens = _ragged_lens(rng, R, seams, dmax, DET_SAMPLES - 3 * DET_ROUND - 2 * DET_LONG)
+    reads, kinds = [], ""
+    for n in lens:
+        x, k = _det_read(rng, n)
+        reads.append(x)
+        kinds += k
+    long_read = flat_round = False
+    if rng.random() < 0.5:                        # one read above DET_LONG samples
+        at = int(rng.integers(R))
+        reads[at], _ = _det_read(rng, int(rng.integers(DET_LONG + 1, DET_LONG + 3000)))
+        long_read = True
+    if rng.random() < 0.5:                        # a whole round of k_detect_fill without a mark, events on both sides
+        at = int(rng.integers(R))
+        n = 3 * DET_ROUND + int(rng.integers(0, 500))
+        lv = np.repeat(rng.normal(500, 80, n // 3 + 1), rng.integers(3, 20, n // 3 + 1))[:n] + rng.normal(0, 2, n)
+        lv[DET_ROUND - 130:2 * DET_ROUND + 130] = float(rng.integers(300, 700))
+        reads[at] = np.rint(lv).astype(np.int16)
+        kinds = kinds[:at] + "p" + kinds[at + 1:]
+        flat_round = True
+    aligned = bool(rng.random() < 0.5)
+    buf, lens, stride = _i16_rows(rng, reads, aligned)
+    return dict(family="detect", R=R, params=params, preset=pk, dmax=dmax, stride=stride, aligned=aligned,
+                long_read=long_read, flat_round=flat_round, total=int(lens.sum()), kinds=kinds, sig=buf, lens=lens,
+                reads=reads, env={})
+
+
+def expect_detect(ora, case):
+    import detect_ref
+    off, rec = detect_ref.detect(case["reads"], case["params"])
+    return dict(off=off, rec=rec)
+
+
+def call_detect(api, case, exp=None):
+    p = case["params"]
+    return api.detect_events_batch(case["sig"], case["lens"], api.det_params(
+        w_short=p[0], w_long=p[1], th_short=p[2], th_long=p[3], peak_height=p[4]))
+
+
+def diff_detect(case, got, exp):
+    off, rec = got
+    if off.shape != exp["off"].shape:
+        return "offsets shaped %s, want %s" % (off.shape, exp["off"].shape)
+    if not np.array_equal(off, exp["off"]):
+        r = int(np.flatnonzero(np.diff(off) != np.diff(exp["off"]))[0])
+        return "read %d (%d samples): %d events, want %d" % (r, case["lens"][r], off[r + 1] - off[r],
+                                                              exp["off"][r + 1] - exp["off"][r])
+    if rec.tobytes() != exp["rec"].tobytes():
+        q = int(np.flatnonzero(rec != exp["rec"])[0])
+        r = int(np.searchsorted(off, q, side="right") - 1)
+        return "read %d (%d samples) event %d: got %s want %s" % (r, case["lens"][r], q - off[r], rec[q], exp["rec"][q])
+    return None
+
+
+# ======================================================================================================================
+# signal HMM: the record call and the segments call on the same case
+# ======================================================================================================================
+# sk_hmm.hip: 64 reads a wavefront; the segments call keeps back pointers, 256 bytes a sample and group of 64 reads, in
+# slices of SK_HMM_SCRATCH_MB (1 MiB: a single group per slice once a read has more than 2 048 samples).
+HMM_COUNTS = (1, 63, 64, 65, 130, 200)
+HMM_LENS = (0, 1, 2, 31, 32, 33, 127, 128, 129, 255)
+HMM_LIMITS = (0, 0, 1, 33, 129, 100000)
+HMM_SAMPLES = 600_000
+
+
+def hmm_slices(case):
+    """Slices sk_launch_hmm_paths makes of the case's reads (per C call; the list form's larger call)."""
+    budget = (int(case["env"]["SK_HMM_SCRATCH_MB"]) << 20) if "SK_HMM_SCRATCH_MB" in case["env"] else 16 << 30
+    n = max([len(r) for r in case["reads"]] + [1])
+    if case["limit"] > 0:
+        n = min(n, case["limit"])
+    nreads = case["R"] if case["feed"] != "list" else max(case["nfloat"], case["R"] - case["nfloat"])
+    groups = (nreads + 63) // 64
+    g = min(max(1, budget // (max(n, 1) * 256)), groups)
+    return -(-groups // g) if groups else 0
+
+
+def draw_hmm(rng):
+    # ---- the model: tools/fuzz_gpu.py's
+    S = int(rng.integers(1, 7))
+    integer = bool(rng.random() < 0.3)
+    if integer:                                   # integer scores: ties
+        hl, ht = rng.integers(-3, 1, S).astype(np.float64), rng.integers(-2, 1, (S, S)).astype(np.float64)
+        hc = rng.integers(-2, 1, (S, 2)).astype(np.float64)
+        hmu = rng.integers(-3, 4, (S, 2)).astype(np.float64) * 100 + 500
+        hh = rng.integers(0, 2, (S, 2)).astype(np.float64)
+    else:
+        hl, ht = np.log(rng.uniform(0.01, 1, S)), np.log(rng.uniform(0.001, 1, (S, S)))
+        hc = np.log(rng.uniform(0.01, 1, (S, 2)) / rng.uniform(2, 90, (S, 2)))
+        hmu = rng.uniform(-200, 1200, (S, 2))
+        hh = np.where(rng.random((S, 2)) < 0.2, 0.0, 1.0 / (2.0 * rng.uniform(2, 90, (S, 2)) ** 2))
+    hl[rng.random(S) < 0.3] = -np.inf
+    if not np.isfinite(hl).any():
+        hl[int(rng.integers(S))] = 0.0
+    ht[rng.random((S, S)) < 0.4] = -np.inf
+    hc[rng.random(S) < 0.5, 1] = -np.inf
+    model = dict(nstates=S, linit=hl, ltrans=ht, c=hc, mu=hmu, h=hh)
+    # ---- the reads
+    env = {}
+    R = int(_pick(rng, HMM_COUNTS))
+    dmax = int(_pick(rng, (70, 300, 1500, 5000)))
+    if rng.random() < 0.35:
+        env["SK_HMM_SCRATCH_MB"] = "1"
+    if rng.random() < 0.3:
+        env["SK_INGEST_MB"] = "1"
+    lens = _ragged_lens(rng, R, HMM_LENS, dmax, HMM_SAMPLES - 3000)
+    limit = int(_pick(rng, HMM_LIMITS))
+    if "SK_HMM_SCRATCH_MB" in env and R >= 130 and rng.random() < 0.7:
+        lens[int(rng.integers(R))] = int(rng.integers(2100, 3000))        # 1 MiB then holds one group of 64 reads: a slice each
+        limit = int(_pick(rng, (0, 100000)))
+    reads = [_det_read(rng, n)[0] for n in lens]
+    feed = _pick(rng, ("batch", "batch", "f64", "list"))
+    cal, nfloat, aligned = None, 0, None
+    case = dict(family="hmm", R=R, S=S, integer=integer, feed=feed, limit=limit, dmax=dmax)
+    if feed == "batch":
+        aligned = bool(rng.random() < 0.5)
+        case["sig"], case["lens"], case["stride"] = _i16_rows(rng, reads, aligned)
+        if rng.random() < 0.5:
+            cal = np.stack([rng.uniform(-50, 50, R), rng.uniform(0.1, 0.3, R)], axis=1)
+    else:
+        for r in range(R):
+            if len(reads[r]) and (feed == "f64" or rng.random() < 0.5):
+                reads[r] = reads[r].astype(np.float64) * float(_pick(rng, (1.0, 0.25, 0.1))) + 0.37    # not integers
+                nfloat += 1
+    case.update(aligned=aligned, calibrated=cal is not None, nfloat=nfloat, total=int(sum(len(r) for r in reads)),
+                model=model, cal=cal, reads=reads, env=env)
+    return case
+
+
+def hmm_model_of(api, case):
+    m = case["model"]
+    return api.HmmModel.from_arrays(m["nstates"], m["linit"], m["ltrans"], m["c"], m["mu"], m["h"])
+
+
+def expect_hmm(ora, case):
+    """rec: the records; parts: [(read indices, rec, off, seg)] per C call of the segments call."""
+    import hmm_path_ref
+    import hmm_ref
+    model, limit, reads = case["model"], case["limit"], case["reads"]        # (the references take the plain arrays)
+    if case["feed"] == "batch":
+        rec = hmm_ref.viterbi_batch(model, case["sig"], case["lens"], case["cal"], limit)
+        return dict(rec=rec, parts=[(list(range(case["R"])),) +
+                                    hmm_path_ref.segments_batch(model, case["sig"], case["lens"], case["cal"], limit)])
+    rec = hmm_ref.viterbi_reads(model, reads, limit)
+    ints = [i for i, r in enumerate(reads) if _is_int_read(r)] if case["feed"] == "list" else []
+    flts = [i for i in range(len(reads)) if i not in set(ints)]
+    parts = []
+    if ints:
+        parts.append((ints,) + hmm_path_ref.segments_reads(model, [reads[i] for i in ints], limit, raw=True))
+    if flts:
+        parts.append((flts,) + hmm_path_ref.segments_reads(model, [reads[i] for i in flts], limit))
+    return dict(rec=rec, parts=parts)
+
+
+def call_hmm(api, case, exp=None):
+    """(records of the record call, records of the segments call, [segments of read r])"""
+    model, limit, reads = hmm_model_of(api, case), case["limit"], case["reads"]
+    if case["feed"] == "batch":
+        rec = api.hmm_viterbi_batch(case["sig"], case["lens"], model, case["cal"], limit)
+        prec, off, seg = api.hmm_segments_batch(case["sig"], case["lens"], model, case["cal"], limit)
+    elif case["feed"] == "f64":
+        rec = api.hmm_viterbi_ragged_f64(*api.pack_f64(reads), model, limit)
+        prec, off, seg = api.hmm_segments_ragged_f64(*api.pack_f64(reads), model, limit)
+    else:
+        rec = api.hmm_viterbi(reads, model, limit)
+        prec, segs = api.hmm_segments(reads, model, limit)
+        return rec, prec, segs
+    return rec, prec, [seg[int(off[r]):int(off[r + 1])] for r in range(len(reads))]
+
+
+def diff_hmm(case, got, exp):
+    return diff_hmm_records(case, got, exp) or diff_hmm_paths(case, got, exp)
+
+
+def diff_hmm_records(case, got, exp):
+    """the record call against hmm_ref"""
+    rec = got[0]
+    if rec.tobytes() != exp["rec"].tobytes():
+        r = int(np.flatnonzero(rec != exp["rec"])[0])
+        return "record of read %d (%d samples): got %s want %s" % (r, len(case["reads"][r]), rec[r], exp["rec"][r])
+    return None
+
+
+def diff_hmm_paths(case, got, exp):
+    """the segments call against hmm_path_ref, its records against the record call's"""
+    rec, prec, segs = got
+    if prec.tobytes() != rec.tobytes():
+        r = int(np.flatnonzero(prec != rec)[0])
+        return "read %d: the segments call's record %s is not the record call's %s" % (r, prec[r], rec[r])
+    for idx, wrec, woff, wseg in exp["parts"]:
+        for k, r in enumerate(idx):
+            want = wseg[int(woff[k]):int(woff[k + 1])]
+            g = segs[r]
+            if g.dtype["sum"] == want.dtype["sum"] and g.tobytes() == want.tobytes():
+                continue
+            n = min(len(g), len(want))
+            bad = np.flatnonzero(np.frombuffer(g[:n].tobytes(), dtype=np.uint8).reshape(n, -1) !=
+                                 np.frombuffer(want[:n].tobytes(), dtype=np.uint8).reshape(n, -1)) if n and \
+                g.dtype.itemsize == want.dtype.itemsize else np.zeros(0, dtype=np.int64)
+            q = int(bad[0]) // g.dtype.itemsize if bad.size else n
+            return "read %d (%d samples): %d segments (sums %s), want %d (%s); segment %d: got %s want %s" % (
+                r, len(case["reads"][r]), len(g), g.dtype["sum"].base, len(want), want.dtype["sum"].base, q,
+                g[q] if q < len(g) else None, want[q] if q < len(want) else None)
+    return None
+
+
+# ======================================================================================================================
+# segment levels
+# ======================================================================================================================
+# sk_seglev.hip: the kept mask in entries of 64 raw samples; k_seglev_stats stages a work item (a segment, or the whole
+# read) of up to SEGLEV_LDS_COLS samples in LDS and takes the scratch tier beyond.
+SEGLEV_LDS_COLS = 4096
+LEVELS_LENS = (0, 1, 63, 64, 65, 127, 128, 129, SEGLEV_LDS_COLS - 1, SEGLEV_LDS_COLS, SEGLEV_LDS_COLS + 1)
+LEVELS_ROUTES = ("batch", "batch_pa", "ragged", "list")
+LEVELS_MAX_SEGS = (1, 2, 64)
+LEVELS_LIMITS = ((0, 900), (0, 900), (-50, 1200), (-50, 1200), (200, 2500))
+
+
+def draw_levels(rng):
+    from squigglekit_amd import synth
+    route = _pick(rng, LEVELS_ROUTES)
+    lo, hi = _pick(rng, LEVELS_LIMITS)
+    seg = dict(error=_pick(rng, (5, 5, 3, 0, 10)), corrector=_pick(rng, (50, 50, 3, 20)),
+               window=_pick(rng, (150, 100, 20, 126, 127, 400)), seg_dist=_pick(rng, (50, 0, 1, 10 ** 9)),
+               std_scale=_pick(rng, SWEEP_STD[:6]), stall_len=_pick(rng, (0.25, 0.05, 0.9, 1.2)), lim_low=lo, lim_hi=hi)
+    base = 20.0 if lo < 0 and rng.random() < 0.7 else 500.0               # lim_low < 0: kept samples of both signs
+    spread = float(_pick(rng, (60.0, 60.0, 20.0, 3.0)))                   # 3: a handful of distinct values, ties
+    if base == 20.0:
+        spread = min(spread, 20.0)
+    reads = []
+    for n in rng.choice(LEVELS_LENS, size=5, replace=False):
+        reads.append(_stall_read(rng, int(n), base, spread))
+    for _ in range(int(_pick(rng, (3, 9, 20)))):
+        reads.append(_stall_read(rng, int(rng.integers(400, 4000)), base, spread))
+    if base == 500.0:
+        M = int(_pick(rng, (512, 2047, 4000)))
+        reads += [r.astype(np.float64) for r in synth.pattern_reads(rng, int(_pick(rng, (2, 5))), M)]
+    # one read above SEGLEV_LDS_COLS samples with a quiet stretch longer than that (a segment for the scratch tier)
+    n = int(rng.integers(2 * SEGLEV_LDS_COLS + 500, 3 * SEGLEV_LDS_COLS))
+    x = rng.normal(base, spread, n)
+    a = int(rng.integers(100, 400))
+    x[a:a + SEGLEV_LDS_COLS + int(rng.integers(50, 400))] = rng.normal(base + spread / 10, spread / 8, 1)[0]
+    x += rng.normal(0, spread / 20, n)
+    reads.append(x)
+    for i in range(len(reads)):                                           # many dropped samples in some reads
+        n = len(reads[i])
+        if n >= 64 and rng.random() < 0.4:
+            k = max(1, n // int(_pick(rng, (5, 20, 60))))
+            reads[i][rng.integers(0, n, k)] = rng.choice([-500, 3000, 2999, hi, lo], k)
+    reads = [np.clip(np.rint(r), -32768, 32767).astype(np.int16) for r in reads]
+    order = rng.permutation(len(reads))
+    reads = [reads[int(i)] for i in order]
+    R = len(reads)
+    case = dict(family="levels", route=route, seg=seg, lo=lo, hi=hi, base=base, spread=spread, R=R,
+                longest=max(len(r) for r in reads))
+    if route != "list":                           # (api.segment_levels takes no max_segs: the list form starts at 64)
+        case["max_segs"] = int(_pick(rng, LEVELS_MAX_SEGS))
+    if route in ("batch", "batch_pa"):
+        case["sig"], case["lens"], case["stride"] = _i16_rows(rng, reads, True, pad=int(base))
+    if route == "batch_pa":
+        cal = np.empty((R, 3))
+        cal[:, 0] = rng.choice([8192.0, 2048.0], R)
+        cal[:, 1] = np.round(rng.uniform(-40, 40, R), 1)
+        cal[:, 2] = rng.uniform(600, 1600, R)
+        if base == 20.0:
+            cal[:, 1] = np.round(rng.uniform(-4, 4, R), 1)
+            cal[:, 2] = cal[:, 0] * rng.uniform(0.8, 1.2, R)              # unit about 1: both signs stay
+        case["calib"] = cal
+        reads = [np.round((r.astype(np.int64) + cal[i, 1]) * (float("{0:.2f}".format(cal[i, 2])) / cal[i, 0]), 2)
+                 for i, r in enumerate(reads)]                            # (segmenter.py's pA values: the reference's input)
+        if base == 500.0:
+            case["lo"], case["hi"] = lo, hi = (0, 900) if lo >= 0 else (-10, 250)
+            seg.update(lim_low=lo, lim_hi=hi)
+    elif route == "ragged":
+        reads = [np.round(r * 0.25 + 0.01 * rng.integers(0, 3, len(r)), 2) for r in reads]    # a 0.01 grid: ties
+        case["lo"], case["hi"] = lo, hi = (lo // 4, hi // 4)
+        seg.update(lim_low=lo, lim_hi=hi)
+    elif route == "list":
+        for i in range(R):
+            if len(reads[i]) and rng.random() < 0.5:
+                reads[i] = reads[i].astype(np.float64) + 0.5
+    case.update(nfloat=sum(r.dtype == np.float64 for r in reads), reads=reads, env={})
+    return case
+
+
+def _no_levels(shape, dtype):
+    """records of slots that hold no span: six NaNs, raw_start = raw_end = -1, n = 0"""
+    a = np.zeros(shape, dtype=dtype)
+    for f in ("mean", "std", "median", "mad", "min", "max"):
+        a[f] = np.nan
+    a["raw_start"] = a["raw_end"] = -1
+    return a
+
+
+def levels_expected(dtype, reads, segs, shape, lo, hi):
+    """(levels [shape], read_level [R]) of the record type `dtype` as plain numpy makes them on the given segments
+    (segs[r]: [[s, e], ..] in filtered coordinates): every record over w = y[s:e], y = the kept samples of the read --
+    int64 for an integer read."""
+    want_l, want_r = _no_levels(shape, dtype), _no_levels(len(reads), dtype)
+
+    def one(w, kept, s):
+        m = np.median(w)
+        return (np.mean(w), np.std(w), m, np.median(np.abs(w - m)), w.min(), w.max(), kept[s], kept[s + len(w) - 1] + 1, len(w), 0)
+    for r, a in enumerate(reads):
+        a = np.asarray(a)
+        if a.dtype.kind in "iu":
+            a = a.astype(np.int64)
+        kept = np.flatnonzero((a > lo) & (a < hi))
+        y = a[kept]
+        if y.size:
+            want_r[r] = one(y, kept, 0)
+        for k in range(min(len(segs[r]), shape[1])):
+            s, e = segs[r][k]
+            if len(y[s:e]):
+                want_l[r, k] = one(y[s:e], kept, s)
+    return want_l, want_r
+
+
+def levels_mismatch(levels, read_level, want_l, want_r):
+    """None, or where the records differ (doubles by bit pattern)"""
+    for got, want, what in ((levels, want_l, "levels"), (read_level, want_r, "read_level")):
+        for f in got.dtype.names:
+            g, w = np.ascontiguousarray(got[f]), np.ascontiguousarray(want[f])
+            if g.dtype.kind == "f":
+                g, w = g.view(np.uint64), w.view(np.uint64)
+            d = np.argwhere(g != w)
+            if d.size:
+                return "%s.%s at %s: got %r want %r" % (what, f, d[0].tolist(), got[f][tuple(d[0])], want[f][tuple(d[0])])
+    return None
+
+
+def expect_levels(ora, case):
+    """segs[r]: the oracle's segments of read r (all of them: the call grows max_segs until none is cut)."""
+    s = case["seg"]
+    p = ora.SegParams(s["error"], s["corrector"], s["window"], s["seg_dist"], s["std_scale"], s["stall_len"])
+    segs = []
+    for r in case["reads"]:
+        f = ora.scale_outliers(np.asarray(r, dtype=np.float64), case["lo"], case["hi"])
+        segs.append([list(x) for x in ((ora.get_segs(f, p, max_segs=f.size // 2 + 8) or []) if f.size else [])])
+    return dict(segs=segs)
+
+
+def call_levels(api, case, exp=None):
+    from squigglekit_amd._lib import SegParams
+    p = SegParams(**case["seg"])
+    if case["route"] == "batch":
+        return api.segment_levels_batch(case["sig"], case["lens"], p, max_segs=case["max_segs"])
+    if case["route"] == "batch_pa":
+        return api.segment_levels_batch_pa(case["sig"], case["lens"], case["calib"], p, max_segs=case["max_segs"])
+    if case["route"] == "ragged":
+        return api.segment_levels_ragged_f64(*api.pack_f64(case["reads"]), None, p, max_segs=case["max_segs"])
+    return api.segment_levels(case["reads"], p)
+
+
+def diff_levels(case, got, exp):
+    segs, nsegs, levels, read_level = got
+    for r, want in enumerate(exp["segs"]):
+        if int(nsegs[r]) != len(want) or segs[r, :nsegs[r]].tolist() != want:
+            return "read %d (%d samples): segments %s, want %s" % (r, len(case["reads"][r]), segs[r, :nsegs[r]].tolist()[:3],
+                                                                    want[:3])
+    want_l, want_r = levels_expected(levels.dtype, case["reads"], exp["segs"], levels.shape, case["lo"], case["hi"])
+    return levels_mismatch(levels, read_level, want_l, want_r)
+
+
+# ======================================================================================================================
+# the twins of the hit family: the read background on the hits cases, events and pooling on the paths cases
+# ======================================================================================================================
+def twin_case(family, case, use_seed=None):
+    """A hits / paths case as its twin's: the same reads, motifs, K, scaling and switches (max_dist is inf, the reads go in
+    as the list); `use_seed` seeds the pooling mask of the events twin."""
+    return dict(case, family=family, of=case["family"], use_seed=int(case["seed"] if use_seed is None else use_seed))
+
+
+def _twin_args(case):
+    return (case["motifs"], case["K"], float("inf"), case["scale"], case["lo"], case["hi"])
+
+
+def events_use(case, m, n):
+    return np.random.default_rng([98, case["use_seed"], m]).random(n) < 0.7
+
+
+def expect_background(ora, case):
+    from test_background_host import reference_background_reads
+    return dict(want=[reference_background_reads(ora, case["reads"], m, case["scale"], case["lo"], case["hi"])
+                      for m in case["motifs"]])
+
+
+def call_background(api, case, exp=None):
+    return api.motifseq_background(case["reads"], *_twin_args(case)), api.motifseq_hits(case["reads"], *_twin_args(case))
+
+
+def diff_background(case, got, exp):
+    got, twin = got
+    for m, want in enumerate(exp["want"]):
+        if got[m][0].tobytes() != twin[m][0].tobytes() or not np.array_equal(got[m][1], twin[m][1]):
+            return "motif %d: hit lists differ from the hit-list call's" % m
+        for r, w in enumerate(want):
+            g = got[m][2][r]
+            if w is None:
+                ok = g["below"] == -1 and all(np.isnan(g[f]) for f in ("mean", "std", "median", "mad"))
+            else:
+                ok = (int(g["below"]), int(g["n"])) == w[4:] and all(
+                    np.float64(g[f]).tobytes() == np.float64(v).tobytes()
+                    for f, v in zip(("mean", "std", "median", "mad"), w))
+            if not ok:
+                return "motif %d read %d (%d samples): got %s want %s" % (m, r, len(case["reads"][r]), g, w)
+    return None
+
+
+def expect_events(ora, case):
+    from test_events_host import reference_batch, reference_pool
+    want = [reference_batch(ora, case["reads"], m, case["K"], case["scale"], case["lo"], case["hi"])[1]
+            for m in case["motifs"]]
+    use = [events_use(case, m, w.shape[0] * w.shape[1]) for m, w in enumerate(want)]
+    return dict(want=want, use=use, pool=[reference_pool(w, u) for w, u in zip(want, use)])
+
+
+def call_events(api, case, exp):
+    got = api.motifseq_events(case["reads"], *_twin_args(case))
+    bad = api.last_path_mismatches()
+    twin = api.motifseq_hits(case["reads"], *_twin_args(case))
+    pools = [api.pool_events(got[m][2], exp["use"][m]) if got[m][2].shape == exp["want"][m].shape else None
+             for m in range(len(case["motifs"]))]
+    return got, twin, bad, pools
+
+
+def diff_events(case, got, exp):
+    got, twin, bad, pools = got
+    for m, want in enumerate(exp["want"]):
+        if got[m][0].tobytes() != twin[m][0].tobytes() or not np.array_equal(got[m][1], twin[m][1]):
+            return "motif %d: hit lists differ from the hit-list call's" % m
+        if bad != 0:
+            return "%d hits failed the path kernel's self-check" % bad
+        if got[m][2].shape != want.shape:
+            return "motif %d: events shaped %s, want %s" % (m, got[m][2].shape, want.shape)
+        if got[m][2].tobytes() != want.tobytes():
+            r, k, i = (int(v[0]) for v in np.nonzero(got[m][2] != want))
+            return "motif %d read %d hit %d point %d: got %s want %s" % (m, r, k, i, got[m][2][r, k, i], want[r, k, i])
+        if any(pools[m][f].tobytes() != exp["pool"][m][f].tobytes() for f in exp["pool"][m].dtype.names):
+            return "motif %d: the pooled model differs from numpy's" % m
+    return None
+
+
+# ======================================================================================================================
 # the older single-set calls, for the interleaved sequence only
 # ======================================================================================================================
 def draw_plain(rng, kind):
@@ -711,16 +1571,23 @@ def result_bytes(got):
         return got.tobytes()
     if got is None:
         return b""
+    if isinstance(got, (int, np.integer)):
+        return b"%d" % int(got)
     return b"|".join(result_bytes(g) for g in got)
 
 
-DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull)
+DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull, panel=draw_panel, detect=draw_detect,
+            hmm=draw_hmm, levels=draw_levels)
 EXPECT = dict(sweep=expect_sweep, hits=expect_hits, paths=expect_paths, pull=expect_pull, segment=expect_plain,
-              motifseq=expect_plain, pa=expect_plain)
+              motifseq=expect_plain, pa=expect_plain, panel=expect_panel, detect=expect_detect, hmm=expect_hmm,
+              levels=expect_levels, background=expect_background, events=expect_events)
 CALL = dict(sweep=call_sweep, hits=call_hits, paths=call_paths, pull=call_pull, segment=call_plain, motifseq=call_plain,
-            pa=call_plain)
+            pa=call_plain, panel=call_panel, detect=call_detect, hmm=call_hmm, levels=call_levels,
+            background=call_background, events=call_events)
 DIFF = dict(sweep=diff_sweep, hits=diff_hits, paths=diff_paths, pull=diff_pull, segment=diff_plain, motifseq=diff_plain,
-            pa=diff_plain)
+            pa=diff_plain, panel=diff_panel, detect=diff_detect, hmm=diff_hmm, levels=diff_levels,
+            background=diff_background, events=diff_events)
+TWIN_OF = dict(background="hits", events="paths")
 
 # ---- the interleaved sequence (tests/test_gpu_random.py::test_interleaved_calls_share_the_context_buffers) --------
 # (family, seed): committed cases by their seeds, the older calls by draw_plain seeds.  Filled beside SEEDS.
@@ -730,9 +1597,18 @@ INTERLEAVE = [("paths", 50), ("sweep", 97), ("pull", 0), ("hits", 1), ("paths", 
               ("pa", 2), ("hits", 214), ("sweep", 60), ("paths", 12), ("motifseq", 2)]
 
 
+# the second sequence: the newer families (panel, detect, hmm, levels) and the two twins between the older calls
+INTERLEAVE2 = [("panel", 4), ("hmm", 3), ("detect", 4), ("background", 1), ("sweep", 97), ("levels", 13), ("panel", 29),
+               ("events", 50), ("hmm", 35), ("pull", 0), ("detect", 27), ("panel", 4), ("hits", 1), ("levels", 22),
+               ("hmm", 3), ("paths", 12), ("detect", 6), ("background", 324), ("panel", 36), ("segment", 3), ("levels", 13),
+               ("events", 12), ("hmm", 10), ("detect", 4), ("motifseq", 2), ("panel", 93)]
+
+
 def interleave_case(family, seed):
     if family in SEEDS:
         return case_of(family, seed)
+    if family in TWIN_OF:
+        return twin_case(family, case_of(TWIN_OF[family], seed))
     case = draw_plain(np.random.default_rng([99, ["segment", "motifseq", "pa"].index(family), int(seed)]), family)
     case["seed"] = int(seed)
     return case

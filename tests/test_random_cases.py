@@ -245,6 +245,479 @@ def test_pull_cases_reach_every_alignment_and_token_length(cases):
     assert set("nthf") <= set(kinds)
 
 
+# ---- the four first families stay what they were ---------------------------------------------------------------------
+# randcases.case_digest of every committed case, computed on the commit before randcases.FAMILY_INDEX replaced
+# sorted(SEEDS).index(family) in rng_of: the mutant table and the "found by" note of RANDOM_CASES.md rest on these cases.
+PINNED = {
+    "hits": {
+        1: "27f07b8c5942dbc366da0a38d2e04789c9ceb96821d5c99491a1b788eb5f3351",
+        20: "4696bdc90ae0bb783c22db9599b8432f7e4a0e40e544740e44e8cbecf55328cb",
+        87: "a48cca924de101d5ddad9d1f3dc1983032a46c750c248bf09986a281263c5bc4",
+        95: "1c6e4e3cf70bc14d45f3f09662d5af7a16f70a5bc6e2e83ed5ef1676c2689607",
+        131: "ae3b7e275dbc5940c51a7a0a16d8c34ef5886d4165605a9f65c773443dbc121a",
+        214: "aa03c3f0e821a5082e78361067c943e1244eff365c3004b332724b8de5f870a4",
+        298: "4cfaa403c86d3c7e49616f531d3612243a4111e833c61824f730f992d6b5428c",
+        324: "f117a8271716f6ce94c278389a7db48a05f8560f9a5687f66205a1813f0e2bba",
+    },
+    "paths": {
+        1: "0eee0e337e3fddb8ee06c73806af3314d18655fd183997dfcc3414456a189df6",
+        12: "263943563af8b702342025e34f75015694e1bb9c8e9b086f7129280ba39fa309",
+        29: "a8edb800ed46b0346ac2c7606de4b1238b24e7c7eeab527b21708b0a59048c7e",
+        50: "e3d9d936b2299b420907542090b571c1bfe086e38840cef7ebfe98eb5040ec3b",
+        123: "52ba1c4839baa8c1001b0e09c29e90f93dc2069bb45d119fd2a63b7be7c52753",
+        135: "18b928e7be9147ef6bb75f585d2b931c8d07fd5a87a116a48cdc1cb4442a51cc",
+        187: "a1aa203da67274cbe51ab7e6efb44ad1c323ffb80bcf26d070165e540f5155e8",
+        272: "fdfef044c36d70963c06c5f257a7d3273c2b506dc7d916349ab00951b1a25e40",
+    },
+    "pull": {
+        0: "aecb19223df2ce52c1527757ab6749adbd909787b8715bd3444f118ade46e50f",
+        3: "c6caceb7c34d79a9859b0bc1fab888520cbbc347d1b8fa3c3c01458cdc856879",
+        21: "cd714ff5ed05cb21b73e229e34a51bca18e92169ae0e2eb42b89566800352207",
+        40: "f6562ed68411614fcd372dcc00618761de1b1eaea43038aba57fd9c566f01c34",
+    },
+    "sweep": {
+        16: "c7390b1cb6a1c3713cdccdd83891432f3ddb3e4abc0a16948c93f0874714e854",
+        22: "6d02cb7a3d88efdb1c4c5952ac7a1c64b28704b9c81ac452148d5b0b7c9d8618",
+        60: "e258e763abcad720cb1b201d10841e8a190ac6fefce6d3899fbc8e5d216f707f",
+        97: "50812934ad981e9924a89f7aefc608ceda918b0a88df58887da2d48b93e0535b",
+    },
+}
+
+
+def test_old_families_keep_their_cases():
+    assert {f: rc.FAMILY_INDEX[f] for f in PINNED} == dict(hits=0, paths=1, pull=2, sweep=3)
+    assert sorted(set(rc.FAMILY_INDEX.values())) == list(range(len(rc.FAMILY_INDEX)))
+    for fam, want in PINNED.items():
+        assert list(want) == rc.SEEDS[fam], fam
+        for seed, digest in want.items():
+            assert rc.case_digest(rc.case_of(fam, seed)) == digest, (fam, seed)
+
+
+# ---- panel -----------------------------------------------------------------------------------------------------------
+def panel_scores(exp):
+    recs, flags = exp["ref"][0], exp["ref"][1]
+    with np.errstate(all="ignore"):
+        s = (recs["dist"] - exp["means"][:, None]) / exp["sds"][:, None]
+    s[:, flags != 0] = np.nan
+    return s
+
+
+def panel_features(case, exp):
+    f = {"K=%d" % case["K"], "route=" + case["route"], "scale=" + case["scale"], case["route"] + " " + case["scale"]}
+    Ns = case["Ns"]
+    for g in rc.panel_groups(case):
+        shaped = [sh for sh in g if sh is not None]
+        for sh in shaped:
+            L, R = sh
+            f.add("L%d R=%d" % (L, R))
+            for k in g[sh]:
+                P = L * R - Ns[k]
+                if P in (0, 1, L - 1):
+                    f.add("L%d P=%s" % (L, {0: "0", 1: "1"}.get(P, "L-1")))
+                if L == 16 and R == 1 and P > 0:
+                    f.add("no-row lanes at L16")
+        apart = [sh for sh in shaped if len(g[sh]) >= 2 and g[sh][-1] - g[sh][0] >= len(g[sh])]
+        if len(shaped) >= 3 and len(apart) >= 2:
+            f.add("three groups interleaved")
+            if None in g:
+                f.add("three groups interleaved and a long motif")
+    for N in (1024, 1025):
+        if N in Ns:
+            f.add("N=%d" % N)
+    wins = rc.panel_windows(case)
+    N0 = Ns[0]
+    L0 = (rc.panel_shape(N0, rc.panel_calls(case)[0] * case["K"], case["env"]) or (64, 0))[0]
+    sizes = {w for _, w in wins}
+    for name, w in (("0", 0), ("1", 1), ("7", 7), ("8", 8), ("9", 9), ("N-1", N0 - 1), ("N", N0), ("N+1", N0 + 1),
+                    ("L-1", L0 - 1), ("L", L0), ("L+1", L0 + 1), ("2L+1", 2 * L0 + 1)):
+        if w in sizes:
+            f.add("window=" + name)
+    if case["win"] is not None:
+        f.add("win rows")
+        if any(tuple(row) == (10 ** 6, -10 ** 6) for row in case["win"].tolist()):
+            f.add("win row (1e6, -1e6)")
+        pairs = [tuple(row) for row in case["win"].tolist()]
+    else:
+        pairs = [case["region"]]
+    for a, b in pairs:
+        if a < 0:
+            f.add("negative begin")
+        if b is None or b == rc.INT32_MAX:
+            f.add("open end")
+        if b is not None and 0 <= b <= a:
+            f.add("begin >= end")
+    if any(lo >= len(r) > 0 for (lo, _), r in zip(wins, case["reads"])):
+        f.add("region beyond the read")
+    flags = exp["ref"][1]
+    if any(flags[r] == 2 and wins[r][1] >= 2 for r in range(case["nreads"])):
+        f.add("MAD 0 window")
+    if any(flags[r] == 1 and wins[r][1] >= 1 for r in range(case["nreads"])):
+        f.add("nothing inside the limits")
+    if "t" in case["kinds"]:
+        f.add("tie-heavy window")
+    if case["route"] == "batch" and case["stride"] > case["longest"] and \
+            any(np.any(case["sig"][r, n:] != 0) for r, n in enumerate(case["lens"])):
+        f.add("stride > longest row, padding not zeros")
+    if case["route"] == "list" and 0 < case["nfloat"] < case["nreads"]:
+        f.add("mixed list")
+    if rc.panel_screened(case):
+        f.add("screened")
+    s = panel_scores(exp)
+    best, second, sb, ss = exp["ref"][3:]
+    if np.any((second >= 0) & (sb == ss)):
+        f.add("tie for best")
+    with np.errstate(invalid="ignore"):
+        if np.any((second >= 0) & (ss > sb) & ((s == ss[None, :]).sum(axis=0) >= 2)):
+            f.add("tie for second")
+    return f
+
+
+def subsequence_dtw(x, y, left_first=False):
+    """(dist, start, end) of the subsequence DTW of motif x in y by the plain recurrence; the smallest of diag, left, up
+    in that order (the reference's), or with left before diag"""
+    N, n = len(x), len(y)
+    D = np.empty((N, n))
+    S = np.empty((N, n), dtype=np.int64)
+    for i in range(N):
+        for j in range(n):
+            c = abs(x[i] - y[j])
+            if i == 0:
+                D[i, j], S[i, j] = c, j
+            elif j == 0:
+                D[i, j], S[i, j] = c + D[i - 1, 0], S[i - 1, 0]
+            else:
+                cand = [(D[i - 1, j - 1], S[i - 1, j - 1]), (D[i, j - 1], S[i, j - 1]), (D[i - 1, j], S[i - 1, j])]
+                if left_first:
+                    cand[0], cand[1] = cand[1], cand[0]
+                best = cand[0]
+                for v in cand[1:]:
+                    if v[0] < best[0]:
+                        best = v
+                D[i, j], S[i, j] = c + best[0], best[1]
+    end = int(np.argmin(D[-1]))
+    return float(D[-1, end]), int(S[-1, end]), end
+
+
+def panel_tie_moves_start(ora, case, exp):
+    """The planted run at the window's median: the reference's record of the zero-led motif is the plain recurrence's, and
+    the same recurrence with `left` before `diag` starts the hit elsewhere."""
+    if not case["plateau"] or "z" not in case["kinds"]:
+        return False
+    k, r = case["plateau"][0], case["kinds"].index("z")
+    lo, w = rc.panel_windows(case)[r]
+    f = ora.scale_outliers(np.asarray(case["reads"][r][lo:lo + w], dtype=np.float64), *rc.PANEL_LIMITS)
+    if exp["ref"][1][r] != 0 or not f.size:
+        return False
+    y = ora.medmad(f)[0]
+    ref = exp["ref"][0][k][r]
+    d, s0, e0 = subsequence_dtw(case["motifs"][k], y)
+    assert (d, s0, e0) == (float(ref["dist"]), int(ref["start"]), int(ref["end"])), rc.describe(case)
+    d2, s1, e1 = subsequence_dtw(case["motifs"][k], y, left_first=True)
+    return d2 == d and e1 == e0 and s1 != s0
+
+
+PANEL_REQUIRED = ({"K=%d" % k for k in rc.PANEL_K} | {"L%d R=%d" % (L, R) for L in (16, 64) for R in range(1, 17)} |
+                  {"L%d P=%s" % (L, P) for L in (16, 64) for P in ("0", "1", "L-1")} |
+                  {"window=" + w for w in ("0", "1", "7", "8", "9", "N-1", "N", "N+1", "L-1", "L", "L+1", "2L+1")} |
+                  {"route=batch", "route=f64", "route=list", "f64 medmad", "f64 zscale", "scale=medmad", "scale=zscale",
+                   "no-row lanes at L16", "three groups interleaved and a long motif", "N=1024", "N=1025", "win rows",
+                   "win row (1e6, -1e6)", "negative begin", "open end", "begin >= end", "region beyond the read",
+                   "MAD 0 window", "nothing inside the limits", "tie-heavy window",
+                   "stride > longest row, padding not zeros", "mixed list", "screened", "tie for best", "tie for second",
+                   "a left / diag tie that moves start"})
+
+
+def test_panel_cases_reach_every_boundary(ora, cases):
+    assert len(cases["panel"]) >= 4
+    have = set()
+    for case, exp in cases["panel"]:
+        have |= panel_features(case, exp)
+        if panel_tie_moves_start(ora, case, exp):
+            have.add("a left / diag tie that moves start")
+        if case["screen"]:
+            assert case["Ns"][0] == 16, rc.describe(case)
+    assert not sorted(PANEL_REQUIRED - have)
+
+
+def test_panel_cases_compare_nine_reads_in_ten_within_the_cell_budget(cases):
+    """In every case fewer than 10 % of the reads are left out of the comparison of dist (MAD 0: the reference divides by
+    zero there), and the oracle fills at most PANEL_CELLS cells."""
+    for case, exp in cases["panel"]:
+        flags = exp["ref"][1]
+        assert 10 * int(np.count_nonzero(flags == 2)) < case["nreads"], rc.describe(case)
+        cells = sum(w for _, w in rc.panel_windows(case)) * sum(case["Ns"])
+        assert cells <= rc.PANEL_CELLS, (cells, rc.describe(case))
+        assert np.any(np.isfinite(exp["ref"][0]["dist"])) or case["kind"] in ("empty", "beyond"), rc.describe(case)
+
+
+# ---- event detection ---------------------------------------------------------------------------------------------------
+def detect_trace(x, params):
+    """detect_ref.marks with one counter added: (marks, silenced) -- silenced counts the times the short detector's peak
+    above its threshold resets the long detector while that one holds a peak above its own threshold."""
+    import detect_ref
+    w_short, w_long, th_short, th_long, h = params
+    n = len(x)
+    ws, th = (int(w_short), int(w_long)), (float(th_short), float(th_long))
+    t = (detect_ref.tstat(x, ws[0]), detect_ref.tstat(x, ws[1]))
+    pos, val, valid, masked_to, out, silenced = [-1, -1], [np.inf, np.inf], [False, False], [-1, -1], [], 0
+    for i in range(n):
+        for k in (0, 1):
+            if i <= masked_to[k]:
+                continue
+            cur = t[k][i]
+            if pos[k] == -1:
+                if cur < val[k]:
+                    val[k] = cur
+                elif cur - val[k] > h:
+                    val[k] = cur
+                    pos[k] = i
+            else:
+                if cur > val[k]:
+                    val[k] = cur
+                    pos[k] = i
+                if k == 0 and val[0] > th[0]:
+                    silenced += pos[1] != -1 and val[1] > th[1]
+                    masked_to[1] = pos[0] + ws[0]
+                    pos[1] = -1
+                    val[1] = np.inf
+                    valid[1] = False
+                if val[k] - cur > h and val[k] > th[k]:
+                    valid[k] = True
+                if valid[k] and i - pos[k] > ws[k] // 2:
+                    out.append(pos[k])
+                    pos[k] = -1
+                    val[k] = cur
+                    valid[k] = False
+    return out, silenced
+
+
+def detect_features(case, exp):
+    import detect_ref
+    ws, wl = case["params"][:2]
+    f = {"R=%d" % case["R"], "preset=" + case["preset"], "stride % 8 == 0" if case["stride"] % 8 == 0 else "stride % 8 != 0"}
+    f |= {"kind=" + k for k in case["kinds"]}
+    if ws == 1:
+        f.add("w_short=1")
+    if wl == 64:
+        f.add("w_long=64")
+    if ws == wl:
+        f.add("w_short=w_long")
+    off, rec = exp["off"], exp["rec"]
+    for r, x in enumerate(case["reads"]):
+        n = len(x)
+        if n in rc.DET_LENS:
+            f.add("len=%d" % n)
+        for w in (ws, wl):
+            for name, v in (("2w-1", 2 * w - 1), ("2w", 2 * w), ("2w+1", 2 * w + 1)):
+                if n == v:
+                    f.add("len=" + name)
+        if n > rc.DET_LONG:
+            f.add("len>8192")
+        marks = rec["start"][off[r]:off[r + 1]][1:].astype(np.int64)      # the boundaries between events
+        if not marks.size:
+            continue
+        if np.any(marks % rc.DET_WORD == 0):
+            f.add("mark at a multiple of 64")
+        if np.any(marks // rc.DET_WORD == (n - 1) // rc.DET_WORD):
+            f.add("mark in the last word")
+        if np.unique(marks // rc.DET_WORD).size < marks.size:
+            f.add("two marks in one word")
+        for k in range(1, n // rc.DET_ROUND):
+            lo, hi = k * rc.DET_ROUND, (k + 1) * rc.DET_ROUND
+            if hi <= n and not np.any((marks >= lo) & (marks < hi)) and np.any(marks < lo) and np.any(marks >= hi):
+                f.add("a round without a mark between events")
+    return f
+
+
+DETECT_REQUIRED = ({"R=%d" % n for n in rc.DET_COUNTS} | {"len=%d" % n for n in rc.DET_LENS} |
+                   {"len=2w-1", "len=2w", "len=2w+1", "len>8192", "stride % 8 == 0", "stride % 8 != 0", "w_short=1",
+                    "w_long=64", "w_short=w_long", "preset=dna", "preset=rna", "preset=drawn", "kind=l", "kind=r", "kind=f",
+                    "kind=p", "mark at a multiple of 64", "mark in the last word", "two marks in one word",
+                    "a round without a mark between events"})
+
+
+def test_detect_cases_reach_every_boundary(cases):
+    assert len(cases["detect"]) >= 4
+    have = set()
+    for case, exp in cases["detect"]:
+        have |= detect_features(case, exp)
+        assert case["total"] <= rc.DET_SAMPLES
+    assert not sorted(DETECT_REQUIRED - have)
+
+
+def detect_silenced(case, most=40):
+    """Reads (of the first `most` with levels) in which the short detector silences a long-detector peak above its
+    threshold; the trace's marks are detect_ref's."""
+    import detect_ref
+    count = 0
+    for x, k in list(zip(case["reads"], case["kinds"]))[:most]:
+        if k in "lp" and 0 < len(x) <= 6000:
+            marks, silenced = detect_trace(x, case["params"])
+            assert marks == detect_ref.marks(x, case["params"])
+            count += silenced > 0
+    return count
+
+
+def test_detect_cases_silence_a_long_mark_by_a_short_peak(cases):
+    assert sum(detect_silenced(case) for case, _ in cases["detect"]) >= 1
+
+
+# ---- signal HMM ------------------------------------------------------------------------------------------------------
+def hmm_final_scores(case):
+    """v[R, S] after the last used sample of every read (hmm_ref's recurrence), NaN rows for empty reads"""
+    import hmm_ref
+    S, linit, ltrans, c, mu, h = hmm_ref.model_arrays(case["model"])
+    if case["feed"] == "batch":
+        x = case["sig"].astype(np.float64)
+        lens = case["lens"].astype(np.int64)
+        if case["cal"] is not None:
+            x = (x + case["cal"][:, :1]) * case["cal"][:, 1:]
+    else:
+        lens = np.array([len(r) for r in case["reads"]], dtype=np.int64)
+        x = np.zeros((len(lens), max(1, int(lens.max(initial=0)))))
+        for i, r in enumerate(case["reads"]):
+            x[i, :len(r)] = r
+    if case["limit"] > 0:
+        lens = np.minimum(lens, case["limit"])
+    v = np.full((len(lens), S), np.nan)
+    for t in range(int(lens.max(initial=0))):
+        act = lens > t
+        e = hmm_ref.emission(c, mu, h, x[:, t])
+        if t == 0:
+            nv = linit[None, :] + e
+        else:
+            with np.errstate(invalid="ignore"):
+                cand = v[:, :, None] + ltrans[None, :, :]
+            b = cand[:, 0, :].copy()
+            for i in range(1, S):
+                b = np.where(cand[:, i, :] > b, cand[:, i, :], b)
+            with np.errstate(invalid="ignore"):
+                nv = b + e
+        v[act] = nv[act]
+    return v
+
+
+def hmm_features(ora, case, exp):
+    f = {"R=%d" % case["R"], "feed=" + case["feed"], "limit=%d" % case["limit"], "S=%d" % case["S"]}
+    if case["integer"]:
+        f.add("integer scores")
+    if case["feed"] == "batch":
+        f.add("calibrated" if case["calibrated"] else "raw")
+        f.add("stride % 8 == 0" if case["stride"] % 8 == 0 else "stride % 8 != 0")
+    if case["feed"] == "list" and 0 < case["nfloat"] < case["R"]:
+        f.add("mixed list")
+    if "SK_INGEST_MB" in case["env"]:
+        f.add("SK_INGEST_MB")
+    if "SK_HMM_SCRATCH_MB" in case["env"] and rc.hmm_slices(case) >= 3 and case["R"] >= 130:
+        f.add("three slices at 130 reads")
+    for r in case["reads"]:
+        if len(r) in rc.HMM_LENS:
+            f.add("len=%d" % len(r))
+        if len(r) > 2000:
+            f.add("len>2000")
+    rec = exp["rec"]
+    used = rec["n_used"] > 0
+    v = hmm_final_scores(case)
+    top = np.nanmax(np.where(np.isnan(v), -np.inf, v), axis=1)
+    if np.any(used & np.isfinite(top) & ((v == top[:, None]).sum(axis=1) >= 2)):
+        f.add("final-state tie")
+        tied = used & np.isfinite(top) & ((v == top[:, None]).sum(axis=1) >= 2)
+        assert np.all(rec["final_state"][tied] == np.argmax(v[tied] == top[tied, None], axis=1))      # the lower state
+    if case["S"] >= 2 and used.any() and np.any(np.all(rec["enter"][used][:, :case["S"]] == -1, axis=0)):
+        f.add("a state no path enters")
+    if case["S"] == 6 and np.any(np.all(rec["enter"][used] >= 0, axis=1)):
+        f.add("every state of a 6-state model in one read")
+    n1 = np.concatenate([p[3]["n1"] for p in exp["parts"]] + [np.zeros(0, dtype=np.int32)])
+    ln = np.concatenate([p[3]["length"] for p in exp["parts"]] + [np.zeros(0, dtype=np.int32)])
+    if np.any(n1 > 0) and np.any(n1 < ln):
+        f.add("both components win")
+    if 0 < case["limit"] < 100000:
+        full = rc.expect_hmm(ora, dict(case, limit=0))
+        for idx, _, off, seg in full["parts"]:
+            for k, r in enumerate(idx):
+                g = seg[int(off[k]):int(off[k + 1])]
+                if len(case["reads"][r]) > case["limit"] and np.any((g["start"] < case["limit"]) &
+                                                                    (g["start"] + g["length"] > case["limit"])):
+                    f.add("limit cuts a segment")
+    return f
+
+
+HMM_REQUIRED = ({"R=%d" % n for n in rc.HMM_COUNTS} | {"len=%d" % n for n in rc.HMM_LENS} |
+                {"limit=%d" % n for n in (0, 1, 33, 129)} | {"S=1", "S=6"} |
+                {"feed=batch", "feed=f64", "feed=list", "mixed list", "calibrated", "raw", "stride % 8 == 0",
+                 "stride % 8 != 0", "integer scores", "SK_INGEST_MB", "three slices at 130 reads", "len>2000",
+                 "final-state tie", "a state no path enters", "every state of a 6-state model in one read",
+                 "both components win", "limit cuts a segment"})
+
+
+def test_hmm_cases_reach_every_boundary(ora, cases):
+    import hmm_path_ref
+    assert len(cases["hmm"]) >= 4
+    have = set()
+    for case, exp in cases["hmm"]:
+        have |= hmm_features(ora, case, exp)
+        assert case["total"] <= rc.HMM_SAMPLES
+        for idx, rec, off, seg in exp["parts"]:          # the reference keeps its own invariants, and both references agree
+            hmm_path_ref.invariants(case["model"], rec, off, seg)
+            assert rec.tobytes() == exp["rec"][idx].tobytes()
+    assert not sorted(HMM_REQUIRED - have)
+
+
+# ---- segment levels --------------------------------------------------------------------------------------------------
+def levels_features(case, exp):
+    f = {"route=" + case["route"]}
+    if "max_segs" in case:                               # (the list form takes none: nothing is claimed for it)
+        assert case["route"] != "list"
+        f.add("max_segs=%d" % case["max_segs"])
+    if case["lo"] < 0:
+        f.add("negative lim_low")
+    for r, (x, segs) in enumerate(zip(case["reads"], exp["segs"])):
+        n = len(x)
+        if n in rc.LEVELS_LENS:
+            f.add("len=%d" % n)
+        if n > rc.SEGLEV_LDS_COLS:
+            f.add("read above SEGLEV_LDS_COLS")
+        if "max_segs" in case and len(segs) > case["max_segs"]:
+            f.add("more segments than max_segs=%d" % case["max_segs"])
+        kept = np.flatnonzero((x > case["lo"]) & (x < case["hi"]))
+        y = x[kept]
+        if kept.size and kept.size < n // 2 + n // 4:
+            f.add("a quarter of the samples dropped")
+        for s, e in segs:
+            w = y[s:e]
+            f.add("span of even length" if len(w) % 2 == 0 else "span of odd length")
+            if len(w) > rc.SEGLEV_LDS_COLS:
+                f.add("segment above SEGLEV_LDS_COLS")
+            if len(w) and w.min() < 0 < w.max():
+                f.add("keys of both signs in a span")
+            if len(w) >= 16 and 4 * np.unique(w).size <= len(w):
+                f.add("tie-heavy span")
+            if len(w) and kept[s] != s:
+                f.add("raw_start differs from the filtered index")
+    if case["route"] == "list" and 0 < case["nfloat"] < case["R"]:
+        f.add("mixed list")
+    return f
+
+
+LEVELS_REQUIRED = ({"route=" + r for r in rc.LEVELS_ROUTES} | {"max_segs=%d" % n for n in rc.LEVELS_MAX_SEGS} |
+                   {"len=%d" % n for n in rc.LEVELS_LENS} |
+                   {"negative lim_low", "read above SEGLEV_LDS_COLS", "segment above SEGLEV_LDS_COLS",
+                    "more segments than max_segs=1", "more segments than max_segs=2", "a quarter of the samples dropped", "span of even length",
+                    "span of odd length", "keys of both signs in a span", "tie-heavy span",
+                    "raw_start differs from the filtered index", "mixed list"})
+
+
+def test_levels_cases_reach_every_boundary(cases):
+    assert len(cases["levels"]) >= 4
+    have = set()
+    segments = 0
+    for case, exp in cases["levels"]:
+        have |= levels_features(case, exp)
+        segments += sum(len(s) for s in exp["segs"])
+    assert not sorted(LEVELS_REQUIRED - have)
+    assert segments >= 10 * len(cases["levels"])         # spans to compare, not only whole reads
+
+
 def test_same_seed_same_case():
     for fam in rc.SEEDS:
         seed = rc.SEEDS[fam][0]
@@ -272,3 +745,26 @@ def test_interleaved_sequence_is_what_it_claims():
     first_paths = next(i for i, (f, _) in enumerate(seq) if f == "paths")
     assert any(f == "hits" and size[i] > max(size[:i]) for i, (f, _) in enumerate(seq) if i > first_paths)
     assert seq.index(seq[first_paths], first_paths + 1) > first_paths      # the first paths call comes again
+
+
+def test_second_interleaved_sequence_is_what_it_claims():
+    """>= 24 calls: the four newer families and both twins between older calls, the longest read going up and down, four
+    calls or more occurring twice."""
+    seq = rc.INTERLEAVE2
+    assert len(seq) >= 24
+    fams = {f for f, _ in seq}
+    assert {"panel", "detect", "hmm", "levels", "background", "events"} <= fams
+    assert len(fams & {"sweep", "hits", "paths", "pull", "segment", "motifseq", "pa"}) >= 4
+    assert len(seq) - len(set(seq)) >= 4
+    for fam, seed in seq:
+        assert fam not in rc.SEEDS or seed in rc.SEEDS[fam]
+        assert fam not in rc.TWIN_OF or seed in rc.SEEDS[rc.TWIN_OF[fam]]
+    size = []
+    for fam, seed in seq:
+        case = rc.interleave_case(fam, seed)
+        size.append(max(len(r) for r in case["reads"]) if "reads" in case else int(np.max(case["lens"])))
+    turns = sum((b - a) * (c - b) < 0 for a, b, c in zip(size, size[1:], size[2:]))
+    assert turns >= 8, size
+    new = [i for i, (f, _) in enumerate(seq) if f in ("panel", "detect", "hmm", "levels")]
+    assert any(size[i] > max(size[:i]) for i in new[1:])                    # a newer family grows the shared buffers
+    assert any(size[i] < size[i - 1] // 4 for i in new if i)               # and one runs in buffers left much larger

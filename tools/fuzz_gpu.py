@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle sweep over shapes the unit tests do not pin: random read counts, ragged
-lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; and, per round, one drawn case each
-of the segmenter sweep, the MotifSeq hit lists, the alignment paths and SquigglePull's text (tests/randcases.py);
-the segment levels of every segmenter round against plain numpy; event detection (random read counts, lengths, strides and
-parameters) against the numpy statement of its definition (tests/detect_ref.py); the signal HMM (the same reads, a random
-model, calibration, limit, either feed) against tests/hmm_ref.py, and its state paths against tests/hmm_path_ref.py.
+lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; the segment levels of every
+segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the segmenter
+sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
+signal HMM with its state paths, segment levels, and the background and events twins of the hit family -- each against the
+reference tests/test_gpu_random.py uses.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -23,33 +23,6 @@ import randcases                                      # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
-
-
-def levels_mismatch(levels, read_level, reads, segs, nsegs, lo, hi):
-    """None, or where the records differ from numpy's on the given segments (doubles by bit pattern)"""
-    want_l, want_r = api.no_levels(levels.shape), api.no_levels(len(reads))
-
-    def one(w, kept, s):
-        m = np.median(w)
-        return (np.mean(w), np.std(w), m, np.median(np.abs(w - m)), w.min(), w.max(), kept[s], kept[s + len(w) - 1] + 1, len(w), 0)
-    for r, a in enumerate(reads):
-        kept = np.flatnonzero((a > lo) & (a < hi))
-        y = a[kept]
-        if y.size:
-            want_r[r] = one(y, kept, 0)
-        for k in range(min(int(nsegs[r]), levels.shape[1])):
-            s, e = segs[r, k]
-            if len(y[s:e]):
-                want_l[r, k] = one(y[s:e], kept, s)
-    for got, want, what in ((levels, want_l, "levels"), (read_level, want_r, "read_level")):
-        for f in got.dtype.names:
-            g, w = np.ascontiguousarray(got[f]), np.ascontiguousarray(want[f])
-            if g.dtype.kind == "f":
-                g, w = g.view(np.uint64), w.view(np.uint64)
-            d = np.argwhere(g != w)
-            if d.size:
-                return "%s.%s at %s: got %r want %r" % (what, f, d[0].tolist(), got[f][tuple(d[0])], want[f][tuple(d[0])])
-    return None
 
 
 def main():
@@ -125,7 +98,9 @@ def main():
             bad += 1
             print("LEVELS segs differ from segment_batch R=%d M=%d %s" % (R, M, kw))
         else:
-            why = levels_mismatch(lv, rl, [sig[r, :lens[r]].astype(np.int64) for r in range(R)], osegs, onsegs, p.lim_low, p.lim_hi)
+            want = randcases.levels_expected(lv.dtype, [sig[r, :lens[r]] for r in range(R)],
+                                             [osegs[r, :onsegs[r]] for r in range(R)], lv.shape, p.lim_low, p.lim_hi)
+            why = randcases.levels_mismatch(lv, rl, *want)
             if why:
                 bad += 1
                 print("LEVELS mismatch R=%d M=%d %s: %s" % (R, M, kw, why))
@@ -301,12 +276,19 @@ def main():
             os.environ.pop("SK_DRNA_STEP", None)
             for key in ("SK_ROLL_TWO_KERNELS", "SK_ROLL_ONE_LOOK", "SK_ROLL_DELTA_SCALE"):
                 os.environ.pop(key, None)
-        # ---- the sweep, the hit lists, the paths and pull: tests/randcases.py's draws with this tool's running generator,
-        # against the same references as tests/test_gpu_random.py (the oracle per (set, read), reference_hits,
-        # reference_paths, numpy_pull_text).  A mismatch line carries the round, so `fuzz_gpu.py <seconds> <seed>` up to
-        # that round rebuilds the case, and the drawn parameters and switches.
-        for fam in ("sweep", "hits", "paths", "pull"):
-            case = randcases.DRAW[fam](rng)
+        # ---- tests/randcases.py's draws with this tool's running generator, against the same references as
+        # tests/test_gpu_random.py: the sweep (the oracle per (set, read)), the hit lists (reference_hits), the paths
+        # (reference_paths), pull (numpy_pull_text), the panel (reference_panel), event detection (detect_ref), the signal
+        # HMM with its state paths (hmm_ref, hmm_path_ref), segment levels (numpy on the oracle's segments); then a
+        # hit-list draw through the background twin (numpy on the oracle's last row, test_background_host.py) and a paths
+        # draw through the events twin with pooling (test_events_host.py).  A mismatch line carries the round, so
+        # `fuzz_gpu.py <seconds> <seed>` up to that round rebuilds the case, and the drawn parameters and switches.
+        for fam in ("sweep", "hits", "paths", "pull", "panel", "detect", "hmm", "levels", "background", "events"):
+            if fam in randcases.TWIN_OF:
+                case = randcases.DRAW[randcases.TWIN_OF[fam]](rng)
+                case = randcases.twin_case(fam, case, use_seed=int(rng.integers(1 << 30)))
+            else:
+                case = randcases.DRAW[fam](rng)
             for key in randcases.SWITCHES:
                 if key in case["env"]:
                     os.environ[key] = case["env"][key]
@@ -317,148 +299,27 @@ def main():
             msg = randcases.DIFF[fam](case, got, exp)
             if msg is None and fam == "paths" and api.last_path_mismatches() != 0:
                 msg = "%d hits failed the path kernel's self-check" % api.last_path_mismatches()
-            if msg is not None:
+            if msg is None and fam == "panel":
+                guard = api.last_dtw_guard()                 # the screening scheme's guard, as test_gpu_panel.same reads it
+                if any(guard[k] for k in ("premise_violations", "audit_mismatches", "alarm", "exact_fallback")):
+                    msg = "the guard counters are not all zero: %s" % guard
+            if msg is not None and fam == "detect":          # (the lines of the sections these draws replaced, as they were)
+                bad += 1
+                print("DETECT mismatch round %d: %d reads, max length %d, stride %d, params %s -- %s" %
+                      (rounds, case["R"], case["dmax"], case["stride"], case["params"], msg))
+            elif msg is not None and fam == "hmm":
+                bad += 1
+                what = "float64 feed" if case["feed"] == "f64" else "list" if case["feed"] == "list" else \
+                    "int16 feed, %s" % ("calibrated" if case["calibrated"] else "raw")
+                print("%s mismatch round %d: %d reads, max length %d, stride %d, %d states%s, limit %d, %s -- %s" %
+                      ("HMM" if randcases.diff_hmm_records(case, got, exp) else "HMM PATH", rounds, case["R"], case["dmax"],
+                       case.get("stride", 0), case["S"], " (integer scores)" if case["integer"] else "", case["limit"], what,
+                       msg))
+            elif msg is not None:
                 bad += 1
                 print("%s mismatch round %d %s: %s" % (fam.upper(), rounds, randcases.describe(case), msg))
             for key in randcases.SWITCHES:
                 os.environ.pop(key, None)
-        # ---- the read background: a hit-list draw through the background twin, every record against numpy on the
-        # oracle's last row (tests/test_background_host.py), the hit lists against the hit-list call's
-        case = randcases.DRAW["hits"](rng)
-        for key in randcases.SWITCHES:
-            if key in case["env"]:
-                os.environ[key] = case["env"][key]
-        from test_background_host import reference_background_reads
-        bkw = (case["motifs"], case["K"], float("inf"), case["scale"], case["lo"], case["hi"])
-        got, twin = api.motifseq_background(case["reads"], *bkw), api.motifseq_hits(case["reads"], *bkw)
-        for m, motif in enumerate(case["motifs"]):
-            want = reference_background_reads(ora, case["reads"], motif, case["scale"], case["lo"], case["hi"])
-            msg = None
-            if got[m][0].tobytes() != twin[m][0].tobytes() or not np.array_equal(got[m][1], twin[m][1]):
-                msg = "hit lists differ from the hit-list call's"
-            for r, w in enumerate(want):
-                g = got[m][2][r]
-                if w is None:
-                    ok = g["below"] == -1 and all(np.isnan(g[f]) for f in ("mean", "std", "median", "mad"))
-                else:
-                    ok = (int(g["below"]), int(g["n"])) == w[4:] and all(
-                        np.float64(g[f]).tobytes() == np.float64(v).tobytes()
-                        for f, v in zip(("mean", "std", "median", "mad"), w))
-                if not ok and msg is None:
-                    msg = "motif %d read %d (%d samples): got %s want %s" % (m, r, len(case["reads"][r]), g, w)
-            if msg is not None:
-                bad += 1
-                print("BACKGROUND mismatch round %d %s: %s" % (rounds, randcases.describe(case), msg))
-        for key in randcases.SWITCHES:
-            os.environ.pop(key, None)
-        # ---- events and pooling: a paths draw through the events twin, every record and the pooled model against the
-        # numpy statement of the contract (tests/test_events_host.py), the hit lists against the hit-list call's
-        case = randcases.DRAW["paths"](rng)
-        for key in randcases.SWITCHES:
-            if key in case["env"]:
-                os.environ[key] = case["env"][key]
-        from test_events_host import reference_batch, reference_pool
-        ekw = (case["motifs"], case["K"], float("inf"), case["scale"], case["lo"], case["hi"])
-        got, twin = api.motifseq_events(case["reads"], *ekw), api.motifseq_hits(case["reads"], *ekw)
-        for m, motif in enumerate(case["motifs"]):
-            _, want = reference_batch(ora, case["reads"], motif, case["K"], case["scale"], case["lo"], case["hi"])
-            msg = None
-            if got[m][0].tobytes() != twin[m][0].tobytes() or not np.array_equal(got[m][1], twin[m][1]):
-                msg = "hit lists differ from the hit-list call's"
-            elif api.last_path_mismatches() != 0:
-                msg = "%d hits failed the path kernel's self-check" % api.last_path_mismatches()
-            elif got[m][2].tobytes() != want.tobytes():
-                r, k, i = (int(v[0]) for v in np.nonzero(got[m][2] != want))
-                msg = "motif %d read %d hit %d point %d: got %s want %s" % (m, r, k, i, got[m][2][r, k, i], want[r, k, i])
-            else:
-                use = rng.random(want.shape[0] * want.shape[1]) < 0.7
-                pool, ref = api.pool_events(got[m][2], use), reference_pool(want, use)
-                if any(pool[f].tobytes() != ref[f].tobytes() for f in api.POOL_DTYPE.names):
-                    msg = "motif %d: the pooled model differs from numpy's" % m
-            if msg is not None:
-                bad += 1
-                print("EVENTS mismatch round %d %s: %s" % (rounds, randcases.describe(case), msg))
-        for key in randcases.SWITCHES:
-            os.environ.pop(key, None)
-        # ---- event detection: random read counts, lengths and parameters against the numpy statement of the
-        # definition (tests/detect_ref.py); every off and every record field exactly
-        import detect_ref
-        dn = int(rng.choice([1, 3, 63, 64, 65, 200]))
-        dmax = int(rng.choice([8, 70, 130, 300, 1500, 5000]))
-        dlens = rng.integers(0, dmax + 1, dn)
-        dreads = []
-        for n in dlens:
-            kind = rng.random()
-            if kind < 0.6:                                      # levels with noise
-                lv = np.repeat(rng.normal(500, 80, n // 3 + 1), rng.integers(1, 20, n // 3 + 1))[:n]
-                x = lv + rng.normal(0, float(rng.choice([0, 2, 8, 30])), lv.size)
-            elif kind < 0.8:                                    # anything an int16 holds
-                x = rng.integers(-32768, 32768, n).astype(np.float64)
-            else:                                               # flat, or two values
-                x = np.where(rng.random(n) < float(rng.choice([0.0, 0.5])), 32767.0, float(rng.integers(-32768, 32767)))
-            dreads.append(np.clip(np.rint(x), -32768, 32767).astype(np.int16))
-        dlens = np.array([x.size for x in dreads])
-        ws = int(rng.integers(1, 65))
-        dpar = [detect_ref.PRESETS["dna"], detect_ref.PRESETS["rna"],
-                (ws, int(rng.integers(ws, 65)), float(rng.choice([0.0, 1.4, 2.5, 20.0])), float(rng.choice([0.0, 4.0, 9.0])),
-                 float(rng.choice([0.0, 0.2, 1.0, 5.0])))][int(rng.integers(3))]
-        dstride = int(max(dlens.max(), 1)) + int(rng.integers(0, 9))     # any stride: rows need not be 16-byte aligned
-        dbuf = np.full((dn, dstride), -7, dtype=np.int16)
-        for r, x in enumerate(dreads):
-            dbuf[r, :x.size] = x
-        goff, grec = api.detect_events_batch(dbuf, dlens.astype(np.int32), api.det_params(
-            w_short=dpar[0], w_long=dpar[1], th_short=dpar[2], th_long=dpar[3], peak_height=dpar[4]))
-        woff, wrec = detect_ref.detect(dreads, dpar)
-        if not np.array_equal(goff, woff) or grec.tobytes() != wrec.tobytes():
-            bad += 1
-            print("DETECT mismatch round %d: %d reads, max length %d, stride %d, params %s" % (rounds, dn, dmax, dstride, dpar))
-        # ---- signal HMM: the same rows under a random model (1 .. 6 states, -inf transitions and components, sometimes
-        # integer scores), a random calibration and limit, through the int16 or the float64 feed, against the numpy
-        # statement (tests/hmm_ref.py); every record byte for byte
-        import hmm_ref
-        hS = int(rng.integers(1, 7))
-        integer = rng.random() < 0.3
-        if integer:
-            hl, ht = rng.integers(-3, 1, hS).astype(np.float64), rng.integers(-2, 1, (hS, hS)).astype(np.float64)
-            hc, hmu = rng.integers(-2, 1, (hS, 2)).astype(np.float64), rng.integers(-3, 4, (hS, 2)).astype(np.float64) * 100 + 500
-            hh = rng.integers(0, 2, (hS, 2)).astype(np.float64)
-        else:
-            hl, ht = np.log(rng.uniform(0.01, 1, hS)), np.log(rng.uniform(0.001, 1, (hS, hS)))
-            hc, hmu = np.log(rng.uniform(0.01, 1, (hS, 2)) / rng.uniform(2, 90, (hS, 2))), rng.uniform(-200, 1200, (hS, 2))
-            hh = np.where(rng.random((hS, 2)) < 0.2, 0.0, 1.0 / (2.0 * rng.uniform(2, 90, (hS, 2)) ** 2))
-        hl[rng.random(hS) < 0.3] = -np.inf
-        if not np.isfinite(hl).any():
-            hl[int(rng.integers(hS))] = 0.0
-        ht[rng.random((hS, hS)) < 0.4] = -np.inf
-        hc[rng.random(hS) < 0.5, 1] = -np.inf
-        hmodel = api.HmmModel.from_arrays(hS, hl, ht, hc, hmu, hh)
-        hlimit = int(rng.choice([0, 0, 1, 33, 129, 100000]))
-        if rng.random() < 0.3:                                  # the float64 feed (no calibration)
-            hgot = api.hmm_viterbi_ragged_f64(*api.pack_f64(dreads), hmodel, hlimit)
-            hwant = hmm_ref.viterbi_reads(hmodel, dreads, hlimit)
-            hwhat = "float64 feed"
-        else:
-            hcal = None if rng.random() < 0.5 else np.stack([rng.uniform(-50, 50, dn), rng.uniform(0.1, 0.3, dn)], axis=1)
-            hgot = api.hmm_viterbi_batch(dbuf, dlens.astype(np.int32), hmodel, hcal, hlimit)
-            hwant = hmm_ref.viterbi_batch(hmodel, dbuf, dlens, hcal, hlimit)
-            hwhat = "int16 feed, %s" % ("calibrated" if hcal is not None else "raw")
-        if hgot.tobytes() != hwant.tobytes():
-            bad += 1
-            print("HMM mismatch round %d: %d reads, max length %d, stride %d, %d states%s, limit %d, %s" %
-                  (rounds, dn, dmax, dstride, hS, " (integer scores)" if integer else "", hlimit, hwhat))
-        # ---- signal HMM state paths: the same reads, model, calibration and limit through the matching segments call,
-        # against the numpy statement (tests/hmm_path_ref.py): records, offsets and segments byte for byte
-        import hmm_path_ref
-        if hwhat == "float64 feed":
-            pgot = api.hmm_segments_ragged_f64(*api.pack_f64(dreads), hmodel, hlimit)
-            pwant = hmm_path_ref.segments_reads(hmodel, dreads, hlimit)
-        else:
-            pgot = api.hmm_segments_batch(dbuf, dlens.astype(np.int32), hmodel, hcal, hlimit)
-            pwant = hmm_path_ref.segments_batch(hmodel, dbuf, dlens, hcal, hlimit)
-        if [x.tobytes() for x in pgot] != [x.tobytes() for x in pwant] or pgot[0].tobytes() != hgot.tobytes():
-            bad += 1
-            print("HMM PATH mismatch round %d: %d reads, max length %d, stride %d, %d states%s, limit %d, %s" %
-                  (rounds, dn, dmax, dstride, hS, " (integer scores)" if integer else "", hlimit, hwhat))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
