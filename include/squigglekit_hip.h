@@ -929,6 +929,64 @@ int sk_hmm_segments_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t 
 int sk_hmm_segments_f64_len(const double *values, const int64_t *in_off, int32_t nreads, const sk_hmm_model *model,
                             int32_t limit, sk_hmm_rec *rec, int64_t *off /* [nreads + 1] */, sk_hmm_segf *seg, int64_t cap);
 
+/* ---- MotifSeq sessions: search reads chunk by chunk as they arrive --------- */
+/* A session owns K motifs (at most 1 024 points each), nslots slots -- one read in progress each, e.g. one per sequencer
+ * channel --, the filter limits, a scale mode and a calibration length W = calib ("MotifSeq sessions";
+ * tests/stream_ref.py states the definition in numpy).  Let raw be all samples pushed to a slot since its last reset,
+ * kept = raw after the filter (scale_low < x < scale_hi, raw units), n = len(kept), seen = len(raw).
+ * Calibration: while n < W and the slot has not been flushed it is calibrating: it buffers its kept samples and its
+ *     records are dist = tail = NaN, start = end = -1, n, seen, flags = SK_FLAG_CALIBRATING.  When n reaches W, center
+ *     and scale are fixed from the first W kept samples (a flush with n >= 1: from all n) -- exactly the statistics
+ *     sk_motifseq_multi_batch_i16 takes of that row -- and never change afterwards.  A reset may hand the slot a
+ *     (center, scale) pair instead; that slot never calibrates.
+ * Search: with y = ((double)kept - center) / scale the record of motif k after any push is that of
+ *     dtw_subsequence(motif_k, y): dist = the first minimum of cost[-1, :], end its column, start by the back-trace
+ *     (diagonal, then j - 1, then i - 1), tail = cost[-1, n - 1]: the cost of the best match that ends at the newest
+ *     sample.  start, end and n are in kept coordinates.  n = 0: dist = tail = NaN, start = end = -1.
+ * medmad with MAD 0: SK_FLAG_DEGENERATE, NaN distances and -1 coordinates until the slot is reset.  A flush at n = 0:
+ *     SK_FLAG_EMPTY (a calibrating slot then stays without statistics, NaN / -1, until it is reset).
+ * The record depends only on the samples pushed so far -- not on how they were cut into chunks, which other slots
+ * shared the call, or the slot's number; a read of n <= W samples pushed in any chunks and flushed has the dist, start,
+ * end, n and flags of sk_motifseq_multi_batch_i16 on the whole read -- field for field, so a slot whose calibration a
+ * flush ended on a MAD of 0 reports the dist = +inf that call leaves for such a read (tail stays NaN), not NaN.
+ * chunks counts the pushes of len > 0 the read has had; a push of len 0 is a peek and changes nothing. */
+#define SK_STREAM_MAX_CALIB 65536
+#define SK_STREAM_MAX_SESSIONS 8
+enum { SK_FLAG_CALIBRATING = 8 };  /* sk_stream_rec.flags: the slot still collects its calibration samples */
+typedef struct sk_stream_params {   /* 32 bytes */
+    int32_t scale_mode;             /* SK_SCALE_MEDMAD or SK_SCALE_ZSCALE */
+    int32_t scale_low, scale_hi;
+    int32_t calib;                  /* W: 1 .. SK_STREAM_MAX_CALIB */
+    int32_t nslots;                 /* 1 .. 65536 */
+    int32_t reserved[3];            /* 0 */
+} sk_stream_params;
+typedef struct sk_stream_rec {      /* 40 bytes */
+    double  dist, tail;
+    int32_t start, end, n, seen, flags, chunks;
+} sk_stream_rec;
+/* motif k = motifs[motif_off[k] .. motif_off[k + 1]).  The session belongs to the context the calling thread is bound
+ * to (at most SK_STREAM_MAX_SESSIONS per context; the handle is valid for threads bound to it; sk_shutdown closes them).
+ * SK_ERR_INVALID: no motifs, an empty motif, calib or nslots out of range, non-zero reserved words, an unknown scale
+ * mode; SK_ERR_UNSUPPORTED: a motif of more than 1 024 points. */
+int sk_stream_open(const double *motifs, const int32_t *motif_off, int32_t nmotifs, const sk_stream_params *p,
+                   int32_t *handle);
+/* Appends len[i] samples (row i of `rows`, `stride` apart; 0 <= len[i] <= stride) to slot slots[i], i < m, and returns
+ * every named slot's records, out [nmotifs][m].  A slot may appear once per call (host form: SK_ERR_INVALID otherwise,
+ * like a slot out of range or an unknown handle). */
+int sk_stream_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride,
+                       const int32_t *len, sk_stream_rec *out);
+/* device-resident form: every pointer is a device pointer, nothing is synchronised; distinct slots are the caller's
+ * contract, d_len[i] is clamped into [0, stride] and an entry whose slot is out of range is skipped (its records: NaN,
+ * -1 and zero counts). */
+int sk_stream_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                           const int32_t *d_len, sk_stream_rec *d_out);
+/* Ends the calibration of the named slots with what they hold (see above) and returns their records like a push. */
+int sk_stream_flush(int32_t handle, const int32_t *slots, int32_t m, sk_stream_rec *out);
+/* Starts a new read in the named slots.  center and scale both NULL: the slots calibrate; both given ([m], scale finite
+ * and not 0, center finite): they search under that normalisation from their first sample. */
+int sk_stream_reset(int32_t handle, const int32_t *slots, int32_t m, const double *center, const double *scale);
+int sk_stream_close(int32_t handle);
+
 #ifdef __cplusplus
 }
 #endif

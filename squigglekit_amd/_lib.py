@@ -26,6 +26,8 @@ SK_OK, SK_ERR_INVALID, SK_ERR_NO_DEVICE, SK_ERR_HIP, SK_ERR_NOMEM, SK_ERR_UNSUPP
 SK_SCALE = {"medmad": 0, "zscale": 1}
 SK_PULL_RAW, SK_PULL_PA = 0, 1
 SK_FLAG_EMPTY, SK_FLAG_DEGENERATE, SK_FLAG_RECENTRE = 1, 2, 4
+SK_FLAG_CALIBRATING = 8                 # sk_stream_rec.flags: the slot still collects its calibration samples
+SK_STREAM_MAX_CALIB, SK_STREAM_MAX_SLOTS, SK_STREAM_MAX_POINTS = 65536, 65536, 1024
 
 
 class SegParams(C.Structure):
@@ -235,6 +237,21 @@ HMM_SEG_DTYPE = np.dtype([("state", "<i4"), ("start", "<i4"), ("length", "<i4"),
 HMM_SEGF_DTYPE = np.dtype([("state", "<i4"), ("start", "<i4"), ("length", "<i4"), ("n1", "<i4"), ("sum", "<f8", (2,)),
                            ("sumsq", "<f8", (2,))])
 
+class StreamParams(C.Structure):
+    """sk_stream_params: what a MotifSeq session is opened with."""
+    _fields_ = [("scale_mode", C.c_int32), ("scale_low", C.c_int32), ("scale_hi", C.c_int32), ("calib", C.c_int32),
+                ("nslots", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class StreamRec(C.Structure):
+    """sk_stream_rec: one slot's record against one motif after a push."""
+    _fields_ = [("dist", C.c_double), ("tail", C.c_double), ("start", C.c_int32), ("end", C.c_int32), ("n", C.c_int32),
+                ("seen", C.c_int32), ("flags", C.c_int32), ("chunks", C.c_int32)]
+
+
+STREAM_DTYPE = np.dtype([("dist", "<f8"), ("tail", "<f8"), ("start", "<i4"), ("end", "<i4"), ("n", "<i4"), ("seen", "<i4"),
+                         ("flags", "<i4"), ("chunks", "<i4")])
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -383,6 +400,15 @@ ABI = {
     "sk_hmm_segments_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp,
                                           C.c_int64]),
     "sk_hmm_segments_f64_len": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp, C.c_int64]),
+    # MotifSeq sessions ("MotifSeq sessions" in include/squigglekit_hip.h; tests/stream_ref.py states them in numpy):
+    # open(motifs, motif_off, nmotifs, params, handle); push(handle, slots, m, rows, stride, len, out [nmotifs][m]) and
+    # its device-resident form; flush(handle, slots, m, out); reset(handle, slots, m, center, scale); close(handle)
+    "sk_stream_open": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(StreamParams), _i32p]),
+    "sk_stream_push_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp]),
+    "sk_stream_push_dev_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp]),
+    "sk_stream_flush": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
+    "sk_stream_reset": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    "sk_stream_close": (C.c_int, [C.c_int32]),
 }
 
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HmmModel, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HmmModel, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -2034,3 +2034,136 @@ def hmm_fit(batches, spec, states, rounds, update=("mean", "sigma"), sigma_floor
         history.append({"round": rnd, "reads": pooled["reads"], "segments": nseg, "max_segments": most, "pooled": pooled,
                         "spec": spec})
     return spec, history
+
+
+# ----------------------------------------------------------------------------
+# MotifSeq sessions: search reads chunk by chunk as they arrive
+# ----------------------------------------------------------------------------
+def stream_slots(slots, nslots):
+    """The slots of one session call as an int32 array: every one inside [0, nslots), none twice."""
+    a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= nslots):
+        raise ValueError("slot outside [0, %d)" % nslots)
+    if np.unique(a).size != a.size:
+        raise ValueError("a slot may appear once per call")
+    return a
+
+
+class MotifStream:
+    """A MotifSeq session (sk_stream_*): `nslots` reads in progress, searched for every motif of `motifs` chunk by chunk.
+    A slot calibrates on its first `calib` kept samples (medmad or zscale, fixed from then on) -- or takes the
+    (center, scale) a reset hands it -- and from then on every push returns, per motif, the record dtw_subsequence would
+    give on all the samples the slot has seen: STREAM_DTYPE [K, m] (dist, tail, start, end, n, seen, flags, chunks).
+
+        with MotifStream([motif], nslots=512) as ms:
+            rec = ms.push(slots, chunks)          # chunks: a list of int16 arrays, or (rows [m, stride], lens [m])
+            rec = ms.flush(slots)                 # end of read: calibrate on what there is
+            ms.reset(slots)                       # the slots start a new read
+    """
+
+    def __init__(self, motifs, nslots, scale="medmad", scale_low=0, scale_hi=1200, calib=2000):
+        self._h = None
+        self._ms, flat, moff = _flat_motifs(motifs)
+        if not self._ms or any(m.size == 0 for m in self._ms):
+            raise ValueError("a session needs at least one motif, none of them empty")
+        if max(m.size for m in self._ms) > _lib.SK_STREAM_MAX_POINTS:
+            raise ValueError("a session takes motifs of at most %d points" % _lib.SK_STREAM_MAX_POINTS)
+        if scale not in _lib.SK_SCALE:
+            raise ValueError("scale must be one of %s" % sorted(_lib.SK_SCALE))
+        if not 1 <= int(calib) <= _lib.SK_STREAM_MAX_CALIB:
+            raise ValueError("calib must be in 1 .. %d, got %d" % (_lib.SK_STREAM_MAX_CALIB, int(calib)))
+        if not 1 <= int(nslots) <= _lib.SK_STREAM_MAX_SLOTS:
+            raise ValueError("nslots must be in 1 .. %d, got %d" % (_lib.SK_STREAM_MAX_SLOTS, int(nslots)))
+        self.nslots, self.K, self.calib = int(nslots), len(self._ms), int(calib)
+        L = _lib.ensure_init()
+        p = _lib.StreamParams(_lib.SK_SCALE[scale], int(scale_low), int(scale_hi), self.calib, self.nslots)
+        h = C.c_int32(-1)
+        check(L.sk_stream_open(ptr(flat), ptr(moff), self.K, C.byref(p), C.byref(h)))
+        self._h = h.value
+
+    handle = property(lambda self: self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                            # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def _open(self):
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return _lib.load()
+
+    def push(self, slots, chunks):
+        """Append chunk i to slot slots[i]; a chunk of length 0 is a peek.  Records [K, m]."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if isinstance(chunks, tuple):
+            rows, lens = chunks
+            rows = np.ascontiguousarray(rows, dtype=np.int16)
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+            if rows.ndim != 2:
+                raise ValueError("rows must be [m, stride]")
+        else:
+            chunks = [np.asarray(c) for c in chunks]
+            if any(c.dtype != np.int16 for c in chunks):
+                raise ValueError("a session takes int16 chunks (raw samples)")
+            rows, lens = pack_i16(chunks)
+        if rows.shape[0] != slots.size or lens.size != slots.size:
+            raise ValueError("one chunk per slot")
+        out = np.zeros((self.K, slots.size), dtype=STREAM_DTYPE)
+        if slots.size:
+            check(L.sk_stream_push_i16(self._h, ptr(slots), slots.size, ptr(rows), rows.shape[1], ptr(lens), ptr(out)))
+        return out
+
+    def flush(self, slots):
+        """End the calibration of the slots with what they hold (end of read).  Records [K, m]."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        out = np.zeros((self.K, slots.size), dtype=STREAM_DTYPE)
+        if slots.size:
+            check(L.sk_stream_flush(self._h, ptr(slots), slots.size, ptr(out)))
+        return out
+
+    def reset(self, slots, center=None, scale=None):
+        """The slots start a new read: calibrating, or under the given normalisation (scalars or one value per slot)."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if (center is None) != (scale is None):
+            raise ValueError("center and scale: both or neither")
+        if center is None:
+            check(L.sk_stream_reset(self._h, ptr(slots), slots.size, None, None))
+            return
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), slots.shape))
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), slots.shape))
+        check(L.sk_stream_reset(self._h, ptr(slots), slots.size, ptr(c), ptr(s)))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L = _lib.load()
+            if L.sk_stream_close(h) not in (0, _lib.SK_ERR_NO_DEVICE):   # (after sk_shutdown the session is gone already)
+                check(-1)
+
+
+def stream_decide(rec, means, sds, accept_z, give_up_after):
+    """What a selective-sequencing client does with the records [K, m] of a push: int8 [K, m], 1 = accept
+    (Z = (dist - mean[k]) / sd[k] <= accept_z, the scoring motifseq_panel takes), -1 = give up (not accepted and
+    n >= give_up_after), 0 = wait.  A NaN distance (calibrating, empty, degenerate) waits.  Host only."""
+    rec = np.asarray(rec)
+    means = np.asarray(means, dtype=np.float64).reshape(-1, *([1] * (rec.ndim - 1)))
+    sds = np.asarray(sds, dtype=np.float64).reshape(-1, *([1] * (rec.ndim - 1)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = (rec["dist"] - means) / sds
+        accept = z <= float(accept_z)                                 # (NaN compares false)
+    out = np.zeros(rec.shape, dtype=np.int8)
+    out[~accept & ~np.isnan(rec["dist"]) & (rec["n"] >= int(give_up_after))] = -1
+    out[accept] = 1
+    return out

@@ -2767,3 +2767,148 @@ int sk_hmm_segments_f64_len(const double *values, const int64_t *in_off, int32_t
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ MotifSeq sessions (sk_stream.hip)
+// Chunk-by-chunk search: the host forms check what the caller handed over, stage it in the session's own buffers and
+// run the device form; the records come back behind one synchronisation.
+namespace {
+
+int check_stream_slots(int32_t nslots, const int32_t *slots, int32_t m, std::vector<uint8_t> &seen)
+{
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m && !slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
+    seen.assign((size_t)nslots, 0);
+    for (int32_t i = 0; i < m; i++) {
+        if (slots[i] < 0 || slots[i] >= nslots)
+            return sk_fail(SK_ERR_INVALID, "slots[%d] = %d is outside [0, %d)", i, slots[i], nslots);
+        if (seen[(size_t)slots[i]]) return sk_fail(SK_ERR_INVALID, "slot %d appears twice in one call", slots[i]);
+        seen[(size_t)slots[i]] = 1;
+    }
+    return SK_OK;
+}
+
+// slots (and rows, len when given) to the session's staging, the device form, the records back
+int stream_host_call(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride,
+                     const int32_t *len, int flush, sk_stream_rec *out)
+{
+    int32_t nslots = 0, K = 0;
+    int rc = sk_stream_session_info(c, handle, &nslots, &K);
+    if (rc) return rc;
+    std::vector<uint8_t> seen;
+    if ((rc = check_stream_slots(nslots, slots, m, seen))) return rc;
+    if (m == 0) return SK_OK;
+    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
+    if (rows || !flush) {
+        if (!rows || !len) return sk_fail(SK_ERR_INVALID, "NULL rows/len");
+        if (stride <= 0) return sk_fail(SK_ERR_INVALID, "stride must be positive");
+        if ((rc = check_len_host(len, m, stride))) return rc;
+    }
+    void *d_slots, *d_rows = nullptr, *d_len = nullptr, *d_out;
+    const size_t ob = (size_t)m * (size_t)K * sizeof(sk_stream_rec);
+    if ((rc = sk_stream_session_stage(c, handle, 0, (size_t)m * sizeof(int32_t), &d_slots))) return rc;
+    if ((rc = sk_stream_session_stage(c, handle, 3, ob, &d_out))) return rc;
+    SK_HIP(hipMemcpyAsync(d_slots, slots, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (rows) {
+        if ((rc = sk_stream_session_stage(c, handle, 1, (size_t)m * (size_t)stride * sizeof(int16_t), &d_rows))) return rc;
+        if ((rc = sk_stream_session_stage(c, handle, 2, (size_t)m * sizeof(int32_t), &d_len))) return rc;
+        // only the samples of each row that count travel
+        int64_t longest = 0;
+        for (int32_t i = 0; i < m; i++) if (len[i] > longest) longest = len[i];
+        if (longest > 0)
+            SK_HIP(hipMemcpy2DAsync(d_rows, (size_t)stride * sizeof(int16_t), rows, (size_t)stride * sizeof(int16_t),
+                                    (size_t)longest * sizeof(int16_t), (size_t)m, hipMemcpyHostToDevice, c->stream));
+        SK_HIP(hipMemcpyAsync(d_len, len, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = sk_stream_session_push(c, handle, (const int32_t *)d_slots, m, (const int16_t *)d_rows, rows ? stride : 1,
+                                     (const int32_t *)d_len, flush, (sk_stream_rec *)d_out))) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_stream_open(const double *motifs, const int32_t *motif_off, int32_t nmotifs, const sk_stream_params *p,
+                   int32_t *handle)
+{
+    // the arguments are checked before the device is looked at
+    if (!p || !handle) return sk_fail(SK_ERR_INVALID, "NULL params/handle");
+    int rc = check_multi(motifs, motif_off, nmotifs, p->scale_mode);
+    if (rc) return rc;
+    for (int32_t k = 0; k < nmotifs; k++)
+        if (motif_off[k + 1] - motif_off[k] > 1024)
+            return sk_fail(SK_ERR_UNSUPPORTED, "motif %d has %d points: a session takes motifs of at most 1024", k,
+                           motif_off[k + 1] - motif_off[k]);
+    if (p->calib < 1 || p->calib > SK_STREAM_MAX_CALIB)
+        return sk_fail(SK_ERR_INVALID, "calib = %d is outside 1 .. %d", p->calib, SK_STREAM_MAX_CALIB);
+    if (p->nslots < 1 || p->nslots > 65536) return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. 65536", p->nslots);
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return sk_fail(SK_ERR_INVALID, "reserved words must be 0");
+    SK_ENTER(c);
+    sk_stream_params q = *p;
+    clamp_limits(&q.scale_low, &q.scale_hi);
+    return sk_stream_session_open(c, motifs, motif_off, nmotifs, &q, handle);
+}
+
+int sk_stream_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride,
+                       const int32_t *len, sk_stream_rec *out)
+{
+    SK_ENTER(c);
+    return stream_host_call(c, handle, slots, m, rows, stride, len, 0, out);
+}
+
+int sk_stream_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                           const int32_t *d_len, sk_stream_rec *d_out)
+{
+    SK_ENTER(c);
+    int rc = sk_stream_session_info(c, handle, nullptr, nullptr);
+    if (rc) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m == 0) return SK_OK;
+    if (!d_slots || !d_rows || !d_len || !d_out) return sk_fail(SK_ERR_INVALID, "NULL pointer");
+    if (stride <= 0) return sk_fail(SK_ERR_INVALID, "stride must be positive");
+    return sk_stream_session_push(c, handle, d_slots, m, d_rows, stride, d_len, 0, d_out);
+}
+
+int sk_stream_flush(int32_t handle, const int32_t *slots, int32_t m, sk_stream_rec *out)
+{
+    SK_ENTER(c);
+    return stream_host_call(c, handle, slots, m, nullptr, 0, nullptr, 1, out);
+}
+
+int sk_stream_reset(int32_t handle, const int32_t *slots, int32_t m, const double *center, const double *scale)
+{
+    SK_ENTER(c);
+    int32_t nslots = 0;
+    int rc = sk_stream_session_info(c, handle, &nslots, nullptr);
+    if (rc) return rc;
+    std::vector<uint8_t> seen;
+    if ((rc = check_stream_slots(nslots, slots, m, seen))) return rc;
+    if ((center == nullptr) != (scale == nullptr)) return sk_fail(SK_ERR_INVALID, "center and scale: both or neither");
+    for (int32_t i = 0; center && i < m; i++)
+        if (!isfinite(center[i]) || !isfinite(scale[i]) || scale[i] == 0.0)
+            return sk_fail(SK_ERR_INVALID, "slot %d: center %g / scale %g (both finite, scale not 0)", slots[i], center[i], scale[i]);
+    if (m == 0) return SK_OK;
+    void *d_slots, *d_cs = nullptr;
+    if ((rc = sk_stream_session_stage(c, handle, 0, (size_t)m * sizeof(int32_t), &d_slots))) return rc;
+    SK_HIP(hipMemcpyAsync(d_slots, slots, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (center) {
+        if ((rc = sk_stream_session_stage(c, handle, 2, 2 * (size_t)m * sizeof(double), &d_cs))) return rc;
+        SK_HIP(hipMemcpyAsync(d_cs, center, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        SK_HIP(hipMemcpyAsync((double *)d_cs + m, scale, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    rc = sk_stream_session_reset(c, handle, (const int32_t *)d_slots, m, (const double *)d_cs,
+                                 d_cs ? (const double *)d_cs + m : nullptr);
+    if (rc) return rc;
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_stream_close(int32_t handle)
+{
+    SK_ENTER(c);
+    return sk_stream_session_close(c, handle);
+}
+
+} // extern "C"

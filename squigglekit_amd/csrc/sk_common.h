@@ -154,6 +154,7 @@ struct sk_ctx {
     std::vector<double> motif_src;    // the motif it was built from (upload cache key, with motif_L)
     int    motif_L = 0;               // lanes per read of the layout in `motif`
     void  *comm = nullptr;            // ncclComm_t of this device (sk_comm.hip), or nullptr
+    void  *sessions[SK_STREAM_MAX_SESSIONS] = {};   // MotifSeq sessions of this context (sk_stream.hip), by handle
     sk_buf commbuf;                   // staging for the small host-side exchanges
 };
 
@@ -476,6 +477,23 @@ int sk_launch_hmm_paths(sk_ctx *c, int feed, const void *d_sig, int64_t stride, 
                         int first, sk_hmm_rec *d_rec, int64_t *d_off, sk_hmm_seg *d_seg, int64_t cap);
 int sk_launch_hmm_stats(sk_ctx *c, int feed, const void *d_sig, int64_t stride, const int64_t *d_roff, int32_t nreads,
                         const double *d_cal, const sk_hmm_model *m, const int64_t *d_off, void *d_seg, int64_t cap);
+
+// ---- MotifSeq sessions (sk_stream.hip) ----
+// The session behind the entry points of sk_api.hip: arguments checked there, every pointer a device pointer here.
+// open: motifs / motif_off on the host, limits already clamped.  push: one ingest, statistics of the slots whose
+// calibration ends in this call, one sweep per motif, the records to d_out [nmotifs][m]; rows == nullptr: no samples
+// (flush != 0: the named slots end their calibration).  reset: d_center / d_scale both nullptr or both [m].
+int sk_stream_session_open(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
+                           const sk_stream_params *p, int32_t *handle);
+int sk_stream_session_info(sk_ctx *c, int32_t handle, int32_t *nslots, int32_t *nmotifs);   // SK_ERR_INVALID: unknown handle
+int sk_stream_session_push(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows,
+                           int64_t stride, const int32_t *d_len, int flush, sk_stream_rec *d_out);
+int sk_stream_session_reset(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const double *d_center,
+                            const double *d_scale);
+// the session's staging room for the host entry points: `bytes` of device memory that lives until the next call
+int sk_stream_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
+int sk_stream_session_close(sk_ctx *c, int32_t handle);
+void sk_stream_close_all(sk_ctx *c);        // sk_shutdown: the context's device is current
 
 // ---- SquigglePull text (sk_pull.hip) ----
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries

@@ -4,7 +4,8 @@ lengths, strides, motif lengths, outlier limits, both scalings, segmenter parame
 segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the segmenter
 sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
 signal HMM with its state paths, segment levels, and the background and events twins of the hit family -- each against the
-reference tests/test_gpu_random.py uses.
+reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
+length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -20,9 +21,63 @@ os.environ["SK_TUNING"] = "1"      # this tool flips tuning switches
 sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
 import randcases                                      # noqa: E402
+import stream_ref                                     # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
+
+
+def session_round(rng):
+    """One drawn MotifSeq session: every record of every push (and of the closing flush) against
+    stream_ref.record on the samples pushed so far.  Returns None, or what differed."""
+    K = int(rng.integers(1, 4))
+    Ns = [int(rng.choice([1, 2, 16, 17, 31, 32, 33, 64, 65, 256, 257, 1024])) if rng.random() < 0.4
+          else int(rng.integers(1, 600)) for _ in range(K)]
+    nslots, W = int(rng.integers(1, 12)), int(rng.choice([1, 2, 17, 100, 500, 2000]))
+    lo, hi = [(0, 1200), (0, 900), (-50, 2500), (400, 650)][int(rng.integers(4))]
+    mode = ["medmad", "zscale"][int(rng.integers(2))]
+    n = int(rng.integers(1, 2500))
+    no_small = rng.random() < 0.5
+    desc = "K=%d N=%s slots=%d W=%d lo=%d hi=%d %s n=%d no_small=%s" % (K, Ns, nslots, W, lo, hi, mode, n, no_small)
+    if no_small:
+        os.environ["SK_DTW_NO_SMALL"] = "1"
+    motifs = [synth.synthetic_motif(N, seed=int(rng.integers(1000))) for N in Ns]
+    sig = synth.squiggle_batch(nslots, n, int(rng.integers(1 << 30)))
+    k = int(rng.integers(0, 60))
+    sig[rng.integers(0, nslots, k), rng.integers(0, n, k)] = rng.choice([-9, 0, 899, 900, 1199, 1200, 3000], k)
+    raw = [np.zeros(0, dtype=np.int16) for _ in range(nslots)]
+    at = [0] * nslots
+    try:
+        with api.MotifStream(motifs, nslots, mode, lo, hi, calib=W) as ms:
+            for final in (False, True):
+                while not final and min(at) < n:
+                    live = [s for s in range(nslots) if at[s] < n and rng.random() < 0.7]
+                    chunks = []
+                    for s in live:
+                        c = min(int(rng.choice([0, 1, 2, 15, 16, 17, 63, 64, 65, 200, 1000])), n - at[s])
+                        chunks.append(sig[s, at[s]:at[s] + c])
+                        raw[s] = np.concatenate([raw[s], chunks[-1]])
+                        at[s] += c
+                    if not live:
+                        continue
+                    rec = ms.push(live, chunks)
+                    for kk in range(K):
+                        for i, s in enumerate(live):
+                            want = stream_ref.record(raw[s], motifs[kk], W, mode, lo, hi, False)
+                            if not stream_ref.same(stream_ref.fields(rec[kk, i]), want):
+                                return "%s: slot %d motif %d after %d samples: got %s want %s" % (
+                                    desc, s, kk, len(raw[s]), stream_ref.fields(rec[kk, i]), want)
+                if final:
+                    rec = ms.flush(list(range(nslots)))
+                    for kk in range(K):
+                        for s in range(nslots):
+                            want = stream_ref.record(raw[s], motifs[kk], W, mode, lo, hi, True)
+                            if not stream_ref.same(stream_ref.fields(rec[kk, s]), want):
+                                return "%s: slot %d motif %d after the flush: got %s want %s" % (
+                                    desc, s, kk, stream_ref.fields(rec[kk, s]), want)
+    finally:
+        os.environ.pop("SK_DTW_NO_SMALL", None)
+    return None
 
 
 def main():
@@ -320,6 +375,11 @@ def main():
                 print("%s mismatch round %d %s: %s" % (fam.upper(), rounds, randcases.describe(case), msg))
             for key in randcases.SWITCHES:
                 os.environ.pop(key, None)
+        # ---- a MotifSeq session against the prefix statement (tests/stream_ref.py) ----
+        msg = session_round(rng)
+        if msg is not None:
+            bad += 1
+            print("SESSION mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
