@@ -264,6 +264,13 @@ struct sk_sdtw_args {
                                           // the writable c->comp / c->prep buffers
 };
 int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a);
+// (L, R) -- lanes per read, rows per lane -- of the exact single pass for a motif of N <= 1 024 points when `count` reads
+// (or (read, motif) pairs, or session slots) are swept at a time.  Every exact sweep takes its shape from here.
+void sk_exact_shape(int N, int64_t count, int *L, int *R);
+// the exact single pass over the `count` motifs of one (L, R) group of a panel in one grid (k_sdtw, MODE_PANEL): d_xlay
+// the panel's layouts, d_mt the group's table entries, motif k's record of read r -> d_all[k * out_stride + r]
+int sk_launch_sdtw_panel(sk_ctx *c, const sk_sdtw_args *a, int L, int R, const double *d_xlay, const sk_panel_motif *d_mt,
+                         int32_t count, sk_hit *d_all, int64_t out_stride);
 // the exact single pass that also stores every read's last row (cost, back-trace start) at r * max_len (sk_sdtw.hip)
 int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t *rowS);
 // hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]
@@ -328,7 +335,7 @@ int sk_launch_region_rows_f64(sk_ctx *c, const double *d_sig, const int64_t *d_s
 // `pairs`: reads x motifs the call will sweep at a time (chooses four reads or one read per wavefront).
 int sk_panel_plan(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs, const double *mean,
                   const double *sd, int64_t pairs);
-// k_panel_dtw over prepared reads (feed / samples / samples_raw / stride / off / prep / nreads / max_len of `base`) and
+// The exact sweep over prepared reads (feed / samples / samples_raw / stride / off / prep / nreads / max_len of `base`) and
 // every motif of the plan: motif k's record of read r -> d_all[k * out_stride + r].  motifs: the caller's (host), for
 // the chained launcher of the long ones.
 int sk_launch_panel_dtw(sk_ctx *c, const sk_sdtw_args *base, const double *motifs, const int32_t *motif_off,

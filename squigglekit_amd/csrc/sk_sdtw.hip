@@ -38,6 +38,8 @@
 //   CHAIN  FULL on one 1 024-row chunk of a longer motif (launch_chained).
 //   ROWS   FULL that also stores the last row, (D[N-1][j], S[N-1][j]) per column: the input of the hit lists
 //          (sk_hits.hip).  12 B per column against 8 VALU instructions per cell.
+//   PANEL  FULL over all (read, motif) pairs of a motif panel's shape group in one grid (sk_panel.hip): blockIdx.y
+//          picks the motif's entry of a device table -- where its layout lies, its short lanes, where its records go.
 #include "sk_sdtw_dev.h"
 #include <math.h>
 #include <stdlib.h>
@@ -63,19 +65,25 @@ void k_sdtw(const sdtw_kargs a)
     const int g = lane / L, l = lane % L;
     int slot = wave * G + g;
     int nreads = a.nreads;
-    if (a.gate_ptr) {                               // whole-call fallback: runs only when the guard raised an alarm
-        if (*a.gate_ptr == 0) return;               // (launch-uniform)
-        if (a.guard && blockIdx.x == 0 && threadIdx.x == 0) a.guard[SK_GUARD_FELLBACK] = 1;
-    }
-    if (a.count_ptr) {                              // retry pass: the list length is only known on the device
-        const int cnt = *a.count_ptr;
-        if (a.total_ptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.total_ptr, cnt);
-        nreads = min(cnt - a.list_off, a.nreads);
-        if (nreads <= 0) return;                    // (block-uniform) nothing listed for this launch
+    if constexpr (MODE != MODE_PANEL) {             // (the panel's grid is neither gated nor driven by a list)
+        if (a.gate_ptr) {                           // whole-call fallback: runs only when the guard raised an alarm
+            if (*a.gate_ptr == 0) return;           // (launch-uniform)
+            if (a.guard && blockIdx.x == 0 && threadIdx.x == 0) a.guard[SK_GUARD_FELLBACK] = 1;
+        }
+        if (a.count_ptr) {                          // retry pass: the list length is only known on the device
+            const int cnt = *a.count_ptr;
+            if (a.total_ptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.total_ptr, cnt);
+            nreads = min(cnt - a.list_off, a.nreads);
+            if (nreads <= 0) return;                // (block-uniform) nothing listed for this launch
+        }
     }
     const bool live = slot < nreads;
     if (!live) slot = nreads - 1;
-    const int r = a.ridx ? a.ridx[a.list_off + slot] : a.read0 + slot;
+    int r;
+    if constexpr (MODE == MODE_PANEL) r = slot;     // all reads, in order: no list, no chunking
+    else r = a.ridx ? a.ridx[a.list_off + slot] : a.read0 + slot;
+    sk_panel_motif mt = {};                         // PANEL: this block's motif (block-uniform: scalar loads)
+    if constexpr (MODE == MODE_PANEL) mt = a.mt[blockIdx.y];
 
     // ---- per-read parameters -------------------------------------------------
     int n, flags = 0;
@@ -122,8 +130,11 @@ void k_sdtw(const sdtw_kargs a)
     // ---- this lane's motif rows ------------------------------------------------
     double x[R];
 #pragma unroll
-    for (int k = 0; k < R; k++) x[k] = a.xlay[l * R + k];
-    const bool shortlane = l < a.P;
+    for (int k = 0; k < R; k++) {
+        if constexpr (MODE == MODE_PANEL) x[k] = a.xlay[mt.xoff + l * R + k];
+        else x[k] = a.xlay[l * R + k];
+    }
+    const bool shortlane = l < (MODE == MODE_PANEL ? mt.P : a.P);
 
     double D[R];
     int    S[R];
@@ -289,7 +300,8 @@ void k_sdtw(const sdtw_kargs a)
             else       { h.dist = __builtin_nan(""); h.start = -1; h.end = -1; }
             h.n = n;
             h.flags = flags;
-            a.out[a.out_by_slot ? a.list_off + slot : r] = h;
+            if constexpr (MODE == MODE_PANEL) a.out[(int64_t)mt.k * a.out_stride + r] = h;
+            else a.out[a.out_by_slot ? a.list_off + slot : r] = h;
         }
     }
 }
@@ -339,12 +351,9 @@ typedef void (*sdtw_fn)(const sdtw_kargs);
 template <int L, int FEED, int MODE>
 sdtw_fn pick_r(int R)
 {
-    switch (R) {
-#define SK_CASE(RR) case RR: return k_sdtw<L, RR, FEED, MODE>;
-        SK_CASE(1) SK_CASE(2) SK_CASE(3) SK_CASE(4) SK_CASE(5) SK_CASE(6) SK_CASE(7) SK_CASE(8)
-        SK_CASE(9) SK_CASE(10) SK_CASE(11) SK_CASE(12) SK_CASE(13) SK_CASE(14) SK_CASE(15) SK_CASE(16)
-#undef SK_CASE
-    }
+#define SK_KERNEL(RR) k_sdtw<L, RR, FEED, MODE>
+    switch (R) { SK_R_CASES_1_16(SK_KERNEL) }
+#undef SK_KERNEL
     return nullptr;
 }
 
@@ -412,13 +421,9 @@ static int launch_chained(sk_ctx *c, const sk_sdtw_args *a, double *finD = nullp
     if (!same) {
         SK_HIP(hipStreamSynchronize(c->stream));
         c->motif_host.assign(total, 0.0);
-        int row = 0;
-        for (int i = 0; i < nchunks; i++)
-            for (int l = 0; l < 64; l++) {
-                const int cnt = (l < Pc[i]) ? Rc[i] - 1 : Rc[i];
-                for (int k = 0; k < cnt; k++) c->motif_host[lay_off[i] + (size_t)l * Rc[i] + k] = a->motif[row++];
-            }
-        if (row != N) return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
+        for (int i = 0; i < nchunks; i++)           // (every chunk but the last holds CH rows)
+            if (!sk_lane_layout(a->motif + (size_t)i * CH, 64 * Rc[i] - Pc[i], 64, Rc[i], &c->motif_host[lay_off[i]]))
+                return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
         int rc = sk_reserve(c, &c->motif, total * sizeof(double));
         if (rc) return rc;
         SK_HIP(hipMemcpyAsync(c->motif.p, c->motif_host.data(), total * sizeof(double), hipMemcpyHostToDevice,
@@ -439,9 +444,7 @@ static int launch_chained(sk_ctx *c, const sk_sdtw_args *a, double *finD = nullp
     double  *bufD[2] = {(double *)c->ckpt.p, (double *)c->ckpt.p + (size_t)batch * row_stride};
     int32_t *bufS[2] = {(int32_t *)(bufD[1] + (size_t)batch * row_stride),
                         (int32_t *)(bufD[1] + (size_t)batch * row_stride) + (size_t)batch * row_stride};
-    sdtw_kargs k;
-    memset(&k, 0, sizeof k);
-    k.samples = a->samples; k.samples_raw = a->samples_raw; k.stride = a->stride; k.off = a->off; k.prep = a->prep;
+    sdtw_kargs k = kargs_of(a);
     k.out = a->out; k.last_row = nullptr; k.row_stride = row_stride;
     c->last_retry = 0;
     c->retry_dev = false;
@@ -491,19 +494,14 @@ static bool screens(const sk_sdtw_args *a, int span, int ck)
 // The laid-out motif stays resident between calls; re-upload only when it changes.
 static int upload_layout(sk_ctx *c, const double *motif, int N, int L, int R)
 {
-    const int P = L * R - N;
     const bool same = c->motif.p && c->motif_L == L && c->motif_src.size() == (size_t)N &&
                       memcmp(c->motif_src.data(), motif, (size_t)N * sizeof(double)) == 0;
     if (!same) {
         // the previous launch may still be reading the old layout
         SK_HIP(hipStreamSynchronize(c->stream));
-        c->motif_host.assign((size_t)L * R, 0.0);
-        int row = 0;
-        for (int l = 0; l < L; l++) {
-            int cnt = (l < P) ? R - 1 : R;
-            for (int k = 0; k < cnt; k++) c->motif_host[(size_t)l * R + k] = motif[row++];
-        }
-        if (row != N) return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
+        c->motif_host.resize((size_t)L * R);
+        if (!sk_lane_layout(motif, N, L, R, c->motif_host.data()))
+            return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
         int rc = sk_reserve(c, &c->motif, c->motif_host.size() * sizeof(double));
         if (rc) return rc;
         SK_HIP(hipMemcpyAsync(c->motif.p, c->motif_host.data(), c->motif_host.size() * sizeof(double),
@@ -516,8 +514,9 @@ static int upload_layout(sk_ctx *c, const double *motif, int N, int L, int R)
     return SK_OK;
 }
 
-// (L, R) of the exact single pass for a motif of N <= 1 024 points over `nreads` reads (the choice sk_launch_sdtw makes)
-static void exact_shape(int N, int32_t nreads, int *L, int *R)
+// (L, R) of the exact single pass for a motif of N <= 1 024 points over `count` reads, or (read, motif) pairs, swept at
+// a time: the one choice of sk_launch_sdtw, sk_launch_sdtw_rows, the panel's plan and the sessions
+void sk_exact_shape(int N, int64_t count, int *L, int *R)
 {
     if (N <= 16 * 16) { *L = 16; *R = (N + 15) / 16; }
     else              { *L = 64; *R = (N + 63) / 64; }
@@ -527,7 +526,7 @@ static void exact_shape(int N, int32_t nreads, int *L, int *R)
     // break-even near 4 096 reads.
     int small_max = 2048;
     if (const char *e = sk_tune("SK_DTW_SMALL_MAX")) { int v = atoi(e); if (v >= 0) small_max = v; }
-    if (*L == 16 && N >= 32 && nreads <= small_max && !sk_tune("SK_DTW_NO_SMALL")) { *L = 64; *R = (N + 63) / 64; }
+    if (*L == 16 && N >= 32 && count <= small_max && !sk_tune("SK_DTW_NO_SMALL")) { *L = 64; *R = (N + 63) / 64; }
 }
 
 // The exact single pass over a->nreads reads that also stores every read's last row: D[N-1][j] to rowD and the
@@ -542,17 +541,35 @@ int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t 
     if (a->fuse) return sk_fail(SK_ERR_INVALID, "internal: fused prologue without a screening pass");
     if (N > 64 * 16) return launch_chained(c, a, rowD, rowS);
     int L, R;
-    exact_shape(N, a->nreads, &L, &R);
+    sk_exact_shape(N, a->nreads, &L, &R);
     int rc = upload_layout(c, a->motif, N, L, R);
     if (rc) return rc;
-    sdtw_kargs k;
-    memset(&k, 0, sizeof k);
-    k.samples = a->samples; k.samples_raw = a->samples_raw; k.stride = a->stride; k.off = a->off; k.prep = a->prep;
+    sdtw_kargs k = kargs_of(a);
     k.nreads = a->nreads; k.read0 = 0; k.xlay = (const double *)c->motif.p; k.P = L * R - N;
     k.out = a->out; k.rowD = rowD; k.rowS = rowS; k.row_stride = a->max_len > 0 ? a->max_len : 1;
     sdtw_fn fn = pick_any(a->feed, L, R, MODE_ROWS);
     if (!fn) return sk_fail(SK_ERR_UNSUPPORTED, "no kernel for L=%d R=%d", L, R);
     return launch(c, fn, k, L);
+}
+
+// MODE_PANEL over the prepared reads of `a` (its motif fields are not read) and the `count` motifs of one (L, R) group
+// of the panel's plan: one grid, blockIdx.y = the motif's entry of d_mt, four wavefronts of reads per workgroup.
+int sk_launch_sdtw_panel(sk_ctx *c, const sk_sdtw_args *a, int L, int R, const double *d_xlay, const sk_panel_motif *d_mt,
+                         int32_t count, sk_hit *d_all, int64_t out_stride)
+{
+    sdtw_fn fn = nullptr;
+    if (a->feed == SK_FEED_I16)
+        fn = L == 16 ? pick_r<16, SK_FEED_I16, MODE_PANEL>(R) : pick_r<64, SK_FEED_I16, MODE_PANEL>(R);
+    else if (a->feed == SK_FEED_F64_NORM)
+        fn = L == 16 ? pick_r<16, SK_FEED_F64_NORM, MODE_PANEL>(R) : pick_r<64, SK_FEED_F64_NORM, MODE_PANEL>(R);
+    if (!fn) return sk_fail(SK_ERR_UNSUPPORTED, "no panel kernel for L=%d R=%d", L, R);
+    sdtw_kargs k = kargs_of(a);
+    k.nreads = a->nreads; k.xlay = d_xlay; k.mt = d_mt; k.out = d_all; k.out_stride = out_stride;
+    const int reads_per_block = 4 * (64 / L);
+    const dim3 grid((a->nreads + reads_per_block - 1) / reads_per_block, count);
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, c->stream, k);
+    SK_HIP(hipGetLastError());
+    return SK_OK;
 }
 
 int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a_in)
@@ -580,14 +597,12 @@ int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a_in)
     }
     if (N > 64 * 16) return launch_chained(c, a);   // more rows than a wavefront keeps in registers
     int L, R;
-    exact_shape(N, a->nreads, &L, &R);
+    sk_exact_shape(N, a->nreads, &L, &R);
     const int P = L * R - N;                 // short lanes (own R-1 rows), always < L
 
     if (int rc = upload_layout(c, a->motif, N, L, R)) return rc;
 
-    sdtw_kargs k;
-    memset(&k, 0, sizeof k);
-    k.samples = a->samples; k.samples_raw = a->samples_raw; k.stride = a->stride; k.off = a->off; k.prep = a->prep;
+    sdtw_kargs k = kargs_of(a);
     k.nreads = a->nreads; k.read0 = 0; k.ridx = nullptr; k.xlay = (const double *)c->motif.p; k.P = P;
     k.out = a->out; k.last_row = a->last_row;
 
@@ -653,16 +668,13 @@ int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a_in)
     // the motif laid out for 64 lanes (the short retry list is swept with a read per wavefront): uploaded here, ahead
     // of everything the call enqueues, because the early retry runs on another stream
     if (L == 16 && !c->motif64_valid && pick_any(a->feed, 64, (N + 63) / 64, MODE_FULL)) {
-        const int R64 = (N + 63) / 64, P64 = 64 * R64 - N;
+        const int R64 = (N + 63) / 64;
         SK_HIP(hipStreamSynchronize(c->stream));          // an earlier launch may still read it
         if (c->stream3) SK_HIP(hipStreamSynchronize(c->stream3));
         if (c->stream4) SK_HIP(hipStreamSynchronize(c->stream4));
-        c->motif64_host.assign((size_t)64 * R64, 0.0);
-        int row = 0;
-        for (int l = 0; l < 64; l++) {
-            const int rows = (l < P64) ? R64 - 1 : R64;
-            for (int kk = 0; kk < rows; kk++) c->motif64_host[(size_t)l * R64 + kk] = a->motif[row++];
-        }
+        c->motif64_host.resize((size_t)64 * R64);
+        if (!sk_lane_layout(a->motif, N, 64, R64, c->motif64_host.data()))
+            return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
         if ((rc = sk_reserve(c, &c->motif64, c->motif64_host.size() * sizeof(double)))) return rc;
         SK_HIP(hipMemcpyAsync(c->motif64.p, c->motif64_host.data(),
                               c->motif64_host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));

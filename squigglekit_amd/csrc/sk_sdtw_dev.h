@@ -2,6 +2,7 @@
 // (sk_sdtw.hip: exact FP64 passes; sk_sdtwq.hip: fixed-point screening pass + certified window).
 #pragma once
 #include "sk_common.h"
+#include <string.h>
 
 namespace {
 
@@ -13,7 +14,21 @@ constexpr int DPP_WAVE_SHL1 = 0x130;   // lane i <- lane i+1 across the wave; la
 constexpr int DPP_WAVE_ROL1 = 0x134;   // lane i <- lane i+1 across the wave (rotate)
 
 enum { MODE_FULL = 0, MODE_DIST = 1, MODE_START = 2, MODE_CHAIN = 3,   // CHAIN: FULL on one row chunk of a long motif
-       MODE_ROWS = 4 };                                                   // ROWS: FULL that also stores the last row (hit lists)
+       MODE_ROWS = 4,                                                     // ROWS: FULL that also stores the last row (hit lists)
+       MODE_PANEL = 5 };                                                  // PANEL: FULL over a table of motifs, one per blockIdx.y
+
+// `case 1: return X(1); ... case 16: return X(16);` (and 17 .. 32) inside a switch on R: X(RR) names the kernel
+// instantiated for RR rows per lane.  The one dispatch on R of every DTW kernel family.
+#define SK_R_CASES_1_16(X)                                                                                              \
+    case 1: return X(1);   case 2: return X(2);   case 3: return X(3);   case 4: return X(4);                           \
+    case 5: return X(5);   case 6: return X(6);   case 7: return X(7);   case 8: return X(8);                           \
+    case 9: return X(9);   case 10: return X(10); case 11: return X(11); case 12: return X(12);                         \
+    case 13: return X(13); case 14: return X(14); case 15: return X(15); case 16: return X(16);
+#define SK_R_CASES_17_32(X)                                                                                             \
+    case 17: return X(17); case 18: return X(18); case 19: return X(19); case 20: return X(20);                         \
+    case 21: return X(21); case 22: return X(22); case 23: return X(23); case 24: return X(24);                         \
+    case 25: return X(25); case 26: return X(26); case 27: return X(27); case 28: return X(28);                         \
+    case 29: return X(29); case 30: return X(30); case 31: return X(31); case 32: return X(32);
 
 // Fixed-point screening (sk_sdtwq.hip): one unit = 2^-22 of a normalised signal unit.
 constexpr int      QS     = 22;
@@ -123,6 +138,32 @@ struct sdtw_kargs {
     double        *rowD;        // [slot][row_stride] or nullptr (last chunk)
     int32_t       *rowS;
     int64_t        row_stride;
+    // MODE_PANEL: one grid over a group of motifs that share (L, R); xlay then holds the whole panel's layouts
+    const sk_panel_motif *mt;   // the group's table entries, indexed by blockIdx.y: layout offset, short lanes, motif index k
+    int64_t        out_stride;  // the record of (motif k, read r) goes to out[k * out_stride + r]
 };
+
+// The argument block of a launch over the prepared reads of `a`: zeroed but for the sample feed.
+inline sdtw_kargs kargs_of(const sk_sdtw_args *a)
+{
+    sdtw_kargs k;
+    memset(&k, 0, sizeof k);
+    k.samples = a->samples; k.samples_raw = a->samples_raw; k.stride = a->stride; k.off = a->off; k.prep = a->prep;
+    return k;
+}
+
+// The per-lane layout every DTW kernel reads its motif rows from, dst[L][R]: row 0 in slot 0 of lane 0, row N-1 in the
+// last slot of the last lane, the first P = L*R - N lanes one row short (their last slot is a pad: 0.0).
+// False when N rows do not fill L lanes that way.
+inline bool sk_lane_layout(const double *motif, int N, int L, int R, double *dst)
+{
+    const int P = L * R - N;
+    int row = 0;
+    for (int l = 0; l < L; l++) {
+        const int cnt = (l < P) ? R - 1 : R;
+        for (int k = 0; k < R; k++) dst[(size_t)l * R + k] = (k < cnt) ? motif[row++] : 0.0;
+    }
+    return row == N;
+}
 
 } // namespace

@@ -884,20 +884,14 @@ typedef void (*sdtw_fn)(const sdtw_kargs);
 template <int L, int FEED, int WHICH>
 sdtw_fn pick_r(int R)
 {
-#define SK_CASE(RR) case RR: return WHICH == 0 ? (sdtw_fn)k_sdtw_q<L, RR, FEED, false> : \
-                                   WHICH == 3 ? (sdtw_fn)k_sdtw_q<L, RR, FEED, (RR >= 2)> : \
-                                   WHICH == 1 ? (sdtw_fn)k_sdtw_p<L, RR, FEED> : (sdtw_fn)k_sdtw_w<L, RR, FEED>;
-    switch (R) {
-        SK_CASE(1) SK_CASE(2) SK_CASE(3) SK_CASE(4) SK_CASE(5) SK_CASE(6) SK_CASE(7) SK_CASE(8)
-        SK_CASE(9) SK_CASE(10) SK_CASE(11) SK_CASE(12) SK_CASE(13) SK_CASE(14) SK_CASE(15) SK_CASE(16)
-    }
+#define SK_KERNEL(RR) (WHICH == 0 ? (sdtw_fn)k_sdtw_q<L, RR, FEED, false> :     \
+                       WHICH == 3 ? (sdtw_fn)k_sdtw_q<L, RR, FEED, (RR >= 2)> : \
+                       WHICH == 1 ? (sdtw_fn)k_sdtw_p<L, RR, FEED> : (sdtw_fn)k_sdtw_w<L, RR, FEED>)
+    switch (R) { SK_R_CASES_1_16(SK_KERNEL) }
     if constexpr (L != 64) {
-        switch (R) {
-            SK_CASE(17) SK_CASE(18) SK_CASE(19) SK_CASE(20) SK_CASE(21) SK_CASE(22) SK_CASE(23) SK_CASE(24)
-            SK_CASE(25) SK_CASE(26) SK_CASE(27) SK_CASE(28) SK_CASE(29) SK_CASE(30) SK_CASE(31) SK_CASE(32)
-        }
+        switch (R) { SK_R_CASES_17_32(SK_KERNEL) }
     }
-#undef SK_CASE
+#undef SK_KERNEL
     return nullptr;
 }
 
@@ -1083,16 +1077,11 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
         SK_HIP(hipStreamSynchronize(c->stream));        // an earlier launch may still read the old one
         std::vector<unsigned> &layq = c->motifq_host;
         std::vector<double> &layw = c->motifw_host;
-        layq.assign((size_t)L * R, 0x80000000u);
-        layw.assign((size_t)L * R, 0.0);
-        int row = 0;
-        for (int l = 0; l < L; l++) {
-            const int cnt = (l < P) ? R - 1 : R;
-            for (int k = 0; k < cnt; k++, row++) {
-                layq[(size_t)l * R + k] = (unsigned)((int)rint(a->motif[row] * QSCALE)) + 0x80000000u;
-                layw[(size_t)l * R + k] = a->motif[row];
-            }
-        }
+        layq.resize((size_t)L * R);
+        layw.resize((size_t)L * R);
+        if (!sk_lane_layout(a->motif, N, L, R, layw.data())) return sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch");
+        for (size_t i = 0; i < layw.size(); i++)        // the quantised twin, slot by slot (a pad's 0.0 gives 0x80000000)
+            layq[i] = (unsigned)((int)rint(layw[i] * QSCALE)) + 0x80000000u;
         if ((rc = sk_reserve(c, &c->motifq, layq.size() * sizeof(unsigned)))) return rc;
         if ((rc = sk_reserve(c, &c->motifw, layw.size() * sizeof(double)))) return rc;
         SK_HIP(hipMemcpyAsync(c->motifq.p, layq.data(), layq.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
@@ -1146,9 +1135,7 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
     sdtw_fn fq = (sdtw_fn)pk(P == 0 ? 3 : 0, L, R), fp = (sdtw_fn)pk(1, L, R), fw = (sdtw_fn)pk(2, L, R);
     if (!fq || !fp || !fw) return sk_fail(SK_ERR_UNSUPPORTED, "no screening kernel for L=%d R=%d", L, R);
 
-    sdtw_kargs k;
-    memset(&k, 0, sizeof k);
-    k.samples = a->samples; k.samples_raw = a->samples_raw; k.stride = a->stride; k.off = a->off; k.prep = a->prep;
+    sdtw_kargs k = kargs_of(a);
     k.xlay = (const double *)c->motifw.p; k.xlayq = (const unsigned *)c->motifq.p; k.P = P; k.out = a->out;
     k.nck = nck; k.ck = ck; k.span = span; k.retry = d_retry; k.retry_cnt = d_retry_cnt;
     k.ckq = (unsigned *)c->ckpt.p; k.lastq = (unsigned *)c->lastq.p; k.lq_stride = (int64_t)lq_stride;

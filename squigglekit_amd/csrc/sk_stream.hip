@@ -21,6 +21,10 @@
 // Per push: k_stream_ingest (filter + compaction of the chunk, calibration buffer, counters), sk_launch_prep_i16 over
 // the buffered rows of the slots whose calibration ends (the statistics of the one-shot path, unchanged),
 // k_stream_adopt (their center / scale), one k_stream_sweep per motif, k_stream_emit (the records).  One stream.
+//
+// Host side shared with the one-shot path: a motif's (L, R) is sk_exact_shape's for nslots reads and its per-lane layout
+// is sk_lane_layout's, so a session's lanes hold the rows the one-shot sweep's lanes hold.  The sweep itself stays a
+// kernel of its own ("One text per thing").
 #include "sk_sdtw_dev.h"
 #include <math.h>
 #include <stdlib.h>
@@ -324,12 +328,9 @@ typedef void (*sweep_fn)(const stream_kargs);
 template <int L>
 sweep_fn pick_sweep_r(int R)
 {
-    switch (R) {
-#define SK_CASE(RR) case RR: return k_stream_sweep<L, RR>;
-        SK_CASE(1) SK_CASE(2) SK_CASE(3) SK_CASE(4) SK_CASE(5) SK_CASE(6) SK_CASE(7) SK_CASE(8)
-        SK_CASE(9) SK_CASE(10) SK_CASE(11) SK_CASE(12) SK_CASE(13) SK_CASE(14) SK_CASE(15) SK_CASE(16)
-#undef SK_CASE
-    }
+#define SK_KERNEL(RR) k_stream_sweep<L, RR>
+    switch (R) { SK_R_CASES_1_16(SK_KERNEL) }
+#undef SK_KERNEL
     return nullptr;
 }
 
@@ -369,17 +370,6 @@ stream_session *session_of(sk_ctx *c, int32_t handle)
     return (stream_session *)c->sessions[handle];
 }
 
-// (L, R) as sk_sdtw.hip's exact single pass chooses them for nslots reads: four slots per wavefront for motifs of up to
-// 256 points, unless the slots are few (SK_DTW_SMALL_MAX, default 2 048) -- then a slot per wavefront
-void stream_shape(int N, int32_t nslots, int *L, int *R)
-{
-    if (N <= 16 * 16) { *L = 16; *R = (N + 15) / 16; }
-    else              { *L = 64; *R = (N + 63) / 64; }
-    int small_max = 2048;
-    if (const char *e = sk_tune("SK_DTW_SMALL_MAX")) { int v = atoi(e); if (v >= 0) small_max = v; }
-    if (*L == 16 && N >= 32 && nslots <= small_max && !sk_tune("SK_DTW_NO_SMALL")) { *L = 64; *R = (N + 63) / 64; }
-}
-
 } // namespace
 
 int sk_stream_session_open(sk_ctx *c, const double *motifs, const int32_t *motif_off, int32_t nmotifs,
@@ -399,16 +389,12 @@ int sk_stream_session_open(sk_ctx *c, const double *motifs, const int32_t *motif
         stream_motif &mo = z->motifs[(size_t)k];
         const double *x = motifs + motif_off[k];
         mo.N = motif_off[k + 1] - motif_off[k];
-        stream_shape(mo.N, p->nslots, &mo.L, &mo.R);
+        sk_exact_shape(mo.N, p->nslots, &mo.L, &mo.R);     // the one-shot call's shape for nslots reads
         mo.P = mo.L * mo.R - mo.N;
         mo.fn = (mo.L == 16) ? pick_sweep_r<16>(mo.R) : pick_sweep_r<64>(mo.R);
         if (!mo.fn) { rc = sk_fail(SK_ERR_UNSUPPORTED, "no session kernel for L=%d R=%d", mo.L, mo.R); break; }
-        lay.assign((size_t)mo.L * mo.R, 0.0);
-        int row = 0;
-        for (int l = 0; l < mo.L; l++) {
-            const int cnt = (l < mo.P) ? mo.R - 1 : mo.R;
-            for (int kk = 0; kk < cnt; kk++) lay[(size_t)l * mo.R + kk] = x[row++];
-        }
+        lay.resize((size_t)mo.L * mo.R);
+        if (!sk_lane_layout(x, mo.N, mo.L, mo.R, lay.data())) { rc = sk_fail(SK_ERR_INVALID, "internal: motif layout mismatch"); break; }
         const size_t cells = (size_t)p->nslots * (size_t)mo.L * (size_t)mo.R;
         if ((rc = sk_reserve(c, &mo.xlay, lay.size() * sizeof(double)))) break;
         if ((rc = sk_reserve(c, &mo.D, cells * sizeof(double)))) break;

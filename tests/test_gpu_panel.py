@@ -274,3 +274,58 @@ def test_cli_region_with_hits_and_paths_equals_presliced_input(gpu, case, tmp_pa
         plain = run_cli(main, ["--i16", npy, "-m", bait, "--region=" + region])
         pre_plain = run_cli(main, ["--i16", str(pre), "-m", bait])
         assert plain[0].split("\n")[1:-1] == [w.replace("pre.npy", "p.npy", 1) + "\t%d" % lo for w in pre_plain[0].split("\n")[1:-1]]
+
+
+# ---- every seam of the pieces the panel shares with the first-match path, in one call --------------------------------
+SEAM_POINTS = (1, 15, 16, 17, 31, 32, 255, 256, 257, 1024, 1025)
+SEAM_REGION = (0, 300)
+
+
+@pytest.fixture(scope="module")
+def seams(ora):
+    """Eleven motifs around every lane and row boundary (1, 15 and 16 points share (L = 16, R = 1) with 15, 1 and 0 short
+    lanes: one grid with blockIdx.y > 0, a table entry of its own per motif, and a lane 0 that owns no row; 1 025 points
+    take the chained launcher) and seven reads -- not a multiple of four, so the last wavefront has dead lane groups --
+    of 0, 300 (every sample outside the limits), 1 and 64 .. 300 samples, as int16 rows and as float64 pA values; the
+    reference composition of both, computed once."""
+    from squigglekit_amd import synth
+    motifs = [synth.synthetic_motif(n, seed=40 + i) for i, n in enumerate(SEAM_POINTS)]
+    sig = synth.squiggle_batch(7, 1000, 4242, motif=motifs[4])[:, 700:]         # (behind the recipe's stall plateau)
+    ints = [sig[0, :0], np.full(300, 2000, dtype=np.int16), sig[2, :1], sig[3, :64], sig[4, :137], sig[5, :211], sig[6, :300]]
+    flts = [np.round((x.astype(np.int64) + 16.0) * (1493.94 / 8192.0), 2) for x in ints]
+    flts[1] = np.full(300, 2000.25)
+    assert [x.size for x in ints] == [0, 300, 1, 64, 137, 211, 300]
+    return motifs, {"int16": ints, "float64": flts}, {k: reference_panel(ora, v, motifs, SEAM_REGION)
+                                                      for k, v in (("int16", ints), ("float64", flts))}
+
+
+@pytest.mark.parametrize("route", ["int16", "float64"])
+@pytest.mark.parametrize("no_small", [False, True])
+def test_every_seam_of_the_shared_sweep(gpu, seams, monkeypatch, no_small, route):
+    """77 (read, motif) pairs, far below the 256 reads at which a group is delegated to the screening path: the one-grid
+    kernel, under both lane layouts (SK_DTW_NO_SMALL: motifs of up to 256 points stay at 16 lanes, R up to 16; unset:
+    32 points and more spread over 64 lanes).  Every record equals (a) the reference composition and (b), field for
+    field, what the first-match entry point returns for the same windows -- the same kernel in another mode (int16:
+    motifseq_multi_batch on region_rows; float64: motifseq_multi_ragged_f64 on the sliced reads)."""
+    from squigglekit_amd import api
+    if no_small:
+        monkeypatch.setenv("SK_DTW_NO_SMALL", "1")
+    motifs, reads, refs = seams
+    mean, sd = model_terms(motifs)
+    if route == "int16":
+        sig, lens = api.pack_i16(reads[route])
+        got = api.motifseq_panel_batch(sig, lens, motifs, mean, sd, region=SEAM_REGION, records=True)
+        rows, wlen, frm = api.region_rows(sig, lens, SEAM_REGION)
+        first = api.motifseq_multi_batch(rows, wlen, motifs)
+        assert np.array_equal(frm, got[1])
+    else:
+        got = api.motifseq_panel_ragged_f64(*api.pack_f64(reads[route]), motifs, mean, sd, region=SEAM_REGION, records=True)
+        first = api.motifseq_multi_ragged_f64(*api.pack_f64([x[slice(*SEAM_REGION)] for x in reads[route]]), motifs)
+    same(got, refs[route], (route, no_small))
+    assert len(got[2]) == len(first) == len(SEAM_POINTS)
+    for k, (g, f) in enumerate(zip(got[2], first)):
+        tag = (route, no_small, SEAM_POINTS[k])
+        nan = np.isnan(g["dist"])
+        assert np.array_equal(nan, np.isnan(f["dist"])) and np.array_equal(bits(g["dist"][~nan]), bits(f["dist"][~nan])), tag
+        for field in ("start", "end", "n", "flags"):
+            assert np.array_equal(g[field], f[field]), (tag, field)
