@@ -87,6 +87,8 @@ static const sk_tunable SK_TUNABLES[] = {
     {"SK_DTW_SPAN2",          "0 500",       "look-back of the window pass's second tier (0: none)"},
     {"SK_DTW_CK",             "64 256",      "steps between checkpoints of the screening pass (multiple of 64)"},
     {"SK_DTW_NOSORT",         "1",           "window passes take the reads in file order"},
+    {"SK_DTW_NOHINT",         "1",           "no start hint: the plain screening sweep, every read's exact window looks back the same number of columns"},
+    {"SK_DTW_HINT_MIN",       "1",           "the start hint is on for calls of at least this many reads (default 500000)"},
     {"SK_DTW_SORT_MIN",       "1",           "window passes sort chunks of at least this many reads"},
     {"SK_DTW_NO_EARLY",       "1",           "no early exact retry beside the window passes"},
     {"SK_DTW_NO_SIBLINGS",    "1",           "reads whose candidate columns fall into two clusters take the exact pass (no second window)"},

@@ -141,6 +141,9 @@ struct sdtw_kargs {
     // MODE_PANEL: one grid over a group of motifs that share (L, R); xlay then holds the whole panel's layouts
     const sk_panel_motif *mt;   // the group's table entries, indexed by blockIdx.y: layout offset, short lanes, motif index k
     int64_t        out_stride;  // the record of (motif k, read r) goes to out[k * out_stride + r]
+    // tagged screening sweep (k_sdtw_qh): the longest path in cells, N + n + 2 -- qerr is 2^T times that there, and the
+    // image-error guard is about the path length
+    unsigned       qplen;
 };
 
 // The argument block of a launch over the prepared reads of `a`: zeroed but for the sample feed.

@@ -114,9 +114,53 @@ __device__ __forceinline__ unsigned shr0(unsigned v, unsigned notfirst)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The start hint (k_sdtw_qh / k_sdtw_ph; DESIGN.md 4.3, "start hint")
+// ---------------------------------------------------------------------------------------------
+// Pass W gives every read the same look-back of `span` columns before its first candidate column, wide enough for the
+// reads that carry a copy of the motif (paths about 0.98 N wide); the others (paths 0.39 N wide at the median) pay for
+// columns their path never visits.  The tagged sweep tells the two apart at no cost per cell: every sample and motif
+// image is truncated to a multiple of 2^T units, so |x - y| is one too and neither v_sad_u32 nor v_min3_u32 touches the
+// low T bits of a cost word -- and lane 0's virtual row -1, all zeros in k_sdtw_q, holds
+// tag(j) = (j >> G) & (2^T - 1) in column j.  A cell then arrives with the tag of the granule (2^G columns) in which its
+// own fixed-point path left row -1; pass Q's epilogue decodes the tags of the candidate columns (the latest granule at or
+// before the column, i.e. modulo 2^(T+G) columns), and the pre-roll restarts MARGIN columns before the earliest of them
+// instead of at jlo - span.
+//   E' : a truncated image is 0 .. 2^T - 1 units below the rounded one, so a local cost moves by at most 2^T - 1 units on
+//        top of the one unit of k_sdtw_q's derivation (file header): at most 2^T units per cell, N + n cells, and the
+//        row -1 entry adds its tag, at most 2^T - 1, once.  E' = 2^T (N + n + 2) + 2^T - 1 (the "+ 2" keeps the slack of
+//        E, scaled), and it is a.qerr for the whole launch set: the interval rule, the candidate rule, the lower bounds
+//        of pass W and its premise test.  The pre-roll runs on UNtruncated images from a truncated checkpoint: a cell it
+//        computes is at most (restored cell + the path's costs + one unit per cell) <= exact + E', as before.
+//   The hint is only a hint: a path that starts before the restart column reaches a restored cell, S = -1, and the read
+//   goes to the second tier with its fixed look-back -- whether the tag wrapped (a path wider than 2^(T+G) columns), the
+//   exact path starts earlier than the fixed-point one by more than MARGIN, or anything else.  tests/test_hint_model.py
+//   checks E' and the tags cell by cell.
+constexpr int HINT_T = 5, HINT_G = 4, HINT_MARGIN = 8;
+constexpr int HINT_MAX_PLEN = 8192;                    // longest path (N + n + 2 cells) the hint is switched on for,
+constexpr int HINT_MIN_READS = 500000;                 // smallest call (see sk_launch_sdtw_screen)
+constexpr int HINT_MAX_R = 25;                         // and most rows per lane (beyond: k_sdtw_qh spills up to twice what k_sdtw_q does)
+constexpr unsigned HINT_MASK = (1u << HINT_T) - 1u;
+
+// shr0 for the tagged sweep: a group's lane 0 gets `tag` -- its virtual row -1 -- where shr0 hands it 0.  One
+// v_cndmask_b32_dpp in the place of shr0<8>'s v_and_b32_dpp (the same issue class: profiles/r06_valu_rate.txt); its lane
+// mask goes to VCC right in front of it, by two scalar moves that are also the two wait states between the VALU write of
+// v and its DPP read (the s_nop 1 of shr0<8>), so the compiler keeps VCC for itself between the steps.
+template <int L>
+__device__ __forceinline__ unsigned shrtag(unsigned v, unsigned tag)
+{
+    static_assert(L == 8 || L == 16, "groups of 8 or 16 lanes in DPP rows of 16");
+    unsigned r;
+    asm("s_mov_b32 vcc_lo, %3\n\t"
+        "s_mov_b32 vcc_hi, %3\n\t"
+        "v_cndmask_b32_dpp %0, %1, %2, vcc row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+        : "=v"(r) : "v"(v), "v"(tag), "i"(L == 8 ? 0x01010101 : 0x00010001) : "vcc");
+    return r;
+}
+
 // the restart point of one read, handed from pass P to pass W
 struct wrec {
-    int32_t tbase;      // first step of the exact recurrence
+    int32_t tbase;      // first step of the exact recurrence (pass Q's epilogue -> k_sdtw_ph: the column to restart at)
     int32_t jlo, jhi;   // candidate columns
     int32_t flags;      // 1: screened (a window exists)  2: the state was restored from a checkpoint
 };
@@ -163,6 +207,35 @@ __device__ __forceinline__ void candidate_columns(const sdtw_kargs &a, int r, in
     jlo_out = jlo; jhi_out = jhi;
 }
 
+// The start hint of read r (tagged sweep): over the candidate columns j in [jlo, jhi] (found as candidate_columns finds
+// them; jlo <= jhi, both inside the read), the first column of the latest granule at or before j that carries the tag in
+// the low bits of j's cost word; the minimum over them.  Every lane of the read's group calls this and gets the result.
+template <int L>
+__device__ __forceinline__ int hint_start(const sdtw_kargs &a, int r, unsigned b, int l, int jlo, int jhi)
+{
+    const unsigned *lastq = a.lastq + (int64_t)(r - a.read0) * a.lq_stride;
+    const unsigned *ls = a.lsum + (int64_t)(r - a.read0) * (a.nck + 1) * L + l;
+    const unsigned thr = (b > QINF - 2u * a.qerr) ? QINF : b + 2u * a.qerr;
+    int hs = 0x7fffffff;
+    // (interval cc holds the columns cc * ck - (L - 1) .. cc * ck + ck - 1)
+    for (int cc = jlo / a.ck; cc <= min(a.nck, (jhi + L - 1) / a.ck); cc++) {
+        if (ls[(int64_t)cc * L] > thr) continue;
+        const int j0 = cc * a.ck + l - (L - 1);
+        for (int q = 0; q < a.ck / L; q++) {
+            const int j = j0 + q * L;
+            if (j < jlo || j > jhi) continue;
+            const unsigned w = lastq[j + L];                              // (rows start L early)
+            if (w > thr) continue;
+            const int gj = j >> HINT_G;
+            const int gs = gj - (int)((unsigned)(gj - (int)(w & HINT_MASK)) & HINT_MASK);
+            hs = min(hs, max(gs, 0) << HINT_G);
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < L; d <<= 1) hs = min(hs, __shfl_xor(hs, d));
+    return hs;
+}
+
 // ---------------------------------------------------------------------------------------------
 // pass Q
 // ---------------------------------------------------------------------------------------------
@@ -170,11 +243,24 @@ __device__ __forceinline__ void candidate_columns(const sdtw_kargs &a, int r, in
 #define SK_Q_WAVES(R) 4    /* four waves per SIMD (128 VGPRs): R <= 32 rows of 3 words + the feed; the little that does not fit is spilled from the cold ends of the kernel */
 #endif
 // P0: every lane owns R rows (the motif fills L x R slots exactly): no short-lane select after the column
+// HINT: the tagged sweep ("start hint" above).  sk_sdtwq_hint.hip compiles this kernel as k_sdtw_qh with HINT = true,
+// every other translation unit as k_sdtw_q with HINT = false -- one text, and k_sdtw_q compiles to what it was.
+#ifdef SK_SDTWQ_HINT
+#define SK_Q_KERNEL k_sdtw_qh
+#define SK_P_KERNEL k_sdtw_ph
+constexpr bool HINT = true;
+#else
+#define SK_Q_KERNEL k_sdtw_q
+#define SK_P_KERNEL k_sdtw_p
+constexpr bool HINT = false;
+#endif
 template <int L, int R, int FEED, bool P0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SK_Q_WAVES(R), 8)))
-void k_sdtw_q(const sdtw_kargs a)
+void SK_Q_KERNEL(const sdtw_kargs a)
 {
     static_assert(L == 8 || L == 16 || L == 64, "lanes per read");
+    static_assert(!HINT || (FEED == SK_FEED_I16 && L <= (1 << HINT_G) && (1 << HINT_G) % L == 0),
+                  "tagged sweep: int16 feed, a block of L steps inside one granule");
     constexpr int G = 64 / L;
     constexpr int CKH = (R + 3) / 2;                // dwords per lane and checkpoint: R + 2 state words, their high halves
     constexpr int U = (L < 16) ? L : 16;            // steps per unrolled run (y values prefetched from LDS)
@@ -257,9 +343,10 @@ void k_sdtw_q(const sdtw_kargs a)
 
     unsigned xq[R];
 #pragma unroll
-    for (int k = 0; k < R; k++) xq[k] = a.xlayq[l * R + k];
+    for (int k = 0; k < R; k++) xq[k] = HINT ? (a.xlayq[l * R + k] & ~HINT_MASK) : a.xlayq[l * R + k];
     const bool shortlane = l < a.P;
     const unsigned notfirst = (l == 0) ? 0u : 0xffffffffu;
+    [[maybe_unused]] unsigned tagv = 0;             // HINT: tag of the granule lane 0's column is in
 
     unsigned Da[R], Db[R];                          // ping-pong: a column reads one, writes the other
 #pragma unroll
@@ -302,7 +389,8 @@ void k_sdtw_q(const sdtw_kargs a)
         double imgerr = 0.0;
         if (FEED == SK_FEED_I16 || fma64)            imgerr = 3.8e-7 + fabs(center) * qa * 1.2e-16;
         else if constexpr (FEED == SK_FEED_F64_NORM) imgerr = 5.7e-7;
-        const bool rej = !(imgerr * (double)a.qerr <= 1.0) && a.hole != SK_HOLE_FMA64_UNGUARDED;   // (NaN: rejected)
+        // (the tagged sweep's a.qerr is E' = 2^T times the path length: the bound is about the path length)
+        const bool rej = !(imgerr * (double)(HINT ? a.qplen : a.qerr) <= 1.0) && a.hole != SK_HOLE_FMA64_UNGUARDED;   // (NaN: rejected)
         if (rej) {
             bad = 1;
             if (l == 0 && a.guard) atomicAdd(&a.guard[SK_GUARD_IMGREJ], 1);
@@ -315,7 +403,8 @@ void k_sdtw_q(const sdtw_kargs a)
         else if constexpr (FEED == SK_FEED_F64_NORM) t = fma64 ? __builtin_fma(raw, qa, qb) : (raw - center) * qa;
         else                                         t = raw * QSCALE;
         const bool ok = fabs(t) < QLIM * QSCALE;     // false for NaN / inf too
-        const unsigned q = (unsigned)__double2loint(t + 6755399441055744.0) ^ 0x80000000u;
+        unsigned q = (unsigned)__double2loint(t + 6755399441055744.0) ^ 0x80000000u;
+        if constexpr (HINT) q &= ~HINT_MASK;        // truncated to a multiple of 2^T units
         const bool in = idx < n;
         bad |= (in && !ok) ? 1 : 0;
         return (in && ok) ? q : QINF;
@@ -343,7 +432,9 @@ void k_sdtw_q(const sdtw_kargs a)
     unsigned F = toq(loadraw(l), l);
     // one step: lane l-1's bottom row comes in by DPP, run the column old -> nw
     auto step = [&](const unsigned (&old)[R], unsigned (&nw)[R], unsigned yq, unsigned *hslot) {
-        const unsigned upq = shr0<L>(botq, notfirst);
+        unsigned upq;
+        if constexpr (HINT) upq = shrtag<L>(botq, tagv);
+        else                upq = shr0<L>(botq, notfirst);
         qcolumn<R>(old, nw, xq, yq, diagq, upq);
         diagq = upq;
         // (a bit select, v_bitop3_b32: 2 cycles of issue against v_cndmask's 4)
@@ -394,6 +485,7 @@ void k_sdtw_q(const sdtw_kargs a)
             ioff = 0;
         }
         unsigned *hw = (l == L - 1) ? ibuf + ioff : dump;             // every other lane writes to a dump row
+        if constexpr (HINT) tagv = (unsigned)(t0 >> HINT_G) & HINT_MASK;   // lane 0 sits on columns t0 .. t0 + L - 1: one granule
         const unsigned *yr;
         if (blk & 1) { ybuf[L + l] = F; yr = ybuf + L - l; }
         else         { ybuf[l] = F; ybuf[2 * L + l] = F; yr = ybuf + 2 * L - l; }
@@ -464,9 +556,21 @@ void k_sdtw_q(const sdtw_kargs a)
                 if (slot_ok) { jhi = ahi; sjlo = blo; sjhi = bhi; }
             }
         }
+        // HINT: where the pre-roll is to restart -- MARGIN columns before the earliest start the candidate columns' tags
+        // decode to; jlo - span as ever where there is nothing to decode, and for a read with a sibling: the second tier
+        // looks at ALL its candidates again, finds them too far apart and sends it to the exact pass, so a hint that is
+        // too short would cost such a read a whole sweep
+        int tx = 0;
+        if constexpr (HINT) {
+            tx = max(0, jlo - a.span);
+            if (live && bq < QSAFE && jhi >= jlo && jhi - jlo <= a.wmax && sjhi < sjlo) {   // (group-uniform)
+                const int hs = hint_start<L>(a, r, bq, l, jlo, jhi);
+                if (hs <= jlo) tx = min(max(hs - HINT_MARGIN, 0), max(jlo - 1, 0));
+            }
+        }
         if (live && l == 0) {
             wrec w;
-            w.tbase = 0; w.jlo = jlo; w.jhi = jhi; w.flags = (sjhi >= sjlo) ? 4 : 0;      // 4: the read has a sibling
+            w.tbase = tx; w.jlo = jlo; w.jhi = jhi; w.flags = (sjhi >= sjlo) ? 4 : 0;     // 4: the read has a sibling
             ((wrec *)a.wrec_q)[r - a.read0] = w;
             // a read the window passes cannot take (no usable minimum, candidates too far apart) goes to the exact
             // retry -- which starts now, beside the window passes, instead of behind them
@@ -483,9 +587,10 @@ void k_sdtw_q(const sdtw_kargs a)
 // ---------------------------------------------------------------------------------------------
 // pass P: candidate columns, restart point, fixed-point pre-roll
 // ---------------------------------------------------------------------------------------------
+// HINT (k_sdtw_ph): the first tier behind the tagged sweep -- the restart column comes from pass Q's epilogue record
 template <int L, int R, int FEED>
 __global__ __launch_bounds__(256)
-void k_sdtw_p(const sdtw_kargs a)
+void SK_P_KERNEL(const sdtw_kargs a)
 {
     constexpr int G = 64 / L;
     constexpr int CKW = R + 2;
@@ -527,9 +632,10 @@ void k_sdtw_p(const sdtw_kargs a)
     // latency that the other waves' sweeps hide); a second-tier launch looks again (its reads come from a list).
     const unsigned b = (unsigned)a.qflag[r - a.read0];   // the screening minimum (pass Q), QINF: not usable
     int jlo, jhi, clustered = 0;                    // clustered: this window holds one of two clusters of candidates
+    [[maybe_unused]] int txq = 0;                   // HINT: pass Q's restart column
     if (!a.tier2) {
         const wrec q = ((const wrec *)a.wrec_q)[r - a.read0];
-        jlo = q.jlo; jhi = q.jhi; clustered = q.flags & 4;
+        jlo = q.jlo; jhi = q.jhi; clustered = q.flags & 4; txq = q.tbase;
     } else if (a.tier2 == 2) {                      // a read's second cluster (sibling list, pass Q's epilogue)
         const sibrec q = ((const sibrec *)a.sib)[slot];
         jlo = q.jlo; jhi = q.jhi; clustered = 4;
@@ -540,7 +646,8 @@ void k_sdtw_p(const sdtw_kargs a)
 
     int tbase = 0, c0 = 0, npre = 0;
     if (screened) {
-        const int tx = max(0, jlo - a.span);        // where the exact recurrence has to start
+        // where the exact recurrence has to start
+        const int tx = (HINT && !a.tier2) ? min(max(txq, 0), jlo) : max(0, jlo - a.span);
         c0 = tx / a.ck;
         if (c0 > a.nck) c0 = a.nck;
         tbase = c0 * a.ck;
@@ -884,9 +991,14 @@ typedef void (*sdtw_fn)(const sdtw_kargs);
 template <int L, int FEED, int WHICH>
 sdtw_fn pick_r(int R)
 {
-#define SK_KERNEL(RR) (WHICH == 0 ? (sdtw_fn)k_sdtw_q<L, RR, FEED, false> :     \
-                       WHICH == 3 ? (sdtw_fn)k_sdtw_q<L, RR, FEED, (RR >= 2)> : \
-                       WHICH == 1 ? (sdtw_fn)k_sdtw_p<L, RR, FEED> : (sdtw_fn)k_sdtw_w<L, RR, FEED>)
+#ifndef SK_SDTWQ_HINT
+#define SK_KERNEL(RR) (WHICH == 0 ? (sdtw_fn)SK_Q_KERNEL<L, RR, FEED, false> :     \
+                       WHICH == 3 ? (sdtw_fn)SK_Q_KERNEL<L, RR, FEED, (RR >= 2)> : \
+                       WHICH == 1 ? (sdtw_fn)SK_P_KERNEL<L, RR, FEED> : (sdtw_fn)k_sdtw_w<L, RR, FEED>)
+#else       /* the tagged sweep and its pre-roll (pass W is the plain scheme's) */
+#define SK_KERNEL(RR) (WHICH == 0 ? (sdtw_fn)SK_Q_KERNEL<L, RR, FEED, false> :     \
+                       WHICH == 3 ? (sdtw_fn)SK_Q_KERNEL<L, RR, FEED, (RR >= 2)> : (sdtw_fn)SK_P_KERNEL<L, RR, FEED>)
+#endif
     switch (R) { SK_R_CASES_1_16(SK_KERNEL) }
     if constexpr (L != 64) {
         switch (R) { SK_R_CASES_17_32(SK_KERNEL) }
@@ -900,13 +1012,19 @@ sdtw_fn pick_l(int L, int R)
 {
     if (L == 8)  return pick_r<8, FEED, WHICH>(R);
     if (L == 16) return pick_r<16, FEED, WHICH>(R);
+#ifndef SK_SDTWQ_HINT
     return pick_r<64, FEED, WHICH>(R);
+#else
+    return nullptr;                                     // (no tagged sweep with a read per wavefront)
+#endif
 }
 
 } // namespace
 
 // (which: 0 = Q, 1 = P, 2 = W)
-#if SK_SDTWQ_FEED == 0
+#if defined(SK_SDTWQ_HINT)
+void *sk_sdtwq_pick_hint(int which, int L, int R)       // (k_sdtw_qh for 0 / 3, k_sdtw_ph for 1)
+#elif SK_SDTWQ_FEED == 0
 void *sk_sdtwq_pick_feed0(int which, int L, int R)
 #elif SK_SDTWQ_FEED == 1
 void *sk_sdtwq_pick_feed1(int which, int L, int R)
@@ -918,13 +1036,18 @@ void *sk_sdtwq_pick_feed2(int which, int L, int R)
     case 0: return (void *)pick_l<0, SK_SDTWQ_FEED>(L, R);
     case 1: return (void *)pick_l<1, SK_SDTWQ_FEED>(L, R);
     case 3: return (void *)pick_l<3, SK_SDTWQ_FEED>(L, R);       // pass Q without short lanes
+#ifndef SK_SDTWQ_HINT
     default: return (void *)pick_l<2, SK_SDTWQ_FEED>(L, R);
+#else
+    default: return nullptr;
+#endif
     }
 }
 
 #ifdef SK_SDTWQ_MAIN
 void *sk_sdtwq_pick_feed1(int which, int L, int R);
 void *sk_sdtwq_pick_feed2(int which, int L, int R);
+void *sk_sdtwq_pick_hint(int which, int L, int R);
 
 // lanes per read of the screening scheme for an N-point motif (SK_DTW_QL = 8 / 16 / 64: A/B runs).  The long lanes
 // of L = 8 pay off once the batch fills the chip with them (8 reads per wavefront: measured 1.75 / 1.45 / 1.50 ms
@@ -959,6 +1082,7 @@ struct order_args {
     const wrec    *rec;                                // pass Q's epilogue records, [read - read0]
     const int32_t *qflag;
     int nreads, read0, span, ck, nck, L, wmax;
+    int hint;                                          // the records hold the restart column (tagged sweep, k_sdtw_ph)
     int32_t *hist;                                     // [ORDER_BINS] counts, then (in place) running cursors
     int32_t *order;                                    // out: read indices (absolute), sorted by key
 };
@@ -971,7 +1095,7 @@ __device__ __forceinline__ int order_key(const order_args &a, int i)
     // wavefronts to start were the longest-running ones; in descending order the short ones fill the tail of the launch
     // (window passes 2.03 -> 1.78 ms at 125 000 reads per call, 12.1 -> 11.9 at 1 M).
     if (!((b < QSAFE) && (q.jhi >= q.jlo) && (q.jhi - q.jlo <= a.wmax))) return ORDER_BINS - 1;   // not screened: no work in P / W, last
-    const int tx = max(0, q.jlo - a.span);             // (pass P's arithmetic)
+    const int tx = a.hint ? min(max(q.tbase, 0), q.jlo) : max(0, q.jlo - a.span);   // (pass P's arithmetic)
     int c0 = tx / a.ck;
     if (c0 > a.nck) c0 = a.nck;
     const int npre = c0 > 0 ? (tx - c0 * a.ck) / a.L : 0;
@@ -1133,7 +1257,22 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
     const pick_fn pk = a->feed == SK_FEED_I16 ? (pick_fn)sk_sdtwq_pick_feed0
                      : a->feed == SK_FEED_F64_NORM ? (pick_fn)sk_sdtwq_pick_feed1 : (pick_fn)sk_sdtwq_pick_feed2;
     sdtw_fn fq = (sdtw_fn)pk(P == 0 ? 3 : 0, L, R), fp = (sdtw_fn)pk(1, L, R), fw = (sdtw_fn)pk(2, L, R);
-    if (!fq || !fp || !fw) return sk_fail(SK_ERR_UNSUPPORTED, "no screening kernel for L=%d R=%d", L, R);
+    // The start hint ("start hint" above): the tagged sweep and, in the first tier, the pre-roll that takes its restart
+    // column.  int16 reads over 8 or 16 lanes.  What it saves grows with the number of reads (a third of the first
+    // tier's window columns); what it costs does not: E' is 2^T times E, so more reads have candidate columns in two or
+    // three places (second windows, early exact retries) and a read in a thousand outruns its hint (second tier) --
+    // rounds that were all but empty and now each take their latency, about 0.45 ms per call (slower
+    // below 125 000 reads, level at 250 000, faster from 500 000 on, 163 and 200 points x 4 000 samples).  So: calls of
+    // at least HINT_MIN_READS reads (SK_DTW_HINT_MIN), paths of up to HINT_MAX_PLEN cells and HINT_MAX_R rows per lane
+    // -- E' in signal units grows with the path length, and nobody measured beyond (SK_DTW_NOHINT=1: off everywhere).
+    const int64_t plen = (int64_t)N + maxlen + 2;
+    int64_t hint_min = HINT_MIN_READS;
+    if (const char *e = sk_tune("SK_DTW_HINT_MIN")) { const int v = atoi(e); if (v > 0) hint_min = v; }   // (tests: small batches too)
+    const bool hint = a->feed == SK_FEED_I16 && (L == 8 || L == 16) && plen <= HINT_MAX_PLEN && R <= HINT_MAX_R &&
+                      a->nreads >= hint_min && sk_tune("SK_DTW_NOHINT") == nullptr;
+    sdtw_fn fp1 = fp;                                   // the first tier's pre-roll
+    if (hint) { fq = (sdtw_fn)sk_sdtwq_pick_hint(P == 0 ? 3 : 0, L, R); fp1 = (sdtw_fn)sk_sdtwq_pick_hint(1, L, R); }
+    if (!fq || !fp || !fp1 || !fw) return sk_fail(SK_ERR_UNSUPPORTED, "no screening kernel for L=%d R=%d", L, R);
 
     sdtw_kargs k = kargs_of(a);
     k.xlay = (const double *)c->motifw.p; k.xlayq = (const unsigned *)c->motifq.p; k.P = P; k.out = a->out;
@@ -1142,7 +1281,8 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
     k.qflag = (int32_t *)c->qflag.p; k.lsum = (unsigned *)c->lsum.p;
     k.wstate = (unsigned *)c->wstate.p; k.wrec = c->wrec.p; k.wrec_q = c->wrecq.p;
     k.early_cnt = d_early_cnt; k.early = d_early;
-    k.qerr = (unsigned)(N + maxlen + 2);
+    k.qplen = (unsigned)plen;
+    k.qerr = hint ? ((unsigned)plen << HINT_T) + HINT_MASK : (unsigned)plen;      // E, or E' of the tagged sweep
     k.wmax = 4 * ck;
     k.lds_wave_words = (64 / L) * ck;                   // pass Q, per wave: the interval's last-row values of its read groups
     k.guard = sk_tune("SK_DTW_NOGUARD") ? nullptr : (int32_t *)c->dtwcnt.p + 8;
@@ -1227,6 +1367,7 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
             order_args oa;
             oa.rec = (const wrec *)c->wrecq.p; oa.qflag = (const int32_t *)c->qflag.p;
             oa.nreads = k.nreads; oa.read0 = k.read0; oa.span = span; oa.ck = ck; oa.nck = nck; oa.L = L; oa.wmax = k.wmax;
+            oa.hint = hint ? 1 : 0;
             oa.hist = (int32_t *)c->order.p; oa.order = oa.hist + ORDER_BINS;
             SK_HIP(hipMemsetAsync(oa.hist, 0, ORDER_BINS * sizeof(int32_t), c->stream));
             const int og = (k.nreads + ORDER_TPB * ORDER_IPT - 1) / (ORDER_TPB * ORDER_IPT);
@@ -1241,7 +1382,7 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
             int32_t *soft = (int32_t *)c->wsoft.p;
             SK_HIP(hipMemsetAsync(soft, 0, sizeof(int32_t), c->stream));
             k.span = span; k.wl_list = order; k.wl_count = nullptr; k.soft = soft + 1; k.soft_cnt = soft;
-            hipLaunchKernelGGL(fp, dim3(grid), dim3(256), 0, c->stream, k);
+            hipLaunchKernelGGL(fp1, dim3(grid), dim3(256), 0, c->stream, k);
             hipLaunchKernelGGL(fw, dim3(grid), dim3(256), 0, c->stream, k);
             SK_HIP(hipGetLastError());
             k.span = span2; k.wl_list = soft + 1; k.wl_count = soft; k.soft = nullptr; k.soft_cnt = nullptr;
@@ -1250,7 +1391,7 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
         } else {
             k.wl_list = order; k.wl_count = nullptr;
         }
-        hipLaunchKernelGGL(fp, dim3(grid), dim3(256), 0, c->stream, k);
+        hipLaunchKernelGGL(tiers ? fp : fp1, dim3(grid), dim3(256), 0, c->stream, k);
         k.total_ptr = nullptr;
         hipLaunchKernelGGL(fw, dim3(grid), dim3(256), 0, c->stream, k);
         SK_HIP(hipGetLastError());
