@@ -140,6 +140,11 @@ constexpr int HINT_T = 5, HINT_G = 4, HINT_MARGIN = 8;
 constexpr int HINT_MAX_PLEN = 8192;                    // longest path (N + n + 2 cells) the hint is switched on for,
 constexpr int HINT_MIN_READS = 500000;                 // smallest call (see sk_launch_sdtw_screen)
 constexpr int HINT_MAX_R = 25;                         // and most rows per lane (beyond: k_sdtw_qh spills up to twice what k_sdtw_q does)
+// ... and the shortest motif: one granule.  The restart column lies up to 2^G - 1 + MARGIN = 23 columns before the path's
+// start, the plain look-back N + 8 columns before the first candidate: a motif shorter than a granule has nothing to save
+// and only pays (256 reads, 8 lanes: 7 points 14 989 window read-steps with the hint against 14 121 without, 12 points
+// 19 451 against 17 148; from 16 points on the hinted windows are the shorter ones -- tests/test_gpu_screen_grid.py)
+constexpr int HINT_MIN_N = 1 << HINT_G;
 constexpr unsigned HINT_MASK = (1u << HINT_T) - 1u;
 
 // shr0 for the tagged sweep: a group's lane 0 gets `tag` -- its virtual row -1 -- where shr0 hands it 0.  One
@@ -1264,12 +1269,13 @@ int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, in
     // rounds that were all but empty and now each take their latency, about 0.45 ms per call (slower
     // below 125 000 reads, level at 250 000, faster from 500 000 on, 163 and 200 points x 4 000 samples).  So: calls of
     // at least HINT_MIN_READS reads (SK_DTW_HINT_MIN), paths of up to HINT_MAX_PLEN cells and HINT_MAX_R rows per lane
-    // -- E' in signal units grows with the path length, and nobody measured beyond (SK_DTW_NOHINT=1: off everywhere).
+    // -- E' in signal units grows with the path length, and nobody measured beyond -- and motifs of at least HINT_MIN_N
+    // points (SK_DTW_NOHINT=1: off everywhere).
     const int64_t plen = (int64_t)N + maxlen + 2;
     int64_t hint_min = HINT_MIN_READS;
     if (const char *e = sk_tune("SK_DTW_HINT_MIN")) { const int v = atoi(e); if (v > 0) hint_min = v; }   // (tests: small batches too)
     const bool hint = a->feed == SK_FEED_I16 && (L == 8 || L == 16) && plen <= HINT_MAX_PLEN && R <= HINT_MAX_R &&
-                      a->nreads >= hint_min && sk_tune("SK_DTW_NOHINT") == nullptr;
+                      N >= HINT_MIN_N && a->nreads >= hint_min && sk_tune("SK_DTW_NOHINT") == nullptr;
     sdtw_fn fp1 = fp;                                   // the first tier's pre-roll
     if (hint) { fq = (sdtw_fn)sk_sdtwq_pick_hint(P == 0 ? 3 : 0, L, R); fp1 = (sdtw_fn)sk_sdtwq_pick_hint(1, L, R); }
     if (!fq || !fp || !fp1 || !fw) return sk_fail(SK_ERR_UNSUPPORTED, "no screening kernel for L=%d R=%d", L, R);

@@ -1,6 +1,7 @@
 """Seeded random cases for the kernel files that have no other randomised test in the suite -- csrc/sk_sweep.hip,
-sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, and through the twins
-of the hit family sk_bg.hip and sk_events.hip: per family  draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
+sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, through the twins of the
+hit family sk_bg.hip and sk_events.hip, and for the switches of the screening scheme sk_sdtwq.hip: per family
+draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
 what the reference says,  call_<family>(api, case, exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or
 the first difference as text.
 
@@ -36,17 +37,20 @@ SEEDS = {
     "detect": [4, 6, 8, 10, 27, 44],
     "hmm": [3, 10, 11, 15, 21, 35, 39, 54],
     "levels": [13, 18, 22, 26, 42, 59],
+    "screen": [67, 106, 119, 157, 238, 268, 281, 333, 337, 383, 387],
 }
 
 # every tuning switch a case may set; a runner clears the ones a case does not name
 SWITCHES = ("SK_SEG_DELTA_SCALE", "SK_WALK_GENERAL", "SK_DTW_SMALL_MAX", "SK_HITS_ROW_BYTES", "SK_PATH_LDS_BYTES",
-            "SK_PATH_SCRATCH_BYTES", "SK_DTW_NO_SMALL", "SK_PANEL_EXACT", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB")
+            "SK_PATH_SCRATCH_BYTES", "SK_DTW_NO_SMALL", "SK_PANEL_EXACT", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB",
+            "SK_DTW_QL", "SK_DTW_HINT_MIN", "SK_DTW_NOHINT", "SK_DTW_CK", "SK_DTW_SORT_MIN", "SK_DTW_SCRATCH_MB",
+            "SK_DTW_NOFUSE", "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY")
 
 
 # the family's number in the seed of its generator.  Frozen: the first four are what sorted(SEEDS).index(family) gave when
 # the table held four keys, so those cases stay what they were (tests/test_random_cases.py pins their digests); a new
 # family takes the next free number, whatever its name.
-FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7)
+FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8)
 
 
 def rng_of(family, seed):
@@ -1422,6 +1426,250 @@ def diff_levels(case, got, exp):
 
 
 # ======================================================================================================================
+# screen: one int16 first-match call through the fixed-point screening scheme (sk_sdtwq.hip)
+# ======================================================================================================================
+# sk_launch_sdtw takes the screening scheme for 256 reads and more whose rows (the stride of an int16 batch) hold at
+# least 4 * (N + N / 8 + 8 + ck) samples; screen_layout gives a motif L lanes per read and R = ceil(N / L) rows per lane,
+# one compiled kernel per (L, R) and pass; the tagged sweep (the start hint) runs for L = 8 and 16 up to HINT_MAX_R rows.
+SCREEN_MIN_READS = 256
+SCREEN_N = (1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 199, 200, 201, 256, 257, 399, 400, 401, 512, 513, 1024)
+SCREEN_CK = (64, 128, 256)                       # SK_DTW_CK: steps between checkpoints; a window spans 4 * ck columns
+SCREEN_LIMITS = ((0, 1200), (0, 900), (-50, 2500), (400, 650))
+SCREEN_CELLS = 1_500_000_000                     # cost-matrix cells the oracle fills per case (see RANDOM_CASES.md)
+SCREEN_HOSTILE = 21                              # the last rows of a screen_batch
+HINT_MAX_R, HINT_MAX_PLEN, HINT_MIN_READS, HINT_MIN_N = 25, 8192, 500000, 16      # sk_sdtwq.hip
+SCREEN_GRID = [(L, R) for L in (8, 16) for R in range(1, 33)] + [(64, R) for R in range(1, 17)]
+
+
+def screen_min_len(N, ck=128):
+    """The shortest row, a multiple of 8, with which a motif of N points takes the screening scheme (sk_sdtw.hip: screens)."""
+    return (4 * (N + N // 8 + 8 + ck) + 7) // 8 * 8
+
+
+def screen_grid_lengths(L, R):
+    """The two motif lengths of a grid test: L * R (no short lanes) and L * R - p, p from 1, L / 2, L - 1 in turn."""
+    p = (1, L // 2, L - 1)[(R - 1) % 3]
+    return [N for N in (L * R, L * R - p) if N > 0]
+
+
+def screen_shape(N, nreads, maxlen, ql=None):
+    """(L, R) as screen_layout (sk_sdtwq.hip) picks them; ql: SK_DTW_QL."""
+    L = 8 if (N <= 256 and nreads >= (65536 if maxlen > 8192 else 49152)) else 16 if N <= 512 else 64
+    if ql is not None:
+        v = int(ql)
+        if (v == 8 and N <= 256) or (v == 16 and N <= 512) or v == 64:
+            L = v
+    return L, (N + L - 1) // L
+
+
+def screen_hint_gate(N, L, R, nreads, maxlen, env):
+    """Whether sk_launch_sdtw_screen takes the tagged sweep for an int16 call."""
+    hint_min = HINT_MIN_READS
+    if int(env.get("SK_DTW_HINT_MIN", "0")) > 0:
+        hint_min = int(env["SK_DTW_HINT_MIN"])
+    return L in (8, 16) and N + maxlen + 2 <= HINT_MAX_PLEN and R <= HINT_MAX_R and N >= HINT_MIN_N and \
+        nreads >= hint_min and "SK_DTW_NOHINT" not in env
+
+
+def screen_chunks(L, R, nreads, maxlen, ck, scratch_mb):
+    """(chunks sk_launch_sdtw_screen makes of a call under SK_DTW_SCRATCH_MB = scratch_mb -- None: one --, the scratch
+    bytes it counts per read)."""
+    nck = (maxlen + L - 1) // ck
+    lq_stride = (maxlen + 3 * L + 7) & ~3
+    per_read = max(nck, 1) * L * ((R + 3) // 2) * 4 + lq_stride * 4 + L * (R + 2) * 4 + (nck + 1) * L * 4 + 64
+    if scratch_mb is None:
+        return 1, per_read
+    chunk = min(nreads, max(64, (int(scratch_mb) << 20) // per_read))
+    return -(-nreads // chunk), per_read
+
+
+def motif_image(v):
+    """A motif in raw units, as synth.squiggle_batch plants it (kept inside the default limits)."""
+    return np.clip(np.rint(np.asarray(v, dtype=np.float64) * 93.4 + 511.0), 1, 1199).astype(np.int16)
+
+
+def screen_motif(N, seed=11):
+    """synthetic_motif(N, seed'), seed' the first from `seed` on whose raw image is not constant (a short motif can be one
+    level: its copies tiled end to end would be a constant row)."""
+    from squigglekit_amd import synth
+    for s in range(seed, seed + 64):
+        motif = synth.synthetic_motif(N, seed=s)
+        if N < 2 or np.unique(motif_image(motif)).size > 1:
+            break
+    return motif
+
+
+def screen_batch(R, M, N, seed, ck=128, motif=None):
+    """(sig [R, M] int16, lens, motif): synth.squiggle_batch rows with the motif planted, all of full length, and behind
+    them SCREEN_HOSTILE rows picked to mislead the screening scheme -- the batch of tests/test_gpu_hint.py with its
+    positions scaled to M and N.  M >= screen_min_len(N, ck)."""
+    from squigglekit_amd import synth
+    assert R > SCREEN_HOSTILE and M >= screen_min_len(N, ck)
+    if motif is None:
+        motif = screen_motif(N)
+    sig = synth.squiggle_batch(R, M, seed, motif=motif)
+    lens = np.full(R, M, dtype=np.int32)
+    copy = motif_image(motif)
+    h, wmax = R - SCREEN_HOSTILE, 4 * ck
+    # two copies further apart than one window takes (4 checkpoint intervals): a second window (sibling)
+    sig[h, 4:4 + N] = copy
+    sig[h, M - N - 4:M - 4] = copy
+    a = M // 8
+    if a + 2 * N + wmax + 8 <= M:                                           # (where M allows)
+        sig[h + 1, a:a + N] = copy
+        sig[h + 1, a + N + wmax + 8:a + 2 * N + wmax + 8] = copy
+    # copies stretched 3x and 4x: paths wider than every look-back; one of them ends on the last sample
+    s3, s4 = motif_image(np.repeat(motif, 3)), motif_image(np.repeat(motif, 4))
+    sig[h + 2, 50:50 + s3.size] = s3
+    sig[h + 3, 50:50 + s4.size] = s4
+    sig[h + 4, M - s3.size:] = s3
+    # copies that start in the read's first granule, and one that ends on its last sample
+    for r, off in ((h + 5, 0), (h + 6, 5), (h + 7, 15), (h + 8, M - N)):
+        sig[r, off:off + N] = copy
+    sig[h + 9, :] = 500                                                     # constant: MAD = 0
+    sig[h + 10, :] = 500 + (np.arange(M) % 2)                               # two levels: every cost ties with many others
+    sig[h + 11, :] = np.tile(copy, M // N + 1)[:M]                          # the motif end to end: near-minima everywhere
+    if _np_mad_is_zero(sig[h + 11], 0, 1200):                               # (a short motif: more than half of it one level)
+        sig[h + 11, :] += ((np.arange(M) // N) % 3).astype(np.int16)        # every tile 0, 1 or 2 raw units up: MAD = 1 unit
+    rng = np.random.default_rng([97, int(seed), N])
+    lens[h + 12:h + 18] = (0, 1, max(N - 1, 0), N, N + 1, M - 1)            # ragged: around the motif's length
+    lens[h + 18:h + 21] = rng.integers(2, M, 3)
+    return sig, lens, motif
+
+
+def _np_mad_is_zero(x, lo, hi):
+    f = x[(x > lo) & (x < hi)].astype(np.float64)
+    return f.size > 0 and float(np.median(np.abs(f - np.median(f)))) == 0.0
+
+
+def screen_mad0_rows(sig, lens, lo=0, hi=1200):
+    """Rows with samples inside the limits whose MAD is 0 (the reference divides by zero there: flag 2, not compared)."""
+    return [r for r in range(sig.shape[0]) if _np_mad_is_zero(sig[r, :lens[r]], lo, hi)]
+
+
+def draw_screen(rng):
+    env = {}
+    nm = int(_pick(rng, (1, 1, 1, 2, 3)))
+    ql = _pick(rng, (None, "8", "16", "64"))
+    if nm > 1 and ql == "64":
+        ql = _pick(rng, (None, "8", "16"))       # (a motif list is there to change L between motifs)
+
+    def one_n(lo, hi):
+        listed = [n for n in SCREEN_N if lo <= n <= hi]
+        return int(_pick(rng, listed)) if rng.random() < 0.5 else int(rng.integers(lo, hi + 1))
+    if nm == 1 and rng.random() < 0.5:           # a length made for the layout: every R under the L asked for, P = 0 and P > 0
+        L = int(ql) if ql else 16
+        N = L * int(rng.integers(1, (32 if L < 64 else 16) + 1)) - int(_pick(rng, (0, 0, 1, L // 2, L - 1, int(rng.integers(L)))))
+        Ns = [max(1, N)]
+    elif nm == 1:
+        Ns = [one_n(1, 1024)]
+    else:
+        # consecutive motifs on different L: the resident quantised motif is keyed on L alone (motifq_L), and the later
+        # motifs read the samples the first motif's prologue compacted
+        classes = ((1, 256), (257, 512), (513, 640)) if ql == "8" else ((1, 512), (513, 640))
+        k0 = int(rng.integers(len(classes)))
+        Ns = [one_n(*classes[(k0 + k) % len(classes)]) for k in range(nm)]
+    from squigglekit_amd import synth
+    motifs = [screen_motif(Ns[0], seed=int(rng.integers(1000)))]
+    motifs += [synth.synthetic_motif(N, seed=int(rng.integers(1000))) for N in Ns[1:]]
+    ck = int(_pick(rng, (128, 128, 64, 256)))
+    if ck != 128:
+        env["SK_DTW_CK"] = str(ck)
+    if ql is not None:
+        env["SK_DTW_QL"] = ql
+    hint = _pick(rng, ("on", "on", "on", "off", "default"))
+    if hint == "on":
+        env["SK_DTW_HINT_MIN"] = "1"
+    elif hint == "off":
+        env["SK_DTW_NOHINT"] = "1"
+    if rng.random() < 0.5:
+        env["SK_DTW_SORT_MIN"] = "1"             # the window passes take every chunk in sorted order
+    for key, p in (("SK_DTW_NOFUSE", 0.3), ("SK_DTW_NO_EARLY", 0.3), ("SK_DTW_NO_SIBLINGS", 0.2)):
+        if rng.random() < p:
+            env[key] = "1"
+    scale = _pick(rng, ("medmad", "medmad", "zscale"))
+    lo, hi = _pick(rng, SCREEN_LIMITS)
+    # ---- rows at the screening threshold of the longest motif and a little above it; 256 to about 700 reads
+    M = screen_min_len(max(Ns), ck) + int(_pick(rng, (0, 0, 8, 24, 200)))
+    R = int(rng.integers(SCREEN_MIN_READS, 701))
+    R = max(SCREEN_MIN_READS, min(R, SCREEN_CELLS // (M * sum(Ns))))
+    sig, lens, _ = screen_batch(R, M, Ns[0], int(rng.integers(1 << 30)), ck=ck, motif=motifs[0])
+    h = R - SCREEN_HOSTILE
+    for m in motifs[1:]:                          # copies of the other motifs in some of the plain rows
+        for r in rng.integers(0, h, 12):
+            at = int(rng.integers(0, M - len(m)))
+            sig[r, at:at + len(m)] = motif_image(m)
+    k = int(rng.integers(0, 40))                  # samples on and beyond the limits
+    sig[rng.integers(0, h, k), rng.integers(0, M, k)] = rng.choice([-9, 0, 899, 900, 1199, 1200, 3000], k)
+    stride = M
+    if rng.random() < 0.4:                        # a stride longer than the longest row, padding that is not zeros
+        stride = M + 8 * int(rng.integers(1, 6))
+        wide = rng.integers(300, 700, size=(R, stride)).astype(np.int16)
+        wide[:, :M] = sig
+        sig = wide
+    case = dict(family="screen", Ns=Ns, R=R, M=M, stride=stride, ck=ck, ql=ql, hint=hint, scale=scale, lo=lo, hi=hi,
+                motifs=motifs, sig=sig, lens=lens, env=env)
+    # ---- SK_DTW_SCRATCH_MB small enough for three chunks or more, where a whole number of MB is
+    if rng.random() < 0.5:
+        L, Rr = screen_shape(Ns[0], R, stride, ql)
+        per_read = screen_chunks(L, Rr, R, stride, ck, 1)[1]
+        mb = per_read * (R // 3) >> 20
+        if mb >= 1:
+            env["SK_DTW_SCRATCH_MB"] = str(mb)
+    return case
+
+
+def screen_plan(case):
+    """Per motif: dict(N, L, R, P, hinted, chunks) as the library lays the call out."""
+    out = []
+    mb = case["env"].get("SK_DTW_SCRATCH_MB")
+    for N in case["Ns"]:
+        L, R = screen_shape(N, case["R"], case["stride"], case["ql"])
+        out.append(dict(N=N, L=L, R=R, P=L * R - N,
+                        hinted=screen_hint_gate(N, L, R, case["R"], case["stride"], case["env"]),
+                        chunks=screen_chunks(L, R, case["R"], case["stride"], case["ck"], mb)[0]))
+    return out
+
+
+def expect_screen(ora, case):
+    """want[m]: the oracle's records of motif m, the reads split over host threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    sig, lens, R = case["sig"], case["lens"], case["R"]
+    per = (R + 15) // 16
+    jobs = [(m, a, min(R, a + per)) for m in range(len(case["motifs"])) for a in range(0, R, per)]
+    mode = 0 if case["scale"] == "medmad" else 1
+    with ThreadPoolExecutor(16) as ex:
+        parts = list(ex.map(lambda j: ora.motifseq_batch_i16(sig[j[1]:j[2]], lens[j[1]:j[2]], case["motifs"][j[0]],
+                                                             scale_mode=mode, lo=case["lo"], hi=case["hi"]), jobs))
+    return dict(want=[np.concatenate([p for j, p in zip(jobs, parts) if j[0] == m]) for m in range(len(case["motifs"]))])
+
+
+def call_screen(api, case, exp=None):
+    args = (case["scale"], case["lo"], case["hi"])
+    if len(case["motifs"]) == 1:
+        return [api.motifseq_batch(case["sig"], case["lens"], case["motifs"][0], *args)]
+    return api.motifseq_multi_batch(case["sig"], case["lens"], case["motifs"], *args)
+
+
+def screen_compared(got, want):
+    """The reads whose records are compared: all but the ones flagged MAD = 0 / std = 0, where the reference divides by
+    zero (a read with nothing inside the limits is compared: n = 0)."""
+    return ((got["flags"] & 2) == 0) & np.isfinite(want["dist"]) | (want["n"] == 0)
+
+
+def diff_screen(case, got, exp):
+    for m, (g, want) in enumerate(zip(got, exp["want"])):
+        ok = screen_compared(g, want)
+        same = (g["start"] == want["start"]) & (g["end"] == want["end"]) & (g["n"] == want["n"]) & \
+               ((_bits(g["dist"]) == _bits(want["dist"])) | (np.isnan(g["dist"]) & np.isnan(want["dist"])))
+        bad = np.flatnonzero(~same & ok)
+        if bad.size:
+            return "motif %d (N=%d) read %d (%d samples): got %s want %s" % (m, case["Ns"][m], bad[0], case["lens"][bad[0]],
+                                                                            g[bad[0]], want[bad[0]])
+    return None
+
+
+# ======================================================================================================================
 # the twins of the hit family: the read background on the hits cases, events and pooling on the paths cases
 # ======================================================================================================================
 def twin_case(family, case, use_seed=None):
@@ -1577,16 +1825,16 @@ def result_bytes(got):
 
 
 DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull, panel=draw_panel, detect=draw_detect,
-            hmm=draw_hmm, levels=draw_levels)
+            hmm=draw_hmm, levels=draw_levels, screen=draw_screen)
 EXPECT = dict(sweep=expect_sweep, hits=expect_hits, paths=expect_paths, pull=expect_pull, segment=expect_plain,
               motifseq=expect_plain, pa=expect_plain, panel=expect_panel, detect=expect_detect, hmm=expect_hmm,
-              levels=expect_levels, background=expect_background, events=expect_events)
+              levels=expect_levels, background=expect_background, events=expect_events, screen=expect_screen)
 CALL = dict(sweep=call_sweep, hits=call_hits, paths=call_paths, pull=call_pull, segment=call_plain, motifseq=call_plain,
             pa=call_plain, panel=call_panel, detect=call_detect, hmm=call_hmm, levels=call_levels,
-            background=call_background, events=call_events)
+            background=call_background, events=call_events, screen=call_screen)
 DIFF = dict(sweep=diff_sweep, hits=diff_hits, paths=diff_paths, pull=diff_pull, segment=diff_plain, motifseq=diff_plain,
             pa=diff_plain, panel=diff_panel, detect=diff_detect, hmm=diff_hmm, levels=diff_levels,
-            background=diff_background, events=diff_events)
+            background=diff_background, events=diff_events, screen=diff_screen)
 TWIN_OF = dict(background="hits", events="paths")
 
 # ---- the interleaved sequence (tests/test_gpu_random.py::test_interleaved_calls_share_the_context_buffers) --------
@@ -1597,11 +1845,14 @@ INTERLEAVE = [("paths", 50), ("sweep", 97), ("pull", 0), ("hits", 1), ("paths", 
               ("pa", 2), ("hits", 214), ("sweep", 60), ("paths", 12), ("motifseq", 2)]
 
 
-# the second sequence: the newer families (panel, detect, hmm, levels) and the two twins between the older calls
+# the second sequence: the newer families (panel, detect, hmm, levels) and the two twins between the older calls; at its
+# end three screening calls (one of them twice, several chunks, the hint, two motifs on different L) between calls of
+# other families, so that the screening scheme's buffers are used again after those have grown the shared ones
 INTERLEAVE2 = [("panel", 4), ("hmm", 3), ("detect", 4), ("background", 1), ("sweep", 97), ("levels", 13), ("panel", 29),
                ("events", 50), ("hmm", 35), ("pull", 0), ("detect", 27), ("panel", 4), ("hits", 1), ("levels", 22),
                ("hmm", 3), ("paths", 12), ("detect", 6), ("background", 324), ("panel", 36), ("segment", 3), ("levels", 13),
-               ("events", 12), ("hmm", 10), ("detect", 4), ("motifseq", 2), ("panel", 93)]
+               ("events", 12), ("hmm", 10), ("detect", 4), ("motifseq", 2), ("panel", 93), ("screen", 268),
+               ("levels", 22), ("screen", 337), ("hits", 1), ("screen", 268)]
 
 
 def interleave_case(family, seed):

@@ -98,3 +98,33 @@ def test_hinted_windows_equal_the_oracle_and_ask_for_fewer_steps(gpu, ora, monke
     print("second tier: %d of %d reads" % (tier2, h))
     assert part.tobytes() == hinted[:h].tobytes()
     assert tier2 <= 0.05 * h, (tier2, h)
+
+
+@pytest.mark.parametrize("N", [7, 12])
+def test_a_motif_shorter_than_a_granule_keeps_the_plain_kernels(gpu, ora, monkeypatch, N):
+    """The restart column of the hint lies up to 15 + 8 columns before the path's start, the plain look-back N + 8 columns
+    before the first candidate: below 16 points the hint can only lengthen a window.  Found by
+    tests/test_gpu_screen_grid.py: 256 reads over 8 lanes asked for 14 989 window read-steps with the hint against 14 121
+    without it at 7 points, 19 451 against 17 148 at 12.  The gate (HINT_MIN_N) now leaves such motifs to k_sdtw_q /
+    k_sdtw_p: forcing the hint on changes neither a record nor the work."""
+    import randcases as rc
+    from squigglekit_amd import api
+    L = gpu.load()
+    monkeypatch.delenv("SK_DTW_NOHINT", raising=False)
+    monkeypatch.setenv("SK_DTW_QL", "8")
+    monkeypatch.setenv("SK_DTW_HINT_MIN", "1")
+    sig, lens, motif = rc.screen_batch(256, rc.screen_min_len(N), N, 70000 + N)
+    launches = C.c_int32()
+    asked = api.motifseq_batch(sig, lens, motif)
+    L.sk_last_dtw_profile(None, C.byref(launches), None, None, None)
+    assert launches.value >= 1, "the batch did not take the screening scheme"
+    steps_asked = _window_steps(L)
+    monkeypatch.setenv("SK_DTW_NOHINT", "1")
+    plain = api.motifseq_batch(sig, lens, motif)
+    steps_plain = _window_steps(L)
+    want = oracle_motifseq_threaded(ora, sig, lens, motif)
+    ok = (plain["flags"] & 2) == 0
+    assert (~ok).sum() <= 2
+    _same(plain[ok], want[ok], "SK_DTW_NOHINT=1")
+    assert asked.tobytes() == plain.tobytes()
+    assert 0 < steps_asked == steps_plain, (steps_asked, steps_plain)

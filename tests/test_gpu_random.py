@@ -1,8 +1,8 @@
 """GPU leg of the seeded random cases (tests/randcases.py): every committed seed -- segmenter sweep (sk_sweep.hip),
 MotifSeq hit lists (sk_hits.hip + k_sdtw's row output), alignment paths (sk_path.hip), SquigglePull text (sk_pull.hip),
 the region + motif panel (sk_panel.hip), event detection (sk_detect.hip), the signal HMM and its state paths
-(sk_hmm.hip), segment levels (sk_seglev.hip), and the read background (sk_bg.hip) and events (sk_events.hip) twins of the
-hit family -- through the public api call, against its reference, exactly; and two interleaved sequences of calls over
+(sk_hmm.hip), segment levels (sk_seglev.hip), the read background (sk_bg.hip) and events (sk_events.hip) twins of the
+hit family, and the switches of the screening scheme (sk_sdtwq.hip) -- through the public api call, against its reference, exactly; and two interleaved sequences of calls over
 the shared grow-only context buffers.  tests/test_random_cases.py (CPU) asserts what the seeds
 reach; tests/RANDOM_CASES.md lists the one-line kernel mutants these tests catch.  A failure names family, seed, the
 drawn parameters and switches, and the first differing (read, hit / set / line): `randcases.case_of(family, seed)`
@@ -31,9 +31,15 @@ def run_case(monkeypatch, ora, case):
     got = rc.CALL[fam](api, case, exp)
     msg = rc.DIFF[fam](case, got, exp)
     assert msg is None, "%s\n  first difference: %s" % (rc.describe(case), msg)
-    if fam in ("hits", "paths", "motifseq", "background", "events"):
+    if fam in ("hits", "paths", "motifseq", "background", "events", "screen"):
         guard = api.last_dtw_guard()
         assert guard["premise_violations"] == 0 and guard["audit_mismatches"] == 0, (rc.describe(case), guard)
+    if fam == "screen":                                      # every motif of the call took the screening scheme, no alarm
+        import ctypes as C
+        from squigglekit_amd import _lib
+        launches = C.c_int32()
+        _lib.load().sk_last_dtw_profile(None, C.byref(launches), None, None, None)
+        assert launches.value >= 1 and guard["alarm"] == 0 and guard["exact_fallback"] == 0, (rc.describe(case), guard)
     if fam == "paths":
         assert api.last_path_mismatches() == 0, rc.describe(case)
     return got, exp
@@ -142,6 +148,29 @@ def test_levels_seed_matches_numpy(gpu, ora, monkeypatch, seed):
         assert segs.shape[1] >= max(case["max_segs"], int(nsegs.max())), rc.describe(case)
 
 
+@pytest.mark.parametrize("seed", rc.SEEDS["screen"])
+def test_screen_seed_matches_the_oracle(gpu, ora, monkeypatch, seed):
+    """One int16 first-match call through the screening scheme under drawn switches (lane layout, hint, checkpoint
+    distance, sorted order, chunks, fused or separate statistics, siblings, early retry, scaling, limits, stride, one to
+    three motifs): every record the oracle's, byte for byte; chunks and retries as the case's plan says."""
+    import ctypes as C
+    case = rc.case_of("screen", seed)
+    got, exp = run_case(monkeypatch, ora, case)
+    L = gpu.load()
+    launches, per = C.c_int32(), C.c_int32()
+    L.sk_last_dtw_profile(None, C.byref(launches), None, None, C.byref(per))
+    assert launches.value == rc.screen_plan(case)[-1]["chunks"], (rc.describe(case), launches.value, per.value)
+    # (the counters of a call add up over its motifs) fewer than a quarter of the (read, motif) pairs took the exact retry
+    assert 4 * L.sk_last_dtw_retries() < case["R"] * len(case["Ns"]), (rc.describe(case), L.sk_last_dtw_retries())
+    for g, want in zip(got, exp["want"]):
+        ok = rc.screen_compared(g, want)
+        assert np.array_equal(g["n"], want["n"]) and 10 * int((~ok).sum()) < case["R"], rc.describe(case)
+    if any(p["hinted"] for p in rc.screen_plan(case)):       # the hint changes which columns a window computes, never a record
+        from squigglekit_amd import api
+        monkeypatch.setenv("SK_DTW_NOHINT", "1")
+        assert rc.result_bytes(rc.call_screen(api, case)) == rc.result_bytes(got), rc.describe(case) + " SK_DTW_NOHINT=1"
+
+
 @pytest.mark.parametrize("seed", rc.SEEDS["hits"])
 def test_background_twin_of_the_hits_seed(gpu, ora, monkeypatch, seed):
     """Every committed hit-list case through api.motifseq_background: the records against numpy on the oracle's last row,
@@ -182,5 +211,6 @@ def test_interleaved_calls_share_the_context_buffers(gpu, ora, monkeypatch):
 
 def test_newer_calls_interleaved_with_the_older_ones(gpu, ora, monkeypatch):
     """The same for the panel, event detection, the signal HMM, segment levels and the two twins, between calls of the
-    older families (c->sig / len / off / out / out2 / misc / comp / prep are shared through sk_reserve)."""
+    older families (c->sig / len / off / out / out2 / misc / comp / prep are shared through sk_reserve); at the end three
+    screening calls, whose checkpoint, last-row and state buffers are used again after calls of other families."""
     run_sequence(monkeypatch, ora, rc.INTERLEAVE2)

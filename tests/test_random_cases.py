@@ -718,6 +718,120 @@ def test_levels_cases_reach_every_boundary(cases):
     assert segments >= 10 * len(cases["levels"])         # spans to compare, not only whole reads
 
 
+# ---- the screening scheme's switches ----------------------------------------------------------------------------------
+def screen_features(case):
+    env, plan = case["env"], rc.screen_plan(case)
+    f = {"motifs=%d" % len(case["Ns"]), "QL=%s" % case["ql"], "hint=" + case["hint"], "scale=" + case["scale"],
+         "limits=%d,%d" % (case["lo"], case["hi"]), "ck=%d" % case["ck"]}
+    f |= {"N=%d" % N for N in case["Ns"] if N in rc.SCREEN_N}
+    if any(N not in rc.SCREEN_N for N in case["Ns"]):
+        f.add("N random")
+    for key in ("SK_DTW_SORT_MIN", "SK_DTW_NOFUSE", "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY"):
+        if key in env:
+            f.add(key)
+    if case["stride"] > int(case["lens"].max()) and np.any(case["sig"][:, case["M"]:] != 0):
+        f.add("stride > longest row, padding not zeros")
+    if case["M"] == rc.screen_min_len(max(case["Ns"]), case["ck"]) and case["stride"] == case["M"]:
+        f.add("rows at the threshold")
+    if max(p["chunks"] for p in plan) >= 3:
+        f.add("chunks>=3")
+    for p in plan:
+        f.add("L%d P%s0" % (p["L"], "=" if p["P"] == 0 else ">"))
+    asked = case["hint"] == "on"
+    hinted = [p for p in plan if p["hinted"]]
+    if asked and any(p["L"] == 64 or p["R"] > rc.HINT_MAX_R or p["N"] < rc.HINT_MIN_N for p in plan):
+        f.add("the gate switches the hint off")
+    if case["hint"] == "default":
+        assert not hinted
+    if asked and hinted:
+        for p in hinted:
+            f.add("hint L%d R%%4=%d" % (p["L"], p["R"] % 4))
+            f.add("hint L%d P%s0" % (p["L"], "=" if p["P"] == 0 else ">"))
+            if p["chunks"] >= 3:
+                f.add("hint + chunks>=3")
+        if "SK_DTW_SORT_MIN" in env:
+            f.add("hint + sorted order")
+        if case["scale"] == "zscale":
+            f.add("hint + zscale")
+        if "SK_DTW_NOFUSE" in env:
+            f.add("hint + SK_DTW_NOFUSE")
+        if case["ck"] != 128:
+            f.add("hint + ck=%d" % case["ck"])
+        Ls = [p["L"] for p in plan]
+        if len(plan) > 1 and all(a != b for a, b in zip(Ls, Ls[1:])):
+            f.add("hint + a motif list that changes L")
+    return f
+
+
+SCREEN_REQUIRED = ({"hint L%d R%%4=%d" % (L, k) for L in (8, 16) for k in range(4)} |
+                   {"L%d P%s0" % (L, c) for L in (8, 16, 64) for c in "=>"} |
+                   {"hint L%d P%s0" % (L, c) for L in (8, 16) for c in "=>"} |
+                   {"limits=%d,%d" % p for p in rc.SCREEN_LIMITS} | {"ck=%d" % c for c in rc.SCREEN_CK} |
+                   {"QL=None", "QL=8", "QL=16", "QL=64", "hint=on", "hint=off", "hint=default", "scale=medmad",
+                    "scale=zscale", "motifs=1", "motifs=2", "motifs=3", "N random", "SK_DTW_SORT_MIN", "SK_DTW_NOFUSE",
+                    "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY", "stride > longest row, padding not zeros",
+                    "rows at the threshold", "chunks>=3", "the gate switches the hint off", "hint + sorted order",
+                    "hint + chunks>=3", "hint + zscale", "hint + SK_DTW_NOFUSE", "hint + ck=64", "hint + ck=256",
+                    "hint + a motif list that changes L"})
+
+
+def test_screen_cases_reach_every_switch_combination(cases):
+    """The combinations no other test of the suite has: the hint together with the sorted order, three chunks, zscale,
+    SK_DTW_NOFUSE, a motif list that changes L, both other checkpoint distances; every R % 4 under both hinted layouts;
+    P = 0 and P > 0 under every L; a case the gate itself keeps from the hint."""
+    assert len(cases["screen"]) >= 4
+    have = set()
+    for case, _ in cases["screen"]:
+        have |= screen_features(case)
+        assert rc.SCREEN_MIN_READS <= case["R"] <= 700 and case["sig"].shape == (case["R"], case["stride"])
+        assert case["stride"] >= rc.screen_min_len(max(case["Ns"]), case["ck"])      # every motif of the call is screened
+        assert int(case["lens"].max()) == case["M"]
+    assert not sorted(SCREEN_REQUIRED - have)
+    assert any(p["L"] == 64 and p["R"] >= 9 for case, _ in cases["screen"] for p in rc.screen_plan(case))
+
+
+def test_screen_cases_compare_nine_reads_in_ten_within_the_cell_budget(cases):
+    """In every case the reads the reference leaves out (MAD or std 0) are under 10 %, few of the others have a path
+    wider than the second tier's look-back (those take the exact retry, whatever the library does), and the oracle fills at
+    most SCREEN_CELLS cells."""
+    for case, exp in cases["screen"]:
+        assert case["R"] * case["stride"] * sum(case["Ns"]) <= rc.SCREEN_CELLS, rc.describe(case)
+        for N, want in zip(case["Ns"], exp["want"]):
+            out = ~np.isfinite(want["dist"]) & (want["n"] > 0)
+            assert 10 * int(out.sum()) < case["R"], rc.describe(case)
+            wide = ~out & (want["end"] - want["start"] + 1 > 2 * N + N // 4 + 16)
+            assert 8 * int(wide.sum()) < case["R"], (rc.describe(case), int(wide.sum()))
+
+
+def test_the_screening_batch_has_two_rows_without_a_result():
+    """randcases.screen_batch over every length of tests/test_gpu_screen_grid.py: the constant row and the one-sample row
+    (unless the filter drops its sample) are the only ones with MAD = 0; one read at least has the full length; the
+    lengths give the layout asked for."""
+    seen = set()
+    for L, R in rc.SCREEN_GRID:
+        lengths = rc.screen_grid_lengths(L, R)
+        assert lengths[0] == L * R and all(0 < N <= L * R for N in lengths)
+        for N in lengths:
+            M = rc.screen_min_len(N)
+            assert M % 8 == 0 and 0 <= M - 4 * (N + N // 8 + 8 + 128) < 8
+            assert rc.screen_shape(N, rc.SCREEN_MIN_READS, M, str(L)) == (L, R)
+            if N in seen:
+                continue
+            seen.add(N)
+            sig, lens, motif = rc.screen_batch(rc.SCREEN_MIN_READS, M, N, 70000 + N)
+            h = rc.SCREEN_MIN_READS - rc.SCREEN_HOSTILE
+            # (the rows of full length cannot have MAD 0 unless more than half of their samples are one value)
+            full = np.flatnonzero(lens == M)
+            top = np.array([np.bincount(sig[r] - sig[r].min()).max() for r in full])
+            suspects = set(full[2 * top >= M - 8]) | set(np.flatnonzero(lens < M))
+            assert full.size >= h and h + 9 in suspects
+            bad = [r for r in sorted(suspects) if rc._np_mad_is_zero(sig[r, :lens[r]], 0, 1200)]
+            assert set(bad) <= {h + 9, h + 13} and h + 9 in bad, (N, bad)
+    assert {p for L, R in rc.SCREEN_GRID for p in [L * R - rc.screen_grid_lengths(L, R)[-1]]} >= {1, 4, 7, 8, 15, 32, 63}
+    assert (rc.screen_min_len(8), rc.screen_min_len(256), rc.screen_min_len(512), rc.screen_min_len(1024)) == \
+        (584, 1696, 2848, 5152)
+
+
 def test_same_seed_same_case():
     for fam in rc.SEEDS:
         seed = rc.SEEDS[fam][0]
@@ -765,6 +879,8 @@ def test_second_interleaved_sequence_is_what_it_claims():
         size.append(max(len(r) for r in case["reads"]) if "reads" in case else int(np.max(case["lens"])))
     turns = sum((b - a) * (c - b) < 0 for a, b, c in zip(size, size[1:], size[2:]))
     assert turns >= 8, size
+    scr = [i for i, (f, _) in enumerate(seq) if f == "screen"]              # screening calls, one twice, not side by side
+    assert len(scr) >= 3 and len({seq[i] for i in scr}) < len(scr) and all(b - a >= 2 for a, b in zip(scr, scr[1:]))
     new = [i for i, (f, _) in enumerate(seq) if f in ("panel", "detect", "hmm", "levels")]
     assert any(size[i] > max(size[:i]) for i in new[1:])                    # a newer family grows the shared buffers
     assert any(size[i] < size[i - 1] // 4 for i in new if i)               # and one runs in buffers left much larger

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle sweep over shapes the unit tests do not pin: random read counts, ragged
-lengths, strides, motif lengths, outlier limits, both scalings, segmenter parameters; the segment levels of every
-segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the segmenter
-sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
+lengths, strides, outlier limits, segmenter parameters; the segment levels of every
+segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the
+screening scheme of MotifSeq's first match under its switches, the segmenter sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
 signal HMM with its state paths, segment levels, and the background and events twins of the hit family -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
 length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py.
@@ -99,36 +99,37 @@ def main():
         lens = rng.integers(0, M + 1, R).astype(np.int32)
         lens[rng.integers(0, R)] = M
         # ---- MotifSeq ----
-        # (round 3: every rows-per-lane instantiation of the screening kernels can come up -- 8 lanes x 1..32 rows up to
-        # 256 points, 16 x 17..32 up to 512, 64 x 9..16 beyond -- not only the lengths the unit tests pin)
-        N = int(rng.choice([1, 7, 16, 17, 100, 163, 200, 256, 257, 400, 512, 513, 1030])) if rng.random() < 0.5 \
-            else int(rng.integers(1, 1025))
-        motif = synth.synthetic_motif(N, seed=int(rng.integers(1000)))
-        lo, hi = [(0, 1200), (0, 900), (-50, 2500), (400, 650)][int(rng.integers(4))]
-        scale = ["medmad", "zscale"][int(rng.integers(2))]
-        # the lanes-per-read layout of the screening scheme (8 is what large batches get by themselves: these batches
-        # are small, so it is asked for), the fused / separate filter + statistics, the early / late exact retry
-        import os
-        ql = [None, "8", "16", "64"][int(rng.integers(4))]
-        for key, val in (("SK_DTW_QL", ql), ("SK_DTW_NOFUSE", "1" if rng.random() < 0.3 else None),
-                         ("SK_DTW_NO_EARLY", "1" if rng.random() < 0.3 else None),
-                         ("SK_DTW_NO_SIBLINGS", "1" if rng.random() < 0.2 else None),  # two clusters: exact pass / second window
-                         ("SK_DTW_SORT_MIN", "1" if rng.random() < 0.5 else None)):     # window passes in sorted order
-            if val is None:
-                os.environ.pop(key, None)
+        # randcases.DRAW["screen"] with this tool's generator: one int16 first-match call of 256 reads and more through
+        # the screening scheme -- every rows-per-lane instantiation of its kernels can come up (8 and 16 lanes x 1..32
+        # rows, 64 x 1..16), with the start hint forced on, forced off or left to its gate, the checkpoint distance, the
+        # sorted window order, several chunks, the fused / separate filter + statistics, the early / late exact retry,
+        # second windows, both scalings, four limit pairs, a stride beyond the longest row, one to three motifs on
+        # different lane layouts -- against the oracle, byte for byte
+        case = randcases.DRAW["screen"](rng)
+        for key in randcases.SWITCHES:
+            if key in case["env"]:
+                os.environ[key] = case["env"][key]
             else:
-                os.environ[key] = val
-        got = api.motifseq_batch(sig, lens, motif, scale=scale, scale_low=lo, scale_hi=hi)
-        want = ora.motifseq_batch_i16(sig, lens, motif, scale_mode=0 if scale == "medmad" else 1, lo=lo, hi=hi)
-        ok = ((got["flags"] & 2) == 0) & np.isfinite(want["dist"]) | (want["n"] == 0)   # MAD == 0 / std == 0 rows aside
-        nan = np.isnan(got["dist"]) & np.isnan(want["dist"])
-        same = (got["start"] == want["start"]) & (got["end"] == want["end"]) & (got["n"] == want["n"]) & \
-               ((got["dist"] == want["dist"]) | nan)
-        if not np.all(same[ok]):
+                os.environ.pop(key, None)
+        exp = randcases.EXPECT["screen"](ora, case)
+        mgot = randcases.CALL["screen"](api, case, exp)
+        for key in randcases.SWITCHES:
+            os.environ.pop(key, None)
+        for N, got, want in zip(case["Ns"], mgot, exp["want"]):
+            ok = randcases.screen_compared(got, want)           # MAD == 0 / std == 0 rows aside
+            nan = np.isnan(got["dist"]) & np.isnan(want["dist"])
+            same = (got["start"] == want["start"]) & (got["end"] == want["end"]) & (got["n"] == want["n"]) & \
+                   ((got["dist"] == want["dist"]) | nan)
+            if not np.all(same[ok]):
+                bad += 1
+                r = int(np.nonzero(~same & ok)[0][0])
+                print("MOTIFSEQ mismatch R=%d M=%d N=%d %s lo=%d hi=%d QL=%s read %d: got %s want %s"
+                      % (case["R"], case["stride"], N, case["scale"], case["lo"], case["hi"], case["ql"], r, got[r], want[r]))
+                print("  %s" % randcases.describe(case))
+        guard = api.last_dtw_guard()
+        if any(guard[k] for k in ("premise_violations", "audit_mismatches", "alarm", "exact_fallback")):
             bad += 1
-            r = int(np.nonzero(~same & ok)[0][0])
-            print("MOTIFSEQ mismatch R=%d M=%d N=%d %s lo=%d hi=%d QL=%s read %d: got %s want %s"
-                  % (R, M, N, scale, lo, hi, ql, r, got[r], want[r]))
+            print("MOTIFSEQ guard counters not all zero round %d %s: %s" % (rounds, randcases.describe(case), guard))
         # ---- segmenter ----
         # (round 4: the default walk jumps between stretches of quiet mask entries, k_seg_walk4 -- window >= 127 and
         # error < min(corrector, 32) take it, with the statistics kernel's hints up to 4 096 samples and a pass of its
