@@ -735,12 +735,17 @@ void k_drna_stats(const int16_t *__restrict__ sig, int64_t stride, const int32_t
                 const double median_b = sc->bcast[0], sd_b = sc->bcast[1];
                 pr.center = median_b; pr.scale = sd_b; pr.top = median_b + sd_b * std_scale; pr.bot = -__builtin_huge_val();
             }
-            // the samples collected so far, from LDS: 64 consecutive ones per wavefront and ballot
+            // the samples collected so far, from LDS: 64 consecutive ones per wavefront and ballot.  Only a wavefront
+            // that holds a sample stores its word: the bit row ends ceil(stride / 64) words (+ 1) in, lcomp follows it,
+            // and the last block's idle wavefronts would put their zeros up to three words further -- into lcomp[0..7],
+            // which wave 0 of the same pass may still be reading when stride <= 128.  (The row was zeroed for this read.)
             for (int base = 0; base < nsofar; base += TPB) {
                 const int i = base + tid;
                 const bool in = i < nsofar && (int)lcomp[i] < itop;
                 const unsigned long long bits = __ballot(in);
-                if (lane == 0) { lbits[2 * (i >> 6)] = (unsigned)bits; lbits[2 * (i >> 6) + 1] = (unsigned)(bits >> 32); }
+                if (lane == 0 && base + 64 * w < nsofar) {
+                    lbits[2 * (i >> 6)] = (unsigned)bits; lbits[2 * (i >> 6) + 1] = (unsigned)(bits >> 32);
+                }
             }
             have = true;
         };

@@ -1,6 +1,7 @@
 """Seeded random cases for the kernel files that have no other randomised test in the suite -- csrc/sk_sweep.hip,
 sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, through the twins of the
-hit family sk_bg.hip and sk_events.hip, and for the switches of the screening scheme sk_sdtwq.hip: per family
+hit family sk_bg.hip and sk_events.hip, for the switches of the screening scheme sk_sdtwq.hip, and for both branches of the
+dRNA segmenter (sk_drna_walk.hip and the dRNA kernels of sk_prep.hip): per family
 draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
 what the reference says,  call_<family>(api, case, exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or
 the first difference as text.
@@ -8,7 +9,7 @@ the first difference as text.
 A plain module: not collected, no conftest, pure numpy, no GPU import at module level (`api` is handed in).  The same
 seed gives the same case on any machine: draw_* take a numpy.random.Generator and nothing else.  Used by
 tests/test_random_cases.py (CPU: the committed seeds reach what they claim), tests/test_gpu_random.py (GPU: every seed
-against its reference, plus two interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
+against its reference, plus three interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
 families is DRAW[family] with its running generator).  tests/RANDOM_CASES.md says what each family draws, the
 references, the budgets, the wall times, and which one-line kernel mutants the committed seeds catch.
 
@@ -16,7 +17,8 @@ The references are the statements that already exist: the oracle's scale_outlier
 sweep, reference_hits (test_hits_host.py), reference_paths (test_paths_host.py), numpy_pull_text (test_squigglepull.py),
 reference_panel (test_panel_host.py), detect_ref.py, hmm_ref.py, hmm_path_ref.py, plain numpy on the oracle's segments
 for the levels, reference_background_reads (test_background_host.py), reference_batch / reference_pool
-(test_events_host.py).  Every comparison is exact: integers as integers, doubles and text byte for byte.
+(test_events_host.py), the oracle's scale_outliers + drna_segs / drna_roll per read for the dRNA branches.  Every comparison
+is exact: integers as integers, doubles and text byte for byte.
 """
 import os
 import sys
@@ -38,19 +40,23 @@ SEEDS = {
     "hmm": [3, 10, 11, 15, 21, 35, 39, 54],
     "levels": [13, 18, 22, 26, 42, 59],
     "screen": [67, 106, 119, 157, 238, 268, 281, 333, 337, 383, 387],
+    "drna": [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 14, 15, 17, 18, 20, 22, 24, 27, 28, 29, 30, 31, 34, 35, 36, 37, 38, 39, 40,
+             54, 56, 65, 66, 74, 116, 117, 140, 170, 210],
+    "roll": [0, 1, 2, 3, 4, 10, 11, 13, 16, 21, 23, 24, 29, 31, 59],
 }
 
 # every tuning switch a case may set; a runner clears the ones a case does not name
 SWITCHES = ("SK_SEG_DELTA_SCALE", "SK_WALK_GENERAL", "SK_DTW_SMALL_MAX", "SK_HITS_ROW_BYTES", "SK_PATH_LDS_BYTES",
             "SK_PATH_SCRATCH_BYTES", "SK_DTW_NO_SMALL", "SK_PANEL_EXACT", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB",
             "SK_DTW_QL", "SK_DTW_HINT_MIN", "SK_DTW_NOHINT", "SK_DTW_CK", "SK_DTW_SORT_MIN", "SK_DTW_SCRATCH_MB",
-            "SK_DTW_NOFUSE", "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY")
+            "SK_DTW_NOFUSE", "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY", "SK_DRNA_STEP", "SK_ROLL_ONE_LOOK",
+            "SK_ROLL_DELTA_SCALE", "SK_ROLL_TWO_KERNELS")
 
 
 # the family's number in the seed of its generator.  Frozen: the first four are what sorted(SEEDS).index(family) gave when
 # the table held four keys, so those cases stay what they were (tests/test_random_cases.py pins their digests); a new
 # family takes the next free number, whatever its name.
-FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8)
+FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8, drna=9, roll=10)
 
 
 def rng_of(family, seed):
@@ -1749,6 +1755,561 @@ def diff_events(case, got, exp):
 
 
 # ======================================================================================================================
+# dRNA segmenter, slow5 branch: k_drna_stats / k_prep_i16<.., WINDOWED, ..> (sk_prep.hip), k_drna_walk(_runs)
+# ======================================================================================================================
+DRNA_SAMPLES = 4_000_000                         # samples the oracle walks per case (about 32 ns each, filter included)
+DRNA_COUNTS = (1, 63, 64, 65, 130, 257)          # one read per lane: a lone lane, a full wave and its neighbours, 5 waves
+DRNA_TILE = 8 * 256                              # k_drna_stats / k_prep_i16: 8 samples per thread, 256 threads
+DRNA_LENS = (0, 1, 63, 64, 65, 127, 128, 129, DRNA_TILE - 1, DRNA_TILE, DRNA_TILE + 1, 2 * DRNA_TILE)
+DRNA_LONG = 70000
+DRNA_W = (1, 2, 63, 64, 65, 100, 128, 1200, 1 << 24, (1 << 24) + 1)       # the scan by runs takes 64 <= w <= 2^24
+DRNA_ERROR = (0, 1, 5, 63, 64, 65, 100, -1)
+DRNA_SEG_DIST = (0, 1, 50, 10 ** 9)
+DRNA_NO_ERR = (0, -7, 2500, 2560, 10 ** 7, INT32_MAX)                     # 2500: mid-word; 2560 = 40 * 64
+DRNA_LIMITS = ((0, 1200), (300, 700), (0, 2049), (0, 2050), (-50, 2500))  # hi - lo - 1 = 2048 | 2049: the one-look gate
+DRNA_STD = (0.8, 0.0, -0.5, 1e6, -1e6, 0.2, 1.5)                          # 1e6: top > 32767; -1e6: nothing in band
+DRNA_WINDOWS = ((1000, 5000), (0, 2000), (0, 16384), (0, 16385), (700, 700), (1000, DRNA_TILE), (0, INT32_MAX))
+DRNA_STRIDES = (8, 64, 128, 136, 320, 384)       # ceil(stride / 64) against the blocks of 256 of finish_stats
+DRNA_ROUTES = ("list", "equal", "padded", "odd")
+DRNA_OUT = 30000                                 # a sample outside every pair of limits above
+DRNA_IN, DRNA_FAR = 400, 700                     # the two levels of a crafted read: in band, out of band
+DRNA_PREFIX = 64                                 # crafted reads: 8 samples of DRNA_FAR, 56 of DRNA_IN; t_start = 0, t_end = 64
+# sk_launch_prep_i16, restated: sizeof(Scratch) = 2 * 4 * 4 + 4 * 8 + 4 * 4 + 256 * 8 + 2 * 8 + 256 * 4 + 128 * 2 + 4 * 4
+PREP_SCRATCH_BYTES = 3440
+DRNA_LDS_GATE = 60 * 1024
+PREP_LDSCOMP_GATE = 40 * 1024
+DRNA_ONE_LOOK_STD = (0.0, 1e6, -1e6)             # signal variants 10 .. 12: these on the script's own parameters (k_drna_stats)
+# the variants of a case: (kind, argument); the first draw of draw_drna picks one
+DRNA_VARIANTS = ([("signal", i) for i in range(13)] + [("mask", i) for i in range(10)] +
+                 [("crafted", s) for s in ("bits", "rearm", "thresh", "prev_err", "merge", "overflow", "exact", "budget")] +
+                 [("stride", s) for s in DRNA_STRIDES] + [("long", s) for s in ("list", "lds-over", "lds-under")])
+
+
+def drna_lds_bytes(stride, nbins, t_end):
+    """Dynamic LDS of k_drna_stats as sk_launch_prep_i16 computes it."""
+    nb4 = (nbins + 3) & ~3
+    return PREP_SCRATCH_BYTES + 4 * nb4 + 4 * (2 * ((stride + 63) // 64) + 2) + 2 * (t_end + DRNA_TILE + 8)
+
+
+def drna_route(case, env=None):
+    """The statistics kernel a case takes: 'one-look' (k_drna_stats) or 'prep<lds|mem,win|all>' (k_prep_i16)."""
+    env = case["env"] if env is None else env
+    p, stride = case["params"], case["stride"]
+    lo, hi = max(p["lim_low"], -32769), min(p["lim_hi"], 32768)
+    nbins = max(0, hi - lo - 1)
+    t0, t1 = p["t_start"], p["t_end"]
+    if "SK_DRNA_STEP" not in env and 1 <= nbins <= 2048 and 0 <= t0 < t1 <= 16384 and stride < (1 << 19) and \
+            drna_lds_bytes(stride, nbins, t1) <= DRNA_LDS_GATE:
+        return "one-look"
+    ldscomp = PREP_SCRATCH_BYTES + 4 * ((nbins + 3) & ~3) + 2 * stride <= PREP_LDSCOMP_GATE
+    return "prep<%s,%s>" % ("lds" if ldscomp else "mem", "win" if t0 > 0 or t1 < INT32_MAX else "all")
+
+
+def drna_walk(case, env=None):
+    """sk_launch_drna_walk: 'runs' (k_drna_walk_runs) or 'step' (k_drna_walk)."""
+    env = case["env"] if env is None else env
+    p = case["params"]
+    runs = 64 <= p["w"] <= (1 << 24) and 0 <= p["window"] <= (1 << 24) and "SK_DRNA_STEP" not in env
+    return "runs" if runs else "step"
+
+
+def _mask_runs(*runs):
+    """(bit, count) pairs -> bool mask."""
+    return np.concatenate([np.full(int(n), bool(b)) for b, n in runs] + [np.zeros(0, dtype=bool)])
+
+
+def _pad_bits(mask, mod, bit=0):
+    """The mask lengthened by `bit` until its length is `mod` modulo 64."""
+    return np.concatenate([mask, np.full((mod - len(mask)) % 64, bool(bit))])
+
+
+def _two_level(mask):
+    return np.where(mask, DRNA_IN, DRNA_FAR).astype(np.int16)
+
+
+def _drna_prefix():
+    return _mask_runs((0, 8), (1, DRNA_PREFIX - 8))
+
+
+def _random_mask(rng, n):
+    """Runs of in-band and out-of-band samples with lengths around the seams of the scan: 1 .. 3, a word, the windows."""
+    out, total = [], 0
+    while total < n:
+        kind = int(rng.integers(6))
+        if kind == 0:                                # a long run with a few holes
+            b = rng.random(int(rng.integers(40, 400))) > float(_pick(rng, (0.0, 0.01, 0.05)))
+        elif kind == 1:                              # a run and a gap of exactly k
+            b = _mask_runs((1, _pick(rng, (1, 2, 62, 63, 64, 65, 127, 128, 129, 200))),
+                           (0, _pick(rng, (1, 2, 3, 5, 6, 7, 50, 51, 52, 64, 65))))
+        elif kind == 2:                              # alternating
+            per = int(rng.integers(2, 6))
+            b = (np.arange(int(rng.integers(20, 300))) % per != 0) ^ bool(rng.integers(2))
+        elif kind == 3:                              # a hole
+            b = np.zeros(int(rng.integers(1, 200)), dtype=bool)
+        elif kind == 4:                              # noise
+            b = rng.random(int(rng.integers(10, 300))) < rng.uniform(0.3, 0.95)
+        else:                                        # trains
+            on, off = int(rng.integers(30, 140)), int(rng.integers(1, 12))
+            b = (np.arange(int(rng.integers(100, 600))) % (on + off)) < on
+        out.append(np.asarray(b, dtype=bool))
+        total += len(b)
+    return np.concatenate(out)[:n] if out else np.zeros(0, dtype=bool)
+
+
+def _mask_read(rng, n):
+    """A two-level read of n samples: the clean prefix, then a random mask (n < DRNA_PREFIX: the prefix cut short)."""
+    return _two_level(np.concatenate([_drna_prefix(), _random_mask(rng, max(0, n - DRNA_PREFIX))])[:n])
+
+
+def _drna_crafted(rng, which):
+    """(params, masks, max_segs): reads whose band mask is the bit pattern given (see RANDOM_CASES.md), each behind the clean
+    prefix -- a run that opens at sample 8.  tests/test_random_cases.py finds every seam in a sample-level trace."""
+    pre = _drna_prefix()
+    P = dict(t_start=0, t_end=DRNA_PREFIX, std_scale=float(_pick(rng, (0.2, 0.8, 1.5))), lim_low=0, lim_hi=1200,
+             no_err_thresh=0)
+    max_segs = 32
+    if which == "bits":
+        # error 0: the first out-of-band sample closes.  A run of 63 from the sample behind a close: closed at bit 63 of the
+        # lane's window; a run of 64: the window is swallowed whole, the next one closes at its bit 0; a run of one sample
+        P.update(error=0, w=128, window=2, seg_dist=0)
+        masks = [np.concatenate([pre, _mask_runs((0, 1), (1, 63), (0, 1), (1, 64), (0, 1), (1, 1), (0, 1), (1, 30), (0, 9))]),
+                 np.concatenate([pre, _mask_runs((0, 1), (1, 64), (0, 1), (1, 63), (0, 3), (1, 1), (0, 2))])]
+    elif which == "rearm":
+        # w = 64, window = 0: c is a multiple of w at start + 63, + 127, ...: a run that opens on a word's first sample
+        # re-arms on its last one, a run that opens on the second sample re-arms on the next word's first one; 130 samples
+        # in band re-arm twice (err = -2), then error + 2 = 3 out-of-band samples are taken and the fourth closes
+        P.update(error=1, w=64, window=0, seg_dist=10 ** 9)
+        m = _pad_bits(np.concatenate([pre, _mask_runs((0, 10))]), 0)
+        m = np.concatenate([m, _mask_runs((1, 130), (0, 4))])
+        m = _pad_bits(m, 1)
+        m = np.concatenate([m, _mask_runs((1, 70), (0, 5), (1, 12), (0, 3))])
+        m2 = _pad_bits(np.concatenate([pre, _mask_runs((0, 3))]), 1)
+        m2 = np.concatenate([m2, _mask_runs((1, 200), (0, 1), (1, 5), (0, 1), (1, 5), (0, 1), (1, 5), (0, 1), (1, 5), (0, 9))])
+        masks = [m, m2]
+    elif which == "thresh":
+        # no_err_thresh = 200 (bit 8 of its word): three out-of-band samples before it are taken and not counted, the run goes
+        # on past it, takes error = 2 counted ones and closes at the third
+        P.update(error=2, no_err_thresh=200, w=1200, window=10, seg_dist=5)
+        masks = [np.concatenate([pre, _mask_runs((1, 100), (0, 3), (1, 40), (0, 2), (1, 5), (0, 1), (1, 20), (0, 40))]),
+                 np.concatenate([pre, _mask_runs((1, 130), (0, 1), (1, 5), (0, 1), (1, 5), (0, 2), (1, 9), (0, 30))])]
+    elif which == "prev_err":
+        # end = i - prev_err with the out-of-band tail inside one piece, and with it split over two pieces (a run that opens
+        # at sample 100 has its first piece end at sample 153: three of the tail before it, two and the closing one behind)
+        P.update(error=5, w=1200, window=10, seg_dist=0)
+        masks = [np.concatenate([pre, _mask_runs((1, 20), (0, 6), (0, 10), (1, 51), (0, 6), (1, 30), (0, 2), (1, 3), (0, 8))])]
+    elif which == "merge":
+        # gaps counted from the closing sample (error 0: end = the closing sample): a run 19 behind it merges, one 20 behind
+        # does not; 21 idle samples (i - last_end = 20) do not stop the scan, 22 do, with a run of 30 behind them
+        P.update(error=0, w=1200, window=5, seg_dist=20)
+        masks = [np.concatenate([pre, _mask_runs((0, 25), (1, 30), (0, 19), (1, 30), (0, 20), (1, 30), (0, 21), (1, 30), (0, 22),
+                                             (1, 30), (0, 5))]),
+                 np.concatenate([pre, _mask_runs((0, 19), (1, 3), (0, 1), (1, 40), (0, 30), (1, 40), (0, 5))])]
+    elif which == "overflow":
+        # more segments than the 32 columns the call begins with: SK_ERR_OVERFLOW, the call grows max_segs
+        P.update(error=0, w=64, window=2, seg_dist=1)
+        masks = [np.concatenate([pre] + [_mask_runs((0, 1 + k % 2), (1, 3 + k % 5)) for k in range(45)] + [_mask_runs((0, 4))])]
+    elif which == "exact":
+        # exactly max_segs = 4 segments, then a run that merges into the last one (the store at column nseg - 1 = max_segs - 1)
+        P.update(error=0, w=100, window=3, seg_dist=3)
+        max_segs = 4
+        masks = [np.concatenate([pre, _mask_runs((0, 3), (1, 5), (0, 3), (1, 5), (0, 4), (1, 5), (0, 2), (1, 7), (0, 3))])]
+    else:
+        # a budget of more than 64: whole windows of out-of-band samples are swallowed
+        P.update(error=int(_pick(rng, (65, 100))), w=int(_pick(rng, (64, 1200))), window=10, seg_dist=50)
+        masks = [np.concatenate([pre, rng.random(400) < 0.5, _mask_runs((0, 130), (1, 40), (0, 200))]),
+                 np.concatenate([pre, _mask_runs((1, 10), (0, 64), (1, 1), (0, 70), (1, 30), (0, 120))])]
+    return P, masks, max_segs
+
+
+def _drop(rng, x, frac):
+    if frac and len(x):
+        x = x.copy()
+        x[rng.random(len(x)) < frac] = DRNA_OUT
+    return x
+
+
+def _fill_reads(rng, count, budget, lo_len=300, hi_len=40000):
+    """`count` dRNA-like reads of about budget / count samples each."""
+    from squigglekit_amd import synth
+    if count <= 0:
+        return []
+    avg = max(lo_len + 1, min(hi_len, budget // count))
+    a, b = max(lo_len, avg // 2), max(lo_len + 2, min(hi_len, avg + avg // 2))
+    reads = synth.drna_reads(count, int(rng.integers(1 << 30)), min_len=a, max_len=b)
+    over, k = sum(len(r) for r in reads) - budget, 0
+    while over > 0:                                  # (the reference's CPU time: never more than the budget)
+        cut = min(over, len(reads[k]) // 2)
+        reads[k] = reads[k][:len(reads[k]) - cut]
+        over, k = over - cut, (k + 1) % count
+    return reads
+
+
+def _batch_rows(rng, reads, route, stride=None):
+    """(sig [R, stride] int16, lens, stride) for a batch route: 'equal' -- the longest row; 'padded' -- beyond it, a
+    multiple of 8, padding that is not zeros; 'odd' -- an odd stride (no vector loads)."""
+    longest = max([len(r) for r in reads] + [1])
+    if stride is None:
+        stride = {"equal": longest, "padded": (longest + 8 + int(rng.integers(0, 40))) // 8 * 8,
+                  "odd": (longest + int(rng.integers(0, 9))) | 1}[route]
+    sig = rng.integers(300, 700, size=(len(reads), stride)).astype(np.int16) if route != "equal" else \
+        np.zeros((len(reads), stride), dtype=np.int16)
+    for i, r in enumerate(reads):
+        sig[i, :len(r)] = r
+        if route == "equal":
+            sig[i, len(r):] = 555
+    return sig, np.array([len(r) for r in reads], dtype=np.int32), int(stride)
+
+
+def draw_drna(rng):
+    kind, arg = DRNA_VARIANTS[int(rng.integers(len(DRNA_VARIANTS)))]
+    P = dict(error=5, no_err_thresh=2500, w=1200, window=100, seg_dist=1200, t_start=1000, t_end=5000, std_scale=0.8,
+             lim_low=0, lim_hi=1200)
+    max_segs, route, stride, lost, crafted_at = 32, "list", None, "", None
+    if kind == "signal":
+        # the statistics: every window, pair of limits, std_scale and read count in turn; the scan's parameters with them
+        i = arg
+        w = DRNA_W[i % 10]
+        (P["lim_low"], P["lim_hi"]), (P["t_start"], P["t_end"]) = DRNA_LIMITS[i % 5], DRNA_WINDOWS[(i + 2) % 7]
+        short = i in (3, 4)                           # rows that k_prep_i16 keeps in LDS (its LDSCOMP instantiations)
+        P.update(w=w, window=int(_pick(rng, (0, 1, 30, 100, 250))), error=DRNA_ERROR[i % 8],
+                 seg_dist=DRNA_SEG_DIST[(i + 2) % 4], no_err_thresh=DRNA_NO_ERR[i % 6], std_scale=DRNA_STD[i % 7])
+        if i >= 10:                                   # the script's parameters, std_scale aside: the one-look kernel
+            P = dict(error=5, no_err_thresh=2500, w=1200, window=100, seg_dist=1200, t_start=1000, t_end=5000,
+                     std_scale=DRNA_ONE_LOOK_STD[i - 10], lim_low=0, lim_hi=1200)
+        R, route = DRNA_COUNTS[(i + 1) % 6], DRNA_ROUTES[i % 4]
+        t0, t1 = P["t_start"], min(P["t_end"], 6000 if short else 20000)
+        seams = list(DRNA_LENS) + [max(0, t0 - 1), t0, t0 + 1, t1 - 1, t1, t1 + 1]
+        special = [rng.integers(300, 700, size=n).astype(np.int16) for n in dict.fromkeys(seams)]
+        special.append(np.full(int(rng.integers(1, 3000)), DRNA_OUT, dtype=np.int16))          # nothing kept
+        x = rng.integers(300, 700, size=2 * DRNA_TILE + int(rng.integers(0, 3000))).astype(np.int16)
+        if DRNA_TILE <= t1 <= 2 * DRNA_TILE:
+            # t1 kept samples in the first two tiles exactly: the collection is complete at a tile's end
+            x[rng.choice(2 * DRNA_TILE, 2 * DRNA_TILE - t1, replace=False)] = DRNA_OUT
+        special.append(x)
+        special = [special[int(k)] for k in rng.permutation(len(special))][:R]
+        fill = _fill_reads(rng, R - len(special), DRNA_SAMPLES - sum(len(s) for s in special), 300, 6000 if short else 40000)
+        fracs = rng.choice([0.0, 0.01, 0.25], size=len(fill))
+        fill = [_drop(rng, f, float(q)) for f, q in zip(fill, fracs)]
+        lost = "".join("n" if q == 0 else "1" if q < 0.1 else "q" for q in fracs)[:40]
+        reads = special + fill
+    elif kind == "mask":
+        # the scan: two-level reads with a drawn mask behind the clean prefix; w and error in turn, the rest drawn
+        i = arg
+        w = DRNA_W[i]
+        # window against w (kw0, the first re-arming count): 0, 1, below, at and above w, a multiple of it -- in turn
+        window = (0, 1, max(0, w - 1 - int(rng.integers(0, 3))), w, w + int(rng.integers(1, 9)), 2 * w)[(i + 1) % 6]
+        if w >= (1 << 20):
+            window = int(_pick(rng, (0, 1, 30, 100)))
+        P.update(t_start=0, t_end=DRNA_PREFIX, std_scale=float(_pick(rng, (0.2, 0.8, 1.5))), w=w, window=window,
+                 error=DRNA_ERROR[(i + 3) % 8], seg_dist=int(_pick(rng, DRNA_SEG_DIST + (50, 200))),
+                 no_err_thresh=int(_pick(rng, (0, 0, -7, 100, 128, 300, 300, 10 ** 7, INT32_MAX))))
+        R, route = int(_pick(rng, DRNA_COUNTS[1:])), _pick(rng, DRNA_ROUTES)
+        lens = [int(_pick(rng, DRNA_LENS)) if rng.random() < 0.3 else int(rng.integers(DRNA_PREFIX, 6000)) for _ in range(R)]
+        reads = [_mask_read(rng, n) for n in lens]
+    elif kind == "crafted":
+        cp, masks, max_segs = _drna_crafted(rng, arg)
+        P.update(cp)
+        R, route = int(_pick(rng, (63, 65, 130))), _pick(rng, DRNA_ROUTES)
+        reads = [_two_level(m) for m in masks]
+        if arg != "exact":                            # (exact: no read may hold more than max_segs segments)
+            reads += [_mask_read(rng, int(rng.integers(DRNA_PREFIX, 3000))) for _ in range(R - len(reads))]
+        else:
+            reads += [_two_level(np.concatenate([_drna_prefix(), _mask_runs((0, 3), (1, int(rng.integers(3, 40))), (0, 9))]))
+                      for _ in range(R - len(reads))]
+        order = rng.permutation(len(reads))
+        reads = [reads[int(k)] for k in order]
+        crafted_at = [int(np.flatnonzero(order == k)[0]) for k in range(len(masks))]
+    elif kind == "stride":
+        # rows of at most `stride` samples that begin with eight out-of-band ones and end their collection at their own end
+        # (fewer than t_end kept): the last block of finish_stats has idle wavefronts (see RANDOM_CASES.md, "Found")
+        stride, route = int(arg), "equal"
+        P.update(t_start=0, t_end=1000, std_scale=0.8, error=0, no_err_thresh=0, w=64, window=int(_pick(rng, (2, 3))),
+                 seg_dist=int(_pick(rng, (0, 1, 50))))
+        R = int(_pick(rng, (130, 257)))
+        reads = []
+        for _ in range(R):
+            n = stride if rng.random() < 0.5 else int(rng.integers(max(1, stride - 63), stride + 1))
+            if stride == 8:
+                m = _mask_runs((0, 3), (1, 4), (0, 1))[:n] if rng.random() < 0.5 else rng.random(n) < 0.6
+            else:
+                body = _random_mask(rng, n)
+                body[:8] = False
+                k = int(body.sum())
+                if 2 * k <= n:                        # (the median stays the in-band level)
+                    body[8:8 + (n - 8) * 3 // 4] = True
+                m = body
+            reads.append(_two_level(np.asarray(m, dtype=bool)))
+    else:
+        from squigglekit_amd import synth
+        R = int(_pick(rng, (3, 4, 6)))
+        reads = _fill_reads(rng, R - 1, 200000, 3000, 60000)
+        reads.append(synth.drna_reads(1, int(rng.integers(1 << 30)), min_len=DRNA_LONG, max_len=DRNA_LONG + 20000)[0])
+        reads = [_drop(rng, x, float(_pick(rng, (0.0, 0.01)))) for x in reads]
+        reads = [reads[int(k)] for k in rng.permutation(R)]
+        if arg == "list":
+            P.update(t_start=0, t_end=INT32_MAX)      # the whole read is the window: k_prep_i16 without WINDOWED
+        else:
+            # t_end = 16384 and 2048 histogram bins: 48 520 + 8 * ceil(stride / 64) bytes against the gate of 61 440
+            route = "padded"
+            P.update(lim_low=0, lim_hi=2049, t_start=int(_pick(rng, (0, 1000))), t_end=16384)
+            stride = 103368 if arg == "lds-over" else 103360
+    case = dict(family="drna", kind=kind, arg=arg, route=route, params=P, max_segs=max_segs, nreads=len(reads), reads=reads,
+                longest=max([len(r) for r in reads] + [0]), lost=lost, env={})
+    if crafted_at is not None:
+        case["crafted_at"] = crafted_at
+    if route == "list":
+        case["stride"] = max(8, (case["longest"] + 7) // 8 * 8)                # api.pack_i16
+    else:
+        case["sig"], case["lens"], case["stride"] = _batch_rows(rng, reads, route, stride)
+    return case
+
+
+def expect_drna(ora, case):
+    """Per read every segment of ora.scale_outliers + ora.drna_segs; `top` and the kept count with them (CPU leg)."""
+    from concurrent.futures import ThreadPoolExecutor
+    p = case["params"]
+    op = ora.DrnaParams(**{k: v for k, v in p.items() if not k.startswith("lim")})
+
+    def one(x):
+        f = ora.scale_outliers(np.asarray(x, dtype=np.float64), p["lim_low"], p["lim_hi"])
+        segs, top = ora.drna_segs(f, op, max_segs=16384)
+        return segs, top, int(f.size)
+    with ThreadPoolExecutor(16) as ex:
+        rows = list(ex.map(one, case["reads"]))
+    assert all(len(r[0]) < 16384 for r in rows)
+    return dict(segs=[r[0] for r in rows], top=[r[1] for r in rows], kept=[r[2] for r in rows])
+
+
+def call_drna(api, case, exp=None):
+    from squigglekit_amd import _lib
+    p = _lib.DrnaParams(**case["params"])
+    if case["route"] == "list":
+        return api.drna_segment_reads(case["reads"], p, max_segs=case["max_segs"])
+    segs, nsegs = api.drna_segment_batch(case["sig"], case["lens"], p, max_segs=case["max_segs"])
+    return [segs[r, :nsegs[r]].tolist() for r in range(case["nreads"])]
+
+
+def diff_drna(case, got, exp):
+    if len(got) != case["nreads"]:
+        return "%d reads returned, want %d" % (len(got), case["nreads"])
+    for r, (g, w) in enumerate(zip(got, exp["segs"])):
+        if g != w:
+            k = next((k for k in range(min(len(g), len(w))) if g[k] != w[k]), min(len(g), len(w)))
+            return "read %d (%d samples, %d kept, top %r): %d segments, want %d; segment %d: got %s want %s" % (
+                r, len(case["reads"][r]), exp["kept"][r], exp["top"][r], len(g), len(w), k, g[k:k + 2], w[k:k + 2])
+    return None
+
+
+# ======================================================================================================================
+# dRNA segmenter, --signal branch: k_roll_stream / k_roll_one / k_roll_stats (sk_prep.hip), k_roll_walk
+# ======================================================================================================================
+ROLL_COUNTS = (1, 31, 32, 33, 63, 64, 65, 130)   # (the redo list of k_roll_stream runs on a grid of 32)
+ROLL_W = (1, 2, 7, 63, 64, 65, 2000, 8192, 12000, 12001, 65535, 65536, 300000)      # 300 000: above every read
+ROLL_STD = (0.5, 0.0, -3.0, 1e12, -1e12)
+ROLL_CHUNK = (8191, 8192, 8193, 16384)           # numpy's summation chunks
+ROLL_LDS_LONG = 35001                            # a row k_roll_one cannot hold in LDS
+ROLL_SCRATCH_LONG = (1 << 17) + 1                # a row beyond sk_roll_one_lds' limit: prefix sums in a scratch row
+ROLL_SHARED_BYTES = 2 * 16 * 4 * 2 + 5 * 64 * 8 + 6 * 8 + 2 * 8          # sizeof(RollShared)
+ROLL_VARIANTS = [("signal", i) for i in range(len(ROLL_W))] + [("crafted", 0), ("crafted", 1000)]
+
+
+def roll_stream_ok(stride, w, lo, hi):
+    """sk_roll_stream_ok, restated."""
+    if w > 12000 or stride > (1 << 21):
+        return False
+    smax = float(max(abs(lo), abs(hi))) * float(w)
+    return smax < 2147483000.0 and smax * smax * float(stride) < 9.0e18
+
+
+def roll_one_lds(stride, w):
+    """sk_roll_one_lds, restated: the LDS bytes of k_roll_one for rows of `stride` samples, 0 when they do not fit."""
+    if w >= 65536 or stride > (1 << 17):
+        return 0
+    i = stride + 1
+    need = PREP_SCRATCH_BYTES + ROLL_SHARED_BYTES + (i + (i >> 3) + 4) * 4
+    return need if need <= 160 * 1024 else 0
+
+
+def roll_route(case, env=None):
+    """drna_roll_dev's choice: 'stream' (k_roll_stream, its redo list through k_roll_one), 'one-look' (k_roll_one for every
+    read) or 'two-kernels' (compaction + k_roll_stats)."""
+    env = case["env"] if env is None else env
+    p, stride = case["params"], case["stride"]
+    lo, hi = max(p["lim_low"], -32769), min(p["lim_hi"], 32768)
+    stream = roll_stream_ok(stride, p["w"], lo, hi) and "SK_ROLL_ONE_LOOK" not in env
+    if (stream or roll_one_lds(stride, p["w"])) and "SK_ROLL_TWO_KERNELS" not in env and "SK_DRNA_STEP" not in env:
+        return "stream" if stream else "one-look"
+    return "two-kernels"
+
+
+def roll_scan(t, bot, seg_dist):
+    """dRNA_segmenter.py:296-316 on a rolling mean, sample by sample: (segments after merging, events).  Events:
+    ('equal', c) a t == bot sample inside or outside a run; ('merge' | 'new', start - last_end) for every run closed behind
+    another; ('open', start) a run still open at the end."""
+    begin, start, end, last_end, segs, ev = False, 0, 0, 0, [], []
+    for c, v in enumerate(t):
+        if v == bot:
+            ev.append(("equal", c, begin))
+        if v < bot and not begin:
+            start, begin = c, True
+        elif v < bot:
+            end = c
+        elif v > bot and begin:
+            if segs and start - last_end < seg_dist:
+                ev.append(("merge", start - last_end))
+                segs[-1][1] = end
+            else:
+                if segs:
+                    ev.append(("new", start - last_end))
+                segs.append([start, end])
+            last_end = end
+            start, end, begin = 0, 0, False
+    if begin:
+        ev.append(("open", start))
+    return segs, ev
+
+
+def _roll_numpy(x, w, std_scale):
+    """(t, bot) of a short integer read in plain numpy (window sums are exact; for the draw only: the reference's
+    t and bot are what the tests use)."""
+    x = np.asarray(x, dtype=np.int64)
+    if len(x) < w + 1:
+        return np.full(len(x), np.nan), np.nan
+    P = np.concatenate([[0], np.cumsum(x)])
+    t = np.concatenate([np.full(w - 1, np.nan), (P[w:] - P[:-w]) / float(w)])
+    v = t[w - 1:]
+    return t, float(v.mean() - v.std(ddof=1) * std_scale)
+
+
+def _blocks(*runs):
+    return np.concatenate([np.full(int(n), int(v), dtype=np.int16) for v, n in runs])
+
+
+def _roll_crafted(rng):
+    """Two-level block reads for w = 4, std_scale = 0 (bot = the mean of t, between the levels): (reads, lo_thresh,
+    hi_thresh, seg_dist).  Lengths and gaps are measured here in plain numpy and asserted by the CPU leg on the reference's
+    own trace."""
+    w, lo_v, hi_v, pad = 4, 400, 600, 60
+
+    def seglen(L):
+        x = _blocks((hi_v, pad), (lo_v, L), (hi_v, pad))
+        s, _ = roll_scan(*_roll_numpy(x, w, 0.0), 0)
+        return (s[0][1] - s[0][0]) if len(s) == 1 else None
+    L0, L1 = int(rng.integers(30, 45)), int(rng.integers(90, 120))
+    lo_t, hi_t = seglen(L0), seglen(L1)
+    reads = [_blocks((lo_v, 40), (hi_v, 40))]                                  # one t == bot = 500.0
+    reads += [_blocks((hi_v, pad), (lo_v, L), (hi_v, pad)) for L in (L0, L0 - 1, L1, L1 + 1)]
+    # two low blocks G apart: seg_dist = the gap the scan sees at G, plus one (merged); at G + 1 the gap is seg_dist (not merged)
+    seg_dist = None
+    for G in range(int(rng.integers(12, 20)), 60):
+        gaps = []
+        for g in (G, G + 1):
+            s, _ = roll_scan(*_roll_numpy(_blocks((hi_v, pad), (lo_v, 30), (hi_v, g), (lo_v, 30), (hi_v, pad)), w, 0.0), 0)
+            gaps.append(s[1][0] - s[0][1] if len(s) == 2 else None)
+        if None not in gaps and gaps[1] == gaps[0] + 1:
+            seg_dist = gaps[0] + 1
+            reads += [_blocks((hi_v, pad), (lo_v, 30), (hi_v, g), (lo_v, 30), (hi_v, pad)) for g in (G, G + 1)]
+            break
+    far = seg_dist + 40
+    reads.append(_blocks((hi_v, pad), (lo_v, L0 - 12), (hi_v, far), (lo_v, L0 + 9), (hi_v, pad)))      # first too short
+    reads.append(_blocks((hi_v, pad), (lo_v, 50)))                                                   # open at the end
+    reads.append(_blocks((hi_v, pad), (lo_v, L0 + 3), (hi_v, far), (lo_v, 50)))                       # a segment, then an open run
+    return reads, lo_t, hi_t, seg_dist
+
+
+def draw_roll(rng):
+    kind, arg = ROLL_VARIANTS[int(rng.integers(len(ROLL_VARIANTS)))]
+    P = dict(w=2000, seg_dist=1500, hi_thresh=200000, lo_thresh=2000, shift=1000, std_scale=0.5, lim_low=0, lim_hi=1200)
+    route = _pick(rng, ("list", "list", "padded", "odd"))
+    lost = ""
+    if kind == "signal":
+        i = arg
+        w = ROLL_W[i]
+        P.update(w=w, std_scale=ROLL_STD[i % 5], lo_thresh=int(_pick(rng, (3, 100, 2000))), shift=int(_pick(rng, (0, 1000))),
+                 seg_dist=int(_pick(rng, (2, 100, 1500, 100000))))
+        if rng.random() < 0.4:
+            P.update(lim_low=300, lim_hi=700)
+        R = ROLL_COUNTS[i % 8]
+        seams = [0, 1, w - 1, w, w + 1, 2 * w] + list(ROLL_CHUNK)
+        if i % 3 == 0 and w <= 12000:
+            seams.append(ROLL_LDS_LONG + int(rng.integers(0, 4000)))
+        if w == 65536:
+            seams.append(ROLL_SCRATCH_LONG + int(rng.integers(0, 3000)))
+        if w == 12001:
+            seams = [n for n in seams if n <= 34000]              # (this case stays on k_roll_one's LDS tier)
+        seams = [n for n in dict.fromkeys(seams) if n <= 140000]
+        special = []
+        for n in seams:
+            x = (450 + 60 * np.sin(np.arange(n) / 900.0) + rng.normal(0, 12, n)).astype(np.int16)
+            if n > 4000:
+                x[n // 3: n // 3 + 2500] -= 150                    # a low stretch of acceptable length
+            special.append(x)
+        special = [special[int(k)] for k in rng.permutation(len(special))][:R]
+        hi_len = 34000 if w == 12001 else 30000
+        fill = _fill_reads(rng, R - len(special), DRNA_SAMPLES - sum(len(s) for s in special), 2000, hi_len)
+        fracs = rng.choice([0.0, 0.01, 0.25], size=len(fill))
+        fill = [_drop(rng, f, float(q)) for f, q in zip(fill, fracs)]
+        lost = "".join("n" if q == 0 else "1" if q < 0.1 else "q" for q in fracs)[:40]
+        reads = special + fill
+    else:
+        reads, lo_t, hi_t, seg_dist = _roll_crafted(rng)
+        P.update(w=4, std_scale=0.0, lo_thresh=lo_t, hi_thresh=hi_t, seg_dist=seg_dist, shift=int(arg))
+        ncraft = len(reads)
+        R = int(_pick(rng, (33, 65)))
+        for _ in range(R - ncraft):                                 # block reads at random
+            runs = [(int(_pick(rng, (400, 600, 500, 450))), int(rng.integers(1, 90))) for _ in range(int(rng.integers(2, 12)))]
+            reads.append(_blocks(*runs))
+        reads[ncraft][::7] = DRNA_OUT                               # (dropped samples: the shift applies to filtered coordinates)
+    case = dict(family="roll", kind=kind, arg=arg, route=route, params=P, nreads=len(reads), reads=reads,
+                longest=max([len(r) for r in reads] + [0]), lost=lost, env={})
+    if kind == "crafted":
+        case["ncrafted"] = ncraft
+    if route == "list":
+        case["stride"] = max(8, (case["longest"] + 7) // 8 * 8)
+    else:
+        case["sig"], case["lens"], case["stride"] = _batch_rows(rng, reads, route)
+    return case
+
+
+def expect_roll(ora, case):
+    from concurrent.futures import ThreadPoolExecutor
+    p = case["params"]
+    op = ora.RollParams(**{k: v for k, v in p.items() if not k.startswith("lim")})
+
+    def one(x):
+        f = ora.scale_outliers(np.asarray(x, dtype=np.float64), p["lim_low"], p["lim_hi"])
+        return ora.drna_roll(f, op), int(f.size)
+    with ThreadPoolExecutor(16) as ex:
+        rows = list(ex.map(one, case["reads"]))
+    return dict(xy=[r[0] for r in rows], kept=[r[1] for r in rows])
+
+
+def call_roll(api, case, exp=None):
+    import ctypes as C
+    from squigglekit_amd import _lib
+    p = _lib.RollParams(**case["params"])
+    if case["route"] == "list":
+        return api.drna_roll_reads(case["reads"], p)
+    # the C entry point on rows of the case's own stride (api.drna_roll_reads packs to a multiple of 8)
+    L = _lib.ensure_init()
+    R = case["nreads"]
+    sig, lens = np.ascontiguousarray(case["sig"]), np.ascontiguousarray(case["lens"])
+    xy, found = np.zeros((R, 2), dtype=np.int32), np.zeros(R, dtype=np.int32)
+    _lib.check(L.sk_drna_roll_batch_i16(_lib.ptr(sig), case["stride"], _lib.ptr(lens), R, C.byref(p), _lib.ptr(xy),
+                                        _lib.ptr(found)))
+    return [(int(xy[i, 0]), int(xy[i, 1])) if found[i] else None for i in range(R)]
+
+
+def diff_roll(case, got, exp):
+    if len(got) != case["nreads"]:
+        return "%d reads returned, want %d" % (len(got), case["nreads"])
+    for r, (g, w) in enumerate(zip(got, exp["xy"])):
+        if g != w:
+            return "read %d (%d samples, %d kept): got %s want %s" % (r, len(case["reads"][r]), exp["kept"][r], g, w)
+    return None
+
+
+# ======================================================================================================================
 # the older single-set calls, for the interleaved sequence only
 # ======================================================================================================================
 def draw_plain(rng, kind):
@@ -1825,16 +2386,17 @@ def result_bytes(got):
 
 
 DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull, panel=draw_panel, detect=draw_detect,
-            hmm=draw_hmm, levels=draw_levels, screen=draw_screen)
+            hmm=draw_hmm, levels=draw_levels, screen=draw_screen, drna=draw_drna, roll=draw_roll)
 EXPECT = dict(sweep=expect_sweep, hits=expect_hits, paths=expect_paths, pull=expect_pull, segment=expect_plain,
               motifseq=expect_plain, pa=expect_plain, panel=expect_panel, detect=expect_detect, hmm=expect_hmm,
-              levels=expect_levels, background=expect_background, events=expect_events, screen=expect_screen)
+              levels=expect_levels, background=expect_background, events=expect_events, screen=expect_screen,
+              drna=expect_drna, roll=expect_roll)
 CALL = dict(sweep=call_sweep, hits=call_hits, paths=call_paths, pull=call_pull, segment=call_plain, motifseq=call_plain,
             pa=call_plain, panel=call_panel, detect=call_detect, hmm=call_hmm, levels=call_levels,
-            background=call_background, events=call_events, screen=call_screen)
+            background=call_background, events=call_events, screen=call_screen, drna=call_drna, roll=call_roll)
 DIFF = dict(sweep=diff_sweep, hits=diff_hits, paths=diff_paths, pull=diff_pull, segment=diff_plain, motifseq=diff_plain,
             pa=diff_plain, panel=diff_panel, detect=diff_detect, hmm=diff_hmm, levels=diff_levels,
-            background=diff_background, events=diff_events, screen=diff_screen)
+            background=diff_background, events=diff_events, screen=diff_screen, drna=diff_drna, roll=diff_roll)
 TWIN_OF = dict(background="hits", events="paths")
 
 # ---- the interleaved sequence (tests/test_gpu_random.py::test_interleaved_calls_share_the_context_buffers) --------
@@ -1853,6 +2415,15 @@ INTERLEAVE2 = [("panel", 4), ("hmm", 3), ("detect", 4), ("background", 1), ("swe
                ("hmm", 3), ("paths", 12), ("detect", 6), ("background", 324), ("panel", 36), ("segment", 3), ("levels", 13),
                ("events", 12), ("hmm", 10), ("detect", 4), ("motifseq", 2), ("panel", 93), ("screen", 268),
                ("levels", 22), ("screen", 337), ("hits", 1), ("screen", 268)]
+
+
+# the third sequence: the two branches of the dRNA segmenter between segmenter, levels, hit-list and detector calls -- of
+# each branch a large case before a small one (257 reads of 4 000 000 samples before 65 two-level reads; rows of 134 000
+# samples on the two-kernel path before rows of 650), cases that come twice, the per-sample switches between them
+INTERLEAVE3 = [("drna", 1), ("segment", 3), ("roll", 0), ("levels", 13), ("drna", 39), ("hits", 1), ("roll", 2),
+               ("detect", 4), ("drna", 14), ("segment", 0), ("roll", 10), ("drna", 39), ("levels", 22), ("roll", 2),
+               ("hits", 324), ("drna", 0), ("roll", 16), ("detect", 27), ("drna", 54), ("roll", 0), ("segment", 3),
+               ("drna", 1), ("roll", 1), ("drna", 15)]
 
 
 def interleave_case(family, seed):

@@ -74,6 +74,45 @@ def test_gpu_matches_oracle_and_reference(gpu, ora, example_read):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("stride", [8, 64, 128, 320, 384])
+def test_gpu_stats_bit_row_store_stays_inside_the_row(gpu, ora, stride):
+    """k_drna_stats classifies what it has collected in blocks of 256 samples, one 64-bit word of the LDS bit row per
+    wavefront.  The row holds ceil(stride / 64) words (+ 1), the collected samples lie directly behind it: a wavefront of
+    the last block without a sample must not store its (zero) word, or -- with ceil(stride / 64) = 4 f + 1 or 4 f + 2, f the
+    last block -- zeros land in the first eight collected samples, which the first wavefront of the same pass is still
+    classifying when stride <= 128.  A zero is in band (top > 0): the first segment would start at 0 instead of 8.
+    Rows that end their collection at their own end (fewer than t_end kept), eight out-of-band samples first, a small
+    window, 300 rows per call; every segment against the oracle."""
+    from squigglekit_amd import api
+    from squigglekit_amd._lib import DrnaParams
+    rng = np.random.default_rng(stride)
+    R = 300
+    sig = np.full((R, stride), 555, dtype=np.int16)
+    lens = np.zeros(R, dtype=np.int32)
+    for r in range(R):
+        if stride == 8:
+            x = [700, 700, 700, 400, 400, 400, 400, 700]
+        else:
+            n = stride if r % 2 else int(rng.integers(max(64, stride - 63), stride + 1))
+            x = [700] * 8
+            while len(x) < n:
+                x += [400] * int(rng.integers(2, 20)) + [700]
+            x = x[:n - 1] + [700]
+        sig[r, :len(x)] = x
+        lens[r] = len(x)
+    kw = dict(t_start=0, t_end=1000, error=0, no_err_thresh=0, w=64, window=2, seg_dist=0)
+    segs, nsegs = api.drna_segment_batch(sig, lens, DrnaParams(**kw))
+    total = 0
+    for r in range(R):
+        f = ora.scale_outliers(sig[r, :lens[r]].astype(float), 0, 1200)
+        want, top = ora.drna_segs(f, ora.DrnaParams(**kw), max_segs=16384)
+        assert 400 < top < 700 and want[0][0] == (3 if stride == 8 else 8)
+        assert segs[r, :nsegs[r]].tolist() == want, (stride, r, int(lens[r]))
+        total += len(want)
+    assert total >= R
+
+
+@pytest.mark.gpu
 def test_drna_cli_gpu(gpu, example_read, capsys):
     import os
     from conftest import GOLD

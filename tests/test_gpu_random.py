@@ -2,8 +2,10 @@
 MotifSeq hit lists (sk_hits.hip + k_sdtw's row output), alignment paths (sk_path.hip), SquigglePull text (sk_pull.hip),
 the region + motif panel (sk_panel.hip), event detection (sk_detect.hip), the signal HMM and its state paths
 (sk_hmm.hip), segment levels (sk_seglev.hip), the read background (sk_bg.hip) and events (sk_events.hip) twins of the
-hit family, and the switches of the screening scheme (sk_sdtwq.hip) -- through the public api call, against its reference, exactly; and two interleaved sequences of calls over
-the shared grow-only context buffers.  tests/test_random_cases.py (CPU) asserts what the seeds
+hit family, the switches of the screening scheme (sk_sdtwq.hip), and both branches of the dRNA segmenter (sk_drna_walk.hip,
+k_drna_stats / k_roll_* of sk_prep.hip; host and device entry points) -- through the public api call, against its reference,
+exactly; and three interleaved sequences of calls over the shared grow-only context buffers.
+tests/test_random_cases.py (CPU) asserts what the seeds
 reach; tests/RANDOM_CASES.md lists the one-line kernel mutants these tests catch.  A failure names family, seed, the
 drawn parameters and switches, and the first differing (read, hit / set / line): `randcases.case_of(family, seed)`
 rebuilds the case on any machine."""
@@ -185,6 +187,147 @@ def test_events_twin_of_the_paths_seed(gpu, ora, monkeypatch, seed):
     run_case(monkeypatch, ora, rc.interleave_case("events", seed))
 
 
+def same_under(monkeypatch, ora, case, got, switches):
+    """The case again under each (switch, value): every record the oracle's still, and the bytes the first call's."""
+    for key, val in switches:
+        again, _ = run_case(monkeypatch, ora, dict(case, env=dict(case["env"], **{key: val})))
+        assert rc.result_bytes(again) == rc.result_bytes(got), "%s %s=%s" % (rc.describe(case), key, val)
+
+
+@pytest.mark.parametrize("seed", rc.SEEDS["drna"])
+def test_drna_seed_matches_the_oracle(gpu, ora, monkeypatch, seed):
+    """dRNA_segmenter's slow5 branch on a drawn case (read count, lengths, route and stride, limits, statistics window,
+    std_scale, the scan's five parameters; two-level reads whose band mask is a drawn or crafted bit pattern): every segment
+    of every read the oracle's.  Then under SK_DRNA_STEP=1 -- k_prep_i16 for the statistics and the per-sample scan
+    k_drna_walk whatever w is -- the same bytes."""
+    case = rc.case_of("drna", seed)
+    got, exp = run_case(monkeypatch, ora, case)
+    assert got == exp["segs"], rc.describe(case)
+    same_under(monkeypatch, ora, case, got, [("SK_DRNA_STEP", "1")])
+
+
+@pytest.mark.parametrize("seed", rc.SEEDS["roll"])
+def test_roll_seed_matches_the_oracle(gpu, ora, monkeypatch, seed):
+    """The --signal branch on a drawn case: (x, y) or None per read as the oracle has them, no read left out; then
+    k_roll_one for every read, every read through the redo list, the two-kernel path and the per-sample scan: the same bytes."""
+    case = rc.case_of("roll", seed)
+    got, exp = run_case(monkeypatch, ora, case)
+    assert got == exp["xy"], rc.describe(case)
+    same_under(monkeypatch, ora, case, got, [("SK_ROLL_ONE_LOOK", "1"), ("SK_ROLL_DELTA_SCALE", "1e13"),
+                                             ("SK_ROLL_TWO_KERNELS", "1"), ("SK_DRNA_STEP", "1")])
+
+
+def _rows_of(case):
+    """(sig [R, stride], lens) as the case's route hands them to the C entry point."""
+    from squigglekit_amd import api
+    if case["route"] == "list":
+        return api.pack_i16(case["reads"])
+    return np.ascontiguousarray(case["sig"]), np.ascontiguousarray(case["lens"])
+
+
+class DevBuffers:
+    """Device buffers for one call of a device entry point: uploaded arrays and outputs with a guard area behind them."""
+    GUARD = 256
+
+    def __init__(self, L):
+        self.L, self.ptrs = L, []
+
+    def up(self, a):
+        from squigglekit_amd import _lib
+        d = self.L.sk_dev_alloc(max(a.nbytes, 8))
+        self.ptrs.append(d)
+        _lib.check(self.L.sk_dev_upload(d, _lib.ptr(a), a.nbytes))
+        return d
+
+    def out(self, nbytes):
+        return self.up(np.full(nbytes + self.GUARD, 0x5A, dtype=np.uint8))
+
+    def down(self, d, shape, dtype):
+        from squigglekit_amd import _lib
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        raw = np.zeros(n + self.GUARD, dtype=np.uint8)
+        _lib.check(self.L.sk_dev_download(_lib.ptr(raw), d, raw.nbytes))
+        assert np.all(raw[n:] == 0x5A), "bytes written behind the output"
+        return raw[:n].view(dtype).reshape(shape)
+
+    def free(self):
+        for d in self.ptrs:
+            self.L.sk_dev_free(d)
+
+
+# one-look statistics + scan by runs | k_prep_i16 (LDS need past the gate) | one-look + the per-sample scan (w = 63); and
+# the case with 46 segments in a read for the call that is given too few columns
+DRNA_DEVICE_SEEDS = (0, 14, 17)
+DRNA_OVERFLOW_SEED = 15
+# k_roll_stream | k_roll_one for every read (w = 12 001) | the two-kernel path (w = 65 536, a row above 2^17)
+ROLL_DEVICE_SEEDS = (31, 16, 0)
+
+
+@pytest.mark.parametrize("seed", DRNA_DEVICE_SEEDS + (DRNA_OVERFLOW_SEED,))
+def test_drna_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed):
+    """sk_drna_segment_dev_i16 -- what the benchmark times -- on device buffers against the host form on the same rows:
+    the same segments and counts, nothing written behind either output.  With too few columns the host form returns
+    SK_ERR_OVERFLOW and both forms leave the true counts in nsegs and the first max_segs segments in segs."""
+    import ctypes as C
+    from squigglekit_amd import _lib
+    L = _lib.ensure_init()
+    case = rc.case_of("drna", seed)
+    for key in rc.SWITCHES:
+        monkeypatch.delenv(key, raising=False)
+    want = rc.expect_drna(ora, case)["segs"]
+    counts = np.array([len(s) for s in want], dtype=np.int32)
+    sig, lens = _rows_of(case)
+    R, stride = sig.shape
+    p = _lib.DrnaParams(**case["params"])
+    for max_segs in ([int(counts.max()) + 1, 4] if seed == DRNA_OVERFLOW_SEED else [max(case["max_segs"], int(counts.max()))]):
+        assert seed != DRNA_OVERFLOW_SEED or counts.max() > 32
+        segs, nsegs = np.zeros((R, max_segs, 2), dtype=np.int32), np.zeros(R, dtype=np.int32)
+        code = L.sk_drna_segment_batch_i16(_lib.ptr(sig), stride, _lib.ptr(lens), R, C.byref(p), _lib.ptr(segs), _lib.ptr(nsegs),
+                                           max_segs)
+        assert code == (_lib.SK_ERR_OVERFLOW if counts.max() > max_segs else _lib.SK_OK), rc.describe(case)
+        assert np.array_equal(nsegs, counts), rc.describe(case)
+        for r in range(R):
+            assert segs[r, :min(counts[r], max_segs)].tolist() == want[r][:max_segs], (rc.describe(case), r)
+        dev = DevBuffers(L)
+        try:
+            d_sig, d_len = dev.up(sig), dev.up(lens)
+            d_segs, d_n = dev.out(segs.nbytes), dev.out(nsegs.nbytes)
+            _lib.check(L.sk_drna_segment_dev_i16(d_sig, stride, d_len, R, C.byref(p), d_segs, d_n, max_segs))
+            _lib.check(L.sk_sync())
+            assert dev.down(d_n, nsegs.shape, np.int32).tobytes() == nsegs.tobytes(), rc.describe(case)
+            assert dev.down(d_segs, segs.shape, np.int32).tobytes() == segs.tobytes(), rc.describe(case)
+        finally:
+            dev.free()
+
+
+@pytest.mark.parametrize("seed", ROLL_DEVICE_SEEDS)
+def test_roll_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed):
+    """sk_drna_roll_dev_i16 on device buffers against the host form and the oracle on the same rows."""
+    import ctypes as C
+    from squigglekit_amd import _lib
+    L = _lib.ensure_init()
+    case = rc.case_of("roll", seed)
+    for key in rc.SWITCHES:
+        monkeypatch.delenv(key, raising=False)
+    want = rc.expect_roll(ora, case)["xy"]
+    sig, lens = _rows_of(case)
+    R, stride = sig.shape
+    p = _lib.RollParams(**case["params"])
+    xy, found = np.zeros((R, 2), dtype=np.int32), np.zeros(R, dtype=np.int32)
+    _lib.check(L.sk_drna_roll_batch_i16(_lib.ptr(sig), stride, _lib.ptr(lens), R, C.byref(p), _lib.ptr(xy), _lib.ptr(found)))
+    assert [(int(xy[r, 0]), int(xy[r, 1])) if found[r] else None for r in range(R)] == want, rc.describe(case)
+    dev = DevBuffers(L)
+    try:
+        d_sig, d_len = dev.up(sig), dev.up(lens)
+        d_xy, d_found = dev.out(xy.nbytes), dev.out(found.nbytes)
+        _lib.check(L.sk_drna_roll_dev_i16(d_sig, stride, d_len, R, C.byref(p), d_xy, d_found))
+        _lib.check(L.sk_sync())
+        assert dev.down(d_found, found.shape, np.int32).tobytes() == found.tobytes(), rc.describe(case)
+        assert dev.down(d_xy, xy.shape, np.int32).tobytes() == xy.tobytes(), rc.describe(case)
+    finally:
+        dev.free()
+
+
 def run_sequence(monkeypatch, ora, seq):
     seen = {}
     for step, (fam, seed) in enumerate(seq):
@@ -214,3 +357,10 @@ def test_newer_calls_interleaved_with_the_older_ones(gpu, ora, monkeypatch):
     older families (c->sig / len / off / out / out2 / misc / comp / prep are shared through sk_reserve); at the end three
     screening calls, whose checkpoint, last-row and state buffers are used again after calls of other families."""
     run_sequence(monkeypatch, ora, rc.INTERLEAVE2)
+
+
+def test_drna_calls_interleaved_with_the_segmenter_and_the_detector(gpu, ora, monkeypatch):
+    """Both dRNA branches between segmenter, levels, hit-list and detector calls: c->mask, prep, comp and misc are the same
+    grow-only buffers for all of them (the rolling branch lays two masks and its redo list or its prefix sums in them, the
+    slow5 branch transposed words of nreads rows), a large case of each family before a small one."""
+    run_sequence(monkeypatch, ora, rc.INTERLEAVE3)

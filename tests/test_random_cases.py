@@ -884,3 +884,358 @@ def test_second_interleaved_sequence_is_what_it_claims():
     new = [i for i, (f, _) in enumerate(seq) if f in ("panel", "detect", "hmm", "levels")]
     assert any(size[i] > max(size[:i]) for i in new[1:])                    # a newer family grows the shared buffers
     assert any(size[i] < size[i - 1] // 4 for i in new if i)               # and one runs in buffers left much larger
+
+
+# ---- the dRNA segmenter, slow5 branch -----------------------------------------------------------------------------------
+def _runs_of(mask):
+    """Lengths of the in-band runs of a bool mask that an out-of-band sample follows."""
+    m = np.concatenate([[False], np.asarray(mask, dtype=bool), [False]])
+    d = np.flatnonzero(m[1:] != m[:-1])
+    return [int(b - a) for a, b in zip(d[::2], d[1::2]) if b < len(mask)]
+
+
+def drna_seams(case, mask):
+    """Labels of the scan's seams in one read's band mask: from the sample-level trace of the reference scan (drna_trace)
+    and, for the 64-sample windows of a lane, from the trips of the piece model (_drna_pieces); both are held to the oracle
+    by tests/test_walk_model.py."""
+    from test_walk_model import _drna_pieces, drna_trace
+    p = case["params"]
+    scan = (p["error"], p["no_err_thresh"], p["w"], p["window"], p["seg_dist"])
+    net, sd = p["no_err_thresh"], p["seg_dist"]
+    segs, ev = drna_trace(mask, *scan)
+    f = set()
+    closes = [e for e in ev if e[0] == "close"]
+    for e in ev:
+        if e[0] == "rearm" and e[1] % 64 in (0, 63):
+            f.add("re-arm on the %s sample of a word" % ("last" if e[1] % 64 == 63 else "first"))
+        elif e[0] == "free" and net % 64 and any(c[2] < e[1] < net < c[1] for c in closes):
+            f.add("a piece cut by no_err_thresh in mid-word takes a sample it does not count")
+        elif e[0] == "short":
+            f.add("a run shorter than window")
+        elif e[0] == "idle" and e[1] == sd:
+            f.add("no stop at i - last_end = seg_dist")
+        elif e[0] == "stop" and e[2] == sd + 1 and any(n >= max(p["window"], 1) for n in _runs_of(mask[e[1]:])):
+            f.add("stop at i - last_end = seg_dist + 1 with a run behind it")
+        elif e[0] == "close":
+            _, i, start, end, prev_err, merged, gap, low, spent = e
+            if low <= -2 and spent >= p["error"] + 2:
+                f.add("err < 0 after two re-arms, then the larger budget spent")
+            if merged and gap == sd - 1:
+                f.add("merge at seg_dist - 1")
+            if not merged and gap == sd:
+                f.add("no merge at seg_dist")
+            if spent > 64:
+                f.add("more than 64 counted samples taken by one run")
+    if len(segs) > case["max_segs"]:
+        f.add("more segments than max_segs")
+    if len(segs) == case["max_segs"] and closes and closes[-1][5]:
+        f.add("max_segs segments and a merge into the last")
+    if rc.drna_walk(case) == "runs":
+        trips = []
+        assert _drna_pieces(mask, *scan, trips=trips) == segs
+        for t in trips:
+            if t[0] == "close":
+                _, pos, q, L, before, prev_err, counted = t
+                if q in (0, 63):
+                    f.add("closed at bit %d of the lane's window" % q)
+                if prev_err > 0 and before:
+                    f.add("end = i - prev_err inside one piece")
+                if prev_err > q and not before:
+                    f.add("end = i - prev_err across two pieces")
+    return f
+
+
+def drna_features(ora, case, exp):
+    p, R, kept = case["params"], case["nreads"], exp["kept"]
+    t0, t1, w, win, net = p["t_start"], p["t_end"], p["w"], p["window"], p["no_err_thresh"]
+    lo, hi = p["lim_low"], p["lim_hi"]
+    stats = rc.drna_route(case)
+    f = {"R=%d" % R if R < 200 else "R>=200", "route=" + case["route"], "stats=" + stats, "walk=" + rc.drna_walk(case),
+         "limits=(%d, %d)" % (lo, hi), "bins=%d" % (hi - lo - 1), "w=%d" % w, "error=%d" % p["error"],
+         "seg_dist=%d" % p["seg_dist"], "std_scale=%g" % p["std_scale"]}
+    assert rc.drna_walk(case, {"SK_DRNA_STEP": "1"}) == "step" and rc.drna_route(case, {"SK_DRNA_STEP": "1"}) != "one-look"
+    if case["kind"] == "stride":
+        f.add("stride=%d, t_start=0" % case["stride"])
+        assert t0 == 0 and all(len(r) < t1 for r in case["reads"])
+    if R % 64:
+        f.add("dead lanes in the last wave")
+    for a in range(0, R, 64):
+        if len({(k - 1) // 64 for k in kept[a:a + 64] if k}) >= 3:
+            f.add("a wave's reads end at three or more words")
+    for x, k in zip(case["reads"], kept):
+        n = len(x)
+        if n in rc.DRNA_LENS:
+            f.add("len=%d" % n)
+        for d in (-1, 0, 1):
+            if n == t0 + d and t0 > 0:
+                f.add("len=t_start%+d" % d)
+            if n == t1 + d:
+                f.add("len=t_end%+d" % d)
+        if n >= rc.DRNA_LONG:
+            f.add("len>=70000")
+        if n and not k:
+            f.add("nothing kept")
+        if 0 < k < t1:
+            f.add("a read ends before t_end")
+        if k and k == t0:
+            f.add("t_start at the kept count")
+        if 0 < k < t0:
+            f.add("t_start beyond the kept count")
+        if n > 1000 and 0.005 < 1 - k / n < 0.02:
+            f.add("1 % of a read dropped")
+        if n > 1000 and 0.2 < 1 - k / n < 0.3:
+            f.add("25 % of a read dropped")
+        if k > t1 and n >= rc.DRNA_TILE and t1 < (1 << 20):
+            keep = (x > lo) & (x < hi)
+            at = np.cumsum(keep)[rc.DRNA_TILE - 1::rc.DRNA_TILE]
+            if t1 in at.tolist():
+                f.add("kept count reaches t_end at a tile's end")
+    # the gates of sk_launch_prep_i16
+    if t1 in (16384, 16385):
+        f.add("t_end=%d" % t1)
+    if t0 == t1:
+        f.add("t_start=t_end")
+    if 1 <= hi - lo - 1 <= 2048 and 0 <= t0 < t1 <= 16384 and case["stride"] < (1 << 19):
+        need = rc.drna_lds_bytes(case["stride"], hi - lo - 1, t1)
+        assert (stats == "one-look") == (need <= rc.DRNA_LDS_GATE)
+        if abs(need - rc.DRNA_LDS_GATE) <= 8:
+            f.add("LDS need %s the gate" % ("at" if need <= rc.DRNA_LDS_GATE else "past"))
+    else:
+        assert stats != "one-look"
+    # top
+    tops = [t for t, k in zip(exp["top"], kept) if k > t0]
+    if p["std_scale"] == 0:
+        f |= {"std_scale=0, median %s" % ("integer" if t == int(t) else "ends in .5") for t in tops}
+    if any(t > 32767 for t in tops):
+        f.add("top > 32767")
+    if p["std_scale"] < 0 and any(t <= lo for t in tops):
+        f.add("nothing in band")
+    if any(np.isnan(t) for t, k in zip(exp["top"], kept) if k):
+        f.add("NaN band")
+        assert all(not s for s, t in zip(exp["segs"], exp["top"]) if np.isnan(t))
+    # the scan's parameters
+    f.add("window " + ("= 0" if win == 0 else "= 1" if win == 1 else "< w" if win < w else "= w" if win == w else
+                       "= k w" if win % w == 0 else "> w"))
+    most = max(kept)
+    f.add("no_err_thresh " + ("= 0" if net == 0 else "< 0" if net < 0 else "= 2^31 - 1" if net == rc.INT32_MAX else
+                              "beyond the read" if net >= most else "on a multiple of 64" if net % 64 == 0 else "in mid-word"))
+    if case["kind"] in ("mask", "crafted"):          # two-level reads: the band mask is the drawn bit pattern
+        for x, t in zip(case["reads"], exp["top"]):
+            assert len(x) < rc.DRNA_PREFIX or (rc.DRNA_IN < t < rc.DRNA_FAR and set(np.unique(x)) <= {rc.DRNA_IN, rc.DRNA_FAR})
+    if case["kind"] == "crafted":
+        for r in case["crafted_at"]:
+            x = case["reads"][r]
+            assert rc.DRNA_IN < exp["top"][r] < rc.DRNA_FAR and set(np.unique(x)) <= {rc.DRNA_IN, rc.DRNA_FAR}
+            f |= drna_seams(case, x < exp["top"][r])
+    return f
+
+
+DRNA_REQUIRED = ({"R=%d" % n for n in rc.DRNA_COUNTS if n < 200} | {"R>=200"} | {"len=%d" % n for n in rc.DRNA_LENS} |
+                 {"len=t_start%+d" % d for d in (-1, 0, 1)} | {"len=t_end%+d" % d for d in (-1, 0, 1)} |
+                 {"route=" + r for r in rc.DRNA_ROUTES} | {"stride=%d, t_start=0" % s for s in rc.DRNA_STRIDES} |
+                 {"limits=(%d, %d)" % l for l in rc.DRNA_LIMITS} | {"bins=2048", "bins=2049"} |
+                 {"stats=one-look", "stats=prep<lds,win>", "stats=prep<mem,win>", "stats=prep<lds,all>", "stats=prep<mem,all>",
+                  "walk=runs", "walk=step"} |
+                 {"w=%d" % w for w in rc.DRNA_W} | {"error=%d" % e for e in rc.DRNA_ERROR} |
+                 {"seg_dist=%d" % s for s in rc.DRNA_SEG_DIST} | {"std_scale=%g" % s for s in rc.DRNA_STD} |
+                 {"window " + s for s in ("= 0", "= 1", "< w", "= w", "> w", "= k w")} |
+                 {"no_err_thresh " + s for s in ("= 0", "< 0", "in mid-word", "on a multiple of 64", "beyond the read",
+                                                 "= 2^31 - 1")} |
+                 {"dead lanes in the last wave", "a wave's reads end at three or more words", "len>=70000", "nothing kept",
+                  "a read ends before t_end", "t_start at the kept count", "t_start beyond the kept count",
+                  "1 % of a read dropped", "25 % of a read dropped", "kept count reaches t_end at a tile's end",
+                  "t_end=16384", "t_end=16385", "t_start=t_end", "LDS need at the gate", "LDS need past the gate",
+                  "std_scale=0, median integer", "std_scale=0, median ends in .5", "top > 32767", "nothing in band", "NaN band",
+                  "re-arm on the last sample of a word", "re-arm on the first sample of a word",
+                  "a piece cut by no_err_thresh in mid-word takes a sample it does not count", "a run shorter than window",
+                  "no stop at i - last_end = seg_dist", "stop at i - last_end = seg_dist + 1 with a run behind it",
+                  "err < 0 after two re-arms, then the larger budget spent", "merge at seg_dist - 1", "no merge at seg_dist",
+                  "more than 64 counted samples taken by one run", "more segments than max_segs",
+                  "max_segs segments and a merge into the last", "closed at bit 0 of the lane's window",
+                  "closed at bit 63 of the lane's window", "end = i - prev_err inside one piece",
+                  "end = i - prev_err across two pieces"})
+
+
+def test_drna_cases_reach_every_boundary(ora, cases):
+    have, segments = set(), 0
+    for case, exp in cases["drna"]:
+        assert sum(len(r) for r in case["reads"]) <= rc.DRNA_SAMPLES, rc.describe(case)
+        have |= drna_features(ora, case, exp)
+        segments += sum(len(s) for s in exp["segs"])
+        if case["kind"] == "crafted" and case["arg"] == "exact":      # no read of the case makes the call grow its columns
+            assert max(len(s) for s in exp["segs"]) == case["max_segs"]
+    assert not sorted(DRNA_REQUIRED - have)
+    assert segments >= 100 * len(cases["drna"])
+
+
+# ---- the dRNA segmenter, --signal branch ---------------------------------------------------------------------------------
+def roll_features(ora, case, exp):
+    p, R = case["params"], case["nreads"]
+    w, lo_t, hi_t, sd = p["w"], p["lo_thresh"], p["hi_thresh"], p["seg_dist"]
+    f = {"R=%d" % R, "route=" + case["route"], "path=" + rc.roll_route(case), "w=%d" % w, "std_scale=%g" % p["std_scale"],
+         "shift=%d" % p["shift"]}
+    assert rc.roll_route(case, {"SK_ROLL_TWO_KERNELS": "1"}) == rc.roll_route(case, {"SK_DRNA_STEP": "1"}) == "two-kernels"
+    assert rc.roll_route(case, {"SK_ROLL_ONE_LOOK": "1"}) != "stream"
+    if rc.roll_route(case) == "stream" and case["stride"] > rc.ROLL_LDS_LONG:
+        assert rc.roll_one_lds(case["stride"], w) == 0
+        f.add("redo list through scratch rows")
+    if w > case["longest"]:
+        f.add("w above every read")
+    for x, k in zip(case["reads"], exp["kept"]):
+        n = len(x)
+        for name, v in (("0", 0), ("1", 1), ("w-1", w - 1), ("w", w), ("w+1", w + 1), ("2w", 2 * w)):
+            if n == v:
+                f.add("len=" + name)
+        if n in rc.ROLL_CHUNK:
+            f.add("len=%d" % n)
+        if n >= rc.ROLL_LDS_LONG:
+            f.add("len>35000")
+        if n >= rc.ROLL_SCRATCH_LONG:
+            f.add("len>2^17")
+        if k < n:
+            f.add("limits drop samples")
+    for xy in exp["xy"]:
+        if xy is not None and xy[0] < 0:
+            f.add("negative result")
+    if case["kind"] == "crafted":
+        op = ora.RollParams(**{k: v for k, v in p.items() if not k.startswith("lim")})
+        for x, want in zip(case["reads"], exp["xy"]):
+            res, t, (mn, sdv, bot) = ora.drna_roll(ora.scale_outliers(x.astype(float), p["lim_low"], p["lim_hi"]), op,
+                                                   want_t=True)
+            segs, ev = rc.roll_scan(t, bot, sd)
+            ok = [s for s in segs if lo_t <= s[1] - s[0] <= hi_t]
+            assert res == want == ((ok[0][0] - p["shift"], ok[0][1] - p["shift"]) if ok else None)
+            for e in ev:
+                if e[0] == "equal":
+                    f.add("t == bot " + ("inside a run" if e[2] else "outside a run"))
+                elif e[0] == "merge" and e[1] == sd - 1:
+                    f.add("merge at seg_dist - 1")
+                elif e[0] == "new" and e[1] == sd:
+                    f.add("no merge at seg_dist")
+                elif e[0] == "open":
+                    f.add("a run open at the end" + (" behind a segment" if segs else ""))
+            for s in segs:
+                for name, v in (("lo_thresh", lo_t), ("lo_thresh - 1", lo_t - 1), ("hi_thresh", hi_t),
+                                ("hi_thresh + 1", hi_t + 1)):
+                    if s[1] - s[0] == v:
+                        f.add("a segment of " + name)
+            if len(ok) and ok[0] is not segs[0]:
+                f.add("first segment rejected by length, a later one accepted")
+    return f
+
+
+ROLL_REQUIRED = ({"R=%d" % n for n in rc.ROLL_COUNTS} | {"w=%d" % w for w in rc.ROLL_W} | {"std_scale=%g" % s for s in rc.ROLL_STD} |
+                 {"len=" + s for s in ("0", "1", "w-1", "w", "w+1", "2w")} | {"len=%d" % n for n in rc.ROLL_CHUNK} |
+                 {"route=list", "route=padded", "route=odd", "path=stream", "path=one-look", "path=two-kernels",
+                  "redo list through scratch rows", "w above every read", "len>35000", "len>2^17", "limits drop samples",
+                  "shift=0", "shift=1000", "negative result", "t == bot outside a run", "merge at seg_dist - 1",
+                  "no merge at seg_dist", "a run open at the end", "a run open at the end behind a segment",
+                  "a segment of lo_thresh", "a segment of lo_thresh - 1", "a segment of hi_thresh",
+                  "a segment of hi_thresh + 1", "first segment rejected by length, a later one accepted"})
+
+
+def test_roll_cases_reach_every_boundary(ora, cases):
+    have, found = set(), 0
+    for case, exp in cases["roll"]:
+        assert sum(len(r) for r in case["reads"]) <= rc.DRNA_SAMPLES, rc.describe(case)
+        have |= roll_features(ora, case, exp)
+        found += sum(xy is not None for xy in exp["xy"])
+    assert not sorted(ROLL_REQUIRED - have)
+    assert found >= 5 * len(cases["roll"])
+
+
+def test_roll_one_look_lds_restated():
+    """randcases.roll_one_lds against the figures DESIGN.md gives for k_roll_one: rows of about 35 000 samples fit 160 KB."""
+    assert rc.roll_one_lds(35000, 2000) and not rc.roll_one_lds(35008, 2000)
+    assert not rc.roll_one_lds(1000, 65536) and rc.roll_one_lds(1000, 65535)
+    assert rc.roll_stream_ok(30000, 12000, 0, 1200) and not rc.roll_stream_ok(30000, 12001, 0, 1200)
+
+
+# ---- the dRNA families stay what they are: a later family or a change of the generators must not renumber or alter them ----
+PINNED_DRNA = {
+    "drna": {
+        0: "905021223d8bc7fa02d0b5d6ffe11434c1675248cd033afbb72a0ef56773f60c",
+        1: "c8efd62f262ecf6223d7f356ec76cf4a1da1c619693e591fa3be8b778bcdcaf0",
+        2: "ac2570c9b20173d36e0b9e65906aaef32cde0648555df89d65f69d5be02bd003",
+        3: "25188d7415fef0ccf03f52277584513b451745e7ae39ce72d6d644fabb076127",
+        4: "fbd9ca14f53feed52047337f4a810cb9c735a85d4f4fd8ffae2d373a0827de37",
+        5: "f843df0d9a1a98918ed917c2838c59495ed97bf20a24ebfa4343f563eb22714f",
+        6: "c2909816528c1c9468b3a5e8c4b37d8acc6ae5449fe257d2ddc9193dd648cb59",
+        7: "1dadab3fc904bac902545b386893eb2ef30910bf495e3e4536671fb46849c93b",
+        8: "7153f3e4760c8821e578ed0311e2698be00625bdfdda87908bca7818c4bfdd17",
+        10: "f0dc609d91bd048571b8262f986b9c0183e423fceabce0764202f5a29ec957de",
+        11: "79803c7c601b2fbd133ba9f49ac86c96964ef281af96d07cc4fdf22ecc000448",
+        14: "d73cc3f6ad0f746ac932219e11c58d0cb8e0b72fd813ed7c0a58840568712b32",
+        15: "c4331c7668efbd62569446cfc345548fac582874945b3ea0610ea72899c9a8a7",
+        17: "885f0b9e653ce0d882b47c7c55e40cd6d21d96299d5e52b4bfdab1483d1c7a05",
+        18: "aa5a2766a70cf76acbc1feb3796912ba883ddd60f44c27590a0da7310a25b626",
+        20: "cc46e094e0ca3272e69a0d2bda4860a21472c90432eee5930a5c30b1dd274f51",
+        22: "f2222ada881e2a1d301d7f52d149be79b611cabd8c81ec335fec03c3e7cbff41",
+        24: "0678ce47a523ef1b5c53725965de0b92f04a5e169892e486a09f264938f7423a",
+        27: "2b15032219da0eccdf1d10436e65e7764a06b802593904c5080958c49bcc8f42",
+        28: "53f7bf0cd9d821a4dee7b901a7e2aee47f4fda46bcfed945dec06985761949fd",
+        29: "68b6b4fc2081cb5590d912df29cbb5034900bae4b9020b11fea63a6dcdcab5d9",
+        30: "aef1d4eac9b5c10f0bf4fdce83b37d68669c22bdb9504fc0385aebefe4f67263",
+        31: "eeba8f5b8b2b1de32679bbe98dcf7a2e02d16f77073053c5a87c9f4ab122dcf6",
+        34: "3341c223753eff2e9cea847c39d8ff8ccbfc9e23a86fe9d1d124015299e893e9",
+        35: "5cc1c9b6fd1b26231e98b43a875523516db5d44dc59de23647777be01f0dfe2b",
+        36: "36bf030f72abeb78ec8a7e5dc388ee039e8a8f5c7346dfe5e726b3d31746b8f1",
+        37: "ef65f82778015f5cf99cdafee6d066090e7489c8eef3406ef66cbbad574fdda9",
+        38: "68626a03088d6f29cc8566f77dac463452bdbc2afdebc089024146e41b926ebc",
+        39: "28f4557ce57d6c92d5db50f7d7cbc22fc7e3682448e20a5fb3e33b8718afb2bb",
+        40: "2753c7b49819f229c9188847757c88c5fb346cc73f65be132d6d5503c1cda6b1",
+        54: "e5a3da041916c5e3c3a46a62800601ef7eb41346a9796baa40baaa54e057daf7",
+        56: "bb12df92500c7e6165a69ca9d5444513088fd6de26abba16919aac5d44fcf915",
+        65: "affc2c7b431cf83218bf1bac20263511100388aad10e8d11e1391bda5728f6a2",
+        66: "4a37bf5741cad8259f5fe94100a9e8fb9d610fb2d03b30658e4a424fd48d48c3",
+        74: "4647fd38a561079ba9690a2aaa011bb64a0c33192eabc97822cac9c33c7442bd",
+        116: "3ddb9cf6364995df9c9760ef906b510bfe84522309f995f1bcf288e4e4c81186",
+        117: "5343bb02fef28e1e9c38cf682ec6e03d8040b68345085f07b4a730437558835b",
+        140: "24bdc3ede8df580f4a426e35911bde0925c9e47bbd18eb770ede31b3105ab18e",
+        170: "0709bfbad753619d12d7f339b63bc692bc1d1725bb1ac5c44813e21509a126ce",
+        210: "8c392f1f4a11b696ed34e4ac139dfde82bd2a70c5dc323dff9a5e83524c91762",
+    },
+    "roll": {
+        0: "88b5fa6950bb988e204efdbfc56d98ec9e2c0432ec3d04b80b53717e993b60dd",
+        1: "1419196a609d8ed15762febaf11e8fc3e2acc6e7f425f6e370fd29797919c83e",
+        2: "86660a49f8a14afe7841aa56c11b185a8d5b90e6ac1c4c1547397aa11f5f6b37",
+        3: "9458fe6b94b8b7e64d6fe09782494690fcba67b3e6ceab694fe26f3df2f27741",
+        4: "5afed6e662940734327a200e3c5989a08006c75ad38f1a92d8f4e3f7d37de10e",
+        10: "e1043e5ca66b80b5417347f9c6f3e3cbaa3d9a81875a7e03abdac2c70c559374",
+        11: "b9e1609168f7a916f642fac8baebc42a33698417e3aa368094a8749baf2ff34d",
+        13: "6b3890a9ef6ee4b1615faacf658038b384fe3631c549f1793850395b59b90523",
+        16: "e7abec7884634bb51c7c9cabfcbaf29c1bb84f2161b27b6e68b98eab20f0e6b4",
+        21: "8917af4b9aa06634c0fbf87d28c68b9a88ebb5faeedade094c4b81095f54d389",
+        23: "1c69647b62d3d19c46a61cf767f38a0903fb9b36d0f9a48182467fedb6ffebb4",
+        24: "9ceadb852be1753c606d6a82932a2525a24d9b4f081f91de0d0b673f2f9e96ef",
+        29: "fb40338895dca86cdf9dbec1f2c3026af2b46d55d7717a329f13cf4adb0f069c",
+        31: "065c557da3d3e8d4502a102fe13784c51043bbc6b2208b727ceb697de226d99b",
+        59: "3489bda94222d16b1f7828c47c1ef9441db26a9a803e53c9fcbbeebe4dde964d",
+    },
+}
+
+
+def test_drna_families_keep_their_cases():
+    assert (rc.FAMILY_INDEX["drna"], rc.FAMILY_INDEX["roll"]) == (9, 10)
+    for fam, want in PINNED_DRNA.items():
+        assert list(want) == rc.SEEDS[fam], fam
+        for seed, digest in want.items():
+            case = rc.case_of(fam, seed)
+            assert rc.case_digest(case) == digest, (fam, seed)
+            assert rc.describe(case).startswith("%s seed=%d kind=" % (fam, seed))
+
+
+def test_third_interleaved_sequence_is_what_it_claims():
+    """Both dRNA branches between segment, levels, hits and detect calls; of each branch a large case before a small one;
+    calls that occur twice."""
+    seq = rc.INTERLEAVE3
+    fams = {f for f, _ in seq}
+    assert fams == {"drna", "roll", "segment", "levels", "hits", "detect"}
+    assert len(seq) - len(set(seq)) >= 4
+    for fam, seed in seq:
+        assert fam not in rc.SEEDS or seed in rc.SEEDS[fam]
+    for fam in ("drna", "roll"):
+        size = [sum(len(r) for r in rc.case_of(f, s)["reads"]) for f, s in seq if f == fam]
+        assert any(b < a // 20 for a, b in zip(size, size[1:])), (fam, size)      # a small case in buffers left much larger
+        assert any(b > 20 * a for a, b in zip(size, size[1:])), (fam, size)       # and one that grows them again
+    assert all(a != b for (a, _), (b, _) in zip(seq, seq[1:]))                     # never the same family twice in a row

@@ -160,9 +160,11 @@ def test_jumping_walk_model_equals_get_segs(ora, seed):
 # ---------------------------------------------------------------------------------------------------------------
 # k_drna_walk_runs (csrc/sk_drna_walk.hip): the dRNA slow5-branch scan by pieces, trip for trip as the kernel takes them
 # ---------------------------------------------------------------------------------------------------------------
-def _drna_pieces(mask, error, no_err_thresh, w, window, seg_dist):
+def _drna_pieces(mask, error, no_err_thresh, w, window, seg_dist, trips=None):
     """The kernel's loop on a Python bool mask (True = a < top): 64-sample windows at the lane's own position, a piece cut
-    at the re-arming sample / at no_err_thresh / at the window's end, close at the (budget + 1)-th out-of-band sample."""
+    at the re-arming sample / at no_err_thresh / at the window's end, close at the (budget + 1)-th out-of-band sample.
+    `trips` (a list) receives one entry per piece: ('close', pos, q, L, in-band samples before q, prev_err, counted) or
+    ('take', pos, L, out-of-band samples taken, counted, re-armed)."""
     n = len(mask)
     kw0 = (max(window, w) + w - 1) // w * w
     prev = err = prev_err = start = last_end = refill = 0
@@ -199,6 +201,8 @@ def _drna_pieces(mask, error, no_err_thresh, w, window, seg_dist):
             else:
                 prev_err += tol if counted else 0
             i = pos + q
+            if trips is not None:
+                trips.append(("close", pos, q, L, bool(before.size), prev_err, counted))
             if i - start >= window:
                 end = i - prev_err
                 if segs and start - last_end < seg_dist:
@@ -215,11 +219,68 @@ def _drna_pieces(mask, error, no_err_thresh, w, window, seg_dist):
             else:
                 prev_err += int(zs.size) if counted else 0
             err += int(zs.size) if counted else 0
+            if trips is not None:
+                trips.append(("take", pos, L, int(zs.size), counted, pos + L - 1 == refill))
             pos += L
             if pos - 1 == refill:
                 err -= 1
                 refill += w
     return segs
+
+
+def drna_trace(mask, error, no_err_thresh, w, window, seg_dist):
+    """dRNA_segmenter.py:112-165 on a bool mask (True = a < top), sample by sample as the reference takes them: (segments,
+    events).  Events: ('rearm', i, err after it); ('free', i) an out-of-band sample taken and not counted (i < no_err_thresh);
+    ('close', i, start, end, prev_err, merged, start - last_end or None, lowest err of the run, counted samples the run took);
+    ('short', i, c) a run closed below `window`; ('idle', i - last_end) the furthest idle sample before a run that opens
+    behind a segment; ('stop', i, i - last_end)."""
+    prev = err = prev_err = c = start = last_end = 0
+    low = spent = 0
+    idle = None
+    segs, ev = [], []
+    for i, inband in enumerate(mask):
+        if inband:
+            if not prev:
+                start, prev, err, low, spent = i, 1, 0, 0, 0
+                if idle is not None:
+                    ev.append(("idle", idle))
+                    idle = None
+            c += 1
+            prev_err = 0
+        elif prev and err < error:
+            c += 1
+            if i >= no_err_thresh:
+                err += 1
+                prev_err += 1
+                spent += 1
+            else:
+                ev.append(("free", i))
+        elif prev:
+            if c >= window:
+                end = i - prev_err
+                merged = bool(segs) and start - last_end < seg_dist
+                ev.append(("close", i, start, end, prev_err, merged, start - last_end if segs else None, low, spent))
+                if merged:
+                    segs[-1][1] = end
+                else:
+                    segs.append([start, end])
+                last_end = end
+            else:
+                ev.append(("short", i, c))
+            prev = c = err = prev_err = 0
+            continue
+        else:
+            if segs and i - last_end > seg_dist:
+                ev.append(("stop", i, i - last_end))
+                break
+            if segs:
+                idle = i - last_end
+            continue
+        if c >= window and c >= w and c % w == 0:
+            err -= 1
+            low = min(low, err)
+            ev.append(("rearm", i, err))
+    return segs, ev
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -243,3 +304,26 @@ def test_drna_scan_by_pieces_model_equals_oracle(ora, seed):
             assert got == want, (seed, kw, len(f))
             total += len(got)
     assert total > 50
+
+
+def test_drna_scan_by_pieces_model_on_the_committed_cases(ora):
+    """The same model on every committed `drna` case of tests/randcases.py that takes the scan by runs (64 <= w <= 2^24,
+    0 <= window <= 2^24): `f < top` through _drna_pieces against ora.drna_segs, every read, every segment -- so a failure of
+    the GPU leg says whether the algorithm or the kernel is wrong.  The sample-level restatement drna_trace, which the CPU leg
+    reads its seams from, is held to the oracle on the two-level cases too."""
+    import randcases as rc
+    total = runs = 0
+    for seed in rc.SEEDS["drna"]:
+        case = rc.case_of("drna", seed)
+        p = case["params"]
+        exp = rc.expect_drna(ora, case)
+        scan = (p["error"], p["no_err_thresh"], p["w"], p["window"], p["seg_dist"])
+        for x, want, top in zip(case["reads"], exp["segs"], exp["top"]):
+            f = ora.scale_outliers(x.astype(float), p["lim_low"], p["lim_hi"])
+            if rc.drna_walk(case) == "runs":
+                assert _drna_pieces(f < top, *scan) == want, (seed, len(x))
+                runs += 1
+            if case["kind"] in ("crafted", "stride"):
+                assert drna_trace(f < top, *scan)[0] == want, (seed, len(x))
+            total += len(want)
+    assert runs > 1000 and total > 1000

@@ -3,7 +3,8 @@
 lengths, strides, outlier limits, segmenter parameters; the segment levels of every
 segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the
 screening scheme of MotifSeq's first match under its switches, the segmenter sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
-signal HMM with its state paths, segment levels, and the background and events twins of the hit family -- each against the
+signal HMM with its state paths, segment levels, both branches of the dRNA segmenter, and the background and events twins of
+the hit family -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
 length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py.
 
@@ -298,40 +299,30 @@ def main():
             if not (np.array_equal(ca[0], cb[0]) and np.array_equal(ca[1], cb[1]) and ha[0].tobytes() == hb[0].tobytes()):
                 bad += 1
                 print("CENTI mismatch: %d reads" % len(cn))
-        # ---- dRNA_segmenter: both branches on a few long ragged reads ----
+        # ---- dRNA_segmenter: both branches, randcases.DRAW["drna"] / DRAW["roll"] with this tool's generator ----
+        # (read counts up to 257 over several wavefronts, batch routes with odd and padded strides, every statistics route and
+        # both scans of the slow5 branch, two-level reads with drawn and crafted band masks; the three routes of the rolling
+        # branch, windows up to 65 536 and rows above 2^17 samples) against the oracle through EXPECT / CALL / DIFF, under a
+        # drawn switch
         if rounds % 2 == 0:
-            from squigglekit_amd._lib import DrnaParams, RollParams
-            dreads = synth.drna_reads(int(rng.integers(1, 9)), int(rng.integers(1 << 30)),
-                                      min_len=int(rng.choice([300, 3000, 9000])), max_len=26000)
-            if rng.random() < 0.5:                              # masks with structure (alternating, trains, near-miss gaps)
-                dreads = dreads + [x for x in synth.pattern_reads(rng, int(rng.integers(1, 5)), int(rng.choice([3000, 9000])))]
-            dkw = [dict(), dict(error=2, no_err_thresh=0, w=50, window=30, seg_dist=100),
-                   dict(t_start=0, t_end=2000, std_scale=0.2), dict(error=0), dict(w=64, window=500, seg_dist=50),
-                   dict(no_err_thresh=100000, error=1), dict(error=9, w=100, window=250, seg_dist=10, std_scale=1.5),
-                   dict(no_err_thresh=777, w=128, window=64, error=3, t_start=0, t_end=9000)][int(rng.integers(8))]
-            if rng.random() < 0.2:
-                os.environ["SK_DRNA_STEP"] = "1"
-            for x, g in zip(dreads, api.drna_segment_reads(dreads, DrnaParams(**dkw))):
-                if g != ora.drna_segs(ora.scale_outliers(x.astype(float), 0, 1200), ora.DrnaParams(**dkw))[0]:
+            for fam, line, switches in (
+                    ("drna", "DRNA mismatch", (None, None, None, None, ("SK_DRNA_STEP", "1"))),
+                    ("roll", "DRNA ROLL mismatch", (None, None, None, None, None, None, ("SK_ROLL_TWO_KERNELS", "1"),
+                                                    ("SK_ROLL_ONE_LOOK", "1"), ("SK_ROLL_DELTA_SCALE", "1e13"),
+                                                    ("SK_DRNA_STEP", "1")))):
+                case = randcases.DRAW[fam](rng)
+                sw = switches[int(rng.integers(len(switches)))]
+                for key in randcases.SWITCHES:
+                    os.environ.pop(key, None)
+                if sw:
+                    os.environ[sw[0]] = sw[1]
+                exp = randcases.EXPECT[fam](ora, case)
+                msg = randcases.DIFF[fam](case, randcases.CALL[fam](api, case, exp), exp)
+                if msg is not None:
                     bad += 1
-                    print("DRNA mismatch n=%d %s step=%s" % (len(x), dkw, os.environ.get("SK_DRNA_STEP")))
-            rkw = [dict(), dict(w=int(rng.choice([3, 64, 999, 2000, 5000]))),
-                   dict(w=800, lo_thresh=200, seg_dist=int(rng.choice([1, 300, 5000])), std_scale=0.25),
-                   dict(w=int(rng.integers(1, 9000)), lo_thresh=int(rng.choice([5, 500, 2000])),
-                        std_scale=float(rng.choice([-0.5, 0.0, 0.1, 0.5, 2.0])))][int(rng.integers(4))]
-            # (round 5: rows of up to ~35 000 samples take the one-look kernel, k_roll_one; the two-kernel path on request)
-            rsw = rng.random()
-            rkey = "SK_ROLL_TWO_KERNELS" if rsw < 0.12 else "SK_ROLL_ONE_LOOK" if rsw < 0.3 else \
-                   "SK_ROLL_DELTA_SCALE" if rsw < 0.4 else None
-            if rkey:
-                os.environ[rkey] = "1e13" if rkey == "SK_ROLL_DELTA_SCALE" else "1"
-            for x, g in zip(dreads, api.drna_roll_reads(dreads, RollParams(**rkw))):
-                if g != ora.drna_roll(ora.scale_outliers(x.astype(float), 0, 1200), ora.RollParams(**rkw)):
-                    bad += 1
-                    print("DRNA ROLL mismatch n=%d %s step=%s switch=%s" % (len(x), rkw, os.environ.get("SK_DRNA_STEP"), rkey))
-            os.environ.pop("SK_DRNA_STEP", None)
-            for key in ("SK_ROLL_TWO_KERNELS", "SK_ROLL_ONE_LOOK", "SK_ROLL_DELTA_SCALE"):
-                os.environ.pop(key, None)
+                    print("%s round %d %s switch=%s: %s" % (line, rounds, randcases.describe(case), sw, msg))
+                for key in randcases.SWITCHES:
+                    os.environ.pop(key, None)
         # ---- tests/randcases.py's draws with this tool's running generator, against the same references as
         # tests/test_gpu_random.py: the sweep (the oracle per (set, read)), the hit lists (reference_hits), the paths
         # (reference_paths), pull (numpy_pull_text), the panel (reference_panel), event detection (detect_ref), the signal
