@@ -15,8 +15,8 @@ import sys
 
 import numpy as np
 
-from . import _lib, api, fastio, tsvio
-from .motifseq_cli import HEADER, load_models
+from . import _lib, api, tsvio
+from .motifseq_cli import HEADER, DistanceModel, load_models
 
 STREAM_HEADER = HEADER + ["decision", "chunks", "samples_seen"]
 
@@ -104,14 +104,11 @@ def lines_of(a, meta, rec, order, lens, decision):
         sys.stderr.write("MotifSeq_stream: the MAD of the calibration samples of {} is 0; skipped\n".format(read_id))
         return None
     out = []
+    model = DistanceModel(a, lens)
     for k, name in enumerate(order):
         dist, start, end = float(rec[k]["dist"]), int(rec[k]["start"]), int(rec[k]["end"])
-        mod_mean = (a.slope * lens[k]) + a.intercept
-        mod_stdev = mod_mean * a.std_const
-        z = (dist - mod_mean) / mod_stdev
-        p_value = fastio.ndtr(z)
-        hit_p = (1 - p_value) * 100
-        row = [fast5, read_id, name, start, end, end - start, dist, mod_mean, mod_stdev, z, p_value, hit_p, decision,
+        z, p_value, hit_p = model.score(dist, k)
+        row = [fast5, read_id, name, start, end, end - start, dist, model.mean[k], model.stdev[k], z, p_value, hit_p, decision,
                int(rec[k]["chunks"]), int(rec[k]["seen"])]
         out.append("\t".join("{}".format(v) for v in row))
     return out
