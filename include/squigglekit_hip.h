@@ -576,6 +576,31 @@ int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
 int sk_dtw_subsequence_path(const double *x, int32_t nx, const double *y, int32_t ny,
                             double *dist, int32_t *start, int32_t *end, int32_t *spans);
 
+/* ---- DTW over a pair list: a query of its own per pair, shared targets --------------------------------------------
+ * The pool is ragged float64: sequence s = values[off[s] .. off[s+1]), nseq sequences, taken as given (no filter, no
+ * normalisation).  A pair names two sequences of the pool: the query and the target.  A sequence may be the query of
+ * some pairs and the target of others; (i, i) is allowed.  out [npairs], in the caller's order.
+ *   SK_PAIRS_SUBSEQUENCE  the record of pair p is what sk_dtw_subsequence(values[query], values[target]) returns: free
+ *       start and end along the target, first argmin of the last row, start by the back-trace order diagonal, j-1,
+ *       i-1; n = the target's length.
+ *   SK_PAIRS_GLOBAL  both ends pinned: D[0][0] = |x0 - y0|, D[0][j] = D[0][j-1] + |x0 - yj|, D[i][0] = D[i-1][0] +
+ *       |xi - y0|, inside |xi - yj| + min3 as above; dist = D[N-1][M-1], start = 0, end = M - 1, n = M.  This is mlpy's
+ *       dtw_std(x, y, dist_only=True) as published; no mlpy build was compared against.  The distance is symmetric bit
+ *       for bit (the transposed path adds the same cells in the same order).
+ * An empty target gives dist NaN, start = end = -1 and SK_FLAG_EMPTY.  SK_ERR_INVALID (with the pair named, nothing
+ * launched, no record written): an empty query, an index outside [0, nseq).  SK_ERR_UNSUPPORTED: a query of more than
+ * 1 024 points (the pair named), npairs above 2^27.  npairs == 0 returns SK_OK.  Non-finite values: unspecified.
+ * Every distinct query is laid out once however many pairs use it; pairs whose queries share a lane layout are swept
+ * by one launch, four pairs to a wavefront for short queries in large calls. */
+enum { SK_PAIRS_SUBSEQUENCE = 0, SK_PAIRS_GLOBAL = 1 };
+typedef struct sk_pair { int32_t query, target; } sk_pair;     /* 8 bytes */
+int sk_dtw_pairs(const double *values, const int64_t *off, int32_t nseq,
+                 const sk_pair *pairs, int64_t npairs, int32_t mode, sk_hit *out);
+/* device-resident form: d_values and d_out on the device; off and pairs on the host (the plan needs the lengths).
+ * Nothing is synchronised after the launches. */
+int sk_dtw_pairs_dev(const double *d_values, const int64_t *off, int32_t nseq,
+                     const sk_pair *pairs, int64_t npairs, int32_t mode, sk_hit *d_out);
+
 /* The same call in mlpy's own C arithmetic for inputs that hold inf / nan -- `min3` as "a; if (b < m) m = b; if (c < m)
  * m = c", fabs, np.argmin's first-NaN rule, the back-trace of subsequence_path, all evaluated literally by one GPU lane
  * over the full cost matrix.  medmad of a read whose MAD is 0 divides by zero (MotifSeq.py:196-199) and the reference

@@ -26,6 +26,7 @@ SK_OK, SK_ERR_INVALID, SK_ERR_NO_DEVICE, SK_ERR_HIP, SK_ERR_NOMEM, SK_ERR_UNSUPP
 SK_SCALE = {"medmad": 0, "zscale": 1}
 SK_PULL_RAW, SK_PULL_PA = 0, 1
 SK_FLAG_EMPTY, SK_FLAG_DEGENERATE, SK_FLAG_RECENTRE = 1, 2, 4
+SK_PAIRS_SUBSEQUENCE, SK_PAIRS_GLOBAL = 0, 1
 SK_FLAG_CALIBRATING = 8                 # sk_stream_rec.flags: the slot still collects its calibration samples
 SK_STREAM_MAX_CALIB, SK_STREAM_MAX_SLOTS, SK_STREAM_MAX_POINTS = 65536, 65536, 1024
 
@@ -339,6 +340,10 @@ ABI = {
                                       C.c_int32, C.c_int32, _vp]),
     "sk_dtw_subsequence_batch": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp]),
     "sk_dtw_subsequence": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _dp, _i32p, _i32p, _vp]),
+    # DTW over a pair list: values, off, nseq, pairs [npairs] of {query, target}, npairs, mode, out [npairs] -- the
+    # device-resident form takes the same list (values / out device, off / pairs host)
+    "sk_dtw_pairs": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp]),
+    "sk_dtw_pairs_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp]),
     "sk_dtw_subsequence_cref": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _dp, _i32p, _i32p]),
     "sk_normalise_i16": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i32p]),
     "sk_normalise_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i32p]),

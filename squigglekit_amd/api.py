@@ -1325,6 +1325,152 @@ def dtw_subsequence_batch(x, ys):
 
 
 # ----------------------------------------------------------------------------
+# DTW over a pair list: a query of its own per pair, shared targets, global mode ("DTW over a pair list" in
+# include/squigglekit_hip.h and DESIGN.md 4.15)
+# ----------------------------------------------------------------------------
+PAIRS_MODES = {"subsequence": _lib.SK_PAIRS_SUBSEQUENCE, "global": _lib.SK_PAIRS_GLOBAL}
+PAIR_DTYPE = np.dtype([("query", "<i4"), ("target", "<i4")])
+
+
+def _as_pool(seqs):
+    """(values float64, off int64 [nseq + 1]) of a list of arrays; a (values, off) tuple passes through."""
+    if isinstance(seqs, tuple) and len(seqs) == 2:
+        values = np.ascontiguousarray(seqs[0], dtype=np.float64).reshape(-1)
+        off = np.ascontiguousarray(seqs[1], dtype=np.int64).reshape(-1)
+        if off.size < 1 or np.any(np.diff(off) < 0) or off[0] < 0 or off[-1] > values.size:
+            raise ValueError("off must hold nseq + 1 non-decreasing offsets into values")
+        return values, off
+    arrs = [np.asarray(s, dtype=np.float64).reshape(-1) for s in seqs]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    if arrs:
+        off[1:] = np.cumsum([a.size for a in arrs])
+    values = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0), dtype=np.float64)
+    return values, off
+
+
+def _as_pairs(pairs):
+    if isinstance(pairs, np.ndarray) and pairs.dtype == PAIR_DTYPE:
+        return np.ascontiguousarray(pairs).reshape(-1)
+    a = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("pair indices must fit int32")
+    out = np.zeros(len(a), dtype=PAIR_DTYPE)
+    out["query"], out["target"] = a[:, 0], a[:, 1]
+    return out
+
+
+def dtw_pairs(seqs, pairs, mode="subsequence"):
+    """DTW of every (query, target) pair of a pool of already-normalised float64 sequences in one call: seqs a list of
+    arrays or a (values, off) tuple, pairs [npairs, 2] indices into it.  Returns HIT_DTYPE [npairs] in the order of the
+    list.  mode "subsequence": the record dtw_subsequence(seqs[q], seqs[t]) gives (n = the target's length); "global":
+    both ends pinned (mlpy's dtw_std(x, y, dist_only=True)): dist = D[N-1][M-1], start = 0, end = M - 1.  A query holds
+    1 .. 1 024 points; an empty target gives a NaN record flagged SK_FLAG_EMPTY.  Single device."""
+    if mode not in PAIRS_MODES:
+        raise ValueError("mode %r: need one of %s" % (mode, sorted(PAIRS_MODES)))
+    L = _lib.ensure_init()
+    values, off = _as_pool(seqs)
+    pr = _as_pairs(pairs)
+    out = np.zeros(len(pr), dtype=HIT_DTYPE)
+    keep = values if values.size else np.zeros(1)
+    check(L.sk_dtw_pairs(ptr(keep), ptr(off), off.size - 1, ptr(pr), len(pr), PAIRS_MODES[mode], ptr(out)))
+    return out
+
+
+def dtw_matrix(seqs, mode="global"):
+    """All pairs of a pool: the float64 [nseq, nseq] distances.  mode "global": only i < j is computed, with the shorter
+    of the two as the query (so the 1 024-point limit applies to the shorter one), then mirrored, diagonal 0.0 -- the
+    global distance is symmetric bit for bit, the transposed path adds the same cells in the same order.  mode
+    "subsequence": the full matrix, dists[i][j] = seqs[i] searched in seqs[j]."""
+    values, off = _as_pool(seqs)
+    n = off.size - 1
+    lens = np.diff(off)
+    if mode == "global":
+        i, j = np.triu_indices(n, 1)
+        swap = lens[j] < lens[i]
+        pr = np.stack([np.where(swap, j, i), np.where(swap, i, j)], axis=1)
+        rec = dtw_pairs((values, off), pr, "global")
+        d = np.zeros((n, n), dtype=np.float64)
+        d[i, j] = rec["dist"]
+        d[j, i] = rec["dist"]
+        return d
+    i, j = np.divmod(np.arange(n * n, dtype=np.int64), n)
+    return dtw_pairs((values, off), np.stack([i, j], axis=1), mode)["dist"].reshape(n, n)
+
+
+def map_queries(queries, targets, mode="subsequence"):
+    """Every query against every target in one call.  Returns (records HIT_DTYPE [T, Q], best int64 [Q]): best[q] is the
+    target with the smallest dist, ties to the smallest target index (-1 when no target gave a distance)."""
+    qs = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
+    ts = [np.asarray(t, dtype=np.float64).reshape(-1) for t in targets]
+    Q, T = len(qs), len(ts)
+    t, q = np.divmod(np.arange(T * Q, dtype=np.int64), max(Q, 1))
+    rec = dtw_pairs(qs + ts, np.stack([q, Q + t], axis=1), mode).reshape(T, Q)
+    return rec, best_targets(rec)
+
+
+def best_targets(records):
+    """best [Q] of records [T, Q]: the smallest dist, ties to the smallest target index; -1 where every dist is NaN."""
+    nan = np.isnan(records["dist"])
+    if nan.shape[0] == 0:
+        return np.full(nan.shape[1], -1, dtype=np.int64)
+    best = np.argmin(np.where(nan, np.inf, records["dist"]), axis=0).astype(np.int64)
+    best[nan.all(axis=0)] = -1
+    return best
+
+
+def tile_targets(targets, piece, overlap):
+    """Long targets cut into pieces of `piece` points that step by piece - overlap, for map_queries: returns (pieces,
+    tiling) with tiling = {"target": int64 [P], "origin": int64 [P], "length": int64 [T]} -- piece p is
+    targets[target[p]][origin[p] : origin[p] + piece].  The last piece of a target ends at its end; a target of at most
+    `piece` points is one piece.  merge_tiles puts the records back in whole-target coordinates."""
+    piece, overlap = int(piece), int(overlap)
+    if not 0 <= overlap < piece:
+        raise ValueError("need 0 <= overlap < piece")
+    step = piece - overlap
+    pieces, tgt, org, length = [], [], [], []
+    for t, y in enumerate(targets):
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        length.append(y.size)
+        s = 0
+        while True:
+            pieces.append(y[s:s + piece])
+            tgt.append(t)
+            org.append(s)
+            if s + piece >= y.size:
+                break
+            s += step
+    return pieces, {"target": np.array(tgt, dtype=np.int64), "origin": np.array(org, dtype=np.int64),
+                    "length": np.array(length, dtype=np.int64)}
+
+
+def merge_tiles(records, tiling):
+    """records [P, Q] of the pieces of tile_targets (subsequence mode) -> records [T, Q] of the whole targets: start and
+    end shifted by the piece's origin, n the whole target's length, per (query, target) the smallest dist, ties to the
+    smallest end.  Guarantee: dist equals the whole-target dist whenever the whole-target match spans at most `overlap`
+    points (some piece then holds the whole match, and no piece can do better than the whole target)."""
+    records = np.asarray(records)
+    tgt, org, length = tiling["target"], tiling["origin"], tiling["length"]
+    T, Q = len(length), records.shape[1]
+    out = np.zeros((T, Q), dtype=HIT_DTYPE)
+    seen = np.zeros(T, dtype=bool)
+    for p in range(records.shape[0]):
+        t = int(tgt[p])
+        r = records[p].copy()
+        has = r["start"] >= 0
+        r["start"][has] += int(org[p])
+        r["end"][has] += int(org[p])
+        r["n"] = int(length[t])
+        if not seen[t]:
+            out[t], seen[t] = r, True
+            continue
+        cur = out[t]
+        better = (r["dist"] < cur["dist"]) | ((r["dist"] == cur["dist"]) & (r["end"] < cur["end"])) | \
+                 (np.isnan(cur["dist"]) & ~np.isnan(r["dist"]))
+        cur[better] = r[better]
+    return out
+
+
+# ----------------------------------------------------------------------------
 # MotifSeq panel: many motifs ranked per read, inside a search region
 # ----------------------------------------------------------------------------
 INT32_MAX = 2 ** 31 - 1

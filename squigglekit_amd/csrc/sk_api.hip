@@ -1019,6 +1019,37 @@ int sk_dtw_subsequence_batch(const double *x, int32_t nx, const double *y, const
     return SK_OK;
 }
 
+// ------------------------------------------------------------------ DTW over a pair list (sk_pairs.hip)
+int sk_dtw_pairs_dev(const double *d_values, const int64_t *off, int32_t nseq,
+                     const sk_pair *pairs, int64_t npairs, int32_t mode, sk_hit *d_out)
+{
+    SK_ENTER(c);
+    return sk_pairs_run(c, d_values, off, 0, nseq, pairs, npairs, mode, d_out);
+}
+
+int sk_dtw_pairs(const double *values, const int64_t *off, int32_t nseq,
+                 const sk_pair *pairs, int64_t npairs, int32_t mode, sk_hit *out)
+{
+    SK_ENTER(c);
+    int rc;
+    if ((rc = sk_pairs_check(off, nseq, pairs, npairs, mode, out))) return rc;   // before anything is copied or launched
+    if (npairs == 0) return SK_OK;
+    if (!values) return sk_fail(SK_ERR_INVALID, "NULL values");
+    for (int32_t s = 0; s < nseq; s++)
+        if (off[s + 1] < off[s]) return sk_fail(SK_ERR_INVALID, "offsets not increasing at sequence %d", s);
+    const int64_t total = nseq ? off[nseq] - off[0] : 0;
+    const size_t vb = (((size_t)(total > 0 ? total : 1) * sizeof(double)) + 15) & ~(size_t)15;
+    if ((rc = sk_reserve(c, &c->pairsval, vb + (size_t)npairs * sizeof(sk_hit)))) return rc;
+    double *d_values = (double *)c->pairsval.p;
+    sk_hit *d_out = (sk_hit *)((char *)c->pairsval.p + vb);
+    if (total > 0)
+        SK_HIP(hipMemcpyAsync(d_values, values + off[0], (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_pairs_run(c, d_values, off, nseq ? off[0] : 0, nseq, pairs, npairs, mode, d_out))) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, (size_t)npairs * sizeof(sk_hit), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
 int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
                        double *dist, int32_t *start, int32_t *end, double *cost_last_row)
 {

@@ -51,6 +51,21 @@ struct sk_panel_group {
     int32_t first, count;   // its run of table entries
 };
 
+// DTW over a pair list (sk_pairs.hip): what one lane group of a launch reads from the per-call device table.  32 bytes.
+struct sk_pair_entry {
+    int64_t toff;     // first sample of the target inside the pool
+    int64_t xoff;     // first double of the query's [L][R] layout inside the call's layout block
+    int32_t n;        // the target's length
+    int32_t P;        // the query's short lanes (own R - 1 rows)
+    int32_t pair;     // the caller's pair index: the record goes to out[pair]
+    int32_t pad;
+};
+// ... and one distinct query of the call: where its points lie in the pool, where its layout goes (k_pairs_layout)
+struct sk_pair_query {
+    int64_t src, xoff;
+    int32_t N, L, R, pad;
+};
+
 struct sk_ctx {
     int         device = -1;
     bool        ready = false;
@@ -112,6 +127,10 @@ struct sk_ctx {
     std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
     std::vector<sk_panel_group> panel_groups;
     std::vector<int32_t> panel_long;          // motifs of more than 1 024 points: the chained launcher, one at a time
+    sk_buf pairs;     // pair list: the distinct queries laid out per lane, then the table (sk_pairs.hip)
+    sk_buf pairsval;  // pair list: the pool and the records of the host entry point
+    std::vector<sk_pair_query> pairs_query;   // one entry per distinct query (kept alive for the async H2D)
+    std::vector<sk_pair_entry> pairs_table;   // one entry per pair, (L, R) group after group
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -271,6 +290,16 @@ void sk_exact_shape(int N, int64_t count, int *L, int *R);
 // the panel's layouts, d_mt the group's table entries, motif k's record of read r -> d_all[k * out_stride + r]
 int sk_launch_sdtw_panel(sk_ctx *c, const sk_sdtw_args *a, int L, int R, const double *d_xlay, const sk_panel_motif *d_mt,
                          int32_t count, sk_hit *d_all, int64_t out_stride);
+// the exact single pass over `count` pairs of one (L, R) group of a pair list in one grid (k_sdtw, MODE_PAIRS; global != 0:
+// MODE_PAIRS_GLOBAL): lane group g reads d_pt[g] -- its query's layout inside d_xlay, its target inside d_values, its
+// pair index -- and writes d_out[pair]
+int sk_launch_sdtw_pairs(sk_ctx *c, int L, int R, int global, const double *d_values, const double *d_xlay,
+                         const sk_pair_entry *d_pt, int32_t count, sk_hit *d_out);
+// the plan and the launches of sk_dtw_pairs (sk_pairs.hip): d_values / d_out on the device, off / pairs on the host;
+// sequence s is d_values[off[s] - off0 .. off[s + 1] - off0).  sk_pairs_check: the argument checks alone (nothing launched)
+int sk_pairs_check(const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs, int32_t mode, const void *out);
+int sk_pairs_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t off0, int32_t nseq, const sk_pair *pairs,
+                 int64_t npairs, int32_t mode, sk_hit *d_out);
 // the exact single pass that also stores every read's last row (cost, back-trace start) at r * max_len (sk_sdtw.hip)
 int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t *rowS);
 // hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]

@@ -40,6 +40,13 @@
 //          (sk_hits.hip).  12 B per column against 8 VALU instructions per cell.
 //   PANEL  FULL over all (read, motif) pairs of a motif panel's shape group in one grid (sk_panel.hip): blockIdx.y
 //          picks the motif's entry of a device table -- where its layout lies, its short lanes, where its records go.
+//   PAIRS  FULL over a list of (query, target) pairs drawn from one pool of float64 sequences (sk_pairs.hip): the table
+//          entry is per LANE GROUP -- the query's layout and short lanes, the target's offset and length, the pair's
+//          output slot -- so the four groups of an L = 16 wavefront sweep four different queries over four targets.
+//   PAIRS_GLOBAL  the same table with both ends pinned (mlpy's dtw_std(x, y, dist_only=True) as published; unpinned in
+//          the sense of SURVEY.md rows D1-D3: no mlpy build was at hand to compare against): the virtual row above
+//          lane 0 carries D = +inf at every column, only the corner (D = 0 at column -1) stays, so D[0][0] = |x0 - y0|
+//          and the first row and column accumulate; the result is D[N-1][n-1], start = 0, end = n - 1.  No S is carried.
 #include "sk_sdtw_dev.h"
 #include <math.h>
 #include <stdlib.h>
@@ -56,7 +63,10 @@ void k_sdtw(const sdtw_kargs a)
     constexpr int G = 64 / L;
     constexpr int SHR = (L == 16) ? DPP_ROW_SHR1 : DPP_WAVE_SHR1;
     constexpr int ROL = (L == 16) ? DPP_ROW_ROL1 : DPP_WAVE_ROL1;
-    constexpr bool TRACK = (MODE != MODE_DIST);
+    constexpr bool PAIRS = (MODE == MODE_PAIRS || MODE == MODE_PAIRS_GLOBAL);
+    constexpr bool GLOBAL = (MODE == MODE_PAIRS_GLOBAL);
+    static_assert(!PAIRS || FEED == SK_FEED_F64_RAW, "pair lists take the pool as given");
+    constexpr bool TRACK = (MODE != MODE_DIST && !GLOBAL);
     constexpr int CKW = R + 3;                      // doubles per lane per checkpoint
     const double INF = __builtin_huge_val();
 
@@ -65,7 +75,7 @@ void k_sdtw(const sdtw_kargs a)
     const int g = lane / L, l = lane % L;
     int slot = wave * G + g;
     int nreads = a.nreads;
-    if constexpr (MODE != MODE_PANEL) {             // (the panel's grid is neither gated nor driven by a list)
+    if constexpr (MODE != MODE_PANEL && !PAIRS) {   // (the panel's and the pair list's grids are neither gated nor driven by a list)
         if (a.gate_ptr) {                           // whole-call fallback: runs only when the guard raised an alarm
             if (*a.gate_ptr == 0) return;           // (launch-uniform)
             if (a.guard && blockIdx.x == 0 && threadIdx.x == 0) a.guard[SK_GUARD_FELLBACK] = 1;
@@ -80,10 +90,12 @@ void k_sdtw(const sdtw_kargs a)
     const bool live = slot < nreads;
     if (!live) slot = nreads - 1;
     int r;
-    if constexpr (MODE == MODE_PANEL) r = slot;     // all reads, in order: no list, no chunking
+    if constexpr (MODE == MODE_PANEL || PAIRS) r = slot;   // all reads (table entries), in order: no list, no chunking
     else r = a.ridx ? a.ridx[a.list_off + slot] : a.read0 + slot;
     sk_panel_motif mt = {};                         // PANEL: this block's motif (block-uniform: scalar loads)
     if constexpr (MODE == MODE_PANEL) mt = a.mt[blockIdx.y];
+    sk_pair_entry pe = {};                          // PAIRS: this lane group's pair (per lane: vector loads)
+    if constexpr (PAIRS) pe = a.pt[r];
 
     // ---- per-read parameters -------------------------------------------------
     int n, flags = 0;
@@ -99,6 +111,10 @@ void k_sdtw(const sdtw_kargs a)
         n = pr.n; flags = pr.flags & SK_FLAG_PUBLIC; center = pr.center; scale = pr.scale;
         rc1 = pr.top; rc2 = pr.bot;                 // zscale re-centring terms (0.0 unless sklearn applied them)
         s64 = (const double *)(((pr.flags & SK_IFLAG_INPLACE) && a.samples_raw) ? a.samples_raw : a.samples) + a.off[r];
+    } else if constexpr (PAIRS) {
+        n = pe.n;
+        if (n == 0) flags = SK_FLAG_EMPTY;
+        s64 = (const double *)a.samples + pe.toff;
     } else {
         n = (int)(a.off[r + 1] - a.off[r]);
         if (n == 0) flags = SK_FLAG_EMPTY;
@@ -132,9 +148,10 @@ void k_sdtw(const sdtw_kargs a)
 #pragma unroll
     for (int k = 0; k < R; k++) {
         if constexpr (MODE == MODE_PANEL) x[k] = a.xlay[mt.xoff + l * R + k];
+        else if constexpr (PAIRS) x[k] = a.xlay[pe.xoff + l * R + k];
         else x[k] = a.xlay[l * R + k];
     }
-    const bool shortlane = l < (MODE == MODE_PANEL ? mt.P : a.P);
+    const bool shortlane = l < (MODE == MODE_PANEL ? mt.P : PAIRS ? pe.P : a.P);
 
     double D[R];
     int    S[R];
@@ -216,6 +233,7 @@ void k_sdtw(const sdtw_kargs a)
             y = dpp_f64<SHR>(F, y);                         // lane 0 takes sample t from the feed
             F = dpp_f64<ROL>(F, F);
             double topD = 0.0;  int topS = t + 1;           // lane 0: virtual row -1 (D = 0, S = column + 1)
+            if constexpr (GLOBAL) topD = INF;               //   pinned start: no free entry along the target
             if constexpr (MODE == MODE_CHAIN) {
                 if (chained) { topD = PFD; topS = PFS; }    //   or the previous chunk's last row at column t
                 PFD = dpp_f64<ROL>(PFD, PFD);
@@ -265,6 +283,8 @@ void k_sdtw(const sdtw_kargs a)
             const int j = t - l;
             if constexpr (MODE == MODE_START) {
                 if (j == end) bestS = S[R - 1];             // S of cell (N-1, end), lane L-1
+            } else if constexpr (GLOBAL) {
+                if (j == n - 1) best = D[R - 1];            // pinned end: cell (N-1, n-1), lane L-1
             } else {
                 // ---- running first-argmin of the last row (meaningful in lane L-1) --
                 if (D[R - 1] < best) {
@@ -296,11 +316,12 @@ void k_sdtw(const sdtw_kargs a)
             }
         } else {
             sk_hit h;
-            if (n > 0) { h.dist = best; h.start = bestS; h.end = bestJ; }
+            if (n > 0) { h.dist = best; h.start = GLOBAL ? 0 : bestS; h.end = GLOBAL ? n - 1 : bestJ; }
             else       { h.dist = __builtin_nan(""); h.start = -1; h.end = -1; }
             h.n = n;
             h.flags = flags;
             if constexpr (MODE == MODE_PANEL) a.out[(int64_t)mt.k * a.out_stride + r] = h;
+            else if constexpr (PAIRS) a.out[pe.pair] = h;
             else a.out[a.out_by_slot ? a.list_off + slot : r] = h;
         }
     }
@@ -570,6 +591,19 @@ int sk_launch_sdtw_panel(sk_ctx *c, const sk_sdtw_args *a, int L, int R, const d
     hipLaunchKernelGGL(fn, grid, dim3(256), 0, c->stream, k);
     SK_HIP(hipGetLastError());
     return SK_OK;
+}
+
+int sk_launch_sdtw_pairs(sk_ctx *c, int L, int R, int global, const double *d_values, const double *d_xlay,
+                         const sk_pair_entry *d_pt, int32_t count, sk_hit *d_out)
+{
+    sdtw_fn fn;
+    if (global) fn = L == 16 ? pick_r<16, SK_FEED_F64_RAW, MODE_PAIRS_GLOBAL>(R) : pick_r<64, SK_FEED_F64_RAW, MODE_PAIRS_GLOBAL>(R);
+    else        fn = L == 16 ? pick_r<16, SK_FEED_F64_RAW, MODE_PAIRS>(R) : pick_r<64, SK_FEED_F64_RAW, MODE_PAIRS>(R);
+    if (!fn || (L != 16 && L != 64)) return sk_fail(SK_ERR_UNSUPPORTED, "no pairs kernel for L=%d R=%d", L, R);
+    sdtw_kargs k;
+    memset(&k, 0, sizeof k);
+    k.samples = d_values; k.nreads = count; k.xlay = d_xlay; k.pt = d_pt; k.out = d_out;
+    return launch(c, fn, k, L);
 }
 
 int sk_launch_sdtw(sk_ctx *c, const sk_sdtw_args *a_in)

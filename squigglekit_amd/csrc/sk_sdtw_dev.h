@@ -15,7 +15,9 @@ constexpr int DPP_WAVE_ROL1 = 0x134;   // lane i <- lane i+1 across the wave (ro
 
 enum { MODE_FULL = 0, MODE_DIST = 1, MODE_START = 2, MODE_CHAIN = 3,   // CHAIN: FULL on one row chunk of a long motif
        MODE_ROWS = 4,                                                     // ROWS: FULL that also stores the last row (hit lists)
-       MODE_PANEL = 5 };                                                  // PANEL: FULL over a table of motifs, one per blockIdx.y
+       MODE_PANEL = 5,                                                    // PANEL: FULL over a table of motifs, one per blockIdx.y
+       MODE_PAIRS = 6,                                                    // PAIRS: FULL over a table of (query, target) pairs, one per lane group
+       MODE_PAIRS_GLOBAL = 7 };                                           // PAIRS_GLOBAL: the same table, both ends pinned, D only
 
 // `case 1: return X(1); ... case 16: return X(16);` (and 17 .. 32) inside a switch on R: X(RR) names the kernel
 // instantiated for RR rows per lane.  The one dispatch on R of every DTW kernel family.
@@ -144,6 +146,9 @@ struct sdtw_kargs {
     // tagged screening sweep (k_sdtw_qh): the longest path in cells, N + n + 2 -- qerr is 2^T times that there, and the
     // image-error guard is about the path length
     unsigned       qplen;
+    // MODE_PAIRS / MODE_PAIRS_GLOBAL: one table entry per lane group (launch slot): the query's layout inside xlay, its short
+    // lanes, the target's place inside samples and its length, where the record goes.  Last, so that no other field moves.
+    const sk_pair_entry *pt;
 };
 
 // The argument block of a launch over the prepared reads of `a`: zeroed but for the sample feed.

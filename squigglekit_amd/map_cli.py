@@ -1,0 +1,201 @@
+"""squiggle_map: search the event levels of each read's first samples in reference squiggles, on the GPU.
+
+    squiggle_map.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
+                    [--piece N --overlap N]
+
+Per read: event detection on the first --prefix raw samples (api.detect_events), the level of every event
+(api.event_levels), (level - mean) / std in numpy, then subsequence DTW of those levels against every target in one call
+(api.map_queries).  The targets are the records of a scrappie squiggle text (-m): each `#name` record's per-base currents
+(tsvio.read_scrappie_levels), z-scored the same way; --both adds each record's reversal as a second target (strand -).
+--piece / --overlap cut long targets into overlapping pieces (api.tile_targets / api.merge_tiles).
+
+Output: the header line, then one line per read (tab separated, floats as Python's "{}" writes them):
+    readID target strand start end events dist dist_per_event second_target second_dist
+start / end: the first and last target point of the match, in the coordinates of the target searched (for strand - those
+of the reversed record).  second_target: the best of the other targets as name + strand, `.` when there is one target
+only.  A read with fewer than 2 events, with levels of zero deviation or with more than 1 024 events gets `.` fields and
+a note on stderr."""
+import argparse
+import sys
+
+import numpy as np
+
+from . import api
+from .detect_cli import iter_tsv_reads
+
+HEADER = ("readID", "target", "strand", "start", "end", "events", "dist", "dist_per_event", "second_target", "second_dist")
+MAX_EVENTS = 1024
+
+
+class _Parser(argparse.ArgumentParser):
+    def error(self, message):
+        sys.stderr.write("error: %s\n" % message)
+        self.print_help()
+        sys.exit(2)
+
+
+def build_parser():
+    p = _Parser(description="squiggle_map (MI355X) - map the event levels of each read's prefix to reference squiggles by DTW")
+    src = p.add_mutually_exclusive_group()
+    src.add_argument("-s", "--signal", help="signal TSV of raw integer samples written by SquigglePull -r (.gz accepted)")
+    src.add_argument("--blow5", help="BLOW5 file (uncompressed or zlib records)")
+    src.add_argument("--i16", help="packed reads: a .npy file holding an int16 array [reads, samples] (read name = row index)")
+    p.add_argument("-m", "--model", help="reference squiggles: scrappie squiggle text, every #name record is a target")
+    p.add_argument("--both", action="store_true", help="also search each record's reversal (strand -)")
+    p.add_argument("--prefix", type=int, default=4000, help="raw samples of each read that are searched (default 4000)")
+    p.add_argument("--rna", action="store_true", help="the rna event-detection preset instead of dna")
+    p.add_argument("--piece", type=int, default=0, help="cut targets into pieces of this many points (0: whole targets)")
+    p.add_argument("--overlap", type=int, default=0, help="points neighbouring pieces share (a match no longer than this is never cut)")
+    p.add_argument("--device", type=int, default=None, help="GPU index (default $SK_DEVICE or 0)")
+    p.add_argument("--batch", type=int, default=4096, help="reads per GPU call")
+    return p
+
+
+def zscore(v):
+    """(v - mean) / std in numpy (ddof 0), or None when fewer than 2 values or no deviation"""
+    v = np.asarray(v, dtype=np.float64)
+    if v.size < 2:
+        return None
+    sd = v.std()
+    if not sd > 0:
+        return None
+    return (v - v.mean()) / sd
+
+
+def load_targets(path, both):
+    """[(name, strand, z-scored levels)] of a scrappie squiggle text; ValueError for a record that cannot be z-scored"""
+    from .tsvio import read_scrappie_levels
+    levels, order, _ = read_scrappie_levels(path)
+    if not order:
+        raise ValueError("no #name record")
+    out = []
+    for name in order:
+        z = zscore(levels[name])
+        if z is None:
+            raise ValueError("record {}: fewer than 2 levels, or levels without deviation".format(name))
+        out.append((name, "+", z))
+        if both:
+            out.append((name, "-", np.ascontiguousarray(z[::-1])))
+    return out
+
+
+def map_lines(read_ids, queries, records, targets):
+    """the output lines of a batch: queries[r] the z-scored levels or None, records [T, Q] over the reads that have some
+    (in order), targets as load_targets returns them"""
+    out, q = [], 0
+    for rid, z in zip(read_ids, queries):
+        if z is None:
+            out.append("{}\t.\t.\t.\t.\t.\t.\t.\t.\t.\n".format(rid))
+            continue
+        col = records[:, q]
+        q += 1
+        d = np.where(np.isnan(col["dist"]), np.inf, col["dist"])
+        b = int(np.argmin(d))
+        rest = d.copy()
+        rest[b] = np.inf
+        s = int(np.argmin(rest)) if len(d) > 1 else -1
+        h = col[b]
+        out.append("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
+            rid, targets[b][0], targets[b][1], int(h["start"]), int(h["end"]), len(z), float(h["dist"]),
+            float(h["dist"]) / len(z), "." if s < 0 else targets[s][0] + targets[s][1],
+            "." if s < 0 else float(col[s]["dist"])))
+    return out
+
+
+class _Batcher:
+    def __init__(self, args, targets, tool_input):
+        self.args, self.targets, self.input = args, targets, tool_input
+        self.params = api.det_params("rna" if args.rna else "dna")
+        self.ids, self.reads = [], []
+
+    def add(self, rid, sig):
+        self.ids.append(rid)
+        self.reads.append(np.asarray(sig)[:self.args.prefix])
+        if len(self.reads) >= max(1, self.args.batch):
+            self.flush()
+
+    def flush(self):
+        if not self.reads:
+            return
+        live = [i for i, r in enumerate(self.reads) if len(r)]
+        lev = {}
+        if live:
+            off, rec = api.detect_events([self.reads[i] for i in live], self.params)
+            values, _ = api.event_levels(off, rec)
+            for k, i in enumerate(live):
+                lev[i] = values[int(off[k]):int(off[k + 1])]
+        queries = []
+        for i, rid in enumerate(self.ids):
+            v = lev.get(i, np.zeros(0))
+            z = zscore(v) if v.size <= MAX_EVENTS else None
+            if z is None:
+                why = ("more than {} events".format(MAX_EVENTS) if v.size > MAX_EVENTS else
+                       "fewer than 2 events" if v.size < 2 else "event levels without deviation")
+                sys.stderr.write("squiggle_map: {} in read {} of {}\n".format(why, rid, self.input))
+            queries.append(z)
+        qs = [z for z in queries if z is not None]
+        ys = [t[2] for t in self.targets]
+        records = np.zeros((len(ys), 0), dtype=api.HIT_DTYPE)
+        if qs:
+            if self.args.piece > 0:
+                pieces, tiling = api.tile_targets(ys, self.args.piece, self.args.overlap)
+                records = api.merge_tiles(api.map_queries(qs, pieces)[0], tiling)
+            else:
+                records = api.map_queries(qs, ys)[0]
+        sys.stdout.write("".join(map_lines(self.ids, queries, records, self.targets)))
+        self.ids, self.reads = [], []
+
+
+def main(argv=None):
+    parser = build_parser()
+    argv = sys.argv[1:] if argv is None else argv
+    args = parser.parse_args(argv)
+    if len(argv) == 0:
+        parser.print_help(sys.stderr)
+        sys.exit(1)
+    if not (args.signal or args.blow5 or args.i16):
+        parser.error("one of -s/--signal, --blow5, --i16 is needed")
+    if not args.model:
+        parser.error("-m/--model is needed")
+    if args.prefix < 1:
+        parser.error("--prefix must be at least 1")
+    if args.piece < 0 or args.overlap < 0 or (args.piece > 0 and args.overlap >= args.piece):
+        parser.error("need 0 <= --overlap < --piece")
+    if args.overlap and not args.piece:
+        parser.error("--overlap needs --piece")
+    try:
+        targets = load_targets(args.model, args.both)
+    except (ValueError, IndexError, OSError) as e:
+        sys.stderr.write("squiggle_map: {}: {}\n".format(args.model, e))
+        sys.exit(2)
+
+    from . import _lib
+    _lib.warm_start(args.device, also=())
+    src = args.signal or args.blow5 or args.i16
+    out = _Batcher(args, targets, src)
+    sys.stdout.write("\t".join(HEADER) + "\n")
+    try:
+        if args.signal:
+            for _, rid, sig in iter_tsv_reads(args.signal):
+                out.add(rid, sig)
+        elif args.blow5:
+            from .blow5 import read_slow5
+            for rec in read_slow5(args.blow5):
+                out.add(rec["read_id"], rec["signal"])
+        else:
+            a = np.load(args.i16, mmap_mode="r")
+            if a.ndim != 2 or a.dtype != np.int16:
+                raise ValueError("need a 2-D int16 array, got {} {}".format(a.dtype, a.shape))
+            for lo in range(0, a.shape[0], max(1, args.batch)):
+                for i, row in enumerate(np.asarray(a[lo:lo + max(1, args.batch)])):
+                    out.add(str(lo + i), row)
+        out.flush()
+    except (ValueError, EOFError, OSError) as e:
+        sys.stdout.flush()
+        sys.stderr.write("squiggle_map: {}: {}\n".format(src, e))
+        sys.exit(2)
+    sys.stdout.flush()
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,9 @@ screening scheme of MotifSeq's first match under its switches, the segmenter swe
 signal HMM with its state paths, segment levels, both branches of the dRNA segmenter, and the background and events twins of
 the hit family -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
-length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py.
+length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py; and one DTW pair
+list (random pool, pair list with repeats and (i, i) pairs, empty targets, both modes and lane layouts) against the
+references of tests/pairs_ref.py.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -21,6 +23,7 @@ os.environ["SK_TUNING"] = "1"      # this tool flips tuning switches
 
 sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
+import pairs_ref                                      # noqa: E402
 import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
@@ -78,6 +81,38 @@ def session_round(rng):
                                     desc, s, kk, stream_ref.fields(rec[kk, s]), want)
     finally:
         os.environ.pop("SK_DTW_NO_SMALL", None)
+    return None
+
+
+def pairs_round(rng):
+    """One drawn pair list: a pool of random lengths (queries of 1 .. 1 024 points around the lane and row boundaries,
+    targets of 0 .. 3 000), pairs drawn with repeats, (i, i) pairs and shared targets, either mode, either lane layout,
+    as a list of arrays or as (values, off) -- against pairs_ref.records.  Returns None, or what differed."""
+    nseq = int(rng.integers(1, 40))
+    seam = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 128, 129, 256, 257, 512, 1023, 1024]
+    lens = [int(rng.choice(seam)) if rng.random() < 0.4 else int(rng.integers(1, 400)) for _ in range(nseq)]
+    ties = rng.random() < 0.4
+    seqs = [pairs_ref.draw(rng, n, ties) for n in lens]
+    ntargets = int(rng.integers(0, 6))
+    seqs += [pairs_ref.draw(rng, int(rng.choice([0, 1, 2, 200, 1500, 3000])), ties) for _ in range(ntargets)]
+    npairs = int(rng.choice([1, 3, 4, 5, 16, 17, 64, 200]))
+    pairs = [(int(rng.integers(0, nseq)), int(rng.integers(0, len(seqs)))) for _ in range(npairs)]
+    pairs += [(q, q) for q in rng.integers(0, nseq, size=int(rng.integers(0, 3))).tolist()]
+    mode = ["subsequence", "global"][int(rng.integers(2))]
+    no_small = rng.random() < 0.5
+    flat = rng.random() < 0.5
+    desc = "nseq=%d lens=%s npairs=%d %s no_small=%s flat=%s ties=%s" % (len(seqs), [len(s) for s in seqs], len(pairs), mode,
+                                                                      no_small, flat, ties)
+    if no_small:
+        os.environ["SK_DTW_NO_SMALL"] = "1"
+    try:
+        got = api.dtw_pairs(api._as_pool(seqs) if flat else seqs, pairs, mode)
+    finally:
+        os.environ.pop("SK_DTW_NO_SMALL", None)
+    want = pairs_ref.records(ora, seqs, pairs, mode)
+    for p in range(len(pairs)):
+        if not pairs_ref.same_records(got[p:p + 1], want[p:p + 1].astype(got.dtype)):
+            return "%s: pair %d %s: got %s want %s" % (desc, p, pairs[p], got[p], want[p])
     return None
 
 
@@ -372,6 +407,11 @@ def main():
         if msg is not None:
             bad += 1
             print("SESSION mismatch round %d %s" % (rounds, msg))
+        # ---- a DTW pair list against the references of tests/pairs_ref.py ----
+        msg = pairs_round(rng)
+        if msg is not None:
+            bad += 1
+            print("PAIRS mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
