@@ -601,6 +601,41 @@ int sk_dtw_pairs(const double *values, const int64_t *off, int32_t nseq,
 int sk_dtw_pairs_dev(const double *d_values, const int64_t *off, int32_t nseq,
                      const sk_pair *pairs, int64_t npairs, int32_t mode, sk_hit *d_out);
 
+/* Warping paths of a pair list: WHICH target points every query point covers (the resquiggle / eventalign assignment).
+ * For pair p = (q, t) with N = len(q), M = len(t) the path is written as spans, int32 [N][2]: query point i covers the
+ * target points [a_i, b_i], in the coordinates of the target -- the meaning of sk_motifseq_paths_*.  The spans of pair p
+ * start at row span_off[p] = sum of N_k over the pairs k < p of one int32 [sum N][2] array: list order, a query used by
+ * several pairs counted once per pair (the caller derives span_off from off and pairs).
+ *   SK_PAIRS_SUBSEQUENCE  mlpy's subsequence_path from (N-1, end): while i > 0 -- at j == 0 up; else diagonal if it
+ *       equals min3(up, diag, left), else left if it does, else up.  a_0 = b_0 = start, b_{N-1} = end.
+ *   SK_PAIRS_GLOBAL  mlpy's path() from (N-1, M-1): while i > 0 || j > 0 -- at i == 0 left, at j == 0 up, else the same
+ *       order.  Row 0 covers [0, b_0]: a_0 = 0, b_{N-1} = M - 1.  This is the path dtw_std(x, y, dist_only=False)
+ *       returns in mlpy as published; no mlpy build was compared against.
+ * In both modes a_i <= b_i and a_{i+1} is b_i or b_i + 1.
+ * have_records == 0: the records are computed first -- byte for byte what sk_dtw_pairs writes -- stored to `records`,
+ * then traced.  have_records == 1: `records` is input and names the window [start, end] of the target to trace, e.g.
+ * the merged records of a tiled search, in whole-target coordinates, against the whole targets.  Subsequence mode uses
+ * start / end / dist; global mode requires start == 0 and end == M - 1.
+ * Self-check per pair: the DTW recomputed on the window ends, in its corner, on the bits of the record's dist, and the
+ * trace ends on the record's start.  A pair that fails -- or whose record has start / end outside [0, M), end < start,
+ * or, in global mode, another window than the whole target -- gets spans -1 and is counted by
+ * sk_last_path_mismatches(); nothing outside the target is ever read.  A record with NaN dist or SK_FLAG_EMPTY gets
+ * spans -1 and is not counted.
+ * Refusals: those of sk_dtw_pairs, same codes and messages, nothing written; a NULL spans is SK_ERR_INVALID.
+ * npairs == 0 returns SK_OK. */
+int sk_dtw_pairs_paths(const double *values, const int64_t *off, int32_t nseq,
+                       const sk_pair *pairs, int64_t npairs, int32_t mode,
+                       sk_hit *records, int32_t have_records, int32_t *spans);
+/* device-resident form: d_values, d_records and d_spans on the device; off and pairs on the host.  The call
+ * synchronises once between its two launches (the second tier's scratch is sized from the first); nothing is
+ * synchronised after them. */
+int sk_dtw_pairs_paths_dev(const double *d_values, const int64_t *off, int32_t nseq,
+                           const sk_pair *pairs, int64_t npairs, int32_t mode,
+                           sk_hit *d_records, int32_t have_records, int32_t *d_spans);
+/* The tiers of the last such call (diagnostic): pairs whose direction words or window did not fit the LDS tier, the
+ * bytes of one scratch slab (sized from those pairs), the wavefronts that shared them.  Any pointer may be NULL. */
+int sk_last_pair_paths_tiers(int64_t *listed, int64_t *slab_bytes, int64_t *waves);
+
 /* The same call in mlpy's own C arithmetic for inputs that hold inf / nan -- `min3` as "a; if (b < m) m = b; if (c < m)
  * m = c", fabs, np.argmin's first-NaN rule, the back-trace of subsequence_path, all evaluated literally by one GPU lane
  * over the full cost matrix.  medmad of a read whose MAD is 0 divides by zero (MotifSeq.py:196-199) and the reference

@@ -344,6 +344,10 @@ ABI = {
     # device-resident form takes the same list (values / out device, off / pairs host)
     "sk_dtw_pairs": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp]),
     "sk_dtw_pairs_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp]),
+    # ... and its warping paths: the same list, then records, have_records, spans [sum N][2]
+    "sk_dtw_pairs_paths": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp]),
+    "sk_dtw_pairs_paths_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp]),
+    "sk_last_pair_paths_tiers": (C.c_int, [_vp, _vp, _vp]),
     "sk_dtw_subsequence_cref": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _dp, _i32p, _i32p]),
     "sk_normalise_i16": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i32p]),
     "sk_normalise_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i32p]),

@@ -1418,6 +1418,97 @@ def best_targets(records):
     return best
 
 
+def pair_span_off(off, pairs):
+    """span_off int64 [npairs + 1] of a pair list: the spans of pair p are rows span_off[p] .. span_off[p + 1] -- the query
+    lengths of the pairs before it, summed in list order (a query used by several pairs counts once per pair)."""
+    off = np.asarray(off, dtype=np.int64)
+    pr = _as_pairs(pairs)
+    out = np.zeros(len(pr) + 1, dtype=np.int64)
+    if len(pr):
+        q = pr["query"].astype(np.int64)
+        out[1:] = np.cumsum(off[q + 1] - off[q])
+    return out
+
+
+def dtw_pairs_paths(seqs, pairs, mode="subsequence", records=None):
+    """dtw_pairs plus the warping path of every pair: (records HIT_DTYPE [npairs], span_off int64 [npairs + 1], spans int32
+    [sum N, 2]).  Rows span_off[p] .. span_off[p + 1] are pair p's spans: query point i covers the target points
+    spans[.., 0] .. spans[.., 1] (target coordinates; expand_path turns them into mlpy's (px, py)).  mode "subsequence":
+    mlpy's subsequence_path; "global": mlpy's path() of dtw_std, row 0 covering [0, b_0].  records=None: the records are
+    computed first (dtw_pairs' bytes) and returned; otherwise they are input and name the window [start, end] of each
+    target to trace (merged records of a tiled search against the whole targets).  A pair without a distance has spans
+    -1; so has a pair whose path fails the kernel's self-check, and last_path_mismatches() counts those."""
+    if mode not in PAIRS_MODES:
+        raise ValueError("mode %r: need one of %s" % (mode, sorted(PAIRS_MODES)))
+    L = _lib.ensure_init()
+    values, off = _as_pool(seqs)
+    pr = _as_pairs(pairs)
+    if len(pr) and (pr["query"].min() < 0 or pr["query"].max() >= off.size - 1):
+        span_off = np.zeros(len(pr) + 1, dtype=np.int64)           # (the library names the pair and refuses)
+    else:
+        span_off = pair_span_off(off, pr)
+    have = records is not None
+    if have:
+        rec = np.ascontiguousarray(records, dtype=HIT_DTYPE).reshape(-1).copy()
+        if len(rec) != len(pr):
+            raise ValueError("records: need one per pair")
+    else:
+        rec = np.zeros(len(pr), dtype=HIT_DTYPE)
+    spans = np.full((int(span_off[-1]), 2), -1, dtype=np.int32)
+    keep = values if values.size else np.zeros(1)
+    keep_spans = spans if spans.size else np.zeros((1, 2), dtype=np.int32)
+    check(L.sk_dtw_pairs_paths(ptr(keep), ptr(off), off.size - 1, ptr(pr), len(pr), PAIRS_MODES[mode],
+                               ptr(rec if len(rec) else np.zeros(1, dtype=HIT_DTYPE)), int(have), ptr(keep_spans)))
+    with _path_lock:
+        _path_mismatches[0] = max(L.sk_last_path_mismatches(), 0) if len(pr) else 0
+    return rec, span_off, spans
+
+
+def last_pair_paths_tiers():
+    """(listed, slab_bytes, waves) of the last dtw_pairs_paths / map_paths call of this thread's device: the pairs that
+    did not fit the kernel's LDS tier, the bytes of one scratch slab (sized from those pairs), the wavefronts that
+    shared them."""
+    L = _lib.ensure_init()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    check(L.sk_last_pair_paths_tiers(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def map_paths(queries, targets, records, which=None):
+    """The warping path of every query in ONE of its targets: (span_off int64 [Q + 1], spans int32 [sum, 2]).  records
+    [T, Q] come from map_queries, or from merge_tiles with the whole targets passed here; which [Q] names the target per
+    query (default best_targets(records)).  A query whose target is -1 has no path: a zero-length entry in span_off."""
+    qs = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
+    ts = [np.asarray(t, dtype=np.float64).reshape(-1) for t in targets]
+    records = np.asarray(records)
+    Q = len(qs)
+    if records.shape != (len(ts), Q):
+        raise ValueError("records: need shape [T, Q] = (%d, %d)" % (len(ts), Q))
+    which = best_targets(records) if which is None else np.asarray(which, dtype=np.int64).reshape(-1)
+    if which.size != Q or np.any(which >= len(ts)):
+        raise ValueError("which: need one target index per query")
+    use = np.flatnonzero(which >= 0)
+    span_off = np.zeros(Q + 1, dtype=np.int64)
+    if use.size == 0:
+        return span_off, np.zeros((0, 2), dtype=np.int32)
+    pr = np.stack([use, Q + which[use]], axis=1)
+    _, off_p, spans = dtw_pairs_paths(qs + ts, pr, "subsequence", records=records[which[use], use])
+    span_off[use + 1] = np.diff(off_p)
+    return np.cumsum(span_off), spans
+
+
+def dtw_std(x, y, dist_only=True):
+    """Drop-in for mlpy.dtw_std(x, y, dist_only): the global DTW of two already-normalised float64 sequences.  Returns
+    dist, or with dist_only=False (dist, None, (px, py)): the cost matrix is never materialised, the path is mlpy's
+    path() rebuilt from the spans of the pair-list path kernel.  x holds 1 .. 1 024 points."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if dist_only:
+        return float(dtw_pairs([x, y], [(0, 1)], "global")["dist"][0])
+    rec, _, spans = dtw_pairs_paths([x, y], [(0, 1)], "global")
+    return float(rec["dist"][0]), None, expand_path(spans)
+
+
 def tile_targets(targets, piece, overlap):
     """Long targets cut into pieces of `piece` points that step by piece - overlap, for map_queries: returns (pieces,
     tiling) with tiling = {"target": int64 [P], "origin": int64 [P], "length": int64 [T]} -- piece p is

@@ -1050,6 +1050,61 @@ int sk_dtw_pairs(const double *values, const int64_t *off, int32_t nseq,
     return SK_OK;
 }
 
+// ... and the warping paths of the list (sk_pairpath.hip): spans [sum N][2], pair after pair
+int sk_dtw_pairs_paths_dev(const double *d_values, const int64_t *off, int32_t nseq,
+                           const sk_pair *pairs, int64_t npairs, int32_t mode,
+                           sk_hit *d_records, int32_t have_records, int32_t *d_spans)
+{
+    SK_ENTER(c);
+    return sk_pair_paths_run(c, d_values, off, 0, nseq, pairs, npairs, mode, d_records, have_records, d_spans);
+}
+
+int sk_dtw_pairs_paths(const double *values, const int64_t *off, int32_t nseq,
+                       const sk_pair *pairs, int64_t npairs, int32_t mode,
+                       sk_hit *records, int32_t have_records, int32_t *spans)
+{
+    SK_ENTER(c);
+    int rc;
+    if ((rc = sk_pairs_check(off, nseq, pairs, npairs, mode, records))) return rc;   // before anything is copied or launched
+    if (!spans) return sk_fail(SK_ERR_INVALID, "NULL spans");
+    if (npairs == 0) return SK_OK;
+    if (!values) return sk_fail(SK_ERR_INVALID, "NULL values");
+    for (int32_t s = 0; s < nseq; s++)
+        if (off[s + 1] < off[s]) return sk_fail(SK_ERR_INVALID, "offsets not increasing at sequence %d", s);
+    int64_t rows = 0;
+    for (int64_t p = 0; p < npairs; p++) rows += off[pairs[p].query + 1] - off[pairs[p].query];
+    const int64_t total = nseq ? off[nseq] - off[0] : 0;
+    const size_t vb = (((size_t)(total > 0 ? total : 1) * sizeof(double)) + 15) & ~(size_t)15;
+    const size_t sb = (size_t)rows * 2 * sizeof(int32_t);
+    if ((rc = sk_reserve(c, &c->pairsval, vb + (size_t)npairs * sizeof(sk_hit)))) return rc;
+    if ((rc = sk_reserve(c, &c->pathspans, sb))) return rc;
+    double *d_values = (double *)c->pairsval.p;
+    sk_hit *d_rec = (sk_hit *)((char *)c->pairsval.p + vb);
+    int32_t *d_spans = (int32_t *)c->pathspans.p;
+    if (total > 0)
+        SK_HIP(hipMemcpyAsync(d_values, values + off[0], (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (have_records)
+        SK_HIP(hipMemcpyAsync(d_rec, records, (size_t)npairs * sizeof(sk_hit), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_pair_paths_run(c, d_values, off, nseq ? off[0] : 0, nseq, pairs, npairs, mode, d_rec, have_records, d_spans)))
+        return rc;
+    if (!have_records)
+        SK_HIP(hipMemcpyAsync(records, d_rec, (size_t)npairs * sizeof(sk_hit), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(spans, d_spans, sb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// the tiers of the last sk_dtw_pairs_paths* call on this context: pairs left to the scratch tier, bytes of one slab,
+// wavefronts of the scratch launch (all 0 when every pair fitted the LDS tier)
+int sk_last_pair_paths_tiers(int64_t *listed, int64_t *slab_bytes, int64_t *waves)
+{
+    SK_ENTER(c);
+    if (listed) *listed = c->pairpath_listed;
+    if (slab_bytes) *slab_bytes = c->pairpath_slab_bytes;
+    if (waves) *waves = c->pairpath_waves;
+    return SK_OK;
+}
+
 int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
                        double *dist, int32_t *start, int32_t *end, double *cost_last_row)
 {

@@ -66,6 +66,14 @@ struct sk_pair_query {
     int32_t N, L, R, pad;
 };
 
+// ... and one pair of a paths call over the list (sk_pairpath.hip): where its query and target lie in the pool, their
+// lengths, the first row of its spans.  32 bytes.
+struct sk_pairpath_entry {
+    int64_t qoff, toff;   // first point of the query / of the target inside the pool
+    int64_t span_off;     // first row of the pair's spans: the query lengths of the pairs before it, summed
+    int32_t N, M;         // the query's and the target's length
+};
+
 struct sk_ctx {
     int         device = -1;
     bool        ready = false;
@@ -131,6 +139,10 @@ struct sk_ctx {
     sk_buf pairsval;  // pair list: the pool and the records of the host entry point
     std::vector<sk_pair_query> pairs_query;   // one entry per distinct query (kept alive for the async H2D)
     std::vector<sk_pair_entry> pairs_table;   // one entry per pair, (L, R) group after group
+    sk_buf pairpath;  // pair-list paths: the table, one sk_pairpath_entry per pair (sk_pairpath.hip)
+    std::vector<sk_pairpath_entry> pairpath_table;   // (kept alive for the async H2D)
+    int64_t pairpath_listed = 0, pairpath_slab_bytes = 0, pairpath_waves = 0;   // the last such call: pairs left to the
+                                                                                 // scratch tier, bytes of a slab, wavefronts
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -300,6 +312,11 @@ int sk_launch_sdtw_pairs(sk_ctx *c, int L, int R, int global, const double *d_va
 int sk_pairs_check(const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs, int32_t mode, const void *out);
 int sk_pairs_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t off0, int32_t nseq, const sk_pair *pairs,
                  int64_t npairs, int32_t mode, sk_hit *d_out);
+// the warping paths of a pair list (sk_pairpath.hip): the checks of sk_pairs_check, then (have_records == 0) sk_pairs_run
+// into d_rec, then the spans of every pair into d_spans [sum N][2], pair after pair in list order.  d_values / d_rec /
+// d_spans on the device.  Resets the mismatch counter (sk_path_begin) and synchronises between its two launches.
+int sk_pair_paths_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t off0, int32_t nseq, const sk_pair *pairs,
+                      int64_t npairs, int32_t mode, sk_hit *d_rec, int32_t have_records, int32_t *d_spans);
 // the exact single pass that also stores every read's last row (cost, back-trace start) at r * max_len (sk_sdtw.hip)
 int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t *rowS);
 // hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]

@@ -1,7 +1,7 @@
 """squiggle_map: search the event levels of each read's first samples in reference squiggles, on the GPU.
 
     squiggle_map.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
-                    [--piece N --overlap N]
+                    [--piece N --overlap N] [--align FILE]
 
 Per read: event detection on the first --prefix raw samples (api.detect_events), the level of every event
 (api.event_levels), (level - mean) / std in numpy, then subsequence DTW of those levels against every target in one call
@@ -14,7 +14,15 @@ Output: the header line, then one line per read (tab separated, floats as Python
 start / end: the first and last target point of the match, in the coordinates of the target searched (for strand - those
 of the reversed record).  second_target: the best of the other targets as name + strand, `.` when there is one target
 only.  A read with fewer than 2 events, with levels of zero deviation or with more than 1 024 events gets `.` fields and
-a note on stderr."""
+a note on stderr.
+
+--align FILE: the event alignment table.  For every read that printed a match, one line per event of the read against
+its best target, under a header line:
+    readID target strand event sample_start sample_length level z ref_first ref_last
+event: the 0-based index; sample_start / sample_length: the event record's start and length; level: its level; z: its
+z-scored value (the query point); ref_first / ref_last: the target points the event covers on the warping path of the
+match (api.map_paths), in the coordinates of the target searched, as start / end above.  With --piece the merged record
+is traced against the whole target.  stdout is the same with and without --align."""
 import argparse
 import sys
 
@@ -24,6 +32,7 @@ from . import api
 from .detect_cli import iter_tsv_reads
 
 HEADER = ("readID", "target", "strand", "start", "end", "events", "dist", "dist_per_event", "second_target", "second_dist")
+ALIGN_HEADER = ("readID", "target", "strand", "event", "sample_start", "sample_length", "level", "z", "ref_first", "ref_last")
 MAX_EVENTS = 1024
 
 
@@ -46,6 +55,7 @@ def build_parser():
     p.add_argument("--rna", action="store_true", help="the rna event-detection preset instead of dna")
     p.add_argument("--piece", type=int, default=0, help="cut targets into pieces of this many points (0: whole targets)")
     p.add_argument("--overlap", type=int, default=0, help="points neighbouring pieces share (a match no longer than this is never cut)")
+    p.add_argument("--align", help="write the event alignment table to this file: one line per event of every matched read")
     p.add_argument("--device", type=int, default=None, help="GPU index (default $SK_DEVICE or 0)")
     p.add_argument("--batch", type=int, default=4096, help="reads per GPU call")
     return p
@@ -102,9 +112,20 @@ def map_lines(read_ids, queries, records, targets):
     return out
 
 
+def align_lines(rid, target, events, levels, z, spans):
+    """the table lines of one read: events its DET_EVENT_DTYPE records, levels / z the level and query point per event,
+    spans [events, 2] of its path in target = (name, strand, ...); none for a read without a path (spans -1)"""
+    spans = np.asarray(spans).reshape(-1, 2)
+    if spans.size == 0 or spans[0, 0] < 0:
+        return []
+    return ["{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
+        rid, target[0], target[1], e, int(events["start"][e]), int(events["length"][e]), float(levels[e]), float(z[e]),
+        int(spans[e, 0]), int(spans[e, 1])) for e in range(len(z))]
+
+
 class _Batcher:
-    def __init__(self, args, targets, tool_input):
-        self.args, self.targets, self.input = args, targets, tool_input
+    def __init__(self, args, targets, tool_input, align=None):
+        self.args, self.targets, self.input, self.align = args, targets, tool_input, align
         self.params = api.det_params("rna" if args.rna else "dna")
         self.ids, self.reads = [], []
 
@@ -118,12 +139,13 @@ class _Batcher:
         if not self.reads:
             return
         live = [i for i, r in enumerate(self.reads) if len(r)]
-        lev = {}
+        lev, evs = {}, {}
         if live:
             off, rec = api.detect_events([self.reads[i] for i in live], self.params)
             values, _ = api.event_levels(off, rec)
             for k, i in enumerate(live):
                 lev[i] = values[int(off[k]):int(off[k + 1])]
+                evs[i] = rec[int(off[k]):int(off[k + 1])]
         queries = []
         for i, rid in enumerate(self.ids):
             v = lev.get(i, np.zeros(0))
@@ -143,6 +165,14 @@ class _Batcher:
             else:
                 records = api.map_queries(qs, ys)[0]
         sys.stdout.write("".join(map_lines(self.ids, queries, records, self.targets)))
+        if self.align is not None and qs:
+            best = api.best_targets(records)
+            span_off, spans = api.map_paths(qs, ys, records, best)
+            rows = [i for i, z in enumerate(queries) if z is not None]
+            for q, i in enumerate(rows):
+                if best[q] >= 0:
+                    self.align.write("".join(align_lines(self.ids[i], self.targets[int(best[q])], evs[i], lev[i], queries[i],
+                                                         spans[int(span_off[q]):int(span_off[q + 1])])))
         self.ids, self.reads = [], []
 
 
@@ -172,7 +202,15 @@ def main(argv=None):
     from . import _lib
     _lib.warm_start(args.device, also=())
     src = args.signal or args.blow5 or args.i16
-    out = _Batcher(args, targets, src)
+    align = None
+    if args.align:
+        try:
+            align = open(args.align, "w")
+        except OSError as e:
+            sys.stderr.write("squiggle_map: {}: {}\n".format(args.align, e))
+            sys.exit(2)
+        align.write("\t".join(ALIGN_HEADER) + "\n")
+    out = _Batcher(args, targets, src, align)
     sys.stdout.write("\t".join(HEADER) + "\n")
     try:
         if args.signal:
@@ -193,8 +231,12 @@ def main(argv=None):
     except (ValueError, EOFError, OSError) as e:
         sys.stdout.flush()
         sys.stderr.write("squiggle_map: {}: {}\n".format(src, e))
+        if align is not None:
+            align.close()
         sys.exit(2)
     sys.stdout.flush()
+    if align is not None:
+        align.close()
 
 
 if __name__ == "__main__":

@@ -8,7 +8,8 @@ the hit family -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
 length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py; and one DTW pair
 list (random pool, pair list with repeats and (i, i) pairs, empty targets, both modes and lane layouts) against the
-references of tests/pairs_ref.py.
+references of tests/pairs_ref.py; and the warping paths of one such list (any tier, computed or supplied records)
+against the references of tests/pair_paths_ref.py.
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -23,6 +24,7 @@ os.environ["SK_TUNING"] = "1"      # this tool flips tuning switches
 
 sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
+import pair_paths_ref                                 # noqa: E402
 import pairs_ref                                      # noqa: E402
 import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
@@ -113,6 +115,52 @@ def pairs_round(rng):
     for p in range(len(pairs)):
         if not pairs_ref.same_records(got[p:p + 1], want[p:p + 1].astype(got.dtype)):
             return "%s: pair %d %s: got %s want %s" % (desc, p, pairs[p], got[p], want[p])
+    return None
+
+
+def pair_paths_round(rng):
+    """One drawn pair list as in pairs_round (queries around the stripe edges, targets of 0 .. 3 000 points, repeats,
+    (i, i) pairs), either mode, the tiers as they fall, every pair in the scratch tier or one wavefront for all of them,
+    records computed or supplied -- spans against pair_paths_ref.list_spans, records against pairs_ref.records, no
+    mismatch counted.  Returns None, or what differed."""
+    nseq = int(rng.integers(1, 30))
+    seam = [1, 2, 3, 15, 16, 17, 63, 64, 65, 127, 128, 129, 200, 256, 257, 1023, 1024]
+    lens = [int(rng.choice(seam)) if rng.random() < 0.4 else int(rng.integers(1, 400)) for _ in range(nseq)]
+    ties = rng.random() < 0.4
+    seqs = [pairs_ref.draw(rng, n, ties) for n in lens]
+    ntargets = int(rng.integers(0, 6))
+    seqs += [pairs_ref.draw(rng, int(rng.choice([0, 1, 2, 200, 513, 1025, 3000])), ties) for _ in range(ntargets)]
+    npairs = int(rng.choice([1, 3, 16, 65, 200]))
+    pairs = [(int(rng.integers(0, nseq)), int(rng.integers(0, len(seqs)))) for _ in range(npairs)]
+    pairs += [(q, q) for q in rng.integers(0, nseq, size=int(rng.integers(0, 3))).tolist()]
+    mode = ["subsequence", "global"][int(rng.integers(2))]
+    tier = int(rng.integers(3))
+    supplied = rng.random() < 0.5
+    desc = "nseq=%d lens=%s npairs=%d %s tier=%d supplied=%s ties=%s" % (len(seqs), [len(s) for s in seqs], len(pairs), mode,
+                                                                      tier, supplied, ties)
+    if tier >= 1:
+        os.environ["SK_PATH_LDS_BYTES"] = "0"
+    if tier == 2:
+        os.environ["SK_PATH_SCRATCH_BYTES"] = "1000"
+    try:
+        records = api.dtw_pairs(seqs, pairs, mode) if supplied else None
+        rec, off, spans = api.dtw_pairs_paths(seqs, pairs, mode, records=records)
+        counted = api.last_path_mismatches()
+    finally:
+        os.environ.pop("SK_PATH_LDS_BYTES", None)
+        os.environ.pop("SK_PATH_SCRATCH_BYTES", None)
+    if counted:
+        return "%s: %d pairs failed the self-check" % (desc, counted)
+    if not pairs_ref.same_records(rec, pairs_ref.records(ora, seqs, pairs, mode).astype(rec.dtype)):
+        return "%s: records differ" % desc
+    woff, want = pair_paths_ref.list_spans(ora, seqs, pairs, mode)
+    if not np.array_equal(off, woff):
+        return "%s: span_off %s want %s" % (desc, off.tolist(), woff.tolist())
+    for p in range(len(pairs)):
+        a, b = int(off[p]), int(off[p + 1])
+        if not np.array_equal(spans[a:b], want[a:b]):
+            return "%s: pair %d %s: spans differ from row %d" % (desc, p, pairs[p],
+                                                               int(np.flatnonzero((spans[a:b] != want[a:b]).any(axis=1))[0]))
     return None
 
 
@@ -412,6 +460,11 @@ def main():
         if msg is not None:
             bad += 1
             print("PAIRS mismatch round %d %s" % (rounds, msg))
+        # ---- ... and the warping paths of one against tests/pair_paths_ref.py ----
+        msg = pair_paths_round(rng)
+        if msg is not None:
+            bad += 1
+            print("PAIR PATHS mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
