@@ -1,7 +1,8 @@
 """Seeded random cases for the kernel files that have no other randomised test in the suite -- csrc/sk_sweep.hip,
 sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, through the twins of the
 hit family sk_bg.hip and sk_events.hip, for the switches of the screening scheme sk_sdtwq.hip, and for both branches of the
-dRNA segmenter (sk_drna_walk.hip and the dRNA kernels of sk_prep.hip): per family
+dRNA segmenter (sk_drna_walk.hip and the dRNA kernels of sk_prep.hip), and for DTW over a pair list with its warping paths
+(sk_pairs.hip, sk_pairpath.hip): per family
 draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
 what the reference says,  call_<family>(api, case, exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or
 the first difference as text.
@@ -9,7 +10,7 @@ the first difference as text.
 A plain module: not collected, no conftest, pure numpy, no GPU import at module level (`api` is handed in).  The same
 seed gives the same case on any machine: draw_* take a numpy.random.Generator and nothing else.  Used by
 tests/test_random_cases.py (CPU: the committed seeds reach what they claim), tests/test_gpu_random.py (GPU: every seed
-against its reference, plus three interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
+against its reference, plus four interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
 families is DRAW[family] with its running generator).  tests/RANDOM_CASES.md says what each family draws, the
 references, the budgets, the wall times, and which one-line kernel mutants the committed seeds catch.
 
@@ -17,7 +18,8 @@ The references are the statements that already exist: the oracle's scale_outlier
 sweep, reference_hits (test_hits_host.py), reference_paths (test_paths_host.py), numpy_pull_text (test_squigglepull.py),
 reference_panel (test_panel_host.py), detect_ref.py, hmm_ref.py, hmm_path_ref.py, plain numpy on the oracle's segments
 for the levels, reference_background_reads (test_background_host.py), reference_batch / reference_pool
-(test_events_host.py), the oracle's scale_outliers + drna_segs / drna_roll per read for the dRNA branches.  Every comparison
+(test_events_host.py), the oracle's scale_outliers + drna_segs / drna_roll per read for the dRNA branches,
+pairs_ref.records and pair_paths_ref.list_spans for the pair lists.  Every comparison
 is exact: integers as integers, doubles and text byte for byte.
 """
 import os
@@ -43,6 +45,8 @@ SEEDS = {
     "drna": [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 14, 15, 17, 18, 20, 22, 24, 27, 28, 29, 30, 31, 34, 35, 36, 37, 38, 39, 40,
              54, 56, 65, 66, 74, 116, 117, 140, 170, 210],
     "roll": [0, 1, 2, 3, 4, 10, 11, 13, 16, 21, 23, 24, 29, 31, 59],
+    "pairs": [4, 5, 7, 9, 23, 54, 119, 130, 133],
+    "pairpaths": [1, 5, 6, 7, 13, 17, 21, 22, 23, 36, 50, 145],
 }
 
 # every tuning switch a case may set; a runner clears the ones a case does not name
@@ -56,7 +60,8 @@ SWITCHES = ("SK_SEG_DELTA_SCALE", "SK_WALK_GENERAL", "SK_DTW_SMALL_MAX", "SK_HIT
 # the family's number in the seed of its generator.  Frozen: the first four are what sorted(SEEDS).index(family) gave when
 # the table held four keys, so those cases stay what they were (tests/test_random_cases.py pins their digests); a new
 # family takes the next free number, whatever its name.
-FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8, drna=9, roll=10)
+FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8, drna=9, roll=10,
+                    pairs=11, pairpaths=12)
 
 
 def rng_of(family, seed):
@@ -76,7 +81,7 @@ def _pick(rng, values):
 
 # what a case holds besides its drawn parameters: the arrays (describe leaves them out, case_digest hashes them)
 ARRAY_KEYS = ("reads", "rows", "sets", "motifs", "prefixes", "calib", "lens", "sig", "win", "means", "sds", "model", "cal",
-              "use")
+              "use", "seqs", "pairs")
 
 
 def _plain(v):
@@ -2310,6 +2315,362 @@ def diff_roll(case, got, exp):
 
 
 # ======================================================================================================================
+# DTW over a pair list (sk_pairs.hip, k_sdtw's MODE_PAIRS / MODE_PAIRS_GLOBAL) and its warping paths (sk_pairpath.hip)
+# ======================================================================================================================
+# query lengths around the lane (16 | 64), row (16 R | 64 R) and stripe (64 s) boundaries; 32 and 256 are where
+# sk_exact_shape changes the lane layout, 1 024 is the longest query
+PAIRS_SEAM = (1, 2, 3, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 256, 257, 512, 1023, 1024)
+PAIRS_SMALL_MAX = 2048                           # sk_exact_shape: up to here a query of 32 .. 256 points takes 64 lanes
+PAIRS_CELLS = 30_000_000                         # cost-matrix cells the oracle fills per case (see RANDOM_CASES.md)
+PAIRS_TARGETS = (0, 1, 2, 3, 200, 513, 1025, 1500, 3000)
+PAIRS_CLIFF = 3000                               # a target that keeps its wavefront running long after its mates ended
+PAIRS_NATURAL_TARGET = 60                        # the natural L = 16 route: targets of a few dozen points
+PAIRS_TILES = ((64, 40), (256, 128), (1024, 512))
+# sk_pairpath.hip
+PP_LDS_WORDS = PATH_LDS_BYTES // 4               # 6 400 direction words
+PP_LDS_COLS = 1024
+PP_ONE_WAVE = "1"                                # SK_PATH_SCRATCH_BYTES below any slab: one wavefront for all listed pairs
+PP_TIERS = ({}, {"SK_PATH_LDS_BYTES": "0"}, {"SK_PATH_LDS_BYTES": "0", "SK_PATH_SCRATCH_BYTES": PP_ONE_WAVE})
+PP_MAX_WAVES = 256                               # 8 wavefronts per CU: no device this runs on has fewer than 32 CUs
+
+
+def pairs_cells(N, M, mode):
+    """cells the oracle fills for one pair: the global mode runs between two sentinels"""
+    if M == 0:
+        return 0
+    return (N + 2) * (M + 2) if mode == "global" else N * M
+
+
+def _pairs_pool(rng, lens, ties):
+    import pairs_ref
+    return [pairs_ref.draw(rng, int(n), ties) for n in lens]
+
+
+def _pairs_within(seqs, pairs, mode, budget, per_pair=1):
+    """the longest prefix of `pairs` (one pair at least) whose reference stays inside the cell budget"""
+    keep, total = [], 0
+    for q, t in pairs:
+        c = per_pair * pairs_cells(len(seqs[q]), len(seqs[t]), mode)
+        if keep and total + c > budget:
+            break
+        keep.append((int(q), int(t)))
+        total += c
+    return keep, total
+
+
+def _pairs_extras(rng, pairs, nq):
+    """(i, i) pairs, a query used by three more pairs, a pair repeated verbatim -- mixed into the list"""
+    pairs = list(pairs)
+    pairs += [(q, q) for q in rng.integers(0, nq, size=int(rng.integers(0, 3))).tolist()]
+    if rng.random() < 0.5:
+        q = int(rng.integers(0, nq))
+        pairs += [(q, pairs[int(rng.integers(len(pairs)))][1]) for _ in range(3)]
+    if rng.random() < 0.5:
+        pairs.insert(int(rng.integers(len(pairs) + 1)), pairs[int(rng.integers(len(pairs)))])
+    return pairs
+
+
+def draw_pairs(rng):
+    """A pool and a pair list for api.dtw_pairs.  kind 'list': the draw of the fuzz tool's former pairs leg (queries around
+    the seams, targets of 0 .. 3 000 points, repeats, (i, i) pairs); 'natural': more than PAIRS_SMALL_MAX pairs without a
+    switch, a query for every R of L = 16 and some on 64 lanes, targets of a few dozen points; 'cliff': every target is
+    either at least PAIRS_CLIFF points or at most 3, so that a wavefront's lane groups end far apart."""
+    kind = _pick(rng, ("list", "list", "list", "natural", "cliff"))
+    mode = _pick(rng, ("subsequence", "global"))
+    ties = bool(rng.random() < 0.4)
+    env = {}
+    if kind == "natural":
+        lens = [16 * R - int(_pick(rng, (0, 1, 15, int(rng.integers(16))))) for R in range(1, 17)]
+        lens += [int(_pick(rng, (257, 300, 512, 1023, 1024))) for _ in range(int(rng.integers(1, 4)))]
+        lens += [int(_pick(rng, PAIRS_SEAM[:17])) for _ in range(int(rng.integers(0, 6)))]
+        nq = len(lens)
+        tl = [0, 1] + [int(rng.integers(2, PAIRS_NATURAL_TARGET + 1)) for _ in range(int(rng.integers(6, 20)))]
+        seqs = _pairs_pool(rng, lens + tl, ties)
+        npairs = PAIRS_SMALL_MAX + 1 + int(_pick(rng, (0, 0, 1, 3, int(rng.integers(300)))))
+        q = np.concatenate([np.arange(nq), rng.integers(0, nq, size=npairs - nq)])       # every query is used
+        pairs = list(zip(q.tolist(), rng.integers(nq, len(seqs), size=npairs).tolist()))
+        pairs[int(rng.integers(npairs))] = (0, 0)
+        pairs[int(rng.integers(1, npairs))] = pairs[0]
+    elif kind == "cliff":
+        if rng.random() < 0.5:
+            env["SK_DTW_NO_SMALL"] = "1"
+        nq = int(rng.integers(2, 9))
+        lens = [int(_pick(rng, (1, 2, 15, 16, 17, 31, 40, 100))) for _ in range(nq)]
+        tl = [int(_pick(rng, (0, 1, 2, 3))) for _ in range(int(rng.integers(2, 6)))]
+        tl += [PAIRS_CLIFF + int(rng.integers(0, 200)) for _ in range(int(rng.integers(1, 3)))]
+        seqs = _pairs_pool(rng, lens + tl, ties)
+        npairs = int(_pick(rng, (3, 5, 9, 14, 30)))
+        pairs = list(zip(rng.integers(0, nq, size=npairs).tolist(), rng.integers(nq, len(seqs), size=npairs).tolist()))
+        pairs = _pairs_extras(rng, pairs, nq)
+    else:
+        if rng.random() < 0.5:
+            env["SK_DTW_NO_SMALL"] = "1"
+        nq = int(rng.integers(1, 40))
+        lens = [int(_pick(rng, PAIRS_SEAM)) if rng.random() < 0.4 else int(rng.integers(1, 400)) for _ in range(nq)]
+        tl = [int(_pick(rng, PAIRS_TARGETS)) for _ in range(int(rng.integers(0, 6)))]
+        seqs = _pairs_pool(rng, lens + tl, ties)
+        npairs = int(_pick(rng, (1, 3, 4, 5, 16, 17, 64, 200)))
+        pairs = list(zip(rng.integers(0, nq, size=npairs).tolist(), rng.integers(0, len(seqs), size=npairs).tolist()))
+        pairs = _pairs_extras(rng, pairs, nq)
+    pairs, cells = _pairs_within(seqs, pairs, mode, PAIRS_CELLS)
+    form = _pick(rng, ("list", "flat"))
+    pad = int(rng.integers(1, 9)) if form == "flat" else 0
+    return dict(family="pairs", kind=kind, mode=mode, ties=ties, form=form, pad=pad, nseq=len(seqs), nq=nq,
+                npairs=len(pairs), cells=cells, seqs=seqs, pairs=np.array(pairs, dtype=np.int64).reshape(-1, 2), env=env)
+
+
+def pairs_pool_of(case):
+    """the pool as the case's form hands it to the library: the list, or (values, off) with off[0] = pad > 0 and NaN in
+    front of the first sequence"""
+    if case["form"] == "list":
+        return case["seqs"]
+    seqs = case["seqs"]
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in seqs])
+    values = np.concatenate([np.full(case["pad"], np.nan)] + [np.asarray(s, dtype=np.float64) for s in seqs])
+    return values, off + case["pad"]
+
+
+def pairs_plan(case):
+    """The host plan of sk_pairs_run as include/squigglekit_hip.h and sk_pairs.hip state it, in plain Python: dict(shape =
+    {query index: (L, R)} by sk_exact_shape(N, npairs) under the case's switches, groups = {(L, R): dict(count, P, order,
+    M)} in launch order (L = 16 before 64, R rising)) -- count pairs, P the sorted short-lane counts L R - N of the group's
+    queries, order the pair indices as the table holds them (longest target first, ties in list order: the stable sort),
+    M their target lengths.  Lane group k of a launch serves order[k]; a wavefront holds 64 / L of them."""
+    seqs, pairs = case["seqs"], case["pairs"]
+    shape, members = {}, {}
+    for p, (q, t) in enumerate(pairs.tolist()):
+        if q not in shape:
+            shape[q] = panel_shape(len(seqs[q]), len(pairs), case["env"])                # (sk_exact_shape, restated there)
+        members.setdefault(shape[q], []).append(p)
+    groups = {}
+    for key in sorted(members):
+        L, R = key
+        order = sorted(members[key], key=lambda p: -len(seqs[pairs[p, 1]]))             # (sorted() is stable)
+        groups[key] = dict(count=len(order), order=order, M=[len(seqs[pairs[p, 1]]) for p in order],
+                           P=sorted({L * R - len(seqs[pairs[p, 0]]) for p in order}))
+    return dict(shape=shape, groups=groups)
+
+
+def expect_pairs(ora, case):
+    import pairs_ref
+    want = pairs_ref.records(ora, case["seqs"], case["pairs"].tolist(), case["mode"])
+    empty = np.array([len(case["seqs"][t]) == 0 for t in case["pairs"][:, 1]], dtype=bool)
+    assert np.array_equal(np.isnan(want["dist"]), empty)       # a NaN distance is expected for an empty target only
+    return dict(want=want)
+
+
+def call_pairs(api, case, exp=None):
+    return api.dtw_pairs(pairs_pool_of(case), case["pairs"], case["mode"])
+
+
+def diff_pairs(case, got, exp):
+    import pairs_ref
+    want = exp["want"]
+    if got.shape != want.shape:
+        return "records shaped %s, want %s" % (got.shape, want.shape)
+    for p in range(len(want)):                                  # every pair, by the rule of pairs_ref.same_records
+        if not pairs_ref.same_records(got[p:p + 1], want[p:p + 1].astype(got.dtype)):
+            q, t = case["pairs"][p]
+            return "pair %d (%d, %d) (N=%d, M=%d): got %s want %s" % (p, q, t, len(case["seqs"][q]), len(case["seqs"][t]),
+                                                                      got[p], want[p])
+    return None
+
+
+# ---- warping paths ------------------------------------------------------------------------------------------------------
+def draw_pairpaths(rng):
+    """A pool and a pair list for api.dtw_pairs_paths: the draw of the fuzz tool's former pair-paths leg (queries around
+    the stripe edges, targets of 0 .. 3 000 points, repeats, (i, i) pairs), either mode, a tier setting of PP_TIERS, and
+    where the records come from -- 'computed' in the call; 'own': the reference's records supplied as they are (NaN,
+    FLAG_EMPTY records of empty targets among them); 'tiles' (subsequence): per pair the reference's records of the
+    query in the pieces of api.tile_targets, merged by api.merge_tiles, traced against the whole target; 'wrong': the
+    reference's records with a drawn handful changed (expect_pairpaths says how)."""
+    mode = _pick(rng, ("subsequence", "global"))
+    ties = bool(rng.random() < 0.4)
+    tier = int(rng.integers(3))
+    records = _pick(rng, ("computed", "computed", "own", "wrong", "tiles"))
+    if records == "tiles":
+        mode = "subsequence"
+    kind = _pick(rng, ("list", "list", "list", "thin"))
+    if kind == "thin":                           # few points against one column or one row: N == 1, M == 1, W == 1
+        nq = int(rng.integers(2, 8))
+        lens = [int(_pick(rng, (1, 1, 2, 3, 64, 65))) for _ in range(nq)]
+        tl = [int(_pick(rng, (1, 1, 2, 16, 17, 1025, 1040))) for _ in range(int(rng.integers(1, 5)))]
+    else:
+        nq = int(rng.integers(1, 30))
+        lens = [int(_pick(rng, PAIRS_SEAM)) if rng.random() < 0.4 else int(rng.integers(1, 400)) for _ in range(nq)]
+        tl = [int(_pick(rng, PAIRS_TARGETS)) for _ in range(int(rng.integers(0, 6)))]
+    seqs = _pairs_pool(rng, lens + tl, ties)
+    npairs = int(_pick(rng, (1, 3, 16, 65, 200)))
+    first = nq if kind == "thin" else 0
+    pairs = list(zip(rng.integers(0, nq, size=npairs).tolist(), rng.integers(first, len(seqs), size=npairs).tolist()))
+    pairs = _pairs_extras(rng, pairs, nq)
+    piece, overlap = _pick(rng, PAIRS_TILES)
+    per_pair = 2 if records != "tiles" else 2 + -(-piece // (piece - overlap))           # records + path (+ the pieces)
+    pairs, cells = _pairs_within(seqs, pairs, mode, PAIRS_CELLS, per_pair)
+    case = dict(family="pairpaths", kind=kind, mode=mode, ties=ties, tier=tier, records=records, nseq=len(seqs), nq=nq,
+                npairs=len(pairs), cells=cells, seqs=seqs, pairs=np.array(pairs, dtype=np.int64).reshape(-1, 2),
+                env=dict(PP_TIERS[tier]))
+    if records == "tiles":
+        case.update(piece=piece, overlap=overlap)
+    if records == "wrong":
+        case.update(nwrong=int(rng.integers(1, 6)), wrong_seed=int(rng.integers(1 << 30)))
+    return case
+
+
+def _pairpaths_tiles(ora, case):
+    """(records, spans per pair) of the 'tiles' kind: per pair the reference's records of the query in every piece of its
+    target, merged into whole-target coordinates; the path is the reference's path in the winning piece (smallest dist,
+    then smallest end, then first piece: merge_tiles' order), shifted by the piece's origin"""
+    import pair_paths_ref
+    import pairs_ref
+    from squigglekit_amd import api
+    seqs = case["seqs"]
+    rec = np.zeros(len(case["pairs"]), dtype=pairs_ref.HIT)
+    parts, memo = [], {}
+    for p, (q, t) in enumerate(case["pairs"].tolist()):
+        if (q, t) not in memo:
+            x = seqs[q]
+            pieces, tiling = api.tile_targets([seqs[t]], case["piece"], case["overlap"])
+            per = pairs_ref.records(ora, [x] + pieces, [(0, 1 + k) for k in range(len(pieces))], "subsequence")
+            merged = api.merge_tiles(per.astype(api.HIT_DTYPE).reshape(-1, 1), tiling)[0, 0]
+            if np.isnan(merged["dist"]):
+                sp = np.full((len(x), 2), -1, dtype=np.int32)
+            else:
+                win = min(range(len(pieces)), key=lambda k: (per["dist"][k], per["end"][k] + tiling["origin"][k], k))
+                sp = pair_paths_ref.spans(ora, x, pieces[win], "subsequence") + np.int32(tiling["origin"][win])
+                assert (sp[0, 0], sp[-1, 1]) == (merged["start"], merged["end"])
+            memo[q, t] = (merged, sp)
+        rec[p] = tuple(memo[q, t][0].tolist())
+        parts.append(memo[q, t][1])
+    return rec, parts
+
+
+def _pairpaths_wrong(ora, case, rec):
+    """(records, indices) of the 'wrong' kind: nwrong pairs with a distance (but never all of them) get their dist moved
+    by one ulp or -- with normal draws, never with ties -- their start moved to another column of the target: in global mode any of 1 .. M - 1
+    (the record no longer names the whole target), in subsequence mode a column of (start, end], which leaves the match's
+    first column out of the window; the corner of that window must then differ from dist in its bits (asserted: the
+    statement of the self-check, include/squigglekit_hip.h)."""
+    rng = np.random.default_rng([97, case["wrong_seed"]])
+    seqs, pairs = case["seqs"], case["pairs"]
+    rec = rec.copy()
+    good = np.flatnonzero(~np.isnan(rec["dist"]))
+    count = min(case["nwrong"], good.size - 1)                 # (a good record at least stays as it is)
+    which = sorted(rng.choice(good, size=count, replace=False).tolist()) if count > 0 else []
+    for p in which:
+        M = len(seqs[pairs[p, 1]])
+        s, e = int(rec["start"][p]), int(rec["end"][p])
+        move = not case["ties"] and rng.random() < 0.5 and (M >= 2 if case["mode"] == "global" else e > s)
+        if move and case["mode"] == "global":
+            rec["start"][p] = int(rng.integers(1, M))
+        elif move:
+            s2 = int(rng.integers(s + 1, e + 1))
+            x, y = seqs[pairs[p, 0]], seqs[pairs[p, 1]]
+            corner = ora.dtw_subsequence(x, y[s2:e + 1], want_cost=True)[3][-1, -1]
+            assert np.float64(corner).tobytes() != np.float64(rec["dist"][p]).tobytes(), (p, s, s2, e)
+            rec["start"][p] = s2
+        else:
+            rec["dist"][p] = np.nextafter(rec["dist"][p], np.inf if rng.random() < 0.5 else -np.inf)
+    return rec, which
+
+
+def pairpaths_plan(case, records, env=None):
+    """What sk_pair_paths_run does with `records` under the switches (the case's, or `env`), restated: dict(listed =
+    the pairs the LDS tier hands on, in list order; W = their windows; slab_bytes, waves as sk_last_pair_paths_tiers
+    reports them; traced = (pair, N, W) of every pair that is traced).  A pair is traced when its record has a distance, no FLAG_EMPTY, 0 <= start <= end < M and, in global
+    mode, names the whole target; it is listed when N ceil(W / 16) exceeds the LDS words or W exceeds PP_LDS_COLS."""
+    env = case["env"] if env is None else env
+    words_max = PP_LDS_WORDS
+    if "SK_PATH_LDS_BYTES" in env:
+        v = int(env["SK_PATH_LDS_BYTES"])
+        if v >= 0 and v // 4 < PP_LDS_WORDS:
+            words_max = v // 4
+    listed, Ws, words, traced = [], [], [], []
+    for p, (q, t) in enumerate(case["pairs"].tolist()):
+        N, M, h = len(case["seqs"][q]), len(case["seqs"][t]), records[p]
+        s, e = int(h["start"]), int(h["end"])
+        if np.isnan(h["dist"]) or h["flags"] & 1 or s < 0 or e < s or e >= M:
+            continue
+        if case["mode"] == "global" and (s != 0 or e != M - 1):
+            continue
+        W = e - s + 1
+        traced.append((p, N, W))
+        if N * ((W + 15) // 16) > words_max or W > PP_LDS_COLS:
+            listed.append(p)
+            Ws.append(W)
+            words.append(N * ((W + 15) // 16))
+    if not listed:
+        return dict(listed=[], W=[], slab_bytes=0, waves=0, traced=traced)
+    slab_words = (2 * max(Ws) + max(words) + 1) & ~1
+    budget = 1 << 30
+    if "SK_PATH_SCRATCH_BYTES" in env and int(env["SK_PATH_SCRATCH_BYTES"]) > 0:
+        budget = int(env["SK_PATH_SCRATCH_BYTES"])
+    waves = max(1, min(budget // (slab_words * 4), PP_MAX_WAVES, len(listed)))
+    return dict(listed=listed, W=Ws, slab_bytes=slab_words * 4, waves=waves, traced=traced)
+
+
+def expect_pairpaths(ora, case):
+    """dict(records: what the call returns as records; supplied: the records handed in, or None; off, spans; mismatches:
+    the pairs the self-check must count; truth: the reference's records of the list)"""
+    import pair_paths_ref
+    import pairs_ref
+    seqs, pairs, mode = case["seqs"], case["pairs"].tolist(), case["mode"]
+    truth = pairs_ref.records(ora, seqs, pairs, mode)
+    off = np.zeros(len(pairs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(seqs[q]) for q, _ in pairs])
+    wrong = []
+    if case["records"] == "tiles":
+        supplied, parts = _pairpaths_tiles(ora, case)
+        spans = np.concatenate(parts)
+    else:
+        woff, spans = pair_paths_ref.list_spans(ora, seqs, pairs, mode)
+        assert np.array_equal(woff, off)
+        supplied = None if case["records"] == "computed" else truth
+        if case["records"] == "wrong":
+            supplied, wrong = _pairpaths_wrong(ora, case, truth)
+            spans = spans.copy()
+            for p in wrong:
+                spans[off[p]:off[p + 1]] = -1
+    return dict(records=truth if supplied is None else supplied, supplied=supplied, off=off, spans=spans, wrong=wrong,
+                mismatches=len(wrong), truth=truth)
+
+
+def call_pairpaths(api, case, exp):
+    """(records, span_off, spans, mismatches counted, (listed, slab_bytes, waves))"""
+    sup = None if exp["supplied"] is None else exp["supplied"].astype(api.HIT_DTYPE)
+    rec, off, spans = api.dtw_pairs_paths(case["seqs"], case["pairs"], case["mode"], records=sup)
+    return rec, off, spans, api.last_path_mismatches(), api.last_pair_paths_tiers()
+
+
+def diff_pairpaths(case, got, exp):
+    import pairs_ref
+    rec, off, spans, counted, tiers = got
+    if not pairs_ref.same_records(rec, exp["records"].astype(rec.dtype)):
+        want = exp["records"].astype(rec.dtype)
+        p = next(p for p in range(len(rec)) if not pairs_ref.same_records(rec[p:p + 1], want[p:p + 1]))
+        return "record of pair %d %s: got %s want %s" % (p, case["pairs"][p].tolist(), rec[p], want[p])
+    if off.dtype != np.int64 or not np.array_equal(off, exp["off"]):
+        return "span_off %s want %s" % (off.tolist()[:8], exp["off"].tolist()[:8])
+    if spans.dtype != np.int32 or spans.shape != exp["spans"].shape:
+        return "spans %s %s, want int32 %s" % (spans.dtype, spans.shape, exp["spans"].shape)
+    for p in range(len(rec)):                                   # every pair
+        a, b = int(off[p]), int(off[p + 1])
+        if not np.array_equal(spans[a:b], exp["spans"][a:b]):
+            i = int(np.flatnonzero((spans[a:b] != exp["spans"][a:b]).any(axis=1))[0])
+            return "pair %d %s (record %s)%s: spans differ from row %d: got %s want %s" % (
+                p, case["pairs"][p].tolist(), exp["records"][p], " [changed record]" if p in exp["wrong"] else "", i,
+                spans[a + i:a + i + 3].tolist(), exp["spans"][a + i:a + i + 3].tolist())
+    if counted != exp["mismatches"]:
+        return "%d pairs failed the self-check, want %d %s" % (counted, exp["mismatches"], exp["wrong"])
+    plan = pairpaths_plan(case, exp["records"])
+    if tiers != (len(plan["listed"]), plan["slab_bytes"], plan["waves"]):
+        return "tiers (listed, slab bytes, wavefronts) %s, want %s" % (tiers, (len(plan["listed"]), plan["slab_bytes"],
+                                                                              plan["waves"]))
+    return None
+
+
+# ======================================================================================================================
 # the older single-set calls, for the interleaved sequence only
 # ======================================================================================================================
 def draw_plain(rng, kind):
@@ -2386,17 +2747,20 @@ def result_bytes(got):
 
 
 DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull, panel=draw_panel, detect=draw_detect,
-            hmm=draw_hmm, levels=draw_levels, screen=draw_screen, drna=draw_drna, roll=draw_roll)
+            hmm=draw_hmm, levels=draw_levels, screen=draw_screen, drna=draw_drna, roll=draw_roll, pairs=draw_pairs,
+            pairpaths=draw_pairpaths)
 EXPECT = dict(sweep=expect_sweep, hits=expect_hits, paths=expect_paths, pull=expect_pull, segment=expect_plain,
               motifseq=expect_plain, pa=expect_plain, panel=expect_panel, detect=expect_detect, hmm=expect_hmm,
               levels=expect_levels, background=expect_background, events=expect_events, screen=expect_screen,
-              drna=expect_drna, roll=expect_roll)
+              drna=expect_drna, roll=expect_roll, pairs=expect_pairs, pairpaths=expect_pairpaths)
 CALL = dict(sweep=call_sweep, hits=call_hits, paths=call_paths, pull=call_pull, segment=call_plain, motifseq=call_plain,
             pa=call_plain, panel=call_panel, detect=call_detect, hmm=call_hmm, levels=call_levels,
-            background=call_background, events=call_events, screen=call_screen, drna=call_drna, roll=call_roll)
+            background=call_background, events=call_events, screen=call_screen, drna=call_drna, roll=call_roll,
+            pairs=call_pairs, pairpaths=call_pairpaths)
 DIFF = dict(sweep=diff_sweep, hits=diff_hits, paths=diff_paths, pull=diff_pull, segment=diff_plain, motifseq=diff_plain,
             pa=diff_plain, panel=diff_panel, detect=diff_detect, hmm=diff_hmm, levels=diff_levels,
-            background=diff_background, events=diff_events, screen=diff_screen, drna=diff_drna, roll=diff_roll)
+            background=diff_background, events=diff_events, screen=diff_screen, drna=diff_drna, roll=diff_roll,
+            pairs=diff_pairs, pairpaths=diff_pairpaths)
 TWIN_OF = dict(background="hits", events="paths")
 
 # ---- the interleaved sequence (tests/test_gpu_random.py::test_interleaved_calls_share_the_context_buffers) --------
@@ -2424,6 +2788,20 @@ INTERLEAVE3 = [("drna", 1), ("segment", 3), ("roll", 0), ("levels", 13), ("drna"
                ("detect", 4), ("drna", 14), ("segment", 0), ("roll", 10), ("drna", 39), ("levels", 22), ("roll", 2),
                ("hits", 324), ("drna", 0), ("roll", 16), ("detect", 27), ("drna", 54), ("roll", 0), ("segment", 3),
                ("drna", 1), ("roll", 1), ("drna", 15)]
+
+
+# the fourth sequence: pair lists and their warping paths between calls of the families whose buffers and counters they
+# share -- sk_pairpath.hip lays an 8-word list header into c->pathlist where sk_path.hip lays 2, both count into
+# c->pathcnt and take slabs of c->pathscratch, and a pair call resets the retry and profile state the screening scheme's
+# counters are read through.  A large case of each kind before a small one (pairs 9: 202 pairs, 19.6 M cells, before
+# pairs 130: 19 pairs; pairpaths 145: 204 pairs, every one listed, before pairpaths 22: 5 pairs), cases that come twice,
+# the all-listed pairpaths 145 directly before and after paths 1, which puts every hit into its own scratch tier, and
+# pairpaths 13 -- four records changed, four mismatches counted -- directly before a paths call that must count none
+INTERLEAVE4 = [("pairs", 9), ("paths", 12), ("pairpaths", 145), ("paths", 1), ("pairpaths", 145), ("events", 50),
+               ("pairs", 130), ("hits", 1), ("pairpaths", 22), ("screen", 268), ("pairs", 119), ("segment", 3),
+               ("pairpaths", 13), ("paths", 187), ("pairpaths", 1), ("screen", 337), ("pairs", 9), ("events", 12),
+               ("pairpaths", 17), ("hits", 324), ("pairs", 130), ("screen", 268), ("pairpaths", 22), ("segment", 0),
+               ("pairs", 5), ("paths", 1), ("pairpaths", 36)]
 
 
 def interleave_case(family, seed):

@@ -3,8 +3,9 @@ MotifSeq hit lists (sk_hits.hip + k_sdtw's row output), alignment paths (sk_path
 the region + motif panel (sk_panel.hip), event detection (sk_detect.hip), the signal HMM and its state paths
 (sk_hmm.hip), segment levels (sk_seglev.hip), the read background (sk_bg.hip) and events (sk_events.hip) twins of the
 hit family, the switches of the screening scheme (sk_sdtwq.hip), and both branches of the dRNA segmenter (sk_drna_walk.hip,
-k_drna_stats / k_roll_* of sk_prep.hip; host and device entry points) -- through the public api call, against its reference,
-exactly; and three interleaved sequences of calls over the shared grow-only context buffers.
+k_drna_stats / k_roll_* of sk_prep.hip; host and device entry points), DTW over a pair list (sk_pairs.hip, k_sdtw's
+MODE_PAIRS / MODE_PAIRS_GLOBAL) and its warping paths (sk_pairpath.hip; host and device entry points) -- through the public
+api call, against its reference, exactly; and four interleaved sequences of calls over the shared grow-only context buffers.
 tests/test_random_cases.py (CPU) asserts what the seeds
 reach; tests/RANDOM_CASES.md lists the one-line kernel mutants these tests catch.  A failure names family, seed, the
 drawn parameters and switches, and the first differing (read, hit / set / line): `randcases.case_of(family, seed)`
@@ -44,6 +45,9 @@ def run_case(monkeypatch, ora, case):
         assert launches.value >= 1 and guard["alarm"] == 0 and guard["exact_fallback"] == 0, (rc.describe(case), guard)
     if fam == "paths":
         assert api.last_path_mismatches() == 0, rc.describe(case)
+    if fam in ("pairs", "pairpaths"):                        # no screening scheme: the counters read zeros, whatever ran before
+        guard = api.last_dtw_guard()
+        assert not any(guard.values()), (rc.describe(case), guard)
     return got, exp
 
 
@@ -242,6 +246,11 @@ class DevBuffers:
     def out(self, nbytes):
         return self.up(np.full(nbytes + self.GUARD, 0x5A, dtype=np.uint8))
 
+    def inout(self, a):
+        """an input the call may also write: its bytes, then the guard area"""
+        guard = np.full(self.GUARD, 0x5A, dtype=np.uint8)
+        return self.up(np.concatenate([np.frombuffer(a.tobytes(), dtype=np.uint8), guard]))
+
     def down(self, d, shape, dtype):
         from squigglekit_amd import _lib
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
@@ -328,6 +337,125 @@ def test_roll_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed)
         dev.free()
 
 
+def other_layout(case):
+    """the switches that put a pairs case on the other lane layout: without SK_DTW_NO_SMALL where it is set, with it
+    where it is not -- and a call above the host threshold, which takes 16 lanes by itself, under a threshold above it"""
+    if "SK_DTW_NO_SMALL" in case["env"]:
+        return {k: v for k, v in case["env"].items() if k != "SK_DTW_NO_SMALL"}
+    if case["npairs"] > rc.PAIRS_SMALL_MAX:
+        return dict(case["env"], SK_DTW_SMALL_MAX=str(1 << 20))
+    return dict(case["env"], SK_DTW_NO_SMALL="1")
+
+
+@pytest.mark.parametrize("seed", rc.SEEDS["pairs"])
+def test_pairs_seed_matches_the_reference(gpu, ora, monkeypatch, seed):
+    """api.dtw_pairs on a drawn pool and pair list (either mode, a list of arrays or (values, off) with off[0] > 0; above
+    the host threshold of 2 048 pairs without a switch, below it with and without SK_DTW_NO_SMALL): every record of every
+    pair the reference's, the guard counters zero; then on the other lane layout: a different plan, the same bytes."""
+    case = rc.case_of("pairs", seed)
+    got, exp = run_case(monkeypatch, ora, case)
+    assert got.dtype == gpu.HIT_DTYPE and len(got) == case["npairs"], rc.describe(case)
+    other = dict(case, env=other_layout(case))
+    assert rc.pairs_plan(other)["shape"] != rc.pairs_plan(case)["shape"] or \
+        all(len(case["seqs"][q]) < 32 or len(case["seqs"][q]) > 256 for q in case["pairs"][:, 0]), rc.describe(case)
+    again, _ = run_case(monkeypatch, ora, other)
+    assert rc.result_bytes(again) == rc.result_bytes(got), "%s under %s" % (rc.describe(case), other["env"])
+
+
+def run_again(monkeypatch, case, exp):
+    """the case under its switches through the GPU against an expectation that exists already"""
+    from squigglekit_amd import api
+    for key in rc.SWITCHES:
+        if key in case["env"]:
+            monkeypatch.setenv(key, case["env"][key])
+        else:
+            monkeypatch.delenv(key, raising=False)
+    got = rc.CALL[case["family"]](api, case, exp)
+    msg = rc.DIFF[case["family"]](case, got, exp)
+    assert msg is None, "%s\n  first difference: %s" % (rc.describe(case), msg)
+    return got
+
+
+@pytest.mark.parametrize("seed", rc.SEEDS["pairpaths"])
+def test_pairpaths_seed_matches_the_reference(gpu, ora, monkeypatch, seed):
+    """api.dtw_pairs_paths on a drawn list: records, span_off and spans of every pair the references', the self-check's
+    count the case's (the changed records, no other), listed pairs, slab and wavefronts as randcases.pairpaths_plan
+    restates them (all in diff_pairpaths); then under the two other tier settings: the same records and spans."""
+    case = rc.case_of("pairpaths", seed)
+    (rec, off, spans, counted, tiers), exp = run_case(monkeypatch, ora, case)
+    assert counted == exp["mismatches"] and tiers[0] == len(rc.pairpaths_plan(case, exp["records"])["listed"])
+    for env in rc.PP_TIERS:
+        if env != case["env"]:
+            again = run_again(monkeypatch, dict(case, env=dict(env)), exp)
+            assert again[2].tobytes() == spans.tobytes() and again[0].tobytes() == rec.tobytes() and again[3] == counted, \
+                "%s under %s" % (rc.describe(case), env)
+
+
+def _padded_pool(case, pad=5):
+    """(values, off) of the case's pool with `pad` NaN in front: the pool need not start at off = 0"""
+    seqs = case["seqs"]
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in seqs])
+    return np.concatenate([np.full(pad, np.nan)] + [np.asarray(s, dtype=np.float64) for s in seqs]), off + pad
+
+
+# the natural L = 16 route (2 049 pairs) | long targets beside short ones, global | SK_DTW_NO_SMALL, six groups and more
+PAIRS_DEVICE_SEEDS = (23, 130, 133)
+# computed records, the tiers as they fall | changed records, global, one wavefront | merged tile records, every pair listed
+PAIRPATHS_DEVICE_SEEDS = (6, 13, 1)
+
+
+@pytest.mark.parametrize("seed", PAIRS_DEVICE_SEEDS)
+def test_pairs_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed):
+    """sk_dtw_pairs_dev on device buffers, the pool at a nonzero offset: the host form's bytes, which are the reference's
+    records, and nothing written behind `out`."""
+    from squigglekit_amd import _lib, api
+    L = _lib.ensure_init()
+    case = rc.case_of("pairs", seed)
+    exp = rc.expect_pairs(ora, case)
+    values, off = _padded_pool(case)
+    pr = api._as_pairs(case["pairs"])
+    host = run_again(monkeypatch, dict(case, form="list"), exp)
+    dev = DevBuffers(L)
+    try:
+        d_val, d_out = dev.up(values), dev.out(host.nbytes)
+        _lib.check(L.sk_dtw_pairs_dev(d_val, _lib.ptr(off), off.size - 1, _lib.ptr(pr), len(pr), api.PAIRS_MODES[case["mode"]],
+                                      d_out))
+        _lib.check(L.sk_sync())
+        assert dev.down(d_out, host.shape, host.dtype).tobytes() == host.tobytes(), rc.describe(case)
+    finally:
+        dev.free()
+
+
+@pytest.mark.parametrize("seed", PAIRPATHS_DEVICE_SEEDS)
+def test_pairpaths_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed):
+    """sk_dtw_pairs_paths_dev on device buffers, the pool at a nonzero offset, records computed or supplied as the case
+    has them: records and spans the host form's bytes (checked against the references), the same mismatch count, nothing
+    written behind `records` or `spans`."""
+    from squigglekit_amd import _lib, api
+    L = _lib.ensure_init()
+    case = rc.case_of("pairpaths", seed)
+    exp = rc.expect_pairpaths(ora, case)
+    rec, _, spans, counted, tiers = run_again(monkeypatch, case, exp)
+    values, off = _padded_pool(case)
+    pr = api._as_pairs(case["pairs"])
+    have = exp["supplied"] is not None
+    dev = DevBuffers(L)
+    try:
+        d_val = dev.up(values)
+        d_rec = dev.inout(exp["supplied"].astype(gpu.HIT_DTYPE)) if have else dev.out(rec.nbytes)
+        d_sp = dev.out(spans.nbytes)
+        _lib.check(L.sk_dtw_pairs_paths_dev(d_val, _lib.ptr(off), off.size - 1, _lib.ptr(pr), len(pr),
+                                            api.PAIRS_MODES[case["mode"]], d_rec, int(have), d_sp))
+        _lib.check(L.sk_sync())
+        assert L.sk_last_path_mismatches() == counted == exp["mismatches"], rc.describe(case)
+        assert api.last_pair_paths_tiers() == tiers, rc.describe(case)
+        assert dev.down(d_rec, rec.shape, rec.dtype).tobytes() == rec.tobytes(), rc.describe(case)
+        assert dev.down(d_sp, spans.shape, np.int32).tobytes() == spans.tobytes(), rc.describe(case)
+    finally:
+        dev.free()
+
+
 def run_sequence(monkeypatch, ora, seq):
     seen = {}
     for step, (fam, seed) in enumerate(seq):
@@ -364,3 +492,11 @@ def test_drna_calls_interleaved_with_the_segmenter_and_the_detector(gpu, ora, mo
     grow-only buffers for all of them (the rolling branch lays two masks and its redo list or its prefix sums in them, the
     slow5 branch transposed words of nreads rows), a large case of each family before a small one."""
     run_sequence(monkeypatch, ora, rc.INTERLEAVE3)
+
+
+def test_pair_calls_interleaved_with_the_path_and_screening_families(gpu, ora, monkeypatch):
+    """Pair lists and their warping paths between paths, events, hit-list, screening and segmenter calls: c->pathcnt,
+    c->pathlist (an 8-word header here, 2 words in sk_path.hip) and c->pathscratch are shared with the alignment paths,
+    and a pair call resets the retry and profile state the screening counters are read through.  Every call against its
+    reference (mismatch counts, tiers and guard counters included), a call that occurs twice the same bytes both times."""
+    run_sequence(monkeypatch, ora, rc.INTERLEAVE4)

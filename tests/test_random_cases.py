@@ -837,9 +837,11 @@ def test_same_seed_same_case():
         seed = rc.SEEDS[fam][0]
         a, b = rc.case_of(fam, seed), rc.case_of(fam, seed)
         assert rc.describe(a) == rc.describe(b)
-        for key in ("reads", "rows", "motifs"):
+        for key in ("reads", "rows", "motifs", "seqs"):
             if key in a:
                 assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a[key], b[key]))
+        if "pairs" in a:
+            assert a["pairs"].tobytes() == b["pairs"].tobytes() and rc.case_digest(a) == rc.case_digest(b)
 
 
 def test_interleaved_sequence_is_what_it_claims():
@@ -1239,3 +1241,278 @@ def test_third_interleaved_sequence_is_what_it_claims():
         assert any(b < a // 20 for a, b in zip(size, size[1:])), (fam, size)      # a small case in buffers left much larger
         assert any(b > 20 * a for a, b in zip(size, size[1:])), (fam, size)       # and one that grows them again
     assert all(a != b for (a, _), (b, _) in zip(seq, seq[1:]))                     # never the same family twice in a row
+
+
+# ---- DTW over a pair list and its warping paths ------------------------------------------------------------------------
+PAIRS_QUERY_LENGTHS = (1, 16, 17, 31, 32, 256, 257, 1023, 1024)
+PAIRS_TIE_CELLS = 400_000                        # pairs up to here get their last row looked at for a tie
+
+
+def pairs_features(ora, case, exp):
+    seqs, pairs, env = case["seqs"], [tuple(p) for p in case["pairs"].tolist()], case["env"]
+    plan = rc.pairs_plan(case)
+    groups = plan["groups"]
+    assert sum(g["count"] for g in groups.values()) == len(pairs) == case["npairs"]
+    assert sorted(p for g in groups.values() for p in g["order"]) == list(range(len(pairs)))
+    f = {"mode=" + case["mode"], "form=" + case["form"]}
+    if case["form"] == "flat":
+        values, off = rc.pairs_pool_of(case)
+        assert off[0] == case["pad"] > 0 and off[-1] == values.size and np.all(np.isnan(values[:off[0]]))
+    if len(pairs) > rc.PAIRS_SMALL_MAX and not env:
+        assert case["kind"] == "natural" and max(len(seqs[t]) for _, t in pairs) <= rc.PAIRS_NATURAL_TARGET
+        if any(L == 16 and R >= 3 for L, R in groups):
+            f.add("natural: an L=16 group with R>=3")
+        if all((16, R) in groups for R in range(1, 17)) and any(L == 64 for L, _ in groups):
+            f.add("natural: all 16 L=16 groups beside L=64")
+    if len(pairs) <= rc.PAIRS_SMALL_MAX:
+        f.add("<=2048 pairs, " + ("SK_DTW_NO_SMALL" if "SK_DTW_NO_SMALL" in env else "plain"))
+    if len(groups) >= 6:
+        f.add(">=6 groups")
+    for (L, R), g in groups.items():
+        if g["count"] == 1:
+            f.add("a group of one pair")
+        if g["count"] % (64 // L):
+            f.add("a group that ends inside a wavefront")
+        for P in g["P"]:
+            assert 0 <= P < L
+            if P in (0, L - 1):
+                f.add("P=" + ("0" if P == 0 else "L-1"))
+        if L == 16:
+            for k in range(0, g["count"], 4):
+                M = g["M"][k:k + 4]
+                assert M == sorted(M, reverse=True)
+                if 0 in M and max(M) > 0:
+                    f.add("an empty target beside live mates at L=16")
+                if max(M) >= rc.PAIRS_CLIFF and any(m <= 3 for m in M):
+                    f.add(">=3000 points beside <=3 in a wavefront")
+    f |= {"N=%d" % len(seqs[q]) for q, _ in pairs if len(seqs[q]) in PAIRS_QUERY_LENGTHS}
+    uses = np.bincount([q for q, _ in pairs])
+    if uses.max() >= 3:
+        f.add("a query in >=3 pairs")
+    if any(q == t for q, t in pairs):
+        f.add("(i, i)")
+    if len(set(pairs)) < len(pairs):
+        f.add("a pair repeated verbatim")
+    for p, (q, t) in enumerate(pairs):
+        N, M = len(seqs[q]), len(seqs[t])
+        if M == 1:
+            f.add("M=1")
+        if 0 < M < N:
+            f.add("M<N " + case["mode"])
+        if M == N and q != t:
+            f.add("M=N " + case["mode"])
+        if case["ties"] and case["mode"] == "subsequence" and 0 < N * M <= PAIRS_TIE_CELLS and "tie" not in f:
+            last = ora.dtw_subsequence(seqs[q], seqs[t], want_cost=True)[3][-1]
+            if int((last == last.min()).sum()) >= 2:
+                assert exp["want"]["end"][p] == int(np.argmin(last))                # the first minimum is the record's
+                f.add("tie")
+    return f
+
+
+PAIRS_REQUIRED = ({"N=%d" % n for n in PAIRS_QUERY_LENGTHS} |
+                  {"mode=subsequence", "mode=global", "form=list", "form=flat", "natural: an L=16 group with R>=3",
+                   "natural: all 16 L=16 groups beside L=64", "<=2048 pairs, plain", "<=2048 pairs, SK_DTW_NO_SMALL",
+                   ">=6 groups", "a group of one pair", "a group that ends inside a wavefront", "P=0", "P=L-1",
+                   "a query in >=3 pairs", "(i, i)", "a pair repeated verbatim", "an empty target beside live mates at L=16",
+                   "M=1", "M<N subsequence", "M<N global", "M=N subsequence", "M=N global",
+                   ">=3000 points beside <=3 in a wavefront", "tie"})
+
+
+def test_pairs_cases_reach_every_boundary(ora, cases):
+    """Both modes and pool forms; the natural L = 16 route (more than 2 048 pairs, no switch) with every R of L = 16 beside
+    L = 64 groups in one call; both switch routes below it; six groups and more, a group of one pair, one that ends inside
+    a wavefront, P = 0 and P = L - 1; the query lengths at the layout's seams; repeats; empty, one-point, shorter and equal
+    targets; a long target beside short ones in a wavefront; a tie on the last row.  The plan is randcases.pairs_plan."""
+    assert len(cases["pairs"]) >= 4
+    have = set()
+    for case, exp in cases["pairs"]:
+        have |= pairs_features(ora, case, exp)
+        assert case["cells"] <= rc.PAIRS_CELLS and len(exp["want"]) == case["npairs"], rc.describe(case)
+    assert not sorted(PAIRS_REQUIRED - have)
+
+
+def pairpaths_features(case, exp):
+    seqs, pairs, mode, kind = case["seqs"], case["pairs"].tolist(), case["mode"], case["records"]
+    plan = rc.pairpaths_plan(case, exp["records"])
+    traced, listed = plan["traced"], plan["listed"]
+    f = {"mode=" + mode, "records=" + kind}
+    scratch = "SK_PATH_LDS_BYTES" in case["env"]
+    if case["tier"] == 0 and traced:
+        words = {p: N * ((W + 15) // 16) for p, N, W in traced}
+        width = {p: W for p, N, W in traced}
+        if not listed:
+            f.add("the LDS tier alone")
+        if any(words[p] > rc.PP_LDS_WORDS for p in listed) and len(listed) < len(traced):
+            f.add("listed by more than 6400 words")
+        if mode == "global" and any(words[p] <= rc.PP_LDS_WORDS and width[p] > rc.PP_LDS_COLS for p in listed):
+            f.add("listed by a global window above 1024 columns")
+    if case["tier"] == 1 and traced:
+        assert len(listed) == len(traced) and plan["waves"] == min(len(listed), rc.PP_MAX_WAVES)
+        if len(listed) >= 2:
+            f.add("every pair listed")
+    if case["tier"] == 2 and traced:
+        assert len(listed) == len(traced) and plan["waves"] == 1
+        d = np.sign(np.diff(plan["W"]))
+        if len(listed) >= 3 and (d > 0).any() and (d < 0).any():
+            f.add("one wavefront, windows up and down")
+    for p, N, W in traced:
+        M = len(seqs[pairs[p][1]])
+        if W % 16 in (0, 1, 15):
+            f.add("W%%16=%d" % (W % 16))
+        if N % 64 in (0, 1, 63):
+            f.add("N%%64=%d" % (N % 64))
+        if (N + 63) // 64 in (1, 2, 16):
+            f.add("stripes=%d" % ((N + 63) // 64))
+        if mode == "global" and M == 1:
+            f.add("global M=1")
+        if mode == "global" and N == 1:
+            f.add("global N=1")
+        if mode == "subsequence" and W == 1:
+            f.add("subsequence: a window of one column")
+    nan = np.isnan(exp["records"]["dist"])
+    if kind == "tiles":
+        assert mode == "subsequence" and not exp["mismatches"]
+        if any(len(seqs[t]) > case["piece"] for _, t in pairs):
+            f.add("tiles: a target of several pieces")
+            if scratch:
+                f.add("tiles: in the scratch tier")
+        # the merged records are whole-target records wherever the whole-target match fits the overlap
+        fits = ~nan & (exp["truth"]["end"] - exp["truth"]["start"] + 1 <= case["overlap"])
+        assert np.array_equal(exp["records"]["dist"][fits], exp["truth"]["dist"][fits])
+    if kind in ("own", "tiles") and nan.any() and not nan.all():
+        assert np.all(exp["records"]["flags"][nan] == 1)
+        f.add("empty-target records among good ones")
+        if kind == "own" and mode == "global":
+            f.add("empty-target records: global")
+        if kind == "own" and scratch:
+            f.add("empty-target records: scratch tier")
+    if kind == "wrong" and exp["wrong"]:
+        assert exp["mismatches"] == len(exp["wrong"]) <= case["nwrong"] and len(exp["wrong"]) < len(pairs)
+        for p in exp["wrong"]:
+            a, b = exp["records"][p], exp["truth"][p]
+            M = len(seqs[pairs[p][1]])
+            assert 0 <= a["start"] <= a["end"] < M and a["end"] == b["end"]        # inside the target
+            assert (a["dist"] != b["dist"]) != (a["start"] != b["start"])         # one change per record
+            f.add("wrong: dist by one ulp" if a["dist"] != b["dist"] else "wrong: start moved")
+        f.add("wrong: " + mode)
+        if scratch:
+            f.add("wrong: scratch tier")
+    return f
+
+
+PAIRPATHS_REQUIRED = ({"W%%16=%d" % k for k in (0, 1, 15)} | {"N%%64=%d" % k for k in (0, 1, 63)} |
+                      {"stripes=%d" % k for k in (1, 2, 16)} |
+                      {"mode=subsequence", "mode=global", "records=computed", "records=own", "records=tiles", "records=wrong",
+                       "the LDS tier alone", "listed by more than 6400 words", "listed by a global window above 1024 columns",
+                       "every pair listed", "one wavefront, windows up and down", "global M=1", "global N=1",
+                       "subsequence: a window of one column", "tiles: a target of several pieces",
+                       "tiles: in the scratch tier", "empty-target records among good ones", "empty-target records: global",
+                       "empty-target records: scratch tier", "wrong: dist by one ulp", "wrong: start moved",
+                       "wrong: subsequence", "wrong: global", "wrong: scratch tier"})
+
+
+def test_pairpaths_cases_reach_every_boundary(cases):
+    """Both modes; records computed, the reference's own, merged tile records against whole targets, records with a
+    handful changed; the LDS tier alone, pairs listed by their words and by a global window, every pair listed, one
+    wavefront for a list whose windows go up and down; the windows, query lengths and stripe counts at the seams; and
+    every reference passes pair_paths_ref.check_invariants."""
+    import pair_paths_ref
+    assert len(cases["pairpaths"]) >= 4
+    have = set()
+    for case, exp in cases["pairpaths"]:
+        have |= pairpaths_features(case, exp)
+        assert case["cells"] <= rc.PAIRS_CELLS and case["npairs"] <= rc.PP_MAX_WAVES, rc.describe(case)
+        off, rec = exp["off"], exp["records"]
+        for p in range(case["npairs"]):
+            sp = exp["spans"][off[p]:off[p + 1]]
+            if np.isnan(rec["dist"][p]) or p in exp["wrong"]:
+                assert np.all(sp == -1), (rc.describe(case), p)
+            else:
+                pair_paths_ref.check_invariants(sp, case["mode"], rec["start"][p], rec["end"][p])
+    assert not sorted(PAIRPATHS_REQUIRED - have)
+
+
+def test_pair_references_stay_inside_the_budget(ora):
+    """The reference of every committed case of either family, timed one by one: PAIRS_CELLS cells at the oracle's rate
+    (150 M cells a second and more on one core) stay under 2 s with room to spare for a slower machine."""
+    import time
+    for fam in ("pairs", "pairpaths"):
+        for seed in rc.SEEDS[fam]:
+            case = rc.case_of(fam, seed)
+            t0 = time.perf_counter()
+            rc.EXPECT[fam](ora, case)
+            assert time.perf_counter() - t0 < 2.0, rc.describe(case)
+
+
+# ---- the pair families stay what they are -------------------------------------------------------------------------------
+PINNED_PAIRS = {
+    "pairs": {
+        4: "f298d3fdd3ee0d2258e5127ad6d1f650b1a42ff7f6c572b96bca57a206c326f9",
+        5: "91fd9d154b4805ca71410a6647a8a04ce01325c2e5e95edbf240f122cc62d5c2",
+        7: "da10a6959f684f47935bbf0a457b3a756c05aedf15241dffcb7a1f737a92aa51",
+        9: "ff8168cb67718f396fd8bd7d1c83236d9da57b2c63709c75bcf6ad9ceda21b91",
+        23: "5615e1c6197dca89ec7d816c6aa70ecc8e0bd04798cbef7e5fb03c171837f4e6",
+        54: "1199f293ef58d73ddc9235aff7fdf85d6b9ce0224bf019b17b2ff2dda24cd79f",
+        119: "dbf5735ed43e3e4bd0b75bd55a82bd1600791e65be83a104a755f90a51fc9755",
+        130: "51588b5ab46d399dbf0db7d34256a3a9ce843ca4e8c71996be39b21978449177",
+        133: "5ed148d98d0a266a688d0e023b5530b3f5d475f92793c1e4e5592ef0fcc59ad9",
+    },
+    "pairpaths": {
+        1: "8674aff0641370c848b59f221bb06df931f09a0a94bdc0c53e2d6ae2a9c84cb4",
+        5: "10e36102ac944aaf036ffbb0df9fa22876b5c203e4cb78839293181a43838715",
+        6: "07142cf7b721cee4bb37bdb8a4d8b71ee50a0822594ba7c1c817d41cdaf702bb",
+        7: "91dfa94ff94aadb9ac03e16fd624f01acf8fc8bdc02feeccc789d2546889f4af",
+        13: "8f25c28f9330a3bbfae0587c69721ad5b6987c973467c2d89a9c12cfb6466b21",
+        17: "009ec2e709e48fe301985e101c77fa2ba4980e0486241b815b350133541889c2",
+        21: "0ebc367519d15d5c5a42ddd8f784bfbfe8f8c73c58c4c504b57b195ea3887b7b",
+        22: "e2ef8856d14c130390f64b9d1a8bbe20830158fad640b84caf6b9db435be6188",
+        23: "305c0cfd9dae4ac06eecf8f5aac22f51ce7c9c0702c5ff95c2f1bc16201c0b43",
+        36: "60e2bebb73995afc174f7557e8b25f74d02af045fe1658676a5184aef1b8059e",
+        50: "99cb656e2ff7f69ba8472c3e124b0415a29d4ff9b52e02c661291f04bc8b7a18",
+        145: "e85ebd97a5517f80374111bb7db6bc43e9ac9f177a9581b0b7285ab0eb391d5e",
+    },
+}
+
+
+def test_pair_families_keep_their_cases():
+    assert (rc.FAMILY_INDEX["pairs"], rc.FAMILY_INDEX["pairpaths"]) == (11, 12)
+    assert [rc.FAMILY_INDEX[f] for f in ("hits", "paths", "pull", "sweep", "panel", "detect", "hmm", "levels", "screen",
+                                         "drna", "roll")] == list(range(11))              # the older numbers stay
+    for fam, want in PINNED_PAIRS.items():
+        assert list(want) == rc.SEEDS[fam], fam
+        for seed, digest in want.items():
+            case = rc.case_of(fam, seed)
+            assert rc.case_digest(case) == digest, (fam, seed)
+            assert rc.describe(case).startswith("%s seed=%d kind=" % (fam, seed))
+            assert set(case["env"]) <= {"SK_DTW_NO_SMALL", "SK_PATH_LDS_BYTES", "SK_PATH_SCRATCH_BYTES"} <= set(rc.SWITCHES)
+
+
+def test_fourth_interleaved_sequence_is_what_it_claims():
+    """Pair lists and pair paths between paths, events, hits, screen and segment calls; of each pair family a large case
+    before a small one; calls that occur twice; an all-listed pair-path case directly before and after a paths case that
+    puts its hits into the scratch tier; a pair-path case that counts mismatches directly before a paths case."""
+    seq = rc.INTERLEAVE4
+    fams = {f for f, _ in seq}
+    assert fams == {"pairs", "pairpaths", "paths", "events", "hits", "screen", "segment"}
+    assert len(seq) >= 24 and len(seq) - len(set(seq)) >= 6
+    for fam, seed in seq:
+        assert fam not in rc.SEEDS or seed in rc.SEEDS[fam]
+        assert fam not in rc.TWIN_OF or seed in rc.SEEDS[rc.TWIN_OF[fam]]
+    assert all(a != b for (a, _), (b, _) in zip(seq, seq[1:]))                    # never the same family twice in a row
+    for fam in ("pairs", "pairpaths"):
+        assert sum(f == fam for f, _ in seq) - len({s for f, s in seq if f == fam}) >= 2       # two of its cases come twice
+        size = [rc.case_of(f, s)["cells"] for f, s in seq if f == fam]
+        assert any(b < a // 20 for a, b in zip(size, size[1:])), (fam, size)      # a small case in buffers left much larger
+        assert any(b > 20 * a for a, b in zip(size, size[1:])), (fam, size)       # and one that grows them again
+    between = others = False
+    for (fa, sa), (fb, sb), (fc, sc) in zip(seq, seq[1:], seq[2:]):
+        if (fa, fb, fc) == ("pairpaths", "paths", "pairpaths"):
+            a, b, c = rc.case_of(fa, sa), rc.case_of(fb, sb), rc.case_of(fc, sc)
+            between |= (a["env"].get("SK_PATH_LDS_BYTES") == b["env"].get("SK_PATH_LDS_BYTES") ==
+                        c["env"].get("SK_PATH_LDS_BYTES") == "0") and min(a["npairs"], c["npairs"]) >= 3
+    assert between
+    for (fa, sa), (fb, _) in zip(seq, seq[1:]):
+        others |= fa == "pairpaths" and rc.case_of(fa, sa)["records"] == "wrong" and fb == "paths"
+    assert others
+    scr = [i for i, (f, _) in enumerate(seq) if f == "screen"]                 # a pair call directly behind every screening call
+    assert len(scr) >= 3 and all(seq[i + 1][0] in ("pairs", "pairpaths") for i in scr)

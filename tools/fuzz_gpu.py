@@ -4,12 +4,11 @@ lengths, strides, outlier limits, segmenter parameters; the segment levels of ev
 segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the
 screening scheme of MotifSeq's first match under its switches, the segmenter sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
 signal HMM with its state paths, segment levels, both branches of the dRNA segmenter, and the background and events twins of
-the hit family -- each against the
+the hit family, DTW over a pair list and the warping paths of one -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
-length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py; and one DTW pair
-list (random pool, pair list with repeats and (i, i) pairs, empty targets, both modes and lane layouts) against the
-references of tests/pairs_ref.py; and the warping paths of one such list (any tier, computed or supplied records)
-against the references of tests/pair_paths_ref.py.
+length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py.  The DTW pair
+lists and their warping paths are two of the families of tests/randcases.py (`pairs`, `pairpaths`: the draws that used to
+live here, against tests/pairs_ref.py and tests/pair_paths_ref.py).
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -24,8 +23,6 @@ os.environ["SK_TUNING"] = "1"      # this tool flips tuning switches
 
 sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
-import pair_paths_ref                                 # noqa: E402
-import pairs_ref                                      # noqa: E402
 import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
@@ -83,84 +80,6 @@ def session_round(rng):
                                     desc, s, kk, stream_ref.fields(rec[kk, s]), want)
     finally:
         os.environ.pop("SK_DTW_NO_SMALL", None)
-    return None
-
-
-def pairs_round(rng):
-    """One drawn pair list: a pool of random lengths (queries of 1 .. 1 024 points around the lane and row boundaries,
-    targets of 0 .. 3 000), pairs drawn with repeats, (i, i) pairs and shared targets, either mode, either lane layout,
-    as a list of arrays or as (values, off) -- against pairs_ref.records.  Returns None, or what differed."""
-    nseq = int(rng.integers(1, 40))
-    seam = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 128, 129, 256, 257, 512, 1023, 1024]
-    lens = [int(rng.choice(seam)) if rng.random() < 0.4 else int(rng.integers(1, 400)) for _ in range(nseq)]
-    ties = rng.random() < 0.4
-    seqs = [pairs_ref.draw(rng, n, ties) for n in lens]
-    ntargets = int(rng.integers(0, 6))
-    seqs += [pairs_ref.draw(rng, int(rng.choice([0, 1, 2, 200, 1500, 3000])), ties) for _ in range(ntargets)]
-    npairs = int(rng.choice([1, 3, 4, 5, 16, 17, 64, 200]))
-    pairs = [(int(rng.integers(0, nseq)), int(rng.integers(0, len(seqs)))) for _ in range(npairs)]
-    pairs += [(q, q) for q in rng.integers(0, nseq, size=int(rng.integers(0, 3))).tolist()]
-    mode = ["subsequence", "global"][int(rng.integers(2))]
-    no_small = rng.random() < 0.5
-    flat = rng.random() < 0.5
-    desc = "nseq=%d lens=%s npairs=%d %s no_small=%s flat=%s ties=%s" % (len(seqs), [len(s) for s in seqs], len(pairs), mode,
-                                                                      no_small, flat, ties)
-    if no_small:
-        os.environ["SK_DTW_NO_SMALL"] = "1"
-    try:
-        got = api.dtw_pairs(api._as_pool(seqs) if flat else seqs, pairs, mode)
-    finally:
-        os.environ.pop("SK_DTW_NO_SMALL", None)
-    want = pairs_ref.records(ora, seqs, pairs, mode)
-    for p in range(len(pairs)):
-        if not pairs_ref.same_records(got[p:p + 1], want[p:p + 1].astype(got.dtype)):
-            return "%s: pair %d %s: got %s want %s" % (desc, p, pairs[p], got[p], want[p])
-    return None
-
-
-def pair_paths_round(rng):
-    """One drawn pair list as in pairs_round (queries around the stripe edges, targets of 0 .. 3 000 points, repeats,
-    (i, i) pairs), either mode, the tiers as they fall, every pair in the scratch tier or one wavefront for all of them,
-    records computed or supplied -- spans against pair_paths_ref.list_spans, records against pairs_ref.records, no
-    mismatch counted.  Returns None, or what differed."""
-    nseq = int(rng.integers(1, 30))
-    seam = [1, 2, 3, 15, 16, 17, 63, 64, 65, 127, 128, 129, 200, 256, 257, 1023, 1024]
-    lens = [int(rng.choice(seam)) if rng.random() < 0.4 else int(rng.integers(1, 400)) for _ in range(nseq)]
-    ties = rng.random() < 0.4
-    seqs = [pairs_ref.draw(rng, n, ties) for n in lens]
-    ntargets = int(rng.integers(0, 6))
-    seqs += [pairs_ref.draw(rng, int(rng.choice([0, 1, 2, 200, 513, 1025, 3000])), ties) for _ in range(ntargets)]
-    npairs = int(rng.choice([1, 3, 16, 65, 200]))
-    pairs = [(int(rng.integers(0, nseq)), int(rng.integers(0, len(seqs)))) for _ in range(npairs)]
-    pairs += [(q, q) for q in rng.integers(0, nseq, size=int(rng.integers(0, 3))).tolist()]
-    mode = ["subsequence", "global"][int(rng.integers(2))]
-    tier = int(rng.integers(3))
-    supplied = rng.random() < 0.5
-    desc = "nseq=%d lens=%s npairs=%d %s tier=%d supplied=%s ties=%s" % (len(seqs), [len(s) for s in seqs], len(pairs), mode,
-                                                                      tier, supplied, ties)
-    if tier >= 1:
-        os.environ["SK_PATH_LDS_BYTES"] = "0"
-    if tier == 2:
-        os.environ["SK_PATH_SCRATCH_BYTES"] = "1000"
-    try:
-        records = api.dtw_pairs(seqs, pairs, mode) if supplied else None
-        rec, off, spans = api.dtw_pairs_paths(seqs, pairs, mode, records=records)
-        counted = api.last_path_mismatches()
-    finally:
-        os.environ.pop("SK_PATH_LDS_BYTES", None)
-        os.environ.pop("SK_PATH_SCRATCH_BYTES", None)
-    if counted:
-        return "%s: %d pairs failed the self-check" % (desc, counted)
-    if not pairs_ref.same_records(rec, pairs_ref.records(ora, seqs, pairs, mode).astype(rec.dtype)):
-        return "%s: records differ" % desc
-    woff, want = pair_paths_ref.list_spans(ora, seqs, pairs, mode)
-    if not np.array_equal(off, woff):
-        return "%s: span_off %s want %s" % (desc, off.tolist(), woff.tolist())
-    for p in range(len(pairs)):
-        a, b = int(off[p]), int(off[p + 1])
-        if not np.array_equal(spans[a:b], want[a:b]):
-            return "%s: pair %d %s: spans differ from row %d" % (desc, p, pairs[p],
-                                                               int(np.flatnonzero((spans[a:b] != want[a:b]).any(axis=1))[0]))
     return None
 
 
@@ -411,9 +330,11 @@ def main():
         # (reference_paths), pull (numpy_pull_text), the panel (reference_panel), event detection (detect_ref), the signal
         # HMM with its state paths (hmm_ref, hmm_path_ref), segment levels (numpy on the oracle's segments); then a
         # hit-list draw through the background twin (numpy on the oracle's last row, test_background_host.py) and a paths
-        # draw through the events twin with pooling (test_events_host.py).  A mismatch line carries the round, so
+        # draw through the events twin with pooling (test_events_host.py); then a DTW pair list (pairs_ref.records) and the
+        # warping paths of one (pair_paths_ref.list_spans; mismatch count and tiers as the case's plan says).  A mismatch line carries the round, so
         # `fuzz_gpu.py <seconds> <seed>` up to that round rebuilds the case, and the drawn parameters and switches.
-        for fam in ("sweep", "hits", "paths", "pull", "panel", "detect", "hmm", "levels", "background", "events"):
+        for fam in ("sweep", "hits", "paths", "pull", "panel", "detect", "hmm", "levels", "background", "events", "pairs",
+                    "pairpaths"):
             if fam in randcases.TWIN_OF:
                 case = randcases.DRAW[randcases.TWIN_OF[fam]](rng)
                 case = randcases.twin_case(fam, case, use_seed=int(rng.integers(1 << 30)))
@@ -433,6 +354,8 @@ def main():
                 guard = api.last_dtw_guard()                 # the screening scheme's guard, as test_gpu_panel.same reads it
                 if any(guard[k] for k in ("premise_violations", "audit_mismatches", "alarm", "exact_fallback")):
                     msg = "the guard counters are not all zero: %s" % guard
+            if msg is None and fam in ("pairs", "pairpaths") and any(api.last_dtw_guard().values()):
+                msg = "the guard counters are not all zero after a pair call: %s" % api.last_dtw_guard()
             if msg is not None and fam == "detect":          # (the lines of the sections these draws replaced, as they were)
                 bad += 1
                 print("DETECT mismatch round %d: %d reads, max length %d, stride %d, params %s -- %s" %
@@ -455,16 +378,6 @@ def main():
         if msg is not None:
             bad += 1
             print("SESSION mismatch round %d %s" % (rounds, msg))
-        # ---- a DTW pair list against the references of tests/pairs_ref.py ----
-        msg = pairs_round(rng)
-        if msg is not None:
-            bad += 1
-            print("PAIRS mismatch round %d %s" % (rounds, msg))
-        # ---- ... and the warping paths of one against tests/pair_paths_ref.py ----
-        msg = pair_paths_round(rng)
-        if msg is not None:
-            bad += 1
-            print("PAIR PATHS mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
