@@ -636,6 +636,47 @@ int sk_dtw_pairs_paths_dev(const double *d_values, const int64_t *off, int32_t n
  * bytes of one scratch slab (sized from those pairs), the wavefronts that shared them.  Any pointer may be NULL. */
 int sk_last_pair_paths_tiers(int64_t *listed, int64_t *slab_bytes, int64_t *waves);
 
+/* Adaptive-band DTW over a pair list: records and warping paths of WHOLE reads in one pass.  The pool, the pair list and
+ * the order of the results are those of sk_dtw_pairs; the start is pinned to cell (0, 0), the end is pinned to
+ * (N-1, M-1) (SK_BAND_PINNED) or free along the last row (SK_BAND_FREE).  Instead of the N x M matrix one wavefront
+ * sweeps the pair's anti-diagonals inside a band of `band` = W cells (64, 128 or 256) that follows the path (the
+ * Suzuki-Kasahara scheme): (N + M - 1) * W cells per pair and W / 4 bytes of direction words per anti-diagonal.
+ *   Band b = 0 .. N + M - 2 has a lower-left corner (I_b, J_b), (I_0, J_0) = (W/2, -W/2); offset o = 0 .. W - 1 of band b
+ *   is the cell (I_b - o, J_b + o).  A cell outside the matrix holds +inf.  D(0, 0) = |x0 - y0|; elsewhere up = D(i-1, j)
+ *   and left = D(i, j-1) are read from band b - 1 and diag = D(i-1, j-1) from band b - 2 at the offsets of those cells,
+ *   +inf when the offset is outside [0, W).  m1 = left < diag ? left : diag; m = up < m1 ? up : m1; D = |x_i - y_j| + m;
+ *   the stored direction is up if up < m1, else left if left < diag, else diagonal (mlpy's back-trace order).
+ *   After band b, with ll = D_b[0] and ur = D_b[W-1]: ur < ll moves right (J + 1), ll < ur moves down (I + 1), anything
+ *   else (equal, both +inf, a NaN) moves right for even b and down for odd b.
+ *   SK_BAND_PINNED  dist = D(N-1, M-1) if the last band holds that cell, else +inf; end = M - 1.
+ *   SK_BAND_FREE    over the bands in ascending order, the first strictly smallest D of row N - 1; end = its column.
+ *   start = 0, n = M.  dist == +inf: the band lost the corner -- dist = +inf, start = end = -1, SK_FLAG_BAND_LOST.
+ * When N <= W/2 and M <= W/2 every cell is in its band: the record is that of SK_PAIRS_GLOBAL (free end: the first argmin
+ * of the full matrix's last row) bit for bit.  Otherwise dist is >= the full matrix's and may be larger.
+ * spans (NULL: records only): int32 [sum N][2] with the meaning and layout of sk_dtw_pairs_paths -- the stored directions
+ * followed from (N-1, end) to (0, 0); a_0 = 0, b_{N-1} = end.  Self-check per pair: the walk stays inside the band and
+ * ends on offset W/2 of band 0; a pair that fails, or lost the corner, gets spans -1 and is counted by
+ * sk_last_path_mismatches().  An empty target gives dist NaN, start = end = -1, SK_FLAG_EMPTY, spans -1, not counted.
+ * Refusals (checked before anything else, nothing written): band not 64 / 128 / 256, an unknown end mode, and those of
+ * sk_dtw_pairs with the same codes and messages, but for the lengths: 1 <= N <= 2^20 and M <= 2^20, SK_ERR_UNSUPPORTED
+ * above with the pair named.  Memory: one slab of ceil(steps * W / 1024) * 256 + ceil(steps / 64) * 8 + 8 bytes per
+ * wavefront, steps = N + M - 1 of the longest listed pair; the slabs of a call take at most 8 GiB (that bounds the
+ * wavefronts, otherwise as many as the device holds at a time); a slab above the budget is SK_ERR_NOMEM.  npairs == 0
+ * returns SK_OK. */
+enum { SK_BAND_PINNED = 0, SK_BAND_FREE = 1 };
+enum { SK_FLAG_BAND_LOST = 16 };   /* sk_hit.flags of sk_dtw_band: the band lost the end cell (dist = +inf) */
+int sk_dtw_band(const double *values, const int64_t *off, int32_t nseq,
+                const sk_pair *pairs, int64_t npairs, int32_t band, int32_t end_mode,
+                sk_hit *records, int32_t *spans /* NULL: records only */);
+/* device-resident form: d_values, d_records and d_spans on the device; off and pairs on the host.  One launch; nothing
+ * is synchronised after it. */
+int sk_dtw_band_dev(const double *d_values, const int64_t *off, int32_t nseq,
+                    const sk_pair *pairs, int64_t npairs, int32_t band, int32_t end_mode,
+                    sk_hit *d_records, int32_t *d_spans);
+/* The plan of the last such call (diagnostic): bytes of one slab (0 for a records-only call), the wavefronts of the
+ * launch, N + M - 1 of the longest listed pair.  Any pointer may be NULL. */
+int sk_last_band_plan(int64_t *slab_bytes, int64_t *waves, int64_t *steps_max);
+
 /* The same call in mlpy's own C arithmetic for inputs that hold inf / nan -- `min3` as "a; if (b < m) m = b; if (c < m)
  * m = c", fabs, np.argmin's first-NaN rule, the back-trace of subsequence_path, all evaluated literally by one GPU lane
  * over the full cost matrix.  medmad of a read whose MAD is 0 divides by zero (MotifSeq.py:196-199) and the reference

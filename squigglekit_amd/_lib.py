@@ -27,6 +27,8 @@ SK_SCALE = {"medmad": 0, "zscale": 1}
 SK_PULL_RAW, SK_PULL_PA = 0, 1
 SK_FLAG_EMPTY, SK_FLAG_DEGENERATE, SK_FLAG_RECENTRE = 1, 2, 4
 SK_PAIRS_SUBSEQUENCE, SK_PAIRS_GLOBAL = 0, 1
+SK_BAND_PINNED, SK_BAND_FREE = 0, 1
+SK_FLAG_BAND_LOST = 16                  # sk_dtw_band: the band lost the end cell (dist = +inf)
 SK_FLAG_CALIBRATING = 8                 # sk_stream_rec.flags: the slot still collects its calibration samples
 SK_STREAM_MAX_CALIB, SK_STREAM_MAX_SLOTS, SK_STREAM_MAX_POINTS = 65536, 65536, 1024
 
@@ -348,6 +350,10 @@ ABI = {
     "sk_dtw_pairs_paths": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp]),
     "sk_dtw_pairs_paths_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp]),
     "sk_last_pair_paths_tiers": (C.c_int, [_vp, _vp, _vp]),
+    # adaptive-band DTW over the same list: band, end_mode, records, spans [sum N][2] or NULL (records only)
+    "sk_dtw_band": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    "sk_dtw_band_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    "sk_last_band_plan": (C.c_int, [_vp, _vp, _vp]),
     "sk_dtw_subsequence_cref": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _dp, _i32p, _i32p]),
     "sk_normalise_i16": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i32p]),
     "sk_normalise_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i32p]),

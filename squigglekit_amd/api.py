@@ -1474,6 +1474,68 @@ def last_pair_paths_tiers():
     return a.value, b.value, c.value
 
 
+# ----------------------------------------------------------------------------
+# Adaptive-band DTW over a pair list: whole reads, records and paths in one pass ("Adaptive-band DTW over a pair list"
+# in include/squigglekit_hip.h and DESIGN.md 4.17)
+# ----------------------------------------------------------------------------
+BAND_ENDS = {"pinned": _lib.SK_BAND_PINNED, "free": _lib.SK_BAND_FREE}
+BAND_WIDTHS = (64, 128, 256)
+
+
+def dtw_band(seqs, pairs, band=128, end="pinned", paths=True):
+    """DTW of every (query, target) pair of a pool inside an adaptive band of `band` cells (64, 128 or 256) per
+    anti-diagonal: the start pinned to (0, 0), the end pinned to (N-1, M-1) or, end="free", free along the last row.
+    Returns (records HIT_DTYPE [npairs], span_off int64 [npairs + 1], spans int32 [sum N, 2]) with the layout of
+    dtw_pairs_paths, or the records alone when paths=False.  Sequences hold up to 2^20 points.  While N and M are at most
+    band / 2 the record is dtw_pairs(mode="global")'s bit for bit; beyond that dist is >= the full matrix's.  A pair whose
+    band lost the end cell has dist +inf, start = end = -1, SK_FLAG_BAND_LOST and spans -1 and is counted by
+    last_path_mismatches(); an empty target gives a NaN record flagged SK_FLAG_EMPTY.  Single device."""
+    if end not in BAND_ENDS:
+        raise ValueError("end %r: need one of %s" % (end, sorted(BAND_ENDS)))
+    if band not in BAND_WIDTHS:
+        raise ValueError("band %r: need one of %s" % (band, list(BAND_WIDTHS)))
+    L = _lib.ensure_init()
+    values, off = _as_pool(seqs)
+    pr = _as_pairs(pairs)
+    rec = np.zeros(len(pr), dtype=HIT_DTYPE)
+    keep = values if values.size else np.zeros(1)
+    keep_rec = rec if len(rec) else np.zeros(1, dtype=HIT_DTYPE)
+    if not paths:
+        check(L.sk_dtw_band(ptr(keep), ptr(off), off.size - 1, ptr(pr), len(pr), int(band), BAND_ENDS[end], ptr(keep_rec), None))
+        return rec
+    if len(pr) and (pr["query"].min() < 0 or pr["query"].max() >= off.size - 1):
+        span_off = np.zeros(len(pr) + 1, dtype=np.int64)           # (the library names the pair and refuses)
+    else:
+        span_off = pair_span_off(off, pr)
+    spans = np.full((int(span_off[-1]), 2), -1, dtype=np.int32)
+    keep_spans = spans if spans.size else np.zeros((1, 2), dtype=np.int32)
+    check(L.sk_dtw_band(ptr(keep), ptr(off), off.size - 1, ptr(pr), len(pr), int(band), BAND_ENDS[end], ptr(keep_rec),
+                        ptr(keep_spans)))
+    with _path_lock:
+        _path_mismatches[0] = max(L.sk_last_path_mismatches(), 0) if len(pr) else 0
+    return rec, span_off, spans
+
+
+def align_reads(queries, targets, band=128, end="pinned"):
+    """dtw_band of query i against target i: (records, span_off, spans)."""
+    qs = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
+    ts = [np.asarray(t, dtype=np.float64).reshape(-1) for t in targets]
+    if len(qs) != len(ts):
+        raise ValueError("align_reads: need one target per query")
+    idx = np.arange(len(qs), dtype=np.int64)
+    return dtw_band(qs + ts, np.stack([idx, len(qs) + idx], axis=1), band, end)
+
+
+def last_band_plan():
+    """(slab_bytes, waves, steps_max) of the last dtw_band / align_reads call of this thread's device: the bytes of one
+    wavefront's slab of direction words and move bits (0 for a records-only call), the wavefronts of the launch, N + M - 1
+    of the longest listed pair."""
+    L = _lib.ensure_init()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    check(L.sk_last_band_plan(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
 def map_paths(queries, targets, records, which=None):
     """The warping path of every query in ONE of its targets: (span_off int64 [Q + 1], spans int32 [sum, 2]).  records
     [T, Q] come from map_queries, or from merge_tiles with the whole targets passed here; which [Q] names the target per

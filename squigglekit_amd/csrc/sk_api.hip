@@ -1105,6 +1105,58 @@ int sk_last_pair_paths_tiers(int64_t *listed, int64_t *slab_bytes, int64_t *wave
     return SK_OK;
 }
 
+// ------------------------------------------------------------------ adaptive-band DTW over a pair list (sk_band.hip)
+// The argument checks run before the context is looked at: a refused call names its reason on any machine.
+int sk_dtw_band_dev(const double *d_values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
+                    int32_t band, int32_t end_mode, sk_hit *d_records, int32_t *d_spans)
+{
+    if (int rc = sk_band_check(off, nseq, pairs, npairs, band, end_mode, d_records)) return rc;
+    SK_ENTER(c);
+    return sk_band_run(c, d_values, off, 0, nseq, pairs, npairs, band, end_mode, d_records, d_spans);
+}
+
+int sk_dtw_band(const double *values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
+                int32_t band, int32_t end_mode, sk_hit *records, int32_t *spans)
+{
+    int rc;
+    if ((rc = sk_band_check(off, nseq, pairs, npairs, band, end_mode, records))) return rc;
+    if (npairs > 0) {
+        if (!values) return sk_fail(SK_ERR_INVALID, "NULL values");
+        for (int32_t s = 0; s < nseq; s++)
+            if (off[s + 1] < off[s]) return sk_fail(SK_ERR_INVALID, "offsets not increasing at sequence %d", s);
+    }
+    SK_ENTER(c);
+    if (npairs == 0) return SK_OK;
+    int64_t rows = 0;
+    for (int64_t p = 0; p < npairs; p++) rows += off[pairs[p].query + 1] - off[pairs[p].query];
+    const int64_t total = nseq ? off[nseq] - off[0] : 0;
+    const size_t vb = (((size_t)(total > 0 ? total : 1) * sizeof(double)) + 15) & ~(size_t)15;
+    const size_t sb = (size_t)rows * 2 * sizeof(int32_t);
+    if ((rc = sk_reserve(c, &c->pairsval, vb + (size_t)npairs * sizeof(sk_hit)))) return rc;
+    if (spans && (rc = sk_reserve(c, &c->pathspans, sb))) return rc;
+    double *d_values = (double *)c->pairsval.p;
+    sk_hit *d_rec = (sk_hit *)((char *)c->pairsval.p + vb);
+    int32_t *d_spans = spans ? (int32_t *)c->pathspans.p : nullptr;
+    if (total > 0)
+        SK_HIP(hipMemcpyAsync(d_values, values + off[0], (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_band_run(c, d_values, off, off[0], nseq, pairs, npairs, band, end_mode, d_rec, d_spans))) return rc;
+    SK_HIP(hipMemcpyAsync(records, d_rec, (size_t)npairs * sizeof(sk_hit), hipMemcpyDeviceToHost, c->stream));
+    if (spans) SK_HIP(hipMemcpyAsync(spans, d_spans, sb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// the plan of the last sk_dtw_band* call on this context: bytes of one slab (0: records only), wavefronts, the longest
+// listed pair's bands
+int sk_last_band_plan(int64_t *slab_bytes, int64_t *waves, int64_t *steps_max)
+{
+    SK_ENTER(c);
+    if (slab_bytes) *slab_bytes = c->band_slab_bytes;
+    if (waves) *waves = c->band_waves;
+    if (steps_max) *steps_max = c->band_steps;
+    return SK_OK;
+}
+
 int sk_dtw_subsequence(const double *x, int32_t nx, const double *y, int32_t ny,
                        double *dist, int32_t *start, int32_t *end, double *cost_last_row)
 {

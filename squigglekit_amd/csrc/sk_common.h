@@ -74,6 +74,15 @@ struct sk_pairpath_entry {
     int32_t N, M;         // the query's and the target's length
 };
 
+// ... and one pair of an adaptive-band call (sk_band.hip): the same places and lengths, and the caller's pair index (the
+// table is ordered longest N + M first; records go to out[pair]).  40 bytes.
+struct sk_band_entry {
+    int64_t qoff, toff;
+    int64_t span_off;
+    int32_t N, M;
+    int32_t pair, pad;
+};
+
 struct sk_ctx {
     int         device = -1;
     bool        ready = false;
@@ -143,6 +152,10 @@ struct sk_ctx {
     std::vector<sk_pairpath_entry> pairpath_table;   // (kept alive for the async H2D)
     int64_t pairpath_listed = 0, pairpath_slab_bytes = 0, pairpath_waves = 0;   // the last such call: pairs left to the
                                                                                  // scratch tier, bytes of a slab, wavefronts
+    sk_buf band;      // adaptive-band DTW: the table, one sk_band_entry per pair (sk_band.hip)
+    sk_buf bandslab;  // ... the wavefronts' slabs: direction words, then move bits
+    std::vector<sk_band_entry> band_table;    // (kept alive for the async H2D)
+    int64_t band_slab_bytes = 0, band_waves = 0, band_steps = 0;   // the last such call (sk_last_band_plan)
     sk_buf ckpt;      // DTW checkpoints (systolic state dumps: doubles or fixed-point units)
     sk_buf motifq;    // fixed-point motif layout
     sk_buf motif64;   // the motif laid out for 64 lanes (retry pass of a short motif)
@@ -355,6 +368,16 @@ int sk_launch_events_pool(sk_ctx *c, const sk_event *d_ev, const uint8_t *d_use,
 // fixed-point screening + certified window over all reads (sk_sdtwq.hip); leaves the retry list on the device
 int sk_launch_sdtw_screen(sk_ctx *c, const sk_sdtw_args *a, int ck, int span, int span2,
                           int32_t *d_retry_cnt, int32_t *d_retry, int32_t *d_early_cnt, int32_t *d_early);
+
+// ---- adaptive-band DTW over a pair list (sk_band.hip) ----
+// sk_band_check: the argument checks alone (host only, nothing launched; usable before a context exists).
+// sk_band_run: the checks, the plan and the one launch; d_values / d_rec / d_spans on the device (d_spans == nullptr:
+// records only), off / pairs on the host, sequence s = d_values[off[s] - off0 .. off[s + 1] - off0).  With spans it
+// resets the mismatch counter (sk_path_begin).
+int sk_band_check(const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs, int32_t band, int32_t end_mode,
+                  const void *out);
+int sk_band_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t off0, int32_t nseq, const sk_pair *pairs,
+                int64_t npairs, int32_t band, int32_t end_mode, sk_hit *d_rec, int32_t *d_spans);
 
 // ---- motif panel inside a search region (sk_panel.hip) ----
 // slice(begin, end).indices(len) of a Python slice with step 1: *lo = start, *hi = stop (stop < start: empty).

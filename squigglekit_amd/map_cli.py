@@ -1,7 +1,7 @@
 """squiggle_map: search the event levels of each read's first samples in reference squiggles, on the GPU.
 
     squiggle_map.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
-                    [--piece N --overlap N] [--align FILE]
+                    [--piece N --overlap N] [--align FILE] [--whole FILE [--band 64|128|256]]
 
 Per read: event detection on the first --prefix raw samples (api.detect_events), the level of every event
 (api.event_levels), (level - mean) / std in numpy, then subsequence DTW of those levels against every target in one call
@@ -22,8 +22,17 @@ its best target, under a header line:
 event: the 0-based index; sample_start / sample_length: the event record's start and length; level: its level; z: its
 z-scored value (the query point); ref_first / ref_last: the target points the event covers on the warping path of the
 match (api.map_paths), in the coordinates of the target searched, as start / end above.  With --piece the merged record
-is traced against the whole target.  stdout is the same with and without --align."""
+is traced against the whole target.  stdout is the same with and without --align.
+
+--whole FILE: the alignment of the WHOLE read, once the prefix has found its locus.  For every read that printed a match:
+event detection on all its samples, the levels z-scored as above, then adaptive-band DTW (api.align_reads, --band cells
+per anti-diagonal, default 128; start pinned, end free) against target[start : start + span] of the matched target and
+strand, span = min(len - start, ceil(N_all * (end - start + 1) / n_prefix * 1.5) + band) with N_all / n_prefix the events of
+the whole read / of its prefix.  FILE gets the --align header and one line per event, ref_first / ref_last in the
+coordinates of the target searched.  A read whose band lost the end, or with fewer than 2 events or levels without
+deviation, writes no lines and a note on stderr.  stdout and --align are the same with and without --whole."""
 import argparse
+import math
 import sys
 
 import numpy as np
@@ -56,6 +65,8 @@ def build_parser():
     p.add_argument("--piece", type=int, default=0, help="cut targets into pieces of this many points (0: whole targets)")
     p.add_argument("--overlap", type=int, default=0, help="points neighbouring pieces share (a match no longer than this is never cut)")
     p.add_argument("--align", help="write the event alignment table to this file: one line per event of every matched read")
+    p.add_argument("--whole", help="write the alignment table of the WHOLE read against the matched locus to this file (adaptive-band DTW)")
+    p.add_argument("--band", type=int, default=128, help="cells per anti-diagonal of the --whole alignment: 64, 128 or 256 (default 128)")
     p.add_argument("--device", type=int, default=None, help="GPU index (default $SK_DEVICE or 0)")
     p.add_argument("--batch", type=int, default=4096, help="reads per GPU call")
     return p
@@ -123,15 +134,23 @@ def align_lines(rid, target, events, levels, z, spans):
         int(spans[e, 0]), int(spans[e, 1])) for e in range(len(z))]
 
 
+def whole_span(length, start, end, n_prefix, n_all, band):
+    """target points the whole read is aligned against, from `start` on: the prefix's points per event, scaled to the
+    whole read's events, half as much again, plus the band; cut at the target's end"""
+    return min(length - start, int(math.ceil(n_all * (end - start + 1) / n_prefix * 1.5)) + band)
+
+
 class _Batcher:
-    def __init__(self, args, targets, tool_input, align=None):
-        self.args, self.targets, self.input, self.align = args, targets, tool_input, align
+    def __init__(self, args, targets, tool_input, align=None, whole=None):
+        self.args, self.targets, self.input, self.align, self.whole = args, targets, tool_input, align, whole
         self.params = api.det_params("rna" if args.rna else "dna")
-        self.ids, self.reads = [], []
+        self.ids, self.reads, self.full = [], [], []
 
     def add(self, rid, sig):
         self.ids.append(rid)
         self.reads.append(np.asarray(sig)[:self.args.prefix])
+        if self.whole is not None:
+            self.full.append(np.asarray(sig))
         if len(self.reads) >= max(1, self.args.batch):
             self.flush()
 
@@ -173,7 +192,42 @@ class _Batcher:
                 if best[q] >= 0:
                     self.align.write("".join(align_lines(self.ids[i], self.targets[int(best[q])], evs[i], lev[i], queries[i],
                                                          spans[int(span_off[q]):int(span_off[q + 1])])))
-        self.ids, self.reads = [], []
+        if self.whole is not None and qs:
+            self.write_whole(queries, records)
+        self.ids, self.reads, self.full = [], [], []
+
+    def write_whole(self, queries, records):
+        """the --whole table of the batch: queries / records as flush made them"""
+        best = api.best_targets(records)
+        rows = [i for i, z in enumerate(queries) if z is not None]
+        todo = [(q, i) for q, i in enumerate(rows) if best[q] >= 0]
+        if not todo:
+            return
+        off, rec = api.detect_events([self.full[i] for _, i in todo], self.params)
+        values, _ = api.event_levels(off, rec)
+        jobs = []                                                   # (read, target, record, events, levels, z, window)
+        for k, (q, i) in enumerate(todo):
+            lev, ev = values[int(off[k]):int(off[k + 1])], rec[int(off[k]):int(off[k + 1])]
+            z = zscore(lev)
+            if z is None:
+                sys.stderr.write("squiggle_map: whole read: {} in read {} of {}\n".format(
+                    "fewer than 2 events" if lev.size < 2 else "event levels without deviation", self.ids[i], self.input))
+                continue
+            t = int(best[q])
+            h = records[t, q]
+            y = self.targets[t][2]
+            start = int(h["start"])
+            span = whole_span(len(y), start, int(h["end"]), len(queries[i]), len(z), self.args.band)
+            jobs.append((i, t, start, ev, lev, z, y[start:start + span]))
+        if not jobs:
+            return
+        hits, span_off, spans = api.align_reads([j[5] for j in jobs], [j[6] for j in jobs], self.args.band, "free")
+        for k, (i, t, start, ev, lev, z, _) in enumerate(jobs):
+            sp = spans[int(span_off[k]):int(span_off[k + 1])]
+            if hits["flags"][k] or sp[0, 0] < 0:
+                sys.stderr.write("squiggle_map: whole read: the band lost the path in read {} of {}\n".format(self.ids[i], self.input))
+                continue
+            self.whole.write("".join(align_lines(self.ids[i], self.targets[t], ev, lev, z, sp + start)))
 
 
 def main(argv=None):
@@ -193,6 +247,10 @@ def main(argv=None):
         parser.error("need 0 <= --overlap < --piece")
     if args.overlap and not args.piece:
         parser.error("--overlap needs --piece")
+    if args.band not in api.BAND_WIDTHS:
+        parser.error("--band must be 64, 128 or 256")
+    if args.band != 128 and not args.whole:
+        parser.error("--band needs --whole")
     try:
         targets = load_targets(args.model, args.both)
     except (ValueError, IndexError, OSError) as e:
@@ -210,7 +268,15 @@ def main(argv=None):
             sys.stderr.write("squiggle_map: {}: {}\n".format(args.align, e))
             sys.exit(2)
         align.write("\t".join(ALIGN_HEADER) + "\n")
-    out = _Batcher(args, targets, src, align)
+    whole = None
+    if args.whole:
+        try:
+            whole = open(args.whole, "w")
+        except OSError as e:
+            sys.stderr.write("squiggle_map: {}: {}\n".format(args.whole, e))
+            sys.exit(2)
+        whole.write("\t".join(ALIGN_HEADER) + "\n")
+    out = _Batcher(args, targets, src, align, whole)
     sys.stdout.write("\t".join(HEADER) + "\n")
     try:
         if args.signal:
@@ -231,12 +297,14 @@ def main(argv=None):
     except (ValueError, EOFError, OSError) as e:
         sys.stdout.flush()
         sys.stderr.write("squiggle_map: {}: {}\n".format(src, e))
-        if align is not None:
-            align.close()
+        for fh in (align, whole):
+            if fh is not None:
+                fh.close()
         sys.exit(2)
     sys.stdout.flush()
-    if align is not None:
-        align.close()
+    for fh in (align, whole):
+        if fh is not None:
+            fh.close()
 
 
 if __name__ == "__main__":

@@ -6,7 +6,9 @@ screening scheme of MotifSeq's first match under its switches, the segmenter swe
 signal HMM with its state paths, segment levels, both branches of the dRNA segmenter, and the background and events twins of
 the hit family, DTW over a pair list and the warping paths of one -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
-length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py.  The DTW pair
+length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py; and one
+adaptive-band DTW list (random lengths up to 4 000, band width, end mode, wavefront count, with and without paths)
+against the statement of tests/band_ref.py.  The DTW pair
 lists and their warping paths are two of the families of tests/randcases.py (`pairs`, `pairpaths`: the draws that used to
 live here, against tests/pairs_ref.py and tests/pair_paths_ref.py).
 
@@ -25,6 +27,7 @@ sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
 import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
+import band_ref                                       # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -80,6 +83,50 @@ def session_round(rng):
                                     desc, s, kk, stream_ref.fields(rec[kk, s]), want)
     finally:
         os.environ.pop("SK_DTW_NO_SMALL", None)
+    return None
+
+
+def band_round(rng):
+    """One drawn adaptive-band list: records bit for bit, spans as integers and the mismatch count against
+    band_ref.records; the records-only call against the same records.  Returns None, or what differed."""
+    W = int(rng.choice(band_ref.WIDTHS))
+    end = band_ref.ENDS[int(rng.integers(2))]
+    waves = [None, "1", "3"][int(rng.integers(3))]
+    npairs = int(rng.integers(1, 25))
+    seqs, pairs = [], []
+    for _ in range(npairs):
+        kind = rng.random()
+        if kind < 0.3:
+            N, M = (int(rng.choice([1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257])) for _ in range(2))
+            x, y = band_ref.ties(rng, N), band_ref.ties(rng, M)
+        elif kind < 0.6:
+            x, y = band_ref.drift_pair(rng, int(rng.integers(8, 1500)), float(rng.uniform(0.3, 0.7)), float(rng.uniform(0.1, 0.6)),
+                                       int(rng.choice([0, 0, 40, 120])), int(rng.choice([0, 0, 150])))
+        else:
+            x, y = rng.normal(size=int(rng.integers(1, 4001))), rng.normal(size=int(rng.integers(0, 4001)))
+        pairs.append((len(seqs), len(seqs) + 1))
+        seqs += [x, y]
+    desc = "W=%d end=%s waves=%s shapes=%s" % (W, end, waves, [(len(seqs[q]), len(seqs[t])) for q, t in pairs])
+    wrec, woff, wspans, lost = band_ref.records(seqs, pairs, W, end)
+    if waves:
+        os.environ["SK_BAND_WAVES"] = waves
+    try:
+        rec, off, spans = api.dtw_band(seqs, pairs, W, end)
+        mism = api.last_path_mismatches()
+        only = api.dtw_band(seqs, pairs, W, end, paths=False)
+    finally:
+        os.environ.pop("SK_BAND_WAVES", None)
+    for p in range(npairs):
+        same = (rec["dist"][p] == wrec["dist"][p] or (np.isnan(rec["dist"][p]) and np.isnan(wrec["dist"][p]))) and \
+            all(rec[f][p] == wrec[f][p] for f in ("start", "end", "n", "flags"))
+        if not same:
+            return "%s: pair %d: got %s want %s" % (desc, p, rec[p], wrec[p])
+        if not np.array_equal(spans[off[p]:off[p + 1]], wspans[woff[p]:woff[p + 1]]):
+            return "%s: pair %d: the spans differ" % (desc, p)
+    if not np.array_equal(off, woff) or mism != lost:
+        return "%s: span_off differs, or %d mismatches counted where %d bands lost the end" % (desc, mism, lost)
+    if only.tobytes() != rec.tobytes():
+        return "%s: the records-only call gives other records" % desc
     return None
 
 
@@ -378,6 +425,11 @@ def main():
         if msg is not None:
             bad += 1
             print("SESSION mismatch round %d %s" % (rounds, msg))
+        # ---- an adaptive-band DTW list against its statement (tests/band_ref.py) ----
+        msg = band_round(rng)
+        if msg is not None:
+            bad += 1
+            print("BAND mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
