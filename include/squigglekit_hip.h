@@ -1088,6 +1088,60 @@ int sk_stream_flush(int32_t handle, const int32_t *slots, int32_t m, sk_stream_r
 int sk_stream_reset(int32_t handle, const int32_t *slots, int32_t m, const double *center, const double *scale);
 int sk_stream_close(int32_t handle);
 
+/* ---- Mapping sessions: the pair-list DTW continued as a read's points arrive ----------------------------------------
+ * sk_dtw_pairs searches finished queries of at most 1 024 points.  A mapping session keeps `nslots` queries in
+ * progress (a channel's event levels, say) and searches each of them in every one of `ntargets` targets as the points
+ * arrive: a push appends a chunk of points to each named slot and returns, per target, the record of everything the
+ * slot has been given since its reset.  Per (slot, target) the session keeps the LAST ROW of the DTW matrix, D (float64)
+ * and the back-trace start S (int32) per target column; a push sweeps only the new rows.
+ * Targets: copied to the device at open; target t = targets[target_off[t] .. target_off[t + 1]), at least one point
+ *     each (SK_ERR_INVALID for an empty one, naming it).
+ * Row state: nslots * (sum of the target lengths) * 12 bytes, updated in place.  SK_ERR_UNSUPPORTED, with the bytes in
+ *     the message, when that exceeds SK_MAP_MAX_STATE_BYTES.
+ * A push: chunk i = values[off[i] .. off[i + 1]) -- float64 points, normalised by the caller -- is appended to slot
+ *     slots[i], i < m.  A chunk of length 0 is a peek: it changes nothing and returns the slot's last records.  A slot
+ *     may appear once per push; a chunk holds at most SK_MAP_MAX_CHUNK points (longer ones are the caller's to cut);
+ *     slots not named are untouched.  A chunk of more than 1 024 points is swept in pieces of 1 024 rows.
+ * The record after a push: out[t * m + i].(dist, start, end, n, flags) is sk_dtw_subsequence(all points slot slots[i]
+ *     has been given since its reset, target t), bit for bit -- whatever the cuts, whichever slots shared the push and
+ *     whatever the total (no limit of 1 024 points: every cell is one correctly rounded add of correctly rounded operands
+ *     and the tie order of the start propagation is a per-cell rule, so rows continued from the stored row are the rows
+ *     of the one-shot sweep).  n is the target's length.  rows = the points given since the reset, pushes = the pushes
+ *     of length > 0 since the reset.  A slot without points: dist NaN, start = end = -1, rows = pushes = 0.
+ * Limits: SK_MAP_MAX_SESSIONS sessions per context, 1 .. SK_MAP_MAX_SLOTS slots, 1 .. SK_MAP_MAX_TARGETS targets,
+ *     nslots * ntargets <= 2^30.  sk_shutdown closes open sessions.
+ * Refusals (SK_ERR_INVALID unless said otherwise) name the entry, slot or target.  Those the arguments alone decide
+ *     come before any device work, in this order: a handle outside [0, SK_MAP_MAX_SESSIONS), m < 0, NULL pointers,
+ *     offsets that decrease, a chunk above SK_MAP_MAX_CHUNK (SK_ERR_UNSUPPORTED), (host form) a slot outside
+ *     [0, SK_MAP_MAX_SLOTS), a slot twice.  Then the session: a handle that is not open, a slot outside [0, nslots).
+ *     A refused push changes nothing. */
+#define SK_MAP_MAX_SESSIONS 8
+#define SK_MAP_MAX_SLOTS 65536
+#define SK_MAP_MAX_TARGETS 65536
+#define SK_MAP_MAX_CHUNK 65536
+#define SK_MAP_MAX_STATE_BYTES ((int64_t)1 << 35)      /* 32 GiB */
+typedef struct sk_map_rec {      /* 32 bytes */
+    double  dist;
+    int32_t start, end, n, flags;   /* sk_hit's fields: n = the target's length */
+    int32_t rows;                /* query points this slot has been given since its reset */
+    int32_t pushes;              /* pushes of length > 0 since its reset */
+} sk_map_rec;
+int sk_map_open(const double *targets, const int64_t *target_off, int32_t ntargets, int32_t nslots, int32_t *handle);
+/* values, off, slots and out are host pointers; the records are complete when the call returns. */
+int sk_map_push(int32_t handle, const int32_t *slots, int32_t m, const double *values, const int64_t *off,
+                sk_map_rec *out);      /* out [ntargets][m] */
+/* device-resident form: d_slots, d_values (chunk i at d_values[off[i] - off[0]]) and d_out are device pointers, off is a
+ * host pointer (the plan is made from the chunk lengths).  The slot numbers are read back (one small copy) and checked
+ * as in the host form; nothing is synchronised behind the launches. */
+int sk_map_push_dev(int32_t handle, const int32_t *d_slots, int32_t m, const double *d_values, const int64_t *off,
+                    sk_map_rec *d_out);
+/* The named slots start a new query: rows = pushes = 0, their row state is ignored from then on. */
+int sk_map_reset(int32_t handle, const int32_t *slots, int32_t m);
+int sk_map_close(int32_t handle);
+/* The last push of the calling thread's context: bytes of row state of its session, (piece, target) entries swept,
+ * sweep launches (one per piece index and (L, R) group).  Any pointer may be NULL. */
+int sk_last_map_plan(int64_t *state_bytes, int64_t *entries, int64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif

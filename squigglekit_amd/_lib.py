@@ -255,6 +255,12 @@ class StreamRec(C.Structure):
 STREAM_DTYPE = np.dtype([("dist", "<f8"), ("tail", "<f8"), ("start", "<i4"), ("end", "<i4"), ("n", "<i4"), ("seen", "<i4"),
                          ("flags", "<i4"), ("chunks", "<i4")])
 
+# sk_map_rec: one slot's record against one target after a push of a mapping session (sk_hit's fields, then the counters)
+MAPREC_DTYPE = np.dtype([("dist", "<f8"), ("start", "<i4"), ("end", "<i4"), ("n", "<i4"), ("flags", "<i4"), ("rows", "<i4"),
+                         ("pushes", "<i4")])
+SK_MAP_MAX_SESSIONS, SK_MAP_MAX_SLOTS, SK_MAP_MAX_TARGETS, SK_MAP_MAX_CHUNK = 8, 65536, 65536, 65536
+SK_MAP_MAX_STATE_BYTES = 1 << 35
+
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -424,6 +430,15 @@ ABI = {
     "sk_stream_flush": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
     "sk_stream_reset": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp]),
     "sk_stream_close": (C.c_int, [C.c_int32]),
+    # mapping sessions ("Mapping sessions" in include/squigglekit_hip.h; tests/mapstream_ref.py states the chained rows):
+    # open(targets, target_off, ntargets, nslots, handle); push(handle, slots, m, values, off, out [ntargets][m]) and its
+    # device-resident form (off stays a host pointer); reset(handle, slots, m); close(handle); the last push's plan
+    "sk_map_open": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _i32p]),
+    "sk_map_push": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "sk_map_push_dev": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "sk_map_reset": (C.c_int, [C.c_int32, _vp, C.c_int32]),
+    "sk_map_close": (C.c_int, [C.c_int32]),
+    "sk_last_map_plan": (C.c_int, [_vp, _vp, _vp]),
 }
 
 

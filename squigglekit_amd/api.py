@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HmmModel, LEVEL_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HmmModel, LEVEL_DTYPE, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -2466,3 +2466,140 @@ def stream_decide(rec, means, sds, accept_z, give_up_after):
     out[~accept & ~np.isnan(rec["dist"]) & (rec["n"] >= int(give_up_after))] = -1
     out[accept] = 1
     return out
+
+
+# ----------------------------------------------------------------------------
+# Mapping sessions: the pair-list DTW continued as a read's events arrive
+# ----------------------------------------------------------------------------
+class MapStream:
+    """A mapping session (sk_map_*): `nslots` queries in progress, each searched in every target of `targets` as its
+    points arrive.  A push appends a chunk of already-normalised float64 points to every named slot and returns
+    MAPREC_DTYPE [T, m]: (dist, start, end, n, flags) of record [t, i] are dtw_subsequence(all points slot slots[i] has
+    had since its reset, targets[t]) bit for bit, whatever the cuts and the total; rows / pushes count them.
+
+        with MapStream(targets, nslots=512) as ms:
+            rec = ms.push(slots, chunks)          # chunks: a list of float64 arrays, or a (values, off) tuple
+            rec = ms.peek(slots)                  # the last records again, nothing swept
+            ms.reset(slots)                       # the slots start a new read
+
+    Long targets: open the session on the pieces of tile_targets and hand map_hits(rec) to merge_tiles."""
+
+    def __init__(self, targets, nslots):
+        self._h = None
+        flat, toff = _as_pool(targets)
+        self.T = toff.size - 1
+        lens = np.diff(toff)
+        if self.T < 1 or self.T > _lib.SK_MAP_MAX_TARGETS:
+            raise ValueError("a mapping session takes 1 .. %d targets" % _lib.SK_MAP_MAX_TARGETS)
+        if np.any(lens == 0):
+            raise ValueError("target %d is empty" % int(np.flatnonzero(lens == 0)[0]))
+        if not 1 <= int(nslots) <= _lib.SK_MAP_MAX_SLOTS:
+            raise ValueError("nslots must be in 1 .. %d, got %d" % (_lib.SK_MAP_MAX_SLOTS, int(nslots)))
+        self.nslots = int(nslots)
+        self.state_bytes = self.nslots * int(toff[-1] - toff[0]) * 12
+        if self.state_bytes > _lib.SK_MAP_MAX_STATE_BYTES:
+            raise ValueError("row state of %d bytes above the cap of %d" % (self.state_bytes, _lib.SK_MAP_MAX_STATE_BYTES))
+        L = _lib.ensure_init()
+        h = C.c_int32(-1)
+        check(L.sk_map_open(ptr(flat), ptr(toff), self.T, self.nslots, C.byref(h)))
+        self._h = h.value
+
+    handle = property(lambda self: self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                            # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def _open(self):
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return _lib.load()
+
+    def push(self, slots, chunks):
+        """Append chunk i to slot slots[i]; a chunk of length 0 is a peek.  Records [T, m]."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        values, off = _as_pool(chunks)
+        if off.size - 1 != slots.size:
+            raise ValueError("one chunk per slot")
+        if off.size > 1 and int(np.diff(off).max()) > _lib.SK_MAP_MAX_CHUNK:
+            raise ValueError("a chunk holds at most %d points" % _lib.SK_MAP_MAX_CHUNK)
+        out = np.zeros((self.T, slots.size), dtype=MAPREC_DTYPE)
+        if slots.size:
+            keep = values if values.size else np.zeros(1)
+            check(L.sk_map_push(self._h, ptr(slots), slots.size, ptr(keep), ptr(off), ptr(out)))
+        return out
+
+    def peek(self, slots):
+        """The named slots' last records [T, m]; nothing is swept."""
+        slots = stream_slots(slots, self.nslots)
+        return self.push(slots, (np.zeros(0), np.zeros(slots.size + 1, dtype=np.int64)))
+
+    def reset(self, slots):
+        """The slots start a new read: rows = pushes = 0."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if slots.size:
+            check(L.sk_map_reset(self._h, ptr(slots), slots.size))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L = _lib.load()
+            if L.sk_map_close(h) not in (0, _lib.SK_ERR_NO_DEVICE):      # (after sk_shutdown the session is gone already)
+                check(-1)
+
+
+def map_hits(rec):
+    """The HIT_DTYPE fields of mapping-session records (a copy, same shape): what merge_tiles and best_targets take."""
+    rec = np.asarray(rec)
+    out = np.zeros(rec.shape, dtype=HIT_DTYPE)
+    for f in HIT_DTYPE.names:
+        out[f] = rec[f]
+    return out
+
+
+def last_map_plan():
+    """The last push of a mapping session: {"state_bytes", "entries", "launches"} (sk_last_map_plan)."""
+    L = _lib.ensure_init()
+    v = [C.c_int64(0) for _ in range(3)]
+    check(L.sk_last_map_plan(*[C.byref(x) for x in v]))
+    return {"state_bytes": v[0].value, "entries": v[1].value, "launches": v[2].value}
+
+
+def map_decide(rec, min_rows, max_dist_per_row, min_margin, give_up_rows):
+    """What a selective-sequencing client does with the records [T, m] of a mapping session's push.  Returns (best int64
+    [m], decision int8 [m]): best is best_targets' rule (the smallest dist, ties to the smallest target index, -1 where
+    every dist is NaN); decision 1 = accept, when rows >= min_rows, dist / rows <= max_dist_per_row and (second-best dist
+    - best dist) / rows >= min_margin (no margin test with one target); -1 = give up: not accepted and rows >=
+    give_up_rows; 0 = wait.  An entry without a distance waits.  Host only."""
+    rec = np.asarray(rec)
+    T, m = rec.shape
+    best = best_targets(rec)
+    dec = np.zeros(m, dtype=np.int8)
+    if T == 0 or m == 0:
+        return best, dec
+    has = best >= 0
+    d = np.where(np.isnan(rec["dist"]), np.inf, rec["dist"])
+    col = np.arange(m)
+    bt = np.where(has, best, 0)
+    dbest = d[bt, col]
+    rows = rec["rows"][bt, col].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        accept = has & (rows >= int(min_rows)) & (dbest / rows <= float(max_dist_per_row))
+        if T > 1:
+            rest = d.copy()
+            rest[bt, col] = np.inf
+            accept &= (rest.min(axis=0) - dbest) / rows >= float(min_margin)
+    dec[has & ~accept & (rows >= int(give_up_rows))] = -1
+    dec[accept] = 1
+    return best, dec

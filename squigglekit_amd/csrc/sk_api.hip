@@ -3050,3 +3050,133 @@ int sk_stream_close(int32_t handle)
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------ mapping sessions (sk_mapstream.hip)
+// What the arguments alone decide is refused here, before the device is looked at; what needs the session (is the
+// handle open, does a slot lie below its nslots) in sk_mapstream.hip.
+namespace {
+
+int check_map_handle(int32_t handle)
+{
+    if (handle < 0 || handle >= SK_MAP_MAX_SESSIONS)
+        return sk_fail(SK_ERR_INVALID, "mapping session handle %d is outside [0, %d)", handle, SK_MAP_MAX_SESSIONS);
+    return SK_OK;
+}
+
+// host_slots: the slot numbers can be read here (range against the ABI's limit, none twice)
+int check_map_push(int32_t handle, const int32_t *slots, int32_t m, const double *values, const int64_t *off, const void *out,
+                   bool host_slots)
+{
+    if (int rc = check_map_handle(handle)) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m == 0) return SK_OK;
+    if (!slots || !off || !out) return sk_fail(SK_ERR_INVALID, "NULL slots/off/out");
+    for (int32_t i = 0; i < m; i++) {
+        const int64_t len = off[i + 1] - off[i];
+        if (len < 0) return sk_fail(SK_ERR_INVALID, "entry %d: offsets not increasing", i);
+        if (len > SK_MAP_MAX_CHUNK)
+            return sk_fail(SK_ERR_UNSUPPORTED, "entry %d: chunk of %lld points (at most %d per push)", i, (long long)len,
+                           SK_MAP_MAX_CHUNK);
+    }
+    if (off[m] > off[0] && !values) return sk_fail(SK_ERR_INVALID, "NULL values");
+    if (!host_slots) return SK_OK;
+    std::vector<uint8_t> seen((size_t)SK_MAP_MAX_SLOTS, 0);
+    for (int32_t i = 0; i < m; i++) {
+        if (slots[i] < 0 || slots[i] >= SK_MAP_MAX_SLOTS)
+            return sk_fail(SK_ERR_INVALID, "entry %d: slot %d is outside [0, %d)", i, slots[i], SK_MAP_MAX_SLOTS);
+        if (seen[(size_t)slots[i]]) return sk_fail(SK_ERR_INVALID, "entry %d: slot %d appears twice in one call", i, slots[i]);
+        seen[(size_t)slots[i]] = 1;
+    }
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_map_open(const double *targets, const int64_t *target_off, int32_t ntargets, int32_t nslots, int32_t *handle)
+{
+    if (!targets || !target_off || !handle) return sk_fail(SK_ERR_INVALID, "NULL targets/target_off/handle");
+    if (ntargets < 1 || ntargets > SK_MAP_MAX_TARGETS)
+        return sk_fail(SK_ERR_INVALID, "ntargets = %d is outside 1 .. %d", ntargets, SK_MAP_MAX_TARGETS);
+    if (nslots < 1 || nslots > SK_MAP_MAX_SLOTS)
+        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_MAP_MAX_SLOTS);
+    for (int32_t t = 0; t < ntargets; t++) {
+        const int64_t M = target_off[t + 1] - target_off[t];
+        if (M == 0) return sk_fail(SK_ERR_INVALID, "target %d is empty", t);
+        if (M < 0 || M > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "target %d: bad length %lld", t, (long long)M);
+    }
+    if ((int64_t)nslots * ntargets > ((int64_t)1 << 30))
+        return sk_fail(SK_ERR_UNSUPPORTED, "nslots * ntargets = %lld above 1073741824", (long long)nslots * ntargets);
+    const int64_t sumM = target_off[ntargets] - target_off[0];
+    if (sumM > SK_MAP_MAX_STATE_BYTES / 12 / nslots)
+        return sk_fail(SK_ERR_UNSUPPORTED, "row state of %lld bytes (%d slots x %lld target points x 12) above the cap of %lld",
+                       (long long)nslots * (long long)sumM * 12, nslots, (long long)sumM, (long long)SK_MAP_MAX_STATE_BYTES);
+    SK_ENTER(c);
+    return sk_map_session_open(c, targets, target_off, ntargets, nslots, handle);
+}
+
+int sk_map_push_dev(int32_t handle, const int32_t *d_slots, int32_t m, const double *d_values, const int64_t *off,
+                    sk_map_rec *d_out)
+{
+    int rc = check_map_push(handle, d_slots, m, d_values, off, d_out, false);
+    if (rc) return rc;
+    SK_ENTER(c);
+    if ((rc = sk_map_session_info(c, handle, nullptr, nullptr))) return rc;
+    if (m == 0) return SK_OK;
+    std::vector<int32_t> slots((size_t)m);                  // the plan is made on the host: the slot numbers come back
+    SK_HIP(hipMemcpyAsync(slots.data(), d_slots, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return sk_map_session_push(c, handle, slots.data(), m, d_values, off, d_out);
+}
+
+int sk_map_push(int32_t handle, const int32_t *slots, int32_t m, const double *values, const int64_t *off, sk_map_rec *out)
+{
+    int rc = check_map_push(handle, slots, m, values, off, out, true);
+    if (rc) return rc;
+    SK_ENTER(c);
+    int32_t T = 0;
+    if ((rc = sk_map_session_info(c, handle, nullptr, &T))) return rc;
+    if (m == 0) return SK_OK;
+    if ((rc = sk_map_session_check_slots(c, handle, slots, m))) return rc;
+    const int64_t total = off[m] - off[0];
+    const size_t ob = (size_t)m * (size_t)T * sizeof(sk_map_rec);
+    void *d_values, *d_out;
+    if ((rc = sk_map_session_stage(c, handle, 0, (size_t)total * sizeof(double), &d_values))) return rc;
+    if ((rc = sk_map_session_stage(c, handle, 1, ob, &d_out))) return rc;
+    if (total > 0)
+        SK_HIP(hipMemcpyAsync(d_values, values + off[0], (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_map_session_push(c, handle, slots, m, (const double *)d_values, off, (sk_map_rec *)d_out))) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_map_reset(int32_t handle, const int32_t *slots, int32_t m)
+{
+    int rc = check_map_handle(handle);
+    if (rc) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m && !slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
+    SK_ENTER(c);
+    if ((rc = sk_map_session_info(c, handle, nullptr, nullptr))) return rc;
+    return sk_map_session_reset(c, handle, slots, m);
+}
+
+int sk_map_close(int32_t handle)
+{
+    if (int rc = check_map_handle(handle)) return rc;
+    SK_ENTER(c);
+    return sk_map_session_close(c, handle);
+}
+
+int sk_last_map_plan(int64_t *state_bytes, int64_t *entries, int64_t *launches)
+{
+    SK_ENTER(c);
+    if (state_bytes) *state_bytes = c->map_state_bytes;
+    if (entries) *entries = c->map_entries;
+    if (launches) *launches = c->map_launches;
+    return SK_OK;
+}
+
+} // extern "C"

@@ -66,6 +66,18 @@ struct sk_pair_query {
     int32_t N, L, R, pad;
 };
 
+// Mapping sessions (sk_mapstream.hip): what one lane group of a MODE_PAIRS_CHAIN launch reads -- a table type of its own,
+// so that sk_pair_entry and the code that reads it stay as they are.  48 bytes.
+struct sk_map_entry {
+    int64_t toff;     // first point of the target inside the session's target pool
+    int64_t xoff;     // first double of the chunk piece's [L][R] layout inside the push's layout block
+    int64_t soff;     // first column of this (slot, target)'s row state inside the session's D / S arrays
+    int32_t n;        // the target's length (>= 1)
+    int32_t P;        // the piece's short lanes (own R - 1 rows)
+    int32_t rec;      // the record goes to last[rec] (slot * ntargets + target)
+    int32_t cont;     // 0: fresh, the virtual row -1 enters (MODE_PAIRS); 1: continuing, the stored row enters (MODE_CHAIN)
+};
+
 // ... and one pair of a paths call over the list (sk_pairpath.hip): where its query and target lie in the pool, their
 // lengths, the first row of its spans.  32 bytes.
 struct sk_pairpath_entry {
@@ -199,6 +211,8 @@ struct sk_ctx {
     int    motif_L = 0;               // lanes per read of the layout in `motif`
     void  *comm = nullptr;            // ncclComm_t of this device (sk_comm.hip), or nullptr
     void  *sessions[SK_STREAM_MAX_SESSIONS] = {};   // MotifSeq sessions of this context (sk_stream.hip), by handle
+    void  *map_sessions[SK_MAP_MAX_SESSIONS] = {};  // mapping sessions of this context (sk_mapstream.hip), by handle
+    int64_t map_state_bytes = 0, map_entries = 0, map_launches = 0;   // the last push of one (sk_last_map_plan)
     sk_buf commbuf;                   // staging for the small host-side exchanges
 };
 
@@ -320,6 +334,13 @@ int sk_launch_sdtw_panel(sk_ctx *c, const sk_sdtw_args *a, int L, int R, const d
 // pair index -- and writes d_out[pair]
 int sk_launch_sdtw_pairs(sk_ctx *c, int L, int R, int global, const double *d_values, const double *d_xlay,
                          const sk_pair_entry *d_pt, int32_t count, sk_hit *d_out);
+// ... and over `count` (chunk piece, target) entries of one (L, R) group of a mapping session's push (k_sdtw,
+// MODE_PAIRS_CHAIN): lane group g reads d_mp[g], sweeps its piece over its target -- fresh or continuing from the row state
+// at stD / stS + soff -- stores the new last row there and writes d_last[rec]
+int sk_launch_sdtw_map(sk_ctx *c, int L, int R, const double *d_targets, const double *d_xlay, const sk_map_entry *d_mp,
+                       int32_t count, double *stD, int32_t *stS, sk_hit *d_last);
+// k_pairs_layout over nq distinct queries (sk_pairs.hip): d_qt[i]'s points from d_values into its per-lane layout in d_lay
+int sk_launch_pairs_layout(sk_ctx *c, const double *d_values, const sk_pair_query *d_qt, int nq, double *d_lay);
 // the plan and the launches of sk_dtw_pairs (sk_pairs.hip): d_values / d_out on the device, off / pairs on the host;
 // sequence s is d_values[off[s] - off0 .. off[s + 1] - off0).  sk_pairs_check: the argument checks alone (nothing launched)
 int sk_pairs_check(const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs, int32_t mode, const void *out);
@@ -570,6 +591,21 @@ int sk_stream_session_reset(sk_ctx *c, int32_t handle, const int32_t *d_slots, i
 int sk_stream_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
 int sk_stream_session_close(sk_ctx *c, int32_t handle);
 void sk_stream_close_all(sk_ctx *c);        // sk_shutdown: the context's device is current
+
+// ---- mapping sessions (sk_mapstream.hip) ----
+// The session behind sk_map_*: arguments that need no session are checked in sk_api.hip, the rest (handle, slots against
+// nslots) here.  open: targets / target_off on the host.  push: slots and off on the host, d_values (chunk i at
+// off[i] - off[0]) and d_out [ntargets][m] on the device; nothing is synchronised behind the launches.
+int sk_map_session_open(sk_ctx *c, const double *targets, const int64_t *target_off, int32_t ntargets, int32_t nslots,
+                        int32_t *handle);
+int sk_map_session_info(sk_ctx *c, int32_t handle, int32_t *nslots, int32_t *ntargets);      // SK_ERR_INVALID: unknown handle
+int sk_map_session_check_slots(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
+int sk_map_session_push(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const double *d_values,
+                        const int64_t *off, sk_map_rec *d_out);
+int sk_map_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
+int sk_map_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
+int sk_map_session_close(sk_ctx *c, int32_t handle);
+void sk_map_close_all(sk_ctx *c);           // sk_shutdown: the context's device is current
 
 // ---- SquigglePull text (sk_pull.hip) ----
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries

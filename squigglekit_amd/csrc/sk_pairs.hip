@@ -45,6 +45,14 @@ void k_pairs_layout(const double *__restrict__ values, const sk_pair_query *__re
 
 } // namespace
 
+int sk_launch_pairs_layout(sk_ctx *c, const double *d_values, const sk_pair_query *d_qt, int nq, double *d_lay)
+{
+    if (nq <= 0) return SK_OK;
+    hipLaunchKernelGGL(k_pairs_layout, dim3((unsigned)nq), dim3(256), 0, c->stream, d_values, d_qt, nq, d_lay);
+    SK_HIP(hipGetLastError());
+    return SK_OK;
+}
+
 int sk_pairs_check(const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs, int32_t mode, const void *out)
 {
     if (mode != SK_PAIRS_SUBSEQUENCE && mode != SK_PAIRS_GLOBAL) return sk_fail(SK_ERR_INVALID, "unknown pairs mode %d", mode);
@@ -129,8 +137,7 @@ int sk_pairs_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t 
     sk_pair_query *d_qt = (sk_pair_query *)(d_pt + npairs);
     SK_HIP(hipMemcpyAsync(d_pt, c->pairs_table.data(), (size_t)npairs * sizeof(sk_pair_entry), hipMemcpyHostToDevice, c->stream));
     SK_HIP(hipMemcpyAsync(d_qt, c->pairs_query.data(), nq * sizeof(sk_pair_query), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_pairs_layout, dim3((unsigned)nq), dim3(256), 0, c->stream, d_values, d_qt, (int)nq, d_lay);
-    SK_HIP(hipGetLastError());
+    if ((rc = sk_launch_pairs_layout(c, d_values, d_qt, (int)nq, d_lay))) return rc;
     SK_HIP(hipEventRecord(c->ev[0], c->stream));            // (no prep kernels: sk_last_kernel_ms reports 0 for them)
     SK_HIP(hipEventRecord(c->ev[1], c->stream));
     SK_HIP(hipEventRecord(c->ev[2], c->stream));

@@ -47,6 +47,15 @@
 //          the sense of SURVEY.md rows D1-D3: no mlpy build was at hand to compare against): the virtual row above
 //          lane 0 carries D = +inf at every column, only the corner (D = 0 at column -1) stays, so D[0][0] = |x0 - y0|
 //          and the first row and column accumulate; the result is D[N-1][n-1], start = 0, end = n - 1.  No S is carried.
+//   PAIRS_CHAIN  FULL over a table of (chunk piece, target) entries of a mapping session's push (sk_mapstream.hip), one per
+//          lane group as PAIRS.  Each entry is fresh (the virtual row -1 enters: PAIRS) or continuing (the last row of the
+//          rows swept before enters, per column from memory: CHAIN's `chained`, decided per lane group) and every entry
+//          stores its new last row, (D, S) per column 0 .. n-1, where the old one lay.  In place is safe: a column's old
+//          value is read by the prefetch a whole block of L steps before lane 0 needs it -- column idx at the start of
+//          block idx / L - 1 at the latest (columns < L before the loop) -- and lane L-1 stores column j at step
+//          j + L - 1, inside block j / L + 1 or the last step of block j / L: later in the program order of the SAME
+//          wavefront (a lane group never leaves its wavefront, and the groups that share one hold different
+//          (slot, target) states), so no column is written before it has been read.
 #include "sk_sdtw_dev.h"
 #include <math.h>
 #include <stdlib.h>
@@ -65,7 +74,8 @@ void k_sdtw(const sdtw_kargs a)
     constexpr int ROL = (L == 16) ? DPP_ROW_ROL1 : DPP_WAVE_ROL1;
     constexpr bool PAIRS = (MODE == MODE_PAIRS || MODE == MODE_PAIRS_GLOBAL);
     constexpr bool GLOBAL = (MODE == MODE_PAIRS_GLOBAL);
-    static_assert(!PAIRS || FEED == SK_FEED_F64_RAW, "pair lists take the pool as given");
+    constexpr bool MAPC = (MODE == MODE_PAIRS_CHAIN);
+    static_assert(!(PAIRS || MAPC) || FEED == SK_FEED_F64_RAW, "pair lists take the pool as given");
     constexpr bool TRACK = (MODE != MODE_DIST && !GLOBAL);
     constexpr int CKW = R + 3;                      // doubles per lane per checkpoint
     const double INF = __builtin_huge_val();
@@ -75,7 +85,7 @@ void k_sdtw(const sdtw_kargs a)
     const int g = lane / L, l = lane % L;
     int slot = wave * G + g;
     int nreads = a.nreads;
-    if constexpr (MODE != MODE_PANEL && !PAIRS) {   // (the panel's and the pair list's grids are neither gated nor driven by a list)
+    if constexpr (MODE != MODE_PANEL && !PAIRS && !MAPC) {   // (the panel's and the pair list's grids are neither gated nor driven by a list)
         if (a.gate_ptr) {                           // whole-call fallback: runs only when the guard raised an alarm
             if (*a.gate_ptr == 0) return;           // (launch-uniform)
             if (a.guard && blockIdx.x == 0 && threadIdx.x == 0) a.guard[SK_GUARD_FELLBACK] = 1;
@@ -90,12 +100,14 @@ void k_sdtw(const sdtw_kargs a)
     const bool live = slot < nreads;
     if (!live) slot = nreads - 1;
     int r;
-    if constexpr (MODE == MODE_PANEL || PAIRS) r = slot;   // all reads (table entries), in order: no list, no chunking
+    if constexpr (MODE == MODE_PANEL || PAIRS || MAPC) r = slot;   // all reads (table entries), in order: no list, no chunking
     else r = a.ridx ? a.ridx[a.list_off + slot] : a.read0 + slot;
     sk_panel_motif mt = {};                         // PANEL: this block's motif (block-uniform: scalar loads)
     if constexpr (MODE == MODE_PANEL) mt = a.mt[blockIdx.y];
     sk_pair_entry pe = {};                          // PAIRS: this lane group's pair (per lane: vector loads)
     if constexpr (PAIRS) pe = a.pt[r];
+    sk_map_entry me = {};                           // PAIRS_CHAIN: this lane group's (chunk piece, target) entry
+    if constexpr (MAPC) me = a.mp[r];
 
     // ---- per-read parameters -------------------------------------------------
     int n, flags = 0;
@@ -115,6 +127,9 @@ void k_sdtw(const sdtw_kargs a)
         n = pe.n;
         if (n == 0) flags = SK_FLAG_EMPTY;
         s64 = (const double *)a.samples + pe.toff;
+    } else if constexpr (MAPC) {
+        n = me.n;                                   // (a session's targets hold at least one point)
+        s64 = (const double *)a.samples + me.toff;
     } else {
         n = (int)(a.off[r + 1] - a.off[r]);
         if (n == 0) flags = SK_FLAG_EMPTY;
@@ -149,9 +164,10 @@ void k_sdtw(const sdtw_kargs a)
     for (int k = 0; k < R; k++) {
         if constexpr (MODE == MODE_PANEL) x[k] = a.xlay[mt.xoff + l * R + k];
         else if constexpr (PAIRS) x[k] = a.xlay[pe.xoff + l * R + k];
+        else if constexpr (MAPC) x[k] = a.xlay[me.xoff + l * R + k];
         else x[k] = a.xlay[l * R + k];
     }
-    const bool shortlane = l < (MODE == MODE_PANEL ? mt.P : PAIRS ? pe.P : a.P);
+    const bool shortlane = l < (MODE == MODE_PANEL ? mt.P : PAIRS ? pe.P : MAPC ? me.P : a.P);
 
     double D[R];
     int    S[R];
@@ -173,6 +189,17 @@ void k_sdtw(const sdtw_kargs a)
         if (chained) {
             pD = a.prevD + (int64_t)(r - a.read0) * a.row_stride;
             pS = a.prevS + (int64_t)(r - a.read0) * a.row_stride;
+            if (l == 0) { diagD = INF; diagS = -1; }
+            if (R == 1 && l == 0 && shortlane) { botD = INF; botS = -1; }
+            PFD = (l < n) ? pD[l] : INF;
+            PFS = (l < n) ? pS[l] : -1;
+        }
+    }
+    if constexpr (MAPC) {                           // the same entry, decided per lane group: the stored row of this
+        chained = me.cont != 0;                     // (slot, target) enters, or (fresh) nothing is read
+        if (chained) {
+            pD = a.rowD + me.soff;
+            pS = a.rowS + me.soff;
             if (l == 0) { diagD = INF; diagS = -1; }
             if (R == 1 && l == 0 && shortlane) { botD = INF; botS = -1; }
             PFD = (l < n) ? pD[l] : INF;
@@ -209,7 +236,7 @@ void k_sdtw(const sdtw_kargs a)
     for (int blk = 0; blk < nblk; blk++) {
         const double Fnext = fetch(tbase + (blk + 1) * L + l);   // in flight during the L steps below
         double PFDn = 0.0;  int PFSn = 0;
-        if constexpr (MODE == MODE_CHAIN) {
+        if constexpr (MODE == MODE_CHAIN || MAPC) {
             if (chained) {
                 const int idx = tbase + (blk + 1) * L + l;
                 PFDn = (idx < n) ? pD[idx] : INF;
@@ -234,7 +261,7 @@ void k_sdtw(const sdtw_kargs a)
             F = dpp_f64<ROL>(F, F);
             double topD = 0.0;  int topS = t + 1;           // lane 0: virtual row -1 (D = 0, S = column + 1)
             if constexpr (GLOBAL) topD = INF;               //   pinned start: no free entry along the target
-            if constexpr (MODE == MODE_CHAIN) {
+            if constexpr (MODE == MODE_CHAIN || MAPC) {
                 if (chained) { topD = PFD; topS = PFS; }    //   or the previous chunk's last row at column t
                 PFD = dpp_f64<ROL>(PFD, PFD);
                 PFS = dpp_i32<ROL>(PFS, PFS);
@@ -302,10 +329,16 @@ void k_sdtw(const sdtw_kargs a)
                         a.rowS[(int64_t)(r - a.read0) * a.row_stride + j] = S[R - 1];
                     }
                 }
+                if constexpr (MAPC) {                       // the new last row, where the old one lay (see the head)
+                    if (live && l == L - 1 && j >= 0 && j < n) {
+                        a.rowD[me.soff + j] = D[R - 1];
+                        a.rowS[me.soff + j] = S[R - 1];
+                    }
+                }
             }
         }
         F = Fnext;
-        if constexpr (MODE == MODE_CHAIN) { PFD = PFDn; PFS = PFSn; }
+        if constexpr (MODE == MODE_CHAIN || MAPC) { PFD = PFDn; PFS = PFSn; }
     }
 
     if (live && l == L - 1) {
@@ -322,6 +355,7 @@ void k_sdtw(const sdtw_kargs a)
             h.flags = flags;
             if constexpr (MODE == MODE_PANEL) a.out[(int64_t)mt.k * a.out_stride + r] = h;
             else if constexpr (PAIRS) a.out[pe.pair] = h;
+            else if constexpr (MAPC) a.out[me.rec] = h;
             else a.out[a.out_by_slot ? a.list_off + slot : r] = h;
         }
     }
@@ -603,6 +637,17 @@ int sk_launch_sdtw_pairs(sk_ctx *c, int L, int R, int global, const double *d_va
     sdtw_kargs k;
     memset(&k, 0, sizeof k);
     k.samples = d_values; k.nreads = count; k.xlay = d_xlay; k.pt = d_pt; k.out = d_out;
+    return launch(c, fn, k, L);
+}
+
+int sk_launch_sdtw_map(sk_ctx *c, int L, int R, const double *d_targets, const double *d_xlay, const sk_map_entry *d_mp,
+                       int32_t count, double *stD, int32_t *stS, sk_hit *d_last)
+{
+    sdtw_fn fn = L == 16 ? pick_r<16, SK_FEED_F64_RAW, MODE_PAIRS_CHAIN>(R) : pick_r<64, SK_FEED_F64_RAW, MODE_PAIRS_CHAIN>(R);
+    if (!fn || (L != 16 && L != 64)) return sk_fail(SK_ERR_UNSUPPORTED, "no mapping-session kernel for L=%d R=%d", L, R);
+    sdtw_kargs k;
+    memset(&k, 0, sizeof k);
+    k.samples = d_targets; k.nreads = count; k.xlay = d_xlay; k.mp = d_mp; k.rowD = stD; k.rowS = stS; k.out = d_last;
     return launch(c, fn, k, L);
 }
 

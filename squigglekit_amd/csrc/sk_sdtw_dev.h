@@ -17,7 +17,9 @@ enum { MODE_FULL = 0, MODE_DIST = 1, MODE_START = 2, MODE_CHAIN = 3,   // CHAIN:
        MODE_ROWS = 4,                                                     // ROWS: FULL that also stores the last row (hit lists)
        MODE_PANEL = 5,                                                    // PANEL: FULL over a table of motifs, one per blockIdx.y
        MODE_PAIRS = 6,                                                    // PAIRS: FULL over a table of (query, target) pairs, one per lane group
-       MODE_PAIRS_GLOBAL = 7 };                                           // PAIRS_GLOBAL: the same table, both ends pinned, D only
+       MODE_PAIRS_GLOBAL = 7,                                             // PAIRS_GLOBAL: the same table, both ends pinned, D only
+       MODE_PAIRS_CHAIN = 8 };                                            // PAIRS_CHAIN: a table of (chunk, target) entries, each fresh or
+                                                                          //   continuing from its stored last row (mapping sessions)
 
 // `case 1: return X(1); ... case 16: return X(16);` (and 17 .. 32) inside a switch on R: X(RR) names the kernel
 // instantiated for RR rows per lane.  The one dispatch on R of every DTW kernel family.
@@ -149,6 +151,9 @@ struct sdtw_kargs {
     // MODE_PAIRS / MODE_PAIRS_GLOBAL: one table entry per lane group (launch slot): the query's layout inside xlay, its short
     // lanes, the target's place inside samples and its length, where the record goes.  Last, so that no other field moves.
     const sk_pair_entry *pt;
+    // MODE_PAIRS_CHAIN: one sk_map_entry per lane group; the row state of every (slot, target) lies in rowD / rowS at the
+    // entry's soff and is read and rewritten in place (row_stride is not used)
+    const sk_map_entry *mp;
 };
 
 // The argument block of a launch over the prepared reads of `a`: zeroed but for the sample feed.

@@ -8,7 +8,9 @@ the hit family, DTW over a pair list and the warping paths of one -- each agains
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
 length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py; and one
 adaptive-band DTW list (random lengths up to 4 000, band width, end mode, wavefront count, with and without paths)
-against the statement of tests/band_ref.py.  The DTW pair
+against the statement of tests/band_ref.py; and one mapping session (tests/mapstream_ref.draw_session: random targets,
+slot count, subsets, cuts up to 2 100 points, resets and peeks, both lane layouts) against the oracle on every slot's
+concatenation after every push.  The DTW pair
 lists and their warping paths are two of the families of tests/randcases.py (`pairs`, `pairpaths`: the draws that used to
 live here, against tests/pairs_ref.py and tests/pair_paths_ref.py).
 
@@ -28,6 +30,7 @@ sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generato
 import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
 import band_ref                                       # noqa: E402
+import mapstream_ref                                  # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -128,6 +131,19 @@ def band_round(rng):
     if only.tobytes() != rec.tobytes():
         return "%s: the records-only call gives other records" % desc
     return None
+
+
+def mapstream_round(rng):
+    """One drawn mapping session against the oracle on the concatenation.  Returns None, or what differed."""
+    case = mapstream_ref.draw_session(rng)
+    no_small = rng.random() < 0.5
+    if no_small:
+        os.environ["SK_DTW_NO_SMALL"] = "1"
+    try:
+        msg = mapstream_ref.run_session(api, ora, case)
+    finally:
+        os.environ.pop("SK_DTW_NO_SMALL", None)
+    return None if msg is None else "no_small=%s %s: %s" % (no_small, mapstream_ref.describe_session(case), msg)
 
 
 def main():
@@ -430,6 +446,11 @@ def main():
         if msg is not None:
             bad += 1
             print("BAND mismatch round %d %s" % (rounds, msg))
+        # ---- a mapping session against the oracle on the concatenation (tests/mapstream_ref.py) ----
+        msg = mapstream_round(rng)
+        if msg is not None:
+            bad += 1
+            print("MAPSTREAM mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
