@@ -798,7 +798,9 @@ int sk_tunables(char *buf, int cap);
 
 /* ---- instrumentation -------------------------------------------------- */
 /* HIP-event durations (ms) of the kernels of the most recent *_dev / batch
- * call on this thread's device: prep (filter+stats), main (DTW or segment walk). */
+ * call on this thread's device: prep (filter+stats), main (DTW or segment walk).
+ * sk_detect_events_dev_i16 and sk_evs_push_dev_i16 are timed calls too: prep 0, main = all their launches (until the
+ * event sessions came, a detect call left the figures of the timed call before it). */
 int sk_last_kernel_ms(float *prep_ms, float *main_ms);
 /* Reads of the most recent DTW call whose optimal path was longer than the two-pass
  * look-back window and were therefore recomputed by the exact single pass (diagnostic). */
@@ -1141,6 +1143,62 @@ int sk_map_close(int32_t handle);
 /* The last push of the calling thread's context: bytes of row state of its session, (piece, target) entries swept,
  * sweep launches (one per piece index and (L, R) group).  Any pointer may be NULL. */
 int sk_last_map_plan(int64_t *state_bytes, int64_t *entries, int64_t *launches);
+
+/* ---- Event sessions: a read cut into events as its samples arrive ---------------------------------------------------
+ * sk_detect_events_* takes whole reads.  An event session keeps `nslots` reads in progress under one sk_det_params and
+ * cuts each of them as its samples arrive.  A slot holds n, the samples it has been given since its reset, the walk
+ * position i, both detectors' states and the last boundary: O(1) state, 416 bytes per slot (160 of state, the last 128
+ * samples), no sample of an event is kept however long the event.
+ * A push: the first len[k] samples of row k (rows + k * stride, int16) are appended to slot slots[k], k < m; then the
+ *     slot's positions i are walked while i + w_long <= n.  For those positions t_short[i] and t_long[i] are what they
+ *     will be in the finished read, whatever follows.  Every mark closes the event [last boundary, pos) and emits its
+ *     record at once, in read coordinates: the marks of both detectors together come in strictly rising order, so an
+ *     event is final the moment its end is marked.
+ * END: end[k] != 0 says the read ends with this chunk (which may be empty).  The remaining positions up to n - 1 are
+ *     walked under the one-shot rule (t_w[i] = 0 for i > n - w, samples at and beyond n count as 0 in the window sums)
+ *     and the closing event [last boundary, n) is emitted (none for n = 0).  An ended slot takes no samples until it is
+ *     reset; an empty chunk for it, END or not, does nothing.  end == NULL: no entry ends.
+ * The records: off gets m + 1 entries, always; entry k's new events are rec[off[k] .. off[k + 1]).  The concatenation of
+ *     everything a slot has emitted from its reset to END is sk_detect_events_i16's array of all its samples, byte for
+ *     byte, whatever the cuts (reads shorter than 2 w, of 1 or of 0 samples included); after any push it is a prefix of
+ *     that array (tests/evstream_ref.py states which).
+ * Overflow: when off[m] > cap the host form returns SK_ERR_OVERFLOW with off complete and rec untouched.  Nothing is
+ *     lost: the session keeps the last push's records on the device until its next push, and sk_evs_fetch delivers them.
+ * Limits: SK_EVS_MAX_SESSIONS sessions per context, 1 .. SK_EVS_MAX_SLOTS slots, a slot holds at most 2^31 - 1 samples,
+ *     m * (stride + 64) at most 2^31 in a push (SK_ERR_UNSUPPORTED).  sk_shutdown closes open sessions.
+ * Refusals (SK_ERR_INVALID unless said otherwise).  Those the arguments alone decide come before a context is looked
+ *     for: a handle outside [0, SK_EVS_MAX_SESSIONS), m < 0, NULL pointers (end may be NULL; rec may be NULL with
+ *     cap == 0), stride < 0, cap < 0, (host form) a negative len or one above stride, a slot outside
+ *     [0, SK_EVS_MAX_SLOTS), a slot twice; at open NULL p / handle, parameters outside sk_detect_events' ranges, nslots
+ *     outside 1 .. SK_EVS_MAX_SLOTS.  Then the session: a handle that is not open, a slot outside [0, nslots), samples
+ *     for an ended slot, a slot whose total would pass 2^31 - 1 samples (SK_ERR_UNSUPPORTED).  A refused push changes
+ *     nothing. */
+#define SK_EVS_MAX_SESSIONS 8
+#define SK_EVS_MAX_SLOTS 1048576
+int sk_evs_open(const sk_det_params *p, int32_t nslots, int32_t *handle);
+/* every pointer a host pointer; off and (when off[m] <= cap) rec are complete when the call returns. */
+int sk_evs_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride,
+                    const int32_t *len, const int32_t *end /* may be NULL */, int64_t *off /* [m + 1] */,
+                    sk_det_event *rec, int64_t cap);
+/* device-resident form: every pointer a device pointer, nothing is synchronised.  Distinct slots inside [0, nslots) are
+ * the caller's contract (an entry with a slot outside is ignored); len is clamped into [0, stride]; samples for an
+ * ended slot are ignored.  The check against cap happens on the device, as in sk_detect_events_dev_i16: the call returns
+ * SK_OK and the caller reads d_off[m] -- above cap, d_rec is untouched and sk_evs_fetch has the records. */
+int sk_evs_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                        const int32_t *d_len, const int32_t *d_end /* may be NULL */, int64_t *d_off /* [m + 1] */,
+                        sk_det_event *d_rec, int64_t cap);
+/* The records the session kept from its last push, compact and in that push's order, to rec (host).  SK_ERR_OVERFLOW
+ * when they are more than cap (nothing written); no push yet: nothing to copy, SK_OK. */
+int sk_evs_fetch(int32_t handle, sk_det_event *rec, int64_t cap);
+/* The named slots start a new read: n = 0, both detectors in their first state, not ended. */
+int sk_evs_reset(int32_t handle, const int32_t *slots, int32_t m);
+int sk_evs_close(int32_t handle);
+/* The last push of the calling thread's context: bytes of slot state of its session, staging rows it reserved
+ * (m * rows per entry).  guard_hits: the slots that the pushes of ALL event sessions of the context have stopped at a
+ * guard since the context was set up -- it only counts up, so one look after any number of pushes covers them all (a
+ * lane that would overrun its staging rows, meet a mark at or below its last boundary or pass 2^31 - 1 samples: always
+ * 0 unless the facts the staging rests on are wrong).  Reading it waits for the pushes.  Any pointer may be NULL. */
+int sk_last_evs_plan(int64_t *state_bytes, int64_t *staged_records, int64_t *guard_hits);
 
 #ifdef __cplusplus
 }

@@ -260,6 +260,7 @@ MAPREC_DTYPE = np.dtype([("dist", "<f8"), ("start", "<i4"), ("end", "<i4"), ("n"
                          ("pushes", "<i4")])
 SK_MAP_MAX_SESSIONS, SK_MAP_MAX_SLOTS, SK_MAP_MAX_TARGETS, SK_MAP_MAX_CHUNK = 8, 65536, 65536, 65536
 SK_MAP_MAX_STATE_BYTES = 1 << 35
+SK_EVS_MAX_SESSIONS, SK_EVS_MAX_SLOTS = 8, 1048576
 
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
@@ -439,6 +440,16 @@ ABI = {
     "sk_map_reset": (C.c_int, [C.c_int32, _vp, C.c_int32]),
     "sk_map_close": (C.c_int, [C.c_int32]),
     "sk_last_map_plan": (C.c_int, [_vp, _vp, _vp]),
+    # event sessions ("Event sessions" in include/squigglekit_hip.h; tests/evstream_ref.py states them on detect_ref):
+    # open(params, nslots, handle); push(handle, slots, m, rows, stride, len, end or NULL, off [m + 1], rec, cap) and its
+    # device-resident form; fetch(handle, rec, cap); reset(handle, slots, m); close(handle); the last push's plan
+    "sk_evs_open": (C.c_int, [C.POINTER(DetParams), C.c_int32, _i32p]),
+    "sk_evs_push_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64]),
+    "sk_evs_push_dev_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64]),
+    "sk_evs_fetch": (C.c_int, [C.c_int32, _vp, C.c_int64]),
+    "sk_evs_reset": (C.c_int, [C.c_int32, _vp, C.c_int32]),
+    "sk_evs_close": (C.c_int, [C.c_int32]),
+    "sk_last_evs_plan": (C.c_int, [_vp, _vp, _vp]),
 }
 
 

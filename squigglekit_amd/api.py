@@ -2603,3 +2603,119 @@ def map_decide(rec, min_rows, max_dist_per_row, min_margin, give_up_rows):
     dec[has & ~accept & (rows >= int(give_up_rows))] = -1
     dec[accept] = 1
     return best, dec
+
+
+# ----------------------------------------------------------------------------
+# Event sessions: a read cut into events as its samples arrive
+# ----------------------------------------------------------------------------
+class EventStream:
+    """An event session (sk_evs_*): `nslots` reads in progress under one sk_det_params, each cut into events as its
+    samples arrive.  A push appends a chunk of int16 raw samples to every named slot and returns (off int64 [m + 1],
+    rec DET_EVENT_DTYPE [off[m]]): entry i's NEW events are rec[off[i]:off[i + 1]], in read coordinates.  Everything a
+    slot returns from its reset to its END is detect_events' array of all its samples, byte for byte, whatever the cuts.
+
+        with EventStream(det_params("dna"), nslots=512) as es:
+            off, rec = es.push(slots, chunks)             # chunks: a list of int16 arrays, or (rows [m, stride], lens [m])
+            off, rec = es.push(slots, chunks, end=flags)  # flags[i] true: slot slots[i]'s read ends with this chunk
+            off, rec = es.finish(slots)                   # END with empty chunks
+            es.reset(slots)                               # the slots start a new read
+
+    The records come in detect_events' dtype: event_levels(off, rec) and event_stdv(rec) take them as they are."""
+
+    def __init__(self, params=None, nslots=1):
+        self._h = None
+        if not 1 <= int(nslots) <= _lib.SK_EVS_MAX_SLOTS:
+            raise ValueError("nslots must be in 1 .. %d, got %d" % (_lib.SK_EVS_MAX_SLOTS, int(nslots)))
+        self.nslots = int(nslots)
+        self.params = params or det_params()
+        L = _lib.ensure_init()
+        h = C.c_int32(-1)
+        check(L.sk_evs_open(C.byref(self.params), self.nslots, C.byref(h)))
+        self._h = h.value
+
+    handle = property(lambda self: self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                            # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def _open(self):
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return _lib.load()
+
+    def push(self, slots, chunks, end=None):
+        """Append chunk i to slot slots[i] (a chunk may be empty); end: None, or one flag per slot -- true says the read
+        ends with this chunk.  Returns (off [m + 1], rec): the new events of every entry."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if isinstance(chunks, tuple):
+            rows, lens = chunks
+            rows = np.ascontiguousarray(rows, dtype=np.int16)
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+            if rows.ndim != 2:
+                raise ValueError("rows must be [m, stride]")
+        else:
+            chunks = [np.asarray(c) for c in chunks]
+            if any(c.dtype != np.int16 for c in chunks):
+                raise ValueError("a session takes int16 chunks (raw samples)")
+            rows, lens = pack_i16(chunks) if chunks else (np.zeros((0, 0), dtype=np.int16), np.zeros(0, dtype=np.int32))
+        m = slots.size
+        if rows.shape[0] != m or lens.size != m:
+            raise ValueError("one chunk per slot")
+        flags = None
+        if end is not None:
+            flags = np.ascontiguousarray(np.broadcast_to(np.asarray(end), (m,)) != 0, dtype=np.int32)
+        off = np.zeros(m + 1, dtype=np.int64)
+        if m == 0:
+            return off, np.zeros(0, dtype=DET_EVENT_DTYPE)
+        keep = rows if rows.size else np.zeros((m, 1), dtype=np.int16)
+        stride = rows.shape[1]
+        cap = int(np.clip(lens, 0, stride).sum()) // 8 + 2 * m
+        rec = np.zeros(cap, dtype=DET_EVENT_DTYPE)
+        rc = L.sk_evs_push_i16(self._h, ptr(slots), m, ptr(keep), stride, ptr(lens), None if flags is None else ptr(flags),
+                               ptr(off), ptr(rec), cap)
+        if rc == _lib.SK_ERR_OVERFLOW and int(off[m]) > cap:          # the session kept them: fetch with room for all
+            rec = np.zeros(int(off[m]), dtype=DET_EVENT_DTYPE)
+            rc = L.sk_evs_fetch(self._h, ptr(rec), rec.size)
+        check(rc)
+        return off, rec[:int(off[m])]
+
+    def finish(self, slots):
+        """The named slots' reads end here (END with empty chunks): (off, rec) of their last events."""
+        slots = stream_slots(slots, self.nslots)
+        m = slots.size
+        return self.push(slots, (np.zeros((m, 0), dtype=np.int16), np.zeros(m, dtype=np.int32)), end=np.ones(m, dtype=np.int32))
+
+    def reset(self, slots):
+        """The slots start a new read."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if slots.size:
+            check(L.sk_evs_reset(self._h, ptr(slots), slots.size))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L = _lib.load()
+            if L.sk_evs_close(h) not in (0, _lib.SK_ERR_NO_DEVICE):      # (after sk_shutdown the session is gone already)
+                check(-1)
+
+
+def last_event_plan():
+    """{"state_bytes", "staged_records"} of the last push of an event session, and "guard_hits": the slots any push of
+    any event session of this thread's context has stopped at a guard so far -- it only counts up, so one look after a
+    run covers every push of it (sk_last_evs_plan)."""
+    L = _lib.ensure_init()
+    v = [C.c_int64(0) for _ in range(3)]
+    check(L.sk_last_evs_plan(*[C.byref(x) for x in v]))
+    return {"state_bytes": v[0].value, "staged_records": v[1].value, "guard_hits": v[2].value}

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 namespace {
@@ -2626,16 +2627,23 @@ int sk_region_rows_i16(const int16_t *sig, int64_t stride, const int32_t *len, i
 // call, then the records.
 namespace {
 
-int check_detect(const void *sig, int64_t stride, const int32_t *len, int32_t nreads, const sk_det_params *p,
-                 const int64_t *off, const sk_det_event *rec, int64_t cap)
+// the ranges of sk_det_params (sk_detect_events_*, sk_evs_open)
+int check_det_params(const sk_det_params *p)
 {
-    int rc = check_i16(sig, stride, len, nreads);
-    if (rc) return rc;
     if (!p) return sk_fail(SK_ERR_INVALID, "NULL sk_det_params");
     if (p->w_short < 1 || p->w_short > p->w_long || p->w_long > 64)
         return sk_fail(SK_ERR_INVALID, "windows must satisfy 1 <= w_short <= w_long <= 64 (got %d, %d)", p->w_short, p->w_long);
     if (!isfinite(p->th_short) || !isfinite(p->th_long)) return sk_fail(SK_ERR_INVALID, "the thresholds must be finite");
     if (!isfinite(p->peak_height) || p->peak_height < 0) return sk_fail(SK_ERR_INVALID, "peak_height must be finite and >= 0");
+    return SK_OK;
+}
+
+int check_detect(const void *sig, int64_t stride, const int32_t *len, int32_t nreads, const sk_det_params *p,
+                 const int64_t *off, const sk_det_event *rec, int64_t cap)
+{
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_det_params(p))) return rc;
     if (!off) return sk_fail(SK_ERR_INVALID, "NULL off");
     if (cap < 0) return sk_fail(SK_ERR_INVALID, "cap < 0");
     if (cap > 0 && !rec) return sk_fail(SK_ERR_INVALID, "NULL rec with a cap");
@@ -2660,9 +2668,15 @@ int sk_detect_events_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t
     }
     if ((rc = sk_reserve(c, &c->detect, sk_detect_work_bytes(nreads, stride)))) return rc;
     int64_t *d_bsum = (int64_t *)c->detect.p + (size_t)nreads * (size_t)sk_detect_words(stride);
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));            // sk_last_kernel_ms: no prep, main = mark + scan + fill
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
     if ((rc = sk_launch_detect_mark(c, d_sig, stride, d_len, nreads, p, c->detect.p, d_off))) return rc;
     if ((rc = sk_launch_detect_scan(c, nreads, d_bsum, d_off))) return rc;
-    return sk_launch_detect_fill(c, d_sig, stride, d_len, nreads, p, c->detect.p, d_off, d_rec, cap);
+    if ((rc = sk_launch_detect_fill(c, d_sig, stride, d_len, nreads, p, c->detect.p, d_off, d_rec, cap))) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    return SK_OK;
 }
 
 int sk_detect_events_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads,
@@ -3176,6 +3190,194 @@ int sk_last_map_plan(int64_t *state_bytes, int64_t *entries, int64_t *launches)
     if (state_bytes) *state_bytes = c->map_state_bytes;
     if (entries) *entries = c->map_entries;
     if (launches) *launches = c->map_launches;
+    return SK_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ event sessions (sk_evstream.hip)
+// What the arguments alone decide is refused here, before a context is looked for; what needs the session (is the handle
+// open, does a slot lie below its nslots, has it ended, how many samples has it had) in sk_evstream.hip.
+namespace {
+
+int check_evs_handle(int32_t handle)
+{
+    if (handle < 0 || handle >= SK_EVS_MAX_SESSIONS)
+        return sk_fail(SK_ERR_INVALID, "event session handle %d is outside [0, %d)", handle, SK_EVS_MAX_SESSIONS);
+    return SK_OK;
+}
+
+// host: slots, len can be read here (len in [0, stride], slots inside the ABI's limit, none twice)
+int check_evs_push(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride, const int32_t *len,
+                   const int64_t *off, const sk_det_event *rec, int64_t cap, bool host)
+{
+    if (int rc = check_evs_handle(handle)) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (!off) return sk_fail(SK_ERR_INVALID, "NULL off");
+    if (cap < 0) return sk_fail(SK_ERR_INVALID, "cap < 0");
+    if (cap > 0 && !rec) return sk_fail(SK_ERR_INVALID, "NULL rec with a cap");
+    if (stride < 0) return sk_fail(SK_ERR_INVALID, "stride < 0");
+    if (m == 0) return SK_OK;
+    if (!slots || !len) return sk_fail(SK_ERR_INVALID, "NULL slots/len");
+    if (stride > 0 && !rows) return sk_fail(SK_ERR_INVALID, "NULL rows");
+    if (stride > 0x7fffffffll) return sk_fail(SK_ERR_INVALID, "stride = %lld above 2147483647", (long long)stride);
+    if ((int64_t)m * (stride + 64) > ((int64_t)1 << 31))
+        return sk_fail(SK_ERR_UNSUPPORTED, "event session push: %d rows of %lld samples in one call", m, (long long)stride);
+    if (!host) return SK_OK;
+    for (int32_t i = 0; i < m; i++)
+        if (len[i] < 0 || len[i] > stride)
+            return sk_fail(SK_ERR_INVALID, "entry %d: len = %d is outside [0, stride = %lld]", i, len[i], (long long)stride);
+    for (int32_t i = 0; i < m; i++)
+        if (slots[i] < 0 || slots[i] >= SK_EVS_MAX_SLOTS)
+            return sk_fail(SK_ERR_INVALID, "entry %d: slot %d is outside [0, %d)", i, slots[i], SK_EVS_MAX_SLOTS);
+    // none twice: the entries ordered by slot (and by entry among equals), so that the later entry of a pair is named
+    std::vector<int32_t> order((size_t)m);
+    for (int32_t i = 0; i < m; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return slots[a] != slots[b] ? slots[a] < slots[b] : a < b; });
+    int32_t twice = -1;
+    for (int32_t k = 1; k < m; k++)
+        if (slots[order[(size_t)k]] == slots[order[(size_t)k - 1]] && (twice < 0 || order[(size_t)k] < twice)) twice = order[(size_t)k];
+    if (twice >= 0) return sk_fail(SK_ERR_INVALID, "entry %d: slot %d appears twice in one call", twice, slots[twice]);
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_evs_open(const sk_det_params *p, int32_t nslots, int32_t *handle)
+{
+    if (int rc = check_det_params(p)) return rc;
+    if (!handle) return sk_fail(SK_ERR_INVALID, "NULL handle");
+    if (nslots < 1 || nslots > SK_EVS_MAX_SLOTS)
+        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_EVS_MAX_SLOTS);
+    SK_ENTER(c);
+    return sk_evs_session_open(c, p, nslots, handle);
+}
+
+int sk_evs_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                        const int32_t *d_len, const int32_t *d_end, int64_t *d_off, sk_det_event *d_rec, int64_t cap)
+{
+    int rc = check_evs_push(handle, d_slots, m, d_rows, stride, d_len, d_off, d_rec, cap, false);
+    if (rc) return rc;
+    SK_ENTER(c);
+    if ((rc = sk_evs_session_info(c, handle, nullptr))) return rc;
+    const int64_t per = sk_evs_session_rows(c, handle, stride);
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));            // sk_last_kernel_ms: no prep, main = walk + scan + gather
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
+    if ((rc = sk_evs_session_push(c, handle, d_slots, m, d_rows, stride, d_len, d_end, per, d_off, nullptr, nullptr, nullptr)))
+        return rc;
+    if ((rc = sk_evs_session_gather(c, handle, d_rec, cap))) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    return SK_OK;
+}
+
+int sk_evs_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride, const int32_t *len,
+                    const int32_t *end, int64_t *off, sk_det_event *rec, int64_t cap)
+{
+    int rc = check_evs_push(handle, slots, m, rows, stride, len, off, rec, cap, true);
+    if (rc) return rc;
+    SK_ENTER(c);
+    if ((rc = sk_evs_session_info(c, handle, nullptr))) return rc;
+    if ((rc = sk_evs_session_check(c, handle, slots, m, len))) return rc;
+    SK_HIP(hipStreamSynchronize(c->stream));                // an earlier call may still read the staging buffers
+    int32_t maxlen = 0;
+    for (int32_t i = 0; i < m; i++) maxlen = len[i] > maxlen ? len[i] : maxlen;
+    // the rows go up as [m][w], w = maxlen rounded up to 8 samples: 16-byte loads whatever the caller's stride
+    const int64_t w = ((int64_t)maxlen + 7) / 8 * 8;
+    const size_t mm = (size_t)(m > 0 ? m : 1);
+    void *d_rows_v, *d_args_v;
+    if ((rc = sk_evs_session_stage(c, handle, 0, mm * (size_t)w * sizeof(int16_t), &d_rows_v))) return rc;
+    if ((rc = sk_evs_session_stage(c, handle, 1, 3 * mm * sizeof(int32_t), &d_args_v))) return rc;
+    int16_t *d_rows = (int16_t *)d_rows_v;
+    int32_t *d_slots = (int32_t *)d_args_v, *d_len = d_slots + mm, *d_end = d_len + mm;
+    if (m > 0) {
+        if (maxlen > 0)
+            SK_HIP(hipMemcpy2DAsync(d_rows, (size_t)w * sizeof(int16_t), rows, (size_t)stride * sizeof(int16_t),
+                                    (size_t)maxlen * sizeof(int16_t), (size_t)m, hipMemcpyHostToDevice, c->stream));
+        SK_HIP(hipMemcpyAsync(d_slots, slots, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        SK_HIP(hipMemcpyAsync(d_len, len, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (end) SK_HIP(hipMemcpyAsync(d_end, end, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    const int64_t per = sk_evs_session_rows(c, handle, maxlen);
+    const int64_t *k_off = nullptr;
+    int32_t km = 0;
+    if ((rc = sk_evs_session_push(c, handle, d_slots, m, d_rows, w, d_len, end ? d_end : nullptr, per, nullptr, slots, len, end)))
+        return rc;
+    if ((rc = sk_evs_session_last(c, handle, &k_off, &km))) return rc;
+    SK_HIP(hipMemcpyAsync(off, k_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    const int64_t total = off[m];
+    if (total > cap)
+        return sk_fail(SK_ERR_OVERFLOW, "the push made %lld events, cap is %lld (sk_evs_fetch has them)", (long long)total,
+                       (long long)cap);
+    if (total == 0) return SK_OK;
+    void *d_out;
+    if ((rc = sk_evs_session_stage(c, handle, 2, (size_t)total * sizeof(sk_det_event), &d_out))) return rc;
+    if ((rc = sk_evs_session_gather(c, handle, (sk_det_event *)d_out, total))) return rc;
+    SK_HIP(hipMemcpyAsync(rec, d_out, (size_t)total * sizeof(sk_det_event), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_evs_fetch(int32_t handle, sk_det_event *rec, int64_t cap)
+{
+    int rc = check_evs_handle(handle);
+    if (rc) return rc;
+    if (cap < 0) return sk_fail(SK_ERR_INVALID, "cap < 0");
+    if (cap > 0 && !rec) return sk_fail(SK_ERR_INVALID, "NULL rec with a cap");
+    SK_ENTER(c);
+    const int64_t *k_off = nullptr;
+    int32_t m = 0;
+    if ((rc = sk_evs_session_last(c, handle, &k_off, &m))) return rc;
+    if (m == 0) return SK_OK;
+    int64_t total = 0;
+    SK_HIP(hipMemcpyAsync(&total, k_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    if (total > cap)
+        return sk_fail(SK_ERR_OVERFLOW, "the last push made %lld events, cap is %lld", (long long)total, (long long)cap);
+    if (total == 0) return SK_OK;
+    void *d_out;
+    if ((rc = sk_evs_session_stage(c, handle, 2, (size_t)total * sizeof(sk_det_event), &d_out))) return rc;
+    if ((rc = sk_evs_session_gather(c, handle, (sk_det_event *)d_out, total))) return rc;
+    SK_HIP(hipMemcpyAsync(rec, d_out, (size_t)total * sizeof(sk_det_event), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_evs_reset(int32_t handle, const int32_t *slots, int32_t m)
+{
+    int rc = check_evs_handle(handle);
+    if (rc) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m && !slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
+    SK_ENTER(c);
+    if ((rc = sk_evs_session_info(c, handle, nullptr))) return rc;
+    return sk_evs_session_reset(c, handle, slots, m);
+}
+
+int sk_evs_close(int32_t handle)
+{
+    if (int rc = check_evs_handle(handle)) return rc;
+    SK_ENTER(c);
+    return sk_evs_session_close(c, handle);
+}
+
+int sk_last_evs_plan(int64_t *state_bytes, int64_t *staged_records, int64_t *guard_hits)
+{
+    SK_ENTER(c);
+    if (state_bytes) *state_bytes = c->evs_state_bytes;
+    if (staged_records) *staged_records = c->evs_staged;
+    if (guard_hits) {
+        unsigned long long g = 0;
+        if (c->evs_valid && c->evscnt.p) {
+            SK_HIP(hipMemcpyAsync(&g, c->evscnt.p, sizeof(g), hipMemcpyDeviceToHost, c->stream));
+            SK_HIP(hipStreamSynchronize(c->stream));
+        }
+        *guard_hits = (int64_t)g;
+    }
     return SK_OK;
 }
 

@@ -213,6 +213,10 @@ struct sk_ctx {
     void  *sessions[SK_STREAM_MAX_SESSIONS] = {};   // MotifSeq sessions of this context (sk_stream.hip), by handle
     void  *map_sessions[SK_MAP_MAX_SESSIONS] = {};  // mapping sessions of this context (sk_mapstream.hip), by handle
     int64_t map_state_bytes = 0, map_entries = 0, map_launches = 0;   // the last push of one (sk_last_map_plan)
+    void  *evs_sessions[SK_EVS_MAX_SESSIONS] = {};  // event sessions of this context (sk_evstream.hip), by handle
+    sk_buf evscnt;                    // ... [0] = slots their pushes stopped at a guard since the context was set up (sk_last_evs_plan)
+    int64_t evs_state_bytes = 0, evs_staged = 0;    // the last push of one: bytes of slot state, staging rows
+    bool   evs_valid = false;         // a push has been made on this context (the counter is meaningful)
     sk_buf commbuf;                   // staging for the small host-side exchanges
 };
 
@@ -608,6 +612,24 @@ int sk_map_session_close(sk_ctx *c, int32_t handle);
 void sk_map_close_all(sk_ctx *c);           // sk_shutdown: the context's device is current
 
 // ---- SquigglePull text (sk_pull.hip) ----
+// ---- event sessions (sk_evstream.hip) ----
+// The session behind sk_evs_*: arguments that need no session are checked in sk_api.hip, the rest (handle, slots against
+// nslots, ended slots, the 2^31 - 1 samples of a slot) here.  A push leaves its staging rows and offsets in the session;
+// sk_evs_session_gather compacts them to a device buffer, as often as asked, until the next push.
+int64_t sk_evs_session_rows(sk_ctx *c, int32_t handle, int64_t maxlen);   // staging rows per entry of such a push
+int sk_evs_session_open(sk_ctx *c, const sk_det_params *p, int32_t nslots, int32_t *handle);
+int sk_evs_session_info(sk_ctx *c, int32_t handle, int32_t *nslots);                         // SK_ERR_INVALID: unknown handle
+int sk_evs_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const int32_t *len);
+int sk_evs_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
+int sk_evs_session_push(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                        const int32_t *d_len, const int32_t *d_end, int64_t per, int64_t *d_off, const int32_t *host_slots,
+                        const int32_t *host_len, const int32_t *host_end);
+int sk_evs_session_gather(sk_ctx *c, int32_t handle, sk_det_event *d_rec, int64_t cap);
+int sk_evs_session_last(sk_ctx *c, int32_t handle, const int64_t **d_off, int32_t *m);
+int sk_evs_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
+int sk_evs_session_close(sk_ctx *c, int32_t handle);
+void sk_evs_close_all(sk_ctx *c);           // sk_shutdown: the context's device is current
+
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries
 int64_t sk_scan_blocks(int64_t n);
 int     sk_launch_scan_i64(sk_ctx *c, const int64_t *v, int64_t n, int64_t *bsum, int64_t *out);

@@ -8,6 +8,9 @@
 // file is compiled with -ffp-contract=off like the rest).  Two peak detectors walk t_short and t_long and mark
 // positions; the boundaries are 0, the marks, n; a record holds start, length, sum and sum of squares of an event.
 //
+// The detector itself -- its window sums and peak state, t from the sums, the step, the slide of the sums -- is in
+// sk_detect_dev.h, the text the event sessions (sk_evstream.hip) run too.
+//
 // k_detect_mark   one lane per read, 64 reads per wavefront (one wavefront per workgroup).  The wavefront loads a tile
 //                 of DET_TILE = 128 samples of each of its 64 rows with 16-byte loads (16 lanes per row; rows that are not
 //                 16-byte aligned take 2-byte loads) into a ring of two tiles per row in LDS.  A row's pitch is 129
@@ -31,18 +34,12 @@
 // k_detect_count then read them coalesced, a sub-batch of a host call is a slice, and k_detect_mark's rare word
 // updates do not care.  Global traffic: 2 bytes per sample twice (mark, fill), 1/8 byte per sample of mark words written
 // and read twice, 24 bytes per event.
-#include "sk_common.h"
+#include "sk_detect_dev.h"
 
 namespace {
 
-constexpr int DET_TILE = 128;                 // samples per row and load round of k_detect_mark
-constexpr int DET_LAG = 64;                   // = the largest window: positions a lane stays behind the newest sample
-constexpr int DET_RING = 2 * DET_TILE;        // samples of a row kept in LDS
-constexpr int DET_PITCH = DET_RING / 2 + 1;   // dwords per row in LDS (odd: lane l at position j -> bank (l + j / 2) mod 32)
 constexpr int FILL_ROUND = 4096;              // samples per round of k_detect_fill (64 per lane)
 constexpr int FILL_PITCH = 33;                // dwords per lane in LDS
-
-static_assert(DET_LAG <= DET_TILE / 2 && DET_LAG >= 64, "the ring holds [i - 64, i + 64] of every position in flight");
 
 struct detect_kargs {
     const int16_t *sig;
@@ -67,81 +64,23 @@ __device__ __forceinline__ int32_t det_len(const detect_kargs &a, int64_t r)
     return (int32_t)n;
 }
 
-// one detector: its window sums at the lane's position, its peak state and the mark word it is gathering
-struct det_state {
-    int32_t  w, half;
-    double   th;
-    int32_t  A, B;               // sum x[i-w..i), sum x[i..i+w)   (samples outside the read count as 0)
-    int64_t  Q;                  // their sums of squares together
-    int32_t  pos, masked_to;
-    double   val;
-    bool     valid;
-    int64_t  widx;               // the mark word being gathered (-1: none)
-    uint64_t wbits;
+// the mark word a detector (det_state, det_step, det_slide: sk_detect_dev.h) is gathering
+struct det_word {
+    int64_t  widx = -1;          // (-1: none)
+    uint64_t wbits = 0;
 };
 
-__device__ __forceinline__ void det_init(det_state &d, int32_t w, double th)
-{
-    d.w = w; d.half = w / 2; d.th = th;
-    d.A = 0; d.B = 0; d.Q = 0;
-    d.pos = -1; d.masked_to = -1; d.val = __builtin_inf(); d.valid = false;
-    d.widx = -1; d.wbits = 0;
-}
-
-__device__ __forceinline__ void det_flush(det_state &d, uint64_t *wrow)
+__device__ __forceinline__ void det_flush(det_word &d, uint64_t *wrow)
 {
     if (d.wbits) wrow[d.widx] |= d.wbits;
     d.wbits = 0;
 }
 
-__device__ __forceinline__ void det_mark(det_state &d, uint64_t *wrow, int32_t p)
+__device__ __forceinline__ void det_mark(det_word &d, uint64_t *wrow, int32_t p)
 {
     const int64_t wi = p >> 6;
     if (wi != d.widx) { det_flush(d, wrow); d.widx = wi; }
     d.wbits |= 1ull << (p & 63);
-}
-
-// t_w[i] from the sums at position i
-__device__ __forceinline__ double det_t(const det_state &d, int32_t i, int32_t n)
-{
-    if (i < d.w || i > n - d.w) return 0.0;
-    const int64_t dd = (int64_t)(d.B - d.A);
-    int64_t v = (int64_t)d.w * d.Q - (int64_t)d.A * (int64_t)d.A - (int64_t)d.B * (int64_t)d.B;
-    if (v < 1) v = 1;
-    const int64_t num = dd * dd * (int64_t)d.w;
-    return sqrt((double)num / (double)v);
-}
-
-// the detector's step at position i with cur = t[i]; `lng`: the long detector a live short peak silences (nullptr for
-// the long detector itself)
-__device__ __forceinline__ void det_step(det_state &d, det_state *lng, double h, int32_t i, double cur, uint64_t *wrow)
-{
-    if (d.pos == -1) {
-        if (cur < d.val) d.val = cur;
-        else if (cur - d.val > h) { d.val = cur; d.pos = i; }
-    } else {
-        if (cur > d.val) { d.val = cur; d.pos = i; }
-        if (lng && d.val > d.th) {
-            lng->masked_to = d.pos + d.w;
-            lng->pos = -1; lng->val = __builtin_inf(); lng->valid = false;
-        }
-        if (d.val - cur > h && d.val > d.th) d.valid = true;
-        if (d.valid && i - d.pos > d.half) {
-            det_mark(d, wrow, d.pos);
-            d.pos = -1; d.val = cur; d.valid = false;
-        }
-    }
-}
-
-// the sums move from position i to i + 1
-__device__ __forceinline__ void det_slide(det_state &d, const int16_t *xrow, int32_t i, int32_t n, int32_t xi)
-{
-    const int32_t jo = i - d.w, jn = i + d.w;
-    const int32_t xo = jo >= 0 ? (int32_t)xrow[jo & (DET_RING - 1)] : 0;
-    const int32_t xn = jn < n ? (int32_t)xrow[jn & (DET_RING - 1)] : 0;
-    d.A += xi - xo;
-    d.B += xn - xi;
-    d.Q += (int64_t)(xn * xn - xo * xo);
 }
 
 __global__ __launch_bounds__(64)
@@ -163,6 +102,7 @@ void k_detect_mark(const detect_kargs a)
     uint64_t *wrow = a.words + (r0 + lane < a.nreads ? (r0 + lane) * a.nwords : 0);
     const double h = a.p.peak_height;
     det_state ds, dl;
+    det_word ws, wl;
     det_init(ds, a.p.w_short, a.p.th_short);
     det_init(dl, a.p.w_long, a.p.th_long);
     int32_t i = 0;
@@ -202,16 +142,16 @@ void k_detect_mark(const detect_kargs a)
         const int32_t seen = (k + 1) * DET_TILE;
         const int32_t limit = seen >= n ? n : seen - DET_LAG;
         for (; i < limit; i++) {
-            if (i > ds.masked_to) det_step(ds, &dl, h, i, det_t(ds, i, n), wrow);
-            if (i > dl.masked_to) det_step(dl, nullptr, h, i, det_t(dl, i, n), wrow);
+            if (i > ds.masked_to) det_step(ds, &dl, h, i, det_t(ds, i, n), [&](int32_t p) { det_mark(ws, wrow, p); });
+            if (i > dl.masked_to) det_step(dl, nullptr, h, i, det_t(dl, i, n), [&](int32_t p) { det_mark(wl, wrow, p); });
             const int32_t xi = (int32_t)xrow[i & (DET_RING - 1)];
             det_slide(ds, xrow, i, n, xi);
             det_slide(dl, xrow, i, n, xi);
         }
         __syncthreads();                                        // the ring's other half is read before tile k + 1 lands
     }
-    det_flush(ds, wrow);
-    det_flush(dl, wrow);
+    det_flush(ws, wrow);
+    det_flush(wl, wrow);
 }
 
 // mark word wi of a read of n samples: bits at and above n and position 0 cleared

@@ -3,11 +3,18 @@
     squiggle_map_stream.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
                            [--piece N --overlap N] [--chunk E] [--calib C] [--channels S]
                            [--min_events N] [--max_dist_per_event X] [--min_margin X] [--give_up N]
+                           [--live [--sample_chunk N]]
 
-Inputs and targets are squiggle_map's.  Events are cut ONCE per read, by api.detect_events on its first --prefix samples,
-and the replay is in event space: a read is dealt to a free channel (a slot of one api.MapStream over all targets) and
-its event levels are pushed --chunk at a time; after every push api.map_decide looks at the read's records.  Cutting
-events as samples arrive is NOT part of this tool: a live client cuts them itself and pushes their levels.
+Inputs and targets are squiggle_map's.  Without --live, events are cut ONCE per read, by api.detect_events on its first
+--prefix samples, and the replay is in event space: a read is dealt to a free channel (a slot of one api.MapStream over
+all targets) and its event levels are pushed --chunk at a time; after every push api.map_decide looks at the read's
+records.
+
+--live: the replay is in SAMPLE space.  Each read's first --prefix samples are pushed --sample_chunk (default 2 000) at
+a time through a slot of an api.EventStream, END with the last chunk; the events every push closes are normalised and
+pushed to the api.MapStream slot of the same number, and api.map_decide runs after every such push.  --live needs
+--calib >= 2 (all events of the prefix are not knowable live): levels are held back until the read has --calib of them
+(or ends), then normalised with their mean and standard deviation, fixed from then on.  --chunk is not used.
 
 --calib C: every level is normalised with the mean and the standard deviation of the read's first C event levels, fixed
 from then on; the read's first push then holds at least those C events.  C = 0 (the default) takes all events of the
@@ -57,6 +64,8 @@ def build_parser():
     p.add_argument("--give_up", type=int, default=400, help="reject a read not accepted after this many events (default 400)")
     p.add_argument("--device", type=int, default=None, help="GPU index (default $SK_DEVICE or 0)")
     p.add_argument("--batch", type=int, default=4096, help="reads per event-detection call")
+    p.add_argument("--live", action="store_true", help="replay in sample space: cut events on the GPU as each read's samples arrive")
+    p.add_argument("--sample_chunk", type=int, default=2000, help="--live: raw samples per push (default 2000)")
     return p
 
 
@@ -71,6 +80,34 @@ def normalise(levels, calib):
     if head.size < 2 or not sd > 0:
         return None
     return (v - head.mean()) / sd
+
+
+def iter_reads(args):
+    """(read id, samples) of the input, in file order"""
+    if args.signal:
+        for _, rid, sig in iter_tsv_reads(args.signal):
+            yield rid, sig
+    elif args.blow5:
+        from .blow5 import read_slow5
+        for rec in read_slow5(args.blow5):
+            yield rec["read_id"], rec["signal"]
+    else:
+        a = np.load(args.i16, mmap_mode="r")
+        if a.ndim != 2 or a.dtype != np.int16:
+            raise ValueError("need a 2-D int16 array, got {} {}".format(a.dtype, a.shape))
+        for i in range(a.shape[0]):
+            yield str(i), np.asarray(a[i])
+
+
+def read_samples(args, src):
+    """[(read id, int16 samples)] of the input: each read's first --prefix samples, for the live replay"""
+    out = []
+    for rid, sig in iter_reads(args):
+        b = api.as_int16_exact(np.asarray(sig)[:args.prefix])
+        if b is None:
+            raise ValueError("read {} is not int16-exact: event detection takes raw samples".format(rid))
+        out.append((rid, np.ascontiguousarray(np.asarray(b).reshape(-1), dtype=np.int16)))
+    return out
 
 
 def read_levels(args, src):
@@ -95,19 +132,8 @@ def read_levels(args, src):
         if len(reads) >= max(1, args.batch):
             flush()
 
-    if args.signal:
-        for _, rid, sig in iter_tsv_reads(args.signal):
-            add(rid, sig)
-    elif args.blow5:
-        from .blow5 import read_slow5
-        for rec in read_slow5(args.blow5):
-            add(rec["read_id"], rec["signal"])
-    else:
-        a = np.load(args.i16, mmap_mode="r")
-        if a.ndim != 2 or a.dtype != np.int16:
-            raise ValueError("need a 2-D int16 array, got {} {}".format(a.dtype, a.shape))
-        for i in range(a.shape[0]):
-            add(str(i), np.asarray(a[i]))
+    for rid, sig in iter_reads(args):
+        add(rid, sig)
     flush()
     return out
 
@@ -169,6 +195,104 @@ def replay(args, targets, reads, src, write):
                 slot_read[s] = None
 
 
+class _LiveRead:
+    """a read in a channel of the live replay"""
+
+    def __init__(self, rid, samples):
+        self.rid, self.samples, self.at = rid, samples, 0           # at: samples pushed
+        self.levels = np.zeros(0)                                   # every event level so far
+        self.mean = self.sd = None                                  # fixed once --calib levels exist (or the read ends)
+        self.z = np.zeros(0)                                        # the normalised levels pushed to the mapping session
+        self.ended = False
+
+
+def replay_live(args, targets, reads, src, write):
+    """deal the reads to the channels, push their SAMPLES chunk by chunk through an event session, normalise the events
+    every push closes and push them to the mapping session; one line per read when it is decided"""
+    ys = [t[2] for t in targets]
+    tiling = None
+    if args.piece > 0:
+        ys, tiling = api.tile_targets(ys, args.piece, args.overlap)
+    queue = deque(reads)
+    S, N, Cal = args.channels, args.sample_chunk, args.calib
+    chan = [None] * S
+    params = api.det_params("rna" if args.rna else "dna")
+
+    def undecidable(r):
+        sys.stderr.write("squiggle_map_stream: {} in read {} of {}\n".format(
+            "fewer than 2 events" if len(r.levels) < 2 else "event levels without deviation", r.rid, src))
+        write("{}\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t0\t0\n".format(r.rid))
+
+    with api.EventStream(params, S) as es, api.MapStream(ys, S) as ms:
+        while True:
+            fresh = []
+            for s in range(S):
+                if chan[s] is None and queue:
+                    chan[s] = _LiveRead(*queue.popleft())
+                    fresh.append(s)
+            if fresh:
+                es.reset(fresh)
+                ms.reset(fresh)
+            live = [s for s in range(S) if chan[s] is not None]
+            if not live:
+                break
+            # ---- samples in, events out
+            chunks, end = [], []
+            for s in live:
+                r = chan[s]
+                chunks.append(r.samples[r.at:r.at + N])
+                r.at = min(len(r.samples), r.at + N)
+                r.ended = r.at >= len(r.samples)
+                end.append(r.ended)
+            off, rec = es.push(live, chunks, end=end)
+            values, _ = api.event_levels(off, rec)
+            # ---- the new levels, normalised once the calibration levels exist
+            mslots, mchunks = [], []
+            for i, s in enumerate(live):
+                r = chan[s]
+                had = len(r.levels)
+                r.levels = np.concatenate([r.levels, values[int(off[i]):int(off[i + 1])]])
+                if r.sd is None:
+                    if len(r.levels) < Cal and not r.ended:
+                        continue                                    # held back
+                    head = r.levels[:Cal]
+                    sd = head.std() if head.size >= 2 else 0.0
+                    if not sd > 0:
+                        undecidable(r)
+                        chan[s] = None
+                        continue
+                    r.mean, r.sd = head.mean(), sd
+                    had = 0
+                new = (r.levels[had:] - r.mean) / r.sd
+                if new.size == 0 and not r.ended:
+                    continue
+                r.z = np.concatenate([r.z, new])
+                mslots.append(s)
+                mchunks.append(new)
+            if not mslots:
+                continue
+            mrec = ms.push(mslots, mchunks)
+            hits = api.map_hits(mrec)
+            if tiling is not None:
+                hits = api.merge_tiles(hits, tiling)
+            full = np.zeros(hits.shape, dtype=api.MAPREC_DTYPE)
+            for f in api.HIT_DTYPE.names:
+                full[f] = hits[f]
+            full["rows"], full["pushes"] = mrec["rows"][:1], mrec["pushes"][:1]
+            _, dec = api.map_decide(full, args.min_events, args.max_dist_per_event, args.min_margin, args.give_up)
+            for i, s in enumerate(mslots):
+                r = chan[s]
+                word = DECISIONS.get(int(dec[i])) or ("end" if r.ended else None)
+                if word is None:
+                    continue
+                line = map_lines([r.rid], [r.z], hits[:, i:i + 1], targets)[0]
+                write("{}\t{}\t{}\t{}\n".format(line[:-1], word, int(mrec["pushes"][0, i]), len(r.z)))
+                chan[s] = None
+    guard = api.last_event_plan()["guard_hits"]
+    if guard:
+        raise ValueError("event session: {} slots stopped at a guard".format(guard))
+
+
 def main(argv=None):
     parser = build_parser()
     argv = sys.argv[1:] if argv is None else argv
@@ -198,6 +322,15 @@ def main(argv=None):
         parser.error("--give_up must be at least 1")
     if args.max_dist_per_event != args.max_dist_per_event or args.min_margin != args.min_margin:
         parser.error("--max_dist_per_event and --min_margin must be numbers")
+    if args.live:
+        if args.calib < 2:
+            parser.error("--live needs --calib >= 2 (the statistics of all events of the prefix are not knowable live)")
+        if args.sample_chunk < 1:
+            parser.error("--sample_chunk must be at least 1")
+        if args.calib + args.sample_chunk > _lib.SK_MAP_MAX_CHUNK:
+            parser.error("--calib + --sample_chunk must be at most {}".format(_lib.SK_MAP_MAX_CHUNK))
+        if args.channels > _lib.SK_EVS_MAX_SLOTS:
+            parser.error("--channels must be in 1 .. {}".format(_lib.SK_EVS_MAX_SLOTS))
     try:
         targets = load_targets(args.model, args.both)
     except (ValueError, IndexError, OSError) as e:
@@ -208,7 +341,10 @@ def main(argv=None):
     src = args.signal or args.blow5 or args.i16
     sys.stdout.write("\t".join(HEADER) + "\n")
     try:
-        replay(args, targets, read_levels(args, src), src, sys.stdout.write)
+        if args.live:
+            replay_live(args, targets, read_samples(args, src), src, sys.stdout.write)
+        else:
+            replay(args, targets, read_levels(args, src), src, sys.stdout.write)
     except (ValueError, EOFError, OSError) as e:
         sys.stdout.flush()
         sys.stderr.write("squiggle_map_stream: {}: {}\n".format(src, e))

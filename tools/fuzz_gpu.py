@@ -10,7 +10,9 @@ length, limits, both scale modes and lane layouts) against the prefix statement 
 adaptive-band DTW list (random lengths up to 4 000, band width, end mode, wavefront count, with and without paths)
 against the statement of tests/band_ref.py; and one mapping session (tests/mapstream_ref.draw_session: random targets,
 slot count, subsets, cuts up to 2 100 points, resets and peeks, both lane layouts) against the oracle on every slot's
-concatenation after every push.  The DTW pair
+concatenation after every push; and one event session (tests/evstream_ref.draw_session: random parameters, slot
+count, reads of four kinds, cuts, subsets, ENDs and resets) against its statement on detect_ref after every push and
+against the one-shot call on every ended read.  The DTW pair
 lists and their warping paths are two of the families of tests/randcases.py (`pairs`, `pairpaths`: the draws that used to
 live here, against tests/pairs_ref.py and tests/pair_paths_ref.py).
 
@@ -31,6 +33,7 @@ import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
 import band_ref                                       # noqa: E402
 import mapstream_ref                                  # noqa: E402
+import evstream_ref                                   # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -144,6 +147,17 @@ def mapstream_round(rng):
     finally:
         os.environ.pop("SK_DTW_NO_SMALL", None)
     return None if msg is None else "no_small=%s %s: %s" % (no_small, mapstream_ref.describe_session(case), msg)
+
+
+def evstream_round(rng):
+    """One drawn event session: every push against evstream_ref.run_session, every ended read against the one-shot call,
+    no guard hit.  Returns None, or what differed."""
+    sess = evstream_ref.draw_session(rng)
+    try:
+        evstream_ref.play_session(api, sess, "fuzz")
+    except AssertionError as e:
+        return str(e)[:3000]
+    return None
 
 
 def main():
@@ -451,6 +465,11 @@ def main():
         if msg is not None:
             bad += 1
             print("MAPSTREAM mismatch round %d %s" % (rounds, msg))
+        # ---- an event session against its statement on detect_ref (tests/evstream_ref.py) ----
+        msg = evstream_round(rng)
+        if msg is not None:
+            bad += 1
+            print("EVSTREAM mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
