@@ -1200,6 +1200,69 @@ int sk_evs_close(int32_t handle);
  * 0 unless the facts the staging rests on are wrong).  Reading it waits for the pushes.  Any pointer may be NULL. */
 int sk_last_evs_plan(int64_t *state_bytes, int64_t *staged_records, int64_t *guard_hits);
 
+/* ---- HMM sessions: Viterbi continued as a read's samples arrive -----------------------------------------------------
+ * sk_hmm_viterbi_* takes finished reads.  An HMM session owns one sk_hmm_model -- checked by the rules of the "signal
+ * HMM" section and copied at open -- and `nslots` slots, each a read in progress.  Viterbi carries O(1) state and never
+ * looks ahead, so a slot holds just that state, 224 bytes: the six scores v (float64), the six enter tuples E[6][6]
+ * (int32), n (the samples since its reset), pushes, and the slot's calibration pair {offset, unit} ({0.0, 1.0}: none).
+ * The sample feed, emission, recurrence, tie order and enter rule are those of the "signal HMM" section, unchanged.  A
+ *     push appends samples t = n, n + 1, .. to the slot: t == 0 takes the linit rule, t >= 1 the recurrence on the stored
+ *     v and E; enter indices are in read coordinates.  Two feeds write to the same state:
+ *       int16 rows with len    x = ((double)raw + offset) * unit with the slot's pair, as sk_hmm_viterbi_i16 does it;
+ *       ragged float64 values  x = the value; chunk i = values[off[i] .. off[i + 1]) -- pA text, event levels.
+ * The record after a push, one sk_hmms_rec (96 bytes) per entry: score, final_state, n_used, enter[6] are the 40 bytes of
+ *     sk_hmm_rec, field for field, and equal sk_hmm_viterbi_* on all the samples the slot has had since its reset --
+ *     whatever the cuts, whichever slots shared the push, whichever slot number the read has.  v[j] = v_j(n - 1) for
+ *     j < S and -inf for j >= S.  At n == 0 every v is -inf and the first 40 bytes are the one-shot's empty record.
+ *     pushes counts the pushes of length > 0; flags is 0 (reserved).
+ * A chunk of length 0 is a peek: it returns the record and changes nothing.  There is no END flag: without look-ahead the
+ *     record after the last push is the finished read's.
+ * Limits: SK_HMMS_MAX_SESSIONS sessions per context, 1 .. SK_HMMS_MAX_SLOTS slots, a slot holds at most 0x7fffff00
+ *     samples (the one-shot's cap), m * (stride + 64) at most 2^31 in an int16 push (SK_ERR_UNSUPPORTED).  sk_shutdown
+ *     closes open sessions.
+ * Refusals (SK_ERR_INVALID unless said otherwise).  Those the arguments alone decide come before a context is looked
+ *     for: a handle outside [0, SK_HMMS_MAX_SESSIONS), m < 0, NULL pointers (with m > 0; in the host form values may be NULL
+ *     when no chunk has a sample), stride < 0, (host forms) a negative len or one above stride, offsets that decrease, a slot outside
+ *     [0, SK_HMMS_MAX_SLOTS), a slot twice; at open a model that breaks the rules (sk_hmm_viterbi's message), NULL
+ *     handle, nslots outside 1 .. SK_HMMS_MAX_SLOTS; at reset a cal2 pair that is not finite.  Then the session: a handle
+ *     that is not open, a slot outside [0, nslots), a slot whose total would pass the cap (SK_ERR_UNSUPPORTED).  A
+ *     refused push changes nothing. */
+#define SK_HMMS_MAX_SESSIONS 8
+#define SK_HMMS_MAX_SLOTS 1048576
+typedef struct sk_hmms_rec {        /* 96 bytes */
+    double  score;                  /* the 40 bytes of sk_hmm_rec ... */
+    int32_t final_state, n_used;
+    int32_t enter[SK_HMM_STATES];
+    double  v[SK_HMM_STATES];       /* v_j(n - 1); -inf for j >= S and at n == 0 */
+    int32_t pushes, flags;
+} sk_hmms_rec;
+int sk_hmms_open(const sk_hmm_model *model, int32_t nslots, int32_t *handle);
+/* every pointer a host pointer; the first len[k] samples of row k (rows + k * stride) go to slot slots[k]; out [m] is
+ * complete when the call returns. */
+int sk_hmms_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride,
+                     const int32_t *len, sk_hmms_rec *out);
+/* device-resident form: every pointer a device pointer, nothing is synchronised.  Distinct slots inside [0, nslots) are
+ * the caller's contract: an entry with a slot outside is skipped and its record is the empty record (n_used 0, every v
+ * -inf, pushes 0).  len is clamped into [0, stride]; samples beyond a slot's cap are ignored and the slot is counted in
+ * guard_hits. */
+int sk_hmms_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                         const int32_t *d_len, sk_hmms_rec *d_out);
+/* ragged float64 values: chunk i = values[off[i] .. off[i + 1]), off [m + 1]; host pointers. */
+int sk_hmms_push_f64(int32_t handle, const int32_t *slots, int32_t m, const double *values, const int64_t *off,
+                     sk_hmms_rec *out);
+/* ... d_slots, d_values, d_off [m + 1] and d_out all device pointers, as sk_hmms_push_dev_i16. */
+int sk_hmms_push_dev_f64(int32_t handle, const int32_t *d_slots, int32_t m, const double *d_values, const int64_t *d_off,
+                         sk_hmms_rec *d_out);
+/* The named slots start a new read: n = pushes = 0, every v -inf.  cal2: NULL (no calibration: {0.0, 1.0}), or m
+ * {offset, unit} pairs, the slots' from then on (the int16 feed uses them). */
+int sk_hmms_reset(int32_t handle, const int32_t *slots, int32_t m, const double *cal2);
+int sk_hmms_close(int32_t handle);
+/* The last push of the calling thread's context: bytes of slot state of its session.  guard_hits: the entries of the
+ * device-form pushes of ALL HMM sessions of the context that brought samples beyond their slot's cap since the context
+ * was set up -- it only counts up, so one look after any number of pushes covers them all.  Reading it waits for the
+ * pushes.  Either pointer may be NULL. */
+int sk_last_hmms_plan(int64_t *state_bytes, int64_t *guard_hits);
+
 #ifdef __cplusplus
 }
 #endif

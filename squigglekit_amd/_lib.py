@@ -261,6 +261,10 @@ MAPREC_DTYPE = np.dtype([("dist", "<f8"), ("start", "<i4"), ("end", "<i4"), ("n"
 SK_MAP_MAX_SESSIONS, SK_MAP_MAX_SLOTS, SK_MAP_MAX_TARGETS, SK_MAP_MAX_CHUNK = 8, 65536, 65536, 65536
 SK_MAP_MAX_STATE_BYTES = 1 << 35
 SK_EVS_MAX_SESSIONS, SK_EVS_MAX_SLOTS = 8, 1048576
+SK_HMMS_MAX_SESSIONS, SK_HMMS_MAX_SLOTS, SK_HMMS_MAX_SAMPLES = 8, 1048576, 0x7fffff00
+# sk_hmms_rec: a slot's record after a push of an HMM session -- sk_hmm_rec's 40 bytes, then the six scores and the counters
+HMMS_DTYPE = np.dtype([("score", "<f8"), ("final_state", "<i4"), ("n_used", "<i4"), ("enter", "<i4", (SK_HMM_STATES,)),
+                       ("v", "<f8", (SK_HMM_STATES,)), ("pushes", "<i4"), ("flags", "<i4")])
 
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
@@ -450,6 +454,18 @@ ABI = {
     "sk_evs_reset": (C.c_int, [C.c_int32, _vp, C.c_int32]),
     "sk_evs_close": (C.c_int, [C.c_int32]),
     "sk_last_evs_plan": (C.c_int, [_vp, _vp, _vp]),
+    # HMM sessions ("HMM sessions" in include/squigglekit_hip.h; tests/hmmstream_ref.py states them on hmm_ref):
+    # open(model, nslots, handle); push_i16(handle, slots, m, rows, stride, len, out [m]), push_f64(handle, slots, m,
+    # values, off [m + 1], out [m]) and their device-resident forms; reset(handle, slots, m, cal2 or NULL);
+    # close(handle); the last push's plan
+    "sk_hmms_open": (C.c_int, [C.POINTER(HmmModel), C.c_int32, _i32p]),
+    "sk_hmms_push_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp]),
+    "sk_hmms_push_dev_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp]),
+    "sk_hmms_push_f64": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "sk_hmms_push_dev_f64": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "sk_hmms_reset": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
+    "sk_hmms_close": (C.c_int, [C.c_int32]),
+    "sk_last_hmms_plan": (C.c_int, [_vp, _vp]),
 }
 
 

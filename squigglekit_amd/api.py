@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HmmModel, LEVEL_DTYPE, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -2719,3 +2719,158 @@ def last_event_plan():
     v = [C.c_int64(0) for _ in range(3)]
     check(L.sk_last_evs_plan(*[C.byref(x) for x in v]))
     return {"state_bytes": v[0].value, "staged_records": v[1].value, "guard_hits": v[2].value}
+
+
+# ----------------------------------------------------------------------------
+# HMM sessions: the signal HMM's Viterbi pass continued as a read's samples arrive
+# ----------------------------------------------------------------------------
+def no_hmm_stream_records(m):
+    """m records of slots that have had no sample: sk_hmm_rec's empty record, every v -inf, no push"""
+    rec = np.zeros(m, dtype=HMMS_DTYPE)
+    rec["final_state"], rec["enter"], rec["v"] = -1, -1, -np.inf
+    return rec
+
+
+class HmmStream:
+    """An HMM session (sk_hmms_*): `nslots` reads in progress under one model, each taken through the Viterbi pass as its
+    samples arrive.  A push appends a chunk to every named slot and returns HMMS_DTYPE [m]: per entry the record
+    hmm_viterbi_batch / hmm_viterbi_ragged_f64 would give on ALL the samples the slot has had since its reset (score,
+    final_state, n_used, enter -- bit for bit, whatever the cuts), then v[6], the six scores behind it, and pushes.  An
+    empty chunk is a peek.  There is no END: the record after the last push is the finished read's.
+
+        with HmmStream(polya_model("rna_pa"), nslots=512) as hs:
+            hs.reset(slots, cal2)                   # a new read per slot; cal2 [m, 2] = (offset, unit) or None
+            rec = hs.push(slots, chunks)            # chunks: a list of int16 arrays, or (rows [m, stride], lens [m])
+            rec = hs.push_values(slots, chunks)     # chunks: a list of float64 arrays (pA, event levels)
+            seg = polya_segments(rec)               # the records are read as hmm_viterbi's are
+            dec = polya_decide(rec, min_body=2000, min_margin=50.0, give_up=60000)
+    """
+
+    def __init__(self, model, nslots=1):
+        self._h = None
+        if not 1 <= int(nslots) <= _lib.SK_HMMS_MAX_SLOTS:
+            raise ValueError("nslots must be in 1 .. %d, got %d" % (_lib.SK_HMMS_MAX_SLOTS, int(nslots)))
+        self.nslots = int(nslots)
+        self.model = model
+        L = _lib.ensure_init()
+        h = C.c_int32(-1)
+        check(L.sk_hmms_open(C.byref(model), self.nslots, C.byref(h)))
+        self._h = h.value
+
+    handle = property(lambda self: self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                            # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def _open(self):
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return _lib.load()
+
+    def push(self, slots, chunks):
+        """Append int16 chunk i to slot slots[i] (a chunk may be empty: a peek); the model sees (raw + offset) * unit with
+        the slot's calibration pair.  Returns HMMS_DTYPE [m]."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if isinstance(chunks, tuple):
+            rows, lens = chunks
+            rows = np.ascontiguousarray(rows, dtype=np.int16)
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+            if rows.ndim != 2:
+                raise ValueError("rows must be [m, stride]")
+        else:
+            chunks = [np.asarray(c) for c in chunks]
+            if any(c.dtype != np.int16 for c in chunks):
+                raise ValueError("push takes int16 chunks (raw samples); float64 values go through push_values")
+            rows, lens = pack_i16(chunks) if chunks else (np.zeros((0, 0), dtype=np.int16), np.zeros(0, dtype=np.int32))
+        m = slots.size
+        if rows.shape[0] != m or lens.size != m:
+            raise ValueError("one chunk per slot")
+        rec = np.zeros(m, dtype=HMMS_DTYPE)
+        if m == 0:
+            return rec
+        keep = rows if rows.size else np.zeros((m, 1), dtype=np.int16)
+        check(L.sk_hmms_push_i16(self._h, ptr(slots), m, ptr(keep), rows.shape[1], ptr(lens), ptr(rec)))
+        return rec
+
+    def push_values(self, slots, chunks):
+        """Append float64 chunk i to slot slots[i]; the model sees the values as they are.  Returns HMMS_DTYPE [m]."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        chunks = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in chunks]
+        m = slots.size
+        if len(chunks) != m:
+            raise ValueError("one chunk per slot")
+        rec = np.zeros(m, dtype=HMMS_DTYPE)
+        if m == 0:
+            return rec
+        off = np.zeros(m + 1, dtype=np.int64)
+        off[1:] = np.cumsum([c.size for c in chunks])
+        values = np.concatenate(chunks) if off[m] else np.zeros(1)
+        check(L.sk_hmms_push_f64(self._h, ptr(slots), m, ptr(values), ptr(off), ptr(rec)))
+        return rec
+
+    def peek(self, slots):
+        """The records of the named slots as they stand; nothing changes."""
+        slots = stream_slots(slots, self.nslots)
+        return self.push(slots, (np.zeros((slots.size, 0), dtype=np.int16), np.zeros(slots.size, dtype=np.int32)))
+
+    def reset(self, slots, cal2=None):
+        """The slots start a new read; cal2 [m, 2] = (offset, unit) per slot for the int16 feed, None: the raw values."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        cal2 = _hmm_cal(cal2, slots.size)
+        if slots.size:
+            check(L.sk_hmms_reset(self._h, ptr(slots), slots.size, None if cal2 is None else ptr(cal2)))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L = _lib.load()
+            if L.sk_hmms_close(h) not in (0, _lib.SK_ERR_NO_DEVICE):     # (after sk_shutdown the session is gone already)
+                check(-1)
+
+
+def last_hmm_stream_plan():
+    """{"state_bytes"} of the last push of an HMM session, and "guard_hits": the entries of device-form pushes of any HMM
+    session of this thread's context that brought samples beyond their slot's cap so far -- it only counts up, so one
+    look after a run covers every push of it (sk_last_hmms_plan)."""
+    L = _lib.ensure_init()
+    v = [C.c_int64(0) for _ in range(2)]
+    check(L.sk_last_hmms_plan(*[C.byref(x) for x in v]))
+    return {"state_bytes": v[0].value, "guard_hits": v[1].value}
+
+
+def polya_decide(rec, min_body, min_margin, give_up):
+    """What a live direct-RNA client does with the records of an HMM session under a polya_model.  Returns int8 per
+    record: 1 = accept (the transcript has begun: map from enter[TRANSCRIPT]) when final_state == TRANSCRIPT, the body
+    is at least min_body samples long (n_used - enter[TRANSCRIPT] >= min_body) and TRANSCRIPT leads every other state by
+    at least min_margin (v[TRANSCRIPT] - max(v[j], j != TRANSCRIPT) >= min_margin); -1 = give up: not accepted and
+    n_used >= give_up (give_up <= 0: never); 0 = wait.  Host only.
+
+    A heuristic, not a proof: the best path into TRANSCRIPT can still move its entry point while POLYA stays
+    competitive, so no record of a prefix is provably final -- which is why the margin is the caller's to set."""
+    rec = np.asarray(rec)
+    flat = rec.reshape(-1)
+    v = flat["v"].reshape(-1, 6)
+    n = flat["n_used"].astype(np.int64)
+    body = n - flat["enter"].reshape(-1, 6)[:, TRANSCRIPT]
+    others = np.delete(v, TRANSCRIPT, axis=1).max(axis=1) if flat.size else np.zeros(0)
+    with np.errstate(invalid="ignore"):
+        margin = v[:, TRANSCRIPT] - others                           # (-inf - -inf = NaN: no margin, the test fails)
+        accept = (flat["final_state"] == TRANSCRIPT) & (body >= int(min_body)) & (margin >= float(min_margin))
+    dec = np.zeros(flat.size, dtype=np.int8)
+    if int(give_up) > 0:
+        dec[~accept & (n >= int(give_up))] = -1
+    dec[accept] = 1
+    return dec.reshape(rec.shape)

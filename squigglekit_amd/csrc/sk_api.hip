@@ -2744,7 +2744,13 @@ int sk_hmm_viterbi_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *
     if (rc) return rc;
     if ((rc = check_hmm(model, limit, nreads, d_rec))) return rc;
     SK_ENTER(c);
-    return sk_launch_hmm_i16(c, d_sig, stride, d_len, nreads, d_cal2, model, limit, d_rec);
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));            // sk_last_kernel_ms: no prep, main = the kernel
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
+    if ((rc = sk_launch_hmm_i16(c, d_sig, stride, d_len, nreads, d_cal2, model, limit, d_rec))) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    return SK_OK;
 }
 
 int sk_hmm_viterbi_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,

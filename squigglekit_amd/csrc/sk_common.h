@@ -217,6 +217,10 @@ struct sk_ctx {
     sk_buf evscnt;                    // ... [0] = slots their pushes stopped at a guard since the context was set up (sk_last_evs_plan)
     int64_t evs_state_bytes = 0, evs_staged = 0;    // the last push of one: bytes of slot state, staging rows
     bool   evs_valid = false;         // a push has been made on this context (the counter is meaningful)
+    void  *hmms_sessions[SK_HMMS_MAX_SESSIONS] = {};   // HMM sessions of this context (sk_hmmstream.hip), by handle
+    sk_buf hmmscnt;                   // ... [0] = slots their pushes met full since the context was set up (sk_last_hmms_plan)
+    int64_t hmms_state_bytes = 0;     // the last push of one: bytes of slot state
+    bool   hmms_valid = false;        // a push has been made on this context (the counter is meaningful)
     sk_buf commbuf;                   // staging for the small host-side exchanges
 };
 
@@ -629,6 +633,10 @@ int sk_evs_session_last(sk_ctx *c, int32_t handle, const int64_t **d_off, int32_
 int sk_evs_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
 int sk_evs_session_close(sk_ctx *c, int32_t handle);
 void sk_evs_close_all(sk_ctx *c);           // sk_shutdown: the context's device is current
+
+// ---- HMM sessions (sk_hmmstream.hip) ----
+// The kernel, the session and the sk_hmms_* entries are all in that file; the runtime only closes what is left open.
+void sk_hmms_close_all(sk_ctx *c);          // sk_shutdown: the context's device is current
 
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries
 int64_t sk_scan_blocks(int64_t n);

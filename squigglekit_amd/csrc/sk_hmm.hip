@@ -20,7 +20,7 @@
 //     The six scores and the six tuples of six sample indices stay in registers: every loop over states is unrolled, the
 //     winning predecessor is chosen by compare-and-select.  The model is a kernel argument, so its constants are wave
 //     uniform and the compiler holds them in scalar registers.  A wavefront has 102 of them and the model alone is 78
-//     doubles, so 245 scalar values are spilled: parked in lanes of vector registers (v_writelane once, v_readlane at
+//     doubles, so 188 scalar values are spilled: parked in lanes of vector registers (v_writelane once, v_readlane at
 //     each use inside the sample loop; no scratch, no memory access -- profiles/hmm_kernel_resources.txt).  That costs
 //     vector ALU issue slots in a loop bound by them and is not removed yet.  A transition or a second
 //     component of -inf is skipped by a scalar branch on a bit mask made on the host -- exact: such a candidate is -inf and
@@ -35,33 +35,12 @@
 //
 // The second half of the file adds the state paths: the same body instantiated with back pointers, the
 // backward sweep and the statistics fill that turn them into segments.
-#include "sk_common.h"
+//
+// The model as the kernel takes it, the tile loads, the emission and the step without back pointers are in sk_hmm_dev.h:
+// the HMM sessions (sk_hmmstream.hip) run the same text on state they carry from push to push.
+#include "sk_hmm_dev.h"
 
 namespace {
-
-constexpr int HS = SK_HMM_STATES;
-
-template <int FEED> struct hmm_feed;
-template <> struct hmm_feed<SK_FEED_I16> {
-    typedef int16_t T;
-    static constexpr int TILE = 128;              // samples per row and load round
-    static constexpr int PITCH = TILE / 2 + 1;    // dwords per row in LDS (odd: lane l at position j -> bank (l + j / 2) mod 32)
-};
-template <> struct hmm_feed<SK_FEED_F64_NORM> {
-    typedef double T;
-    static constexpr int TILE = 32;
-    static constexpr int PITCH = TILE * 2 + 2;    // lane l at position j -> dwords 66 l + 2 j, + 1: bank pair 2 (l + j) mod 64
-};
-
-// the model as the kernel takes it: flat arrays, and which transitions / second components are not -inf
-struct hmm_kmodel {
-    double   linit[HS];
-    double   ltrans[HS * HS];     // [from * 6 + to]
-    double   c[HS * 2], mu[HS * 2], h[HS * 2];
-    uint64_t tmask;               // bit from * 6 + to: ltrans is not -inf
-    uint32_t cmask;               // bit j: component 1 of state j is not -inf
-    int32_t  S;
-};
 
 struct hmm_kargs {
     const void    *sig;           // int16 rows of `stride`, or float64 values
@@ -95,62 +74,6 @@ __device__ __forceinline__ int32_t hmm_len(const hmm_kargs &a, int64_t r)
     if (n < 0) n = 0;
     if (a.limit > 0 && n > a.limit) n = a.limit;
     return (int32_t)n;
-}
-
-// tile k of the wavefront's 64 rows -> LDS; row `row` holds its samples [k * TILE, min((k + 1) * TILE, nrow[row]))
-template <int FEED>
-__device__ __forceinline__ void hmm_load_tile(const hmm_kargs &a, uint32_t *tile, const int32_t *nrow, int64_t r0, int k, int lane)
-{
-    constexpr int TILE = hmm_feed<FEED>::TILE, PITCH = hmm_feed<FEED>::PITCH;
-    if (FEED == SK_FEED_I16) {
-        const int16_t *sig = (const int16_t *)a.sig;
-        if (a.vec) {
-#pragma unroll 4
-            for (int it = 0; it < 16; it++) {
-                const int row = it * 4 + (lane >> 4);
-                const int32_t pos = k * TILE + (lane & 15) * 8;
-                if (pos < nrow[row]) {                          // (a row of the batch: nrow is 0 past nreads)
-                    const uint4 v = *(const uint4 *)(sig + (r0 + row) * a.stride + pos);
-                    uint32_t *dst = tile + row * PITCH + ((lane & 15) * 4);
-                    dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
-                }
-            }
-        } else {
-            // Knowingly slow: 2-byte loads, 128 bytes per load instruction, one row after the other.  Taken only when the
-            // base or the stride breaks the 16-byte alignment; the loop over samples, not this one, bounds the kernel.
-            int16_t *t16 = (int16_t *)tile;
-            for (int row = 0; row < 64; row++) {
-                const int32_t nr = nrow[row];
-                for (int cc = lane; cc < TILE; cc += 64) {
-                    const int32_t pos = k * TILE + cc;
-                    if (pos < nr) t16[row * (2 * PITCH) + cc] = sig[(r0 + row) * a.stride + pos];
-                }
-            }
-        }
-    } else {
-        const double *sig = (const double *)a.sig;
-#pragma unroll 4
-        for (int it = 0; it < 32; it++) {
-            const int row = it * 2 + (lane >> 5);
-            const int32_t pos = k * TILE + (lane & 31);
-            if (pos < nrow[row]) {
-                const double v = sig[a.off[r0 + row] + pos];
-                *(double *)(tile + row * PITCH + (lane & 31) * 2) = v;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ double hmm_emit(const hmm_kmodel &m, int j, double x)
-{
-    const double d0 = x - m.mu[2 * j];
-    double e = m.c[2 * j] - (d0 * d0) * m.h[2 * j];
-    if ((m.cmask >> j) & 1u) {
-        const double d1 = x - m.mu[2 * j + 1];
-        const double e1 = m.c[2 * j + 1] - (d1 * d1) * m.h[2 * j + 1];
-        if (e1 > e) e = e1;
-    }
-    return e;
 }
 
 // BP: the instantiation that keeps the back pointers.  It carries, instead of the enter tuples, the winning predecessor
@@ -196,7 +119,7 @@ void k_hmm_viterbi(const hmm_kargs a)
     const T *xrow = (const T *)tile + (size_t)lane * (PITCH * 4 / sizeof(T));
     const int ntiles = (nmax + TILE - 1) / TILE;
     for (int k = 0; k < ntiles; k++) {
-        hmm_load_tile<FEED>(a, tile, nrow, r0, k, lane);
+        hmm_load_tile<FEED>(a.sig, a.stride, a.off, a.vec, tile, nrow, r0, k, lane);
         __syncthreads();
         const int32_t t0 = k * TILE;
         const int32_t tend = nmax - t0 < TILE ? nmax - t0 : TILE;   // wave uniform
@@ -209,58 +132,36 @@ void k_hmm_viterbi(const hmm_kargs a)
 #pragma unroll
                     for (int j = 0; j < HS; j++)
                         if (j < S) { v[j] = a.m.linit[j] + hmm_emit(a.m, j, x); E[j][j] = 0; NS[j] = 1; }
+                } else if (!BP) {
+                    hmm_step(a.m, S, x, t, v, E);
                 } else {
                     double nv[HS];
-                    int32_t NE[HS][HS];
                     int32_t NN[HS];
                     uint32_t argw = 0;
 #pragma unroll
                     for (int j = 0; j < HS; j++) {
                         nv[j] = ninf;
                         NN[j] = 0;
-#pragma unroll
-                        for (int q = 0; q < HS; q++) NE[j][q] = -1;
                         if (j < S) {
                             double b = v[0] + a.m.ltrans[j];    // predecessor 0: always taken
                             int32_t arg = 0, ns = NS[0];
-                            if (!BP) {
-#pragma unroll
-                                for (int q = 0; q < HS; q++) NE[j][q] = E[0][q];
-                            }
 #pragma unroll
                             for (int i = 1; i < HS; i++)
                                 if (i < S && ((a.m.tmask >> (i * HS + j)) & 1ull)) {
                                     const double cand = v[i] + a.m.ltrans[i * HS + j];
                                     const bool w = cand > b;
                                     b = w ? cand : b;
-                                    if (BP) {
-                                        arg = w ? i : arg;
-                                        ns = w ? NS[i] : ns;
-                                    } else {
-#pragma unroll
-                                        for (int q = 0; q < HS; q++) NE[j][q] = w ? E[i][q] : NE[j][q];
-                                    }
+                                    arg = w ? i : arg;
+                                    ns = w ? NS[i] : ns;
                                 }
-                            if (BP) {
-                                NN[j] = ns + (arg != j ? 1 : 0);
-                                argw |= (uint32_t)arg << (3 * j);
-                            } else {
-                                NE[j][j] = NE[j][j] < 0 ? t : NE[j][j];
-                            }
+                            NN[j] = ns + (arg != j ? 1 : 0);
+                            argw |= (uint32_t)arg << (3 * j);
                             nv[j] = b + hmm_emit(a.m, j, x);
                         }
                     }
 #pragma unroll
-                    for (int j = 0; j < HS; j++) {
-                        v[j] = nv[j];
-                        if (BP) {
-                            NS[j] = NN[j];
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < HS; q++) E[j][q] = NE[j][q];
-                        }
-                    }
-                    if (BP) bprow[(size_t)t * 64] = argw;        // t < n <= npad: inside the group's rows
+                    for (int j = 0; j < HS; j++) { v[j] = nv[j]; NS[j] = NN[j]; }
+                    bprow[(size_t)t * 64] = argw;                // t < n <= npad: inside the group's rows
                 }
             }
         }
@@ -332,30 +233,6 @@ const char *sk_hmm_model_error(const sk_hmm_model *m)
     }
     if (!any) return "at least one linit must be finite";
     return nullptr;
-}
-
-static hmm_kmodel hmm_flatten(const sk_hmm_model *m)
-{
-    hmm_kmodel k;
-    const double ninf = -__builtin_inf();
-    const int S = m->nstates;
-    k.S = S; k.tmask = 0; k.cmask = 0;
-    for (int i = 0; i < HS; i++) {
-        const bool in = i < S;
-        k.linit[i] = in ? m->linit[i] : ninf;
-        for (int j = 0; j < HS; j++) {
-            const double lt = (in && j < S) ? m->ltrans[i][j] : ninf;
-            k.ltrans[i * HS + j] = lt;
-            if (lt != ninf) k.tmask |= 1ull << (i * HS + j);
-        }
-        for (int q = 0; q < 2; q++) {
-            k.c[2 * i + q] = in ? m->c[i][q] : ninf;
-            k.mu[2 * i + q] = in ? m->mu[i][q] : 0.0;
-            k.h[2 * i + q] = in ? m->h[i][q] : 0.0;
-        }
-        if (k.c[2 * i + 1] != ninf) k.cmask |= 1u << i;
-    }
-    return k;
 }
 
 // the records of nreads int16 rows (d_cal: {offset, unit} per read or nullptr) -> d_rec[0 .. nreads)

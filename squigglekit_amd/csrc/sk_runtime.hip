@@ -230,9 +230,10 @@ int sk_shutdown(void)
         sk_stream_close_all(c);
         sk_map_close_all(c);
         sk_evs_close_all(c);
+        sk_hmms_close_all(c);
         sk_buf *bufs[] = {&c->sig, &c->len, &c->off, &c->comp, &c->prep, &c->mask,
                           &c->motif, &c->out, &c->out2, &c->misc, &c->ckpt, &c->retry, &c->motifq, &c->lastq, &c->qflag,
-                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate, &c->pull, &c->pulltext, &c->sweep, &c->sweeprec, &c->hitrows, &c->bgrec, &c->pathcnt, &c->pathlist, &c->pathscratch, &c->pathmotif, &c->pathspans, &c->events, &c->poolev, &c->pool, &c->panel, &c->panelwin, &c->panelaux, &c->panelrec, &c->seglev, &c->seglevwork, &c->detect, &c->detectout, &c->hmm, &c->hmmpath, &c->hmmseg, &c->pairs, &c->pairsval, &c->pairpath, &c->band, &c->bandslab, &c->evscnt};
+                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate, &c->pull, &c->pulltext, &c->sweep, &c->sweeprec, &c->hitrows, &c->bgrec, &c->pathcnt, &c->pathlist, &c->pathscratch, &c->pathmotif, &c->pathspans, &c->events, &c->poolev, &c->pool, &c->panel, &c->panelwin, &c->panelaux, &c->panelrec, &c->seglev, &c->seglevwork, &c->detect, &c->detectout, &c->hmm, &c->hmmpath, &c->hmmseg, &c->pairs, &c->pairsval, &c->pairpath, &c->band, &c->bandslab, &c->evscnt, &c->hmmscnt};
         for (sk_buf *b : bufs) free_buf(b);
         for (int i = 0; i < 4; i++) (void)hipEventDestroy(c->ev[i]);
         for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);

@@ -1,0 +1,285 @@
+"""GPU: HMM sessions (sk_hmms_*, api.HmmStream) against tests/hmmstream_ref.py.  Every comparison is == on bytes: the
+definition has no tolerance.  After every push the records are the reference's, a finished read's record is the one-shot
+api.hmm_viterbi_* record, and guard_hits is 0 after every test."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import hmm_ref
+import hmmstream_ref as HR
+
+pytestmark = pytest.mark.gpu
+
+NINF = -np.inf
+GRID = (1, 31, 32, 33, 127, 128, 129, 255, 257, 1000, None)             # chunk lengths of the cut grid; None: whole
+
+
+@pytest.fixture(autouse=True)
+def no_guard_hit(gpu):
+    yield
+    from squigglekit_amd import api
+    assert api.last_hmm_stream_plan()["guard_hits"] == 0
+
+
+def levels(rng, n):
+    return rng.integers(380, 620, n).astype(np.int16)
+
+
+def small_ints(rng, n):
+    return rng.integers(0, 4, n).astype(np.int16)
+
+
+@pytest.fixture(scope="module")
+def grid_read():
+    """the read of the cut grid and the reference's record after each of its prefixes: table[n], computed once (one slot,
+    one sample per push -- by the definition a slot's record depends on nothing but its own samples)"""
+    from squigglekit_amd import api
+    x = HR.small_drna_read(np.random.default_rng(20261020), 1500)
+    model = api.polya_model("synth_raw")
+    ref = HR.Session(model, 1)
+    table = [ref.records([0])[0]]
+    for t in range(len(x)):
+        table.append(ref.push([0], [x[t:t + 1]], "i16")[0])
+    table = np.array(table, dtype=HR.DTYPE)
+    last = table[len(x)]
+    assert last["final_state"] == api.TRANSCRIPT and (last["enter"] >= 0).all(), last   # the reference alone: every state visited
+    return x, model, table
+
+
+def test_cut_grid(gpu, grid_read):
+    """one read under every chunk length of the grid, both feeds, each in a slot of one session"""
+    from squigglekit_amd import api
+    x, model, table = grid_read
+    n, G = len(x), len(GRID)
+    cut = [n if c is None else c for c in GRID]
+    with api.HmmStream(model, 2 * G) as hs:
+        at = np.zeros(G, dtype=np.int64)
+        pushes = 0
+        while (at < n).any():
+            live = np.flatnonzero(at < n)
+            chunks = [x[at[g]:at[g] + cut[g]] for g in live]
+            pushes += 1
+            want = table[np.minimum(at[live] + [cut[g] for g in live], n)].copy()
+            want["pushes"] = pushes
+            got = hs.push(live, chunks)
+            HR.assert_records(got, want, live, "int16 feed, push %d" % pushes)
+            got = hs.push_values(live + G, [c.astype(np.float64) for c in chunks])
+            HR.assert_records(got, want, live + G, "float64 feed, push %d" % pushes)
+            at[live] += [len(c) for c in chunks]
+        assert pushes == n
+        last = hs.peek(np.arange(2 * G))
+    whole = api.hmm_viterbi_batch(x[None, :], None, model)[0]
+    whole_f = api.hmm_viterbi_ragged_f64(x.astype(np.float64), [0, n], model)[0]
+    assert whole.tobytes() == whole_f.tobytes() == table[n].tobytes()[:40]
+    for name in api.HMM_DTYPE.names:
+        assert all(r[name].tobytes() == whole[name].tobytes() for r in last), name
+    assert last["pushes"].tolist() == [-(-n // c) for c in cut] * 2
+    seg = api.polya_segments(last)                                       # HMMS_DTYPE goes where HMM_DTYPE goes
+    assert seg.tobytes() == api.polya_segments(np.repeat(whole, 2 * G)).tobytes() and seg["found"].all()
+
+
+@pytest.mark.parametrize("S", [1, 64, 65, 130])
+def test_wave_mates(gpu, S):
+    """pushes that name a shuffled subset: fresh, continuing and peeked slots in one wavefront, chunk lengths 0 .. 300,
+    both feeds, resets in mid-read, calibrated slots next to uncalibrated ones"""
+    from squigglekit_amd import api
+    from test_gpu_hmm import random_model
+    rng = np.random.default_rng(60 + S)
+    model = random_model(rng, 6) if S != 64 else api.polya_model("synth_raw")
+    sess = HR.draw_session(rng, nslots=S, budget=4000 + 2000 * S, maxlen=300, draw_chunk=levels)
+    kinds = [op[0] for op in sess["ops"]]
+    assert "reset" in kinds and any(op[2] is not None for op in sess["ops"] if op[0] == "reset")
+    assert HR.play_session(api, model, sess, "wave mates S=%d" % S) >= 10
+
+
+def dying_model():
+    """two states; nothing leaves state 0, the only one a read can start in: every score is -inf from the second sample on"""
+    return {"nstates": 2, "linit": np.array([0.0, NINF]), "ltrans": np.array([[NINF, NINF], [-1.0, 0.0]]),
+            "c": np.array([[0.0, NINF], [-1.0, -2.0]]), "mu": np.array([[1.0, 0.0], [2.0, 3.0]]), "h": np.array([[1.0, 0.0], [0.0, 1.0]])}
+
+
+def unreachable_model(rng):
+    m = HR.tie_model(rng, 4)
+    m["linit"][:] = [0.0, -1.0, NINF, -2.0]
+    m["ltrans"][:, 2] = NINF                                             # nothing enters state 2 and no read starts there
+    m["ltrans"][0, 0] = 0.0
+    return m
+
+
+@pytest.mark.parametrize("which", ["S1", "S2", "S6", "unreachable", "dying"])
+def test_models(gpu, which):
+    """tie-heavy models (integer ltrans, c, mu, h and integer samples: every tie is exact) of 1, 2 and 6 states, a model
+    with a state nothing reaches, and one whose states all die"""
+    from squigglekit_amd import api
+    rng = np.random.default_rng({"S1": 1, "S2": 2, "S6": 6, "unreachable": 7, "dying": 8}[which])
+    model = dying_model() if which == "dying" else unreachable_model(rng) if which == "unreachable" else HR.tie_model(rng, int(which[1]))
+    if which[0] == "S":                                                  # every state can stay: the scores do not all die
+        d = np.arange(model["nstates"])
+        model["ltrans"][d, d] = np.where(np.isfinite(model["ltrans"][d, d]), model["ltrans"][d, d], -1.0)
+    sess = HR.draw_session(rng, nslots=70, budget=60000, maxlen=150, draw_chunk=small_ints, cal_prob=0.0)
+    want = HR.run_session(model, sess)[-1]                               # the closing peek at every slot
+    if which == "dying":
+        assert ((want["n_used"] < 2) | ((want["score"] == NINF) & (want["final_state"] == 0))).all() and (want["n_used"] > 1).any()
+    if which == "unreachable":
+        assert (want["enter"][:, 2] == -1).all() and (want["v"][:, 2] == NINF).all() and (want["n_used"] > 0).any()
+    HR.play_session(api, model, sess, "model " + which)
+
+
+def test_two_sessions_open_at_once(gpu):
+    from squigglekit_amd import api
+    rng = np.random.default_rng(9)
+    ma, mb = api.polya_model("synth_raw"), HR.tie_model(rng, 3)
+    sa = HR.draw_session(rng, nslots=5, budget=5000, maxlen=200, draw_chunk=levels)
+    sb = HR.draw_session(rng, nslots=66, budget=40000, maxlen=100, draw_chunk=small_ints)
+    with api.HmmStream(ma, 5) as ha, api.HmmStream(HR.lib_model(mb), 66) as hb:
+        assert ha.handle != hb.handle
+        ia, ib = HR.iter_session(ha, ma, sa, "session a"), HR.iter_session(hb, mb, sb, "session b")
+        done = [False, False]
+        while not all(done):                                             # one op of each in turn
+            for k, it in enumerate((ia, ib)):
+                if not done[k]:
+                    done[k] = next(it, None) is None
+        assert api.last_hmm_stream_plan()["state_bytes"] in (5 * 224, 66 * 224)
+
+
+def test_device_forms_give_the_bytes_of_the_host_forms(gpu):
+    """push_dev_* on device buffers: the reference's bytes and the host forms'.  The int16 rows alternate between an
+    aligned layout (stride 304, 16-byte loads) and an odd one (stride 303 from an odd sample offset: 2-byte loads); every
+    push carries two entries that name no slot of the session: their records are empty and nobody else is touched."""
+    from squigglekit_amd import _lib, api
+    L = _lib.load()
+    rng = np.random.default_rng(10)
+    S, M = 70, 72
+    model = api.polya_model("synth_raw")
+    sess = HR.draw_session(rng, nslots=S, budget=100000, maxlen=300, draw_chunk=levels)
+    want = HR.run_session(model, sess)
+    d_rows, d_vals = L.sk_dev_alloc(M * 304 * 2 + 16), L.sk_dev_alloc(M * 300 * 8 + 8)
+    d_slots, d_len, d_off, d_out = (L.sk_dev_alloc(n) for n in (M * 4, M * 4, (M + 1) * 8, M * 96))
+    up = lambda d, a: _lib.check(L.sk_dev_upload(d, _lib.ptr(a), a.nbytes))   # noqa: E731
+    try:
+        with api.HmmStream(model, S) as dev, api.HmmStream(model, S) as host:
+            j = 0
+            for op in sess["ops"]:
+                if op[0] == "reset":
+                    dev.reset(op[1], op[2])
+                    host.reset(op[1], op[2])
+                    continue
+                _, slots, chunks, feed = op
+                m = len(slots) + 2
+                named = np.concatenate([slots[:1], [S], slots[1:], [-1]]).astype(np.int32)   # entries 1 and m - 1 name no slot
+                parts = chunks[:1] + [levels(rng, 9).astype(chunks[0].dtype)] + chunks[1:] + [levels(rng, 5).astype(chunks[0].dtype)]
+                lens = np.array([len(c) for c in parts], dtype=np.int32)
+                up(d_slots, named)
+                if feed == "i16":
+                    odd = j % 2 == 1
+                    stride = 303 if odd else 304
+                    rows = np.full((m, stride), -12345, dtype=np.int16)
+                    for i, c in enumerate(parts):
+                        rows[i, :len(c)] = c
+                    up(d_rows + (2 if odd else 0), rows)
+                    up(d_len, lens)
+                    _lib.check(L.sk_hmms_push_dev_i16(dev.handle, d_slots, m, d_rows + (2 if odd else 0), stride, d_len, d_out))
+                else:
+                    off = np.zeros(m + 1, dtype=np.int64)
+                    off[1:] = np.cumsum(lens)
+                    vals = np.concatenate(parts + [np.zeros(1)])
+                    up(d_vals, vals)
+                    up(d_off, off)
+                    _lib.check(L.sk_hmms_push_dev_f64(dev.handle, d_slots, m, d_vals, d_off, d_out))
+                got = np.zeros(m, dtype=api.HMMS_DTYPE)
+                _lib.check(L.sk_dev_download(_lib.ptr(got), d_out, got.nbytes))
+                outside = got[[1, m - 1]]
+                assert outside.tobytes() == HR.empty_records(2).tobytes(), (j, outside)
+                inside = np.delete(got, [1, m - 1])
+                HR.assert_records(inside, want[j], slots, "device form, push %d (%s)" % (j, feed), sess)
+                h = host.push(slots, chunks) if feed == "i16" else host.push_values(slots, chunks)
+                assert h.tobytes() == inside.tobytes(), j
+                j += 1
+            feeds = [op[3] for op in sess["ops"] if op[0] == "push"]
+            assert {"f64"} < set(feeds) and {j % 2 for j, f in enumerate(feeds) if f == "i16"} == {0, 1}   # both layouts ran
+            # the host form after device-form pushes knows how far every slot has come
+            assert dev.peek(np.arange(S)).tobytes() == want[-1].tobytes()
+    finally:
+        for p in (d_rows, d_vals, d_slots, d_len, d_off, d_out):
+            L.sk_dev_free(p)
+
+
+def test_lifecycle_and_session_refusals(gpu):
+    """Through the C entries, by return code: every call on a handle inside [0, 8) that was never opened or has been
+    closed; a slot == nslots in push and reset -- out and the session are as they were; a ninth open; reopening."""
+    from squigglekit_amd import _lib, api
+    L = _lib.load()
+    INV = _lib.SK_ERR_INVALID
+    i32 = lambda *v: np.array(v, dtype=np.int32)                        # noqa: E731
+    model = api.polya_model("synth_raw")
+    x = HR.small_drna_read(np.random.default_rng(11), 600)
+    out = np.full(96 * 2, 0xAB, dtype=np.uint8)
+
+    def push16(fn, handle, slots, chunks):
+        rows, lens = api.pack_i16(chunks)
+        return getattr(L, fn)(handle, _lib.ptr(slots), len(slots), _lib.ptr(rows), rows.shape[1], _lib.ptr(lens), _lib.ptr(out))
+
+    def push64(fn, handle, slots, chunks):
+        off = np.zeros(len(chunks) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(c) for c in chunks])
+        vals = np.concatenate(chunks).astype(np.float64)
+        return getattr(L, fn)(handle, _lib.ptr(slots), len(slots), _lib.ptr(vals), _lib.ptr(off), _lib.ptr(out))
+
+    def refused(rc, words):
+        msg = L.sk_last_error().decode()
+        assert rc == INV and words in msg, (rc, msg)
+        assert np.all(out == 0xAB)                                      # nothing was written
+
+    def unknown(handle):
+        words = "unknown HMM session handle %d" % handle
+        for fn in ("sk_hmms_push_i16", "sk_hmms_push_dev_i16"):          # (refused before a pointer is followed)
+            refused(push16(fn, handle, i32(0), [x[:10]]), words)
+        for fn in ("sk_hmms_push_f64", "sk_hmms_push_dev_f64"):
+            refused(push64(fn, handle, i32(0), [x[:10]]), words)
+        refused(L.sk_hmms_reset(handle, _lib.ptr(i32(0)), 1, None), words)
+        refused(L.sk_hmms_close(handle), words)
+
+    streams = [api.HmmStream(model, 2) for _ in range(8)]
+    try:
+        assert sorted(s.handle for s in streams) == list(range(8))
+        h = C.c_int32(-7)
+        rc = L.sk_hmms_open(C.byref(model), 2, C.byref(h))              # a ninth
+        assert rc == INV and "8 HMM sessions are open" in L.sk_last_error().decode() and h.value == -7
+        hs = streams[3]
+        first = hs.push([0, 1], [x[:200], x[:50]])
+        refused(push16("sk_hmms_push_i16", hs.handle, i32(1, 2), [x[50:60], x[:5]]), "entry 1: slot 2 is outside [0, 2)")
+        refused(push64("sk_hmms_push_f64", hs.handle, i32(2, 0), [x[:5], x[200:210]]), "entry 0: slot 2 is outside [0, 2)")
+        refused(L.sk_hmms_reset(hs.handle, _lib.ptr(i32(0, 2)), 2, None), "entry 1: slot 2 is outside [0, 2)")
+        assert hs.peek([0, 1]).tobytes() == first.tobytes()             # a refused call changes nothing
+        last = hs.push([1, 0], [x[50:], x[200:]])
+        want = api.hmm_viterbi_batch(x[None, :], None, model)[0]
+        for name in api.HMM_DTYPE.names:
+            assert last[0][name].tobytes() == last[1][name].tobytes() == want[name].tobytes(), name
+        gone = hs.handle
+        hs.close()
+        unknown(gone)                                                    # closed: as if never opened
+        with pytest.raises(ValueError):
+            hs.push([0], [x[:3]])
+        again = api.HmmStream(model, 3)                                  # the handle is free again
+        streams[3] = again
+        assert again.handle == gone
+        rec = again.push([2], [x])[0]
+        assert rec["score"].tobytes() == want["score"].tobytes() and rec["pushes"] == 1
+    finally:
+        for s in streams:
+            s.close()
+    unknown(0)
+
+
+def test_plan_reports_state(gpu):
+    from squigglekit_amd import api
+    with api.HmmStream(api.polya_model("rna_pa"), 3000) as hs:
+        hs.reset([5, 7], [[3.0, 0.1825], [0.0, 1.0]])
+        rec = hs.push([5, 7], [np.full(100, 500, dtype=np.int16), np.zeros(0, dtype=np.int16)])
+        plan = api.last_hmm_stream_plan()
+    assert plan == {"state_bytes": 3000 * 224, "guard_hits": 0}
+    assert rec["n_used"].tolist() == [100, 0] and rec["pushes"].tolist() == [1, 0]
+    want = hmm_ref.viterbi_batch(api.polya_model("rna_pa"), np.full((1, 100), 500, dtype=np.int16), [100], cal2=[[3.0, 0.1825]])[0]
+    assert rec[0].tobytes()[:40] == want.tobytes()
+    assert rec[1].tobytes() == HR.empty_records(1)[0].tobytes()
