@@ -1144,6 +1144,41 @@ int sk_map_close(int32_t handle);
  * sweep launches (one per piece index and (L, R) group).  Any pointer may be NULL. */
 int sk_last_map_plan(int64_t *state_bytes, int64_t *entries, int64_t *launches);
 
+/* ---- Hit lists over a pair list: up to max_hits non-overlapping loci per pair and per session slot ------------------
+ * sk_dtw_pairs and a mapping session's push report one locus per (query, target): the first argmin of the last row.
+ * A hit list keeps going, by the rule of the MotifSeq hit lists above.  For a query x of N points and a target y of M
+ * points let d_j = D[N-1][j] of sk_dtw_subsequence(x, y) and s_j the column where mlpy's back-trace from (N-1, j) ends
+ * (tie order: diagonal, then left, then up).  max_hits rounds; each takes the smallest admissible d_j, ties to the
+ * smallest j; a column is admissible if d_j <= max_dist and [s_j, j] is disjoint from every interval taken before.
+ * Records: hit k of a list is an sk_hit (dist = d_j, start = s_j, end = j, n = M, flags); an unused slot holds dist NaN,
+ *     start = end = -1 and the pair's n and flags; count is the number of hits.  An empty target: count 0, n = 0 and
+ *     SK_FLAG_EMPTY in every slot.  With max_dist = +inf hit 1 is sk_dtw_pairs' record byte for byte.
+ * Limits: max_hits 1 .. 64; max_dist not NaN (+inf: no cut); subsequence mode only; a query holds 1 .. 1 024 points.
+ * sk_dtw_pairs_hits: the arguments, checks, codes and messages of sk_dtw_pairs (subsequence mode), then the two limits
+ *     above, then NULL out / count -- all of it before a context is looked for; npairs = 0 is SK_OK.  The last rows
+ *     (12 bytes per target column) are kept for a slice of the list at a time: slices of consecutive pairs whose rows fit
+ *     the row buffer of the MotifSeq hit lists (2 GiB), at least one pair each.  out [npairs][max_hits], count [npairs].
+ * sk_dtw_pairs_hits_dev: d_values, d_out and d_count are device pointers, off and pairs host pointers; nothing is
+ *     synchronised behind the last launch.
+ * sk_map_hits: the lists of the named slots of a mapping session against every target, selected from the rows the
+ *     pushes stored: nothing is swept and nothing of the session changes.  out [ntargets][m][max_hits], count
+ *     [ntargets][m].  Hit 1 equals the sk_hit fields of the slot's last push record.  A slot without points: count 0,
+ *     every slot dist NaN, start = end = -1, n = the target's length, flags 0.  Slots are checked as sk_map_push checks
+ *     them (refusals in its order, the two limits above after m < 0); a refused call writes nothing.
+ * sk_map_hits_dev: d_slots, d_out and d_count are device pointers; the slot numbers are read back (one small copy).
+ * sk_last_pair_hits_plan: the last of these calls on the calling thread's context -- bytes of last rows selected from at
+ *     a time, slices (1 for a session), rows of more than 4 096 columns (those take a workgroup each, the others a
+ *     wavefront each).  Any pointer may be NULL. */
+int sk_dtw_pairs_hits(const double *values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
+                      int32_t max_hits, double max_dist, sk_hit *out, int32_t *count);
+int sk_dtw_pairs_hits_dev(const double *d_values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
+                          int32_t max_hits, double max_dist, sk_hit *d_out, int32_t *d_count);
+int sk_map_hits(int32_t handle, const int32_t *slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *out,
+                int32_t *count);
+int sk_map_hits_dev(int32_t handle, const int32_t *d_slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *d_out,
+                    int32_t *d_count);
+int sk_last_pair_hits_plan(int64_t *row_bytes, int64_t *slices, int64_t *long_rows);
+
 /* ---- Event sessions: a read cut into events as its samples arrive ---------------------------------------------------
  * sk_detect_events_* takes whole reads.  An event session keeps `nslots` reads in progress under one sk_det_params and
  * cuts each of them as its samples arrive.  A slot holds n, the samples it has been given since its reset, the walk

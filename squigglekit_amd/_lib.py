@@ -444,6 +444,14 @@ ABI = {
     "sk_map_reset": (C.c_int, [C.c_int32, _vp, C.c_int32]),
     "sk_map_close": (C.c_int, [C.c_int32]),
     "sk_last_map_plan": (C.c_int, [_vp, _vp, _vp]),
+    # hit lists over a pair list ("Hit lists over a pair list" in include/squigglekit_hip.h): the pair list, then max_hits,
+    # max_dist, out [npairs][K], count [npairs]; from a session's stored rows: handle, slots, m, max_hits, max_dist, out
+    # [T][m][K], count [T][m]; the last call's plan
+    "sk_dtw_pairs_hits": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_dtw_pairs_hits_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_map_hits": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_map_hits_dev": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_last_pair_hits_plan": (C.c_int, [_vp, _vp, _vp]),
     # event sessions ("Event sessions" in include/squigglekit_hip.h; tests/evstream_ref.py states them on detect_ref):
     # open(params, nslots, handle); push(handle, slots, m, rows, stride, len, end or NULL, off [m + 1], rec, cap) and its
     # device-resident form; fetch(handle, rec, cap); reset(handle, slots, m); close(handle); the last push's plan

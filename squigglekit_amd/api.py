@@ -1624,6 +1624,123 @@ def merge_tiles(records, tiling):
 
 
 # ----------------------------------------------------------------------------
+# Hit lists over a pair list: up to K non-overlapping loci per pair ("Hit lists over a pair list" in
+# include/squigglekit_hip.h and DESIGN.md 4.21)
+# ----------------------------------------------------------------------------
+def _hit_limits(max_hits, max_dist):
+    K, md = int(max_hits), float(max_dist)
+    if not 1 <= K <= 64:
+        raise ValueError("max_hits must be in 1 .. 64, got %d" % K)
+    if md != md:
+        raise ValueError("max_dist is NaN")
+    return K, md
+
+
+def dtw_pairs_hits(seqs, pairs, max_hits=8, max_dist=np.inf):
+    """Up to max_hits non-overlapping loci of every (query, target) pair of a pool (subsequence mode): (hits HIT_DTYPE
+    [npairs, K], count int32 [npairs]).  From the last row d_j = D[N-1][j] and the back-trace starts s_j, K rounds take the
+    smallest admissible d_j (ties: the smallest j); a column is admissible if d_j <= max_dist and [s_j, j] is disjoint
+    from every interval taken before.  hits[p, k] for k < count[p] is (dist, start = s_j, end = j, n = M, flags); the
+    rest hold dist NaN, start = end = -1.  With max_dist = inf hits[:, 0] is dtw_pairs' record byte for byte.  Single
+    device."""
+    K, md = _hit_limits(max_hits, max_dist)
+    L = _lib.ensure_init()
+    values, off = _as_pool(seqs)
+    pr = _as_pairs(pairs)
+    hits = np.zeros((len(pr), K), dtype=HIT_DTYPE)
+    count = np.zeros(len(pr), dtype=np.int32)
+    keep = values if values.size else np.zeros(1)
+    keep_hits = hits if hits.size else np.zeros(1, dtype=HIT_DTYPE)
+    keep_count = count if count.size else np.zeros(1, dtype=np.int32)
+    check(L.sk_dtw_pairs_hits(ptr(keep), ptr(off), off.size - 1, ptr(pr), len(pr), K, md, ptr(keep_hits), ptr(keep_count)))
+    return hits, count
+
+
+def map_queries_hits(queries, targets, max_hits=8, max_dist=np.inf):
+    """Every query against every target, up to max_hits loci each: (hits HIT_DTYPE [T, Q, K], count int32 [T, Q]);
+    hits[:, :, 0] are map_queries' records when max_dist is inf."""
+    qs = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
+    ts = [np.asarray(t, dtype=np.float64).reshape(-1) for t in targets]
+    Q, T = len(qs), len(ts)
+    t, q = np.divmod(np.arange(T * Q, dtype=np.int64), max(Q, 1))
+    hits, count = dtw_pairs_hits(qs + ts, np.stack([q, Q + t], axis=1), max_hits, max_dist)
+    return hits.reshape(T, Q, -1), count.reshape(T, Q)
+
+
+def last_pair_hits_plan():
+    """The last dtw_pairs_hits / map_queries_hits / MapStream.hits call of this thread's device: {"row_bytes": bytes of
+    last rows selected from at a time, "slices": slices of the pair list (1 for a session), "long_rows": rows of more than
+    4 096 columns (a workgroup each; the others take a wavefront each)}."""
+    L = _lib.ensure_init()
+    v = [C.c_int64(0) for _ in range(3)]
+    check(L.sk_last_pair_hits_plan(*[C.byref(x) for x in v]))
+    return {"row_bytes": v[0].value, "slices": v[1].value, "long_rows": v[2].value}
+
+
+def merge_tile_hits(hits, count, tiling, max_hits):
+    """Hit lists [P, Q, K] / counts [P, Q] of the pieces of tile_targets -> (hits [T, Q, max_hits], count [T, Q]) in
+    whole-target coordinates.  Per (target, query): the pieces' hits are pooled, shifted by their piece's origin, ordered
+    by (dist, end, start) and taken greedily while disjoint from those taken -- a locus two overlapping pieces both
+    report is kept once.  Hit 1 equals merge_tiles' record.  Host only."""
+    hits, count = np.asarray(hits), np.asarray(count)
+    K = _hit_limits(max_hits, 0.0)[0]
+    tgt, org, length = tiling["target"], tiling["origin"], tiling["length"]
+    T, Q = len(length), hits.shape[1]
+    out = np.zeros((T, Q, K), dtype=HIT_DTYPE)
+    out["dist"], out["start"], out["end"] = np.nan, -1, -1
+    cnt = np.zeros((T, Q), dtype=np.int32)
+    for t in range(T):
+        ps = np.flatnonzero(tgt == t)
+        out["n"][t] = int(length[t])
+        for q in range(Q):
+            if ps.size:
+                out["flags"][t, q] = hits["flags"][ps[0], q, 0]
+            pool = []
+            for p in ps:
+                for k in range(int(count[p, q])):
+                    h = hits[p, q, k]
+                    pool.append((float(h["dist"]), int(h["end"]) + int(org[p]), int(h["start"]) + int(org[p]), int(h["flags"])))
+            pool.sort(key=lambda c: c[:3])
+            taken = []
+            for d, e, s, fl in pool:
+                if len(taken) == K:
+                    break
+                if all(e < s0 or s > e0 for s0, e0 in taken):
+                    out[t, q, len(taken)] = (d, s, e, int(length[t]), fl)
+                    taken.append((s, e))
+            cnt[t, q] = len(taken)
+    return out, cnt
+
+
+def locus_margin(hits, count):
+    """Over ALL listed loci of all targets (hits [T, Q, K], count [T, Q]): (best_target int64 [Q], best_hit HIT_DTYPE [Q],
+    second_dist float64 [Q]).  The best locus has the smallest dist, ties to the smallest target, then to the smallest
+    end; second_dist is the smallest dist of any OTHER listed locus -- hit 2 of the best target or any hit of another
+    target -- and +inf when there is none.  A query without a locus: best_target -1, a NaN record.  Host only."""
+    hits, count = np.asarray(hits), np.asarray(count)
+    T, Q = count.shape
+    best = np.full(Q, -1, dtype=np.int64)
+    rec = np.zeros(Q, dtype=HIT_DTYPE)
+    rec["dist"], rec["start"], rec["end"] = np.nan, -1, -1
+    second = np.full(Q, np.inf)
+    if T == 0 or Q == 0:
+        return best, rec, second
+    K = hits.shape[2]
+    first = np.where(count > 0, hits["dist"][:, :, 0], np.inf)          # a list is ordered by (dist, end): its hit 1 leads
+    bt = np.argmin(first, axis=0)
+    col = np.arange(Q)
+    has = count[bt, col] > 0
+    best[has] = bt[has]
+    rec[has] = hits[bt, col, 0][has]
+    rest = first.copy()
+    rest[bt, col] = np.inf
+    if K > 1:
+        rest[bt, col] = np.where(count[bt, col] > 1, hits["dist"][bt, col, 1], np.inf)
+    second[has] = rest.min(axis=0)[has]
+    return best, rec, second
+
+
+# ----------------------------------------------------------------------------
 # MotifSeq panel: many motifs ranked per read, inside a search region
 # ----------------------------------------------------------------------------
 INT32_MAX = 2 ** 31 - 1
@@ -2544,6 +2661,20 @@ class MapStream:
         slots = stream_slots(slots, self.nslots)
         return self.push(slots, (np.zeros(0), np.zeros(slots.size + 1, dtype=np.int64)))
 
+    def hits(self, slots, max_hits=2, max_dist=np.inf):
+        """Up to max_hits non-overlapping loci of the named slots in every target, selected from the rows the pushes
+        stored (dtw_pairs_hits' rule): (hits HIT_DTYPE [T, m, K], count int32 [T, m]).  Nothing is swept and nothing of
+        the session changes; hits[:, :, 0] are the HIT fields of the slots' last push records; a slot without points
+        has count 0."""
+        L = self._open()
+        K, md = _hit_limits(max_hits, max_dist)
+        slots = stream_slots(slots, self.nslots)
+        hits = np.zeros((self.T, slots.size, K), dtype=HIT_DTYPE)
+        count = np.zeros((self.T, slots.size), dtype=np.int32)
+        if slots.size:
+            check(L.sk_map_hits(self._h, ptr(slots), slots.size, K, md, ptr(hits), ptr(count)))
+        return hits, count
+
     def reset(self, slots):
         """The slots start a new read: rows = pushes = 0."""
         L = self._open()
@@ -2600,6 +2731,32 @@ def map_decide(rec, min_rows, max_dist_per_row, min_margin, give_up_rows):
             rest = d.copy()
             rest[bt, col] = np.inf
             accept &= (rest.min(axis=0) - dbest) / rows >= float(min_margin)
+    dec[has & ~accept & (rows >= int(give_up_rows))] = -1
+    dec[accept] = 1
+    return best, dec
+
+
+def map_decide_loci(hits, count, rows, min_rows, max_dist_per_row, min_margin, give_up_rows):
+    """map_decide's rule over hit lists (hits [T, m, K], count [T, m] of MapStream.hits; rows [m], or [T, m] as the push
+    records hold them): the margin is (second_dist - best dist) / rows with locus_margin's second_dist -- the next locus
+    on ANY target, the best one included -- and a +inf margin (no other locus) passes.  Returns (best int64 [m],
+    decision int8 [m]) as map_decide does; with K = 1 and two or more targets it returns what map_decide returns.  Host
+    only."""
+    hits, count = np.asarray(hits), np.asarray(count)
+    T, m = count.shape
+    best, rec, second = locus_margin(hits, count)
+    dec = np.zeros(m, dtype=np.int8)
+    if T == 0 or m == 0:
+        return best, dec
+    has = best >= 0
+    rows = np.asarray(rows)
+    if rows.ndim == 2:
+        rows = rows[np.where(has, best, 0), np.arange(m)]
+    rows = rows.astype(np.float64)
+    dbest = np.where(has, rec["dist"], np.inf)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        accept = has & (rows >= int(min_rows)) & (dbest / rows <= float(max_dist_per_row))
+        accept &= (second - dbest) / rows >= float(min_margin)
     dec[has & ~accept & (rows >= int(give_up_rows))] = -1
     dec[accept] = 1
     return best, dec

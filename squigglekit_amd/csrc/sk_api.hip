@@ -1106,6 +1106,74 @@ int sk_last_pair_paths_tiers(int64_t *listed, int64_t *slab_bytes, int64_t *wave
     return SK_OK;
 }
 
+// ------------------------------------------------------------------ hit lists over a pair list (sk_pairs.hip, sk_pairhits.hip)
+// hits_check's rules for max_hits and max_dist, with its words
+static int check_hit_limits(int32_t max_hits, double max_dist)
+{
+    if (max_hits < 1 || max_hits > 64) return sk_fail(SK_ERR_INVALID, "max_hits %d outside 1..64", max_hits);
+    if (max_dist != max_dist) return sk_fail(SK_ERR_INVALID, "max_dist is NaN");
+    return SK_OK;
+}
+
+// what the arguments alone decide, before a context is looked for: sk_pairs_check's rules, then the hit lists'
+static int check_pairs_hits(const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs, int32_t max_hits,
+                            double max_dist, const void *out, const void *count)
+{
+    int rc;
+    if ((rc = sk_pairs_check(off, nseq, pairs, npairs, SK_PAIRS_SUBSEQUENCE, off))) return rc;   // (out and count: below)
+    if ((rc = check_hit_limits(max_hits, max_dist))) return rc;
+    if (npairs && (!out || !count)) return sk_fail(SK_ERR_INVALID, "NULL out/count");
+    return SK_OK;
+}
+
+int sk_dtw_pairs_hits_dev(const double *d_values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
+                          int32_t max_hits, double max_dist, sk_hit *d_out, int32_t *d_count)
+{
+    int rc;
+    if ((rc = check_pairs_hits(off, nseq, pairs, npairs, max_hits, max_dist, d_out, d_count))) return rc;
+    if (npairs == 0) return SK_OK;
+    if (!d_values) return sk_fail(SK_ERR_INVALID, "NULL values");
+    SK_ENTER(c);
+    return sk_pairs_hits_run(c, d_values, off, 0, nseq, pairs, npairs, max_hits, max_dist, d_out, d_count);
+}
+
+int sk_dtw_pairs_hits(const double *values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
+                      int32_t max_hits, double max_dist, sk_hit *out, int32_t *count)
+{
+    int rc;
+    if ((rc = check_pairs_hits(off, nseq, pairs, npairs, max_hits, max_dist, out, count))) return rc;
+    if (npairs == 0) return SK_OK;
+    if (!values) return sk_fail(SK_ERR_INVALID, "NULL values");
+    for (int32_t s = 0; s < nseq; s++)
+        if (off[s + 1] < off[s]) return sk_fail(SK_ERR_INVALID, "offsets not increasing at sequence %d", s);
+    SK_ENTER(c);
+    const int64_t total = nseq ? off[nseq] - off[0] : 0;
+    const size_t vb = (((size_t)(total > 0 ? total : 1) * sizeof(double)) + 15) & ~(size_t)15;
+    const size_t ob = (size_t)npairs * (size_t)max_hits * sizeof(sk_hit), cb = (size_t)npairs * sizeof(int32_t);
+    if ((rc = sk_reserve(c, &c->pairsval, vb + ob + cb))) return rc;
+    double *d_values = (double *)c->pairsval.p;
+    sk_hit *d_out = (sk_hit *)((char *)c->pairsval.p + vb);
+    int32_t *d_count = (int32_t *)((char *)d_out + ob);
+    if (total > 0)
+        SK_HIP(hipMemcpyAsync(d_values, values + off[0], (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_pairs_hits_run(c, d_values, off, off[0], nseq, pairs, npairs, max_hits, max_dist, d_out, d_count))) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, d_count, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+// the last sk_dtw_pairs_hits* / sk_map_hits* call on this context: bytes of last rows selected from at a time, slices of
+// the pair list (1 for a session), rows that took the long tier
+int sk_last_pair_hits_plan(int64_t *row_bytes, int64_t *slices, int64_t *long_rows)
+{
+    SK_ENTER(c);
+    if (row_bytes) *row_bytes = c->pairhits_row_bytes;
+    if (slices) *slices = c->pairhits_slices;
+    if (long_rows) *long_rows = c->pairhits_long_rows;
+    return SK_OK;
+}
+
 // ------------------------------------------------------------------ adaptive-band DTW over a pair list (sk_band.hip)
 // The argument checks run before the context is looked at: a refused call names its reason on any machine.
 int sk_dtw_band_dev(const double *d_values, const int64_t *off, int32_t nseq, const sk_pair *pairs, int64_t npairs,
@@ -3181,6 +3249,60 @@ int sk_map_reset(int32_t handle, const int32_t *slots, int32_t m)
     SK_ENTER(c);
     if ((rc = sk_map_session_info(c, handle, nullptr, nullptr))) return rc;
     return sk_map_session_reset(c, handle, slots, m);
+}
+
+// hit lists from a session's stored rows: what the arguments alone decide, in sk_map_push's order, then the hit lists' rules
+static int check_map_hits(int32_t handle, const int32_t *slots, int32_t m, int32_t max_hits, double max_dist, const void *out,
+                          const void *count, bool host_slots)
+{
+    if (int rc = check_map_handle(handle)) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (int rc = check_hit_limits(max_hits, max_dist)) return rc;
+    if (m == 0) return SK_OK;
+    if (!slots || !out || !count) return sk_fail(SK_ERR_INVALID, "NULL slots/out/count");
+    if (!host_slots) return SK_OK;
+    std::vector<uint8_t> seen((size_t)SK_MAP_MAX_SLOTS, 0);
+    for (int32_t i = 0; i < m; i++) {
+        if (slots[i] < 0 || slots[i] >= SK_MAP_MAX_SLOTS)
+            return sk_fail(SK_ERR_INVALID, "entry %d: slot %d is outside [0, %d)", i, slots[i], SK_MAP_MAX_SLOTS);
+        if (seen[(size_t)slots[i]]) return sk_fail(SK_ERR_INVALID, "entry %d: slot %d appears twice in one call", i, slots[i]);
+        seen[(size_t)slots[i]] = 1;
+    }
+    return SK_OK;
+}
+
+int sk_map_hits_dev(int32_t handle, const int32_t *d_slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *d_out,
+                    int32_t *d_count)
+{
+    int rc = check_map_hits(handle, d_slots, m, max_hits, max_dist, d_out, d_count, false);
+    if (rc) return rc;
+    SK_ENTER(c);
+    if ((rc = sk_map_session_info(c, handle, nullptr, nullptr))) return rc;
+    if (m == 0) return SK_OK;
+    std::vector<int32_t> slots((size_t)m);                  // the table is made on the host: the slot numbers come back
+    SK_HIP(hipMemcpyAsync(slots.data(), d_slots, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return sk_map_session_hits(c, handle, slots.data(), m, max_hits, max_dist, d_out, d_count);
+}
+
+int sk_map_hits(int32_t handle, const int32_t *slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *out, int32_t *count)
+{
+    int rc = check_map_hits(handle, slots, m, max_hits, max_dist, out, count, true);
+    if (rc) return rc;
+    SK_ENTER(c);
+    int32_t T = 0;
+    if ((rc = sk_map_session_info(c, handle, nullptr, &T))) return rc;
+    if (m == 0) return SK_OK;
+    if ((rc = sk_map_session_check_slots(c, handle, slots, m))) return rc;
+    const size_t ob = (size_t)m * (size_t)T * (size_t)max_hits * sizeof(sk_hit), cb = (size_t)m * (size_t)T * sizeof(int32_t);
+    void *d_out;
+    if ((rc = sk_map_session_stage(c, handle, 1, ob + cb, &d_out))) return rc;
+    int32_t *d_count = (int32_t *)((char *)d_out + ob);
+    if ((rc = sk_map_session_hits(c, handle, slots, m, max_hits, max_dist, (sk_hit *)d_out, d_count))) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, d_count, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
 }
 
 int sk_map_close(int32_t handle)

@@ -78,6 +78,15 @@ struct sk_map_entry {
     int32_t cont;     // 0: fresh, the virtual row -1 enters (MODE_PAIRS); 1: continuing, the stored row enters (MODE_CHAIN)
 };
 
+// Hit lists over a pair list / a mapping session (sk_pairhits.hip): one last row of the select's table.  24 bytes.
+struct sk_rowhit_entry {
+    int64_t col0;     // first column of the row inside the D and S arrays
+    int64_t list;     // its K records go to out[list * K ..], its count to count[list]
+    int32_t n;        // columns (the target's length)
+    int32_t flags;    // SK_FLAG_* of the records, | SK_ROWHIT_NOROW
+};
+#define SK_ROWHIT_NOROW 0x100   // internal (never reaches sk_hit::flags): no row is stored -- count 0, nothing is read
+
 // ... and one pair of a paths call over the list (sk_pairpath.hip): where its query and target lie in the pool, their
 // lengths, the first row of its spans.  32 bytes.
 struct sk_pairpath_entry {
@@ -160,6 +169,10 @@ struct sk_ctx {
     sk_buf pairsval;  // pair list: the pool and the records of the host entry point
     std::vector<sk_pair_query> pairs_query;   // one entry per distinct query (kept alive for the async H2D)
     std::vector<sk_pair_entry> pairs_table;   // one entry per pair, (L, R) group after group
+    sk_buf rowhit;    // pair / session hit lists: the select's table, one sk_rowhit_entry per row (sk_pairhits.hip)
+    std::vector<sk_rowhit_entry> rowhit_table;       // (kept alive for the async H2D)
+    std::vector<sk_map_entry>    pairhits_sweep;     // pair hit lists: the sweep's entries, slice after slice (kept alive likewise)
+    int64_t pairhits_row_bytes = 0, pairhits_slices = 0, pairhits_long_rows = 0;   // the last such call (sk_last_pair_hits_plan)
     sk_buf pairpath;  // pair-list paths: the table, one sk_pairpath_entry per pair (sk_pairpath.hip)
     std::vector<sk_pairpath_entry> pairpath_table;   // (kept alive for the async H2D)
     int64_t pairpath_listed = 0, pairpath_slab_bytes = 0, pairpath_waves = 0;   // the last such call: pairs left to the
@@ -364,6 +377,16 @@ int sk_launch_sdtw_rows(sk_ctx *c, const sk_sdtw_args *a, double *rowD, int32_t 
 // hit lists (sk_hits.hip): up to K disjoint matches per read from those rows; out [nreads][K], count [nreads]
 int sk_launch_hits_select(sk_ctx *c, const double *rowD, const int32_t *rowS, int64_t row_stride, const sk_hit *rec,
                           int32_t nreads, int32_t K, double max_dist, sk_hit *out, int32_t *count);
+// hit lists over a table of ragged rows (sk_pairhits.hip): tab[0 .. nrows) on the host (reordered: longest first) is
+// copied to entry `at` of c->rowhit (sk_rowhits_reserve: room for that many entries) and selected from -- rows of up to
+// 4 096 columns by one wavefront each, longer ones by a workgroup each; *long_rows += the latter
+int sk_rowhits_reserve(sk_ctx *c, int64_t nrows);
+int sk_launch_rowhits(sk_ctx *c, sk_rowhit_entry *tab, int64_t at, int32_t nrows, const double *rowD, const int32_t *rowS,
+                      int32_t K, double max_dist, sk_hit *out, int32_t *count, int64_t *long_rows);
+// the plan and the launches of sk_dtw_pairs_hits (sk_pairs.hip): d_values / d_out [npairs][K] / d_count on the device,
+// off / pairs on the host; checked by the caller (sk_pairs_check, the hit-list rules), npairs > 0
+int sk_pairs_hits_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t off0, int32_t nseq, const sk_pair *pairs,
+                      int64_t npairs, int32_t K, double max_dist, sk_hit *d_out, int32_t *d_count);
 // read background (sk_bg.hip): mean, std, median, MAD and the count below mean - std of each read's last row, in numpy's
 // order and bit for bit; rec supplies n and the flags (flagged reads: NaN fields, below -1); out [nreads]
 int sk_launch_row_background(sk_ctx *c, const double *rowD, int64_t row_stride, const sk_hit *rec, int32_t nreads,
@@ -611,6 +634,10 @@ int sk_map_session_check_slots(sk_ctx *c, int32_t handle, const int32_t *slots, 
 int sk_map_session_push(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const double *d_values,
                         const int64_t *off, sk_map_rec *d_out);
 int sk_map_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
+// hit lists from the stored rows of the named slots (checked against nslots here), every target: d_out [ntargets][m][K],
+// d_count [ntargets][m] on the device; nothing is swept, nothing of the session changes
+int sk_map_session_hits(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, int32_t K, double max_dist, sk_hit *d_out,
+                        int32_t *d_count);
 int sk_map_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
 int sk_map_session_close(sk_ctx *c, int32_t handle);
 void sk_map_close_all(sk_ctx *c);           // sk_shutdown: the context's device is current

@@ -273,6 +273,44 @@ int sk_map_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_
     return SK_OK;
 }
 
+// Hit lists from the stored rows (sk_pairhits.hip): one table entry per (target, named slot), list index t * m + i, the
+// row where the pushes left it.  A slot without points has no row: count 0, the empty record of k_map_emit in every
+// place.  Reads the row state and writes the caller's buffers only.
+int sk_map_session_hits(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, int32_t K, double max_dist, sk_hit *d_out,
+                        int32_t *d_count)
+{
+    map_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    if (m <= 0) return SK_OK;
+    int rc;
+    if ((rc = sk_map_session_check_slots(c, handle, slots, m))) return rc;
+    SK_HIP(hipStreamSynchronize(c->stream));               // an earlier call may still read the old table
+    const int64_t nrows = (int64_t)z->T * m;
+    c->rowhit_table.resize((size_t)nrows);
+    for (int32_t t = 0; t < z->T; t++)
+        for (int32_t i = 0; i < m; i++) {
+            const int32_t s = slots[i];
+            sk_rowhit_entry e;
+            e.col0 = (int64_t)s * z->sumM + z->toff[(size_t)t];
+            e.list = (int64_t)t * m + i;
+            e.n = (int32_t)(z->toff[(size_t)t + 1] - z->toff[(size_t)t]);
+            e.flags = z->rows[(size_t)s] > 0 ? 0 : SK_ROWHIT_NOROW;
+            c->rowhit_table[(size_t)e.list] = e;
+        }
+    if ((rc = sk_rowhits_reserve(c, nrows))) return rc;
+    c->pairhits_long_rows = 0;
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));            // sk_last_kernel_ms: no prep, main = the table's copy + the select
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
+    if ((rc = sk_launch_rowhits(c, c->rowhit_table.data(), 0, (int32_t)nrows, (const double *)z->stD.p, (const int32_t *)z->stS.p,
+                                K, max_dist, d_out, d_count, &c->pairhits_long_rows))) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    c->pairhits_row_bytes = (int64_t)m * z->sumM * 12;
+    c->pairhits_slices = 1;
+    return SK_OK;
+}
+
 int sk_map_session_close(sk_ctx *c, int32_t handle)
 {
     map_session *z = session_of(c, handle);

@@ -154,3 +154,118 @@ int sk_pairs_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t 
     c->ev_valid = true;
     return SK_OK;
 }
+
+// ---- hit lists over the list (the select: sk_pairhits.hip) -------------------------------------------------------------
+// The queries are shaped and laid out as above, once each.  The list is cut, in list order, into slices whose last rows
+// (12 B per target column: D f64, S i32) fit the budget of sk_hits' row buffer (SK_HITS_ROW_BYTES, 2 GiB; a slice holds at
+// least one pair).  A slice's pairs are swept as FRESH sk_map_entry entries (k_sdtw, MODE_PAIRS_CHAIN: the virtual row -1
+// enters, the last row is stored at soff) -- one launch per (L, R) group, longest target first -- and its rows go through
+// the select; the next slice follows on the same stream and reuses the buffer.  An empty target is not swept: its entry
+// of the select carries SK_FLAG_EMPTY.
+int sk_pairs_hits_run(sk_ctx *c, const double *d_values, const int64_t *off, int64_t off0, int32_t nseq, const sk_pair *pairs,
+                      int64_t npairs, int32_t K, double max_dist, sk_hit *d_out, int32_t *d_count)
+{
+    SK_HIP(hipStreamSynchronize(c->stream));               // an earlier call may still read the old plan
+    size_t budget = (size_t)2 << 30;
+    if (const char *e = sk_tune("SK_HITS_ROW_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    const int64_t budget_cols = (int64_t)(budget / 12);
+    // ---- distinct queries: shape and layout, once each ------------------------------------------------------------------
+    std::vector<int64_t> xoff_of((size_t)nseq, -1);
+    std::vector<uint8_t> key_of((size_t)nseq, 0);           // (L == 64) * 16 + R - 1
+    c->pairs_query.clear();
+    int64_t nlay = 0;
+    for (int64_t p = 0; p < npairs; p++) {
+        const int32_t q = pairs[p].query;
+        if (xoff_of[q] >= 0) continue;
+        const int N = (int)(off[q + 1] - off[q]);
+        int L, R;
+        sk_exact_shape(N, npairs, &L, &R);
+        xoff_of[q] = nlay;
+        key_of[q] = (uint8_t)((L == 64 ? 16 : 0) + R - 1);
+        sk_pair_query e;
+        e.src = off[q] - off0; e.xoff = nlay; e.N = N; e.L = L; e.R = R; e.pad = 0;
+        c->pairs_query.push_back(e);
+        nlay += (int64_t)L * R;
+    }
+    // ---- slices, and per slice the sweep's entries group after group and the select's table ---------------------------
+    struct run { int64_t first; int32_t count; int L, R; };
+    struct slice { int64_t p0, p1; size_t run0, run1; };
+    std::vector<slice> slices;
+    std::vector<run> runs;
+    c->pairhits_sweep.clear();
+    c->rowhit_table.resize((size_t)npairs);
+    int64_t max_cols = 0, max_pairs = 0;
+    std::vector<int32_t> order;
+    for (int64_t p0 = 0; p0 < npairs;) {
+        int64_t cols = 0, p1 = p0;
+        while (p1 < npairs) {
+            const int32_t t = pairs[p1].target;
+            const int64_t M = off[t + 1] - off[t];
+            if (p1 > p0 && cols + M > budget_cols) break;
+            c->rowhit_table[(size_t)p1] = {cols, p1, (int32_t)M, M == 0 ? SK_FLAG_EMPTY : 0};
+            cols += M;
+            p1++;
+        }
+        slice sl;
+        sl.p0 = p0; sl.p1 = p1; sl.run0 = runs.size();
+        for (int g = 0; g < 32; g++) {
+            order.clear();
+            for (int64_t p = p0; p < p1; p++)
+                if (key_of[pairs[p].query] == g && c->rowhit_table[(size_t)p].n > 0) order.push_back((int32_t)p);
+            if (order.empty()) continue;
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+                return c->rowhit_table[(size_t)a].n > c->rowhit_table[(size_t)b].n;
+            });
+            const int L = g >= 16 ? 64 : 16, R = (g & 15) + 1;
+            runs.push_back({(int64_t)c->pairhits_sweep.size(), (int32_t)order.size(), L, R});
+            for (int32_t p : order) {
+                const int32_t q = pairs[p].query, t = pairs[p].target;
+                sk_map_entry e;
+                e.toff = off[t] - off0; e.xoff = xoff_of[q]; e.soff = c->rowhit_table[(size_t)p].col0;
+                e.n = c->rowhit_table[(size_t)p].n; e.P = L * R - (int32_t)(off[q + 1] - off[q]);
+                e.rec = (int32_t)(p - p0); e.cont = 0;
+                c->pairhits_sweep.push_back(e);
+            }
+        }
+        sl.run1 = runs.size();
+        slices.push_back(sl);
+        max_cols = std::max(max_cols, cols);
+        max_pairs = std::max(max_pairs, p1 - p0);
+        p0 = p1;
+    }
+    // ---- room: layouts + the two tables of the queries and the sweep; the row buffer; the select's table ---------------
+    const size_t nq = c->pairs_query.size(), ne = c->pairhits_sweep.size();
+    int rc = sk_reserve(c, &c->pairs, (size_t)nlay * sizeof(double) + ne * sizeof(sk_map_entry) + nq * sizeof(sk_pair_query) + 16);
+    if (rc) return rc;
+    const size_t colsD = (size_t)(max_cols > 0 ? max_cols : 1), colsS = (colsD + 1) & ~(size_t)1;
+    if ((rc = sk_reserve(c, &c->hitrows, colsD * sizeof(double) + colsS * sizeof(int32_t) + (size_t)max_pairs * sizeof(sk_hit)))) return rc;
+    if ((rc = sk_rowhits_reserve(c, npairs))) return rc;
+    double *d_lay = (double *)c->pairs.p;
+    sk_map_entry *d_mp = (sk_map_entry *)(d_lay + nlay);
+    sk_pair_query *d_qt = (sk_pair_query *)(d_mp + ne);
+    double *rowD = (double *)c->hitrows.p;
+    int32_t *rowS = (int32_t *)(rowD + colsD);
+    sk_hit *d_last = (sk_hit *)(rowS + colsS);              // the sweep's own records: hit 1 of the select says the same
+    if (ne) SK_HIP(hipMemcpyAsync(d_mp, c->pairhits_sweep.data(), ne * sizeof(sk_map_entry), hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipMemcpyAsync(d_qt, c->pairs_query.data(), nq * sizeof(sk_pair_query), hipMemcpyHostToDevice, c->stream));
+    if ((rc = sk_launch_pairs_layout(c, d_values, d_qt, (int)nq, d_lay))) return rc;
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));            // (no prep kernels: sk_last_kernel_ms reports 0 for them)
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
+    c->pairhits_long_rows = 0;
+    for (const slice &sl : slices) {
+        for (size_t i = sl.run0; i < sl.run1; i++)
+            if ((rc = sk_launch_sdtw_map(c, runs[i].L, runs[i].R, d_values, d_lay, d_mp + runs[i].first, runs[i].count, rowD, rowS,
+                                         d_last))) return rc;
+        if ((rc = sk_launch_rowhits(c, c->rowhit_table.data() + sl.p0, sl.p0, (int32_t)(sl.p1 - sl.p0), rowD, rowS, K, max_dist,
+                                    d_out, d_count, &c->pairhits_long_rows))) return rc;
+    }
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->pairhits_row_bytes = max_cols * 12;
+    c->pairhits_slices = (int64_t)slices.size();
+    c->last_retry = 0;
+    c->retry_dev = false;                                   // (no screening counters: sk_last_dtw_guard reads none)
+    c->prof_chunks = 0;
+    c->ev_valid = true;
+    return SK_OK;
+}

@@ -119,6 +119,7 @@ static const sk_tunable SK_TUNABLES[] = {
     {"SK_ROLL_ONE_LOOK",      "1",           "dRNA_segmenter rolling-mean branch: the workgroup-per-read kernel in numpy's order for every read instead of the streaming kernel with certified thresholds"},
     {"SK_ROLL_DELTA_SCALE",   "1e13",        "dRNA_segmenter rolling-mean branch: multiplier of the certification margin (large: every read is redone in numpy's order)"},
     {"SK_HITS_ROW_BYTES",     "1000000",     "hit lists: bytes of the last-row buffer (12 B per column and read; default 2 GiB; small values force many chunks of reads)"},
+    {"SK_ROWHITS_ONE_WAVE",   "1",           "pair / session hit lists: rows beyond 4 096 columns through one wavefront each instead of a workgroup of 16 (A/B runs)"},
     {"SK_PANEL_EXACT",        "1",           "motif panel: the one-grid exact kernel also for long windows over many reads (default: those take the screening scheme, one launch set per motif)"},
     {"SK_PATH_LDS_BYTES",     "0",           "alignment paths: bytes of direction words a hit may keep in LDS (default and most 25600; 0: every hit takes the scratch tier)"},
     {"SK_PATH_SCRATCH_BYTES", "1000000",     "alignment paths: byte budget of the scratch tier's slabs (default 1 GiB; small values leave one wavefront)"},
@@ -233,7 +234,7 @@ int sk_shutdown(void)
         sk_hmms_close_all(c);
         sk_buf *bufs[] = {&c->sig, &c->len, &c->off, &c->comp, &c->prep, &c->mask,
                           &c->motif, &c->out, &c->out2, &c->misc, &c->ckpt, &c->retry, &c->motifq, &c->lastq, &c->qflag,
-                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate, &c->pull, &c->pulltext, &c->sweep, &c->sweeprec, &c->hitrows, &c->bgrec, &c->pathcnt, &c->pathlist, &c->pathscratch, &c->pathmotif, &c->pathspans, &c->events, &c->poolev, &c->pool, &c->panel, &c->panelwin, &c->panelaux, &c->panelrec, &c->seglev, &c->seglevwork, &c->detect, &c->detectout, &c->hmm, &c->hmmpath, &c->hmmseg, &c->pairs, &c->pairsval, &c->pairpath, &c->band, &c->bandslab, &c->evscnt, &c->hmmscnt};
+                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate, &c->pull, &c->pulltext, &c->sweep, &c->sweeprec, &c->hitrows, &c->bgrec, &c->pathcnt, &c->pathlist, &c->pathscratch, &c->pathmotif, &c->pathspans, &c->events, &c->poolev, &c->pool, &c->panel, &c->panelwin, &c->panelaux, &c->panelrec, &c->seglev, &c->seglevwork, &c->detect, &c->detectout, &c->hmm, &c->hmmpath, &c->hmmseg, &c->pairs, &c->pairsval, &c->pairpath, &c->rowhit, &c->band, &c->bandslab, &c->evscnt, &c->hmmscnt};
         for (sk_buf *b : bufs) free_buf(b);
         for (int i = 0; i < 4; i++) (void)hipEventDestroy(c->ev[i]);
         for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);

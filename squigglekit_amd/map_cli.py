@@ -2,6 +2,7 @@
 
     squiggle_map.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
                     [--piece N --overlap N] [--align FILE] [--whole FILE [--band 64|128|256]]
+                    [--hits K --secondary FILE [--max_dist_per_event X]]
 
 Per read: event detection on the first --prefix raw samples (api.detect_events), the level of every event
 (api.event_levels), (level - mean) / std in numpy, then subsequence DTW of those levels against every target in one call
@@ -30,7 +31,15 @@ per anti-diagonal, default 128; start pinned, end free) against target[start : s
 strand, span = min(len - start, ceil(N_all * (end - start + 1) / n_prefix * 1.5) + band) with N_all / n_prefix the events of
 the whole read / of its prefix.  FILE gets the --align header and one line per event, ref_first / ref_last in the
 coordinates of the target searched.  A read whose band lost the end, or with fewer than 2 events or levels without
-deviation, writes no lines and a note on stderr.  stdout and --align are the same with and without --whole."""
+deviation, writes no lines and a note on stderr.  stdout and --align are the same with and without --whole.
+
+--hits K --secondary FILE: every locus, not only the best.  Up to K non-overlapping loci per read and target
+(api.map_queries_hits; with --piece the pieces' lists go through api.merge_tile_hits), --max_dist_per_event X keeps those
+with dist / events <= X.  FILE gets a header line and one line per listed locus of every read that has some, a read's loci
+in the order of (dist, target, end):
+    readID rank target strand start end dist dist_per_event margin
+rank: 1 for the read's best locus; margin: dist minus the dist of the read's best locus.  stdout is the same with and
+without these flags."""
 import argparse
 import math
 import sys
@@ -41,6 +50,7 @@ from . import api
 from .detect_cli import iter_tsv_reads
 
 HEADER = ("readID", "target", "strand", "start", "end", "events", "dist", "dist_per_event", "second_target", "second_dist")
+SECONDARY_HEADER = ("readID", "rank", "target", "strand", "start", "end", "dist", "dist_per_event", "margin")
 ALIGN_HEADER = ("readID", "target", "strand", "event", "sample_start", "sample_length", "level", "z", "ref_first", "ref_last")
 MAX_EVENTS = 1024
 
@@ -67,6 +77,9 @@ def build_parser():
     p.add_argument("--align", help="write the event alignment table to this file: one line per event of every matched read")
     p.add_argument("--whole", help="write the alignment table of the WHOLE read against the matched locus to this file (adaptive-band DTW)")
     p.add_argument("--band", type=int, default=128, help="cells per anti-diagonal of the --whole alignment: 64, 128 or 256 (default 128)")
+    p.add_argument("--hits", type=int, default=0, help="list up to this many non-overlapping loci per read and target (1..64; needs --secondary)")
+    p.add_argument("--secondary", help="write every listed locus of every read to this file (needs --hits)")
+    p.add_argument("--max_dist_per_event", type=float, default=None, help="list only loci with dist / events at most this (needs --hits)")
     p.add_argument("--device", type=int, default=None, help="GPU index (default $SK_DEVICE or 0)")
     p.add_argument("--batch", type=int, default=4096, help="reads per GPU call")
     return p
@@ -123,6 +136,24 @@ def map_lines(read_ids, queries, records, targets):
     return out
 
 
+def secondary_lines(read_ids, queries, hits, count, targets, max_dist_per_event=None):
+    """the --secondary lines of a batch: hits [T, Q, K] / count [T, Q] over the reads that have a query (in order)"""
+    out, q = [], 0
+    for rid, z in zip(read_ids, queries):
+        if z is None:
+            continue
+        loci = [(float(hits[t, q, k]["dist"]), t, int(hits[t, q, k]["end"]), int(hits[t, q, k]["start"]))
+                for t in range(count.shape[0]) for k in range(int(count[t, q]))]
+        q += 1
+        if max_dist_per_event is not None:
+            loci = [c for c in loci if c[0] / len(z) <= max_dist_per_event]
+        loci.sort()
+        for rank, (d, t, e, a) in enumerate(loci):
+            out.append("{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\t{}\n".format(
+                rid, rank + 1, targets[t][0], targets[t][1], a, e, d, d / len(z), d - loci[0][0]))
+    return out
+
+
 def align_lines(rid, target, events, levels, z, spans):
     """the table lines of one read: events its DET_EVENT_DTYPE records, levels / z the level and query point per event,
     spans [events, 2] of its path in target = (name, strand, ...); none for a read without a path (spans -1)"""
@@ -141,8 +172,9 @@ def whole_span(length, start, end, n_prefix, n_all, band):
 
 
 class _Batcher:
-    def __init__(self, args, targets, tool_input, align=None, whole=None):
+    def __init__(self, args, targets, tool_input, align=None, whole=None, secondary=None):
         self.args, self.targets, self.input, self.align, self.whole = args, targets, tool_input, align, whole
+        self.secondary = secondary
         self.params = api.det_params("rna" if args.rna else "dna")
         self.ids, self.reads, self.full = [], [], []
 
@@ -184,6 +216,14 @@ class _Batcher:
             else:
                 records = api.map_queries(qs, ys)[0]
         sys.stdout.write("".join(map_lines(self.ids, queries, records, self.targets)))
+        if self.secondary is not None and qs:
+            if self.args.piece > 0:
+                hits, count = api.map_queries_hits(qs, pieces, self.args.hits)
+                hits, count = api.merge_tile_hits(hits, count, tiling, self.args.hits)
+            else:
+                hits, count = api.map_queries_hits(qs, ys, self.args.hits)
+            self.secondary.write("".join(secondary_lines(self.ids, queries, hits, count, self.targets,
+                                                         self.args.max_dist_per_event)))
         if self.align is not None and qs:
             best = api.best_targets(records)
             span_off, spans = api.map_paths(qs, ys, records, best)
@@ -251,6 +291,12 @@ def main(argv=None):
         parser.error("--band must be 64, 128 or 256")
     if args.band != 128 and not args.whole:
         parser.error("--band needs --whole")
+    if bool(args.hits) != bool(args.secondary):
+        parser.error("--hits and --secondary go together")
+    if args.secondary and not 1 <= args.hits <= 64:
+        parser.error("--hits must be in 1 .. 64")
+    if args.max_dist_per_event is not None and (not args.hits or args.max_dist_per_event != args.max_dist_per_event):
+        parser.error("--max_dist_per_event needs --hits and a number")
     try:
         targets = load_targets(args.model, args.both)
     except (ValueError, IndexError, OSError) as e:
@@ -276,7 +322,15 @@ def main(argv=None):
             sys.stderr.write("squiggle_map: {}: {}\n".format(args.whole, e))
             sys.exit(2)
         whole.write("\t".join(ALIGN_HEADER) + "\n")
-    out = _Batcher(args, targets, src, align, whole)
+    secondary = None
+    if args.secondary:
+        try:
+            secondary = open(args.secondary, "w")
+        except OSError as e:
+            sys.stderr.write("squiggle_map: {}: {}\n".format(args.secondary, e))
+            sys.exit(2)
+        secondary.write("\t".join(SECONDARY_HEADER) + "\n")
+    out = _Batcher(args, targets, src, align, whole, secondary)
     sys.stdout.write("\t".join(HEADER) + "\n")
     try:
         if args.signal:
@@ -297,12 +351,12 @@ def main(argv=None):
     except (ValueError, EOFError, OSError) as e:
         sys.stdout.flush()
         sys.stderr.write("squiggle_map: {}: {}\n".format(src, e))
-        for fh in (align, whole):
+        for fh in (align, whole, secondary):
             if fh is not None:
                 fh.close()
         sys.exit(2)
     sys.stdout.flush()
-    for fh in (align, whole):
+    for fh in (align, whole, secondary):
         if fh is not None:
             fh.close()
 

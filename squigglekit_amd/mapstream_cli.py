@@ -3,7 +3,7 @@
     squiggle_map_stream.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
                            [--piece N --overlap N] [--chunk E] [--calib C] [--channels S]
                            [--min_events N] [--max_dist_per_event X] [--min_margin X] [--give_up N]
-                           [--live [--sample_chunk N]]
+                           [--live [--sample_chunk N]] [--locus_margin [--hits K]]
 
 Inputs and targets are squiggle_map's.  Without --live, events are cut ONCE per read, by api.detect_events on its first
 --prefix samples, and the replay is in event space: a read is dealt to a free channel (a slot of one api.MapStream over
@@ -23,6 +23,10 @@ prefix -- squiggle_map's z-score, which only a replay can know -- so the last re
 Decision (api.map_decide): accept when events >= --min_events, dist / events <= --max_dist_per_event and (second-best
 dist - best dist) / events >= --min_margin; reject when not accepted and events >= --give_up; otherwise the read goes on,
 and a read whose events run out prints `end`.
+--locus_margin: the margin is taken to the next LOCUS, not to the next target: after every push the slots' hit lists
+(MapStream.hits, up to --hits loci per target, default 2; with --piece merged by api.merge_tile_hits) go to
+api.map_decide_loci, whose second dist is the best of all other listed loci -- the second copy of a repeat on the best
+target included.  A read with one locus in all has an infinite margin.  The columns are the same.
 
 Output: the header line, then one line per read at the moment of its decision (so not in file order):
     readID target strand start end events dist dist_per_event second_target second_dist decision pushes events_seen
@@ -66,6 +70,8 @@ def build_parser():
     p.add_argument("--batch", type=int, default=4096, help="reads per event-detection call")
     p.add_argument("--live", action="store_true", help="replay in sample space: cut events on the GPU as each read's samples arrive")
     p.add_argument("--sample_chunk", type=int, default=2000, help="--live: raw samples per push (default 2000)")
+    p.add_argument("--locus_margin", action="store_true", help="accept on the margin to the next locus on any target (hit lists) instead of the next target")
+    p.add_argument("--hits", type=int, default=2, help="--locus_margin: loci listed per read and target, 1 .. 64 (default 2)")
     return p
 
 
@@ -138,6 +144,17 @@ def read_levels(args, src):
     return out
 
 
+def decide(args, ms, slots, full, tiling):
+    """the decisions int8 [m] after a push: full = the (merged) records [T, m] of the named slots with their counters"""
+    rule = (args.min_events, args.max_dist_per_event, args.min_margin, args.give_up)
+    if not args.locus_margin:
+        return api.map_decide(full, *rule)[1]
+    hits, count = ms.hits(slots, args.hits)
+    if tiling is not None:
+        hits, count = api.merge_tile_hits(hits, count, tiling, args.hits)
+    return api.map_decide_loci(hits, count, full["rows"][0], *rule)[1]
+
+
 def replay(args, targets, reads, src, write):
     """deal the reads to the channels, push their events chunk by chunk, write one line per read when it is decided"""
     ys = [t[2] for t in targets]
@@ -184,7 +201,7 @@ def replay(args, targets, reads, src, write):
             for f in api.HIT_DTYPE.names:
                 full[f] = hits[f]
             full["rows"], full["pushes"] = rec["rows"][:1], rec["pushes"][:1]
-            _, dec = api.map_decide(full, args.min_events, args.max_dist_per_event, args.min_margin, args.give_up)
+            dec = decide(args, ms, live, full, tiling)
             for i, s in enumerate(live):
                 rid, z, seen = slot_read[s]
                 word = DECISIONS.get(int(dec[i])) or ("end" if seen >= len(z) else None)
@@ -279,7 +296,7 @@ def replay_live(args, targets, reads, src, write):
             for f in api.HIT_DTYPE.names:
                 full[f] = hits[f]
             full["rows"], full["pushes"] = mrec["rows"][:1], mrec["pushes"][:1]
-            _, dec = api.map_decide(full, args.min_events, args.max_dist_per_event, args.min_margin, args.give_up)
+            dec = decide(args, ms, mslots, full, tiling)
             for i, s in enumerate(mslots):
                 r = chan[s]
                 word = DECISIONS.get(int(dec[i])) or ("end" if r.ended else None)
@@ -322,6 +339,10 @@ def main(argv=None):
         parser.error("--give_up must be at least 1")
     if args.max_dist_per_event != args.max_dist_per_event or args.min_margin != args.min_margin:
         parser.error("--max_dist_per_event and --min_margin must be numbers")
+    if not 1 <= args.hits <= 64:
+        parser.error("--hits must be in 1 .. 64")
+    if args.hits != 2 and not args.locus_margin:
+        parser.error("--hits needs --locus_margin")
     if args.live:
         if args.calib < 2:
             parser.error("--live needs --calib >= 2 (the statistics of all events of the prefix are not knowable live)")

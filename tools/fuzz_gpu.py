@@ -12,7 +12,9 @@ against the statement of tests/band_ref.py; and one mapping session (tests/mapst
 slot count, subsets, cuts up to 2 100 points, resets and peeks, both lane layouts) against the oracle on every slot's
 concatenation after every push; and one event session (tests/evstream_ref.draw_session: random parameters, slot
 count, reads of four kinds, cuts, subsets, ENDs and resets) against its statement on detect_ref after every push and
-against the one-shot call on every ended read.  The DTW pair
+against the one-shot call on every ended read; and one hit-list round (tests/pair_hits_ref.py: a drawn pair list with its
+K, max_dist and row budget, and a drawn session script whose hits() are read after every push) against the statement
+there.  The DTW pair
 lists and their warping paths are two of the families of tests/randcases.py (`pairs`, `pairpaths`: the draws that used to
 live here, against tests/pairs_ref.py and tests/pair_paths_ref.py).
 
@@ -34,6 +36,7 @@ import stream_ref                                     # noqa: E402
 import band_ref                                       # noqa: E402
 import mapstream_ref                                  # noqa: E402
 import evstream_ref                                   # noqa: E402
+import pair_hits_ref                                  # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -147,6 +150,15 @@ def mapstream_round(rng):
     finally:
         os.environ.pop("SK_DTW_NO_SMALL", None)
     return None if msg is None else "no_small=%s %s: %s" % (no_small, mapstream_ref.describe_session(case), msg)
+
+
+def pairhits_round(rng):
+    """One drawn pair list and one drawn session script through the hit lists.  Returns None, or what differed."""
+    msg = pair_hits_ref.run_pairs_case(api, ora, pair_hits_ref.draw_pairs_case(rng), os.environ)
+    if msg is not None:
+        return "pair list: " + msg
+    msg = pair_hits_ref.run_session_case(api, pair_hits_ref.draw_session_case(rng))
+    return None if msg is None else "session: " + msg
 
 
 def evstream_round(rng):
@@ -470,6 +482,11 @@ def main():
         if msg is not None:
             bad += 1
             print("EVSTREAM mismatch round %d %s" % (rounds, msg))
+        # ---- hit lists over a pair list and from a session's stored rows (tests/pair_hits_ref.py) ----
+        msg = pairhits_round(rng)
+        if msg is not None:
+            bad += 1
+            print("PAIRHITS mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
