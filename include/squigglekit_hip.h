@@ -1298,6 +1298,85 @@ int sk_hmms_close(int32_t handle);
  * pushes.  Either pointer may be NULL. */
 int sk_last_hmms_plan(int64_t *state_bytes, int64_t *guard_hits);
 
+/* ---- Live mapping sessions: samples in, mapping records and decisions out --------------------------------------------
+ * An event session cuts events, a mapping session continues the DTW; what a selective-sequencing client needs between
+ * them -- the level of every event, held back until the read can be normalised, then normalised -- and behind them -- one
+ * decision per read -- is this section.  A live session keeps `nslots` channels in progress under one sk_det_params, one
+ * calibration length C = calib and one set of targets.  It owns an event session and a mapping session (one handle of
+ * each of those tables while it is open); their kernels do the cutting and the sweep, unchanged.
+ * The definition.  Per slot, since its reset, lev[0 .. E) are the levels of the events emitted so far,
+ *     level = (double)sum / (double)length of the event record.  The slot is in one of three states.
+ *     CALIBRATING (after a reset): nothing has been mapped.  After a push, with E events in all and `ended` the END flag
+ *         of this or an earlier push: if E < C and not ended the new levels are held back (held = E).  Otherwise
+ *         head = lev[0 .. min(C, E)); with fewer than 2 levels in head, or not (sd > 0), the slot becomes UNDECIDABLE
+ *         (mean = sd = NaN); otherwise mean = the sum of head in numpy's add.reduce order / n and
+ *         sd = sqrt(sum((x - mean) * (x - mean)) / n) in the same order -- np.mean and np.std bit for bit -- the slot
+ *         becomes MAPPING and the chunk handed to the mapping side is (lev[0 .. E) - mean) / sd, held levels first.
+ *     MAPPING: the chunk is (new levels - mean) / sd; mean and sd stay until the reset.
+ *     UNDECIDABLE: events are still cut and counted, nothing is mapped until the reset.
+ *     One divide, one subtract and one divide per level, each correctly rounded: no tolerance anywhere.
+ * A push: the event session's push of the sample chunks (its rules for len, END and ended slots), the bridge above, the
+ *     mapping session's push of the chunks the bridge made, the summary.  out[t * m + k] is sk_map_push's record of slot
+ *     slots[k] against target t: (dist, start, end, n, flags) of sk_dtw_subsequence(every normalised level the slot has
+ *     been handed, target t) bit for bit, rows the number of those levels, pushes the pushes that handed at least one; a
+ *     slot that has been handed nothing has dist NaN, start = end = -1, rows = pushes = 0.  info[k] is the slot's state
+ *     after the push (events = E, mapped = levels handed so far, new_events = events this push cut).
+ * The summary (rule != NULL): best[k] from the records of entry k, with d[t] = dist, NaN replaced by +inf: target = the
+ *     first t of the smallest d[t], -1 when every dist is NaN; dist, start, end, rows are that record's (NaN, -1, -1 and
+ *     record 0's rows without a target); second_target = the first t of the smallest d over the others (the best set to
+ *     +inf: 0 when all are +inf), -1 with one target; second_dist = that record's dist as it stands (NaN with one
+ *     target).  decision 1 (accept) when there is a target, rows >= min_rows, dist / rows <= max_dist_per_row and, with
+ *     more than one target, (d[second_target] - dist) / rows >= min_margin; -1 (give up) when there is a target, it is
+ *     not accepted and rows >= give_up_rows; 0 (wait) otherwise.
+ * sk_live_fetch: the normalised chunks of the last push, compact: off [m + 1] always, values when off[m] <= cap
+ *     (SK_ERR_OVERFLOW otherwise, off still complete); before the first push nothing is written.
+ * sk_live_hits: sk_map_hits on the inner mapping session.  sk_live_reset: the slots start a new read (CALIBRATING).
+ * Limits: SK_LIVE_MAX_SESSIONS per context, calib in 2 .. SK_LIVE_MAX_CALIB, nslots in 1 .. SK_MAP_MAX_SLOTS, the
+ *     targets' limits of sk_map_open.  sk_shutdown closes open sessions.
+ * Refusals (SK_ERR_INVALID unless said otherwise).  Those the arguments alone decide come before a context is looked
+ *     for: at open sk_evs_open's for p and handle, calib outside its range, then sk_map_open's for the targets and
+ *     nslots; at a push sk_evs_push_i16's (without off / rec / cap), NULL out / info, best without rule or rule without
+ *     best, a rule with a NaN threshold or give_up_rows < 1.  Then the session: a handle that is not open, a slot outside
+ *     [0, nslots), samples for an ended slot (host form), (calib - 1) + the event session's staging rows for `stride`
+ *     above SK_MAP_MAX_CHUNK (SK_ERR_UNSUPPORTED).  A refused push changes nothing. */
+#define SK_LIVE_MAX_SESSIONS 8
+#define SK_LIVE_MAX_CALIB 8192      /* one numpy reduction buffer; 64 KB of hold buffer per slot at most */
+enum { SK_LIVE_CALIBRATING = 0, SK_LIVE_MAPPING = 1, SK_LIVE_UNDECIDABLE = 2 };
+typedef struct sk_live_info {       /* 40 bytes */
+    double  mean, sd;               /* NaN until fixed, NaN when undecidable */
+    int32_t events, mapped, held, state, ended, new_events;
+} sk_live_info;
+typedef struct sk_live_rule { int32_t min_rows, give_up_rows; double max_dist_per_row, min_margin; } sk_live_rule;
+typedef struct sk_live_best {       /* 40 bytes */
+    double  dist, second_dist;
+    int32_t target, start, end, rows, second_target, decision;
+} sk_live_best;
+int sk_live_open(const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off,
+                 int32_t ntargets, int32_t nslots, int32_t *handle);
+/* every pointer a host pointer; out [ntargets][m], info [m] and best [m] are complete when the call returns. */
+int sk_live_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride,
+                     const int32_t *len, const int32_t *end /* may be NULL */, const sk_live_rule *rule /* may be NULL */,
+                     sk_map_rec *out /* [ntargets][m] */, sk_live_info *info /* [m] */,
+                     sk_live_best *best /* [m]; NULL iff rule NULL */);
+/* device-resident form: slots, rows, len, end, out, info, best are device pointers, rule a host pointer.  The slot
+ * numbers and the chunk lengths the bridge made are read back (the sweep is planned on the host); the slots are checked
+ * against nslots and for doubles, len is clamped into [0, stride], samples for an ended slot are ignored. */
+int sk_live_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                         const int32_t *d_len, const int32_t *d_end /* may be NULL */, const sk_live_rule *rule /* may be NULL */,
+                         sk_map_rec *d_out, sk_live_info *d_info, sk_live_best *d_best);
+int sk_live_fetch(int32_t handle, int64_t *off /* [m + 1] */, double *values, int64_t cap);
+int sk_live_hits(int32_t handle, const int32_t *slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *out, int32_t *count);
+int sk_live_reset(int32_t handle, const int32_t *slots, int32_t m);
+int sk_live_close(int32_t handle);
+/* The last push of a live session on the calling thread's context: bytes of slot state (both inner sessions' and
+ * nslots * (calib * 8 + 40) of its own), the normalised levels the bridge handed to the mapping side, the kernels the
+ * session launched itself (count, fill, summary) plus the sweep's launches.  Any pointer may be NULL. */
+int sk_last_live_plan(int64_t *state_bytes, int64_t *bridged_levels, int64_t *launches);
+/* Timing of the session's last push, when it was this context's last timed call: sk_last_kernel_ms gives prep = the
+ * bridge (count, scan, fill) and main = the whole push from the event cutting to the summary, the read-back and the
+ * host-side plan of the sweep included; this gives the bridge again and the summary kernel alone (0 without a rule). */
+int sk_live_last_ms(int32_t handle, float *bridge_ms, float *summary_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,20 @@ SK_MAP_MAX_SESSIONS, SK_MAP_MAX_SLOTS, SK_MAP_MAX_TARGETS, SK_MAP_MAX_CHUNK = 8,
 SK_MAP_MAX_STATE_BYTES = 1 << 35
 SK_EVS_MAX_SESSIONS, SK_EVS_MAX_SLOTS = 8, 1048576
 SK_HMMS_MAX_SESSIONS, SK_HMMS_MAX_SLOTS, SK_HMMS_MAX_SAMPLES = 8, 1048576, 0x7fffff00
+SK_LIVE_MAX_SESSIONS, SK_LIVE_MAX_CALIB = 8, 8192
+SK_LIVE_CALIBRATING, SK_LIVE_MAPPING, SK_LIVE_UNDECIDABLE = 0, 1, 2
+# sk_live_info: a live session's slot after a push; sk_live_best: the decision summary of one entry (40 bytes each)
+LIVEINFO_DTYPE = np.dtype([("mean", "<f8"), ("sd", "<f8"), ("events", "<i4"), ("mapped", "<i4"), ("held", "<i4"),
+                           ("state", "<i4"), ("ended", "<i4"), ("new_events", "<i4")])
+LIVEBEST_DTYPE = np.dtype([("dist", "<f8"), ("second_dist", "<f8"), ("target", "<i4"), ("start", "<i4"), ("end", "<i4"),
+                           ("rows", "<i4"), ("second_target", "<i4"), ("decision", "<i4")])
+
+
+class LiveRule(C.Structure):
+    """sk_live_rule: api.map_decide's thresholds, for the decision summary of a live session's push."""
+    _fields_ = [("min_rows", C.c_int32), ("give_up_rows", C.c_int32), ("max_dist_per_row", C.c_double),
+                ("min_margin", C.c_double)]
+
 # sk_hmms_rec: a slot's record after a push of an HMM session -- sk_hmm_rec's 40 bytes, then the six scores and the counters
 HMMS_DTYPE = np.dtype([("score", "<f8"), ("final_state", "<i4"), ("n_used", "<i4"), ("enter", "<i4", (SK_HMM_STATES,)),
                        ("v", "<f8", (SK_HMM_STATES,)), ("pushes", "<i4"), ("flags", "<i4")])
@@ -474,6 +488,20 @@ ABI = {
     "sk_hmms_reset": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
     "sk_hmms_close": (C.c_int, [C.c_int32]),
     "sk_last_hmms_plan": (C.c_int, [_vp, _vp]),
+    # live mapping sessions ("Live mapping sessions" in include/squigglekit_hip.h; tests/live_ref.py states them on
+    # evstream_ref and mapstream_ref): open(params, calib, targets, target_off, ntargets, nslots, handle); push(handle,
+    # slots, m, rows, stride, len, end or NULL, rule or NULL, out [T][m], info [m], best [m] or NULL) and its
+    # device-resident form; fetch(handle, off [m + 1], values, cap); hits as sk_map_hits; reset; close; the last plan
+    "sk_live_open": (C.c_int, [C.POINTER(DetParams), C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _i32p]),
+    "sk_live_push_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp, C.POINTER(LiveRule), _vp, _vp, _vp]),
+    "sk_live_push_dev_i16": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int64, _vp, _vp, C.POINTER(LiveRule), _vp, _vp,
+                                       _vp]),
+    "sk_live_fetch": (C.c_int, [C.c_int32, _vp, _vp, C.c_int64]),
+    "sk_live_hits": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp]),
+    "sk_live_reset": (C.c_int, [C.c_int32, _vp, C.c_int32]),
+    "sk_live_close": (C.c_int, [C.c_int32]),
+    "sk_last_live_plan": (C.c_int, [_vp, _vp, _vp]),
+    "sk_live_last_ms": (C.c_int, [C.c_int32, _vp, _vp]),
 }
 
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -2876,6 +2876,167 @@ def last_event_plan():
     v = [C.c_int64(0) for _ in range(3)]
     check(L.sk_last_evs_plan(*[C.byref(x) for x in v]))
     return {"state_bytes": v[0].value, "staged_records": v[1].value, "guard_hits": v[2].value}
+
+
+# ----------------------------------------------------------------------------
+# Live mapping sessions: samples in, mapping records and decisions out
+# ----------------------------------------------------------------------------
+def live_rule(min_rows, max_dist_per_row, min_margin, give_up_rows):
+    """map_decide's thresholds, in its argument order, as the sk_live_rule a LiveMap push takes."""
+    return LiveRule(int(min_rows), int(give_up_rows), float(max_dist_per_row), float(min_margin))
+
+
+class LiveMap:
+    """A live mapping session (sk_live_*): `nslots` channels in progress under one sk_det_params, one calibration length
+    `calib` and one set of targets.  A push appends a chunk of int16 raw samples to every named slot; on the device the
+    events are cut (EventStream's kernel), their levels held back until the slot has `calib` of them (or ends), then
+    normalised with the mean and standard deviation of those and swept over every target (MapStream's kernel).  Returns
+    (rec MAPREC_DTYPE [T, m], info LIVEINFO_DTYPE [m]) -- rec as MapStream.push would return it for the normalised levels
+    the slot has been handed, info the slot's state -- and with a rule also best LIVEBEST_DTYPE [m]: map_decide's choice
+    and decision per entry.
+
+        with LiveMap(det_params("dna"), 200, targets, nslots=512) as lm:
+            rec, info = lm.push(slots, chunks, end=flags)         # chunks: a list of int16 arrays, or (rows, lens)
+            rec, info, best = lm.push(slots, chunks, rule=live_rule(100, 0.5, 0.05, 400))
+            off, z = lm.fetch()                                   # the normalised chunks of the last push
+            hits, count = lm.hits(slots, 2)                       # MapStream.hits on the inner session
+            lm.reset(slots)                                       # the slots start a new read
+
+    A live session holds one event-session and one mapping-session handle of the context while it is open."""
+
+    def __init__(self, params, calib, targets, nslots):
+        self._h = None
+        flat, toff = _as_pool(targets)
+        self.T = toff.size - 1
+        lens = np.diff(toff)
+        if self.T < 1 or self.T > _lib.SK_MAP_MAX_TARGETS:
+            raise ValueError("a live session takes 1 .. %d targets" % _lib.SK_MAP_MAX_TARGETS)
+        if np.any(lens == 0):
+            raise ValueError("target %d is empty" % int(np.flatnonzero(lens == 0)[0]))
+        if not 1 <= int(nslots) <= _lib.SK_MAP_MAX_SLOTS:
+            raise ValueError("nslots must be in 1 .. %d, got %d" % (_lib.SK_MAP_MAX_SLOTS, int(nslots)))
+        if not 2 <= int(calib) <= _lib.SK_LIVE_MAX_CALIB:
+            raise ValueError("calib must be in 2 .. %d, got %d" % (_lib.SK_LIVE_MAX_CALIB, int(calib)))
+        self.nslots, self.calib = int(nslots), int(calib)
+        self.params = params or det_params()
+        self._last_m = 0
+        L = _lib.ensure_init()
+        h = C.c_int32(-1)
+        check(L.sk_live_open(C.byref(self.params), self.calib, ptr(flat), ptr(toff), self.T, self.nslots, C.byref(h)))
+        self._h = h.value
+
+    handle = property(lambda self: self._h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                            # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def _open(self):
+        if self._h is None:
+            raise ValueError("the session is closed")
+        return _lib.load()
+
+    def push(self, slots, chunks, end=None, rule=None):
+        """Append chunk i to slot slots[i] (a chunk may be empty); end: None, or one flag per slot -- true says the read
+        ends with this chunk; rule: None, or a live_rule / (min_rows, max_dist_per_row, min_margin, give_up_rows).
+        Returns (rec [T, m], info [m]) or, with a rule, (rec, info, best [m])."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if isinstance(chunks, tuple):
+            rows, lens = chunks
+            rows = np.ascontiguousarray(rows, dtype=np.int16)
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+            if rows.ndim != 2:
+                raise ValueError("rows must be [m, stride]")
+        else:
+            chunks = [np.asarray(c) for c in chunks]
+            if any(c.dtype != np.int16 for c in chunks):
+                raise ValueError("a session takes int16 chunks (raw samples)")
+            rows, lens = pack_i16(chunks) if chunks else (np.zeros((0, 0), dtype=np.int16), np.zeros(0, dtype=np.int32))
+        m = slots.size
+        if rows.shape[0] != m or lens.size != m:
+            raise ValueError("one chunk per slot")
+        flags = None
+        if end is not None:
+            flags = np.ascontiguousarray(np.broadcast_to(np.asarray(end), (m,)) != 0, dtype=np.int32)
+        if rule is not None and not isinstance(rule, LiveRule):
+            rule = live_rule(*rule)
+        rec = np.zeros((self.T, m), dtype=MAPREC_DTYPE)
+        info = np.zeros(m, dtype=LIVEINFO_DTYPE)
+        best = np.zeros(m, dtype=LIVEBEST_DTYPE) if rule is not None else None
+        if m:
+            keep = rows if rows.size else np.zeros((m, 1), dtype=np.int16)
+            check(L.sk_live_push_i16(self._h, ptr(slots), m, ptr(keep), rows.shape[1], ptr(lens),
+                                     None if flags is None else ptr(flags), None if rule is None else C.byref(rule),
+                                     ptr(rec), ptr(info), None if best is None else ptr(best)))
+            self._last_m = m
+        return (rec, info) if rule is None else (rec, info, best)
+
+    def finish(self, slots, rule=None):
+        """The named slots' reads end here (END with empty chunks): what push returns."""
+        slots = stream_slots(slots, self.nslots)
+        m = slots.size
+        return self.push(slots, (np.zeros((m, 0), dtype=np.int16), np.zeros(m, dtype=np.int32)), end=np.ones(m, dtype=np.int32),
+                         rule=rule)
+
+    def fetch(self):
+        """(off int64 [m + 1], values float64 [off[m]]): the normalised chunks the last push handed to the mapping side,
+        entry i's at values[off[i]:off[i + 1]]."""
+        L = self._open()
+        m = self._last_m
+        off = np.zeros(m + 1, dtype=np.int64)
+        if m == 0:
+            return off, np.zeros(0)
+        rc = L.sk_live_fetch(self._h, ptr(off), None, 0)
+        if rc == _lib.SK_ERR_OVERFLOW:
+            values = np.zeros(int(off[m]), dtype=np.float64)
+            rc = L.sk_live_fetch(self._h, ptr(off), ptr(values), values.size)
+        else:
+            values = np.zeros(0)
+        check(rc)
+        return off, values
+
+    def hits(self, slots, max_hits=2, max_dist=np.inf):
+        """MapStream.hits of the named slots on the inner mapping session: (hits HIT_DTYPE [T, m, K], count int32 [T, m])."""
+        L = self._open()
+        K, md = _hit_limits(max_hits, max_dist)
+        slots = stream_slots(slots, self.nslots)
+        hits = np.zeros((self.T, slots.size, K), dtype=HIT_DTYPE)
+        count = np.zeros((self.T, slots.size), dtype=np.int32)
+        if slots.size:
+            check(L.sk_live_hits(self._h, ptr(slots), slots.size, K, md, ptr(hits), ptr(count)))
+        return hits, count
+
+    def reset(self, slots):
+        """The slots start a new read: CALIBRATING, no events, nothing mapped."""
+        L = self._open()
+        slots = stream_slots(slots, self.nslots)
+        if slots.size:
+            check(L.sk_live_reset(self._h, ptr(slots), slots.size))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L = _lib.load()
+            if L.sk_live_close(h) not in (0, _lib.SK_ERR_NO_DEVICE):     # (after sk_shutdown the session is gone already)
+                check(-1)
+
+
+def last_live_plan():
+    """The last push of a live session: {"state_bytes", "bridged_levels", "launches"} (sk_last_live_plan)."""
+    L = _lib.ensure_init()
+    v = [C.c_int64(0) for _ in range(3)]
+    check(L.sk_last_live_plan(*[C.byref(x) for x in v]))
+    return {"state_bytes": v[0].value, "bridged_levels": v[1].value, "launches": v[2].value}
 
 
 # ----------------------------------------------------------------------------

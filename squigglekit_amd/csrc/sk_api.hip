@@ -3151,6 +3151,27 @@ int check_map_handle(int32_t handle)
     return SK_OK;
 }
 
+// the targets and the slot count of a mapping session (sk_map_open, sk_live_open): counts, lengths, the caps
+int check_map_shape(const int64_t *target_off, int32_t ntargets, int32_t nslots)
+{
+    if (ntargets < 1 || ntargets > SK_MAP_MAX_TARGETS)
+        return sk_fail(SK_ERR_INVALID, "ntargets = %d is outside 1 .. %d", ntargets, SK_MAP_MAX_TARGETS);
+    if (nslots < 1 || nslots > SK_MAP_MAX_SLOTS)
+        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_MAP_MAX_SLOTS);
+    for (int32_t t = 0; t < ntargets; t++) {
+        const int64_t M = target_off[t + 1] - target_off[t];
+        if (M == 0) return sk_fail(SK_ERR_INVALID, "target %d is empty", t);
+        if (M < 0 || M > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "target %d: bad length %lld", t, (long long)M);
+    }
+    if ((int64_t)nslots * ntargets > ((int64_t)1 << 30))
+        return sk_fail(SK_ERR_UNSUPPORTED, "nslots * ntargets = %lld above 1073741824", (long long)nslots * ntargets);
+    const int64_t sumM = target_off[ntargets] - target_off[0];
+    if (sumM > SK_MAP_MAX_STATE_BYTES / 12 / nslots)
+        return sk_fail(SK_ERR_UNSUPPORTED, "row state of %lld bytes (%d slots x %lld target points x 12) above the cap of %lld",
+                       (long long)nslots * (long long)sumM * 12, nslots, (long long)sumM, (long long)SK_MAP_MAX_STATE_BYTES);
+    return SK_OK;
+}
+
 // host_slots: the slot numbers can be read here (range against the ABI's limit, none twice)
 int check_map_push(int32_t handle, const int32_t *slots, int32_t m, const double *values, const int64_t *off, const void *out,
                    bool host_slots)
@@ -3185,21 +3206,7 @@ extern "C" {
 int sk_map_open(const double *targets, const int64_t *target_off, int32_t ntargets, int32_t nslots, int32_t *handle)
 {
     if (!targets || !target_off || !handle) return sk_fail(SK_ERR_INVALID, "NULL targets/target_off/handle");
-    if (ntargets < 1 || ntargets > SK_MAP_MAX_TARGETS)
-        return sk_fail(SK_ERR_INVALID, "ntargets = %d is outside 1 .. %d", ntargets, SK_MAP_MAX_TARGETS);
-    if (nslots < 1 || nslots > SK_MAP_MAX_SLOTS)
-        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_MAP_MAX_SLOTS);
-    for (int32_t t = 0; t < ntargets; t++) {
-        const int64_t M = target_off[t + 1] - target_off[t];
-        if (M == 0) return sk_fail(SK_ERR_INVALID, "target %d is empty", t);
-        if (M < 0 || M > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "target %d: bad length %lld", t, (long long)M);
-    }
-    if ((int64_t)nslots * ntargets > ((int64_t)1 << 30))
-        return sk_fail(SK_ERR_UNSUPPORTED, "nslots * ntargets = %lld above 1073741824", (long long)nslots * ntargets);
-    const int64_t sumM = target_off[ntargets] - target_off[0];
-    if (sumM > SK_MAP_MAX_STATE_BYTES / 12 / nslots)
-        return sk_fail(SK_ERR_UNSUPPORTED, "row state of %lld bytes (%d slots x %lld target points x 12) above the cap of %lld",
-                       (long long)nslots * (long long)sumM * 12, nslots, (long long)sumM, (long long)SK_MAP_MAX_STATE_BYTES);
+    if (int rc = check_map_shape(target_off, ntargets, nslots)) return rc;
     SK_ENTER(c);
     return sk_map_session_open(c, targets, target_off, ntargets, nslots, handle);
 }
@@ -3271,6 +3278,23 @@ static int check_map_hits(int32_t handle, const int32_t *slots, int32_t m, int32
     return SK_OK;
 }
 
+// the host form of the hit lists of an open mapping session (sk_map_hits, sk_live_hits on its inner session): m >= 1
+static int map_hits_host(sk_ctx *c, int32_t handle, int32_t T, const int32_t *slots, int32_t m, int32_t max_hits, double max_dist,
+                         sk_hit *out, int32_t *count)
+{
+    int rc;
+    if ((rc = sk_map_session_check_slots(c, handle, slots, m))) return rc;
+    const size_t ob = (size_t)m * (size_t)T * (size_t)max_hits * sizeof(sk_hit), cb = (size_t)m * (size_t)T * sizeof(int32_t);
+    void *d_out;
+    if ((rc = sk_map_session_stage(c, handle, 1, ob + cb, &d_out))) return rc;
+    int32_t *d_count = (int32_t *)((char *)d_out + ob);
+    if ((rc = sk_map_session_hits(c, handle, slots, m, max_hits, max_dist, (sk_hit *)d_out, d_count))) return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(count, d_count, cb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
 int sk_map_hits_dev(int32_t handle, const int32_t *d_slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *d_out,
                     int32_t *d_count)
 {
@@ -3293,16 +3317,7 @@ int sk_map_hits(int32_t handle, const int32_t *slots, int32_t m, int32_t max_hit
     int32_t T = 0;
     if ((rc = sk_map_session_info(c, handle, nullptr, &T))) return rc;
     if (m == 0) return SK_OK;
-    if ((rc = sk_map_session_check_slots(c, handle, slots, m))) return rc;
-    const size_t ob = (size_t)m * (size_t)T * (size_t)max_hits * sizeof(sk_hit), cb = (size_t)m * (size_t)T * sizeof(int32_t);
-    void *d_out;
-    if ((rc = sk_map_session_stage(c, handle, 1, ob + cb, &d_out))) return rc;
-    int32_t *d_count = (int32_t *)((char *)d_out + ob);
-    if ((rc = sk_map_session_hits(c, handle, slots, m, max_hits, max_dist, (sk_hit *)d_out, d_count))) return rc;
-    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipMemcpyAsync(count, d_count, cb, hipMemcpyDeviceToHost, c->stream));
-    SK_HIP(hipStreamSynchronize(c->stream));
-    return SK_OK;
+    return map_hits_host(c, handle, T, slots, m, max_hits, max_dist, out, count);
 }
 
 int sk_map_close(int32_t handle)
@@ -3506,6 +3521,193 @@ int sk_last_evs_plan(int64_t *state_bytes, int64_t *staged_records, int64_t *gua
         }
         *guard_hits = (int64_t)g;
     }
+    return SK_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ live mapping sessions (sk_live.hip)
+// What the arguments alone decide is refused here, before a context is looked for, in the order of sk_evs_push_i16 /
+// sk_map_open; what needs the session (is the handle open, does a slot lie below its nslots, has it ended, does the
+// stride fit the mapping side's chunk limit) in sk_live.hip.
+namespace {
+
+int check_live_handle(int32_t handle)
+{
+    if (handle < 0 || handle >= SK_LIVE_MAX_SESSIONS)
+        return sk_fail(SK_ERR_INVALID, "live session handle %d is outside [0, %d)", handle, SK_LIVE_MAX_SESSIONS);
+    return SK_OK;
+}
+
+int check_live_push(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride, const int32_t *len,
+                    const sk_live_rule *rule, const void *out, const void *info, const void *best, bool host)
+{
+    if (int rc = check_live_handle(handle)) return rc;
+    const int64_t off_stands_in = 0;                        // (sk_evs_push's checks of off / rec / cap have nothing to find)
+    if (int rc = check_evs_push(0, slots, m, rows, stride, len, &off_stands_in, nullptr, 0, host)) return rc;
+    if (m > 0 && (!out || !info)) return sk_fail(SK_ERR_INVALID, "NULL out/info");
+    if (best && !rule) return sk_fail(SK_ERR_INVALID, "best without a rule");
+    if (rule && !best && m > 0) return sk_fail(SK_ERR_INVALID, "a rule without best");
+    if (rule) {
+        if (rule->max_dist_per_row != rule->max_dist_per_row || rule->min_margin != rule->min_margin)
+            return sk_fail(SK_ERR_INVALID, "rule: max_dist_per_row and min_margin must be numbers");
+        if (rule->give_up_rows < 1) return sk_fail(SK_ERR_INVALID, "rule: give_up_rows = %d is below 1", rule->give_up_rows);
+    }
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_live_open(const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off, int32_t ntargets,
+                 int32_t nslots, int32_t *handle)
+{
+    if (int rc = check_det_params(p)) return rc;
+    if (!handle) return sk_fail(SK_ERR_INVALID, "NULL handle");
+    if (calib < 2 || calib > SK_LIVE_MAX_CALIB)
+        return sk_fail(SK_ERR_INVALID, "calib = %d is outside 2 .. %d", calib, SK_LIVE_MAX_CALIB);
+    if (!targets || !target_off) return sk_fail(SK_ERR_INVALID, "NULL targets/target_off");
+    if (int rc = check_map_shape(target_off, ntargets, nslots)) return rc;
+    SK_ENTER(c);
+    return sk_live_session_open(c, p, calib, targets, target_off, ntargets, nslots, handle);
+}
+
+int sk_live_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
+                         const int32_t *d_len, const int32_t *d_end, const sk_live_rule *rule, sk_map_rec *d_out,
+                         sk_live_info *d_info, sk_live_best *d_best)
+{
+    int rc = check_live_push(handle, d_slots, m, d_rows, stride, d_len, rule, d_out, d_info, d_best, false);
+    if (rc) return rc;
+    SK_ENTER(c);
+    int32_t evs = -1;
+    if ((rc = sk_live_session_info(c, handle, nullptr, nullptr, &evs, nullptr))) return rc;
+    if (m == 0) return SK_OK;
+    std::vector<int32_t> slots((size_t)m);                  // the sweep is planned on the host: the slot numbers come back
+    SK_HIP(hipMemcpyAsync(slots.data(), d_slots, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = sk_live_session_check(c, handle, slots.data(), m, stride, nullptr))) return rc;
+    const int64_t per = sk_evs_session_rows(c, evs, stride);
+    return sk_live_session_push(c, handle, slots.data(), d_slots, m, d_rows, stride, d_len, d_end, per, nullptr, nullptr, rule,
+                                d_out, d_info, d_best);
+}
+
+int sk_live_push_i16(int32_t handle, const int32_t *slots, int32_t m, const int16_t *rows, int64_t stride, const int32_t *len,
+                     const int32_t *end, const sk_live_rule *rule, sk_map_rec *out, sk_live_info *info, sk_live_best *best)
+{
+    int rc = check_live_push(handle, slots, m, rows, stride, len, rule, out, info, best, true);
+    if (rc) return rc;
+    SK_ENTER(c);
+    int32_t evs = -1, T = 0;
+    if ((rc = sk_live_session_info(c, handle, nullptr, &T, &evs, nullptr))) return rc;
+    if (m == 0) return SK_OK;
+    if ((rc = sk_live_session_check(c, handle, slots, m, stride, len))) return rc;
+    SK_HIP(hipStreamSynchronize(c->stream));                // an earlier call may still read the staging buffers
+    int32_t maxlen = 0;
+    for (int32_t i = 0; i < m; i++) maxlen = len[i] > maxlen ? len[i] : maxlen;
+    // the rows go up as [m][w], w = maxlen rounded up to 8 samples, as in sk_evs_push_i16
+    const int64_t w = ((int64_t)maxlen + 7) / 8 * 8;
+    const size_t mm = (size_t)m;
+    const size_t ob = mm * (size_t)T * sizeof(sk_map_rec), ib = mm * sizeof(sk_live_info), bb = mm * sizeof(sk_live_best);
+    void *d_rows_v, *d_args_v, *d_out, *d_info, *d_best = nullptr;
+    if ((rc = sk_evs_session_stage(c, evs, 0, mm * (size_t)w * sizeof(int16_t), &d_rows_v))) return rc;
+    if ((rc = sk_evs_session_stage(c, evs, 1, 3 * mm * sizeof(int32_t), &d_args_v))) return rc;
+    if ((rc = sk_live_session_stage(c, handle, 0, ob, &d_out))) return rc;
+    if ((rc = sk_live_session_stage(c, handle, 1, ib, &d_info))) return rc;
+    if (rule && (rc = sk_live_session_stage(c, handle, 2, bb, &d_best))) return rc;
+    int16_t *d_rows = (int16_t *)d_rows_v;
+    int32_t *d_slots = (int32_t *)d_args_v, *d_len = d_slots + mm, *d_end = d_len + mm;
+    if (maxlen > 0)
+        SK_HIP(hipMemcpy2DAsync(d_rows, (size_t)w * sizeof(int16_t), rows, (size_t)stride * sizeof(int16_t),
+                                (size_t)maxlen * sizeof(int16_t), mm, hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipMemcpyAsync(d_slots, slots, mm * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    SK_HIP(hipMemcpyAsync(d_len, len, mm * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (end) SK_HIP(hipMemcpyAsync(d_end, end, mm * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    const int64_t per = sk_evs_session_rows(c, evs, maxlen);
+    if ((rc = sk_live_session_push(c, handle, slots, d_slots, m, d_rows, w, d_len, end ? d_end : nullptr, per, len, end, rule,
+                                   (sk_map_rec *)d_out, (sk_live_info *)d_info, (sk_live_best *)d_best)))
+        return rc;
+    SK_HIP(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipMemcpyAsync(info, d_info, ib, hipMemcpyDeviceToHost, c->stream));
+    if (rule) SK_HIP(hipMemcpyAsync(best, d_best, bb, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_live_fetch(int32_t handle, int64_t *off, double *values, int64_t cap)
+{
+    int rc = check_live_handle(handle);
+    if (rc) return rc;
+    if (!off) return sk_fail(SK_ERR_INVALID, "NULL off");
+    if (cap < 0) return sk_fail(SK_ERR_INVALID, "cap < 0");
+    if (cap > 0 && !values) return sk_fail(SK_ERR_INVALID, "NULL values with a cap");
+    SK_ENTER(c);
+    const int64_t *k_off = nullptr;
+    const double *k_values = nullptr;
+    int32_t m = 0;
+    if ((rc = sk_live_session_last(c, handle, &k_off, &k_values, &m))) return rc;
+    if (m == 0) return SK_OK;
+    SK_HIP(hipMemcpyAsync(off, k_off, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    const int64_t total = off[m];
+    if (total > cap)
+        return sk_fail(SK_ERR_OVERFLOW, "the last push made %lld normalised levels, cap is %lld", (long long)total, (long long)cap);
+    if (total == 0) return SK_OK;
+    SK_HIP(hipMemcpyAsync(values, k_values, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_live_hits(int32_t handle, const int32_t *slots, int32_t m, int32_t max_hits, double max_dist, sk_hit *out, int32_t *count)
+{
+    int rc = check_live_handle(handle);
+    if (rc) return rc;
+    if ((rc = check_map_hits(0, slots, m, max_hits, max_dist, out, count, true))) return rc;
+    SK_ENTER(c);
+    int32_t T = 0, map = -1;
+    if ((rc = sk_live_session_info(c, handle, nullptr, &T, nullptr, &map))) return rc;
+    if (m == 0) return SK_OK;
+    return map_hits_host(c, map, T, slots, m, max_hits, max_dist, out, count);
+}
+
+int sk_live_reset(int32_t handle, const int32_t *slots, int32_t m)
+{
+    int rc = check_live_handle(handle);
+    if (rc) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m && !slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
+    SK_ENTER(c);
+    if ((rc = sk_live_session_info(c, handle, nullptr, nullptr, nullptr, nullptr))) return rc;
+    return sk_live_session_reset(c, handle, slots, m);
+}
+
+int sk_live_close(int32_t handle)
+{
+    if (int rc = check_live_handle(handle)) return rc;
+    SK_ENTER(c);
+    return sk_live_session_close(c, handle);
+}
+
+int sk_live_last_ms(int32_t handle, float *bridge_ms, float *summary_ms)
+{
+    if (int rc = check_live_handle(handle)) return rc;
+    SK_ENTER(c);
+    float best = 0.f, prep = 0.f;
+    if (int rc = sk_live_session_best_ms(c, handle, &best)) return rc;
+    if (!c->ev_valid) return sk_fail(SK_ERR_INVALID, "no timed call yet");
+    SK_HIP(hipEventSynchronize(c->ev[3]));
+    SK_HIP(hipEventElapsedTime(&prep, c->ev[0], c->ev[1]));
+    if (bridge_ms) *bridge_ms = prep;
+    if (summary_ms) *summary_ms = best;
+    return SK_OK;
+}
+
+int sk_last_live_plan(int64_t *state_bytes, int64_t *bridged_levels, int64_t *launches)
+{
+    SK_ENTER(c);
+    if (state_bytes) *state_bytes = c->live_state_bytes;
+    if (bridged_levels) *bridged_levels = c->live_levels;
+    if (launches) *launches = c->live_launches;
     return SK_OK;
 }
 

@@ -234,6 +234,8 @@ struct sk_ctx {
     sk_buf hmmscnt;                   // ... [0] = slots their pushes met full since the context was set up (sk_last_hmms_plan)
     int64_t hmms_state_bytes = 0;     // the last push of one: bytes of slot state
     bool   hmms_valid = false;        // a push has been made on this context (the counter is meaningful)
+    void  *live_sessions[SK_LIVE_MAX_SESSIONS] = {};   // live mapping sessions of this context (sk_live.hip), by handle
+    int64_t live_state_bytes = 0, live_levels = 0, live_launches = 0;   // the last push of one (sk_last_live_plan)
     sk_buf commbuf;                   // staging for the small host-side exchanges
 };
 
@@ -657,6 +659,7 @@ int sk_evs_session_push(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32
                         const int32_t *host_len, const int32_t *host_end);
 int sk_evs_session_gather(sk_ctx *c, int32_t handle, sk_det_event *d_rec, int64_t cap);
 int sk_evs_session_last(sk_ctx *c, int32_t handle, const int64_t **d_off, int32_t *m);
+int sk_evs_session_staging(sk_ctx *c, int32_t handle, const sk_det_event **d_stage, int64_t *per);
 int sk_evs_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
 int sk_evs_session_close(sk_ctx *c, int32_t handle);
 void sk_evs_close_all(sk_ctx *c);           // sk_shutdown: the context's device is current
@@ -664,6 +667,27 @@ void sk_evs_close_all(sk_ctx *c);           // sk_shutdown: the context's device
 // ---- HMM sessions (sk_hmmstream.hip) ----
 // The kernel, the session and the sk_hmms_* entries are all in that file; the runtime only closes what is left open.
 void sk_hmms_close_all(sk_ctx *c);          // sk_shutdown: the context's device is current
+
+// ---- live mapping sessions (sk_live.hip) ----
+// The session behind sk_live_*: an event session and a mapping session of its own (opened and closed through the
+// functions above: one handle of each table while it is open), the bridge between them and the decision summary.
+// Arguments that need no session are checked in sk_api.hip.  push: host_slots checked by the caller's entry against
+// nothing but the ABI's limits -- the session checks them against nslots; every d_ pointer a device pointer; host_len /
+// host_end as in sk_evs_session_push (nullptr: a device-form push).  d_best is written only when rule is given.
+int sk_live_session_open(sk_ctx *c, const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off,
+                         int32_t ntargets, int32_t nslots, int32_t *handle);
+int sk_live_session_info(sk_ctx *c, int32_t handle, int32_t *nslots, int32_t *ntargets, int32_t *evs, int32_t *map);
+int sk_live_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, int64_t stride, const int32_t *len);
+int sk_live_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
+int sk_live_session_push(sk_ctx *c, int32_t handle, const int32_t *host_slots, const int32_t *d_slots, int32_t m,
+                         const int16_t *d_rows, int64_t stride, const int32_t *d_len, const int32_t *d_end, int64_t per,
+                         const int32_t *host_len, const int32_t *host_end, const sk_live_rule *rule, sk_map_rec *d_out,
+                         sk_live_info *d_info, sk_live_best *d_best);
+int sk_live_session_last(sk_ctx *c, int32_t handle, const int64_t **d_off, const double **d_values, int32_t *m);
+int sk_live_session_best_ms(sk_ctx *c, int32_t handle, float *ms);
+int sk_live_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
+int sk_live_session_close(sk_ctx *c, int32_t handle);
+void sk_live_close_all(sk_ctx *c);          // sk_shutdown, BEFORE the two tables it holds handles of are emptied
 
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries
 int64_t sk_scan_blocks(int64_t n);

@@ -519,6 +519,16 @@ int sk_evs_session_last(sk_ctx *c, int32_t handle, const int64_t **d_off, int32_
     return SK_OK;
 }
 
+// the last push's staging rows (device, [m][per]: entry k's new events are its first off[k + 1] - off[k] rows) and per
+int sk_evs_session_staging(sk_ctx *c, int32_t handle, const sk_det_event **d_stage, int64_t *per)
+{
+    evs_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    *d_stage = (const sk_det_event *)z->stage.p;
+    *per = z->pushed ? z->last_per : 0;
+    return SK_OK;
+}
+
 int sk_evs_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m)
 {
     evs_session *z = session_of(c, handle);

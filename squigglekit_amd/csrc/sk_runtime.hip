@@ -229,6 +229,7 @@ int sk_shutdown(void)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         sk_stream_close_all(c);
+        sk_live_close_all(c);
         sk_map_close_all(c);
         sk_evs_close_all(c);
         sk_hmms_close_all(c);

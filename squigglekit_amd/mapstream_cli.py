@@ -3,7 +3,7 @@
     squiggle_map_stream.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
                            [--piece N --overlap N] [--chunk E] [--calib C] [--channels S]
                            [--min_events N] [--max_dist_per_event X] [--min_margin X] [--give_up N]
-                           [--live [--sample_chunk N]] [--locus_margin [--hits K]]
+                           [--live [--sample_chunk N] [--fused]] [--locus_margin [--hits K]]
 
 Inputs and targets are squiggle_map's.  Without --live, events are cut ONCE per read, by api.detect_events on its first
 --prefix samples, and the replay is in event space: a read is dealt to a free channel (a slot of one api.MapStream over
@@ -15,6 +15,9 @@ a time through a slot of an api.EventStream, END with the last chunk; the events
 pushed to the api.MapStream slot of the same number, and api.map_decide runs after every such push.  --live needs
 --calib >= 2 (all events of the prefix are not knowable live): levels are held back until the read has --calib of them
 (or ends), then normalised with their mean and standard deviation, fixed from then on.  --chunk is not used.
+--live --fused: the same replay through ONE api.LiveMap: levels, hold-back, normalisation and the hand-over to the mapping
+side happen on the device, and so does the decision unless --piece or --locus_margin is given (merged records and hit
+lists are decided on the host, from the returned records and LiveMap.hits).  The output is --live's, byte for byte.
 
 --calib C: every level is normalised with the mean and the standard deviation of the read's first C event levels, fixed
 from then on; the read's first push then holds at least those C events.  C = 0 (the default) takes all events of the
@@ -70,6 +73,7 @@ def build_parser():
     p.add_argument("--batch", type=int, default=4096, help="reads per event-detection call")
     p.add_argument("--live", action="store_true", help="replay in sample space: cut events on the GPU as each read's samples arrive")
     p.add_argument("--sample_chunk", type=int, default=2000, help="--live: raw samples per push (default 2000)")
+    p.add_argument("--fused", action="store_true", help="--live: one live mapping session -- events, normalisation, mapping and the decision without a host round trip")
     p.add_argument("--locus_margin", action="store_true", help="accept on the margin to the next locus on any target (hit lists) instead of the next target")
     p.add_argument("--hits", type=int, default=2, help="--locus_margin: loci listed per read and target, 1 .. 64 (default 2)")
     return p
@@ -310,6 +314,88 @@ def replay_live(args, targets, reads, src, write):
         raise ValueError("event session: {} slots stopped at a guard".format(guard))
 
 
+def replay_fused(args, targets, reads, src, write):
+    """replay_live through one api.LiveMap: the samples go in, the records, the slots' states and (without --piece and
+    --locus_margin) the decisions come out; the same lines in the same order"""
+    ys = [t[2] for t in targets]
+    tiling = None
+    if args.piece > 0:
+        ys, tiling = api.tile_targets(ys, args.piece, args.overlap)
+    queue = deque(reads)
+    S, N = args.channels, args.sample_chunk
+    chan = [None] * S
+    params = api.det_params("rna" if args.rna else "dna")
+    rule = None
+    if tiling is None and not args.locus_margin:
+        rule = api.live_rule(args.min_events, args.max_dist_per_event, args.min_margin, args.give_up)
+
+    with api.LiveMap(params, args.calib, ys, S) as lm:
+        while True:
+            fresh = []
+            for s in range(S):
+                if chan[s] is None and queue:
+                    chan[s] = _LiveRead(*queue.popleft())
+                    chan[s].mapped = 0
+                    fresh.append(s)
+            if fresh:
+                lm.reset(fresh)
+            live = [s for s in range(S) if chan[s] is not None]
+            if not live:
+                break
+            chunks, end = [], []
+            for s in live:
+                r = chan[s]
+                chunks.append(r.samples[r.at:r.at + N])
+                r.at = min(len(r.samples), r.at + N)
+                r.ended = r.at >= len(r.samples)
+                end.append(r.ended)
+            res = lm.push(live, chunks, end=end, rule=rule)
+            rec, info = res[0], res[1]
+            # ---- the slots whose read cannot be normalised, then the ones that were handed levels (or ended)
+            idx = []
+            for i, s in enumerate(live):
+                r = chan[s]
+                state = int(info["state"][i])
+                if state == _lib.SK_LIVE_UNDECIDABLE:
+                    sys.stderr.write("squiggle_map_stream: {} in read {} of {}\n".format(
+                        "fewer than 2 events" if int(info["events"][i]) < 2 else "event levels without deviation", r.rid, src))
+                    write("{}\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t0\t0\n".format(r.rid))
+                    chan[s] = None
+                    continue
+                if state != _lib.SK_LIVE_MAPPING:
+                    continue                                        # held back
+                new, r.mapped = int(info["mapped"][i]) - r.mapped, int(info["mapped"][i])
+                if new == 0 and not r.ended:
+                    continue
+                idx.append(i)
+            if not idx:
+                continue
+            mslots = [live[i] for i in idx]
+            mrec = rec[:, idx]
+            hits = api.map_hits(mrec)
+            if tiling is not None:
+                hits = api.merge_tiles(hits, tiling)
+            if rule is not None:
+                dec = res[2]["decision"][idx]
+            else:
+                full = np.zeros(hits.shape, dtype=api.MAPREC_DTYPE)
+                for f in api.HIT_DTYPE.names:
+                    full[f] = hits[f]
+                full["rows"], full["pushes"] = mrec["rows"][:1], mrec["pushes"][:1]
+                dec = decide(args, lm, mslots, full, tiling)
+            for i, s in enumerate(mslots):
+                r = chan[s]
+                word = DECISIONS.get(int(dec[i])) or ("end" if r.ended else None)
+                if word is None:
+                    continue
+                line = map_lines([r.rid], [range(r.mapped)], hits[:, i:i + 1], targets)[0]
+                write("{}\t{}\t{}\t{}\n".format(line[:-1], word, int(mrec["pushes"][0, i]), r.mapped))
+                chan[s] = None
+    guard = api.last_event_plan()["guard_hits"]
+    if guard:
+        raise ValueError("event session: {} slots stopped at a guard".format(guard))
+
+
 def main(argv=None):
     parser = build_parser()
     argv = sys.argv[1:] if argv is None else argv
@@ -352,6 +438,10 @@ def main(argv=None):
             parser.error("--calib + --sample_chunk must be at most {}".format(_lib.SK_MAP_MAX_CHUNK))
         if args.channels > _lib.SK_EVS_MAX_SLOTS:
             parser.error("--channels must be in 1 .. {}".format(_lib.SK_EVS_MAX_SLOTS))
+        if args.fused and args.calib > _lib.SK_LIVE_MAX_CALIB:
+            parser.error("--fused: --calib must be at most {}".format(_lib.SK_LIVE_MAX_CALIB))
+    elif args.fused:
+        parser.error("--fused needs --live")
     try:
         targets = load_targets(args.model, args.both)
     except (ValueError, IndexError, OSError) as e:
@@ -363,7 +453,7 @@ def main(argv=None):
     sys.stdout.write("\t".join(HEADER) + "\n")
     try:
         if args.live:
-            replay_live(args, targets, read_samples(args, src), src, sys.stdout.write)
+            (replay_fused if args.fused else replay_live)(args, targets, read_samples(args, src), src, sys.stdout.write)
         else:
             replay(args, targets, read_levels(args, src), src, sys.stdout.write)
     except (ValueError, EOFError, OSError) as e:
