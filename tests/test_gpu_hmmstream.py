@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 NINF = -np.inf
 GRID = (1, 31, 32, 33, 127, 128, 129, 255, 257, 1000, None)             # chunk lengths of the cut grid; None: whole
+LAYOUTS = ((304, 0), (303, 2), (303, 0), (304, 2), (304, 8), (301, 6))   # device rows: (stride in samples, byte shift of the base)
 
 
 @pytest.fixture(autouse=True)
@@ -144,13 +145,14 @@ def test_two_sessions_open_at_once(gpu):
 
 
 def test_device_forms_give_the_bytes_of_the_host_forms(gpu):
-    """push_dev_* on device buffers: the reference's bytes and the host forms'.  The int16 rows alternate between an
-    aligned layout (stride 304, 16-byte loads) and an odd one (stride 303 from an odd sample offset: 2-byte loads); every
+    """push_dev_* on device buffers: the reference's bytes and the host forms'.  The int16 rows take LAYOUTS in turn: the
+    aligned one (stride 304, 16-byte loads), and odd strides and bases shifted by 2, 6 and 8 bytes (2-byte loads); every
     push carries two entries that name no slot of the session: their records are empty and nobody else is touched."""
     from squigglekit_amd import _lib, api
     L = _lib.load()
     rng = np.random.default_rng(10)
     S, M = 70, 72
+    ran = []
     model = api.polya_model("synth_raw")
     sess = HR.draw_session(rng, nslots=S, budget=100000, maxlen=300, draw_chunk=levels)
     want = HR.run_session(model, sess)
@@ -172,14 +174,14 @@ def test_device_forms_give_the_bytes_of_the_host_forms(gpu):
                 lens = np.array([len(c) for c in parts], dtype=np.int32)
                 up(d_slots, named)
                 if feed == "i16":
-                    odd = j % 2 == 1
-                    stride = 303 if odd else 304
+                    stride, shift = LAYOUTS[len(ran) % len(LAYOUTS)]
+                    ran.append((stride, shift))
                     rows = np.full((m, stride), -12345, dtype=np.int16)
                     for i, c in enumerate(parts):
                         rows[i, :len(c)] = c
-                    up(d_rows + (2 if odd else 0), rows)
+                    up(d_rows + shift, rows)
                     up(d_len, lens)
-                    _lib.check(L.sk_hmms_push_dev_i16(dev.handle, d_slots, m, d_rows + (2 if odd else 0), stride, d_len, d_out))
+                    _lib.check(L.sk_hmms_push_dev_i16(dev.handle, d_slots, m, d_rows + shift, stride, d_len, d_out))
                 else:
                     off = np.zeros(m + 1, dtype=np.int64)
                     off[1:] = np.cumsum(lens)
@@ -197,7 +199,7 @@ def test_device_forms_give_the_bytes_of_the_host_forms(gpu):
                 assert h.tobytes() == inside.tobytes(), j
                 j += 1
             feeds = [op[3] for op in sess["ops"] if op[0] == "push"]
-            assert {"f64"} < set(feeds) and {j % 2 for j, f in enumerate(feeds) if f == "i16"} == {0, 1}   # both layouts ran
+            assert {"f64"} < set(feeds) and set(ran) == set(LAYOUTS)     # every layout ran
             # the host form after device-form pushes knows how far every slot has come
             assert dev.peek(np.arange(S)).tobytes() == want[-1].tobytes()
     finally:
