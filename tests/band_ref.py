@@ -222,6 +222,14 @@ def records(seqs, pairs, W, end, trace=True):
     return rec, off, (np.concatenate(parts) if parts else np.zeros((0, 2), dtype=np.int32)), lost
 
 
+def mismatches(seqs, pairs, off, spans):
+    """the pairs sk_last_path_mismatches() counts after a call with paths, from what `records` returned: a target of at
+    least one point and spans of -1 -- the band lost the corner, or the walk left the band or the matrix.  (A path has
+    a_0 = 0, so the first row tells; a pair without rows -- an empty query, which the library refuses -- is not counted.)"""
+    return sum(1 for p, (q, t) in enumerate(pairs)
+               if len(seqs[t]) > 0 and off[p] < off[p + 1] and spans[off[p], 0] == -1)
+
+
 def check_invariants(sp, end):
     """a_i <= b_i, a_{i+1} is b_i or b_i + 1, a_0 = 0, b_{N-1} = end"""
     sp = np.asarray(sp)
@@ -247,3 +255,30 @@ def drift_pair(rng, M=400, p=0.55, noise=0.3, stall=120, extra=0):
     if extra:
         y = np.concatenate([y, rng.normal(size=extra)])
     return x, y
+
+
+# the non-finite kinds the band tests lay into a pair (the header: "equal, both +inf, a NaN" move the band by parity; a
+# NaN never wins a `<`, so it is never the free end; an inf in a row or a column costs +inf along it)
+NONFINITE = ("nan in a query", "+inf in a query", "-inf in a query", "nan in a target", "+inf in a target",
+             "-inf in a target", "nan at x[0]", "nan in the target's last point", "nan in 20 % of a target")
+
+
+def lay_non_finite(rng, x, y, kind):
+    """(x, y) with one kind of NONFINITE laid into a copy of the query or of the target (one of the two is returned as
+    it came)"""
+    query = "query" in kind or "x[0]" in kind
+    v = np.array(x if query else y, dtype=np.float64)
+    if v.size:
+        bad = np.nan if "nan" in kind else (-np.inf if "-inf" in kind else np.inf)
+        if "x[0]" in kind:
+            v[0] = bad
+        elif "last point" in kind:
+            v[-1] = bad
+        elif "20 %" in kind:
+            mask = rng.random(v.size) < 0.2
+            if not mask.any():                                  # (a short target: one point at least)
+                mask[int(rng.integers(v.size))] = True
+            v[mask] = bad
+        else:
+            v[int(rng.integers(v.size))] = bad
+    return (v, y) if query else (x, v)

@@ -1,8 +1,8 @@
 """Seeded random cases for the kernel files that have no other randomised test in the suite -- csrc/sk_sweep.hip,
 sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, through the twins of the
 hit family sk_bg.hip and sk_events.hip, for the switches of the screening scheme sk_sdtwq.hip, and for both branches of the
-dRNA segmenter (sk_drna_walk.hip and the dRNA kernels of sk_prep.hip), and for DTW over a pair list with its warping paths
-(sk_pairs.hip, sk_pairpath.hip): per family
+dRNA segmenter (sk_drna_walk.hip and the dRNA kernels of sk_prep.hip), for DTW over a pair list with its warping paths
+(sk_pairs.hip, sk_pairpath.hip), and for the adaptive-band DTW (sk_band.hip): per family
 draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
 what the reference says,  call_<family>(api, case, exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or
 the first difference as text.
@@ -10,16 +10,17 @@ the first difference as text.
 A plain module: not collected, no conftest, pure numpy, no GPU import at module level (`api` is handed in).  The same
 seed gives the same case on any machine: draw_* take a numpy.random.Generator and nothing else.  Used by
 tests/test_random_cases.py (CPU: the committed seeds reach what they claim), tests/test_gpu_random.py (GPU: every seed
-against its reference, plus four interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
+against its reference, plus five interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
 families is DRAW[family] with its running generator).  tests/RANDOM_CASES.md says what each family draws, the
-references, the budgets, the wall times, and which one-line kernel mutants the committed seeds catch.
+references, the budgets, the wall times, and which one-line kernel mutants the committed seeds catch
+(tests/RANDOM_CASES_BAND.md for the band family).
 
 The references are the statements that already exist: the oracle's scale_outliers + get_segs per (set, read) for the
 sweep, reference_hits (test_hits_host.py), reference_paths (test_paths_host.py), numpy_pull_text (test_squigglepull.py),
 reference_panel (test_panel_host.py), detect_ref.py, hmm_ref.py, hmm_path_ref.py, plain numpy on the oracle's segments
 for the levels, reference_background_reads (test_background_host.py), reference_batch / reference_pool
 (test_events_host.py), the oracle's scale_outliers + drna_segs / drna_roll per read for the dRNA branches,
-pairs_ref.records and pair_paths_ref.list_spans for the pair lists.  Every comparison
+pairs_ref.records and pair_paths_ref.list_spans for the pair lists, band_ref.records for the band.  Every comparison
 is exact: integers as integers, doubles and text byte for byte.
 """
 import os
@@ -47,6 +48,7 @@ SEEDS = {
     "roll": [0, 1, 2, 3, 4, 10, 11, 13, 16, 21, 23, 24, 29, 31, 59],
     "pairs": [4, 5, 7, 9, 23, 54, 119, 130, 133],
     "pairpaths": [1, 5, 6, 7, 13, 17, 21, 22, 23, 36, 50, 145],
+    "band": [27, 29, 44, 54, 61, 70, 75, 112, 138, 195, 238, 240, 297, 299, 331, 351, 423, 458],
 }
 
 # every tuning switch a case may set; a runner clears the ones a case does not name
@@ -54,14 +56,14 @@ SWITCHES = ("SK_SEG_DELTA_SCALE", "SK_WALK_GENERAL", "SK_DTW_SMALL_MAX", "SK_HIT
             "SK_PATH_SCRATCH_BYTES", "SK_DTW_NO_SMALL", "SK_PANEL_EXACT", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB",
             "SK_DTW_QL", "SK_DTW_HINT_MIN", "SK_DTW_NOHINT", "SK_DTW_CK", "SK_DTW_SORT_MIN", "SK_DTW_SCRATCH_MB",
             "SK_DTW_NOFUSE", "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY", "SK_DRNA_STEP", "SK_ROLL_ONE_LOOK",
-            "SK_ROLL_DELTA_SCALE", "SK_ROLL_TWO_KERNELS")
+            "SK_ROLL_DELTA_SCALE", "SK_ROLL_TWO_KERNELS", "SK_BAND_WAVES")
 
 
 # the family's number in the seed of its generator.  Frozen: the first four are what sorted(SEEDS).index(family) gave when
 # the table held four keys, so those cases stay what they were (tests/test_random_cases.py pins their digests); a new
 # family takes the next free number, whatever its name.
 FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8, drna=9, roll=10,
-                    pairs=11, pairpaths=12)
+                    pairs=11, pairpaths=12, band=13)
 
 
 def rng_of(family, seed):
@@ -2671,6 +2673,209 @@ def diff_pairpaths(case, got, exp):
 
 
 # ======================================================================================================================
+# adaptive-band DTW over a pair list (sk_band.hip: k_band<K, PATHS>, K = W / 64)
+# ======================================================================================================================
+# lengths: the first points of a sequence, the half band h = W / 2 (cell (0, 0) sits at offset h: up to h points every cell
+# is in its band), the 64-sample stream blocks and their refills (63 .. 129), the widest band and its neighbours
+BAND_EDGES = (1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257)
+BAND_LONG = 4000                                 # uniform draws reach this length: 7 999 anti-diagonals in one pair
+BAND_STEPS = 24_000                              # anti-diagonals the statement sweeps per case (see RANDOM_CASES_BAND.md)
+BAND_POOL = 24
+BAND_LIST = 40
+BAND_FORMS = ("list", "flat", "device")
+BAND_WAVES = (None, "1", "3", "7")               # SK_BAND_WAVES: the wavefronts of the launch, at most
+BAND_KINDS = ("ties", "normal", "drift", "stall", "const", "ramps")
+BAND_GUARD = 256                                 # bytes behind each output of the device form
+
+
+def band_edges(W):
+    return tuple(sorted(set(BAND_EDGES + (W // 2 - 1, W // 2, W // 2 + 1))))
+
+
+def _band_len(rng, W):
+    u = rng.random()
+    if u < 0.5:
+        return int(_pick(rng, band_edges(W)))
+    return int(rng.integers(1, 401)) if u < 0.8 else int(rng.integers(1, BAND_LONG + 1))
+
+
+def _band_unit(rng, kind, W):
+    """one (query, target) of a kind of BAND_KINDS"""
+    import band_ref
+    if kind in ("drift", "stall"):
+        return band_ref.drift_pair(rng, int(rng.integers(8, 1500)), float(rng.uniform(0.3, 0.7)), float(rng.uniform(0.1, 0.6)),
+                                   int(_pick(rng, (40, 120))) if kind == "stall" else 0,
+                                   int(_pick(rng, (40, 150))) if kind == "stall" else 0)
+    N, M = _band_len(rng, W), _band_len(rng, W)
+    if kind == "ties":
+        return band_ref.ties(rng, N), band_ref.ties(rng, M)
+    if kind == "const":                          # every move decision is a tie: parity alone steers the band
+        v = float(_pick(rng, (0.0, 1.5, -2.0)))
+        return np.full(N, v), np.full(M, v if rng.random() < 0.7 else v + 1.0)
+    if kind == "ramps":                          # opposed monotone ramps
+        return np.linspace(-1.0, 1.0, N), np.linspace(1.0, -1.0, M)
+    return rng.normal(size=N), rng.normal(size=M)
+
+
+def band_steps(N, M):
+    return N + M - 1 if M else 0
+
+
+def draw_band(rng):
+    """A pool and a pair list for api.dtw_band: what the fuzz tool's former band leg drew (lengths up to BAND_LONG, forced
+    wavefront counts, the records-only call) and more -- the call shape (W, end, with or without paths, the pool as a list,
+    as (values, off) with off[0] > 0, or resident on the device), a pool of at most BAND_POOL sequences built from 1 .. 8
+    (query, target) units of BAND_KINDS, a list of at most BAND_LIST entries over it (every unit, then drawn (q, t) over
+    the whole pool, so a sequence is query here and target there; (i, i) pairs, a pair repeated verbatim, sometimes an
+    empty target), cut to BAND_STEPS anti-diagonals over its distinct pairs and shuffled; and in a quarter of the cases
+    one non-finite kind of band_ref.NONFINITE laid into a sequence of a listed pair."""
+    import band_ref
+    W = int(_pick(rng, band_ref.WIDTHS))
+    end = _pick(rng, band_ref.ENDS)
+    paths = bool(rng.random() < 0.6)
+    form = _pick(rng, BAND_FORMS)
+    waves = _pick(rng, BAND_WAVES)
+    nunits = int(rng.integers(1, 9))
+    kinds = [_pick(rng, BAND_KINDS) for _ in range(nunits)]
+    seqs, pairs = [], []
+    for kind in kinds:
+        x, y = _band_unit(rng, kind, W)
+        pairs.append((len(seqs), len(seqs) + 1))
+        seqs += [x, y]
+    nlive = len(seqs)                            # (every sequence so far can be a query)
+    if rng.random() < 0.4:
+        seqs.append(np.zeros(0))
+        pairs.append((int(rng.integers(nlive)), len(seqs) - 1))
+    for n in [_band_len(rng, W) for _ in range(int(rng.integers(0, BAND_POOL - len(seqs) + 1)) // 3)]:
+        seqs.append(rng.normal(size=n) if rng.random() < 0.5 else np.rint(rng.normal(size=n) * 2))
+    live = [k for k, s in enumerate(seqs) if len(s)]
+    extra = int(rng.integers(0, BAND_LIST - len(pairs) + 1)) if rng.random() < 0.7 else 0
+    pairs += list(zip(rng.choice(live, size=extra).tolist(), rng.integers(0, len(seqs), size=extra).tolist()))
+    if rng.random() < 0.6:
+        pairs += [(q, q) for q in rng.choice(live, size=int(rng.integers(1, 3))).tolist()]
+    if rng.random() < 0.6:
+        pairs.insert(int(rng.integers(len(pairs) + 1)), pairs[int(rng.integers(len(pairs)))])
+    keep, seen, total = [], set(), 0             # the statement's CPU time: a pair that would pass the budget is left out
+    for q, t in pairs[:BAND_LIST]:
+        c = 0 if (q, t) in seen else band_steps(len(seqs[q]), len(seqs[t]))
+        if keep and total + c > BAND_STEPS:
+            continue
+        keep.append((int(q), int(t)))
+        seen.add((q, t))
+        total += c
+    pairs = [keep[int(i)] for i in rng.permutation(len(keep))]
+    nonfinite = None
+    if rng.random() < 0.25:
+        nonfinite = _pick(rng, band_ref.NONFINITE)
+        where = [(q, t) for q, t in pairs if len(seqs[t])] or pairs
+        q, t = where[int(rng.integers(len(where)))]
+        x, y = band_ref.lay_non_finite(rng, seqs[q], seqs[t], nonfinite)
+        if x is not seqs[q]:
+            seqs[q] = x
+        else:
+            seqs[t] = y
+    env = {} if waves is None else {"SK_BAND_WAVES": waves}
+    return dict(family="band", W=W, end=end, paths=paths, form=form, pad=int(rng.integers(1, 9)) if form != "list" else 0,
+                kinds="".join(k[0] for k in kinds), nonfinite=nonfinite, nseq=len(seqs), npairs=len(pairs), steps=total,
+                longest=max(band_steps(len(seqs[q]), len(seqs[t])) for q, t in pairs), seqs=seqs,
+                pairs=np.array(pairs, dtype=np.int64).reshape(-1, 2), env=env)
+
+
+def expect_band(ora, case):
+    """dict(records, off, spans by band_ref.records; lost: pairs whose band lost the corner; mismatches: pairs with a
+    target and without a path, failed walks included -- what a call with paths must count)"""
+    import band_ref
+    pairs = case["pairs"].tolist()
+    rec, off, spans, lost = band_ref.records(case["seqs"], pairs, case["W"], case["end"])
+    return dict(records=rec, off=off, spans=spans, lost=lost, mismatches=band_ref.mismatches(case["seqs"], pairs, off, spans))
+
+
+def band_device_call(api, case, with_spans, nspans):
+    """sk_dtw_band_dev on device buffers, the pool behind case['pad'] NaN: (records, spans [nspans, 2] or None, the
+    mismatches counted, whether the bytes behind both outputs are still what was laid there)"""
+    from squigglekit_amd import _lib
+    L = _lib.ensure_init()
+    values, off = pairs_pool_of(case)
+    pr = api._as_pairs(case["pairs"])
+    outs = [np.full(len(pr) * api.HIT_DTYPE.itemsize + BAND_GUARD, 0x5A, dtype=np.uint8),
+            np.full(nspans * 8 + BAND_GUARD, 0x5A, dtype=np.uint8)]
+    ptrs = []
+    try:
+        for a in [values if values.size else np.zeros(1)] + outs:
+            ptrs.append(L.sk_dev_alloc(max(a.nbytes, 8)))
+            _lib.check(L.sk_dev_upload(ptrs[-1], _lib.ptr(a), a.nbytes))
+        _lib.check(L.sk_dtw_band_dev(ptrs[0], _lib.ptr(off), off.size - 1, _lib.ptr(pr), len(pr), case["W"],
+                                     api.BAND_ENDS[case["end"]], ptrs[1], ptrs[2] if with_spans else None))
+        _lib.check(L.sk_sync())
+        for a, d in zip(outs, ptrs[1:]):
+            _lib.check(L.sk_dev_download(_lib.ptr(a), d, a.nbytes))
+    finally:
+        for d in ptrs:
+            L.sk_dev_free(d)
+    rec = outs[0][:-BAND_GUARD].view(api.HIT_DTYPE).copy()
+    spans = outs[1][:-BAND_GUARD].view(np.int32).reshape(-1, 2).copy()
+    clean = bool(np.all(outs[0][-BAND_GUARD:] == 0x5A) and np.all(outs[1][-BAND_GUARD:] == 0x5A))
+    if not with_spans:
+        clean = clean and bool(np.all(outs[1] == 0x5A))
+    return rec, (spans if with_spans else None), (int(L.sk_last_path_mismatches()) if with_spans else None), clean
+
+
+def call_band(api, case, exp):
+    """(records, span_off, spans, mismatches counted, api.last_band_plan(), clean) of the case's own call: span_off, spans
+    and the count are None without paths; clean: nothing written behind an output of the device form"""
+    if case["form"] == "device":
+        rec, spans, counted, clean = band_device_call(api, case, case["paths"], int(exp["off"][-1]))
+        return rec, exp["off"] if case["paths"] else None, spans, counted, api.last_band_plan(), clean
+    got = api.dtw_band(pairs_pool_of(case), case["pairs"], case["W"], case["end"], paths=case["paths"])
+    if not case["paths"]:
+        return got, None, None, None, api.last_band_plan(), True
+    return got[0], got[1], got[2], api.last_path_mismatches(), api.last_band_plan(), True
+
+
+def band_slab_bytes(steps, W):
+    """include/squigglekit_hip.h: one wavefront's slab for a longest pair of `steps` anti-diagonals"""
+    return -(-steps * W // 1024) * 256 + -(-steps // 64) * 8 + 8
+
+
+def diff_band(case, got, exp):
+    import pairs_ref
+    rec, off, spans, counted, plan, clean = got
+    want = exp["records"]
+    if rec.shape != want.shape:
+        return "records shaped %s, want %s" % (rec.shape, want.shape)
+    seqs, pairs = case["seqs"], case["pairs"]
+    for p in range(len(want)):                                  # every pair, by the rule of pairs_ref.same_records
+        if not pairs_ref.same_records(rec[p:p + 1], want[p:p + 1].astype(rec.dtype)):
+            q, t = pairs[p]
+            return "pair %d (%d, %d) (N=%d, M=%d): got %s want %s" % (p, q, t, len(seqs[q]), len(seqs[t]), rec[p], want[p])
+    if not clean:
+        return "bytes written behind an output of the device form"
+    steps = case["longest"]
+    slab, waves, steps_max = plan
+    if steps_max != steps or slab != (band_slab_bytes(max(steps, 1), case["W"]) if case["paths"] else 0):
+        return "plan (slab bytes, wavefronts, steps) %s for a longest pair of %d anti-diagonals" % (plan, steps)
+    forced = case["env"].get("SK_BAND_WAVES")
+    if not 1 <= waves <= min(case["npairs"], int(forced) if forced else case["npairs"]):
+        return "%d wavefronts for %d pairs under SK_BAND_WAVES=%s" % (waves, case["npairs"], forced)
+    if not case["paths"]:
+        return None
+    if off.dtype != np.int64 or not np.array_equal(off, exp["off"]):
+        return "span_off %s want %s" % (off.tolist()[:8], exp["off"].tolist()[:8])
+    if spans.dtype != np.int32 or spans.shape != exp["spans"].shape:
+        return "spans %s %s, want int32 %s" % (spans.dtype, spans.shape, exp["spans"].shape)
+    for p in range(len(want)):                                  # every pair
+        a, b = int(off[p]), int(off[p + 1])
+        if not np.array_equal(spans[a:b], exp["spans"][a:b]):
+            i = int(np.flatnonzero((spans[a:b] != exp["spans"][a:b]).any(axis=1))[0])
+            return "pair %d %s (record %s): spans differ from row %d: got %s want %s" % (
+                p, pairs[p].tolist(), want[p], i, spans[a + i:a + i + 3].tolist(), exp["spans"][a + i:a + i + 3].tolist())
+    if counted != exp["mismatches"]:
+        return "%s pairs counted without a path, want %d (%d of them lost the corner)" % (counted, exp["mismatches"],
+                                                                                         exp["lost"])
+    return None
+
+
+# ======================================================================================================================
 # the older single-set calls, for the interleaved sequence only
 # ======================================================================================================================
 def draw_plain(rng, kind):
@@ -2748,19 +2953,19 @@ def result_bytes(got):
 
 DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull, panel=draw_panel, detect=draw_detect,
             hmm=draw_hmm, levels=draw_levels, screen=draw_screen, drna=draw_drna, roll=draw_roll, pairs=draw_pairs,
-            pairpaths=draw_pairpaths)
+            pairpaths=draw_pairpaths, band=draw_band)
 EXPECT = dict(sweep=expect_sweep, hits=expect_hits, paths=expect_paths, pull=expect_pull, segment=expect_plain,
               motifseq=expect_plain, pa=expect_plain, panel=expect_panel, detect=expect_detect, hmm=expect_hmm,
               levels=expect_levels, background=expect_background, events=expect_events, screen=expect_screen,
-              drna=expect_drna, roll=expect_roll, pairs=expect_pairs, pairpaths=expect_pairpaths)
+              drna=expect_drna, roll=expect_roll, pairs=expect_pairs, pairpaths=expect_pairpaths, band=expect_band)
 CALL = dict(sweep=call_sweep, hits=call_hits, paths=call_paths, pull=call_pull, segment=call_plain, motifseq=call_plain,
             pa=call_plain, panel=call_panel, detect=call_detect, hmm=call_hmm, levels=call_levels,
             background=call_background, events=call_events, screen=call_screen, drna=call_drna, roll=call_roll,
-            pairs=call_pairs, pairpaths=call_pairpaths)
+            pairs=call_pairs, pairpaths=call_pairpaths, band=call_band)
 DIFF = dict(sweep=diff_sweep, hits=diff_hits, paths=diff_paths, pull=diff_pull, segment=diff_plain, motifseq=diff_plain,
             pa=diff_plain, panel=diff_panel, detect=diff_detect, hmm=diff_hmm, levels=diff_levels,
             background=diff_background, events=diff_events, screen=diff_screen, drna=diff_drna, roll=diff_roll,
-            pairs=diff_pairs, pairpaths=diff_pairpaths)
+            pairs=diff_pairs, pairpaths=diff_pairpaths, band=diff_band)
 TWIN_OF = dict(background="hits", events="paths")
 
 # ---- the interleaved sequence (tests/test_gpu_random.py::test_interleaved_calls_share_the_context_buffers) --------
@@ -2802,6 +3007,16 @@ INTERLEAVE4 = [("pairs", 9), ("paths", 12), ("pairpaths", 145), ("paths", 1), ("
                ("pairpaths", 13), ("paths", 187), ("pairpaths", 1), ("screen", 337), ("pairs", 9), ("events", 12),
                ("pairpaths", 17), ("hits", 324), ("pairs", 130), ("screen", 268), ("pairpaths", 22), ("segment", 0),
                ("pairs", 5), ("paths", 1), ("pairpaths", 36)]
+
+
+# the fifth sequence: band lists between pair lists, their warping paths and hit lists.  sk_band_run counts into c->pathcnt
+# through sk_path_begin, as sk_pairpath.hip and sk_path.hip do, and keeps a table and slabs of its own that only grow:
+# pairpaths 13 (four mismatches counted) directly before band 54 (none), band 331 (one walk that fails) and band 27
+# (three lost pairs) directly before pairpaths 7 and pairs 130 (none), the widest slabs (band 44: 256 cells, 4 875
+# anti-diagonals) before a list of one pair of 205 (band 351) and again after it, cases that come twice
+INTERLEAVE5 = [("band", 44), ("pairpaths", 13), ("band", 54), ("hits", 1), ("band", 351), ("pairs", 130), ("band", 331),
+               ("pairpaths", 7), ("band", 297), ("hits", 324), ("band", 44), ("pairs", 5), ("band", 27), ("pairs", 130),
+               ("band", 75), ("pairpaths", 13), ("band", 351), ("hits", 1), ("band", 331)]
 
 
 def interleave_case(family, seed):

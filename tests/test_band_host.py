@@ -110,3 +110,30 @@ def test_empty_target_and_record_shape():
     rec, off, spans, lost = br.records([np.ones(5), np.zeros(0), np.arange(7.0)], [(0, 1), (0, 2), (2, 0), (0, 2)], 64, "pinned")
     assert off.tolist() == [0, 5, 10, 17, 22] and spans.shape == (22, 2) and lost == 0
     assert rec["flags"].tolist() == [1, 0, 0, 0] and rec[1] == rec[3]
+
+
+def test_mismatches_counts_lost_corners_and_failed_walks_but_no_empty_target():
+    """what a call with paths must count: an inf in the query loses the corner; an empty target has no path and is not
+    counted; `records` goes on returning the lost pairs alone"""
+    rng = np.random.default_rng(6)
+    x = br.ties(rng, 90)
+    seqs = [x, br.ties(rng, 80), np.zeros(0), br.lay_non_finite(rng, x, x, "+inf in a query")[0]]
+    pairs = [(0, 1), (0, 2), (3, 1), (3, 1), (1, 0)]
+    rec, off, spans, lost = br.records(seqs, pairs, 64, "pinned")
+    assert lost == 2 and rec["flags"].tolist() == [0, br.FLAG_EMPTY, br.FLAG_BAND_LOST, br.FLAG_BAND_LOST, 0]
+    assert br.mismatches(seqs, pairs, off, spans) == 2
+    spans[off[4]:off[5]] = -1                                       # a walk that failed: counted, though not lost
+    assert br.mismatches(seqs, pairs, off, spans) == 3
+    assert np.isinf(seqs[3]).sum() == 1 and np.isfinite(x).all()    # lay_non_finite works on a copy
+
+
+def test_every_non_finite_kind_lays_a_value_even_into_one_point():
+    rng = np.random.default_rng(7)
+    for kind in br.NONFINITE:
+        for _ in range(20):
+            x, y = br.lay_non_finite(rng, np.zeros(1), np.zeros(1), kind)
+            assert np.isfinite(x).all() != np.isfinite(y).all(), kind
+    # a pair without rows has no first row to look at: not counted, and the next pair's rows are not read for it
+    off = np.array([0, 0, 3], dtype=np.int64)
+    spans = np.full((3, 2), -1, dtype=np.int32)
+    assert br.mismatches([np.zeros(0), np.zeros(3)], [(0, 1), (1, 1)], off, spans) == 1

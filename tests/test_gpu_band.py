@@ -1,6 +1,9 @@
 """GPU: adaptive-band DTW over a pair list (sk_dtw_band, sk_band.hip) against the statement in tests/band_ref.py, which
-never is the code under test.  Every comparison: the records bit for bit, the spans equal as integers, no mismatch
-counted.  Equality with the full matrix is asserted only where every cell lies in its band (N, M <= W / 2)."""
+never is the code under test.  Every comparison: the records bit for bit, the spans equal as integers, the mismatches
+counted those of the statement -- none for finite inputs, the pairs without a path where an inf or a NaN makes some.
+Equality with the full matrix is asserted only where every cell lies in its band (N, M <= W / 2)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -171,22 +174,22 @@ def test_device_resident_form_equals_the_host_form(gpu, mixed):
     pad = np.concatenate([np.full(7, np.nan), values])                # the pool need not start at off = 0
     off7 = off + 7
     pr = api._as_pairs(pairs)
-    for end in ENDS:
-        rec, span_off, spans = api.dtw_band(seqs, pairs, 128, end)
-        rec7, _, spans7 = api.dtw_band((pad, off7), pr, 128, end)
+    for W, end in [(W, end) for W in WIDTHS for end in ENDS]:
+        rec, span_off, spans = api.dtw_band(seqs, pairs, W, end)
+        rec7, _, spans7 = api.dtw_band((pad, off7), pr, W, end)
         assert rec7.tobytes() == rec.tobytes() and spans7.tobytes() == spans.tobytes()
         d_val, d_rec, d_sp = L.sk_dev_alloc(pad.nbytes), L.sk_dev_alloc(len(pr) * 24), L.sk_dev_alloc(spans.nbytes)
         try:
             gpu.check(L.sk_dev_upload(d_val, gpu.ptr(pad), pad.nbytes))
             for with_spans in (True, False):
-                gpu.check(L.sk_dtw_band_dev(d_val, gpu.ptr(off7), off7.size - 1, gpu.ptr(pr), len(pr), 128,
+                gpu.check(L.sk_dtw_band_dev(d_val, gpu.ptr(off7), off7.size - 1, gpu.ptr(pr), len(pr), W,
                                             api.BAND_ENDS[end], d_rec, d_sp if with_spans else None))
                 gpu.check(L.sk_sync())
                 dev_rec = np.zeros(len(pr), dtype=gpu.HIT_DTYPE)
                 dev_sp = np.zeros_like(spans)
                 gpu.check(L.sk_dev_download(gpu.ptr(dev_rec), d_rec, dev_rec.nbytes))
                 gpu.check(L.sk_dev_download(gpu.ptr(dev_sp), d_sp, dev_sp.nbytes))
-                assert dev_rec.tobytes() == rec.tobytes() and dev_sp.tobytes() == spans.tobytes(), (end, with_spans)
+                assert dev_rec.tobytes() == rec.tobytes() and dev_sp.tobytes() == spans.tobytes(), (W, end, with_spans)
             assert L.sk_last_path_mismatches() == 0
         finally:
             L.sk_dev_free(d_val)
@@ -228,3 +231,142 @@ def test_seeded_random_pairs(gpu, end):
         got, mism = run(seqs, pairs, W, end)
         assert mism == want[3]
         check(got, want, (call, W, end))
+
+
+# ---- lists longer than the launch ------------------------------------------------------------------------------------
+LAUNCH_PAIRS, LAUNCH_ENTRIES = 240, 20000
+
+
+@functools.lru_cache(maxsize=None)
+def launch_pairs(W):
+    """(seqs, pairs, {end: (records, spans per pair, pairs without a path)}): LAUNCH_PAIRS distinct pairs, N and M in
+    [1, 200] with the edge lengths among them, every third pair tie-heavy, every twentieth lost by an inf in its query"""
+    rng = np.random.default_rng(18 + W)
+    edges = [n for n in (1, 2, 3, W // 2 - 1, W // 2, W // 2 + 1, 63, 64, 65, 127, 128, 129, 199, 200) if n <= 200]
+    seqs, pairs = [], []
+    for k in range(LAUNCH_PAIRS):
+        N, M = (int(rng.choice(edges)) if rng.random() < 0.3 else int(rng.integers(1, 201)) for _ in range(2))
+        x, y = pairs_ref.draw(rng, N, k % 3 == 0), pairs_ref.draw(rng, M, k % 3 == 0)
+        if k % 20 == 7:
+            x, y = br.lay_non_finite(rng, x, y, "+inf in a query")
+        pairs.append((len(seqs), len(seqs) + 1))
+        seqs += [x, y]
+    want = {}
+    for end in ENDS:
+        rec, off, spans, lost = br.records(seqs, pairs, W, end)
+        parts = [spans[off[p]:off[p + 1]] for p in range(LAUNCH_PAIRS)]
+        nopath = np.array([sp[0, 0] == -1 for sp in parts])
+        assert lost == LAUNCH_PAIRS // 20 <= br.mismatches(seqs, pairs, off, spans) == nopath.sum()
+        want[end] = (rec, parts, nopath)
+    return seqs, pairs, want
+
+
+def launch_index(W, n):
+    """n list entries over the distinct pairs, every pair at least once"""
+    rng = np.random.default_rng(180 + W)
+    return rng.permutation(np.concatenate([np.arange(LAUNCH_PAIRS), rng.integers(0, LAUNCH_PAIRS, size=n - LAUNCH_PAIRS)]))
+
+
+@pytest.mark.parametrize("W", WIDTHS)
+def test_lists_longer_than_the_launch(gpu, W):
+    """20 000 entries under the launch the library chooses (at most 32 wavefronts per CU: 8 192 on 256 CUs): every
+    wavefront strides to a second pair and further, takes its slab from a longer pair to a shorter one, and adds to the
+    one mismatch counter.  The expectations are the 240 distinct pairs' by index."""
+    from squigglekit_amd import api
+    seqs, pairs, want = launch_pairs(W)
+    n = LAUNCH_ENTRIES
+    for end in ENDS + ("records only",):
+        while True:
+            idx = launch_index(W, n)
+            listed = [pairs[i] for i in idx]
+            got = api.dtw_band(seqs, listed, W, "pinned" if end == "records only" else end, paths=end != "records only")
+            waves = api.last_band_plan()[1]
+            if 2 * waves < n or n > LAUNCH_ENTRIES:
+                break
+            n = 2 * waves + LAUNCH_ENTRIES                            # a device that holds more: a list longer than that
+        assert 2 * waves < len(idx), (waves, len(idx))                # nothing forced: every wavefront takes pairs in turn
+        wrec, parts, nopath = want["pinned" if end == "records only" else end]
+        rec = got if end == "records only" else got[0]
+        assert pairs_ref.same_records(rec, wrec[idx].astype(rec.dtype)), (W, end)
+        if end == "records only":
+            continue
+        assert np.array_equal(got[1], np.concatenate([[0], np.cumsum([len(parts[i]) for i in idx])])), (W, end)
+        assert got[2].dtype == np.int32 and np.array_equal(got[2], np.concatenate([parts[i] for i in idx])), (W, end)
+        assert api.last_path_mismatches() == nopath[idx].sum() > 0, (W, end)
+
+
+# ---- long reads ------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def long_reads():
+    """a drifting pair of an 18 000-level target (a stall of 500, 2 000 more target points) and a tie-heavy pair of
+    20 000 x 20 000"""
+    rng = np.random.default_rng(19)
+    x, y = br.drift_pair(rng, 18000, 0.6, 0.3, 500, 2000)
+    return [x, y, br.ties(rng, 20000), br.ties(rng, 20000)]
+
+
+@pytest.mark.parametrize("W", WIDTHS)
+def test_long_reads(gpu, W):
+    """50 000 and 40 000 anti-diagonals in a pair: 8 times the longest pair of the tests above"""
+    from squigglekit_amd import api
+    seqs = long_reads()
+    for end, pairs in (("pinned", [(2, 3), (0, 1)]), ("free", [(0, 1)])):
+        want = br.records(seqs, pairs, W, end)
+        assert want[3] == 0 and br.mismatches(seqs, pairs, want[1], want[2]) == 0     # a condition on the input
+        got, mism = run(seqs, pairs, W, end)
+        assert mism == 0
+        check(got, want, (W, end))
+        steps = max(len(seqs[q]) + len(seqs[t]) - 1 for q, t in pairs)
+        slab = -(-steps * W // 1024) * 256 + -(-steps // 64) * 8 + 8          # the header's formula for one wavefront's slab
+        assert steps > 39000 and api.last_band_plan() == (slab, len(pairs), steps)
+        for p in range(len(pairs)):
+            br.check_invariants(got[2][got[1][p]:got[1][p + 1]], got[0]["end"][p])
+        assert end == "pinned" or got[0]["end"][0] < len(seqs[1]) - 1000             # the free end is not the pinned one
+
+
+# ---- non-finite values -----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def non_finite_list():
+    """(seqs, pairs, kinds): 48 pairs, drifting (odd k) and tie-heavy (even k) in turn, pair k with kind k % 9 of
+    band_ref.NONFINITE -- 2 and 9 are coprime, so every kind meets both sorts of pair"""
+    rng = np.random.default_rng(21)
+    seqs, pairs, kinds = [], [], []
+    for k in range(48):
+        if k % 2:
+            x, y = br.drift_pair(rng, int(rng.integers(30, 160)), 0.55, 0.3, 40 * (k % 4 == 1), 50 * (k % 8 == 3))
+        else:
+            x, y = br.ties(rng, int(rng.integers(1, 300))), br.ties(rng, int(rng.integers(1, 300)))
+        kinds.append(br.NONFINITE[k % len(br.NONFINITE)])
+        x, y = br.lay_non_finite(rng, x, y, kinds[-1])
+        pairs.append((len(seqs), len(seqs) + 1))
+        seqs += [x, y]
+    return seqs, pairs, kinds
+
+
+@pytest.mark.parametrize("W", WIDTHS)
+def test_non_finite_values_follow_the_statement(gpu, W):
+    """NaN and inf in the pool: a NaN at a band end moves the band by parity, a NaN never is the free end, an inf costs
+    +inf along its row or column.  From the statement alone the list holds pairs with a finite dist and a path, pairs
+    with a NaN dist and a path (pinned), pairs with a NaN dist whose walk leaves the band (counted, not lost) and lost
+    pairs; the library gives the same records, spans and count."""
+    from squigglekit_amd import api
+    seqs, pairs, kinds = non_finite_list()
+    for drifting in (0, 1):                                          # from the list alone: every kind, on both sorts of pair
+        assert {kinds[k] for k in range(drifting, len(pairs), 2)} == set(br.NONFINITE)
+    assert all(not (np.isfinite(seqs[q]).all() and np.isfinite(seqs[t]).all()) for q, t in pairs)
+    seen = set()
+    for end in ENDS:
+        want = br.records(seqs, pairs, W, end)
+        wrec, woff, wspans, lost = want
+        path = np.array([wspans[woff[p], 0] != -1 for p in range(len(pairs))])
+        seen |= {"finite with a path"} if (np.isfinite(wrec["dist"]) & path).any() else set()
+        seen |= {"NaN with a path"} if (np.isnan(wrec["dist"]) & path).any() else set()
+        seen |= {"NaN, the walk fails"} if (np.isnan(wrec["dist"]) & ~path).any() else set()
+        seen |= {"lost"} if lost else set()
+        assert end == "pinned" or not np.isnan(wrec["dist"]).any()       # a NaN never wins the free end's `<`
+        got, mism = run(seqs, pairs, W, end)
+        check(got, want, (W, end))
+        assert mism == br.mismatches(seqs, pairs, woff, wspans) >= lost > 0, (W, end)
+        only = api.dtw_band(seqs, pairs, W, end, paths=False)
+        assert pairs_ref.same_records(only, wrec.astype(only.dtype)) and only.tobytes() == got[0].tobytes(), (W, end)
+    assert seen == {"finite with a path", "NaN with a path", "NaN, the walk fails", "lost"}

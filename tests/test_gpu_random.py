@@ -5,9 +5,11 @@ the region + motif panel (sk_panel.hip), event detection (sk_detect.hip), the si
 hit family, the switches of the screening scheme (sk_sdtwq.hip), and both branches of the dRNA segmenter (sk_drna_walk.hip,
 k_drna_stats / k_roll_* of sk_prep.hip; host and device entry points), DTW over a pair list (sk_pairs.hip, k_sdtw's
 MODE_PAIRS / MODE_PAIRS_GLOBAL) and its warping paths (sk_pairpath.hip; host and device entry points) -- through the public
-api call, against its reference, exactly; and four interleaved sequences of calls over the shared grow-only context buffers.
+api call, against its reference, exactly; the adaptive-band DTW (sk_band.hip; host and device entry points) likewise; and
+five interleaved sequences of calls over the shared grow-only context buffers.
 tests/test_random_cases.py (CPU) asserts what the seeds
-reach; tests/RANDOM_CASES.md lists the one-line kernel mutants these tests catch.  A failure names family, seed, the
+reach; tests/RANDOM_CASES.md (tests/RANDOM_CASES_BAND.md for the band) lists the one-line kernel mutants these tests
+catch.  A failure names family, seed, the
 drawn parameters and switches, and the first differing (read, hit / set / line): `randcases.case_of(family, seed)`
 rebuilds the case on any machine."""
 import numpy as np
@@ -48,6 +50,11 @@ def run_case(monkeypatch, ora, case):
     if fam in ("pairs", "pairpaths"):                        # no screening scheme: the counters read zeros, whatever ran before
         guard = api.last_dtw_guard()
         assert not any(guard.values()), (rc.describe(case), guard)
+    if fam == "band":
+        if case["paths"]:                                    # lost corners and failed walks, no other pair
+            assert got[3] == exp["mismatches"] >= exp["lost"], (rc.describe(case), got[3], exp["mismatches"])
+        if "SK_BAND_WAVES" in case["env"]:
+            assert api.last_band_plan()[1] <= int(case["env"]["SK_BAND_WAVES"]), (rc.describe(case), api.last_band_plan())
     return got, exp
 
 
@@ -456,6 +463,41 @@ def test_pairpaths_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, 
         dev.free()
 
 
+@pytest.mark.parametrize("seed", rc.SEEDS["band"])
+def test_band_seed_matches_the_statement(gpu, ora, monkeypatch, seed):
+    """api.dtw_band (or, device form, sk_dtw_band_dev) on a drawn pool and list under a drawn width, end, pool form and
+    SK_BAND_WAVES, with paths or records only as drawn: every record of every pair the statement's (bits of dist, two NaNs
+    agree), span_off and spans as integers, the mismatch count the statement's pairs without a path, the plan the header's
+    slab formula and no more wavefronts than forced (all in diff_band); then the other of the two calls -- records only
+    where paths were drawn, paths where they were not: the same record bytes."""
+    case = rc.case_of("band", seed)
+    got, exp = run_case(monkeypatch, ora, case)
+    other = run_again(monkeypatch, dict(case, paths=not case["paths"]), exp)
+    assert other[0].tobytes() == got[0].tobytes(), rc.describe(case)
+    assert (other if case["paths"] else got)[4][0] == 0 < (got if case["paths"] else other)[4][0], rc.describe(case)
+
+
+# W = 128 pinned, 35 pairs under 3 wavefronts | W = 256 free, 30 pairs under 3 | W = 64 pinned, three pairs lost by a -inf
+BAND_DEVICE_SEEDS = (138, 297, 240)
+
+
+@pytest.mark.parametrize("seed", BAND_DEVICE_SEEDS)
+def test_band_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed):
+    """sk_dtw_band_dev on device buffers, the pool at a nonzero offset, with spans and without: the host form's records
+    and spans (checked against the statement), the same mismatch count, nothing written behind `records` or `spans`, and
+    without spans nothing written to them at all."""
+    from squigglekit_amd import api
+    case = rc.case_of("band", seed)
+    assert case["form"] == "device"
+    exp = rc.expect_band(ora, case)
+    rec, off, spans, counted, _, _ = run_again(monkeypatch, dict(case, form="list", paths=True), exp)
+    for with_spans in (True, False):
+        drec, dspans, dcounted, clean = rc.band_device_call(api, case, with_spans, len(spans))
+        assert clean and drec.tobytes() == rec.tobytes(), (rc.describe(case), with_spans)
+        assert not with_spans or (dspans.tobytes() == spans.tobytes() and dcounted == counted == exp["mismatches"])
+        assert api.last_band_plan()[0] == (rc.band_slab_bytes(case["longest"], case["W"]) if with_spans else 0)
+
+
 def run_sequence(monkeypatch, ora, seq):
     seen = {}
     for step, (fam, seed) in enumerate(seq):
@@ -500,3 +542,11 @@ def test_pair_calls_interleaved_with_the_path_and_screening_families(gpu, ora, m
     and a pair call resets the retry and profile state the screening counters are read through.  Every call against its
     reference (mismatch counts, tiers and guard counters included), a call that occurs twice the same bytes both times."""
     run_sequence(monkeypatch, ora, rc.INTERLEAVE4)
+
+
+def test_band_calls_interleaved_with_the_pair_and_hit_families(gpu, ora, monkeypatch):
+    """Band lists between pair lists, their warping paths and hit lists: c->pathcnt is the one mismatch counter of all
+    path kernels (a call that counts some directly before one that must count none, both ways round), the band's table and
+    slabs only grow (the widest slabs before a list of one short pair and again after it).  Every call against its
+    reference, a call that occurs twice the same bytes both times."""
+    run_sequence(monkeypatch, ora, rc.INTERLEAVE5)

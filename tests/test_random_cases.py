@@ -1516,3 +1516,161 @@ def test_fourth_interleaved_sequence_is_what_it_claims():
     assert others
     scr = [i for i, (f, _) in enumerate(seq) if f == "screen"]                 # a pair call directly behind every screening call
     assert len(scr) >= 3 and all(seq[i + 1][0] in ("pairs", "pairpaths") for i in scr)
+
+
+# ---- adaptive-band DTW over a pair list ---------------------------------------------------------------------------------
+from band_ref import NONFINITE                  # noqa: E402
+BAND_LONG_STEPS = 6000                           # the longest pair of the older band tests has 5 999 anti-diagonals
+
+
+def band_features(case, exp):
+    """From the case and the statement's answer alone.  The three outcome classes of a pair with a target: a finite
+    dist with a path, a NaN dist with a path (a NaN reached the pinned corner), lost (dist +inf, no path)."""
+    import band_ref
+    seqs, pairs, W = case["seqs"], [tuple(p) for p in case["pairs"].tolist()], case["W"]
+    rec, off, spans = exp["records"], exp["off"], exp["spans"]
+    assert len(rec) == case["npairs"] == len(pairs) <= rc.BAND_LIST and case["nseq"] == len(seqs) <= rc.BAND_POOL
+    assert case["steps"] == sum(rc.band_steps(len(seqs[q]), len(seqs[t])) for q, t in set(pairs))
+    assert case["longest"] == max(rc.band_steps(len(seqs[q]), len(seqs[t])) for q, t in pairs)
+    if case["form"] != "list":
+        values, voff = rc.pairs_pool_of(case)
+        assert voff[0] == case["pad"] > 0 and voff[-1] == values.size and np.all(np.isnan(values[:voff[0]]))
+    how = "paths" if case["paths"] else "records only"
+    f = {"W=%d %s %s" % (W, case["end"], how), "form=" + case["form"],
+         "SK_BAND_WAVES=%s" % case["env"].get("SK_BAND_WAVES", "unset")}
+    lost = failed = 0
+    for p, (q, t) in enumerate(pairs):
+        N, M = len(seqs[q]), len(seqs[t])
+        sp = spans[off[p]:off[p + 1]]
+        assert sp.shape == (N, 2)
+        for name, n in (("N", N), ("M", M)):
+            if n in rc.BAND_EDGES:
+                f.add("%s=%d" % (name, n))
+            if n - W // 2 in (-1, 0, 1):
+                f.add("%s=W/2%+d" % (name, n - W // 2))
+        if M == 0:
+            assert np.isnan(rec["dist"][p]) and rec["flags"][p] == band_ref.FLAG_EMPTY and np.all(sp == -1)
+            continue
+        if rc.band_steps(N, M) > BAND_LONG_STEPS:
+            f.add(">6000 anti-diagonals")
+        if q != t and np.all(seqs[q] == seqs[q][0]) and np.all(seqs[t] == seqs[t][0]) and min(N, M) > W // 2:
+            f.add("a constant against a constant beyond W/2")
+        if rec["flags"][p] & band_ref.FLAG_BAND_LOST:
+            assert rec["dist"][p] == np.inf and (rec["start"][p], rec["end"][p]) == (-1, -1) and np.all(sp == -1)
+            lost += 1
+            f.add(how + ": lost")
+        elif np.all(sp == -1):
+            failed += 1
+            f.add(how + ": a walk that fails")
+        else:
+            band_ref.check_invariants(sp, rec["end"][p])
+            if np.isnan(rec["dist"][p]):
+                assert case["end"] == "pinned"
+                f.add(how + ": a NaN dist with a path")
+            else:
+                assert rec["dist"][p] < np.inf
+                f.add(how + ": a finite dist with a path")
+    assert exp["lost"] == lost and exp["mismatches"] == lost + failed, rc.describe(case)
+    if case["nonfinite"] is None:
+        assert lost == 0 and failed == 0, rc.describe(case)        # no finite input loses the corner (RANDOM_CASES_BAND.md)
+    else:
+        f.add("non-finite: " + case["nonfinite"])
+    queries, targets = {q for q, _ in pairs}, {t for _, t in pairs}
+    shape = {"shared": any(q in targets and any(t == q and qq != q for qq, t in pairs) for q in queries),
+             "(i, i)": any(q == t for q, t in pairs), "repeated": len(set(pairs)) < len(pairs),
+             "empty": any(len(seqs[t]) == 0 for _, t in pairs)}
+    f |= {"list: " + k for k, v in shape.items() if v}
+    if all(shape.values()):
+        f.add("list: shared, (i, i), repeated and empty together")
+    if len(pairs) == 1:
+        f.add("a list of one pair")
+    return f
+
+
+BAND_REQUIRED = ({"W=%d %s %s" % (W, end, how) for W in (64, 128, 256) for end in ("pinned", "free")
+                  for how in ("paths", "records only")} |
+                 {"form=" + v for v in rc.BAND_FORMS} | {"SK_BAND_WAVES=%s" % (v or "unset") for v in rc.BAND_WAVES} |
+                 {"%s=%d" % (a, n) for a in "NM" for n in rc.BAND_EDGES} |
+                 {"%s=W/2%+d" % (a, d) for a in "NM" for d in (-1, 0, 1)} |
+                 {"paths: a finite dist with a path", "paths: a NaN dist with a path", "paths: lost", "records only: lost",
+                  "paths: a walk that fails", "list: shared, (i, i), repeated and empty together", "a list of one pair",
+                  "a constant against a constant beyond W/2", ">6000 anti-diagonals"} |
+                 {"non-finite: " + v for v in NONFINITE})
+
+
+def test_band_cases_reach_every_boundary(cases):
+    """All 12 (W, end, paths) calls, the three pool forms, every SK_BAND_WAVES value; with paths the three outcome classes
+    and without them a lost record; a list with a shared sequence, an (i, i) pair, a repeated pair and an empty target;
+    and a list of one pair; every edge length as N and as M; constants against each other beyond the half band; a pair
+    above 6 000 anti-diagonals; every non-finite kind, and a walk that leaves the band (counted, though the corner was
+    not lost).  Without a non-finite value no pair is lost and no walk fails."""
+    assert len(cases["band"]) >= 12
+    have = set()
+    for case, exp in cases["band"]:
+        have |= band_features(case, exp)
+        assert case["steps"] <= max(rc.BAND_STEPS, case["longest"]), rc.describe(case)
+    assert not sorted(BAND_REQUIRED - have)
+    assert sum(exp["mismatches"] for case, exp in cases["band"] if case["paths"]) > 0
+
+
+def test_band_references_stay_inside_the_budget(ora):
+    """The statement on every committed case, timed one by one: BAND_STEPS anti-diagonals at 35 to 45 microseconds each
+    stay under 2 s with room for a slower machine (tests/RANDOM_CASES_BAND.md has the times)."""
+    import time
+    for seed in rc.SEEDS["band"]:
+        case = rc.case_of("band", seed)
+        t0 = time.perf_counter()
+        rc.EXPECT["band"](ora, case)
+        assert time.perf_counter() - t0 < 2.0, rc.describe(case)
+
+
+PINNED_BAND = {
+    27: "a948bc6592b0a81021cdb5a8d414bde0ffe1bfd759d31881758222d29fb72da0",
+    29: "b3fdc1970d5bbf9ffcb5b20e8d578fc5a35e175709e6cac662b64246a14de7f8",
+    44: "105b94b82bd50879eb2602793d2c033c52a4a5f6b44245168568049a386d8a97",
+    54: "8bfbfbae94127ef9490e18f4bf844095910eab19bad26eebd0a485ae1c407ec4",
+    61: "32311bbe505dba175be17d3318b5292a764e51c83bebb1549aa4f6f406069309",
+    70: "2773fe8be1e9b1d457d9852d36625c4fa0f130cfbcdbb01bbec0d97b6fd7a3ac",
+    75: "57a97cb81e3817c0e7193126237d51dddc82e79b1347397d5f4c97693408107e",
+    112: "ea361cfae51a61063814b4cc7c9a3e02be65d2a7ee58efe3f808b19783f98106",
+    138: "6f83b0f8c42bcb2fac1573edb4d4149bc971c1686ec655470e2174bb2dd38b6e",
+    195: "f000435ffc8f9b3c71c67d98f7cb61ad3fc20946d99189e7e7aa65d9a841437c",
+    238: "5a1b35c96fb4970e01d67f02bebf69b212748b258167c1912a5ae4324bb3bd91",
+    240: "40b9bcfcfea7c734da48d7f6012f4d84b15f99687a30dc21f82943f0c56bfc6a",
+    297: "e9260a83638589e5db86b7afbf999786232fda6f73f4d8a2c3aa3ad87a50fbc5",
+    299: "fd863a3ea01cd09240a026bda6a47a82c0f967183e3006e94abc76e87d9c7116",
+    331: "8df9bc53056cff0b2bbe94300faf42b25809b174f22f8be7cbeaa8b67c369bea",
+    351: "e39b2f15f47a26d1e4c7519e8f9709fbb3cc1960ead490bb15d341b250242225",
+    423: "48683d6668712253fe0607df669b4c2f9348fd62cf4a15762edb535dbfeb478f",
+    458: "07111f3946cc07a40dbe00906fc0e1ff13c0abe1aebf7eb90988fc2aefa61620",
+}
+
+
+def test_band_family_keeps_its_cases():
+    assert rc.FAMILY_INDEX["band"] == 13 and rc.SWITCHES[-1] == "SK_BAND_WAVES"
+    assert [rc.FAMILY_INDEX[f] for f in ("hits", "paths", "pull", "sweep", "panel", "detect", "hmm", "levels", "screen",
+                                         "drna", "roll", "pairs", "pairpaths")] == list(range(13))     # (they stay)
+    assert list(PINNED_BAND) == rc.SEEDS["band"]
+    for seed, digest in PINNED_BAND.items():
+        case = rc.case_of("band", seed)
+        assert rc.case_digest(case) == digest, seed
+        assert rc.describe(case).startswith("band seed=%d W=" % seed) and set(case["env"]) <= {"SK_BAND_WAVES"}
+
+
+def test_fifth_interleaved_sequence_is_what_it_claims(cases):
+    """Band lists between pairs, pairpaths and hits cases, never two of a family in a row; band cases that come twice; a
+    call that counts mismatches directly before one of the other kind that must count none, both ways round; the widest
+    slabs before a list of one short pair and again after it."""
+    seq = rc.INTERLEAVE5
+    assert {f for f, _ in seq} == {"band", "pairs", "pairpaths", "hits"}
+    assert all(fam not in rc.SEEDS or seed in rc.SEEDS[fam] for fam, seed in seq)
+    assert all((a == "band") != (b == "band") for (a, _), (b, _) in zip(seq, seq[1:]))
+    band = [s for f, s in seq if f == "band"]
+    assert len(band) - len(set(band)) >= 3
+    counted = {case["seed"]: exp["mismatches"] if case["paths"] else None for case, exp in cases["band"]}
+    wrong = {case["seed"]: exp["mismatches"] for case, exp in cases["pairpaths"]}
+    steps = list(zip(seq, seq[1:]))
+    assert any(fa == "pairpaths" and wrong[sa] > 0 and fb == "band" and counted[sb] == 0 for (fa, sa), (fb, sb) in steps)
+    assert any(fa == "band" and (counted[sa] or 0) > 0 and fb == "pairpaths" and wrong[sb] == 0 for (fa, sa), (fb, sb) in steps)
+    slab = [rc.band_slab_bytes(max(rc.case_of("band", s)["longest"], 1), rc.case_of("band", s)["W"]) for s in band]
+    assert any(b < a // 20 for a, b in zip(slab, slab[1:])) and any(b > 20 * a for a, b in zip(slab, slab[1:])), slab

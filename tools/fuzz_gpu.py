@@ -4,19 +4,17 @@ lengths, strides, outlier limits, segmenter parameters; the segment levels of ev
 segmenter round against plain numpy; and, per round, one drawn case of every family of tests/randcases.py -- the
 screening scheme of MotifSeq's first match under its switches, the segmenter sweep, the MotifSeq hit lists, the alignment paths, SquigglePull's text, the region + motif panel, event detection, the
 signal HMM with its state paths, segment levels, both branches of the dRNA segmenter, and the background and events twins of
-the hit family, DTW over a pair list and the warping paths of one -- each against the
+the hit family, DTW over a pair list, the warping paths of one and the adaptive-band DTW of one -- each against the
 reference tests/test_gpu_random.py uses; and one MotifSeq session (random motif lengths, slot count, cuts, calibration
 length, limits, both scale modes and lane layouts) against the prefix statement of tests/stream_ref.py; and one
-adaptive-band DTW list (random lengths up to 4 000, band width, end mode, wavefront count, with and without paths)
-against the statement of tests/band_ref.py; and one mapping session (tests/mapstream_ref.draw_session: random targets,
-slot count, subsets, cuts up to 2 100 points, resets and peeks, both lane layouts) against the oracle on every slot's
+mapping session (tests/mapstream_ref.draw_session: random targets, slot count, subsets, cuts up to 2 100 points, resets and peeks, both lane layouts) against the oracle on every slot's
 concatenation after every push; and one event session (tests/evstream_ref.draw_session: random parameters, slot
 count, reads of four kinds, cuts, subsets, ENDs and resets) against its statement on detect_ref after every push and
 against the one-shot call on every ended read; and one hit-list round (tests/pair_hits_ref.py: a drawn pair list with its
 K, max_dist and row budget, and a drawn session script whose hits() are read after every push) against the statement
 there.  The DTW pair
-lists and their warping paths are two of the families of tests/randcases.py (`pairs`, `pairpaths`: the draws that used to
-live here, against tests/pairs_ref.py and tests/pair_paths_ref.py).
+lists, their warping paths and the adaptive band are three of the families of tests/randcases.py (`pairs`, `pairpaths`,
+`band`: the draws that used to live here, against tests/pairs_ref.py, tests/pair_paths_ref.py and tests/band_ref.py).
 
     python tools/fuzz_gpu.py [seconds=120] [seed=1]
 
@@ -33,7 +31,6 @@ sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))        # the seeded case generators and their references
 import randcases                                      # noqa: E402
 import stream_ref                                     # noqa: E402
-import band_ref                                       # noqa: E402
 import mapstream_ref                                  # noqa: E402
 import evstream_ref                                   # noqa: E402
 import pair_hits_ref                                  # noqa: E402
@@ -92,50 +89,6 @@ def session_round(rng):
                                     desc, s, kk, stream_ref.fields(rec[kk, s]), want)
     finally:
         os.environ.pop("SK_DTW_NO_SMALL", None)
-    return None
-
-
-def band_round(rng):
-    """One drawn adaptive-band list: records bit for bit, spans as integers and the mismatch count against
-    band_ref.records; the records-only call against the same records.  Returns None, or what differed."""
-    W = int(rng.choice(band_ref.WIDTHS))
-    end = band_ref.ENDS[int(rng.integers(2))]
-    waves = [None, "1", "3"][int(rng.integers(3))]
-    npairs = int(rng.integers(1, 25))
-    seqs, pairs = [], []
-    for _ in range(npairs):
-        kind = rng.random()
-        if kind < 0.3:
-            N, M = (int(rng.choice([1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257])) for _ in range(2))
-            x, y = band_ref.ties(rng, N), band_ref.ties(rng, M)
-        elif kind < 0.6:
-            x, y = band_ref.drift_pair(rng, int(rng.integers(8, 1500)), float(rng.uniform(0.3, 0.7)), float(rng.uniform(0.1, 0.6)),
-                                       int(rng.choice([0, 0, 40, 120])), int(rng.choice([0, 0, 150])))
-        else:
-            x, y = rng.normal(size=int(rng.integers(1, 4001))), rng.normal(size=int(rng.integers(0, 4001)))
-        pairs.append((len(seqs), len(seqs) + 1))
-        seqs += [x, y]
-    desc = "W=%d end=%s waves=%s shapes=%s" % (W, end, waves, [(len(seqs[q]), len(seqs[t])) for q, t in pairs])
-    wrec, woff, wspans, lost = band_ref.records(seqs, pairs, W, end)
-    if waves:
-        os.environ["SK_BAND_WAVES"] = waves
-    try:
-        rec, off, spans = api.dtw_band(seqs, pairs, W, end)
-        mism = api.last_path_mismatches()
-        only = api.dtw_band(seqs, pairs, W, end, paths=False)
-    finally:
-        os.environ.pop("SK_BAND_WAVES", None)
-    for p in range(npairs):
-        same = (rec["dist"][p] == wrec["dist"][p] or (np.isnan(rec["dist"][p]) and np.isnan(wrec["dist"][p]))) and \
-            all(rec[f][p] == wrec[f][p] for f in ("start", "end", "n", "flags"))
-        if not same:
-            return "%s: pair %d: got %s want %s" % (desc, p, rec[p], wrec[p])
-        if not np.array_equal(spans[off[p]:off[p + 1]], wspans[woff[p]:woff[p + 1]]):
-            return "%s: pair %d: the spans differ" % (desc, p)
-    if not np.array_equal(off, woff) or mism != lost:
-        return "%s: span_off differs, or %d mismatches counted where %d bands lost the end" % (desc, mism, lost)
-    if only.tobytes() != rec.tobytes():
-        return "%s: the records-only call gives other records" % desc
     return None
 
 
@@ -420,10 +373,12 @@ def main():
         # HMM with its state paths (hmm_ref, hmm_path_ref), segment levels (numpy on the oracle's segments); then a
         # hit-list draw through the background twin (numpy on the oracle's last row, test_background_host.py) and a paths
         # draw through the events twin with pooling (test_events_host.py); then a DTW pair list (pairs_ref.records) and the
-        # warping paths of one (pair_paths_ref.list_spans; mismatch count and tiers as the case's plan says).  A mismatch line carries the round, so
+        # warping paths of one (pair_paths_ref.list_spans; mismatch count and tiers as the case's plan says), then an
+        # adaptive-band list (its statement's records, spans and mismatch count; with paths or records only, host or device
+        # form and wavefront count as drawn).  A mismatch line carries the round, so
         # `fuzz_gpu.py <seconds> <seed>` up to that round rebuilds the case, and the drawn parameters and switches.
         for fam in ("sweep", "hits", "paths", "pull", "panel", "detect", "hmm", "levels", "background", "events", "pairs",
-                    "pairpaths"):
+                    "pairpaths", "band"):
             if fam in randcases.TWIN_OF:
                 case = randcases.DRAW[randcases.TWIN_OF[fam]](rng)
                 case = randcases.twin_case(fam, case, use_seed=int(rng.integers(1 << 30)))
@@ -445,6 +400,14 @@ def main():
                     msg = "the guard counters are not all zero: %s" % guard
             if msg is None and fam in ("pairs", "pairpaths") and any(api.last_dtw_guard().values()):
                 msg = "the guard counters are not all zero after a pair call: %s" % api.last_dtw_guard()
+            if msg is None and fam == "band":                # the other of the two calls: its own diff, the same record bytes
+                other = dict(case, paths=not case["paths"])
+                again = randcases.CALL[fam](api, other, exp)
+                msg = randcases.DIFF[fam](other, again, exp)
+                if msg is None and again[0].tobytes() != got[0].tobytes():
+                    msg = "the call with paths and the records-only call give other records"
+                if msg is not None:
+                    msg = "paths=%s instead: %s" % (other["paths"], msg)
             if msg is not None and fam == "detect":          # (the lines of the sections these draws replaced, as they were)
                 bad += 1
                 print("DETECT mismatch round %d: %d reads, max length %d, stride %d, params %s -- %s" %
@@ -467,11 +430,6 @@ def main():
         if msg is not None:
             bad += 1
             print("SESSION mismatch round %d %s" % (rounds, msg))
-        # ---- an adaptive-band DTW list against its statement (tests/band_ref.py) ----
-        msg = band_round(rng)
-        if msg is not None:
-            bad += 1
-            print("BAND mismatch round %d %s" % (rounds, msg))
         # ---- a mapping session against the oracle on the concatenation (tests/mapstream_ref.py) ----
         msg = mapstream_round(rng)
         if msg is not None:
