@@ -1377,6 +1377,72 @@ int sk_last_live_plan(int64_t *state_bytes, int64_t *bridged_levels, int64_t *la
  * host-side plan of the sweep included; this gives the bridge again and the summary kernel alone (0 without a rule). */
 int sk_live_last_ms(int32_t handle, float *bridge_ms, float *summary_ms);
 
+/* Gated live sessions: start at the transcript start an HMM gate finds (tests/livegate_ref.py states this in numpy).
+ * A direct-RNA read begins with open pore, leader, adapter and poly(A): none of it belongs to a target, and all of it
+ * would go into the calibration head.  A gated session is a live session plus one sk_hmm_model (checked and copied at
+ * open as sk_hmms_open does; the session owns one HMM session handle beside its event and mapping handles), one gate
+ * rule sk_live_gate, and per slot a gate record and a hold ring of the last G = hold events the slot was cut.
+ * Reset: the slot is GATING, t0 = -1, the ring empty; the HMM slot is reset with the slot's calibration pair:
+ *     sk_live_reset gives it none ({0.0, 1.0}), sk_live_reset_cal gives m {offset, unit} pairs as sk_hmms_reset takes them.
+ * A push, per named slot:
+ *     1. The chunk goes to the slot's HMM state only while the slot is GATING and has not ended; after the decision the
+ *        HMM slot stands still, so its record stays the record at the decision.  The event session takes the chunk as in
+ *        an ungated session, from sample 0.
+ *     2. While GATING, api.polya_decide's rule on the slot's HMM record, expression for expression, `state` in place of
+ *        TRANSCRIPT: accept when final_state == state and n_used - enter[state] >= min_body and
+ *        v[state] - max(v[j], j != state) >= min_margin (the max over all six entries, -inf included; one float64
+ *        subtract; a NaN margin fails).  On accept t0 = enter[state] and the slot is OPEN until its reset.  Otherwise,
+ *        when give_up > 0 and n_used >= give_up, the slot is REJECTED.  Otherwise, when the push carries END, the slot is
+ *        REJECTED with flag ENDED.  decided_n = n_used at any of the three.
+ *     3. An event is released iff the slot is OPEN and event.start >= t0 (read coordinates): an event that straddles t0
+ *        is dropped, whether it is emitted before or after the decision.  On the push that opens the gate the released
+ *        events are those of the ring with start >= t0, oldest first, then those of this push with start >= t0; the
+ *        events of that push do not pass through the ring.  While the slot stays GATING the events of the push are
+ *        appended to the ring, which keeps the last G; TRUNCATED is set at the opening iff an event the ring had
+ *        overwritten had start >= t0 (exact: the start of the most recently overwritten event is kept).  What is still
+ *        held is released.  After the decision the ring is empty.
+ *     4. The released events are the lev[0 .. E) of the definition above: sk_live_info's events, new_events, held and
+ *        mapped count released events; END passes through unchanged, so a slot that ends while gating becomes
+ *        UNDECIDABLE (fewer than 2 levels) and a give-up-rejected slot stays CALIBRATING with 0 events until it ends.
+ *        Records, sk_live_fetch, sk_live_hits and the summary are those of the definition above over the released levels.
+ * sk_live_push_i16 and sk_live_push_dev_i16 take gated handles as they are.  In the device form samples for an ended
+ *     slot are ignored by both inner sessions.
+ * sk_live_gate_fetch: the gate records and the HMM records of the entries of the last push (nothing before the first);
+ *     either pointer may be NULL.  sk_live_gate_fetch_dev: the same to device pointers, a stream-ordered copy with
+ *     nothing synchronised.
+ * Limits: hold in 1 .. SK_LIVE_MAX_GATE_HOLD; a slot takes at most 0x7fffff00 samples (the HMM session's cap,
+ *     SK_ERR_UNSUPPORTED in the host form whatever the gate's state; the device form ignores what is beyond and counts
+ *     the slot in sk_last_hmms_plan's guard_hits while it is gating).
+ * Refusals (SK_ERR_INVALID unless said otherwise).  By the arguments alone, before a context is looked for: at open
+ *     sk_live_open's in its order, then a NULL model or gate, a model that breaks sk_hmms_open's rules (its message),
+ *     state outside [0, nstates), min_body < 1, hold outside its range, a NaN min_margin; at sk_live_reset_cal
+ *     sk_live_reset's, then a cal2 that is NULL or not finite; at sk_live_gate_fetch a handle outside the table.  Then
+ *     the session: sk_live_gate_fetch or sk_live_reset_cal on an ungated handle; a push whose (calib - 1) + hold + the
+ *     event session's staging rows for `stride` exceed SK_MAP_MAX_CHUNK (SK_ERR_UNSUPPORTED).  A refused call changes
+ *     nothing.
+ * sk_last_live_plan's state_bytes add the HMM session's bytes and nslots * (hold * 24 + 40) (ring and slot record); its
+ *     launches add 3 (the chunk lengths, the HMM push, the gate). */
+#define SK_LIVE_MAX_GATE_HOLD 4096
+enum { SK_LIVE_GATE_GATING = 0, SK_LIVE_GATE_OPEN = 1, SK_LIVE_GATE_REJECTED = 2 };
+enum { SK_LIVE_GATE_TRUNCATED = 1, SK_LIVE_GATE_ENDED = 2 };
+typedef struct sk_live_gate {       /* 24 bytes */
+    int32_t state, min_body, give_up, hold;
+    double  min_margin;
+} sk_live_gate;
+typedef struct sk_live_gate_info {  /* 32 bytes */
+    int32_t state, t0, decided_n, events_cut, released, ring, dropped, flags;
+} sk_live_gate_info;
+int sk_live_open_gated(const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off,
+                       int32_t ntargets, int32_t nslots, const sk_hmm_model *model, const sk_live_gate *gate,
+                       int32_t *handle);
+int sk_live_reset_cal(int32_t handle, const int32_t *slots, int32_t m, const double *cal2 /* [m][2] */);
+int sk_live_gate_fetch(int32_t handle, sk_live_gate_info *gate /* [m] or NULL */, sk_hmms_rec *rec /* [m] or NULL */);
+int sk_live_gate_fetch_dev(int32_t handle, sk_live_gate_info *d_gate, sk_hmms_rec *d_rec);
+/* Timing of a gated session's last push, from HIP events of its own: the HMM side (the chunk lengths and k_hmms_push) and
+ * the gate (k_live_gate and the scan of the released counts).  In a gated push sk_live_last_ms's bridge includes the
+ * gate.  Either pointer may be NULL; SK_ERR_INVALID on an ungated handle. */
+int sk_live_gate_last_ms(int32_t handle, float *hmm_ms, float *gate_ms);
+
 #ifdef __cplusplus
 }
 #endif

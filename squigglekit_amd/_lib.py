@@ -276,6 +276,20 @@ class LiveRule(C.Structure):
     _fields_ = [("min_rows", C.c_int32), ("give_up_rows", C.c_int32), ("max_dist_per_row", C.c_double),
                 ("min_margin", C.c_double)]
 
+
+# gated live sessions: sk_live_gate (the rule, 24 bytes) and sk_live_gate_info (a slot's gate record, 32 bytes)
+SK_LIVE_MAX_GATE_HOLD = 4096
+SK_LIVE_GATE_GATING, SK_LIVE_GATE_OPEN, SK_LIVE_GATE_REJECTED = 0, 1, 2
+SK_LIVE_GATE_TRUNCATED, SK_LIVE_GATE_ENDED = 1, 2
+GATE_DTYPE = np.dtype([("state", "<i4"), ("t0", "<i4"), ("decided_n", "<i4"), ("events_cut", "<i4"), ("released", "<i4"),
+                       ("ring", "<i4"), ("dropped", "<i4"), ("flags", "<i4")])
+
+
+class LiveGate(C.Structure):
+    """sk_live_gate: api.polya_decide's thresholds with the state whose entry is the start, and the hold ring's length."""
+    _fields_ = [("state", C.c_int32), ("min_body", C.c_int32), ("give_up", C.c_int32), ("hold", C.c_int32),
+                ("min_margin", C.c_double)]
+
 # sk_hmms_rec: a slot's record after a push of an HMM session -- sk_hmm_rec's 40 bytes, then the six scores and the counters
 HMMS_DTYPE = np.dtype([("score", "<f8"), ("final_state", "<i4"), ("n_used", "<i4"), ("enter", "<i4", (SK_HMM_STATES,)),
                        ("v", "<f8", (SK_HMM_STATES,)), ("pushes", "<i4"), ("flags", "<i4")])
@@ -502,6 +516,15 @@ ABI = {
     "sk_live_close": (C.c_int, [C.c_int32]),
     "sk_last_live_plan": (C.c_int, [_vp, _vp, _vp]),
     "sk_live_last_ms": (C.c_int, [C.c_int32, _vp, _vp]),
+    # gated live sessions ("Gated live sessions" in the header; tests/livegate_ref.py): open_gated(sk_live_open's
+    # arguments up to nslots, model, gate, handle); reset_cal(handle, slots, m, cal2 [m][2]); gate_fetch(handle,
+    # gate [m] or NULL, rec [m] or NULL) and its device-resident form
+    "sk_live_open_gated": (C.c_int, [C.POINTER(DetParams), C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(HmmModel),
+                                     C.POINTER(LiveGate), _i32p]),
+    "sk_live_reset_cal": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
+    "sk_live_gate_fetch": (C.c_int, [C.c_int32, _vp, _vp]),
+    "sk_live_gate_fetch_dev": (C.c_int, [C.c_int32, _vp, _vp]),
+    "sk_live_gate_last_ms": (C.c_int, [C.c_int32, _vp, _vp]),
 }
 
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -2886,6 +2886,16 @@ def live_rule(min_rows, max_dist_per_row, min_margin, give_up_rows):
     return LiveRule(int(min_rows), int(give_up_rows), float(max_dist_per_row), float(min_margin))
 
 
+def live_gate(model, min_body, min_margin, give_up=0, hold=1024, state=TRANSCRIPT):
+    """The gate of a gated LiveMap: (model, sk_live_gate).  polya_decide's thresholds in its argument order -- a slot's
+    gate opens at enter[state] when the HMM record ends in `state` (TRANSCRIPT = 5 for a polya_model), the body is at
+    least min_body samples long and `state` leads every other state by min_margin; give_up <= 0: never -- and `hold`,
+    the events a slot keeps while it is gating (1 .. 4096)."""
+    if not isinstance(model, HmmModel):
+        raise TypeError("model must be an HmmModel (hmm_model / polya_model)")
+    return model, LiveGate(int(state), int(min_body), int(give_up), int(hold), float(min_margin))
+
+
 class LiveMap:
     """A live mapping session (sk_live_*): `nslots` channels in progress under one sk_det_params, one calibration length
     `calib` and one set of targets.  A push appends a chunk of int16 raw samples to every named slot; on the device the
@@ -2902,9 +2912,17 @@ class LiveMap:
             hits, count = lm.hits(slots, 2)                       # MapStream.hits on the inner session
             lm.reset(slots)                                       # the slots start a new read
 
-    A live session holds one event-session and one mapping-session handle of the context while it is open."""
+    A live session holds one event-session and one mapping-session handle of the context while it is open.
 
-    def __init__(self, params, calib, targets, nslots):
+    gate=live_gate(polya_model("rna_pa"), min_body=2000, min_margin=50.0) makes it a GATED session (it then holds an
+    HMM-session handle too): every slot also runs HmmStream's Viterbi pass on its samples and holds the last `hold` events
+    back; once polya_decide's rule accepts, only the events that start at or after the transcript start enter[state]
+    reach the calibration head and the mapping side -- events, held, mapped and new_events count those.
+
+            lm.reset(slots, cal2)                                 # cal2 [m, 2] = (offset, unit) for the HMM's int16 feed
+            gate, hrec = lm.gate()                                # GATE_DTYPE [m], HMMS_DTYPE [m] of the last push"""
+
+    def __init__(self, params, calib, targets, nslots, gate=None):
         self._h = None
         flat, toff = _as_pool(targets)
         self.T = toff.size - 1
@@ -2922,7 +2940,15 @@ class LiveMap:
         self._last_m = 0
         L = _lib.ensure_init()
         h = C.c_int32(-1)
-        check(L.sk_live_open(C.byref(self.params), self.calib, ptr(flat), ptr(toff), self.T, self.nslots, C.byref(h)))
+        self.gated = gate is not None
+        if gate is None:
+            check(L.sk_live_open(C.byref(self.params), self.calib, ptr(flat), ptr(toff), self.T, self.nslots, C.byref(h)))
+        else:
+            model, rule = gate
+            if not 1 <= rule.hold <= _lib.SK_LIVE_MAX_GATE_HOLD:
+                raise ValueError("hold must be in 1 .. %d, got %d" % (_lib.SK_LIVE_MAX_GATE_HOLD, rule.hold))
+            check(L.sk_live_open_gated(C.byref(self.params), self.calib, ptr(flat), ptr(toff), self.T, self.nslots,
+                                       C.byref(model), C.byref(rule), C.byref(h)))
         self._h = h.value
 
     handle = property(lambda self: self._h)
@@ -3016,12 +3042,30 @@ class LiveMap:
             check(L.sk_live_hits(self._h, ptr(slots), slots.size, K, md, ptr(hits), ptr(count)))
         return hits, count
 
-    def reset(self, slots):
-        """The slots start a new read: CALIBRATING, no events, nothing mapped."""
+    def reset(self, slots, cal2=None):
+        """The slots start a new read: CALIBRATING, no events, nothing mapped; in a gated session GATING, with cal2 [m, 2] =
+        (offset, unit) per slot for the HMM's int16 feed (None: the raw values)."""
         L = self._open()
         slots = stream_slots(slots, self.nslots)
-        if slots.size:
+        cal2 = _hmm_cal(cal2, slots.size)
+        if cal2 is not None and not self.gated:
+            raise ValueError("only a gated session takes calibration pairs")
+        if slots.size and cal2 is None:
             check(L.sk_live_reset(self._h, ptr(slots), slots.size))
+        elif slots.size:
+            check(L.sk_live_reset_cal(self._h, ptr(slots), slots.size, ptr(cal2)))
+
+    def gate(self):
+        """(gate GATE_DTYPE [m], rec HMMS_DTYPE [m]) of the entries of the last push of a gated session: the slots' gate
+        records and the HMM records the decisions were taken on."""
+        L = self._open()
+        if not self.gated:
+            raise ValueError("the session has no gate")
+        gate = np.zeros(self._last_m, dtype=GATE_DTYPE)
+        rec = np.zeros(self._last_m, dtype=HMMS_DTYPE)
+        if self._last_m:
+            check(L.sk_live_gate_fetch(self._h, ptr(gate), ptr(rec)))
+        return gate, rec
 
     def close(self):
         if self._h is not None:

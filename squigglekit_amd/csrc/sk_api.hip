@@ -3570,7 +3570,28 @@ int sk_live_open(const sk_det_params *p, int32_t calib, const double *targets, c
     if (!targets || !target_off) return sk_fail(SK_ERR_INVALID, "NULL targets/target_off");
     if (int rc = check_map_shape(target_off, ntargets, nslots)) return rc;
     SK_ENTER(c);
-    return sk_live_session_open(c, p, calib, targets, target_off, ntargets, nslots, handle);
+    return sk_live_session_open(c, p, calib, targets, target_off, ntargets, nslots, nullptr, nullptr, handle);
+}
+
+int sk_live_open_gated(const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off, int32_t ntargets,
+                       int32_t nslots, const sk_hmm_model *model, const sk_live_gate *gate, int32_t *handle)
+{
+    if (int rc = check_det_params(p)) return rc;
+    if (!handle) return sk_fail(SK_ERR_INVALID, "NULL handle");
+    if (calib < 2 || calib > SK_LIVE_MAX_CALIB)
+        return sk_fail(SK_ERR_INVALID, "calib = %d is outside 2 .. %d", calib, SK_LIVE_MAX_CALIB);
+    if (!targets || !target_off) return sk_fail(SK_ERR_INVALID, "NULL targets/target_off");
+    if (int rc = check_map_shape(target_off, ntargets, nslots)) return rc;
+    if (!model || !gate) return sk_fail(SK_ERR_INVALID, "NULL model/gate");
+    if (const char *what = sk_hmm_model_error(model)) return sk_fail(SK_ERR_INVALID, "sk_hmm_model: %s", what);
+    if (gate->state < 0 || gate->state >= model->nstates)
+        return sk_fail(SK_ERR_INVALID, "gate: state = %d is outside [0, nstates = %d)", gate->state, model->nstates);
+    if (gate->min_body < 1) return sk_fail(SK_ERR_INVALID, "gate: min_body = %d is below 1", gate->min_body);
+    if (gate->hold < 1 || gate->hold > SK_LIVE_MAX_GATE_HOLD)
+        return sk_fail(SK_ERR_INVALID, "gate: hold = %d is outside 1 .. %d", gate->hold, SK_LIVE_MAX_GATE_HOLD);
+    if (gate->min_margin != gate->min_margin) return sk_fail(SK_ERR_INVALID, "gate: min_margin must be a number");
+    SK_ENTER(c);
+    return sk_live_session_open(c, p, calib, targets, target_off, ntargets, nslots, model, gate, handle);
 }
 
 int sk_live_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
@@ -3678,7 +3699,53 @@ int sk_live_reset(int32_t handle, const int32_t *slots, int32_t m)
     if (m && !slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
     SK_ENTER(c);
     if ((rc = sk_live_session_info(c, handle, nullptr, nullptr, nullptr, nullptr))) return rc;
-    return sk_live_session_reset(c, handle, slots, m);
+    return sk_live_session_reset(c, handle, slots, m, nullptr);
+}
+
+int sk_live_reset_cal(int32_t handle, const int32_t *slots, int32_t m, const double *cal2)
+{
+    int rc = check_live_handle(handle);
+    if (rc) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m && !slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
+    if (!cal2) return sk_fail(SK_ERR_INVALID, "NULL cal2");
+    for (int32_t i = 0; i < 2 * m; i++)
+        if (!(cal2[i] - cal2[i] == 0.0))
+            return sk_fail(SK_ERR_INVALID, "entry %d: the calibration pair {offset, unit} must be finite", i / 2);
+    SK_ENTER(c);
+    if ((rc = sk_live_session_info(c, handle, nullptr, nullptr, nullptr, nullptr))) return rc;
+    return sk_live_session_reset(c, handle, slots, m, cal2);
+}
+
+int sk_live_gate_fetch(int32_t handle, sk_live_gate_info *gate, sk_hmms_rec *rec)
+{
+    int rc = check_live_handle(handle);
+    if (rc) return rc;
+    SK_ENTER(c);
+    const sk_live_gate_info *k_gate = nullptr;
+    const sk_hmms_rec *k_rec = nullptr;
+    int32_t m = 0;
+    if ((rc = sk_live_session_gate_last(c, handle, &k_gate, &k_rec, &m))) return rc;
+    if (m == 0) return SK_OK;
+    if (gate) SK_HIP(hipMemcpyAsync(gate, k_gate, (size_t)m * sizeof(sk_live_gate_info), hipMemcpyDeviceToHost, c->stream));
+    if (rec) SK_HIP(hipMemcpyAsync(rec, k_rec, (size_t)m * sizeof(sk_hmms_rec), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_live_gate_fetch_dev(int32_t handle, sk_live_gate_info *d_gate, sk_hmms_rec *d_rec)
+{
+    int rc = check_live_handle(handle);
+    if (rc) return rc;
+    SK_ENTER(c);
+    const sk_live_gate_info *k_gate = nullptr;
+    const sk_hmms_rec *k_rec = nullptr;
+    int32_t m = 0;
+    if ((rc = sk_live_session_gate_last(c, handle, &k_gate, &k_rec, &m))) return rc;
+    if (m == 0) return SK_OK;
+    if (d_gate) SK_HIP(hipMemcpyAsync(d_gate, k_gate, (size_t)m * sizeof(sk_live_gate_info), hipMemcpyDeviceToDevice, c->stream));
+    if (d_rec) SK_HIP(hipMemcpyAsync(d_rec, k_rec, (size_t)m * sizeof(sk_hmms_rec), hipMemcpyDeviceToDevice, c->stream));
+    return SK_OK;
 }
 
 int sk_live_close(int32_t handle)
@@ -3699,6 +3766,17 @@ int sk_live_last_ms(int32_t handle, float *bridge_ms, float *summary_ms)
     SK_HIP(hipEventElapsedTime(&prep, c->ev[0], c->ev[1]));
     if (bridge_ms) *bridge_ms = prep;
     if (summary_ms) *summary_ms = best;
+    return SK_OK;
+}
+
+int sk_live_gate_last_ms(int32_t handle, float *hmm_ms, float *gate_ms)
+{
+    if (int rc = check_live_handle(handle)) return rc;
+    SK_ENTER(c);
+    float h = 0.f, g = 0.f;
+    if (int rc = sk_live_session_gate_ms(c, handle, &h, &g)) return rc;
+    if (hmm_ms) *hmm_ms = h;
+    if (gate_ms) *gate_ms = g;
     return SK_OK;
 }
 

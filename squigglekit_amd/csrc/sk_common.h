@@ -653,6 +653,7 @@ int64_t sk_evs_session_rows(sk_ctx *c, int32_t handle, int64_t maxlen);   // sta
 int sk_evs_session_open(sk_ctx *c, const sk_det_params *p, int32_t nslots, int32_t *handle);
 int sk_evs_session_info(sk_ctx *c, int32_t handle, int32_t *nslots);                         // SK_ERR_INVALID: unknown handle
 int sk_evs_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const int32_t *len);
+int sk_evs_session_check_cap(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const int32_t *len, int64_t cap);
 int sk_evs_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
 int sk_evs_session_push(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
                         const int32_t *d_len, const int32_t *d_end, int64_t per, int64_t *d_off, const int32_t *host_slots,
@@ -666,7 +667,16 @@ void sk_evs_close_all(sk_ctx *c);           // sk_shutdown: the context's device
 
 // ---- HMM sessions (sk_hmmstream.hip) ----
 // The kernel, the session and the sk_hmms_* entries are all in that file; the runtime only closes what is left open.
+// sk_hmms_session_*: the session without the entry checks, for a gated live session's own HMM session -- device
+// pointers, nothing synchronised, k_hmms_push and k_hmms_reset as the entries launch them.
+#define SK_HMMS_CAP 0x7fffff00              // samples a slot can hold
 void sk_hmms_close_all(sk_ctx *c);          // sk_shutdown: the context's device is current
+int sk_hmms_session_open(sk_ctx *c, const sk_hmm_model *model, int32_t nslots, int32_t *handle);
+int sk_hmms_session_push_dev_i16(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows,
+                                 int64_t stride, const int32_t *d_len, sk_hmms_rec *d_out);
+int sk_hmms_session_reset_dev(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const double *d_cal2);
+int64_t sk_hmms_session_bytes(sk_ctx *c, int32_t handle);
+int sk_hmms_session_close(sk_ctx *c, int32_t handle);
 
 // ---- live mapping sessions (sk_live.hip) ----
 // The session behind sk_live_*: an event session and a mapping session of its own (opened and closed through the
@@ -675,8 +685,11 @@ void sk_hmms_close_all(sk_ctx *c);          // sk_shutdown: the context's device
 // nothing but the ABI's limits -- the session checks them against nslots; every d_ pointer a device pointer; host_len /
 // host_end as in sk_evs_session_push (nullptr: a device-form push).  d_best is written only when rule is given.
 int sk_live_session_open(sk_ctx *c, const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off,
-                         int32_t ntargets, int32_t nslots, int32_t *handle);
+                         int32_t ntargets, int32_t nslots, const sk_hmm_model *model /* nullptr: ungated */,
+                         const sk_live_gate *gate, int32_t *handle);
 int sk_live_session_info(sk_ctx *c, int32_t handle, int32_t *nslots, int32_t *ntargets, int32_t *evs, int32_t *map);
+// the last push's gate records and HMM records (device, [m]); SK_ERR_INVALID on an ungated session
+int sk_live_session_gate_last(sk_ctx *c, int32_t handle, const sk_live_gate_info **d_gate, const sk_hmms_rec **d_rec, int32_t *m);
 int sk_live_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, int64_t stride, const int32_t *len);
 int sk_live_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p);
 int sk_live_session_push(sk_ctx *c, int32_t handle, const int32_t *host_slots, const int32_t *d_slots, int32_t m,
@@ -685,9 +698,39 @@ int sk_live_session_push(sk_ctx *c, int32_t handle, const int32_t *host_slots, c
                          sk_live_info *d_info, sk_live_best *d_best);
 int sk_live_session_last(sk_ctx *c, int32_t handle, const int64_t **d_off, const double **d_values, int32_t *m);
 int sk_live_session_best_ms(sk_ctx *c, int32_t handle, float *ms);
-int sk_live_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m);
+int sk_live_session_gate_ms(sk_ctx *c, int32_t handle, float *hmm_ms, float *gate_ms);
+int sk_live_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const double *cal2 /* gated only */);
 int sk_live_session_close(sk_ctx *c, int32_t handle);
-void sk_live_close_all(sk_ctx *c);          // sk_shutdown, BEFORE the two tables it holds handles of are emptied
+void sk_live_close_all(sk_ctx *c);          // sk_shutdown, BEFORE the tables it holds handles of are emptied
+
+// ---- the gate of a gated live session (sk_livegate.hip) ----
+// The kernels between the inner sessions of a gated live session: the HMM chunk lengths ahead of the HMM push, and
+// k_live_gate behind both pushes -- decision, hold ring, released rows.  Every pointer a device pointer.
+struct sk_gate_slot {                       // 40 bytes: a slot's gate record and what the ring remembers
+    sk_live_gate_info g;
+    int32_t last_drop;                      // the start of the event the ring overwrote last (dropped > 0)
+    int32_t pad;
+};
+struct sk_gate_args {
+    sk_gate_slot        *state;             // [nslots]
+    sk_det_event        *ring;              // [nslots][G]: event number e of the slot at e % G
+    const sk_live_info  *live;              // [nslots]: the live side's records (ended, as of the push before)
+    int32_t              nslots, G;
+    const int32_t       *slots;             // [m]
+    int32_t              m;
+    const int32_t       *len, *end;         // [m]; end may be nullptr
+    const sk_hmms_rec   *hrec;              // [m]: the HMM push's records
+    const sk_det_event  *stage;             // [m][per]: the event push's staging rows
+    int64_t              per;
+    const int64_t       *eoff;              // [m + 1]: the event push's offsets
+    sk_det_event        *rel;               // [m][G + per] out: the released rows
+    int64_t             *rcnt;              // [m] out: their counts
+    sk_live_gate_info   *ginfo;             // [m] out
+    sk_live_gate         rule;
+};
+int sk_livegate_reset(sk_ctx *c, sk_gate_slot *state, int32_t nslots, const int32_t *d_slots, int32_t m);
+int sk_livegate_lengths(sk_ctx *c, const sk_gate_args &a, int32_t *d_hlen);
+int sk_livegate_release(sk_ctx *c, const sk_gate_args &a);
 
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries
 int64_t sk_scan_blocks(int64_t n);

@@ -439,6 +439,21 @@ int sk_evs_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32_
     return SK_OK;
 }
 
+// host form of a session that keeps a second, smaller sample cap per slot (a gated live session: the HMM side's)
+int sk_evs_session_check_cap(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const int32_t *len, int64_t cap)
+{
+    evs_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    if (int rc = refresh_mirror(c, z)) return rc;
+    for (int32_t i = 0; i < m; i++) {
+        const int32_t s = slots[i];
+        if (s < 0 || s >= z->nslots) continue;
+        if ((int64_t)z->n[(size_t)s] + len[i] > cap)
+            return sk_fail(SK_ERR_UNSUPPORTED, "entry %d: slot %d would hold more than %lld samples", i, s, (long long)cap);
+    }
+    return SK_OK;
+}
+
 int sk_evs_session_stage(sk_ctx *c, int32_t handle, int which, size_t bytes, void **p)
 {
     evs_session *z = session_of(c, handle);

@@ -27,7 +27,8 @@
 
 namespace {
 
-constexpr int32_t HMMS_CAP = 0x7fffff00;      // samples a slot can hold: the one-shot call's cap
+constexpr int32_t HMMS_CAP = SK_HMMS_CAP;     // samples a slot can hold: the one-shot call's cap (sk_common.h: a gated
+                                              // live session refuses by the same number)
 
 struct hmms_slot {               // 224 bytes
     double  v[HS];
@@ -327,18 +328,9 @@ void sk_hmms_close_all(sk_ctx *c)
         if (c->hmms_sessions[i]) { destroy((hmms_session *)c->hmms_sessions[i]); c->hmms_sessions[i] = nullptr; }
 }
 
-// ------------------------------------------------------------------ the C ABI
-// What the arguments alone decide is refused first, before a context is looked for; then what needs the session: is the
-// handle open, does a slot lie below its nslots, would a slot pass its cap.
-extern "C" {
-
-int sk_hmms_open(const sk_hmm_model *model, int32_t nslots, int32_t *handle)
+// ---- the session behind sk_hmms_open, and the device forms a gated live session (sk_live.hip) drives its own with ----
+int sk_hmms_session_open(sk_ctx *c, const sk_hmm_model *model, int32_t nslots, int32_t *handle)
 {
-    if (const char *what = sk_hmm_model_error(model)) return sk_fail(SK_ERR_INVALID, "sk_hmm_model: %s", what);
-    if (!handle) return sk_fail(SK_ERR_INVALID, "NULL handle");
-    if (nslots < 1 || nslots > SK_HMMS_MAX_SLOTS)
-        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_HMMS_MAX_SLOTS);
-    SK_ENTER(c);
     int h = -1;
     for (int i = 0; i < SK_HMMS_MAX_SESSIONS; i++) if (!c->hmms_sessions[i]) { h = i; break; }
     if (h < 0) return sk_fail(SK_ERR_INVALID, "%d HMM sessions are open on this context already", SK_HMMS_MAX_SESSIONS);
@@ -356,6 +348,56 @@ int sk_hmms_open(const sk_hmm_model *model, int32_t nslots, int32_t *handle)
     c->hmms_sessions[h] = z;
     *handle = h;
     return SK_OK;
+}
+
+// int16 rows, every pointer a device pointer, nothing synchronised, no event recorded
+int sk_hmms_session_push_dev_i16(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows,
+                                 int64_t stride, const int32_t *d_len, sk_hmms_rec *d_out)
+{
+    hmms_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    z->mirror_stale = true;
+    return launch_push(c, z, SK_FEED_I16, d_slots, m, d_rows, stride, d_len, nullptr, d_out);
+}
+
+// d_slots [m] (nullptr: all, m = nslots), d_cal2 [m][2] or nullptr: device pointers, nothing synchronised
+int sk_hmms_session_reset_dev(sk_ctx *c, int32_t handle, const int32_t *d_slots, int32_t m, const double *d_cal2)
+{
+    hmms_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    z->mirror_stale = true;
+    return launch_reset(c, z, d_slots, m, d_cal2);
+}
+
+int64_t sk_hmms_session_bytes(sk_ctx *c, int32_t handle)
+{
+    hmms_session *z = session_of(c, handle);
+    return z ? (int64_t)z->nslots * (int64_t)sizeof(hmms_slot) : 0;
+}
+
+int sk_hmms_session_close(sk_ctx *c, int32_t handle)
+{
+    hmms_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    SK_HIP(hipStreamSynchronize(c->stream));
+    destroy(z);
+    c->hmms_sessions[handle] = nullptr;
+    return SK_OK;
+}
+
+// ------------------------------------------------------------------ the C ABI
+// What the arguments alone decide is refused first, before a context is looked for; then what needs the session: is the
+// handle open, does a slot lie below its nslots, would a slot pass its cap.
+extern "C" {
+
+int sk_hmms_open(const sk_hmm_model *model, int32_t nslots, int32_t *handle)
+{
+    if (const char *what = sk_hmm_model_error(model)) return sk_fail(SK_ERR_INVALID, "sk_hmm_model: %s", what);
+    if (!handle) return sk_fail(SK_ERR_INVALID, "NULL handle");
+    if (nslots < 1 || nslots > SK_HMMS_MAX_SLOTS)
+        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_HMMS_MAX_SLOTS);
+    SK_ENTER(c);
+    return sk_hmms_session_open(c, model, nslots, handle);
 }
 
 int sk_hmms_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
@@ -476,12 +518,7 @@ int sk_hmms_close(int32_t handle)
 {
     if (int rc = check_handle(handle)) return rc;
     SK_ENTER(c);
-    hmms_session *z = session_of(c, handle);
-    if (!z) return SK_ERR_INVALID;
-    SK_HIP(hipStreamSynchronize(c->stream));
-    destroy(z);
-    c->hmms_sessions[handle] = nullptr;
-    return SK_OK;
+    return sk_hmms_session_close(c, handle);
 }
 
 int sk_last_hmms_plan(int64_t *state_bytes, int64_t *guard_hits)

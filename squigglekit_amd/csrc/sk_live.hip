@@ -22,6 +22,11 @@
 // The order of a push: event push, count, scan, fill, the read-back of off (m + 1 int64: sk_map_session_push plans on the
 // host from lengths), the mapping push on the compact values, the summary.  Every division is a correctly rounded IEEE
 // operation (-ffp-contract=off is the build's rule), so the values are numpy's bit for bit.
+//
+// A GATED session ("Gated live sessions" in the header; kernels in sk_livegate.hip) also owns an HMM session.  Its push:
+// event push, the HMM chunk lengths, the HMM push (k_hmms_push, unchanged, on the same rows), the gate, a scan of the
+// released counts -- and then count, scan, fill and the rest exactly as above, with stage / per / eoff pointing at the
+// released rows instead of the event push's staging rows.  The read-back stays the m + 1 offsets.
 #include "sk_common.h"
 #include "sk_prepw_dev.h"
 #include <math.h>
@@ -198,15 +203,26 @@ struct live_session {
     bool    pushed = false;
     hipEvent_t ev_best[2] = {nullptr, nullptr};     // around the last push's summary kernel (sk_live_last_ms)
     bool    best_timed = false;
+    // a gated session (sk_livegate.hip): its HMM session, the rule, and per slot a gate record and a ring of G events
+    bool    gated = false;
+    int32_t hmms = -1, G = 0;
+    sk_live_gate rule = {};
+    sk_buf gstate, ring;                    // sk_gate_slot [nslots], sk_det_event [nslots][G]
+    // the last push: HMM chunk lengths, HMM records, gate records, released rows [m][G + per], their counts / offsets
+    sk_buf hlen, hrec, ginfo, rel, roff;
+    hipEvent_t ev_gate[4] = {nullptr, nullptr, nullptr, nullptr};   // around the HMM side, around the gate and its scan
+    bool    gate_timed = false;
 };
 
 void free_buf(sk_buf *b) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
 
 void destroy(live_session *z)
 {
-    sk_buf *bufs[] = {&z->state, &z->hold, &z->off, &z->values, &z->host[0], &z->host[1], &z->host[2], &z->host[3]};
+    sk_buf *bufs[] = {&z->state, &z->hold, &z->off, &z->values, &z->host[0], &z->host[1], &z->host[2], &z->host[3],
+                      &z->gstate, &z->ring, &z->hlen, &z->hrec, &z->ginfo, &z->rel, &z->roff};
     for (sk_buf *b : bufs) free_buf(b);
     for (hipEvent_t e : z->ev_best) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : z->ev_gate) if (e) (void)hipEventDestroy(e);
     delete z;
 }
 
@@ -231,7 +247,7 @@ int launch_reset(sk_ctx *c, live_session *z, const int32_t *d_slots, int32_t m)
 } // namespace
 
 int sk_live_session_open(sk_ctx *c, const sk_det_params *p, int32_t calib, const double *targets, const int64_t *target_off,
-                         int32_t ntargets, int32_t nslots, int32_t *handle)
+                         int32_t ntargets, int32_t nslots, const sk_hmm_model *model, const sk_live_gate *gate, int32_t *handle)
 {
     int h = -1;
     for (int i = 0; i < SK_LIVE_MAX_SESSIONS; i++) if (!c->live_sessions[i]) { h = i; break; }
@@ -245,15 +261,31 @@ int sk_live_session_open(sk_ctx *c, const sk_det_params *p, int32_t calib, const
         destroy(z);
         return rc;
     }
+    if (model && (rc = sk_hmms_session_open(c, model, nslots, &z->hmms))) {
+        (void)sk_evs_session_close(c, z->evs);
+        (void)sk_map_session_close(c, z->map);
+        destroy(z);
+        return rc;
+    }
     rc = sk_reserve(c, &z->state, (size_t)nslots * sizeof(sk_live_info));
     if (!rc) rc = sk_reserve(c, &z->hold, (size_t)nslots * (size_t)calib * sizeof(double));
     // (the hold buffers need no clearing: an entry is read only below the slot's event count)
     for (int i = 0; i < 2 && !rc; i++)
         if (hipEventCreate(&z->ev_best[i]) != hipSuccess) rc = sk_fail(SK_ERR_HIP, "creating the summary's events failed");
     if (!rc) rc = launch_reset(c, z, nullptr, nslots);
+    if (!rc && model) {
+        z->gated = true; z->rule = *gate; z->G = gate->hold;
+        rc = sk_reserve(c, &z->gstate, (size_t)nslots * sizeof(sk_gate_slot));
+        // (the rings need no clearing: an entry is read only below the slot's ring count)
+        if (!rc) rc = sk_reserve(c, &z->ring, (size_t)nslots * (size_t)z->G * sizeof(sk_det_event));
+        if (!rc) rc = sk_livegate_reset(c, (sk_gate_slot *)z->gstate.p, nslots, nullptr, nslots);
+        for (int i = 0; i < 4 && !rc; i++)
+            if (hipEventCreate(&z->ev_gate[i]) != hipSuccess) rc = sk_fail(SK_ERR_HIP, "creating the gate's events failed");
+    }
     if (rc) {
         (void)sk_evs_session_close(c, z->evs);
         (void)sk_map_session_close(c, z->map);
+        if (z->hmms >= 0) (void)sk_hmms_session_close(c, z->hmms);
         destroy(z);
         return rc;
     }
@@ -273,6 +305,17 @@ int sk_live_session_info(sk_ctx *c, int32_t handle, int32_t *nslots, int32_t *nt
     return SK_OK;
 }
 
+int sk_live_session_gate_last(sk_ctx *c, int32_t handle, const sk_live_gate_info **d_gate, const sk_hmms_rec **d_rec, int32_t *m)
+{
+    live_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    if (!z->gated) return sk_fail(SK_ERR_INVALID, "live session %d has no gate", handle);
+    *d_gate = (const sk_live_gate_info *)z->ginfo.p;
+    *d_rec = (const sk_hmms_rec *)z->hrec.p;
+    *m = z->pushed ? z->last_m : 0;
+    return SK_OK;
+}
+
 // what a push is refused for by the session: slots against nslots and for doubles, (len given: the host form) samples
 // for an ended slot and a total past 2^31 - 1, a stride whose events could pass the mapping side's chunk limit
 int sk_live_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, int64_t stride, const int32_t *len)
@@ -282,8 +325,13 @@ int sk_live_session_check(sk_ctx *c, int32_t handle, const int32_t *slots, int32
     int rc;
     if ((rc = sk_map_session_check_slots(c, z->map, slots, m))) return rc;
     if (len && (rc = sk_evs_session_check(c, z->evs, slots, m, len))) return rc;
+    if (len && z->gated && (rc = sk_evs_session_check_cap(c, z->evs, slots, m, len, SK_HMMS_CAP))) return rc;
     if (stride >= 0) {
         const int64_t per = sk_evs_session_rows(c, z->evs, stride);
+        if (z->gated && (int64_t)(z->C - 1) + z->G + per > SK_MAP_MAX_CHUNK)
+            return sk_fail(SK_ERR_UNSUPPORTED, "live session push: calib - 1 = %d held levels, hold = %d gated events and up to %lld "
+                           "events of %lld samples could make a chunk above %d points", z->C - 1, z->G, (long long)per,
+                           (long long)stride, SK_MAP_MAX_CHUNK);
         if ((int64_t)(z->C - 1) + per > SK_MAP_MAX_CHUNK)
             return sk_fail(SK_ERR_UNSUPPORTED, "live session push: calib - 1 = %d held levels and up to %lld events of %lld samples "
                            "could make a chunk above %d points", z->C - 1, (long long)per, (long long)stride, SK_MAP_MAX_CHUNK);
@@ -314,9 +362,17 @@ int sk_live_session_push(sk_ctx *c, int32_t handle, const int32_t *host_slots, c
     // everything the push needs of its own is reserved before anything moves
     const size_t off_bytes = ((size_t)m + 1 + (size_t)sk_scan_blocks(m)) * sizeof(int64_t);
     if ((rc = sk_reserve(c, &z->off, off_bytes))) return rc;
-    if ((rc = sk_reserve(c, &z->values, (size_t)m * (size_t)((int64_t)(z->C - 1) + per) * sizeof(double)))) return rc;
+    const int64_t rper = z->gated ? (int64_t)z->G + per : per;      // rows per entry the bridge reads: released, or staged
+    if ((rc = sk_reserve(c, &z->values, (size_t)m * (size_t)((int64_t)(z->C - 1) + rper) * sizeof(double)))) return rc;
     int64_t *d_off = (int64_t *)z->off.p, *d_bsum = d_off + m + 1;
     double *d_values = (double *)z->values.p;
+    if (z->gated) {
+        if ((rc = sk_reserve(c, &z->hlen, (size_t)m * sizeof(int32_t)))) return rc;
+        if ((rc = sk_reserve(c, &z->hrec, (size_t)m * sizeof(sk_hmms_rec)))) return rc;
+        if ((rc = sk_reserve(c, &z->ginfo, (size_t)m * sizeof(sk_live_gate_info)))) return rc;
+        if ((rc = sk_reserve(c, &z->rel, (size_t)m * (size_t)rper * sizeof(sk_det_event)))) return rc;
+        if ((rc = sk_reserve(c, &z->roff, off_bytes))) return rc;
+    }
 
     SK_HIP(hipEventRecord(c->ev[2], c->stream));            // sk_last_kernel_ms: main = the whole push, prep = the bridge
     if ((rc = sk_evs_session_push(c, z->evs, d_slots, m, d_rows, stride, d_len, d_end, per, nullptr, host_slots, host_len, host_end)))
@@ -329,7 +385,36 @@ int sk_live_session_push(sk_ctx *c, int32_t handle, const int32_t *host_slots, c
     int64_t eper = 0;
     if ((rc = sk_evs_session_staging(c, z->evs, &a.stage, &eper))) return rc;
     if (em != m || eper != per) return sk_fail(SK_ERR_INVALID, "internal: the event push left %d entries of %lld rows", em, (long long)eper);
+    sk_gate_args g;
+    if (z->gated) {
+        // the HMM side: lengths masked by the gate's state and the slot's END (both as the push before left them: the
+        // event push above touches neither), then k_hmms_push on the same rows
+        g.state = (sk_gate_slot *)z->gstate.p; g.ring = (sk_det_event *)z->ring.p; g.live = (const sk_live_info *)z->state.p;
+        g.nslots = z->nslots; g.G = z->G; g.slots = d_slots; g.m = m; g.len = d_len; g.end = d_end;
+        g.hrec = (const sk_hmms_rec *)z->hrec.p; g.stage = a.stage; g.per = per; g.eoff = a.eoff;
+        g.rel = (sk_det_event *)z->rel.p; g.rcnt = (int64_t *)z->roff.p; g.ginfo = (sk_live_gate_info *)z->ginfo.p;
+        g.rule = z->rule;
+        z->gate_timed = false;
+        SK_HIP(hipEventRecord(z->ev_gate[0], c->stream));
+        if ((rc = sk_livegate_lengths(c, g, (int32_t *)z->hlen.p))) return rc;
+        // (the internal form makes none of sk_hmms_push_dev_i16's argument checks.  Its limit m * (stride + 64) <= 2^31
+        // holds because check_evs_push (sk_api.hip) has put the SAME bound on the same m and stride before any live push
+        // gets here: whoever loosens the event session's limit must check k_hmms_push's indexing, or bound it here.)
+        if ((rc = sk_hmms_session_push_dev_i16(c, z->hmms, d_slots, m, d_rows, stride, (const int32_t *)z->hlen.p,
+                                               (sk_hmms_rec *)z->hrec.p)))
+            return rc;
+        SK_HIP(hipEventRecord(z->ev_gate[1], c->stream));
+    }
     SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    if (z->gated) {
+        // the gate, then the bridge below on the released rows in place of the staged ones
+        SK_HIP(hipEventRecord(z->ev_gate[2], c->stream));
+        if ((rc = sk_livegate_release(c, g))) return rc;
+        if ((rc = sk_launch_scan_i64(c, g.rcnt, m, g.rcnt + m + 1, g.rcnt))) return rc;
+        SK_HIP(hipEventRecord(z->ev_gate[3], c->stream));
+        z->gate_timed = true;
+        a.stage = g.rel; a.per = rper; a.eoff = g.rcnt;
+    }
     hipLaunchKernelGGL(k_live_count, dim3((unsigned)m), dim3(64), 0, c->stream, a);
     SK_HIP(hipGetLastError());
     if ((rc = sk_launch_scan_i64(c, d_off, m, d_bsum, d_off))) return rc;
@@ -356,6 +441,11 @@ int sk_live_session_push(sk_ctx *c, int32_t handle, const int32_t *host_slots, c
     c->ev_valid = true;
     c->live_state_bytes = c->evs_state_bytes + c->map_state_bytes             // (both inner pushes have just set theirs)
                           + (int64_t)z->nslots * ((int64_t)z->C * 8 + (int64_t)sizeof(sk_live_info));
+    if (z->gated) {                                         // + the HMM session, the rings and gate slots; lengths, HMM push, gate
+        c->live_state_bytes += sk_hmms_session_bytes(c, z->hmms)
+                               + (int64_t)z->nslots * ((int64_t)z->G * (int64_t)sizeof(sk_det_event) + (int64_t)sizeof(sk_gate_slot));
+        launches += 3;
+    }
     c->live_levels = z->hoff[(size_t)m];
     c->live_launches = launches;
     return SK_OK;
@@ -384,18 +474,42 @@ int sk_live_session_best_ms(sk_ctx *c, int32_t handle, float *ms)
     return SK_OK;
 }
 
-int sk_live_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m)
+// milliseconds of the last push's HMM side (lengths, k_hmms_push) and of its gate (k_live_gate, the scan), from the
+// session's own events
+int sk_live_session_gate_ms(sk_ctx *c, int32_t handle, float *hmm_ms, float *gate_ms)
 {
     live_session *z = session_of(c, handle);
     if (!z) return SK_ERR_INVALID;
+    if (!z->gated) return sk_fail(SK_ERR_INVALID, "live session %d has no gate", handle);
+    *hmm_ms = 0.f; *gate_ms = 0.f;
+    if (!z->gate_timed) return SK_OK;
+    SK_HIP(hipEventSynchronize(z->ev_gate[3]));
+    SK_HIP(hipEventElapsedTime(hmm_ms, z->ev_gate[0], z->ev_gate[1]));
+    SK_HIP(hipEventElapsedTime(gate_ms, z->ev_gate[2], z->ev_gate[3]));
+    return SK_OK;
+}
+
+int sk_live_session_reset(sk_ctx *c, int32_t handle, const int32_t *slots, int32_t m, const double *cal2)
+{
+    live_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    if (cal2 && !z->gated) return sk_fail(SK_ERR_INVALID, "live session %d has no gate: it takes no calibration pairs", handle);
     if (m <= 0) return SK_OK;
     int rc;
     if ((rc = sk_map_session_check_slots(c, z->map, slots, m))) return rc;   // (before either inner session moves)
     if ((rc = sk_evs_session_reset(c, z->evs, slots, m))) return rc;         // (waits for the stream)
     if ((rc = sk_map_session_reset(c, z->map, slots, m))) return rc;
-    void *d_slots;
-    if ((rc = sk_live_session_stage(c, handle, 3, (size_t)m * sizeof(int32_t), &d_slots))) return rc;
+    void *stage;                                            // the pairs (gated, given), then the slots
+    const size_t cal_bytes = cal2 ? 2 * (size_t)m * sizeof(double) : 0;
+    if ((rc = sk_live_session_stage(c, handle, 3, cal_bytes + (size_t)m * sizeof(int32_t), &stage))) return rc;
+    double *d_cal2 = cal2 ? (double *)stage : nullptr;
+    void *d_slots = (char *)stage + cal_bytes;
     SK_HIP(hipMemcpyAsync(d_slots, slots, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (z->gated) {
+        if (cal2) SK_HIP(hipMemcpyAsync(d_cal2, cal2, cal_bytes, hipMemcpyHostToDevice, c->stream));
+        if ((rc = sk_hmms_session_reset_dev(c, z->hmms, (const int32_t *)d_slots, m, d_cal2))) return rc;
+        if ((rc = sk_livegate_reset(c, (sk_gate_slot *)z->gstate.p, z->nslots, (const int32_t *)d_slots, m))) return rc;
+    }
     if ((rc = launch_reset(c, z, (const int32_t *)d_slots, m))) return rc;
     SK_HIP(hipStreamSynchronize(c->stream));               // (slots is the caller's memory)
     return SK_OK;
@@ -408,6 +522,7 @@ int sk_live_session_close(sk_ctx *c, int32_t handle)
     SK_HIP(hipStreamSynchronize(c->stream));
     (void)sk_evs_session_close(c, z->evs);
     (void)sk_map_session_close(c, z->map);
+    if (z->hmms >= 0) (void)sk_hmms_session_close(c, z->hmms);
     destroy(z);
     c->live_sessions[handle] = nullptr;
     return SK_OK;

@@ -3,7 +3,7 @@
     squiggle_map_stream.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
                            [--piece N --overlap N] [--chunk E] [--calib C] [--channels S]
                            [--min_events N] [--max_dist_per_event X] [--min_margin X] [--give_up N]
-                           [--live [--sample_chunk N] [--fused]] [--locus_margin [--hits K]]
+                           [--live [--sample_chunk N] [--fused] [--polya_gate ...]] [--locus_margin [--hits K]]
 
 Inputs and targets are squiggle_map's.  Without --live, events are cut ONCE per read, by api.detect_events on its first
 --prefix samples, and the replay is in event space: a read is dealt to a free channel (a slot of one api.MapStream over
@@ -18,6 +18,17 @@ pushed to the api.MapStream slot of the same number, and api.map_decide runs aft
 --live --fused: the same replay through ONE api.LiveMap: levels, hold-back, normalisation and the hand-over to the mapping
 side happen on the device, and so does the decision unless --piece or --locus_margin is given (merged records and hit
 lists are decided on the host, from the returned records and LiveMap.hits).  The output is --live's, byte for byte.
+--live --polya_gate [--gate_preset P | --gate_model FILE] [--min_body N] [--gate_margin X] [--gate_give_up N]
+[--gate_hold G]: direct RNA.  A read begins with open pore, leader, adapter and poly(A); none of it belongs to a target.
+Every channel's samples also go through the signal HMM of dRNA_polya_stream (api.HmmStream; under a pA --gate_preset a
+BLOW5 record's calibration pair goes to the slot, with --gate_model too: the preset says which units the model is in), and api.polya_decide's rule -- the path ends in TRANSCRIPT, has been there
+--min_body samples, leads every other state by --gate_margin -- opens the channel's gate at the transcript start.  Only
+events that START at or after it are levels of the read: the hold-back, the --calib statistics and the mapping begin
+there.  While the gate is shut the channel keeps its last --gate_hold events, so the ones between the start and the
+decision are not lost.  A read whose gate has not opened after --gate_give_up samples (0: never), or when it ends, prints
+`gate_reject` at that moment.  Lines carry one more column, transcript_start (-1: the gate never opened).  Without --fused
+the gate runs on the host from HmmStream, polya_decide, EventStream and MapStream; with --fused one gated api.LiveMap
+does it on the device; the two print the same lines byte for byte.
 
 --calib C: every level is normalised with the mean and the standard deviation of the read's first C event levels, fixed
 from then on; the read's first push then holds at least those C events.  C = 0 (the default) takes all events of the
@@ -74,6 +85,13 @@ def build_parser():
     p.add_argument("--live", action="store_true", help="replay in sample space: cut events on the GPU as each read's samples arrive")
     p.add_argument("--sample_chunk", type=int, default=2000, help="--live: raw samples per push (default 2000)")
     p.add_argument("--fused", action="store_true", help="--live: one live mapping session -- events, normalisation, mapping and the decision without a host round trip")
+    p.add_argument("--polya_gate", action="store_true", help="--live: map from the transcript start a signal HMM finds (direct RNA): events before it are dropped")
+    p.add_argument("--gate_preset", default="rna_pa", choices=sorted(api.POLYA_PRESETS), help="--polya_gate: the HMM's preset (default rna_pa)")
+    p.add_argument("--gate_model", metavar="FILE", help="--polya_gate: model description (JSON, api.hmm_spec_to_json) in place of the preset's numbers")
+    p.add_argument("--min_body", type=int, default=2000, help="--polya_gate: open when the path has been in TRANSCRIPT for this many samples (default 2000)")
+    p.add_argument("--gate_margin", type=float, default=20.0, help="--polya_gate: ... and TRANSCRIPT leads every other state by this (default 20)")
+    p.add_argument("--gate_give_up", type=int, default=0, help="--polya_gate: reject a read whose gate has not opened after this many samples (0: never)")
+    p.add_argument("--gate_hold", type=int, default=1024, help="--polya_gate: events a channel keeps while its gate is shut, 1 .. 4096 (default 1024)")
     p.add_argument("--locus_margin", action="store_true", help="accept on the margin to the next locus on any target (hit lists) instead of the next target")
     p.add_argument("--hits", type=int, default=2, help="--locus_margin: loci listed per read and target, 1 .. 64 (default 2)")
     return p
@@ -111,13 +129,15 @@ def iter_reads(args):
 
 def read_samples(args, src):
     """[(read id, int16 samples)] of the input: each read's first --prefix samples, for the live replay"""
-    out = []
-    for rid, sig in iter_reads(args):
-        b = api.as_int16_exact(np.asarray(sig)[:args.prefix])
-        if b is None:
-            raise ValueError("read {} is not int16-exact: event detection takes raw samples".format(rid))
-        out.append((rid, np.ascontiguousarray(np.asarray(b).reshape(-1), dtype=np.int16)))
-    return out
+    return [(rid, _prefix_i16(args, rid, sig)) for rid, sig in iter_reads(args)]
+
+
+def _prefix_i16(args, rid, sig):
+    """a read's first --prefix samples as int16"""
+    b = api.as_int16_exact(np.asarray(sig)[:args.prefix])
+    if b is None:
+        raise ValueError("read {} is not int16-exact: event detection takes raw samples".format(rid))
+    return np.ascontiguousarray(np.asarray(b).reshape(-1), dtype=np.int16)
 
 
 def read_levels(args, src):
@@ -396,6 +416,228 @@ def replay_fused(args, targets, reads, src, write):
         raise ValueError("event session: {} slots stopped at a guard".format(guard))
 
 
+def read_samples_cal(args, src):
+    """[(read id, int16 samples, (offset, unit))] for --polya_gate: read_samples with the calibration pair the gate's
+    model sees the samples through.  The pairs come from the file as dRNA_polya_stream takes them (polya_cli.iter_input):
+    the BLOW5 record's under a pA --gate_preset, with or without --gate_model, and (0, 1) otherwise.  Each pair travels
+    with its own record: nothing is looked up by read id."""
+    from .polya_cli import PA_PRESETS, iter_input
+    if args.blow5:
+        reads = iter_input(args, args.gate_preset in PA_PRESETS, args.batch)
+    else:
+        reads = ((rid, sig, None) for rid, sig in iter_reads(args))
+    out = []
+    for rid, sig, cal in reads:
+        out.append((rid, _prefix_i16(args, rid, sig), (0.0, 1.0) if cal is None else cal))
+    return out
+
+
+class _GatedRead(_LiveRead):
+    """a read in a channel of the gated live replay"""
+
+    def __init__(self, rid, samples, cal):
+        _LiveRead.__init__(self, rid, samples)
+        self.cal = cal
+        self.mapped = 0                                             # normalised levels handed to the mapping side
+        self.t0 = -1
+        self.gate, self.ring = _lib.SK_LIVE_GATE_GATING, None       # the gate's state; the host gate's ring of held events
+
+
+class _HostGate:
+    """What a gated api.LiveMap does, from existing parts on the host: HmmStream -> polya_decide -> EventStream -> the
+    filter start >= t0 behind a ring of --gate_hold events -> hold-back and normalisation -> MapStream.  push() returns
+    the slots' states as the LiveMap's info and gate() would; records() pushes the levels of the named entries on."""
+
+    def __init__(self, args, params, ys, S, model):
+        self.args = args
+        self.hs, self.es, self.ms = api.HmmStream(model, S), api.EventStream(params, S), api.MapStream(ys, S)
+        self.hits = self.ms.hits
+
+    def close(self):
+        for x in (self.hs, self.es, self.ms):
+            x.close()
+
+    def reset(self, slots, reads):
+        self.hs.reset(slots, np.array([r.cal for r in reads], dtype=np.float64))
+        self.es.reset(slots)
+        self.ms.reset(slots)
+        for r in reads:
+            r.ring = deque(maxlen=self.args.gate_hold)
+
+    def push(self, live, reads, chunks, end):
+        a = self.args
+        gating = [i for i, r in enumerate(reads) if r.gate == _lib.SK_LIVE_GATE_GATING]
+        hrec = self.hs.push([live[i] for i in gating], [chunks[i] for i in gating])
+        dec = api.polya_decide(hrec, a.min_body, a.gate_margin, a.gate_give_up)
+        off, rec = self.es.push(live, chunks, end=end)
+        was = [r.gate for r in reads]
+        for k, i in enumerate(gating):
+            r = reads[i]
+            if dec[k] == 1:
+                r.gate, r.t0 = _lib.SK_LIVE_GATE_OPEN, int(hrec["enter"][k][api.TRANSCRIPT])
+            elif dec[k] == -1 or end[i]:
+                r.gate = _lib.SK_LIVE_GATE_REJECTED
+        info = np.zeros(len(live), dtype=api.LIVEINFO_DTYPE)
+        gate = np.zeros(len(live), dtype=api.GATE_DTYPE)
+        self.handed = []
+        for i, r in enumerate(reads):
+            new = rec[int(off[i]):int(off[i + 1])]
+            released = new[:0]
+            if r.gate == _lib.SK_LIVE_GATE_OPEN:
+                cand = (list(r.ring) if was[i] == _lib.SK_LIVE_GATE_GATING else []) + list(new)
+                keep = [e for e in cand if int(e["start"]) >= r.t0]
+                released = np.array(keep, dtype=rec.dtype) if keep else new[:0]
+                r.ring.clear()
+            elif r.gate == _lib.SK_LIVE_GATE_GATING:
+                r.ring.extend(new)
+            # ---- the live side on the released events: replay_live's hold-back and normalisation
+            lev = released["sum"].astype(np.float64) / released["length"].astype(np.float64)
+            had = len(r.levels)
+            r.levels = np.concatenate([r.levels, lev])
+            state, chunk = _lib.SK_LIVE_CALIBRATING, np.zeros(0)
+            if r.sd is None and r.mean is None:
+                if not (len(r.levels) < a.calib and not r.ended):
+                    head = r.levels[:a.calib]
+                    sd = head.std() if head.size >= 2 else 0.0
+                    if not sd > 0:
+                        r.mean = np.nan                             # undecidable from here on
+                    else:
+                        r.mean, r.sd = head.mean(), sd
+                        had = 0
+            if r.sd is not None:
+                state, chunk = _lib.SK_LIVE_MAPPING, (r.levels[had:] - r.mean) / r.sd
+            elif r.mean is not None:
+                state = _lib.SK_LIVE_UNDECIDABLE
+            self.handed.append(chunk)
+            info[i] = (np.nan, np.nan, len(r.levels), r.mapped + len(chunk), 0, state, int(r.ended), len(lev))
+            gate[i]["state"], gate[i]["t0"] = r.gate, r.t0
+        return info, gate
+
+    def records(self, live, idx):
+        return self.ms.push([live[i] for i in idx], [self.handed[i] for i in idx])
+
+
+class _FusedGate:
+    """the same through one gated api.LiveMap"""
+
+    def __init__(self, args, params, ys, S, model, rule):
+        gate = api.live_gate(model, args.min_body, args.gate_margin, args.gate_give_up, args.gate_hold)
+        self.lm, self.rule = api.LiveMap(params, args.calib, ys, S, gate=gate), rule
+        self.hits = self.lm.hits
+
+    def close(self):
+        self.lm.close()
+
+    def reset(self, slots, reads):
+        self.lm.reset(slots, np.array([r.cal for r in reads], dtype=np.float64))
+
+    def push(self, live, reads, chunks, end):
+        self.res = self.lm.push(live, chunks, end=end, rule=self.rule)
+        gate, _ = self.lm.gate()
+        for r, g in zip(reads, gate):
+            r.gate, r.t0 = int(g["state"]), int(g["t0"])
+        return self.res[1], gate
+
+    def records(self, live, idx):
+        return self.res[0][:, idx]
+
+
+def replay_gated(args, targets, reads, src, write):
+    """--live --polya_gate: replay_live / replay_fused behind a poly(A) gate -- every read's samples also go through the
+    signal HMM, and only the events from the transcript start it finds on reach the calibration head and the mapping
+    session.  One line per read when it is decided, rejected by the gate or found undecidable; the unfused and the fused
+    route print the same lines in the same order."""
+    ys = [t[2] for t in targets]
+    tiling = None
+    if args.piece > 0:
+        ys, tiling = api.tile_targets(ys, args.piece, args.overlap)
+    queue = deque(reads)
+    S, N = args.channels, args.sample_chunk
+    chan = [None] * S
+    params = api.det_params("rna" if args.rna else "dna")
+    if args.gate_model:
+        with open(args.gate_model) as fh:
+            model = api.hmm_model(*api.hmm_spec_from_json(fh.read()))
+    else:
+        model = api.polya_model(args.gate_preset)
+    if model.nstates != 6:
+        raise ValueError("the gate reads the six states of api.POLYA_STATES; the model has {}".format(model.nstates))
+    rule = None
+    if args.fused and tiling is None and not args.locus_margin:
+        rule = api.live_rule(args.min_events, args.max_dist_per_event, args.min_margin, args.give_up)
+    eng = _FusedGate(args, params, ys, S, model, rule) if args.fused else _HostGate(args, params, ys, S, model)
+    dots = "\t.\t.\t.\t.\t.\t.\t.\t.\t.\t"
+    try:
+        while True:
+            fresh = []
+            for s in range(S):
+                if chan[s] is None and queue:
+                    chan[s] = _GatedRead(*queue.popleft())
+                    fresh.append(s)
+            if fresh:
+                eng.reset(fresh, [chan[s] for s in fresh])
+            live = [s for s in range(S) if chan[s] is not None]
+            if not live:
+                break
+            chunks, end = [], []
+            for s in live:
+                r = chan[s]
+                chunks.append(r.samples[r.at:r.at + N])
+                r.at = min(len(r.samples), r.at + N)
+                r.ended = r.at >= len(r.samples)
+                end.append(r.ended)
+            info, gate = eng.push(live, [chan[s] for s in live], chunks, end)
+            # ---- the reads the gate has rejected, the ones that cannot be normalised, then the ones handed levels (or ended)
+            idx = []
+            for i, s in enumerate(live):
+                r = chan[s]
+                state = int(info["state"][i])
+                if int(gate["state"][i]) == _lib.SK_LIVE_GATE_REJECTED:
+                    write("{}{}gate_reject\t0\t0\t-1\n".format(r.rid, dots))
+                    chan[s] = None
+                    continue
+                if state == _lib.SK_LIVE_UNDECIDABLE:
+                    sys.stderr.write("squiggle_map_stream: {} in read {} of {}\n".format(
+                        "fewer than 2 events" if int(info["events"][i]) < 2 else "event levels without deviation", r.rid, src))
+                    write("{}{}.\t0\t0\t{}\n".format(r.rid, dots, r.t0))
+                    chan[s] = None
+                    continue
+                if state != _lib.SK_LIVE_MAPPING:
+                    continue                                        # gating, or held back
+                new, r.mapped = int(info["mapped"][i]) - r.mapped, int(info["mapped"][i])
+                if new == 0 and not r.ended:
+                    continue
+                idx.append(i)
+            if not idx:
+                continue
+            mslots = [live[i] for i in idx]
+            mrec = eng.records(live, idx)
+            hits = api.map_hits(mrec)
+            if tiling is not None:
+                hits = api.merge_tiles(hits, tiling)
+            if rule is not None:
+                dec = eng.res[2]["decision"][idx]
+            else:
+                full = np.zeros(hits.shape, dtype=api.MAPREC_DTYPE)
+                for f in api.HIT_DTYPE.names:
+                    full[f] = hits[f]
+                full["rows"], full["pushes"] = mrec["rows"][:1], mrec["pushes"][:1]
+                dec = decide(args, eng, mslots, full, tiling)
+            for i, s in enumerate(mslots):
+                r = chan[s]
+                word = DECISIONS.get(int(dec[i])) or ("end" if r.ended else None)
+                if word is None:
+                    continue
+                line = map_lines([r.rid], [range(r.mapped)], hits[:, i:i + 1], targets)[0]
+                write("{}\t{}\t{}\t{}\t{}\n".format(line[:-1], word, int(mrec["pushes"][0, i]), r.mapped, r.t0))
+                chan[s] = None
+    finally:
+        eng.close()
+    guard = api.last_event_plan()["guard_hits"]
+    if guard:
+        raise ValueError("event session: {} slots stopped at a guard".format(guard))
+
+
 def main(argv=None):
     parser = build_parser()
     argv = sys.argv[1:] if argv is None else argv
@@ -440,8 +682,19 @@ def main(argv=None):
             parser.error("--channels must be in 1 .. {}".format(_lib.SK_EVS_MAX_SLOTS))
         if args.fused and args.calib > _lib.SK_LIVE_MAX_CALIB:
             parser.error("--fused: --calib must be at most {}".format(_lib.SK_LIVE_MAX_CALIB))
+        if args.polya_gate:
+            if args.min_body < 1:
+                parser.error("--min_body must be at least 1")
+            if not 1 <= args.gate_hold <= _lib.SK_LIVE_MAX_GATE_HOLD:
+                parser.error("--gate_hold must be in 1 .. {}".format(_lib.SK_LIVE_MAX_GATE_HOLD))
+            if args.gate_margin != args.gate_margin:
+                parser.error("--gate_margin must be a number")
+            if args.calib + args.gate_hold + args.sample_chunk > _lib.SK_MAP_MAX_CHUNK:
+                parser.error("--calib + --gate_hold + --sample_chunk must be at most {}".format(_lib.SK_MAP_MAX_CHUNK))
     elif args.fused:
         parser.error("--fused needs --live")
+    if args.polya_gate and not args.live:
+        parser.error("--polya_gate needs --live")
     try:
         targets = load_targets(args.model, args.both)
     except (ValueError, IndexError, OSError) as e:
@@ -450,9 +703,11 @@ def main(argv=None):
 
     _lib.warm_start(args.device, also=())
     src = args.signal or args.blow5 or args.i16
-    sys.stdout.write("\t".join(HEADER) + "\n")
+    sys.stdout.write("\t".join(HEADER + (("transcript_start",) if args.polya_gate else ())) + "\n")
     try:
-        if args.live:
+        if args.polya_gate:
+            replay_gated(args, targets, read_samples_cal(args, src), src, sys.stdout.write)
+        elif args.live:
             (replay_fused if args.fused else replay_live)(args, targets, read_samples(args, src), src, sys.stdout.write)
         else:
             replay(args, targets, read_levels(args, src), src, sys.stdout.write)
