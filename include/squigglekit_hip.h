@@ -1032,6 +1032,81 @@ int sk_hmm_segments_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t 
 int sk_hmm_segments_f64_len(const double *values, const int64_t *in_off, int32_t nreads, const sk_hmm_model *model,
                             int32_t limit, sk_hmm_rec *rec, int64_t *off /* [nreads + 1] */, sk_hmm_segf *seg, int64_t cap);
 
+/* ---- signal HMM: posteriors ---------------------------------------------- */
+/* How much probability stands behind a boundary: forward-backward over the model of the "signal HMM" section, the
+ * expected counts of Baum-Welch, and optionally the posterior of every sample ("Signal HMM posteriors";
+ * tests/hmm_post_ref.py states it in numpy).  Model, samples, calibration, limit and the emission e_j(x) = max(a_0, a_1)
+ * are those of the "signal HMM" section, unchanged.  Every operation below is one correctly rounded float64 operation, in
+ * the order written (no multiply-add).  Constants are given by their bit patterns.
+ *
+ * sk_exp(d):  if not d >= -700.0 (this covers -inf): 0.0.  Otherwise
+ *     k = rint(d * LOG2E)                      round half to even
+ *     r = (d - k * LN2_HI) - k * LN2_LO
+ *     p = C13, then p = p * r + Cq for q = 12 .. 0
+ *     result = ldexp(p, (int)k)                never subnormal: 2^-1010 is normal
+ *     LOG2E = 0x3FF71547652B82FE, LN2_HI = 0x3FE62E42FEE00000, LN2_LO = 0x3DEA39EF35793C76; Cq = the double nearest 1 / q!:
+ *     C0 = C1 = 0x3FF0000000000000, C2 = 0x3FE0000000000000, C3 = 0x3FC5555555555555, C4 = 0x3FA5555555555555,
+ *     C5 = 0x3F81111111111111, C6 = 0x3F56C16C16C16C17, C7 = 0x3F2A01A01A01A01A, C8 = 0x3EFA01A01A01A01A,
+ *     C9 = 0x3EC71DE3A556C734, C10 = 0x3E927E4FB7789F5C, C11 = 0x3E5AE64567F544E4, C12 = 0x3E21EED8EFF8D898,
+ *     C13 = 0x3DE6124613A86D09.
+ * sk_log(s), 1 <= s < 8:  f = s, k = 0; three times: if f > SQRT2 then f = f * 0.5, k = k + 1;
+ *     z = (f - 1.0) / (f + 1.0) -- the IEEE division --, z2 = z * z
+ *     p = D23, then p = p * z2 + Dq for q = 21, 19, .., 1
+ *     result = k * LN2 + (z + z) * p
+ *     SQRT2 = 0x3FF6A09E667F3BCD, LN2 = 0x3FE62E42FEFA39EF; Dq = the double nearest 1 / q: D1 = 0x3FF0000000000000,
+ *     D3 = 0x3FD5555555555555, D5 = 0x3FC999999999999A, D7 = 0x3FC2492492492492, D9 = 0x3FBC71C71C71C71C,
+ *     D11 = 0x3FB745D1745D1746, D13 = 0x3FB3B13B13B13B14, D15 = 0x3FB1111111111111, D17 = 0x3FAE1E1E1E1E1E1E,
+ *     D19 = 0x3FAAF286BCA1AF28, D21 = 0x3FA8618618618618, D23 = 0x3FA642C8590B2164.
+ * lse(c_0 .. c_{K-1}):  m = the maximum in rising index, by `>`; if m == -inf the result is -inf; otherwise s = 0.0, then
+ *     s = s + sk_exp(c_i - m) in rising i; the result is m + sk_log(s) (1 <= s <= K <= 6).  A candidate of -inf adds an
+ *     exact 0.0.
+ * Forward:    alpha_j(0) = linit[j] + e_j(x_0);  alpha_j(t) = lse_i(alpha_i(t-1) + ltrans[i][j]) + e_j(x_t);
+ *             L = lse_j alpha_j(n-1).
+ * Backward:   beta_i(n-1) = 0.0;  u_ij(t) = ltrans[i][j] + (e_j(x_{t+1}) + beta_j(t+1));  beta_i(t) = lse_j u_ij(t).
+ * Posteriors: gamma_j(t) = sk_exp((alpha_j(t) + beta_j(t)) - L);
+ *             xi_ij(t) = sk_exp((alpha_i(t) + u_ij(t)) - L) for t <= n - 2.
+ * Record sk_hmm_post: loglik = L, n_used = n, final_post[j] = gamma_j(n-1); occ[j] starts at 0.0 and takes
+ *     occ[j] += gamma_j(t) for t = n-1 down to 0.  Entries at and above S are 0.0.
+ * Record sk_hmm_counts (optional): for falling t, with m the winning component of state j at x_t (m = 1 when a_1 > a_0),
+ *     n[j][m] += gamma, sx[j][m] += gamma * x, sxx[j][m] += gamma * (x * x), x in model units (after any calibration);
+ *     xi[i][j] += xi_ij(t) for t = n-2 down to 0; init[j] = gamma_j(0).  Every sum starts at 0.0.
+ * Dense posteriors (optional): the caller gives goff [nreads + 1], the running sum of n_used from goff[0] = 0 (it knows n
+ *     from len and limit); gamma[(goff[r] + t) * 6 + j] = gamma_j(t), 0.0 for j >= S.
+ * n = 0: loglik 0.0, flags 0, everything else 0.  L == -inf (a model with a dead end): loglik -inf, flags =
+ *     SK_HMM_POST_IMPOSSIBLE, every probability and count 0.0, dense rows included.
+ * No NaN is ever written: valid input gives no +inf (as in the "signal HMM" section), so alpha, beta and L are finite or
+ *     -inf; lse answers -inf before it would form -inf - -inf; sk_exp is given a finite number or -inf and answers the
+ *     latter with 0.0; and a read with L == -inf is answered with zeros instead of sk_exp(.. - L). */
+#define SK_HMM_POST_IMPOSSIBLE 1
+typedef struct sk_hmm_post {        /* 112 bytes */
+    double  loglik;
+    int32_t n_used, flags;
+    double  final_post[SK_HMM_STATES];
+    double  occ[SK_HMM_STATES];
+} sk_hmm_post;
+typedef struct sk_hmm_counts {      /* 624 bytes */
+    double  n[SK_HMM_STATES][2], sx[SK_HMM_STATES][2], sxx[SK_HMM_STATES][2];
+    double  xi[SK_HMM_STATES][SK_HMM_STATES];       /* [from][to] */
+    double  init[SK_HMM_STATES];
+} sk_hmm_counts;
+/* The arguments of sk_hmm_viterbi_i16 with post [nreads] in rec's place, then counts [nreads] or NULL, then goff
+ * [nreads + 1] and gamma [goff[nreads] * 6] or both NULL.  The checks are sk_hmm_viterbi_*'s; in addition exactly one of
+ * goff / gamma being NULL is SK_ERR_INVALID -- all before the device is looked at.  The host forms also refuse a goff
+ * that is not the running sum of n_used. */
+int sk_hmm_posterior_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,
+                         const sk_hmm_model *model, int32_t limit, sk_hmm_post *post, sk_hmm_counts *counts,
+                         const int64_t *goff, double *gamma);
+/* device-resident form: every pointer is a device pointer but `model` (host); d_len[r] is clamped into [0, stride];
+ * nothing is synchronised.  d_goff is the caller's promise: rows [d_goff[r], d_goff[r] + n_used) of d_gamma are written.
+ * Scratch: 3 072 bytes per 64 reads and 128 samples, and 393 216 bytes per 64 reads of a slice; a large batch is worked
+ * through in slices of whole 64-read groups within a fixed budget. */
+int sk_hmm_posterior_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const double *d_cal2, const sk_hmm_model *model, int32_t limit, sk_hmm_post *d_post,
+                             sk_hmm_counts *d_counts, const int64_t *d_goff, double *d_gamma);
+/* ragged float64 values: read r = values[off[r] .. off[r+1]), x_t = the value. */
+int sk_hmm_posterior_f64_len(const double *values, const int64_t *off, int32_t nreads, const sk_hmm_model *model,
+                             int32_t limit, sk_hmm_post *post, sk_hmm_counts *counts, const int64_t *goff, double *gamma);
+
 /* ---- MotifSeq sessions: search reads chunk by chunk as they arrive --------- */
 /* A session owns K motifs (at most 1 024 points each), nslots slots -- one read in progress each, e.g. one per sequencer
  * channel --, the filter limits, a scale mode and a calibration length W = calib ("MotifSeq sessions";

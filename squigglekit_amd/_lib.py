@@ -239,6 +239,13 @@ HMM_SEG_DTYPE = np.dtype([("state", "<i4"), ("start", "<i4"), ("length", "<i4"),
                           ("sumsq", "<i8", (2,))])
 HMM_SEGF_DTYPE = np.dtype([("state", "<i4"), ("start", "<i4"), ("length", "<i4"), ("n1", "<i4"), ("sum", "<f8", (2,)),
                            ("sumsq", "<f8", (2,))])
+# sk_hmm_post / sk_hmm_counts: a read's posterior record (112 bytes) and its soft counts (624 bytes)
+SK_HMM_POST_IMPOSSIBLE = 1
+HMM_POST_DTYPE = np.dtype([("loglik", "<f8"), ("n_used", "<i4"), ("flags", "<i4"), ("final_post", "<f8", (SK_HMM_STATES,)),
+                           ("occ", "<f8", (SK_HMM_STATES,))])
+HMM_COUNTS_DTYPE = np.dtype([("n", "<f8", (SK_HMM_STATES, 2)), ("sx", "<f8", (SK_HMM_STATES, 2)),
+                             ("sxx", "<f8", (SK_HMM_STATES, 2)), ("xi", "<f8", (SK_HMM_STATES, SK_HMM_STATES)),
+                             ("init", "<f8", (SK_HMM_STATES,))])
 
 class StreamParams(C.Structure):
     """sk_stream_params: what a MotifSeq session is opened with."""
@@ -454,6 +461,13 @@ ABI = {
     "sk_hmm_segments_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp,
                                           C.c_int64]),
     "sk_hmm_segments_f64_len": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp, C.c_int64]),
+    # signal HMM posteriors ("signal HMM: posteriors"; tests/hmm_post_ref.py states them in numpy): the arguments of the
+    # matching sk_hmm_viterbi_* call with post in rec's place, then counts or NULL, then goff and gamma or both NULL
+    "sk_hmm_posterior_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp,
+                                       _vp]),
+    "sk_hmm_posterior_dev_i16": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, C.POINTER(HmmModel), C.c_int32, _vp, _vp,
+                                           _vp, _vp]),
+    "sk_hmm_posterior_f64_len": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(HmmModel), C.c_int32, _vp, _vp, _vp, _vp]),
     # MotifSeq sessions ("MotifSeq sessions" in include/squigglekit_hip.h; tests/stream_ref.py states them in numpy):
     # open(motifs, motif_off, nmotifs, params, handle); push(handle, slots, m, rows, stride, len, out [nmotifs][m]) and
     # its device-resident form; flush(handle, slots, m, out); reset(handle, slots, m, center, scale); close(handle)

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_COUNTS_DTYPE, HMM_DTYPE, HMM_POST_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -2450,6 +2450,148 @@ def hmm_fit(batches, spec, states, rounds, update=("mean", "sigma"), sigma_floor
         history.append({"round": rnd, "reads": pooled["reads"], "segments": nseg, "max_segments": most, "pooled": pooled,
                         "spec": spec})
     return spec, history
+
+
+# ----------------------------------------------------------------------------
+# signal HMM posteriors: forward-backward per read, soft counts, Baum-Welch (the definition: "signal HMM: posteriors" in
+# include/squigglekit_hip.h)
+# ----------------------------------------------------------------------------
+def _posterior_out(R, n_used, counts, dense):
+    """post, counts, goff, gamma and the pointers the C call takes for them"""
+    post = np.zeros(R, dtype=HMM_POST_DTYPE)
+    cnt = np.zeros(R, dtype=HMM_COUNTS_DTYPE) if counts else None
+    goff = gamma = None
+    if dense:
+        goff = np.concatenate([[0], np.cumsum(n_used, dtype=np.int64)]).astype(np.int64)
+        gamma = np.zeros((int(goff[R]), _lib.SK_HMM_STATES), dtype=np.float64)
+    args = (ptr(post), ptr(cnt) if counts else None, ptr(goff) if dense else None,
+            ptr(gamma if gamma is not None and gamma.size else np.zeros(1)) if dense else None)
+    return post, cnt, goff, gamma, args
+
+
+def _n_used(lens, limit):
+    lens = np.minimum(np.asarray(lens, dtype=np.int64), 0x7fffff00)
+    return np.minimum(lens, int(limit)) if limit > 0 else lens
+
+
+def hmm_posterior_batch(sig, lens, model, cal2=None, limit=0, counts=False, dense=False):
+    """Forward-backward over every row of an int16 [R, stride] batch (cal2, limit: hmm_viterbi_batch's): (post, counts,
+    goff, gamma).  post HMM_POST_DTYPE [R]: loglik, n_used, flags (SK_HMM_POST_IMPOSSIBLE: the model gives the read
+    probability 0), final_post[6] = P(state at the last sample), occ[6] = the expected samples per state.  counts
+    HMM_COUNTS_DTYPE [R] or None: the soft counts of Baum-Welch in the model's units (hmm_soft_pool pools them).  dense:
+    gamma float64 [goff[R], 6], read r's posteriors are gamma[goff[r]:goff[r + 1]]; else goff and gamma are None."""
+    L = _lib.ensure_init()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    if sig.ndim != 2:
+        raise ValueError("sig must be [reads, samples]")
+    R, stride = sig.shape
+    lens = (np.full(R, stride, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32))
+    if lens.shape != (R,):
+        raise ValueError("lens must hold one length per row")
+    cal2 = _hmm_cal(cal2, R)
+    post, cnt, goff, gamma, args = _posterior_out(R, _n_used(np.clip(lens, 0, stride), limit), counts, dense)
+    if R and stride:
+        check(L.sk_hmm_posterior_i16(ptr(sig), stride, ptr(lens), R, None if cal2 is None else ptr(cal2), C.byref(model),
+                                     int(limit), *args))
+    return post, cnt, goff, gamma
+
+
+def hmm_posterior_ragged_f64(values, off, model, limit=0, counts=False, dense=False):
+    """hmm_posterior_batch for ragged float64 reads: read r is values[off[r]:off[r + 1]], seen as it is."""
+    L = _lib.ensure_init()
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    R = max(off.size - 1, 0)
+    post, cnt, goff, gamma, args = _posterior_out(R, _n_used(np.diff(off), limit), counts, dense)
+    if values.size == 0:
+        values = np.zeros(1)
+    if R:
+        check(L.sk_hmm_posterior_f64_len(ptr(values), ptr(off), R, C.byref(model), int(limit), *args))
+    return post, cnt, goff, gamma
+
+
+def hmm_posterior(reads, model, limit=0, counts=False, dense=False):
+    """The posteriors of a list of reads of any lengths: (post [R], counts [R] or None, gammas or None) with gammas[r] the
+    float64 [n_used, 6] posteriors of read r.  Integer-valued reads go through the int16 feed, the rest through the
+    float64 one (the same bytes either way); input order is kept."""
+    R = len(reads)
+    post = np.zeros(R, dtype=HMM_POST_DTYPE)
+    cnt = np.zeros(R, dtype=HMM_COUNTS_DTYPE) if counts else None
+    gammas = [None] * R if dense else None
+    ints, arrs, flts = _split_int16(reads)
+    parts = []
+    if ints:
+        parts.append((ints, hmm_posterior_batch(*pack_i16([np.asarray(a).reshape(-1) for a in arrs]), model, None, limit,
+                                                counts, dense)))
+    if flts:
+        parts.append((flts, hmm_posterior_ragged_f64(*pack_f64([reads[i] for i in flts]), model, limit, counts, dense)))
+    for idx, (p, c, goff, gamma) in parts:
+        post[idx] = p
+        if counts:
+            cnt[idx] = c
+        if dense:
+            for k, i in enumerate(idx):
+                gammas[i] = gamma[int(goff[k]):int(goff[k + 1])]
+    return post, cnt, gammas
+
+
+def hmm_soft_pool(post, counts, S):
+    """The soft counts of a batch pooled into hmm_pool's dict, for hmm_refit and hmm_pool_add: "n", "sum", "sumsq" [S, 2]
+    and "trans" [S, S], "init" [S] as float64 -- expected counts in the model's units, summed over the reads in rising
+    order -- and "reads": the reads with samples and a probability above 0 (an integer)."""
+    post, counts = np.asarray(post), np.asarray(counts)
+    if post.shape != counts.shape:
+        raise ValueError("post and counts must describe the same reads")
+    ok = (post["n_used"] > 0) & (post["flags"] == 0)
+    return {"n": counts["n"][:, :S].sum(axis=0), "sum": counts["sx"][:, :S].sum(axis=0),
+            "sumsq": counts["sxx"][:, :S].sum(axis=0), "trans": counts["xi"][:, :S, :S].sum(axis=0),
+            "init": counts["init"][:, :S].sum(axis=0), "reads": int(ok.sum())}
+
+
+def hmm_fit_em(batches, spec, states, rounds, update=("mean", "sigma"), sigma_floor=1.0, min_count=16, pseudo=1.0, limit=0,
+               decode=None):
+    """Baum-Welch: hmm_fit's loop with posteriors in place of paths -- `rounds` times take the soft counts of every batch
+    under the current model, pool them (hmm_soft_pool), refit (hmm_refit).  batches: as hmm_fit takes them.  decode: None
+    for the GPU (hmm_posterior_batch / hmm_posterior_ragged_f64), or decode(batch, model, limit) -> an iterable of (post,
+    counts).  Returns (spec, history): history[i] = {"round", "reads", "loglik", "pooled", "spec"} of round i -- loglik is
+    the total over the reads the model gives a probability above 0, under the model the round STARTED with."""
+    def gpu_decode(batch, model, limit):
+        if isinstance(batch, tuple):
+            sig, lens, cal2 = (tuple(batch) + (None,))[:3]
+            yield hmm_posterior_batch(sig, lens, model, cal2, limit, counts=True)[:2]
+        else:
+            ints, arrs, flts = _split_int16(batch)
+            if ints:
+                yield hmm_posterior_batch(*pack_i16([np.asarray(a).reshape(-1) for a in arrs]), model, None, limit,
+                                          counts=True)[:2]
+            if flts:
+                yield hmm_posterior_ragged_f64(*pack_f64([batch[i] for i in flts]), model, limit, counts=True)[:2]
+    decode = decode or gpu_decode
+    S = len(spec[0])
+    history = []
+    for rnd in range(int(rounds)):
+        model = hmm_model(*spec)
+        pooled, loglik = None, 0.0
+        for batch in (batches() if callable(batches) else [batches]):
+            for post, counts in decode(batch, model, limit):
+                pooled = hmm_pool_add(pooled, hmm_soft_pool(post, counts, S))
+                loglik += float(post["loglik"][post["flags"] == 0].sum())
+        if pooled is None:
+            raise ValueError("hmm_fit_em: no reads")
+        spec = hmm_refit(spec, pooled, states, update, sigma_floor, min_count, pseudo)
+        history.append({"round": rnd, "reads": pooled["reads"], "loglik": loglik, "pooled": pooled, "spec": spec})
+    return spec, history
+
+
+def hmm_boundary_interval(gamma_of_read, states, lo=0.05, hi=0.95):
+    """Where the read enters a set of states, as an interval (host numpy): with c(t) = the sum over j in `states` of
+    gamma_j(t), (the first t at which c(t) > lo, the first t at which c(t) > hi); -1 where there is none."""
+    g = np.asarray(gamma_of_read, dtype=np.float64).reshape(-1, _lib.SK_HMM_STATES)
+    c = np.zeros(len(g))
+    for j in states:
+        c = c + g[:, int(j)]
+    first = lambda mask: int(np.argmax(mask)) if mask.any() else -1   # noqa: E731
+    return first(c > lo), first(c > hi)
 
 
 # ----------------------------------------------------------------------------

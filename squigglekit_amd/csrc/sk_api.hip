@@ -2994,6 +2994,164 @@ int sk_hmm_segments_f64_len(const double *values, const int64_t *in_off, int32_t
 
 } // extern "C"
 
+// ------------------------------------------------------------------ signal HMM: posteriors (sk_hmm_post.hip)
+// The definition: include/squigglekit_hip.h, "signal HMM: posteriors".  Per sub-batch and per slice of whole 64-read
+// groups: the forward kernel, then the backward kernel; records, counts and dense rows of the whole call come back in one
+// copy each.
+namespace {
+
+int check_hmm_post(const sk_hmm_model *model, int32_t limit, int32_t nreads, const sk_hmm_post *post, const int64_t *goff,
+                   const double *gamma)
+{
+    if (const char *what = sk_hmm_model_error(model)) return sk_fail(SK_ERR_INVALID, "sk_hmm_model: %s", what);
+    if (limit < 0) return sk_fail(SK_ERR_INVALID, "limit < 0");
+    if (nreads && !post) return sk_fail(SK_ERR_INVALID, "NULL post");
+    if ((goff == nullptr) != (gamma == nullptr)) return sk_fail(SK_ERR_INVALID, "goff and gamma must both be given or both be NULL");
+    return SK_OK;
+}
+
+// host forms: goff must be the running sum of the samples each read uses, from 0 -- the kernel writes by it
+template <class Len>
+int check_goff_host(const int64_t *goff, int32_t nreads, int32_t limit, Len len_of)
+{
+    if (!goff) return SK_OK;
+    if (goff[0] != 0) return sk_fail(SK_ERR_INVALID, "goff[0] must be 0");
+    for (int32_t r = 0; r < nreads; r++) {
+        int64_t n = len_of(r);
+        if (n > 0x7fffff00) n = 0x7fffff00;
+        if (limit > 0 && n > limit) n = limit;
+        if (goff[r + 1] - goff[r] != n)
+            return sk_fail(SK_ERR_INVALID, "goff[%d + 1] - goff[%d] = %lld, the read uses %lld samples", r, r,
+                           (long long)(goff[r + 1] - goff[r]), (long long)n);
+    }
+    return SK_OK;
+}
+
+// the device side of a host form's outputs in c->hmm (records, then calibration pairs) and c->hmmpostout (counts, goff,
+// dense rows)
+struct PostOut {
+    sk_hmm_post   *post = nullptr;
+    double        *cal = nullptr;
+    sk_hmm_counts *counts = nullptr;
+    int64_t       *goff = nullptr;
+    double        *gamma = nullptr;
+    size_t         gamma_bytes = 0;
+};
+
+int post_out_reserve(sk_ctx *c, int32_t nreads, const double *cal2, bool counts, const int64_t *goff, PostOut *o)
+{
+    int rc;
+    const size_t post_bytes = (size_t)nreads * sizeof(sk_hmm_post);
+    if ((rc = sk_reserve(c, &c->hmm, post_bytes + (size_t)nreads * 2 * sizeof(double)))) return rc;
+    o->post = (sk_hmm_post *)c->hmm.p;
+    if (cal2) {
+        o->cal = (double *)((char *)c->hmm.p + post_bytes);
+        SK_HIP(hipMemcpyAsync(o->cal, cal2, (size_t)nreads * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    const size_t cnt_bytes = counts ? (size_t)nreads * sizeof(sk_hmm_counts) : 0;
+    const size_t goff_bytes = goff ? ((size_t)nreads + 1) * sizeof(int64_t) : 0;
+    o->gamma_bytes = goff ? (size_t)goff[nreads] * SK_HMM_STATES * sizeof(double) : 0;
+    if ((rc = sk_reserve(c, &c->hmmpostout, cnt_bytes + goff_bytes + o->gamma_bytes + 16))) return rc;
+    char *p = (char *)c->hmmpostout.p;
+    if (counts) o->counts = (sk_hmm_counts *)p;
+    if (goff) {
+        o->goff = (int64_t *)(p + cnt_bytes);
+        o->gamma = (double *)(p + cnt_bytes + goff_bytes);
+        SK_HIP(hipMemcpyAsync(o->goff, goff, goff_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return SK_OK;
+}
+
+int post_out_finish(sk_ctx *c, int32_t nreads, const PostOut &o, sk_hmm_post *post, sk_hmm_counts *counts, double *gamma)
+{
+    SK_HIP(hipMemcpyAsync(post, o.post, (size_t)nreads * sizeof(sk_hmm_post), hipMemcpyDeviceToHost, c->stream));
+    if (counts) SK_HIP(hipMemcpyAsync(counts, o.counts, (size_t)nreads * sizeof(sk_hmm_counts), hipMemcpyDeviceToHost, c->stream));
+    if (gamma && o.gamma_bytes) SK_HIP(hipMemcpyAsync(gamma, o.gamma, o.gamma_bytes, hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sk_hmm_posterior_dev_i16(const int16_t *d_sig, int64_t stride, const int32_t *d_len, int32_t nreads,
+                             const double *d_cal2, const sk_hmm_model *model, int32_t limit, sk_hmm_post *d_post,
+                             sk_hmm_counts *d_counts, const int64_t *d_goff, double *d_gamma)
+{
+    int rc = check_i16(d_sig, stride, d_len, nreads);
+    if (rc) return rc;
+    if ((rc = check_hmm_post(model, limit, nreads, d_post, d_goff, d_gamma))) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) return SK_OK;
+    const int64_t npad = sk_hmm_npad(stride, limit);
+    if ((rc = sk_reserve(c, &c->hmmpost, sk_hmm_post_work_bytes(nreads, npad)))) return rc;
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));            // sk_last_kernel_ms: no prep, main = the kernels
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
+    if ((rc = sk_launch_hmm_post(c, SK_FEED_I16, d_sig, stride, d_len, nullptr, nreads, d_cal2, model, limit, npad,
+                                 c->hmmpost.p, d_post, d_counts, d_goff, d_gamma)))
+        return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
+    return SK_OK;
+}
+
+int sk_hmm_posterior_i16(const int16_t *sig, int64_t stride, const int32_t *len, int32_t nreads, const double *cal2,
+                         const sk_hmm_model *model, int32_t limit, sk_hmm_post *post, sk_hmm_counts *counts,
+                         const int64_t *goff, double *gamma)
+{
+    int rc = check_i16(sig, stride, len, nreads);
+    if (rc) return rc;
+    if ((rc = check_hmm_post(model, limit, nreads, post, goff, gamma))) return rc;
+    if ((rc = check_len_host(len, nreads, stride))) return rc;
+    if ((rc = check_goff_host(goff, nreads, limit, [&](int32_t r) { return (int64_t)len[r]; }))) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) return SK_OK;
+    const SubBatches B = sub_batches(nreads, stride);
+    const int64_t npad = sk_hmm_npad(stride, limit);
+    PostOut o;
+    if ((rc = sk_reserve(c, &c->sig, (size_t)nreads * (size_t)stride * sizeof(int16_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->len, (size_t)nreads * sizeof(int32_t)))) return rc;
+    if ((rc = sk_reserve(c, &c->hmmpost, sk_hmm_post_work_bytes(B.per, npad)))) return rc;
+    if ((rc = post_out_reserve(c, nreads, cal2, counts != nullptr, goff, &o))) return rc;
+    rc = ingest_rows(c, B, (int16_t *)c->sig.p, sig, stride, len, nreads,
+                     [&](int32_t r0, int32_t nr, const int16_t *d_sig, const int32_t *d_len) {
+                         return sk_launch_hmm_post(c, SK_FEED_I16, d_sig, stride, d_len, nullptr, nr,
+                                                   o.cal ? o.cal + 2 * (size_t)r0 : nullptr, model, limit, npad, c->hmmpost.p,
+                                                   o.post + r0, o.counts ? o.counts + r0 : nullptr,
+                                                   o.goff ? o.goff + r0 : nullptr, o.gamma);
+                     });
+    if (rc) return rc;
+    return post_out_finish(c, nreads, o, post, counts, gamma);
+}
+
+int sk_hmm_posterior_f64_len(const double *values, const int64_t *off, int32_t nreads, const sk_hmm_model *model,
+                             int32_t limit, sk_hmm_post *post, sk_hmm_counts *counts, const int64_t *goff, double *gamma)
+{
+    if (nreads < 0) return sk_fail(SK_ERR_INVALID, "nreads < 0");
+    int rc = check_hmm_post(model, limit, nreads, post, goff, gamma);
+    if (rc) return rc;
+    if (nreads && (!values || !off)) return sk_fail(SK_ERR_INVALID, "NULL values/off");
+    for (int32_t r = 0; r < nreads; r++)
+        if (off[r + 1] < off[r] || off[r + 1] - off[r] > 0x7fffff00) return sk_fail(SK_ERR_INVALID, "bad length for read %d", r);
+    if ((rc = check_goff_host(goff, nreads, limit, [&](int32_t r) { return off[r + 1] - off[r]; }))) return rc;
+    SK_ENTER(c);
+    if (nreads == 0) return SK_OK;
+    int64_t total, maxlen;
+    if ((rc = stage_ragged_f64(c, values, off, nreads, &total, &maxlen))) return rc;
+    const int64_t npad = sk_hmm_npad(maxlen, limit);
+    PostOut o;
+    if ((rc = sk_reserve(c, &c->hmmpost, sk_hmm_post_work_bytes(nreads, npad)))) return rc;
+    if ((rc = post_out_reserve(c, nreads, nullptr, counts != nullptr, goff, &o))) return rc;
+    if ((rc = sk_launch_hmm_post(c, SK_FEED_F64_NORM, c->sig.p, 0, nullptr, (const int64_t *)c->off.p, nreads, nullptr, model,
+                                 limit, npad, c->hmmpost.p, o.post, o.counts, o.goff, o.gamma)))
+        return rc;
+    return post_out_finish(c, nreads, o, post, counts, gamma);
+}
+
+} // extern "C"
+
 // ------------------------------------------------------------------ MotifSeq sessions (sk_stream.hip)
 // Chunk-by-chunk search: the host forms check what the caller handed over, stage it in the session's own buffers and
 // run the device form; the records come back behind one synchronisation.

@@ -161,6 +161,8 @@ struct sk_ctx {
     sk_buf hmm;       // signal HMM: the sk_hmm_rec records of the host entry points, then their {offset, unit} pairs (sk_hmm.hip)
     sk_buf hmmpath;   // state paths: a slice's back pointers [group][t][lane], its segment counts, the scan's block sums
     sk_buf hmmseg;    // state paths: off [nreads + 1], then the sk_hmm_seg records of the host entry points
+    sk_buf hmmpost;   // posteriors: a slice's L, checkpoints [group][block][state][lane] and slabs (sk_hmm_post.hip)
+    sk_buf hmmpostout; // posteriors: counts, goff and dense rows of the host entry points
     std::vector<double> panel_host;           // laid-out motifs as uploaded (kept alive for the async H2D)
     std::vector<sk_panel_motif> panel_table;  // one entry per motif of at most 1 024 points, group after group
     std::vector<sk_panel_group> panel_groups;
@@ -607,6 +609,15 @@ int sk_launch_hmm_paths(sk_ctx *c, int feed, const void *d_sig, int64_t stride, 
                         int first, sk_hmm_rec *d_rec, int64_t *d_off, sk_hmm_seg *d_seg, int64_t cap);
 int sk_launch_hmm_stats(sk_ctx *c, int feed, const void *d_sig, int64_t stride, const int64_t *d_roff, int32_t nreads,
                         const double *d_cal, const sk_hmm_model *m, const int64_t *d_off, void *d_seg, int64_t cap);
+
+// ---- signal HMM posteriors (sk_hmm_post.hip) ----
+// Forward-backward per read (the header's "signal HMM: posteriors"): records -> d_post, soft counts -> d_counts (or
+// nullptr), dense rows -> d_gamma + d_goff[r] * 6 (or both nullptr).  npad as for the state paths; the scratch of a slice
+// of whole 64-read groups takes sk_hmm_post_work_bytes(nreads, npad) bytes, within the state paths' budget.
+size_t sk_hmm_post_work_bytes(int32_t nreads, int64_t npad);
+int sk_launch_hmm_post(sk_ctx *c, int feed, const void *d_sig, int64_t stride, const int32_t *d_len, const int64_t *d_roff,
+                       int32_t nreads, const double *d_cal, const sk_hmm_model *m, int32_t limit, int64_t npad, void *d_work,
+                       sk_hmm_post *d_post, sk_hmm_counts *d_counts, const int64_t *d_goff, double *d_gamma);
 
 // ---- MotifSeq sessions (sk_stream.hip) ----
 // The session behind the entry points of sk_api.hip: arguments checked there, every pointer a device pointer here.

@@ -2,7 +2,8 @@
 
     dRNA_polya.py -f reads.blow5 | -s signals.tsv | --i16 FILE.npy  [--preset rna_pa|synth_raw] [--limit N] [--rate]
                   [--model FILE.json] [--segments FILE] [--polya_net]
-                  [--refit N --states ADAPTER,POLYA [--model_out FILE.json] [--fit_only]]
+                  [--refit N --states ADAPTER,POLYA [--em] [--model_out FILE.json] [--fit_only]]
+                  [--posterior] [--interval Q]
 
 Output, tab separated, one line per read and no header:
     readID adapter_start adapter_end polya_start polya_end polya_samples score_per_sample
@@ -31,7 +32,20 @@ The best path itself (api.hmm_segments*; these flags take the state-path route, 
 --refit N --states A,B   Viterbi training before the output: the input is streamed N times, the paths of every batch are
                     pooled, and after each pass the mean and sigma of the Gaussian components of the named states (names
                     or indices) are re-estimated (api.hmm_fit, api.hmm_refit).  --model_out FILE.json gets the fitted
-                    description; the usual lines follow under the fitted model unless --fit_only is given."""
+                    description; the usual lines follow under the fitted model unless --fit_only is given.
+                    --em trains by Baum-Welch instead (api.hmm_fit_em): soft counts from the posteriors in place of the
+                    hard counts of the paths.
+
+How much probability stands behind the coordinates (api.hmm_posterior*; forward-backward over the same model, which must
+have the six states of a preset):
+--posterior         appends loglik_per_sample (the read's log-likelihood over the samples used), polya_expected (the
+                    expected number of samples in POLYA) and p_transcript (the probability that the last sample used is
+                    in TRANSCRIPT); `.` `.` `.` for a read without samples or one the model gives probability 0.
+--interval Q        appends polya_start_lo polya_start_hi transcript_start_lo transcript_start_hi, from the posterior of
+                    every sample: the first sample at which P(state in POLYA, CLIFF, TRANSCRIPT) exceeds Q and 1 - Q, and
+                    the same for P(state is TRANSCRIPT) -- the tail starts inside the first pair and ends just before the
+                    second (api.hmm_boundary_interval); `.` where the probability never gets there.
+Without these flags the output is what it was."""
 import argparse
 import sys
 
@@ -67,6 +81,10 @@ def build_parser():
     p.add_argument("--states", default="", help="--refit: the states to re-estimate, names or indices, comma separated")
     p.add_argument("--model_out", metavar="FILE.json", help="--refit: write the fitted model description here")
     p.add_argument("--fit_only", action="store_true", help="--refit: stop after the model is written")
+    p.add_argument("--em", action="store_true", help="--refit: Baum-Welch (soft counts from the posteriors) instead of Viterbi training")
+    p.add_argument("--posterior", action="store_true", help="append loglik_per_sample, polya_expected and p_transcript")
+    p.add_argument("--interval", type=float, default=None, metavar="Q",
+                   help="append the samples at which the tail's start and the transcript's start pass probability Q and 1 - Q")
     return p
 
 
@@ -74,9 +92,9 @@ def _fmt(v):
     return "." if v < 0 else str(int(v))
 
 
-def polya_lines(names, records, rates=None, net=None):
+def polya_lines(names, records, rates=None, net=None, extra=None):
     """the output lines of a batch; rates: per read samples_per_event (float, <= 0 or NaN: none) when --rate is on;
-    net: per read polya_net when --polya_net is on"""
+    net: per read polya_net when --polya_net is on; extra: per read the --posterior / --interval columns"""
     seg = api.polya_segments(records)
     out = []
     for r, rid in enumerate(names):
@@ -92,7 +110,29 @@ def polya_lines(names, records, rates=None, net=None):
                 cols += [".", "."]
         if net is not None:
             cols.append(str(int(net[r])))
+        if extra is not None:
+            cols += extra[r]
         out.append("\t".join(cols) + "\n")
+    return out
+
+
+def posterior_columns(post, gammas, posterior, interval):
+    """per read the --posterior columns (post: HMM_POST_DTYPE) and the --interval Q columns (gammas: per read [n, 6])"""
+    out = []
+    for r in range(len(post)):
+        cols = []
+        ok = int(post["n_used"][r]) > 0 and int(post["flags"][r]) == 0
+        if posterior:
+            cols += (["{}".format(float(post["loglik"][r]) / int(post["n_used"][r])),
+                      "{}".format(float(post["occ"][r][api.POLYA])),
+                      "{}".format(float(post["final_post"][r][api.TRANSCRIPT]))] if ok else [".", ".", "."])
+        if interval is not None:
+            iv = (-1, -1, -1, -1)
+            if ok:
+                iv = (api.hmm_boundary_interval(gammas[r], (api.POLYA, api.CLIFF, api.TRANSCRIPT), interval, 1.0 - interval) +
+                      api.hmm_boundary_interval(gammas[r], (api.TRANSCRIPT,), interval, 1.0 - interval))
+            cols += [_fmt(v) for v in iv]
+        out.append(cols)
     return out
 
 
@@ -146,6 +186,9 @@ class _Batcher:
         self.seg_out, self.net = seg_out, args.polya_net
         self.state_names = api.POLYA_STATES if not args.model else None
         self.limit, self.rate, self.batch, self.input = max(0, args.limit), args.rate, max(1, args.batch), tool_input
+        self.posterior, self.interval = args.posterior, args.interval
+        if (self.posterior or self.interval is not None) and self.model.nstates != 6:
+            raise ValueError("--posterior and --interval need a model of the six states " + ", ".join(api.POLYA_STATES))
         self.names, self.reads, self.cal = [], [], []
 
     def add(self, rid, sig, cal=None):
@@ -183,8 +226,30 @@ class _Batcher:
             except ValueError:
                 raise ValueError("--rate needs raw integer samples (event detection runs on them)") from None
             rates[keep] = samples_per_event(rec[keep], off, ev)
-        sys.stdout.write("".join(polya_lines(self.names, rec, rates, net if self.net else None)))
+        extra = None
+        if self.posterior or self.interval is not None:
+            extra = self.flush_posterior(keep, reads)
+        sys.stdout.write("".join(polya_lines(self.names, rec, rates, net if self.net else None, extra)))
         self.names, self.reads, self.cal = [], [], []
+
+    def flush_posterior(self, keep, reads):
+        """the --posterior / --interval columns of every read of the batch (a read without samples: `.` throughout)"""
+        dense = self.interval is not None
+        post = np.zeros(len(self.reads), dtype=api.HMM_POST_DTYPE)
+        gammas = [None] * len(self.reads)
+        if reads and self.cal:                           # BLOW5 rows under a pA preset
+            buf, lens = api.pack_i16(reads)
+            cal = np.array([self.cal[i] for i in keep], dtype=np.float64)
+            p, _c, goff, gamma = api.hmm_posterior_batch(buf, lens, self.model, cal, self.limit, dense=dense)
+            g = [gamma[int(goff[k]):int(goff[k + 1])] for k in range(len(reads))] if dense else None
+        elif reads:
+            p, _c, g = api.hmm_posterior(reads, self.model, self.limit, dense=dense)
+        if reads:
+            post[keep] = p
+            if dense:
+                for k, i in enumerate(keep):
+                    gammas[i] = g[k]
+        return posterior_columns(post, gammas, self.posterior, self.interval)
 
     def flush_paths(self, keep, reads, rec):
         """the records of the reads with samples through the state-path route, their --segments lines, their polya_net"""
@@ -301,8 +366,10 @@ def main(argv=None):
         parser.error("--limit must be >= 0")
     if args.refit < 0:
         parser.error("--refit must be >= 0")
-    if (args.model_out or args.fit_only or args.states) and not args.refit:
-        parser.error("--states, --model_out and --fit_only go with --refit N")
+    if (args.model_out or args.fit_only or args.states or args.em) and not args.refit:
+        parser.error("--states, --em, --model_out and --fit_only go with --refit N")
+    if args.interval is not None and not 0.0 < args.interval < 0.5:
+        parser.error("--interval Q needs 0 < Q < 0.5")
 
     from . import _lib
     _lib.warm_start(args.device, also=())
@@ -316,8 +383,9 @@ def main(argv=None):
         if args.refit:
             spec = api.polya_spec(args.preset) if spec is None else spec
             states = parse_states(args.states, len(spec[0]), not args.model)
-            spec, _history = api.hmm_fit(fit_batches(args, args.preset in PA_PRESETS, max(1, args.batch)), spec, states,
-                                         args.refit, limit=max(0, args.limit))
+            fit = api.hmm_fit_em if args.em else api.hmm_fit
+            spec, _history = fit(fit_batches(args, args.preset in PA_PRESETS, max(1, args.batch)), spec, states,
+                                 args.refit, limit=max(0, args.limit))
             if args.model_out:
                 with open(args.model_out, "w") as fh:
                     fh.write(api.hmm_spec_to_json(spec))

@@ -12,7 +12,8 @@ concatenation after every push; and one event session (tests/evstream_ref.draw_s
 count, reads of four kinds, cuts, subsets, ENDs and resets) against its statement on detect_ref after every push and
 against the one-shot call on every ended read; and one hit-list round (tests/pair_hits_ref.py: a drawn pair list with its
 K, max_dist and row budget, and a drawn session script whose hits() are read after every push) against the statement
-there.  The DTW pair
+there; and one posterior round (randcases.draw_hmm's models, reads, feeds and switches, a limit of at most 1 200 samples so
+that the statement stays quick, SK_HMM_POST_BLOCK drawn) against tests/hmm_post_ref.py, every double by its bits.  The DTW pair
 lists, their warping paths and the adaptive band are three of the families of tests/randcases.py (`pairs`, `pairpaths`,
 `band`: the draws that used to live here, against tests/pairs_ref.py, tests/pair_paths_ref.py and tests/band_ref.py).
 
@@ -34,6 +35,7 @@ import stream_ref                                     # noqa: E402
 import mapstream_ref                                  # noqa: E402
 import evstream_ref                                   # noqa: E402
 import pair_hits_ref                                  # noqa: E402
+import hmm_post_ref                                   # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -112,6 +114,47 @@ def pairhits_round(rng):
         return "pair list: " + msg
     msg = pair_hits_ref.run_session_case(api, pair_hits_ref.draw_session_case(rng))
     return None if msg is None else "session: " + msg
+
+
+def hmm_post_round(rng):
+    """One drawn posterior call (records, soft counts, dense rows) against tests/hmm_post_ref.py, bit for bit.  Returns
+    None, or what differed."""
+    case = randcases.draw_hmm(rng)
+    limit = case["limit"] if 0 < case["limit"] <= 1200 else 1200
+    env = dict(case["env"])
+    if rng.random() < 0.4:
+        env["SK_HMM_POST_BLOCK"] = "256"
+    counts, dense = bool(rng.random() < 0.8), bool(rng.random() < 0.8)
+    model, reads = randcases.hmm_model_of(api, case), case["reads"]
+    desc = "%d reads, max length %d, %d states%s, limit %d, feed %s%s, counts %s, dense %s, env %s" % (
+        case["R"], case["dmax"], case["S"], " (integer scores)" if case["integer"] else "", limit, case["feed"],
+        " calibrated" if case["calibrated"] else "", counts, dense, env)
+    os.environ.update(env)
+    try:
+        if case["feed"] == "batch":
+            want = hmm_post_ref.posterior_batch(case["model"], case["sig"], case["lens"], case["cal"], limit)
+            post, cnt, goff, gamma = api.hmm_posterior_batch(case["sig"], case["lens"], model, case["cal"], limit, counts, dense)
+        else:
+            want = hmm_post_ref.posterior_reads(case["model"], reads, limit)
+            if case["feed"] == "f64":
+                post, cnt, goff, gamma = api.hmm_posterior_ragged_f64(*api.pack_f64(reads), model, limit, counts, dense)
+            else:
+                post, cnt, gammas = api.hmm_posterior(reads, model, limit, counts, dense)
+                gamma = np.concatenate(gammas + [np.zeros((0, 6))]) if dense else None
+    finally:
+        for key in env:
+            os.environ.pop(key, None)
+    if post.tobytes() != want[0].tobytes():
+        bad = [r for r in range(len(post)) if post[r].tobytes() != want[0][r].tobytes()]
+        return "%s: the record of read %d differs: got %s want %s" % (desc, bad[0], post[bad[0]], want[0][bad[0]])
+    if counts and cnt.tobytes() != want[1].tobytes():
+        bad = [r for r in range(len(cnt)) if cnt[r].tobytes() != want[1][r].tobytes()]
+        return "%s: the counts of read %d differ" % (desc, bad[0])
+    if dense and gamma.tobytes() != want[3].tobytes():
+        return "%s: the dense posteriors differ" % desc
+    if dense and np.isnan(gamma).any():
+        return "%s: a NaN among the dense posteriors" % desc
+    return None
 
 
 def evstream_round(rng):
@@ -445,6 +488,11 @@ def main():
         if msg is not None:
             bad += 1
             print("PAIRHITS mismatch round %d %s" % (rounds, msg))
+        # ---- the signal HMM's posteriors against their statement (tests/hmm_post_ref.py) ----
+        msg = hmm_post_round(rng)
+        if msg is not None:
+            bad += 1
+            print("HMM POSTERIOR mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
