@@ -1372,6 +1372,41 @@ int sk_hmms_close(int32_t handle);
  * was set up -- it only counts up, so one look after any number of pushes covers them all.  Reading it waits for the
  * pushes.  Either pointer may be NULL. */
 int sk_last_hmms_plan(int64_t *state_bytes, int64_t *guard_hits);
+/* Filtered sessions: the forward recursion of "signal HMM: posteriors" carried beside the Viterbi pass.
+ * A session opened with SK_HMMS_FILTER keeps, beside each 224-byte slot, alpha[6] (float64, 48 bytes, an array of its
+ *     own): the slot layout and a plain session's state_bytes = nslots * 224 stay as they are, a filtered session reports
+ *     nslots * 272.  A reset sets every alpha to -inf.  A push appends samples t = n, n + 1, .. for either feed:
+ *       t == 0   alpha_j = linit[j] + e_j(x) for j < S;
+ *       t >= 1   alpha_j = lse_i(alpha_i + ltrans[i][j]) + e_j(x), with sk_exp, sk_log and lse exactly as that section
+ *                states them (the forward step of sk_hmm_posterior_*, transitions of -inf skipped as there);
+ *     x is the value the Viterbi step of the same sample sees, and samples past the slot's cap are ignored by both
+ *     recurrences alike.  The Viterbi side of the slot and sk_hmms_rec are untouched: a filtered session's records are
+ *     byte for byte a plain session's.
+ * The filter of a slot, sk_hmms_filt (64 bytes).  n == 0: all zero.  Otherwise L = lse_j alpha_j in rising j < S,
+ *     loglik = L, post[j] = sk_exp((alpha_j + 0.0) - L) for j < S and 0.0 above: P(state at the newest sample | the samples
+ *     so far).  L == -inf: loglik = -inf, flags = SK_HMM_POST_IMPOSSIBLE, every post 0.0.  No NaN is ever written, by that
+ *     section's argument.  For a read of n samples the one-shot record has beta(n - 1) = 0.0, so loglik and post are
+ *     sk_hmm_posterior_*'s loglik and final_post of the samples the slot has had since its reset, bit for bit, whatever
+ *     the cuts.
+ * sk_hmms_open_ex: flags == 0 is sk_hmms_open exactly; the only other value is SK_HMMS_FILTER; unknown bits are
+ *     SK_ERR_INVALID by the arguments alone, before sk_hmms_open's own refusals.  The four push entries and sk_hmms_reset
+ *     take filtered handles as they are.
+ * sk_hmms_filter (host pointers) reads the named slots as they stand and changes nothing; a slot may appear twice.
+ *     sk_hmms_filter_dev: device pointers, stream-ordered, nothing synchronised; an entry whose slot lies outside
+ *     [0, nslots) gets the all-zero record.
+ * Refusals (SK_ERR_INVALID), in the section's order.  By the arguments alone: a handle outside the table, m < 0, a NULL
+ *     pointer with m > 0, (host form) a slot outside [0, SK_HMMS_MAX_SLOTS).  Then by the session: a handle that is not
+ *     open, (host form) a slot at or above nslots, a handle that was opened without SK_HMMS_FILTER (the message says so).
+ *     A refused call leaves out untouched. */
+#define SK_HMMS_FILTER 1
+typedef struct sk_hmms_filt {       /* 64 bytes */
+    double  loglik;                 /* log P(the samples so far); 0.0 at n == 0 */
+    int32_t n_used, flags;          /* flags: SK_HMM_POST_IMPOSSIBLE */
+    double  post[SK_HMM_STATES];    /* P(state j at sample n - 1 | samples 0 .. n - 1) */
+} sk_hmms_filt;
+int sk_hmms_open_ex(const sk_hmm_model *model, int32_t nslots, int32_t flags, int32_t *handle);
+int sk_hmms_filter(int32_t handle, const int32_t *slots, int32_t m, sk_hmms_filt *out);
+int sk_hmms_filter_dev(int32_t handle, const int32_t *d_slots, int32_t m, sk_hmms_filt *d_out);
 
 /* ---- Live mapping sessions: samples in, mapping records and decisions out --------------------------------------------
  * An event session cuts events, a mapping session continues the DTW; what a selective-sequencing client needs between

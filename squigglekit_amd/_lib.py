@@ -300,6 +300,9 @@ class LiveGate(C.Structure):
 # sk_hmms_rec: a slot's record after a push of an HMM session -- sk_hmm_rec's 40 bytes, then the six scores and the counters
 HMMS_DTYPE = np.dtype([("score", "<f8"), ("final_state", "<i4"), ("n_used", "<i4"), ("enter", "<i4", (SK_HMM_STATES,)),
                        ("v", "<f8", (SK_HMM_STATES,)), ("pushes", "<i4"), ("flags", "<i4")])
+# sk_hmms_filt: a slot's filter in a session opened with SK_HMMS_FILTER -- loglik and P(state at the newest sample)
+SK_HMMS_FILTER = 1
+HMMS_FILT_DTYPE = np.dtype([("loglik", "<f8"), ("n_used", "<i4"), ("flags", "<i4"), ("post", "<f8", (SK_HMM_STATES,))])
 
 # every symbol include/squigglekit_hip.h declares: name -> (restype, argtypes)
 _vp, _i16p, _i32p, _i64p, _dp = (C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32),
@@ -516,6 +519,10 @@ ABI = {
     "sk_hmms_reset": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
     "sk_hmms_close": (C.c_int, [C.c_int32]),
     "sk_last_hmms_plan": (C.c_int, [_vp, _vp]),
+    # ... filtered sessions (SK_HMMS_FILTER): the forward recursion carried beside the Viterbi pass (tests/hmmfilter_ref.py)
+    "sk_hmms_open_ex": (C.c_int, [C.POINTER(HmmModel), C.c_int32, C.c_int32, _i32p]),
+    "sk_hmms_filter": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
+    "sk_hmms_filter_dev": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp]),
     # live mapping sessions ("Live mapping sessions" in include/squigglekit_hip.h; tests/live_ref.py states them on
     # evstream_ref and mapstream_ref): open(params, calib, targets, target_off, ntargets, nslots, handle); push(handle,
     # slots, m, rows, stride, len, end or NULL, rule or NULL, out [T][m], info [m], best [m] or NULL) and its

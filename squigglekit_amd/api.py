@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_COUNTS_DTYPE, HMM_DTYPE, HMM_POST_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_COUNTS_DTYPE, HMM_DTYPE, HMM_POST_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HMMS_FILT_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -3248,9 +3248,18 @@ class HmmStream:
             rec = hs.push_values(slots, chunks)     # chunks: a list of float64 arrays (pA, event levels)
             seg = polya_segments(rec)               # the records are read as hmm_viterbi's are
             dec = polya_decide(rec, min_body=2000, min_margin=50.0, give_up=60000)
+
+    filter=True opens a filtered session (SK_HMMS_FILTER): every slot also carries the forward recursion of the
+    posteriors (hmm_posterior_*), 48 bytes more per slot, and filter(slots) returns HMMS_FILT_DTYPE [m]: loglik of the
+    samples so far and post[j] = P(state j at the newest sample | the samples so far) -- hmm_posterior_*'s loglik and
+    final_post of the same prefix, bit for bit.  The records of push are those of a plain session, byte for byte.
+
+        with HmmStream(polya_model("rna_pa"), nslots=512, filter=True) as hs:
+            rec = hs.push(slots, chunks)
+            dec = polya_decide_post(rec, hs.filter(slots), min_body=2000, min_post=0.99, give_up=60000)
     """
 
-    def __init__(self, model, nslots=1):
+    def __init__(self, model, nslots=1, filter=False):                   # noqa: A002 -- the ABI's word
         self._h = None
         if not 1 <= int(nslots) <= _lib.SK_HMMS_MAX_SLOTS:
             raise ValueError("nslots must be in 1 .. %d, got %d" % (_lib.SK_HMMS_MAX_SLOTS, int(nslots)))
@@ -3258,7 +3267,11 @@ class HmmStream:
         self.model = model
         L = _lib.ensure_init()
         h = C.c_int32(-1)
-        check(L.sk_hmms_open(C.byref(model), self.nslots, C.byref(h)))
+        self.filtered = bool(filter)
+        if self.filtered:
+            check(L.sk_hmms_open_ex(C.byref(model), self.nslots, _lib.SK_HMMS_FILTER, C.byref(h)))
+        else:
+            check(L.sk_hmms_open(C.byref(model), self.nslots, C.byref(h)))
         self._h = h.value
 
     handle = property(lambda self: self._h)
@@ -3329,6 +3342,16 @@ class HmmStream:
         slots = stream_slots(slots, self.nslots)
         return self.push(slots, (np.zeros((slots.size, 0), dtype=np.int16), np.zeros(slots.size, dtype=np.int32)))
 
+    def filter(self, slots):
+        """HMMS_FILT_DTYPE [m] of the named slots as they stand (a slot may appear twice); nothing changes.  The session
+        must have been opened with filter=True."""
+        L = self._open()
+        slots = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        out = np.zeros(slots.size, dtype=HMMS_FILT_DTYPE)
+        if slots.size:
+            check(L.sk_hmms_filter(self._h, ptr(slots), slots.size, ptr(out)))
+        return out
+
     def reset(self, slots, cal2=None):
         """The slots start a new read; cal2 [m, 2] = (offset, unit) per slot for the int16 feed, None: the raw values."""
         L = self._open()
@@ -3376,5 +3399,38 @@ def polya_decide(rec, min_body, min_margin, give_up):
     dec = np.zeros(flat.size, dtype=np.int8)
     if int(give_up) > 0:
         dec[~accept & (n >= int(give_up))] = -1
+    dec[accept] = 1
+    return dec.reshape(rec.shape)
+
+
+def polya_decide_post(rec, filt, min_body, min_post, give_up, min_rate=None):
+    """polya_decide with a probability in the margin's place: rec HMMS_DTYPE and filt HMMS_FILT_DTYPE of the same slots
+    after the same push of a filtered HmmStream under a polya_model.  Returns int8 per record: 1 = accept when
+    final_state == TRANSCRIPT, n_used - enter[TRANSCRIPT] >= min_body and filt.post[TRANSCRIPT] >= min_post; -1 = reject
+    when not accepted and any of: the model gives the samples probability 0 (flags & IMPOSSIBLE); give_up > 0 and
+    n_used >= give_up; min_rate is given, n_used >= min_body and loglik / n_used < min_rate (a read the model fits badly:
+    junk); 0 = wait.  Host only.
+
+    What is probabilistic: THAT the transcript has begun -- under the left-to-right polya_model post[TRANSCRIPT] is the
+    probability, given every sample so far, that the newest sample lies in the transcript.  What is not: WHERE it began
+    -- the entry point still comes from the Viterbi record's enter[TRANSCRIPT], the best single path, and can still move
+    while the read goes on (hmm_posterior_* with dense=True and hmm_boundary_interval bound it on a finished read)."""
+    rec, filt = np.asarray(rec), np.asarray(filt)
+    if rec.shape != filt.shape:
+        raise ValueError("one filter per record: %s records, %s filters" % (rec.shape, filt.shape))
+    flat, ff = rec.reshape(-1), filt.reshape(-1)
+    n = flat["n_used"].astype(np.int64)
+    body = n - flat["enter"].reshape(-1, 6)[:, TRANSCRIPT]
+    post = ff["post"].reshape(-1, 6)[:, TRANSCRIPT]
+    accept = (flat["final_state"] == TRANSCRIPT) & (body >= int(min_body)) & (post >= float(min_post))
+    reject = (ff["flags"] & _lib.SK_HMM_POST_IMPOSSIBLE) != 0
+    if int(give_up) > 0:
+        reject |= n >= int(give_up)
+    if min_rate is not None:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rate = ff["loglik"] / np.maximum(n, 1)
+            reject |= (n > 0) & (n >= int(min_body)) & (rate < float(min_rate))
+    dec = np.zeros(flat.size, dtype=np.int8)
+    dec[reject & ~accept] = -1
     dec[accept] = 1
     return dec.reshape(rec.shape)

@@ -1,7 +1,8 @@
 // sk_hmm_dev.h -- the device text of the signal HMM that the one-shot kernels (sk_hmm.hip) and the HMM sessions
 // (sk_hmmstream.hip) share: the model as a kernel takes it, the LDS tile of a wavefront's 64 rows, the emission, and the
-// recurrence's step without back pointers.  One text, so that a session's scores and tuples are the one-shot call's by
-// construction.  The definition: include/squigglekit_hip.h, "signal HMM".
+// recurrence's step without back pointers; and the text of the posteriors that sk_hmm_post.hip and a filtered session
+// share: sk_exp, sk_log, the log-sum-exp and the forward step.  One text, so that a session's scores, tuples and alpha are
+// the one-shot calls' by construction.  The definition: include/squigglekit_hip.h, "signal HMM" and "signal HMM: posteriors".
 #pragma once
 #include "sk_common.h"
 
@@ -153,6 +154,141 @@ __device__ __forceinline__ void hmm_result(int S, const double (&v)[HS], const i
             for (int q = 0; q < HS; q++) en[q] = w ? E[j][q] : en[q];
         }
     score = best;
+}
+
+// ---- the sums of probabilities (signal HMM: posteriors) that the one-shot kernels (sk_hmm_post.hip) and a
+// filtered HMM session (sk_hmmstream.hip) share: one text, so that a session's alpha is the one-shot call's by construction.
+#define SK_F64(bits) __longlong_as_double((long long)(bits))
+
+// The constants of sk_exp and sk_log by their bit patterns (include/squigglekit_hip.h and tests/hmm_post_ref.py state the
+// same ones; sk_hmm_post.hip pins them with static_asserts).  SK_EXP_Cq: the double nearest 1 / q!; SK_LOG_Dq: the double
+// nearest 1 / q.
+#define SK_LOG2E  0x3FF71547652B82FEull
+#define SK_LN2_HI 0x3FE62E42FEE00000ull
+#define SK_LN2_LO 0x3DEA39EF35793C76ull
+#define SK_SQRT2  0x3FF6A09E667F3BCDull
+#define SK_LN2    0x3FE62E42FEFA39EFull
+#define SK_EXP_C0  0x3FF0000000000000ull
+#define SK_EXP_C1  0x3FF0000000000000ull
+#define SK_EXP_C2  0x3FE0000000000000ull
+#define SK_EXP_C3  0x3FC5555555555555ull
+#define SK_EXP_C4  0x3FA5555555555555ull
+#define SK_EXP_C5  0x3F81111111111111ull
+#define SK_EXP_C6  0x3F56C16C16C16C17ull
+#define SK_EXP_C7  0x3F2A01A01A01A01Aull
+#define SK_EXP_C8  0x3EFA01A01A01A01Aull
+#define SK_EXP_C9  0x3EC71DE3A556C734ull
+#define SK_EXP_C10 0x3E927E4FB7789F5Cull
+#define SK_EXP_C11 0x3E5AE64567F544E4ull
+#define SK_EXP_C12 0x3E21EED8EFF8D898ull
+#define SK_EXP_C13 0x3DE6124613A86D09ull
+#define SK_LOG_D1  0x3FF0000000000000ull
+#define SK_LOG_D3  0x3FD5555555555555ull
+#define SK_LOG_D5  0x3FC999999999999Aull
+#define SK_LOG_D7  0x3FC2492492492492ull
+#define SK_LOG_D9  0x3FBC71C71C71C71Cull
+#define SK_LOG_D11 0x3FB745D1745D1746ull
+#define SK_LOG_D13 0x3FB3B13B13B13B14ull
+#define SK_LOG_D15 0x3FB1111111111111ull
+#define SK_LOG_D17 0x3FAE1E1E1E1E1E1Eull
+#define SK_LOG_D19 0x3FAAF286BCA1AF28ull
+#define SK_LOG_D21 0x3FA8618618618618ull
+#define SK_LOG_D23 0x3FA642C8590B2164ull
+
+// sk_exp(d), d <= 0 (or a rounding error above): 0.0 unless d >= -700.0; else k = rint(d * LOG2E), r = (d - k * LN2_HI)
+// - k * LN2_LO, a degree-13 Horner sum of r with the doubles nearest 1 / q!, scaled by 2^k.  No result is subnormal.
+__device__ __forceinline__ double sk_exp(double d)
+{
+    const bool ok = d >= -700.0;                                // false for -inf (and for a NaN, which never comes)
+    const double dd = ok ? d : 0.0;
+    const double k = rint(dd * SK_F64(SK_LOG2E));               // round half to even
+    const double r = (dd - k * SK_F64(SK_LN2_HI)) - k * SK_F64(SK_LN2_LO);
+    double p = SK_F64(SK_EXP_C13);                              // 1 / 13!
+    p = p * r + SK_F64(SK_EXP_C12);
+    p = p * r + SK_F64(SK_EXP_C11);
+    p = p * r + SK_F64(SK_EXP_C10);
+    p = p * r + SK_F64(SK_EXP_C9);
+    p = p * r + SK_F64(SK_EXP_C8);
+    p = p * r + SK_F64(SK_EXP_C7);
+    p = p * r + SK_F64(SK_EXP_C6);
+    p = p * r + SK_F64(SK_EXP_C5);
+    p = p * r + SK_F64(SK_EXP_C4);
+    p = p * r + SK_F64(SK_EXP_C3);
+    p = p * r + SK_F64(SK_EXP_C2);
+    p = p * r + SK_F64(SK_EXP_C1);
+    p = p * r + SK_F64(SK_EXP_C0);
+    const double v = ldexp(p, (int)k);
+    return ok ? v : 0.0;
+}
+
+// sk_log(s), 1 <= s < 8: three conditional halvings bring f into (sqrt(1/2), sqrt(2)], then 2 atanh((f - 1) / (f + 1)) as a
+// Horner sum in z^2 with the doubles nearest 1 / q, q = 23, 21, .., 1.  The division is the IEEE one.
+__device__ __forceinline__ double sk_log(double s)
+{
+    const double SQRT2 = SK_F64(SK_SQRT2);
+    double f = s, k = 0.0;
+#pragma unroll
+    for (int it = 0; it < 3; it++) {
+        const bool big = f > SQRT2;
+        f = big ? f * 0.5 : f;
+        k = big ? k + 1.0 : k;
+    }
+    const double z = (f - 1.0) / (f + 1.0);
+    const double z2 = z * z;
+    double p = SK_F64(SK_LOG_D23);                              // 1 / 23
+    p = p * z2 + SK_F64(SK_LOG_D21);
+    p = p * z2 + SK_F64(SK_LOG_D19);
+    p = p * z2 + SK_F64(SK_LOG_D17);
+    p = p * z2 + SK_F64(SK_LOG_D15);
+    p = p * z2 + SK_F64(SK_LOG_D13);
+    p = p * z2 + SK_F64(SK_LOG_D11);
+    p = p * z2 + SK_F64(SK_LOG_D9);
+    p = p * z2 + SK_F64(SK_LOG_D7);
+    p = p * z2 + SK_F64(SK_LOG_D5);
+    p = p * z2 + SK_F64(SK_LOG_D3);
+    p = p * z2 + SK_F64(SK_LOG_D1);
+    return k * SK_F64(SK_LN2) + (z + z) * p;
+}
+
+// lse of the candidates c[i] whose bit is set in `mask` (wave uniform; a candidate left out is -inf, see the head of the
+// file): m = the maximum in rising i by `>`, -inf if that is -inf, else m + sk_log(sum of sk_exp(c[i] - m) in rising i).
+// Where m is -inf the differences are NaN, sk_exp answers 0.0 and the sum is dropped.
+__device__ __forceinline__ double post_lse(const double (&c)[HS], uint32_t mask)
+{
+    const double ninf = -__builtin_inf();
+    double m = ninf;
+#pragma unroll
+    for (int i = 0; i < HS; i++)
+        if ((mask >> i) & 1u) m = c[i] > m ? c[i] : m;
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < HS; i++)
+        if ((mask >> i) & 1u) s = s + sk_exp(c[i] - m);
+    const double v = m + sk_log(s);
+    return m == ninf ? ninf : v;
+}
+
+// alpha of sample t - 1 -> of sample t (t >= 1)
+__device__ __forceinline__ void post_fwd_step(const hmm_kmodel &m, int S, double x, double (&al)[HS])
+{
+    const double ninf = -__builtin_inf();
+    double na[HS];
+#pragma unroll
+    for (int j = 0; j < HS; j++) {
+        na[j] = ninf;
+        if (j < S) {
+            double c[HS];
+            uint32_t mask = 0;
+#pragma unroll
+            for (int i = 0; i < HS; i++) {
+                c[i] = ninf;
+                if (i < S && ((m.tmask >> (i * HS + j)) & 1ull)) { c[i] = al[i] + m.ltrans[i * HS + j]; mask |= 1u << i; }
+            }
+            na[j] = post_lse(c, mask) + hmm_emit(m, j, x);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < HS; j++) al[j] = na[j];
 }
 
 // host: the kernel's model of a checked sk_hmm_model

@@ -3,9 +3,10 @@
 // The definition is the project's own (include/squigglekit_hip.h, "signal HMM: posteriors"; DESIGN.md 4.24;
 // tests/hmm_post_ref.py restates it in numpy).  Model, samples, calibration, limit and the emission e_j(x) are those of
 // the Viterbi pass (sk_hmm_dev.h), unchanged.  The sums of probabilities need exp and log; both are stated as short, fixed
-// sequences of correctly rounded float64 operations (sk_exp, sk_log below -- add, multiply, one IEEE division, rint,
-// ldexp; the file is compiled with -ffp-contract=off like the rest), so a numpy statement of the same operations in the
-// same order gives the same bits.
+// sequences of correctly rounded float64 operations (sk_exp, sk_log in sk_hmm_dev.h -- add, multiply, one IEEE division,
+// rint, ldexp; the file is compiled with -ffp-contract=off like the rest), so a numpy statement of the same operations in
+// the same order gives the same bits.  sk_exp, sk_log, post_lse and the forward step post_fwd_step live in sk_hmm_dev.h:
+// a filtered HMM session (sk_hmmstream.hip) carries alpha from push to push with the same text.
 //
 // One lane per read, 64 reads per wavefront, one wavefront per workgroup -- k_hmm_viterbi's mapping, tiles and feeds --
 // so every sum of a read is sequential in t, which is what the definition asks.  Alpha cannot be kept for every sample
@@ -31,103 +32,29 @@
 
 namespace {
 
-#define SK_F64(bits) __longlong_as_double((long long)(bits))
-
-// sk_exp(d), d <= 0 (or a rounding error above): 0.0 unless d >= -700.0; else k = rint(d * LOG2E), r = (d - k * LN2_HI)
-// - k * LN2_LO, a degree-13 Horner sum of r with the doubles nearest 1 / q!, scaled by 2^k.  No result is subnormal.
-__device__ __forceinline__ double sk_exp(double d)
-{
-    const bool ok = d >= -700.0;                                // false for -inf (and for a NaN, which never comes)
-    const double dd = ok ? d : 0.0;
-    const double k = rint(dd * SK_F64(0x3FF71547652B82FEull));  // LOG2E; round half to even
-    const double r = (dd - k * SK_F64(0x3FE62E42FEE00000ull)) - k * SK_F64(0x3DEA39EF35793C76ull);   // LN2_HI, LN2_LO
-    double p = SK_F64(0x3DE6124613A86D09ull);                   // 1 / 13!
-    p = p * r + SK_F64(0x3E21EED8EFF8D898ull);                  // 1 / 12!
-    p = p * r + SK_F64(0x3E5AE64567F544E4ull);
-    p = p * r + SK_F64(0x3E927E4FB7789F5Cull);
-    p = p * r + SK_F64(0x3EC71DE3A556C734ull);
-    p = p * r + SK_F64(0x3EFA01A01A01A01Aull);
-    p = p * r + SK_F64(0x3F2A01A01A01A01Aull);
-    p = p * r + SK_F64(0x3F56C16C16C16C17ull);
-    p = p * r + SK_F64(0x3F81111111111111ull);
-    p = p * r + SK_F64(0x3FA5555555555555ull);
-    p = p * r + SK_F64(0x3FC5555555555555ull);
-    p = p * r + SK_F64(0x3FE0000000000000ull);
-    p = p * r + SK_F64(0x3FF0000000000000ull);                  // 1 / 1!
-    p = p * r + SK_F64(0x3FF0000000000000ull);                  // 1 / 0!
-    const double v = ldexp(p, (int)k);
-    return ok ? v : 0.0;
-}
-
-// sk_log(s), 1 <= s < 8: three conditional halvings bring f into (sqrt(1/2), sqrt(2)], then 2 atanh((f - 1) / (f + 1)) as a
-// Horner sum in z^2 with the doubles nearest 1 / q, q = 23, 21, .., 1.  The division is the IEEE one.
-__device__ __forceinline__ double sk_log(double s)
-{
-    const double SQRT2 = SK_F64(0x3FF6A09E667F3BCDull);
-    double f = s, k = 0.0;
-#pragma unroll
-    for (int it = 0; it < 3; it++) {
-        const bool big = f > SQRT2;
-        f = big ? f * 0.5 : f;
-        k = big ? k + 1.0 : k;
-    }
-    const double z = (f - 1.0) / (f + 1.0);
-    const double z2 = z * z;
-    double p = SK_F64(0x3FA642C8590B2164ull);                   // 1 / 23
-    p = p * z2 + SK_F64(0x3FA8618618618618ull);                 // 1 / 21
-    p = p * z2 + SK_F64(0x3FAAF286BCA1AF28ull);
-    p = p * z2 + SK_F64(0x3FAE1E1E1E1E1E1Eull);
-    p = p * z2 + SK_F64(0x3FB1111111111111ull);
-    p = p * z2 + SK_F64(0x3FB3B13B13B13B14ull);
-    p = p * z2 + SK_F64(0x3FB745D1745D1746ull);
-    p = p * z2 + SK_F64(0x3FBC71C71C71C71Cull);
-    p = p * z2 + SK_F64(0x3FC2492492492492ull);
-    p = p * z2 + SK_F64(0x3FC999999999999Aull);
-    p = p * z2 + SK_F64(0x3FD5555555555555ull);                 // 1 / 3
-    p = p * z2 + SK_F64(0x3FF0000000000000ull);                 // 1 / 1
-    return k * SK_F64(0x3FE62E42FEFA39EFull) + (z + z) * p;     // LN2
-}
-
-// lse of the candidates c[i] whose bit is set in `mask` (wave uniform; a candidate left out is -inf, see the head of the
-// file): m = the maximum in rising i by `>`, -inf if that is -inf, else m + sk_log(sum of sk_exp(c[i] - m) in rising i).
-// Where m is -inf the differences are NaN, sk_exp answers 0.0 and the sum is dropped.
-__device__ __forceinline__ double post_lse(const double (&c)[HS], uint32_t mask)
-{
-    const double ninf = -__builtin_inf();
-    double m = ninf;
-#pragma unroll
-    for (int i = 0; i < HS; i++)
-        if ((mask >> i) & 1u) m = c[i] > m ? c[i] : m;
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < HS; i++)
-        if ((mask >> i) & 1u) s = s + sk_exp(c[i] - m);
-    const double v = m + sk_log(s);
-    return m == ninf ? ninf : v;
-}
-
-// alpha of sample t - 1 -> of sample t (t >= 1)
-__device__ __forceinline__ void post_fwd_step(const hmm_kmodel &m, int S, double x, double (&al)[HS])
-{
-    const double ninf = -__builtin_inf();
-    double na[HS];
-#pragma unroll
-    for (int j = 0; j < HS; j++) {
-        na[j] = ninf;
-        if (j < S) {
-            double c[HS];
-            uint32_t mask = 0;
-#pragma unroll
-            for (int i = 0; i < HS; i++) {
-                c[i] = ninf;
-                if (i < S && ((m.tmask >> (i * HS + j)) & 1ull)) { c[i] = al[i] + m.ltrans[i * HS + j]; mask |= 1u << i; }
-            }
-            na[j] = post_lse(c, mask) + hmm_emit(m, j, x);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < HS; j++) al[j] = na[j];
-}
+// The constants of the definition (the head of the file; include/squigglekit_hip.h, tests/hmm_post_ref.py) against the ones
+// sk_exp and sk_log of sk_hmm_dev.h run on: bit pattern for bit pattern, checked where the one-shot kernels are compiled.
+static_assert(SK_LOG2E == 0x3FF71547652B82FEull && SK_LN2_HI == 0x3FE62E42FEE00000ull && SK_LN2_LO == 0x3DEA39EF35793C76ull,
+              "sk_exp: LOG2E, LN2_HI, LN2_LO");
+static_assert(SK_SQRT2 == 0x3FF6A09E667F3BCDull && SK_LN2 == 0x3FE62E42FEFA39EFull, "sk_log: SQRT2, LN2");
+static_assert(SK_EXP_C0 == 0x3FF0000000000000ull && SK_EXP_C1 == 0x3FF0000000000000ull && SK_EXP_C2 == 0x3FE0000000000000ull,
+              "sk_exp: the doubles nearest 1 / q!");
+static_assert(SK_EXP_C3 == 0x3FC5555555555555ull && SK_EXP_C4 == 0x3FA5555555555555ull && SK_EXP_C5 == 0x3F81111111111111ull,
+              "sk_exp: the doubles nearest 1 / q!");
+static_assert(SK_EXP_C6 == 0x3F56C16C16C16C17ull && SK_EXP_C7 == 0x3F2A01A01A01A01Aull && SK_EXP_C8 == 0x3EFA01A01A01A01Aull,
+              "sk_exp: the doubles nearest 1 / q!");
+static_assert(SK_EXP_C9 == 0x3EC71DE3A556C734ull && SK_EXP_C10 == 0x3E927E4FB7789F5Cull && SK_EXP_C11 == 0x3E5AE64567F544E4ull,
+              "sk_exp: the doubles nearest 1 / q!");
+static_assert(SK_EXP_C12 == 0x3E21EED8EFF8D898ull && SK_EXP_C13 == 0x3DE6124613A86D09ull,
+              "sk_exp: the doubles nearest 1 / q!");
+static_assert(SK_LOG_D1 == 0x3FF0000000000000ull && SK_LOG_D3 == 0x3FD5555555555555ull && SK_LOG_D5 == 0x3FC999999999999Aull,
+              "sk_log: the doubles nearest 1 / q, q odd");
+static_assert(SK_LOG_D7 == 0x3FC2492492492492ull && SK_LOG_D9 == 0x3FBC71C71C71C71Cull && SK_LOG_D11 == 0x3FB745D1745D1746ull,
+              "sk_log: the doubles nearest 1 / q, q odd");
+static_assert(SK_LOG_D13 == 0x3FB3B13B13B13B14ull && SK_LOG_D15 == 0x3FB1111111111111ull && SK_LOG_D17 == 0x3FAE1E1E1E1E1E1Eull,
+              "sk_log: the doubles nearest 1 / q, q odd");
+static_assert(SK_LOG_D19 == 0x3FAAF286BCA1AF28ull && SK_LOG_D21 == 0x3FA8618618618618ull && SK_LOG_D23 == 0x3FA642C8590B2164ull,
+              "sk_log: the doubles nearest 1 / q, q odd");
 
 struct post_kargs {
     const void    *sig;           // int16 rows of `stride`, or float64 values

@@ -7,7 +7,7 @@
 // just goes on where the last one stopped: sample t = n, n + 1, .. of the slot takes the `linit` rule for t == 0 and the
 // recurrence otherwise, and the record after the push is sk_hmm_viterbi_*'s of everything the slot has had, bit for bit.
 //
-// k_hmms_push<FEED>   one lane per named entry, 64 entries per wavefront (one wavefront per workgroup): k_hmm_viterbi's
+// k_hmms_push<FEED, FILT>  one lane per named entry, 64 entries per wavefront (one wavefront per workgroup): k_hmm_viterbi's
 //     mapping, its LDS tiles and its text (sk_hmm_dev.h: hmm_load_tile, hmm_emit, hmm_first, hmm_step).  A lane loads its
 //     slot's 224 bytes, walks the `len` samples of its chunk and stores the state back; then it writes the 96-byte
 //     record.  The sample index is the lane's own here -- t = n0 + position in the chunk -- so the t == 0 case is a
@@ -18,6 +18,19 @@
 //     reason stated in sk_hmm.hip).  Samples that would take a slot past 0x7fffff00 are ignored and the slot is counted in
 //     the context's guard counter (the host form refuses such a push before anything runs).
 // k_hmms_reset        the named slots (or all) back to n = 0 with a calibration pair ({0.0, 1.0}: none).
+//
+// A FILTERED session (SK_HMMS_FILTER; tests/hmmfilter_ref.py) also carries the forward recursion of the
+// posteriors (sk_hmm_post.hip): alpha[6] per slot, 48 bytes in an array of their own beside the 224-byte
+// slots, -inf after a reset.  k_hmms_push<FEED, true> loads, steps and stores it with the text k_hmm_fwd runs
+// (sk_hmm_dev.h: post_fwd_step), on the x the Viterbi step of the same sample sees, so the filter after n samples is the
+// one-shot record's loglik and final_post of the same prefix (beta(n - 1) = 0), bit for bit.  The forward steps of a
+// tile run as a second loop over the LDS tile, behind the Viterbi steps of that tile.  The bits cannot differ from a
+// fused loop's, so the resource lines chose: 154 / 144 VGPRs this way, 157 / 145 with the forward step inside the Viterbi
+// loop (both without spill or scratch).  All the second loop repeats is the tile's LDS read and the emission -- a dozen
+// operations against the 36 sk_exp and 6 sk_log of a step -- and the Viterbi loop's code stays the plain kernel's.
+// k_hmms_push<FEED, false> is the plain session's kernel, untouched by the flag.
+// k_hmms_filter       one lane per named entry: n and alpha -> sk_hmms_filt (loglik = lse_j alpha_j, post[j] =
+//     sk_exp((alpha_j + 0.0) - L)); it changes nothing.
 //
 // Distinct slots per push are what makes the lanes independent: the host form checks it, the device form has it as the
 // caller's contract.
@@ -38,11 +51,16 @@ struct hmms_slot {               // 224 bytes
     int32_t flags, pad;
 };
 
+struct hmms_alpha { double a[HS]; };   // 48 bytes: a filtered session's forward variables, -inf at n == 0
+
 static_assert(sizeof(hmms_slot) == 224, "hmms_slot is 224 bytes");
+static_assert(sizeof(hmms_alpha) == 48, "hmms_alpha is 48 bytes");
+static_assert(sizeof(sk_hmms_filt) == 64, "sk_hmms_filt is 64 bytes (include/squigglekit_hip.h)");
 static_assert(sizeof(sk_hmms_rec) == 96, "sk_hmms_rec is 96 bytes (include/squigglekit_hip.h)");
 
 struct hmms_kargs {
     hmms_slot     *state;        // [nslots]
+    hmms_alpha    *alpha;        // [nslots] of a filtered session (FILT), else nullptr
     int32_t        nslots;
     int32_t        m;
     const int32_t *slots;        // [m]
@@ -68,7 +86,7 @@ __device__ __forceinline__ void hmms_first(hmms_slot &st, double offset, double 
     st.n = 0; st.pushes = 0; st.offset = offset; st.unit = unit; st.flags = 0; st.pad = 0;
 }
 
-template <int FEED>
+template <int FEED, bool FILT>
 __global__ __launch_bounds__(64)
 void k_hmms_push(const hmms_kargs a)
 {
@@ -85,6 +103,11 @@ void k_hmms_push(const hmms_kargs a)
     hmms_slot st;
     if (slot >= 0) st = a.state[slot];
     else hmms_first(st, 0.0, 1.0);
+    double al[FILT ? HS : 1];
+    if constexpr (FILT) {
+#pragma unroll
+        for (int j = 0; j < HS; j++) al[j] = slot >= 0 ? a.alpha[slot].a[j] : -__builtin_inf();
+    }
     int64_t l = 0;
     if (slot >= 0) {
         if (FEED == SK_FEED_I16) {
@@ -124,6 +147,22 @@ void k_hmms_push(const hmms_kargs a)
                 else        hmm_step(a.mdl, S, x, t, st.v, st.E);
             }
         }
+        if constexpr (FILT) {                                   // the forward steps of the same samples, same x
+            for (int jj = 0; jj < pend; jj++) {
+                const int32_t pos = p0 + jj;
+                if (pos < len) {
+                    double x = (double)xrow[jj];
+                    if (FEED == SK_FEED_I16) x = sk_raw_to_pa(x, st.offset, st.unit);
+                    if (n0 + pos == 0) {
+#pragma unroll
+                        for (int j = 0; j < HS; j++)
+                            if (j < S) al[j] = a.mdl.linit[j] + hmm_emit(a.mdl, j, x);
+                    } else {
+                        post_fwd_step(a.mdl, S, x, al);
+                    }
+                }
+            }
+        }
         __syncthreads();                                        // the tile is read before the next one lands
     }
 
@@ -131,6 +170,12 @@ void k_hmms_push(const hmms_kargs a)
         st.n = n0 + len;
         st.pushes += 1;
         a.state[slot] = st;
+        if constexpr (FILT) {
+            hmms_alpha o;
+#pragma unroll
+            for (int j = 0; j < HS; j++) o.a[j] = al[j];
+            a.alpha[slot] = o;
+        }
     }
     if (k >= a.m) return;
     sk_hmms_rec out;
@@ -148,7 +193,8 @@ void k_hmms_push(const hmms_kargs a)
     a.out[k] = out;
 }
 
-__global__ void k_hmms_reset(hmms_slot *state, int32_t nslots, const int32_t *slots, int32_t m, const double *cal2)
+__global__ void k_hmms_reset(hmms_slot *state, hmms_alpha *alpha, int32_t nslots, const int32_t *slots, int32_t m,
+                             const double *cal2)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= m) return;
@@ -157,12 +203,51 @@ __global__ void k_hmms_reset(hmms_slot *state, int32_t nslots, const int32_t *sl
     hmms_slot st;
     hmms_first(st, cal2 ? cal2[2 * idx] : 0.0, cal2 ? cal2[2 * idx + 1] : 1.0);
     state[s] = st;
+    if (alpha) {
+        hmms_alpha o;
+#pragma unroll
+        for (int j = 0; j < HS; j++) o.a[j] = -__builtin_inf();
+        alpha[s] = o;
+    }
+}
+
+// the filter of the named slots as they stand: L = lse_j alpha_j in rising j < S, post[j] = sk_exp((alpha_j + 0.0) - L) --
+// k_hmm_fwd's L and k_hmm_bwd's gamma at the last sample, where beta is 0.0.  n == 0 and a slot outside the session: zeros.
+__global__ void k_hmms_filter(const hmms_slot *state, const hmms_alpha *alpha, int32_t nslots, int32_t S, const int32_t *slots,
+                              int32_t m, sk_hmms_filt *out)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= m) return;
+    const int32_t s = slots[idx];
+    const bool in = s >= 0 && s < nslots;
+    const int32_t n = in ? state[s].n : 0;
+    const double ninf = -__builtin_inf();
+    double al[HS];
+#pragma unroll
+    for (int j = 0; j < HS; j++) al[j] = (in && j < S) ? alpha[s].a[j] : ninf;
+    sk_hmms_filt o;
+    o.loglik = 0.0; o.n_used = n; o.flags = 0;
+#pragma unroll
+    for (int j = 0; j < HS; j++) o.post[j] = 0.0;
+    if (n > 0) {
+        const double Lr = post_lse(al, (1u << S) - 1u);
+        const bool live = Lr != ninf;
+        const double L = live ? Lr : 0.0;
+        o.loglik = Lr;
+        o.flags = live ? 0 : SK_HMM_POST_IMPOSSIBLE;
+#pragma unroll
+        for (int j = 0; j < HS; j++)
+            if (j < S) { const double g = sk_exp((al[j] + 0.0) - L); o.post[j] = live ? g : 0.0; }
+    }
+    out[idx] = o;
 }
 
 struct hmms_session {
     int32_t nslots = 0;
     sk_hmm_model model;
     sk_buf state;                           // hmms_slot [nslots]
+    sk_buf alpha;                           // hmms_alpha [nslots] of a filtered session (SK_HMMS_FILTER), else empty
+    bool filter = false;
     std::vector<int32_t> n;                 // per slot, as the host forms know them: samples since the reset
     bool mirror_stale = false;              // a device-form push has moved slots the host did not see
     sk_buf rows, args, out;                 // the host forms' staging: samples; slots, lengths / offsets, pairs; records
@@ -172,7 +257,7 @@ void free_buf(sk_buf *b) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap
 
 void destroy(hmms_session *z)
 {
-    sk_buf *bufs[] = {&z->state, &z->rows, &z->args, &z->out};
+    sk_buf *bufs[] = {&z->state, &z->alpha, &z->rows, &z->args, &z->out};
     for (sk_buf *b : bufs) free_buf(b);
     delete z;
 }
@@ -276,11 +361,17 @@ int check_session_slots(sk_ctx *c, hmms_session *z, const int32_t *slots, int32_
     return SK_OK;
 }
 
+// bytes of slot state: 224 per slot, and 48 more for a filtered session's alpha
+int64_t session_bytes(const hmms_session *z)
+{
+    return (int64_t)z->nslots * (int64_t)(sizeof(hmms_slot) + (z->filter ? sizeof(hmms_alpha) : 0));
+}
+
 int launch_reset(sk_ctx *c, hmms_session *z, const int32_t *d_slots, int32_t m, const double *d_cal2)
 {
     if (m <= 0) return SK_OK;
     hipLaunchKernelGGL(k_hmms_reset, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (hmms_slot *)z->state.p,
-                       z->nslots, d_slots, m, d_cal2);
+                       (hmms_alpha *)z->alpha.p, z->nslots, d_slots, m, d_cal2);
     SK_HIP(hipGetLastError());
     return SK_OK;
 }
@@ -289,17 +380,22 @@ int launch_reset(sk_ctx *c, hmms_session *z, const int32_t *d_slots, int32_t m, 
 int launch_push(sk_ctx *c, hmms_session *z, int feed, const int32_t *d_slots, int32_t m, const void *d_sig, int64_t stride,
                 const int32_t *d_len, const int64_t *d_off, sk_hmms_rec *d_out)
 {
-    c->hmms_state_bytes = (int64_t)z->nslots * (int64_t)sizeof(hmms_slot);
+    c->hmms_state_bytes = session_bytes(z);
     c->hmms_valid = true;
     if (m <= 0) return SK_OK;
     hmms_kargs a;
-    a.state = (hmms_slot *)z->state.p; a.nslots = z->nslots; a.m = m; a.slots = d_slots;
+    a.state = (hmms_slot *)z->state.p; a.alpha = z->filter ? (hmms_alpha *)z->alpha.p : nullptr; a.nslots = z->nslots; a.m = m; a.slots = d_slots;
     a.sig = d_sig; a.stride = stride; a.len = d_len; a.off = d_off;
     a.vec = (feed == SK_FEED_I16 && (uintptr_t)d_sig % 16 == 0 && stride % 8 == 0) ? 1 : 0;
     a.out = d_out; a.guard = (unsigned long long *)c->hmmscnt.p; a.mdl = hmm_flatten(&z->model);
     const dim3 grid((unsigned)((m + 63) / 64));
-    if (feed == SK_FEED_I16) hipLaunchKernelGGL(k_hmms_push<SK_FEED_I16>, grid, dim3(64), 0, c->stream, a);
-    else                     hipLaunchKernelGGL(k_hmms_push<SK_FEED_F64_NORM>, grid, dim3(64), 0, c->stream, a);
+    if (z->filter) {
+        if (feed == SK_FEED_I16) hipLaunchKernelGGL((k_hmms_push<SK_FEED_I16, true>), grid, dim3(64), 0, c->stream, a);
+        else                     hipLaunchKernelGGL((k_hmms_push<SK_FEED_F64_NORM, true>), grid, dim3(64), 0, c->stream, a);
+    } else {
+        if (feed == SK_FEED_I16) hipLaunchKernelGGL((k_hmms_push<SK_FEED_I16, false>), grid, dim3(64), 0, c->stream, a);
+        else                     hipLaunchKernelGGL((k_hmms_push<SK_FEED_F64_NORM, false>), grid, dim3(64), 0, c->stream, a);
+    }
     SK_HIP(hipGetLastError());
     return SK_OK;
 }
@@ -320,6 +416,61 @@ int timed_push(sk_ctx *c, hmms_session *z, int feed, const int32_t *d_slots, int
 
 int reserve(sk_ctx *c, sk_buf *b, size_t bytes) { return sk_reserve(c, b, bytes ? bytes : 1); }
 
+// what the arguments of a filter call decide (host: the slots can be read here; a slot may appear twice)
+int check_filter(int32_t handle, const int32_t *slots, int32_t m, const sk_hmms_filt *out, bool host)
+{
+    if (int rc = check_handle(handle)) return rc;
+    if (m < 0) return sk_fail(SK_ERR_INVALID, "m < 0");
+    if (m == 0) return SK_OK;
+    if (!slots) return sk_fail(SK_ERR_INVALID, "NULL slots");
+    if (!out) return sk_fail(SK_ERR_INVALID, "NULL out");
+    return host ? check_slots_host(slots, m, true) : SK_OK;
+}
+
+// the session of a handle, if it is open and carries alpha
+hmms_session *filtered_session_of(sk_ctx *c, int32_t handle)
+{
+    hmms_session *z = session_of(c, handle);
+    if (z && !z->filter) {
+        sk_fail(SK_ERR_INVALID, "HMM session handle %d was opened without SK_HMMS_FILTER: it carries no alpha", handle);
+        return nullptr;
+    }
+    return z;
+}
+
+// the filter proper, every pointer a device pointer; nothing is synchronised
+int launch_filter(sk_ctx *c, hmms_session *z, const int32_t *d_slots, int32_t m, sk_hmms_filt *d_out)
+{
+    if (m <= 0) return SK_OK;
+    hipLaunchKernelGGL(k_hmms_filter, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const hmms_slot *)z->state.p,
+                       (const hmms_alpha *)z->alpha.p, z->nslots, (int32_t)z->model.nstates, d_slots, m, d_out);
+    SK_HIP(hipGetLastError());
+    return SK_OK;
+}
+
+// a session of nslots reset slots; filter: with alpha beside the slots (SK_HMMS_FILTER)
+int session_open(sk_ctx *c, const sk_hmm_model *model, int32_t nslots, bool filter, int32_t *handle)
+{
+    int h = -1;
+    for (int i = 0; i < SK_HMMS_MAX_SESSIONS; i++) if (!c->hmms_sessions[i]) { h = i; break; }
+    if (h < 0) return sk_fail(SK_ERR_INVALID, "%d HMM sessions are open on this context already", SK_HMMS_MAX_SESSIONS);
+    hmms_session *z = new hmms_session();
+    z->nslots = nslots; z->model = *model; z->filter = filter;
+    z->n.assign((size_t)nslots, 0);
+    int rc = sk_reserve(c, &z->state, (size_t)nslots * sizeof(hmms_slot));
+    if (!rc && filter) rc = sk_reserve(c, &z->alpha, (size_t)nslots * sizeof(hmms_alpha));
+    if (!rc && !c->hmmscnt.p) {                             // the context's guard counter: 0 once, then it only counts
+        rc = sk_reserve(c, &c->hmmscnt, sizeof(unsigned long long));
+        if (!rc && hipMemsetAsync(c->hmmscnt.p, 0, sizeof(unsigned long long), c->stream) != hipSuccess)
+            rc = sk_fail(SK_ERR_HIP, "clearing the guard counter failed");
+    }
+    if (!rc) rc = launch_reset(c, z, nullptr, nslots, nullptr);
+    if (rc) { destroy(z); return rc; }
+    c->hmms_sessions[h] = z;
+    *handle = h;
+    return SK_OK;
+}
+
 } // namespace
 
 void sk_hmms_close_all(sk_ctx *c)
@@ -331,23 +482,7 @@ void sk_hmms_close_all(sk_ctx *c)
 // ---- the session behind sk_hmms_open, and the device forms a gated live session (sk_live.hip) drives its own with ----
 int sk_hmms_session_open(sk_ctx *c, const sk_hmm_model *model, int32_t nslots, int32_t *handle)
 {
-    int h = -1;
-    for (int i = 0; i < SK_HMMS_MAX_SESSIONS; i++) if (!c->hmms_sessions[i]) { h = i; break; }
-    if (h < 0) return sk_fail(SK_ERR_INVALID, "%d HMM sessions are open on this context already", SK_HMMS_MAX_SESSIONS);
-    hmms_session *z = new hmms_session();
-    z->nslots = nslots; z->model = *model;
-    z->n.assign((size_t)nslots, 0);
-    int rc = sk_reserve(c, &z->state, (size_t)nslots * sizeof(hmms_slot));
-    if (!rc && !c->hmmscnt.p) {                             // the context's guard counter: 0 once, then it only counts
-        rc = sk_reserve(c, &c->hmmscnt, sizeof(unsigned long long));
-        if (!rc && hipMemsetAsync(c->hmmscnt.p, 0, sizeof(unsigned long long), c->stream) != hipSuccess)
-            rc = sk_fail(SK_ERR_HIP, "clearing the guard counter failed");
-    }
-    if (!rc) rc = launch_reset(c, z, nullptr, nslots, nullptr);
-    if (rc) { destroy(z); return rc; }
-    c->hmms_sessions[h] = z;
-    *handle = h;
-    return SK_OK;
+    return session_open(c, model, nslots, false, handle);
 }
 
 // int16 rows, every pointer a device pointer, nothing synchronised, no event recorded
@@ -372,7 +507,7 @@ int sk_hmms_session_reset_dev(sk_ctx *c, int32_t handle, const int32_t *d_slots,
 int64_t sk_hmms_session_bytes(sk_ctx *c, int32_t handle)
 {
     hmms_session *z = session_of(c, handle);
-    return z ? (int64_t)z->nslots * (int64_t)sizeof(hmms_slot) : 0;
+    return z ? session_bytes(z) : 0;
 }
 
 int sk_hmms_session_close(sk_ctx *c, int32_t handle)
@@ -398,6 +533,17 @@ int sk_hmms_open(const sk_hmm_model *model, int32_t nslots, int32_t *handle)
         return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_HMMS_MAX_SLOTS);
     SK_ENTER(c);
     return sk_hmms_session_open(c, model, nslots, handle);
+}
+
+int sk_hmms_open_ex(const sk_hmm_model *model, int32_t nslots, int32_t flags, int32_t *handle)
+{
+    if (flags & ~SK_HMMS_FILTER) return sk_fail(SK_ERR_INVALID, "flags = 0x%x: the only flag is SK_HMMS_FILTER", (unsigned)flags);
+    if (const char *what = sk_hmm_model_error(model)) return sk_fail(SK_ERR_INVALID, "sk_hmm_model: %s", what);
+    if (!handle) return sk_fail(SK_ERR_INVALID, "NULL handle");
+    if (nslots < 1 || nslots > SK_HMMS_MAX_SLOTS)
+        return sk_fail(SK_ERR_INVALID, "nslots = %d is outside 1 .. %d", nslots, SK_HMMS_MAX_SLOTS);
+    SK_ENTER(c);
+    return session_open(c, model, nslots, (flags & SK_HMMS_FILTER) != 0, handle);
 }
 
 int sk_hmms_push_dev_i16(int32_t handle, const int32_t *d_slots, int32_t m, const int16_t *d_rows, int64_t stride,
@@ -511,6 +657,42 @@ int sk_hmms_reset(int32_t handle, const int32_t *slots, int32_t m, const double 
     if ((rc = launch_reset(c, z, d_slots, m, cal2 ? d_cal : nullptr))) return rc;
     SK_HIP(hipStreamSynchronize(c->stream));                // (slots and cal2 are the caller's memory)
     for (int32_t i = 0; i < m; i++) z->n[(size_t)slots[i]] = 0;
+    return SK_OK;
+}
+
+int sk_hmms_filter(int32_t handle, const int32_t *slots, int32_t m, sk_hmms_filt *out)
+{
+    int rc = check_filter(handle, slots, m, out, true);
+    if (rc) return rc;
+    SK_ENTER(c);
+    hmms_session *z = session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    if (m > 0 && (rc = check_session_slots(c, z, slots, m, nullptr))) return rc;
+    if (!(z = filtered_session_of(c, handle))) return SK_ERR_INVALID;
+    if (m == 0) return SK_OK;
+    SK_HIP(hipStreamSynchronize(c->stream));                // an earlier call may still read the staging buffers
+    const size_t mm = (size_t)m;
+    if ((rc = reserve(c, &z->args, mm * sizeof(int32_t)))) return rc;
+    if ((rc = reserve(c, &z->out, mm * sizeof(sk_hmms_filt)))) return rc;
+    SK_HIP(hipMemcpyAsync(z->args.p, slots, mm * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_filter(c, z, (const int32_t *)z->args.p, m, (sk_hmms_filt *)z->out.p))) return rc;
+    SK_HIP(hipMemcpyAsync(out, z->out.p, mm * sizeof(sk_hmms_filt), hipMemcpyDeviceToHost, c->stream));
+    SK_HIP(hipStreamSynchronize(c->stream));
+    return SK_OK;
+}
+
+int sk_hmms_filter_dev(int32_t handle, const int32_t *d_slots, int32_t m, sk_hmms_filt *d_out)
+{
+    if (int rc = check_filter(handle, d_slots, m, d_out, false)) return rc;
+    SK_ENTER(c);
+    hmms_session *z = filtered_session_of(c, handle);
+    if (!z) return SK_ERR_INVALID;
+    SK_HIP(hipEventRecord(c->ev[0], c->stream));
+    SK_HIP(hipEventRecord(c->ev[1], c->stream));
+    SK_HIP(hipEventRecord(c->ev[2], c->stream));
+    if (int rc = launch_filter(c, z, d_slots, m, d_out)) return rc;
+    SK_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->ev_valid = true;
     return SK_OK;
 }
 

@@ -13,7 +13,9 @@ count, reads of four kinds, cuts, subsets, ENDs and resets) against its statemen
 against the one-shot call on every ended read; and one hit-list round (tests/pair_hits_ref.py: a drawn pair list with its
 K, max_dist and row budget, and a drawn session script whose hits() are read after every push) against the statement
 there; and one posterior round (randcases.draw_hmm's models, reads, feeds and switches, a limit of at most 1 200 samples so
-that the statement stays quick, SK_HMM_POST_BLOCK drawn) against tests/hmm_post_ref.py, every double by its bits.  The DTW pair
+that the statement stays quick, SK_HMM_POST_BLOCK drawn) against tests/hmm_post_ref.py, every double by its bits; and one
+filtered HMM session (hmmstream_ref.draw_session's script on a drawn model, beside a plain session) against
+tests/hmmfilter_ref.py after every push, every double by its bits.  The DTW pair
 lists, their warping paths and the adaptive band are three of the families of tests/randcases.py (`pairs`, `pairpaths`,
 `band`: the draws that used to live here, against tests/pairs_ref.py, tests/pair_paths_ref.py and tests/band_ref.py).
 
@@ -36,6 +38,8 @@ import mapstream_ref                                  # noqa: E402
 import evstream_ref                                   # noqa: E402
 import pair_hits_ref                                  # noqa: E402
 import hmm_post_ref                                   # noqa: E402
+import hmmstream_ref                                  # noqa: E402
+import hmmfilter_ref                                  # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
 from squigglekit_amd._lib import SegParams           # noqa: E402
 from oracle import oracle as ora                      # noqa: E402
@@ -154,6 +158,24 @@ def hmm_post_round(rng):
         return "%s: the dense posteriors differ" % desc
     if dense and np.isnan(gamma).any():
         return "%s: a NaN among the dense posteriors" % desc
+    return None
+
+
+def hmmfilter_round(rng):
+    """One drawn filtered HMM session (hmmstream_ref.draw_session: slot count, subsets, cuts, both feeds, resets with and
+    without calibration pairs; a drawn tie model or a preset) beside a plain one: after every push the records of both and
+    the filter against tests/hmmfilter_ref.py, bit for bit.  Returns None, or what differed."""
+    kind = int(rng.integers(3))
+    if kind == 0:
+        model, draw = hmmstream_ref.tie_model(rng), lambda r, n: r.integers(0, 4, n).astype(np.int16)
+    else:
+        model, draw = api.polya_model(("synth_raw", "rna_pa")[kind - 1]), lambda r, n: r.integers(380, 620, n).astype(np.int16)
+    nslots = int(rng.integers(1, 200))
+    sess = hmmstream_ref.draw_session(rng, nslots=nslots, budget=150 * nslots, maxlen=int(rng.integers(1, 200)), draw_chunk=draw)
+    try:
+        hmmfilter_ref.play_session(api, model, sess, "%d slots" % nslots)
+    except AssertionError as e:
+        return "%s model: %s" % (("tie", "synth_raw", "rna_pa")[kind], str(e)[:600])
     return None
 
 
@@ -493,6 +515,11 @@ def main():
         if msg is not None:
             bad += 1
             print("HMM POSTERIOR mismatch round %d %s" % (rounds, msg))
+        # ---- one filtered HMM session against its statement (tests/hmmfilter_ref.py) ----
+        msg = hmmfilter_round(rng)
+        if msg is not None:
+            bad += 1
+            print("HMM FILTER mismatch round %d %s" % (rounds, msg))
     print("fuzz: %d rounds, %d mismatching configurations" % (rounds, bad))
     sys.exit(1 if bad else 0)
 
