@@ -2,7 +2,8 @@
 sk_hits.hip, sk_path.hip, sk_pull.hip, sk_panel.hip, sk_detect.hip, sk_hmm.hip, sk_seglev.hip, through the twins of the
 hit family sk_bg.hip and sk_events.hip, for the switches of the screening scheme sk_sdtwq.hip, and for both branches of the
 dRNA segmenter (sk_drna_walk.hip and the dRNA kernels of sk_prep.hip), for DTW over a pair list with its warping paths
-(sk_pairs.hip, sk_pairpath.hip), and for the adaptive-band DTW (sk_band.hip): per family
+(sk_pairs.hip, sk_pairpath.hip), for the adaptive-band DTW (sk_band.hip), and for the signal HMM's posteriors
+(sk_hmm_post.hip; their cases also feed filtered HMM sessions, sk_hmmstream.hip): per family
 draw_<family>(rng) -> case,  expect_<family>(ora, case) ->
 what the reference says,  call_<family>(api, case, exp) -> what the GPU says,  diff_<family>(case, got, exp) -> None or
 the first difference as text.
@@ -10,17 +11,18 @@ the first difference as text.
 A plain module: not collected, no conftest, pure numpy, no GPU import at module level (`api` is handed in).  The same
 seed gives the same case on any machine: draw_* take a numpy.random.Generator and nothing else.  Used by
 tests/test_random_cases.py (CPU: the committed seeds reach what they claim), tests/test_gpu_random.py (GPU: every seed
-against its reference, plus five interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
+against its reference, plus six interleaved sequences) and tools/fuzz_gpu.py (open-ended: every draw it makes of these
 families is DRAW[family] with its running generator).  tests/RANDOM_CASES.md says what each family draws, the
 references, the budgets, the wall times, and which one-line kernel mutants the committed seeds catch
-(tests/RANDOM_CASES_BAND.md for the band family).
+(tests/RANDOM_CASES_BAND.md for the band family, tests/RANDOM_CASES_HMMPOST.md for the posteriors).
 
 The references are the statements that already exist: the oracle's scale_outliers + get_segs per (set, read) for the
 sweep, reference_hits (test_hits_host.py), reference_paths (test_paths_host.py), numpy_pull_text (test_squigglepull.py),
 reference_panel (test_panel_host.py), detect_ref.py, hmm_ref.py, hmm_path_ref.py, plain numpy on the oracle's segments
 for the levels, reference_background_reads (test_background_host.py), reference_batch / reference_pool
 (test_events_host.py), the oracle's scale_outliers + drna_segs / drna_roll per read for the dRNA branches,
-pairs_ref.records and pair_paths_ref.list_spans for the pair lists, band_ref.records for the band.  Every comparison
+pairs_ref.records and pair_paths_ref.list_spans for the pair lists, band_ref.records for the band,
+hmm_post_ref.posterior_batch / posterior_reads for the posteriors.  Every comparison
 is exact: integers as integers, doubles and text byte for byte.
 """
 import os
@@ -49,6 +51,7 @@ SEEDS = {
     "pairs": [4, 5, 7, 9, 23, 54, 119, 130, 133],
     "pairpaths": [1, 5, 6, 7, 13, 17, 21, 22, 23, 36, 50, 145],
     "band": [27, 29, 44, 54, 61, 70, 75, 112, 138, 195, 238, 240, 297, 299, 331, 351, 423, 458],
+    "hmmpost": [2, 8, 21, 22, 31, 34, 37, 48, 68, 77, 124, 137, 148, 162, 185, 215, 217, 239, 305, 339, 427, 465],
 }
 
 # every tuning switch a case may set; a runner clears the ones a case does not name
@@ -56,14 +59,14 @@ SWITCHES = ("SK_SEG_DELTA_SCALE", "SK_WALK_GENERAL", "SK_DTW_SMALL_MAX", "SK_HIT
             "SK_PATH_SCRATCH_BYTES", "SK_DTW_NO_SMALL", "SK_PANEL_EXACT", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB",
             "SK_DTW_QL", "SK_DTW_HINT_MIN", "SK_DTW_NOHINT", "SK_DTW_CK", "SK_DTW_SORT_MIN", "SK_DTW_SCRATCH_MB",
             "SK_DTW_NOFUSE", "SK_DTW_NO_SIBLINGS", "SK_DTW_NO_EARLY", "SK_DRNA_STEP", "SK_ROLL_ONE_LOOK",
-            "SK_ROLL_DELTA_SCALE", "SK_ROLL_TWO_KERNELS", "SK_BAND_WAVES")
+            "SK_ROLL_DELTA_SCALE", "SK_ROLL_TWO_KERNELS", "SK_HMM_POST_BLOCK", "SK_BAND_WAVES")
 
 
 # the family's number in the seed of its generator.  Frozen: the first four are what sorted(SEEDS).index(family) gave when
 # the table held four keys, so those cases stay what they were (tests/test_random_cases.py pins their digests); a new
 # family takes the next free number, whatever its name.
 FAMILY_INDEX = dict(hits=0, paths=1, pull=2, sweep=3, panel=4, detect=5, hmm=6, levels=7, screen=8, drna=9, roll=10,
-                    pairs=11, pairpaths=12, band=13)
+                    pairs=11, pairpaths=12, band=13, hmmpost=14)
 
 
 def rng_of(family, seed):
@@ -1151,8 +1154,10 @@ def hmm_slices(case):
     return -(-groups // g) if groups else 0
 
 
-def draw_hmm(rng):
-    # ---- the model: tools/fuzz_gpu.py's
+def _draw_hmm_model(rng):
+    """(model, S, integer): tools/fuzz_gpu.py's model -- S = 1 .. 6, integer scores (ties) in 30 % of the draws and logs of
+    uniform draws otherwise, 30 % of linit and 40 % of ltrans -inf, half the states without a second component, 20 % of
+    h zero.  draw_hmm and draw_hmmpost begin with it: the order of its draws is part of the pinned cases."""
     S = int(rng.integers(1, 7))
     integer = bool(rng.random() < 0.3)
     if integer:                                   # integer scores: ties
@@ -1170,7 +1175,11 @@ def draw_hmm(rng):
         hl[int(rng.integers(S))] = 0.0
     ht[rng.random((S, S)) < 0.4] = -np.inf
     hc[rng.random(S) < 0.5, 1] = -np.inf
-    model = dict(nstates=S, linit=hl, ltrans=ht, c=hc, mu=hmu, h=hh)
+    return dict(nstates=S, linit=hl, ltrans=ht, c=hc, mu=hmu, h=hh), S, integer
+
+
+def draw_hmm(rng):
+    model, S, integer = _draw_hmm_model(rng)
     # ---- the reads
     env = {}
     R = int(_pick(rng, HMM_COUNTS))
@@ -1277,6 +1286,308 @@ def diff_hmm_paths(case, got, exp):
             return "read %d (%d samples): %d segments (sums %s), want %d (%s); segment %d: got %s want %s" % (
                 r, len(case["reads"][r]), len(g), g.dtype["sum"].base, len(want), want.dtype["sum"].base, q,
                 g[q] if q < len(g) else None, want[q] if q < len(want) else None)
+    return None
+
+
+# ======================================================================================================================
+# signal HMM posteriors (sk_hmm_post.hip: k_hmm_fwd<FEED>, k_hmm_bwd<FEED, COUNTS>; tests/RANDOM_CASES_HMMPOST.md)
+# ======================================================================================================================
+# lengths: 0, 1, 2; the float64 tile's seams (32 values), the int16 tile's (128 samples); the block seams at B = 128, 256
+# and 1 024 with their neighbours
+POST_LENS = (0, 1, 2, 31, 32, 33, 127, 128, 129, 255, 256, 257, 383, 384, 385, 511, 512, 513, 1023, 1024, 1025)
+POST_LIMITS = (0, 0, 1, 33, 129, 1000, 100000)
+POST_DMAX = (70, 300, 1500, 2600)
+POST_BLOCKS = (None, "256", "1024", "4096", "100")          # SK_HMM_POST_BLOCK; 100 is refused by post_block(): 128
+POST_SAMPLES = 200_000                           # samples per case (the statement's CPU time, RANDOM_CASES_HMMPOST.md)
+POST_LONGEST = 2600                              # ... and of its longest read: 21 blocks at B = 128
+# sub_batches() of sk_api.hip never cuts a call of fewer than 8 192 rows, so in a fifth of the batch cases under
+# SK_INGEST_MB=1 the read count is this one: short reads and one of POST_MANY_LONG samples, whose stride of 130 or more
+# brings the sub-batch down to its floor of 4 096 rows -- three sub-batches of 2 800
+POST_MANY = 8400
+POST_MANY_SHORT = 12
+POST_MANY_LONG = 130
+POST_GUARD = 256                                 # bytes behind each output of the device form
+
+
+def post_block_of(env):
+    """post_block() of sk_hmm_post.hip"""
+    v = int(env.get("SK_HMM_POST_BLOCK", "0"))
+    return v if 128 <= v <= 4096 and v % 128 == 0 else 128
+
+
+def hmmpost_calls(case):
+    """[(reads, npad, stride or None)] per C call of the case's api call: sk_hmm_npad over the stride of an int16 batch
+    (api.pack_i16's for the integer reads of a list), over the longest read of a float64 call"""
+    lens = [len(r) for r in case["reads"]]
+    limit = case["limit"]
+
+    def npad(n):
+        return max(1, min(n, limit) if limit > 0 else n)
+    if case["feed"] == "batch":
+        return [(case["R"], npad(case["stride"]), case["stride"])]
+    if case["feed"] == "f64":
+        return [(case["R"], npad(max(lens + [0])), None)]
+    ints = [n for n, r in zip(lens, case["reads"]) if _is_int_read(r)]
+    flts = [n for n, r in zip(lens, case["reads"]) if not _is_int_read(r)]
+    calls = []
+    if ints:
+        stride = max(8, (max(ints) + 7) // 8 * 8)
+        calls.append((len(ints), npad(stride), stride))
+    if flts:
+        calls.append((len(flts), npad(max(flts)), None))
+    return calls
+
+
+def hmmpost_sub_batches(case):
+    """Sub-batches sub_batches() of sk_api.hip makes of the case's largest int16 host call (1 for a float64 call)"""
+    most = 1
+    target = (int(case["env"]["SK_INGEST_MB"]) << 20) if "SK_INGEST_MB" in case["env"] else 256 << 20
+    for nreads, _, stride in hmmpost_calls(case):
+        if stride is None:
+            continue
+        per = max(4096, target // (stride * 2))
+        if per * 2 <= nreads:
+            most = max(most, -(-nreads // per))
+    return most
+
+
+def hmmpost_slices(case):
+    """Slices sk_launch_hmm_post makes of the case's reads -- post_group_bytes / post_slice_groups of sk_hmm_post.hip -- per
+    launch (a sub-batch of the largest C call), the most of the case's calls"""
+    budget = (int(case["env"]["SK_HMM_SCRATCH_MB"]) << 20) if "SK_HMM_SCRATCH_MB" in case["env"] else 16 << 30
+    B = post_block_of(case["env"])
+    most = 0
+    for nreads, npad, stride in hmmpost_calls(case):
+        if stride is not None:
+            nsub = hmmpost_sub_batches(dict(case, feed="batch", R=nreads, stride=stride))
+            nreads = -(-nreads // nsub)
+        group_bytes = 64 * 8 + (-(-npad // B) + B) * (6 * 64 * 8)
+        groups = (nreads + 63) // 64
+        g = min(max(1, budget // group_bytes), groups)
+        most = max(most, -(-groups // g))
+    return most
+
+
+def draw_hmmpost(rng):
+    """One posterior call: draw_hmm's model; R of HMM_COUNTS (or POST_MANY, see there) reads, each with a length of POST_LENS
+    or a uniform one up to a drawn maximum, inside POST_SAMPLES samples and POST_LONGEST a read, drawn as draw_hmm draws
+    them; the feed (an int16 batch with an aligned or an unaligned stride, with or without calibration pairs; float64
+    values; a list of integer and float reads), the limit, which outputs are asked for, and the switches
+    SK_HMM_POST_BLOCK, SK_HMM_SCRATCH_MB and SK_INGEST_MB."""
+    model, S, integer = _draw_hmm_model(rng)
+    env = {}
+    R = int(_pick(rng, HMM_COUNTS))
+    dmax = int(_pick(rng, POST_DMAX))
+    block = _pick(rng, POST_BLOCKS)
+    if block is not None:
+        env["SK_HMM_POST_BLOCK"] = block
+    if rng.random() < 0.35:
+        env["SK_HMM_SCRATCH_MB"] = "1"
+    if rng.random() < 0.3:
+        env["SK_INGEST_MB"] = "1"
+    feed = _pick(rng, ("batch", "batch", "f64", "list"))
+    limit = int(_pick(rng, POST_LIMITS))
+    counts, dense = bool(rng.random() < 0.8), bool(rng.random() < 0.8)
+    many = bool("SK_INGEST_MB" in env and feed == "batch" and rng.random() < 0.2)
+    if many:
+        R, dmax = POST_MANY, POST_MANY_SHORT
+        lens = [int(n) for n in rng.integers(0, POST_MANY_SHORT + 1, R)]
+        lens[int(rng.integers(R))] = POST_MANY_LONG
+    else:
+        lens = _ragged_lens(rng, R, POST_LENS, dmax, POST_SAMPLES)
+    reads = [_det_read(rng, n)[0] for n in lens]
+    cal, nfloat, aligned = None, 0, None
+    case = dict(family="hmmpost", R=R, S=S, integer=integer, feed=feed, limit=limit, dmax=dmax, counts=counts, dense=dense)
+    if feed == "batch":
+        aligned = bool(rng.random() < 0.5)
+        case["sig"], case["lens"], case["stride"] = _i16_rows(rng, reads, aligned)
+        if rng.random() < 0.5:
+            cal = np.stack([rng.uniform(-50, 50, R), rng.uniform(0.1, 0.3, R)], axis=1)
+    else:
+        for r in range(R):
+            if len(reads[r]) and (feed == "f64" or rng.random() < 0.5):
+                reads[r] = reads[r].astype(np.float64) * float(_pick(rng, (1.0, 0.25, 0.1))) + 0.37    # not integers
+                nfloat += 1
+    case.update(aligned=aligned, calibrated=cal is not None, nfloat=nfloat, total=int(sum(len(r) for r in reads)),
+                longest=max(len(r) for r in reads), model=model, cal=cal, reads=reads, env=env)
+    return case
+
+
+def hmmpost_rows(case):
+    """(x float64 [R, N] in the model's units, n_used int64 [R]): what the statement runs on"""
+    lens = np.array([len(r) for r in case["reads"]], dtype=np.int64)
+    x = np.zeros((case["R"], max(1, int(lens.max(initial=0)))))
+    for i, r in enumerate(case["reads"]):
+        x[i, :len(r)] = np.asarray(r, dtype=np.float64)
+    if case["cal"] is not None:
+        x = (x + case["cal"][:, :1]) * case["cal"][:, 1:]
+    return x, (np.minimum(lens, case["limit"]) if case["limit"] > 0 else lens)
+
+
+POST_CLASS_CUTS = (32, 128, 512)                 # where expect_hmmpost may part the reads by the samples they use
+POST_STEP_READS = 140                            # a time step of the statement costs what 140 padded samples cost
+
+
+def hmmpost_classes(used):
+    """The reads parted by the samples they use, for the statement's CPU time alone: hmm_post_ref advances the reads of a
+    call together over the rectangle [reads, longest], and every read's arithmetic is the statement's whatever its
+    neighbours are, so a few short rectangles give the bytes of the one wide one.  Of the partitions at subsets of
+    POST_CLASS_CUTS, the one with the smallest sum of longest * (POST_STEP_READS + reads)."""
+    used = np.asarray(used, dtype=np.int64)
+    best = None
+    for pick in range(1 << len(POST_CLASS_CUTS)):
+        cuts = [c for k, c in enumerate(POST_CLASS_CUTS) if pick >> k & 1]
+        cls = np.searchsorted(cuts, used, side="left") if cuts else np.zeros(used.size, dtype=np.int64)
+        parts = [np.flatnonzero(cls == k) for k in range(len(cuts) + 1)]
+        parts = [p for p in parts if p.size]
+        cost = sum(int(used[p].max()) * (POST_STEP_READS + p.size) for p in parts)
+        if best is None or cost < best[0]:
+            best = (cost, parts)
+    return best[1]
+
+
+def expect_hmmpost(ora, case, whole=False):
+    """dict(post, counts, goff, gamma) by hmm_post_ref.posterior_batch / posterior_reads, always with counts and dense rows:
+    one call per class of hmmpost_classes (whole: one call over all reads -- the same bytes, asserted on the CPU)"""
+    import hmm_post_ref
+    used = hmmpost_rows(case)[1]
+    parts = [np.arange(case["R"])] if whole else hmmpost_classes(used)
+    post = np.zeros(case["R"], dtype=hmm_post_ref.POST_DTYPE)
+    counts = np.zeros(case["R"], dtype=hmm_post_ref.COUNTS_DTYPE)
+    goff = np.concatenate([[0], np.cumsum(used)]).astype(np.int64)
+    gamma = np.zeros((int(goff[-1]), hmm_post_ref.STATES))
+    for idx in parts:
+        if case["feed"] == "batch":
+            p, c, off, g = hmm_post_ref.posterior_batch(case["model"], case["sig"][idx], case["lens"][idx],
+                                                        None if case["cal"] is None else case["cal"][idx], case["limit"])
+        else:
+            p, c, off, g = hmm_post_ref.posterior_reads(case["model"], [case["reads"][i] for i in idx], case["limit"])
+        post[idx], counts[idx] = p, c
+        for k, r in enumerate(idx):
+            gamma[goff[r]:goff[r + 1]] = g[off[k]:off[k + 1]]
+    assert np.array_equal(post["n_used"], used)
+    return dict(post=post, counts=counts, goff=goff, gamma=gamma)
+
+
+def call_hmmpost(api, case, exp=None):
+    """(post, counts or None, goff or None, gamma [goff[R], 6] or None) of the case's call with the outputs it asks for"""
+    model, limit, reads, counts, dense = hmm_model_of(api, case), case["limit"], case["reads"], case["counts"], case["dense"]
+    if case["feed"] == "batch":
+        return api.hmm_posterior_batch(case["sig"], case["lens"], model, case["cal"], limit, counts, dense)
+    if case["feed"] == "f64":
+        return api.hmm_posterior_ragged_f64(*api.pack_f64(reads), model, limit, counts, dense)
+    post, cnt, gammas = api.hmm_posterior(reads, model, limit, counts, dense)
+    if not dense:
+        return post, cnt, None, None
+    goff = np.concatenate([[0], np.cumsum([len(g) for g in gammas])]).astype(np.int64)
+    return post, cnt, goff, np.concatenate(gammas + [np.zeros((0, 6))])
+
+
+def hmmpost_device_call(api, case, counts, dense, shift=0):
+    """sk_hmm_posterior_dev_i16 on device buffers, the rows `shift` bytes behind a 16-byte boundary, POST_GUARD bytes of
+    0x5A behind post, counts and the dense rows: (post, counts or None, goff or None, gamma or None, clean) -- clean:
+    nothing written behind an output, and nothing at all to one that was not asked for"""
+    import ctypes as C
+    from squigglekit_amd import _lib
+    L = _lib.ensure_init()
+    sig, lens = np.ascontiguousarray(case["sig"]), np.ascontiguousarray(case["lens"])
+    R, stride = sig.shape
+    n = np.clip(lens.astype(np.int64), 0, stride)
+    goff = np.concatenate([[0], np.cumsum(np.minimum(n, case["limit"]) if case["limit"] > 0 else n)]).astype(np.int64)
+    sizes = (R * 112, R * 624, int(goff[R]) * 48)
+    outs = [np.full(s + POST_GUARD, 0x5A, dtype=np.uint8) for s in sizes]
+    ins = [sig, lens, goff] + ([np.ascontiguousarray(case["cal"])] if case["cal"] is not None else [])
+    model = hmm_model_of(api, case)
+    ptrs = []
+    try:
+        for a in ins + outs:
+            ptrs.append(L.sk_dev_alloc(a.nbytes + 16))
+            _lib.check(L.sk_dev_upload(ptrs[-1] + (shift if a is sig else 0), _lib.ptr(a), a.nbytes))
+        d_out = ptrs[len(ins):]
+        _lib.check(L.sk_hmm_posterior_dev_i16(ptrs[0] + shift, stride, ptrs[1], R, ptrs[3] if case["cal"] is not None else None,
+                                              C.byref(model), case["limit"], d_out[0], d_out[1] if counts else None,
+                                              ptrs[2] if dense else None, d_out[2] if dense else None))
+        _lib.check(L.sk_sync())
+        for a, d in zip(outs, d_out):
+            _lib.check(L.sk_dev_download(_lib.ptr(a), d, a.nbytes))
+    finally:
+        for d in ptrs:
+            L.sk_dev_free(d)
+    clean = all(bool(np.all(a[-POST_GUARD:] == 0x5A)) for a in outs)
+    if not counts:
+        clean = clean and bool(np.all(outs[1] == 0x5A))
+    if not dense:
+        clean = clean and bool(np.all(outs[2] == 0x5A))
+    post = outs[0][:-POST_GUARD].view(api.HMM_POST_DTYPE).copy()
+    cnt = outs[1][:-POST_GUARD].view(api.HMM_COUNTS_DTYPE).copy() if counts else None
+    gamma = outs[2][:-POST_GUARD].view(np.float64).reshape(-1, 6).copy() if dense else None
+    return post, cnt, goff if dense else None, gamma, clean
+
+
+POST_BOTH_SEED, POST_BOTH_READS = 22, 65
+
+
+def hmmpost_both_kinds(case, exp, R=POST_BOTH_READS):
+    """A hand-made case out of a drawn batch case with impossible reads: R of its reads, a possible one with samples and an
+    impossible one in turn, so that lane by lane a wavefront holds both kinds (emissions are finite, so where a drawn
+    model has impossible reads its possible ones have at most S samples, and a drawn wavefront holds few of them).
+    `exp` is the statement's answer to `case`: it only says which reads are which."""
+    post = exp["post"]
+    live = np.flatnonzero((post["flags"] == 0) & (post["n_used"] > 0))
+    live = np.concatenate([live[post["n_used"][live] >= 2], live[post["n_used"][live] < 2]])     # two samples and more first
+    dead = np.flatnonzero(post["flags"] != 0)
+    assert case["feed"] == "batch" and len(live) >= (R + 1) // 2 and len(dead) >= R // 2
+    idx = np.empty(R, dtype=np.int64)
+    idx[0::2], idx[1::2] = live[:(R + 1) // 2], dead[:R // 2]
+    reads = [case["reads"][int(i)] for i in idx]
+    return dict(case, made="both kinds", R=R, sig=np.ascontiguousarray(case["sig"][idx]), lens=case["lens"][idx].copy(),
+                cal=None if case["cal"] is None else case["cal"][idx].copy(), reads=reads,
+                total=int(sum(len(r) for r in reads)), longest=max(len(r) for r in reads))
+
+
+def _u64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def diff_hmmpost(case, got, exp):
+    """What a posterior call returned against the statement, every double by its bit pattern: no tolerance anywhere"""
+    post, cnt, goff, gamma = got[:4]
+    want = exp["post"]
+    if post.shape != want.shape:
+        return "records shaped %s, want %s" % (post.shape, want.shape)
+    for f in ("n_used", "flags"):
+        if not np.array_equal(post[f], want[f]):
+            r = int(np.flatnonzero(post[f] != want[f])[0])
+            return "read %d: %s %d, want %d" % (r, f, post[f][r], want[f][r])
+    checks = [("post", post, want, ("loglik", "final_post", "occ"))]
+    if cnt is not None:
+        checks.append(("counts", cnt, exp["counts"], ("n", "sx", "sxx", "xi", "init")))
+    for name, g, w, fields in checks:
+        if g.shape != w.shape:
+            return "%s shaped %s, want %s" % (name, g.shape, w.shape)
+        for f in fields:
+            bad = np.flatnonzero((_u64(g[f]) != _u64(w[f])).reshape(len(w), -1).any(axis=1))
+            if bad.size:
+                r = int(bad[0])
+                return "read %d (%d samples used): %s.%s got %r want %r" % (r, want["n_used"][r], name, f, g[f][r], w[f][r])
+    if post.tobytes() != want.tobytes():
+        return "the records' bytes differ where no field does"
+    if len(got) > 4 and not got[4]:                             # (before the return below: the call without dense rows too)
+        return "bytes written behind an output of the device form, or to one that was not asked for"
+    if gamma is None:
+        return None
+    if not np.array_equal(np.asarray(goff, dtype=np.int64), exp["goff"]):
+        return "goff %s want %s" % (np.asarray(goff).tolist()[:8], exp["goff"].tolist()[:8])
+    if gamma.shape != exp["gamma"].shape:
+        return "dense rows shaped %s, want %s" % (gamma.shape, exp["gamma"].shape)
+    if np.isnan(gamma).any():
+        return "a NaN among the dense rows, first at row %d" % int(np.flatnonzero(np.isnan(gamma).any(axis=1))[0])
+    bad = np.flatnonzero((_u64(gamma) != _u64(exp["gamma"])).any(axis=1))
+    if bad.size:
+        q = int(bad[0])
+        r = int(np.searchsorted(exp["goff"], q, side="right") - 1)
+        return "read %d (%d samples used): gamma differs first at sample %d: got %r want %r" % (
+            r, want["n_used"][r], q - int(exp["goff"][r]), gamma[q], exp["gamma"][q])
     return None
 
 
@@ -2953,19 +3264,20 @@ def result_bytes(got):
 
 DRAW = dict(sweep=draw_sweep, hits=draw_hits, paths=draw_paths, pull=draw_pull, panel=draw_panel, detect=draw_detect,
             hmm=draw_hmm, levels=draw_levels, screen=draw_screen, drna=draw_drna, roll=draw_roll, pairs=draw_pairs,
-            pairpaths=draw_pairpaths, band=draw_band)
+            pairpaths=draw_pairpaths, band=draw_band, hmmpost=draw_hmmpost)
 EXPECT = dict(sweep=expect_sweep, hits=expect_hits, paths=expect_paths, pull=expect_pull, segment=expect_plain,
               motifseq=expect_plain, pa=expect_plain, panel=expect_panel, detect=expect_detect, hmm=expect_hmm,
               levels=expect_levels, background=expect_background, events=expect_events, screen=expect_screen,
-              drna=expect_drna, roll=expect_roll, pairs=expect_pairs, pairpaths=expect_pairpaths, band=expect_band)
+              drna=expect_drna, roll=expect_roll, pairs=expect_pairs, pairpaths=expect_pairpaths, band=expect_band,
+              hmmpost=expect_hmmpost)
 CALL = dict(sweep=call_sweep, hits=call_hits, paths=call_paths, pull=call_pull, segment=call_plain, motifseq=call_plain,
             pa=call_plain, panel=call_panel, detect=call_detect, hmm=call_hmm, levels=call_levels,
             background=call_background, events=call_events, screen=call_screen, drna=call_drna, roll=call_roll,
-            pairs=call_pairs, pairpaths=call_pairpaths, band=call_band)
+            pairs=call_pairs, pairpaths=call_pairpaths, band=call_band, hmmpost=call_hmmpost)
 DIFF = dict(sweep=diff_sweep, hits=diff_hits, paths=diff_paths, pull=diff_pull, segment=diff_plain, motifseq=diff_plain,
             pa=diff_plain, panel=diff_panel, detect=diff_detect, hmm=diff_hmm, levels=diff_levels,
             background=diff_background, events=diff_events, screen=diff_screen, drna=diff_drna, roll=diff_roll,
-            pairs=diff_pairs, pairpaths=diff_pairpaths, band=diff_band)
+            pairs=diff_pairs, pairpaths=diff_pairpaths, band=diff_band, hmmpost=diff_hmmpost)
 TWIN_OF = dict(background="hits", events="paths")
 
 # ---- the interleaved sequence (tests/test_gpu_random.py::test_interleaved_calls_share_the_context_buffers) --------
@@ -3017,6 +3329,16 @@ INTERLEAVE4 = [("pairs", 9), ("paths", 12), ("pairpaths", 145), ("paths", 1), ("
 INTERLEAVE5 = [("band", 44), ("pairpaths", 13), ("band", 54), ("hits", 1), ("band", 351), ("pairs", 130), ("band", 331),
                ("pairpaths", 7), ("band", 297), ("hits", 324), ("band", 44), ("pairs", 5), ("band", 27), ("pairs", 130),
                ("band", 75), ("pairpaths", 13), ("band", 351), ("hits", 1), ("band", 331)]
+
+
+# the sixth sequence: posterior calls between Viterbi, detector, levels, pair-list and band calls.  c->hmm holds the
+# records of both HMM calls (with the calibration pairs behind them), c->hmmpost and c->hmmpostout only grow, c->sig / len /
+# off are everyone's: the largest case (hmmpost 305: a list of 200 reads, 165 258 samples) before a call of one read of 33
+# samples (hmmpost 427), hmmpost 185 -- four slices of one group under SK_HMM_SCRATCH_MB=1 -- directly after hmm 35, whose
+# state-path call takes three slices of the same budget, cases that come twice
+INTERLEAVE6 = [("hmmpost", 305), ("detect", 4), ("hmmpost", 427), ("hmm", 35), ("hmmpost", 185), ("levels", 13),
+               ("hmmpost", 68), ("pairs", 130), ("hmmpost", 2), ("band", 351), ("hmmpost", 185), ("hmm", 3),
+               ("hmmpost", 427), ("detect", 27), ("hmmpost", 34)]
 
 
 def interleave_case(family, seed):

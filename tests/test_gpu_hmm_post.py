@@ -306,6 +306,56 @@ def test_soft_pool_refit_and_interval(gpu, pool, models, want):
         assert -1 <= lo and (hi == -1 or lo <= hi < p["n_used"])
 
 
+def test_the_cut_off_of_sk_exp_is_inclusive(gpu):
+    """sk_exp(d) is 0.0 unless d >= -700.0.  Two states that never reach each other, the first with a constant emission
+    of 0.0, the second of c: on a read of one sample L = 0.0 (the second term of the sum is absorbed) and the second
+    state's posterior is sk_exp(c - 0.0).  c = -700.0 gives 2^-1010 times a polynomial, about 9.86e-305, not 0.0; the
+    next double below -700.0 gives 0.0, and so does a second sample (-1 400.0).  No drawn case gets an argument of
+    exactly -700.0 outside a sum that absorbs it (tests/RANDOM_CASES_HMMPOST.md), so this model is made by hand.  The
+    one-shot call on both feeds and a filtered session, against the statement, by bits."""
+    from squigglekit_amd import api
+    below = np.nextafter(-700.0, -np.inf)
+    edge = float(ref.sk_exp(np.array([-700.0]))[0])
+    assert 9.8e-305 < edge < 9.9e-305 and ref.sk_exp(np.array([below]))[0] == 0.0
+    reads = [np.array([500], dtype=np.int16), np.array([500, 501], dtype=np.int16), np.zeros(0, dtype=np.int16)]
+    buf, lens = rows_of(reads)
+    for c, first in ((-700.0, edge), (below, 0.0)):
+        arrays = dict(nstates=2, linit=np.zeros(2), ltrans=np.array([[0.0, NINF], [NINF, 0.0]]),
+                      c=np.array([[0.0, NINF], [c, NINF]]), mu=np.zeros((2, 2)), h=np.zeros((2, 2)))
+        theirs = ref.posterior_batch(arrays, buf, lens)
+        assert theirs[0]["loglik"].tolist() == [0.0, 0.0, 0.0] and theirs[3][:, 1].tolist() == [first, 0.0, 0.0]
+        assert theirs[0]["occ"][:2, 1].tolist() == [first, 0.0] and theirs[1]["init"][:2, 1].tolist() == [first, 0.0]
+        model = api.HmmModel.from_arrays(2, arrays["linit"], arrays["ltrans"], arrays["c"], arrays["mu"], arrays["h"])
+        assert_same(api.hmm_posterior_batch(buf, lens, model, counts=True, dense=True), theirs, "c = %r, int16 feed" % c)
+        got = api.hmm_posterior_ragged_f64(*api.pack_f64([r.astype(np.float64) for r in reads]), model, counts=True, dense=True)
+        assert_same(got, theirs, "c = %r, float64 feed" % c)
+        with api.HmmStream(model, 3, filter=True) as hs:
+            hs.push([0, 1], reads[:2])
+            filt = hs.filter([0, 1, 2])
+        assert bits(filt["post"]).tolist() == bits(theirs[0]["final_post"]).tolist() and filt["loglik"].tolist() == [0.0] * 3
+
+
+def test_three_em_rounds_equal_the_statement(gpu):
+    """three rounds of hmm_fit_em on 40 drawn reads of 100 .. 400 samples, from the GPU and with the statement as
+    `decode`: the same model, loglik and pooled bytes in every round -- rounds 2 and 3 run under the models the rounds
+    before them fitted, which no other test has seen"""
+    from squigglekit_amd import api
+    rng = np.random.default_rng(20261022)
+    reads = [planted(rng, int(n)) for n in rng.integers(100, 401, 40)]
+    spec = api.polya_spec("synth_raw")
+    mine, h1 = api.hmm_fit_em(reads, spec, (api.ADAPTER, api.POLYA), 3, min_count=4)
+    theirs, h2 = api.hmm_fit_em(reads, spec, (api.ADAPTER, api.POLYA), 3, min_count=4,
+                                decode=lambda batch, model, limit: [ref.posterior_reads(model, batch, limit)[:2]])
+    assert mine == theirs and len(h1) == len(h2) == 3
+    for a, b in zip(h1, h2):
+        assert a["spec"] == b["spec"] and a["reads"] == b["reads"] == len(reads), a["round"]
+        assert np.float64(a["loglik"]).tobytes() == np.float64(b["loglik"]).tobytes(), a["round"]
+        for f in ("n", "sum", "sumsq", "trans", "init"):
+            assert a["pooled"][f].tobytes() == b["pooled"][f].tobytes(), (a["round"], f)
+    assert h1[0]["spec"] != spec and h1[1]["spec"] != h1[0]["spec"] and h1[2]["spec"] != h1[1]["spec"]   # the model moved
+    assert h1[0]["loglik"] < h1[1]["loglik"] < h1[2]["loglik"]
+
+
 def test_cli_posterior_and_interval_columns(gpu, pool, models, tmp_path, capsys):
     """dRNA_polya.py -s --posterior --interval 0.1 on the GPU: the first seven columns are the tool's usual ones, the other
     seven those of the statement's posteriors; a read without samples has `.` throughout"""

@@ -5,10 +5,12 @@ the region + motif panel (sk_panel.hip), event detection (sk_detect.hip), the si
 hit family, the switches of the screening scheme (sk_sdtwq.hip), and both branches of the dRNA segmenter (sk_drna_walk.hip,
 k_drna_stats / k_roll_* of sk_prep.hip; host and device entry points), DTW over a pair list (sk_pairs.hip, k_sdtw's
 MODE_PAIRS / MODE_PAIRS_GLOBAL) and its warping paths (sk_pairpath.hip; host and device entry points) -- through the public
-api call, against its reference, exactly; the adaptive-band DTW (sk_band.hip; host and device entry points) likewise; and
-five interleaved sequences of calls over the shared grow-only context buffers.
+api call, against its reference, exactly; the adaptive-band DTW (sk_band.hip; host and device entry points) likewise; the
+signal HMM's posteriors (sk_hmm_post.hip; host and device entry points) against tests/hmm_post_ref.py bit for bit, each case
+also through a filtered HMM session (sk_hmmstream.hip); and six interleaved sequences of calls over the shared grow-only
+context buffers.
 tests/test_random_cases.py (CPU) asserts what the seeds
-reach; tests/RANDOM_CASES.md (tests/RANDOM_CASES_BAND.md for the band) lists the one-line kernel mutants these tests
+reach; tests/RANDOM_CASES.md (tests/RANDOM_CASES_BAND.md for the band, tests/RANDOM_CASES_HMMPOST.md for the posteriors) lists the one-line kernel mutants these tests
 catch.  A failure names family, seed, the
 drawn parameters and switches, and the first differing (read, hit / set / line): `randcases.case_of(family, seed)`
 rebuilds the case on any machine."""
@@ -498,6 +500,149 @@ def test_band_device_form_gives_the_host_form_bytes(gpu, ora, monkeypatch, seed)
         assert api.last_band_plan()[0] == (rc.band_slab_bytes(case["longest"], case["W"]) if with_spans else 0)
 
 
+_hmmpost_cases = {}
+
+
+def hmmpost_case(seed):
+    """(case, the statement's answer) of a committed hmmpost seed: computed once, shared by the tests below, never changed"""
+    if seed not in _hmmpost_cases:
+        case = rc.case_of("hmmpost", seed)
+        _hmmpost_cases[seed] = (case, rc.expect_hmmpost(None, case))
+    return _hmmpost_cases[seed]
+
+
+@pytest.mark.parametrize("seed", rc.SEEDS["hmmpost"])
+def test_hmmpost_seed_matches_the_statement(gpu, monkeypatch, seed):
+    """api.hmm_posterior_batch, hmm_posterior_ragged_f64 or hmm_posterior on a drawn model and drawn reads under drawn
+    switches, with the outputs the case asks for: n_used, flags, every double of the records and of the counts by its
+    bits, goff as integers, the dense rows by their bits and without a NaN (all in diff_hmmpost).  Then the complementary
+    call -- counts where none were drawn and the other way round, likewise the dense rows -- which takes the other
+    instantiation of k_hmm_bwd: what it returns is the statement's too, and its records are the first call's bytes."""
+    case, exp = hmmpost_case(seed)
+    got = run_again(monkeypatch, case, exp)
+    assert (got[1] is not None) == case["counts"] and (got[3] is not None) == case["dense"], rc.describe(case)
+    other = run_again(monkeypatch, dict(case, counts=not case["counts"], dense=not case["dense"]), exp)
+    assert other[0].tobytes() == got[0].tobytes() == exp["post"].tobytes(), rc.describe(case)
+
+
+def test_hmmpost_wavefront_with_both_kinds_of_reads_lane_by_lane(gpu, monkeypatch):
+    """The hand-made case of randcases.hmmpost_both_kinds: 65 reads, a possible one (two samples in most) in every even
+    lane and an impossible one in every odd lane, against the statement, with counts and dense rows and without."""
+    made = rc.hmmpost_both_kinds(*hmmpost_case(rc.POST_BOTH_SEED))
+    exp = rc.expect_hmmpost(None, made)
+    assert (exp["post"]["flags"][0::2] == 0).all() and (exp["post"]["flags"][1::2] != 0).all()
+    for counts, dense in ((True, True), (False, False)):
+        got = run_again(monkeypatch, dict(made, counts=counts, dense=dense), exp)
+        assert got[0].tobytes() == exp["post"].tobytes() and (got[1] is not None) == counts and (got[3] is not None) == dense
+
+
+# a calibrated batch on the 2-byte load path (stride 1 499), six states | SK_HMM_SCRATCH_MB=1: 200 reads in four slices of
+# one group, B = 4 096 | an aligned stride (1 032), calibrated: 16-byte loads as it stands, and vec = 0 through the base
+# when that is shifted by 2 or by 8 bytes
+HMMPOST_DEVICE_SEEDS = (162, 185, 34)
+HMMPOST_SHIFTED_SEED = 34
+
+
+@pytest.mark.parametrize("seed", HMMPOST_DEVICE_SEEDS)
+def test_hmmpost_device_form_gives_the_host_form_bytes(gpu, monkeypatch, seed):
+    """sk_hmm_posterior_dev_i16 on device buffers with guard bytes behind post, counts and the dense rows: the host form's
+    bytes, which are the statement's; with counts and the dense rows NULL the same records and not a byte written to
+    either buffer.  The seed with the aligned stride runs again with its rows 2 and 8 bytes behind a 16-byte boundary."""
+    from squigglekit_amd import api
+    case, exp = hmmpost_case(seed)
+    assert case["feed"] == "batch"
+    case = dict(case, counts=True, dense=True)
+    host = run_again(monkeypatch, case, exp)
+    assert seed != HMMPOST_SHIFTED_SEED or case["stride"] % 8 == 0
+    for shift in ((0, 2, 8) if seed == HMMPOST_SHIFTED_SEED else (0,)):
+        for counts, dense in ((True, True), (False, False)):
+            got = rc.hmmpost_device_call(api, case, counts, dense, shift)
+            msg = rc.diff_hmmpost(case, got, exp)
+            assert msg is None, "%s shift %d counts %s dense %s\n  first difference: %s" % (rc.describe(case), shift, counts,
+                                                                                         dense, msg)
+            assert got[4], "%s shift %d counts %s dense %s: bytes behind an output, or in a buffer that was not asked for" % (
+                rc.describe(case), shift, counts, dense)
+            assert got[0].tobytes() == host[0].tobytes(), (rc.describe(case), shift)
+            assert (got[1] is None) == (not counts) and (got[3] is None) == (not dense)
+            if counts:
+                assert got[1].tobytes() == host[1].tobytes() and got[3].tobytes() == host[3].tobytes(), (rc.describe(case), shift)
+
+
+FILTER_CHUNKS = (0, 1, 2, 31, 32, 33, 127, 128, 129)                   # 0: a peek; the seams of both tiles
+
+
+def same_as_records(filt, post, slots, what):
+    """the filters of `slots` against loglik, final_post, n_used and flags of their posterior records, bit for bit"""
+    want = np.zeros(len(slots), dtype=filt.dtype)
+    for f, g in (("loglik", "loglik"), ("n_used", "n_used"), ("flags", "flags"), ("post", "final_post")):
+        want[f] = post[g][slots]
+    assert not np.isnan(filt["loglik"]).any() and not np.isnan(filt["post"]).any(), what
+    if filt.tobytes() != want.tobytes():
+        bad = [i for i in range(len(want)) if filt[i].tobytes() != want[i].tobytes()]
+        raise AssertionError("%s: slot %d (%d slots differ)\n got  %r\n want %r" % (what, int(slots[bad[0]]), len(bad),
+                                                                                  filt[bad[0]], want[bad[0]]))
+
+
+@pytest.mark.parametrize("seed", rc.SEEDS["hmmpost"])
+def test_filtered_session_twin_of_the_hmmpost_seed(gpu, monkeypatch, seed):
+    """Every committed posterior case through a filtered session (k_hmms_push<FILT = true>) beside a plain one: each read's
+    first n_used samples arrive as chunks cut by default_rng([99, 14, seed]) -- 0, 1, 2, the seams of both tiles, or the
+    rest of the read at once -- for a shuffled subset of the slots per push, integer reads through push (under the case's
+    calibration pairs), float reads through push_values.  The plain session's records are the filtered one's bytes after
+    every push; once, at a drawn push, the filters of all slots are the statement of the prefixes pushed so far; at the end
+    they are loglik, final_post, n_used and flags of the case's records, and a slot that got nothing has the empty filter."""
+    import hmm_post_ref
+    import hmmfilter_ref as FR
+    from squigglekit_amd import api
+    case, exp = hmmpost_case(seed)
+    for key in rc.SWITCHES:
+        monkeypatch.delenv(key, raising=False)
+    rng = np.random.default_rng([99, 14, seed])
+    x, used = rc.hmmpost_rows(case)
+    R, reads = case["R"], case["reads"]
+    is_int = np.array([rc._is_int_read(r) for r in reads])
+    model = rc.hmm_model_of(api, case)
+    everyone = np.arange(R)
+    at = np.zeros(R, dtype=np.int64)
+    check_at, rounds, checked = int(rng.integers(1, 5)), 0, False
+    what = rc.describe(case)
+    with api.HmmStream(model, R, filter=True) as hf, api.HmmStream(model, R) as hp:
+        if case["cal"] is not None:
+            hf.reset(everyone, case["cal"])
+            hp.reset(everyone, case["cal"])
+        assert hf.filter(everyone).tobytes() == FR.empty_filters(R).tobytes(), what
+        while (at < used).any() or not checked:
+            live = np.flatnonzero(at < used)
+            named = np.concatenate([live[rng.random(live.size) < 0.7], everyone[rng.random(R) < 0.05]])
+            named = rng.permutation(np.unique(np.concatenate([named, live[:1]]))).astype(np.int64)
+            cut = np.where(rng.random(named.size) < 0.25, 1 << 30, rng.choice(FILTER_CHUNKS, size=named.size))
+            cut = np.minimum(cut, used[named] - at[named])
+            for ints in (True, False):
+                sel = is_int[named] == ints
+                slots, n = named[sel], cut[sel]
+                if not slots.size:
+                    continue
+                chunks = [reads[s][at[s]:at[s] + k] for s, k in zip(slots, n)]
+                if ints:
+                    chunks = [np.asarray(c, dtype=np.int16) for c in chunks]
+                    rec, plain = hf.push(slots, chunks), hp.push(slots, chunks)
+                else:
+                    rec, plain = hf.push_values(slots, chunks), hp.push_values(slots, chunks)
+                at[slots] += n
+                assert plain.tobytes() == rec.tobytes() and np.array_equal(rec["n_used"], at[slots]), (what, rounds)
+            rounds += 1
+            if rounds >= check_at and not checked:
+                checked = True
+                prefix = hmm_post_ref.posterior_rows(case["model"], x, at, counts=False, dense=False)[0]
+                same_as_records(hf.filter(everyone), prefix, everyone, "%s: prefixes after %d rounds" % (what, rounds))
+        assert np.array_equal(at, used)
+        same_as_records(hf.filter(everyone), exp["post"], everyone, what + ": the whole reads")
+        nothing = np.flatnonzero(used == 0)
+        assert hf.filter(nothing).tobytes() == FR.empty_filters(nothing.size).tobytes(), what
+        assert hf.peek(everyone).tobytes() == hp.peek(everyone).tobytes(), what
+    assert api.last_hmm_stream_plan()["guard_hits"] == 0
+
+
 def run_sequence(monkeypatch, ora, seq):
     seen = {}
     for step, (fam, seed) in enumerate(seq):
@@ -550,3 +695,11 @@ def test_band_calls_interleaved_with_the_pair_and_hit_families(gpu, ora, monkeyp
     slabs only grow (the widest slabs before a list of one short pair and again after it).  Every call against its
     reference, a call that occurs twice the same bytes both times."""
     run_sequence(monkeypatch, ora, rc.INTERLEAVE5)
+
+
+def test_posterior_calls_interleaved_with_the_viterbi_and_other_families(gpu, ora, monkeypatch):
+    """Posterior calls between Viterbi, detector, levels, pair-list and band calls: c->hmm holds the records of both HMM
+    calls, c->hmmpost (L, checkpoints, slabs) and c->hmmpostout (counts, goff, dense rows) only grow -- the largest case
+    before a call of one short read, a case in four slices directly after a state-path call in three slices of the same
+    SK_HMM_SCRATCH_MB budget.  Every call against its reference, a call that occurs twice the same bytes both times."""
+    run_sequence(monkeypatch, ora, rc.INTERLEAVE6)

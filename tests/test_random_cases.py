@@ -1674,3 +1674,270 @@ def test_fifth_interleaved_sequence_is_what_it_claims(cases):
     assert any(fa == "band" and (counted[sa] or 0) > 0 and fb == "pairpaths" and wrong[sb] == 0 for (fa, sa), (fb, sb) in steps)
     slab = [rc.band_slab_bytes(max(rc.case_of("band", s)["longest"], 1), rc.case_of("band", s)["W"]) for s in band]
     assert any(b < a // 20 for a, b in zip(slab, slab[1:])) and any(b > 20 * a for a, b in zip(slab, slab[1:])), slab
+
+
+# ---- signal HMM posteriors ----------------------------------------------------------------------------------------------
+# the seeds chosen for the two labels that need impossible reads; every other committed case is held to the 90 % cap
+HMMPOST_IMPOSSIBLE_SEEDS = (22, 68, 339)
+HMMPOST_MIXED_CASES = 4
+
+
+def hmmpost_features(case, exp):
+    """(labels, stats) from the case and the statement's answer alone.  stats: reads with samples, the possible ones among
+    them, whether the case counts as "mixed" (S >= 4, and at least half of all used samples lie in a possible read and
+    have max_j gamma_j(t) < 0.999)."""
+    import hmm_post_ref
+    from hmm_ref import model_arrays
+    post, cnt, goff, gamma = exp["post"], exp["counts"], exp["goff"], exp["gamma"]
+    R, S, env = case["R"], case["S"], case["env"]
+    x, used = rc.hmmpost_rows(case)
+    assert np.array_equal(post["n_used"], used) and case["total"] <= rc.POST_SAMPLES and case["longest"] <= rc.POST_LONGEST
+    assert case["total"] == sum(len(r) for r in case["reads"]) and case["longest"] == max(len(r) for r in case["reads"])
+    B = rc.post_block_of(env)
+    f = {"R=%d" % R, "S=%d" % S, "integer" if case["integer"] else "real", "block=%s" % env.get("SK_HMM_POST_BLOCK", "unset"),
+         "counts=%d dense=%d" % (case["counts"], case["dense"])}
+    f |= {"n_used=%d" % n for n in set(used.tolist()) if n in rc.POST_LENS}
+    if case["feed"] == "batch":
+        assert (case["stride"] % 8 == 0) == case["aligned"]
+        f.add("batch %s %s" % ("aligned" if case["aligned"] else "unaligned", "calibrated" if case["calibrated"] else "raw"))
+    elif case["feed"] == "f64":
+        assert case["nfloat"] == int((np.array([len(r) for r in case["reads"]]) > 0).sum())
+        f.add("feed=f64")
+    elif 0 < case["nfloat"] < R:
+        f.add("feed=list, integer and float reads")
+    if B == 128 and used.max(initial=0) > 19 * 128:
+        f.add("20 blocks at B = 128")
+    if env.get("SK_HMM_POST_BLOCK") == "4096" and 0 < used.max(initial=0) < 4096:
+        f.add("4096: every read shorter than the block")
+    if "SK_HMM_SCRATCH_MB" in env:
+        f |= {"%d slices" % k for k in (2, 3) if rc.hmmpost_slices(case) >= k}
+    if "SK_INGEST_MB" in env and rc.hmmpost_sub_batches(case) >= 2:
+        f.add("2 sub-batches")
+    lens = np.array([len(r) for r in case["reads"]])
+    if np.any(used < lens) and np.any((used == lens) & (lens > 0)):
+        f.add("the limit cuts some reads and not others")
+    live = (post["flags"] == 0) & (used > 0)
+    dead = post["flags"] != 0
+    assert not np.any(dead & (used == 0)) and np.all(np.isfinite(post["loglik"][live])) and np.all(post["loglik"][dead] == -np.inf)
+    lanes = 0                                                             # possible reads in a group that has both kinds
+    if case["feed"] != "list" and rc.hmmpost_sub_batches(case) == 1:      # (reads r and r + 1 share a wavefront by r // 64)
+        for g in range(0, R, 64):
+            if live[g:g + 64].any() and dead[g:g + 64].any():
+                f.add("a group of 64 with possible and impossible reads")
+                lanes = max(lanes, int(live[g:g + 64].sum()))
+    for r in np.flatnonzero(dead & (used >= 3))[:8]:
+        if hmm_post_ref.posterior_rows(case["model"], x[r:r + 1], [2], counts=False, dense=False)[0]["flags"][0] == 0:
+            f.add("a possible prefix of an impossible read, n >= 3")
+    if np.any(live[:, None] & (post["occ"][:, :S] == 0.0)):
+        f.add("a possible read with a state of occ 0.0")
+    if np.any(live[:, None] & (cnt["n"][:, :S, 0] > 0) & (cnt["n"][:, :S, 1] > 0)):
+        f.add("both components win in one read")
+    _, _, _, c, mu, h = model_arrays(case["model"])
+    at = np.arange(x.shape[1])[None, :] < used[:, None]
+    with np.errstate(invalid="ignore"):
+        a0 = c[:, 0] - ((x[..., None] - mu[:, 0]) * (x[..., None] - mu[:, 0])) * h[:, 0]
+        a1 = c[:, 1] - ((x[..., None] - mu[:, 1]) * (x[..., None] - mu[:, 1])) * h[:, 1]
+    if np.any(at[..., None] & (a1 == a0) & np.isfinite(a0)):
+        assert case["integer"]
+        f.add("a1 == a0")
+    top = gamma[:, :S].max(axis=1, initial=0.0)
+    row_live = np.repeat(live, used)
+    inner = (gamma[:, :S] > 0.0) & (gamma[:, :S] < 1.0)
+    for r in np.flatnonzero(live):
+        g = gamma[goff[r]:goff[r + 1], :S]
+        if np.any(g == 0.0) and inner[goff[r]:goff[r + 1]].any():
+            f.add("an exact 0.0 beside values inside (0, 1)")
+            break
+    assert not gamma[:, S:].any() and not gamma[~row_live].any() and not np.isnan(gamma).any()
+    mixed = S >= 4 and len(top) > 0 and 2 * int((row_live & (top < 0.999)).sum()) >= len(top)
+    return f, dict(reads=int((used > 0).sum()), possible=int(live.sum()), mixed=bool(mixed), lanes=lanes)
+
+
+HMMPOST_REQUIRED = ({"R=%d" % n for n in rc.HMM_COUNTS} | {"n_used=%d" % n for n in rc.POST_LENS} |
+                    {"S=%d" % s for s in range(1, 7)} | {"integer", "real", "feed=f64", "feed=list, integer and float reads"} |
+                    {"batch %s %s" % (a, c) for a in ("aligned", "unaligned") for c in ("calibrated", "raw")} |
+                    {"block=%s" % (b or "unset") for b in rc.POST_BLOCKS} |
+                    {"counts=%d dense=%d" % (c, d) for c in (0, 1) for d in (0, 1)} |
+                    {"20 blocks at B = 128", "4096: every read shorter than the block", "2 slices", "3 slices",
+                     "2 sub-batches", "the limit cuts some reads and not others",
+                     "a group of 64 with possible and impossible reads", "a possible prefix of an impossible read, n >= 3",
+                     "a possible read with a state of occ 0.0", "both components win in one read", "a1 == a0",
+                     "an exact 0.0 beside values inside (0, 1)"})
+HMMPOST_IMPOSSIBLE_LABELS = ("a group of 64 with possible and impossible reads", "a possible prefix of an impossible read, n >= 3")
+
+
+def test_hmmpost_cases_reach_every_boundary(cases):
+    """Every read count, every length of POST_LENS as some read's n_used, S = 1 .. 6, integer and real-valued models, every
+    feed (the batch aligned and unaligned, each calibrated and raw), every SK_HMM_POST_BLOCK setting, a read of 20 blocks
+    at B = 128 and a case under 4096 whose reads are all shorter than the block, two and three slices, two ingest
+    sub-batches, a limit that cuts some reads only, the four (counts, dense) calls; possible and impossible reads in one
+    wavefront, an impossible read with a possible prefix; an unreachable state in a possible read, both components
+    winning within a read, a1 == a0, an exact 0.0 beside values inside (0, 1); and HMMPOST_MIXED_CASES cases with S >= 4
+    in which at least half of all samples have max_j gamma_j(t) < 0.999.  Outside HMMPOST_IMPOSSIBLE_SEEDS nine reads in
+    ten with samples are possible, and over all cases at least 2 000 reads are possible and not empty -- also when the
+    cases of POST_MANY short reads are left out.  The wavefront with both kinds of reads is reached by two cases at the
+    least, in one of them with four possible reads or more (a case has impossible reads only where every path of its
+    model ends, so its possible reads have at most S samples and are few among lengths drawn up to 70 and more)."""
+    assert 12 <= len(cases["hmmpost"]) <= 24 and set(HMMPOST_IMPOSSIBLE_SEEDS) <= set(rc.SEEDS["hmmpost"])
+    have, mixed, possible, ordinary, lanes = set(), 0, 0, 0, []
+    for case, exp in cases["hmmpost"]:
+        f, st = hmmpost_features(case, exp)
+        have |= f
+        mixed += st["mixed"]
+        possible += st["possible"]
+        ordinary += st["possible"] if case["R"] <= max(rc.HMM_COUNTS) else 0
+        lanes += [st["lanes"]] if st["lanes"] else []
+        if case["seed"] in HMMPOST_IMPOSSIBLE_SEEDS:
+            assert f & set(HMMPOST_IMPOSSIBLE_LABELS), rc.describe(case)
+        else:
+            assert 10 * st["possible"] >= 9 * st["reads"], (rc.describe(case), st)
+    assert not sorted(HMMPOST_REQUIRED - have)
+    assert mixed >= HMMPOST_MIXED_CASES and possible >= 2000, (mixed, possible)
+    # ... and not through the cases of POST_MANY reads of 0 .. 12 samples alone: as many among the cases of HMM_COUNTS
+    assert ordinary >= 2000, ordinary
+    # the group with both kinds of reads rests on more than one case and on more than one possible read in it
+    assert len(lanes) >= 2 and max(lanes) >= 4, lanes
+
+
+def test_hmmpost_references_stay_inside_the_budget():
+    """The statement on every committed case, timed one by one: POST_SAMPLES samples and POST_LONGEST time steps stay under
+    3 s with room for a slower machine (tests/RANDOM_CASES_HMMPOST.md has the times)."""
+    import time
+    for seed in rc.SEEDS["hmmpost"]:
+        case = rc.case_of("hmmpost", seed)
+        t0 = time.perf_counter()
+        rc.EXPECT["hmmpost"](None, case)
+        assert time.perf_counter() - t0 < 3.0, rc.describe(case)
+
+
+def test_hmmpost_statement_by_classes_is_the_one_call():
+    """expect_hmmpost calls the statement once per class of randcases.hmmpost_classes (short rectangles in place of the wide
+    one: the CPU time of 8 400 short reads beside one of 130 samples falls sevenfold).  Every read's arithmetic is its own,
+    so the bytes are those of one call over all reads: asserted on three committed cases that fall into several classes,
+    a batch of 8 400 reads, a calibrated batch and a mixed list."""
+    for seed in (22, 34, 37):
+        case = rc.case_of("hmmpost", seed)
+        parts = rc.hmmpost_classes(rc.hmmpost_rows(case)[1])
+        assert len(parts) >= 2 and sorted(np.concatenate(parts).tolist()) == list(range(case["R"])), rc.describe(case)
+        one, whole = rc.expect_hmmpost(None, case), rc.expect_hmmpost(None, case, whole=True)
+        assert all(one[k].dtype == whole[k].dtype and one[k].tobytes() == whole[k].tobytes() for k in whole), rc.describe(case)
+
+
+PINNED_HMMPOST = {
+    2: "c3be055e3107ddb68c979ffb9b3e7b329de437e39ddfba0465a8dd24f5c4e7d3",
+    8: "ae0ed0e2a993f72efb6a5a0ff41742ba0048ef81e9a5d64d2fda4a2e485bd2b9",
+    21: "9ec3b96a0b3a769489749d252ddd90540a38349ccb0f043403d6da057fc72d16",
+    22: "3076e13e18a3d4ca0dd73cbebcd1336586e243558fa09a645b00d9ecc7f61109",
+    31: "c47f114ad41dd9d59a36b55eaa24e89dc2f67dd6c667cce2e4ba9d1fe3f73d91",
+    34: "bd5aa16bb987d7afba355555c0d1bc15d8bd42ef0badf1d900cd1d6059d87021",
+    37: "2e976b4767da6bc67f5d8a50deb798eb56bef4b16644d2a4f73a6e906d814f20",
+    48: "c5efd520e99019c80d6e597ca6841dd16807dd9e28f75a230ba793c7411b7077",
+    68: "6270a1803c908c6104b63e3e62ce13553568578ccd4a5c9de2108145d2db5d24",
+    77: "862c0ced2f190c9cf178327276b6e3e6e61ed6a4b01724b1bfad39161c6157a2",
+    124: "e9f68ac8b790d9e047981b6cb0a0425e5b9eadcc3782c003c5cc1dbe742a6a12",
+    137: "f4edfda1a03261c7a044e01603f029cfade24b0de89fc2c35074b08aa56228ce",
+    148: "3ed3272a2065c188ee2b60e0885314c811b7940bc5c151c72fa66215b1347260",
+    162: "0fd449fdced58a4ccedfa886cc97b2ba09f8c64740919352cc0bcacaf132a6c9",
+    185: "be327027757d85b5be490af3a0cbc9352a6b7de72ac3c4d55b6a0db4ff4188ff",
+    215: "e49dce7958f7dc1edd4ddd669887889c48564b2811c8427463f28aaab9865b30",
+    217: "65579ee21f7a053cf70cf25a51d021bbdcab77e756a96e62b7a69831432e1340",
+    239: "bb36e3b9cb15811a7b4603a92736791b9103cd9aa1d5dc66f75f37513bc07ba7",
+    305: "cdac25454e5c02998888ed0d1381d4de33d40731ae7c0d06b76a8f2ed454463f",
+    339: "189ab78722dc67d81d3f1ed280b69b716017ba8377177f567e9a1be12cc53f3d",
+    427: "75f9ea0051e3a5916b699c122c8eb89ebef81020fa94da9f1024e66098606756",
+    465: "af8cb7bfe2fd0815b7a7bbffa3e8905b71af8d0aa142a87d3c5ffc97618941cb",
+}
+
+
+def test_hmmpost_family_keeps_its_cases():
+    assert rc.FAMILY_INDEX["hmmpost"] == 14 and "SK_HMM_POST_BLOCK" in rc.SWITCHES
+    assert list(PINNED_HMMPOST) == rc.SEEDS["hmmpost"]
+    for seed, digest in PINNED_HMMPOST.items():
+        case = rc.case_of("hmmpost", seed)
+        assert rc.case_digest(case) == digest, seed
+        assert rc.describe(case).startswith("hmmpost seed=%d R=" % seed)
+        assert set(case["env"]) <= {"SK_HMM_POST_BLOCK", "SK_HMM_SCRATCH_MB", "SK_INGEST_MB"}
+
+
+def test_hmmpost_hand_made_case_holds_both_kinds_of_reads_lane_by_lane(cases):
+    """randcases.hmmpost_both_kinds out of seed POST_BOTH_SEED: one call, one sub-batch, and in its first group of 64 a
+    possible read in every even lane, an impossible one in every odd lane; at least 20 of the possible ones have two
+    samples, so that they take a forward step, a backward step and a transition count beside lanes that are dead."""
+    case, exp = next((c, e) for c, e in cases["hmmpost"] if c["seed"] == rc.POST_BOTH_SEED)
+    made = rc.hmmpost_both_kinds(case, exp)
+    post = rc.expect_hmmpost(None, made)["post"]
+    assert made["R"] == rc.POST_BOTH_READS == 65 and rc.hmmpost_sub_batches(made) == 1 and made["sig"].shape[0] == 65
+    live, dead = (post["flags"] == 0) & (post["n_used"] > 0), post["flags"] != 0
+    assert live[0::2].all() and dead[1::2].all() and int((post["n_used"][:64][live[:64]] >= 2).sum()) >= 20
+    assert np.all(post["n_used"][dead] >= 3) and made["total"] == sum(len(r) for r in made["reads"]) <= case["total"]
+
+
+def test_diff_hmmpost_reports_an_unclean_device_call_whatever_it_returned():
+    """The fifth entry of what hmmpost_device_call returns (nothing written behind an output, nothing at all to a buffer
+    that was not asked for) is looked at with and without counts and dense rows; a host call has no fifth entry."""
+    case = rc.case_of("hmmpost", 427)
+    exp = rc.expect_hmmpost(None, case)
+    full = (exp["post"].copy(), exp["counts"].copy(), exp["goff"].copy(), exp["gamma"].copy())
+    bare = (exp["post"].copy(), None, None, None)
+    for got in (full, bare):
+        assert rc.diff_hmmpost(case, got, exp) is None and rc.diff_hmmpost(case, got + (True,), exp) is None
+        assert "not asked for" in rc.diff_hmmpost(case, got + (False,), exp)
+
+
+def hmmpost_against_scipy(case, exp, most=8, longest=600):
+    """(largest |loglik difference| in ulp of the scipy route's, largest |gamma difference|, the same divided by
+    max(1, |loglik|) * 2^-52, reads compared): up to `most` possible reads of at most `longest` samples"""
+    from test_hmm_post_host import plain_forward_backward
+    x, used = rc.hmmpost_rows(case)
+    post, goff, gamma, S = exp["post"], exp["goff"], exp["gamma"], case["S"]
+    worst_l = worst_g = worst_s = 0.0
+    rows = [r for r in range(case["R"]) if post["flags"][r] == 0 and 0 < used[r] <= longest][:most]
+    for r in rows:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            L, g, _ = plain_forward_backward(case["model"], x[r, :used[r]])
+        worst_l = max(worst_l, abs(post["loglik"][r] - L) / np.spacing(abs(L)))
+        d = float(np.abs(gamma[goff[r]:goff[r + 1], :S] - g).max())
+        worst_g = max(worst_g, d)
+        worst_s = max(worst_s, d / (max(1.0, abs(L)) * 2.0 ** -52))
+    return worst_l, worst_g, worst_s, len(rows)
+
+
+def test_hmmpost_statement_against_the_scipy_route(cases):
+    """The statement is the oracle of the GPU leg: on the real-valued committed cases (up to 8 possible reads of at most 600
+    samples each) it is compared with plain_forward_backward of tests/test_hmm_post_host.py, scipy's logsumexp and numpy's
+    exp.
+
+    Measured (numpy 2, scipy 1.x, glibc): loglik equals the scipy route's to the last bit on all 106 reads (bound: 4 ulp, as in
+    test_statement_against_a_plain_logsumexp_forward_backward), gamma differs by at most 3.64e-12, which is 1.43 in units of
+    max(1, |L|) * 2^-52.  Both routes carry |L| * 2^-53 in the argument of the last exp, and the
+    drawn reads hold anything an int16 holds, so |L| reaches 1e10 and more where the planted reads of
+    test_statement_against_a_plain_logsumexp_forward_backward stay near 1e4: the absolute gamma difference is that rounding
+    error, which the scaled figure shows.  The bounds are four times the measured values, for other libm and scipy builds."""
+    worst = [0.0, 0.0, 0.0, 0]
+    for case, exp in cases["hmmpost"]:
+        if case["integer"]:
+            continue
+        got = hmmpost_against_scipy(case, exp)
+        worst = [max(a, b) for a, b in zip(worst[:3], got[:3])] + [worst[3] + got[3]]
+    print("loglik %.3g ulp, gamma %.3g absolute, %.3g in units of max(1, |L|) * 2^-52, %d reads" % tuple(worst))
+    assert worst[3] >= 40
+    assert worst[0] <= 4 and worst[1] <= 4 * 3.64e-12 and worst[2] <= 4 * 1.43
+
+
+def test_sixth_interleaved_sequence_is_what_it_claims(cases):
+    """Posterior cases between hmm, detect, levels, pairs and band cases, never two of a family in a row; two posterior
+    cases that come twice; the largest case before the smallest; a case in at least two slices under SK_HMM_SCRATCH_MB=1
+    directly after a Viterbi case whose state-path call is sliced under the same budget."""
+    seq = rc.INTERLEAVE6
+    assert {f for f, _ in seq} == {"hmmpost", "hmm", "detect", "levels", "pairs", "band"}
+    assert all(seed in rc.SEEDS[fam] for fam, seed in seq)
+    assert all((a == "hmmpost") != (b == "hmmpost") for (a, _), (b, _) in zip(seq, seq[1:]))
+    mine = [s for f, s in seq if f == "hmmpost"]
+    assert len(mine) - len(set(mine)) >= 2
+    by_seed = {case["seed"]: case for case, _ in cases["hmmpost"]}
+    used = {case["seed"]: int(exp["post"]["n_used"].sum()) for case, exp in cases["hmmpost"]}      # (samples the call uses)
+    assert used[mine[0]] == max(used.values()) > 1000 * used[mine[1]] and used[mine[1]] == min(used.values())
+    hmm = {case["seed"]: case for case, _ in cases["hmm"]}
+    assert any(fa == "hmm" and "SK_HMM_SCRATCH_MB" in hmm[sa]["env"] and rc.hmm_slices(hmm[sa]) >= 2 and fb == "hmmpost" and
+               "SK_HMM_SCRATCH_MB" in by_seed[sb]["env"] and rc.hmmpost_slices(by_seed[sb]) >= 2
+               for (fa, sa), (fb, sb) in zip(seq, seq[1:]))

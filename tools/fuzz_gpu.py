@@ -12,8 +12,8 @@ concatenation after every push; and one event session (tests/evstream_ref.draw_s
 count, reads of four kinds, cuts, subsets, ENDs and resets) against its statement on detect_ref after every push and
 against the one-shot call on every ended read; and one hit-list round (tests/pair_hits_ref.py: a drawn pair list with its
 K, max_dist and row budget, and a drawn session script whose hits() are read after every push) against the statement
-there; and one posterior round (randcases.draw_hmm's models, reads, feeds and switches, a limit of at most 1 200 samples so
-that the statement stays quick, SK_HMM_POST_BLOCK drawn) against tests/hmm_post_ref.py, every double by its bits; and one
+there; and one posterior round (the `hmmpost` family of tests/randcases.py: draw_hmm's models, reads of up to 2 600
+samples, feeds, outputs and switches, SK_HMM_POST_BLOCK among them) against tests/hmm_post_ref.py, every double by its bits; and one
 filtered HMM session (hmmstream_ref.draw_session's script on a drawn model, beside a plain session) against
 tests/hmmfilter_ref.py after every push, every double by its bits.  The DTW pair
 lists, their warping paths and the adaptive band are three of the families of tests/randcases.py (`pairs`, `pairpaths`,
@@ -37,7 +37,6 @@ import stream_ref                                     # noqa: E402
 import mapstream_ref                                  # noqa: E402
 import evstream_ref                                   # noqa: E402
 import pair_hits_ref                                  # noqa: E402
-import hmm_post_ref                                   # noqa: E402
 import hmmstream_ref                                  # noqa: E402
 import hmmfilter_ref                                  # noqa: E402
 from squigglekit_amd import api, synth               # noqa: E402
@@ -121,43 +120,22 @@ def pairhits_round(rng):
 
 
 def hmm_post_round(rng):
-    """One drawn posterior call (records, soft counts, dense rows) against tests/hmm_post_ref.py, bit for bit.  Returns
-    None, or what differed."""
-    case = randcases.draw_hmm(rng)
-    limit = case["limit"] if 0 < case["limit"] <= 1200 else 1200
-    env = dict(case["env"])
-    if rng.random() < 0.4:
-        env["SK_HMM_POST_BLOCK"] = "256"
-    counts, dense = bool(rng.random() < 0.8), bool(rng.random() < 0.8)
-    model, reads = randcases.hmm_model_of(api, case), case["reads"]
-    desc = "%d reads, max length %d, %d states%s, limit %d, feed %s%s, counts %s, dense %s, env %s" % (
-        case["R"], case["dmax"], case["S"], " (integer scores)" if case["integer"] else "", limit, case["feed"],
-        " calibrated" if case["calibrated"] else "", counts, dense, env)
-    os.environ.update(env)
+    """One drawn posterior call -- randcases.DRAW["hmmpost"] with the running generator: the family the suite's committed
+    seeds come from -- against tests/hmm_post_ref.py through randcases.diff_hmmpost, every double by its bits; then the
+    complementary call (the other outputs, the other k_hmm_bwd).  Returns None, or what differed."""
+    case = randcases.DRAW["hmmpost"](rng)
+    exp = randcases.EXPECT["hmmpost"](ora, case)
+    for key in randcases.SWITCHES:
+        os.environ.pop(key, None)
+    os.environ.update(case["env"])
     try:
-        if case["feed"] == "batch":
-            want = hmm_post_ref.posterior_batch(case["model"], case["sig"], case["lens"], case["cal"], limit)
-            post, cnt, goff, gamma = api.hmm_posterior_batch(case["sig"], case["lens"], model, case["cal"], limit, counts, dense)
-        else:
-            want = hmm_post_ref.posterior_reads(case["model"], reads, limit)
-            if case["feed"] == "f64":
-                post, cnt, goff, gamma = api.hmm_posterior_ragged_f64(*api.pack_f64(reads), model, limit, counts, dense)
-            else:
-                post, cnt, gammas = api.hmm_posterior(reads, model, limit, counts, dense)
-                gamma = np.concatenate(gammas + [np.zeros((0, 6))]) if dense else None
+        for c in (case, dict(case, counts=not case["counts"], dense=not case["dense"])):
+            msg = randcases.DIFF["hmmpost"](c, randcases.CALL["hmmpost"](api, c, exp), exp)
+            if msg is not None:
+                return "%s counts=%s dense=%s: %s" % (randcases.describe(case), c["counts"], c["dense"], msg)
     finally:
-        for key in env:
+        for key in case["env"]:
             os.environ.pop(key, None)
-    if post.tobytes() != want[0].tobytes():
-        bad = [r for r in range(len(post)) if post[r].tobytes() != want[0][r].tobytes()]
-        return "%s: the record of read %d differs: got %s want %s" % (desc, bad[0], post[bad[0]], want[0][bad[0]])
-    if counts and cnt.tobytes() != want[1].tobytes():
-        bad = [r for r in range(len(cnt)) if cnt[r].tobytes() != want[1][r].tobytes()]
-        return "%s: the counts of read %d differ" % (desc, bad[0])
-    if dense and gamma.tobytes() != want[3].tobytes():
-        return "%s: the dense posteriors differ" % desc
-    if dense and np.isnan(gamma).any():
-        return "%s: a NaN among the dense posteriors" % desc
     return None
 
 
