@@ -1553,6 +1553,60 @@ int sk_live_gate_fetch_dev(int32_t handle, sk_live_gate_info *d_gate, sk_hmms_re
  * gate.  Either pointer may be NULL; SK_ERR_INVALID on an ungated handle. */
 int sk_live_gate_last_ms(int32_t handle, float *hmm_ms, float *gate_ms);
 
+/* Reference pile-up: per-point event statistics over aligned reads (tests/pileup_ref.py states this in numpy).
+ * sk_dtw_pairs_paths, sk_dtw_band and the mapping calls say which target points every query point (event) of a pair
+ * covers.  The pile-up turns that table round: for every point of every target, the events that cover it, in the reading
+ * order of the table, and their statistics.
+ * Inputs: span_off [npairs + 1] and spans [nrows][2] in the layout of those calls -- the rows of pair p are
+ *     span_off[p] .. span_off[p + 1], row e covers the target points a_e .. b_e, a_e < 0 is "no path"; value [nrows] the
+ *     query point of the row (an event's normalised level), dwell [nrows] its samples (NULL: ones); target [npairs] the
+ *     target the pair was aligned to (NULL: zeros; negative: the pair is left out), shift [npairs] added to both ends of
+ *     every span of the pair (NULL: zeros; a pair traced against target[start : start + span] has shift = start), use
+ *     [npairs] (NULL: all ones; 0 leaves the pair out); tlen [ntargets] the targets' lengths.  toff = their running sum:
+ *     point j of target t has the flat index toff[t] + j, Mtot = toff[ntargets].
+ * Entries: row e of pair p is USED when target[p] >= 0, use[p] != 0 and a_e >= 0; a used row is one entry of every point
+ *     a_e + shift[p] .. b_e + shift[p] of target[p].  A point's list is ordered by ascending row index.
+ * out [Mtot], one sk_pile_rec per flat point; with v = value and d = dwell over the point's list, in order, numpy's
+ *     expressions and its order of summation (np.add.reduce: buffers of 8 192 terms, the pairwise tree inside one), bit
+ *     for bit:
+ *         level = np.mean(v)   level_sd = np.std(v)   vmin = np.min(v)   vmax = np.max(v)
+ *         dwell_mean = np.sum(d, dtype=int64) / n     dwell_sd = np.std(d.astype(float64))
+ *         n = entries   depth = distinct pairs among them   shared = entries whose row covers more than one point
+ *     A point without entries has six NaN doubles (0x7FF8000000000000) and three zeros.  A NaN among v gives NaN in the
+ *     four statistics of v: the first NaN of the list, quieted.  A NaN that the arithmetic itself makes (inf - inf) has
+ *     the bits 0xFFF8000000000000, which is what numpy gives on an x86-64 host; a list that holds both a NaN and such
+ *     a sum gets the list's NaN.  When a list holds both zeros the sign of a zero vmin / vmax is not defined.  No field
+ *     is formed with floating-point atomics: two calls give the same bytes.
+ * ent_off [Mtot + 1], ent_row [ent_cap] (both NULL, or both set): the inverted index itself -- the rows of flat point m
+ *     are ent_row[ent_off[m] .. ent_off[m + 1]), ascending.  ent_off[Mtot] = the sum of b_e - a_e + 1 over the used rows.
+ * Refusals (SK_ERR_INVALID), checked before anything is written to out / ent_off / ent_row.  By the arguments alone:
+ *     npairs, nrows or ntargets negative, a NULL out / tlen / span_off, NULL spans / value with nrows > 0, one of ent_off
+ *     / ent_row without the other, a negative ent_cap, a negative tlen (the target is named).  Then on the device, the
+ *     lowest offending pair index named in sk_last_error() whatever the launch order: span_off[0] != 0, span_off not
+ *     non-decreasing (the pair whose range ends before it begins), span_off[npairs] != nrows -- these three first, since
+ *     they decide which pair a row belongs to; then target[p] >= ntargets (whether or not the pair is used), a used row
+ *     with b_e < a_e, a used row whose shifted span leaves [0, tlen[t]).  Then ent_cap below the number of entries.
+ *     npairs == 0 or nrows == 0 is SK_OK with every record the empty one; tlen == 0 is legal.
+ * Limits: nrows <= 2^31 - 1, Mtot <= 2^40, entries per point <= 2^31 - 1, entries in all <= 2^40 (SK_ERR_UNSUPPORTED
+ *     with the limit named); device memory per entry 4 bytes, 8 when a list takes the merge tier; 16 bytes per point and
+ *     4 per row beside them (SK_ERR_NOMEM when it does not fit).
+ * sk_pileup: every pointer a host pointer.  sk_pileup_dev: device pointers but tlen, which stays on the host (the
+ *     convention of sk_dtw_pairs_paths_dev); it synchronises once, to read the checks' verdict and the entry count.
+ * sk_last_pileup_plan: the last such call on this context -- entries, the longest list, the lists that took the merge
+ *     tier, bytes of device scratch; any pointer may be NULL. */
+typedef struct sk_pile_rec {        /* 64 bytes */
+    double  level, level_sd, vmin, vmax, dwell_mean, dwell_sd;
+    int32_t depth, n, shared, pad;
+} sk_pile_rec;
+int sk_pileup(const int64_t *span_off, const int32_t *spans, const double *value, const int32_t *dwell,
+              const int32_t *target, const int32_t *shift, const uint8_t *use, int32_t npairs, int64_t nrows,
+              const int64_t *tlen, int32_t ntargets, sk_pile_rec *out, int64_t *ent_off, int32_t *ent_row, int64_t ent_cap);
+int sk_pileup_dev(const int64_t *d_span_off, const int32_t *d_spans, const double *d_value, const int32_t *d_dwell,
+                  const int32_t *d_target, const int32_t *d_shift, const uint8_t *d_use, int32_t npairs, int64_t nrows,
+                  const int64_t *tlen, int32_t ntargets, sk_pile_rec *d_out, int64_t *d_ent_off, int32_t *d_ent_row,
+                  int64_t ent_cap);
+int sk_last_pileup_plan(int64_t *entries, int64_t *longest_list, int64_t *lists_in_long_tier, int64_t *scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,6 +292,17 @@ GATE_DTYPE = np.dtype([("state", "<i4"), ("t0", "<i4"), ("decided_n", "<i4"), ("
                        ("ring", "<i4"), ("dropped", "<i4"), ("flags", "<i4")])
 
 
+class PileRec(C.Structure):
+    """sk_pile_rec: one flat reference point of a pile-up (64 bytes)."""
+    _fields_ = [("level", C.c_double), ("level_sd", C.c_double), ("vmin", C.c_double), ("vmax", C.c_double),
+                ("dwell_mean", C.c_double), ("dwell_sd", C.c_double), ("depth", C.c_int32), ("n", C.c_int32),
+                ("shared", C.c_int32), ("pad", C.c_int32)]
+
+
+PILE_DTYPE = np.dtype([("level", "<f8"), ("level_sd", "<f8"), ("vmin", "<f8"), ("vmax", "<f8"), ("dwell_mean", "<f8"),
+                       ("dwell_sd", "<f8"), ("depth", "<i4"), ("n", "<i4"), ("shared", "<i4"), ("pad", "<i4")])
+
+
 class LiveGate(C.Structure):
     """sk_live_gate: api.polya_decide's thresholds with the state whose entry is the start, and the hold ring's length."""
     _fields_ = [("state", C.c_int32), ("min_body", C.c_int32), ("give_up", C.c_int32), ("hold", C.c_int32),
@@ -546,6 +557,13 @@ ABI = {
     "sk_live_gate_fetch": (C.c_int, [C.c_int32, _vp, _vp]),
     "sk_live_gate_fetch_dev": (C.c_int, [C.c_int32, _vp, _vp]),
     "sk_live_gate_last_ms": (C.c_int, [C.c_int32, _vp, _vp]),
+    # reference pile-up ("Reference pile-up" in the header; tests/pileup_ref.py states it in numpy): span_off, spans, value,
+    # dwell, target, shift, use, npairs, nrows, tlen, ntargets, out [Mtot], ent_off, ent_row, ent_cap -- the device-resident
+    # form takes the same list (tlen stays a host pointer); the last call's plan
+    "sk_pileup": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64]),
+    "sk_pileup_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp,
+                                C.c_int64]),
+    "sk_last_pileup_plan": (C.c_int, [_vp, _vp, _vp, _vp]),
 }
 
 

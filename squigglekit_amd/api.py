@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_COUNTS_DTYPE, HMM_DTYPE, HMM_POST_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HMMS_FILT_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
+from ._lib import (BG_DTYPE, DET_EVENT_DTYPE, DetParams, EVENT_DTYPE, GATE_DTYPE, LiveGate, HIT_DTYPE, HMM_COUNTS_DTYPE, HMM_DTYPE, HMM_POST_DTYPE, HMM_SEG_DTYPE, HMM_SEGF_DTYPE, HMMS_DTYPE, HMMS_FILT_DTYPE, HmmModel, LEVEL_DTYPE, LIVEBEST_DTYPE, LIVEINFO_DTYPE, LiveRule, MAPREC_DTYPE, PANEL_DTYPE, PILE_DTYPE, POOL_DTYPE, STREAM_DTYPE, SWEEP_REC_DTYPE, SWEEP_SUM_DTYPE, SegParams, SquiggleKitError, SweepSet,  # noqa: F401
                    check, ptr)
 
 
@@ -3434,3 +3434,163 @@ def polya_decide_post(rec, filt, min_body, min_post, give_up, min_rate=None):
     dec[reject & ~accept] = -1
     dec[accept] = 1
     return dec.reshape(rec.shape)
+
+
+# ----------------------------------------------------------------------------
+# Reference pile-up: per-point event statistics over aligned reads ("Reference pile-up" in include/squigglekit_hip.h and
+# DESIGN.md 4.26; tests/pileup_ref.py states it in numpy)
+# ----------------------------------------------------------------------------
+PILE_CMP_DTYPE = np.dtype([("depth_a", "<i4"), ("depth_b", "<i4"), ("level_a", "<f8"), ("level_b", "<f8"), ("diff", "<f8"),
+                           ("t", "<f8"), ("df", "<f8"), ("d", "<f8")])
+
+
+def _pile_vec(x, n, dtype, name, fill):
+    if x is None:
+        return np.full(n, fill, dtype=dtype)
+    a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+    if a.size != n:
+        raise ValueError("%s: need %d entries, got %d" % (name, n, a.size))
+    return a
+
+
+def pileup(span_off, spans, value, dwell=None, target=None, shift=None, use=None, tlen=None, entries=False):
+    """The alignment table turned round: for every point of every target the rows (events) that cover it, and their
+    statistics.  span_off int64 [P + 1] and spans int32 [E, 2] in the layout of dtw_pairs_paths / dtw_band / map_paths (a
+    row with a negative first entry has no path); value float64 [E] the query point of each row, dwell int32 [E] its
+    samples (default ones); target int32 [P] the target each pair was aligned to (default 0; negative leaves the pair
+    out), shift int32 [P] added to both ends of the pair's spans (default 0), use [P] a mask (0 leaves the pair out); tlen
+    the targets' lengths.  Returns pile PILE_DTYPE [sum(tlen)], target after target (pile_split cuts it up): level,
+    level_sd, vmin, vmax, dwell_mean and dwell_sd are np.mean / np.std / np.min / np.max / np.sum(int64) / n / np.std over
+    the point's rows in ascending row order, bit for bit; depth the distinct pairs, n the rows, shared the rows that cover
+    more than one point; a point nobody covers has NaN and zeros.  entries=True: (pile, ent_off int64 [sum(tlen) + 1],
+    ent_row int32) as well, the rows of flat point m being ent_row[ent_off[m]:ent_off[m + 1]], ascending.  The library
+    refuses (SquiggleKitError, code -1, the lowest offending pair named) a span that ends before it begins or leaves its
+    target, a target index beyond tlen, and a span_off that is no non-decreasing cover of the rows.  Single device."""
+    if tlen is None:
+        raise ValueError("pileup: tlen (the targets' lengths) is required")
+    span_off = np.ascontiguousarray(span_off, dtype=np.int64).reshape(-1)
+    if span_off.size < 1:
+        raise ValueError("span_off: need npairs + 1 entries")
+    P = span_off.size - 1
+    spans = np.ascontiguousarray(spans, dtype=np.int32).reshape(-1, 2)
+    E = len(spans)
+    value = _pile_vec(value, E, np.float64, "value", 0.0)
+    dwell = _pile_vec(dwell, E, np.int32, "dwell", 1)
+    target = _pile_vec(target, P, np.int32, "target", 0)
+    shift = _pile_vec(shift, P, np.int32, "shift", 0)
+    use = None if use is None else _pile_vec(np.asarray(use) != 0, P, np.uint8, "use", 1)
+    tlen = np.ascontiguousarray(tlen, dtype=np.int64).reshape(-1)
+    mtot = int(tlen.sum()) if tlen.size and tlen.min() >= 0 else 0
+    pile = np.zeros(mtot, dtype=PILE_DTYPE)
+    ent_off = ent_row = None
+    cap = 0
+    if entries:
+        # the entries, to size ent_row (a span_off the library will refuse leaves it empty)
+        if P and E and span_off[0] == 0 and span_off[-1] == E and not np.any(np.diff(span_off) < 0):
+            rp = np.repeat(np.arange(P), np.diff(span_off))
+            on = (target[rp] >= 0) & (spans[:, 0] >= 0)
+            if use is not None:
+                on &= use[rp] != 0
+            cap = int(np.maximum(spans[on, 1].astype(np.int64) - spans[on, 0] + 1, 0).sum())
+        ent_off = np.zeros(mtot + 1, dtype=np.int64)
+        ent_row = np.zeros(cap, dtype=np.int32)
+
+    def p(a, empty):
+        return ptr(a if a.size else empty)
+    z8, z4 = np.zeros(1, dtype=np.int64), np.zeros(2, dtype=np.int32)
+    L = _lib.ensure_init()                                          # (after the checks that need no device)
+    check(L.sk_pileup(ptr(span_off), p(spans, z4), p(value, np.zeros(1)), p(dwell, z4), p(target, z4), p(shift, z4),
+                      None if use is None else p(use, np.zeros(1, dtype=np.uint8)), P, E, p(tlen, z8), tlen.size,
+                      p(pile, np.zeros(1, dtype=PILE_DTYPE)), None if ent_off is None else ptr(ent_off),
+                      None if ent_row is None else p(ent_row, z4), cap))
+    return (pile, ent_off, ent_row) if entries else pile
+
+
+def last_pileup_plan():
+    """The last pileup call of this thread's device: {"entries", "longest_list", "lists_in_long_tier", "scratch_bytes"} --
+    the entries of the inverted index, the longest point's list, the lists that were put in order by the merge tier
+    instead of inside one wavefront's LDS, the bytes of device scratch."""
+    L = _lib.ensure_init()
+    v = [C.c_int64() for _ in range(4)]
+    check(L.sk_last_pileup_plan(*[C.byref(x) for x in v]))
+    return dict(zip(("entries", "longest_list", "lists_in_long_tier", "scratch_bytes"), (x.value for x in v)))
+
+
+def pileup_of_map(queries, dwells, targets, records, span_off, spans, which=None):
+    """pileup over what map_queries / map_paths returned: queries the (normalised) query sequences, dwells one int array
+    per query (or None: ones), records [T, Q], (span_off, spans) from map_paths(queries, targets, records, which).  The
+    target of query q is which[q] (default best_targets(records)); a query without a path is left out.  Returns the pile
+    over the targets, in their order."""
+    qs = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
+    Q = len(qs)
+    which = best_targets(np.asarray(records)) if which is None else np.asarray(which, dtype=np.int64).reshape(-1)
+    if which.size != Q:
+        raise ValueError("which: need one target index per query")
+    span_off = np.asarray(span_off, dtype=np.int64).reshape(-1)
+    if span_off.size != Q + 1:
+        raise ValueError("span_off: need one entry per query and one more (map_paths' layout)")
+    has = np.diff(span_off) > 0
+    if any(has[q] and span_off[q + 1] - span_off[q] != qs[q].size for q in range(Q)):
+        raise ValueError("span_off does not match the queries' lengths")
+    value = np.concatenate([qs[q] for q in range(Q) if has[q]]) if has.any() else np.zeros(0)
+    dwell = None
+    if dwells is not None:
+        ds = [np.asarray(d, dtype=np.int32).reshape(-1) for d in dwells]
+        if len(ds) != Q or any(ds[q].size != qs[q].size for q in range(Q)):
+            raise ValueError("dwells: need one entry per query point")
+        dwell = np.concatenate([ds[q] for q in range(Q) if has[q]]) if has.any() else np.zeros(0, dtype=np.int32)
+    tlen = [np.asarray(t).size for t in targets]
+    return pileup(span_off, spans, value, dwell=dwell, target=np.where(has, which, -1), tlen=tlen)
+
+
+def pile_split(pile, tlen):
+    """The per-target views of a flat pile (or of any per-point array): a list, target after target."""
+    tlen = np.asarray(tlen, dtype=np.int64).reshape(-1)
+    if tlen.size and tlen.min() < 0 or int(tlen.sum()) != len(pile):
+        raise ValueError("pile_split: the lengths do not add up to the pile's %d points" % len(pile))
+    toff = np.concatenate([[0], np.cumsum(tlen)])
+    return [pile[toff[t]:toff[t + 1]] for t in range(tlen.size)]
+
+
+def refine_targets(targets, pile, min_depth=1):
+    """One step of DTW barycentre averaging for whole references, the counterpart of refine_motif: point j of a target
+    becomes the pile's level there when depth >= min_depth and the level is a number, and stays as it is otherwise.
+    Returns new arrays, one per target.  Host numpy."""
+    ts = [np.asarray(t, dtype=np.float64).reshape(-1) for t in targets]
+    out = []
+    for t, part in zip(ts, pile_split(pile, [t.size for t in ts])):
+        ok = (part["depth"] >= int(min_depth)) & ~np.isnan(part["level"])
+        out.append(np.where(ok, part["level"], t))
+    return out
+
+
+def pileup_compare(a, b, min_depth=2):
+    """Two piles of the same targets (two samples), point by point: PILE_CMP_DTYPE per point.  With n the rows of a point
+    (the pile's n), sd its level_sd and v = sd**2 * n / (n - 1) the unbiased variance:
+        diff = level_a - level_b
+        t    = diff / sqrt(v_a / n_a + v_b / n_b)                                          (Welch)
+        df   = (v_a / n_a + v_b / n_b)**2 / ((v_a / n_a)**2 / (n_a - 1) + (v_b / n_b)**2 / (n_b - 1))   (Welch-Satterthwaite)
+        d    = diff / sqrt((sd_a**2 + sd_b**2) / 2)
+    t, df and d are NaN where either side has n < min_depth (min_depth >= 2) or both variances are zero.  No p-value: a
+    normal approximation would mislead at low depth.  Host numpy."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("pileup_compare: need two piles of the same points")
+    if int(min_depth) < 2:
+        raise ValueError("pileup_compare: min_depth must be at least 2")
+    out = np.zeros(len(a), dtype=PILE_CMP_DTYPE)
+    out["depth_a"], out["depth_b"] = a["depth"], b["depth"]
+    out["level_a"], out["level_b"] = a["level"], b["level"]
+    na, nb = a["n"].astype(np.float64), b["n"].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["diff"] = a["level"] - b["level"]
+        va = a["level_sd"] ** 2 * na / (na - 1)
+        vb = b["level_sd"] ** 2 * nb / (nb - 1)
+        sa, sb = va / na, vb / nb
+        t = out["diff"] / np.sqrt(sa + sb)
+        df = (sa + sb) ** 2 / (sa ** 2 / (na - 1) + sb ** 2 / (nb - 1))
+        d = out["diff"] / np.sqrt((a["level_sd"] ** 2 + b["level_sd"] ** 2) / 2)
+    bad = (a["n"] < int(min_depth)) | (b["n"] < int(min_depth)) | ((va == 0) & (vb == 0))
+    for name, v in (("t", t), ("df", df), ("d", d)):
+        out[name] = np.where(bad, np.nan, v)
+    return out

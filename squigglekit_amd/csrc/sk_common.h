@@ -239,6 +239,12 @@ struct sk_ctx {
     void  *live_sessions[SK_LIVE_MAX_SESSIONS] = {};   // live mapping sessions of this context (sk_live.hip), by handle
     int64_t live_state_bytes = 0, live_levels = 0, live_launches = 0;   // the last push of one (sk_last_live_plan)
     sk_buf commbuf;                   // staging for the small host-side exchanges
+    sk_buf pile;      // reference pile-up: counters, target offsets, row pairs, offsets, cursors, chunk table (sk_pileup.hip)
+    sk_buf pileent;   // ... the inverted index's rows, 4 bytes per entry
+    sk_buf pilealt;   // ... the long tier's second copy of them (merge passes go back and forth)
+    sk_buf pilein;    // ... the inputs of the host entry point
+    sk_buf pileout;   // ... and its records
+    int64_t pile_entries = 0, pile_longest = 0, pile_long_lists = 0, pile_scratch_bytes = 0;   // the last such call (sk_last_pileup_plan)
 };
 
 // ---- tuning switches (sk_runtime.hip) ----
@@ -742,6 +748,15 @@ struct sk_gate_args {
 int sk_livegate_reset(sk_ctx *c, sk_gate_slot *state, int32_t nslots, const int32_t *d_slots, int32_t m);
 int sk_livegate_lengths(sk_ctx *c, const sk_gate_args &a, int32_t *d_hlen);
 int sk_livegate_release(sk_ctx *c, const sk_gate_args &a);
+
+// ---- reference pile-up (sk_pileup.hip) ----
+// The header's "Reference pile-up": every array on the device but tlen (host).  d_use / d_dwell / d_target / d_shift may
+// be nullptr (all used / ones / zeros / zeros); d_ent_off and d_ent_row both nullptr or both set.  Nothing is written to
+// d_out / d_ent_off / d_ent_row before the checks have passed (one read-back of the counters).
+int sk_pileup_run(sk_ctx *c, const int64_t *d_span_off, const int32_t *d_spans, const double *d_value, const int32_t *d_dwell,
+                  const int32_t *d_target, const int32_t *d_shift, const uint8_t *d_use, int32_t npairs, int64_t nrows,
+                  const int64_t *tlen, int32_t ntargets, sk_pile_rec *d_out, int64_t *d_ent_off, int32_t *d_ent_row,
+                  int64_t ent_cap);
 
 // exclusive int64 scan: out[0 .. n] = prefix sums of v[0 .. n) (out may be v); bsum: sk_scan_blocks(n) entries
 int64_t sk_scan_blocks(int64_t n);

@@ -124,7 +124,8 @@ static const sk_tunable SK_TUNABLES[] = {
     {"SK_PATH_LDS_BYTES",     "0",           "alignment paths: bytes of direction words a hit may keep in LDS (default and most 25600; 0: every hit takes the scratch tier)"},
     {"SK_PATH_SCRATCH_BYTES", "1000000",     "alignment paths: byte budget of the scratch tier's slabs (default 1 GiB; small values leave one wavefront)"},
     {"SK_BAND_WAVES",         "1",           "adaptive-band DTW: wavefronts of the launch (default: one per pair up to what the device holds at a time and the slab budget; 1: one wavefront with one slab works through the list)"},
-    {"SK_INGEST_MB",          "1 4",         "sub-batch size of the host entry points in MB"},
+    {"SK_PILE_LDS_ENTRIES",   "64",          "reference pile-up: entries of a point's list that are put in order inside one wavefront's LDS (default and most 4096, at least 2; longer lists take the merge tier)"},
+    {"SK_INGEST_MB",          "1 4",        "sub-batch size of the host entry points in MB"},
     {"SK_HMM_SCRATCH_MB",     "1",           "signal HMM state paths and posteriors: scratch budget in MB (default 16384; small values force slices of one or two 64-read groups)"},
     {"SK_HMM_POST_BLOCK",     "256",         "signal HMM posteriors: samples between alpha checkpoints, a multiple of 128 (default 128)"},
     {"SK_F64_OLD",            "1",           "float64 reads: numpy-order statistics kernel for every read"},
@@ -236,7 +237,8 @@ int sk_shutdown(void)
         sk_hmms_close_all(c);
         sk_buf *bufs[] = {&c->sig, &c->len, &c->off, &c->comp, &c->prep, &c->mask,
                           &c->motif, &c->out, &c->out2, &c->misc, &c->ckpt, &c->retry, &c->motifq, &c->lastq, &c->qflag,
-                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate, &c->pull, &c->pulltext, &c->sweep, &c->sweeprec, &c->hitrows, &c->bgrec, &c->pathcnt, &c->pathlist, &c->pathscratch, &c->pathmotif, &c->pathspans, &c->events, &c->poolev, &c->pool, &c->panel, &c->panelwin, &c->panelaux, &c->panelrec, &c->seglev, &c->seglevwork, &c->detect, &c->detectout, &c->hmm, &c->hmmpath, &c->hmmseg, &c->hmmpost, &c->hmmpostout, &c->pairs, &c->pairsval, &c->pairpath, &c->rowhit, &c->band, &c->bandslab, &c->evscnt, &c->hmmscnt};
+                          &c->motif64, &c->commbuf, &c->dtwcnt, &c->wsoft, &c->wstate, &c->wrec, &c->motifw, &c->lsum, &c->wrecq, &c->order, &c->pacal, &c->seghints, &c->audit, &c->rlen, &c->redo, &c->sib, &c->sibout, &c->sibstate, &c->pull, &c->pulltext, &c->sweep, &c->sweeprec, &c->hitrows, &c->bgrec, &c->pathcnt, &c->pathlist, &c->pathscratch, &c->pathmotif, &c->pathspans, &c->events, &c->poolev, &c->pool, &c->panel, &c->panelwin, &c->panelaux, &c->panelrec, &c->seglev, &c->seglevwork, &c->detect, &c->detectout, &c->hmm, &c->hmmpath, &c->hmmseg, &c->hmmpost, &c->hmmpostout, &c->pairs, &c->pairsval, &c->pairpath, &c->rowhit, &c->band, &c->bandslab, &c->evscnt, &c->hmmscnt,
+                          &c->pile, &c->pileent, &c->pilealt, &c->pilein, &c->pileout};
         for (sk_buf *b : bufs) free_buf(b);
         for (int i = 0; i < 4; i++) (void)hipEventDestroy(c->ev[i]);
         for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);

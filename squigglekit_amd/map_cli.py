@@ -3,6 +3,7 @@
     squiggle_map.py -s signals.tsv | --blow5 FILE | --i16 FILE.npy  -m reference.model [--both] [--prefix N] [--rna]
                     [--piece N --overlap N] [--align FILE] [--whole FILE [--band 64|128|256]]
                     [--hits K --secondary FILE [--max_dist_per_event X]]
+                    [--pileup FILE [--pileup_of align|whole]]
 
 Per read: event detection on the first --prefix raw samples (api.detect_events), the level of every event
 (api.event_levels), (level - mean) / std in numpy, then subsequence DTW of those levels against every target in one call
@@ -39,7 +40,20 @@ with dist / events <= X.  FILE gets a header line and one line per listed locus 
 in the order of (dist, target, end):
     readID rank target strand start end dist dist_per_event margin
 rank: 1 for the read's best locus; margin: dist minus the dist of the read's best locus.  stdout is the same with and
-without these flags."""
+without these flags.
+
+--pileup FILE [--pileup_of align|whole]: the alignment table turned round.  The rows one of the two tables has -- those of
+--align (the default; the paths are traced whether or not --align is given) or those of --whole (which then must be given)
+-- are kept over the whole run, 20 bytes per event (z, sample_length and the two ends of its span) and 8 per read, and go
+through api.pileup in one call at the end.  FILE gets a header line and one line per point of every target, in the order of
+the targets:
+    target strand pos ref_z depth events shared level level_sd min max dwell_mean dwell_sd
+pos: the point, in the coordinates of the target searched; ref_z: the target's z-scored level there; depth: the reads that
+cover the point; events: the table rows that do (events - depth of them stayed on the point); shared: the rows among them
+that also cover a neighbour (a skip); level / level_sd / min / max: mean, standard deviation (ddof 0), minimum and maximum
+of the rows' z in table order, as numpy computes them; dwell_mean / dwell_sd: the same of their sample_length.  A point
+nobody covers has `.` in the six statistics.  stdout, --align, --whole and --secondary are the same with and without
+--pileup; a FILE that cannot be written fails before the run."""
 import argparse
 import math
 import sys
@@ -52,6 +66,8 @@ from .detect_cli import iter_tsv_reads
 HEADER = ("readID", "target", "strand", "start", "end", "events", "dist", "dist_per_event", "second_target", "second_dist")
 SECONDARY_HEADER = ("readID", "rank", "target", "strand", "start", "end", "dist", "dist_per_event", "margin")
 ALIGN_HEADER = ("readID", "target", "strand", "event", "sample_start", "sample_length", "level", "z", "ref_first", "ref_last")
+PILEUP_HEADER = ("target", "strand", "pos", "ref_z", "depth", "events", "shared", "level", "level_sd", "min", "max",
+                 "dwell_mean", "dwell_sd")
 MAX_EVENTS = 1024
 
 
@@ -80,6 +96,11 @@ def build_parser():
     p.add_argument("--hits", type=int, default=0, help="list up to this many non-overlapping loci per read and target (1..64; needs --secondary)")
     p.add_argument("--secondary", help="write every listed locus of every read to this file (needs --hits)")
     p.add_argument("--max_dist_per_event", type=float, default=None, help="list only loci with dist / events at most this (needs --hits)")
+    p.add_argument("--pileup", help="write per-point statistics of the aligned events (one line per point of every target) to this file; "
+                                    "keeps 20 bytes per aligned event until the end of the run")
+    p.add_argument("--pileup_of", choices=("align", "whole"), default="align",
+                   help="the table --pileup turns round: the prefix alignment of --align (default; traced also without --align) "
+                        "or the whole-read alignment of --whole")
     p.add_argument("--device", type=int, default=None, help="GPU index (default $SK_DEVICE or 0)")
     p.add_argument("--batch", type=int, default=4096, help="reads per GPU call")
     return p
@@ -171,10 +192,48 @@ def whole_span(length, start, end, n_prefix, n_all, band):
     return min(length - start, int(math.ceil(n_all * (end - start + 1) / n_prefix * 1.5)) + band)
 
 
+class _Pile:
+    """the rows --pileup keeps over the run: per matched read its z, sample lengths and spans, its target and shift"""
+
+    def __init__(self):
+        self.z, self.length, self.spans, self.target, self.shift = [], [], [], [], []
+
+    def add(self, z, events, spans, target, shift):
+        self.z.append(np.asarray(z, dtype=np.float64))
+        self.length.append(np.asarray(events["length"], dtype=np.int32))
+        self.spans.append(np.asarray(spans, dtype=np.int32).reshape(-1, 2))
+        self.target.append(int(target))
+        self.shift.append(int(shift))
+
+    def table(self, targets):
+        """the text of FILE: one api.pileup call over everything kept"""
+        span_off = np.concatenate([[0], np.cumsum([len(z) for z in self.z])]).astype(np.int64)
+        cat = lambda parts, empty: np.concatenate(parts) if parts else empty                     # noqa: E731
+        pile = api.pileup(span_off, cat(self.spans, np.zeros((0, 2), dtype=np.int32)), cat(self.z, np.zeros(0)),
+                          dwell=cat(self.length, np.zeros(0, dtype=np.int32)), target=np.array(self.target, dtype=np.int32),
+                          shift=np.array(self.shift, dtype=np.int32), tlen=[len(t[2]) for t in targets])
+        return pileup_text(targets, pile)
+
+
+def pileup_text(targets, pile):
+    """the --pileup table: targets as load_targets returns them, pile the PILE_DTYPE records of all their points"""
+    out = ["\t".join(PILEUP_HEADER) + "\n"]
+    for (name, strand, y), part in zip(targets, api.pile_split(pile, [len(t[2]) for t in targets])):
+        for j in range(len(y)):
+            r = part[j]
+            stats = ["."] * 6 if r["n"] == 0 else ["{}".format(float(r[k])) for k in
+                                                   ("level", "level_sd", "vmin", "vmax", "dwell_mean", "dwell_sd")]
+            out.append("\t".join([name, strand, str(j), "{}".format(float(y[j])), str(int(r["depth"])), str(int(r["n"])),
+                                  str(int(r["shared"]))] + stats) + "\n")
+    return "".join(out)
+
+
 class _Batcher:
-    def __init__(self, args, targets, tool_input, align=None, whole=None, secondary=None):
+    def __init__(self, args, targets, tool_input, align=None, whole=None, secondary=None, pile=None):
         self.args, self.targets, self.input, self.align, self.whole = args, targets, tool_input, align, whole
         self.secondary = secondary
+        self.pile = pile                                            # the rows --pileup keeps (a _Pile), or None
+        self.pile_align = pile is not None and args.pileup_of == "align"
         self.params = api.det_params("rna" if args.rna else "dna")
         self.ids, self.reads, self.full = [], [], []
 
@@ -224,14 +283,18 @@ class _Batcher:
                 hits, count = api.map_queries_hits(qs, ys, self.args.hits)
             self.secondary.write("".join(secondary_lines(self.ids, queries, hits, count, self.targets,
                                                          self.args.max_dist_per_event)))
-        if self.align is not None and qs:
+        if (self.align is not None or self.pile_align) and qs:
             best = api.best_targets(records)
             span_off, spans = api.map_paths(qs, ys, records, best)
             rows = [i for i, z in enumerate(queries) if z is not None]
             for q, i in enumerate(rows):
                 if best[q] >= 0:
-                    self.align.write("".join(align_lines(self.ids[i], self.targets[int(best[q])], evs[i], lev[i], queries[i],
-                                                         spans[int(span_off[q]):int(span_off[q + 1])])))
+                    sp = spans[int(span_off[q]):int(span_off[q + 1])]
+                    if self.align is not None:
+                        self.align.write("".join(align_lines(self.ids[i], self.targets[int(best[q])], evs[i], lev[i],
+                                                             queries[i], sp)))
+                    if self.pile_align and len(sp) and sp[0, 0] >= 0:
+                        self.pile.add(queries[i], evs[i], sp, best[q], 0)
         if self.whole is not None and qs:
             self.write_whole(queries, records)
         self.ids, self.reads, self.full = [], [], []
@@ -268,6 +331,8 @@ class _Batcher:
                 sys.stderr.write("squiggle_map: whole read: the band lost the path in read {} of {}\n".format(self.ids[i], self.input))
                 continue
             self.whole.write("".join(align_lines(self.ids[i], self.targets[t], ev, lev, z, sp + start)))
+            if self.pile is not None and not self.pile_align:
+                self.pile.add(z, ev, sp, t, start)                  # the spans as traced: inside target[start:]
 
 
 def main(argv=None):
@@ -297,6 +362,10 @@ def main(argv=None):
         parser.error("--hits must be in 1 .. 64")
     if args.max_dist_per_event is not None and (not args.hits or args.max_dist_per_event != args.max_dist_per_event):
         parser.error("--max_dist_per_event needs --hits and a number")
+    if args.pileup_of == "whole" and not args.pileup:
+        parser.error("--pileup_of needs --pileup")
+    if args.pileup and args.pileup_of == "whole" and not args.whole:
+        parser.error("--pileup_of whole needs --whole")
     try:
         targets = load_targets(args.model, args.both)
     except (ValueError, IndexError, OSError) as e:
@@ -330,7 +399,14 @@ def main(argv=None):
             sys.stderr.write("squiggle_map: {}: {}\n".format(args.secondary, e))
             sys.exit(2)
         secondary.write("\t".join(SECONDARY_HEADER) + "\n")
-    out = _Batcher(args, targets, src, align, whole, secondary)
+    pileup = None
+    if args.pileup:
+        try:
+            pileup = open(args.pileup, "w")
+        except OSError as e:
+            sys.stderr.write("squiggle_map: {}: {}\n".format(args.pileup, e))
+            sys.exit(2)
+    out = _Batcher(args, targets, src, align, whole, secondary, _Pile() if pileup is not None else None)
     sys.stdout.write("\t".join(HEADER) + "\n")
     try:
         if args.signal:
@@ -348,15 +424,17 @@ def main(argv=None):
                 for i, row in enumerate(np.asarray(a[lo:lo + max(1, args.batch)])):
                     out.add(str(lo + i), row)
         out.flush()
+        if pileup is not None:
+            pileup.write(out.pile.table(targets))
     except (ValueError, EOFError, OSError) as e:
         sys.stdout.flush()
         sys.stderr.write("squiggle_map: {}: {}\n".format(src, e))
-        for fh in (align, whole, secondary):
+        for fh in (align, whole, secondary, pileup):
             if fh is not None:
                 fh.close()
         sys.exit(2)
     sys.stdout.flush()
-    for fh in (align, whole, secondary):
+    for fh in (align, whole, secondary, pileup):
         if fh is not None:
             fh.close()
 
